@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- timesteps/s labelled+tracked on synthetic ERA5-like Z500 anomaly slabs (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload era5_1deg_djf30|era5_025deg|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload era5_1deg_djf30|era5_025deg|...] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (threshold -> 2-D labelling with longitude wrap -> overlap filter ->
 3-D tracking -> persistence -> flag) over one batch: the whole (T, ny, nx) slab of the workload, already
@@ -87,6 +87,38 @@ def device_fill(trk, d_in, wl):
     per = (T + m - 1) // m
     for q, tb in enumerate(range(0, T, per)):
         trk.synth_fill(C.c_void_p(d_in.value + tb * ny * nx * 4), min(per, T - tb), ny, nx, seed=100 + q)
+
+
+DUMP_SAMPLE_BYTES = 40 << 20      # float64 flag timesteps in flag_sample.npy (with flag_per_step.npy: below 64 MB for every workload)
+
+
+def dump_outputs(trk, d_out, wl, n_tracked, out_dir, chunk_px=1 << 26):
+    """what the timed pass handed its caller -- the (T, ny, nx) int32 flag slab in d_out and n_tracked -- as float64 .npy files:
+    n_tracked.npy (1,); flag_per_step.npy (T, 2): nonzero pixels and sum of the ids of every timestep (the whole slab);
+    flag_sample.npy (k, ny, nx): the timesteps flag_sample_t.npy (k,) of a fixed seeded draw, as many as DUMP_SAMPLE_BYTES hold.
+    The slab comes down in chunks of whole timesteps, so slabs beyond host memory work too."""
+    import ctypes as C
+    T, ny, nx = wl["T"], wl["ny"], wl["nx"]
+    k = min(T, max(1, DUMP_SAMPLE_BYTES // (ny * nx * 8)))
+    pick = np.sort(np.random.default_rng(20240607).choice(T, size=k, replace=False))
+    per_step = np.zeros((T, 2), dtype=np.float64)
+    sample = np.zeros((k, ny, nx), dtype=np.float64)
+    nt = max(1, min(T, chunk_px // (ny * nx)))
+    buf = np.empty((nt, ny, nx), dtype=np.int32)
+    for tb in range(0, T, nt):
+        n = min(nt, T - tb)
+        chunk = buf[:n]
+        trk.d2h(chunk, C.c_void_p(d_out.value + tb * ny * nx * 4))
+        per_step[tb:tb + n, 0] = np.count_nonzero(chunk, axis=(1, 2))
+        per_step[tb:tb + n, 1] = chunk.sum(axis=(1, 2), dtype=np.int64)
+        sel = np.nonzero((pick >= tb) & (pick < tb + n))[0]
+        sample[sel] = chunk[pick[sel] - tb]
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = dict(n_tracked=np.array([n_tracked], dtype=np.float64), flag_per_step=per_step, flag_sample=sample,
+                  flag_sample_t=pick.astype(np.float64))
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return dict(dir=os.path.abspath(out_dir), files=sorted(n + ".npy" for n in arrays), bytes=int(sum(v.nbytes for v in arrays.values())))
 
 
 def pmc_traffic_source(kernel, workload):
@@ -419,6 +451,9 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="N > 1: weak = one member of the workload per GPU, concatenated on the time axis (default); "
                          "strong = the single-GPU slab split over the GPUs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (flag slab summary and a seeded sample of its "
+                         "timesteps, n_tracked) as float64 DIR/<name>.npy, 64 MB at most; e.g. bench_outputs/ (N = 1 only)")
     ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic from the committed capture under profiles/ instead of two rocprofv3 --pmc child runs")
     ap.add_argument("--no-parity-check", action="store_true",
@@ -433,6 +468,10 @@ def main():
         return pmc_child(args)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs: single-GPU runs only (--gpus 1)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))                     # no launcher: the ranks are started here
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -485,6 +524,8 @@ def main():
     per, nmeas = trk.timing_sums(reset=True)
     last = trk.timings()                              # (host-side timers of the last pass: informational)
     per.update({k: last[k] for k in ("host_seam_driver", "total", "d2h", "h2d")})
+    # d_out still holds the last timed step's flags here: everything below (extra passes, stream ceiling) writes over it
+    dumped = dump_outputs(trk, d_out, wl, n_tracked, args.dump_outputs) if args.dump_outputs else None
     # per-group kernel times of the small kernels: a few extra, untimed passes with events around every group (each
     # event record is a command of its own and would stretch the timed passes)
     trk.set_timing(2)
@@ -535,7 +576,7 @@ def main():
                              avg_kernel_ms=per.get(kern),
                              other_streaming_kernel={k: dict(achieved=alg_bytes[k] / (per[k] * 1e-3) / 1e9, avg_kernel_ms=per[k])
                                                      for k in alg_bytes if k != kern and per.get(k, 0) > 0}),
-               kernels_ms=per, workload_stats=trk.stats(), pmc_live=live_pmc,
+               kernels_ms=per, workload_stats=trk.stats(), pmc_live=live_pmc, dumped_outputs=dumped,
                # what a PLAIN 16-byte non-temporal stream reaches on this board, measured here on the same two buffers (best of 5): the write
                # kernel cannot beat the store stream, the threshold kernel not the load stream -- `frac` above stays against the 8 TB/s peak
                stream_ceiling=stream_ceiling(trk, d_in, d_out, nbytes, per),

@@ -431,7 +431,7 @@ class _ResultPool:
                 i += 1
         if blk is None:
             self.misses += 1
-            blk = dict(mem=np.empty(nbytes, dtype=np.uint8), registered=False)
+            blk = dict(mem=self._pages(nbytes), registered=False)
         else:
             self.hits += 1
             trk = self._trk()
@@ -444,6 +444,15 @@ class _ResultPool:
             self._leased[id(blk)] = blk
         weakref.finalize(carr, self._release, blk)
         return np.frombuffer(carr, dtype=dtype).reshape(shape)
+
+    @staticmethod
+    def _pages(nbytes):
+        """a block of pages of its own (anonymous mapping, page-aligned, whole pages).  hipHostRegister pins whole pages: a block
+        from malloc can share its first and last page with a neighbouring array (the input slab, say), and registering the block
+        then registers part of that array too -- its next copy to the device faulted on the GPU"""
+        import mmap
+        size = (nbytes + mmap.PAGESIZE - 1) // mmap.PAGESIZE * mmap.PAGESIZE
+        return np.frombuffer(mmap.mmap(-1, size, flags=mmap.MAP_PRIVATE), dtype=np.uint8)
 
     def _unregister(self, blk):
         trk = self._trk()

@@ -55,3 +55,21 @@ def test_release_inside_a_gc_pass_while_the_lock_is_held():
     again = pool.take(shape)
     assert pool.hits == 1 and len(pool._returned) == 0
     del again
+
+
+def test_blocks_own_whole_pages():
+    """a block the pool may register with HIP shares no page with any other array: registration pins whole pages"""
+    import mmap
+    pool = _native._ResultPool(_Trk())
+    big = np.ones(40 << 20, np.uint8)                         # a large free raises malloc's mmap threshold: later arrays come from the heap
+    del big
+    before = np.empty(10 << 20, np.uint8)
+    a = pool.take((3, 1000, 1000))
+    after = np.empty(10 << 20, np.uint8)
+    blk = next(iter(pool._leased.values()))["mem"]
+    lo, hi = blk.ctypes.data, blk.ctypes.data + blk.nbytes
+    assert lo % mmap.PAGESIZE == 0 and hi % mmap.PAGESIZE == 0 and lo <= a.ctypes.data and a.ctypes.data + a.nbytes <= hi
+    for x in (before, after):
+        assert x.ctypes.data + x.nbytes <= lo or x.ctypes.data >= hi
+    del a
+    pool.close()
