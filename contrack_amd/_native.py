@@ -34,6 +34,7 @@ EXPORTS = [
     "ctk_anom_f32", "ctk_anom_f64", "ctk_resident_anom", "ctk_resident_anom_generation", "ctk_track_resident", "ctk_percentile_f32", "ctk_percentile_f64",
     "ctk_lifecycle_f32", "ctk_lifecycle_f64", "ctk_lifecycle_f32_dev", "ctk_lifecycle_f64_dev", "ctk_lifecycle_rows", "ctk_lifecycle_exact",
     "ctk_track_stream_f32", "ctk_track_stream_f64", "ctk_track_stream_cb", "ctk_stream_times",
+    "ctk_set_threshold_field",
 ]
 
 READ_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)       # ctk_read_chunk_fn
@@ -77,6 +78,7 @@ def lib():
     L.ctk_track_f64.argtypes = track_args
     L.ctk_track_f64_dev.argtypes = track_args
     L.ctk_release_io.argtypes = [p]
+    L.ctk_set_threshold_field.argtypes = [p, p, i32, i64, i32, i32, p, i64]
     L.ctk_track_stream_f32.argtypes = track_args + [i64]
     L.ctk_track_stream_f64.argtypes = track_args + [i64]
     L.ctk_track_stream_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, p, i32, p, dbl, i32, i32, WRITE_CHUNK_FN, p, C.POINTER(i64), i64]
@@ -176,6 +178,20 @@ def lib():
     L.ctk_track_sharded_f64_dev.argtypes = sharded_args
     _lib = L
     return L
+
+
+def _thr_or_field(thr, T):
+    """per-step thresholds as float64 (T,), or None: the handle's threshold field (Tracker.set_threshold_field)"""
+    if thr is None:
+        return None
+    thr = np.ascontiguousarray(thr, dtype=np.float64)
+    if thr.shape != (T,):
+        raise ValueError("thr must have shape (T,) and wrow (ny,)")
+    return thr
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
 
 
 def check(rc):
@@ -530,9 +546,9 @@ class Tracker:
     def track(self, anom, thr, cmp_op, wrow, overlap, persistence, twosided=True, f64=False, out=None):
         anom = np.ascontiguousarray(anom, dtype=np.float64 if f64 else np.float32)
         T, ny, nx = anom.shape
-        thr = np.ascontiguousarray(thr, dtype=np.float64)
+        thr = _thr_or_field(thr, T)
         wrow = np.ascontiguousarray(wrow, dtype=np.float32)
-        if thr.shape != (T,) or wrow.shape != (ny,):
+        if wrow.shape != (ny,):
             raise ValueError("thr must have shape (T,) and wrow (ny,)")
         if out is not None:
             if out.dtype != np.int32 or out.shape != (T, ny, nx) or not out.flags.c_contiguous or not out.flags.writeable:
@@ -542,7 +558,7 @@ class Tracker:
             flag = self._pool.take((T, ny, nx))
         n = C.c_int64(0)
         fn = lib().ctk_track_f64 if f64 else lib().ctk_track_f32
-        check(fn(self._h, anom.ctypes.data, T, ny, nx, thr.ctypes.data, int(cmp_op), wrow.ctypes.data,
+        check(fn(self._h, anom.ctypes.data, T, ny, nx, _ptr(thr), int(cmp_op), wrow.ctypes.data,
                                   float(overlap), int(persistence), int(bool(twosided)), flag.ctypes.data, C.byref(n)))
         return flag, int(n.value)
 
@@ -570,9 +586,9 @@ class Tracker:
             dt = source.dtype
         if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise ValueError("the slab must be float32 or float64")
-        thr = np.ascontiguousarray(thr, dtype=np.float64)
+        thr = _thr_or_field(thr, T)
         wrow = np.ascontiguousarray(wrow, dtype=np.float32)
-        if thr.shape != (T,) or wrow.shape != (ny,):
+        if wrow.shape != (ny,):
             raise ValueError("thr must have shape (T,) and wrow (ny,)")
         out = None
         if sink is None:
@@ -582,7 +598,7 @@ class Tracker:
                 raise ValueError("the sink array must be C-contiguous int32 (T, ny, nx)")
             out = sink
         n = C.c_int64(0)
-        tail = (thr.ctypes.data, int(cmp_op), wrow.ctypes.data, float(overlap), int(persistence), int(bool(twosided)))
+        tail = (_ptr(thr), int(cmp_op), wrow.ctypes.data, float(overlap), int(persistence), int(bool(twosided)))
         if not callable(source) and not callable(sink):
             fn = L.ctk_track_stream_f64 if dt == np.float64 else L.ctk_track_stream_f32
             check(fn(self._h, source.ctypes.data, T, ny, nx, *tail, sink.ctypes.data, C.byref(n), int(chunk_steps)))
@@ -663,11 +679,11 @@ class Tracker:
         if shape is None:
             raise ContrackHipError("no anomaly slab is resident on the device")
         T, ny, nx, _ = shape
-        thr = np.ascontiguousarray(thr, dtype=np.float64)
+        thr = _thr_or_field(thr, T)
         wrow = np.ascontiguousarray(wrow, dtype=np.float32)
         flag = self._pool.take((T, ny, nx))
         n = C.c_int64(0)
-        check(lib().ctk_track_resident(self._h, thr.ctypes.data, int(cmp_op), wrow.ctypes.data, float(overlap), int(persistence),
+        check(lib().ctk_track_resident(self._h, _ptr(thr), int(cmp_op), wrow.ctypes.data, float(overlap), int(persistence),
                                        int(bool(twosided)), flag.ctypes.data, C.byref(n)))
         return flag, int(n.value)
 
@@ -694,6 +710,30 @@ class Tracker:
     def release_io(self):
         """free the device copies of slab / result that the host-array calls keep in the handle"""
         check(lib().ctk_release_io(self._h))
+
+    # ---- threshold field (ctk_set_threshold_field) ----------------------------------------------------------------
+    def set_threshold_field(self, field, plane_of_step):
+        """threshold per grid point for the following calls with thr=None: field (nplanes, ny, nx), step t compared with
+        field[plane_of_step[t]].  float32 stays float32; float16 and integers of up to 16 bits are exact in float32 and become it
+        (numpy compares a float32 slab with them in float32); every other dtype becomes float64 (numpy compares in float64)."""
+        field = np.asarray(field)
+        if field.ndim != 3:
+            raise ValueError("the threshold field must be (nplanes, ny, nx)")
+        if field.dtype.kind not in "fiub":
+            raise TypeError("the threshold field must be numeric")
+        small = field.dtype == np.float16 or (field.dtype.kind in "iub" and field.dtype.itemsize <= 2)
+        field = np.ascontiguousarray(field, dtype=np.float32 if (field.dtype == np.float32 or small) else np.float64)
+        pos = np.asarray(plane_of_step)
+        if pos.ndim != 1 or pos.dtype.kind not in "iu":
+            raise ValueError("plane_of_step must be a 1-D integer array")
+        if pos.size and (pos.min() < 0 or pos.max() >= field.shape[0]):
+            raise ValueError("plane_of_step must index the field's planes")
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        check(lib().ctk_set_threshold_field(self._h, field.ctypes.data, field.itemsize, field.shape[0], field.shape[1], field.shape[2],
+                                            pos.ctypes.data, pos.shape[0]))
+
+    def clear_threshold_field(self):
+        check(lib().ctk_set_threshold_field(self._h, None, 4, 0, 0, 0, None, 0))
 
     # ---- device-resident --------------------------------------------------------------------------
     def malloc(self, nbytes):
@@ -747,15 +787,20 @@ class Tracker:
         c = getattr(self, "_pc", None)
         if c is not None and c[0] is thr and c[1] is wrow:
             return c[2], c[3], thr, wrow
-        t = np.ascontiguousarray(thr, dtype=np.float64)
+        t = None if thr is None else np.ascontiguousarray(thr, dtype=np.float64)       # None: the handle's threshold field
         w = np.ascontiguousarray(wrow, dtype=np.float32)
-        tp, wp = t.ctypes.data, w.ctypes.data
-        self._pc = (thr, wrow, tp, wp) if (t is thr and w is wrow) else None      # (never the address of a converted copy)
+        tp, wp = _ptr(t), w.ctypes.data
+        self._pc = (thr, wrow, tp, wp) if (t is thr and w is wrow and t is not None) else None      # (never the address of a converted copy)
         return tp, wp, t, w
 
-    def track_dev(self, anom_dev, T, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, flag_dev):
+    def track_dev(self, anom_dev, T, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, flag_dev, f64=False):
+        """thr=None: the threshold field set with set_threshold_field; f64: anom_dev holds float64"""
         tp, wp, thr, wrow = self._thr_w_ptrs(thr, wrow)
         n = C.c_int64(0)
+        if f64:
+            check(lib().ctk_track_f64_dev(self._h, anom_dev, T, ny, nx, tp, int(cmp_op), wp,
+                                          float(overlap), int(persistence), int(bool(twosided)), flag_dev, C.byref(n)))
+            return int(n.value)
         check(lib().ctk_track_f32_dev(self._h, anom_dev, T, ny, nx, tp, int(cmp_op), wp,
                                       float(overlap), int(persistence), int(bool(twosided)), flag_dev, C.byref(n)))
         return int(n.value)
@@ -764,7 +809,7 @@ class Tracker:
                           f64=False):
         """the whole path on the time shard [t_begin, t_begin + T_local) of T_total steps; every rank of `comm` must call"""
         tp, wp, thr, wrow = self._thr_w_ptrs(thr, wrow)
-        if thr.shape != (T_local,):
+        if thr is not None and thr.shape != (T_local,):
             raise ValueError("thr must hold one value per local timestep")
         n = C.c_int64(0)
         fn = lib().ctk_track_sharded_f64_dev if f64 else lib().ctk_track_sharded_f32_dev
@@ -893,9 +938,9 @@ class Tracker:
 
     # ---- staged (time-sharded) -------------------------------------------------------------------
     def shard_label2d(self, anom_dev, T, ny, nx, thr, cmp_op, wrow, has_prev):
-        thr = np.ascontiguousarray(thr, dtype=np.float64)
+        thr = None if thr is None else np.ascontiguousarray(thr, dtype=np.float64)
         wrow = np.ascontiguousarray(wrow, dtype=np.float32)
-        check(lib().ctk_shard_label2d(self._h, anom_dev, T, ny, nx, thr.ctypes.data, int(cmp_op), wrow.ctypes.data, int(bool(has_prev))))
+        check(lib().ctk_shard_label2d(self._h, anom_dev, T, ny, nx, _ptr(thr), int(cmp_op), wrow.ctypes.data, int(bool(has_prev))))
 
     def halo_size(self):
         s = C.c_size_t(0)

@@ -72,23 +72,70 @@ def prepare_thresholds(threshold, T, data_dtype):
     return np.ascontiguousarray(out, dtype=np.float64)
 
 
+def is_threshold_field(threshold):
+    """a numpy threshold with ndim >= 2 whose last two axes are not (1, 1) varies by grid point; scalars, (T,) and (T, 1, 1) do not"""
+    if hasattr(threshold, "dims") or isinstance(threshold, (bool, int, float)):
+        return False
+    arr = np.asarray(threshold)
+    return arr.ndim >= 2 and arr.shape[-2:] != (1, 1)
+
+
+def field_planes(tll):
+    """a (T, ny, nx) threshold (broadcast views allowed) -> (planes (nplanes, ny, nx), plane_of_step (T,)): ONE plane when the
+    array does not vary along time (a (ny, nx) field broadcast over the steps), else one plane per step"""
+    T = tll.shape[0]
+    if T <= 1 or tll.strides[0] == 0:
+        return np.ascontiguousarray(tll[:1]), np.zeros(T, dtype=np.int32)
+    return np.ascontiguousarray(tll), np.arange(T, dtype=np.int32)
+
+
+def broadcast_field(threshold, shape, sort=(0, 1, 2)):
+    """numpy's broadcasting of `threshold` against a variable of `shape` (the variable's own dim order), then the (time, lat, lon)
+    transpose `sort` -> (planes, plane_of_step) as field_planes"""
+    arr = np.asarray(threshold)
+    if arr.dtype.kind not in "fiub":
+        raise TypeError("threshold must be numeric")
+    try:
+        full = np.broadcast_shapes(arr.shape, tuple(shape))
+    except ValueError:
+        full = None
+    if full != tuple(shape):
+        raise ValueError("a threshold of shape {} does not broadcast against the variable's shape {}".format(arr.shape, tuple(shape)))
+    return field_planes(np.broadcast_to(arr, tuple(shape)).transpose(sort))
+
+
+def _track_field(trk, planes, pos, call):
+    """one call with the handle's threshold field set to (planes, pos); the field is cleared again afterwards (it can be GBs)"""
+    trk.set_threshold_field(planes, pos)
+    try:
+        return call(None)
+    finally:
+        trk.clear_threshold_field()
+
+
 def track_numpy(anom, wrow, threshold, gorl, overlap, persistence, twosided=True, device=None):
     """run_contrack on a (time, lat, lon) numpy slab.  Returns (flag int32 (T,ny,nx), n_tracked).
 
     anom float32 (other dtypes are compared exactly in float64 on the device), wrow float32 (ny,) from
-    `row_weights`, threshold scalar or per-timestep vector, gorl in {'>=','<=','>','<','ge','le','gt','lt'}."""
+    `row_weights`, threshold scalar, per-timestep vector or a threshold field: a numpy array of ndim >= 2 (last two axes not (1, 1))
+    that broadcasts against anom, e.g. (ny, nx) or (T, ny, nx) -- pixel (t, y, x) is compared with its own value, under numpy's
+    promotion rules; gorl in {'>=','<=','>','<','ge','le','gt','lt'}."""
     if gorl not in _native.CMP_OPS:
         raise ValueError(_native.GORL_ERRMSG)
     anom = np.asarray(anom)
     if anom.ndim != 3:
         raise ValueError("anom must be (time, lat, lon)")
-    thr = prepare_thresholds(threshold, anom.shape[0], anom.dtype)
+    field = broadcast_field(threshold, anom.shape) if is_threshold_field(threshold) else None
+    thr = None if field is not None else prepare_thresholds(threshold, anom.shape[0], anom.dtype)
     trk = _tracker(device)
     if anom.dtype != np.float32:
         if anom.dtype.kind not in "fiub":
             raise TypeError("anom must be a real numeric array")
-        return trk.track(anom.astype(np.float64), thr, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, f64=True)
-    return trk.track(anom, thr, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided)
+        a64 = anom.astype(np.float64)
+        call = lambda t: trk.track(a64, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, f64=True)
+    else:
+        call = lambda t: trk.track(anom, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided)
+    return call(thr) if field is None else _track_field(trk, field[0], field[1], call)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -516,6 +563,61 @@ class contrack(object):
             v = np.asarray(t.data).astype('datetime64[D]')
             return (v - v.astype('datetime64[Y]')).astype(int) + 1
 
+    def _coord(self, da, name):
+        try:
+            c = da[name]
+        except (KeyError, IndexError, TypeError):
+            return None
+        return np.asarray(getattr(c, "data", c))
+
+    def _doy_field(self, threshold):
+        """a DataArray over 'dayofyear' and the spatial dims (any order; a missing spatial dim broadcasts) -> (planes, plane_of_step):
+        transposed by name, the spatial labels aligned with the dataset's (a reversed latitude is reordered), the plane of every
+        step from its day of year (contrack.py:648-661 with a threshold that varies by grid point)"""
+        lat_n, lon_n = self._latitude_name, self._longitude_name
+        dims = tuple(threshold.dims)
+        extra = [d for d in dims if d not in ('dayofyear', lat_n, lon_n)]
+        if extra:
+            raise ValueError("the threshold's dims {} must be 'dayofyear', {!r} and {!r}".format(dims, lat_n, lon_n))
+        arr = np.asarray(threshold.data)
+        for d in (lat_n, lon_n):
+            if d not in dims:
+                arr, dims = arr[..., None], dims + (d,)
+        arr = arr.transpose([dims.index(d) for d in ('dayofyear', lat_n, lon_n)])
+        for ax, d in ((1, lat_n), (2, lon_n)):
+            want = np.asarray(self.ds[d].data)
+            if arr.shape[ax] == 1 and d not in threshold.dims:
+                arr = np.repeat(arr, len(want), axis=ax)
+                continue
+            have = self._coord(threshold, d)
+            if have is None:
+                if arr.shape[ax] != len(want):
+                    raise ValueError("the threshold has {} {} values, the dataset {}".format(arr.shape[ax], d, len(want)))
+                continue
+            if have.shape == want.shape and np.array_equal(have, want):
+                continue
+            pos = {v: i for i, v in enumerate(have.tolist())}
+            if len(pos) != len(have) or len(have) != len(want) or any(v not in pos for v in want.tolist()):
+                raise ValueError("the threshold's {} labels are not the dataset's".format(d))
+            arr = np.take(arr, [pos[v] for v in want.tolist()], axis=ax)
+        coord = self._coord(threshold, 'dayofyear')
+        if coord is None:
+            coord = np.arange(1, arr.shape[0] + 1)
+        pos = {int(d): i for i, d in enumerate(coord)}
+        plane_of_step = np.array([pos[int(d)] for d in self._dayofyear()], dtype=np.int32)      # KeyError: a day the threshold lacks
+        return np.ascontiguousarray(arr), plane_of_step
+
+    def _threshold_args(self, threshold, shape, sort, T, dtype):
+        """(per-step thresholds, None) or (None, (planes, plane_of_step)) for a threshold field"""
+        if hasattr(threshold, "dims") and hasattr(threshold, "data") and np.ndim(threshold.data) >= 2:
+            if 'dayofyear' not in threshold.dims:
+                # (xarray's grouped compare refuses it as well)
+                raise ValueError("a threshold with dims {} has no 'dayofyear' dimension".format(tuple(threshold.dims)))
+            return None, self._doy_field(threshold)
+        if is_threshold_field(threshold):
+            return None, broadcast_field(threshold, shape, sort)
+        return self._thresholds_per_step(threshold, T, dtype), None
+
     def _thresholds_per_step(self, threshold, T, dtype):
         """scalar, or a 1-D DataArray over 'dayofyear' (contrack.py:648-661) -> per-timestep values"""
         if hasattr(threshold, "dims") and hasattr(threshold, "data"):
@@ -537,7 +639,9 @@ class contrack(object):
     def run_contrack(self, variable, threshold, gorl, overlap, persistence, twosided=True, chunk_steps=None):
         """Spatial and temporal tracking of closed contours; adds the integer variable 'flag' to the dataset.
 
-        variable: name of the input field; threshold: number or 1-D DataArray over 'dayofyear'; gorl: one of
+        variable: name of the input field; threshold: number, 1-D DataArray over 'dayofyear', a threshold field -- a DataArray over
+        'dayofyear' and the spatial dims (any order, labels aligned by name) or a numpy array that broadcasts against the variable
+        in its own dim order (e.g. (lat, lon) or (time, lat, lon)); gorl: one of
         [>, >=, <, <=, ge, le, gt, lt]; overlap: fraction [0-1] of area overlap between consecutive steps;
         persistence: minimum life time in time steps; twosided: forward+backward overlap test (True) or forward
         only.
@@ -567,15 +671,16 @@ class contrack(object):
             slab = None
         else:
             slab = np.asarray(da.data).transpose(sort)
-            thr = self._thresholds_per_step(threshold, slab.shape[0], slab.dtype)
+            thr, field = self._threshold_args(threshold, da.shape, sort, slab.shape[0], slab.dtype)
             if self._resident_for(variable, da.data, slab.shape, slab.dtype != np.float32):
                 # calc_anom left this very slab in HBM: no host-to-device copy
-                flag, n_tracked = trk.track_resident(thr, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided)
+                call = lambda t: trk.track_resident(t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided)
             elif slab.dtype == np.float32:
-                flag, n_tracked = trk.track(np.ascontiguousarray(slab), thr, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided)
+                call = lambda t: trk.track(np.ascontiguousarray(slab), t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided)
             else:
-                flag, n_tracked = trk.track(np.ascontiguousarray(slab, dtype=np.float64), thr, _native.CMP_OPS[gorl], wrow, overlap,
-                                            persistence, twosided, f64=True)
+                call = lambda t: trk.track(np.ascontiguousarray(slab, dtype=np.float64), t, _native.CMP_OPS[gorl], wrow, overlap,
+                                           persistence, twosided, f64=True)
+            flag, n_tracked = call(thr) if field is None else _track_field(trk, field[0], field[1], call)
         if slab is not None and slab.nbytes > (4 << 30):
             trk.release_io()               # a big one-off slab: do not keep 2 x its size allocated on the GPU
         logger.info("Create new variable 'flag'...")
@@ -604,15 +709,16 @@ class contrack(object):
         """run_contrack with the variable read slice by slice"""
         shape = tuple(da.shape[i] for i in sort)                                  # (time, lat, lon)
         dtype = np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
-        thr = self._thresholds_per_step(threshold, shape[0], dtype)
+        thr, field = self._threshold_args(threshold, da.shape, sort, shape[0], dtype)
         tname = self._time_name
 
         def reader(t0, nt, out):
             part = da.isel(**{tname: slice(t0, t0 + nt)}) if hasattr(da, "isel") else None
             arr = np.asarray(part.data if part is not None else np.asarray(da.data).take(range(t0, t0 + nt), axis=dims.index(tname)))
             out[...] = arr.transpose(sort)
-        return trk.track_stream(reader, thr, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, shape=shape, dtype=dtype,
-                                chunk_steps=chunk_steps)
+        call = lambda t: trk.track_stream(reader, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, shape=shape, dtype=dtype,
+                                          chunk_steps=chunk_steps)
+        return call(thr) if field is None else _track_field(trk, field[0], field[1], call)
 
     # ---- life cycle (contrack.py:798-906), consumer of `flag` (SURVEY.md section 8(f) N1) ----------------------------
     def _time_labels(self):

@@ -323,6 +323,13 @@ struct ctk_handle {
     // what the device copies of thresholds / weight limbs were made from
     std::vector<double> c_thr; std::vector<float> c_w;
     int64_t c_T = -1; bool c_f64 = false, c_thr_valid = false, c_w_valid = false; int c_cmp = -1, c_w_nx = -1;
+    // threshold field (ctk_set_threshold_field): the caller's field as given (f32 / f64 [np][ny][nx]), plane of every step, the float32
+    // field the float32 compare reads (the caller's own when it is float32, else prepared for fld_prep_op), the plane-major step order
+    DevBuf fld_raw, fld_f32, fld_pos, fld_order;
+    int64_t fld_T = -1, fld_np = 0; int fld_ny = 0, fld_nx = 0, fld_esz = 0;
+    int fld_prep_op = -1;                        // op fld_f32 was prepared for (-1: not prepared)
+    int64_t fld_order_chunk = -1;                // chunk length the order in fld_order was built for (steps sorted by plane inside each chunk)
+    std::vector<int32_t> fld_pos_host, fld_order_host;
     int w_minlsb = 0;                            // lowest set bit over the integer row weights
     int64_t last_alive = 0, last_nlab = 0;
     int64_t rowoff_T = -1; int rowoff_ny = -1; void *rowoff_p = nullptr;     // what seam_rowoff currently holds
@@ -567,7 +574,8 @@ extern "C" void ctk_destroy(ctk_handle *h)
                       &h->rv_cand_cnt, &h->rv_cand_off, &h->rv_cand, &h->rv_cand_scratch, &h->rv_seam_res, &h->rv_scalars, &h->rv_mark, &h->rv_inv, &h->rv_ff,
                       &h->lc_rows, &h->lc_cnt, &h->lc_wlo, &h->lc_whi, &h->lc_w, &h->rv_dmap, &h->rv_dorig, &h->rv_dbox, &h->rv_inex, &h->rv_touch, &h->io_in, &h->io_out,
                       &h->sh_mask_next, &h->sh_send, &h->sh_recv, &h->sh_prev, &h->sh_elist, &h->sh_ovr_slot, &h->sh_ovr_val,
-                      &h->sh_amb_list, &h->sh_counts, &h->sh_cl_shared, &h->sh_cl_sent, &h->chunk_vals, &h->lc_work, &h->lc_ovf, &h->lc_ekeys, &h->lc_offs, &h->lc_sw, &h->lc_sp, &h->lc_out, &h->lc_cross, &h->lc_gtab, &h->lc_occ, &h->lc_cp, &h->an_out, &h->an_clim, &h->an_raw, &h->an_idx, &h->sd_parent, &h->sd_tmin, &h->sd_tmax, &h->sd_root, &h->sd_nops, &h->sd_lbox, &h->rv_pstate, &h->ci_bsum, &h->scan_bsum};
+                      &h->sh_amb_list, &h->sh_counts, &h->sh_cl_shared, &h->sh_cl_sent, &h->chunk_vals, &h->lc_work, &h->lc_ovf, &h->lc_ekeys, &h->lc_offs, &h->lc_sw, &h->lc_sp, &h->lc_out, &h->lc_cross, &h->lc_gtab, &h->lc_occ, &h->lc_cp, &h->an_out, &h->an_clim, &h->an_raw, &h->an_idx, &h->sd_parent, &h->sd_tmin, &h->sd_tmax, &h->sd_root, &h->sd_nops, &h->sd_lbox, &h->rv_pstate, &h->ci_bsum, &h->scan_bsum,
+                      &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order};
     for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->base ? b->base : b->p);
     if (h->h_blob) (void)hipHostFree(h->h_blob);
     if (h->h_small) (void)hipHostFree(h->h_small);
@@ -862,13 +870,96 @@ static int threshold_rows(int ny, int nx, int64_t T)
     return std::min(ny, env > 0 ? env : 16);
 }
 
+// Threshold field for the following track calls (include/contrack_hip.h).  The field stays on the device until it is cleared or
+// replaced: repeated calls with the same climatology upload nothing.
+extern "C" int ctk_set_threshold_field(ctk_handle *h, const void *field, int elem_bytes, int64_t nplanes, int ny, int nx,
+                                       const int32_t *plane_of_step, int64_t T)
+{
+    if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));                  // nothing in flight reads the old field
+    h->fld_T = -1; h->fld_prep_op = -1; h->fld_order_chunk = -1;
+    h->c_thr_valid = false;
+    if (!field) {
+        for (DevBuf *b : {&h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order}) {
+            if (b->p) (void)hipFree(b->base ? b->base : b->p);
+            *b = DevBuf();
+        }
+        h->fld_pos_host.clear();
+        return CTK_OK;
+    }
+    if ((elem_bytes != 4 && elem_bytes != 8) || nplanes < 1 || ny < 1 || nx < 1 || T < 0 || (T > 0 && !plane_of_step))
+        return ctk_set_error(CTK_E_INVALID, "ctk_set_threshold_field: bad arguments (elem_bytes=%d nplanes=%lld ny=%d nx=%d T=%lld)", elem_bytes,
+                             (long long)nplanes, ny, nx, (long long)T);
+    if (nplanes > 0x7fffffffll) return ctk_set_error(CTK_E_RANGE, "ctk_set_threshold_field: more than 2^31-1 planes");
+    for (int64_t t = 0; t < T; t++)
+        if (plane_of_step[t] < 0 || plane_of_step[t] >= nplanes)
+            return ctk_set_error(CTK_E_INVALID, "ctk_set_threshold_field: plane_of_step[%lld] = %d is not in [0, %lld)", (long long)t, plane_of_step[t], (long long)nplanes);
+    const size_t bytes = (size_t)nplanes * ny * nx * elem_bytes;
+    CTKCHK(ensure(h, h->fld_raw, bytes));
+    CTKCHK(ensure(h, h->fld_pos, (size_t)std::max<int64_t>(T, 1) * 4));
+    HIPCHK(hipMemcpy(h->fld_raw.p, field, bytes, hipMemcpyHostToDevice));
+    if (T > 0) HIPCHK(hipMemcpy(h->fld_pos.p, plane_of_step, (size_t)T * 4, hipMemcpyHostToDevice));
+    h->fld_pos_host.assign(plane_of_step, plane_of_step + T);
+    h->fld_T = T; h->fld_np = nplanes; h->fld_ny = ny; h->fld_nx = nx; h->fld_esz = elem_bytes;
+    return CTK_OK;
+}
+
+// the device side of a field call: the float32 compare field for this op (from a float64 field, once per field and op) and the
+// plane-major step order for launches of `chunk` steps (once per field and chunk length)
+static int prepare_field(ctk_handle *h, bool f64, int cmp_op, int64_t chunk)
+{
+    hipStream_t s = h->stream;
+    const int64_t n = h->fld_np * h->fld_ny * h->fld_nx;
+    if (!f64 && h->fld_esz == 8 && h->fld_prep_op != cmp_op) {
+        CTKCHK(ensure(h, h->fld_f32, (size_t)n * 4));
+        const int g = (int)std::min<int64_t>((n + 255) / 256, 8192);
+        const double *in = P<double>(h->fld_raw);
+        float *out = P<float>(h->fld_f32);
+        switch (cmp_op) {
+        case 0: k_thr_field_prep<0><<<g, 256, 0, s>>>(in, out, n); break;
+        case 1: k_thr_field_prep<1><<<g, 256, 0, s>>>(in, out, n); break;
+        case 2: k_thr_field_prep<2><<<g, 256, 0, s>>>(in, out, n); break;
+        default: k_thr_field_prep<3><<<g, 256, 0, s>>>(in, out, n); break;
+        }
+        HIPCHK(hipGetLastError());
+        h->fld_prep_op = cmp_op;
+    }
+    // (CTK_THR_FIELD_ORDER=0: launch order, for tools/thr_field_probe.py; the key carries it so that a change is seen)
+    const char *om = getenv("CTK_THR_FIELD_ORDER");
+    const int64_t key = (om && atoi(om) == 0) ? -chunk - 1 : chunk;
+    if (h->fld_order_chunk != key) {
+        const int64_t T = h->fld_T;
+        std::vector<int32_t> &ord = h->fld_order_host;
+        ord.resize((size_t)std::max<int64_t>(T, 1));
+        for (int64_t c0 = 0; c0 < T; c0 += chunk) {
+            const int64_t nt = std::min<int64_t>(chunk, T - c0);
+            int32_t *o = ord.data() + c0;
+            for (int64_t i = 0; i < nt; i++) o[i] = (int32_t)i;                    // step of the chunk, relative to its first step
+            if (key >= 0) {
+                const int32_t *p = h->fld_pos_host.data() + c0;
+                std::stable_sort(o, o + nt, [p](int32_t a, int32_t b) { return p[a] < p[b]; });
+            }
+        }
+        CTKCHK(ensure(h, h->fld_order, ord.size() * 4));
+        HIPCHK(hipMemcpyAsync(h->fld_order.p, ord.data(), ord.size() * 4, hipMemcpyHostToDevice, s));
+        h->fld_order_chunk = key;
+    }
+    return CTK_OK;
+}
+
 // defer_compact (time-sharded path): the dense component tables are built after the halo has arrived, because the halo's
 // components come first in them
 static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int64_t T, int ny, int nx, const double *thr,
                               int cmp_op, const float *wrow, int has_prev, bool defer_compact = false)
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
-    if (T < 0 || ny < 1 || nx < 1 || (T > 0 && ((!anom_dev && !h->sio) || !thr)) || !wrow)
+    // thr == NULL: the threshold field set on the handle (ctk_set_threshold_field), if its shape is this call's
+    const bool fld_call = T > 0 && !thr && h->fld_T == T && h->fld_ny == ny && h->fld_nx == nx;
+    if (T > 0 && !thr && !fld_call && ny >= 1 && nx >= 1)
+        return ctk_set_error(CTK_E_INVALID, "ctk_shard_label2d: thr is NULL and no threshold field of shape (T=%lld, ny=%d, nx=%d) is set%s", (long long)T, ny, nx,
+                             h->fld_T >= 0 ? " (the field set has another shape)" : "");
+    if (T < 0 || ny < 1 || nx < 1 || (T > 0 && ((!anom_dev && !h->sio) || (!thr && !fld_call))) || !wrow)
         return ctk_set_error(CTK_E_INVALID, "ctk_shard_label2d: bad shape (T=%lld ny=%d nx=%d) or null pointer", (long long)T, ny, nx);
     if (cmp_op < 0 || cmp_op > 3) return ctk_set_error(CTK_E_INVALID, "ctk_shard_label2d: cmp_op %d not in 0..3", cmp_op);
     if (nx > 65535 || ny > 65535) return ctk_set_error(CTK_E_RANGE, "ctk_shard_label2d: grid %dx%d exceeds 65535 per axis", ny, nx);
@@ -888,7 +979,8 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
     // pinned memory, so that the uploads are asynchronous and nothing has to be waited for before the first kernel.
     // Thresholds / weights equal to the previous call's are already on the device: nothing is converted or uploaded.
     const size_t thr_bytes = (size_t)std::max<int64_t>(T, 1) * 8;
-    const bool same_thr = h->c_thr_valid && h->c_T == T && h->c_f64 == f64 && h->c_cmp == cmp_op && (T == 0 || memcmp(h->c_thr.data(), thr, (size_t)T * 8) == 0);
+    const bool same_thr = fld_call || (h->c_thr_valid && h->c_T == T && h->c_f64 == f64 && h->c_cmp == cmp_op && (T == 0 || memcmp(h->c_thr.data(), thr, (size_t)T * 8) == 0));
+    if (fld_call) h->c_thr_valid = false;                             // (a field call leaves no per-step thresholds behind)
     const bool same_w = h->c_w_valid && (int)h->c_w.size() == ny && h->c_w_nx == nx && memcmp(h->c_w.data(), wrow, (size_t)ny * 4) == 0;
     double *thr32 = nullptr;
     int64_t *wlo = nullptr;
@@ -956,6 +1048,7 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
     if (T == 0) HIPCHK(hipMemsetAsync(h->counters.p, 0, CTK_CNT_ZEROED * 4, s));
     if (T > 0) {
         if (!same_thr) { HIPCHK(hipMemcpyAsync(h->thr32.p, thr32, (size_t)T * (f64 ? 8 : 4), hipMemcpyHostToDevice, s)); h->c_thr_valid = true; }
+        if (fld_call) CTKCHK(prepare_field(h, f64, cmp_op, h->sio ? h->sio->chunk : T));
     }
     if (!same_w) { HIPCHK(hipMemcpyAsync(h->wlo.p, wlo, w_bytes, hipMemcpyHostToDevice, s)); h->c_w_valid = true; }    // same layout on both sides
     HT("uploads queued");
@@ -972,6 +1065,29 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
             const unsigned g4 = (unsigned)nblk4;
             uint64_t *mk = P<uint64_t>(h->mask) + t0 * ny * W;
             uint32_t *zc = t0 == 0 ? P<uint32_t>(h->counters) : nullptr;
+            if (fld_call) {                                  // the threshold field: its own kernels, launched here and nowhere else
+                const bool vf = v4;
+                const float *f32 = h->fld_esz == 4 ? P<float>(h->fld_raw) : P<float>(h->fld_f32);
+                const int32_t *pos = P<int32_t>(h->fld_pos) + t0, *ord = P<int32_t>(h->fld_order) + t0;
+                const char *fx = getenv("CTK_THR_FIELD_XCD");                 // (chunk -> XCD mapping, tools/thr_field_probe.py)
+                const int fld_xcd = fx ? atoi(fx) : 0;                          // (1: no faster, measured -- DESIGN.md section 3)
+#define LAUNCH_FLD(OP)                                                                                                                      \
+    do {                                                                                                                                \
+        if (vf) k_threshold_field<OP, 4><<<g4, 256, 0, s>>>((const float *)src, f32, pos, ord, ny, nx, W, mk, rbt, zc, fld_xcd);                  \
+        else if (!f64) k_threshold_field_g<OP, float, float><<<g, 256, 0, s>>>((const float *)src, f32, pos, rows, ny, nx, W, mk, zc);     \
+        else if (h->fld_esz == 4) k_threshold_field_g<OP, double, float><<<g, 256, 0, s>>>((const double *)src, P<float>(h->fld_raw), pos, rows, ny, nx, W, mk, zc); \
+        else k_threshold_field_g<OP, double, double><<<g, 256, 0, s>>>((const double *)src, P<double>(h->fld_raw), pos, rows, ny, nx, W, mk, zc); \
+    } while (0)
+                switch (cmp_op) {
+                case 0: LAUNCH_FLD(0); break;
+                case 1: LAUNCH_FLD(1); break;
+                case 2: LAUNCH_FLD(2); break;
+                default: LAUNCH_FLD(3); break;
+                }
+#undef LAUNCH_FLD
+                HIPCHK(hipGetLastError());
+                return CTK_OK;
+            }
             // ballot form: float32, rows of at most 64 words
             static const int thr_variant = getenv("CTK_THRESHOLD") ? atoi(getenv("CTK_THRESHOLD")) : 7;
             const bool v6 = !f64 && W <= 64 && (thr_variant == 6 || !v4);      // ballot form: where the float4 form does not apply (or on request)
@@ -1034,7 +1150,7 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
         if (mask_fresh) { h->mask_tries = 0; h->mask_ratio = 0.0; h->mask_check_pending = true; h->mask_check_retries = 0; }
         static const bool check_first = getenv("CTK_MASK_CHECK_FIRST") != nullptr;
         const bool v7_path = !f64 && (nx % 4 == 0) && (((uintptr_t)anom_dev & 15) == 0);
-        if (anom_dev && h->mask_check_pending && (check_first || !mask_fresh) && h->mask_off_dbg < 0 && ctk_env().mask_tune && v7_path &&
+        if (anom_dev && !fld_call && h->mask_check_pending && (check_first || !mask_fresh) && h->mask_off_dbg < 0 && ctk_env().mask_tune && v7_path &&
             (size_t)T * ny * nx * 4 >= ((size_t)128 << 20)) {
             h->mask_check_pending = false;
             h->mask_spacer_gb = 0.0;
@@ -1333,11 +1449,13 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
 extern "C" int ctk_shard_label2d(ctk_handle *h, const float *anom_dev, int64_t T, int ny, int nx, const double *thr, int cmp_op,
                                  const float *wrow, int has_prev)
 {
+    if (h && T > 0 && !thr) return ctk_set_error(CTK_E_INVALID, "ctk_shard_label2d: thr is NULL (the staged entries take per-step thresholds, not a threshold field)");
     return shard_label2d_impl(h, anom_dev, false, T, ny, nx, thr, cmp_op, wrow, has_prev);
 }
 extern "C" int ctk_shard_label2d_f64(ctk_handle *h, const double *anom_dev, int64_t T, int ny, int nx, const double *thr, int cmp_op,
                                      const float *wrow, int has_prev)
 {
+    if (h && T > 0 && !thr) return ctk_set_error(CTK_E_INVALID, "ctk_shard_label2d_f64: thr is NULL (the staged entries take per-step thresholds, not a threshold field)");
     return shard_label2d_impl(h, anom_dev, true, T, ny, nx, thr, cmp_op, wrow, has_prev);
 }
 

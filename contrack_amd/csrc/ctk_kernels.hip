@@ -421,6 +421,146 @@ __global__ __launch_bounds__(256) void k_threshold(const TIN *__restrict__ anom,
 }
 
 // ------------------------------------------------------------------------------------------------
+// K0f threshold FIELD -> bit mask        (contrack.py:648-671 with a threshold that varies by grid point, NaN -> 0)
+// fld is f32/f64 [nplanes][ny][nx] with the slab's pitch; step t is compared with plane pos[t].  Same mask layout and the same
+// zero_counters duty as the scalar kernels: everything downstream is unchanged.
+//
+// k_threshold_field (float32, nx % 4 == 0, 16-byte aligned slab): k_threshold_v7's decomposition, one workgroup per (step, rb rows),
+// workgroup b takes step order[b / nchunk] -- the host passes the steps sorted by plane (stable), so that the workgroups that read
+// one plane run together and a day-of-year field comes from HBM about once instead of once per step.  The slab is streamed with
+// non-temporal loads, the field with ordinary ones (it should stay in L2 / MALL between the steps that share a plane).
+// k_threshold_field_g (any nx, float32 or float64 slab): lane l tests pixel 64k+l, __ballot packs a word; the compare is made in
+// the slab's type against the field widened to it.
+// ------------------------------------------------------------------------------------------------
+template <int OP>
+__device__ __forceinline__ uint32_t thr_nibble4(const f32x4 v, const f32x4 th)
+{
+    uint32_t nib = 0;
+    // thr_nibble with one threshold per pixel: nib = (((w) 2 + z) 2 + y) 2 + x; NaN on either side compares false
+#define CTK_CMP4_ADDC(INS)                                                                                                        \
+    asm volatile(INS " vcc, %1, %5\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t" INS " vcc, %2, %6\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t" \
+                 INS " vcc, %3, %7\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t" INS " vcc, %4, %8\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc"      \
+                 : "+v"(nib) : "v"(v.w), "v"(v.z), "v"(v.y), "v"(v.x), "v"(th.w), "v"(th.z), "v"(th.y), "v"(th.x) : "vcc")
+    if (OP == 0) CTK_CMP4_ADDC("v_cmp_ge_f32");
+    else if (OP == 1) CTK_CMP4_ADDC("v_cmp_le_f32");
+    else if (OP == 2) CTK_CMP4_ADDC("v_cmp_gt_f32");
+    else CTK_CMP4_ADDC("v_cmp_lt_f32");
+#undef CTK_CMP4_ADDC
+    return nib;
+}
+
+// U = float4 pairs (slab + field) in flight per lane: 4 keeps the kernel at <= 64 VGPRs
+template <int OP, int U>
+__global__ __launch_bounds__(256) void k_threshold_field(const float *__restrict__ anom, const float *__restrict__ fld,
+                                                         const int32_t *__restrict__ pos, const int32_t *__restrict__ order,
+                                                         int ny, int nx, int W, uint64_t *__restrict__ mask, int rb,
+                                                         uint32_t *__restrict__ zero_counters, int xcd)
+{
+    if (zero_counters && blockIdx.x == 0 && threadIdx.x < CTK_CNT_ZEROED) zero_counters[threadIdx.x] = 0u;
+    const int nchunk = (ny + rb - 1) / rb;
+    // (xcd = 1: one contiguous eighth of the plane-major order per XCD -- the steps of a plane then share ONE XCD's L2)
+    const unsigned bid = xcd_chunk(blockIdx.x, gridDim.x, xcd);
+    const unsigned si = bid / (unsigned)nchunk;
+    const int t = order[si], plane = pos[t];                // wave-uniform: scalar loads
+    const int y0 = (int)(bid - si * (unsigned)nchunk) * rb, tid = (int)threadIdx.x;
+    const int rows = min(rb, ny - y0);
+    const int n4 = nx >> 2, n4p = W << 4;
+    const int total = rows * n4p;
+    const int64_t row0 = (int64_t)t * ny + y0;
+    const char *base = (const char *)(anom + row0 * (int64_t)nx);
+    const char *fbase = (const char *)(fld + ((int64_t)plane * ny + y0) * (int64_t)nx);      // same in-plane offsets as the slab
+    char *mbase = (char *)(mask + row0 * W);
+    const int sub = tid & 15;
+    const uint32_t shift = (uint32_t)(4 * (sub & 7));
+    int nr = tid / n4p, nc = tid - nr * n4p;
+    const int dr = 256 / n4p, dc = 256 - dr * n4p;
+    const uint32_t pitch = (uint32_t)nx * 4u, wpitch = (uint32_t)W * 8u;
+    for (int i0 = 0; i0 < total; i0 += 256 * U) {
+        f32x4 v[U], th[U];
+        uint32_t moff[U], vm[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int cl = min(nc, n4 - 1);                // padding slots re-read the row's last quad; their bits are cleared
+            const int rl = min(nr, rows - 1);              // lanes beyond the chunk re-read its last row and store nothing
+            const uint32_t off = (uint32_t)rl * pitch + (uint32_t)cl * 16u;
+            v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(base + off));
+            th[u] = *reinterpret_cast<const f32x4 *>(fbase + off);
+            vm[u] = nc < n4 ? 0xfu : 0u;
+            moff[u] = nr < rows ? (uint32_t)nr * wpitch + (uint32_t)(nc >> 4) * 8u : 0xffffffffu;
+            nr += dr; nc += dc;
+            if (nc >= n4p) { nc -= n4p; nr++; }
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t nib = thr_nibble4<OP>(v[u], th[u]) & vm[u];
+            uint32_t x = nib << shift;
+            x = dpp_or<0xB1>(x);
+            x = dpp_or<0x4E>(x);
+            x = dpp_or<0x141>(x);
+            const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x140, 0xF, 0xF, false);
+            if (sub == 0 && moff[u] != 0xffffffffu) *reinterpret_cast<uint64_t *>(mbase + moff[u]) = ((uint64_t)hi << 32) | x;
+        }
+    }
+}
+
+template <int OP, typename TIN, typename TF>
+__global__ __launch_bounds__(256) void k_threshold_field_g(const TIN *__restrict__ anom, const TF *__restrict__ fld, const int32_t *__restrict__ pos,
+                                                           int64_t nrows, int ny, int nx, int W, uint64_t *__restrict__ mask,
+                                                           uint32_t *__restrict__ zero_counters)
+{
+    if (zero_counters && blockIdx.x == 0 && threadIdx.x < CTK_CNT_ZEROED) zero_counters[threadIdx.x] = 0u;
+    const int lane = lane_id();
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    const TIN qnan = (TIN)__builtin_nanf("");
+    for (int64_t row = wave; row < nrows; row += nwaves) {
+        const int64_t t = row / ny;
+        const TIN *src = anom + row * (int64_t)nx;
+        const TF *frow = fld + ((int64_t)pos[t] * ny + (row - t * ny)) * (int64_t)nx;
+        for (int w0 = 0; w0 < W; w0 += WAVE) {
+            const int wn = min(WAVE, W - w0);
+            uint64_t mine = 0;
+            for (int k = 0; k < wn; k += 8) {
+                TIN v[8], th[8];
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const int x = (w0 + k + j) * 64 + lane;
+                    v[j] = (x < nx) ? src[x] : qnan;
+                    th[j] = (x < nx) ? (TIN)frow[x] : qnan;
+                }
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const uint64_t b = __ballot(cmp_op<OP, TIN>(v[j], th[j]));
+                    if (lane == k + j) mine = b;
+                }
+            }
+            if (lane < wn) mask[row * W + w0 + lane] = mine;
+        }
+    }
+}
+
+// the float32 field the float32 compare reads, from a float64 field: adjust_threshold (ctk_api.hip) per element, so that
+// `x <op> out[i]` in float32 equals `(double)x <op> in[i]`; NaN stays NaN
+__device__ __forceinline__ float f32_step(float f, bool up)           // std::nextafterf(f, up ? +inf : -inf) for f not NaN
+{
+    if (f == 0.0f) return up ? __uint_as_float(1u) : -__uint_as_float(1u);
+    const uint32_t b = __float_as_uint(f);
+    return __uint_as_float(((f > 0.0f) == up) ? b + 1u : b - 1u);
+}
+template <int OP>
+__global__ __launch_bounds__(256) void k_thr_field_prep(const double *__restrict__ in, float *__restrict__ out, int64_t n)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double thr = in[i];
+        float f = (float)thr;
+        if (thr != thr) f = __builtin_nanf("");
+        else if (OP == 0 || OP == 3) { if ((double)f < thr) f = f32_step(f, true); }
+        else if ((double)f > thr) f = f32_step(f, false);
+        out[i] = f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // K0b runs per row / per word from the mask: one workgroup per timestep, one thread per row.
 //   wstart[row][w] = run starts in words < w of the row      rowstart[t][y] = first run of row y
 //   tcount[t]      = runs of the timestep

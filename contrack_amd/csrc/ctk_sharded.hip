@@ -1606,7 +1606,10 @@ static int track_sharded_entry(ctk_handle *h, ctk_comm *c, const void *anom_dev,
                                int64_t *n_tracked)
 {
     if (h) h->sh_collective_err = false;
-    const int rc = track_sharded_impl(h, c, anom_dev, f64, T_local, t_begin, T_total, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, flag_dev, n_tracked);
+    // (a threshold field, ctk_set_threshold_field, is not taken here: thr == NULL is refused like any other null argument)
+    const int rc = (h && T_local > 0 && !thr)
+        ? ctk_set_error(CTK_E_INVALID, "ctk_track_sharded: thr is NULL (the time-shard entries take per-step thresholds, not a threshold field)")
+        : track_sharded_impl(h, c, anom_dev, f64, T_local, t_begin, T_total, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, flag_dev, n_tracked);
     if (rc != CTK_OK && c && h && !h->sh_collective_err) {
         std::string msg = ctk_last_error();                          // (the abort drains the stream: keep the message of the cause)
         ctk_comm_abort(c, rc);

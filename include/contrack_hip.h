@@ -68,6 +68,16 @@ int ctk_track_f32_dev(ctk_handle *h, const float *anom_dev, int64_t T, int ny, i
                       const double *thr, int cmp_op, const float *wrow, double overlap,
                       int persistence, int twosided, int32_t *flag_dev, int64_t *n_tracked);
 
+/* Threshold field for the following track calls on this handle (contrack.py:648-671 with a threshold that varies by grid point).
+ * field: host array, elem_bytes 4 (float32) or 8 (float64), [nplanes][ny][nx]; plane_of_step[T]: plane used by step t
+ * (0 <= p < nplanes).  field == NULL clears it.  A track call uses the field only when it is passed thr == NULL and its (T, ny, nx)
+ * match; thr != NULL keeps today's path.  Taken by the host, _dev, resident and streaming entries; the staged and time-shard entries
+ * refuse thr == NULL.  The compare is numpy's: a float32 slab against a float32 field in float32, against a float64 field exactly as
+ * (double)x <op> field (the float32 copy it reads is prepared once per field and op), a float64 slab in float64.  NaN compares false.
+ * The field stays on the device until it is cleared or replaced. */
+int ctk_set_threshold_field(ctk_handle *h, const void *field, int elem_bytes, int64_t nplanes, int ny, int nx,
+                            const int32_t *plane_of_step, int64_t T);
+
 /* The host-array entries keep device copies of the slab and of the result in the handle between calls (grow-only, so that
  * repeated calls do not reallocate).  ctk_release_io frees them (and the copy lanes): call it after a one-off large slab. */
 int ctk_release_io(ctk_handle *h);
