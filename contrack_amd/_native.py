@@ -35,6 +35,7 @@ EXPORTS = [
     "ctk_lifecycle_f32", "ctk_lifecycle_f64", "ctk_lifecycle_f32_dev", "ctk_lifecycle_f64_dev", "ctk_lifecycle_rows", "ctk_lifecycle_exact",
     "ctk_track_stream_f32", "ctk_track_stream_f64", "ctk_track_stream_cb", "ctk_stream_times",
     "ctk_set_threshold_field",
+    "ctk_frequency_dev", "ctk_frequency", "ctk_frequency_cb", "ctk_debug_set_freq", "ctk_debug_time_freq",
 ]
 
 READ_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)       # ctk_read_chunk_fn
@@ -83,6 +84,11 @@ def lib():
     L.ctk_track_stream_f64.argtypes = track_args + [i64]
     L.ctk_track_stream_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, p, i32, p, dbl, i32, i32, WRITE_CHUNK_FN, p, C.POINTER(i64), i64]
     L.ctk_stream_times.argtypes = [p, C.POINTER(dbl)]
+    L.ctk_frequency_dev.argtypes = [p, p, i64, i32, i32, p, i32, C.c_int32, p, i32]
+    L.ctk_frequency.argtypes = [p, p, i64, i32, i32, p, i32, C.c_int32, p, i64]
+    L.ctk_frequency_cb.argtypes = [p, i64, i32, i32, READ_CHUNK_FN, p, p, i32, C.c_int32, p, i64]
+    L.ctk_debug_set_freq.argtypes = [p, i64, i32]
+    L.ctk_debug_time_freq.argtypes = [p, p, i64, i32, i32, p, i32, C.c_int32, p, i32, C.POINTER(dbl)]
     L.ctk_shard_label2d.argtypes = [p, p, i64, i32, i32, p, i32, p, i32]
     L.ctk_shard_label2d_f64.argtypes = [p, p, i64, i32, i32, p, i32, p, i32]
     L.ctk_shard_halo_size.argtypes = [p, C.POINTER(sz)]
@@ -188,6 +194,29 @@ def _thr_or_field(thr, T):
     if thr.shape != (T,):
         raise ValueError("thr must have shape (T,) and wrow (ny,)")
     return thr
+
+
+def _groups(group, T, ngroups=None):
+    """group ids per timestep as int32 (T,) and the number of groups; group None: one group (ids NULL).  Ids are checked against
+    [0, ngroups) by the library; here only what the conversion to int32 could hide."""
+    if group is None:
+        return None, 1 if ngroups is None else int(ngroups)
+    g = np.asarray(group)
+    if g.ndim != 1 or g.shape[0] != T:
+        raise ValueError("group must hold one id per timestep (%d), not shape %s" % (T, g.shape))
+    if g.dtype.kind not in "iu":
+        raise ValueError("group ids must be integers")
+    if g.size and (g.min() < np.iinfo(np.int32).min or g.max() > np.iinfo(np.int32).max):
+        raise ValueError("group ids beyond int32")
+    g = np.ascontiguousarray(g, dtype=np.int32)
+    return g, (int(g.max()) + 1 if g.size else 1) if ngroups is None else int(ngroups)
+
+
+def _above(above):
+    a = int(above)
+    if a < np.iinfo(np.int32).min or a > np.iinfo(np.int32).max:
+        raise ValueError("above must fit int32")
+    return a
 
 
 def _ptr(a):
@@ -640,6 +669,74 @@ class Tracker:
         ms = (C.c_double * 4)()
         check(lib().ctk_stream_times(self._h, ms))
         return dict(zip(("reader", "writer", "input_phase", "output_phase"), (float(v) for v in ms)))
+
+    # ---- blocking frequency (README.rst:159-160) ---------------------------------------------------------------------
+    def frequency(self, flag, group=None, ngroups=None, above=0, chunk_steps=0):
+        """counts[g, y, x] = #{t : group[t] == g and flag[t, y, x] > above} of an int32 (T, ny, nx) host slab (ctk_frequency: chunks
+        of `chunk_steps` timesteps pass through the device, 0: about 256 MB each).  group None: one group.  ngroups None:
+        max(group) + 1.  Returns uint32 (ngroups, ny, nx)."""
+        flag = np.asarray(flag)
+        if flag.ndim != 3:
+            raise ValueError("flag must be (time, lat, lon)")
+        if flag.dtype != np.int32:
+            if flag.dtype.kind not in "iub" or flag.dtype.itemsize > 4 or flag.dtype == np.uint32:
+                raise ValueError("flag must be int32 here (wider ids: frequency_cb, or contrack.frequency_numpy)")
+        flag = np.ascontiguousarray(flag, dtype=np.int32)
+        T, ny, nx = flag.shape
+        g, G = _groups(group, T, ngroups)
+        counts = np.empty((max(G, 1), ny, nx), dtype=np.uint32)
+        check(lib().ctk_frequency(self._h, flag.ctypes.data, T, ny, nx, _ptr(g), G, _above(above), counts.ctypes.data, int(chunk_steps)))
+        return counts
+
+    def frequency_cb(self, reader, shape, group=None, ngroups=None, above=0, chunk_steps=0):
+        """the same with the flag read chunk by chunk: reader(t0, nt, out) fills `out`, an int32 (nt, ny, nx) view of pinned memory,
+        with the timesteps [t0, t0 + nt)"""
+        T, ny, nx = (int(v) for v in shape)
+        g, G = _groups(group, T, ngroups)
+        counts = np.empty((max(G, 1), ny, nx), dtype=np.uint32)
+        errors = []
+
+        def rd(_user, t0, nt, dst):
+            try:
+                reader(int(t0), int(nt), np.ctypeslib.as_array(C.cast(dst, C.POINTER(C.c_int32)), shape=(nt, ny, nx)))
+                return 0
+            except BaseException as e:                    # an exception must not cross the C frames
+                errors.append(e)
+                return 1
+        rcb = READ_CHUNK_FN(rd)
+        rc = lib().ctk_frequency_cb(self._h, T, ny, nx, rcb, None, _ptr(g), G, _above(above), counts.ctypes.data, int(chunk_steps))
+        if errors:
+            raise errors[0]
+        check(rc)
+        return counts
+
+    def frequency_dev(self, flag_dev, T, ny, nx, group=None, ngroups=None, above=0, counts_dev=None, accumulate=False):
+        """ctk_frequency_dev on an int32 flag in device memory.  counts_dev None: the uint32 (ngroups, ny, nx) counts are returned;
+        else they are written (accumulate: added) to that device buffer and None is returned."""
+        g, G = _groups(group, T, ngroups)
+        if counts_dev is not None:
+            check(lib().ctk_frequency_dev(self._h, flag_dev, int(T), int(ny), int(nx), _ptr(g), G, _above(above), counts_dev, int(bool(accumulate))))
+            return None
+        counts = np.empty((max(G, 1), int(ny), int(nx)), dtype=np.uint32)
+        d = self.malloc(max(counts.nbytes, 4))
+        try:
+            check(lib().ctk_frequency_dev(self._h, flag_dev, int(T), int(ny), int(nx), _ptr(g), G, _above(above), d, 0))
+            self.d2h(counts, d)
+        finally:
+            self.free(d)
+        return counts
+
+    def debug_set_freq(self, slice_steps=0, nt=None):
+        """k_freq experiments: timesteps per slice (0: the library's rule), nontemporal (True) or plain (False) 16-byte loads, None:
+        the library's default (nontemporal)"""
+        check(lib().ctk_debug_set_freq(self._h, int(slice_steps), -1 if nt is None else int(bool(nt))))
+
+    def time_freq(self, flag_dev, T, ny, nx, counts_dev, group=None, ngroups=None, above=0, reps=10):
+        """k_freq alone between HIP events (counts_dev: device buffer of ngroups * ny * nx uint32): (best, mean) ms per launch"""
+        g, G = _groups(group, T, ngroups)
+        ms = (C.c_double * 2)()
+        check(lib().ctk_debug_time_freq(self._h, flag_dev, int(T), int(ny), int(nx), _ptr(g), G, _above(above), counts_dev, int(reps), ms))
+        return float(ms[0]), float(ms[1])
 
     # ---- calc_anom / percentile threshold on the device ---------------------------------------------------------
     def anomalies(self, x, group, ngroups, window=1, smooth=1, clim=None, want_anom=True, want_clim=False, keep_resident=False):

@@ -3,9 +3,9 @@
 
 Same constructor, `read`, `read_xarray`, `set_up`, `calc_clim`, `calc_anom`, `run_contrack` signatures, the
 same `ValueError` / `IOError` texts, the same INFO log lines and the same `flag` variable (dims of the input
-variable, int32 ids identical to the reference's, same attrs).  `run_contrack`, `run_lifecycle`, `calc_clim` / `calc_anom`
-and the percentile threshold of the reference's README run on the GPU; `calc_anom` leaves its slab resident in HBM so that
-the following `run_contrack` does not cross PCIe on the way in.
+variable, int32 ids identical to the reference's, same attrs).  `run_contrack`, `run_lifecycle`, `calc_clim` / `calc_anom`,
+the percentile threshold and the blocking frequency (`calc_frequency`, README.rst:159-160) of the reference's README run on the
+GPU; `calc_anom` leaves its slab resident in HBM so that the following `run_contrack` does not cross PCIe on the way in.
 
 xarray is imported lazily: the class itself only needs the small part of the Dataset/DataArray API listed in
 tests/minixr.py, so it also works on any duck-typed dataset.  `track_numpy` is the array-level entry.
@@ -136,6 +136,58 @@ def track_numpy(anom, wrow, threshold, gorl, overlap, persistence, twosided=True
     else:
         call = lambda t: trk.track(anom, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided)
     return call(thr) if field is None else _track_field(trk, field[0], field[1], call)
+
+
+SEASONS = np.array(['DJF', 'DJF', 'MAM', 'MAM', 'MAM', 'JJA', 'JJA', 'JJA', 'SON', 'SON', 'SON', 'DJF'])
+
+
+def season_of_month(month):
+    """xarray's time.season: 'DJF', 'MAM', 'JJA' or 'SON' for months 1..12 (np.unique orders them DJF, JJA, MAM, SON, as
+    groupby('time.season') does)"""
+    month = np.asarray(month)
+    if month.size and (month.min() < 1 or month.max() > 12):
+        raise ValueError("months must lie in 1..12")
+    return SEASONS[month.astype(np.int64) - 1]
+
+
+def frequency_percent(counts, n):
+    """counts (G, ...) / n[g] * 100 in float64, divided first as xr.where(...).sum('time') / ntime * 100 does (README.rst:159-160);
+    an empty group (n[g] == 0) gives NaN, numpy's 0 / 0"""
+    counts = np.asarray(counts)
+    n = np.asarray(n, dtype=np.int64).reshape((-1,) + (1,) * (counts.ndim - 1))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return counts.astype(np.float64) / n * 100
+
+
+def frequency_numpy(flag, group=None, above=0, percent=True, device=None):
+    """the blocking frequency of README.rst:159-160 on a (time, lat, lon) integer flag slab:
+        np.where(flag > above, 1, 0).sum(axis=0) / T * 100           (above = 1 is the README's expression)
+    per group of timesteps when `group` (one id in [0, G) per timestep, any order in time) is given.  The count runs on the GPU
+    (ctk_frequency); int32 and narrower flags are read as they are, wider ones are converted to int32 chunk by chunk (an id beyond
+    int32 raises ValueError).  Returns float64 percent (G, ny, nx) -- (ny, nx) without `group` -- or, with percent=False, int64
+    counts of the same shape."""
+    flag = np.asarray(flag)
+    if flag.ndim != 3:
+        raise ValueError("flag must be (time, lat, lon)")
+    if flag.dtype.kind not in "iub":
+        raise ValueError("flag must be an integer field")
+    T, ny, nx = flag.shape
+    trk = _tracker(device)
+    ids, G = _native._groups(group, T)
+    if flag.dtype.itemsize < 4 or flag.dtype == np.int32:
+        counts = trk.frequency(flag, ids, G, above)
+    else:
+        lo, hi = np.iinfo(np.int32).min, np.iinfo(np.int32).max
+
+        def reader(t0, nt, out):
+            part = flag[t0:t0 + nt]
+            if part.size and (part.max() > hi or part.min() < lo):
+                raise ValueError("flag ids beyond int32")
+            out[...] = part
+        counts = trk.frequency_cb(reader, flag.shape, ids, G, above)
+    counts = counts.astype(np.int64)
+    out = frequency_percent(counts, np.bincount(ids, minlength=G) if ids is not None else [T]) if percent else counts
+    return out[0] if group is None else out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -454,7 +506,9 @@ class contrack(object):
             vals = np.asarray(getattr(t.dt, groupby))
         except (AttributeError, TypeError):
             import pandas as pd
-            vals = np.asarray(getattr(pd.DatetimeIndex(np.asarray(t.data)), groupby))
+            idx = pd.DatetimeIndex(np.asarray(t.data))
+            # (pandas has no season: the months mapped as xarray's time.season does)
+            vals = season_of_month(idx.month) if groupby == 'season' else np.asarray(getattr(idx, groupby))
         uniq, ids = np.unique(vals, return_inverse=True)
         return ids.astype(np.int32), uniq
 
@@ -464,10 +518,10 @@ class contrack(object):
         sort = [dims.index(d) for d in (self._time_name, self._latitude_name, self._longitude_name)]
         return np.asarray(da.data).transpose(sort), dims, sort
 
-    def _wrap(self, like, data, dims, coords=None, attrs=None):
+    def _wrap(self, like, data, dims, coords=None, attrs=None, name=None):
         """a labelled array of the same class as `like` (xarray.DataArray, or whatever duck-typed dataset is wrapped)"""
         try:                                         # (the climatology keeps the variable's name, as xarray's groupby().mean() does)
-            return type(like)(data, dims=dims, coords=coords, attrs=attrs or {}, name=getattr(like, "name", None))
+            return type(like)(data, dims=dims, coords=coords, attrs=attrs or {}, name=name or getattr(like, "name", None))
         except TypeError:
             return type(like)(data, dims=dims, coords=coords, attrs=attrs or {})
 
@@ -719,6 +773,37 @@ class contrack(object):
         call = lambda t: trk.track_stream(reader, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, shape=shape, dtype=dtype,
                                           chunk_steps=chunk_steps)
         return call(thr) if field is None else _track_field(trk, field[0], field[1], call)
+
+    # ---- blocking frequency (README.rst:159-160), consumer of `flag` ------------------------------------------------------
+    def calc_frequency(self, flag='flag', groupby=None, above=0):
+        """percentage of time steps with flag > above at every grid point: xr.where(ds[flag] > above, 1, 0).sum(dim='time') /
+        ntime * 100 -- the README's blocking frequency with above=1 -- or, with groupby ('month', 'season', 'year', ...), the same
+        per value of time.<groupby> (ascending; seasons as xarray orders them: DJF, JJA, MAM, SON), as groupby(...).sum() /
+        group size * 100.  Returns a labelled float64 array ('%') over the variable's own spatial dims, the group dim in the time
+        dim's place; it is not added to the dataset.  The count runs on the GPU (frequency_numpy)."""
+        self._ensure_set_up()
+        da = self.ds[flag]
+        dims = tuple(da.dims)
+        names = (self._time_name, self._latitude_name, self._longitude_name)
+        slab = np.asarray(da.data).transpose([dims.index(d) for d in names])
+        if groupby is None:
+            ids, uniq = None, None
+        else:
+            ids, uniq = self._group_ids(groupby)
+        freq = frequency_numpy(slab, ids, above=above)
+        if groupby is None:
+            out_dims = tuple(d for d in dims if d != self._time_name)
+            data = freq.transpose([names[1:].index(d) for d in out_dims])
+        else:
+            out_dims = tuple(groupby if d == self._time_name else d for d in dims)
+            data = freq.transpose([((groupby,) + names[1:]).index(d) for d in out_dims])
+        coords = {} if groupby is None else {groupby: uniq}
+        for name in (self._latitude_name, self._longitude_name):
+            coords[name] = np.asarray(self.ds[name].data)
+        attrs = {'units': '%', 'long_name': 'contrack frequency', 'standard_name': 'contrack frequency',
+                 'history': ' '.join(['Calculated from {} with input attributes:', 'flag > {},', 'groupby = {}.']).format(
+                     flag, above, groupby)}
+        return self._wrap(da, np.ascontiguousarray(data), out_dims, coords, attrs, name='frequency')
 
     # ---- life cycle (contrack.py:798-906), consumer of `flag` (SURVEY.md section 8(f) N1) ----------------------------
     def _time_labels(self):

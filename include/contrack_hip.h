@@ -375,6 +375,22 @@ int ctk_track_resident(ctk_handle *h, const double *thr, int cmp_op, const float
 int ctk_percentile_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, int y0, int y1, double q, double *out);
 int ctk_percentile_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, int y0, int y1, double q, double *out);
 
+/* ---- the blocking-frequency climatology of the reference's tutorial (README.rst:159-160) ---------------------------------------
+ *   xr.where(block['flag'] > 1, 1, 0).sum(dim='time') / block.ntime * 100     -- on the int32 flag slab (T, ny, nx), per group:
+ *   counts[g][y][x] = #{t : group[t] == g and flag[t][y][x] > above}            (exact; the caller divides: counts / n[g] * 100)
+ * group: T host ints in [0, ngroups) (month, season ... of every timestep; any order in time), NULL = one group (ngroups = 1).
+ * above = 1 is the README's expression, 0 counts every tracked id.  One read of the slab (k_freq, ctk_freq.hip), a few atomics.
+ * ctk_frequency_dev: flag in HBM; accumulate = 1 adds to counts_dev (time shards, a caller's own chunks), 0 overwrites it.
+ * ctk_frequency / _cb: a host array or a reader callback (ctk_read_chunk_fn, int32 elements); the flag passes through two
+ * chunk-sized device buffers, chunk k+1 copied while chunk k is counted (as ctk_track_stream_*; chunk_steps = 0: about 256 MB per
+ * chunk), so a slab larger than HBM or read lazily from a file works.  T must stay below 2^32 (uint32 counts). */
+int ctk_frequency_dev(ctk_handle *h, const int32_t *flag_dev, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int32_t above,
+                      uint32_t *counts_dev /* [ngroups][ny][nx] */, int accumulate /* 0: overwrite, 1: add */);
+int ctk_frequency(ctk_handle *h, const int32_t *flag, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int32_t above,
+                  uint32_t *counts /* host [ngroups][ny][nx] */, int64_t chunk_steps);
+int ctk_frequency_cb(ctk_handle *h, int64_t T, int ny, int nx, ctk_read_chunk_fn reader, void *reader_user, const int32_t *group, int ngroups,
+                     int32_t above, uint32_t *counts /* host */, int64_t chunk_steps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,13 @@ int ctk_check_flag_dev(ctk_handle *h, const float *anom_dev, const int32_t *flag
 int ctk_expand_runs_host(const uint64_t *mask, const uint32_t *rowstart, const uint32_t *run_base, const int32_t *run_val, int64_t T, int ny, int nx,
                          int32_t *flag, int *wrote_background, int *complex_runs);
 
+/* k_freq experiments (tools/freq_probe.py): timesteps per slice (0: the library's rule) and the 16-byte loads (0 plain, 1 nontemporal,
+ * -1 the library's default: nontemporal) */
+int ctk_debug_set_freq(ctk_handle *h, int64_t slice, int nt);
+/* k_freq alone between HIP events: one launch that overwrites counts_dev, then `reps` timed launches that add to it; ms2 = {best, mean} */
+int ctk_debug_time_freq(ctk_handle *h, const int32_t *flag_dev, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int32_t above,
+                        uint32_t *counts_dev, int reps, double *ms2);
+
 #ifdef __cplusplus
 }
 #endif
