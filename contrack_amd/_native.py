@@ -34,7 +34,7 @@ EXPORTS = [
     "ctk_anom_f32", "ctk_anom_f64", "ctk_resident_anom", "ctk_resident_anom_generation", "ctk_track_resident", "ctk_percentile_f32", "ctk_percentile_f64",
     "ctk_lifecycle_f32", "ctk_lifecycle_f64", "ctk_lifecycle_f32_dev", "ctk_lifecycle_f64_dev", "ctk_lifecycle_rows", "ctk_lifecycle_exact",
     "ctk_track_stream_f32", "ctk_track_stream_f64", "ctk_track_stream_cb", "ctk_stream_times",
-    "ctk_set_threshold_field",
+    "ctk_set_threshold_field", "ctk_set_segments",
     "ctk_frequency_dev", "ctk_frequency", "ctk_frequency_cb", "ctk_debug_set_freq", "ctk_debug_time_freq",
 ]
 
@@ -80,6 +80,7 @@ def lib():
     L.ctk_track_f64_dev.argtypes = track_args
     L.ctk_release_io.argtypes = [p]
     L.ctk_set_threshold_field.argtypes = [p, p, i32, i64, i32, i32, p, i64]
+    L.ctk_set_segments.argtypes = [p, p, i64]
     L.ctk_track_stream_f32.argtypes = track_args + [i64]
     L.ctk_track_stream_f64.argtypes = track_args + [i64]
     L.ctk_track_stream_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, p, i32, p, dbl, i32, i32, WRITE_CHUNK_FN, p, C.POINTER(i64), i64]
@@ -831,6 +832,19 @@ class Tracker:
 
     def clear_threshold_field(self):
         check(lib().ctk_set_threshold_field(self._h, None, 4, 0, 0, 0, None, 0))
+
+    # ---- segment breaks (ctk_set_segments) ----------------------------------------------------------------------------
+    def set_segments(self, starts):
+        """independent time segments for the following track calls: starts = first step of every segment (0 first, strictly
+        increasing).  No overlap, filter exemption or 3-D link crosses a break; ids stay unique over the slab."""
+        st = np.asarray(starts)
+        if st.ndim != 1 or (st.size and st.dtype.kind not in "iu"):
+            raise ValueError("segment starts must be a 1-D integer array")
+        st = np.ascontiguousarray(st, dtype=np.int64)
+        check(lib().ctk_set_segments(self._h, st.ctypes.data if st.size else None, st.shape[0]))
+
+    def clear_segments(self):
+        check(lib().ctk_set_segments(self._h, None, 0))
 
     # ---- device-resident --------------------------------------------------------------------------
     def malloc(self, nbytes):

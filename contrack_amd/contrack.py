@@ -113,13 +113,51 @@ def _track_field(trk, planes, pos, call):
         trk.clear_threshold_field()
 
 
-def track_numpy(anom, wrow, threshold, gorl, overlap, persistence, twosided=True, device=None):
+def _track_segments(trk, starts, call):
+    """one call with the handle's segment breaks set to `starts` (None: no segments, the call as it is); cleared again afterwards.
+    `call` takes no argument: it may itself be a _track_field call."""
+    if starts is None:
+        return call()
+    trk.set_segments(starts)
+    try:
+        return call()
+    finally:
+        trk.clear_segments()
+
+
+def segment_starts(starts, T):
+    """validated segment starts (int64): 1-D, starts[0] == 0, strictly increasing, every start < T"""
+    st = np.asarray(starts)
+    if st.ndim != 1 or st.size == 0 or st.dtype.kind not in "iu":
+        raise ValueError("segments must be a non-empty 1-D integer array of start indices")
+    st = st.astype(np.int64)
+    if st[0] != 0:
+        raise ValueError("the first segment must start at step 0 (segments[0] = {})".format(st[0]))
+    if np.any(np.diff(st) <= 0):
+        raise ValueError("segment starts must be strictly increasing")
+    if st[-1] >= T:
+        raise ValueError("segment start {} lies beyond the {} time steps".format(st[-1], T))
+    return st
+
+
+def gap_starts(steps):
+    """segment starts of a time axis from its T - 1 steps between consecutive timestamps: a new segment wherever the step is
+    larger than the smallest one (a seasonal selection, concatenated members)"""
+    steps = np.asarray(steps)
+    if steps.size == 0:
+        return np.zeros(1, dtype=np.int64)
+    return np.concatenate([[0], np.nonzero(steps > steps.min())[0] + 1]).astype(np.int64)
+
+
+def track_numpy(anom, wrow, threshold, gorl, overlap, persistence, twosided=True, device=None, segments=None):
     """run_contrack on a (time, lat, lon) numpy slab.  Returns (flag int32 (T,ny,nx), n_tracked).
 
     anom float32 (other dtypes are compared exactly in float64 on the device), wrow float32 (ny,) from
     `row_weights`, threshold scalar, per-timestep vector or a threshold field: a numpy array of ndim >= 2 (last two axes not (1, 1))
     that broadcasts against anom, e.g. (ny, nx) or (T, ny, nx) -- pixel (t, y, x) is compared with its own value, under numpy's
-    promotion rules; gorl in {'>=','<=','>','<','ge','le','gt','lt'}."""
+    promotion rules; gorl in {'>=','<=','>','<','ge','le','gt','lt'}.
+    segments (extension): int array of segment starts (0 first, strictly increasing) -- independent series concatenated in time
+    (ensemble members, seasons); no overlap, filter exemption or 3-D link crosses a break, ids stay unique over the slab."""
     if gorl not in _native.CMP_OPS:
         raise ValueError(_native.GORL_ERRMSG)
     anom = np.asarray(anom)
@@ -135,7 +173,8 @@ def track_numpy(anom, wrow, threshold, gorl, overlap, persistence, twosided=True
         call = lambda t: trk.track(a64, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, f64=True)
     else:
         call = lambda t: trk.track(anom, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided)
-    return call(thr) if field is None else _track_field(trk, field[0], field[1], call)
+    starts = None if segments is None else segment_starts(segments, anom.shape[0])
+    return _track_segments(trk, starts, lambda: call(thr) if field is None else _track_field(trk, field[0], field[1], call))
 
 
 SEASONS = np.array(['DJF', 'DJF', 'MAM', 'MAM', 'MAM', 'JJA', 'JJA', 'JJA', 'SON', 'SON', 'SON', 'DJF'])
@@ -473,6 +512,20 @@ class contrack(object):
             raise ValueError(' '.join(['{} not increasing. This should', 'not happen?!']).format(dim))
         return delta
 
+    def _time_steps(self):
+        """the steps between consecutive timestamps, decoded as _get_resolution decodes the time axis (hours; the numbers
+        themselves for a numeric 'days since' axis)"""
+        dim = self._time_name
+        try:
+            stamps = np.asarray(self.ds[dim].to_index().values)
+            return (stamps[1:] - stamps[:-1]).astype('timedelta64[h]')
+        except AttributeError:
+            attrs = getattr(self.ds[dim], "attrs", {})
+            if 'units' in attrs and 'days' in attrs['units']:
+                var = np.asarray(self.ds[dim].data)
+                return var[1:] - var[:-1]
+            raise ValueError('Can not decode time with unit {}'.format(attrs.get('units')))
+
     def _ensure_set_up(self):
         logger.info("Set up dimensions...")
         if hasattr(self, '_time_name'):
@@ -690,7 +743,7 @@ class contrack(object):
             return prepare_thresholds(values, T, dtype)
         return prepare_thresholds(threshold, T, dtype)
 
-    def run_contrack(self, variable, threshold, gorl, overlap, persistence, twosided=True, chunk_steps=None):
+    def run_contrack(self, variable, threshold, gorl, overlap, persistence, twosided=True, chunk_steps=None, segments=None):
         """Spatial and temporal tracking of closed contours; adds the integer variable 'flag' to the dataset.
 
         variable: name of the input field; threshold: number, 1-D DataArray over 'dayofyear', a threshold field -- a DataArray over
@@ -702,15 +755,38 @@ class contrack(object):
         chunk_steps (extension, not in the reference): stream the variable through the GPU in slices of that many time steps
         (0: about 256 MB each) instead of materialising it on the host and in HBM -- for a lazily loaded netCDF variable
         (xr.open_dataset) each slice is read from the file when its turn comes (`isel(time=slice)`), and the device holds four
-        slices and the bit mask instead of twice the slab.  Same result."""
-        logger.info("\nRun ConTrack \n########### \n    threshold:    {} {} \n    overlap:      {} \n"
-                    "    persistence:  {} time steps".format(gorl, threshold, overlap, persistence))
+        slices and the bit mask instead of twice the slab.  Same result.
+        segments (extension): the time axis as independent series -- None (one series, the reference's behaviour), an int array of
+        segment start indices along time, 'gaps' (a new segment wherever the step to the previous timestamp is larger than the
+        smallest step: a seasonal selection) or the name of an extra dimension of the variable (e.g. 'member': each member is a
+        segment; the threshold is a number, a per-time vector or a 'dayofyear' DataArray, applied to every member).  Every
+        segment is tracked as if alone (no overlap, filter exemption or 3-D link across a break); ids stay unique over the
+        whole result.  Not with chunk_steps."""
+        if segments is not None and chunk_steps is not None:
+            raise ValueError("segments and chunk_steps cannot be combined (the streaming path does not take segment breaks)")
         self._ensure_set_up()
+        da = self.ds[variable]
+        dims = tuple(da.dims)
+        member = segments if isinstance(segments, str) and segments != 'gaps' else None
+        if member is not None:
+            if member not in dims:
+                raise ValueError("segments={!r}: the variable {!r} has no such dimension (dims {})".format(member, variable, dims))
+            if len(dims) != 4:
+                raise ValueError("segments={!r}: the variable must be 4-D ({!r}, time, lat, lon in any order), it has dims {}".format(member, member, dims))
+        T = da.shape[dims.index(self._time_name)]
+        if member is not None:
+            starts = np.arange(da.shape[dims.index(member)], dtype=np.int64) * T
+        elif isinstance(segments, str):
+            starts = gap_starts(self._time_steps())
+        else:
+            starts = None if segments is None else segment_starts(segments, T)
+        nseg = 1 if starts is None else len(starts)
+        logger.info("\nRun ConTrack \n########### \n    threshold:    {} {} \n    overlap:      {} \n"
+                    "    persistence:  {} time steps".format(gorl, threshold, overlap, persistence) +
+                    ("" if segments is None else " \n    segments:     {}".format(nseg)))
         logger.info("Find individual contours...")
         if gorl not in _native.CMP_OPS:
             raise ValueError(_native.GORL_ERRMSG)
-        da = self.ds[variable]
-        dims = tuple(da.dims)
         sort = [dims.index(d) for d in (self._time_name, self._latitude_name, self._longitude_name)]
         lat = self.ds[self._latitude_name].data
         wrow = row_weights(lat, self._dlat, self._dlon)
@@ -723,6 +799,9 @@ class contrack(object):
             # the variable is read slice by slice and passes through chunk-sized device buffers
             flag, n_tracked = self._run_streaming(trk, da, dims, sort, threshold, gorl, wrow, overlap, persistence, twosided, int(chunk_steps))
             slab = None
+        elif member is not None:
+            # (member, time, lat, lon) flattened to (member * time, lat, lon): each member is one segment
+            flag, n_tracked, slab = self._run_members(trk, da, dims, member, starts, threshold, gorl, wrow, overlap, persistence, twosided)
         else:
             slab = np.asarray(da.data).transpose(sort)
             thr, field = self._threshold_args(threshold, da.shape, sort, slab.shape[0], slab.dtype)
@@ -734,7 +813,7 @@ class contrack(object):
             else:
                 call = lambda t: trk.track(np.ascontiguousarray(slab, dtype=np.float64), t, _native.CMP_OPS[gorl], wrow, overlap,
                                            persistence, twosided, f64=True)
-            flag, n_tracked = call(thr) if field is None else _track_field(trk, field[0], field[1], call)
+            flag, n_tracked = _track_segments(trk, starts, lambda: call(thr) if field is None else _track_field(trk, field[0], field[1], call))
         if slab is not None and slab.nbytes > (4 << 30):
             trk.release_io()               # a big one-off slab: do not keep 2 x its size allocated on the GPU
         logger.info("Create new variable 'flag'...")
@@ -743,13 +822,19 @@ class contrack(object):
         # wrap-around); slabs of that size get the reference's dtype here.
         if flag.size >= INT64_FLAG_FROM:
             flag = flag.astype(np.int64)
-        inverse = np.argsort(sort)
         attrs = {'units': 'flag', 'long_name': 'contrack flag', 'standard_name': 'contrack flag',
                  'history': ' '.join(['Calculated from {} with input attributes:', 'threshold = {} {},', 'overlap fraction = {},',
                                       'persistence time steps = {}.', 'twosided = {}']).format(
                      variable, gorl, threshold, overlap, persistence, twosided),
                  'reference': 'https://github.com/steidani/ConTrack'}
-        self.ds['flag'] = (dims, flag.transpose(inverse), attrs)
+        if segments is not None:
+            attrs['history'] += ', segments = {} ({})'.format(segments if isinstance(segments, str) else 'starts', nseg)
+        if member is not None:
+            sort4 = [dims.index(d) for d in (member, self._time_name, self._latitude_name, self._longitude_name)]
+            out = flag.reshape((len(starts), T) + flag.shape[1:]).transpose(np.argsort(sort4))
+        else:
+            out = flag.transpose(np.argsort(sort))
+        self.ds['flag'] = (dims, out, attrs)
         st = _tracker().stats()
         if st.get("off_fused_path_reason", 0):
             # not an error: the result is the same, the call was slower (exact areas / host resolver)
@@ -758,6 +843,28 @@ class contrack(object):
                    4: "{} overlap decisions on rounding boundaries were re-evaluated with numpy-order sums".format(st.get("exact_fixups", 0))}
             logger.info("run_contrack left the fused device path: " + why.get(st["off_fused_path_reason"], "host resolver"))
         logger.info("Running contrack... DONE\n{} contours tracked".format(n_tracked))
+
+    def _run_members(self, trk, da, dims, member, starts, threshold, gorl, wrow, overlap, persistence, twosided):
+        """run_contrack over an extra dimension: the variable transposed to (member, time, lat, lon) and flattened in time, one
+        segment per member; the threshold of each time step applies to every member.  Returns (flag (M*T, ny, nx), n, slab)."""
+        sort4 = [dims.index(d) for d in (member, self._time_name, self._latitude_name, self._longitude_name)]
+        arr = np.asarray(da.data).transpose(sort4)
+        M, T = arr.shape[0], arr.shape[1]
+        slab = np.ascontiguousarray(arr.reshape((M * T,) + arr.shape[2:]), dtype=np.float32 if arr.dtype == np.float32 else np.float64)
+        if hasattr(threshold, "dims") and hasattr(threshold, "data") and np.ndim(threshold.data) >= 2:
+            if 'dayofyear' not in threshold.dims:
+                raise ValueError("a threshold with dims {} has no 'dayofyear' dimension".format(tuple(threshold.dims)))
+            planes, pos = self._doy_field(threshold)
+            thr, field = None, (planes, np.tile(pos, M))
+        elif is_threshold_field(threshold):
+            raise ValueError("segments={!r}: a numpy threshold field cannot be combined with a member dimension; give a number, a "
+                             "per-time vector or a 'dayofyear' DataArray".format(member))
+        else:
+            thr, field = np.tile(self._thresholds_per_step(threshold, T, slab.dtype), M), None
+        f64 = slab.dtype == np.float64
+        call = lambda t: trk.track(slab, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, f64=f64)
+        flag, n = _track_segments(trk, starts, lambda: call(thr) if field is None else _track_field(trk, field[0], field[1], call))
+        return flag, n, slab
 
     def _run_streaming(self, trk, da, dims, sort, threshold, gorl, wrow, overlap, persistence, twosided, chunk_steps):
         """run_contrack with the variable read slice by slice"""

@@ -28,7 +28,7 @@
 int ctk_set_error(int code, const char *fmt, ...);            // ctk_resolve.cpp
 extern "C" int ctk_weights_to_limbs(const float *wrow, int ny, int64_t npix, int64_t *wlo, int64_t *whi, int32_t *wshift, int32_t *limb_bits);
 int ctk_resolve_ex(const void *const *blobs, const size_t *nbytes, int nshards, double overlap, int twosided, CtkExactAreas *exact,
-                   ctk_result **out);                              // ctk_resolve.cpp
+                   ctk_result **out, const uint8_t *seg_edge = nullptr);       // ctk_resolve.cpp
 double ctk_np_sum(const double *a, size_t n);
 
 #define HIPCHK(expr)                                                                                          \
@@ -330,6 +330,14 @@ struct ctk_handle {
     int fld_prep_op = -1;                        // op fld_f32 was prepared for (-1: not prepared)
     int64_t fld_order_chunk = -1;                // chunk length the order in fld_order was built for (steps sorted by plane inside each chunk)
     std::vector<int32_t> fld_pos_host, fld_order_host;
+    // segment breaks (ctk_set_segments): the starts as given (empty: none), the per-step edge table of the last T it was built for
+    // (bit 0 first step of a segment, bit 1 last step; host copy for the host resolver) and, during a one-call track, the device
+    // table the filter and overlap launches take (nullptr: no segments -- the unsegmented kernels)
+    std::vector<int64_t> seg_starts;
+    DevBuf seg_edge;
+    std::vector<uint8_t> seg_edge_host;
+    int64_t seg_edge_T = -1;
+    const uint8_t *seg_cur = nullptr;
     // blocking frequency (ctk_freq.hip): counts of the host entries, group ids; experiments (ctk_debug_set_freq)
     DevBuf fq_counts, fq_group;
     int64_t fq_slice_dbg = 0; int fq_nt = -1;
@@ -578,7 +586,7 @@ extern "C" void ctk_destroy(ctk_handle *h)
                       &h->lc_rows, &h->lc_cnt, &h->lc_wlo, &h->lc_whi, &h->lc_w, &h->rv_dmap, &h->rv_dorig, &h->rv_dbox, &h->rv_inex, &h->rv_touch, &h->io_in, &h->io_out,
                       &h->sh_mask_next, &h->sh_send, &h->sh_recv, &h->sh_prev, &h->sh_elist, &h->sh_ovr_slot, &h->sh_ovr_val,
                       &h->sh_amb_list, &h->sh_counts, &h->sh_cl_shared, &h->sh_cl_sent, &h->chunk_vals, &h->lc_work, &h->lc_ovf, &h->lc_ekeys, &h->lc_offs, &h->lc_sw, &h->lc_sp, &h->lc_out, &h->lc_cross, &h->lc_gtab, &h->lc_occ, &h->lc_cp, &h->an_out, &h->an_clim, &h->an_raw, &h->an_idx, &h->sd_parent, &h->sd_tmin, &h->sd_tmax, &h->sd_root, &h->sd_nops, &h->sd_lbox, &h->rv_pstate, &h->ci_bsum, &h->scan_bsum,
-                      &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order, &h->fq_counts, &h->fq_group};
+                      &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order, &h->fq_counts, &h->fq_group, &h->seg_edge};
     for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->base ? b->base : b->p);
     if (h->h_blob) (void)hipHostFree(h->h_blob);
     if (h->h_small) (void)hipHostFree(h->h_small);
@@ -905,6 +913,50 @@ extern "C" int ctk_set_threshold_field(ctk_handle *h, const void *field, int ele
     if (T > 0) HIPCHK(hipMemcpy(h->fld_pos.p, plane_of_step, (size_t)T * 4, hipMemcpyHostToDevice));
     h->fld_pos_host.assign(plane_of_step, plane_of_step + T);
     h->fld_T = T; h->fld_np = nplanes; h->fld_ny = ny; h->fld_nx = nx; h->fld_esz = elem_bytes;
+    return CTK_OK;
+}
+
+// Segment breaks for the following track calls (include/contrack_hip.h).  The starts are kept; the per-step edge table is built on
+// the device by the first call of a given T (segment_table) and reused while T stays the same.
+extern "C" int ctk_set_segments(ctk_handle *h, const int64_t *starts, int64_t nseg)
+{
+    if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
+    if (nseg < 0 || (nseg > 0 && !starts)) return ctk_set_error(CTK_E_INVALID, "ctk_set_segments: bad arguments (nseg=%lld)", (long long)nseg);
+    if (nseg > 0) {
+        if (starts[0] != 0) return ctk_set_error(CTK_E_INVALID, "ctk_set_segments: starts[0] = %lld, must be 0", (long long)starts[0]);
+        for (int64_t k = 1; k < nseg; k++)
+            if (starts[k] <= starts[k - 1])
+                return ctk_set_error(CTK_E_INVALID, "ctk_set_segments: starts must be strictly increasing (starts[%lld] = %lld after %lld)", (long long)k,
+                                     (long long)starts[k], (long long)starts[k - 1]);
+        if (starts[nseg - 1] > 0x7ffffffell) return ctk_set_error(CTK_E_RANGE, "ctk_set_segments: start %lld beyond int32 timesteps", (long long)starts[nseg - 1]);
+    }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));                  // nothing in flight reads the old table
+    h->seg_starts.assign(starts, starts + nseg);
+    h->seg_edge_T = -1;
+    h->seg_edge_host.clear();
+    return CTK_OK;
+}
+
+// The edge table of the segments for a slab of T steps (T > the last start): bit 0 = first step of a segment, bit 1 = last step.
+static int segment_table(ctk_handle *h, int64_t T)
+{
+    const std::vector<int64_t> &st = h->seg_starts;
+    if (T <= st.back())
+        return ctk_set_error(CTK_E_INVALID, "ctk_track: the last segment starts at step %lld, the slab has %lld steps", (long long)st.back(), (long long)T);
+    if (h->seg_edge_T != T) {
+        std::vector<uint8_t> &e = h->seg_edge_host;
+        e.assign((size_t)T, 0);
+        for (size_t k = 0; k < st.size(); k++) {
+            e[(size_t)st[k]] |= 1u;
+            if (st[k] > 0) e[(size_t)st[k] - 1] |= 2u;
+        }
+        e[(size_t)T - 1] |= 2u;
+        CTKCHK(ensure(h, h->seg_edge, (size_t)T));
+        HIPCHK(hipMemcpy(h->seg_edge.p, e.data(), (size_t)T, hipMemcpyHostToDevice));
+        h->seg_edge_T = T;
+    }
+    h->seg_cur = P<uint8_t>(h->seg_edge);
     return CTK_OK;
 }
 
@@ -1452,12 +1504,14 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
 extern "C" int ctk_shard_label2d(ctk_handle *h, const float *anom_dev, int64_t T, int ny, int nx, const double *thr, int cmp_op,
                                  const float *wrow, int has_prev)
 {
+    if (h && !h->seg_starts.empty()) return ctk_set_error(CTK_E_INVALID, "ctk_shard_label2d: segments are set on this handle (ctk_set_segments); the staged entries do not take them");
     if (h && T > 0 && !thr) return ctk_set_error(CTK_E_INVALID, "ctk_shard_label2d: thr is NULL (the staged entries take per-step thresholds, not a threshold field)");
     return shard_label2d_impl(h, anom_dev, false, T, ny, nx, thr, cmp_op, wrow, has_prev);
 }
 extern "C" int ctk_shard_label2d_f64(ctk_handle *h, const double *anom_dev, int64_t T, int ny, int nx, const double *thr, int cmp_op,
                                      const float *wrow, int has_prev)
 {
+    if (h && !h->seg_starts.empty()) return ctk_set_error(CTK_E_INVALID, "ctk_shard_label2d_f64: segments are set on this handle (ctk_set_segments); the staged entries do not take them");
     if (h && T > 0 && !thr) return ctk_set_error(CTK_E_INVALID, "ctk_shard_label2d_f64: thr is NULL (the staged entries take per-step thresholds, not a threshold field)");
     return shard_label2d_impl(h, anom_dev, true, T, ny, nx, thr, cmp_op, wrow, has_prev);
 }
@@ -1563,12 +1617,22 @@ static int launch_overlap(ctk_handle *h)
         static const int ov_small = getenv("CTK_OVERLAP_SMALL") ? atoi(getenv("CTK_OVERLAP_SMALL")) : -1;
         // (small planes in long shards: room for five waves per SIMD -- 96 VGPRs, 14 of the 105 in scratch -- 3.49 -> 3.05 ms at 438 000 x 192 x 288;
         // at 2707 x 181 x 360, one round of latency chains, the same costs <5, 256> ten of its 36 us: only here)
-        if (ov_small == 1 || (ov_small < 0 && h->T > 65536 && nwords <= 2048)) k_overlap<4, 128, 5><<<(int)h->T, 128, 0, h->stream>>>(a);
-        else if (h->T <= 1024 && nwords >= 8192) k_overlap<4, 512><<<(int)h->T, 512, 0, h->stream>>>(a);
-        else if (per <= 4 || per > 8) k_overlap<4><<<(int)h->T, 256, 0, h->stream>>>(a);
-        else if (per == 5) k_overlap<5><<<(int)h->T, 256, 0, h->stream>>>(a);
-        else if (per == 6) k_overlap<6><<<(int)h->T, 256, 0, h->stream>>>(a);
-        else k_overlap<8><<<(int)h->T, 256, 0, h->stream>>>(a);
+        // (segment breaks: the SEG builds, which read the edge table)
+        OverlapArgsSeg as;
+        static_cast<OverlapArgs &>(as) = a;
+        as.seg_edge = h->seg_cur;
+#define CTK_OVERLAP(OVB, TH, WPE)                                                                        \
+        do {                                                                                             \
+            if (as.seg_edge) k_overlap<OVB, TH, WPE, true><<<(int)h->T, TH, 0, h->stream>>>(as);         \
+            else k_overlap<OVB, TH, WPE><<<(int)h->T, TH, 0, h->stream>>>(a);                            \
+        } while (0)
+        if (ov_small == 1 || (ov_small < 0 && h->T > 65536 && nwords <= 2048)) CTK_OVERLAP(4, 128, 5);
+        else if (h->T <= 1024 && nwords >= 8192) CTK_OVERLAP(4, 512, 1);
+        else if (per <= 4 || per > 8) CTK_OVERLAP(4, 256, 1);
+        else if (per == 5) CTK_OVERLAP(5, 256, 1);
+        else if (per == 6) CTK_OVERLAP(6, 256, 1);
+        else CTK_OVERLAP(8, 256, 1);
+#undef CTK_OVERLAP
     }
     HIPCHK(hipGetLastError());
     return CTK_OK;
@@ -1835,6 +1899,33 @@ struct ResolveIn {
     size_t extra_dense = 0;                      // dense label ids beyond those of candidate records (time shards)
 };
 
+// Filter launches: with segment breaks (h->seg_cur) the SEG builds, which never filter the first and last step of a segment;
+// else the SEG = false builds, the kernels the unsegmented call has always launched.
+static void launch_rs_pass(const ctk_handle *h, int grid, const ResolveDev &r, int it, const uint32_t *pair_base, const uint32_t *pair_cnt, uint8_t *tdirty)
+{
+    if (h->seg_cur) k_rs_pass<true><<<grid, 64, 0, h->stream>>>(r, it, pair_base, pair_cnt, tdirty, h->seg_cur);
+    else k_rs_pass<false><<<grid, 64, 0, h->stream>>>(r, it, pair_base, pair_cnt, tdirty, nullptr);
+}
+static void launch_rs_pass_sys(const ctk_handle *h, int grid, const ResolveDev &r, int it0, int K, const uint32_t *pair_base, const uint32_t *pair_cnt,
+                               uint32_t *pstate, int prep_inline, int do_unite)
+{
+    if (h->seg_cur) k_rs_pass_sys<true><<<grid, 64, 0, h->stream>>>(r, it0, K, pair_base, pair_cnt, pstate, prep_inline, do_unite, h->seg_cur);
+    else k_rs_pass_sys<false><<<grid, 64, 0, h->stream>>>(r, it0, K, pair_base, pair_cnt, pstate, prep_inline, do_unite, nullptr);
+}
+// two_pc: the build with two workgroups per CU (k_rs_pass_blk_2pc)
+static void launch_rs_pass_blk(const ctk_handle *h, bool two_pc, int nb, const ResolveDev &r, int it0, int K, const uint32_t *pair_base, const uint32_t *pair_cnt,
+                               uint32_t *pstate, int prep_inline, int do_unite)
+{
+    hipStream_t s = h->stream;
+    if (h->seg_cur) {
+        if (two_pc) k_rs_pass_blk_2pc<true><<<nb, 64 * PB_G, 0, s>>>(r, it0, K, pair_base, pair_cnt, pstate, prep_inline, do_unite, h->seg_cur);
+        else k_rs_pass_blk<true><<<nb, 64 * PB_G, 0, s>>>(r, it0, K, pair_base, pair_cnt, pstate, prep_inline, do_unite, h->seg_cur);
+    } else {
+        if (two_pc) k_rs_pass_blk_2pc<false><<<nb, 64 * PB_G, 0, s>>>(r, it0, K, pair_base, pair_cnt, pstate, prep_inline, do_unite, nullptr);
+        else k_rs_pass_blk<false><<<nb, 64 * PB_G, 0, s>>>(r, it0, K, pair_base, pair_cnt, pstate, prep_inline, do_unite, nullptr);
+    }
+}
+
 // returns CTK_OK, a negative error, or +1 = "take the host path" (pair table overflow / filter not converged)
 // work space + kernel argument block of the resolver kernels for the tables `in`
 struct ResolvePlan {
@@ -1934,7 +2025,7 @@ static int device_resolve(ctk_handle *h, const ResolveIn &in, double overlap, in
         // overlap filter: a round of passes (passes after the fixed point return at once)
         if (T > 2)
             for (int it = it_done; it < it_done + ROUND; it++)
-                k_rs_pass<<<(int)(T - 2), 64, 0, s>>>(r, it, in.pair_base, in.pair_cnt, P<uint8_t>(h->rv_tdirty));        // t_lo = 1 .. t_hi = T-2
+                launch_rs_pass(h, (int)(T - 2), r, it, in.pair_base, in.pair_cnt, P<uint8_t>(h->rv_tdirty));        // t_lo = 1 .. t_hi = T-2
         it_done += ROUND;
         if (it_done > ROUND) k_rs_parent_init<<<gc, 256, 0, s>>>(r);          // the first round's parents were set by k_rs_init
         k_rs_unite<<<gp, 256, 0, s>>>(r);
@@ -2409,13 +2500,12 @@ static int resolve_async(ctk_handle *h, double overlap, int twosided, int persis
         static const bool pass_blk = !getenv("CTK_PASS_SYS");           // (the one-wave-per-workgroup form, for comparison)
         if (sys && NP > 0 && pass_blk) {
             const int nb = (int)((T - 1 + PB_G - 1) / PB_G);
-            if (nb > h->n_cus) k_rs_pass_blk_2pc<<<nb, 64 * PB_G, 0, s>>>(r, 0, NP, in.pair_base, in.pair_cnt, r.pstate, 1, 1);      // (two workgroups per CU: ctk_resolve_dev.hip)
-            else k_rs_pass_blk<<<nb, 64 * PB_G, 0, s>>>(r, 0, NP, in.pair_base, in.pair_cnt, r.pstate, 1, 1);
+            launch_rs_pass_blk(h, nb > h->n_cus, nb, r, 0, NP, in.pair_base, in.pair_cnt, r.pstate, 1, 1);      // (two workgroups per CU when nb > CUs: ctk_resolve_dev.hip)
         }
-        else if (sys && NP > 0) k_rs_pass_sys<<<(int)(T - 1), 64, 0, s>>>(r, 0, NP, in.pair_base, in.pair_cnt, r.pstate, 1, 1);
+        else if (sys && NP > 0) launch_rs_pass_sys(h, (int)(T - 1), r, 0, NP, in.pair_base, in.pair_cnt, r.pstate, 1, 1);
         else
             for (int it = 0; it < NP; it++)
-                k_rs_pass<<<(int)(T - 2), 64, 0, s>>>(r, it, in.pair_base, in.pair_cnt, P<uint8_t>(h->rv_tdirty));
+                launch_rs_pass(h, (int)(T - 2), r, it, in.pair_base, in.pair_cnt, P<uint8_t>(h->rv_tdirty));
         if (sys && NP > 0) { /* united by k_rs_pass_sys */ }
         else if (h->fz_pslot) k_rs_unite_slots<<<(int)std::min<int64_t>((T * h->fz_pslot + 255) / 256 + 1, 4096), 256, 0, s>>>(r, in.pair_cnt, h->fz_pslot);
         else k_rs_unite<<<gp, 256, 0, s>>>(r);
@@ -2592,7 +2682,11 @@ static int track_dev_impl(ctk_handle *h, const void *anom_dev, bool f64, int64_t
     const double t0 = now_ms();
     HT0();
     h->in_one_call = true;
-    struct OneCall { ctk_handle *h; ~OneCall() { h->in_one_call = false; } } one_call{h};
+    struct OneCall { ctk_handle *h; ~OneCall() { h->in_one_call = false; h->seg_cur = nullptr; } } one_call{h};
+    if (!h->seg_starts.empty()) {
+        HIPCHK(hipSetDevice(h->device));
+        CTKCHK(segment_table(h, T));
+    }
     CTKCHK(shard_label2d_impl(h, anom_dev, f64, T, ny, nx, thr, cmp_op, wrow, 0));
     HT("label2d stage done");
     CTKCHK(ctk_shard_overlap(h));
@@ -2638,7 +2732,7 @@ static int track_dev_impl(ctk_handle *h, const void *anom_dev, bool f64, int64_t
         const double t1 = now_ms();
         ctk_result *res = nullptr;
         ExactFromDevice exact(h);                                 // numpy-order sums for decisions flagged ambiguous
-        CTKCHK(ctk_resolve_ex(&blob, &nbytes, 1, overlap, twosided, &exact, &res));
+        CTKCHK(ctk_resolve_ex(&blob, &nbytes, 1, overlap, twosided, &exact, &res, h->seg_cur ? h->seg_edge_host.data() : nullptr));
         h->ms[CTK_T_HOST_RESOLVE] += now_ms() - t1;
         h->stats[CTK_S_AMBIGUOUS] = res->n_ambiguous;
         h->stats[CTK_S_EXACT_FIXUPS] = res->n_exact;
@@ -3144,6 +3238,7 @@ static int track_stream_impl(ctk_handle *h, StreamIO &io, bool f64, int64_t T, i
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
     if (T < 0 || ny < 1 || nx < 1 || chunk_steps < 0) return ctk_set_error(CTK_E_INVALID, "ctk_track_stream: bad shape");
+    if (!h->seg_starts.empty()) return ctk_set_error(CTK_E_INVALID, "ctk_track_stream: segments are set on this handle (ctk_set_segments); the streaming entries do not take them");
     if (T > 0 && ((!io.host_in && !io.read) || (!io.host_out && !io.write))) return ctk_set_error(CTK_E_INVALID, "ctk_track_stream: no source or no sink");
     HIPCHK(hipSetDevice(h->device));
     io.esz = f64 ? 8 : 4;

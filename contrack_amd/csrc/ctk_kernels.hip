@@ -1324,6 +1324,17 @@ struct OverlapArgs {
     uint32_t pslot;
     uint32_t upair_cap;            // ungrouped records the end of the buffer may hold
 };
+// the arguments of the SEG build (segment breaks, ctk_set_segments): seg_edge[t] bit 0 = t is the first step of a segment.  A type of
+// its own, so that the unsegmented build keeps its argument block.
+struct OverlapArgsSeg : OverlapArgs {
+    const uint8_t *seg_edge;
+};
+template <bool SEG, typename A>
+__device__ __forceinline__ bool seg_first(const A &a, int t)
+{
+    if constexpr (SEG) return (a.seg_edge[t] & 1u) != 0;
+    else return false;
+}
 
 __device__ __forceinline__ void pair_prepare(const OverlapArgs &a, uint32_t slot, uint32_t cb, uint32_t db, uint32_t c, uint32_t d, int64_t lo, int64_t hi)
 {
@@ -1349,11 +1360,13 @@ __device__ __forceinline__ void emit_pair(const OverlapArgs &a, uint32_t t, uint
 // 181 x 360: five per thread; with four a second step ran for the last 62 words)
 // THREADS: 256, or 1024 when the timesteps alone leave the chip empty (480 x 721 x 1440: 16 steps of three round trips per plane
 // with 256 threads, 4 with 1024)
-template <int OVB, int THREADS = 256, int WPE = 1 /* waves per SIMD the compiler has to make room for (experiment: occupancy against spills) */>
-__global__ __launch_bounds__(THREADS, WPE) void k_overlap(OverlapArgs a)
+// SEG: segment breaks.  The first step of a segment is treated like t == 0 without a halo: no predecessor, no records -- so no overlap,
+// forward or backward, and no 3-D link across the break.  The unsegmented call launches SEG = false, whose code is what it was.
+template <int OVB, int THREADS = 256, int WPE = 1 /* waves per SIMD the compiler has to make room for (experiment: occupancy against spills) */, bool SEG = false>
+__global__ __launch_bounds__(THREADS, WPE) void k_overlap(std::conditional_t<SEG, OverlapArgsSeg, OverlapArgs> a)
 {
     const int t = (int)blockIdx.x;
-    if (t == 0 && !a.has_prev) {
+    if ((t == 0 && !a.has_prev) || (SEG && seg_first<SEG>(a, t))) {
         if (threadIdx.x == 0) { a.pair_base[t] = 0; a.pair_cnt[t] = 0; }
         return;
     }

@@ -156,8 +156,9 @@ double ctk_np_sum(const double *a, size_t n)
     return res;
 }
 
+// seg_edge (nullptr: none): T flags, nonzero = the step is the first or last of a segment (ctk_set_segments) and is not filtered
 int ctk_resolve_ex(const void *const *blobs, const size_t *nbytes, int nshards, double overlap, int twosided, CtkExactAreas *exact,
-                   ctk_result **out);
+                   ctk_result **out, const uint8_t *seg_edge = nullptr);
 
 // test hook (GPU-free): the numpy-order sum used for decisions on rounded area sums
 extern "C" double ctk_debug_np_sum(const double *a, size_t n) { return ctk_np_sum(a, n); }
@@ -169,7 +170,7 @@ extern "C" int ctk_resolve(const void *const *blobs, const size_t *nbytes, int n
 }
 
 int ctk_resolve_ex(const void *const *blobs, const size_t *nbytes, int nshards, double overlap, int twosided, CtkExactAreas *exact,
-                   ctk_result **out)
+                   ctk_result **out, const uint8_t *seg_edge)
 {
     if (!blobs || !nbytes || nshards <= 0 || !out) return ctk_set_error(CTK_E_INVALID, "ctk_resolve: bad arguments");
     *out = nullptr;
@@ -282,6 +283,7 @@ int ctk_resolve_ex(const void *const *blobs, const size_t *nbytes, int nshards, 
         int64_t n_ambiguous = 0, n_exact_fixups = 0;
         auto rep_of = [&](int64_t t, uint32_t c) { return coff[(size_t)t] + mrep[(size_t)(coff[(size_t)t] + c)]; };
         for (int64_t t = 1; t < T - 1; t++) {
+            if (seg_edge && seg_edge[t]) continue;          // first / last step of a segment: not filtered (its range(1, T-1))
             // backward overlap: co-occurrences with components of t-1 that SURVIVED the filter (contrack.py:719)
             for (int64_t k = poff[(size_t)t]; k < poff[(size_t)t + 1]; k++) {
                 const CtkPair &p = pairs[(size_t)k];

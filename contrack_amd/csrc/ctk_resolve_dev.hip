@@ -294,8 +294,12 @@ __global__ void k_rs_prep(ResolveDev r)
 // The workgroup's work is a chain of dependent loads; independent ones are issued together (three global-memory
 // round trips instead of nine): [everything indexed by t] -> [pair records and component constants of the first 64
 // pairs / components] -> [keep bits of the pairs' predecessors].
+// SEG (segment breaks, ctk_set_segments): a timestep with seg_edge[t] != 0 is the first or the last step of a segment and is not
+// filtered (contrack.py:706, range(1, T-1) of each segment): its keep bits stay 1 and it reports "unchanged".  seg_edge is read by the
+// SEG = true builds only; the unsegmented call launches SEG = false (k_rs_pass, k_rs_pass_sys, k_rs_pass_blk*), code as it was.
+template <bool SEG>
 __global__ __launch_bounds__(64) void k_rs_pass(ResolveDev r, int it, const uint32_t *__restrict__ pair_base, const uint32_t *__restrict__ pair_cnt,
-                                                uint8_t *__restrict__ tdirty)
+                                                uint8_t *__restrict__ tdirty, const uint8_t *__restrict__ seg_edge)
 {
     if (dev_tables_bad(r)) return;
     const int t = (int)blockIdx.x + r.t_lo;                    // one slab: timesteps 1 .. T-2 are filtered
@@ -310,7 +314,7 @@ __global__ __launch_bounds__(64) void k_rs_pass(ResolveDev r, int it, const uint
     const uint32_t pb = pair_base[t], pn = pair_cnt[t];
     const uint32_t nu = dev_nungrouped(r);
     if (ch_prev == 0) return;                                  // fixed point reached in an earlier pass
-    if (!d_prev) { if (lane == 0) dcur[t] = 0; return; }
+    if (!d_prev || (SEG && seg_edge[t])) { if (lane == 0) dcur[t] = 0; return; }
     const uint32_t nct = ce - cb;
     __shared__ long long Bl[2 * CTK_PASS_COMPS];
     const bool lds = nct <= CTK_PASS_COMPS;
@@ -418,9 +422,11 @@ __global__ __launch_bounds__(64) void k_rs_pass(ResolveDev r, int it, const uint
 // iteration whose predecessor did not change in the previous one does nothing but publish its word.  K <= 24.
 // changed[] (per pass, read by the host / the mailbox) is kept as k_rs_pass keeps it.
 // ------------------------------------------------------------------------------------------------
+template <bool SEG>
 __global__ __launch_bounds__(64) void k_rs_pass_sys(ResolveDev r, int it0, int K, const uint32_t *__restrict__ pair_base, const uint32_t *__restrict__ pair_cnt,
                                                     uint32_t *__restrict__ pstate /* [T + 1], zeroed */, int prep_inline /* k_rs_prep's work for this timestep first */,
-                                                    int do_unite /* k_rs_unite's work for the pairs of this timestep last; the grid then also covers t_hi + 1 .. T - 1 */)
+                                                    int do_unite /* k_rs_unite's work for the pairs of this timestep last; the grid then also covers t_hi + 1 .. T - 1 */,
+                                                    const uint8_t *__restrict__ seg_edge)
 {
     if (dev_tables_bad(r)) return;
     const int Kfull = K;
@@ -433,6 +439,7 @@ __global__ __launch_bounds__(64) void k_rs_pass_sys(ResolveDev r, int it0, int K
     const uint32_t nct = ce - cb;
     const bool filtered = t <= r.t_hi;                     // (workgroups behind t_hi only unite their pairs)
     if (!filtered) K = 0;
+    const bool seg_keep = SEG && filtered && seg_edge[t];  // first / last step of a segment: publishes its iterations, never evaluates
     __shared__ long long Bl[2 * CTK_PASS_COMPS];
     const bool lds = nct <= CTK_PASS_COMPS;
     long long *B = lds ? Bl : (long long *)(r.B + 2 * (int64_t)cb);
@@ -476,6 +483,7 @@ __global__ __launch_bounds__(64) void k_rs_pass_sys(ResolveDev r, int it0, int K
             evaluate = (st >> (k - 1)) & 1u;
         }
         bool wave_any = false;
+        if (SEG && seg_keep) evaluate = false;
         if (evaluate) {
             if (lds) for (uint32_t c = lane; c < 2 * nct; c += 64) Bl[c] = 0;
             const uint8_t kd0 = has_p ? __hip_atomic_load(&keep[rd0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (uint8_t)0;
@@ -618,8 +626,10 @@ __device__ unsigned long long g_pb_t[4 * 1024];      // per workgroup: first ent
 #define PB_MARK_MIN(k) do { } while (0)
 #define PB_MARK_MAX(k) do { } while (0)
 #endif
+template <bool SEG>
 __device__ __forceinline__ void rs_pass_blk_body(const ResolveDev &r, int it0, int K, const uint32_t *__restrict__ pair_base, const uint32_t *__restrict__ pair_cnt,
-                                                 uint32_t *__restrict__ pstate /* [T + 1], zeroed */, int prep_inline, int do_unite)
+                                                 uint32_t *__restrict__ pstate /* [T + 1], zeroed */, int prep_inline, int do_unite,
+                                                 const uint8_t *__restrict__ seg_edge)
 {
     if (dev_tables_bad(r)) return;
     __shared__ long long Bl_all[PB_G][2 * PB_COMPS];
@@ -641,6 +651,7 @@ __device__ __forceinline__ void rs_pass_blk_body(const ResolveDev &r, int it0, i
     const uint32_t nct = ce - cb;
     const bool filtered = live && t <= r.t_hi;                 // (waves behind t_hi only unite their pairs)
     if (!filtered) K = 0;
+    const bool seg_keep = SEG && filtered && seg_edge[t];      // first / last step of a segment: publishes its iterations, never evaluates
     const bool lds = nct <= PB_COMPS;
     long long *B = lds ? Bl : (long long *)(r.B + 2 * (int64_t)cb);
     // the predecessor's bits and word: through LDS if it is a wave of this workgroup and its components fit there
@@ -715,6 +726,7 @@ __device__ __forceinline__ void rs_pass_blk_body(const ResolveDev &r, int it0, i
             evaluate = (st >> (k - 1)) & 1u;
         }
         bool wave_any = false;
+        if (SEG && seg_keep) evaluate = false;
         if (evaluate) {
             if (lds) for (uint32_t c = lane; c < 2 * nct; c += 64) Bl[c] = 0;
             const uint8_t kd0 = has_p ? pred_keep(rd0) : (uint8_t)0;
@@ -842,15 +854,17 @@ __device__ __forceinline__ void rs_pass_blk_body(const ResolveDev &r, int it0, i
 // instead of two (CTK_SGPR_8WAVES, ctk_kernels.hip) -- that is the build for launches with more workgroups than CUs (438 000 x 192 x 288: 2.5 ->
 // 1.9 ms).  A launch that leaves CUs empty anyway (2707 steps: 170 workgroups) is one chain per workgroup, and the ~110 values the limit moves
 // into VGPR lanes sit in that chain: 29.8 -> 32.6 us; it keeps all its SGPRs.
+template <bool SEG>
 __global__ __launch_bounds__(64 * PB_G) void k_rs_pass_blk(ResolveDev r, int it0, int K, const uint32_t *__restrict__ pair_base, const uint32_t *__restrict__ pair_cnt,
-                                                           uint32_t *__restrict__ pstate, int prep_inline, int do_unite)
+                                                           uint32_t *__restrict__ pstate, int prep_inline, int do_unite, const uint8_t *__restrict__ seg_edge)
 {
-    rs_pass_blk_body(r, it0, K, pair_base, pair_cnt, pstate, prep_inline, do_unite);
+    rs_pass_blk_body<SEG>(r, it0, K, pair_base, pair_cnt, pstate, prep_inline, do_unite, seg_edge);
 }
+template <bool SEG>
 __global__ __launch_bounds__(64 * PB_G) CTK_SGPR_8WAVES void k_rs_pass_blk_2pc(ResolveDev r, int it0, int K, const uint32_t *__restrict__ pair_base, const uint32_t *__restrict__ pair_cnt,
-                                                                               uint32_t *__restrict__ pstate, int prep_inline, int do_unite)
+                                                                               uint32_t *__restrict__ pstate, int prep_inline, int do_unite, const uint8_t *__restrict__ seg_edge)
 {
-    rs_pass_blk_body(r, it0, K, pair_base, pair_cnt, pstate, prep_inline, do_unite);
+    rs_pass_blk_body<SEG>(r, it0, K, pair_base, pair_cnt, pstate, prep_inline, do_unite, seg_edge);
 }
 
 __global__ void k_rs_unite(ResolveDev r)

@@ -1096,14 +1096,13 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
                     // previous round's k_sh_unpack_keep); with `spec` also the 3-D unions of the surviving pairs
                     if (spec && parent_dirty) k_rs_parent_init<<<gc, 256, 0, s>>>(r);
                     const int nb = (int)((T - r.t_lo + PB_G - 1) / PB_G);
-                    if (nb > h->n_cus) k_rs_pass_blk_2pc<<<nb, 64 * PB_G, 0, s>>>(r, it_done, npass, in.pair_base, in.pair_cnt, r.pstate, prepped ? 0 : 1, spec ? 1 : 0);
-                    else k_rs_pass_blk<<<nb, 64 * PB_G, 0, s>>>(r, it_done, npass, in.pair_base, in.pair_cnt, r.pstate, prepped ? 0 : 1, spec ? 1 : 0);
+                    launch_rs_pass_blk(h, nb > h->n_cus, nb, r, it_done, npass, in.pair_base, in.pair_cnt, r.pstate, prepped ? 0 : 1, spec ? 1 : 0);
                     united = spec;
                     prepped = true;
                 } else {
                     if (!prepped) { k_rs_prep<<<gc, 256, 0, s>>>(r); prepped = true; }
                     for (int it = it_done; it < it_done + npass; it++)
-                        k_rs_pass<<<npass_grid, 64, 0, s>>>(r, it, in.pair_base, in.pair_cnt, P<uint8_t>(h->rv_tdirty));
+                        launch_rs_pass(h, npass_grid, r, it, in.pair_base, in.pair_cnt, P<uint8_t>(h->rv_tdirty));
                 }
             }
             HIPCHK(hipGetLastError());
@@ -1606,8 +1605,11 @@ static int track_sharded_entry(ctk_handle *h, ctk_comm *c, const void *anom_dev,
                                int64_t *n_tracked)
 {
     if (h) h->sh_collective_err = false;
-    // (a threshold field, ctk_set_threshold_field, is not taken here: thr == NULL is refused like any other null argument)
-    const int rc = (h && T_local > 0 && !thr)
+    // (a threshold field, ctk_set_threshold_field, is not taken here: thr == NULL is refused like any other null argument; nor are
+    // segment breaks, ctk_set_segments)
+    const int rc = (h && !h->seg_starts.empty())
+        ? ctk_set_error(CTK_E_INVALID, "ctk_track_sharded: segments are set on this handle (ctk_set_segments); the time-shard entries do not take them")
+        : (h && T_local > 0 && !thr)
         ? ctk_set_error(CTK_E_INVALID, "ctk_track_sharded: thr is NULL (the time-shard entries take per-step thresholds, not a threshold field)")
         : track_sharded_impl(h, c, anom_dev, f64, T_local, t_begin, T_total, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, flag_dev, n_tracked);
     if (rc != CTK_OK && c && h && !h->sh_collective_err) {

@@ -78,6 +78,21 @@ int ctk_track_f32_dev(ctk_handle *h, const float *anom_dev, int64_t T, int ny, i
 int ctk_set_threshold_field(ctk_handle *h, const void *field, int elem_bytes, int64_t nplanes, int ny, int nx,
                             const int32_t *plane_of_step, int64_t T);
 
+/* Segment breaks for the following track calls on this handle: the time axis is K independent series (ensemble members concatenated
+ * in time, a seasonal selection with gaps).  starts[0] = 0 < starts[1] < ... < starts[nseg-1]; segment k is the steps
+ * [starts[k], starts[k+1]) (the last one ends at T).  starts == NULL or nseg == 0 clears them.  Sticky, like the threshold field.
+ * At a break the pass changes three things and nothing else:
+ *   - no overlap pairs between the two planes (the first step of a segment has no predecessor, as t = 0 has);
+ *   - the first and the last step of every segment are exempt from the overlap filter (contrack.py:706-742, range(1, T-1) of
+ *     each segment), so their components are kept whatever twosided says;
+ *   - no 3-D connection across it (contrack.py:747-751).
+ * So each segment's ids minus an offset equal, bit for bit, run_contrack on that segment alone; ids are unique over the slab and keep
+ * scipy's raster numbering (the offset of segment k is the number of 3-D components of segments 0 .. k-1); persistence counts
+ * inside a segment; n_tracked is len(np.unique(flag)) - 1 of the whole result.  starts == {0} gives today's result.
+ * Taken by the host, _dev and resident entries (with or without a threshold field).  A call whose T <= starts[nseg-1] returns
+ * CTK_E_INVALID; the streaming, staged and time-shard entries return CTK_E_INVALID while segments are set. */
+int ctk_set_segments(ctk_handle *h, const int64_t *starts, int64_t nseg);
+
 /* The host-array entries keep device copies of the slab and of the result in the handle between calls (grow-only, so that
  * repeated calls do not reallocate).  ctk_release_io frees them (and the copy lanes): call it after a one-off large slab. */
 int ctk_release_io(ctk_handle *h);
