@@ -773,8 +773,10 @@ __device__ inline double np_walk(uint32_t cn, Leaf leaf, NpFrame *f)
 // combines them in the tree's order.  lo / ln: LDS scratch for 128 leaves.
 // Two such sums over lists of the same length at once (k_life_exact: the area and the weighted sum of one contour): the tree, and
 // so the list of leaves, depends on the length only -- it is listed once per chunk LENGTH (every chunk but the last is 8192 long),
-// the leaves of both lists are summed side by side (threads 0..63 / 64..127 of a group: its first two waves; the other two take no part -- k_life_exact
-// gives them other work) and combined by two waves at the same time.
+// the 2 * nl leaves of both lists are summed side by side by threads 0..127 of a group (its first two waves; the other two take no part --
+// k_life_exact gives them other work), leaf j of the pair of lists on thread j % 128, and combined by two waves at the same time.  numpy's
+// tree has at most 65 leaves per block of 8192 (441 block lengths in 7689..8191 have 65), so 2 * nl <= 130 and a thread sums one leaf,
+// threads 0 and 1 two; lv holds 128 slots per list (a at lv[0..nl), b at lv[128..128 + nl)).
 // lv: 256 doubles, frames: 2 x 16.  Results valid in thread 0 (ra) and thread 64 (rb).
 // Round 5: a workgroup of 1024 threads takes FOUR blocks per round (groups of 256 threads, each with its own leaf list, leaf sums and
 // the two threads that walk the trees); the block sums are added in the order of the blocks by thread 0 / thread 64, as numpy's
@@ -804,8 +806,10 @@ __device__ inline void wg_np_sum2(const double *a, const double *b, size_t n, ui
         }
         sync();
         const int nl = cn ? nleaf_all[grp] : 0;
-        if (t8 < nl) lv[t8] = dev_np_leaf(a + c0 + lo[t8], ln[t8]);
-        else if (t8 >= 64 && t8 - 64 < nl) lv[64 + t8] = dev_np_leaf(b + c0 + lo[t8 - 64], ln[t8 - 64]);
+        for (int j = t8; j < 2 * nl; j += 128) {
+            if (j < nl) lv[j] = dev_np_leaf(a + c0 + lo[j], ln[j]);
+            else lv[128 + j - nl] = dev_np_leaf(b + c0 + lo[j - nl], ln[j - nl]);
+        }
         sync();
         if (cn && t8 == 0) { int k = 0; cres[grp] = np_walk(cn, [&](uint32_t, uint32_t) { return lv[k++]; }, frames); }
         else if (cn && t8 == 64) { int k = 128; cres[4 + grp] = np_walk(cn, [&](uint32_t, uint32_t) { return lv[k++]; }, frames + 16); }

@@ -3,7 +3,7 @@
 imported under tests/minixr.py) -- run_contrack to get `flag`, then run_lifecycle(flag, variable) -- on seeded inputs
 and stores inputs + the reference's DataFrame columns under tests/golden/life/.  Build container only.
 
-    python tests/golden/make_life_golden.py
+    python tests/golden/make_life_golden.py [big]
 
 Each .npz: field (float32 as int16 / q_scale, or float64 raw; 'field_ref' names refslab_input.npz), flag (int32),
 lat, lon, wrow (float32), time (datetime64[h] as int64 hours since 1970), and the reference's columns
@@ -126,7 +126,43 @@ def main():
     other = q8(smooth_field(8, 31, 48, 22, amp=40.0) + 500.0)
     flag2, df2, _ = reference_run(q8(f), lat, lon, t, 55.5, ">=", 0.25, 2, True, variable_field=other)
     save("othervar", q8(f), flag2, lat, lon, wrow, t, df2, variable=other)
+    make_big()
+
+
+BIG_RUNS = ((7689, 10 * 360 + 123, 360), (8191, 34 * 360 + 20, 320), (16383, 63 * 360 + 260, 200))
+
+
+def big_masks(ny=181, nx=360):
+    """the contours of 'big' as (pixel count, boolean plane): runs of `width` columns from `start` (a flat index), filled row by
+    row, the last row partial.  7689 (8191, and 8192 + 8191) pixels: a block of numpy's np.sum with 65 leaves.  The first run
+    starts mid-row and spans whole rows (both seam columns, roll shift 1), the second stays clear of the seam, the third is a band
+    of columns 260..359, 0..99 (roll shift 260).  Empty rows keep them apart."""
+    out = []
+    for L, start, width in BIG_RUNS:
+        y0, x0 = divmod(start, nx)
+        k = np.arange(L)
+        m = np.zeros((ny, nx), bool)
+        m[y0 + k // width, (x0 + k % width) % nx] = True
+        out.append((L, m))
+    return out
+
+
+def make_big():
+    """large contours on the 1 degree grid with a constant value on a half cent: every weighted sum is exact, the intensity is
+    200.125 exactly and the reference prints 200.12 -- a rounding boundary, so the row takes the exact path"""
+    os.makedirs(OUT, exist_ok=True)
+    lat, lon = grid(181, 360)
+    f = np.zeros((3, 181, 360), np.float32)
+    for _, m in big_masks():
+        f[:, m] = 200.125
+    t = (np.datetime64("2001-12-30T00", "h") + np.arange(3) * 6).astype("datetime64[ns]")
+    flag, df, wrow = reference_run(f, lat, lon, t, 150, ">=", 0.5, 2, True)
+    assert len(df) == 9 and set(df.Intensity) == {200.12}
+    save("big", f, flag, lat, lon, wrow, t, df)
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["big"]:
+        make_big()                                   # python tests/golden/make_life_golden.py big: that case alone
+    else:
+        main()

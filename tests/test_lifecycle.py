@@ -13,7 +13,7 @@ CASES = life_util.case_names()
 
 
 def test_fixtures_present():
-    assert {"refslab", "smooth0", "smooth1", "smooth2", "ring", "float64", "othervar"} <= set(CASES)
+    assert {"refslab", "smooth0", "smooth1", "smooth2", "ring", "float64", "othervar", "big"} <= set(CASES)
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -213,3 +213,176 @@ def test_hip_lifecycle_limits(tracker):
     assert np.array_equal(rows["area"], want["area"]) and np.allclose(rows["swvy"], want["swvy"], rtol=1e-12)
     with pytest.raises(ValueError):
         tracker.lifecycle(flag, np.ones((1, ny, nx + 1), np.float32), wrow)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# large contours: numpy's np.sum tree (blocks of 8192, leaves of <= 128) and the exact path on contours that reach its hard cases
+# ---------------------------------------------------------------------------------------------------------------
+def _values(rng, n):
+    return rng.standard_normal(n) * 10.0 ** rng.uniform(-6, 6, n)
+
+
+def test_np_tree_sum_is_numpy_sum():
+    rng = np.random.default_rng(11)
+    for n in life_util.sweep_lengths() + life_util.edge_lengths() + life_util.round_lengths() + [105000, 721 * 1440]:
+        a = _values(rng, n)
+        assert life_util.np_tree_sum(a) == np.sum(a), n
+        lv = life_util.np_leaves(n)
+        assert lv[0][0] == 0 and all(o + m == o2 for (o, m), (o2, _) in zip(lv, lv[1:])) and sum(m for _, m in lv) == n
+
+
+def test_np_leaves_at_most_65_per_block():
+    """the bound wg_np_sum2 relies on: 441 block lengths (7689..8191) have 65 leaves, none has more, 8192 has 64"""
+    counts = np.array([len(life_util.np_leaves(n)) for n in range(1, 8193)])
+    assert counts.max() == 65 and (counts == 65).sum() == 441
+    l65 = life_util.leaf_lengths(65)
+    assert len(l65) == 441 and l65[0] == 7689 and l65[-1] == 8191
+    assert counts[8191] == 64 and len(life_util.np_leaves(8192 * 3 + 8191)) == 3 * 64 + 65
+
+
+@pytest.mark.parametrize("grid,kind", [("1deg", "raster"), ("1deg", "band"), ("1deg", "full"), ("0.25deg", "raster")])
+def test_large_cases_have_the_prescribed_shapes(grid, kind):
+    lengths = ([7689, 8191, 8192, 16383] if grid == "1deg" else life_util.round_lengths()[-4:] + [721 * 1440]) + life_util.edge_lengths()
+    c = life_util.large_life_case(lengths, grid, kind, seed=3)
+    flag, (ny, nx) = c["flag"], c["flag"].shape[1:]
+    for ident, L in zip(c["ids"], c["lengths"]):
+        assert (flag == ident).sum() == L
+    rows = life_util.numpy_rows(flag, c["field"], c["wrow"])
+    big = rows[np.isin(rows["label"], c["ids"][c["lengths"] >= 2 * nx])]
+    assert len(big) >= 4
+    if kind == "raster":
+        assert (big["shift"] == 1).all()                                   # both seam columns, every column occupied
+    elif kind == "band":
+        assert (big["shift"] > 1).all()                                    # across the seam, rolled order != raster order
+    else:
+        for r in big:
+            assert (flag[r["t"]] == r["label"]).any(axis=1).all()          # every row, the pole rows included
+        assert (big["shift"] > 1).sum() >= 1
+    assert (c["field"] < 0).any() and np.ptp(np.log10(np.abs(c["field"][flag != 0]))) > 10
+
+
+@pytest.mark.parametrize("grid,kind,dtype", [("1deg", "raster", np.float32), ("1deg", "band", np.float64), ("0.25deg", "band", np.float32)])
+def test_large_cases_tell_summation_orders_apart(grid, kind, dtype):
+    """a kernel that summed in another order than numpy's would fail on these values: np.sum differs from the sequential sum, above
+    8192 from the unblocked pairwise sum, and np.bincount's sequential sums over the rolled list from np.sum of that list"""
+    lengths = life_util.sweep_lengths()[::8] + life_util.edge_lengths() if grid == "1deg" else \
+        life_util.round_lengths() + [105000] + [8192 * k + r for k in (1, 2, 5) for r in (100, 3000, 5000)]
+    c = life_util.large_life_case(lengths, grid, kind, dtype=dtype, seed=4)
+    flag, field = c["flag"], c["field"]
+    rows = life_util.numpy_rows(flag, field, c["wrow"])
+    ex = life_util.numpy_exact_rows(flag, field, c["wrow"], rows, extent=True)
+    wgrid = np.ones(flag.shape[1:]) * c["wrow"].astype(np.float64)[:, None]
+    seq, unblocked, rolled = [], [], []
+    for r, e in zip(rows, ex):
+        m = flag[r["t"]] == r["label"]
+        p = wgrid[m] * field[r["t"]][m]
+        assert e["swv"] == np.sum(p)
+        if len(p) >= 129:
+            seq.append(np.sum(p) != life_util.seq_sum(p))
+        if len(p) > 8192 and not 16384 <= len(p) < 16400:                  # (there the unblocked tree's first split is at 8192: the same tree)
+            unblocked.append(np.sum(p) != life_util.np_tree_sum(p, block=None))
+        sh = int(r["shift"]) if r["shift"] > 0 else 0
+        pr = np.roll(np.where(m, field[r["t"]].astype(np.float64), 0.0) * wgrid, -sh, axis=1)[np.roll(m, -sh, axis=1)]
+        assert e["s"] == life_util.seq_sum(pr)
+        rolled.append(e["s"] != np.sum(pr))
+    assert len(seq) >= 10 and np.mean(seq) >= 2 / 3
+    assert np.mean(rolled) >= 2 / 3
+    if grid != "1deg":
+        assert len(unblocked) >= 10 and np.mean(unblocked) >= 2 / 3
+
+
+def _check_exact(tracker, c, idx=None):
+    """lifecycle_exact on rows idx (default: all) of the last lifecycle call equals numpy's own calls bit for bit"""
+    rows = life_util.numpy_rows(c["flag"], c["field"], c["wrow"])
+    idx = np.arange(len(rows)) if idx is None else np.asarray(idx)
+    ex = tracker.lifecycle_exact(idx)
+    want = life_util.numpy_exact_rows(c["flag"], c["field"], c["wrow"], rows[idx], extent=True)
+    for k in ("area", "swv", "s", "sy", "sx"):
+        bad = np.nonzero(ex[k] != want[k])[0]
+        assert len(bad) == 0, (k, len(bad), "pixel counts", [int((c["flag"][rows[idx[i]]["t"]] == rows[idx[i]]["label"]).sum()) for i in bad[:8]])
+
+
+def _large_rows(tracker, c):
+    """tracker.lifecycle on a large case: t / label / shift as numpy_rows, the area as math.fsum of the weights (exact: integer
+    limbs, rounded once)"""
+    import math
+    rows = tracker.lifecycle(c["flag"], c["field"], c["wrow"])
+    want = life_util.numpy_rows(c["flag"], c["field"], c["wrow"])
+    for k in ("t", "label", "shift"):
+        assert np.array_equal(rows[k], want[k]), k
+    w64 = c["wrow"].astype(np.float64)
+    fs = [math.fsum(np.repeat(w64, (c["flag"][r["t"]] == r["label"]).sum(axis=1))) for r in rows]
+    assert np.array_equal(rows["area"], np.array(fs))
+    return rows, want
+
+
+LARGE = [("1deg", kind, dt, False) for kind in ("raster", "band", "full") for dt in (np.float32, np.float64)] + \
+        [("0.25deg", kind, dt, False) for kind in ("raster", "band", "full") for dt in (np.float32, np.float64)] + \
+        [("1deg", "band", np.float64, True), ("0.25deg", "raster", np.float32, True)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("grid,kind,dtype,positive", LARGE)
+def test_hip_lifecycle_exact_large_contours(tracker, grid, kind, dtype, positive):
+    """1 deg: every length 7600..8192 (the 441 block lengths with 65 leaves among them) and the block edges of the sequential sums,
+    256-thread launch; 0.25 deg: 8192 k + r (k = 1, 2, 3, 4, 12; r = 0, 1, 7689, 8191), the 105 000 pixels of DESIGN 9 and (raster)
+    the whole plane, 1024-thread launch"""
+    if grid == "1deg":
+        lengths = life_util.sweep_lengths() + life_util.edge_lengths()
+    else:
+        lengths = life_util.round_lengths() + [105000] + ([721 * 1440] if kind == "raster" else [])
+    c = life_util.large_life_case(lengths, grid, kind, dtype=dtype, positive=positive, seed=len(lengths) + 7 * positive)
+    rows, want = _large_rows(tracker, c)
+    if positive:
+        for k in ("swv", "swvy", "swvx"):
+            assert np.allclose(rows[k], want[k], rtol=1e-12, atol=0), k
+    _check_exact(tracker, c)
+
+
+@pytest.mark.gpu
+def test_hip_lifecycle_exact_launch_shapes(tracker):
+    """the same rows under the 256-thread launch (no listed row above 8192 pixels) and the 1024-thread one (a row of 8192 + 8191
+    listed with them), in order, permuted and with duplicates"""
+    small = life_util.edge_lengths() + [7600, 7688, 7689, 7690, 7900, 8190, 8191, 8192]
+    c = life_util.large_life_case(small + [8192 + 8191], "1deg", "band", dtype=np.float64, seed=21)
+    rows, _ = _large_rows(tracker, c)
+    counts = np.array([(c["flag"][r["t"]] == r["label"]).sum() for r in rows])
+    i_small, i_big = np.nonzero(counts <= 8192)[0], np.nonzero(counts > 8192)[0]
+    assert len(i_big) == 1 and len(i_small) == len(small)
+    _check_exact(tracker, c, i_small)                                       # 256 threads
+    _check_exact(tracker, c)                                                # 1024 threads, every row
+    rng = np.random.default_rng(5)
+    _check_exact(tracker, c, rng.permutation(len(rows)))
+    _check_exact(tracker, c, np.concatenate([i_big, i_small[::-1], i_small[-3:], i_big]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nx", [767, 768, 769, 1537])
+def test_hip_lifecycle_exact_row_widths(tracker, nx):
+    """rows of one batch of k_life_rows / k_life_lists (768 = LR_U x 64 columns), one column past it, and three batches"""
+    for kind, dtype in (("raster", np.float32), ("band", np.float64)):
+        c = life_util.large_life_case([129, 513, nx, 7689, 8191, 8192, 16383, 2 * nx + 1], (41, nx), kind, dtype=dtype, seed=nx)
+        rows, _ = _large_rows(tracker, c)
+        assert (rows["shift"] > 0).sum() >= 4
+        _check_exact(tracker, c)
+
+
+@pytest.mark.gpu
+def test_hip_big_golden_rows_take_the_exact_path(tracker):
+    """the 'big' golden: contours of 7689, 8191 and 8192 + 8191 pixels whose intensity sits on a half cent go through
+    lifecycle_exact, and the frame is the reference's"""
+    from contrack_amd.contrack import lifecycle_columns
+    g = life_util.load("big")
+    rows = tracker.lifecycle(g["flag"], g["variable"], g["wrow"])
+    seen = []
+
+    class Recorder:
+        def lifecycle_exact(self, idx):
+            seen.extend(int(i) for i in idx)
+            return tracker.lifecycle_exact(idx)
+    cols = lifecycle_columns(rows, g["lat"], g["lon"], life_util.dates_of(g["time"]), Recorder())
+    counts = sorted({int((g["flag"][r["t"]] == r["label"]).sum()) for r in rows[seen]})
+    assert sorted(set(seen)) == list(range(len(rows))) and counts == [7689, 8191, 16383]
+    got = [(int(f), d, int(lo), int(la), float(it), float(sz)) for f, d, lo, la, it, sz in
+           zip(cols["Flag"], cols["Date"], cols["Longitude"], cols["Latitude"], cols["Intensity"], cols["Size"])]
+    assert got == g["frame"]
