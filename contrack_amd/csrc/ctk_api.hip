@@ -44,32 +44,29 @@ double ctk_np_sum(const double *a, size_t n);
         if (r_ != CTK_OK) return r_; \
     } while (0)
 
-static int g_ht = -1; static double g_ht0 = 0;
-static double now_ms_fwd() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-#define HT(name) do { if (g_ht < 0) g_ht = getenv("CTK_HOSTTRACE") ? 1 : 0; if (g_ht) { double t_ = now_ms_fwd(); fprintf(stderr, "HT %-28s %9.1f us\n", name, (t_ - g_ht0) * 1e3); } } while (0)
-#define HT0() do { if (g_ht < 0) g_ht = getenv("CTK_HOSTTRACE") ? 1 : 0; if (g_ht) g_ht0 = now_ms_fwd(); } while (0)
-
-// Debug / experiment switches of the environment, read ONCE per process (getenv is a linear scan of environ and not safe against a
-// concurrent setenv from another rank's host thread; the passes shave microseconds).
+// Switches of the environment, read ONCE per process, here and nowhere else in this translation unit (getenv is a linear scan of
+// environ and not safe against a concurrent setenv from another rank's host thread; the passes shave microseconds).
 struct CtkEnv {
-    int sd_dbg = 0, relabel_rows = 0, xcd_thr = 0, xcd_rel = 0, relabel_threads = 0;
-    bool pass_launches = false, print_ptrs = false, seamstats = false, relabel_plain = false, relabel_v4 = false, hosttrace = false,
-         sh_no_slots = false, no_spec_x4 = false, sh_force_split = false, sh_host_seam = false, rle_out = true, mask_tune = true;
-    int rle_lanes = 0, rle_per_lane = 0;
+    int sd_dbg = 0, mask_tries = 0;
+    bool seamstats = false, hosttrace = false, hostprof = false, shdebug = false, sh_force_split = false, rle_out = true, mask_tune = true, async = true;
     CtkEnv()
     {
         auto num = [](const char *k) { const char *e = getenv(k); return e ? atoi(e) : 0; };
         auto on = [](const char *k) { return getenv(k) != nullptr; };
-        sd_dbg = num("CTK_SD_DBG"); relabel_rows = num("CTK_RELABEL_ROWS"); xcd_thr = getenv("CTK_XCD_THR") ? num("CTK_XCD_THR") : 64; xcd_rel = num("CTK_XCD_REL"); relabel_threads = num("CTK_RELABEL_THREADS");      // (tools/xcd_probe.py, NOTES round 4)
-        pass_launches = on("CTK_PASS_LAUNCHES"); print_ptrs = on("CTK_PRINT_PTRS"); seamstats = on("CTK_SEAMSTATS");
-        relabel_plain = on("CTK_RELABEL_PLAIN"); relabel_v4 = on("CTK_RELABEL_V4"); hosttrace = on("CTK_HOSTTRACE");
-        sh_no_slots = on("CTK_SH_NO_SLOTS"); no_spec_x4 = on("CTK_NO_SPEC_X4"); sh_force_split = on("CTK_SH_FORCE_SPLIT"); sh_host_seam = on("CTK_SH_HOST_SEAM");
-        rle_out = !(getenv("CTK_RLE_OUT") && num("CTK_RLE_OUT") == 0);
-        mask_tune = !(getenv("CTK_MASK_TUNE") && num("CTK_MASK_TUNE") == 0);
-        rle_lanes = num("CTK_RLE_LANES"); rle_per_lane = num("CTK_RLE_PER_LANE");
+        sd_dbg = num("CTK_SD_DBG"); seamstats = on("CTK_SEAMSTATS"); hosttrace = on("CTK_HOSTTRACE"); hostprof = on("CTK_HOSTPROF"); shdebug = on("CTK_SHDEBUG");
+        sh_force_split = on("CTK_SH_FORCE_SPLIT");
+        rle_out = !(on("CTK_RLE_OUT") && num("CTK_RLE_OUT") == 0);
+        mask_tune = !(on("CTK_MASK_TUNE") && num("CTK_MASK_TUNE") == 0);
+        mask_tries = std::min(std::max(num("CTK_MASK_TRIES"), 0), 1);
+        async = !(on("CTK_ASYNC") && num("CTK_ASYNC") == 0);
     }
 };
 static const CtkEnv &ctk_env() { static const CtkEnv e; return e; }
+
+static double g_ht0 = 0;
+static double now_ms_fwd() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+#define HT(name) do { if (ctk_env().hosttrace) { double t_ = now_ms_fwd(); fprintf(stderr, "HT %-28s %9.1f us\n", name, (t_ - g_ht0) * 1e3); } } while (0)
+#define HT0() do { if (ctk_env().hosttrace) g_ht0 = now_ms_fwd(); } while (0)
 
 struct ShardScratch;
 static void shard_scratch_free(ShardScratch *s);            // ctk_sharded.hip
@@ -79,7 +76,6 @@ namespace {
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
-    void *base = nullptr;                           // the allocation p lies in when p was placed inside a larger one (ensure_placed); else nullptr
 };
 
 enum State { ST_IDLE = 0, ST_LABELLED, ST_OVERLAPPED, ST_TABLES, ST_EXTENTS };
@@ -294,7 +290,6 @@ struct ctk_handle {
     std::vector<uint32_t> rle_run_base;            // host copy of run_base (deliver_runs)
     std::vector<RleBlock> rle_blocks;
     bool rle_out = false;                          // this call's result leaves the device as run tables: launch_relabel is a no-op
-    int64_t mask_off_dbg = -1;                     // ctk_debug_set_mask_offset: the mask placed this many bytes into a larger allocation (-1: plain)
     int rle_mode = -1;                             // ctk_set_result_transfer: -1 environment (CTK_RLE_OUT, default on), 0 dense copy, 1 runs, 2 runs wanted but made unavailable (test hook)
     // time-sharded path (ctk_sharded.hip)
     DevBuf sh_mask_next, sh_send, sh_recv, sh_prev, sh_elist, sh_ovr_slot, sh_ovr_val, sh_amb_list, sh_counts, sh_cl_shared, sh_cl_sent;
@@ -304,7 +299,6 @@ struct ctk_handle {
     uint32_t *h_mail2 = nullptr;                   // pinned, device-written scalars
     void *h_shard = nullptr, *h_lab = nullptr, *h_seam = nullptr;        // pinned: gathered boundary records / label tables / shared seam groups
     size_t h_shard_cap = 0, h_lab_cap = 0, h_seam_cap = 0;
-    bool sh_slots = false;                             // time-shard path: k_overlap writes its records into fixed per-timestep slots
     bool halo_in_zero = false; void *halo_in_zero_p = nullptr; size_t halo_in_zero_cap = 0;     // the halo header of a first shard is already zero
     uint32_t sh_capB = 0, sh_capC = 0, sh_capD = 0;     // agreed capacities of the exchanged records (grow-only)
     std::vector<std::pair<int32_t, int32_t>> sh_pairs;
@@ -363,9 +357,6 @@ struct ctk_handle {
     int debug_stall = 0;                          // test hook (ctk_debug_set_spin): the first workgroup of the chain is late (1) / never publishes (2)
     bool no_sys = false, sh_retrying = false;
     int small_threads[3] = {0, 0, 0};              // experiments (ctk_debug_set_small_threads): threads of k_extent / k_run_values / k_compact_init, 0 = default
-    int relabel_threads = 0, relabel_rows_dbg = 0;  // experiments (ctk_debug_set_relabel): threads / rows per workgroup of k_relabel_v5, 0 = default
-    int xcd_thr = -1, xcd_rel = -1;               // chunk -> XCD mapping of the two streaming kernels (xcd_chunk); -1: the environment's / default
-    int xcd_thr_tuned = -1;                       // (round 4 tuned the XCD tile size of the threshold kernel per placement; no longer: -1)
     bool thr_nostore = false;                     // the threshold kernel without its mask stores: the yardstick of the mask placement check
     bool thr_probe = false;                       // the launches of that check run under their own kernel name (k_threshold_probe)
     bool rel_probe = false;                       // ... and those of the write kernel's chunk -> XCD timing (k_relabel_probe)
@@ -374,7 +365,7 @@ struct ctk_handle {
     int mask_check_retries = 0;                   // checks that found the device busy with other work (their times meant nothing)
     int mask_tries = 0; double mask_ratio = 0.0;  // allocations of the mask that were checked when it was last (re)allocated; kernel time / its time without stores
     double mask_check_ms = 0; double mask_spacer_gb = 0;        // host time / spacer memory held by the last mask placement check
-    int xcd_rel_tuned = -1;                       // the same for the write kernel (tune_relabel), for the shape below
+    int xcd_rel_tuned = -1;                       // chunk -> XCD mapping of the write kernel (xcd_chunk, tune_relabel) for the shape below; -1: launch order
     int64_t rel_tuned_T = -1; int rel_tuned_ny = 0, rel_tuned_nx = 0; const void *rel_tuned_flag = nullptr;
     int64_t rel_seen_T = -1; int rel_seen_ny = 0, rel_seen_nx = 0;      // the shape of the previous pass (tuning waits for the second pass on a shape)
     bool sh_collective_err = false;               // the time-shard path's error was decided identically on every rank
@@ -412,7 +403,7 @@ int ensure(ctk_handle *h, DevBuf &b, size_t need)
     if (b.cap >= need) return CTK_OK;
     // hipFree waits for the device: with a collective in flight that wait must be the communicator's guarded one
     if (b.p && h && h->active_comm) { if (int rc = ctk_comm_wait(h->active_comm)) return rc; }
-    if (b.p) { (void)hipFree(b.base ? b.base : b.p); b.p = nullptr; b.base = nullptr; b.cap = 0; }
+    if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
     size_t cap = need + need / 8 + 256;                   // a little head room: sizes vary between calls
     hipError_t e = hipMalloc(&b.p, cap);
     if (e != hipSuccess) {
@@ -425,22 +416,6 @@ int ensure(ctk_handle *h, DevBuf &b, size_t need)
     }
     b.cap = cap;
     (void)h;
-    return CTK_OK;
-}
-
-// the same with the buffer placed `off` bytes into an allocation that is `slack` bytes larger (placement experiments / tuning:
-// where a buffer lies decides which HBM channels its stream meets)
-int ensure_placed(ctk_handle *h, DevBuf &b, size_t need, size_t off, size_t slack)
-{
-    if (need == 0) need = 8;
-    if (b.cap >= need && b.base && (size_t)((char *)b.p - (char *)b.base) == off) return CTK_OK;
-    if (b.p && h && h->active_comm) { if (int rc = ctk_comm_wait(h->active_comm)) return rc; }
-    if (b.p) { (void)hipFree(b.base ? b.base : b.p); b.p = nullptr; b.base = nullptr; b.cap = 0; }
-    const size_t cap = need + need / 8 + 256;
-    void *q = nullptr;
-    const hipError_t e = hipMalloc(&q, cap + slack);
-    if (e != hipSuccess) return ctk_set_error(CTK_E_NOMEM, "hipMalloc(%zu bytes) failed: %s", cap + slack, hipGetErrorString(e));
-    b.base = q; b.p = (char *)q + off; b.cap = cap;
     return CTK_OK;
 }
 
@@ -587,7 +562,7 @@ extern "C" void ctk_destroy(ctk_handle *h)
                       &h->sh_mask_next, &h->sh_send, &h->sh_recv, &h->sh_prev, &h->sh_elist, &h->sh_ovr_slot, &h->sh_ovr_val,
                       &h->sh_amb_list, &h->sh_counts, &h->sh_cl_shared, &h->sh_cl_sent, &h->chunk_vals, &h->lc_work, &h->lc_ovf, &h->lc_ekeys, &h->lc_offs, &h->lc_sw, &h->lc_sp, &h->lc_out, &h->lc_cross, &h->lc_gtab, &h->lc_occ, &h->lc_cp, &h->an_out, &h->an_clim, &h->an_raw, &h->an_idx, &h->sd_parent, &h->sd_tmin, &h->sd_tmax, &h->sd_root, &h->sd_nops, &h->sd_lbox, &h->rv_pstate, &h->ci_bsum, &h->scan_bsum,
                       &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order, &h->fq_counts, &h->fq_group, &h->seg_edge};
-    for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->base ? b->base : b->p);
+    for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (h->h_blob) (void)hipHostFree(h->h_blob);
     if (h->h_small) (void)hipHostFree(h->h_small);
     if (h->h_cand) (void)hipHostFree(h->h_cand);
@@ -691,26 +666,12 @@ extern "C" int ctk_debug_set_seam_caps(ctk_handle *h, int labels, int ops)
     return CTK_OK;
 }
 
-extern "C" int ctk_debug_set_xcd(ctk_handle *h, int thr_mode, int rel_mode)
-{
-    if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
-    h->xcd_thr = thr_mode; h->xcd_rel = rel_mode;
-    return CTK_OK;
-}
-
 extern "C" int ctk_debug_set_small_threads(ctk_handle *h, int extent, int run_values, int compact_init)
 {
     for (int v : {run_values, compact_init}) if (v != 0 && v != 64 && v != 128 && v != 256) return ctk_set_error(CTK_E_INVALID, "ctk_debug_set_small_threads: 0 / 64 / 128 / 256");
     if (extent != 0 && extent != 64 && extent != 128 && extent != 256 && extent != 1024) return ctk_set_error(CTK_E_INVALID, "ctk_debug_set_small_threads: extent 0 / 64 / 128 / 256, or 1024 = k_extent_blk");
     if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
     h->small_threads[0] = extent; h->small_threads[1] = run_values; h->small_threads[2] = compact_init;
-    return CTK_OK;
-}
-
-extern "C" int ctk_debug_set_relabel(ctk_handle *h, int threads, int rows)
-{
-    if (!h || (threads != 0 && threads != 128 && threads != 256 && threads != 257 && threads != 512 && threads != 1024) || rows < 0) return ctk_set_error(CTK_E_INVALID, "ctk_debug_set_relabel: threads 0 / 256 / 512 / 1024, rows >= 0");
-    h->relabel_threads = threads; h->relabel_rows_dbg = rows;
     return CTK_OK;
 }
 
@@ -729,9 +690,9 @@ extern "C" int ctk_debug_time_relabel(ctk_handle *h, int32_t *flag_dev, int pers
     if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed"); }
     int rows = 0;
     const int32_t *cv = chunk_vals_for(h, flag_dev, &rows);
-    const int keep_variant = h->rel_variant, keep_xcd = h->xcd_rel;
+    const int keep_variant = h->rel_variant, keep_xcd = h->xcd_rel_tuned;
     h->rel_variant = variant;
-    if (xcd >= 0) h->xcd_rel = xcd;
+    if (xcd >= 0) h->xcd_rel_tuned = xcd;
     int rc = CTK_OK;
     hipError_t err = hipSuccess;
     for (int r = 0; r < reps && rc == CTK_OK && err == hipSuccess; r++) {
@@ -743,7 +704,7 @@ extern "C" int ctk_debug_time_relabel(ctk_handle *h, int32_t *flag_dev, int pers
         if (err == hipSuccess) err = hipEventElapsedTime(&f, e0, e1);
         ms[r] = f;
     }
-    h->rel_variant = keep_variant; h->xcd_rel = keep_xcd;
+    h->rel_variant = keep_variant; h->xcd_rel_tuned = keep_xcd;
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (rc != CTK_OK) return rc;
     if (err != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "ctk_debug_time_relabel: %s", hipGetErrorString(err));
@@ -764,35 +725,6 @@ extern "C" int ctk_set_filter_round(ctk_handle *h, int passes)
     if (!h || passes < 1 || passes > 32) return ctk_set_error(CTK_E_INVALID, "ctk_set_filter_round: 1..32 passes per round");
     h->filter_round = passes;
     h->async_passes = passes;                            // (the fused pass launches this many; it adapts from there)
-    return CTK_OK;
-}
-
-extern "C" int ctk_debug_set_mask_offset(ctk_handle *h, int64_t off)
-{
-    if (!h || off < -1 || off > ((int64_t)64 << 20) || (off > 0 && (off & 255))) return ctk_set_error(CTK_E_INVALID, "ctk_debug_set_mask_offset: -1 or a multiple of 256 up to 64 MB");
-    h->mask_off_dbg = off;
-    return CTK_OK;
-}
-
-// placement experiments: frees one work-space buffer, so that the next call allocates it anew (somewhere else)
-extern "C" int ctk_debug_drop_buffer(ctk_handle *h, int which)
-{
-    if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
-    DevBuf *b = nullptr;
-    switch (which) {
-    case 0: b = &h->mask; break;
-    case 1: b = &h->wstart; break;
-    case 2: b = &h->rowstart; break;
-    case 3: b = &h->chunk_vals; break;
-    case 4: b = &h->run_val; break;
-    case 5: b = &h->run_base; break;
-    default: return ctk_set_error(CTK_E_INVALID, "ctk_debug_drop_buffer: 0..5");
-    }
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (b->p) { (void)hipFree(b->base ? b->base : b->p); b->p = nullptr; b->base = nullptr; b->cap = 0; }
-    h->c_thr_valid = false; h->c_w_valid = false; h->fz_init = false;
-    h->runs_cap = 0;                                          // (the run-indexed buffers are looked at again: no speculative launch into a dropped one)
     return CTK_OK;
 }
 
@@ -852,8 +784,6 @@ extern "C" int ctk_get_timings(ctk_handle *h, double *ms)
 // ------------------------------------------------------------------------------------------------
 // stage 1
 // ------------------------------------------------------------------------------------------------
-// rows per workgroup of k_threshold_v4.  Swept on MI355X: 2707 x 181 x 360: 8..64 rows 0.128-0.137 ms (4 rows 0.195);
-// 480 x 721 x 1440: 2..32 rows 0.345-0.366 ms -- flat, 16 it is.
 static int stream_in(ctk_handle *h, bool f64, int64_t T, int ny, int nx, const std::function<int(const void *, int64_t, int64_t)> &consume);
 static int stream_out(ctk_handle *h, int persistence, const int32_t *chunk_vals);
 
@@ -874,12 +804,9 @@ static int launch_scan_u32(ctk_handle *h, const uint32_t *in, int64_t n, uint32_
     return CTK_OK;
 }
 
-static int threshold_rows(int ny, int nx, int64_t T)
-{
-    (void)nx; (void)T;
-    static const int env = getenv("CTK_THR_ROWS") ? atoi(getenv("CTK_THR_ROWS")) : 0;
-    return std::min(ny, env > 0 ? env : 16);
-}
+// rows per workgroup of the float4 threshold kernels (swept on their first form, k_threshold_v4, on MI355X: 2707 x 181 x 360: 8..64
+// rows 0.128-0.137 ms (4 rows 0.195); 480 x 721 x 1440: 2..32 rows 0.345-0.366 ms -- flat, 16 it is)
+static int threshold_rows(int ny) { return std::min(ny, CTK_RB); }
 
 // Threshold field for the following track calls (include/contrack_hip.h).  The field stays on the device until it is cleared or
 // replaced: repeated calls with the same climatology upload nothing.
@@ -893,7 +820,7 @@ extern "C" int ctk_set_threshold_field(ctk_handle *h, const void *field, int ele
     h->c_thr_valid = false;
     if (!field) {
         for (DevBuf *b : {&h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order}) {
-            if (b->p) (void)hipFree(b->base ? b->base : b->p);
+            if (b->p) (void)hipFree(b->p);
             *b = DevBuf();
         }
         h->fld_pos_host.clear();
@@ -980,10 +907,7 @@ static int prepare_field(ctk_handle *h, bool f64, int cmp_op, int64_t chunk)
         HIPCHK(hipGetLastError());
         h->fld_prep_op = cmp_op;
     }
-    // (CTK_THR_FIELD_ORDER=0: launch order, for tools/thr_field_probe.py; the key carries it so that a change is seen)
-    const char *om = getenv("CTK_THR_FIELD_ORDER");
-    const int64_t key = (om && atoi(om) == 0) ? -chunk - 1 : chunk;
-    if (h->fld_order_chunk != key) {
+    if (h->fld_order_chunk != chunk) {
         const int64_t T = h->fld_T;
         std::vector<int32_t> &ord = h->fld_order_host;
         ord.resize((size_t)std::max<int64_t>(T, 1));
@@ -991,14 +915,12 @@ static int prepare_field(ctk_handle *h, bool f64, int cmp_op, int64_t chunk)
             const int64_t nt = std::min<int64_t>(chunk, T - c0);
             int32_t *o = ord.data() + c0;
             for (int64_t i = 0; i < nt; i++) o[i] = (int32_t)i;                    // step of the chunk, relative to its first step
-            if (key >= 0) {
-                const int32_t *p = h->fld_pos_host.data() + c0;
-                std::stable_sort(o, o + nt, [p](int32_t a, int32_t b) { return p[a] < p[b]; });
-            }
+            const int32_t *p = h->fld_pos_host.data() + c0;
+            std::stable_sort(o, o + nt, [p](int32_t a, int32_t b) { return p[a] < p[b]; });
         }
         CTKCHK(ensure(h, h->fld_order, ord.size() * 4));
         HIPCHK(hipMemcpyAsync(h->fld_order.p, ord.data(), ord.size() * 4, hipMemcpyHostToDevice, s));
-        h->fld_order_chunk = key;
+        h->fld_order_chunk = chunk;
     }
     return CTK_OK;
 }
@@ -1083,8 +1005,7 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
     }
 
     const void *mask_before = h->mask.p;
-    if (h->mask_off_dbg >= 0) CTKCHK(ensure_placed(h, h->mask, (size_t)nrows * W * 8, (size_t)h->mask_off_dbg, (size_t)64 << 20));
-    else CTKCHK(ensure(h, h->mask, (size_t)nrows * W * 8));
+    CTKCHK(ensure(h, h->mask, (size_t)nrows * W * 8));
     const bool mask_fresh = h->mask.p != mask_before;
     CTKCHK(ensure(h, h->wstart, (size_t)nrows * W * 2));
     CTKCHK(ensure(h, h->rowstart, (size_t)nrows * 4));
@@ -1097,8 +1018,6 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
     CTKCHK(ensure(h, h->counters, CTK_CNT_WORDS * 4));
     CTKCHK(ensure_host(&h->h_small, &h->h_small_cap, (size_t)(T + 1) * 4 + 1024));     // run_base copy + scalar downloads
 
-    if (h->pass_no <= 1 && ctk_env().print_ptrs)                     // (placement experiments, tools/thr_handle_probe.py)
-        fprintf(stderr, "PTRS in %p mask %p thr32 %p counters %p wstart %p rowstart %p\n", anom_dev, h->mask.p, h->thr32.p, h->counters.p, h->wstart.p, h->rowstart.p);
     // (the device counters are zeroed by the first threshold launch of the pass; k_rowcount writes every tcount[t])
     if (T == 0) HIPCHK(hipMemsetAsync(h->counters.p, 0, CTK_CNT_ZEROED * 4, s));
     if (T > 0) {
@@ -1110,7 +1029,7 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
 
     if (T > 0) {
         Timer tm(h, CTK_K_THRESHOLD);
-        const int rbt = threshold_rows(ny, nx, T);
+        const int rbt = threshold_rows(ny);
         // timesteps [t0, t0 + nt) of the slab, at `src` on the device
         auto launch_threshold = [&](const void *src, int64_t t0, int64_t nt) -> int {
             const int64_t rows = nt * ny;
@@ -1124,11 +1043,9 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
                 const bool vf = v4;
                 const float *f32 = h->fld_esz == 4 ? P<float>(h->fld_raw) : P<float>(h->fld_f32);
                 const int32_t *pos = P<int32_t>(h->fld_pos) + t0, *ord = P<int32_t>(h->fld_order) + t0;
-                const char *fx = getenv("CTK_THR_FIELD_XCD");                 // (chunk -> XCD mapping, tools/thr_field_probe.py)
-                const int fld_xcd = fx ? atoi(fx) : 0;                          // (1: no faster, measured -- DESIGN.md section 3)
 #define LAUNCH_FLD(OP)                                                                                                                      \
     do {                                                                                                                                \
-        if (vf) k_threshold_field<OP, 4><<<g4, 256, 0, s>>>((const float *)src, f32, pos, ord, ny, nx, W, mk, rbt, zc, fld_xcd);                  \
+        if (vf) k_threshold_field<OP, 4><<<g4, 256, 0, s>>>((const float *)src, f32, pos, ord, ny, nx, W, mk, rbt, zc);                           \
         else if (!f64) k_threshold_field_g<OP, float, float><<<g, 256, 0, s>>>((const float *)src, f32, pos, rows, ny, nx, W, mk, zc);     \
         else if (h->fld_esz == 4) k_threshold_field_g<OP, double, float><<<g, 256, 0, s>>>((const double *)src, P<float>(h->fld_raw), pos, rows, ny, nx, W, mk, zc); \
         else k_threshold_field_g<OP, double, double><<<g, 256, 0, s>>>((const double *)src, P<double>(h->fld_raw), pos, rows, ny, nx, W, mk, zc); \
@@ -1143,9 +1060,8 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
                 HIPCHK(hipGetLastError());
                 return CTK_OK;
             }
-            // ballot form: float32, rows of at most 64 words
-            static const int thr_variant = getenv("CTK_THRESHOLD") ? atoi(getenv("CTK_THRESHOLD")) : 7;
-            const bool v6 = !f64 && W <= 64 && (thr_variant == 6 || !v4);      // ballot form: where the float4 form does not apply (or on request)
+            // ballot form: float32, rows of at most 64 words, where the float4 form does not apply
+            const bool v6 = !f64 && W <= 64 && !v4;
             // k_threshold_v7: loads per lane and step such that the steps of a full chunk carry the fewest idle loads
             int u7 = 8;
             {
@@ -1155,27 +1071,23 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
             }
             const int R6 = std::max(1, 64 / W), nchunk_t = (ny + R6 - 1) / R6;
             const int64_t nchunks = nt * nchunk_t;
-            const int thr_xcd = h->xcd_thr >= 0 ? h->xcd_thr : (h->xcd_thr_tuned >= 0 ? h->xcd_thr_tuned : ctk_env().xcd_thr);
-            static const bool thr_nostore_env = getenv("CTK_THR_STORE") && atoi(getenv("CTK_THR_STORE")) == 2;      // (probes: the kernel without its stores)
-            const bool thr_probe = h->thr_probe || h->thr_nostore || thr_nostore_env;                       // a launch of the mask placement check: its own kernel name
-            static const int64_t g6max = getenv("CTK_THR_GRID") ? atoll(getenv("CTK_THR_GRID")) : 16384;
-            const unsigned g6 = (unsigned)std::min<int64_t>((nchunks + 3) / 4, g6max);
+            const int thr_xcd = 64;                                                     // chunk -> XCD tiles of 64 (xcd_chunk; NOTES round 4)
+            const bool thr_probe = h->thr_probe || h->thr_nostore;                      // a launch of the mask placement check: its own kernel name
+            const int nostore = h->thr_nostore ? 1 : 0;
+            const unsigned g6 = (unsigned)std::min<int64_t>((nchunks + 3) / 4, 16384);
 #define LAUNCH_THR(OP)                                                                                                                      \
     do {                                                                                                                                \
         if (v6) k_threshold_v6<OP, 8><<<g6, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, R6, nchunk_t, nchunks, zc); \
         else if (f64) k_threshold<OP, double><<<g, 256, 0, s>>>((const double *)src, P<double>(h->thr32) + t0, rows, ny, nx, W, mk, zc); \
-        else if (v4 && thr_variant == 44) k_threshold_v4<OP, 4><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc); \
-        else if (v4 && thr_variant == 42) k_threshold_v4<OP, 2><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc); \
-        else if (v4 && thr_variant == 4) k_threshold_v4<OP><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc); \
-        else if (v4 && u7 == 4 && thr_probe) k_threshold_probe<OP, 4><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd, (h->thr_nostore || thr_nostore_env) ? 1 : 0); \
+        else if (v4 && u7 == 4 && thr_probe) k_threshold_probe<OP, 4><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd, nostore); \
         else if (v4 && u7 == 4) k_threshold_v7<OP, 4><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd); \
-        else if (v4 && u7 == 5 && thr_probe) k_threshold_probe<OP, 5><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd, (h->thr_nostore || thr_nostore_env) ? 1 : 0); \
+        else if (v4 && u7 == 5 && thr_probe) k_threshold_probe<OP, 5><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd, nostore); \
         else if (v4 && u7 == 5) k_threshold_v7<OP, 5><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd); \
-        else if (v4 && u7 == 6 && thr_probe) k_threshold_probe<OP, 6><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd, (h->thr_nostore || thr_nostore_env) ? 1 : 0); \
+        else if (v4 && u7 == 6 && thr_probe) k_threshold_probe<OP, 6><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd, nostore); \
         else if (v4 && u7 == 6) k_threshold_v7<OP, 6><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd); \
-        else if (v4 && u7 == 7 && thr_probe) k_threshold_probe<OP, 7><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd, (h->thr_nostore || thr_nostore_env) ? 1 : 0); \
+        else if (v4 && u7 == 7 && thr_probe) k_threshold_probe<OP, 7><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd, nostore); \
         else if (v4 && u7 == 7) k_threshold_v7<OP, 7><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd); \
-        else if (v4 && thr_probe) k_threshold_probe<OP, 8><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd, (h->thr_nostore || thr_nostore_env) ? 1 : 0); \
+        else if (v4 && thr_probe) k_threshold_probe<OP, 8><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd, nostore); \
         else if (v4) k_threshold_v7<OP, 8><<<g4, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, ny, nx, W, mk, rbt, zc, thr_xcd); \
         else k_threshold<OP, float><<<g, 256, 0, s>>>((const float *)src, P<float>(h->thr32) + t0, rows, ny, nx, W, mk, zc); \
     } while (0)
@@ -1201,11 +1113,10 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
         // per handle and mask size; CTK_MASK_TUNE=0 turns it off.
         // WHEN: not in the call that allocated the mask but in the next one that uses it -- a one-shot run_contrack never pays for it (a
         // few launches mean nothing to a handle that is used again and again, and are pure overhead for one that is not: round-4
-        // verdict); CTK_MASK_CHECK_FIRST=1: in the first call, as in round 4.
+        // verdict).
         if (mask_fresh) { h->mask_tries = 0; h->mask_ratio = 0.0; h->mask_check_pending = true; h->mask_check_retries = 0; }
-        static const bool check_first = getenv("CTK_MASK_CHECK_FIRST") != nullptr;
         const bool v7_path = !f64 && (nx % 4 == 0) && (((uintptr_t)anom_dev & 15) == 0);
-        if (anom_dev && !fld_call && h->mask_check_pending && (check_first || !mask_fresh) && h->mask_off_dbg < 0 && ctk_env().mask_tune && v7_path &&
+        if (anom_dev && !fld_call && h->mask_check_pending && !mask_fresh && ctk_env().mask_tune && v7_path &&
             (size_t)T * ny * nx * 4 >= ((size_t)128 << 20)) {
             h->mask_check_pending = false;
             h->mask_spacer_gb = 0.0;
@@ -1229,7 +1140,7 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
                 };
                 int rc = CTK_OK;
                 double ro_ms = 0.0, best_ms = 1e30;
-                static const double accept_first = getenv("CTK_MASK_ACCEPT") ? atof(getenv("CTK_MASK_ACCEPT")) : 1.085;
+                const double accept = 1.085;
                 h->thr_probe = true;
                 struct ProbeOff { ctk_handle *h; ~ProbeOff() { h->thr_probe = false; h->thr_nostore = false; } } probe_off{h};
                 h->thr_nostore = true;                                                  // the yardstick: the same kernel without its stores
@@ -1241,7 +1152,7 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
                 // Is the device ours?  With other work on it (other handles tracking their members at the same time) the times mean
                 // nothing -- the kernel "with stores" came out at 0.3-0.85 of the one without in bench.py's four-handle block.  The
                 // yardstick once more: apart by more than 4 %, or slower than the kernel with its stores, and the mask stays where it is.
-                if (rc == CTK_OK && best_ms > accept_first * ro_ms) {
+                if (rc == CTK_OK && best_ms > accept * ro_ms) {
                     double ro2 = 0.0;
                     h->thr_nostore = true;
                     rc = time_it(&ro2);
@@ -1259,8 +1170,7 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
                 // the allocator happened to place the mask.  (The one retry found memory of the other class for about a quarter of this
                 // round's handles and cost 1.3-6 ms of the handle's second call, once 32 ms: hipMalloc / hipFree of the spacer synchronise
                 // the device.)  CTK_MASK_TRIES=1: the one retry described above, opt-in.
-                static const int max_tries = getenv("CTK_MASK_TRIES") ? std::min(std::max(atoi(getenv("CTK_MASK_TRIES")), 0), 1) : 0;
-                const double accept = accept_first;
+                const int max_tries = ctk_env().mask_tries;
                 std::vector<void *> held;                                               // the spacer and the rejected mask: freed when the search is over
                 struct FreeHeld { std::vector<void *> &v; ~FreeHeld() { for (void *q : v) (void)hipFree(q); } } free_held{held};
                 for (int k = 0; rc == CTK_OK && k < max_tries && best_ms > accept * ro_ms; k++) {
@@ -1277,7 +1187,7 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
                     double ms = 0.0;
                     rc = time_it(&ms);
                     h->mask_tries++;
-                    if (rc == CTK_OK && ms < best_ms) { held.push_back(best.base ? best.base : best.p); best = nb; best_ms = ms; }
+                    if (rc == CTK_OK && ms < best_ms) { held.push_back(best.p); best = nb; best_ms = ms; }
                     else held.push_back(nb.p);
                     h->mask = best;
                 }
@@ -1300,9 +1210,8 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
         // one workgroup per timestep: few timesteps of a tall grid leave the chip empty and the rows of a plane in a long chain
         // (480 x 721 x 1440: 52 us with 4 waves per plane) -- more waves per plane then (first form of the kernel only)
         // (71 VGPRs: three 512-thread workgroups per CU, one round for <= 768 planes; 1024 threads ran in two rounds)
-        static const int rc_env = getenv("CTK_RC_THREADS") ? atoi(getenv("CTK_RC_THREADS")) : 0;      // (experiments)
         // (throughput regime, small planes -- 438 000 x 192 x 288: 128 threads 1.39 -> 0.86 ms, 64: 1.02)
-        const int rc_threads = rc_env > 0 ? rc_env : ((W <= 64 && ny <= RC_ROWS && ny > 256 && T <= 2048) ? 512 : ((T > 65536 && (int64_t)ny * W <= 2048) ? 128 : 256));
+        const int rc_threads = (W <= 64 && ny <= RC_ROWS && ny > 256 && T <= 2048) ? 512 : ((T > 65536 && (int64_t)ny * W <= 2048) ? 128 : 256);
         if (T > 0) k_rowcount<<<(int)T, rc_threads, 0, s>>>(P<uint64_t>(h->mask), ny, W, P<uint16_t>(h->wstart), P<uint32_t>(h->rowstart), P<uint32_t>(h->tcount));
         CTKCHK(launch_scan_u32(h, P<uint32_t>(h->tcount), T, P<uint32_t>(h->run_base), h->h_mail1, scan_stamp));
         HIPCHK(hipGetLastError());
@@ -1318,12 +1227,10 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
     // (v1hi: small planes in long shards are labelled by the 20 KB variant, which carries 832 runs -- the planes with 833 .. 1024 runs
     // then need the 1024-run variant behind it; v0_ok depends on the shape alone, so a speculative launch and the later check agree)
     struct VariantSet { bool v1, v2, v3, glb, one, v1hi; };
-    static const bool v0_env = !getenv("CTK_L2D_NO_SMALL");
     // (round 6: the same for planes of 961 .. 1088 words -- 181 x 360 -- with 768 runs and 20.3 KB: eight workgroups per CU instead of the six
-    // of the 25.6 KB variant, k_label2d 52.5 -> 49 us at 2707 x 181 x 360; CTK_L2D_SMALL1=0 turns it off)
-    static const bool v0b_env = !(getenv("CTK_L2D_SMALL1") && atoi(getenv("CTK_L2D_SMALL1")) == 0);
-    const bool v0b = v0_env && v0b_env && ny <= 256 && (int64_t)ny * W > 960 && (int64_t)ny * W <= 1088;
-    const bool v0_ok = (v0_env && T > 65536 && ny <= 256 && (int64_t)ny * W <= 960) || v0b;
+    // of the 25.6 KB variant, k_label2d 52.5 -> 49 us at 2707 x 181 x 360)
+    const bool v0b = ny <= 256 && (int64_t)ny * W > 960 && (int64_t)ny * W <= 1088;
+    const bool v0_ok = (T > 65536 && ny <= 256 && (int64_t)ny * W <= 960) || v0b;
     const uint32_t v0_runs = v0b ? 768u : 832u;
     auto launch_label2d = [&](const VariantSet &vs, uint32_t cap_runs) -> int {
         Label2dArgs a;
@@ -1340,11 +1247,7 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
         if (vs.v1) {
             if (v0b) k_label2d_lds<768, 272, -1, 256, 256><<<(int)T, 256, 0, s>>>(a);
             else if (v0_ok) k_label2d_lds<832, 240, -1, 256, 256><<<(int)T, 256, 0, s>>>(a);
-            else {
-                // (experiment, CTK_L2D_PAD_KB: unused dynamic LDS on top of the kernel's 25.6 KB -- fewer workgroups per CU; NOTES round 6)
-                static const int pad_kb = getenv("CTK_L2D_PAD_KB") ? atoi(getenv("CTK_L2D_PAD_KB")) : 0;
-                k_label2d_lds<1024, 288, -1, 256><<<(int)T, 256, (size_t)pad_kb * 1024, s>>>(a);
-            }
+            else k_label2d_lds<1024, 288, -1, 256><<<(int)T, 256, 0, s>>>(a);
         }
         if (vs.v1hi) { if (v0b) k_label2d_lds<1024, 288, 768, 256><<<(int)T, 256, 0, s>>>(a); else k_label2d_lds<1024, 288, 832, 256><<<(int)T, 256, 0, s>>>(a); }
         if (vs.v2) {
@@ -1434,8 +1337,7 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
         CTKCHK(ensure(h, h->g_rs, (size_t)T * (ny + 1) * 4));
     }
     if (T > 0) {
-        static const bool no_one = getenv("CTK_L2D_NO_ONE") != nullptr;
-        const bool prefer_one = !no_one && T <= 512 && h->max_runs_step > 1024;
+        const bool prefer_one = T <= 512 && h->max_runs_step > 1024;
         const bool none_lds = !launched.v1 && !launched.v2 && !launched.v3 && !launched.one;
         VariantSet need = {true, h->max_runs_step > 1024, h->max_runs_step > 2048, h->need_glb, false, v0_ok && h->max_runs_step > v0_runs};
         if (prefer_one && (none_lds || launched.one)) need = {false, false, false, h->need_glb, true, false};
@@ -1594,7 +1496,7 @@ static int launch_overlap(ctk_handle *h)
     a.cprefix = nullptr; a.mrep = nullptr; a.p_rc = nullptr; a.p_rd = nullptr; a.p_gc = nullptr; a.p_gd = nullptr; a.F = nullptr;
     a.pslot = 0; a.upair_cap = h->pair_cap;
     h->fz_pslot = 0;
-    if ((h->fz_init || h->sh_slots) && (uint64_t)h->T * CTK_PSLOT + 4096 <= (uint64_t)h->pair_cap) {
+    if (h->fz_init && (uint64_t)h->T * CTK_PSLOT + 4096 <= (uint64_t)h->pair_cap) {
         a.pslot = CTK_PSLOT; a.upair_cap = h->pair_cap - (uint32_t)(h->T * CTK_PSLOT);
         h->fz_pslot = CTK_PSLOT;
     }
@@ -1613,8 +1515,7 @@ static int launch_overlap(ctk_handle *h)
         // few large planes: more waves per plane (480 x 721 x 1440: 256 threads 60 us, 1024 -- one workgroup per CU at 101 VGPRs,
         // two rounds -- 53, 512 -- two per CU, one round -- 49.5)
         // many small planes (throughput regime): two waves per plane, ten workgroups per CU at 101 VGPRs -- 438 000 x 192 x 288: 3.95 -> 3.50 ms
-        // (eight words per thread in one step: 169 VGPRs, 5.5 ms); CTK_OVERLAP_SMALL=1 / 0 forces / forbids it
-        static const int ov_small = getenv("CTK_OVERLAP_SMALL") ? atoi(getenv("CTK_OVERLAP_SMALL")) : -1;
+        // (eight words per thread in one step: 169 VGPRs, 5.5 ms)
         // (small planes in long shards: room for five waves per SIMD -- 96 VGPRs, 14 of the 105 in scratch -- 3.49 -> 3.05 ms at 438 000 x 192 x 288;
         // at 2707 x 181 x 360, one round of latency chains, the same costs <5, 256> ten of its 36 us: only here)
         // (segment breaks: the SEG builds, which read the edge table)
@@ -1626,7 +1527,7 @@ static int launch_overlap(ctk_handle *h)
             if (as.seg_edge) k_overlap<OVB, TH, WPE, true><<<(int)h->T, TH, 0, h->stream>>>(as);         \
             else k_overlap<OVB, TH, WPE><<<(int)h->T, TH, 0, h->stream>>>(a);                            \
         } while (0)
-        if (ov_small == 1 || (ov_small < 0 && h->T > 65536 && nwords <= 2048)) CTK_OVERLAP(4, 128, 5);
+        if (h->T > 65536 && nwords <= 2048) CTK_OVERLAP(4, 128, 5);
         else if (h->T <= 1024 && nwords >= 8192) CTK_OVERLAP(4, 512, 1);
         else if (per <= 4 || per > 8) CTK_OVERLAP(4, 256, 1);
         else if (per == 5) CTK_OVERLAP(5, 256, 1);
@@ -1646,7 +1547,7 @@ extern "C" int ctk_shard_overlap(ctk_handle *h)
     if (h->has_prev && (!h->halo_in.p || !h->halo_valid))
         return ctk_set_error(CTK_E_STATE, "ctk_shard_overlap: has_prev set but no halo imported since ctk_shard_label2d");
     size_t want = (size_t)h->total_runs / 2 + (size_t)h->T * 8 + 4096;
-    if (h->fz_init || h->sh_slots) want = std::max<size_t>(want, (size_t)h->T * CTK_PSLOT + (size_t)h->T * 8 + 8192);       // fixed slots per timestep + ungrouped
+    if (h->fz_init) want = std::max<size_t>(want, (size_t)h->T * CTK_PSLOT + (size_t)h->T * 8 + 8192);       // fixed slots per timestep + ungrouped
     if (want > 0x7fffffffull) want = 0x7fffffffull;
     if (h->pair_cap < want || !h->pairs.p) {
         CTKCHK(ensure(h, h->pairs, want * sizeof(CtkPair)));
@@ -1843,9 +1744,8 @@ static int launch_extents(ctk_handle *h, bool ext_filled = false, bool with_fina
         // (one wave per plane beyond 2048 planes; two on wide grids, whose complex components are folded row by row: 14 600 x 721 x 1440 0.40 -> 0.26 ms)
         a.T = h->T;
         // round 6: sixteen timesteps per workgroup, the ids' extents reduced in LDS before they touch memory (k_extent_blk), for shards of
-        // more than 2048 timesteps on narrow grids (where k_extent ran one wave per plane); CTK_EXTENT_BLK=0 / 1 forbids / forces it
-        static const int ext_blk = getenv("CTK_EXTENT_BLK") ? atoi(getenv("CTK_EXTENT_BLK")) : -1;
-        const bool blk = h->small_threads[0] == 1024 || (h->small_threads[0] == 0 && (ext_blk == 1 || (ext_blk < 0 && h->T > 2048 && h->nx < 1024)));
+        // more than 2048 timesteps on narrow grids (where k_extent ran one wave per plane)
+        const bool blk = h->small_threads[0] == 1024 || (h->small_threads[0] == 0 && h->T > 2048 && h->nx < 1024);
         if (blk) k_extent_blk<<<(int)((h->T + EX_TW - 1) / EX_TW), 64 * EX_TW, 0, s>>>(a);
         else k_extent<<<(int)h->T, h->small_threads[0] > 0 ? h->small_threads[0] : (h->T > 2048 ? (h->nx >= 1024 ? 128 : 64) : 256), 0, s>>>(a);
         HIPCHK(hipGetLastError());
@@ -1905,12 +1805,6 @@ static void launch_rs_pass(const ctk_handle *h, int grid, const ResolveDev &r, i
 {
     if (h->seg_cur) k_rs_pass<true><<<grid, 64, 0, h->stream>>>(r, it, pair_base, pair_cnt, tdirty, h->seg_cur);
     else k_rs_pass<false><<<grid, 64, 0, h->stream>>>(r, it, pair_base, pair_cnt, tdirty, nullptr);
-}
-static void launch_rs_pass_sys(const ctk_handle *h, int grid, const ResolveDev &r, int it0, int K, const uint32_t *pair_base, const uint32_t *pair_cnt,
-                               uint32_t *pstate, int prep_inline, int do_unite)
-{
-    if (h->seg_cur) k_rs_pass_sys<true><<<grid, 64, 0, h->stream>>>(r, it0, K, pair_base, pair_cnt, pstate, prep_inline, do_unite, h->seg_cur);
-    else k_rs_pass_sys<false><<<grid, 64, 0, h->stream>>>(r, it0, K, pair_base, pair_cnt, pstate, prep_inline, do_unite, nullptr);
 }
 // two_pc: the build with two workgroups per CU (k_rs_pass_blk_2pc)
 static void launch_rs_pass_blk(const ctk_handle *h, bool two_pc, int nb, const ResolveDev &r, int it0, int K, const uint32_t *pair_base, const uint32_t *pair_cnt,
@@ -2262,7 +2156,7 @@ static int relabel_rows(const ctk_handle *h)
     //   2000 steps: 3 rows 1.37 | 4: 1.31 | 6: 1.02 | 8: 1.12 | 12: 1.10        14 600 steps: 6 rows 1.03 | 8: 1.07 | 9: 1.09
     // i.e. the smallest chunk that keeps the launch at or below ~250 000 workgroups, and not more than ~2300 stores (6 rows).
     // Narrow rows (192 x 288, configs[4]: 72 stores per row), 438 000 steps, ms per launch: 32 rows 21.6 | 48: 20.2 | 64: 18.9 | 96: 18.5 | 192: 22.8
-    // (tools/cesm_relabel_sweep.py) -- the cap of ~2300 stores was found on 1440-wide rows (360 stores each); up to ~6900 where a row is short.
+    // (round 6 sweep) -- the cap of ~2300 stores was found on 1440-wide rows (360 stores each); up to ~6900 where a row is short.
     const int store_cap = n4r >= 256 ? 2304 : 6912;
     const int rb_max = std::min(h->ny, std::max(rb, std::min(96, store_cap / n4r)));
     // Round 6, with eight workgroups per CU really there (CTK_SGPR_8WAVES), us per launch: 480 steps 2 rows 371 | 3: 332-349 | 4: 353-367 | 5: 337-345 |
@@ -2270,8 +2164,6 @@ static int relabel_rows(const ctk_handle *h)
     // -> the smallest chunk that keeps the launch at or below ~130 000 workgroups (it was 250 000).
     while (rb < rb_max && h->T * ((h->ny + rb - 1) / rb) > 130000) rb++;
     while (rb < h->ny && h->T * ((h->ny + rb - 1) / rb) >= (1 << 24)) rb++;
-    if (ctk_env().relabel_rows > 0) rb = std::min(h->ny, ctk_env().relabel_rows);
-    if (h->relabel_rows_dbg > 0) rb = std::min(h->ny, h->relabel_rows_dbg);
     return rb;
 }
 static bool relabel_fast_ok(const ctk_handle *h, const int32_t *flag_dev, int rb)
@@ -2309,9 +2201,8 @@ static int launch_relabel(ctk_handle *h, int persistence, int32_t *flag_dev, boo
     a.nrows = nt * h->ny; a.ny = h->ny; a.nx = h->nx; a.W = h->W;
     a.chunk_vals = chunk_vals ? chunk_vals + t0 * nchunk * CTK_CV : nullptr;
     a.guard = h->guard_on ? P<uint32_t>(h->counters) : nullptr;
-    a.plain_stores = ctk_env().relabel_plain ? 1 : 0;
-    a.xcd_remap = h->xcd_rel >= 0 ? h->xcd_rel : (h->xcd_rel_tuned >= 0 ? h->xcd_rel_tuned : ctk_env().xcd_rel);
-    a.fast_zero = h->relabel_threads == 257 ? 1 : 0;       // (experiment, off: NOTES round 4)
+    a.plain_stores = 0; a.fast_zero = 0;                   // (kept in the kernel for its register allocation: ctk_kernels.hip, RelabelArgs)
+    a.xcd_remap = h->xcd_rel_tuned >= 0 ? h->xcd_rel_tuned : 0;
     a.tab_batched = nt * nchunk < 200000 ? 1 : 0;          // (1 deg, 480 x 0.25 deg: -4 %; 14 600 x 0.25 deg: +2.7 % -- NOTES round 4)
     const int64_t npl = (int64_t)h->ny * h->nx;
     const int rvcap = 2048;
@@ -2324,30 +2215,22 @@ static int launch_relabel(ctk_handle *h, int persistence, int32_t *flag_dev, boo
         const int rv5 = 512;
         const size_t tab5 = (size_t)rb * h->W * 8 + (((size_t)rb * h->W * 2 + 7) & ~(size_t)7) + ((((size_t)rb + 1) * 4 + 7) & ~(size_t)7) +
                             (((size_t)rv5 * 4 + 15) & ~(size_t)15) + 16;
-        // threads per workgroup: 256; wider (experiment, CTK_RELABEL_THREADS / ctk_debug_set_relabel_threads) gives a tall chunk fewer
-        // stores per lane at the same number of workgroups -- the LDS budget grows with the waves (same occupancy in waves per CU)
-        const int th = h->relabel_threads > 0 ? h->relabel_threads : (ctk_env().relabel_threads > 0 ? ctk_env().relabel_threads : 256);
         // 20 KB = eight workgroups of 256 threads per CU.  A chunk that needs three or more images at that size gets 24 or 28 KB (six / five
         // workgroups per CU) if that brings it down to two: 14 600 x 721 x 1440 in 6-row chunks (34 KB of values) 11.46 -> 10.55 ms,
         // 2000 steps 1.55 -> 1.47; 32 KB: 14.1 ms (four per CU); 438 000 x 192 x 288 in 96-row chunks: 9 or 6 images, no difference
-        // (tools/cesm_relabel_sweep.py, CTK_RELABEL_LDS_KB)
-        static const int lds_kb_env = getenv("CTK_RELABEL_LDS_KB") ? atoi(getenv("CTK_RELABEL_LDS_KB")) : 0;
         auto rows_per_image = [&](size_t bud) { int q = rb; while (q > 1 && tab5 + (size_t)q * h->nx * 4 > bud) q--; return q; };
-        size_t budget = (size_t)(lds_kb_env > 0 ? lds_kb_env : 20) * 1024 * (size_t)th / 256;
+        size_t budget = (size_t)20 * 1024;
         int sub = rows_per_image(budget);
-        if (lds_kb_env <= 0 && (rb + sub - 1) / sub > 2)
+        if ((rb + sub - 1) / sub > 2)
             for (int kb = 24; kb <= 28; kb += 4) {
-                const size_t b2 = (size_t)kb * 1024 * (size_t)th / 256;
+                const size_t b2 = (size_t)kb * 1024;
                 const int s2 = rows_per_image(b2);
                 if ((rb + s2 - 1) / s2 <= 2) { budget = b2; sub = s2; break; }
             }
         const size_t lds5 = tab5 + (size_t)sub * h->nx * 4;
-        if (lds5 <= budget && !ctk_env().relabel_v4) {
-            if (h->rel_probe && th == 256) k_relabel_probe<256><<<grid, 256, lds5, h->stream>>>(a, rb, rv5, sub);      // (tune_relabel's launches: their own kernel name)
-            else if (th == 1024) k_relabel_v5<1024><<<grid, 1024, lds5, h->stream>>>(a, rb, rv5, sub);
-            else if (th == 512) k_relabel_v5<512><<<grid, 512, lds5, h->stream>>>(a, rb, rv5, sub);
-            else if (th == 128) k_relabel_v5<128><<<grid, 128, lds5, h->stream>>>(a, rb, rv5, sub);
-            else if (h->rel_variant == 1 || (h->rel_variant < 0 && getenv("CTK_RELABEL_SGPR") && atoi(getenv("CTK_RELABEL_SGPR")) == 0)) k_relabel_v5_allsgpr<256><<<grid, 256, lds5, h->stream>>>(a, rb, rv5, sub);
+        if (lds5 <= budget) {
+            if (h->rel_probe) k_relabel_probe<256><<<grid, 256, lds5, h->stream>>>(a, rb, rv5, sub);      // (tune_relabel's launches: their own kernel name)
+            else if (h->rel_variant == 1) k_relabel_v5_allsgpr<256><<<grid, 256, lds5, h->stream>>>(a, rb, rv5, sub);
             else k_relabel_v5<256><<<grid, 256, lds5, h->stream>>>(a, rb, rv5, sub);
             h->stats[CTK_S_RELABEL_KERNEL] = 5;
         }
@@ -2419,7 +2302,7 @@ extern "C" int ctk_shard_count_tracked(ctk_handle *h, int64_t *n_alive)
 // ------------------------------------------------------------------------------------------------
 static bool async_wanted(ctk_handle *h)
 {
-    if (h->use_async < 0) { const char *e = getenv("CTK_ASYNC"); h->use_async = (e && atoi(e) == 0) ? 0 : 1; }
+    if (h->use_async < 0) h->use_async = ctk_env().async ? 1 : 0;
     return h->use_async == 1 && h->in_one_call && !h->sio && h->T >= 1 && !(h->async_off_ny == h->ny && h->async_off_nx == h->nx);
 }
 
@@ -2482,9 +2365,9 @@ static int resolve_async(ctk_handle *h, double overlap, int twosided, int persis
     sd.lab_cap = h->debug_sd_lab ? std::min(h->debug_sd_lab, SD_LAB) : SD_LAB; sd.ops_cap = h->debug_sd_ops ? std::min(h->debug_sd_ops, 64) : 64;
     h->d_op_next = sd.op_next;
     h->nops = 1;                                                  // (unknown here; nonzero = the folds look at the chains)
-    // filter passes: all of them in one launch (k_rs_pass_sys, at most 24 iterations) when every workgroup of the launch can wait
+    // filter passes: all of them in one launch (k_rs_pass_blk, at most 24 iterations) when every workgroup of the launch can wait
     // for its predecessor, else one launch per pass
-    const bool sys = !ctk_env().pass_launches && !h->no_sys && h->async_passes <= 24;
+    const bool sys = !h->no_sys && h->async_passes <= 24;
     const int NP = T > 2 ? std::min(std::max(h->async_passes, 2), sys ? 24 : CTK_MAX_JACOBI) : 0;
     if (sys) { CTKCHK(ensure(h, h->rv_pstate, (size_t)(T + 1) * 4 * CTK_PSTATE_STRIDE)); r.pstate = P<uint32_t>(h->rv_pstate); }
     h->guard_on = true;
@@ -2495,22 +2378,19 @@ static int resolve_async(ctk_handle *h, double overlap, int twosided, int persis
             k_rs_init<<<gc, 256, 0, s>>>(r);
             k_rs_pairs<<<gp, 256, 0, s>>>(r);
         }
-        if (!(sys && NP > 0)) k_rs_prep<<<gc, 256, 0, s>>>(r);         // (k_rs_pass_sys does it for its own timestep)
-        // (grid: the filtered timesteps 1 .. T-2 and T-1, whose workgroup only unites its pairs)
-        static const bool pass_blk = !getenv("CTK_PASS_SYS");           // (the one-wave-per-workgroup form, for comparison)
-        if (sys && NP > 0 && pass_blk) {
+        if (!(sys && NP > 0)) k_rs_prep<<<gc, 256, 0, s>>>(r);         // (k_rs_pass_blk does it for its own timesteps)
+        // (timesteps 1 .. T-2 are filtered; T-1's wave only unites its pairs)
+        if (sys && NP > 0) {
             const int nb = (int)((T - 1 + PB_G - 1) / PB_G);
             launch_rs_pass_blk(h, nb > h->n_cus, nb, r, 0, NP, in.pair_base, in.pair_cnt, r.pstate, 1, 1);      // (two workgroups per CU when nb > CUs: ctk_resolve_dev.hip)
         }
-        else if (sys && NP > 0) launch_rs_pass_sys(h, (int)(T - 1), r, 0, NP, in.pair_base, in.pair_cnt, r.pstate, 1, 1);
         else
             for (int it = 0; it < NP; it++)
                 launch_rs_pass(h, (int)(T - 2), r, it, in.pair_base, in.pair_cnt, P<uint8_t>(h->rv_tdirty));
-        if (sys && NP > 0) { /* united by k_rs_pass_sys */ }
+        if (sys && NP > 0) { /* united by k_rs_pass_blk */ }
         else if (h->fz_pslot) k_rs_unite_slots<<<(int)std::min<int64_t>((T * h->fz_pslot + 255) / 256 + 1, 4096), 256, 0, s>>>(r, in.pair_cnt, h->fz_pslot);
         else k_rs_unite<<<gp, 256, 0, s>>>(r);
-        static const bool rank_mark = !getenv("CTK_NO_RANK_MARK");
-        const bool merged = rank_mark && nsb <= CTK_RL_BLOCKS;
+        const bool merged = nsb <= CTK_RL_BLOCKS;
         if (!merged) r.lab_root = nullptr;
         k_rs_roots<<<nsb, 256, 0, s>>>(r, P<uint32_t>(h->rv_bsum));
         if (merged) {
@@ -2553,8 +2433,7 @@ static int resolve_async(ctk_handle *h, double overlap, int twosided, int persis
     am.changed = r.changed; am.ambig = r.ambig; am.rec_cnt = P<uint32_t>(h->rv_cand_cnt); am.t_nops = sd.t_nops; am.pair_cnt = in.pair_cnt; am.t_alive = P<uint32_t>(h->seam_off); am.T = T; am.passes = NP;
     {
         Timer tm(h, CTK_K_COUNT);
-        static const bool count_f = !getenv("CTK_COUNT_OLD");
-        if (h->last_nlab <= 1000000 && NP <= 32 && count_f)      // (one round of loads, one barrier: round 6)
+        if (h->last_nlab <= 1000000 && NP <= 32)      // (one round of loads, one barrier: round 6)
             k_count_alive_f<<<1, 1024, 0, s>>>(P<uint32_t>(h->counters), h->h_mail1 + 8, am);
         else if (h->last_nlab <= 1000000)             // (the previous pass' id count: a slab of the same kind)
             k_count_alive_1<<<1, 1024, 0, s>>>(P<int32_t>(h->ext), h->n_labels, persistence, P<uint32_t>(h->counters), h->h_mail1 + 8, am);
@@ -2568,8 +2447,7 @@ static int resolve_async(ctk_handle *h, double overlap, int twosided, int persis
         // stamp instead of waiting for the stream's completion signal (which arrives several microseconds later); every kernel
         // of the pass has finished when the stamp is there -- they run in stream order.  The health check is rare (a query on a
         // busy stream enqueues a marker).
-        static const bool poll_env = !getenv("CTK_SYNC_STREAM");
-        const bool poll = poll_env && h->timing < 2;                   // (level-2 timing has an event BEHIND the last kernel: wait for the stream)
+        const bool poll = h->timing < 2;                  // (level-2 timing has an event BEHIND the last kernel: wait for the stream)
         volatile uint32_t *vm = h->h_amail;
         bool done = false;
         if (poll)
@@ -2634,11 +2512,11 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
 
 // How the chunks of the write kernel are dealt to the XCDs decides a few per cent of its time, and which way is best depends on the
 // grid and on where the caller's `flag` lies (2707 x 181 x 360: one contiguous eighth per XCD -5 ... -8 % against launch order,
-// 480 x 721 x 1440: launch order best by 2-5 %; tools/xcd_probe.py).  After the first pass on a new shape / output buffer the kernel is
+// 480 x 721 x 1440: launch order best by 2-5 %; NOTES round 4).  After the first pass on a new shape / output buffer the kernel is
 // timed in the three ways on the finished tables (it writes the same flags again) and the fastest kept.  ~1 ms, once.
 static void tune_relabel(ctk_handle *h, int persistence, int32_t *flag_dev)
 {
-    if (h->xcd_rel >= 0 || !ctk_env().mask_tune || h->sio || h->rle_out || !flag_dev || h->state != ST_TABLES) return;
+    if (!ctk_env().mask_tune || h->sio || h->rle_out || !flag_dev || h->state != ST_TABLES) return;
     // once per SHAPE (round 4 also keyed on the output pointer: a caller that alternates output buffers re-tuned on every call --
     // advisor finding); slabs beyond 8 GB keep the launch order (nine extra passes of the write kernel would cost ~100 ms at
     // 14 600 x 721 x 1440, where launch order measured best anyway)
@@ -2916,8 +2794,8 @@ static size_t rle_need(const uint32_t *run_base, int64_t T, int ny, int W)
 static bool rle_blocks(const uint32_t *run_base, int64_t T, int ny, int W, size_t cap, std::vector<RleBlock> &out)
 {
     const size_t per_t = rle_per_t(ny, W);
-    const int lanes_cfg = ctk_env().rle_lanes > 0 ? std::min(ctk_env().rle_lanes, kRleLanes) : kRleLanes, per_lane = ctk_env().rle_per_lane > 0 ? ctk_env().rle_per_lane : 8;
-    const int64_t want = std::max<int64_t>(1, (T + lanes_cfg * per_lane - 1) / (lanes_cfg * per_lane));        // ~8 blocks per lane (probe: tools/exp/rle_probe.py)
+    const int per_lane = 8;
+    const int64_t want = std::max<int64_t>(1, (T + kRleLanes * per_lane - 1) / (kRleLanes * per_lane));        // ~8 blocks per lane (probe: tools/exp/rle_probe.py)
     out.clear();
     for (int64_t t0 = 0; t0 < T;) {
         int64_t nt = 0;
@@ -2976,7 +2854,7 @@ static int deliver_runs(ctk_handle *h, int persistence, int32_t *flag, int *wrot
     if (!h->rle || !h->rle->init(rle_need(rb.data(), T, ny, W))) { (void)ctk_set_error(CTK_E_NOMEM, "result transfer: no pinned memory for the lane buffers"); return CTK_RLE_UNAVAILABLE; }
     if (!rle_blocks(rb.data(), T, ny, W, h->rle->cap, blocks)) { (void)ctk_set_error(CTK_E_INTERNAL, "result transfer: a timestep's tables do not fit a lane buffer"); return CTK_RLE_UNAVAILABLE; }
     const size_t nb = blocks.size();
-    const int lanes = (int)std::min<size_t>(ctk_env().rle_lanes > 0 ? std::min(ctk_env().rle_lanes, kRleLanes) : kRleLanes, nb);
+    const int lanes = (int)std::min<size_t>(kRleLanes, nb);
     std::atomic<int64_t> wait_us(0), exp_us(0);
     std::atomic<bool> ok(true), zero(false);
     std::vector<unsigned char> cx(nb, 0);                                          // blocks that hold a run of a complex component
@@ -3013,13 +2891,7 @@ static int deliver_runs(ctk_handle *h, int persistence, int32_t *flag, int *wrot
         (void)hipStreamSynchronize(L.st);                                             // (nothing of this call is left in flight on an error path)
     };
     const double tr1 = now_ms();
-    static const bool fresh_threads = getenv("CTK_RLE_FRESH_THREADS") != nullptr;      // (round 4's form, for comparison)
-    if (fresh_threads) {
-        std::vector<std::thread> th;
-        th.reserve((size_t)lanes);
-        for (int i = 0; i < lanes; i++) th.emplace_back(work, i);
-        for (auto &t : th) t.join();
-    } else if (!h->rle->crew.run(lanes, work)) ok = false;
+    if (!h->rle->crew.run(lanes, work)) ok = false;
     if (ctk_env().hosttrace) fprintf(stderr, "runs: %zu blocks on %d lanes | setup %.2f ms, lanes %.2f ms (per lane: waiting %.2f, expanding %.2f)\n", nb, lanes, tr1 - tr_begin, now_ms() - tr1, wait_us / 1e3 / lanes, exp_us / 1e3 / lanes);
     if (!ok) { (void)ctk_set_error(CTK_E_NODEVICE, "result transfer (run tables) failed: %s", hipGetErrorString(hipGetLastError())); return CTK_RLE_UNAVAILABLE; }
     // blocks with complex components: the write kernel, block by block
@@ -3389,8 +3261,6 @@ static_assert(sizeof(ctk_life_row) == sizeof(CtkLifeRowDev), "row layouts must a
 // as the launch keeps a few thousand workgroups.
 static int life_rows_per_wave(int64_t T, int ny, int nx)
 {
-    static const int env = getenv("CTK_LIFE_ROWS") ? atoi(getenv("CTK_LIFE_ROWS")) : 0;
-    if (env > 0) return env;
     const int64_t nsx = (nx + LB_SW - 1) / LB_SW;
     int g = std::max(1, (ny + 80) / 160);
     while (T * nsx * g < 2048 && (ny + 4 * g - 1) / (4 * g) > 8) g++;

@@ -127,9 +127,9 @@ __device__ __forceinline__ void uf_unite(uint32_t *p, uint32_t a, uint32_t b)
 // thr[t] is the threshold the host derived so that the compare in the slab's dtype equals the
 // reference's compare (ctk_api: adjust_threshold).
 //
-// k_threshold_v4 (float32, nx % 4 == 0, 16-byte aligned slab): one workgroup per (timestep, 16 rows);
-// every lane issues 8 independent non-temporal float4 loads, the 4 compare bits of a lane are ORed across
-// its 16-lane group (64 pixels = one mask word) with 4 cross-lane steps, lane 0 of the group stores the word.
+// k_threshold_v7 (float32, nx % 4 == 0, 16-byte aligned slab): one workgroup per (timestep, 16 rows), non-temporal float4
+// loads, the 4 compare bits of a lane ORed across its 16-lane group (64 pixels = one mask word).
+// k_threshold_v6 (float32, W <= 64, where v7 does not apply): one ballot per 64 pixels.
 // k_threshold (generic: any nx, float32 / float64): lane l tests pixel 64k+l, __ballot packs a word.
 // ------------------------------------------------------------------------------------------------
 template <int OP, typename TIN>
@@ -158,7 +158,7 @@ __device__ __forceinline__ uint32_t row16_or(uint32_t v)
 }
 
 // Workgroup b of a launch lands on XCD b % 8 (round-robin dispatch).  With `on`, the chunk a workgroup takes is remapped so that every
-// XCD streams ONE contiguous eighth of the slab instead of every eighth chunk (experiment, CTK_XCD_REMAP).
+// XCD streams ONE contiguous eighth of the slab instead of every eighth chunk (on == 1), or tiles of `on` consecutive chunks (on > 1).
 __device__ __forceinline__ unsigned xcd_chunk(unsigned b, unsigned n, int on)
 {
     if (!on) return b;
@@ -185,52 +185,8 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 #define CTK_SGPR_8WAVES __attribute__((amdgpu_num_sgpr(80)))
 #define CTK_RB 16                  // rows per workgroup in the two streaming kernels
 
-template <int OP, int U = 8 /* independent 16-byte loads in flight per lane (8 vs 4: 2.5 % at 1 deg, equal at 0.25 deg) */>
-__global__ __launch_bounds__(256) void k_threshold_v4(const float *__restrict__ anom, const float *__restrict__ thr32,
-                                                      int ny, int nx, int W, uint64_t *__restrict__ mask, int rb,
-                                                      uint32_t *__restrict__ zero_counters /* the pass' device counters start at zero (or nullptr) */)
-{
-    if (zero_counters && blockIdx.x == 0 && threadIdx.x < CTK_CNT_ZEROED) zero_counters[threadIdx.x] = 0u;
-    const int nchunk = (ny + rb - 1) / rb;
-    const int t = (int)(blockIdx.x / (unsigned)nchunk), y0 = (int)(blockIdx.x - (unsigned)t * nchunk) * rb, tid = (int)threadIdx.x;
-    const int rows = min(rb, ny - y0);
-    const float th = thr32[t];
-    const int n4 = nx >> 2, n4p = (n4 + 15) & ~15;         // float4 slots per row, padded to whole 16-lane groups (= words)
-    const int total = rows * n4p;
-    const int64_t row0 = (int64_t)t * ny + y0;
-    const float *base = anom + row0 * (int64_t)nx;
-    const int sub = tid & 15;
-    // (row, slot) of the lane's next load, advanced by 256 slots at a time without dividing
-    int nr = tid / n4p, nc = tid - nr * n4p;
-    const int dr = 256 / n4p, dc = 256 - dr * n4p;
-    for (int i0 = 0; i0 < total; i0 += 256 * U) {
-        f32x4 v[U];
-        int rr[U], cc[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int i = i0 + u * 256 + tid;
-            const int r = nr, c = nc;
-            rr[u] = r; cc[u] = c;
-            if (i < total && c < n4) v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(base + (int64_t)r * nx) + c);
-            else v[u] = (f32x4)(__builtin_nanf(""));
-            nr += dr; nc += dc;
-            if (nc >= n4p) { nc -= n4p; nr++; }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint32_t nib = (cmp_op<OP, float>(v[u].x, th) ? 1u : 0u) | (cmp_op<OP, float>(v[u].y, th) ? 2u : 0u) |
-                                 (cmp_op<OP, float>(v[u].z, th) ? 4u : 0u) | (cmp_op<OP, float>(v[u].w, th) ? 8u : 0u);
-            // lanes 16g .. 16g+15 hold the 64 pixels of one word: place the nibble, OR across the group
-            uint32_t lo = (sub < 8) ? (nib << (4 * sub)) : 0u, hi = (sub >= 8) ? (nib << (4 * (sub - 8))) : 0u;
-            lo = row16_or(lo);
-            hi = row16_or(hi);
-            if (sub == 0 && i0 + u * 256 + tid < total) mask[(row0 + rr[u]) * W + (cc[u] >> 4)] = ((uint64_t)hi << 32) | lo;
-        }
-    }
-}
-
-// k_threshold_v7: k_threshold_v4's decomposition (one workgroup per (timestep, rb rows), 16-byte non-temporal loads, a 16-lane
-// DPP row = 64 pixels = one mask word) with a third of its VALU work.  SQ counters (profiles/r04_sq_1deg.md) showed v4 to be
+// k_threshold_v7: one workgroup per (timestep, rb rows), 16-byte non-temporal loads, a 16-lane DPP row = 64 pixels = one mask
+// word -- the decomposition of round 4's k_threshold_v4 with a third of its VALU work.  SQ counters (profiles/r04_sq_1deg.md) showed v4 to be
 // VALU-bound, not memory-bound: 446 VALU instructions per wave = 85 % of every SIMD's issue slots for the 125 us the kernel ran --
 // 58 per float4 load, most of them 64-bit address arithmetic, lane predicates and the two-register (lo / hi) 16-lane reduction.
 // Here: 32-bit byte offsets from a wave-uniform base (saddr form), (row, slot) advanced without divisions, the four compare
@@ -454,12 +410,11 @@ template <int OP, int U>
 __global__ __launch_bounds__(256) void k_threshold_field(const float *__restrict__ anom, const float *__restrict__ fld,
                                                          const int32_t *__restrict__ pos, const int32_t *__restrict__ order,
                                                          int ny, int nx, int W, uint64_t *__restrict__ mask, int rb,
-                                                         uint32_t *__restrict__ zero_counters, int xcd)
+                                                         uint32_t *__restrict__ zero_counters)
 {
     if (zero_counters && blockIdx.x == 0 && threadIdx.x < CTK_CNT_ZEROED) zero_counters[threadIdx.x] = 0u;
     const int nchunk = (ny + rb - 1) / rb;
-    // (xcd = 1: one contiguous eighth of the plane-major order per XCD -- the steps of a plane then share ONE XCD's L2)
-    const unsigned bid = xcd_chunk(blockIdx.x, gridDim.x, xcd);
+    const unsigned bid = blockIdx.x;
     const unsigned si = bid / (unsigned)nchunk;
     const int t = order[si], plane = pos[t];                // wave-uniform: scalar loads
     const int y0 = (int)(bid - si * (unsigned)nchunk) * rb, tid = (int)threadIdx.x;
@@ -1881,8 +1836,11 @@ struct RelabelArgs {
     int ny, nx, W;
     const int32_t *chunk_vals;     // [T][nchunk][CTK_CV] (k_run_values) or nullptr
     const uint32_t *guard;         // see ctk_guard_bad
-    int plain_stores;              // experiment: plain instead of non-temporal stores
-    int xcd_remap;                 // experiment: every XCD streams one contiguous eighth of the slab (xcd_chunk)
+    // plain_stores / fast_zero: forms no launch selects (the host passes 0).  They stay because k_relabel_v5 compiled without their
+    // two branches allocates its registers differently and measured 1-16 % slower on the same tables (same-handle A/B of the three
+    // chunk -> XCD orders, 1 deg and 0.25 deg bench slabs)
+    int plain_stores;              // plain instead of non-temporal stores
+    int xcd_remap;                 // k_relabel_v5: chunk -> XCD mapping (xcd_chunk; tune_relabel picks it per shape)
     int fast_zero;                 // k_relabel_v5: a chunk without a run is written as zeros straight from registers (no LDS image)
     int tab_batched;               // k_relabel_v5: the chunk's tables in one round of unconditional loads (launches below ~200 000 workgroups)
 };
@@ -1974,7 +1932,7 @@ __device__ unsigned long long g_rel_acc[4096];       // [0..1023] sums of (end -
 #define REL_OUT() do { } while (0)
 #define REL_MARK(k) do { } while (0)
 #endif
-template <int TH /* threads: 256; 512 / 1024 for tall chunks (fewer stores per lane at the same number of workgroups) */>
+template <int TH /* threads per workgroup: 256 */>
 __device__ __forceinline__ void relabel_v5_body(const RelabelArgs &a, int rb, int rvcap, int sub /* rows per LDS image: rb, or less for tall chunks */)
 {
     REL_IN();
@@ -2119,7 +2077,7 @@ __device__ __forceinline__ void relabel_v5_body(const RelabelArgs &a, int rb, in
 template <int TH>
 __global__ __launch_bounds__(TH) CTK_SGPR_8WAVES void k_relabel_v5(RelabelArgs a, int rb, int rvcap, int sub) { relabel_v5_body<TH>(a, rb, rvcap, sub); }
 template <int TH>
-__global__ __launch_bounds__(TH) void k_relabel_v5_allsgpr(RelabelArgs a, int rb, int rvcap, int sub) { relabel_v5_body<TH>(a, rb, rvcap, sub); }      // (A/B: CTK_RELABEL_SGPR=0)
+__global__ __launch_bounds__(TH) void k_relabel_v5_allsgpr(RelabelArgs a, int rb, int rvcap, int sub) { relabel_v5_body<TH>(a, rb, rvcap, sub); }      // (A/B: ctk_debug_time_relabel variant 1)
 // the same code under another name: the launches that time the chunk -> XCD mapping once per shape (tune_relabel, ctk_api.hip) -- kept
 // apart so that a profile's statistics of k_relabel_v5 are those of the passes (as k_threshold_probe does for the mask placement check)
 template <int TH>

@@ -76,7 +76,7 @@ struct ResolveDev {
     int32_t *ext;                         // time extents of the ids, reset by k_rs_roots: ext[l] = min t, ext[ext_off + l] = max t
     int64_t ext_off;
     uint32_t *counters_w;                 // the write-stage counters are reset by k_rs_roots as well
-    uint32_t *pstate;                     // [T + 1] k_rs_pass_sys: per timestep (iterations done) << 24 | changed bits; zeroed by k_rs_init
+    uint32_t *pstate;                     // [T + 1] k_rs_pass_blk*: per timestep (iterations done) << 24 | changed bits; zeroed by k_rs_init
     // Inter-workgroup waits of the systolic filter kernels are BOUNDED (HIP promises nothing about dispatch order; a wait for a
     // workgroup that is not resident would be a hung GPU): a wait that lasts longer than spin_limit ticks of the 100 MHz wall clock
     // gives up -- CTK_POISON_SPIN in *poison, the wave publishes a "poisoned" state word so that nobody waits for IT, and the pass is
@@ -101,7 +101,7 @@ __device__ __forceinline__ bool spin_expired(SpinGuard &g, uint64_t limit)
 }
 #define CTK_PSTATE_POISONED 0xffffffffu       // "published everything" for whoever waits: the pass is invalid anyway
 
-#define CTK_PSTATE_STRIDE 32        // words between the per-timestep state words of k_rs_pass_sys: one 128-byte line each (the words are
+#define CTK_PSTATE_STRIDE 32        // words between the per-timestep state words of k_rs_pass_blk*: one 128-byte line each (the words are
                                     // polled with device-scope loads: neighbours in one line would all hit the same memory channel)
 #define CTK_CHG_SLOTS 64            // 'changed' words per filter pass (= wave width: one ballot reads them)
 #define CTK_MAX_JACOBI 240          // hard cap of filter passes on the device (then: host resolver)
@@ -220,38 +220,6 @@ __global__ void k_rs_pairs(ResolveDev r)
     }
 }
 
-// k_rs_pairs on pair records in fixed per-timestep slots (k_overlap with pslot, time-shard path): thread = slot, + the ungrouped ones
-__global__ void k_rs_pairs_slots(ResolveDev r, const uint32_t *__restrict__ pair_cnt, uint32_t pslot)
-{
-    if (!dev_tables_bad(r)) {
-        const uint64_t nslots = (uint64_t)r.T * pslot;
-        const uint32_t nu = dev_nungrouped(r);
-        for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < nslots + nu; k += (uint64_t)gridDim.x * blockDim.x) {
-            uint32_t i;
-            if (k < nslots) {
-                const uint32_t t = (uint32_t)(k / pslot), j = (uint32_t)(k - (uint64_t)t * pslot);
-                if (j >= pair_cnt[t]) continue;
-                i = (uint32_t)k;
-            } else i = r.pair_cap - 1u - (uint32_t)(k - nslots);
-            const CtkPair p = r.pairs[i];
-            const uint32_t cb = r.cprefix[p.t], db = r.cprefix[(int32_t)p.t - 1];
-            const uint32_t gc = cb + p.c, gd = db + p.d;
-            const uint32_t rc = cb + r.mrep[gc], rd = db + r.mrep[gd];
-            r.p_gc[i] = gc; r.p_gd[i] = gd; r.p_rc[i] = rc; r.p_rd[i] = rd;
-            atomicAdd((unsigned long long *)&r.F[2 * (int64_t)rd], (unsigned long long)p.lo);
-            atomicAdd((unsigned long long *)&r.F[2 * (int64_t)rd + 1], (unsigned long long)p.hi);
-        }
-    }
-    const uint32_t nc = dev_tables_bad(r) ? 0u : dev_ncomps(r);
-    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < nc; g += gridDim.x * blockDim.x) {
-        const uint16_t *q = r.box + 4 * (int64_t)g;
-        if (r.next_tiny[q[0]] <= (int32_t)q[1]) {
-            const uint32_t rep = r.cprefix[(int32_t)r.comp_t[g]] + r.mrep[g];
-            if (r.touch[rep] == 0u) atomicOr(&r.touch[rep], 1u);
-        }
-    }
-}
-
 // 1/areacon and the forward fraction do not change between passes
 __device__ __forceinline__ void dev_prep_comp(const ResolveDev &r, uint32_t g, double *inv_out, double *ff_out, bool *inex_out = nullptr)
 {
@@ -296,7 +264,7 @@ __global__ void k_rs_prep(ResolveDev r)
 // pairs / components] -> [keep bits of the pairs' predecessors].
 // SEG (segment breaks, ctk_set_segments): a timestep with seg_edge[t] != 0 is the first or the last step of a segment and is not
 // filtered (contrack.py:706, range(1, T-1) of each segment): its keep bits stay 1 and it reports "unchanged".  seg_edge is read by the
-// SEG = true builds only; the unsegmented call launches SEG = false (k_rs_pass, k_rs_pass_sys, k_rs_pass_blk*), code as it was.
+// SEG = true builds only; the unsegmented call launches SEG = false (k_rs_pass, k_rs_pass_blk*), code as it was.
 template <bool SEG>
 __global__ __launch_bounds__(64) void k_rs_pass(ResolveDev r, int it, const uint32_t *__restrict__ pair_base, const uint32_t *__restrict__ pair_cnt,
                                                 uint8_t *__restrict__ tdirty, const uint8_t *__restrict__ seg_edge)
@@ -421,184 +389,8 @@ __global__ __launch_bounds__(64) void k_rs_pass(ResolveDev r, int it, const uint
 // three dependent round trips + the launch, 4.7 us a pass, 47-56 us for the ten to twelve passes of the bench slab).  An
 // iteration whose predecessor did not change in the previous one does nothing but publish its word.  K <= 24.
 // changed[] (per pass, read by the host / the mailbox) is kept as k_rs_pass keeps it.
-// ------------------------------------------------------------------------------------------------
-template <bool SEG>
-__global__ __launch_bounds__(64) void k_rs_pass_sys(ResolveDev r, int it0, int K, const uint32_t *__restrict__ pair_base, const uint32_t *__restrict__ pair_cnt,
-                                                    uint32_t *__restrict__ pstate /* [T + 1], zeroed */, int prep_inline /* k_rs_prep's work for this timestep first */,
-                                                    int do_unite /* k_rs_unite's work for the pairs of this timestep last; the grid then also covers t_hi + 1 .. T - 1 */,
-                                                    const uint8_t *__restrict__ seg_edge)
-{
-    if (dev_tables_bad(r)) return;
-    const int Kfull = K;
-    const int t = (int)blockIdx.x + r.t_lo;
-    const int lane = (int)threadIdx.x;
-    // round trip 1
-    const uint32_t cb = r.cprefix[t], ce = r.cprefix[t + 1];
-    const uint32_t pb = pair_base[t], pn = pair_cnt[t];
-    const uint32_t nu = dev_nungrouped(r);
-    const uint32_t nct = ce - cb;
-    const bool filtered = t <= r.t_hi;                     // (workgroups behind t_hi only unite their pairs)
-    if (!filtered) K = 0;
-    const bool seg_keep = SEG && filtered && seg_edge[t];  // first / last step of a segment: publishes its iterations, never evaluates
-    __shared__ long long Bl[2 * CTK_PASS_COMPS];
-    const bool lds = nct <= CTK_PASS_COMPS;
-    long long *B = lds ? Bl : (long long *)(r.B + 2 * (int64_t)cb);
-    // round trip 2: first pair and first component of this lane (constant over the iterations)
-    uint8_t *keep = r.keep0;
-    const bool has_p = (uint32_t)lane < pn, has_c = (uint32_t)lane < nct;
-    const uint32_t k0 = pb + lane, g0 = cb + lane;
-    const uint32_t rd0 = has_p ? r.p_rd[k0] : 0u, rc0 = has_p ? r.p_rc[k0] : 0u;
-    CtkPair p0;
-    if (has_p) p0 = r.pairs[k0]; else { p0.lo = 0; p0.hi = 0; }
-    const uint32_t mrep0 = has_c ? r.mrep[g0] : 0xffffffffu;
-    double inv0 = 0.0, ff0 = 0.0;
-    if (prep_inline && filtered) {
-        for (uint32_t c = lane; c < nct; c += 64) {
-            double a, b;
-            dev_prep_comp(r, cb + c, &a, &b);
-            if (c == (uint32_t)lane) { inv0 = a; ff0 = b; }
-        }
-        if (nct > 64) __syncthreads();                     // (components beyond the first 64 are re-read from memory below)
-    } else if (has_c) { inv0 = r.inv[g0]; ff0 = r.ff[g0]; }
-    uint8_t kold0 = has_c ? __hip_atomic_load(&keep[g0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (uint8_t)0;
-    const bool dyn_pred = t > r.t_lo;                      // the predecessor is filtered by this launch too
-    uint32_t mybits = 0;
-    for (int k = 0; k < K; k++) {
-        const int it = it0 + k;
-        bool evaluate = k == 0;
-        if (k > 0 && dyn_pred) {
-            uint32_t st;
-            // relaxed polls (an acquire load invalidates the caches on EVERY poll: 2705 waves doing that made an iteration cost 95 us);
-            // the bits are read with device-scope loads, which need no invalidation
-            SpinGuard sg;
-            bool gave_up = false;
-            while (((st = __hip_atomic_load(&pstate[(size_t)(t - 1) * CTK_PSTATE_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 24) < (uint32_t)k) {
-                __builtin_amdgcn_s_sleep(2);
-                if (spin_expired(sg, r.spin_limit)) { gave_up = true; break; }
-            }
-            if (gave_up) {
-                if (lane == 0) { atomicOr(r.poison, CTK_POISON_SPIN); __hip_atomic_store(&pstate[(size_t)t * CTK_PSTATE_STRIDE], CTK_PSTATE_POISONED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-                return;
-            }
-            evaluate = (st >> (k - 1)) & 1u;
-        }
-        bool wave_any = false;
-        if (SEG && seg_keep) evaluate = false;
-        if (evaluate) {
-            if (lds) for (uint32_t c = lane; c < 2 * nct; c += 64) Bl[c] = 0;
-            const uint8_t kd0 = has_p ? __hip_atomic_load(&keep[rd0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (uint8_t)0;
-            __syncthreads();
-            if (has_p && kd0) {
-                const uint32_t c = rc0 - cb;
-                atomicAdd((unsigned long long *)&B[2 * c], (unsigned long long)p0.lo);
-                atomicAdd((unsigned long long *)&B[2 * c + 1], (unsigned long long)p0.hi);
-            }
-            for (uint32_t i = lane + 64; i < pn; i += 64) {            // timesteps with more than 64 pair records
-                const uint32_t kk = pb + i;
-                if (!__hip_atomic_load(&keep[r.p_rd[kk]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) continue;
-                const CtkPair p = r.pairs[kk];
-                const uint32_t c = r.p_rc[kk] - cb;
-                atomicAdd((unsigned long long *)&B[2 * c], (unsigned long long)p.lo);
-                atomicAdd((unsigned long long *)&B[2 * c + 1], (unsigned long long)p.hi);
-            }
-            if (nu) {                                                   // records that bypassed the hash table (rare)
-                for (uint32_t i = lane; i < nu; i += 64) {
-                    const CtkPair p = r.pairs[r.pair_cap - 1u - i];
-                    if ((int)p.t != t) continue;
-                    if (!__hip_atomic_load(&keep[r.p_rd[r.pair_cap - 1u - i]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) continue;
-                    const uint32_t c = r.p_rc[r.pair_cap - 1u - i] - cb;
-                    atomicAdd((unsigned long long *)&B[2 * c], (unsigned long long)p.lo);
-                    atomicAdd((unsigned long long *)&B[2 * c + 1], (unsigned long long)p.hi);
-                }
-            }
-            __syncthreads();
-            bool any = false;
-            for (uint32_t c = lane; c < nct; c += 64) {
-                const uint32_t g = cb + c;
-                const bool first = c == (uint32_t)lane;
-                long long blo, bhi;
-                if (lds) { blo = Bl[2 * c]; bhi = Bl[2 * c + 1]; }
-                else {
-                    blo = __hip_atomic_load(&B[2 * c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    bhi = __hip_atomic_load(&B[2 * c + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&B[2 * c], 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&B[2 * c + 1], 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                if ((first ? mrep0 : r.mrep[g]) != c) continue;         // representatives only
-                bool inexact = r.inex[g] != 0;
-                const double bwd = dev_limbs_to_double(blo, bhi, r.wshift, r.limb_bits, &inexact);
-                double fb = (first ? inv0 : r.inv[g]) * bwd, ff = first ? ff0 : r.ff[g];
-                const uint32_t os = r.ovr_slot ? r.ovr_slot[g] : 0u;
-                if (os & 0x80000000u) {
-                    const double *v = r.ovr_val + 3 * (size_t)(os & 0x3fffffffu);
-                    const double inv = 1.0 / v[0];
-                    fb = inv * v[2]; ff = inv * v[1];
-                } else if (inexact) {
-                    const double tol = CTK_AMBIG_ULPS * 2.220446049250313e-16 * fabs(r.overlap);
-                    if ((ff != 0 && fabs(ff - r.overlap) <= tol) || (r.twosided && fb != 0 && fabs(fb - r.overlap) <= tol)) {
-                        *r.ambig = 1u;
-                        if (r.ovr_slot && os == 0u) {
-                            const uint32_t idx = atomicAdd(r.amb_cnt, 1u);
-                            if (idx < r.amb_cap) { r.amb_list[idx] = g; r.ovr_slot[g] = 0x40000000u | idx; }
-                        }
-                    }
-                }
-                bool kill = false;
-                if (r.twosided) {
-                    if (fb != 0 && ff != 0) { if (fb < r.overlap || ff < r.overlap) kill = true; }
-                    if (fb != 0 && ff == 0) { if (fb < r.overlap) kill = true; }
-                    if (fb == 0 && ff != 0) { if (ff < r.overlap) kill = true; }
-                } else {
-                    if (ff < r.overlap) kill = true;
-                }
-                const uint8_t kn = kill ? 0 : 1;
-                // only this workgroup writes the bits of timestep t (device-scope load: what an earlier iteration of this launch stored)
-                const uint8_t kold = first ? kold0 : __hip_atomic_load(&keep[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (kn != kold) { __hip_atomic_store(&keep[g], kn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); any = true; if (first) kold0 = kn; }
-            }
-            wave_any = __ballot(any) != 0ull;
-            __syncthreads();                                            // (Bl is zeroed again by the next evaluation)
-        }
-        if (wave_any) mybits |= 1u << k;
-        if (lane == 0) {
-            if (wave_any) r.changed[it * CTK_CHG_SLOTS + (t & (CTK_CHG_SLOTS - 1))] = 1u;
-            // the bits (device-scope stores: written through to the coherence point) before the word that announces them: all
-            // stores of this wave acknowledged, then the word.  (A release fence would write back the whole L2 of this XCD.)
-            __builtin_amdgcn_s_waitcnt(0);
-            __hip_atomic_store(&pstate[(size_t)t * CTK_PSTATE_STRIDE], ((uint32_t)(k + 1) << 24) | mybits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if (!do_unite) return;
-    // 3-D links of this timestep (contrack.py:748-750): its kept components with the kept components of t-1 they overlap.  The
-    // predecessor's bits are final once it has published all of its iterations.
-    if (t - 1 >= r.t_lo && t - 1 <= r.t_hi) {
-        const uint32_t need = (uint32_t)Kfull;
-        SpinGuard sg;
-        while ((__hip_atomic_load(&pstate[(size_t)(t - 1) * CTK_PSTATE_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 24) < need) {
-            __builtin_amdgcn_s_sleep(2);
-            if (spin_expired(sg, r.spin_limit)) { if (lane == 0) atomicOr(r.poison, CTK_POISON_SPIN); return; }
-        }
-    }
-    auto link = [&](uint32_t slot) {
-        if (!__hip_atomic_load(&keep[r.p_rc[slot]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ||
-            !__hip_atomic_load(&keep[r.p_rd[slot]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-        uint32_t a = r.p_gc[slot], b = r.p_gd[slot];
-        for (;;) {
-            a = gfind(r.parent, a);
-            b = gfind(r.parent, b);
-            if (a == b) break;
-            if (a < b) { const uint32_t q = a; a = b; b = q; }
-            const uint32_t old = atomicMin(&r.parent[a], b);
-            if (old == a) break;
-            a = old;
-        }
-    };
-    for (uint32_t i = lane; i < pn; i += 64) link(pb + i);
-    for (uint32_t i = lane; i < nu; i += 64) { if ((int)r.pairs[r.pair_cap - 1u - i].t == t) link(r.pair_cap - 1u - i); }
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_rs_pass_sys with PB_G consecutive timesteps per workgroup, one WAVE each ("blocked systolic").  The hand-shake between
+//
+// k_rs_pass_blk: PB_G consecutive timesteps per workgroup, one WAVE each ("blocked systolic").  The hand-shake between
 // neighbouring timesteps -- a word that says how many iterations the predecessor has published and in which of them its bits
 // changed -- costs ~2.5 us through memory (device-scope store, acknowledgement, device-scope poll from another CU) and is paid
 // once per iteration: 12 iterations = 31 us of the bench pass, nearly all of it waiting.  Inside a workgroup the word and the

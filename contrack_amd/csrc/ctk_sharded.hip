@@ -44,18 +44,6 @@ __global__ void k_halo_pack(const uint64_t *__restrict__ mask, const uint16_t *_
     for (size_t i = i0; i < (size_t)n && i < cap_runs; i += st) oc[i] = run_comp[rb + i];
 }
 
-// table rows of the halo components: each is its own (already seam-resolved) representative at "timestep -1"
-__global__ void k_halo_comps_init(const uint32_t *__restrict__ nh_ptr, uint32_t *__restrict__ mrep, uint32_t *__restrict__ comp_t,
-                                  uint16_t *__restrict__ box, int64_t *__restrict__ area)
-{
-    const uint32_t nh = *nh_ptr;
-    for (uint32_t h = blockIdx.x * blockDim.x + threadIdx.x; h < nh; h += gridDim.x * blockDim.x) {
-        mrep[h] = h; comp_t[h] = 0xffffffffu;
-        box[4 * (size_t)h] = 0; box[4 * (size_t)h + 1] = 0; box[4 * (size_t)h + 2] = 0; box[4 * (size_t)h + 3] = 0;
-        area[2 * (size_t)h] = 0; area[2 * (size_t)h + 1] = 0;
-    }
-}
-
 // forward overlap of the shard's LAST timestep (contrack.py:718) from the next shard's first bit mask
 __global__ __launch_bounds__(256) void k_sh_fwd_last(ResolveDev r, const uint64_t *__restrict__ mask, const uint16_t *__restrict__ wstart,
                                                      const uint32_t *__restrict__ rowstart, const uint32_t *__restrict__ run_base,
@@ -163,7 +151,7 @@ __global__ __launch_bounds__(256) void k_sh_unpack_keep(ResolveDev r, const unsi
             const uint32_t *src = (const uint32_t *)(gathered + (size_t)q * slot + bound_off);
             for (size_t i = threadIdx.x; i < bslot / 4; i += blockDim.x) bound_pinned[(size_t)q * (bslot / 4) + i] = src[i];
         }
-    if (r.pstate) for (int64_t t = threadIdx.x; t <= r.T; t += blockDim.x) r.pstate[(size_t)t * CTK_PSTATE_STRIDE] = 0u;      // (the next round of k_rs_pass_sys counts from zero)
+    if (r.pstate) for (int64_t t = threadIdx.x; t <= r.T; t += blockDim.x) r.pstate[(size_t)t * CTK_PSTATE_STRIDE] = 0u;      // (the next round of k_rs_pass_blk counts from zero)
     __shared__ uint32_t s_diff_any, s_my_diff;
     if (threadIdx.x == 0) { s_diff_any = 0; s_my_diff = 0; }
     __syncthreads();
@@ -683,8 +671,7 @@ struct ShardScratch {
 static void shard_scratch_free(ShardScratch *s) { delete s; }
 
 // CTK_SHDEBUG=1: synchronise and report after every stage (finds the stage a fault belongs to)
-static int g_shdbg = -1;
-#define SHDBG(name) do { if (g_shdbg < 0) g_shdbg = getenv("CTK_SHDEBUG") ? 1 : 0; if (g_shdbg) { hipError_t e_ = hipStreamSynchronize(s); \
+#define SHDBG(name) do { if (ctk_env().shdebug) { hipError_t e_ = hipStreamSynchronize(s); \
     fprintf(stderr, "[shard %d/%d] %-24s %s\n", rank, world, name, hipGetErrorString(e_)); } } while (0)
 
 // X5 + X6 with the seam merges of the shard's own clusters driven on the DEVICE (see k_sh_seam_init).  Everything up to the extent
@@ -936,44 +923,35 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     // One launch (k_compact_init, as in the one-call pass): every timestep's workgroup sums the component counts in front of it
     // itself, compacts its tables and initialises the resolver's per-component arrays; k_overlap then prepares every pair record
     // as it writes it.  (Before: scan, compaction, halo rows, k_rs_init and k_rs_pairs_slots -- five launches, ~29 us at 1 deg.)
-    const bool sys_pass = !ctk_env().pass_launches && !h->no_sys;
-    const bool one_init = !ctk_env().sh_no_slots;
+    const bool sys_pass = !h->no_sys;
     {
         Timer tm(h, CTK_K_SCAN);
-        if (one_init) {
-            const size_t R0 = (size_t)(h->total_runs ? h->total_runs : 1) + halo2_max_runs(h);
-            CTKCHK(ensure(h, h->rv_F, R0 * 16)); CTKCHK(ensure(h, h->rv_B, R0 * 16));
-            CTKCHK(ensure(h, h->rv_keep0, R0)); CTKCHK(ensure(h, h->rv_keep1, R0));
-            CTKCHK(ensure(h, h->rv_touch, R0 * 4)); CTKCHK(ensure(h, h->rv_parent, R0 * 4));
-            CTKCHK(ensure(h, h->rv_changed, (size_t)(CTK_MAX_JACOBI + 8) * CTK_CHG_SLOTS * 4));
-            CTKCHK(ensure(h, h->rv_scalars, 64));
-            CTKCHK(ensure(h, h->sh_ovr_slot, R0 * 4));
-            if (sys_pass) CTKCHK(ensure(h, h->rv_pstate, (size_t)(T + 1) * 4 * CTK_PSTATE_STRIDE));
-            CompInit ci;
-            ci.F = P<int64_t>(h->rv_F); ci.B = P<int64_t>(h->rv_B); ci.keep0 = P<uint8_t>(h->rv_keep0); ci.keep1 = P<uint8_t>(h->rv_keep1);
-            ci.touch = P<uint32_t>(h->rv_touch); ci.parent = P<uint32_t>(h->rv_parent); ci.changed = P<uint32_t>(h->rv_changed);
-            ci.ambig = P<uint32_t>(h->rv_scalars) + 1; ci.pstate = sys_pass ? P<uint32_t>(h->rv_pstate) : nullptr;
-            ci.next_tiny = (const int32_t *)(P<int64_t>(h->wlo) + 2 * (size_t)h->ny);
-            ci.nchanged = (CTK_MAX_JACOBI + 1) * CTK_CHG_SLOTS; ci.pstride = CTK_PSTATE_STRIDE; ci.T = T;
-            ci.base_ptr = nh_ptr; ci.ovr_slot = P<uint32_t>(h->sh_ovr_slot); ci.amb_cnt = P<uint32_t>(h->rv_scalars) + 2; ci.dcount = P<uint32_t>(h->rv_scalars);
-            ci.bsum = nullptr;
-            if (T > 4 * CTK_CI_BLOCK) {
-                const int nb = (int)((T + CTK_CI_BLOCK - 1) / CTK_CI_BLOCK);
-                CTKCHK(ensure(h, h->ci_bsum, (size_t)nb * 4));
-                k_sum_blocks<<<nb, CTK_CI_BLOCK, 0, s>>>(P<uint32_t>(h->ncomp), T, P<uint32_t>(h->ci_bsum));
-                ci.bsum = P<uint32_t>(h->ci_bsum);
-            }
-            k_compact_init<<<(int)T, 256, 0, s>>>(P<uint32_t>(h->run_base), P<uint32_t>(h->ncomp), CPX(h), P<uint32_t>(h->cs_mrep), P<uint32_t>(h->cs_box),
-                                                  P<int64_t>(h->cs_area), P<uint32_t>(h->d_mrep), P<uint16_t>(h->d_box), P<int64_t>(h->d_area),
-                                                  P<uint32_t>(h->d_comp_t), ci);
-            h->fz_init = true;                        // (k_overlap: the resolver's view of every pair record is written with the record)
-        } else {
-            k_scan_u32<<<1, 1024, 0, s>>>(P<uint32_t>(h->ncomp), T, CPX(h), P<uint32_t>(h->counters) + CTK_CNT_OVERFLOW, nullptr, nh_ptr);
-            k_compact_comps<<<(int)T, 256, 0, s>>>(P<uint32_t>(h->run_base), P<uint32_t>(h->ncomp), CPX(h), P<uint32_t>(h->cs_mrep), P<uint32_t>(h->cs_box),
-                                                   P<int64_t>(h->cs_area), P<uint32_t>(h->d_mrep), P<uint16_t>(h->d_box), P<int64_t>(h->d_area),
-                                                   P<uint32_t>(h->d_comp_t));
-            k_halo_comps_init<<<16, 256, 0, s>>>(nh_ptr, P<uint32_t>(h->d_mrep), P<uint32_t>(h->d_comp_t), P<uint16_t>(h->d_box), P<int64_t>(h->d_area));
+        const size_t R0 = (size_t)(h->total_runs ? h->total_runs : 1) + halo2_max_runs(h);
+        CTKCHK(ensure(h, h->rv_F, R0 * 16)); CTKCHK(ensure(h, h->rv_B, R0 * 16));
+        CTKCHK(ensure(h, h->rv_keep0, R0)); CTKCHK(ensure(h, h->rv_keep1, R0));
+        CTKCHK(ensure(h, h->rv_touch, R0 * 4)); CTKCHK(ensure(h, h->rv_parent, R0 * 4));
+        CTKCHK(ensure(h, h->rv_changed, (size_t)(CTK_MAX_JACOBI + 8) * CTK_CHG_SLOTS * 4));
+        CTKCHK(ensure(h, h->rv_scalars, 64));
+        CTKCHK(ensure(h, h->sh_ovr_slot, R0 * 4));
+        if (sys_pass) CTKCHK(ensure(h, h->rv_pstate, (size_t)(T + 1) * 4 * CTK_PSTATE_STRIDE));
+        CompInit ci;
+        ci.F = P<int64_t>(h->rv_F); ci.B = P<int64_t>(h->rv_B); ci.keep0 = P<uint8_t>(h->rv_keep0); ci.keep1 = P<uint8_t>(h->rv_keep1);
+        ci.touch = P<uint32_t>(h->rv_touch); ci.parent = P<uint32_t>(h->rv_parent); ci.changed = P<uint32_t>(h->rv_changed);
+        ci.ambig = P<uint32_t>(h->rv_scalars) + 1; ci.pstate = sys_pass ? P<uint32_t>(h->rv_pstate) : nullptr;
+        ci.next_tiny = (const int32_t *)(P<int64_t>(h->wlo) + 2 * (size_t)h->ny);
+        ci.nchanged = (CTK_MAX_JACOBI + 1) * CTK_CHG_SLOTS; ci.pstride = CTK_PSTATE_STRIDE; ci.T = T;
+        ci.base_ptr = nh_ptr; ci.ovr_slot = P<uint32_t>(h->sh_ovr_slot); ci.amb_cnt = P<uint32_t>(h->rv_scalars) + 2; ci.dcount = P<uint32_t>(h->rv_scalars);
+        ci.bsum = nullptr;
+        if (T > 4 * CTK_CI_BLOCK) {
+            const int nb = (int)((T + CTK_CI_BLOCK - 1) / CTK_CI_BLOCK);
+            CTKCHK(ensure(h, h->ci_bsum, (size_t)nb * 4));
+            k_sum_blocks<<<nb, CTK_CI_BLOCK, 0, s>>>(P<uint32_t>(h->ncomp), T, P<uint32_t>(h->ci_bsum));
+            ci.bsum = P<uint32_t>(h->ci_bsum);
         }
+        k_compact_init<<<(int)T, 256, 0, s>>>(P<uint32_t>(h->run_base), P<uint32_t>(h->ncomp), CPX(h), P<uint32_t>(h->cs_mrep), P<uint32_t>(h->cs_box),
+                                              P<int64_t>(h->cs_area), P<uint32_t>(h->d_mrep), P<uint16_t>(h->d_box), P<int64_t>(h->d_area),
+                                              P<uint32_t>(h->d_comp_t), ci);
+        h->fz_init = true;                        // (k_overlap: the resolver's view of every pair record is written with the record)
         HIPCHK(hipGetLastError());
     }
     h->state = ST_LABELLED;
@@ -982,10 +960,8 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     // ---- stage 2: co-occurrence histogram (the first local timestep against the halo) ------------------------------------
     // (fixed per-timestep slots for the pair records instead of one global counter that every timestep's workgroup adds to:
     // same-address atomics from eight XCDs, 11 of that kernel's 50 us at 1 deg)
-    h->sh_slots = !ctk_env().sh_no_slots;
+    // (fz_init, set above: k_overlap writes into the slots and prepares the pair records -- what k_rs_init and k_rs_pairs* do elsewhere)
     const int rc_ov = shard_overlap_v2(h);
-    h->sh_slots = false;
-    const bool tables_ready = h->fz_init;             // (k_compact_init + k_overlap did what k_rs_init and k_rs_pairs* do)
     h->fz_init = false;
     CTKCHK(rc_ov);
     const uint32_t pslot = h->fz_pslot;
@@ -1041,12 +1017,6 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     bool first_round = true;
     {
         Timer tm(h, CTK_K_RESOLVE);
-        if (!tables_ready) {
-            k_rs_init<<<gc, 256, 0, s>>>(r);                               // (also zeroes the resolver's scalars)
-            const int gps = (int)std::min<uint64_t>(((uint64_t)T * std::max<uint32_t>(pslot, 1u) + 255) / 256 + 16, 4096);
-            if (pslot) k_rs_pairs_slots<<<gps, 256, 0, s>>>(r, in.pair_cnt, pslot);
-            else k_rs_pairs<<<gp, 256, 0, s>>>(r);
-        }
         if (has_next)
             k_sh_fwd_last<<<(int)std::min<size_t>((nw + 255) / 256, 1024), 256, 0, s>>>(r, P<uint64_t>(h->mask), P<uint16_t>(h->wstart), P<uint32_t>(h->rowstart),
                                                                                         P<uint32_t>(h->run_base), P<uint32_t>(h->run_comp),
@@ -1060,7 +1030,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     size_t seam_pre_n = 0;
     const void *seam_pre_ptrs[10] = {h->rv_mark.p, h->rv_dmap.p, h->op_first.p, h->sd_parent.p, h->sd_tmin.p, h->sd_tmax.p, h->sd_nops.p, h->sd_lbox.p,
                                      h->sh_cl_shared.p, h->sh_cl_sent.p};
-    if (!ctk_env().sh_host_seam && !(h->sh_dev_off_ny == ny && h->sh_dev_off_nx == nx) && T <= 65536) {
+    if (!(h->sh_dev_off_ny == ny && h->sh_dev_off_nx == nx) && T <= 65536) {
         size_t n = std::min(h->rv_mark.cap, std::min(h->sh_cl_shared.cap, h->sh_cl_sent.cap));
         for (const DevBuf *b : {&h->rv_dmap, &h->op_first, &h->sd_parent, &h->sd_tmin, &h->sd_tmax, &h->sd_nops}) n = std::min(n, b->cap / 4);
         n = std::min(n, h->sd_lbox.cap / 24);
@@ -1086,7 +1056,6 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
         if (it_done + npass > CTK_MAX_JACOBI) COLLECTIVE_FAIL(CTK_E_RANGE, "ctk_track_sharded: overlap filter did not converge within %d passes", CTK_MAX_JACOBI);      // (the rounds are in lockstep)
         // (decided before the passes: a speculating round lets the filter kernel unite the pairs itself)
         spec = first_round ? world == 1 : true;
-        if (ctk_env().no_spec_x4) spec = false;                      // (experiments: set it for every rank or for none)
         bool united = false;
         {
             Timer tm(h, CTK_K_RESOLVE);
@@ -1290,7 +1259,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     int64_t alive = 0;
     bool zero = false;
     for (int attempt = 0;; attempt++) {
-    const bool dev_seam = attempt == 0 && !ctk_env().sh_host_seam && !(h->sh_dev_off_ny == ny && h->sh_dev_off_nx == nx) && T <= 65536 &&
+    const bool dev_seam = attempt == 0 && !(h->sh_dev_off_ny == ny && h->sh_dev_off_nx == nx) && T <= 65536 &&
                           NL + 2 < 0x7fffffffll;
     if (dev_seam) {
         bool too_many = false;
@@ -1352,7 +1321,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     const CtkCand *hc = (const CtkCand *)dst;
     const int32_t *ho = (const int32_t *)(dst + cb), *hbx = ho + nd;
 
-    static const bool hostprof = getenv("CTK_HOSTPROF") != nullptr;
+    const bool hostprof = ctk_env().hostprof;
     static double hp_acc[8] = {0}; static int hp_n = 0;
     double hp_t = now_ms();
     auto HP = [&](int k) { if (hostprof) { const double n = now_ms(); hp_acc[k] += n - hp_t; hp_t = n; } };

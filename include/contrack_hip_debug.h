@@ -54,13 +54,6 @@ int ctk_debug_set_mailbox(ctk_handle *h, uint32_t cand_records, uint32_t labels)
  * chain arrives late (limit / 4); 2: it never publishes; 0: normal.  Also clears the handle's "no one-launch pass" state. */
 int ctk_debug_set_spin(ctk_handle *h, double limit_ms, int stall_mode);
 
-/* experiments: which chunk of the slab the workgroups of the two streaming kernels take (0 = in launch order, 1 = one contiguous eighth
- * per XCD, k > 1 = tiles of k chunks per XCD); -1 = the default */
-int ctk_debug_set_xcd(ctk_handle *h, int thr_mode, int rel_mode);
-
-/* experiments: threads (0 = default, 256 / 512 / 1024) and rows (0 = default) per workgroup of the write kernel k_relabel_v5 */
-int ctk_debug_set_relabel(ctk_handle *h, int threads, int rows);
-
 /* measurement support (bench.py, next to the roofline): best-of-`reps` time in ms of a PLAIN stream over a 16-byte-aligned device buffer --
  * mode 1: 16-byte non-temporal stores of zeros, 32 KB per workgroup in launch order; mode 2: the same with one contiguous eighth of the
  * buffer per XCD (the faster store stream on every size timed; the better of the two bounds the write kernel); mode 0: 16-byte
@@ -75,12 +68,6 @@ int ctk_debug_time_relabel(ctk_handle *h, int32_t *flag_dev, int persistence, in
  * k_compact_init of the one-call pass; extent = 1024: the sixteen-timesteps-per-workgroup form k_extent_blk whatever the shard's length
  * (test hook: by default it serves shards of more than 2048 timesteps on grids narrower than 1024) */
 int ctk_debug_set_small_threads(ctk_handle *h, int extent, int run_values, int compact_init);
-
-/* placement experiment: the bit mask `off` bytes (a multiple of 256, up to 64 MB) into a larger allocation from the next call on; -1: plain */
-int ctk_debug_set_mask_offset(ctk_handle *h, int64_t off);
-
-/* placement experiment: frees one work-space buffer (0 mask, 1 wstart, 2 rowstart, 3 chunk_vals, 4 run_val, 5 run_base); the next call allocates it anew */
-int ctk_debug_drop_buffer(ctk_handle *h, int which);
 
 /* filter passes launched per round before convergence is checked on the host (default 10, 1..32)   */
 int ctk_set_filter_round(ctk_handle *h, int passes);

@@ -3,8 +3,6 @@
 Per shape (SHAPES="T,ny,nx;T,ny,nx", default the bench slab 2707 x 181 x 360 and 480 x 721 x 1440), on a device-generated slab:
   scalar       per-step thresholds                                   -> k_threshold_v7
   doy          a 366-plane float32 field, DJF day-of-year planes     -> k_threshold_field, steps in plane-major order
-  doy_launch   the same in launch order (CTK_THR_FIELD_ORDER=0)
-  *_xcd0       the same without the chunk -> XCD remap (CTK_THR_FIELD_XCD=0: workgroup b on XCD b % 8)
   full         a (T, ny, nx) float32 field: 8 B/px read
   load8        a plain 16-byte load stream over T * ny * nx * 8 bytes (ctk_debug_stream_ceiling mode 0)
 Times are the handle's HIP-event timers around the threshold kernel (mean over REPS passes); run it under
@@ -58,20 +56,12 @@ def main():
         doy = planes(366, ny, nx, 1)
         trk.set_threshold_field(doy, doy0)
         out["doy_ms"] = thr_ms(trk, lambda: run(None))
-        os.environ["CTK_THR_FIELD_XCD"] = "0"
-        out["doy_xcd0_ms"] = thr_ms(trk, lambda: run(None))
-        os.environ["CTK_THR_FIELD_ORDER"] = "0"
-        out["doy_launch_xcd0_ms"] = thr_ms(trk, lambda: run(None))
-        del os.environ["CTK_THR_FIELD_XCD"]
-        out["doy_launch_ms"] = thr_ms(trk, lambda: run(None))
-        del os.environ["CTK_THR_FIELD_ORDER"]
         base = planes(16, ny, nx, 2)
         trk.set_threshold_field(base[np.arange(T) % 16], np.arange(T, dtype=np.int32))
         out["full_ms"] = thr_ms(trk, lambda: run(None))
         trk.clear_threshold_field()
         out["load8_ms"] = trk.stream_ceiling(d_ld, 2 * nb, 0, reps=REPS)
         out["doy_over_scalar"] = out["doy_ms"] / out["scalar_ms"]
-        out["doy_launch_over_plane_major"] = out["doy_launch_ms"] / out["doy_ms"]
         out["full_of_load8_stream"] = out["load8_ms"] / out["full_ms"]
         print(json.dumps(out), flush=True)
         for p in (d_in, d_out, d_ld):

@@ -1,6 +1,5 @@
 """Round 5: the time of k_threshold (and k_relabel) on eight handles of one process, on the same slab -- the "modes" of the kernel per
-handle.  CTK_MASK_TUNE=0: without the mask placement check; CTK_THR_STORE=2: the kernel without its stores; SHAPE=T,ny,nx; NH handles.
-(tools/mask_check_probe.sh, tools/mask_store_probe.sh)"""
+handle.  CTK_MASK_TUNE=0: without the mask placement check; SHAPE=T,ny,nx; NH handles.  (tools/mask_check_probe.sh)"""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
