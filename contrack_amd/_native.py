@@ -31,7 +31,7 @@ EXPORTS = [
     "ctk_comm_destroy", "ctk_comm_rank", "ctk_comm_world", "ctk_comm_barrier", "ctk_comm_allgather_host", "ctk_comm_ops",
     "ctk_comm_set_timeout", "ctk_comm_rccl_library", "ctk_comm_failed", "ctk_comm_abort_rank", "ctk_debug_fail_at", "ctk_synth_fill_window", "ctk_checksum_i32_dev", "ctk_dev_memset", "ctk_check_flag_dev",
     "ctk_track_sharded_f32_dev", "ctk_track_sharded_f64_dev",
-    "ctk_anom_f32", "ctk_anom_f64", "ctk_resident_anom", "ctk_resident_anom_generation", "ctk_track_resident", "ctk_percentile_f32", "ctk_percentile_f64",
+    "ctk_anom_f32", "ctk_anom_f64", "ctk_resident_anom", "ctk_resident_anom_generation", "ctk_track_resident", "ctk_percentile_f32", "ctk_percentile_f64", "ctk_debug_percentile_values",
     "ctk_lifecycle_f32", "ctk_lifecycle_f64", "ctk_lifecycle_f32_dev", "ctk_lifecycle_f64_dev", "ctk_lifecycle_rows", "ctk_lifecycle_exact",
     "ctk_track_stream_f32", "ctk_track_stream_f64", "ctk_track_stream_cb", "ctk_stream_times",
     "ctk_set_threshold_field", "ctk_set_segments",
@@ -160,6 +160,7 @@ def lib():
     L.ctk_track_resident.argtypes = [p, p, i32, p, dbl, i32, i32, p, C.POINTER(i64)]
     for name in ("ctk_percentile_f32", "ctk_percentile_f64"):
         getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, i32, dbl, C.POINTER(dbl)]
+    L.ctk_debug_percentile_values.argtypes = [p, p, i64]
     L.ctk_comm_unique_id.argtypes = [p]
     L.ctk_comm_init_rccl.argtypes = [p, p, i32, i32, pp]
     L.ctk_comm_group_create.argtypes = [i32, pp]
@@ -800,6 +801,12 @@ class Tracker:
         fn = lib().ctk_percentile_f64 if f64 else lib().ctk_percentile_f32
         check(fn(self._h, ptr, T, ny, nx, int(y0), int(y1), float(q), C.byref(out)))
         return float(out.value)
+
+    def debug_percentile_values(self, n):
+        """test hook: the n per-grid-point quantiles (band, row-major) of the last percentile() call"""
+        v = np.empty(int(n), dtype=np.float64)
+        check(lib().ctk_debug_percentile_values(self._h, v.ctypes.data, int(n)))
+        return v
 
     def release_io(self):
         """free the device copies of slab / result that the host-array calls keep in the handle"""

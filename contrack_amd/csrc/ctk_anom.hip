@@ -155,11 +155,11 @@ __global__ __launch_bounds__(256) void k_quantile(const VT *__restrict__ x, int6
             const double t = h - (double)lo;
             const double a = (double)an_unkey(s_prefix[px]);
             const double bb = (s_le[px] > lo + 1 || lo + 1 >= s_n[px]) ? a : (double)an_unkey(s_next[px]);
-            // numpy's _lerp: a + (b - a) * t, taken from the other end for t >= 0.5
+            // numpy's _lerp exactly: a + (b - a) * t, taken from the other end for t >= 0.5 -- no shortcut for t == 0 or a == b
+            // (numpy gives NaN there when a or b is infinite: inf * 0, inf - inf)
             const double d = bb - a;
             r = a + d * t;
             if (t >= 0.5) r = bb - d * (1.0 - t);
-            if (t == 0.0 || d == 0.0) r = a;
         }
         out[pb] = r;
     }
@@ -199,6 +199,7 @@ static int anom_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx,
     CTKCHK(ensure(h, h->io_in, n * esz));
     CTKCHK(ensure(h, h->an_out, n * esz));
     CTKCHK(ensure(h, h->an_clim, (size_t)ngroups * npix * esz));
+    h->an_pct_n = -1;                                                  // (an_raw is overwritten below)
     CTKCHK(ensure(h, h->an_raw, (size_t)ngroups * npix * esz));
     CTKCHK(ensure(h, h->an_idx, ((size_t)2 * T + ngroups + 2) * 4));
     HIPCHK(hipMemcpy(h->io_in.p, x_host, n * esz, hipMemcpyHostToDevice));
@@ -300,6 +301,7 @@ static int percentile_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, i
         if (h->an_T != T || h->an_ny != ny || h->an_nx != nx || h->an_f64 != (sizeof(VT) == 8)) return ctk_set_error(CTK_E_STATE, "ctk_percentile: no matching anomaly slab is resident");
         x_dev = (const VT *)h->an_out.p;
     }
+    h->an_pct_n = -1;
     CTKCHK(ensure(h, h->an_raw, ((size_t)nband + 8) * 8));
     double *qv = P<double>(h->an_raw);
     k_quantile<VT, KT><<<(unsigned)((nband + 63) / 64), 256, 0, s>>>(x_dev, T, npix, (int64_t)y0 * nx, nband, q, qv);
@@ -307,6 +309,7 @@ static int percentile_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, i
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, qv + nband, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    h->an_pct_n = nband;
     return CTK_OK;
 }
 extern "C" int ctk_percentile_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, int y0, int y1, double q, double *out)
@@ -316,4 +319,15 @@ extern "C" int ctk_percentile_f32(ctk_handle *h, const float *x, int64_t T, int 
 extern "C" int ctk_percentile_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, int y0, int y1, double q, double *out)
 {
     return percentile_impl<double, uint64_t>(h, x, T, ny, nx, y0, y1, q, out);
+}
+
+// test hook: the per-pixel quantiles of the last ctk_percentile_* call (band order, row-major), still in an_raw
+extern "C" int ctk_debug_percentile_values(ctk_handle *h, double *out, int64_t n)
+{
+    if (!h || !out) return ctk_set_error(CTK_E_INVALID, "null argument");
+    if (h->an_pct_n < 0) return ctk_set_error(CTK_E_STATE, "ctk_debug_percentile_values: no ctk_percentile_* result is held");
+    if (n != h->an_pct_n) return ctk_set_error(CTK_E_INVALID, "ctk_debug_percentile_values: n = %lld, the last band had %lld pixels", (long long)n, (long long)h->an_pct_n);
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpy(out, h->an_raw.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return CTK_OK;
 }

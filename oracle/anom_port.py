@@ -21,6 +21,10 @@ What is restated is the documented behaviour of the xarray calls:
                          (numpy's default linear interpolation, NaNs skipped), then the mean over the band's grid points.
 
 Sums are taken in float64; results are cast to the dtype of the input where xarray would keep it (float32 in, float32 out).
+Every sum runs in the order of the kernels' loops (a group's timesteps in time order, a window from its first element), so the
+kernels of contrack_amd/csrc/ctk_anom.hip reproduce this module bit for bit (tests/test_anom_port.py pins the order).
+Also unpinned: on a float32 slab, numpy >= 2 np.nanquantile interpolates in float32 and returns float32 values (up to ~1.6e-4 from
+the float64 interpolation here per grid point); the README's xarray expression on a float32 slab is that, this module is not.
 """
 import numpy as np
 
@@ -30,34 +34,52 @@ def centred_window(i, w):
 
 
 def rolling_mean_centred(a, w, axis=0):
-    """mean over the centred window of w along `axis`; NaN where the window leaves the axis or contains a NaN"""
+    """mean over the centred window of w along `axis`; NaN where the window leaves the axis or contains a NaN.
+    The window's sum runs from its first element to its last, one addition per offset (vectorised over the positions)."""
     a = np.moveaxis(np.asarray(a, dtype=np.float64), axis, 0)
     n = a.shape[0]
     out = np.full(a.shape, np.nan)
-    for i in range(n):
-        lo, hi = centred_window(i, w)
-        if lo < 0 or hi >= n:
-            continue
-        out[i] = a[lo:hi + 1].sum(axis=0) / w          # (a NaN in the window makes the sum NaN)
+    first, last = w // 2, n - 1 - (w - 1) // 2         # the positions whose window lies inside the axis
+    if last >= first:
+        m = last - first + 1
+        s = np.zeros((m,) + a.shape[1:])
+        for j in range(w):
+            s += a[j:j + m]                            # a[lo + j] for every position (a NaN in the window makes the sum NaN)
+        out[first:last + 1] = s / w
     return np.moveaxis(out, 0, axis)
+
+
+def _nanmean_rows(rows, shape):
+    """mean of the non-NaN entries of a sequence of arrays, summed in the sequence's order (NaN where none)"""
+    s, c = np.zeros(shape), np.zeros(shape, dtype=np.int64)
+    for r in rows:
+        ok = ~np.isnan(r)
+        s = np.where(ok, s + np.where(ok, r, 0.0), s)
+        c += ok
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(c > 0, s / np.maximum(c, 1), np.nan), c
 
 
 def calc_clim(x, group, ngroups, window=1):
     """x (T, ny, nx); group[t] in [0, ngroups).  Returns clim (ngroups, ny, nx) float64."""
     x = np.asarray(x)
-    raw = np.full((ngroups,) + x.shape[1:], np.nan)
-    for g in range(ngroups):
-        sel = x[np.asarray(group) == g].astype(np.float64)
-        if len(sel):
-            cnt = np.sum(~np.isnan(sel), axis=0)
-            with np.errstate(invalid="ignore", divide="ignore"):
-                raw[g] = np.where(cnt > 0, np.nansum(sel, axis=0) / np.maximum(cnt, 1), np.nan)
+    group = np.asarray(group)
+    # group means: the timesteps of each group in time order, the k-th of every group added in step k
+    order = np.argsort(group, kind="stable")
+    cnt = np.bincount(group, minlength=ngroups)
+    off = np.concatenate([[0], np.cumsum(cnt)[:-1]])
+    s, c = np.zeros((ngroups,) + x.shape[1:]), np.zeros((ngroups,) + x.shape[1:], dtype=np.int64)
+    for k in range(int(cnt.max()) if len(cnt) else 0):
+        gs = np.nonzero(cnt > k)[0]
+        v = x[order[off[gs] + k]].astype(np.float64)
+        ok = ~np.isnan(v)
+        s[gs] = np.where(ok, s[gs] + np.where(ok, v, 0.0), s[gs])
+        c[gs] += ok
+    with np.errstate(invalid="ignore", divide="ignore"):
+        raw = np.where(c > 0, s / np.maximum(c, 1), np.nan)
     raw = raw.astype(x.dtype).astype(np.float64) if x.dtype == np.float32 else raw
     clim = rolling_mean_centred(raw, window, axis=0)
-    tail = raw[-window:]
-    cnt = np.sum(~np.isnan(tail), axis=0)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        fill = np.where(cnt > 0, np.nansum(tail, axis=0) / np.maximum(cnt, 1), np.nan)
+    fill, _ = _nanmean_rows(raw[max(0, ngroups - window):], raw.shape[1:])
     return np.where(np.isnan(clim), fill[None], clim)
 
 
