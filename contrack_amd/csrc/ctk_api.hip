@@ -1206,6 +1206,8 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
     // The host learns the run totals from the scan kernel's block of scalars in pinned memory and knows that it is complete by
     // the stamp the kernel writes last (an event record after the kernel is a command of its own: 5 us of stream time).
     const uint32_t scan_stamp = (uint32_t)(h->pass_no & 0x7fffffffu) | 0x80000000u;
+    int rc_launched = 0;                    // (CTK_S_ROWCOUNT_THREADS, CTK_S_LABEL_FORMS: recorded after the statistics are reset below)
+    int64_t label_forms = 0;
     {
         Timer tm(h, CTK_KI_ROWCOUNT);
         // one workgroup per timestep: few timesteps of a tall grid leave the chip empty and the rows of a plane in a long chain
@@ -1214,6 +1216,7 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
         // (throughput regime, small planes -- 438 000 x 192 x 288: 128 threads 1.39 -> 0.86 ms, 64: 1.02)
         const int rc_threads = (W <= 64 && ny <= RC_ROWS && ny > 256 && T <= 2048) ? 512 : ((T > 65536 && (int64_t)ny * W <= 2048) ? 128 : 256);
         if (T > 0) k_rowcount<<<(int)T, rc_threads, 0, s>>>(P<uint64_t>(h->mask), ny, W, P<uint16_t>(h->wstart), P<uint32_t>(h->rowstart), P<uint32_t>(h->tcount));
+        rc_launched = T > 0 ? rc_threads : 0;
         CTKCHK(launch_scan_u32(h, P<uint32_t>(h->tcount), T, P<uint32_t>(h->run_base), h->h_mail1, scan_stamp));
         HIPCHK(hipGetLastError());
     }
@@ -1251,6 +1254,8 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
             else k_label2d_lds<1024, 288, -1, 256><<<(int)T, 256, 0, s>>>(a);
         }
         if (vs.v1hi) { if (v0b) k_label2d_lds<1024, 288, 768, 256><<<(int)T, 256, 0, s>>>(a); else k_label2d_lds<1024, 288, 832, 256><<<(int)T, 256, 0, s>>>(a); }
+        label_forms |= (vs.one ? 1 : 0) | (vs.v1 ? (v0b ? 2 : v0_ok ? 4 : 8) : 0) | (vs.v1hi ? (v0b ? 16 : 32) : 0) | (vs.v2 ? 64 : 0) |
+                       (vs.v3 ? 128 : 0) | (vs.glb ? 256 : 0);           // (CTK_S_LABEL_FORMS)
         if (vs.v2) {
             HIPCHK(hipStreamWaitEvent(h->side[0], h->ev_fork, 0));
             k_label2d_lds<2048, 512, 1024, 512><<<(int)T, 512, 0, h->side[0]>>>(a);
@@ -1325,6 +1330,7 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
         }
         h->runs_cap = (uint32_t)std::min<size_t>(Rc, 0xffffffffu);
         launched = {false, false, false, false, false};           // whatever ran speculatively ran on too small buffers
+        if (spec) label_forms |= 512;
     }
     if (defer_compact) {
         // room for the halo's components in front of the shard's own (at most one per two pixels of a row)
@@ -1356,6 +1362,7 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
         h->spec_set.glb = need.glb;
         h->spec_ny = ny; h->spec_nx = nx; h->spec_T = T;
     }
+    h->stats[CTK_S_LABEL_FORMS] = label_forms; h->stats[CTK_S_ROWCOUNT_THREADS] = rc_launched;
     h->fz_init = false;
     if (!defer_compact && T > 0 && h->use_device_resolve && async_wanted(h)) {
         // fused one-call path: prefix of the component counts, compaction and the initialisation of the resolver's per-component
@@ -1527,6 +1534,7 @@ static int launch_overlap(ctk_handle *h)
         do {                                                                                             \
             if (as.seg_edge) k_overlap<OVB, TH, WPE, true><<<(int)h->T, TH, 0, h->stream>>>(as);         \
             else k_overlap<OVB, TH, WPE><<<(int)h->T, TH, 0, h->stream>>>(a);                            \
+            h->stats[CTK_S_OVERLAP_FORM] = (as.seg_edge ? 1000000 : 0) + OVB * 10000 + TH * 10 + WPE;     \
         } while (0)
         if (h->T > 65536 && nwords <= 2048) CTK_OVERLAP(4, 128, 5);
         else if (h->T <= 1024 && nwords >= 8192) CTK_OVERLAP(4, 512, 1);

@@ -295,6 +295,14 @@ int ctk_get_stats(ctk_handle *h, int64_t *out /* [CTK_NSTATS] */);
 /* statistics added after that are read with an explicit length: writes min(n, CTK_NSTATS_ALL) entries, returns CTK_OK */
 #define CTK_S_MASK_CHECK_US 25    /* host time of the last mask placement check, microseconds (bounded: at most one other allocation); sticky */
 #define CTK_S_MASK_SPACER_MB 26   /* device memory that check held as a spacer while it ran (freed before the call went on), MB; sticky */
+#define CTK_S_LABEL_FORMS   27    /* bit mask of the 2-D labelling kernels the last call launched (the speculative launch and the one after
+                                   * the run scan together): 1 k_label2d_lds<4096,512,-1,1024> (one launch for every timestep),
+                                   * 2 <768,272,-1,256,256>, 4 <832,240,-1,256,256>, 8 <1024,288,-1,256>, 16 <1024,288,768,256>,
+                                   * 32 <1024,288,832,256>, 64 <2048,512,1024,512>, 128 <4096,512,2048,1024>, 256 k_label2d_glb;
+                                   * 512: a speculative launch ran on too small run buffers and was discarded */
+#define CTK_S_OVERLAP_FORM  28    /* the last k_overlap launch: OVB * 10000 + THREADS * 10 + waves per SIMD, + 1000000 for the build that
+                                   * reads segment breaks */
+#define CTK_S_ROWCOUNT_THREADS 29 /* threads per workgroup of the last k_rowcount launch (512, 256 or 128) */
 #define CTK_NSTATS_ALL      32
 int ctk_get_stats_n(ctk_handle *h, int64_t *out, int n);
 int ctk_get_timings(ctk_handle *h, double *ms /* [CTK_NTIMERS] */);

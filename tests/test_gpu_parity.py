@@ -3,8 +3,8 @@ oracle.  Bit-exact: ids are the reference's ids (identity permutation)."""
 import numpy as np
 import pytest
 
-import cpu_tables
 import golden_util
+import staged_util
 from contrack_amd import _native, synth
 
 pytestmark = pytest.mark.gpu
@@ -56,47 +56,13 @@ def test_extent_kernel_with_sixteen_timesteps_per_workgroup(name):
         t.close()
 
 
-def _staged(trk, anom, thr, op, wrow):
-    T, ny, nx = anom.shape
-    d = trk.malloc(anom.nbytes)
-    try:
-        trk.h2d(d, anom)
-        trk.shard_label2d(d, T, ny, nx, thr, op, wrow, False)
-        mask = trk.debug_mask(T, ny, nx)
-        lab_nw = trk.debug_label2d(T, ny, nx, True)
-        lab_m = trk.debug_label2d(T, ny, nx, False)
-        trk.shard_overlap()
-        blob = trk.shard_tables()
-    finally:
-        trk.free(d)
-    return mask, lab_nw, lab_m, blob
-
-
 @pytest.mark.parametrize("name", ["refslab_two", "syn2deg_s0", "busy_s1", "noise", "odd_65x130", "odd_9x65", "nan_speckle",
                                   "thr_vector", "all_fg", "all_bg", "chain_a", "cesm_like"])
 def test_staged_outputs_match_oracle(trk, oracle_lib, name):
     """threshold mask, scipy-numbered 2-D labels before/after the seam merge (contrack.py:684-698), and the
     component / pair / seam tables."""
     g = golden_util.load(name)
-    op = _native.CMP_OPS[g["gorl"]]
-    mask, lab_nw, lab_m, blob = _staged(trk, g["anom"], g["thr"], op, g["wrow"])
-    omask = oracle_lib.threshold_mask(g["anom"], g["thr"], g["gorl"])
-    assert np.array_equal(mask, omask)
-    olab, _ = oracle_lib.label(omask, 0)
-    assert np.array_equal(lab_nw, olab)
-    _, _, stage = oracle_lib.run_contrack(g["anom"], g["thr"], g["gorl"], g["wrow"], g["overlap"], g["persistence"], g["twosided"],
-                                          return_stage=True)
-    assert np.array_equal(lab_m, stage)
-    wlo, whi, wshift, lb = _native.weights_to_limbs(g["wrow"], npix=omask.shape[1] * omask.shape[2], with_bits=True)
-    ref = cpu_tables.parse_blob(cpu_tables.pack_blob(cpu_tables.build_tables(omask.astype(bool), wlo, whi), wshift, False, limb_bits=lb))
-    got = cpu_tables.parse_blob(blob)
-    assert got["T"] == ref["T"] and got["wshift"] == ref["wshift"]
-    assert np.array_equal(got["ncomp"], ref["ncomp"])
-    assert np.array_equal(got["mrep"], ref["mrep"])
-    assert np.array_equal(got["box"], ref["box"])
-    assert np.array_equal(got["area"], ref["area"])
-    assert got["pairs"] == ref["pairs"]
-    assert got["seams"] == ref["seams"]
+    staged_util.check_staged(trk, oracle_lib, g["anom"], g["thr"], g["gorl"], g["wrow"], g["overlap"], g["persistence"], g["twosided"])
 
 
 CASES_VS_ORACLE = [

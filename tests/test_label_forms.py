@@ -1,0 +1,90 @@
+"""The planes of tests/test_gpu_label_forms.py have the run and component counts they claim, and together they reach every row-count,
+2-D labelling and overlap form on both sides of every branch the selection lets a plane reach (tests/label_forms.py restates the
+selection in ctk_api.hip and the kernels' guards).  No GPU needed."""
+import numpy as np
+import pytest
+
+import label_forms as lf
+
+
+def test_restatement_edges():
+    # v0b: 961 .. 1088 words of at most 256 rows; v0_ok: at most 960 words in shards of more than 65536 steps
+    assert lf.label_variant(8, 181, 360, 768, False) == "v1_768" and lf.label_variant(8, 181, 360, 769, False) == "v1hi_768"
+    assert lf.label_variant(8, 256, 256, 1024, False) == "v1hi_768" and lf.label_variant(8, 256, 256, 1025, False) == "v2"
+    assert lf.label_variant(8, 192, 288, 900, False) == "v1"
+    assert lf.label_variant(65537, 192, 288, 832, False) == "v1_832" and lf.label_variant(65537, 192, 288, 833, False) == "v1hi_832"
+    assert lf.label_variant(65536, 192, 288, 900, False) == "v1"
+    assert lf.label_variant(8, 1024, 64, 4096, False) == "v3" and lf.label_variant(8, 1024, 64, 4097, False) == "glb"
+    assert lf.label_variant(8, 1025, 64, 0, False) == "glb"
+    assert lf.label_variant(8, 721, 1440, 0, True) == "one" and lf.label_variant(8, 721, 1440, 4097, True) == "glb"
+    assert lf.staged("v1", 128, 9) and not lf.staged("v1", 577, 2)                   # 1152 / 1154 words
+    assert lf.staged("v2", 32, 64) and not lf.staged("v2", 683, 3)                    # 2048 / 2049 words
+    assert not lf.staged("v3", 4, 1) and not lf.staged("one", 4, 1)                   # 1024 threads: never staged
+    assert lf.staged("v1_768", 1, 1088) and lf.staged("v1_832", 1, 960)               # the selection edge is the staging edge
+    assert lf.tables_in_lds("v1_832", 240) and not lf.tables_in_lds("v1_832", 241)
+    assert lf.tables_in_lds("v1_768", 272) and not lf.tables_in_lds("v1_768", 273)
+    assert lf.tables_in_lds("v1", 288) and not lf.tables_in_lds("v1", 289)
+    assert lf.tables_in_lds("v3", 512) and not lf.tables_in_lds("v3", 513) and not lf.tables_in_lds("glb", 1)
+    ov = lambda T, ny, W: lf.overlap_name(lf.overlap_form(T, ny, W, False))
+    assert [ov(8, n, 1) for n in (1024, 1025, 1280, 1281, 1536, 1537, 2048, 2049, 8191, 8192)] == \
+        ["overlap<4,256,1>", "overlap<5,256,1>", "overlap<5,256,1>", "overlap<6,256,1>", "overlap<6,256,1>", "overlap<8,256,1>",
+         "overlap<8,256,1>", "overlap<4,256,1>", "overlap<4,256,1>", "overlap<4,512,1>"]
+    assert ov(1025, 128, 64) == "overlap<4,256,1>" and ov(65537, 32, 2) == "overlap<4,128,5>" and ov(65537, 32, 65) == "overlap<4,256,1>"
+    assert lf.overlap_form(8, 32, 2, True) == 1042561 and lf.overlap_form(65537, 32, 2, False) == 41285
+    assert [lf.rowcount_threads(4, ny, 1) for ny in (256, 257, 2048, 2049)] == [256, 512, 512, 256]
+    assert lf.rowcount_threads(2049, 721, 23) == 256 and lf.rowcount_threads(65537, 32, 2) == 128
+
+
+@pytest.mark.parametrize("case", lf.CASES, ids=lambda c: c["name"])
+def test_case_planes_have_the_claimed_counts(case, oracle_lib):
+    pl = lf.planes_of(case)
+    for k in sorted(set(lf.schedule_of(case))):
+        p = pl[k]
+        runs, comps = lf.claimed(case, k)
+        assert int(lf.count_runs(p[None])[0]) == runs, k
+        _, n = oracle_lib.label(p[None], 0)
+        assert n == comps, k
+        spec = case["planes"][k]
+        if spec[0] == "stack" and spec[3]:
+            assert int((p[:, 0] & p[:, -1]).sum()) == spec[3], k                  # seam rows
+    assert case["reach"] <= lf.case_forms(case), case["reach"] - lf.case_forms(case)
+
+
+def test_cases_reach_every_form():
+    got = set()
+    for c in lf.CASES:
+        got |= c["reach"]
+    assert got == set(lf.FORMS), sorted(set(lf.FORMS) - got)
+
+
+def test_run_ends_at_word_edges():
+    """the stack planes put run ends at bits 62, 63, 0 and 1 of mask words and let runs cross a word boundary"""
+    c = lf.CASE_BY_NAME["runs_721x1440"]
+    p = lf.planes_of(c)["r1024"].astype(bool)
+    ends = p & ~np.concatenate([p[:, 1:], np.zeros((p.shape[0], 1), dtype=bool)], axis=1)
+    bits = set((np.nonzero(ends)[1] % 64).tolist())
+    assert {62, 63, 0, 1} <= bits
+    crosses = p[:, 63::64][:, :p.shape[1] // 64] & p[:, 64::64]
+    assert crosses.any()
+    # runs that end in a partial last word and wrap: seam rows on grids with nx % 64 != 0
+    assert any(c["nx"] % 64 and any(s[0] == "stack" and s[3] for s in c["planes"].values()) for c in lf.CASES)
+
+
+def test_pair_edges_count_pairs():
+    """dots and bars: one distinct (c, d) pair per dot with the next plane"""
+    import cpu_tables
+    for name, want in (("pairs_128", 128), ("pairs_129", 129), ("pairs_600", 600)):
+        c = lf.CASE_BY_NAME[name]
+        m = lf.mask_of(c).astype(bool)
+        tb = cpu_tables.build_tables(m[:3], np.ones(c["ny"], np.int64), np.zeros(c["ny"], np.int64))
+        per_t = np.bincount([p[0] for p in tb["pairs"]], minlength=3)
+        assert per_t[1] == want and per_t[2] == want
+
+
+def test_speculation_sequences_reach_their_branches():
+    seen = 0
+    for seq in lf.SPEC_SEQUENCES:
+        h = lf.Handle()
+        for T, ny, nx, runs in lf.spec_calls(seq):
+            seen |= h.label2d(T, ny, nx, runs)
+    assert seen & lf.DISCARDED_BIT and seen & lf.LABEL_BIT["one"] and seen & lf.LABEL_BIT["glb"] and seen & lf.LABEL_BIT["v1hi_832"]
