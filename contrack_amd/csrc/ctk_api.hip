@@ -1362,7 +1362,7 @@ static int shard_label2d_impl(ctk_handle *h, const void *anom_dev, bool f64, int
         h->spec_set.glb = need.glb;
         h->spec_ny = ny; h->spec_nx = nx; h->spec_T = T;
     }
-    h->stats[CTK_S_LABEL_FORMS] = label_forms; h->stats[CTK_S_ROWCOUNT_THREADS] = rc_launched;
+    h->stats[CTK_S_LABEL_FORMS] = label_forms; h->stats[CTK_S_ROWCOUNT_THREADS] = rc_launched; h->stats[CTK_S_DEVICE_CUS] = h->n_cus;
     h->fz_init = false;
     if (!defer_compact && T > 0 && h->use_device_resolve && async_wanted(h)) {
         // fused one-call path: prefix of the component counts, compaction and the initialisation of the resolver's per-component
@@ -1755,8 +1755,10 @@ static int launch_extents(ctk_handle *h, bool ext_filled = false, bool with_fina
         // round 6: sixteen timesteps per workgroup, the ids' extents reduced in LDS before they touch memory (k_extent_blk), for shards of
         // more than 2048 timesteps on narrow grids (where k_extent ran one wave per plane)
         const bool blk = h->small_threads[0] == 1024 || (h->small_threads[0] == 0 && h->T > 2048 && h->nx < 1024);
+        const int ex_threads = h->small_threads[0] > 0 ? h->small_threads[0] : (h->T > 2048 ? (h->nx >= 1024 ? 128 : 64) : 256);
         if (blk) k_extent_blk<<<(int)((h->T + EX_TW - 1) / EX_TW), 64 * EX_TW, 0, s>>>(a);
-        else k_extent<<<(int)h->T, h->small_threads[0] > 0 ? h->small_threads[0] : (h->T > 2048 ? (h->nx >= 1024 ? 128 : 64) : 256), 0, s>>>(a);
+        else k_extent<<<(int)h->T, ex_threads, 0, s>>>(a);
+        h->stats[CTK_S_EXTENT_FORM] = blk ? 1024 : ex_threads;
         HIPCHK(hipGetLastError());
     }
     return CTK_OK;
@@ -1932,6 +1934,7 @@ static int device_resolve(ctk_handle *h, const ResolveIn &in, double overlap, in
         it_done += ROUND;
         if (it_done > ROUND) k_rs_parent_init<<<gc, 256, 0, s>>>(r);          // the first round's parents were set by k_rs_init
         k_rs_unite<<<gp, 256, 0, s>>>(r);
+        h->stats[CTK_S_FILTER_FORMS] |= (T > 2 ? (h->seg_cur ? 128 : 64) : 0) | 512;
         const uint32_t *ncp = in.cprefix + T;
         k_rs_roots<<<nsb, 256, 0, s>>>(r, P<uint32_t>(h->rv_bsum));                       // (nsb blocks of 256 components)
         k_rs_rank<<<nsb, 256, 0, s>>>(r.isroot, ncp, P<uint32_t>(h->rv_bsum), r.rank, P<uint32_t>(h->rv_boff) + nsb);
@@ -2242,8 +2245,9 @@ static int launch_relabel(ctk_handle *h, int persistence, int32_t *flag_dev, boo
             else if (h->rel_variant == 1) k_relabel_v5_allsgpr<256><<<grid, 256, lds5, h->stream>>>(a, rb, rv5, sub);
             else k_relabel_v5<256><<<grid, 256, lds5, h->stream>>>(a, rb, rv5, sub);
             h->stats[CTK_S_RELABEL_KERNEL] = 5;
+            h->stats[CTK_S_RELABEL_SHAPE] |= ((int64_t)rb << 24) | ((int64_t)sub << 8) | (a.tab_batched ? 1 : 2) | (4 << ((int)(budget >> 10) / 4 - 5));
         }
-        else { k_relabel_v4<<<grid, 256, lds, h->stream>>>(a, rb, rvcap); h->stats[CTK_S_RELABEL_KERNEL] = 4; }
+        else { k_relabel_v4<<<grid, 256, lds, h->stream>>>(a, rb, rvcap); h->stats[CTK_S_RELABEL_KERNEL] = 4; h->stats[CTK_S_RELABEL_SHAPE] |= (int64_t)rb << 24; }
     } else if (nt > 0) {
         a.chunk_vals = nullptr;
         k_relabel<<<grid_for_rows(a.nrows), 256, 0, h->stream>>>(a);
@@ -2268,6 +2272,7 @@ extern "C" int ctk_shard_write(ctk_handle *h, int persistence, int32_t *flag_dev
                                                    P<int32_t>(h->ext), h->n_labels, persistence, P<uint32_t>(h->d_mrep), 0, 0, P<int32_t>(h->run_val),
                                                    P<uint32_t>(h->rowstart), h->ny, cv_rows, cv);
             HIPCHK(hipGetLastError());
+            h->stats[CTK_S_RUNVAL_FORM] = 2560 + (cv ? 1 : 0);
         }
         {
             Timer tm(h, CTK_K_RELABEL);
@@ -2282,6 +2287,7 @@ extern "C" int ctk_shard_write(ctk_handle *h, int persistence, int32_t *flag_dev
         else
             k_count_alive<<<(int)std::min<int64_t>((h->n_labels + 255) / 256 + 1, 4096), 256, 0, s>>>(P<int32_t>(h->ext), h->n_labels, persistence, P<uint32_t>(h->counters),
                                                                                                     h->h_mail1 + 8, AsyncMail{});
+        h->stats[CTK_S_COUNT_FORM] |= h->n_labels <= 262144 ? 8 : 16;
         HIPCHK(hipGetLastError());
     }
     HT("tail launched");
@@ -2389,17 +2395,21 @@ static int resolve_async(ctk_handle *h, double overlap, int twosided, int persis
         }
         if (!(sys && NP > 0)) k_rs_prep<<<gc, 256, 0, s>>>(r);         // (k_rs_pass_blk does it for its own timesteps)
         // (timesteps 1 .. T-2 are filtered; T-1's wave only unites its pairs)
+        int64_t ff = 0;                                                // (CTK_S_FILTER_FORMS)
         if (sys && NP > 0) {
             const int nb = (int)((T - 1 + PB_G - 1) / PB_G);
             launch_rs_pass_blk(h, nb > h->n_cus, nb, r, 0, NP, in.pair_base, in.pair_cnt, r.pstate, 1, 1);      // (two workgroups per CU when nb > CUs: ctk_resolve_dev.hip)
+            ff |= (nb > h->n_cus ? 4 : 1) << (h->seg_cur ? 1 : 0);
         }
         else
             for (int it = 0; it < NP; it++)
                 launch_rs_pass(h, (int)(T - 2), r, it, in.pair_base, in.pair_cnt, P<uint8_t>(h->rv_tdirty));
+        if (!sys && NP > 0) ff |= h->seg_cur ? 32 : 16;
         if (sys && NP > 0) { /* united by k_rs_pass_blk */ }
-        else if (h->fz_pslot) k_rs_unite_slots<<<(int)std::min<int64_t>((T * h->fz_pslot + 255) / 256 + 1, 4096), 256, 0, s>>>(r, in.pair_cnt, h->fz_pslot);
-        else k_rs_unite<<<gp, 256, 0, s>>>(r);
+        else if (h->fz_pslot) { k_rs_unite_slots<<<(int)std::min<int64_t>((T * h->fz_pslot + 255) / 256 + 1, 4096), 256, 0, s>>>(r, in.pair_cnt, h->fz_pslot); ff |= 256; }
+        else { k_rs_unite<<<gp, 256, 0, s>>>(r); ff |= 512; }
         const bool merged = nsb <= CTK_RL_BLOCKS;
+        h->stats[CTK_S_FILTER_FORMS] |= ff | (merged ? 1024 : 2048) | ((int64_t)NP << 16);
         if (!merged) r.lab_root = nullptr;
         k_rs_roots<<<nsb, 256, 0, s>>>(r, P<uint32_t>(h->rv_bsum));
         if (merged) {
@@ -2426,7 +2436,9 @@ static int resolve_async(ctk_handle *h, double overlap, int twosided, int persis
     {
         Timer tm(h, CTK_K_RUNLABEL);
         // (one wave per plane in the throughput regime with few runs per plane: 438 000 x 192 x 288 1.19 -> 0.63 ms)
-        k_run_values<<<(int)T, h->small_threads[1] > 0 ? h->small_threads[1] : ((T > 65536 && h->total_runs / (size_t)T < 1024) ? 64 : 256), 0, s>>>(P<uint32_t>(h->run_base), P<uint32_t>(h->run_comp), CPX(h), P<int32_t>(h->comp_label),
+        const int rv_threads = h->small_threads[1] > 0 ? h->small_threads[1] : ((T > 65536 && h->total_runs / (size_t)T < 1024) ? 64 : 256);
+        h->stats[CTK_S_RUNVAL_FORM] = rv_threads * 10 + (cv ? 1 : 0);
+        k_run_values<<<(int)T, rv_threads, 0, s>>>(P<uint32_t>(h->run_base), P<uint32_t>(h->run_comp), CPX(h), P<int32_t>(h->comp_label),
                                             P<int32_t>(h->ext), h->n_labels, persistence, P<uint32_t>(h->d_mrep), 0, 0, P<int32_t>(h->run_val),
                                             P<uint32_t>(h->rowstart), h->ny, cv_rows, cv, P<uint32_t>(h->counters),
                                             P<uint32_t>(h->rv_boff) + nsb, P<uint32_t>(h->seam_off) /* t_alive: [T + 1], unused on this path otherwise */);
@@ -2448,6 +2460,7 @@ static int resolve_async(ctk_handle *h, double overlap, int twosided, int persis
             k_count_alive_1<<<1, 1024, 0, s>>>(P<int32_t>(h->ext), h->n_labels, persistence, P<uint32_t>(h->counters), h->h_mail1 + 8, am);
         else
             k_count_alive<<<1024, 256, 0, s>>>(P<int32_t>(h->ext), h->n_labels, persistence, P<uint32_t>(h->counters), h->h_mail1 + 8, am);
+        h->stats[CTK_S_COUNT_FORM] |= (h->last_nlab <= 1000000 && NP <= 32) ? 1 : (h->last_nlab <= 1000000 ? 2 : 4);
         HIPCHK(hipGetLastError());
     }
     HT("fused pass launched");

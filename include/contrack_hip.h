@@ -303,7 +303,23 @@ int ctk_get_stats(ctk_handle *h, int64_t *out /* [CTK_NSTATS] */);
 #define CTK_S_OVERLAP_FORM  28    /* the last k_overlap launch: OVB * 10000 + THREADS * 10 + waves per SIMD, + 1000000 for the build that
                                    * reads segment breaks */
 #define CTK_S_ROWCOUNT_THREADS 29 /* threads per workgroup of the last k_rowcount launch (512, 256 or 128) */
-#define CTK_NSTATS_ALL      32
+#define CTK_S_FILTER_FORMS  30    /* bit mask of the overlap-filter, union and rank kernels the last one-call track launched (the fused pass
+                                   * and, if it fell off, the synchronous resolver together): 1 k_rs_pass_blk, 2 its SEG build,
+                                   * 4 k_rs_pass_blk_2pc, 8 its SEG build, 16 k_rs_pass (one launch per pass) in the fused pass, 32 its SEG
+                                   * build, 64 k_rs_pass in the synchronous resolver, 128 its SEG build, 256 k_rs_unite_slots, 512 k_rs_unite,
+                                   * 1024 the fused pass ranked in one launch (k_fz_rank_mark), 2048 in three (k_rs_rank, k_rs_labels,
+                                   * k_fz_mark); bits 16 and up: the filter passes the fused pass launched (NP) */
+#define CTK_S_EXTENT_FORM   31    /* the last k_extent launch: its threads per workgroup (64, 128 or 256), or 1024 for k_extent_blk */
+#define CTK_S_RUNVAL_FORM   32    /* the last k_run_values launch: threads per workgroup * 10, + 1 if it built the chunk-ordered copy of the
+                                   * run values (CTK_CV per chunk) for the write kernel */
+#define CTK_S_RELABEL_SHAPE 33    /* the write launches of the last call, ORed: rows per chunk (rb) << 24 | rows per LDS image of
+                                   * k_relabel_v5 (sub; 0 for the other kernels) << 8 | 1 a k_relabel_v5 launch loaded its tables in one
+                                   * batch (tab_batched), 2 one with three loops, 4 / 8 / 16 its LDS budget was 20 / 24 / 28 KB.  A streamed
+                                   * call launches once per block of timesteps: rb and sub are those of the whole shard, the flags of all */
+#define CTK_S_COUNT_FORM    34    /* bit mask of the alive-count kernels the last call launched: 1 k_count_alive_f, 2 k_count_alive_1,
+                                   * 4 k_count_alive in the fused pass; 8 k_count_alive_1, 16 k_count_alive in ctk_shard_write */
+#define CTK_S_DEVICE_CUS    35    /* compute units of the handle's device (the k_rs_pass_blk_2pc edge: more workgroups than CUs) */
+#define CTK_NSTATS_ALL      40
 int ctk_get_stats_n(ctk_handle *h, int64_t *out, int n);
 int ctk_get_timings(ctk_handle *h, double *ms /* [CTK_NTIMERS] */);
 
