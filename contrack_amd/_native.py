@@ -24,7 +24,7 @@ EXPORTS = [
     "ctk_track_f32_dev", "ctk_track_f64", "ctk_track_f64_dev", "ctk_release_io", "ctk_shard_label2d", "ctk_shard_label2d_f64", "ctk_shard_halo_size", "ctk_shard_halo_export",
     "ctk_shard_halo_import", "ctk_shard_overlap", "ctk_shard_tables", "ctk_resolve", "ctk_result_free",
     "ctk_result_info", "ctk_result_arrays", "ctk_result_nshards", "ctk_weights_to_limbs", "ctk_shard_extents", "ctk_shard_write",
-    "ctk_shard_count_tracked", "ctk_debug_mask", "ctk_debug_label2d", "ctk_debug_set_pair_capacity", "ctk_debug_set_mailbox", "ctk_debug_set_seam_caps", "ctk_debug_set_spin", "ctk_debug_set_small_threads", "ctk_debug_np_sum", "ctk_debug_boundary_resolve", "ctk_set_timing", "ctk_get_timings", "ctk_get_timing_sums", "ctk_set_device_resolve", "ctk_set_fused_pass", "ctk_set_result_transfer", "ctk_expand_runs_host", "ctk_set_filter_round", "ctk_get_stats", "ctk_get_stats_n", "ctk_debug_stream_ceiling", "ctk_debug_time_relabel",
+    "ctk_shard_count_tracked", "ctk_debug_mask", "ctk_debug_label2d", "ctk_debug_set_pair_capacity", "ctk_debug_set_mailbox", "ctk_debug_set_seam_caps", "ctk_debug_set_spin", "ctk_debug_set_small_threads", "ctk_debug_forms", "ctk_debug_np_sum", "ctk_debug_boundary_resolve", "ctk_set_timing", "ctk_get_timings", "ctk_get_timing_sums", "ctk_set_device_resolve", "ctk_set_fused_pass", "ctk_set_result_transfer", "ctk_expand_runs_host", "ctk_set_filter_round", "ctk_get_stats", "ctk_get_stats_n", "ctk_debug_stream_ceiling", "ctk_debug_time_relabel",
     "ctk_dev_malloc", "ctk_dev_free", "ctk_host_alloc", "ctk_host_free", "ctk_host_register", "ctk_host_unregister", "ctk_memcpy_h2d", "ctk_memcpy_d2h", "ctk_sync", "ctk_stream",
     "ctk_synth_fill",
     "ctk_comm_unique_id", "ctk_comm_init_rccl", "ctk_comm_group_create", "ctk_comm_group_destroy", "ctk_comm_init_local", "ctk_comm_init_shm",
@@ -56,6 +56,28 @@ class ContrackHipError(RuntimeError):
 
 class CommError(ContrackHipError):
     """CTK_E_COMM: another rank of the time-shard path gave up, died or did not arrive in time; the communicator is retired"""
+
+
+class FormQuery(C.Structure):
+    """ctk_form_query of include/contrack_hip_debug.h"""
+    _fields_ = [(n, C.c_int64) for n in (
+        "T nt ny nx f64 aligned16 field max_runs_step total_runs n_labels last_nlab async_passes no_sys n_cus seg pslot path forced_extent forced_run_values forced_compact_init spec_set launched").split()]
+
+
+class FormPlan(C.Structure):
+    """ctk_form_plan of include/contrack_hip_debug.h"""
+    _fields_ = [(n, C.c_int64) for n in (
+        "thr_kind thr_u7 thr_rbt thr_grid rowcount_threads v0b v0_ok v0_runs need_glb spec_launched spec_bits missing missing_bits next_spec overlap_form extent_form write_kernel write_rb write_sub write_kb write_batched write_lds write_grid write_shape chunk_copy runval_threads compact_init_threads count_staged count_fused filter_sys filter_passes filter_blk filter_two_pc filter_nb filter_unite filter_merged filter_bits filter_bits_sync round_blk round_two_pc round_nb").split()]
+
+
+def forms(T, ny, nx, nt=None, aligned16=True, async_passes=24, n_cus=256, **query):
+    """ctk_debug_forms: what the library's launch rules (csrc/ctk_forms.h) decide for these numbers, as a dict; no handle, no GPU.
+    nt defaults to T; every other field of FormQuery defaults to 0."""
+    q = FormQuery(T=T, nt=T if nt is None else nt, ny=ny, nx=nx, aligned16=int(aligned16), async_passes=async_passes, n_cus=n_cus,
+                  **{k: int(v) for k, v in query.items()})
+    p = FormPlan()
+    check(lib().ctk_debug_forms(C.byref(q), C.byref(p)))
+    return {n: getattr(p, n) for n, _ in FormPlan._fields_}
 
 
 def lib():
@@ -114,6 +136,7 @@ def lib():
     L.ctk_debug_set_seam_caps.argtypes = [p, i32, i32]
     L.ctk_debug_set_spin.argtypes = [p, dbl, i32]
     L.ctk_debug_set_small_threads.argtypes = [p, i32, i32, i32]
+    L.ctk_debug_forms.argtypes = [C.POINTER(FormQuery), C.POINTER(FormPlan)]
     L.ctk_debug_np_sum.argtypes = [p, sz]
     L.ctk_debug_np_sum.restype = dbl
     L.ctk_debug_boundary_resolve.argtypes = [i32, p, p, p, p, p, p, p, p, p]

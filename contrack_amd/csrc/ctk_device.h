@@ -30,6 +30,19 @@
 #define CTK_ZF_STRIDE 16
 #define CTK_CNT_WORDS (CTK_ZF_OFF + CTK_ZF_SLOTS * CTK_ZF_STRIDE)
 
+// shapes the kernels are built for and the launch rules of ctk_forms.h decide by
+#define CTK_RB 16                  // rows per workgroup in the two streaming kernels (k_threshold_v7, k_threshold_field)
+#define RC_ROWS 2048               // k_rowcount's first form: row totals in LDS
+#define CTK_LDS_RUNS 4096          // runs / rows of a timestep the LDS variants of k_label2d carry at most (beyond: k_label2d_glb)
+#define CTK_LDS_NY 1024
+#define CTK_CV 64                  // run values per chunk in the chunk-ordered copy (more runs in a chunk: staged from run_val)
+#define CTK_CV_MAXCHUNK 1024       // chunks per timestep the copy is built for
+#define EX_TW 16                   // timesteps (waves) of one k_extent_blk workgroup
+#define CTK_MAX_JACOBI 240         // hard cap of filter passes on the device (then: host resolver)
+#define CTK_JACOBI_ROUND 10        // passes launched per round before convergence is checked
+#define PB_G 16                    // timesteps (waves) of one k_rs_pass_blk workgroup
+#define CTK_RL_BLOCKS 8192         // rank blocks of 256 components whose sums fit LDS (k_rs_rank_labels, k_fz_rank_mark)
+
 // overflow bits
 #define CTK_OVF_PAIRS 1u
 #define CTK_OVF_SEAMS 2u

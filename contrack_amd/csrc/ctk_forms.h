@@ -1,0 +1,379 @@
+// ctk_forms.h -- which kernel instance a launch takes, with how many threads, how much LDS and how many rows per chunk: every such
+// rule of the pass once, as a pure function of the numbers it depends on (internal).
+//
+// Host only: no HIP, no ctk_handle, no heap, no statics.  The launch functions of ctk_api.hip / ctk_sharded.hip ask here, map the
+// answer to the template instance with one switch and write the CTK_S_* statistic from the same value; ctk_debug_forms
+// (include/contrack_hip_debug.h) returns the same answers to the tests without a device.  The constants the rules share with the
+// kernels (CTK_RB, RC_ROWS, CTK_LDS_RUNS, CTK_LDS_NY, CTK_CV_MAXCHUNK, EX_TW, PB_G, CTK_RL_BLOCKS, CTK_MAX_JACOBI) are in ctk_device.h.
+#pragma once
+#include <stdint.h>
+#include <stddef.h>
+#include <algorithm>
+#include "ctk_device.h"
+
+// the path a launch belongs to: the staged entries (ctk_shard_*, also the synchronous resolution of a one-call track), the fused
+// one-call pass (resolve_async), the time-sharded path (ctk_track_sharded_*)
+enum CtkPath { CTK_PATH_STAGED = 0, CTK_PATH_FUSED = 1, CTK_PATH_SHARDED = 2 };
+
+// 4 waves per 256-thread workgroup, one row per wave; >> 256 CUs, grid-stride over the rest
+inline int ctk_grid_for_rows(int64_t nrows) { return (int)std::min<int64_t>(std::max<int64_t>((nrows + 3) / 4, 1), 256 * 16); }
+
+// ------------------------------------------------------------------------------------------------
+// threshold
+// ------------------------------------------------------------------------------------------------
+enum CtkThrKind {
+    CTK_THR_V7 = 0,          // k_threshold_v7<OP, U> (k_threshold_probe<OP, U> in the mask placement check)
+    CTK_THR_V6,              // k_threshold_v6<OP, 8>
+    CTK_THR_F32,             // k_threshold<OP, float>
+    CTK_THR_F64,             // k_threshold<OP, double>
+    CTK_THR_FIELD_VEC,       // k_threshold_field<OP, 4>
+    CTK_THR_FIELD_GEN        // k_threshold_field_g<OP, slab type, field type>
+};
+#define CTK_THR_XCD_TILE 64  // chunk -> XCD tiles of 64 (xcd_chunk; NOTES round 4)
+struct CtkThrForm {
+    int kind;
+    int u7;                  // V7: loads per lane and step (4 .. 8)
+    int rbt;                 // V7 / FIELD_VEC: rows per workgroup
+    int r6, nchunk_t;        // V6: rows per chunk, chunks per timestep
+    int64_t nchunks;         // V6: chunks of the launch
+    unsigned grid;
+};
+// timesteps [t0, t0 + nt) of a slab; aligned16: the address of its first step is a multiple of 16 bytes; field: the compare
+// value is the threshold field (its own kernels)
+inline CtkThrForm ctk_threshold_form(int64_t nt, int ny, int nx, int W, bool f64, bool aligned16, bool field)
+{
+    CtkThrForm f = {};
+    // rows per workgroup of the float4 kernels (swept on their first form, k_threshold_v4, on MI355X: 2707 x 181 x 360: 8..64
+    // rows 0.128-0.137 ms (4 rows 0.195); 480 x 721 x 1440: 2..32 rows 0.345-0.366 ms -- flat, 16 it is)
+    f.rbt = std::min(ny, CTK_RB);
+    const int64_t nblk4 = nt * ((ny + f.rbt - 1) / f.rbt);                             // one workgroup per (timestep, rbt rows)
+    const bool v4 = !f64 && (nx % 4 == 0) && aligned16 && nblk4 < (1 << 24);           // < 2^32 work-items
+    f.u7 = 8;
+    f.r6 = std::max(1, 64 / W); f.nchunk_t = (ny + f.r6 - 1) / f.r6;
+    f.nchunks = nt * f.nchunk_t;
+    f.grid = (unsigned)ctk_grid_for_rows(nt * ny);
+    if (field) { f.kind = v4 ? CTK_THR_FIELD_VEC : CTK_THR_FIELD_GEN; if (v4) f.grid = (unsigned)nblk4; return f; }
+    if (!f64 && W <= 64 && !v4) {        // ballot form: float32, rows of at most 64 words, where the float4 form does not apply
+        f.kind = CTK_THR_V6;
+        f.grid = (unsigned)std::min<int64_t>((f.nchunks + 3) / 4, 16384);
+    } else if (f64) f.kind = CTK_THR_F64;
+    else if (!v4) f.kind = CTK_THR_F32;
+    else {
+        f.kind = CTK_THR_V7;
+        f.grid = (unsigned)nblk4;
+        // loads per lane and step such that the steps of a full chunk carry the fewest idle loads
+        const int L = (f.rbt * W * 16 + 255) / 256;
+        int best = 1 << 30;
+        for (int u = 8; u >= 4; u--) { const int waste = (L + u - 1) / u * u - L; if (waste < best) { best = waste; f.u7 = u; } }
+    }
+    return f;
+}
+
+// ------------------------------------------------------------------------------------------------
+// row count
+// ------------------------------------------------------------------------------------------------
+// one workgroup per timestep: few timesteps of a tall grid leave the chip empty and the rows of a plane in a long chain
+// (480 x 721 x 1440: 52 us with 4 waves per plane) -- more waves per plane then (first form of the kernel only)
+// (71 VGPRs: three 512-thread workgroups per CU, one round for <= 768 planes; 1024 threads ran in two rounds)
+// (throughput regime, small planes -- 438 000 x 192 x 288: 128 threads 1.39 -> 0.86 ms, 64: 1.02)
+inline int ctk_rowcount_threads(int64_t T, int ny, int W)
+{
+    return (W <= 64 && ny <= RC_ROWS && ny > 256 && T <= 2048) ? 512 : ((T > 65536 && (int64_t)ny * W <= 2048) ? 128 : 256);
+}
+
+// ------------------------------------------------------------------------------------------------
+// 2-D labelling.  The variants take disjoint sets of timesteps (by run count; nruns == 0 goes to the small one).
+// ------------------------------------------------------------------------------------------------
+// runs the k_label2d_lds instances carry (their RUNS / RUNS_BELOW template arguments at the launch)
+#define CTK_LBL_V0B_RUNS 768
+#define CTK_LBL_V0_RUNS 832
+#define CTK_LBL_V1_RUNS 1024
+#define CTK_LBL_V2_RUNS 2048
+struct CtkVariantSet { bool v1, v2, v3, glb, one, v1hi; };
+inline bool ctk_variants_any(const CtkVariantSet &v) { return v.v1 || v.v2 || v.v3 || v.glb || v.one || v.v1hi; }
+struct CtkLabelShape {
+    // (v1hi: small planes in long shards are labelled by the 20 KB variant, which carries 832 runs -- the planes with 833 .. 1024 runs
+    // then need the 1024-run variant behind it; v0_ok depends on the shape alone, so a speculative launch and the later check agree)
+    // (round 6: the same for planes of 961 .. 1088 words -- 181 x 360 -- with 768 runs and 20.3 KB: eight workgroups per CU instead of the six
+    // of the 25.6 KB variant, k_label2d 52.5 -> 49 us at 2707 x 181 x 360)
+    bool v0b, v0_ok;
+    uint32_t v0_runs;
+};
+inline CtkLabelShape ctk_label_shape(int64_t T, int ny, int W)
+{
+    CtkLabelShape s;
+    s.v0b = ny <= 256 && (int64_t)ny * W > 960 && (int64_t)ny * W <= 1088;
+    s.v0_ok = (T > 65536 && ny <= 256 && (int64_t)ny * W <= 960) || s.v0b;
+    s.v0_runs = s.v0b ? CTK_LBL_V0B_RUNS : CTK_LBL_V0_RUNS;
+    return s;
+}
+// planes no LDS variant takes
+inline bool ctk_label_need_glb(uint32_t max_runs_step, int ny) { return max_runs_step > CTK_LDS_RUNS || ny > CTK_LDS_NY; }
+// what the speculative launch takes from the set the previous call left
+inline CtkVariantSet ctk_label_speculative(const CtkVariantSet &spec_set, const CtkLabelShape &sh)
+{
+    CtkVariantSet v = spec_set;
+    v.v1hi = spec_set.v1hi && sh.v0_ok;
+    return v;
+}
+// CTK_S_LABEL_FORMS bits of one launch of the set (512: a speculative launch ran on too small buffers)
+#define CTK_LABEL_DISCARDED 512
+inline int64_t ctk_label_form_bits(const CtkVariantSet &vs, const CtkLabelShape &sh)
+{
+    return (vs.one ? 1 : 0) | (vs.v1 ? (sh.v0b ? 2 : sh.v0_ok ? 4 : 8) : 0) | (vs.v1hi ? (sh.v0b ? 16 : 32) : 0) | (vs.v2 ? 64 : 0) |
+           (vs.v3 ? 128 : 0) | (vs.glb ? 256 : 0);
+}
+struct CtkLabelPlan {
+    CtkVariantSet missing;   // to launch now, behind what ran speculatively (`launched`)
+    CtkVariantSet next;      // the next call's speculative set
+};
+// after the run scan.  Few timesteps of a busy grid (T <= 512 workgroups: the chip holds them all at once even at two per CU): ONE
+// launch of the largest LDS variant for every timestep instead -- 1024 threads per plane finish a plane sooner than 256 or 512, and
+// the fork / join of the side streams (two events, ~20 us of stream time at 480 x 721 x 1440) disappears.
+inline CtkLabelPlan ctk_label_plan(int64_t T, int ny, const CtkLabelShape &sh, uint32_t max_runs_step, const CtkVariantSet &launched)
+{
+    const bool glb = ctk_label_need_glb(max_runs_step, ny);
+    const bool v2 = max_runs_step > CTK_LBL_V1_RUNS, v3 = max_runs_step > CTK_LBL_V2_RUNS;
+    const bool prefer_one = T <= 512 && max_runs_step > CTK_LBL_V1_RUNS;
+    const bool none_lds = !launched.v1 && !launched.v2 && !launched.v3 && !launched.one;
+    CtkVariantSet need = {true, v2, v3, glb, false, sh.v0_ok && max_runs_step > sh.v0_runs};
+    // (launched.one: the large variant took every timestep it can take)
+    if ((prefer_one && none_lds) || launched.one) need = {false, false, false, glb, true, false};
+    CtkLabelPlan p;
+    p.missing = {need.v1 && !launched.v1, need.v2 && !launched.v2, need.v3 && !launched.v3, need.glb && !launched.glb, need.one && !launched.one,
+                 need.v1hi && !launched.v1hi};
+    if (prefer_one) p.next = {false, false, false, need.glb, true, need.v1hi};
+    else p.next = {true, v2, v3, need.glb, false, need.v1hi};
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------
+// overlap: k_overlap<OVB, TH, WPE>; the form is its statistic code OVB * 10000 + TH * 10 + WPE (CTK_S_OVERLAP_FORM; + CTK_OVERLAP_SEG for
+// the builds that read the segment edge table)
+// ------------------------------------------------------------------------------------------------
+#define CTK_OVERLAP_CODE(OVB, TH, WPE) ((OVB) * 10000 + (TH) * 10 + (WPE))
+#define CTK_OVERLAP_SEG 1000000
+// (register budgets that allow more waves per SIMD -- 5, 6, 8 instead of the 3 that 135 VGPRs leave at OVB = 5 -- were
+// measured, before and after the kernel's live state was cut from 135 to 117 VGPRs: the spills cost more than the occupancy
+// returns -- 39 us at 4 waves per SIMD, 44 at 5, 60 at 6)
+// few large planes: more waves per plane (480 x 721 x 1440: 256 threads 60 us, 1024 -- one workgroup per CU at 101 VGPRs,
+// two rounds -- 53, 512 -- two per CU, one round -- 49.5)
+// many small planes (throughput regime): two waves per plane, ten workgroups per CU at 101 VGPRs -- 438 000 x 192 x 288: 3.95 -> 3.50 ms
+// (eight words per thread in one step: 169 VGPRs, 5.5 ms)
+// (small planes in long shards: room for five waves per SIMD -- 96 VGPRs, 14 of the 105 in scratch -- 3.49 -> 3.05 ms at 438 000 x 192 x 288;
+// at 2707 x 181 x 360, one round of latency chains, the same costs <5, 256> ten of its 36 us: only here)
+inline int ctk_overlap_form(int64_t T, int ny, int W)
+{
+    const int nwords = ny * W, per = (nwords + 255) / 256;                             // words per thread if one step is to cover all
+    if (T > 65536 && nwords <= 2048) return CTK_OVERLAP_CODE(4, 128, 5);
+    if (T <= 1024 && nwords >= 8192) return CTK_OVERLAP_CODE(4, 512, 1);
+    if (per <= 4 || per > 8) return CTK_OVERLAP_CODE(4, 256, 1);
+    if (per == 5) return CTK_OVERLAP_CODE(5, 256, 1);
+    if (per == 6) return CTK_OVERLAP_CODE(6, 256, 1);
+    return CTK_OVERLAP_CODE(8, 256, 1);
+}
+
+// ------------------------------------------------------------------------------------------------
+// extents: threads of k_extent, or CTK_EXTENT_BLK = k_extent_blk (the value is CTK_S_EXTENT_FORM)
+// ------------------------------------------------------------------------------------------------
+#define CTK_EXTENT_BLK 1024
+// (a timestep has ~40 components: one wave per timestep puts every plane of a long slab on the chip at once -- 11.2 instead of
+// 14.0 us at 2707 x 181 x 360, equal at 480 x 721 x 1440; tools/small_probe.py)
+// (one wave per plane beyond 2048 planes; two on wide grids, whose complex components are folded row by row: 14 600 x 721 x 1440 0.40 -> 0.26 ms)
+// round 6: sixteen timesteps per workgroup, the ids' extents reduced in LDS before they touch memory (k_extent_blk), for shards of
+// more than 2048 timesteps on narrow grids (where k_extent ran one wave per plane)
+// forced: ctk_debug_set_small_threads' extent (0 = the rule)
+inline int ctk_extent_form(int64_t T, int nx, int forced)
+{
+    if (forced > 0) return forced;                 // (1024 = CTK_EXTENT_BLK)
+    if (T > 2048) return nx < 1024 ? CTK_EXTENT_BLK : 128;
+    return 256;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the write pass (k_relabel_v5 / k_relabel_v4 / k_relabel)
+// ------------------------------------------------------------------------------------------------
+#define CTK_RV5 512          // run values k_relabel_v5 stages in LDS
+#define CTK_RVCAP 2048       // ... k_relabel_v4
+enum CtkWriteKernel { CTK_WR_NONE = -1, CTK_WR_GENERIC = 0, CTK_WR_V4 = 4, CTK_WR_V5 = 5 };       // (the values of CTK_S_RELABEL_KERNEL)
+// rows per chunk (workgroup) of a T-step shard.  k_relabel_v4, measured on MI355X (ms):
+//   2707 x 181 x 360:    990 int4 stores per workgroup (11 rows) 0.147 | 720: 0.159 | 1440: 0.168 | 540: 0.182
+//   480 x 721 x 1440:    720 (2 rows) 0.337 | 2880 (8 rows) 0.343 | 2160: 0.359 | 1440: 0.366
+//   14600 x 721 x 1440:  2880 (8 rows, 1.3 M workgroups) 10.9 | 5760: 11.6 | 1440 (2.6 M): 14.0 | 720 (5.3 M): 17.1
+// (k_relabel_v4, round 1; for k_relabel_v5 see the table inside)
+inline int ctk_write_rows(int64_t T, int ny, int nx)
+{
+    const int n4r = std::max(1, nx / 4);
+    int rb = std::min(ny, std::max(1, std::min(64, 1024 / n4r)));
+    // Rows per chunk at 721 x 1440, ns of kernel time per ROW (round 3, `CTK_RELABEL_ROWS` sweeps):
+    //   480 steps: 2 rows 0.98 | 3: 1.06 | 6: 1.10        1000 steps: 2 rows 1.53 | 3: 1.03 | 4: 1.04 | 6: 1.08
+    //   2000 steps: 3 rows 1.37 | 4: 1.31 | 6: 1.02 | 8: 1.12 | 12: 1.10        14 600 steps: 6 rows 1.03 | 8: 1.07 | 9: 1.09
+    // i.e. the smallest chunk that keeps the launch at or below ~250 000 workgroups, and not more than ~2300 stores (6 rows).
+    // Narrow rows (192 x 288, configs[4]: 72 stores per row), 438 000 steps, ms per launch: 32 rows 21.6 | 48: 20.2 | 64: 18.9 | 96: 18.5 | 192: 22.8
+    // (round 6 sweep) -- the cap of ~2300 stores was found on 1440-wide rows (360 stores each); up to ~6900 where a row is short.
+    const int store_cap = n4r >= 256 ? 2304 : 6912;
+    const int rb_max = std::min(ny, std::max(rb, std::min(96, store_cap / n4r)));
+    // Round 6, with eight workgroups per CU really there (CTK_SGPR_8WAVES), us per launch: 480 steps 2 rows 371 | 3: 332-349 | 4: 353-367 | 5: 337-345 |
+    // 6: 348-353; 1000 steps 3 rows 716-734 | 4: 702-707 | 5: 609-699 | 6: 599-707; 2000 steps 4 rows 1688-1762 | 5: 1518-1553 | 6: 1370-1373
+    // -> the smallest chunk that keeps the launch at or below ~130 000 workgroups (it was 250 000).
+    while (rb < rb_max && T * ((ny + rb - 1) / rb) > 130000) rb++;
+    while (rb < ny && T * ((ny + rb - 1) / rb) >= (1 << 24)) rb++;
+    return rb;
+}
+// LDS bytes of a chunk's tables in the word-sliced write kernels: mask words, word starts, row starts of rb rows
+inline size_t ctk_write_tables_lds(int rb, int W)
+{
+    return (size_t)rb * W * 8 + (((size_t)rb * W * 2 + 7) & ~(size_t)7) + ((((size_t)rb + 1) * 4 + 7) & ~(size_t)7);
+}
+struct CtkWritePlan {
+    int kernel;              // CtkWriteKernel
+    int rb;                  // rows per chunk (of the whole shard: the chunk-ordered copy is built for it)
+    int sub;                 // V5: rows per LDS image of flag values
+    int kb;                  // V5: the LDS budget, KB (20, 24 or 28)
+    int tab_batched;
+    int64_t nchunk;          // chunks per timestep
+    unsigned grid;           // V5 / V4: one workgroup per (timestep, chunk); GENERIC: grid-stride over the rows
+    size_t lds;              // dynamic LDS of the launch
+    int64_t shape;           // the launch's bits of CTK_S_RELABEL_SHAPE
+};
+// timesteps [t0, t0 + nt) of a T-step shard; aligned16: of the address these timesteps are written to
+inline CtkWritePlan ctk_write_plan(int64_t T, int64_t nt, int ny, int nx, int W, bool aligned16)
+{
+    CtkWritePlan p = {};
+    p.rb = ctk_write_rows(T, ny, nx);
+    p.nchunk = (ny + p.rb - 1) / p.rb;
+    const int64_t nblk4 = nt * p.nchunk;
+    p.tab_batched = nblk4 < 200000 ? 1 : 0;          // (1 deg, 480 x 0.25 deg: -4 %; 14 600 x 0.25 deg: +2.7 % -- NOTES round 4)
+    const size_t tables = ctk_write_tables_lds(p.rb, W), lds4 = tables + (size_t)CTK_RVCAP * 4;
+    if (!((nx % 4 == 0) && aligned16 && (int64_t)ny * nx < 0x7fffffff && nblk4 < (1 << 24) && nt > 0 && lds4 <= 60 * 1024)) {
+        p.kernel = nt > 0 ? CTK_WR_GENERIC : CTK_WR_NONE;
+        p.grid = (unsigned)ctk_grid_for_rows(nt * ny);
+        return p;
+    }
+    p.grid = (unsigned)nblk4;
+    // word-centric form: the LDS image of `sub` rows of flag values (sub x nx x 4 bytes) leaves eight workgroups per CU; tall
+    // chunks (the 8-row chunks of slabs with many timesteps) are written in several passes of `sub` rows
+    const size_t tab5 = tables + (((size_t)CTK_RV5 * 4 + 15) & ~(size_t)15) + 16;
+    // 20 KB = eight workgroups of 256 threads per CU.  A chunk that needs three or more images at that size gets 24 or 28 KB (six / five
+    // workgroups per CU) if that brings it down to two: 14 600 x 721 x 1440 in 6-row chunks (34 KB of values) 11.46 -> 10.55 ms,
+    // 2000 steps 1.55 -> 1.47; 32 KB: 14.1 ms (four per CU); 438 000 x 192 x 288 in 96-row chunks: 9 or 6 images, no difference
+    auto rows_per_image = [&](int kb) { int q = p.rb; while (q > 1 && tab5 + (size_t)q * nx * 4 > (size_t)kb * 1024) q--; return q; };
+    p.kb = 20;
+    p.sub = rows_per_image(p.kb);
+    if ((p.rb + p.sub - 1) / p.sub > 2)
+        for (int kb = 24; kb <= 28; kb += 4) {
+            const int s2 = rows_per_image(kb);
+            if ((p.rb + s2 - 1) / s2 <= 2) { p.kb = kb; p.sub = s2; break; }
+        }
+    p.lds = tab5 + (size_t)p.sub * nx * 4;
+    if (p.lds <= (size_t)p.kb * 1024) {
+        p.kernel = CTK_WR_V5;
+        p.shape = ((int64_t)p.rb << 24) | ((int64_t)p.sub << 8) | (p.tab_batched ? 1 : 2) | (4 << (p.kb / 4 - 5));
+    } else {
+        p.kernel = CTK_WR_V4; p.sub = 0; p.kb = 0;
+        p.lds = lds4;
+        p.shape = (int64_t)p.rb << 24;
+    }
+    return p;
+}
+// k_run_values builds the chunk-ordered copy of the run values when a word-sliced kernel will write the shard
+inline bool ctk_write_chunk_copy(const CtkWritePlan &whole_shard) { return whole_shard.kernel >= CTK_WR_V4 && whole_shard.nchunk <= CTK_CV_MAXCHUNK; }
+
+// ------------------------------------------------------------------------------------------------
+// the one-workgroup-per-timestep kernels k_run_values and k_compact_init.  forced: ctk_debug_set_small_threads' value (0 = the
+// rule); only the fused pass has a rule of its own and takes the override, the staged and the time-sharded path launch 256 threads
+// ------------------------------------------------------------------------------------------------
+// (one wave per plane in the throughput regime with few runs per plane: 438 000 x 192 x 288 1.19 -> 0.63 ms)
+inline int ctk_runval_threads(CtkPath path, int64_t T, uint64_t total_runs, int forced)
+{
+    if (path != CTK_PATH_FUSED) return 256;
+    if (forced > 0) return forced;
+    return (T > 65536 && total_runs / (uint64_t)T < 1024) ? 64 : 256;
+}
+inline int64_t ctk_runval_code(int threads, bool chunk_copy) { return threads * 10 + (chunk_copy ? 1 : 0); }       // CTK_S_RUNVAL_FORM
+// (one wave per plane in the throughput regime -- 438 000 x 192 x 288: 0.81 -> 0.55 ms; 256 in the latency regime, NOTES round 4)
+inline int ctk_compact_init_threads(CtkPath path, int64_t T, int forced)
+{
+    if (path != CTK_PATH_FUSED) return 256;
+    if (forced > 0) return forced;
+    return T > 65536 ? 64 : 256;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the alive count; the values are the bits of CTK_S_COUNT_FORM
+// ------------------------------------------------------------------------------------------------
+enum CtkCountForm {
+    CTK_COUNT_F = 1,         // fused pass: k_count_alive_f (one round of loads, one barrier: round 6)
+    CTK_COUNT_1 = 2,         // fused pass: k_count_alive_1
+    CTK_COUNT_FULL = 4,      // fused pass: k_count_alive
+    CTK_COUNT_W1 = 8,        // ctk_shard_write: k_count_alive_1
+    CTK_COUNT_WFULL = 16     // ctk_shard_write: k_count_alive
+};
+inline int ctk_count_form_staged(int64_t n_labels) { return n_labels <= 262144 ? CTK_COUNT_W1 : CTK_COUNT_WFULL; }
+// last_nlab: the previous pass' id count (a slab of the same kind); passes: the filter passes the fused pass launched.
+// k_count_alive_f reads one 'changed' word per pass with its first 32 lanes and DEPENDS on passes <= 32 being checked here and
+// nowhere else: it has no clamp of its own.
+inline int ctk_count_form_fused(int64_t last_nlab, int passes)
+{
+    if (last_nlab > 1000000) return CTK_COUNT_FULL;
+    return passes <= 32 ? CTK_COUNT_F : CTK_COUNT_1;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the overlap filter, the 3-D unions behind it and the numbering of the ids; bits of CTK_S_FILTER_FORMS
+// ------------------------------------------------------------------------------------------------
+#define CTK_PB_MAX_PASSES 24 // iterations one k_rs_pass_blk launch takes
+// blocks of 256 components of the rank scan (k_rs_roots / k_rs_rank) over tables of at most R components (components <= runs)
+inline int64_t ctk_rank_blocks(size_t R) { return (int64_t)(((R ? R : 1) + 255) / 256); }
+enum CtkFilterBits {
+    CTK_FF_BLK = 1, CTK_FF_BLK_SEG = 2, CTK_FF_2PC = 4, CTK_FF_2PC_SEG = 8,            // k_rs_pass_blk / k_rs_pass_blk_2pc, fused pass
+    CTK_FF_PASS = 16, CTK_FF_PASS_SEG = 32,                                            // k_rs_pass per pass, fused pass
+    CTK_FF_SYNC = 64, CTK_FF_SYNC_SEG = 128,                                           // k_rs_pass per pass, synchronous resolver
+    CTK_FF_UNITE_SLOTS = 256, CTK_FF_UNITE = 512, CTK_FF_RANK_MERGED = 1024, CTK_FF_RANK_SPLIT = 2048
+};
+// one round of `npass` passes over `steps` timesteps: all of them in one launch (k_rs_pass_blk) when every workgroup of the launch
+// can wait for its predecessor (no_sys: a wait of this handle once gave up), else one launch per pass
+struct CtkFilterRound {
+    bool blk;
+    bool two_pc;             // the build with two workgroups per CU, when the launch is larger than the chip (ctk_resolve_dev.hip)
+    int nb;                  // workgroups of the block launch
+};
+inline CtkFilterRound ctk_filter_round(int64_t steps, int npass, bool no_sys, int n_cus)
+{
+    CtkFilterRound r;
+    r.blk = !no_sys && npass <= CTK_PB_MAX_PASSES;
+    r.nb = (int)((steps + PB_G - 1) / PB_G);
+    r.two_pc = r.nb > n_cus;
+    return r;
+}
+enum CtkUnite { CTK_UNITE_IN_PASS = 0, CTK_UNITE_SLOTS, CTK_UNITE_PAIRS };              // k_rs_pass_blk itself / k_rs_unite_slots / k_rs_unite
+struct CtkFilterPlan {
+    bool sys;                // the block launch is allowed (its per-timestep state words are needed)
+    int passes;              // NP
+    CtkFilterRound round;    // (blk: sys && passes > 0)
+    int unite;               // CtkUnite
+    bool merged;             // numbering and seam marks in one launch (k_fz_rank_mark), while the block sums fit LDS
+    int64_t bits;            // CTK_S_FILTER_FORMS of the pass
+};
+// the fused pass: async_passes = the passes the handle launches (previous pass' count + 2); pslot: pair-record slots per timestep
+// (0: ungrouped records); nsb: blocks of 256 components of the rank scan.  (timesteps 1 .. T-2 are filtered; T-1's wave only unites
+// its pairs)
+inline CtkFilterPlan ctk_filter_plan_fused(int64_t T, int async_passes, bool no_sys, int n_cus, bool seg, int pslot, int64_t nsb)
+{
+    CtkFilterPlan p;
+    p.sys = !no_sys && async_passes <= CTK_PB_MAX_PASSES;
+    p.passes = T > 2 ? std::min(std::max(async_passes, 2), p.sys ? CTK_PB_MAX_PASSES : CTK_MAX_JACOBI) : 0;
+    p.round = ctk_filter_round(T - 1, p.passes, no_sys, n_cus);
+    p.round.blk = p.sys && p.passes > 0;
+    p.unite = p.round.blk ? CTK_UNITE_IN_PASS : (pslot ? CTK_UNITE_SLOTS : CTK_UNITE_PAIRS);
+    p.merged = nsb <= CTK_RL_BLOCKS;
+    p.bits = 0;
+    if (p.round.blk) p.bits |= (p.round.two_pc ? CTK_FF_2PC : CTK_FF_BLK) << (seg ? 1 : 0);
+    else if (p.passes > 0) p.bits |= seg ? CTK_FF_PASS_SEG : CTK_FF_PASS;
+    if (p.unite == CTK_UNITE_SLOTS) p.bits |= CTK_FF_UNITE_SLOTS;
+    if (p.unite == CTK_UNITE_PAIRS) p.bits |= CTK_FF_UNITE;
+    p.bits |= (p.merged ? CTK_FF_RANK_MERGED : CTK_FF_RANK_SPLIT) | ((int64_t)p.passes << 16);
+    return p;
+}
+// the synchronous resolver: one launch per pass over timesteps 1 .. T-2, k_rs_unite, split rank
+inline int64_t ctk_filter_bits_sync(int64_t T, bool seg) { return (T > 2 ? (seg ? CTK_FF_SYNC_SEG : CTK_FF_SYNC) : 0) | CTK_FF_UNITE; }

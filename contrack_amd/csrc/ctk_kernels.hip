@@ -183,7 +183,6 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 // costs nothing measurable: k_relabel_v5 -3 ... -5 % in the same process (tools/relabel_variants.py), 18.0 -> 15.2 ms at 438 000 x 192 x 288;
 // k_rs_pass_blk there 2.5 -> 1.9 ms (its second build, k_rs_pass_blk_2pc; short launches keep their SGPRs: ctk_resolve_dev.hip).
 #define CTK_SGPR_8WAVES __attribute__((amdgpu_num_sgpr(80)))
-#define CTK_RB 16                  // rows per workgroup in the two streaming kernels
 
 // k_threshold_v7: one workgroup per (timestep, rb rows), 16-byte non-temporal loads, a 16-lane DPP row = 64 pixels = one mask
 // word -- the decomposition of round 4's k_threshold_v4 with a third of its VALU work.  SQ counters (profiles/r04_sq_1deg.md) showed v4 to be
@@ -520,7 +519,6 @@ __global__ __launch_bounds__(256) void k_thr_field_prep(const double *__restrict
 //   wstart[row][w] = run starts in words < w of the row      rowstart[t][y] = first run of row y
 //   tcount[t]      = runs of the timestep
 // ------------------------------------------------------------------------------------------------
-#define RC_ROWS 2048
 __global__ __launch_bounds__(1024) CTK_SGPR_8WAVES void k_rowcount(const uint64_t *__restrict__ mask, int ny, int W, uint16_t *__restrict__ wstart,
                                                   uint32_t *__restrict__ rowstart, uint32_t *__restrict__ tcount)
 {
@@ -1033,8 +1031,6 @@ __device__ __forceinline__ void label2d_body(const Label2dArgs &a, const int t, 
     PHASE_MARK(8);
 }
 
-#define CTK_LDS_RUNS 4096
-#define CTK_LDS_NY 1024
 
 // LDS variants: RUNS = most runs per timestep carried, COMPS = components whose bbox/area tables live in LDS
 // (the table area doubles as the staging area of the timestep's mask words, COMPS*4 words).
@@ -1496,8 +1492,6 @@ __global__ __launch_bounds__(THREADS, WPE) void k_overlap(std::conditional_t<SEG
 // ctk_resolve.cpp): only used for the rare "complex" components.
 //   first / next : per label, the chain of ops that have it as `hi`, in execution order
 // ------------------------------------------------------------------------------------------------
-#define CTK_CV 64                       // run values per chunk in the chunk-ordered copy (more runs in a chunk: staged from run_val)
-#define CTK_CV_MAXCHUNK 1024            // chunks per timestep the copy is built for
 struct FoldArgs {
     const CtkOp *ops;          // execution order
     const int32_t *first;      // [n_labels + 1] first op that has the label as `hi` (-1: none)
@@ -1663,7 +1657,6 @@ __global__ __launch_bounds__(256) CTK_SGPR_8WAVES void k_extent(ExtentArgs a)
 // With one wave per timestep that chain is the kernel: 2.0 ms at 438 000 x 192 x 288 (93 % of the wave cycles waiting).  Here the
 // waves of a workgroup reduce (id -> first / last timestep) in an LDS hash first and the workgroup touches global memory once per
 // id: EX_TW times fewer hot operations (the scheme of k_fz_groups).  Complex components (per-pixel folds) update directly, as before.
-#define EX_TW 16
 #define EX_HS 512
 #define EX_PROBES 8
 __global__ __launch_bounds__(64 * EX_TW) void k_extent_blk(ExtentArgs a)

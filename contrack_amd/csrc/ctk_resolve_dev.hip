@@ -104,8 +104,6 @@ __device__ __forceinline__ bool spin_expired(SpinGuard &g, uint64_t limit)
 #define CTK_PSTATE_STRIDE 32        // words between the per-timestep state words of k_rs_pass_blk*: one 128-byte line each (the words are
                                     // polled with device-scope loads: neighbours in one line would all hit the same memory channel)
 #define CTK_CHG_SLOTS 64            // 'changed' words per filter pass (= wave width: one ballot reads them)
-#define CTK_MAX_JACOBI 240          // hard cap of filter passes on the device (then: host resolver)
-#define CTK_JACOBI_ROUND 10         // passes launched per round before convergence is checked
 
 // pair records: k in [0, ng) are the grouped ones pairs[k]; k in [ng, ng+nu) the ungrouped ones stored from the
 // end of the buffer downwards (k_overlap)
@@ -399,7 +397,6 @@ __global__ __launch_bounds__(64) void k_rs_pass(ResolveDev r, int it, const uint
 // Same iteration, same fixed point (contrack.py:706-742), same outputs (keep bits in memory, changed[], pstate of the
 // workgroups' last timesteps).  Waves synchronise only with themselves after the start-up barrier.
 // ------------------------------------------------------------------------------------------------
-#define PB_G 16
 #define PB_COMPS 128         // components of a timestep whose backward sums and keep bits live in LDS (more: memory, as before)
 // the lanes of ONE wave hand data to each other through LDS (executed in order for a wave) -- or, for timesteps whose sums live
 // in the global scratch, through memory: then the operations have to be complete first
@@ -775,7 +772,6 @@ __global__ __launch_bounds__(256) void k_rs_rank(const uint32_t *__restrict__ is
 // k_rs_rank + k_rs_labels in one launch (while the block sums fit LDS): every workgroup builds the exclusive prefix of ALL block
 // counts itself (a few hundred values), then label = 1 + prefix[block of the root] + roots in front of it inside that block.
 // rank[] is not written (the time-shard path, which reads it, keeps the two kernels); *total = number of labels.
-#define CTK_RL_BLOCKS 8192
 __global__ __launch_bounds__(256) void k_rs_rank_labels(ResolveDev r, const uint32_t *__restrict__ bsum, uint32_t nsb, uint32_t *__restrict__ total)
 {
     extern __shared__ uint32_t pre[];                       // [nsb]

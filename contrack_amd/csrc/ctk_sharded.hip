@@ -948,7 +948,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
             k_sum_blocks<<<nb, CTK_CI_BLOCK, 0, s>>>(P<uint32_t>(h->ncomp), T, P<uint32_t>(h->ci_bsum));
             ci.bsum = P<uint32_t>(h->ci_bsum);
         }
-        k_compact_init<<<(int)T, 256, 0, s>>>(P<uint32_t>(h->run_base), P<uint32_t>(h->ncomp), CPX(h), P<uint32_t>(h->cs_mrep), P<uint32_t>(h->cs_box),
+        k_compact_init<<<(int)T, ctk_compact_init_threads(CTK_PATH_SHARDED, T, h->small_threads[2]), 0, s>>>(P<uint32_t>(h->run_base), P<uint32_t>(h->ncomp), CPX(h), P<uint32_t>(h->cs_mrep), P<uint32_t>(h->cs_box),
                                               P<int64_t>(h->cs_area), P<uint32_t>(h->d_mrep), P<uint16_t>(h->d_box), P<int64_t>(h->d_area),
                                               P<uint32_t>(h->d_comp_t), ci);
         h->fz_init = true;                        // (k_overlap: the resolver's view of every pair record is written with the record)
@@ -1060,12 +1060,12 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
         {
             Timer tm(h, CTK_K_RESOLVE);
             if (npass_grid > 0) {
-                if (sys_pass && npass <= 24) {
+                const CtkFilterRound fr = ctk_filter_round(T - r.t_lo, npass, !sys_pass, h->n_cus);
+                if (fr.blk) {
                     // all passes of the round in one launch (neighbour hand-shake through LDS / pstate, zeroed by k_rs_init / by the
                     // previous round's k_sh_unpack_keep); with `spec` also the 3-D unions of the surviving pairs
                     if (spec && parent_dirty) k_rs_parent_init<<<gc, 256, 0, s>>>(r);
-                    const int nb = (int)((T - r.t_lo + PB_G - 1) / PB_G);
-                    launch_rs_pass_blk(h, nb > h->n_cus, nb, r, it_done, npass, in.pair_base, in.pair_cnt, r.pstate, prepped ? 0 : 1, spec ? 1 : 0);
+                    launch_rs_pass_blk(h, fr.two_pc, fr.nb, r, it_done, npass, in.pair_base, in.pair_cnt, r.pstate, prepped ? 0 : 1, spec ? 1 : 0);
                     united = spec;
                     prepped = true;
                 } else {
@@ -1516,7 +1516,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     int32_t *cv = chunk_vals_for(h, flag_dev, &cv_rows);
     {
         Timer tm(h, CTK_K_RUNLABEL);
-        k_run_values<<<(int)T, 256, 0, s>>>(P<uint32_t>(h->run_base), P<uint32_t>(h->run_comp), CPX(h), P<int32_t>(h->comp_label), P<int32_t>(h->ext), NL,
+        k_run_values<<<(int)T, ctk_runval_threads(CTK_PATH_SHARDED, T, h->total_runs, h->small_threads[1]), 0, s>>>(P<uint32_t>(h->run_base), P<uint32_t>(h->run_comp), CPX(h), P<int32_t>(h->comp_label), P<int32_t>(h->ext), NL,
                                             persistence, P<uint32_t>(h->d_mrep), 0, 0, P<int32_t>(h->run_val), P<uint32_t>(h->rowstart), ny, cv_rows, cv);
         HIPCHK(hipGetLastError());
     }

@@ -69,6 +69,21 @@ int ctk_debug_time_relabel(ctk_handle *h, int32_t *flag_dev, int persistence, in
  * (test hook: by default it serves shards of more than 2048 timesteps on grids narrower than 1024) */
 int ctk_debug_set_small_threads(ctk_handle *h, int extent, int run_values, int compact_init);
 
+/* test hook, GPU-free, no handle: what the launch rules of contrack_amd/csrc/ctk_forms.h decide for a call of these numbers, so that
+ * the tests' restatements of the rules (tests/label_forms.py, tail_forms.py, threshold_forms.py) are compared with the library on the
+ * CPU.  Every field is an int64.  Query: a launch over timesteps [t0, t0 + nt) of a T-step shard of (ny, nx) planes; f64 / aligned16 /
+ * field: the slab's (for the write plan: the output's) element type and 16-byte alignment, the threshold-field call; max_runs_step,
+ * total_runs: what the run scan reported; n_labels, last_nlab: ids of this / the previous pass; async_passes, no_sys, n_cus, seg,
+ * pslot: the filter's state (for round_*: one round of async_passes passes over T timesteps); path: 0 staged, 1 fused, 2 time-sharded;
+ * forced_*: ctk_debug_set_small_threads; spec_set / launched: labelling variant sets as bits v1 1, v2 2, v3 4, glb 8, one 16, v1hi 32
+ * (the previous call's speculative set / what ran speculatively on buffers that were large enough).
+ * Plan: thr_kind 0 v7, 1 v6, 2 generic float32, 3 generic float64, 4 field vector, 5 field generic; *_bits as in CTK_S_LABEL_FORMS /
+ * CTK_S_FILTER_FORMS; overlap_form, extent_form, write_kernel, write_shape, count_* as the statistics of the same name report them;
+ * filter_unite 0 inside the pass kernel, 1 k_rs_unite_slots, 2 k_rs_unite. */
+typedef struct ctk_form_query { int64_t T, nt, ny, nx, f64, aligned16, field, max_runs_step, total_runs, n_labels, last_nlab, async_passes, no_sys, n_cus, seg, pslot, path, forced_extent, forced_run_values, forced_compact_init, spec_set, launched; } ctk_form_query;
+typedef struct ctk_form_plan { int64_t thr_kind, thr_u7, thr_rbt, thr_grid, rowcount_threads, v0b, v0_ok, v0_runs, need_glb, spec_launched, spec_bits, missing, missing_bits, next_spec, overlap_form, extent_form, write_kernel, write_rb, write_sub, write_kb, write_batched, write_lds, write_grid, write_shape, chunk_copy, runval_threads, compact_init_threads, count_staged, count_fused, filter_sys, filter_passes, filter_blk, filter_two_pc, filter_nb, filter_unite, filter_merged, filter_bits, filter_bits_sync, round_blk, round_two_pc, round_nb; } ctk_form_plan;
+int ctk_debug_forms(const ctk_form_query *q, ctk_form_plan *p);
+
 /* filter passes launched per round before convergence is checked on the host (default 10, 1..32)   */
 int ctk_set_filter_round(ctk_handle *h, int passes);
 

@@ -1,16 +1,18 @@
-"""Which row-count, 2-D labelling and overlap kernel forms a call launches: a restatement of contrack_amd/csrc/ctk_api.hip
-(k_rowcount's threads :1217, the labelling variants v0b / v0_ok / v0_runs :1236-1238 and launch_label2d :1239-1276, the speculative
-launch :1280-1286, the capacity check and regrowth :1308-1333, the launch after the run scan and the next call's speculative set
-:1345-1363, launch_overlap's forms :1522-1543) and of the instances' own guards in contrack_amd/csrc/ctk_kernels.hip (k_label2d_lds
-:1049-1110: the plane it takes :1086/:1103, the staged mask :1066; k_label2d_glb :1117; label2d_body's tables in LDS :948).
-Host-only.  Kept in step with the C++ by tests/test_label_forms.py and, on the GPU, by the statistics CTK_S_LABEL_FORMS,
+"""Which row-count, 2-D labelling and overlap kernel forms a call launches: a restatement of the rules in
+contrack_amd/csrc/ctk_forms.h (ctk_rowcount_threads, ctk_label_shape for v0b / v0_ok / v0_runs, ctk_label_speculative, ctk_label_plan
+for the launch after the run scan and the next call's speculative set, ctk_label_form_bits, ctk_overlap_form), of the protocol around
+them in contrack_amd/csrc/ctk_api.hip (label2d_speculate, label2d_regrow's capacity check, label2d_finish_labels, launch_label2d) and
+of the instances' own guards in contrack_amd/csrc/ctk_kernels.hip (k_label2d_lds: the planes it takes by RUNS / RUNS_BELOW / NYCAP, its
+staged mask; k_label2d_glb; label2d_body's component tables in LDS).
+Host-only.  Kept in step with the C++ by tests/test_label_forms.py which compares it with the library itself (ctk_debug_forms), and, on
+the GPU, by the statistics CTK_S_LABEL_FORMS,
 CTK_S_OVERLAP_FORM and CTK_S_ROWCOUNT_THREADS that tests/test_gpu_label_forms.py asserts.
 
 It also builds the planes that reach the forms: 0/1 planes with a prescribed number of runs, 2-D components (no wrap), seam rows
 and, for the pair edges, distinct overlapping (c, d) pairs with the next plane."""
 import numpy as np
 
-CTK_LDS_RUNS = 4096              # ctk_kernels.hip: runs an LDS variant can carry at most; beyond: k_label2d_glb
+CTK_LDS_RUNS = 4096              # ctk_device.h: runs an LDS variant can carry at most; beyond: k_label2d_glb
 CTK_LDS_NY = 1024                # ... rows; beyond: k_label2d_glb
 RC_ROWS = 2048                   # k_rowcount's first form: row totals in LDS
 CTK_PSLOT = 128                  # ctk_api.hip: pair-record slots per timestep of the fused path
@@ -39,14 +41,14 @@ def nwords(ny, nx):
 
 
 def rowcount_threads(T, ny, W):
-    """ctk_api.hip:1217"""
+    """ctk_rowcount_threads (ctk_forms.h)"""
     if W <= 64 and ny <= RC_ROWS and ny > 256 and T <= 2048:
         return 512
     return 128 if (T > 65536 and ny * W <= 2048) else 256
 
 
 def _v0(T, ny, W):
-    """(v0b, v0_ok, v0_runs): ctk_api.hip:1236-1238"""
+    """(v0b, v0_ok, v0_runs): ctk_label_shape (ctk_forms.h)"""
     v0b = ny <= 256 and 960 < ny * W <= 1088
     v0_ok = (T > 65536 and ny <= 256 and ny * W <= 960) or v0b
     return v0b, v0_ok, 768 if v0b else 832
@@ -63,7 +65,7 @@ def _v1hi_name(T, ny, W):
 
 def label_variant(T, ny, nx, nruns, prefer_one):
     """the instance that labels a plane of nruns runs.  prefer_one: the call runs the one-launch form (T <= 512 and some plane above
-    1024 runs, ctk_api.hip:1347-1350).  Each instance returns from planes outside its range (ctk_kernels.hip:1086, :1103, :1117), so
+    1024 runs, ctk_label_plan's prefer_one).  Each instance returns from planes outside its range (k_label2d_lds, k_label2d_glb), so
     the set launched decides nothing about a plane beyond which of these ranges exist; the ranges below are disjoint and cover all."""
     W = (nx + 63) // 64
     if nruns > CTK_LDS_RUNS or ny > CTK_LDS_NY:
@@ -81,7 +83,7 @@ def label_variant(T, ny, nx, nruns, prefer_one):
 
 
 def staged(variant, ny, W):
-    """the instance stages the plane's mask words in LDS (ctk_kernels.hip:1066).  For the two small-plane instances the staging edge
+    """the instance stages the plane's mask words in LDS (k_label2d_lds).  For the two small-plane instances the staging edge
     is the selection edge: v1_768 takes only planes of at most 1088 words = its COMPS * 4, v1_832 only planes of at most 960 = its
     COMPS * 4, and v1hi_768 / v1hi_832 serve the same planes; so these always stage and have no unstaged side."""
     if variant == "glb":
@@ -92,12 +94,12 @@ def staged(variant, ny, W):
 
 
 def tables_in_lds(variant, ncomp):
-    """label2d_body's component tables live in LDS (ctk_kernels.hip:948); k_label2d_glb passes no LDS table"""
+    """label2d_body's component tables live in LDS (ctk_kernels.hip); k_label2d_glb passes no LDS table"""
     return variant != "glb" and ncomp <= INSTANCES[variant][1]
 
 
 def overlap_form(T, ny, W, seg):
-    """CTK_S_OVERLAP_FORM of launch_overlap (ctk_api.hip:1522-1543)"""
+    """CTK_S_OVERLAP_FORM of launch_overlap: ctk_overlap_form (ctk_forms.h)"""
     nw = ny * W
     per = (nw + 255) // 256
     if T > 65536 and nw <= 2048:
@@ -122,7 +124,7 @@ def overlap_name(code):
 
 class Handle:
     """the speculation state of one ctk_handle (runs_cap, spec_set, spec_ny / spec_nx / spec_T) and the CTK_S_LABEL_FORMS bits of
-    every call that labels (ctk_api.hip:1280-1363)"""
+    every call that labels (label2d_speculate .. label2d_finish_labels in ctk_api.hip, with the rules of ctk_forms.h)"""
 
     def __init__(self):
         self.runs_cap = 0

@@ -1,31 +1,30 @@
-"""Which filter, rank, extent, run-value, write and count kernel forms a call launches: a restatement of
-contrack_amd/csrc/ctk_api.hip (relabel_rows :2162-2180, relabel_fast_ok :2181-2186, the chunk-ordered copy chunk_vals_for
-:2188-2197, launch_relabel :2200-2258 with the k_relabel_v5 image / budget / tab_batched choice :2218-2249, launch_extents
-:1733-1767, k_run_values' threads in ctk_shard_write :2271 and in the fused pass :2439, the alive-count kernels of ctk_shard_write
-:2285-2291 and of the fused pass :2457-2463, the filter passes, union and rank form of the fused pass :2385-2413 with the handle's
-pass count :2495 / :2512, the synchronous resolver's passes :1932-1937) and of the kernels' own edges in
-contrack_amd/csrc/ctk_kernels.hip (k_run_values' alive count :1751-1767, the chunk copy and the staged run values of k_relabel_v4
-:1874-1878 and relabel_v5_body :1991-1995, the valid bits of a row's last word :2008) and ctk_resolve_dev.hip (k_rs_pass'
-CTK_PASS_COMPS :261, k_rs_pass_blk's LDS edges :447-450).  Host-only.  Kept in step with the C++ by tests/test_tail_forms.py and,
-on the GPU, by the statistics CTK_S_FILTER_FORMS, CTK_S_EXTENT_FORM, CTK_S_RUNVAL_FORM, CTK_S_RELABEL_SHAPE and CTK_S_COUNT_FORM
+"""Which filter, rank, extent, run-value, write and count kernel forms a call launches: a restatement of the rules in
+contrack_amd/csrc/ctk_forms.h (ctk_write_rows, ctk_write_tables_lds, ctk_write_plan with the k_relabel_v5 image / budget / tab_batched
+choice, ctk_write_chunk_copy, ctk_extent_form, ctk_runval_threads for the staged, fused and time-sharded path, ctk_count_form_staged,
+ctk_count_form_fused, ctk_filter_plan_fused for the filter passes, union and rank form of the fused pass, ctk_filter_bits_sync for the
+synchronous resolver), of the handle's pass count in resolve_async (contrack_amd/csrc/ctk_api.hip) and of the kernels' own edges in
+contrack_amd/csrc/ctk_kernels.hip (k_run_values' alive count, the chunk copy and the staged run values of k_relabel_v4 and
+relabel_v5_body, the valid bits of a row's last word) and ctk_resolve_dev.hip (k_rs_pass' CTK_PASS_COMPS, k_rs_pass_blk's LDS edges
+PB_COMPS).  Host-only.  Kept in step with the C++ by tests/test_tail_forms.py, which compares it with the library itself
+(ctk_debug_forms), and, on the GPU, by the statistics CTK_S_FILTER_FORMS, CTK_S_EXTENT_FORM, CTK_S_RUNVAL_FORM, CTK_S_RELABEL_SHAPE and CTK_S_COUNT_FORM
 that tests/test_gpu_tail_forms*.py assert.
 
 It also builds the slabs that land on the edges: planes with a prescribed number of runs in every write chunk, dot lattices with
 a prescribed number of 3-D ids, and a removal cascade of a prescribed length."""
 import numpy as np
 
-CTK_CV = 64                      # ctk_kernels.hip: run values per chunk in the chunk-ordered copy
+CTK_CV = 64                      # ctk_device.h: run values per chunk in the chunk-ordered copy
 CTK_CV_MAXCHUNK = 1024           # chunks per timestep the copy is built for
 RV5 = 512                        # run values k_relabel_v5 stages in LDS
 RVCAP = 2048                     # ... k_relabel_v4
-CTK_RL_BLOCKS = 8192             # ctk_resolve_dev.hip: rank blocks of 256 runs the merged rank launch takes
+CTK_RL_BLOCKS = 8192             # ctk_device.h: rank blocks of 256 runs the merged rank launch takes
 PB_G = 16                        # timesteps per k_rs_pass_blk workgroup
 PB_COMPS = 128                   # components / pairs of a timestep whose sums live in LDS in k_rs_pass_blk
 CTK_PASS_COMPS = 512             # ... in k_rs_pass
 CTK_JACOBI_ROUND = 10
 CTK_MAX_JACOBI = 240
 EXTENT_BLK = 1024                # CTK_S_EXTENT_FORM of k_extent_blk
-MAX_SHARD_T = 4000000            # ctk_api.hip: timesteps a shard may hold
+MAX_SHARD_T = 4000000            # label2d_begin (ctk_api.hip): timesteps a shard may hold
 
 # CTK_S_FILTER_FORMS bits
 F_BLK, F_BLK_SEG, F_2PC, F_2PC_SEG, F_PASS, F_PASS_SEG, F_SYNC, F_SYNC_SEG, F_UNITE_SLOTS, F_UNITE, F_RANK_MERGED, F_RANK_SPLIT = \
@@ -46,7 +45,7 @@ def _a16(n):
 
 
 def relabel_rows(T, ny, nx):
-    """rows per write chunk (ctk_api.hip:2159-2177)"""
+    """rows per write chunk: ctk_write_rows (ctk_forms.h)"""
     n4r = max(1, nx // 4)
     rb = min(ny, max(1, min(64, 1024 // n4r)))
     store_cap = 2304 if n4r >= 256 else 6912
@@ -63,7 +62,7 @@ def _tables(rb, W):
 
 
 def _fast(nt, ny, nx, rb, aligned):
-    """the word-sliced kernels may run: ctk_api.hip:2220 (and relabel_fast_ok :2182 with the whole shard's T)"""
+    """the word-sliced kernels may run: the test of ctk_write_plan (ctk_forms.h; for the chunk copy with the whole shard's T)"""
     W = (nx + 63) // 64
     nchunk = (ny + rb - 1) // rb
     return (nx % 4 == 0 and aligned and ny * nx < 0x7fffffff and nt * nchunk < (1 << 24) and nt > 0
@@ -71,7 +70,7 @@ def _fast(nt, ny, nx, rb, aligned):
 
 
 def chunk_copy(T, ny, nx, aligned=True):
-    """k_run_values builds the chunk-ordered copy (chunk_vals_for, ctk_api.hip:2185-2194; not for run-table results)"""
+    """k_run_values builds the chunk-ordered copy (ctk_write_chunk_copy in ctk_forms.h; chunk_vals_for: not for run-table results)"""
     rb = relabel_rows(T, ny, nx)
     return _fast(T, ny, nx, rb, aligned) and (ny + rb - 1) // rb <= CTK_CV_MAXCHUNK
 
@@ -120,7 +119,7 @@ def stream_blocks(T, chunk):
 
 
 def extent_form(T, nx, forced=0):
-    """CTK_S_EXTENT_FORM (launch_extents, ctk_api.hip:1757-1761); forced: ctk_debug_set_small_threads' extent"""
+    """CTK_S_EXTENT_FORM (launch_extents: ctk_extent_form in ctk_forms.h); forced: ctk_debug_set_small_threads' extent"""
     if forced == 1024 or (forced == 0 and T > 2048 and nx < 1024):
         return EXTENT_BLK
     if forced:
@@ -160,7 +159,7 @@ def chunk_runs(mask, rb):
 
 
 def chunk_value_forms(kernel, cv, runs):
-    """where the write kernel takes a chunk's run values from (k_relabel_v4 :1882-1887, relabel_v5_body :1987-1991)"""
+    """where the write kernel takes a chunk's run values from (k_relabel_v4, relabel_v5_body in ctk_kernels.hip)"""
     out = set()
     cap = RV5 if kernel == 5 else RVCAP
     name = "v5" if kernel == 5 else "v4"
@@ -175,8 +174,8 @@ def chunk_value_forms(kernel, cv, runs):
 
 
 class Handle:
-    """the resolver state of one ctk_handle the fused pass reads (async_passes, last_nlab, no_sys: ctk_api.hip:2379-2380, :2445-2450,
-    :2482, :2499) and the forms a one-call track launches"""
+    """the resolver state of one ctk_handle the fused pass reads (async_passes, last_nlab, no_sys: resolve_async in ctk_api.hip, which hands
+    them to ctk_filter_plan_fused and ctk_count_form_fused and updates them from the pass' mail) and the forms a one-call track launches"""
 
     def __init__(self, n_cus):
         self.n_cus = n_cus
@@ -219,7 +218,7 @@ class Handle:
 
 
 def write_count(n_labels):
-    """ctk_shard_write's alive count (:2281-2288)"""
+    """ctk_shard_write's alive count: ctk_count_form_staged (ctk_forms.h)"""
     return W_1 if n_labels <= 262144 else W_FULL
 
 
@@ -372,7 +371,7 @@ def filter_slab(T, ny, nx, edges, fill=2):
 
 def filter_edge_forms(ncomp, npairs, filtered=None):
     """the LDS / lane edges of k_rs_pass_blk and k_rs_pass the filtered timesteps 1 .. T-2 reach: ncomp[t] components, npairs[t]
-    pair records with t - 1 (ctk_resolve_dev.hip:261, :447-450)"""
+    pair records with t - 1 (k_rs_pass, k_rs_pass_blk in ctk_resolve_dev.hip)"""
     T = len(ncomp)
     out = set()
     for t in range(1, T - 1):
@@ -461,7 +460,7 @@ CASCADE_T = 36
 _case("cascade", CASCADE_T, 32, 360, lambda: cascade_slab(CASCADE_T), {"pass_blk", "pass_sync", "pass_fused", "pass_fused:SEG", "count_1", "count_f", "unite", "unite_slots"},
       cascade=CASCADE_T - 1)
 
-# the filter passes' LDS edges (ctk_resolve_dev.hip:261, :447-450): a timestep t of nc one-row bars whose predecessor holds nb dots
+# the filter passes' LDS edges (CTK_PASS_COMPS of k_rs_pass, PB_COMPS of k_rs_pass_blk in ctk_resolve_dev.hip): a timestep t of nc one-row bars whose predecessor holds nb dots
 # (FILTER_EDGES: (t, nb, nc)); the bars' backward overlap is 1/3 while the dots live (removed), 0 if the dots were read as removed
 # (kept): a bar's fate depends on reading its predecessor's bits right.  w = (t - 1) % 16 is the wave of t in its k_rs_pass_blk
 # workgroup (0: the predecessor is in the workgroup before).

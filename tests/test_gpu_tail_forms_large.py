@@ -149,7 +149,7 @@ def test_multi_image_write(name, oracle_lib):
 
 
 def test_2p24_write_workgroups_is_beyond_the_shard_limit():
-    """The generic k_relabel's third condition, 2^24 workgroups a launch or more (ctk_api.hip:2223), needs one chunk a step (the rows
+    """The generic k_relabel's third condition, 2^24 workgroups a launch or more (ctk_write_plan in ctk_forms.h), needs one chunk a step (the rows
     rule grows the chunk until the launch fits or the chunk is the plane) and so 2^24 steps: beyond the 4 000 000 steps a shard may
     hold.  The call is refused before anything is written.  2 GB of device memory, a second."""
     T, ny, nx = 1 << 24, 4, 4

@@ -1,6 +1,7 @@
 """The planes of tests/test_gpu_label_forms.py have the run and component counts they claim, and together they reach every row-count,
 2-D labelling and overlap form on both sides of every branch the selection lets a plane reach (tests/label_forms.py restates the
-selection in ctk_api.hip and the kernels' guards).  No GPU needed."""
+selection in ctk_forms.h and the kernels' guards, and is compared here with what the library itself decides: ctk_debug_forms).  No GPU
+needed."""
 import numpy as np
 import pytest
 
@@ -88,3 +89,89 @@ def test_speculation_sequences_reach_their_branches():
         for T, ny, nx, runs in lf.spec_calls(seq):
             seen |= h.label2d(T, ny, nx, runs)
     assert seen & lf.DISCARDED_BIT and seen & lf.LABEL_BIT["one"] and seen & lf.LABEL_BIT["glb"] and seen & lf.LABEL_BIT["v1hi_832"]
+
+
+# ---- the restatement against the library's own rules (contrack_amd/csrc/ctk_forms.h, through ctk_debug_forms) -------------------
+_SET = ("v1", "v2", "v3", "glb", "one", "v1hi")                  # bit i of ctk_form_query.spec_set / .launched
+
+
+def _to_bits(vs):
+    return sum(1 << i for i, k in enumerate(_SET) if vs[k])
+
+
+def _from_bits(b):
+    return {k: bool(b >> i & 1) for i, k in enumerate(_SET)}
+
+
+class LibHandle:
+    """lf.Handle with every decision taken by the library: the speculative launch, the launch after the scan and the next call's
+    set come from ctk_label_speculative / ctk_label_plan / ctk_label_form_bits; what is left here is label2d_speculate's and
+    label2d_regrow's bookkeeping (ctk_api.hip)"""
+
+    def __init__(self):
+        self.runs_cap, self.spec, self.spec_shape, self.spec_T = 0, 0, None, -1
+
+    def label2d(self, T, ny, nx, runs):
+        from contrack_amd import _native
+        runs = np.asarray(runs, dtype=np.int64)
+        R, mx = int(runs.sum()), int(runs.max())
+        spec = self.runs_cap > 0 and self.spec_shape == (ny, nx) and (not self.spec & 8 or self.spec_T >= T)
+        p = _native.forms(T, ny, nx, max_runs_step=mx, spec_set=self.spec)
+        bits, launched = (p["spec_bits"], p["spec_launched"]) if spec else (0, 0)
+        if not (spec and R <= self.runs_cap):
+            self.runs_cap = min(R + R // 8 + 1024, 0xffffffff)
+            launched = 0
+            bits |= lf.DISCARDED_BIT if spec else 0
+        p = _native.forms(T, ny, nx, max_runs_step=mx, launched=launched)
+        self.spec, self.spec_shape, self.spec_T = p["next_spec"], (ny, nx), T
+        return bits | p["missing_bits"]
+
+
+_EDGE_T = (1, 512, 513, 1024, 1025, 2048, 2049, 65536, 65537)
+# (ny, nx): ny * W on both sides of 960, 1088 (also within 256 rows: 240 x 4 / 31 x 31, 136 x 8 / 33 x 33), 2048 and 8192 words; ny of 256 / 257, 1024 / 1025, 2048 / 2049 rows; W of 64 / 65 words
+_EDGE_GRIDS = [(ny, 64 * W) for ny, W in ((960, 1), (961, 1), (240, 4), (31, 31), (192, 5), (193, 5), (1088, 1), (1089, 1), (33, 33), (256, 4), (257, 4), (136, 8),
+                                           (137, 8), (2048, 1), (2049, 1), (128, 16), (129, 16), (8191, 1), (8192, 1), (128, 64), (127, 65),
+                                           (32, 2), (1024, 1), (1025, 1), (181, 6), (721, 23))] + [(181, 360), (192, 288), (721, 1440)]
+
+
+def test_shape_rules_agree_with_the_library():
+    from contrack_amd import _native
+    for T in _EDGE_T:
+        for ny, nx in _EDGE_GRIDS + [(c["ny"], c["nx"]) for c in lf.CASES]:
+            W = (nx + 63) // 64
+            for seg in (False, True):
+                p = _native.forms(T, ny, nx, seg=seg)
+                assert p["rowcount_threads"] == lf.rowcount_threads(T, ny, W), (T, ny, nx)
+                assert (bool(p["v0b"]), bool(p["v0_ok"]), p["v0_runs"]) == lf._v0(T, ny, W), (T, ny, nx)
+                assert p["overlap_form"] == lf.overlap_form(T, ny, W, seg), (T, ny, nx, seg)
+
+
+def test_labelling_protocol_agrees_with_the_library():
+    """one call from every state a handle can be in: every speculative set, run buffers that fit and that do not, the run edges of
+    every variant, short and long shards of plain, v0 and v0b planes and of planes no LDS variant takes"""
+    n = 0
+    for T in (4, 512, 513, 65537):
+        for ny, nx in ((181, 360), (32, 128), (721, 1440), (1025, 64)):
+            for mx in (0, 768, 769, 832, 833, 1024, 1025, 2048, 2049, 4096, 4097):
+                for spec in range(64):
+                    for cap, spec_T in ((0, T), (1 << 30, T), (1, T), (1 << 30, T - 1)):
+                        a, b = lf.Handle(), LibHandle()
+                        a.runs_cap = b.runs_cap = cap
+                        a.spec, b.spec = _from_bits(spec), spec
+                        a.spec_shape = b.spec_shape = (ny, nx)
+                        a.spec_T = b.spec_T = spec_T
+                        assert a.label2d(T, ny, nx, [mx, 3]) == b.label2d(T, ny, nx, [mx, 3]), (T, ny, nx, mx, spec, cap, spec_T)
+                        assert (_to_bits(a.spec), a.runs_cap) == (b.spec, b.runs_cap)
+                        n += 1
+    assert n > 40000
+
+
+def test_cases_and_sequences_agree_with_the_library():
+    for c in lf.CASES:
+        runs = [lf.claimed(c, k)[0] for k in lf.schedule_of(c)]
+        assert lf.Handle().label2d(c["T"], c["ny"], c["nx"], runs) == LibHandle().label2d(c["T"], c["ny"], c["nx"], runs), c["name"]
+    for seq in lf.SPEC_SEQUENCES:
+        a, b = lf.Handle(), LibHandle()
+        for T, ny, nx, runs in lf.spec_calls(seq):
+            assert a.label2d(T, ny, nx, runs) == b.label2d(T, ny, nx, runs), seq["name"]
+            assert _to_bits(a.spec) == b.spec

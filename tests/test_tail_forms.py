@@ -1,7 +1,7 @@
 """The slabs of tests/test_gpu_tail_forms.py have the run, id and pass counts they claim, and together with the large shapes of
 tests/test_gpu_tail_forms_large.py they reach every filter, rank, extent, run-value, write and count form on both sides of every
-branch the selection lets a slab reach (tests/tail_forms.py restates the selection in ctk_api.hip and the kernels' edges).  No GPU
-needed."""
+branch the selection lets a slab reach (tests/tail_forms.py restates the selection in ctk_forms.h and the kernels' edges, and
+is compared here with what the library itself decides: ctk_debug_forms).  No GPU needed."""
 import numpy as np
 import pytest
 from scipy import ndimage
@@ -138,3 +138,96 @@ def test_cases_reach_every_form():
     for v in tf.LARGE.values():
         got |= v[3]
     assert got == set(tf.FORMS), (sorted(set(tf.FORMS) - got), sorted(got - set(tf.FORMS)))
+
+
+# ---- the restatement against the library's own rules (contrack_amd/csrc/ctk_forms.h, through ctk_debug_forms) -------------------
+BASELINE_SHAPES = [(90, 181, 360), (2707, 181, 360), (480, 721, 1440), (14600, 721, 1440), (7300, 721, 1440), (58400, 721, 1440),
+                   (438000, 192, 288), (54750, 192, 288)]
+
+
+def _write_shapes():
+    out = BASELINE_SHAPES + [(c["T"], c["ny"], c["nx"]) for c in tf.CASES] + [v[:3] for v in tf.LARGE.values()]
+    out += [(6, 19, 4416), (6, 19, 4480), (6, 19, 4608), (6, 21, 362), (6, 1024, 4096), (6, 1025, 4096), (6, 65535, 4), (tf.MAX_SHARD_T, 65, 4)]
+    # the rows loop: launches of 130 000 / 130 001 workgroups before and after a step of rb, and its 2^24 cap
+    for ny, nx in ((721, 1440), (181, 360), (192, 288), (64, 4)):
+        for rb in range(1, 13):
+            nchunk = (ny + rb - 1) // rb
+            out += [(130000 // nchunk + d, ny, nx) for d in (0, 1)]
+    out += [((1 << 24) + d, ny, nx) for d in (-1, 0) for ny, nx in ((4, 4), (8, 1024), (1, 4))]
+    out += [((1 << 24) // 2 + d, 8, 4) for d in (-1, 0, 1)]
+    return sorted(set(out))
+
+
+def test_write_plan_agrees_with_the_library():
+    from contrack_amd import _native
+    kernels = set()
+    for T, ny, nx in _write_shapes():
+        W = (nx + 63) // 64
+        for aligned in (True, False):
+            whole = tf.write_form(T, ny, nx, aligned)
+            nchunk = (ny + whole["rb"] - 1) // whole["rb"]
+            # the whole shard, stream blocks on both sides of tab_batched's 200 000 workgroups, an empty block
+            for nt in sorted({T, min(T, 1), 0, min(T, 199999 // nchunk + 1), min(T, 199999 // nchunk + 2)}):
+                f = tf.write_form(T, ny, nx, aligned, nt=nt)
+                p = _native.forms(T, ny, nx, nt=nt, aligned16=aligned)
+                key = (T, ny, nx, aligned, nt)
+                assert p["write_rb"] == f["rb"] == tf.relabel_rows(T, ny, nx), key
+                assert p["write_kernel"] == (-1 if f["kernel"] is None else f["kernel"]), key
+                assert p["write_shape"] == tf.relabel_shape([f]), key
+                assert bool(p["chunk_copy"]) == tf.chunk_copy(T, ny, nx, aligned), key
+                if f["kernel"] == 5:
+                    assert (p["write_sub"], p["write_kb"], bool(p["write_batched"])) == (f["sub"], f["kb"], f["batched"]), key
+                    assert p["write_lds"] == tf._tables(f["rb"], W) + tf._a16(tf.RV5 * 4) + 16 + f["sub"] * nx * 4 <= f["kb"] * 1024, key
+                if f["kernel"] == 4:
+                    assert p["write_lds"] == tf._tables(f["rb"], W) + tf.RVCAP * 4, key
+                if f["kernel"] in (4, 5):
+                    assert p["write_grid"] == nt * nchunk, key
+                kernels.add(f["kernel"])
+    assert kernels == {5, 4, 0, None}
+
+
+def test_small_kernel_rules_agree_with_the_library():
+    from contrack_amd import _native
+    for T in (6, 2048, 2049, 65536, 65537):
+        for nx in (360, 1023, 1024, 1440):
+            for forced in (0, 64, 128, 256, 1024):
+                assert _native.forms(T, 8, nx, forced_extent=forced)["extent_form"] == tf.extent_form(T, nx, forced), (T, nx, forced)
+        for per in (1, 1023, 1024):
+            for path in (0, 1, 2):                                       # staged, fused, time-sharded
+                for forced in (0, 64, 128, 256):
+                    p = _native.forms(T, 8, 64, total_runs=T * per, path=path, forced_run_values=forced, forced_compact_init=forced)
+                    assert p["runval_threads"] == tf.runval_threads(T, T * per, path == 1, forced), (T, per, path, forced)
+                    # k_compact_init: a rule and the override in the fused pass only
+                    assert p["compact_init_threads"] == ((forced or (64 if T > 65536 else 256)) if path == 1 else 256), (T, path, forced)
+    for n in (0, 262144, 262145):
+        assert _native.forms(6, 8, 64, n_labels=n)["count_staged"] == tf.write_count(n)
+
+
+def test_fused_filter_plan_agrees_with_the_library():
+    from contrack_amd import _native
+    n = 0
+    for T in (1, 2, 3, 36, 4096, 4097, 4098, 1665, 1666):
+        for passes in (1, 2, 10, 24, 25, 32, 33, 48, 240, 300):
+            for last_nlab in (0, 1000000, 1000001):
+                for runs in (0, 100, tf.RANK_EDGE, tf.RANK_EDGE + 1):
+                    for n_cus in (104, 256):
+                        for seg in (False, True):
+                            for pslot in (0, 128):
+                                h = tf.Handle(n_cus)
+                                h.async_passes, h.last_nlab = passes, last_nlab
+                                bits, cnt, NP = h.fused(T, runs, seg)
+                                p = _native.forms(T, 8, 64, async_passes=passes, last_nlab=last_nlab, total_runs=runs, n_cus=n_cus, seg=seg, pslot=pslot)
+                                key = (T, passes, last_nlab, runs, n_cus, seg, pslot)
+                                unite = 0 if not h.unite_needed(T) else (tf.F_UNITE_SLOTS if pslot else tf.F_UNITE)
+                                assert p["filter_bits"] == bits | unite | (NP << 16), key
+                                assert (p["filter_passes"], p["count_fused"]) == (NP, cnt), key
+                                assert p["filter_unite"] == {0: 0, tf.F_UNITE_SLOTS: 1, tf.F_UNITE: 2}[unite], key
+                                assert p["filter_bits_sync"] == ((tf.F_SYNC_SEG if seg else tf.F_SYNC) if T > 2 else 0) | tf.F_UNITE, key
+                                n += 1
+    assert n > 8000
+    # a handle whose wait once gave up launches one kernel per pass; a round of the time-sharded path has the same two edges
+    assert _native.forms(36, 8, 64, no_sys=1)["filter_bits"] & tf.F_PASS and not _native.forms(36, 8, 64, no_sys=1)["filter_sys"]
+    for T, want in ((4096, 0), (4097, 1)):
+        p = _native.forms(T, 8, 64, async_passes=24, n_cus=256)
+        assert (p["round_blk"], p["round_two_pc"], p["round_nb"]) == (1, want, (T + tf.PB_G - 1) // tf.PB_G)
+    assert not _native.forms(4096, 8, 64, async_passes=25)["round_blk"] and not _native.forms(4096, 8, 64, no_sys=1)["round_blk"]

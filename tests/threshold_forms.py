@@ -1,9 +1,9 @@
-"""Which scalar threshold kernel a launch picks: a restatement of launch_threshold in contrack_amd/csrc/ctk_api.hip (threshold_rows
-:810, the float4 test v4 :1039, v6 :1065, the loads per lane u7 :1067-1072, the launch chain LAUNCH_THR :1080-1094), so that the
-tests can choose shapes that reach every form.  Host-only; kept in step with the C++ by tests/test_threshold_forms.py and, on the
-GPU, by a kernel trace of tests/test_gpu_threshold_scalar.py."""
+"""Which scalar threshold kernel a launch picks: a restatement of ctk_threshold_form in contrack_amd/csrc/ctk_forms.h (the rows per
+workgroup rbt, the float4 test v4, the ballot form v6, the loads per lane u7), which launch_threshold in ctk_api.hip maps to the
+kernel instance, so that the tests can choose shapes that reach every form.  Host-only; kept in step with the C++ by
+tests/test_threshold_forms.py, which compares it with the library itself (ctk_debug_forms), and, on the GPU, by a kernel trace of tests/test_gpu_threshold_scalar.py."""
 
-CTK_RB = 16                                      # rows per workgroup of the streaming kernels (ctk_kernels.hip)
+CTK_RB = 16                                      # rows per workgroup of the streaming kernels (ctk_device.h)
 FORMS = ("v7_4", "v7_5", "v7_6", "v7_7", "v7_8", "v6", "generic_f32", "generic_f64")
 
 
