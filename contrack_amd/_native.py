@@ -36,6 +36,7 @@ EXPORTS = [
     "ctk_track_stream_f32", "ctk_track_stream_f64", "ctk_track_stream_cb", "ctk_stream_times",
     "ctk_set_threshold_field", "ctk_set_segments",
     "ctk_frequency_dev", "ctk_frequency", "ctk_frequency_cb", "ctk_debug_set_freq", "ctk_debug_time_freq",
+    "ctk_percentile_groups_f32", "ctk_percentile_groups_f64", "ctk_debug_percentile_groups_sweeps", "ctk_debug_time_percentile_groups",
 ]
 
 READ_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)       # ctk_read_chunk_fn
@@ -184,6 +185,10 @@ def lib():
     for name in ("ctk_percentile_f32", "ctk_percentile_f64"):
         getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, i32, dbl, C.POINTER(dbl)]
     L.ctk_debug_percentile_values.argtypes = [p, p, i64]
+    for name in ("ctk_percentile_groups_f32", "ctk_percentile_groups_f64"):
+        getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, i32, p, i32, i32, dbl, p]
+    L.ctk_debug_percentile_groups_sweeps.argtypes = [p, C.POINTER(i64)]
+    L.ctk_debug_time_percentile_groups.argtypes = [p, p, i64, i32, i32, i32, i32, p, i32, i32, dbl, i32, p, p]
     L.ctk_comm_unique_id.argtypes = [p]
     L.ctk_comm_init_rccl.argtypes = [p, p, i32, i32, pp]
     L.ctk_comm_group_create.argtypes = [i32, pp]
@@ -824,6 +829,49 @@ class Tracker:
         fn = lib().ctk_percentile_f64 if f64 else lib().ctk_percentile_f32
         check(fn(self._h, ptr, T, ny, nx, int(y0), int(y1), float(q), C.byref(out)))
         return float(out.value)
+
+    def percentile_groups(self, x, y0, y1, group, ngroups, q, window=1):
+        """per group g the exact q-quantile (np.nanquantile, 'linear', float64) of rows [y0, y1) pooled over every timestep whose
+        group lies in the centred, circular window of `window` groups around g (ctk_percentile_groups_*); x (T, ny, nx) float32 /
+        float64, or None: the resident anomaly slab.  group: T ids in [0, ngroups).  Returns float64 (ngroups,)."""
+        if x is None:
+            shape = self.resident_anom()
+            if shape is None:
+                raise ContrackHipError("no anomaly slab is resident on the device")
+            T, ny, nx, f64 = shape
+            ptr = None
+        else:
+            x = np.ascontiguousarray(x)
+            if x.ndim != 3:
+                raise ValueError("x must be (time, lat, lon)")
+            f64 = x.dtype != np.float32
+            if f64:
+                x = np.ascontiguousarray(x, dtype=np.float64)
+            T, ny, nx = x.shape
+            ptr = x.ctypes.data
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        if group.shape != (T,):
+            raise ValueError("group must hold one id per timestep")
+        out = np.empty(int(ngroups), dtype=np.float64)
+        fn = lib().ctk_percentile_groups_f64 if f64 else lib().ctk_percentile_groups_f32
+        check(fn(self._h, ptr, T, ny, nx, int(y0), int(y1), group.ctypes.data, int(ngroups), int(window), float(q), out.ctypes.data))
+        return out
+
+    def debug_percentile_groups_sweeps(self):
+        """test hook: band reads of the last percentile_groups() call"""
+        n = C.c_int64(0)
+        check(lib().ctk_debug_percentile_groups_sweeps(self._h, C.byref(n)))
+        return int(n.value)
+
+    def time_percentile_groups(self, x_dev, T, ny, nx, y0, y1, group, ngroups, q, window=1, reps=3):
+        """measurement on a float32 slab in device memory (tools/pctl_probe.py): (values, ms per call, ms of one plain read of the
+        band, ms of the scalar percentile's kernels, ms of every band sweep of one call)"""
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        out = np.empty(int(ngroups), dtype=np.float64)
+        ms = (C.c_double * 12)()
+        check(lib().ctk_debug_time_percentile_groups(self._h, x_dev, int(T), int(ny), int(nx), int(y0), int(y1), group.ctypes.data, int(ngroups),
+                                                     int(window), float(q), int(reps), out.ctypes.data, ms))
+        return out, float(ms[0]), float(ms[1]), float(ms[2]), [float(v) for v in ms[3:3 + self.debug_percentile_groups_sweeps()]]
 
     def debug_percentile_values(self, n):
         """test hook: the n per-grid-point quantiles (band, row-major) of the last percentile() call"""

@@ -229,6 +229,36 @@ def frequency_numpy(flag, group=None, above=0, percent=True, device=None):
     return out[0] if group is None else out
 
 
+def percentile_groups_numpy(anom, rows, group, q, window=1, device=None):
+    """the threshold recipe of README.rst:235-240 on a (time, lat, lon) float slab: per group g (one id in [0, G) per timestep,
+    G = max(group) + 1, any order in time) the q-quantile of rows[0] <= y < rows[1] pooled over every timestep whose group lies in
+    the centred window of `window` groups around g, circular over the groups:
+        np.nanquantile(anom[np.isin(group, [(g + d) % G for d in range(-(window // 2), (window - 1) // 2 + 1)]), rows[0]:rows[1]]
+                       .astype(np.float64), q)
+    exactly (order statistics by radix selection on the GPU, numpy's linear interpolation; NaN for an empty pool).  Returns
+    float64 (G,)."""
+    anom = np.asarray(anom)
+    if anom.ndim != 3:
+        raise ValueError("anom must be (time, lat, lon)")
+    y0, y1 = (int(v) for v in rows)
+    _check_percentile_args(q, window)
+    if not 0 <= y0 < y1 <= anom.shape[1]:
+        raise ValueError("rows {} are not rows of a grid of {}".format((y0, y1), anom.shape[1]))
+    ids, G = _native._groups(group, anom.shape[0])
+    if ids is None:
+        ids, G = np.zeros(anom.shape[0], dtype=np.int32), 1
+    if anom.dtype.kind != "f":
+        anom = anom.astype(np.float64)
+    return _tracker(device).percentile_groups(anom, y0, y1, ids, G, q, window)
+
+
+def _check_percentile_args(q, window):
+    if not (0.0 <= float(q) <= 1.0):
+        raise ValueError("q = {} is not in [0, 1]".format(q))
+    if int(window) != window or int(window) < 1:
+        raise ValueError("window = {} (a whole number of groups, at least 1)".format(window))
+
+
 # ------------------------------------------------------------------------------------------------
 # the class
 # ------------------------------------------------------------------------------------------------
@@ -646,10 +676,18 @@ class contrack(object):
         return res[0] == _fingerprint(np.asarray(arr)) and res[1] == trk.resident_generation() and \
             trk.resident_anom() == (shape[0], shape[1], shape[2], bool(is_f64))
 
-    def percentile_threshold(self, variable='anom', q=0.90, lat_bounds=(50, 80)):
+    def percentile_threshold(self, variable='anom', q=0.90, lat_bounds=(50, 80), groupby=None, window=1):
         """the more objective threshold of the reference's README (README.rst:150-151):
         block[variable].sel(latitude=band).quantile([q], dim='time').mean() -- the mean over the latitude band of the
-        per-grid-point q-quantile over time.  Evaluated on the GPU (exact order statistics, numpy's linear interpolation)."""
+        per-grid-point q-quantile over time.  Evaluated on the GPU (exact order statistics, numpy's linear interpolation).
+
+        With groupby ('dayofyear', 'month', 'season', ...) the README's recommended recipe (README.rst:235-240): per value of
+        time.<groupby> the q-quantile of the whole band pooled over every timestep whose group lies in the centred window of
+        `window` groups around it (circular: 1 January sees late December), np.nanquantile in float64.  Returns a 1-D labelled
+        array over `groupby` (the values present, ascending); with groupby='dayofyear' it can be given to
+        run_contrack(threshold=...) as it is."""
+        if groupby is not None:
+            _check_percentile_args(q, window)
         self._ensure_set_up()
         slab, dims, sort = self._slab_tll(variable)
         lat = np.asarray(self.ds[self._latitude_name].data, dtype=np.float64)
@@ -658,8 +696,19 @@ class contrack(object):
             raise ValueError("latitude band {} selects no contiguous rows".format(lat_bounds))
         if slab.dtype.kind != "f":
             slab = slab.astype(np.float64)
+        ids, uniq = (None, None) if groupby is None else self._group_ids(groupby)
         resident = self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, slab.shape, slab.dtype != np.float32)
-        return _tracker().percentile(None if resident else slab, int(rows[0]), int(rows[-1]) + 1, q)
+        if groupby is None:
+            return _tracker().percentile(None if resident else slab, int(rows[0]), int(rows[-1]) + 1, q)
+        vals = _tracker().percentile_groups(None if resident else slab, int(rows[0]), int(rows[-1]) + 1, ids, len(uniq), q, int(window))
+        da = self.ds[variable]
+        attrs = {'long_name': '{} percentile threshold'.format(variable), 'q': float(q), 'window': int(window),
+                 'lat_bounds': (float(min(lat_bounds)), float(max(lat_bounds))),
+                 'history': ' '.join(['Calculated from {} with input attributes:', 'q = {},', 'latitude band = {},', 'groupby = {},',
+                                      'window = {} groups.']).format(variable, q, tuple(lat_bounds), groupby, window)}
+        if 'units' in getattr(da, "attrs", {}):
+            attrs['units'] = da.attrs['units']
+        return self._wrap(da, vals, (groupby,), {groupby: uniq}, attrs, name='{}_q{:g}'.format(variable, float(q) * 100))
 
     # ---- the hot path (contrack.py:583-796) -----------------------------------------------------------------
     def _dayofyear(self):

@@ -88,6 +88,23 @@ __device__ __forceinline__ uint64_t an_key(double v) { const uint64_t u = (uint6
 __device__ __forceinline__ float an_unkey(uint32_t k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
 __device__ __forceinline__ double an_unkey(uint64_t k) { return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k)); }
 
+// np.quantile(method='linear') of n >= 1 values from its order statistics: a = the value of rank lo = floor((n - 1) q), le = how
+// many values are <= a, nx = the smallest value above a (read only where rank lo + 1 exists and is not a again).  Shared by
+// k_quantile and k_pctl_finish (ctk_pctl.hip).
+__device__ __forceinline__ double an_np_quantile(uint64_t n, double q, double a, double nx, uint64_t le)
+{
+    const double h = ((double)n - 1.0) * q;
+    const uint64_t lo = (uint64_t)floor(h);
+    const double t = h - (double)lo;
+    const double bb = (le > lo + 1 || lo + 1 >= n) ? a : nx;
+    // numpy's _lerp exactly: a + (b - a) * t, taken from the other end for t >= 0.5 -- no shortcut for t == 0 or a == b
+    // (numpy gives NaN there when a or b is infinite: inf * 0, inf - inf)
+    const double d = bb - a;
+    double r = a + d * t;
+    if (t >= 0.5) r = bb - d * (1.0 - t);
+    return r;
+}
+
 template <typename VT, typename KT>
 __global__ __launch_bounds__(256) void k_quantile(const VT *__restrict__ x, int64_t T, int64_t npix, int64_t p0, int64_t nband, double q, double *__restrict__ out)
 {
@@ -148,19 +165,7 @@ __global__ __launch_bounds__(256) void k_quantile(const VT *__restrict__ x, int6
     }
     __syncthreads();
     if (threadIdx.x < 64 && live) {
-        double r = __builtin_nan("");
-        if (s_n[px]) {
-            const double h = ((double)s_n[px] - 1.0) * q;
-            const uint32_t lo = (uint32_t)floor(h);
-            const double t = h - (double)lo;
-            const double a = (double)an_unkey(s_prefix[px]);
-            const double bb = (s_le[px] > lo + 1 || lo + 1 >= s_n[px]) ? a : (double)an_unkey(s_next[px]);
-            // numpy's _lerp exactly: a + (b - a) * t, taken from the other end for t >= 0.5 -- no shortcut for t == 0 or a == b
-            // (numpy gives NaN there when a or b is infinite: inf * 0, inf - inf)
-            const double d = bb - a;
-            r = a + d * t;
-            if (t >= 0.5) r = bb - d * (1.0 - t);
-        }
+        const double r = s_n[px] ? an_np_quantile((uint64_t)s_n[px], q, (double)an_unkey(s_prefix[px]), (double)an_unkey(s_next[px]), (uint64_t)s_le[px]) : __builtin_nan("");
         out[pb] = r;
     }
 }

@@ -377,3 +377,37 @@ inline CtkFilterPlan ctk_filter_plan_fused(int64_t T, int async_passes, bool no_
 }
 // the synchronous resolver: one launch per pass over timesteps 1 .. T-2, k_rs_unite, split rank
 inline int64_t ctk_filter_bits_sync(int64_t T, bool seg) { return (T > 2 ? (seg ? CTK_FF_SYNC_SEG : CTK_FF_SYNC) : 0) | CTK_FF_UNITE; }
+
+// ------------------------------------------------------------------------------------------------
+// percentile per group (ctk_pctl.hip): radix selection over all groups at once
+// ------------------------------------------------------------------------------------------------
+#define CTK_PCTL_BITS 11          // widest digit: 2048 bins, 8 KB of uint32 per histogram
+#define CTK_PCTL_BINS (1 << CTK_PCTL_BITS)
+#define CTK_PCTL_LDS_SLOTS 4      // histograms a sweep workgroup keeps in LDS (32 KB: 4 workgroups per CU); the distinct prefixes of a
+                                  // day beyond them are deep digits, whose few matching values go to HBM one atomic each
+#define CTK_PCTL_MAX_WINDOW 1024  // distinct prefixes of a day's targets held in LDS (a window below the group count is at most this)
+#define CTK_PCTL_MAX_SLOTS (1ll << 19)   // histograms (groups x distinct prefixes per day) of 8 KB a call may ask for: 4 GB
+#define CTK_PCTL_CHUNK 16384      // band values per sweep workgroup (256 lanes x 16 loads of 16 bytes, float32)
+struct CtkPctlForm {
+    int levels;                   // sweeps that build histograms: 3 for 32-bit keys (11/11/10 bits), 6 for 64-bit (11/11/11/11/10/10)
+    int shift[8], bits[8];        // digit of level l: (key >> shift[l]) & ((1 << bits[l]) - 1), most significant first
+    int sweeps;                   // band reads of one call: levels + the closing sweep -- independent of the groups and the window
+    int stride;                   // histogram slots per day: the distinct prefixes its targets can have (1 when every group pools everything)
+    int64_t chunk;
+    unsigned chunks;              // workgroups per timestep
+};
+inline CtkPctlForm ctk_pctl_form(int keybits, int64_t nband, int G, int W)
+{
+    CtkPctlForm f = {};
+    f.levels = (keybits + CTK_PCTL_BITS - 1) / CTK_PCTL_BITS;
+    const int base = keybits / f.levels, extra = keybits % f.levels;
+    int left = keybits;
+    for (int l = 0; l < f.levels; l++) { f.bits[l] = base + (l < extra ? 1 : 0); left -= f.bits[l]; f.shift[l] = left; }
+    f.sweeps = f.levels + 1;
+    f.stride = W >= G ? 1 : W;
+    f.chunk = CTK_PCTL_CHUNK;
+    f.chunks = (unsigned)((nband + f.chunk - 1) / f.chunk);
+    return f;
+}
+// per-day histogram counters are uint32: a day's timesteps x band pixels must stay below 2^32
+inline bool ctk_pctl_day_fits(int64_t steps_of_day, int64_t nband) { return steps_of_day == 0 || nband <= (int64_t)0xffffffffll / steps_of_day; }

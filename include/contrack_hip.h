@@ -413,6 +413,21 @@ int ctk_track_resident(ctk_handle *h, const double *thr, int cmp_op, const float
  * time (numpy's linear interpolation, NaNs skipped), then the mean over the band.  x = NULL: the resident anomaly slab. */
 int ctk_percentile_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, int y0, int y1, double q, double *out);
 int ctk_percentile_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, int y0, int y1, double q, double *out);
+/* README.rst:235-240 (the threshold "defined as the 10th percentile of the ... anomaly distribution over 30-90N at each calendar day"),
+ * the producer of the 1-D dayofyear threshold that contrack.py:648-661 consumes.  Pooled, windowed, exact: for every group g
+ *   pool(g) = { x[t, y, :] : y0 <= y < y1, group[t] in { (g + d) mod ngroups : -(window / 2) <= d <= (window - 1) / 2 } }
+ *   out[g]  = np.nanquantile(pool(g) as float64, q)         (method 'linear', NaNs skipped; an empty pool gives NaN)
+ * The window is centred as calc_clim's and taken circularly over the groups (1 January sees late December); window >= ngroups pools
+ * every timestep for every group; a group without a timestep still gets the value of its window.  group: T host ints in
+ * [0, ngroups).  x = NULL: the resident anomaly slab (shape and dtype must match).  The band is read 4 times (float32) or 7 times
+ * (float64), whatever ngroups and window are.  Device memory: ngroups x window (1 when window >= ngroups) histograms of 8 KB,
+ * 93 MB at 366 x 31.  CTK_E_INVALID: bad arguments (checked before any device call), a window below ngroups but above 1024, more
+ * than 2^19 histograms (4 GB), or a group whose timesteps x band values reach 2^32 (its counters are uint32). */
+int ctk_percentile_groups_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group, int ngroups, int window,
+                              double q, double *out /* ngroups */);
+/* README.rst:235-240 / contrack.py:648-661: the same on a float64 slab (64-bit keys: 7 reads of the band) */
+int ctk_percentile_groups_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group, int ngroups, int window,
+                              double q, double *out /* ngroups */);
 
 /* ---- the blocking-frequency climatology of the reference's tutorial (README.rst:159-160) ---------------------------------------
  *   xr.where(block['flag'] > 1, 1, 0).sum(dim='time') / block.ntime * 100     -- on the int32 flag slab (T, ny, nx), per group:

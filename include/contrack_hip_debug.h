@@ -130,6 +130,15 @@ int ctk_debug_time_freq(ctk_handle *h, const int32_t *flag_dev, int64_t T, int n
  * major), before their mean is taken; an error if no result is held (a ctk_anom_* call or ctk_release_io in between) or n differs */
 int ctk_debug_percentile_values(ctk_handle *h, double *out, int64_t n);
 
+/* test hook: how often the last ctk_percentile_groups_* call on this handle read the band (launches of k_pctl_sweep and k_pctl_close) */
+int ctk_debug_percentile_groups_sweeps(ctk_handle *h, int64_t *sweeps);
+/* measurement (tools/pctl_probe.py) on a float32 slab in device memory: ms12 = { ctk_percentile_groups per call (best of reps, host
+ * clock: upload of the ids, every kernel, download, synchronisation), one plain 16-byte read stream over the band with the sweeps'
+ * grid (best of reps, HIP events), the scalar percentile's kernels (k_quantile + k_nanmean, once, HIP events), then the band sweeps
+ * of one more call one by one (HIP events), 0 beyond the last }; out: the ngroups results */
+int ctk_debug_time_percentile_groups(ctk_handle *h, const float *x_dev, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group, int ngroups,
+                                     int window, double q, int reps, double *out, double *ms12);
+
 #ifdef __cplusplus
 }
 #endif
