@@ -2,7 +2,8 @@
 
 `contrack` is the drop-in class (same constructor / set_up / calc_anom / run_contrack signatures and the
 same 'flag' output variable as steidani/ConTrack's contrack.contrack); `track_numpy` is the array-level
-entry underneath it, `frequency_numpy` the blocking frequency (README.rst:159-160 of the reference) of its `flag`.
+entry underneath it, `frequency_numpy` the blocking frequency (README.rst:159-160 of the reference) of its `flag`,
+`percentile_field_numpy` the per-grid-point percentile threshold field per group of timesteps.
 Compute goes through hand-written HIP kernels behind a ctypes C ABI
 (include/contrack_hip.h); there is no CPU fallback.
 """
@@ -10,7 +11,7 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name in ("contrack", "track_numpy", "frequency_numpy", "row_weights", "prepare_thresholds"):
+    if name in ("contrack", "track_numpy", "frequency_numpy", "percentile_field_numpy", "row_weights", "prepare_thresholds"):
         from . import contrack as _m
         return getattr(_m, name)
     raise AttributeError(name)

@@ -37,6 +37,7 @@ EXPORTS = [
     "ctk_set_threshold_field", "ctk_set_segments",
     "ctk_frequency_dev", "ctk_frequency", "ctk_frequency_cb", "ctk_debug_set_freq", "ctk_debug_time_freq",
     "ctk_percentile_groups_f32", "ctk_percentile_groups_f64", "ctk_debug_percentile_groups_sweeps", "ctk_debug_time_percentile_groups",
+    "ctk_percentile_field_f32", "ctk_percentile_field_f64", "ctk_debug_percentile_field_plan", "ctk_debug_percentile_field_form", "ctk_debug_time_percentile_field",
 ]
 
 READ_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)       # ctk_read_chunk_fn
@@ -69,6 +70,14 @@ class FormPlan(C.Structure):
     """ctk_form_plan of include/contrack_hip_debug.h"""
     _fields_ = [(n, C.c_int64) for n in (
         "thr_kind thr_u7 thr_rbt thr_grid rowcount_threads v0b v0_ok v0_runs need_glb spec_launched spec_bits missing missing_bits next_spec overlap_form extent_form write_kernel write_rb write_sub write_kb write_batched write_lds write_grid write_shape chunk_copy runval_threads compact_init_threads count_staged count_fused filter_sys filter_passes filter_blk filter_two_pc filter_nb filter_unite filter_merged filter_bits filter_bits_sync round_blk round_two_pc round_nb").split()]
+
+
+def debug_percentile_field_plan(keybytes, max_pool_steps, ngroups, window):
+    """ctk_debug_percentile_field_plan: what ctk_pfield_plan (csrc/ctk_forms.h) decides, as a dict (form 0 direct / 1 ring, cap in pool
+    timesteps, pixel tile, ring bytes); no handle, no GPU"""
+    v = np.zeros(4, dtype=np.int64)
+    check(lib().ctk_debug_percentile_field_plan(int(keybytes), int(max_pool_steps), int(ngroups), int(window), v.ctypes.data))
+    return dict(form=int(v[0]), cap=int(v[1]), tile=int(v[2]), ring_bytes=int(v[3]))
 
 
 def forms(T, ny, nx, nt=None, aligned16=True, async_passes=24, n_cus=256, **query):
@@ -189,6 +198,11 @@ def lib():
         getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, i32, p, i32, i32, dbl, p]
     L.ctk_debug_percentile_groups_sweeps.argtypes = [p, C.POINTER(i64)]
     L.ctk_debug_time_percentile_groups.argtypes = [p, p, i64, i32, i32, i32, i32, p, i32, i32, dbl, i32, p, p]
+    for name in ("ctk_percentile_field_f32", "ctk_percentile_field_f64"):
+        getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, i32, p, i32, i32, dbl, p]
+    L.ctk_debug_percentile_field_plan.argtypes = [i32, i64, i32, i32, p]
+    L.ctk_debug_percentile_field_form.argtypes = [p, p]
+    L.ctk_debug_time_percentile_field.argtypes = [p, p, i32, i64, i32, i32, i32, i32, p, i32, i32, dbl, i32, p, p, p]
     L.ctk_comm_unique_id.argtypes = [p]
     L.ctk_comm_init_rccl.argtypes = [p, p, i32, i32, pp]
     L.ctk_comm_group_create.argtypes = [i32, pp]
@@ -872,6 +886,53 @@ class Tracker:
         check(lib().ctk_debug_time_percentile_groups(self._h, x_dev, int(T), int(ny), int(nx), int(y0), int(y1), group.ctypes.data, int(ngroups),
                                                      int(window), float(q), int(reps), out.ctypes.data, ms))
         return out, float(ms[0]), float(ms[1]), float(ms[2]), [float(v) for v in ms[3:3 + self.debug_percentile_groups_sweeps()]]
+
+    def percentile_field(self, x, y0, y1, group, ngroups, q, window=1):
+        """per group g and grid point of rows [y0, y1) the exact q-quantile (np.nanquantile, 'linear', float64) over every timestep
+        whose group lies in the centred, circular window of `window` groups around g (ctk_percentile_field_*); x (T, ny, nx)
+        float32 / float64, or None: the resident anomaly slab.  group: T ids in [0, ngroups).  Returns float64
+        (ngroups, y1 - y0, nx)."""
+        if x is None:
+            shape = self.resident_anom()
+            if shape is None:
+                raise ContrackHipError("no anomaly slab is resident on the device")
+            T, ny, nx, f64 = shape
+            ptr = None
+        else:
+            x = np.ascontiguousarray(x)
+            if x.ndim != 3:
+                raise ValueError("x must be (time, lat, lon)")
+            f64 = x.dtype != np.float32
+            if f64:
+                x = np.ascontiguousarray(x, dtype=np.float64)
+            T, ny, nx = x.shape
+            ptr = x.ctypes.data
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        if group.shape != (T,):
+            raise ValueError("group must hold one id per timestep")
+        out = np.empty((max(int(ngroups), 0), max(int(y1) - int(y0), 0), nx), dtype=np.float64)
+        fn = lib().ctk_percentile_field_f64 if f64 else lib().ctk_percentile_field_f32
+        check(fn(self._h, ptr, T, ny, nx, int(y0), int(y1), group.ctypes.data, int(ngroups), int(window), float(q), out.ctypes.data))
+        return out
+
+    def debug_percentile_field_form(self):
+        """test hook: (form, longest pool in timesteps) of the last percentile_field() call; form 0 direct, 1 ring, -1 none yet"""
+        v = np.zeros(2, dtype=np.int64)
+        check(lib().ctk_debug_percentile_field_form(self._h, v.ctypes.data))
+        return int(v[0]), int(v[1])
+
+    def time_percentile_field(self, x_dev, T, ny, nx, y0, y1, group, ngroups, q, window=1, reps=3, f64=False, want_fields=True):
+        """measurement on a slab in device memory (tools/pfield_probe.py): (field of the chosen form, field of the direct form
+        forced -- both None without want_fields --, ms per call of the chosen form, ms of the direct form, ms of one plain read
+        of the band, the chosen form)"""
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        shape = (int(ngroups), int(y1) - int(y0), int(nx))
+        a = np.empty(shape, dtype=np.float64) if want_fields else None
+        b = np.empty(shape, dtype=np.float64) if want_fields else None
+        ms = (C.c_double * 4)()
+        check(lib().ctk_debug_time_percentile_field(self._h, x_dev, int(bool(f64)), int(T), int(ny), int(nx), int(y0), int(y1), group.ctypes.data,
+                                                    int(ngroups), int(window), float(q), int(reps), _ptr(a), _ptr(b), ms))
+        return a, b, float(ms[0]), float(ms[1]), float(ms[2]), int(ms[3])
 
     def debug_percentile_values(self, n):
         """test hook: the n per-grid-point quantiles (band, row-major) of the last percentile() call"""

@@ -252,6 +252,27 @@ def percentile_groups_numpy(anom, rows, group, q, window=1, device=None):
     return _tracker(device).percentile_groups(anom, y0, y1, ids, G, q, window)
 
 
+def percentile_field_numpy(anom, rows, group, q, window=1, device=None):
+    """the per-grid-point twin of percentile_groups_numpy: per group g and grid point of rows[0] <= y < rows[1] the q-quantile over
+    every timestep whose group lies in the centred window of `window` groups around g, circular over the groups:
+        np.nanquantile(anom[np.isin(group, [(g + d) % G for d in range(-(window // 2), (window - 1) // 2 + 1)]), rows[0]:rows[1]]
+                       .astype(np.float64), q, axis=0)
+    exactly (ctk_percentile_field_*; NaN for an empty or all-NaN pool).  Returns float64 (G, rows[1] - rows[0], nx)."""
+    anom = np.asarray(anom)
+    if anom.ndim != 3:
+        raise ValueError("anom must be (time, lat, lon)")
+    y0, y1 = (int(v) for v in rows)
+    _check_percentile_args(q, window)
+    if not 0 <= y0 < y1 <= anom.shape[1]:
+        raise ValueError("rows {} are not rows of a grid of {}".format((y0, y1), anom.shape[1]))
+    ids, G = _native._groups(group, anom.shape[0])
+    if ids is None:
+        ids, G = np.zeros(anom.shape[0], dtype=np.int32), 1
+    if anom.dtype.kind != "f":
+        anom = anom.astype(np.float64)
+    return _tracker(device).percentile_field(anom, y0, y1, ids, G, q, window)
+
+
 def _check_percentile_args(q, window):
     if not (0.0 <= float(q) <= 1.0):
         raise ValueError("q = {} is not in [0, 1]".format(q))
@@ -709,6 +730,41 @@ class contrack(object):
         if 'units' in getattr(da, "attrs", {}):
             attrs['units'] = da.attrs['units']
         return self._wrap(da, vals, (groupby,), {groupby: uniq}, attrs, name='{}_q{:g}'.format(variable, float(q) * 100))
+
+    def percentile_field(self, variable='anom', q=0.90, groupby='dayofyear', window=1, lat_bounds=None):
+        """the local definition of an extreme: per value of time.<groupby> and per grid point the q-quantile over every timestep
+        whose group lies in the centred window of `window` groups around it (circular: 1 January sees late December),
+        np.nanquantile in float64, evaluated exactly on the GPU.  Returns a labelled array over (groupby, latitude, longitude) on
+        the whole grid (the group values present, ascending); rows outside lat_bounds (None: every row) are NaN and are never
+        flagged.  With groupby='dayofyear' it can be given to run_contrack(threshold=...) as it is."""
+        _check_percentile_args(q, window)
+        self._ensure_set_up()
+        slab, dims, sort = self._slab_tll(variable)
+        lat = np.asarray(self.ds[self._latitude_name].data, dtype=np.float64)
+        bounds = (lat.min(), lat.max()) if lat_bounds is None else lat_bounds
+        rows = np.nonzero((lat >= min(bounds)) & (lat <= max(bounds)))[0]
+        if len(rows) == 0 or not np.array_equal(rows, np.arange(rows[0], rows[-1] + 1)):
+            raise ValueError("latitude band {} selects no contiguous rows".format(lat_bounds))
+        if slab.dtype.kind != "f":
+            slab = slab.astype(np.float64)
+        ids, uniq = self._group_ids(groupby)
+        resident = self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, slab.shape, slab.dtype != np.float32)
+        y0, y1 = int(rows[0]), int(rows[-1]) + 1
+        band = _tracker().percentile_field(None if resident else slab, y0, y1, ids, len(uniq), q, int(window))
+        vals = np.full((len(uniq),) + slab.shape[1:], np.nan)
+        vals[:, y0:y1] = band
+        da = self.ds[variable]
+        attrs = {'long_name': '{} percentile threshold field'.format(variable), 'q': float(q), 'window': int(window),
+                 'lat_bounds': (float(min(bounds)), float(max(bounds))),
+                 'history': ' '.join(['Calculated from {} with input attributes:', 'q = {},', 'latitude band = {},', 'groupby = {},',
+                                      'window = {} groups.']).format(variable, q, tuple(float(b) for b in bounds), groupby, window)}
+        if 'units' in getattr(da, "attrs", {}):
+            attrs['units'] = da.attrs['units']
+        coords = {groupby: uniq}
+        for name in (self._latitude_name, self._longitude_name):
+            coords[name] = np.asarray(self.ds[name].data)
+        return self._wrap(da, vals, (groupby, self._latitude_name, self._longitude_name), coords, attrs,
+                          name='{}_q{:g}_field'.format(variable, float(q) * 100))
 
     # ---- the hot path (contrack.py:583-796) -----------------------------------------------------------------
     def _dayofyear(self):

@@ -411,3 +411,47 @@ inline CtkPctlForm ctk_pctl_form(int keybits, int64_t nband, int G, int W)
 }
 // per-day histogram counters are uint32: a day's timesteps x band pixels must stay below 2^32
 inline bool ctk_pctl_day_fits(int64_t steps_of_day, int64_t nband) { return steps_of_day == 0 || nband <= (int64_t)0xffffffffll / steps_of_day; }
+
+// ------------------------------------------------------------------------------------------------
+// percentile field per group and grid point (ctk_pfield.hip): a radix selection per (group, pixel)
+// ------------------------------------------------------------------------------------------------
+#define CTK_PFIELD_LDS_BYTES 163840   // what a workgroup may declare on gfx950
+#define CTK_PFIELD_RING_THREADS 512   // ring form: lanes per pixel = 512 / pixel tile
+#define CTK_PFIELD_DIRECT_THREADS 256
+#define CTK_PFIELD_DIRECT_TILE 64     // direct form: pixels per workgroup (4 lanes per pixel, as k_quantile)
+#define CTK_PFIELD_MIN_TILE 8         // ring form: the pixel tile is 32, 16 or 8 -- the widest whose ring holds the longest pool
+#define CTK_PFIELD_MAX_TILE 32
+enum CtkPfieldForm { CTK_PFIELD_DIRECT = 0, CTK_PFIELD_RING = 1 };
+// LDS of a selection workgroup beside the ring: 257 uint32 bins per pixel, one partial sum per lane, 64 bytes of rank state per pixel
+constexpr int64_t ctk_pfield_select_bytes(int tile, int threads) { return (int64_t)tile * 257 * 4 + (int64_t)threads * 4 + (int64_t)tile * 64; }
+// timesteps the ring of a workgroup of `tile` pixels holds
+constexpr int64_t ctk_pfield_ring_steps(int keybytes, int tile)
+{
+    return (CTK_PFIELD_LDS_BYTES - ctk_pfield_select_bytes(tile, CTK_PFIELD_RING_THREADS)) / ((int64_t)tile * keybytes);
+}
+// the longest pool (in timesteps) the ring form takes: 4 783 for float32, 2 391 for float64
+#define CTK_PFIELD_CAP_F32 ctk_pfield_ring_steps(4, CTK_PFIELD_MIN_TILE)
+#define CTK_PFIELD_CAP_F64 ctk_pfield_ring_steps(8, CTK_PFIELD_MIN_TILE)
+struct CtkPfieldPlan {
+    int form;                     // CtkPfieldForm
+    int64_t cap;                  // longest pool of the ring form for this key width
+    int tile;                     // pixels per workgroup
+    int64_t ring_steps, ring_bytes;   // the ring of the chosen tile (0: direct form)
+    int planes;                   // planes selected: G, or 1 when the window covers every group (the plane is replicated)
+};
+// max_pool_steps: the most timesteps any group's window pools
+inline CtkPfieldPlan ctk_pfield_plan(int keybytes, int64_t max_pool_steps, int G, int W)
+{
+    CtkPfieldPlan p = {};
+    p.cap = keybytes == 4 ? CTK_PFIELD_CAP_F32 : CTK_PFIELD_CAP_F64;
+    p.planes = W >= G ? 1 : G;
+    p.form = max_pool_steps <= p.cap ? CTK_PFIELD_RING : CTK_PFIELD_DIRECT;
+    p.tile = CTK_PFIELD_DIRECT_TILE;
+    if (p.form == CTK_PFIELD_RING) {
+        p.tile = CTK_PFIELD_MAX_TILE;
+        while (p.tile > CTK_PFIELD_MIN_TILE && ctk_pfield_ring_steps(keybytes, p.tile) < max_pool_steps) p.tile /= 2;
+        p.ring_steps = ctk_pfield_ring_steps(keybytes, p.tile);
+        p.ring_bytes = p.ring_steps * p.tile * keybytes;
+    }
+    return p;
+}

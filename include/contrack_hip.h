@@ -428,6 +428,20 @@ int ctk_percentile_groups_f32(ctk_handle *h, const float *x, int64_t T, int ny, 
 /* README.rst:235-240 / contrack.py:648-661: the same on a float64 slab (64-bit keys: 7 reads of the band) */
 int ctk_percentile_groups_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group, int ngroups, int window,
                               double q, double *out /* ngroups */);
+/* The per-grid-point twin: the threshold FIELD over (group, latitude, longitude) that ctk_set_threshold_field consumes -- the
+ * q-quantile over time AT EACH GRID POINT of rows [y0, y1), per group, pooled over the same centred, circular window of groups:
+ *   pool(g, y, x') = { x[t, y, x'] : group[t] in { (g + d) mod ngroups : -(window / 2) <= d <= (window - 1) / 2 } }
+ *   out[g][y - y0][x'] = np.nanquantile(pool as float64, q)  (method 'linear', NaNs skipped; an empty or all-NaN pool gives NaN)
+ * exactly: infinities, signed zeros and subnormals as numpy's _lerp treats them.  x = NULL: the resident anomaly slab.  Two forms
+ * (ctk_pfield_plan, csrc/ctk_forms.h; csrc/ctk_pfield.hip): while the longest pool has at most 4 783 timesteps (float32; 2 391 for
+ * float64) a workgroup keeps the pool of its 32, 16 or 8 pixels in LDS as a ring of timesteps and walks the groups, so the slab
+ * is read 1 + window / ngroups times; longer pools are selected straight from HBM, group by group.  window >= ngroups: one plane
+ * is selected and replicated.  Device memory: the ngroups planes.  CTK_E_INVALID: bad arguments (checked before any device
+ * call), T >= 2^31 (pool counts are uint32), ngroups x band pixels / 8 beyond 2^31 - 1. */
+int ctk_percentile_field_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group, int ngroups, int window,
+                             double q, double *out /* ngroups * (y1 - y0) * nx */);
+int ctk_percentile_field_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group, int ngroups, int window,
+                             double q, double *out /* ngroups * (y1 - y0) * nx */);
 
 /* ---- the blocking-frequency climatology of the reference's tutorial (README.rst:159-160) ---------------------------------------
  *   xr.where(block['flag'] > 1, 1, 0).sum(dim='time') / block.ntime * 100     -- on the int32 flag slab (T, ny, nx), per group:

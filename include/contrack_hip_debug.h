@@ -139,6 +139,19 @@ int ctk_debug_percentile_groups_sweeps(ctk_handle *h, int64_t *sweeps);
 int ctk_debug_time_percentile_groups(ctk_handle *h, const float *x_dev, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group, int ngroups,
                                      int window, double q, int reps, double *out, double *ms12);
 
+/* what ctk_pfield_plan (csrc/ctk_forms.h) decides for keys of `keybytes` (4 / 8) bytes, a longest pool of max_pool_steps timesteps,
+ * ngroups and window: out4 = { form (0 direct, 1 ring), the ring form's cap in pool timesteps, pixels per workgroup, bytes of the ring
+ * (0: direct form) }.  Host only: no handle, no GPU. */
+int ctk_debug_percentile_field_plan(int keybytes, int64_t max_pool_steps, int ngroups, int window, int64_t *out4);
+/* test hook: out2 = { form the last ctk_percentile_field_* call on this handle took (-1: none yet), its longest pool in timesteps } */
+int ctk_debug_percentile_field_form(ctk_handle *h, int64_t *out2);
+/* measurement (tools/pfield_probe.py) on a slab in device memory (is_f64 != 0: float64): ms4 = { the form ctk_pfield_plan chooses,
+ * the direct form forced on the same input (both per call, best of reps, host clock: upload of the lists, every kernel,
+ * synchronisation; the download of the field is outside), one plain 16-byte read stream over the band (k_pctl_read, best of reps,
+ * HIP events), the chosen form (0 direct, 1 ring) }; out / out_direct (either may be NULL): the two fields, ngroups * (y1 - y0) * nx */
+int ctk_debug_time_percentile_field(ctk_handle *h, const void *x_dev, int is_f64, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group,
+                                    int ngroups, int window, double q, int reps, double *out, double *out_direct, double *ms4);
+
 #ifdef __cplusplus
 }
 #endif
