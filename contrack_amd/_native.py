@@ -24,7 +24,7 @@ EXPORTS = [
     "ctk_track_f32_dev", "ctk_track_f64", "ctk_track_f64_dev", "ctk_release_io", "ctk_shard_label2d", "ctk_shard_label2d_f64", "ctk_shard_halo_size", "ctk_shard_halo_export",
     "ctk_shard_halo_import", "ctk_shard_overlap", "ctk_shard_tables", "ctk_resolve", "ctk_result_free",
     "ctk_result_info", "ctk_result_arrays", "ctk_result_nshards", "ctk_weights_to_limbs", "ctk_shard_extents", "ctk_shard_write",
-    "ctk_shard_count_tracked", "ctk_debug_mask", "ctk_debug_label2d", "ctk_debug_set_pair_capacity", "ctk_debug_set_mailbox", "ctk_debug_set_seam_caps", "ctk_debug_set_spin", "ctk_debug_set_small_threads", "ctk_debug_forms", "ctk_debug_np_sum", "ctk_debug_boundary_resolve", "ctk_set_timing", "ctk_get_timings", "ctk_get_timing_sums", "ctk_set_device_resolve", "ctk_set_fused_pass", "ctk_set_result_transfer", "ctk_expand_runs_host", "ctk_set_filter_round", "ctk_get_stats", "ctk_get_stats_n", "ctk_debug_stream_ceiling", "ctk_debug_time_relabel",
+    "ctk_shard_count_tracked", "ctk_debug_mask", "ctk_debug_label2d", "ctk_debug_set_pair_capacity", "ctk_debug_set_mailbox", "ctk_debug_set_seam_caps", "ctk_debug_set_spin", "ctk_debug_set_small_threads", "ctk_debug_forms", "ctk_debug_np_sum", "ctk_debug_boundary_resolve", "ctk_debug_boundary_resolve_breaks", "ctk_set_timing", "ctk_get_timings", "ctk_get_timing_sums", "ctk_set_device_resolve", "ctk_set_fused_pass", "ctk_set_result_transfer", "ctk_expand_runs_host", "ctk_set_filter_round", "ctk_get_stats", "ctk_get_stats_n", "ctk_debug_stream_ceiling", "ctk_debug_time_relabel",
     "ctk_dev_malloc", "ctk_dev_free", "ctk_host_alloc", "ctk_host_free", "ctk_host_register", "ctk_host_unregister", "ctk_memcpy_h2d", "ctk_memcpy_d2h", "ctk_sync", "ctk_stream",
     "ctk_synth_fill",
     "ctk_comm_unique_id", "ctk_comm_init_rccl", "ctk_comm_group_create", "ctk_comm_group_destroy", "ctk_comm_init_local", "ctk_comm_init_shm",
@@ -35,6 +35,7 @@ EXPORTS = [
     "ctk_lifecycle_f32", "ctk_lifecycle_f64", "ctk_lifecycle_f32_dev", "ctk_lifecycle_f64_dev", "ctk_lifecycle_rows", "ctk_lifecycle_exact",
     "ctk_track_stream_f32", "ctk_track_stream_f64", "ctk_track_stream_cb", "ctk_stream_times",
     "ctk_set_threshold_field", "ctk_set_segments",
+    "ctk_track_stream_seg_f32", "ctk_track_stream_seg_f64", "ctk_track_stream_seg_cb", "ctk_track_sharded_seg_f32_dev", "ctk_track_sharded_seg_f64_dev",
     "ctk_frequency_dev", "ctk_frequency", "ctk_frequency_cb", "ctk_debug_set_freq", "ctk_debug_time_freq",
     "ctk_percentile_groups_f32", "ctk_percentile_groups_f64", "ctk_debug_percentile_groups_sweeps", "ctk_debug_time_percentile_groups",
     "ctk_percentile_field_f32", "ctk_percentile_field_f64", "ctk_debug_percentile_field_plan", "ctk_debug_percentile_field_form", "ctk_debug_time_percentile_field",
@@ -116,6 +117,9 @@ def lib():
     L.ctk_track_stream_f32.argtypes = track_args + [i64]
     L.ctk_track_stream_f64.argtypes = track_args + [i64]
     L.ctk_track_stream_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, p, i32, p, dbl, i32, i32, WRITE_CHUNK_FN, p, C.POINTER(i64), i64]
+    L.ctk_track_stream_seg_f32.argtypes = track_args + [i64, p, i64]
+    L.ctk_track_stream_seg_f64.argtypes = track_args + [i64, p, i64]
+    L.ctk_track_stream_seg_cb.argtypes = L.ctk_track_stream_cb.argtypes + [p, i64]
     L.ctk_stream_times.argtypes = [p, C.POINTER(dbl)]
     L.ctk_frequency_dev.argtypes = [p, p, i64, i32, i32, p, i32, C.c_int32, p, i32]
     L.ctk_frequency.argtypes = [p, p, i64, i32, i32, p, i32, C.c_int32, p, i64]
@@ -150,6 +154,7 @@ def lib():
     L.ctk_debug_np_sum.argtypes = [p, sz]
     L.ctk_debug_np_sum.restype = dbl
     L.ctk_debug_boundary_resolve.argtypes = [i32, p, p, p, p, p, p, p, p, p]
+    L.ctk_debug_boundary_resolve_breaks.argtypes = [i32, p, p, p, p, p, p, p, p, p, p]
     L.ctk_set_timing.argtypes = [p, i32]
     L.ctk_get_timings.argtypes = [p, p]
     L.ctk_get_timing_sums.argtypes = [p, p, p, i32]
@@ -222,8 +227,18 @@ def lib():
     sharded_args = [p, p, p, i64, i64, i64, i32, i32, p, i32, p, dbl, i32, i32, p, C.POINTER(i64)]
     L.ctk_track_sharded_f32_dev.argtypes = sharded_args
     L.ctk_track_sharded_f64_dev.argtypes = sharded_args
+    L.ctk_track_sharded_seg_f32_dev.argtypes = sharded_args + [p, i64]
+    L.ctk_track_sharded_seg_f64_dev.argtypes = sharded_args + [p, i64]
     _lib = L
     return L
+
+
+def _seg_starts(segments):
+    """segment starts given with a call as a C-contiguous int64 array (the library checks their values)"""
+    st = np.asarray(segments)
+    if st.ndim != 1 or (st.size and st.dtype.kind not in "iu"):
+        raise ValueError("segment starts must be a 1-D integer array")
+    return np.ascontiguousarray(st, dtype=np.int64)
 
 
 def _thr_or_field(thr, T):
@@ -632,7 +647,8 @@ class Tracker:
         return flag, int(n.value)
 
     # ---- streaming entries (next row N4) ------------------------------------------------------------------------
-    def track_stream(self, source, thr, cmp_op, wrow, overlap, persistence, twosided=True, sink=None, shape=None, dtype=None, chunk_steps=0):
+    def track_stream(self, source, thr, cmp_op, wrow, overlap, persistence, twosided=True, sink=None, shape=None, dtype=None, chunk_steps=0,
+                     segments=None):
         """ctk_track_* with the slab passing through chunk-sized device buffers (device footprint: 4 chunks + slab / 32).
 
         source: a (T, ny, nx) float32 / float64 array (np.memmap included), or a callable reader(t0, nt, out) that fills
@@ -640,6 +656,8 @@ class Tracker:
                 and `dtype` are required;
         sink:   None (a new int32 array is returned), an int32 array (T, ny, nx), or a callable writer(t0, nt, flags) that
                 receives each flag chunk as a (nt, ny, nx) int32 view valid during the call.
+        segments: None, or the first step of every independent time segment (0 first, strictly increasing, below T) -- the
+                semantics of set_segments, given with the call (ctk_track_stream_seg_*); breaks and chunks are unrelated.
         Returns (flag array or None, n_tracked)."""
         L = lib()
         if callable(source):
@@ -668,9 +686,14 @@ class Tracker:
             out = sink
         n = C.c_int64(0)
         tail = (_ptr(thr), int(cmp_op), wrow.ctypes.data, float(overlap), int(persistence), int(bool(twosided)))
+        st = None if segments is None else _seg_starts(segments)
+        seg = () if st is None else (st.ctypes.data if st.size else None, st.shape[0])
         if not callable(source) and not callable(sink):
-            fn = L.ctk_track_stream_f64 if dt == np.float64 else L.ctk_track_stream_f32
-            check(fn(self._h, source.ctypes.data, T, ny, nx, *tail, sink.ctypes.data, C.byref(n), int(chunk_steps)))
+            if st is None:
+                fn = L.ctk_track_stream_f64 if dt == np.float64 else L.ctk_track_stream_f32
+            else:
+                fn = L.ctk_track_stream_seg_f64 if dt == np.float64 else L.ctk_track_stream_seg_f32
+            check(fn(self._h, source.ctypes.data, T, ny, nx, *tail, sink.ctypes.data, C.byref(n), int(chunk_steps), *seg))
             return out, int(n.value)
         errors = []
 
@@ -698,7 +721,8 @@ class Tracker:
                 errors.append(e)
                 return 1
         rcb, wcb = READ_CHUNK_FN(rd), WRITE_CHUNK_FN(wr)
-        rc = L.ctk_track_stream_cb(self._h, dt.itemsize, T, ny, nx, rcb, None, *tail, wcb, None, C.byref(n), int(chunk_steps))
+        fn = L.ctk_track_stream_cb if st is None else L.ctk_track_stream_seg_cb
+        rc = fn(self._h, dt.itemsize, T, ny, nx, rcb, None, *tail, wcb, None, C.byref(n), int(chunk_steps), *seg)
         if errors:
             raise errors[0]
         check(rc)
@@ -1052,15 +1076,21 @@ class Tracker:
         return int(n.value)
 
     def track_sharded_dev(self, comm, anom_dev, T_local, t_begin, T_total, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, flag_dev,
-                          f64=False):
-        """the whole path on the time shard [t_begin, t_begin + T_local) of T_total steps; every rank of `comm` must call"""
+                          f64=False, segments=None):
+        """the whole path on the time shard [t_begin, t_begin + T_local) of T_total steps; every rank of `comm` must call.
+        segments: None, or the first step of every independent time segment as GLOBAL indices into [0, T_total) (0 first, strictly
+        increasing), the same on every rank (ctk_track_sharded_seg_*_dev)"""
         tp, wp, thr, wrow = self._thr_w_ptrs(thr, wrow)
         if thr is not None and thr.shape != (T_local,):
             raise ValueError("thr must hold one value per local timestep")
         n = C.c_int64(0)
-        fn = lib().ctk_track_sharded_f64_dev if f64 else lib().ctk_track_sharded_f32_dev
+        if segments is None:
+            fn, seg = (lib().ctk_track_sharded_f64_dev if f64 else lib().ctk_track_sharded_f32_dev), ()
+        else:
+            st = _seg_starts(segments)
+            fn, seg = (lib().ctk_track_sharded_seg_f64_dev if f64 else lib().ctk_track_sharded_seg_f32_dev), (st.ctypes.data if st.size else None, st.shape[0])
         check(fn(self._h, comm.ptr, anom_dev, int(T_local), int(t_begin), int(T_total), ny, nx, tp, int(cmp_op), wp,
-                 float(overlap), int(persistence), int(bool(twosided)), flag_dev, C.byref(n)))
+                 float(overlap), int(persistence), int(bool(twosided)), flag_dev, C.byref(n), *seg))
         return int(n.value)
 
     # ---- run_lifecycle reductions ------------------------------------------------------------------------

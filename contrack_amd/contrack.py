@@ -19,7 +19,8 @@ Stated deviations from the reference:
     and the C ABI stay int32.
   * the numpy array behind `ds['anom']` after `calc_anom` is read-only (its twin stays in HBM for `run_contrack`); assign a
     new array to the variable to change it.
-  * `run_contrack(..., chunk_steps=n)` (extension): stream the variable through the GPU in slices of n time steps.
+  * `run_contrack(..., chunk_steps=n)` (extension): stream the variable through the GPU in slices of n time steps; combines with
+    `segments='gaps'` and with a member dimension.
 """
 import logging
 import os
@@ -149,7 +150,7 @@ def gap_starts(steps):
     return np.concatenate([[0], np.nonzero(steps > steps.min())[0] + 1]).astype(np.int64)
 
 
-def track_numpy(anom, wrow, threshold, gorl, overlap, persistence, twosided=True, device=None, segments=None):
+def track_numpy(anom, wrow, threshold, gorl, overlap, persistence, twosided=True, device=None, segments=None, chunk_steps=None):
     """run_contrack on a (time, lat, lon) numpy slab.  Returns (flag int32 (T,ny,nx), n_tracked).
 
     anom float32 (other dtypes are compared exactly in float64 on the device), wrow float32 (ny,) from
@@ -157,7 +158,9 @@ def track_numpy(anom, wrow, threshold, gorl, overlap, persistence, twosided=True
     that broadcasts against anom, e.g. (ny, nx) or (T, ny, nx) -- pixel (t, y, x) is compared with its own value, under numpy's
     promotion rules; gorl in {'>=','<=','>','<','ge','le','gt','lt'}.
     segments (extension): int array of segment starts (0 first, strictly increasing) -- independent series concatenated in time
-    (ensemble members, seasons); no overlap, filter exemption or 3-D link crosses a break, ids stay unique over the slab."""
+    (ensemble members, seasons); no overlap, filter exemption or 3-D link crosses a break, ids stay unique over the slab.
+    chunk_steps (extension): stream the slab (an array or np.memmap the host holds) through chunk-sized device buffers, that many
+    time steps at a time (0: about 256 MB each); same result, with or without segments."""
     if gorl not in _native.CMP_OPS:
         raise ValueError(_native.GORL_ERRMSG)
     anom = np.asarray(anom)
@@ -166,6 +169,16 @@ def track_numpy(anom, wrow, threshold, gorl, overlap, persistence, twosided=True
     field = broadcast_field(threshold, anom.shape) if is_threshold_field(threshold) else None
     thr = None if field is not None else prepare_thresholds(threshold, anom.shape[0], anom.dtype)
     trk = _tracker(device)
+    if chunk_steps is not None:
+        # the streaming entries take the starts with the call (the handle's sticky segments are for the one-call entries)
+        starts = None if segments is None else segment_starts(segments, anom.shape[0])
+        if anom.dtype not in (np.float32, np.float64):
+            if anom.dtype.kind not in "fiub":
+                raise TypeError("anom must be a real numeric array")
+            anom = anom.astype(np.float64)
+        call = lambda t: trk.track_stream(anom, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, chunk_steps=int(chunk_steps),
+                                          segments=starts)
+        return call(thr) if field is None else _track_field(trk, field[0], field[1], call)
     if anom.dtype != np.float32:
         if anom.dtype.kind not in "fiub":
             raise TypeError("anom must be a real numeric array")
@@ -866,9 +879,13 @@ class contrack(object):
         smallest step: a seasonal selection) or the name of an extra dimension of the variable (e.g. 'member': each member is a
         segment; the threshold is a number, a per-time vector or a 'dayofyear' DataArray, applied to every member).  Every
         segment is tracked as if alone (no overlap, filter exemption or 3-D link across a break); ids stay unique over the
-        whole result.  Not with chunk_steps."""
-        if segments is not None and chunk_steps is not None:
-            raise ValueError("segments and chunk_steps cannot be combined (the streaming path does not take segment breaks)")
+        whole result.  With chunk_steps: 'gaps' and a member dimension stream as any other call (each slice is read when its turn
+        comes -- for a member dimension `isel(member=m, time=slice)`, a chunk that spans two members in two pieces; the flattened
+        (member * time, lat, lon) slab is never built on the host); explicit start indices together with chunk_steps stay refused
+        here -- track_numpy(..., segments=starts, chunk_steps=n) takes them."""
+        if segments is not None and chunk_steps is not None and not isinstance(segments, str):
+            raise ValueError("segments given as start indices and chunk_steps cannot be combined in run_contrack; use segments='gaps' or a "
+                             "member dimension, or track_numpy(..., segments=starts, chunk_steps=n)")
         self._ensure_set_up()
         da = self.ds[variable]
         dims = tuple(da.dims)
@@ -900,9 +917,15 @@ class contrack(object):
         # them as it goes through them, contrack.py:646-772)
         logger.info("Apply overlap...")
         logger.info("Apply persistence...")
-        if chunk_steps is not None:
+        if chunk_steps is not None and member is not None:
+            # every member read slice by slice: flat step m * T + t is isel(member=m, time=t)
+            flag, n_tracked = self._run_members_streaming(trk, da, dims, member, starts, threshold, gorl, wrow, overlap, persistence, twosided,
+                                                          int(chunk_steps))
+            slab = None
+        elif chunk_steps is not None:
             # the variable is read slice by slice and passes through chunk-sized device buffers
-            flag, n_tracked = self._run_streaming(trk, da, dims, sort, threshold, gorl, wrow, overlap, persistence, twosided, int(chunk_steps))
+            flag, n_tracked = self._run_streaming(trk, da, dims, sort, threshold, gorl, wrow, overlap, persistence, twosided, int(chunk_steps),
+                                                  starts)
             slab = None
         elif member is not None:
             # (member, time, lat, lon) flattened to (member * time, lat, lon): each member is one segment
@@ -956,23 +979,50 @@ class contrack(object):
         arr = np.asarray(da.data).transpose(sort4)
         M, T = arr.shape[0], arr.shape[1]
         slab = np.ascontiguousarray(arr.reshape((M * T,) + arr.shape[2:]), dtype=np.float32 if arr.dtype == np.float32 else np.float64)
-        if hasattr(threshold, "dims") and hasattr(threshold, "data") and np.ndim(threshold.data) >= 2:
-            if 'dayofyear' not in threshold.dims:
-                raise ValueError("a threshold with dims {} has no 'dayofyear' dimension".format(tuple(threshold.dims)))
-            planes, pos = self._doy_field(threshold)
-            thr, field = None, (planes, np.tile(pos, M))
-        elif is_threshold_field(threshold):
-            raise ValueError("segments={!r}: a numpy threshold field cannot be combined with a member dimension; give a number, a "
-                             "per-time vector or a 'dayofyear' DataArray".format(member))
-        else:
-            thr, field = np.tile(self._thresholds_per_step(threshold, T, slab.dtype), M), None
+        thr, field = self._member_threshold_args(threshold, member, M, T, slab.dtype)
         f64 = slab.dtype == np.float64
         call = lambda t: trk.track(slab, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, f64=f64)
         flag, n = _track_segments(trk, starts, lambda: call(thr) if field is None else _track_field(trk, field[0], field[1], call))
         return flag, n, slab
 
-    def _run_streaming(self, trk, da, dims, sort, threshold, gorl, wrow, overlap, persistence, twosided, chunk_steps):
-        """run_contrack with the variable read slice by slice"""
+    def _member_threshold_args(self, threshold, member, M, T, dtype):
+        """(thr, field) of a call over M members of T steps each: the threshold of a time step applies to every member"""
+        if hasattr(threshold, "dims") and hasattr(threshold, "data") and np.ndim(threshold.data) >= 2:
+            if 'dayofyear' not in threshold.dims:
+                raise ValueError("a threshold with dims {} has no 'dayofyear' dimension".format(tuple(threshold.dims)))
+            planes, pos = self._doy_field(threshold)
+            return None, (planes, np.tile(pos, M))
+        if is_threshold_field(threshold):
+            raise ValueError("segments={!r}: a numpy threshold field cannot be combined with a member dimension; give a number, a "
+                             "per-time vector or a 'dayofyear' DataArray".format(member))
+        return np.tile(self._thresholds_per_step(threshold, T, dtype), M), None
+
+    def _run_members_streaming(self, trk, da, dims, member, starts, threshold, gorl, wrow, overlap, persistence, twosided, chunk_steps):
+        """run_contrack over an extra dimension with the variable read slice by slice: flat step m * T + t of the (M * T, lat, lon)
+        series is step t of member m, read as isel(member=m, time=slice) -- a chunk that spans two members in two pieces; the
+        flattened slab exists nowhere on the host.  Returns (flag (M*T, ny, nx), n)."""
+        tname = self._time_name
+        M, T = da.shape[dims.index(member)], da.shape[dims.index(tname)]
+        dims3 = tuple(d for d in dims if d != member)                             # what isel(member=m) leaves
+        sort3 = [dims3.index(d) for d in (tname, self._latitude_name, self._longitude_name)]
+        shape = (M * T,) + tuple(da.shape[dims.index(d)] for d in (self._latitude_name, self._longitude_name))
+        dtype = np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
+        thr, field = self._member_threshold_args(threshold, member, M, T, dtype)
+
+        def reader(t0, nt, out):
+            done = 0
+            while done < nt:
+                m, t = divmod(t0 + done, T)
+                n = min(nt - done, T - t)
+                part = da.isel(**{member: m, tname: slice(t, t + n)})
+                out[done:done + n] = np.asarray(part.data).transpose(sort3)
+                done += n
+        call = lambda t: trk.track_stream(reader, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, shape=shape, dtype=dtype,
+                                          chunk_steps=chunk_steps, segments=starts)
+        return call(thr) if field is None else _track_field(trk, field[0], field[1], call)
+
+    def _run_streaming(self, trk, da, dims, sort, threshold, gorl, wrow, overlap, persistence, twosided, chunk_steps, starts=None):
+        """run_contrack with the variable read slice by slice; starts: segment breaks of the call"""
         shape = tuple(da.shape[i] for i in sort)                                  # (time, lat, lon)
         dtype = np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
         thr, field = self._threshold_args(threshold, da.shape, sort, shape[0], dtype)
@@ -982,8 +1032,9 @@ class contrack(object):
             part = da.isel(**{tname: slice(t0, t0 + nt)}) if hasattr(da, "isel") else None
             arr = np.asarray(part.data if part is not None else np.asarray(da.data).take(range(t0, t0 + nt), axis=dims.index(tname)))
             out[...] = arr.transpose(sort)
+        seg = {} if starts is None else {"segments": starts}        # (no segments: the call as it has always been made)
         call = lambda t: trk.track_stream(reader, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, shape=shape, dtype=dtype,
-                                          chunk_steps=chunk_steps)
+                                          chunk_steps=chunk_steps, **seg)
         return call(thr) if field is None else _track_field(trk, field[0], field[1], call)
 
     # ---- blocking frequency (README.rst:159-160), consumer of `flag` ------------------------------------------------------

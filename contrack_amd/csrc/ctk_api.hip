@@ -334,6 +334,12 @@ struct ctk_handle {
     std::vector<uint8_t> seg_edge_host;
     int64_t seg_edge_T = -1;
     const uint8_t *seg_cur = nullptr;
+    // ... and its host twin, indexed like seg_cur (the host resolver; a time shard reads the bits of its first and last step from it)
+    const uint8_t *seg_cur_host = nullptr;
+    // segment starts given to the running call as an argument (ctk_track_stream_seg_*; empty: none): every pass of that call
+    // -- the dense re-run too -- builds its table from them
+    std::vector<int64_t> seg_call;
+    bool seg_shard_breaks = false;                       // a time-shard call with more than one segment (every rank alike) is running
     // blocking frequency (ctk_freq.hip): counts of the host entries, group ids; experiments (ctk_debug_set_freq)
     DevBuf fq_counts, fq_group;
     // percentile per group (ctk_pctl.hip): histograms per (day, distinct prefix); ranks, prefixes, lists, ids; band sweeps of the last call
@@ -922,6 +928,51 @@ static int segment_table(ctk_handle *h, int64_t T)
         h->seg_edge_T = T;
     }
     h->seg_cur = P<uint8_t>(h->seg_edge);
+    h->seg_cur_host = h->seg_edge_host.data();
+    return CTK_OK;
+}
+
+// Segment starts given as an ARGUMENT of a call (the streaming and time-shard entries, ctk_track_*_seg_*): the rules of
+// ctk_set_segments, the last start below the `T_total` steps of the whole slab, and no sticky segments on the handle beside them.
+static int segment_args_check(const ctk_handle *h, const char *who, const int64_t *starts, int64_t nseg, int64_t T_total)
+{
+    if (!h->seg_starts.empty())
+        return ctk_set_error(CTK_E_INVALID, "%s: segments are set on this handle (ctk_set_segments) and given as an argument; clear the handle's first", who);
+    if (nseg < 0 || (nseg > 0 && !starts)) return ctk_set_error(CTK_E_INVALID, "%s: bad segment arguments (nseg=%lld)", who, (long long)nseg);
+    if (nseg == 0) return CTK_OK;
+    if (starts[0] != 0) return ctk_set_error(CTK_E_INVALID, "%s: segment starts[0] = %lld, must be 0", who, (long long)starts[0]);
+    for (int64_t k = 1; k < nseg; k++)
+        if (starts[k] <= starts[k - 1])
+            return ctk_set_error(CTK_E_INVALID, "%s: segment starts must be strictly increasing (starts[%lld] = %lld after %lld)", who, (long long)k,
+                                 (long long)starts[k], (long long)starts[k - 1]);
+    if (starts[nseg - 1] >= T_total)
+        return ctk_set_error(CTK_E_INVALID, "%s: the last segment starts at step %lld, the slab has %lld steps", who, (long long)starts[nseg - 1], (long long)T_total);
+    return CTK_OK;
+}
+
+// The edge table of the (checked) starts `st` over a slab of T_total steps; the steps [t_begin, t_begin + T) of it -- a time shard, or
+// the whole slab -- become the current table of the launches and of the host.  One segment: no table, the unsegmented kernels.
+static int segment_table_call(ctk_handle *h, const std::vector<int64_t> &st, int64_t T_total, int64_t t_begin, int64_t T)
+{
+    h->seg_cur = nullptr; h->seg_cur_host = nullptr;
+    if (st.size() < 2 || T < 1) return CTK_OK;
+    std::vector<uint8_t> &e = h->seg_edge_host;
+    h->seg_edge_T = -1;                                        // (not the table segment_table remembers)
+    e.assign((size_t)T_total, 0);
+    for (size_t k = 0; k < st.size(); k++) {
+        e[(size_t)st[k]] |= 1u;
+        if (st[k] > 0) e[(size_t)st[k] - 1] |= 2u;
+    }
+    e[(size_t)T_total - 1] |= 2u;
+    // a shard inside one segment launches the unsegmented kernels (the first step of the slab and its last one are edges to them too)
+    bool any = false;
+    for (int64_t t = t_begin; t < t_begin + T && !any; t++)
+        any = (e[(size_t)t] & ~((t == 0 ? 1u : 0u) | (t == T_total - 1 ? 2u : 0u))) != 0;
+    if (!any) return CTK_OK;
+    CTKCHK(ensure(h, h->seg_edge, (size_t)T));
+    HIPCHK(hipMemcpy(h->seg_edge.p, e.data() + t_begin, (size_t)T, hipMemcpyHostToDevice));
+    h->seg_cur = P<uint8_t>(h->seg_edge);
+    h->seg_cur_host = e.data() + t_begin;
     return CTK_OK;
 }
 
@@ -2617,10 +2668,13 @@ static int track_dev_impl(ctk_handle *h, const void *anom_dev, bool f64, int64_t
     const double t0 = now_ms();
     HT0();
     h->in_one_call = true;
-    struct OneCall { ctk_handle *h; ~OneCall() { h->in_one_call = false; h->seg_cur = nullptr; } } one_call{h};
+    struct OneCall { ctk_handle *h; ~OneCall() { h->in_one_call = false; h->seg_cur = nullptr; h->seg_cur_host = nullptr; } } one_call{h};
     if (!h->seg_starts.empty()) {
         HIPCHK(hipSetDevice(h->device));
         CTKCHK(segment_table(h, T));
+    } else if (!h->seg_call.empty()) {                         // the starts a streaming entry was given (checked there against this T)
+        HIPCHK(hipSetDevice(h->device));
+        CTKCHK(segment_table_call(h, h->seg_call, T, 0, T));
     }
     CTKCHK(shard_label2d_impl(h, anom_dev, f64, T, ny, nx, thr, cmp_op, wrow, 0));
     HT("label2d stage done");
@@ -2667,7 +2721,7 @@ static int track_dev_impl(ctk_handle *h, const void *anom_dev, bool f64, int64_t
         const double t1 = now_ms();
         ctk_result *res = nullptr;
         ExactFromDevice exact(h);                                 // numpy-order sums for decisions flagged ambiguous
-        CTKCHK(ctk_resolve_ex(&blob, &nbytes, 1, overlap, twosided, &exact, &res, h->seg_cur ? h->seg_edge_host.data() : nullptr));
+        CTKCHK(ctk_resolve_ex(&blob, &nbytes, 1, overlap, twosided, &exact, &res, h->seg_cur ? h->seg_cur_host : nullptr));
         h->ms[CTK_T_HOST_RESOLVE] += now_ms() - t1;
         h->stats[CTK_S_AMBIGUOUS] = res->n_ambiguous;
         h->stats[CTK_S_EXACT_FIXUPS] = res->n_exact;
@@ -3163,11 +3217,20 @@ static int stream_out(ctk_handle *h, int persistence, const int32_t *chunk_vals)
 }
 
 static int track_stream_impl(ctk_handle *h, StreamIO &io, bool f64, int64_t T, int ny, int nx, const double *thr, int cmp_op, const float *wrow,
-                             double overlap, int persistence, int twosided, int64_t *n_tracked, int64_t chunk_steps)
+                             double overlap, int persistence, int twosided, int64_t *n_tracked, int64_t chunk_steps,
+                             const int64_t *starts = nullptr, int64_t nseg = 0, bool seg_entry = false /* an entry with segment arguments */)
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
     if (T < 0 || ny < 1 || nx < 1 || chunk_steps < 0) return ctk_set_error(CTK_E_INVALID, "ctk_track_stream: bad shape");
-    if (!h->seg_starts.empty()) return ctk_set_error(CTK_E_INVALID, "ctk_track_stream: segments are set on this handle (ctk_set_segments); the streaming entries do not take them");
+    if (!seg_entry && !h->seg_starts.empty())
+        return ctk_set_error(CTK_E_INVALID, "ctk_track_stream: segments are set on this handle (ctk_set_segments); the streaming entries take them as an argument (ctk_track_stream_seg_*)");
+    // segment starts of THIS call: kept in the handle while it runs, so that every pass through track_dev_impl -- the dense re-run
+    // below, the route through the time-shard path, the host resolver -- builds and sees the same edge table
+    struct SegCall { ctk_handle *h; ~SegCall() { h->seg_call.clear(); } } seg_call{h};
+    if (seg_entry) {
+        CTKCHK(segment_args_check(h, "ctk_track_stream_seg", starts, nseg, std::max<int64_t>(T, 1)));
+        if (nseg > 1) h->seg_call.assign(starts, starts + nseg);         // (one segment: the unsegmented call)
+    }
     if (T > 0 && ((!io.host_in && !io.read) || (!io.host_out && !io.write))) return ctk_set_error(CTK_E_INVALID, "ctk_track_stream: no source or no sink");
     HIPCHK(hipSetDevice(h->device));
     io.esz = f64 ? 8 : 4;
@@ -3225,6 +3288,32 @@ extern "C" int ctk_track_stream_cb(ctk_handle *h, int elem_bytes, int64_t T, int
     StreamIO io;
     io.read = reader; io.read_user = reader_user; io.write = writer; io.write_user = writer_user;
     return track_stream_impl(h, io, elem_bytes == 8, T, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, n_tracked, chunk_steps);
+}
+// ... with segment breaks as an argument of the call (include/contrack_hip.h)
+extern "C" int ctk_track_stream_seg_f32(ctk_handle *h, const float *anom, int64_t T, int ny, int nx, const double *thr, int cmp_op, const float *wrow,
+                                        double overlap, int persistence, int twosided, int32_t *flag, int64_t *n_tracked, int64_t chunk_steps,
+                                        const int64_t *starts, int64_t nseg)
+{
+    StreamIO io;
+    io.host_in = anom; io.host_out = flag;
+    return track_stream_impl(h, io, false, T, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, n_tracked, chunk_steps, starts, nseg, true);
+}
+extern "C" int ctk_track_stream_seg_f64(ctk_handle *h, const double *anom, int64_t T, int ny, int nx, const double *thr, int cmp_op, const float *wrow,
+                                        double overlap, int persistence, int twosided, int32_t *flag, int64_t *n_tracked, int64_t chunk_steps,
+                                        const int64_t *starts, int64_t nseg)
+{
+    StreamIO io;
+    io.host_in = anom; io.host_out = flag;
+    return track_stream_impl(h, io, true, T, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, n_tracked, chunk_steps, starts, nseg, true);
+}
+extern "C" int ctk_track_stream_seg_cb(ctk_handle *h, int elem_bytes, int64_t T, int ny, int nx, ctk_read_chunk_fn reader, void *reader_user, const double *thr,
+                                       int cmp_op, const float *wrow, double overlap, int persistence, int twosided, ctk_write_chunk_fn writer,
+                                       void *writer_user, int64_t *n_tracked, int64_t chunk_steps, const int64_t *starts, int64_t nseg)
+{
+    if (elem_bytes != 4 && elem_bytes != 8) return ctk_set_error(CTK_E_INVALID, "ctk_track_stream_seg_cb: elem_bytes must be 4 (float32) or 8 (float64)");
+    StreamIO io;
+    io.read = reader; io.read_user = reader_user; io.write = writer; io.write_user = writer_user;
+    return track_stream_impl(h, io, elem_bytes == 8, T, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, n_tracked, chunk_steps, starts, nseg, true);
 }
 extern "C" int ctk_stream_times(ctk_handle *h, double *ms4)
 {

@@ -546,9 +546,9 @@ extern "C" int ctk_weights_to_limbs(const float *wrow, int ny, int64_t npix, int
 // test hook (GPU-free): the label numbering across time-shard boundaries (boundary_resolve, ctk_seam.h) on flat arrays.
 // last_flat / halo_flat: the per-rank records one after the other (nlast[q] / nh[q] entries each).
 // ---------------------------------------------------------------------------------------------
-extern "C" int ctk_debug_boundary_resolve(int world, const int32_t *nlast, const int32_t *nh, const int32_t *nroots, const int32_t *last_flat,
-                                          const int32_t *halo_flat, int64_t *off, int32_t *last_label_flat, int32_t *halo_label_flat,
-                                          int32_t *n_absorbed)
+static int debug_boundary_resolve(int world, const int32_t *nlast, const int32_t *nh, const int32_t *nroots, const int32_t *last_flat,
+                                  const int32_t *halo_flat, int64_t *off, int32_t *last_label_flat, int32_t *halo_label_flat,
+                                  int32_t *n_absorbed, bool breaks, int32_t *n_crossing)
 {
     if (world < 1 || !nlast || !nh || !nroots || !off) return ctk_set_error(CTK_E_INVALID, "ctk_debug_boundary_resolve: bad arguments");
     std::vector<BoundaryIn> in((size_t)world);
@@ -559,7 +559,8 @@ extern "C" int ctk_debug_boundary_resolve(int world, const int32_t *nlast, const
         lo += (size_t)nlast[q]; ho += (size_t)nh[q];
     }
     BoundaryOut out;
-    if (!boundary_resolve(in, out)) return ctk_set_error(CTK_E_INVALID, "ctk_debug_boundary_resolve: contradictory records");
+    if (!boundary_resolve(in, out, breaks)) return ctk_set_error(CTK_E_INVALID, "ctk_debug_boundary_resolve: contradictory records");
+    if (n_crossing) *n_crossing = (int32_t)out.crossing.size();
     memcpy(off, out.off.data(), sizeof(int64_t) * ((size_t)world + 1));
     lo = ho = 0;
     for (int q = 0; q < world; q++) {
@@ -569,4 +570,17 @@ extern "C" int ctk_debug_boundary_resolve(int world, const int32_t *nlast, const
         lo += (size_t)nlast[q]; ho += (size_t)nh[q];
     }
     return CTK_OK;
+}
+extern "C" int ctk_debug_boundary_resolve(int world, const int32_t *nlast, const int32_t *nh, const int32_t *nroots, const int32_t *last_flat,
+                                          const int32_t *halo_flat, int64_t *off, int32_t *last_label_flat, int32_t *halo_label_flat,
+                                          int32_t *n_absorbed)
+{
+    return debug_boundary_resolve(world, nlast, nh, nroots, last_flat, halo_flat, off, last_label_flat, halo_label_flat, n_absorbed, false, nullptr);
+}
+// ... of a call with segment breaks (ctk_track_sharded_seg_*): a rank behind a cut that is a break reports no halo components
+extern "C" int ctk_debug_boundary_resolve_breaks(int world, const int32_t *nlast, const int32_t *nh, const int32_t *nroots, const int32_t *last_flat,
+                                                 const int32_t *halo_flat, int64_t *off, int32_t *last_label_flat, int32_t *halo_label_flat,
+                                                 int32_t *n_absorbed, int32_t *n_crossing)
+{
+    return debug_boundary_resolve(world, nlast, nh, nroots, last_flat, halo_flat, off, last_label_flat, halo_label_flat, n_absorbed, true, n_crossing);
 }

@@ -121,7 +121,10 @@ struct BoundaryOut {
 };
 
 // returns false if the records contradict each other (a kept halo component whose twin was filtered out, ...)
-inline bool boundary_resolve(const std::vector<BoundaryIn> &in, BoundaryOut &out)
+// breaks: the call has segment breaks (the same on every rank).  A rank whose first step starts a segment reports NO halo components
+// (nh = 0) whatever its predecessor's last step holds: nothing is united across that cut and the predecessor's last-step sets do
+// not count as crossing it, so every set keeps the number its own shard's raster order gives it.
+inline bool boundary_resolve(const std::vector<BoundaryIn> &in, BoundaryOut &out, bool breaks = false)
 {
     const int W = (int)in.size();
     // nodes: per rank [last comps | halo comps]
@@ -138,7 +141,7 @@ inline bool boundary_resolve(const std::vector<BoundaryIn> &in, BoundaryOut &out
     for (int q = 0; q < W; q++) {
         const BoundaryIn &b = in[(size_t)q];
         if (q == 0 && b.nh != 0) return false;
-        if (q > 0 && b.nh != in[(size_t)q - 1].nlast) return false;
+        if (q > 0 && b.nh != in[(size_t)q - 1].nlast && !(breaks && b.nh == 0)) return false;
         for (int h = 0; h < b.nh; h++) {
             const int32_t r = b.halo[h];
             if (r < 0) continue;
@@ -220,7 +223,7 @@ inline bool boundary_resolve(const std::vector<BoundaryIn> &in, BoundaryOut &out
             const int64_t l = label_of_set(find(nodeL(q, c)));
             if (l <= 0 || l > INT32_MAX) return false;
             out.last_label[(size_t)q][(size_t)c] = (int32_t)l;
-            if (q + 1 < W) out.crossing.push_back((int32_t)l);         // (nothing follows the last rank's last timestep)
+            if (q + 1 < W && in[(size_t)q + 1].nh > 0) out.crossing.push_back((int32_t)l);         // (nothing follows the last rank's last timestep, or the last step of a segment)
         }
         const std::vector<int32_t> &A = out.absorbed[(size_t)q];
         out.absorbed_label[(size_t)q].assign(A.size(), 0);

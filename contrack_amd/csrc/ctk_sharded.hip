@@ -881,7 +881,16 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
 #define INJECT(k) do { if (h->debug_fail_stage == (k)) { h->debug_fail_stage = 0; return ctk_set_error(CTK_E_INTERNAL, "injected failure at stage %d (test hook)", (k)); } } while (0)
     const double t_call = now_ms();
     hipStream_t s = h->stream;
-    const bool has_prev = rank > 0, has_next = rank + 1 < world;
+    // Segment breaks (ctk_track_sharded_seg_*; h->seg_cur / seg_cur_host are this shard's slice of the edge table, set by the
+    // entry).  A cut that is a break -- my first step starts a segment / my last step ends one -- is, for everything this rank
+    // builds, no cut at all: no halo (no co-occurrence records, no backward overlap, no 3-D union: the step is "t = 0 without a
+    // previous shard"), no forward overlap of the last step, its first / last step outside the filter range like the first and
+    // last step of the whole slab, no label marked as reaching the next shard.  The EXCHANGES stay what they are on every rank
+    // (halo shift, keep-bit rounds, boundary all-gather; same order, same payload sizes): what arrives over a break is not looked
+    // at.  cut_* = a neighbour exists; has_* = ... and the series continues across the cut.
+    const bool cut_prev = rank > 0, cut_next = rank + 1 < world;
+    const uint8_t *seg_host = h->seg_cur ? h->seg_cur_host : nullptr;
+    const bool has_prev = cut_prev && !(seg_host && (seg_host[0] & 1u)), has_next = cut_next && !(seg_host && (seg_host[T - 1] & 2u));
     if (!h->shard) h->shard = new (std::nothrow) ShardScratch();
     if (!h->shard) return ctk_set_error(CTK_E_NOMEM, "out of memory");
     ShardScratch &S = *h->shard;
@@ -907,13 +916,17 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     }
     // (the zeroed header is remembered by address AND capacity: a regrown buffer may come back at the same address; every other
     // writer of halo_in -- ctk_shard_halo_import, a call with has_prev -- clears the flag)
-    if (!has_prev && !(h->halo_in_zero && h->halo_in_zero_p == h->halo_in.p && h->halo_in_zero_cap == h->halo_in.cap)) {       // no halo: zero components (kept from call to call)
+    if (!cut_prev && !(h->halo_in_zero && h->halo_in_zero_p == h->halo_in.p && h->halo_in_zero_cap == h->halo_in.cap)) {       // no halo: zero components (kept from call to call)
         HIPCHK(hipMemsetAsync(h->halo_in.p, 0, sizeof(HaloHeader), s));
         h->halo_in_zero = true; h->halo_in_zero_p = h->halo_in.p; h->halo_in_zero_cap = h->halo_in.cap;
     }
-    if (has_prev) h->halo_in_zero = false;
+    if (cut_prev) h->halo_in_zero = false;
+    if (cut_next && !has_next) HIPCHK(hipMemsetAsync(h->halo_out.p, 0, sizeof(HaloHeader), s));      // a break: the halo that travels is empty
     CTKCHK(ctk_comm_shift(c, +1, h->halo_out.p, hb, h->halo_in.p, hb));
     CTKCHK(ctk_comm_shift(c, -1, h->mask.p, nw * 8, h->sh_mask_next.p, nw * 8));
+    // my first step starts a segment: whatever the previous rank sent, this shard has no halo components (the shifts are ordered on
+    // the stream or complete when they return); boundary_resolve then finds nh = 0 and connects nothing across the cut
+    if (cut_prev && !has_prev) HIPCHK(hipMemsetAsync(h->halo_in.p, 0, sizeof(HaloHeader), s));
     const uint32_t *nh_ptr = &((const HaloHeader *)h->halo_in.p)->ncomp;
     h->halo_valid = has_prev;
     SHDBG("X1");
@@ -992,7 +1005,8 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     r.nh_ptr = nh_ptr;
     CTKCHK(ensure(h, h->rv_lab_root, R * 4));
     r.lab_root = P<int32_t>(h->rv_lab_root);            // (k_rs_roots keeps a copy of the root indices: a second attempt of X5 starts from them)
-    r.t_lo = has_prev ? 0 : 1;                       // global timesteps 1 .. T_total-2 are filtered
+    r.t_lo = has_prev ? 0 : 1;                       // global timesteps 1 .. T_total-2 are filtered (segments: has_* say whether my first /
+                                                     // last step is one of a segment; those inside the shard are skipped by the SEG builds)
     r.t_hi = has_next ? (int)T - 1 : (int)T - 2;
     const uint32_t AMB_CAP = 1u << 16;
     CTKCHK(ensure(h, h->sh_ovr_slot, R * 4));
@@ -1148,6 +1162,9 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
             const size_t cw = (size_t)nflag * 3 * (size_t)ny;
             CTKCHK(ensure(h, h->sh_counts, cw * 4));
             HIPCHK(hipMemsetAsync(h->sh_counts.p, 0, cw * 4, s));
+            // (segment breaks: a component listed here belongs to a FILTERED step, which is never the first or last of its segment,
+            // so the planes t - 1 and t + 1 the kernel reads lie in the same segment -- also at a cut that is a break, where has_prev /
+            // has_next are false and step 0 / T - 1 is not filtered: the kernel is the unsegmented one)
             const char *hl = (const char *)h->halo_in.p + sizeof(HaloHeader);
             PlaneRef halo = {(const uint64_t *)hl, (const uint16_t *)(hl + halo_off_wstart(h)), (const uint32_t *)(hl + halo_off_rowstart(h)),
                              (const uint32_t *)(hl + halo_off_runcomp(h))};
@@ -1220,7 +1237,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
         if (b.nlast < 0 || b.nh < 0 || (uint32_t)b.nlast > capB || (uint32_t)b.nh > capB) COLLECTIVE_FAIL(CTK_E_INTERNAL, "boundary record of rank %d is malformed", q);
     }
     INJECT(4);
-    if (!boundary_resolve(S.bin, S.bout)) COLLECTIVE_FAIL(CTK_E_INTERNAL, "ctk_track_sharded: the shards' boundary records contradict each other");
+    if (!boundary_resolve(S.bin, S.bout, h->seg_shard_breaks)) COLLECTIVE_FAIL(CTK_E_INTERNAL, "ctk_track_sharded: the shards' boundary records contradict each other");
     const int64_t NL = S.bout.off[(size_t)world];
     if (NL > 0x7ffffff0ll) COLLECTIVE_FAIL(CTK_E_RANGE, "ctk_track_sharded: more than 2^31 - 16 ids");
     h->n_labels = NL; h->t_begin = t_begin;
@@ -1252,7 +1269,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
         if (ctk_env().sh_force_split) return true;        // (experiments: the split / exchange even without shared groups; every rank or none)
         for (int q = 0; q < world; q++) {
             for (int32_t l : S.bout.halo_label[(size_t)q]) if (l > 0) return true;
-            if (q + 1 < world) for (int32_t l : S.bout.last_label[(size_t)q]) if (l > 0) return true;
+            if (q + 1 < world && S.bin[(size_t)q + 1].nh > 0) for (int32_t l : S.bout.last_label[(size_t)q]) if (l > 0) return true;      // (nh = 0: a segment break, or no component)
         }
         return false;
     }();
@@ -1334,7 +1351,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     bool any_boundary_label = ctk_env().sh_force_split;      // (experiments: the split / exchange even without shared groups; every rank or none)
     for (int q = 0; q < world && !any_boundary_label; q++) {
         for (int32_t l : S.bout.halo_label[(size_t)q]) if (l > 0) { any_boundary_label = true; break; }
-        if (q + 1 < world) for (int32_t l : S.bout.last_label[(size_t)q]) if (l > 0) { any_boundary_label = true; break; }
+        if (q + 1 < world && S.bin[(size_t)q + 1].nh > 0) for (int32_t l : S.bout.last_label[(size_t)q]) if (l > 0) { any_boundary_label = true; break; }
     }
     size_t nGd = 0;
     int64_t nGc = 0;
@@ -1571,16 +1588,28 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
 // the communicator -- they return CTK_E_COMM from their next wait instead of sitting in a collective for ever
 static int track_sharded_entry(ctk_handle *h, ctk_comm *c, const void *anom_dev, bool f64, int64_t T_local, int64_t t_begin, int64_t T_total, int ny, int nx,
                                const double *thr, int cmp_op, const float *wrow, double overlap, int persistence, int twosided, int32_t *flag_dev,
-                               int64_t *n_tracked)
+                               int64_t *n_tracked, const int64_t *starts = nullptr, int64_t nseg = 0, bool seg_entry = false /* an entry with segment arguments */)
 {
     if (h) h->sh_collective_err = false;
+    // Segment breaks given with the call (global step indices, the same on every rank): this shard's slice of the edge table over
+    // T_total becomes the table of the launches (h->seg_cur) and of the host (h->seg_cur_host) for the time of the call.
+    struct SegOff { ctk_handle *h; ~SegOff() { if (h) { h->seg_cur = nullptr; h->seg_cur_host = nullptr; h->seg_shard_breaks = false; } } } seg_off{h};
+    auto seg_setup = [&]() -> int {
+        CTKCHK(segment_args_check(h, "ctk_track_sharded_seg", starts, nseg, T_total));
+        if (nseg < 2 || T_local < 1 || t_begin < 0 || t_begin + T_local > T_total) return CTK_OK;      // (one segment: the unsegmented call; a bad shard: refused below)
+        HIPCHK(hipSetDevice(h->device));
+        h->seg_shard_breaks = true;
+        return segment_table_call(h, std::vector<int64_t>(starts, starts + nseg), T_total, t_begin, T_local);
+    };
     // (a threshold field, ctk_set_threshold_field, is not taken here: thr == NULL is refused like any other null argument; nor are
-    // segment breaks, ctk_set_segments)
-    const int rc = (h && !h->seg_starts.empty())
-        ? ctk_set_error(CTK_E_INVALID, "ctk_track_sharded: segments are set on this handle (ctk_set_segments); the time-shard entries do not take them")
+    // the handle's sticky segment breaks, ctk_set_segments)
+    int rc = (h && !seg_entry && !h->seg_starts.empty())
+        ? ctk_set_error(CTK_E_INVALID, "ctk_track_sharded: segments are set on this handle (ctk_set_segments); the time-shard entries take them as an argument (ctk_track_sharded_seg_*)")
         : (h && T_local > 0 && !thr)
         ? ctk_set_error(CTK_E_INVALID, "ctk_track_sharded: thr is NULL (the time-shard entries take per-step thresholds, not a threshold field)")
-        : track_sharded_impl(h, c, anom_dev, f64, T_local, t_begin, T_total, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, flag_dev, n_tracked);
+        : CTK_OK;
+    if (rc == CTK_OK && h && seg_entry) rc = seg_setup();
+    if (rc == CTK_OK) rc = track_sharded_impl(h, c, anom_dev, f64, T_local, t_begin, T_total, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, flag_dev, n_tracked);
     if (rc != CTK_OK && c && h && !h->sh_collective_err) {
         std::string msg = ctk_last_error();                          // (the abort drains the stream: keep the message of the cause)
         ctk_comm_abort(c, rc);
@@ -1607,4 +1636,20 @@ extern "C" int ctk_track_sharded_f64_dev(ctk_handle *h, ctk_comm *c, const doubl
                                          int32_t *flag_dev, int64_t *n_tracked)
 {
     return track_sharded_entry(h, c, anom_dev, true, T_local, t_begin, T_total, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, flag_dev, n_tracked);
+}
+
+// ... with segment breaks: starts_global are indices into [0, T_total), identical on every rank (include/contrack_hip.h)
+extern "C" int ctk_track_sharded_seg_f32_dev(ctk_handle *h, ctk_comm *c, const float *anom_dev, int64_t T_local, int64_t t_begin, int64_t T_total, int ny, int nx,
+                                             const double *thr, int cmp_op, const float *wrow, double overlap, int persistence, int twosided,
+                                             int32_t *flag_dev, int64_t *n_tracked, const int64_t *starts_global, int64_t nseg)
+{
+    return track_sharded_entry(h, c, anom_dev, false, T_local, t_begin, T_total, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, flag_dev, n_tracked,
+                               starts_global, nseg, true);
+}
+extern "C" int ctk_track_sharded_seg_f64_dev(ctk_handle *h, ctk_comm *c, const double *anom_dev, int64_t T_local, int64_t t_begin, int64_t T_total, int ny, int nx,
+                                             const double *thr, int cmp_op, const float *wrow, double overlap, int persistence, int twosided,
+                                             int32_t *flag_dev, int64_t *n_tracked, const int64_t *starts_global, int64_t nseg)
+{
+    return track_sharded_entry(h, c, anom_dev, true, T_local, t_begin, T_total, ny, nx, thr, cmp_op, wrow, overlap, persistence, twosided, flag_dev, n_tracked,
+                               starts_global, nseg, true);
 }

@@ -193,8 +193,10 @@ class ShardedTracker:
             self.comm = None
         self.trk.close()
 
-    def track(self, anom_local, t_begin, T_total, thr_local, cmp_op, wrow, overlap, persistence, twosided=True):
-        """Collective.  A rank that fails BEFORE it reaches the C entry (bad arguments, no device memory, a failed upload) aborts the
+    def track(self, anom_local, t_begin, T_total, thr_local, cmp_op, wrow, overlap, persistence, twosided=True, segments=None):
+        """Collective.  segments (None: one series): the first step of every independent time segment as GLOBAL indices into
+        [0, T_total), 0 first, strictly increasing -- the same on every rank; breaks may fall on shard cuts or anywhere else.
+        A rank that fails BEFORE it reaches the C entry (bad arguments, no device memory, a failed upload) aborts the
         communicator, so that the other ranks raise CommError instead of waiting for it until the deadline; inside the entry the
         library does that itself -- except for errors every rank derives from the same gathered data, which leave the communicator
         usable (csrc/ctk_sharded.hip, COLLECTIVE_FAIL)."""
@@ -222,7 +224,7 @@ class ShardedTracker:
                     pass
                 raise
             n = self.trk.track_sharded_dev(self.comm, d_in, T, t_begin, T_total, ny, nx, thr_local, cmp_op, wrow, overlap, persistence,
-                                           twosided, d_out, f64=f64)
+                                           twosided, d_out, f64=f64, segments=segments)
             flag = np.empty((T, ny, nx), dtype=np.int32)
             self.trk.d2h(flag, d_out)
         finally:

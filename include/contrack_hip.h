@@ -90,7 +90,9 @@ int ctk_set_threshold_field(ctk_handle *h, const void *field, int elem_bytes, in
  * scipy's raster numbering (the offset of segment k is the number of 3-D components of segments 0 .. k-1); persistence counts
  * inside a segment; n_tracked is len(np.unique(flag)) - 1 of the whole result.  starts == {0} gives today's result.
  * Taken by the host, _dev and resident entries (with or without a threshold field).  A call whose T <= starts[nseg-1] returns
- * CTK_E_INVALID; the streaming, staged and time-shard entries return CTK_E_INVALID while segments are set. */
+ * CTK_E_INVALID; the streaming, staged and time-shard entries return CTK_E_INVALID while segments are set.  The streaming and
+ * time-shard paths take the starts as an ARGUMENT of the call instead (ctk_track_stream_seg_*, ctk_track_sharded_seg_*_dev below:
+ * same rules, same semantics); those refuse a handle that also has sticky segments set. */
 int ctk_set_segments(ctk_handle *h, const int64_t *starts, int64_t nseg);
 
 /* The host-array entries keep device copies of the slab and of the result in the handle between calls (grow-only, so that
@@ -207,6 +209,21 @@ int  ctk_track_sharded_f32_dev(ctk_handle *h, ctk_comm *c, const float *anom_dev
 int  ctk_track_sharded_f64_dev(ctk_handle *h, ctk_comm *c, const double *anom_dev, int64_t T_local, int64_t t_begin, int64_t T_total,
                                int ny, int nx, const double *thr, int cmp_op, const float *wrow, double overlap,
                                int persistence, int twosided, int32_t *flag_dev, int64_t *n_tracked);
+/* ... with segment breaks (semantics: ctk_set_segments).  starts_global[nseg] are step indices into [0, T_total): starts_global[0] = 0,
+ * strictly increasing, the last one below T_total (CTK_E_INVALID otherwise, and for a handle with sticky segments set).  EVERY rank
+ * passes the SAME starts -- they are an argument of the collective; ranks that pass different ones get an undefined result or
+ * CTK_E_INTERNAL, as ranks that disagree about T_total do.  Breaks may fall anywhere: inside a shard, on a shard cut (then the two
+ * ranks exchange what they always exchange and ignore it), one per step.  flag / n_tracked are what the one-call entries return
+ * with ctk_set_segments on the whole slab.  nseg == 0 or starts_global == {0} is ctk_track_sharded_*_dev, bit for bit, with the
+ * same kernels. */
+int  ctk_track_sharded_seg_f32_dev(ctk_handle *h, ctk_comm *c, const float *anom_dev, int64_t T_local, int64_t t_begin, int64_t T_total,
+                                   int ny, int nx, const double *thr /* T_local */, int cmp_op, const float *wrow, double overlap,
+                                   int persistence, int twosided, int32_t *flag_dev, int64_t *n_tracked, const int64_t *starts_global,
+                                   int64_t nseg);
+int  ctk_track_sharded_seg_f64_dev(ctk_handle *h, ctk_comm *c, const double *anom_dev, int64_t T_local, int64_t t_begin, int64_t T_total,
+                                   int ny, int nx, const double *thr, int cmp_op, const float *wrow, double overlap,
+                                   int persistence, int twosided, int32_t *flag_dev, int64_t *n_tracked, const int64_t *starts_global,
+                                   int64_t nseg);
 
 /* ---- next row N4: streaming entries (xr.open_dataset contrack.py:176 -> run_contrack -> to_netcdf README.rst:154) ------------
  * ctk_track_f32 / _f64 for slabs that should not (or cannot) sit in HBM twice: the slab passes through two chunk-sized device
@@ -231,6 +248,20 @@ int ctk_track_stream_f64(ctk_handle *h, const double *anom, int64_t T, int ny, i
 int ctk_track_stream_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, int64_t T, int ny, int nx, ctk_read_chunk_fn reader,
                         void *reader_user, const double *thr, int cmp_op, const float *wrow, double overlap, int persistence, int twosided,
                         ctk_write_chunk_fn writer, void *writer_user, int64_t *n_tracked, int64_t chunk_steps);
+/* ... with segment breaks (semantics: ctk_set_segments): starts[0] = 0, strictly increasing, the last one below T (CTK_E_INVALID
+ * otherwise, and for a handle with sticky segments set).  Chunks and segments are unrelated: a break may fall inside a chunk, on a
+ * chunk boundary, and a chunk may be shorter than a segment.  thr == NULL (the handle's threshold field) is taken as in
+ * ctk_track_stream_*.  nseg == 0 or starts == {0} is ctk_track_stream_*, bit for bit, with the same kernels. */
+int ctk_track_stream_seg_f32(ctk_handle *h, const float *anom, int64_t T, int ny, int nx, const double *thr, int cmp_op, const float *wrow,
+                             double overlap, int persistence, int twosided, int32_t *flag, int64_t *n_tracked, int64_t chunk_steps,
+                             const int64_t *starts, int64_t nseg);
+int ctk_track_stream_seg_f64(ctk_handle *h, const double *anom, int64_t T, int ny, int nx, const double *thr, int cmp_op, const float *wrow,
+                             double overlap, int persistence, int twosided, int32_t *flag, int64_t *n_tracked, int64_t chunk_steps,
+                             const int64_t *starts, int64_t nseg);
+int ctk_track_stream_seg_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, int64_t T, int ny, int nx, ctk_read_chunk_fn reader,
+                            void *reader_user, const double *thr, int cmp_op, const float *wrow, double overlap, int persistence,
+                            int twosided, ctk_write_chunk_fn writer, void *writer_user, int64_t *n_tracked, int64_t chunk_steps,
+                            const int64_t *starts, int64_t nseg);
 /* times of the last streaming call: {reader callbacks, writer callbacks, input phase, output phase} in ms */
 int ctk_stream_times(ctk_handle *h, double *ms4);
 

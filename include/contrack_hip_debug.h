@@ -39,6 +39,11 @@ double ctk_debug_np_sum(const double *a, size_t n);
 int ctk_debug_boundary_resolve(int world, const int32_t *nlast, const int32_t *nh, const int32_t *nroots, const int32_t *last_flat,
                                const int32_t *halo_flat, int64_t *off /* [world+1] */, int32_t *last_label_flat, int32_t *halo_label_flat,
                                int32_t *n_absorbed /* [world] */);
+/* ... of a call with segment breaks (ctk_track_sharded_seg_*): nh[q] = 0 against a non-empty last step of rank q-1 is a cut that is
+ * a break, nothing crosses it; n_crossing: the number of ids whose time extent the ranks would exchange */
+int ctk_debug_boundary_resolve_breaks(int world, const int32_t *nlast, const int32_t *nh, const int32_t *nroots, const int32_t *last_flat,
+                                      const int32_t *halo_flat, int64_t *off /* [world+1] */, int32_t *last_label_flat,
+                                      int32_t *halo_label_flat, int32_t *n_absorbed /* [world] */, int32_t *n_crossing);
 
 /* test hook: labels / operations of one seam cluster the device seam driver accepts (0 = its limits, 64 each): clusters beyond
  * send the pass to the synchronous path with the host driver, and the grid stays there */
