@@ -267,6 +267,14 @@ def _groups(group, T, ngroups=None):
     return g, (int(g.max()) + 1 if g.size else 1) if ngroups is None else int(ngroups)
 
 
+def _group_ids(group, T):
+    """group ids as a C-contiguous int32 (T,) array (the library checks their values)"""
+    group = np.ascontiguousarray(group, dtype=np.int32)
+    if group.shape != (T,):
+        raise ValueError("group must hold one id per timestep")
+    return group
+
+
 def _above(above):
     a = int(above)
     if a < np.iinfo(np.int32).min or a > np.iinfo(np.int32).max:
@@ -810,9 +818,7 @@ class Tracker:
         if f64:
             x = np.ascontiguousarray(x, dtype=np.float64)
         T, ny, nx = x.shape
-        group = np.ascontiguousarray(group, dtype=np.int32)
-        if group.shape != (T,):
-            raise ValueError("group must hold one id per timestep")
+        group = _group_ids(group, T)
         cin = None if clim is None else np.ascontiguousarray(clim, dtype=x.dtype)
         if cin is not None and cin.shape != (ngroups, ny, nx):
             raise ValueError("clim must have shape (ngroups, ny, nx)")
@@ -848,22 +854,26 @@ class Tracker:
                                        int(bool(twosided)), flag.ctypes.data, C.byref(n)))
         return flag, int(n.value)
 
-    def percentile(self, x, y0, y1, q):
-        """mean over rows [y0, y1) of the per-grid-point q-quantile over time; x = None: the resident anomaly slab"""
-        out = C.c_double(0.0)
+    def _slab_or_resident(self, x):
+        """(pointer, T, ny, nx, is float64, the array the pointer points into) of a host slab -- made C-contiguous, float32 kept,
+        anything else as float64 --, or of the resident anomaly slab (x None: pointer NULL)"""
         if x is None:
             shape = self.resident_anom()
             if shape is None:
                 raise ContrackHipError("no anomaly slab is resident on the device")
-            T, ny, nx, f64 = shape
-            ptr = None
-        else:
-            x = np.ascontiguousarray(x)
-            f64 = x.dtype != np.float32
-            if f64:
-                x = np.ascontiguousarray(x, dtype=np.float64)
-            T, ny, nx = x.shape
-            ptr = x.ctypes.data
+            return (None,) + shape + (None,)
+        x = np.ascontiguousarray(x)
+        if x.ndim != 3:
+            raise ValueError("x must be (time, lat, lon)")
+        f64 = x.dtype != np.float32
+        if f64:
+            x = np.ascontiguousarray(x, dtype=np.float64)
+        return (x.ctypes.data,) + x.shape + (f64, x)
+
+    def percentile(self, x, y0, y1, q):
+        """mean over rows [y0, y1) of the per-grid-point q-quantile over time; x = None: the resident anomaly slab"""
+        out = C.c_double(0.0)
+        ptr, T, ny, nx, f64, _keep = self._slab_or_resident(x)
         fn = lib().ctk_percentile_f64 if f64 else lib().ctk_percentile_f32
         check(fn(self._h, ptr, T, ny, nx, int(y0), int(y1), float(q), C.byref(out)))
         return float(out.value)
@@ -872,24 +882,8 @@ class Tracker:
         """per group g the exact q-quantile (np.nanquantile, 'linear', float64) of rows [y0, y1) pooled over every timestep whose
         group lies in the centred, circular window of `window` groups around g (ctk_percentile_groups_*); x (T, ny, nx) float32 /
         float64, or None: the resident anomaly slab.  group: T ids in [0, ngroups).  Returns float64 (ngroups,)."""
-        if x is None:
-            shape = self.resident_anom()
-            if shape is None:
-                raise ContrackHipError("no anomaly slab is resident on the device")
-            T, ny, nx, f64 = shape
-            ptr = None
-        else:
-            x = np.ascontiguousarray(x)
-            if x.ndim != 3:
-                raise ValueError("x must be (time, lat, lon)")
-            f64 = x.dtype != np.float32
-            if f64:
-                x = np.ascontiguousarray(x, dtype=np.float64)
-            T, ny, nx = x.shape
-            ptr = x.ctypes.data
-        group = np.ascontiguousarray(group, dtype=np.int32)
-        if group.shape != (T,):
-            raise ValueError("group must hold one id per timestep")
+        ptr, T, ny, nx, f64, _keep = self._slab_or_resident(x)
+        group = _group_ids(group, T)
         out = np.empty(int(ngroups), dtype=np.float64)
         fn = lib().ctk_percentile_groups_f64 if f64 else lib().ctk_percentile_groups_f32
         check(fn(self._h, ptr, T, ny, nx, int(y0), int(y1), group.ctypes.data, int(ngroups), int(window), float(q), out.ctypes.data))
@@ -916,24 +910,8 @@ class Tracker:
         whose group lies in the centred, circular window of `window` groups around g (ctk_percentile_field_*); x (T, ny, nx)
         float32 / float64, or None: the resident anomaly slab.  group: T ids in [0, ngroups).  Returns float64
         (ngroups, y1 - y0, nx)."""
-        if x is None:
-            shape = self.resident_anom()
-            if shape is None:
-                raise ContrackHipError("no anomaly slab is resident on the device")
-            T, ny, nx, f64 = shape
-            ptr = None
-        else:
-            x = np.ascontiguousarray(x)
-            if x.ndim != 3:
-                raise ValueError("x must be (time, lat, lon)")
-            f64 = x.dtype != np.float32
-            if f64:
-                x = np.ascontiguousarray(x, dtype=np.float64)
-            T, ny, nx = x.shape
-            ptr = x.ctypes.data
-        group = np.ascontiguousarray(group, dtype=np.int32)
-        if group.shape != (T,):
-            raise ValueError("group must hold one id per timestep")
+        ptr, T, ny, nx, f64, _keep = self._slab_or_resident(x)
+        group = _group_ids(group, T)
         out = np.empty((max(int(ngroups), 0), max(int(y1) - int(y0), 0), nx), dtype=np.float64)
         fn = lib().ctk_percentile_field_f64 if f64 else lib().ctk_percentile_field_f32
         check(fn(self._h, ptr, T, ny, nx, int(y0), int(y1), group.ctypes.data, int(ngroups), int(window), float(q), out.ctypes.data))

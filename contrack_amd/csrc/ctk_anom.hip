@@ -9,16 +9,6 @@
 // dtype where xarray keeps it.
 #pragma once
 
-// gfx950 only.  k_quantile alone keeps 66 KB of static LDS per workgroup (64 pixels x 257 histogram bins): more than the 64 KB a
-// workgroup gets on gfx90a / gfx942.  The Makefile's ARCH is overridable for gfx950 variants (xnack / sramecc suffixes), not for
-// other parts.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "libcontrack_hip.so is written for gfx950 (MI355X): build with ARCH=gfx950"
-#endif
-
-template <typename VT>
-__device__ __forceinline__ bool an_isnan(VT v) { return v != v; }
-
 // clim_raw[g][p] = mean over the timesteps of group g, NaNs skipped (contrack.py:483)
 template <typename VT>
 __global__ __launch_bounds__(256) void k_clim_raw(const VT *__restrict__ x, const int32_t *__restrict__ tlist, const int32_t *__restrict__ goff, int64_t npix,
@@ -82,92 +72,18 @@ __global__ __launch_bounds__(256) void k_anom(const VT *__restrict__ x, const VT
     }
 }
 
-// ---- N3: q-quantile over time per grid point of rows [y0, y1), exact (radix selection on order-preserving integer keys) -----
-__device__ __forceinline__ uint32_t an_key(float v) { const uint32_t u = __float_as_uint(v); return (u >> 31) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ uint64_t an_key(double v) { const uint64_t u = (uint64_t)__double_as_longlong(v); return (u >> 63) ? ~u : (u | 0x8000000000000000ull); }
-__device__ __forceinline__ float an_unkey(uint32_t k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
-__device__ __forceinline__ double an_unkey(uint64_t k) { return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k)); }
-
-// np.quantile(method='linear') of n >= 1 values from its order statistics: a = the value of rank lo = floor((n - 1) q), le = how
-// many values are <= a, nx = the smallest value above a (read only where rank lo + 1 exists and is not a again).  Shared by
-// k_quantile and k_pctl_finish (ctk_pctl.hip).
-__device__ __forceinline__ double an_np_quantile(uint64_t n, double q, double a, double nx, uint64_t le)
-{
-    const double h = ((double)n - 1.0) * q;
-    const uint64_t lo = (uint64_t)floor(h);
-    const double t = h - (double)lo;
-    const double bb = (le > lo + 1 || lo + 1 >= n) ? a : nx;
-    // numpy's _lerp exactly: a + (b - a) * t, taken from the other end for t >= 0.5 -- no shortcut for t == 0 or a == b
-    // (numpy gives NaN there when a or b is infinite: inf * 0, inf - inf)
-    const double d = bb - a;
-    double r = a + d * t;
-    if (t >= 0.5) r = bb - d * (1.0 - t);
-    return r;
-}
-
+// ---- N3: q-quantile over time per grid point of rows [y0, y1), exact: pf_select (ctk_select.h) on the pixel's whole column -------
 template <typename VT, typename KT>
-__global__ __launch_bounds__(256) void k_quantile(const VT *__restrict__ x, int64_t T, int64_t npix, int64_t p0, int64_t nband, double q, double *__restrict__ out)
+__global__ __launch_bounds__(CTK_PFIELD_DIRECT_THREADS) void k_quantile(const VT *__restrict__ x, int64_t T, int64_t npix, int64_t p0, int64_t nband, double q,
+                                                                        double *__restrict__ out)
 {
-    __shared__ uint32_t hist[64][257];
-    __shared__ uint32_t s_n[64], s_k[64];
-    __shared__ KT s_prefix[64], s_next[64];
-    __shared__ uint32_t s_le[64];
-    const int px = (int)threadIdx.x & 63, tq = (int)threadIdx.x >> 6;
-    const int64_t pb = (int64_t)blockIdx.x * 64 + px;
+    constexpr int TILE = CTK_PFIELD_DIRECT_TILE, NT = CTK_PFIELD_DIRECT_THREADS;
+    __shared__ PfSel<KT, TILE, NT> S;
+    const int64_t pb = (int64_t)blockIdx.x * TILE + (int)threadIdx.x % TILE;
     const bool live = pb < nband;
-    const VT *col = x + p0 + pb;
-    if (threadIdx.x < 64) { s_n[px] = 0; s_prefix[px] = 0; s_next[px] = ~(KT)0; s_le[px] = 0; }
-    __syncthreads();
-    // values that count (NaNs are skipped, np.nanquantile)
-    {
-        uint32_t c = 0;
-        if (live) for (int64_t t = tq; t < T; t += 4) c += an_isnan(col[t * npix]) ? 0u : 1u;
-        if (c) atomicAdd(&s_n[px], c);
-    }
-    __syncthreads();
-    if (threadIdx.x < 64) { const double h = ((double)s_n[px] - 1.0) * q; s_k[px] = s_n[px] ? (uint32_t)floor(h) : 0u; }
-    constexpr int NB = (int)sizeof(KT);
-    for (int b = NB - 1; b >= 0; b--) {
-        for (int i = (int)threadIdx.x; i < 64 * 257; i += 256) (&hist[0][0])[i] = 0;
-        __syncthreads();
-        if (live && s_n[px]) {
-            const KT pre = s_prefix[px];
-            for (int64_t t = tq; t < T; t += 4) {
-                const VT v = col[t * npix];
-                if (an_isnan(v)) continue;
-                const KT k = an_key(v);
-                if (b == NB - 1 || (k >> (8 * (b + 1))) == pre) atomicAdd(&hist[px][(uint32_t)(k >> (8 * b)) & 255u], 1u);
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < 64 && s_n[px]) {
-            uint32_t k = s_k[px], cum = 0;
-            int bin = 0;
-            for (; bin < 256; bin++) { if (cum + hist[px][bin] > k) break; cum += hist[px][bin]; }
-            s_prefix[px] = (s_prefix[px] << 8) | (KT)min(bin, 255);
-            s_k[px] = k - cum;
-        }
-        __syncthreads();
-    }
-    // the next larger value and the number of values <= the selected one
-    if (live && s_n[px]) {
-        const KT sel = s_prefix[px];
-        uint32_t le = 0;
-        KT nx = ~(KT)0;
-        for (int64_t t = tq; t < T; t += 4) {
-            const VT v = col[t * npix];
-            if (an_isnan(v)) continue;
-            const KT k = an_key(v);
-            if (k <= sel) le++; else if (k < nx) nx = k;
-        }
-        if (le) atomicAdd(&s_le[px], le);
-        if (nx != ~(KT)0) atomicMin(&s_next[px], nx);
-    }
-    __syncthreads();
-    if (threadIdx.x < 64 && live) {
-        const double r = s_n[px] ? an_np_quantile((uint64_t)s_n[px], q, (double)an_unkey(s_prefix[px]), (double)an_unkey(s_next[px]), (uint64_t)s_le[px]) : __builtin_nan("");
-        out[pb] = r;
-    }
+    const VT *col = x + p0 + (live ? pb : 0);
+    const double r = pf_select<VT, KT, TILE, NT>(S, [&](int j) { return col[(int64_t)j * npix]; }, (int)T, live, q);
+    if ((int)threadIdx.x < TILE && live) out[pb] = r;
 }
 
 // mean of the non-NaN entries, fixed order (one workgroup, pairwise tree)
@@ -190,6 +106,63 @@ __global__ __launch_bounds__(1024) void k_nanmean(const double *__restrict__ v, 
 // ------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------
+// ---- shared by the percentile entries (ctk_percentile_* below, ctk_pctl.hip, ctk_pfield.hip) and ctk_anom_* ------------------------
+struct PctlArgs {
+    int64_t T; int ny, nx, y0, y1; const int32_t *group; int ngroups, window; double q;
+    int64_t npix() const { return (int64_t)ny * nx; }
+    int64_t nband() const { return (int64_t)(y1 - y0) * nx; }                  // the band: rows [y0, y1) of every plane ...
+    int64_t p0() const { return (int64_t)y0 * nx; }                            // ... from this element of the plane on
+};
+
+// what ctk_percentile_groups_* and ctk_percentile_field_* check alike
+static int pctl_validate_common(const ctk_handle *h, const PctlArgs &a, const double *out, const char *name)
+{
+    if (!h || !out || !a.group) return ctk_set_error(CTK_E_INVALID, "%s: null argument", name);
+    if (a.T < 1 || a.ny < 1 || a.nx < 1) return ctk_set_error(CTK_E_INVALID, "%s: bad shape (T=%lld ny=%d nx=%d)", name, (long long)a.T, a.ny, a.nx);
+    if (a.T > 0x7fffffffll) return ctk_set_error(CTK_E_INVALID, "%s: T=%lld timesteps (at most 2^31 - 1)", name, (long long)a.T);
+    if (a.y0 < 0 || a.y1 > a.ny || a.y0 >= a.y1) return ctk_set_error(CTK_E_INVALID, "%s: rows [%d, %d) are not rows of a grid of %d", name, a.y0, a.y1, a.ny);
+    if (a.ngroups < 1) return ctk_set_error(CTK_E_INVALID, "%s: ngroups=%d (at least 1)", name, a.ngroups);
+    if (a.window < 1) return ctk_set_error(CTK_E_INVALID, "%s: window=%d (at least 1)", name, a.window);
+    if (!(a.q >= 0.0 && a.q <= 1.0)) return ctk_set_error(CTK_E_INVALID, "%s: q=%g is not in [0, 1]", name, a.q);
+    for (int64_t t = 0; t < a.T; t++)
+        if (a.group[t] < 0 || a.group[t] >= a.ngroups) return ctk_set_error(CTK_E_INVALID, "%s: group[%lld] = %d is not in [0, %d)", name, (long long)t, a.group[t], a.ngroups);
+    return CTK_OK;
+}
+
+// the slab an entry selects on: x_host uploaded into io_in on the handle's stream, or (x_host NULL) the resident anomaly slab
+template <typename VT>
+static int pctl_slab(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx, const char *who, const VT **x_dev)
+{
+    if (x_host) {
+        const size_t bytes = (size_t)T * (size_t)ny * (size_t)nx * sizeof(VT);
+        CTKCHK(ensure(h, h->io_in, bytes));
+        HIPCHK(hipMemcpyAsync(h->io_in.p, x_host, bytes, hipMemcpyHostToDevice, h->stream));
+        *x_dev = (const VT *)h->io_in.p;
+    } else {
+        if (h->an_T != T || h->an_ny != ny || h->an_nx != nx || h->an_f64 != (sizeof(VT) == 8)) return ctk_set_error(CTK_E_STATE, "%s: no matching anomaly slab is resident", who);
+        *x_dev = (const VT *)h->an_out.p;
+    }
+    return CTK_OK;
+}
+
+// counting sort of the timesteps by group (ids in [0, G), T < 2^31): slist[off[g] .. off[g + 1]) = the steps of group g, rising
+static void steps_by_group(const int32_t *group, int64_t T, int G, int32_t *slist, int32_t *off)
+{
+    std::fill(off, off + G + 1, 0);
+    for (int64_t t = 0; t < T; t++) off[group[t] + 1]++;
+    for (int g = 0; g < G; g++) off[g + 1] += off[g];
+    std::vector<int32_t> cur(off, off + G);
+    for (int64_t t = 0; t < T; t++) slist[cur[(size_t)group[t]]++] = (int32_t)t;
+}
+
+// the scalar percentile's kernels on the handle's stream: qv[0 .. nband) the per-pixel quantiles, qv[nband] their mean
+template <typename VT, typename KT>
+static void launch_quantile(ctk_handle *h, const VT *x_dev, int64_t T, int64_t npix, int64_t p0, int64_t nband, double q, double *qv)
+{
+    k_quantile<VT, KT><<<(unsigned)((nband + CTK_PFIELD_DIRECT_TILE - 1) / CTK_PFIELD_DIRECT_TILE), CTK_PFIELD_DIRECT_THREADS, 0, h->stream>>>(x_dev, T, npix, p0, nband, q, qv);
+    k_nanmean<<<1, 1024, 0, h->stream>>>(qv, nband, qv + nband);
+}
+
 template <typename VT>
 static int anom_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
                      const VT *clim_in, VT *anom_out, VT *clim_out, int keep_resident)
@@ -211,13 +184,7 @@ static int anom_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx,
     // timesteps sorted by group, group offsets, group of every timestep
     std::vector<int32_t> idx((size_t)2 * T + ngroups + 1);
     int32_t *tlist = idx.data(), *goff = tlist + T, *grp = goff + ngroups + 1;
-    std::fill(goff, goff + ngroups + 1, 0);
-    for (int64_t t = 0; t < T; t++) goff[group[t] + 1]++;
-    for (int g = 0; g < ngroups; g++) goff[g + 1] += goff[g];
-    {
-        std::vector<int32_t> cur(goff, goff + ngroups);
-        for (int64_t t = 0; t < T; t++) tlist[cur[(size_t)group[t]]++] = (int32_t)t;
-    }
+    steps_by_group(group, T, ngroups, tlist, goff);
     memcpy(grp, group, (size_t)T * 4);
     HIPCHK(hipMemcpy(h->an_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
     const int32_t *d_tlist = P<int32_t>(h->an_idx), *d_goff = d_tlist + T, *d_grp = d_goff + ngroups + 1;
@@ -294,23 +261,16 @@ template <typename VT, typename KT>
 static int percentile_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx, int y0, int y1, double q, double *out)
 {
     if (!h || !out || T < 1 || ny < 1 || nx < 1 || y0 < 0 || y1 > ny || y0 >= y1 || !(q >= 0.0 && q <= 1.0)) return ctk_set_error(CTK_E_INVALID, "ctk_percentile: bad arguments");
+    if (T > 0x7fffffffll) return ctk_set_error(CTK_E_INVALID, "ctk_percentile: T=%lld timesteps (at most 2^31 - 1)", (long long)T);
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const int64_t npix = (int64_t)ny * nx, nband = (int64_t)(y1 - y0) * nx;
     const VT *x_dev;
-    if (x_host) {
-        CTKCHK(ensure(h, h->io_in, (size_t)T * npix * sizeof(VT)));
-        HIPCHK(hipMemcpy(h->io_in.p, x_host, (size_t)T * npix * sizeof(VT), hipMemcpyHostToDevice));
-        x_dev = (const VT *)h->io_in.p;
-    } else {
-        if (h->an_T != T || h->an_ny != ny || h->an_nx != nx || h->an_f64 != (sizeof(VT) == 8)) return ctk_set_error(CTK_E_STATE, "ctk_percentile: no matching anomaly slab is resident");
-        x_dev = (const VT *)h->an_out.p;
-    }
+    CTKCHK(pctl_slab(h, x_host, T, ny, nx, "ctk_percentile", &x_dev));
     h->an_pct_n = -1;
     CTKCHK(ensure(h, h->an_raw, ((size_t)nband + 8) * 8));
     double *qv = P<double>(h->an_raw);
-    k_quantile<VT, KT><<<(unsigned)((nband + 63) / 64), 256, 0, s>>>(x_dev, T, npix, (int64_t)y0 * nx, nband, q, qv);
-    k_nanmean<<<1, 1024, 0, s>>>(qv, nband, qv + nband);
+    launch_quantile<VT, KT>(h, x_dev, T, npix, (int64_t)y0 * nx, nband, q, qv);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, qv + nband, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));

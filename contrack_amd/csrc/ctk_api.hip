@@ -8,6 +8,7 @@
 #include "ctk_seam.h"
 #include "ctk_comm.h"
 #include "ctk_forms.h"
+#include "ctk_select.h"
 #include "../../include/contrack_hip_debug.h"
 
 #include <chrono>

@@ -418,7 +418,7 @@ inline bool ctk_pctl_day_fits(int64_t steps_of_day, int64_t nband) { return step
 #define CTK_PFIELD_LDS_BYTES 163840   // what a workgroup may declare on gfx950
 #define CTK_PFIELD_RING_THREADS 512   // ring form: lanes per pixel = 512 / pixel tile
 #define CTK_PFIELD_DIRECT_THREADS 256
-#define CTK_PFIELD_DIRECT_TILE 64     // direct form: pixels per workgroup (4 lanes per pixel, as k_quantile)
+#define CTK_PFIELD_DIRECT_TILE 64     // direct form: pixels per workgroup (4 lanes per pixel); k_quantile runs the same tile
 #define CTK_PFIELD_MIN_TILE 8         // ring form: the pixel tile is 32, 16 or 8 -- the widest whose ring holds the longest pool
 #define CTK_PFIELD_MAX_TILE 32
 enum CtkPfieldForm { CTK_PFIELD_DIRECT = 0, CTK_PFIELD_RING = 1 };

@@ -5,7 +5,7 @@
 // rows [y0, y1) on every timestep whose group lies in the centred window of W groups around g, taken circularly over the G groups:
 //     pool(g) = { x[t, y, :] : y0 <= y < y1, group[t] in { (g + d) mod G : -(W / 2) <= d <= (W - 1) / 2 } }
 //
-// Radix selection on the order-preserving keys of an_key (ctk_anom.hip), for all groups at once.  Histograms are additive over days:
+// Radix selection on the order-preserving keys of an_key (ctk_select.h), for all groups at once.  Histograms are additive over days:
 //   k_pctl_sweep   one read of the band per digit.  A workgroup takes CTK_PCTL_CHUNK values of ONE timestep, so its day d is
 //                  uniform; it counts the digit in LDS and adds the nonzero bins to the histograms of its day in HBM.  From the second
 //                  digit on a value counts only under a prefix one of the day's TARGETS (the groups whose window holds d) has
@@ -16,7 +16,7 @@
 //                  values <= it and, where another key shares its upper digits, the next larger key come from the same histogram.
 //   k_pctl_close   the closing sweep, for the groups whose next larger key lies under another prefix: per (day, distinct selected
 //                  key s) the smallest key above s.  Workgroups of a day none of whose targets needs it return before reading.
-//   k_pctl_finish  numpy's interpolation (an_np_quantile, shared with k_quantile).
+//   k_pctl_finish  numpy's interpolation (an_np_quantile, shared with pf_select).
 // The band is read once per sweep: ctk_pctl_form().sweeps times per call (4 for float32, 7 for float64), whatever G and W are.
 // Window sums, ranks and n are 64-bit; the per-day counters are uint32 behind the host check ctk_pctl_day_fits.
 #pragma once
@@ -60,9 +60,6 @@ __device__ __forceinline__ void pctl_stream(const double *base, int64_t len, F f
     const int64_t done = head + nv * 2;
     if (done + tid < len) fn(base[done + tid]);
 }
-
-__device__ __forceinline__ void pctl_atomic_min(uint32_t *p, uint32_t v) { atomicMin(p, v); }
-__device__ __forceinline__ void pctl_atomic_min(uint64_t *p, uint64_t v) { atomicMin((unsigned long long *)p, (unsigned long long)v); }
 
 // the window of group g: `cnt` members, member j is (start + j) mod G.  mirrored: the TARGETS of day g (the groups whose window holds it)
 __device__ __forceinline__ void pctl_window(int g, int G, int W, bool mirrored, int *start, int *cnt)
@@ -298,27 +295,14 @@ __global__ __launch_bounds__(256) void k_pctl_read(const VT *__restrict__ x, int
 // ------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------
-struct PctlArgs {
-    int64_t T; int ny, nx, y0, y1; const int32_t *group; int ngroups, window; double q;
-};
-
 static int pctl_validate(const ctk_handle *h, const PctlArgs &a, const double *out, const char *name)
 {
-    if (!h || !out || !a.group) return ctk_set_error(CTK_E_INVALID, "%s: null argument", name);
-    if (a.T < 1 || a.ny < 1 || a.nx < 1) return ctk_set_error(CTK_E_INVALID, "%s: bad shape (T=%lld ny=%d nx=%d)", name, (long long)a.T, a.ny, a.nx);
-    if (a.T > 0x7fffffffll) return ctk_set_error(CTK_E_INVALID, "%s: T=%lld timesteps (at most 2^31 - 1)", name, (long long)a.T);
-    if (a.y0 < 0 || a.y1 > a.ny || a.y0 >= a.y1) return ctk_set_error(CTK_E_INVALID, "%s: rows [%d, %d) are not rows of a grid of %d", name, a.y0, a.y1, a.ny);
-    if (a.ngroups < 1) return ctk_set_error(CTK_E_INVALID, "%s: ngroups=%d (at least 1)", name, a.ngroups);
-    if (a.window < 1) return ctk_set_error(CTK_E_INVALID, "%s: window=%d (at least 1)", name, a.window);
-    if (!(a.q >= 0.0 && a.q <= 1.0)) return ctk_set_error(CTK_E_INVALID, "%s: q=%g is not in [0, 1]", name, a.q);
+    CTKCHK(pctl_validate_common(h, a, out, name));
     if (a.window < a.ngroups && a.window > CTK_PCTL_MAX_WINDOW)
         return ctk_set_error(CTK_E_INVALID, "%s: a window of %d groups (below the %d groups) exceeds %d", name, a.window, a.ngroups, CTK_PCTL_MAX_WINDOW);
     std::vector<int64_t> steps((size_t)a.ngroups, 0);
-    for (int64_t t = 0; t < a.T; t++) {
-        if (a.group[t] < 0 || a.group[t] >= a.ngroups) return ctk_set_error(CTK_E_INVALID, "%s: group[%lld] = %d is not in [0, %d)", name, (long long)t, a.group[t], a.ngroups);
-        steps[(size_t)a.group[t]]++;
-    }
-    const int64_t nband = (int64_t)(a.y1 - a.y0) * a.nx;
+    for (int64_t t = 0; t < a.T; t++) steps[(size_t)a.group[t]]++;
+    const int64_t nband = a.nband();
     for (int g = 0; g < a.ngroups; g++)
         if (!ctk_pctl_day_fits(steps[(size_t)g], nband))
             return ctk_set_error(CTK_E_INVALID, "%s: group %d has %lld timesteps of %lld band values: its uint32 counters would overflow (2^32)", name, g,
@@ -338,7 +322,7 @@ static int pctl_launch(ctk_handle *h, const VT *x_dev, const PctlArgs &a, const 
 {
     hipStream_t s = h->stream;
     const int G = a.ngroups, W = a.window;
-    const int64_t npix = (int64_t)a.ny * a.nx, nband = (int64_t)(a.y1 - a.y0) * a.nx, p0 = (int64_t)a.y0 * a.nx;
+    const int64_t npix = a.npix(), nband = a.nband(), p0 = a.p0();
     const CtkPctlForm f = ctk_pctl_form((int)sizeof(KT) * 8, nband, G, W);
     const size_t slots = (size_t)G * (size_t)f.stride;
     CTKCHK(ensure(h, h->pc_hist, slots * CTK_PCTL_BINS * 4));
@@ -383,16 +367,8 @@ static int percentile_groups_impl(ctk_handle *h, const VT *x_host, int64_t T, in
     const PctlArgs a = {T, ny, nx, y0, y1, group, ngroups, window, q};
     CTKCHK(pctl_validate(h, a, out, "ctk_percentile_groups"));
     HIPCHK(hipSetDevice(h->device));
-    const int64_t npix = (int64_t)ny * nx;
     const VT *x_dev;
-    if (x_host) {
-        CTKCHK(ensure(h, h->io_in, (size_t)T * npix * sizeof(VT)));
-        HIPCHK(hipMemcpyAsync(h->io_in.p, x_host, (size_t)T * npix * sizeof(VT), hipMemcpyHostToDevice, h->stream));
-        x_dev = (const VT *)h->io_in.p;
-    } else {
-        if (h->an_T != T || h->an_ny != ny || h->an_nx != nx || h->an_f64 != (sizeof(VT) == 8)) return ctk_set_error(CTK_E_STATE, "ctk_percentile_groups: no matching anomaly slab is resident");
-        x_dev = (const VT *)h->an_out.p;
-    }
+    CTKCHK(pctl_slab(h, x_host, T, ny, nx, "ctk_percentile_groups", &x_dev));
     const double *out_dev = nullptr;
     CTKCHK((pctl_launch<VT, KT>(h, x_dev, a, &out_dev)));
     HIPCHK(hipMemcpyAsync(out, out_dev, (size_t)ngroups * 8, hipMemcpyDeviceToHost, h->stream));
@@ -431,7 +407,7 @@ extern "C" int ctk_debug_time_percentile_groups(ctk_handle *h, const float *x_de
     if (!x_dev || !ms12 || reps < 1) return ctk_set_error(CTK_E_INVALID, "ctk_debug_time_percentile_groups: null buffer or reps < 1");
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    const int64_t npix = (int64_t)ny * nx, nband = (int64_t)(y1 - y0) * nx, p0 = (int64_t)y0 * nx;
+    const int64_t npix = a.npix(), nband = a.nband(), p0 = a.p0();
     for (int i = 0; i < 12; i++) ms12[i] = 0;
     double best = 1e30;
     for (int r = 0; r <= reps; r++) {                                          // (the first call grows the buffers)
@@ -475,8 +451,7 @@ extern "C" int ctk_debug_time_percentile_groups(ctk_handle *h, const float *x_de
         h->an_pct_n = -1;
         double *qv = P<double>(h->an_raw);
         if (hipEventRecord(ev[0], s) != hipSuccess) rc = ctk_set_error(CTK_E_NODEVICE, "hipEventRecord failed");
-        k_quantile<float, uint32_t><<<(unsigned)((nband + 63) / 64), 256, 0, s>>>(x_dev, T, npix, p0, nband, q, qv);
-        k_nanmean<<<1, 1024, 0, s>>>(qv, nband, qv + nband);
+        launch_quantile<float, uint32_t>(h, x_dev, T, npix, p0, nband, q, qv);
         if (rc == CTK_OK && hipEventRecord(ev[1], s) != hipSuccess) rc = ctk_set_error(CTK_E_NODEVICE, "hipEventRecord failed");
         elapsed(ev[0], ev[1], &ms12[2]);
     }

@@ -6,7 +6,7 @@
 //
 // The host sorts the timesteps by group once (a step list and G + 1 offsets).  The members of a window are consecutive groups
 // modulo G, so every pool is one circular slice of that list: positions [A_g, A_g + len_g) of the list repeated, with A_g and
-// A_g + len_g rising with g.  One radix selection (pf_select: 8-bit digits of the order-preserving keys of an_key, most
+// A_g + len_g rising with g.  One radix selection (pf_select, ctk_select.h: 8-bit digits of the order-preserving keys of an_key, most
 // significant first, per-pixel histograms in LDS, several lanes per pixel) serves two forms (ctk_pfield_plan, ctk_forms.h):
 //   k_pfield_direct  a workgroup takes 64 consecutive pixels of the band and ONE group and fetches every pass from global memory
 //                    through the step list: sizeof(key) reads of the pool per (group, pixel).  Valid for pools of any length.
@@ -18,90 +18,6 @@
 // W >= G: every group has the same pool -- one plane is selected and k_pfield_replicate copies it.  Pool counts are per pixel:
 // uint32 behind the host check T < 2^31.  Every load of the slab is one element wide: the band may start at any row.
 #pragma once
-
-template <typename KT, int TILE, int NT>
-struct PfSel {
-    uint32_t hist[TILE][257];
-    uint32_t part[TILE][NT / TILE];      // sums of 256 / (NT / TILE) consecutive bins
-    uint32_t n[TILE], k[TILE], k0[TILE], le[TILE];
-    KT prefix[TILE], next[TILE];
-};
-
-// the q-quantile of the `len` pool values fetch(0 .. len) of this lane's pixel (tid % TILE; the NT / TILE lanes tid / TILE of a pixel
-// share the pool); every thread of the workgroup calls it, lane 0 of a live pixel gets the result.  Ends behind a barrier.
-template <typename VT, typename KT, int TILE, int NT, typename F>
-__device__ __forceinline__ double pf_select(PfSel<KT, TILE, NT> &S, F fetch, int len, bool live, double q)
-{
-    constexpr int L = NT / TILE, SEG = 256 / L, NB = (int)sizeof(KT);
-    static_assert(NT % TILE == 0 && L <= 256 && 256 % L == 0, "lanes per pixel must divide the 256 bins");
-    static_assert(sizeof(PfSel<KT, TILE, NT>) <= ctk_pfield_select_bytes(TILE, NT), "ctk_pfield_select_bytes is what the plan counts");
-    const int tid = (int)threadIdx.x, px = tid % TILE, lane = tid / TILE;
-    if (lane == 0) { S.prefix[px] = 0; S.next[px] = ~(KT)0; S.n[px] = 0; S.le[px] = 0; }
-#pragma unroll
-    for (int b = NB - 1; b >= 0; b--) {
-        const bool first = b == NB - 1;
-        for (int i = tid; i < TILE * 257; i += NT) (&S.hist[0][0])[i] = 0;
-        __syncthreads();
-        if (live && (first || S.n[px])) {
-            const KT pre = S.prefix[px];
-            KT nx = ~(KT)0;
-            for (int j = lane; j < len; j += L) {
-                const VT v = fetch(j);
-                if (an_isnan(v)) continue;                                     // (np.nanquantile)
-                const KT k = an_key(v);
-                const KT up = first ? pre : (KT)(k >> (8 * (b + 1) < 8 * NB ? 8 * (b + 1) : 0));
-                if (up == pre) atomicAdd(&S.hist[px][(uint32_t)(k >> (8 * b)) & 255u], 1u);
-                else if (b == 0 && up > pre && k < nx) nx = k;
-            }
-            if (b == 0 && nx != ~(KT)0) pctl_atomic_min(&S.next[px], nx);
-        }
-        __syncthreads();
-        if (live) {
-            uint32_t s = 0;
-#pragma unroll
-            for (int i = 0; i < SEG; i++) s += S.hist[px][lane * SEG + i];
-            S.part[px][lane] = s;
-        }
-        __syncthreads();
-        if (lane == 0 && live) {
-            uint32_t n = S.n[px];
-            if (first) {
-                n = 0;
-                for (int i = 0; i < L; i++) n += S.part[px][i];
-                const uint32_t k0 = n ? (uint32_t)floor(((double)n - 1.0) * q) : 0u;
-                S.n[px] = n; S.k0[px] = k0; S.k[px] = k0;
-            }
-            if (n) {
-                const uint32_t k = S.k[px];
-                uint32_t cum = 0;
-                int sg = 0;
-                for (; sg < L - 1; sg++) { const uint32_t c = S.part[px][sg]; if (cum + c > k) break; cum += c; }
-                int bin = sg * SEG;
-                for (; bin < sg * SEG + SEG - 1; bin++) { const uint32_t c = S.hist[px][bin]; if (cum + c > k) break; cum += c; }
-                const KT pre = S.prefix[px];
-                S.prefix[px] = (KT)(pre << 8) | (KT)bin;
-                S.k[px] = k - cum;
-                if (b == 0) {
-                    S.le[px] = (S.k0[px] - k) + cum + S.hist[px][bin];
-                    int nb = bin + 1;                                          // the next key under the same prefix, if there is one
-                    for (; nb < sg * SEG + SEG; nb++) if (S.hist[px][nb]) break;
-                    if (nb == sg * SEG + SEG) {
-                        int s2 = sg + 1;
-                        for (; s2 < L; s2++) if (S.part[px][s2]) break;
-                        nb = 256;
-                        if (s2 < L) for (nb = s2 * SEG; !S.hist[px][nb]; nb++) {}
-                    }
-                    if (nb < 256) S.next[px] = (KT)(pre << 8) | (KT)nb;        // (below every key under a larger prefix)
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (lane != 0 || !live) return 0.0;
-    if (!S.n[px]) return __builtin_nan("");
-    const double a = (double)an_unkey(S.prefix[px]);
-    return an_np_quantile((uint64_t)S.n[px], q, a, S.next[px] == ~(KT)0 ? a : (double)an_unkey(S.next[px]), (uint64_t)S.le[px]);
-}
 
 // blockIdx.x = plane + planes * tile: the workgroups of a tile's groups run together and share its columns in the cache
 template <typename VT, typename KT>
@@ -172,16 +88,8 @@ struct PfPrep {
 
 static int pfield_validate(const ctk_handle *h, const PctlArgs &a, const double *out, const char *name)
 {
-    if (!h || !out || !a.group) return ctk_set_error(CTK_E_INVALID, "%s: null argument", name);
-    if (a.T < 1 || a.ny < 1 || a.nx < 1) return ctk_set_error(CTK_E_INVALID, "%s: bad shape (T=%lld ny=%d nx=%d)", name, (long long)a.T, a.ny, a.nx);
-    if (a.T > 0x7fffffffll) return ctk_set_error(CTK_E_INVALID, "%s: T=%lld timesteps (at most 2^31 - 1)", name, (long long)a.T);
-    if (a.y0 < 0 || a.y1 > a.ny || a.y0 >= a.y1) return ctk_set_error(CTK_E_INVALID, "%s: rows [%d, %d) are not rows of a grid of %d", name, a.y0, a.y1, a.ny);
-    if (a.ngroups < 1) return ctk_set_error(CTK_E_INVALID, "%s: ngroups=%d (at least 1)", name, a.ngroups);
-    if (a.window < 1) return ctk_set_error(CTK_E_INVALID, "%s: window=%d (at least 1)", name, a.window);
-    if (!(a.q >= 0.0 && a.q <= 1.0)) return ctk_set_error(CTK_E_INVALID, "%s: q=%g is not in [0, 1]", name, a.q);
-    for (int64_t t = 0; t < a.T; t++)
-        if (a.group[t] < 0 || a.group[t] >= a.ngroups) return ctk_set_error(CTK_E_INVALID, "%s: group[%lld] = %d is not in [0, %d)", name, (long long)t, a.group[t], a.ngroups);
-    const int64_t nband = (int64_t)(a.y1 - a.y0) * a.nx, tiles = (nband + CTK_PFIELD_MIN_TILE - 1) / CTK_PFIELD_MIN_TILE;
+    CTKCHK(pctl_validate_common(h, a, out, name));
+    const int64_t nband = a.nband(), tiles = (nband + CTK_PFIELD_MIN_TILE - 1) / CTK_PFIELD_MIN_TILE;
     if (tiles * (int64_t)a.ngroups > 0x7fffffffll)
         return ctk_set_error(CTK_E_INVALID, "%s: %d groups x a band of %lld values is too large", name, a.ngroups, (long long)nband);
     return CTK_OK;
@@ -191,14 +99,9 @@ static void pfield_prepare(const PctlArgs &a, PfPrep &p)
 {
     const int G = a.ngroups, W = a.window;
     const int64_t T = a.T;
-    std::vector<int64_t> off((size_t)G + 1, 0);
-    for (int64_t t = 0; t < T; t++) off[(size_t)a.group[t] + 1]++;
-    for (int g = 0; g < G; g++) off[(size_t)g + 1] += off[(size_t)g];
+    std::vector<int32_t> off((size_t)G + 1);
     p.slist.resize((size_t)T);
-    {
-        std::vector<int64_t> cur(off.begin(), off.end() - 1);
-        for (int64_t t = 0; t < T; t++) p.slist[(size_t)cur[(size_t)a.group[t]]++] = (int32_t)t;
-    }
+    steps_by_group(a.group, T, G, p.slist.data(), off.data());
     if (W >= G) { p.pa.assign(1, 0); p.plen.assign(1, (int32_t)T); p.max_pool = T; return; }
     auto off2 = [&](int64_t u) { return off[(size_t)(u % G)] + T * (u / G); };
     p.pa.resize((size_t)G); p.plen.resize((size_t)G);
@@ -217,7 +120,7 @@ static int pfield_launch(ctk_handle *h, const VT *x_dev, const PctlArgs &a, cons
 {
     hipStream_t s = h->stream;
     const int G = a.ngroups, T = (int)a.T;
-    const int64_t npix = (int64_t)a.ny * a.nx, nband = (int64_t)(a.y1 - a.y0) * a.nx, p0 = (int64_t)a.y0 * a.nx;
+    const int64_t npix = a.npix(), nband = a.nband(), p0 = a.p0();
     const CtkPfieldPlan f = ctk_pfield_plan((int)sizeof(KT), force_direct ? INT64_MAX : p.max_pool, G, a.window);
     const int planes = f.planes;
     CTKCHK(ensure(h, h->pf_out, (size_t)G * (size_t)nband * 8));
@@ -250,20 +153,12 @@ static int percentile_field_impl(ctk_handle *h, const VT *x_host, int64_t T, int
     const PctlArgs a = {T, ny, nx, y0, y1, group, ngroups, window, q};
     CTKCHK(pfield_validate(h, a, out, "ctk_percentile_field"));
     HIPCHK(hipSetDevice(h->device));
-    const int64_t npix = (int64_t)ny * nx, nband = (int64_t)(y1 - y0) * nx;
     const VT *x_dev;
-    if (x_host) {
-        CTKCHK(ensure(h, h->io_in, (size_t)T * npix * sizeof(VT)));
-        HIPCHK(hipMemcpyAsync(h->io_in.p, x_host, (size_t)T * npix * sizeof(VT), hipMemcpyHostToDevice, h->stream));
-        x_dev = (const VT *)h->io_in.p;
-    } else {
-        if (h->an_T != T || h->an_ny != ny || h->an_nx != nx || h->an_f64 != (sizeof(VT) == 8)) return ctk_set_error(CTK_E_STATE, "ctk_percentile_field: no matching anomaly slab is resident");
-        x_dev = (const VT *)h->an_out.p;
-    }
+    CTKCHK(pctl_slab(h, x_host, T, ny, nx, "ctk_percentile_field", &x_dev));
     PfPrep prep;
     pfield_prepare(a, prep);
     CTKCHK((pfield_launch<VT, KT>(h, x_dev, a, prep, false)));
-    HIPCHK(hipMemcpyAsync(out, h->pf_out.p, (size_t)ngroups * (size_t)nband * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(out, h->pf_out.p, (size_t)ngroups * (size_t)a.nband() * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return CTK_OK;
 }
@@ -305,7 +200,7 @@ template <typename VT, typename KT>
 static int time_pfield_impl(ctk_handle *h, const VT *x_dev, const PctlArgs &a, int reps, double *out, double *out_direct, double *ms4)
 {
     hipStream_t s = h->stream;
-    const int64_t npix = (int64_t)a.ny * a.nx, nband = (int64_t)(a.y1 - a.y0) * a.nx, p0 = (int64_t)a.y0 * a.nx;
+    const int64_t npix = a.npix(), nband = a.nband(), p0 = a.p0();
     PfPrep prep;
     pfield_prepare(a, prep);
     for (int form = 0; form < 2; form++) {

@@ -441,7 +441,8 @@ int ctk_resident_anom_generation(ctk_handle *h, uint64_t *generation);
 int ctk_track_resident(ctk_handle *h, const double *thr, int cmp_op, const float *wrow, double overlap, int persistence, int twosided,
                        int32_t *flag, int64_t *n_tracked);
 /* README.rst:150-151: anom.sel(latitude=rows y0..y1-1).quantile(q, dim='time').mean() -- per grid point the exact q-quantile over
- * time (numpy's linear interpolation, NaNs skipped), then the mean over the band.  x = NULL: the resident anomaly slab. */
+ * time (numpy's linear interpolation, NaNs skipped), then the mean over the band.  x = NULL: the resident anomaly slab.
+ * T <= 2^31 - 1 (CTK_E_INVALID beyond, checked before x is read), as for the two entries below. */
 int ctk_percentile_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, int y0, int y1, double q, double *out);
 int ctk_percentile_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, int y0, int y1, double q, double *out);
 /* README.rst:235-240 (the threshold "defined as the 10th percentile of the ... anomaly distribution over 30-90N at each calendar day"),

@@ -253,6 +253,33 @@ def test_percentile_inf_neighbours(trk, dtype):
         _check_values(trk.debug_percentile_values(cols.shape[1]), x, q, (dtype.__name__, "inf neighbours", "q", q))
 
 
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
+@pytest.mark.parametrize("T", [1, 5, 259])                          # 259: no multiple of the 4 lanes per pixel, more than the 256 bins
+def test_scalar_and_field_entries_are_one_selection(trk, T, dtype):
+    """k_quantile and k_pfield_direct / k_pfield_ring run the same pf_select: one group holding every step with window 1 is the
+    scalar entry's pool, and the per-pixel values agree in every bit.  65 pixels: two workgroups, the second with one pixel."""
+    rng = np.random.default_rng(1000 + T)
+    for kind in ("normal", "allnan"):
+        x = np.full((T, 3, 65), np.nan, dtype=dtype)
+        x[:, 1, :] = _columns(kind, T, 65, dtype, rng)
+        x[:, 0, :] = dtype(7.0)
+        for q in QS:
+            trk.percentile(x, 1, 2, q)
+            vals = trk.debug_percentile_values(65)
+            field = trk.percentile_field(x, 1, 2, np.zeros(T, dtype=np.int32), 1, q, window=1)[0].ravel()
+            assert np.array_equal(np.isnan(vals), np.isnan(field)), (dtype.__name__, "T", T, kind, "q", q, "NaN positions")
+            assert np.array_equal(vals.view(np.uint64)[~np.isnan(vals)], field.view(np.uint64)[~np.isnan(field)]), (dtype.__name__, "T", T, kind, "q", q)
+
+
+def test_scalar_entry_refuses_2p31_steps(trk):
+    """the selection counts its pool in an int: T = 2^31 is refused before the slab is touched (the buffer holds one value)"""
+    x = np.zeros(1, dtype=np.float32)
+    out = _native.C.c_double(0.0)
+    with pytest.raises(ValueError, match="at most 2\\^31 - 1"):
+        _native.check(_native.lib().ctk_percentile_f32(trk.handle, x.ctypes.data, 2 ** 31, 1, 1, 0, 1, 0.5, _native.C.byref(out)))
+    assert trk.percentile(x.reshape(1, 1, 1), 0, 1, 0.5) == 0.0      # the handle goes on working
+
+
 # ---- long and large slabs ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("G", [3000, 70000], ids=["G3000", "G70000"])
 def test_long_slab_beyond_grid_y_limit(trk, G):
