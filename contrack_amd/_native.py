@@ -39,10 +39,11 @@ EXPORTS = [
     "ctk_frequency_dev", "ctk_frequency", "ctk_frequency_cb", "ctk_debug_set_freq", "ctk_debug_time_freq",
     "ctk_percentile_groups_f32", "ctk_percentile_groups_f64", "ctk_debug_percentile_groups_sweeps", "ctk_debug_time_percentile_groups",
     "ctk_percentile_field_f32", "ctk_percentile_field_f64", "ctk_debug_percentile_field_plan", "ctk_debug_percentile_field_form", "ctk_debug_time_percentile_field",
+    "ctk_anom_seg_f32", "ctk_anom_seg_f64", "ctk_anom_stream_f32", "ctk_anom_stream_f64", "ctk_anom_stream_cb", "ctk_debug_anom_form",
 ]
 
 READ_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)       # ctk_read_chunk_fn
-WRITE_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)      # ctk_write_chunk_fn
+WRITE_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)      # ctk_write_chunk_fn, ctk_write_values_fn
 
 # ctk_life_row (include/contrack_hip.h)
 LIFE_ROW = np.dtype([("t", "<i4"), ("label", "<i4"), ("shift", "<i4"), ("pad", "<i4"),
@@ -193,6 +194,12 @@ def lib():
     L.ctk_lifecycle_exact.argtypes = [p, p, i64, p]
     for name in ("ctk_anom_f32", "ctk_anom_f64"):
         getattr(L, name).argtypes = [p, p, i64, i32, i32, p, i32, i32, i32, p, p, p, i32]
+    for name in ("ctk_anom_seg_f32", "ctk_anom_seg_f64"):
+        getattr(L, name).argtypes = L.ctk_anom_f32.argtypes + [p, i64]
+    for name in ("ctk_anom_stream_f32", "ctk_anom_stream_f64"):
+        getattr(L, name).argtypes = [p, p, i64, i32, i32, p, i32, i32, i32, p, i64, p, p, p, i64]
+    L.ctk_anom_stream_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, p, i32, i32, i32, p, i64, p, p, WRITE_CHUNK_FN, p, i64]
+    L.ctk_debug_anom_form.argtypes = [p, C.POINTER(i64)]
     L.ctk_resident_anom.argtypes = [p, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.ctk_resident_anom_generation.argtypes = [p, C.POINTER(C.c_uint64)]
     L.ctk_track_resident.argtypes = [p, p, i32, p, dbl, i32, i32, p, C.POINTER(i64)]
@@ -811,8 +818,10 @@ class Tracker:
         return float(ms[0]), float(ms[1])
 
     # ---- calc_anom / percentile threshold on the device ---------------------------------------------------------
-    def anomalies(self, x, group, ngroups, window=1, smooth=1, clim=None, want_anom=True, want_clim=False, keep_resident=False):
-        """x (T, ny, nx) float32 / float64; group: T ids in [0, ngroups).  Returns (anom or None, clim or None)."""
+    def anomalies(self, x, group, ngroups, window=1, smooth=1, clim=None, want_anom=True, want_clim=False, keep_resident=False, segments=None):
+        """x (T, ny, nx) float32 / float64; group: T ids in [0, ngroups).  Returns (anom or None, clim or None).
+        segments: None, or the first step of every independent time segment (0 first, strictly increasing, below T): the smoothing
+        stays inside a segment (ctk_anom_seg_*); the climatology is pooled over all of them."""
         x = np.ascontiguousarray(x)
         f64 = x.dtype != np.float32
         if f64:
@@ -824,11 +833,106 @@ class Tracker:
             raise ValueError("clim must have shape (ngroups, ny, nx)")
         anom = np.empty_like(x) if want_anom else None
         cout = np.empty((ngroups, ny, nx), dtype=x.dtype) if want_clim else None
-        fn = lib().ctk_anom_f64 if f64 else lib().ctk_anom_f32
-        check(fn(self._h, x.ctypes.data, T, ny, nx, group.ctypes.data, int(ngroups), int(window), int(smooth),
-                 None if cin is None else cin.ctypes.data, None if anom is None else anom.ctypes.data,
-                 None if cout is None else cout.ctypes.data, int(bool(keep_resident))))
+        args = (self._h, x.ctypes.data, T, ny, nx, group.ctypes.data, int(ngroups), int(window), int(smooth),
+                None if cin is None else cin.ctypes.data, None if anom is None else anom.ctypes.data,
+                None if cout is None else cout.ctypes.data, int(bool(keep_resident)))
+        if segments is None:
+            check((lib().ctk_anom_f64 if f64 else lib().ctk_anom_f32)(*args))
+        else:
+            st = _seg_starts(segments)
+            check((lib().ctk_anom_seg_f64 if f64 else lib().ctk_anom_seg_f32)(*args, st.ctypes.data if st.size else None, st.shape[0]))
         return anom, cout
+
+    def anomalies_stream(self, source, group, ngroups, window=1, smooth=1, clim=None, sink=None, shape=None, dtype=None, chunk_steps=0,
+                         segments=None, want_clim=False):
+        """anomalies(..., segments=...) with the slab passing through chunk-sized device buffers (ctk_anom_stream_*): the device holds
+        a few chunks, 12 bytes per (group, pixel) and the climatology, never the slab.  Same bits as anomalies for every chunk_steps
+        (0: about 256 MB per chunk; below smooth - 1 it is raised to smooth - 1).
+
+        source: a (T, ny, nx) float32 / float64 array (np.memmap included), or a callable reader(t0, nt, out) that fills `out` (a
+                (nt, ny, nx) view of pinned memory) with the timesteps [t0, t0 + nt) -- then `shape` = (T, ny, nx) and `dtype` are
+                required.  It is read twice without `clim` (climatology, then anomalies), once with it; ranges never overlap.
+        sink:   None (a new array of the slab's dtype is returned), False (no anomalies: the climatology only), an array (T, ny, nx)
+                of the slab's dtype, or a callable writer(t0, nt, values) that receives each chunk as a (nt, ny, nx) view valid during
+                the call, every step once in rising order.
+        Returns (anom array or None, clim or None)."""
+        L = lib()
+        if callable(source):
+            if shape is None or dtype is None:
+                raise ValueError("a reader callback needs shape=(T, ny, nx) and dtype")
+            T, ny, nx = (int(v) for v in shape)
+            dt = np.dtype(dtype)
+        else:
+            source = np.ascontiguousarray(source) if not isinstance(source, np.memmap) else source
+            if source.dtype not in (np.float32, np.float64):
+                source = np.ascontiguousarray(source, dtype=np.float64)
+            if source.ndim != 3:
+                raise ValueError("the slab must be (time, lat, lon)")
+            T, ny, nx = source.shape
+            dt = source.dtype
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("the slab must be float32 or float64")
+        group = _group_ids(group, T)
+        cin = None if clim is None else np.ascontiguousarray(clim, dtype=dt)
+        if cin is not None and cin.shape != (ngroups, ny, nx):
+            raise ValueError("clim must have shape (ngroups, ny, nx)")
+        cout = np.empty((ngroups, ny, nx), dtype=dt) if want_clim else None
+        out = None
+        if sink is None:
+            out = sink = np.empty((T, ny, nx), dtype=dt)
+        elif sink is False:
+            sink = None
+            if cout is None:
+                raise ValueError("sink=False without want_clim asks for nothing")
+        elif not callable(sink):
+            if sink.dtype != dt or sink.shape != (T, ny, nx) or not sink.flags.c_contiguous:
+                raise ValueError("the sink array must be C-contiguous (T, ny, nx) of the slab's dtype")
+            out = sink
+        st = _seg_starts(segments if segments is not None else [])
+        mid = (group.ctypes.data, int(ngroups), int(window), int(smooth), st.ctypes.data if st.size else None, st.shape[0], _ptr(cin))
+        if not callable(source) and not callable(sink):
+            fn = L.ctk_anom_stream_f64 if dt == np.float64 else L.ctk_anom_stream_f32
+            check(fn(self._h, source.ctypes.data, T, ny, nx, *mid, _ptr(sink), _ptr(cout), int(chunk_steps)))
+            return out, cout
+        errors = []
+        ctype = C.c_float if dt == np.float32 else C.c_double
+
+        def rd(_user, t0, nt, dst):
+            try:
+                view = np.ctypeslib.as_array(C.cast(dst, C.POINTER(ctype)), shape=(nt, ny, nx))
+                if callable(source):
+                    source(int(t0), int(nt), view)
+                else:
+                    view[...] = source[t0:t0 + nt]
+                return 0
+            except BaseException as e:                    # an exception must not cross the C frames
+                errors.append(e)
+                return 1
+
+        def wr(_user, t0, nt, src):
+            try:
+                view = np.ctypeslib.as_array(C.cast(src, C.POINTER(ctype)), shape=(nt, ny, nx))
+                if callable(sink):
+                    sink(int(t0), int(nt), view)
+                else:
+                    sink[t0:t0 + nt] = view
+                return 0
+            except BaseException as e:
+                errors.append(e)
+                return 1
+        rcb = READ_CHUNK_FN(rd)
+        wcb = WRITE_CHUNK_FN(wr) if sink is not None else C.cast(None, WRITE_CHUNK_FN)
+        rc = L.ctk_anom_stream_cb(self._h, dt.itemsize, T, ny, nx, rcb, None, *mid, _ptr(cout), wcb, None, int(chunk_steps))
+        if errors:
+            raise errors[0]
+        check(rc)
+        return out, cout
+
+    def debug_anom_form(self):
+        """the kernel form of the last anomalies(segments=...) / anomalies_stream launch: 1 LDS ring, 0 plain, -1 none yet"""
+        v = C.c_int64(0)
+        check(lib().ctk_debug_anom_form(self._h, C.byref(v)))
+        return int(v.value)
 
     def resident_anom(self):
         T, ny, nx, f = C.c_int64(0), C.c_int(0), C.c_int(0), C.c_int(0)

@@ -242,6 +242,30 @@ def frequency_numpy(flag, group=None, above=0, percent=True, device=None):
     return out[0] if group is None else out
 
 
+def anomalies_numpy(x, group, ngroups=None, window=1, smooth=1, clim=None, segments=None, chunk_steps=None, device=None):
+    """calc_clim / calc_anom on a (time, lat, lon) float slab: `group` holds one id in [0, G) per timestep (G = ngroups, or
+    max(group) + 1), the climatology is the mean per group smoothed over `window` groups (or `clim`, (G, ny, nx)), the anomaly is
+    smoothed over `smooth` timesteps.  Returns (anom, clim) in the slab's dtype (float32 kept, anything else float64).
+    segments: int array of segment starts (0 first, strictly increasing) -- the smoothing does not cross a break (NaN where its
+    window would), the climatology is pooled over every segment.  chunk_steps: stream the slab (an array or np.memmap the host
+    holds) through chunk-sized device buffers, that many time steps at a time (0: about 256 MB each); same bits."""
+    x = np.asarray(x) if not isinstance(x, np.memmap) else x
+    if x.ndim != 3:
+        raise ValueError("x must be (time, lat, lon)")
+    if x.dtype.kind != "f":
+        if x.dtype.kind not in "iub":
+            raise TypeError("x must be a real numeric array")
+        x = x.astype(np.float64)
+    if group is None:
+        raise ValueError("group must hold one id per timestep")
+    ids, G = _native._groups(group, x.shape[0], ngroups)
+    starts = None if segments is None else segment_starts(segments, x.shape[0])
+    trk = _tracker(device)
+    if chunk_steps is None:
+        return trk.anomalies(x, ids, G, window=window, smooth=smooth, clim=clim, want_clim=True, segments=starts)
+    return trk.anomalies_stream(x, ids, G, window=window, smooth=smooth, clim=clim, chunk_steps=int(chunk_steps), segments=starts, want_clim=True)
+
+
 def percentile_groups_numpy(anom, rows, group, q, window=1, device=None):
     """the threshold recipe of README.rst:235-240 on a (time, lat, lon) float slab: per group g (one id in [0, G) per timestep,
     G = max(group) + 1, any order in time) the q-quantile of rows[0] <= y < rows[1] pooled over every timestep whose group lies in
@@ -642,29 +666,80 @@ class contrack(object):
         except TypeError:
             return type(like)(data, dims=dims, coords=coords, attrs=attrs or {})
 
-    def calc_clim(self, variable, window=1, groupby='dayofyear'):
+    def calc_clim(self, variable, window=1, groupby='dayofyear', segments=None, chunk_steps=None):
         """climatological mean per `groupby` value, smoothed with a centred running mean over `window` groups; NaNs of the
-        running mean (both ends of the axis) are replaced by the mean of the last `window` groups, as the reference does"""
-        slab, dims, sort = self._slab_tll(variable)
-        ids, uniq = self._group_ids(groupby)
-        if slab.dtype.kind != "f":
-            slab = slab.astype(np.float64)
-        _, clim = _tracker().anomalies(slab, ids, len(uniq), window=window, smooth=1, want_anom=False, want_clim=True)
+        running mean (both ends of the axis) are replaced by the mean of the last `window` groups, as the reference does.
+        segments (extension): as in run_contrack; with the name of a member dimension the variable is 4-D (any dim order) and the
+        climatology is pooled over all members (the ensemble climatology), over (groupby, lat, lon); breaks along time ('gaps',
+        start indices) do not change a climatology.  chunk_steps (extension): the variable is read slice by slice (`isel`) and
+        passes through chunk-sized device buffers, once; the slab is never built on the host."""
+        if segments is None and chunk_steps is None:
+            slab, dims, sort = self._slab_tll(variable)
+            ids, uniq = self._group_ids(groupby)
+            if slab.dtype.kind != "f":
+                slab = slab.astype(np.float64)
+            _, clim = _tracker().anomalies(slab, ids, len(uniq), window=window, smooth=1, want_anom=False, want_clim=True)
+        else:
+            self._ensure_set_up()
+            ids, uniq = self._group_ids(groupby)
+            source, shape, dtype, ids, _, _ = self._anom_source(variable, segments, chunk_steps, ids)
+            if chunk_steps is None:
+                _, clim = _tracker().anomalies(source, ids, len(uniq), window=window, smooth=1, want_anom=False, want_clim=True)
+            else:
+                _, clim = _tracker().anomalies_stream(source, ids, len(uniq), window=window, smooth=1, sink=False, shape=shape, dtype=dtype,
+                                                      chunk_steps=int(chunk_steps), want_clim=True)
         da = self.ds[variable]
         coords = {groupby: uniq}
         for name in (self._latitude_name, self._longitude_name):
             coords[name] = np.asarray(self.ds[name].data)
         return self._wrap(da, clim, (groupby, self._latitude_name, self._longitude_name), coords)
 
-    def calc_anom(self, variable, window=1, smooth=1, groupby='dayofyear', clim=None):
+    def _anom_source(self, variable, segments, chunk_steps, ids, only=None):
+        """what calc_clim / calc_anom hand to the tracker for `segments` / `chunk_steps`: (source, (steps, ny, nx), dtype, group ids
+        per flat step, segment starts or None, member dimension or None).  source is the (steps, ny, nx) float slab, or with
+        chunk_steps a reader of slices of the variable; a member dimension is flattened to steps m * T + t, the group of which is
+        the group of t.  only=m: member m alone (its T steps)."""
+        da = self.ds[variable]
+        dims = tuple(da.dims)
+        member, starts, T = self._segment_args(variable, da, dims, segments)
+        if member is not None:
+            M = da.shape[dims.index(member)]
+            if only is None:
+                ids = np.tile(ids, M)
+            if chunk_steps is not None:
+                return self._member_reader(da, dims, member, only) + (ids, starts, member)
+            sort4 = [dims.index(d) for d in (member, self._time_name, self._latitude_name, self._longitude_name)]
+            arr = np.asarray(da.data).transpose(sort4)
+            arr = arr.reshape((M * T,) + arr.shape[2:]) if only is None else arr[only]
+            slab = np.ascontiguousarray(arr, dtype=np.float32 if arr.dtype == np.float32 else np.float64)
+            return slab, slab.shape, slab.dtype, ids, starts, member
+        if chunk_steps is not None:
+            if len(dims) != 3:
+                raise ValueError("the variable {!r} must be 3-D (time, lat, lon in any order), it has dims {}".format(variable, dims))
+            return self._time_reader(da, dims) + (ids, starts, None)
+        slab = self._slab_tll(variable)[0]
+        slab = np.ascontiguousarray(slab, dtype=np.float32 if slab.dtype == np.float32 else np.float64)
+        return slab, slab.shape, slab.dtype, ids, starts, None
+
+    def calc_anom(self, variable, window=1, smooth=1, groupby='dayofyear', clim=None, segments=None, chunk_steps=None, pool=True):
         """adds the variable 'anom': departure of `variable` from its climatology (calc_clim, or the one given as `clim`:
         a labelled array over `groupby` on this grid, or the path of one), smoothed with a centred running mean over `smooth`
-        timesteps.  The slab also stays resident on the GPU: a following run_contrack(variable='anom') starts from HBM."""
+        timesteps.  The slab also stays resident on the GPU: a following run_contrack(variable='anom') starts from HBM.
+        segments (extension, the meaning it has in run_contrack): None -- one series, the smoothing crosses every break, as the
+        reference's does; 'gaps' or an int array of start indices -- the smoothing does not cross a break ('anom' is NaN where its
+        window would); the name of a member dimension -- the variable is 4-D in any dim order, the smoothing stays inside each
+        member, 'anom' gets the variable's own dims and the climatology is pooled over all members (pool=True, the ensemble
+        climatology) or is each member's own (pool=False: what xarray's grouped arithmetic gives on a 4-D variable, one call per
+        member).  The resident slab is not kept for member calls.
+        chunk_steps (extension): the variable is read slice by slice (`isel`, a chunk that spans two members in two pieces) and
+        passes through chunk-sized device buffers -- twice without `clim`, once with it; only 'anom' is built on the host and
+        nothing stays resident."""
         self._ensure_set_up()
-        slab, dims, sort = self._slab_tll(variable)
-        if slab.dtype.kind != "f":
-            slab = slab.astype(np.float64)
         ids, uniq = self._group_ids(groupby)
+        if segments is None and chunk_steps is None:
+            slab, dims, sort = self._slab_tll(variable)
+            if slab.dtype.kind != "f":
+                slab = slab.astype(np.float64)
         clim_arr = None
         if clim is None:
             logger.info('Calculating climatological mean from {}...'.format(variable))
@@ -687,12 +762,17 @@ class contrack(object):
                 raise ValueError("the climatology has no {} {} (present in {!r}); it covers {}..{}".format(
                     groupby, missing[:5] + (['...'] if len(missing) > 5 else []), variable, cvals.min(), cvals.max()))
             clim_arr = np.stack([carr[pos[v]] for v in uniq.tolist()])       # one plane per group value present in the data
-        anom, _ = _tracker().anomalies(slab, ids, len(uniq), window=window, smooth=smooth, clim=clim_arr, keep_resident=True)
         da = self.ds[variable]
         attrs = {'units': da.attrs['units'], 'long_name': da.attrs['long_name'] + ' Anomaly',
                  'standard_name': da.attrs['long_name'] + ' anomaly',
                  'history': ' '.join(['Calculated from {} with input attributes:', 'smoothing time steps = {},',
                                       'climatology = {}.']).format(variable, smooth, clim_txt)}
+        if segments is not None or chunk_steps is not None:
+            self.ds['anom'] = (tuple(da.dims), self._anom_segments(variable, ids, len(uniq), window, smooth, clim_arr, segments, chunk_steps, pool, attrs), attrs)
+            self._anom_resident = None
+            logger.info('Calculating Anomaly... DONE')
+            return
+        anom, _ = _tracker().anomalies(slab, ids, len(uniq), window=window, smooth=smooth, clim=clim_arr, keep_resident=True)
         anom.flags.writeable = False                         # (its twin stays in HBM for run_contrack: see _fingerprint)
         out = anom.transpose(np.argsort(sort))
         self.ds['anom'] = (dims, out, attrs)
@@ -700,6 +780,35 @@ class contrack(object):
         # the second and this instance's run_contrack goes back to its own host array)
         self._anom_resident = (_fingerprint(np.asarray(self.ds['anom'].data)), _tracker().resident_generation())
         logger.info('Calculating Anomaly... DONE')
+
+    def _anom_segments(self, variable, ids, G, window, smooth, clim_arr, segments, chunk_steps, pool, attrs):
+        """'anom' in the variable's own dim order for calc_anom's extensions; the history attribute names the segments"""
+        trk = _tracker()
+        dims = tuple(self.ds[variable].dims)
+
+        def one(only=None):
+            source, shape, dtype, gids, starts, member = self._anom_source(variable, segments, chunk_steps, ids, only)
+            if only is not None:
+                starts = None                                       # (a member alone is one series)
+            if chunk_steps is None:
+                return trk.anomalies(source, gids, G, window=window, smooth=smooth, clim=clim_arr, segments=starts)[0], starts, member
+            return trk.anomalies_stream(source, gids, G, window=window, smooth=smooth, clim=clim_arr, shape=shape, dtype=dtype,
+                                        chunk_steps=int(chunk_steps), segments=starts)[0], starts, member
+        member = self._segment_args(variable, self.ds[variable], dims, segments)[0]
+        if member is not None and not pool:
+            M = self.ds[variable].shape[dims.index(member)]
+            parts = [one(m) for m in range(M)]
+            anom, starts = np.concatenate([q[0] for q in parts]), np.arange(M)
+        else:
+            anom, starts, _ = one()
+        if segments is not None:
+            attrs['history'] += ', segments = {} ({}){}'.format(segments if isinstance(segments, str) else 'starts', 1 if starts is None else len(starts),
+                                                               '' if member is None or pool else ', climatology per member')
+        if member is not None:
+            sort4 = [dims.index(d) for d in (member, self._time_name, self._latitude_name, self._longitude_name)]
+            return anom.reshape((self.ds[variable].shape[dims.index(member)], -1) + anom.shape[1:]).transpose(np.argsort(sort4))
+        sort = [dims.index(d) for d in (self._time_name, self._latitude_name, self._longitude_name)]
+        return anom.transpose(np.argsort(sort))
 
     def _resident_for(self, variable, arr, shape, is_f64):
         """True if `variable` is this instance's anomaly and its twin is still the slab resident in HBM"""
@@ -710,7 +819,22 @@ class contrack(object):
         return res[0] == _fingerprint(np.asarray(arr)) and res[1] == trk.resident_generation() and \
             trk.resident_anom() == (shape[0], shape[1], shape[2], bool(is_f64))
 
-    def percentile_threshold(self, variable='anom', q=0.90, lat_bounds=(50, 80), groupby=None, window=1):
+    def _slab_pooled(self, variable, segments):
+        """((steps, lat, lon) slab, members) for the percentile entries: the variable itself (segments None), or a 4-D variable with
+        the member dimension `segments` flattened to (member * time, lat, lon) -- pooling over time is indifferent to the breaks"""
+        if segments is None:
+            return self._slab_tll(variable)[0], 1
+        if not isinstance(segments, str) or segments == 'gaps':
+            raise ValueError("segments={!r}: the percentile entries take the name of a member dimension (breaks along time do not "
+                             "change a percentile over time)".format(segments))
+        da = self.ds[variable]
+        dims = tuple(da.dims)
+        member = self._segment_args(variable, da, dims, segments)[0]
+        sort4 = [dims.index(d) for d in (member, self._time_name, self._latitude_name, self._longitude_name)]
+        arr = np.asarray(da.data).transpose(sort4)
+        return arr.reshape((-1,) + arr.shape[2:]), arr.shape[0]
+
+    def percentile_threshold(self, variable='anom', q=0.90, lat_bounds=(50, 80), groupby=None, window=1, segments=None):
         """the more objective threshold of the reference's README (README.rst:150-151):
         block[variable].sel(latitude=band).quantile([q], dim='time').mean() -- the mean over the latitude band of the
         per-grid-point q-quantile over time.  Evaluated on the GPU (exact order statistics, numpy's linear interpolation).
@@ -719,11 +843,13 @@ class contrack(object):
         time.<groupby> the q-quantile of the whole band pooled over every timestep whose group lies in the centred window of
         `window` groups around it (circular: 1 January sees late December), np.nanquantile in float64.  Returns a 1-D labelled
         array over `groupby` (the values present, ascending); with groupby='dayofyear' it can be given to
-        run_contrack(threshold=...) as it is."""
+        run_contrack(threshold=...) as it is.
+        segments (extension): the name of a member dimension of a 4-D variable -- the members are pooled: the variable is taken as
+        (member * time, lat, lon) and every member's steps carry the groups of the time axis."""
         if groupby is not None:
             _check_percentile_args(q, window)
         self._ensure_set_up()
-        slab, dims, sort = self._slab_tll(variable)
+        slab, M = self._slab_pooled(variable, segments)
         lat = np.asarray(self.ds[self._latitude_name].data, dtype=np.float64)
         rows = np.nonzero((lat >= min(lat_bounds)) & (lat <= max(lat_bounds)))[0]
         if len(rows) == 0 or not np.array_equal(rows, np.arange(rows[0], rows[-1] + 1)):
@@ -731,7 +857,9 @@ class contrack(object):
         if slab.dtype.kind != "f":
             slab = slab.astype(np.float64)
         ids, uniq = (None, None) if groupby is None else self._group_ids(groupby)
-        resident = self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, slab.shape, slab.dtype != np.float32)
+        if ids is not None and M > 1:
+            ids = np.tile(ids, M)
+        resident = segments is None and self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, slab.shape, slab.dtype != np.float32)
         if groupby is None:
             return _tracker().percentile(None if resident else slab, int(rows[0]), int(rows[-1]) + 1, q)
         vals = _tracker().percentile_groups(None if resident else slab, int(rows[0]), int(rows[-1]) + 1, ids, len(uniq), q, int(window))
@@ -744,15 +872,16 @@ class contrack(object):
             attrs['units'] = da.attrs['units']
         return self._wrap(da, vals, (groupby,), {groupby: uniq}, attrs, name='{}_q{:g}'.format(variable, float(q) * 100))
 
-    def percentile_field(self, variable='anom', q=0.90, groupby='dayofyear', window=1, lat_bounds=None):
+    def percentile_field(self, variable='anom', q=0.90, groupby='dayofyear', window=1, lat_bounds=None, segments=None):
         """the local definition of an extreme: per value of time.<groupby> and per grid point the q-quantile over every timestep
         whose group lies in the centred window of `window` groups around it (circular: 1 January sees late December),
         np.nanquantile in float64, evaluated exactly on the GPU.  Returns a labelled array over (groupby, latitude, longitude) on
         the whole grid (the group values present, ascending); rows outside lat_bounds (None: every row) are NaN and are never
-        flagged.  With groupby='dayofyear' it can be given to run_contrack(threshold=...) as it is."""
+        flagged.  With groupby='dayofyear' it can be given to run_contrack(threshold=...) as it is.
+        segments (extension): the name of a member dimension of a 4-D variable; the members are pooled as in percentile_threshold."""
         _check_percentile_args(q, window)
         self._ensure_set_up()
-        slab, dims, sort = self._slab_tll(variable)
+        slab, M = self._slab_pooled(variable, segments)
         lat = np.asarray(self.ds[self._latitude_name].data, dtype=np.float64)
         bounds = (lat.min(), lat.max()) if lat_bounds is None else lat_bounds
         rows = np.nonzero((lat >= min(bounds)) & (lat <= max(bounds)))[0]
@@ -761,7 +890,9 @@ class contrack(object):
         if slab.dtype.kind != "f":
             slab = slab.astype(np.float64)
         ids, uniq = self._group_ids(groupby)
-        resident = self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, slab.shape, slab.dtype != np.float32)
+        if M > 1:
+            ids = np.tile(ids, M)
+        resident = segments is None and self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, slab.shape, slab.dtype != np.float32)
         y0, y1 = int(rows[0]), int(rows[-1]) + 1
         band = _tracker().percentile_field(None if resident else slab, y0, y1, ids, len(uniq), q, int(window))
         vals = np.full((len(uniq),) + slab.shape[1:], np.nan)
@@ -861,6 +992,57 @@ class contrack(object):
             return prepare_thresholds(values, T, dtype)
         return prepare_thresholds(threshold, T, dtype)
 
+    def _segment_args(self, variable, da, dims, segments):
+        """`segments` as run_contrack documents it -> (name of the member dimension or None, segment starts or None, steps of the
+        time axis)"""
+        member = segments if isinstance(segments, str) and segments != 'gaps' else None
+        if member is not None:
+            if member not in dims:
+                raise ValueError("segments={!r}: the variable {!r} has no such dimension (dims {})".format(member, variable, dims))
+            if len(dims) != 4:
+                raise ValueError("segments={!r}: the variable must be 4-D ({!r}, time, lat, lon in any order), it has dims {}".format(member, member, dims))
+        T = da.shape[dims.index(self._time_name)]
+        if member is not None:
+            starts = np.arange(da.shape[dims.index(member)], dtype=np.int64) * T
+        elif isinstance(segments, str):
+            starts = gap_starts(self._time_steps())
+        else:
+            starts = None if segments is None else segment_starts(segments, T)
+        return member, starts, T
+
+    def _time_reader(self, da, dims):
+        """(reader(t0, nt, out), (T, ny, nx), dtype) of a 3-D variable read slice by slice along time (isel where there is one)"""
+        tname = self._time_name
+        sort = [dims.index(d) for d in (tname, self._latitude_name, self._longitude_name)]
+        shape = tuple(da.shape[i] for i in sort)
+        dtype = np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
+
+        def reader(t0, nt, out):
+            part = da.isel(**{tname: slice(t0, t0 + nt)}) if hasattr(da, "isel") else None
+            arr = np.asarray(part.data if part is not None else np.asarray(da.data).take(range(t0, t0 + nt), axis=dims.index(tname)))
+            out[...] = arr.transpose(sort)
+        return reader, shape, dtype
+
+    def _member_reader(self, da, dims, member, only=None):
+        """(reader, (M * T, ny, nx), dtype) of a 4-D variable: flat step m * T + t of the (M * T, lat, lon) series is step t of member
+        m, read as isel(member=m, time=slice) -- a chunk that spans two members in two pieces.  only=m: that member alone, (T, ny, nx)."""
+        tname = self._time_name
+        M, T = da.shape[dims.index(member)], da.shape[dims.index(tname)]
+        dims3 = tuple(d for d in dims if d != member)                             # what isel(member=m) leaves
+        sort3 = [dims3.index(d) for d in (tname, self._latitude_name, self._longitude_name)]
+        shape = ((M if only is None else 1) * T,) + tuple(da.shape[dims.index(d)] for d in (self._latitude_name, self._longitude_name))
+        dtype = np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
+
+        def reader(t0, nt, out):
+            done = 0
+            while done < nt:
+                m, t = divmod(t0 + done, T)
+                n = min(nt - done, T - t)
+                part = da.isel(**{member: m if only is None else only, tname: slice(t, t + n)})
+                out[done:done + n] = np.asarray(part.data).transpose(sort3)
+                done += n
+        return reader, shape, dtype
+
     def run_contrack(self, variable, threshold, gorl, overlap, persistence, twosided=True, chunk_steps=None, segments=None):
         """Spatial and temporal tracking of closed contours; adds the integer variable 'flag' to the dataset.
 
@@ -889,19 +1071,7 @@ class contrack(object):
         self._ensure_set_up()
         da = self.ds[variable]
         dims = tuple(da.dims)
-        member = segments if isinstance(segments, str) and segments != 'gaps' else None
-        if member is not None:
-            if member not in dims:
-                raise ValueError("segments={!r}: the variable {!r} has no such dimension (dims {})".format(member, variable, dims))
-            if len(dims) != 4:
-                raise ValueError("segments={!r}: the variable must be 4-D ({!r}, time, lat, lon in any order), it has dims {}".format(member, member, dims))
-        T = da.shape[dims.index(self._time_name)]
-        if member is not None:
-            starts = np.arange(da.shape[dims.index(member)], dtype=np.int64) * T
-        elif isinstance(segments, str):
-            starts = gap_starts(self._time_steps())
-        else:
-            starts = None if segments is None else segment_starts(segments, T)
+        member, starts, T = self._segment_args(variable, da, dims, segments)
         nseg = 1 if starts is None else len(starts)
         logger.info("\nRun ConTrack \n########### \n    threshold:    {} {} \n    overlap:      {} \n"
                     "    persistence:  {} time steps".format(gorl, threshold, overlap, persistence) +
@@ -1001,37 +1171,17 @@ class contrack(object):
         """run_contrack over an extra dimension with the variable read slice by slice: flat step m * T + t of the (M * T, lat, lon)
         series is step t of member m, read as isel(member=m, time=slice) -- a chunk that spans two members in two pieces; the
         flattened slab exists nowhere on the host.  Returns (flag (M*T, ny, nx), n)."""
-        tname = self._time_name
-        M, T = da.shape[dims.index(member)], da.shape[dims.index(tname)]
-        dims3 = tuple(d for d in dims if d != member)                             # what isel(member=m) leaves
-        sort3 = [dims3.index(d) for d in (tname, self._latitude_name, self._longitude_name)]
-        shape = (M * T,) + tuple(da.shape[dims.index(d)] for d in (self._latitude_name, self._longitude_name))
-        dtype = np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
+        M, T = da.shape[dims.index(member)], da.shape[dims.index(self._time_name)]
+        reader, shape, dtype = self._member_reader(da, dims, member)
         thr, field = self._member_threshold_args(threshold, member, M, T, dtype)
-
-        def reader(t0, nt, out):
-            done = 0
-            while done < nt:
-                m, t = divmod(t0 + done, T)
-                n = min(nt - done, T - t)
-                part = da.isel(**{member: m, tname: slice(t, t + n)})
-                out[done:done + n] = np.asarray(part.data).transpose(sort3)
-                done += n
         call = lambda t: trk.track_stream(reader, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, shape=shape, dtype=dtype,
                                           chunk_steps=chunk_steps, segments=starts)
         return call(thr) if field is None else _track_field(trk, field[0], field[1], call)
 
     def _run_streaming(self, trk, da, dims, sort, threshold, gorl, wrow, overlap, persistence, twosided, chunk_steps, starts=None):
         """run_contrack with the variable read slice by slice; starts: segment breaks of the call"""
-        shape = tuple(da.shape[i] for i in sort)                                  # (time, lat, lon)
-        dtype = np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
+        reader, shape, dtype = self._time_reader(da, dims)                         # shape: (time, lat, lon)
         thr, field = self._threshold_args(threshold, da.shape, sort, shape[0], dtype)
-        tname = self._time_name
-
-        def reader(t0, nt, out):
-            part = da.isel(**{tname: slice(t0, t0 + nt)}) if hasattr(da, "isel") else None
-            arr = np.asarray(part.data if part is not None else np.asarray(da.data).take(range(t0, t0 + nt), axis=dims.index(tname)))
-            out[...] = arr.transpose(sort)
         seg = {} if starts is None else {"segments": starts}        # (no segments: the call as it has always been made)
         call = lambda t: trk.track_stream(reader, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, shape=shape, dtype=dtype,
                                           chunk_steps=chunk_steps, **seg)

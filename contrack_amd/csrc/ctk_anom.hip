@@ -4,6 +4,8 @@
 //       resident in HBM for run_contrack (ctk_track_resident): the producer of the hot path's input no longer pays PCIe twice.
 //   N3  the percentile threshold of README.rst:150-151: per grid point of a latitude band the q-quantile over time (exact
 //       order statistics by radix selection, numpy's linear interpolation), then the mean over the band.
+//       Over independent time segments (members, seasons) and streamed through chunk-sized buffers: ctk_anom_seg.hip, which launches
+//       k_clim_raw / k_clim_roll from here unchanged and replaces k_anom by a form that reads every input once per tile.
 // The reference evaluates these with xarray, which cannot be installed in the build container: what is implemented is the
 // numpy restatement in oracle/anom_port.py (PARITY UNPINNED, see its header); sums in float64, results rounded to the input's
 // dtype where xarray keeps it.

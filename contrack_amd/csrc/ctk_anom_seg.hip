@@ -1,0 +1,380 @@
+// ctk_anom_seg.hip -- calc_clim / calc_anom (row N2, ctk_anom.hip) over independent time segments, resident and streamed (included by
+// ctk_api.hip).  The climatology is the one of ctk_anom_*: pooled over every timestep of a group whatever its segment.  The smoothing
+// stays inside a segment: anom[t] is the mean over the centred window of `smooth` steps only if that window lies inside t's segment,
+// else NaN -- as ctk_anom_* gives where the window leaves the axis.  Sums and rounding places are k_anom's, so one segment gives
+// ctk_anom_*'s bits.
+//
+// k_anom_ring: one thread per pixel and tile of output steps.  The thread walks the steps its tile needs once (tile + smooth - 1 of
+// them), computes each raw anomaly x[j] - clim[group[j]] once and keeps the last `smooth` of them in a ring in LDS (slot k of lane l at
+// ring[k * 256 + l]: consecutive lanes, consecutive banks); every output re-adds the ring from its oldest slot, which is k_anom's
+// order of additions.  x, group and clim are read once per step and tile instead of `smooth` times per output.  k_anom_plain is
+// k_anom with the segment test, for a smoothing whose ring does not fit (ctk_anom_plan, ctk_forms.h).
+// Both take the slab as a window: plane 0 of `x` is step xbase, steps [xlo, xhi) of it may be read; plane 0 of `out` is step o0.  The
+// resident entry passes the whole slab, the streamed entry a chunk with the smooth - 1 steps before it.
+//
+// Streamed (ctk_anom_stream_*): pass 1 adds each chunk into float64 sums and int32 counts per (group, pixel) kept in HBM (k_clim_acc;
+// a group's steps arrive in rising t and are added in that order: k_clim_raw's bits), k_clim_fin turns them into the raw group
+// means, k_clim_roll runs on them unchanged.  Pass 2 streams the chunks again through two windows of chunk + smooth - 1 steps; the
+// last smooth - 1 steps of a window are copied in front of the next one on the device, so the reader is never asked for a step twice
+// in a pass.  Output lags input by (smooth - 1) / 2 steps; the last chunk closes the gap.
+#pragma once
+
+template <typename VT>
+__global__ __launch_bounds__(CTK_ANOM_THREADS) void k_anom_ring(const VT *__restrict__ x, int64_t xbase, int64_t xlo, int64_t xhi, const VT *__restrict__ clim,
+                                                                const int32_t *__restrict__ group, const uint8_t *__restrict__ valid, int64_t npix, int smooth,
+                                                                int64_t o0, int64_t o1, int64_t tile, VT *__restrict__ out)
+{
+    extern __shared__ __align__(16) unsigned char an_ring_lds[];
+    VT *ring = (VT *)an_ring_lds + threadIdx.x;
+    const int64_t p = (int64_t)blockIdx.x * CTK_ANOM_THREADS + threadIdx.x;
+    if (p >= npix) return;                                                       // (no barrier below: a lane's ring is its own)
+    const int64_t t0 = o0 + (int64_t)blockIdx.y * tile, t1 = min(o1, t0 + tile);
+    const int back = smooth / 2, fwd = (smooth - 1) / 2;
+    int slot = 0;
+#pragma unroll 4
+    for (int64_t j = t0 - back; j < t1 + fwd; j++) {
+        if (j >= xlo && j < xhi)                                                 // (a step outside is in no valid window)
+            ring[slot * CTK_ANOM_THREADS] = (VT)((double)x[(j - xbase) * npix + p] - (double)clim[(int64_t)group[j] * npix + p]);
+        const int next = slot + 1 == smooth ? 0 : slot + 1;                       // the oldest slot: step j - (smooth - 1)
+        const int64_t t = j - fwd;
+        if (t >= t0) {
+            VT r = (VT)__builtin_nanf("");
+            if (valid[t]) {
+                double s = 0.0;
+                int k = next;
+                for (int i = 0; i < smooth; i++) { s += (double)ring[k * CTK_ANOM_THREADS]; k = k + 1 == smooth ? 0 : k + 1; }
+                r = (VT)(s / smooth);
+            }
+            out[(t - o0) * npix + p] = r;
+        }
+        slot = next;
+    }
+}
+
+template <typename VT>
+__global__ __launch_bounds__(CTK_ANOM_THREADS) void k_anom_plain(const VT *__restrict__ x, int64_t xbase, int64_t xlo, int64_t xhi, const VT *__restrict__ clim,
+                                                                 const int32_t *__restrict__ group, const uint8_t *__restrict__ valid, int64_t npix, int smooth,
+                                                                 int64_t o0, int64_t o1, int64_t tile, VT *__restrict__ out)
+{
+    const int64_t p = (int64_t)blockIdx.x * CTK_ANOM_THREADS + threadIdx.x;
+    if (p >= npix) return;
+    const int64_t t0 = o0 + (int64_t)blockIdx.y * tile, t1 = min(o1, t0 + tile);
+    for (int64_t t = t0; t < t1; t++) {
+        const int64_t lo = t - smooth / 2, hi = t + (smooth - 1) / 2;
+        VT r = (VT)__builtin_nanf("");
+        if (valid[t] && lo >= xlo && hi < xhi) {
+            double s = 0.0;
+            for (int64_t j = lo; j <= hi; j++) s += (double)(VT)((double)x[(j - xbase) * npix + p] - (double)clim[(int64_t)group[j] * npix + p]);
+            r = (VT)(s / smooth);
+        }
+        out[(t - o0) * npix + p] = r;
+    }
+}
+
+// sums / counts of the groups += the nt steps of a chunk (group: the chunk's ids).  Workgroup row y takes the groups g with
+// g % gridDim.y == y and walks the chunk in time order: the running sum of the group it is in stays in registers and goes back to HBM
+// when the group changes, so every (group, pixel) sum sees its steps in rising t, one addition each, as k_clim_raw's loop
+template <typename VT>
+__global__ __launch_bounds__(256) void k_clim_acc(const VT *__restrict__ x, const int32_t *__restrict__ group, int64_t nt, int64_t npix, double *__restrict__ sums,
+                                                  int32_t *__restrict__ counts)
+{
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= npix) return;
+    int cur = -1, c = 0;
+    double s = 0.0;
+    for (int64_t t = 0; t < nt; t++) {
+        const int g = group[t];
+        if (g % (int)gridDim.y != (int)blockIdx.y) continue;
+        if (g != cur) {
+            if (cur >= 0) { sums[(int64_t)cur * npix + p] = s; counts[(int64_t)cur * npix + p] = c; }
+            cur = g;
+            s = sums[(int64_t)g * npix + p]; c = counts[(int64_t)g * npix + p];
+        }
+        const VT v = x[t * npix + p];
+        if (!an_isnan(v)) { s += (double)v; c++; }
+    }
+    if (cur >= 0) { sums[(int64_t)cur * npix + p] = s; counts[(int64_t)cur * npix + p] = c; }
+}
+
+// raw[g][p] = the group mean of the sums (k_clim_raw's last line)
+template <typename VT>
+__global__ __launch_bounds__(256) void k_clim_fin(const double *__restrict__ sums, const int32_t *__restrict__ counts, int64_t n, VT *__restrict__ raw)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c = counts[i];
+    raw[i] = c ? (VT)(sums[i] / c) : (VT)__builtin_nanf("");
+}
+
+// ------------------------------------------------------------------------------------------------
+// host
+// ------------------------------------------------------------------------------------------------
+// valid[t] = the centred window of `smooth` steps around t lies inside t's segment (starts checked; none: one segment)
+static void anom_window_valid(const int64_t *starts, int64_t nseg, int64_t T, int smooth, std::vector<uint8_t> &valid)
+{
+    valid.assign((size_t)T, 0);
+    const int64_t one = 0;
+    if (nseg < 1) { starts = &one; nseg = 1; }
+    for (int64_t k = 0; k < nseg; k++) {
+        const int64_t s = starts[k], e = k + 1 < nseg ? starts[k + 1] : T;
+        for (int64_t t = s + smooth / 2; t + (smooth - 1) / 2 < e; t++) valid[(size_t)t] = 1;
+    }
+}
+
+static int anom_seg_check(const char *who, const void *h, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                          const int64_t *starts, int64_t nseg)
+{
+    if (!h || !group || T < 1 || ny < 1 || nx < 1 || ngroups < 1 || window < 1 || smooth < 1) return ctk_set_error(CTK_E_INVALID, "%s: bad arguments", who);
+    for (int64_t t = 0; t < T; t++)
+        if (group[t] < 0 || group[t] >= ngroups) return ctk_set_error(CTK_E_INVALID, "%s: group[%lld] = %d outside 0..%d", who, (long long)t, group[t], ngroups - 1);
+    return segment_starts_check(who, starts, nseg, T);
+}
+
+// anomalies of the output steps [o0, o1) on the handle's stream (the window arguments: see the kernels)
+template <typename VT>
+static int launch_anom_seg(ctk_handle *h, const VT *x, int64_t xbase, int64_t xlo, int64_t xhi, const VT *clim, const int32_t *group_dev, const uint8_t *valid_dev,
+                           int64_t npix, int smooth, int64_t o0, int64_t o1, VT *out)
+{
+    const CtkAnomPlan pl = ctk_anom_plan((int)sizeof(VT), smooth, o1 - o0, npix);
+    h->an_form = pl.form;
+    const dim3 grid(pl.gx, pl.gy);
+    if (pl.form == CTK_ANOM_RING)
+        k_anom_ring<VT><<<grid, CTK_ANOM_THREADS, pl.lds, h->stream>>>(x, xbase, xlo, xhi, clim, group_dev, valid_dev, npix, smooth, o0, o1, pl.tile, out);
+    else
+        k_anom_plain<VT><<<grid, CTK_ANOM_THREADS, 0, h->stream>>>(x, xbase, xlo, xhi, clim, group_dev, valid_dev, npix, smooth, o0, o1, pl.tile, out);
+    HIPCHK(hipGetLastError());
+    return CTK_OK;
+}
+
+// ctk_anom_* with segments: anom_impl's steps, the anomaly kernel replaced
+template <typename VT>
+static int anom_seg_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                         const VT *clim_in, VT *anom_out, VT *clim_out, int keep_resident, const int64_t *starts, int64_t nseg)
+{
+    if (h && (!x_host || (!anom_out && !clim_out && !keep_resident))) return ctk_set_error(CTK_E_INVALID, "ctk_anom_seg: bad arguments");
+    CTKCHK(anom_seg_check("ctk_anom_seg", h, T, ny, nx, group, ngroups, window, smooth, starts, nseg));
+    if (T > 0x7fffffffll) return ctk_set_error(CTK_E_INVALID, "ctk_anom_seg: T=%lld timesteps (at most 2^31 - 1)", (long long)T);
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const int64_t npix = (int64_t)ny * nx;
+    const size_t esz = sizeof(VT), n = (size_t)T * (size_t)npix, cb = (size_t)ngroups * npix * esz;
+    CTKCHK(ensure(h, h->io_in, n * esz));
+    CTKCHK(ensure(h, h->an_out, n * esz));
+    CTKCHK(ensure(h, h->an_clim, cb));
+    h->an_pct_n = -1;                                                  // (an_raw is overwritten below)
+    CTKCHK(ensure(h, h->an_raw, cb));
+    CTKCHK(ensure(h, h->an_idx, ((size_t)2 * T + ngroups + 2) * 4));
+    CTKCHK(ensure(h, h->an_valid, (size_t)T));
+    HIPCHK(hipMemcpy(h->io_in.p, x_host, n * esz, hipMemcpyHostToDevice));
+    std::vector<int32_t> idx((size_t)2 * T + ngroups + 1);
+    int32_t *tlist = idx.data(), *goff = tlist + T, *grp = goff + ngroups + 1;
+    steps_by_group(group, T, ngroups, tlist, goff);
+    memcpy(grp, group, (size_t)T * 4);
+    HIPCHK(hipMemcpy(h->an_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
+    const int32_t *d_tlist = P<int32_t>(h->an_idx), *d_goff = d_tlist + T, *d_grp = d_goff + ngroups + 1;
+    const unsigned gx = (unsigned)((npix + 255) / 256);
+    if (clim_in) {
+        HIPCHK(hipMemcpy(h->an_clim.p, clim_in, cb, hipMemcpyHostToDevice));
+    } else {
+        k_clim_raw<VT><<<dim3(gx, (unsigned)ngroups), 256, 0, s>>>((const VT *)h->io_in.p, d_tlist, d_goff, npix, (VT *)h->an_raw.p);
+        k_clim_roll<VT><<<dim3(gx, (unsigned)std::min(ngroups, 64)), 256, 0, s>>>((const VT *)h->an_raw.p, ngroups, window, npix, (VT *)h->an_clim.p);
+        HIPCHK(hipGetLastError());
+    }
+    if (clim_out) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipMemcpy(clim_out, h->an_clim.p, cb, hipMemcpyDeviceToHost)); }
+    if (anom_out || keep_resident) {
+        std::vector<uint8_t> valid;
+        anom_window_valid(starts, nseg, T, smooth, valid);
+        HIPCHK(hipMemcpy(h->an_valid.p, valid.data(), (size_t)T, hipMemcpyHostToDevice));
+        h->an_T = -1; h->an_gen++;                                     // the resident slab (if any) is being overwritten
+        CTKCHK(launch_anom_seg<VT>(h, (const VT *)h->io_in.p, 0, 0, T, (const VT *)h->an_clim.p, d_grp, P<uint8_t>(h->an_valid), npix, smooth, 0, T, (VT *)h->an_out.p));
+        HIPCHK(hipStreamSynchronize(s));
+        if (keep_resident) { h->an_T = T; h->an_ny = ny; h->an_nx = nx; h->an_f64 = sizeof(VT) == 8; }
+        if (anom_out) {
+            if (!h->bounce) h->bounce = new (std::nothrow) BouncePool();
+            if (!h->bounce || !bounce_copy(*h->bounce, h->device, h->an_out.p, anom_out, n * esz, false))
+                HIPCHK(hipMemcpy(anom_out, h->an_out.p, n * esz, hipMemcpyDeviceToHost));
+        }
+    }
+    return CTK_OK;
+}
+
+extern "C" int ctk_anom_seg_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                                const float *clim_in, float *anom_out, float *clim_out, int keep_resident, const int64_t *starts, int64_t nseg)
+{
+    return anom_seg_impl<float>(h, x, T, ny, nx, group, ngroups, window, smooth, clim_in, anom_out, clim_out, keep_resident, starts, nseg);
+}
+extern "C" int ctk_anom_seg_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                                const double *clim_in, double *anom_out, double *clim_out, int keep_resident, const int64_t *starts, int64_t nseg)
+{
+    return anom_seg_impl<double>(h, x, T, ny, nx, group, ngroups, window, smooth, clim_in, anom_out, clim_out, keep_resident, starts, nseg);
+}
+
+// test hook: the kernel form of the last ctk_anom_seg_* / ctk_anom_stream_* launch on this handle (CtkAnomForm; -1: none yet)
+extern "C" int ctk_debug_anom_form(ctk_handle *h, int64_t *form)
+{
+    if (!h || !form) return ctk_set_error(CTK_E_INVALID, "null argument");
+    *form = h->an_form;
+    return CTK_OK;
+}
+
+// ---- streamed ------------------------------------------------------------------------------------------------------------------
+// pass 2: the chunks pass through two windows [smooth - 1 steps kept from the chunk before | chunk] in io_in and two output buffers in
+// io_out; chunk k + 1 travels while the kernel works on chunk k and chunk k - 1 leaves
+template <typename VT>
+static int anom_stream_pass2(ctk_handle *h, StreamIO &io, int64_t T, int64_t npix, int smooth, const int32_t *group_dev, const uint8_t *valid_dev, const char *name)
+{
+    const size_t plane = (size_t)npix * sizeof(VT);
+    const int64_t chunk = io.chunk, halo = smooth - 1, fwd = (smooth - 1) / 2;
+    const size_t wbytes = (size_t)(chunk + halo) * plane, obytes = (size_t)(chunk + smooth) * plane;
+    const double t_pass = now_ms();
+    io.passes_in++;
+    if (io.host_out_v && !h->bounce) h->bounce = new (std::nothrow) BouncePool();
+    struct Pending { int64_t t0 = -1, nt = 0; int b = 0; } pend;
+    auto drain = [&](const Pending &q) -> int {                                  // output chunk q leaves the device
+        if (q.t0 < 0) return CTK_OK;
+        const double d0 = now_ms();
+        char *dev = (char *)h->io_out.p + (size_t)q.b * obytes;
+        HIPCHK(hipEventSynchronize(h->ev_rel[q.b]));
+        if (io.write_v) {
+            HIPCHK(hipMemcpyAsync(h->pin_out[q.b], dev, (size_t)q.nt * plane, hipMemcpyDeviceToHost, h->side[0]));
+            HIPCHK(hipEventRecord(h->ev_d2h[q.b], h->side[0]));
+            HIPCHK(hipEventSynchronize(h->ev_d2h[q.b]));
+            const double w0 = now_ms();
+            const int rc = io.write_v(io.write_user, q.t0, q.nt, h->pin_out[q.b]);
+            io.ms_write += now_ms() - w0;
+            if (rc) return ctk_set_error(CTK_E_INVALID, "%s: the writer returned %d for timesteps [%lld, %lld)", name, rc, (long long)q.t0, (long long)(q.t0 + q.nt));
+        } else {
+            char *dst = (char *)io.host_out_v + (size_t)q.t0 * plane;
+            if (!h->bounce || !bounce_copy(*h->bounce, h->device, dev, dst, (size_t)q.nt * plane, false))
+                HIPCHK(hipMemcpy(dst, dev, (size_t)q.nt * plane, hipMemcpyDeviceToHost));
+        }
+        io.ms_out += now_ms() - d0;
+        return CTK_OK;
+    };
+    int64_t o_done = 0;
+    int k = 0;
+    for (int64_t c0 = 0; c0 < T; c0 += chunk, k++) {
+        const int b = k & 1;
+        const int64_t nt = std::min<int64_t>(chunk, T - c0);
+        const bool last = c0 + nt == T;
+        char *win = (char *)h->io_in.p + (size_t)b * wbytes, *body = win + (size_t)halo * plane;
+        if (k >= 2) HIPCHK(hipEventSynchronize(h->ev_thr[b]));                 // the window (and its pinned twin) is free again
+        if (io.read) {
+            const double r0 = now_ms();
+            const int rc = io.read(io.read_user, c0, nt, h->pin_in[b]);
+            io.ms_read += now_ms() - r0;
+            if (rc) return ctk_set_error(CTK_E_INVALID, "%s: the reader returned %d for timesteps [%lld, %lld)", name, rc, (long long)c0, (long long)(c0 + nt));
+            HIPCHK(hipMemcpyAsync(body, h->pin_in[b], (size_t)nt * plane, hipMemcpyHostToDevice, h->copy_stream));
+        } else {
+            HIPCHK(hipMemcpyAsync(body, (const char *)io.host_in + (size_t)c0 * plane, (size_t)nt * plane, hipMemcpyHostToDevice, h->copy_stream));
+        }
+        HIPCHK(hipEventRecord(h->ev_h2d[b], h->copy_stream));
+        HIPCHK(hipStreamWaitEvent(h->stream, h->ev_h2d[b], 0));
+        // steps [c0 - halo, c0 + nt) are in the window now (the first chunk has nothing in front of it): the outputs whose window ends
+        // inside them, and everything that is left once the last chunk is there
+        const int64_t xlo = k == 0 ? 0 : c0 - halo, o0 = o_done, o1 = last ? T : std::max<int64_t>(o_done, c0 + nt - fwd);
+        if (o1 > o0) {
+            CTKCHK(launch_anom_seg<VT>(h, (const VT *)win, c0 - halo, xlo, c0 + nt, (const VT *)h->an_clim.p, group_dev, valid_dev, npix, smooth, o0, o1,
+                                       (VT *)((char *)h->io_out.p + (size_t)b * obytes)));
+            HIPCHK(hipEventRecord(h->ev_rel[b], h->stream));
+        }
+        // the last `halo` steps in front of the next chunk (a chunk that is not the last has nt == chunk >= halo steps: they lie in its body)
+        if (!last && halo > 0)
+            HIPCHK(hipMemcpyAsync((char *)h->io_in.p + (size_t)(b ^ 1) * wbytes, win + (size_t)nt * plane, (size_t)halo * plane, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipEventRecord(h->ev_thr[b], h->stream));
+        CTKCHK(drain(pend));
+        pend = Pending();
+        if (o1 > o0) { pend.t0 = o0; pend.nt = o1 - o0; pend.b = b; }
+        o_done = o1;
+    }
+    CTKCHK(drain(pend));
+    io.ms_in += now_ms() - t_pass - io.ms_out;
+    return CTK_OK;
+}
+
+template <typename VT>
+static int anom_stream_impl(ctk_handle *h, StreamIO &io, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                            const int64_t *starts, int64_t nseg, const VT *clim_in, VT *clim_out, int64_t chunk_steps, const char *name)
+{
+    const bool sink = io.host_out_v || io.write_v;
+    if (h && ((!io.host_in && !io.read) || (!sink && !clim_out) || chunk_steps < 0)) return ctk_set_error(CTK_E_INVALID, "%s: no source, nothing to produce or chunk_steps < 0", name);
+    CTKCHK(anom_seg_check(name, h, T, ny, nx, group, ngroups, window, smooth, starts, nseg));
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const int64_t npix = (int64_t)ny * nx;
+    const size_t plane = (size_t)npix * sizeof(VT), cb = (size_t)ngroups * plane, ng = (size_t)ngroups * (size_t)npix;
+    io.esz = sizeof(VT);
+    io.chunk = chunk_steps > 0 ? chunk_steps : std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / plane));
+    io.chunk = std::min<int64_t>(std::max<int64_t>(io.chunk, std::max<int64_t>(smooth - 1, 1)), T);       // (at least the halo: see pass 2)
+    const double t_call = now_ms();
+    CTKCHK(ensure(h, h->an_clim, cb));
+    h->an_pct_n = -1;                                                  // (an_raw is overwritten below)
+    CTKCHK(ensure(h, h->an_raw, cb));
+    CTKCHK(ensure(h, h->an_idx, (size_t)T * 4));
+    CTKCHK(stream_setup(h, (size_t)(io.chunk + smooth - 1) * plane, 0, io.read != nullptr));
+    if (sink) CTKCHK(stream_setup(h, 0, (size_t)(io.chunk + smooth) * plane, io.write_v != nullptr));
+    HIPCHK(hipMemcpy(h->an_idx.p, group, (size_t)T * 4, hipMemcpyHostToDevice));
+    const int32_t *d_grp = P<int32_t>(h->an_idx);
+    struct Sio { ctk_handle *h; ~Sio() { h->sio = nullptr; } } sio{h};
+    h->sio = &io;
+    const unsigned gx = (unsigned)((npix + 255) / 256);
+    if (clim_in) {
+        HIPCHK(hipMemcpy(h->an_clim.p, clim_in, cb, hipMemcpyHostToDevice));
+    } else {
+        CTKCHK(ensure(h, h->an_acc, ng * 12));
+        double *sums = P<double>(h->an_acc);
+        int32_t *counts = (int32_t *)(sums + ng);
+        HIPCHK(hipMemsetAsync(sums, 0, ng * 12, s));
+        const unsigned gy = (unsigned)std::min(ngroups, 32);
+        const int rc = stream_in(h, sizeof(VT) == 8, T, ny, nx, [&](const void *chunk, int64_t c0, int64_t nt) -> int {
+            k_clim_acc<VT><<<dim3(gx, gy), 256, 0, s>>>((const VT *)chunk, d_grp + c0, nt, npix, sums, counts);
+            HIPCHK(hipGetLastError());
+            return CTK_OK;
+        });
+        if (rc != CTK_OK) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamSynchronize(s); return rc; }      // (a reader gave up: nothing stays in flight)
+        k_clim_fin<VT><<<(unsigned)((ng + 255) / 256), 256, 0, s>>>(sums, counts, (int64_t)ng, (VT *)h->an_raw.p);
+        k_clim_roll<VT><<<dim3(gx, (unsigned)std::min(ngroups, 64)), 256, 0, s>>>((const VT *)h->an_raw.p, ngroups, window, npix, (VT *)h->an_clim.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));                               // (pass 2 reuses the chunk buffers)
+    }
+    if (clim_out) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipMemcpy(clim_out, h->an_clim.p, cb, hipMemcpyDeviceToHost)); }
+    if (sink) {
+        std::vector<uint8_t> valid;
+        anom_window_valid(starts, nseg, T, smooth, valid);
+        CTKCHK(ensure(h, h->an_valid, (size_t)T));
+        HIPCHK(hipMemcpy(h->an_valid.p, valid.data(), (size_t)T, hipMemcpyHostToDevice));
+        const int rc = anom_stream_pass2<VT>(h, io, T, npix, smooth, d_grp, P<uint8_t>(h->an_valid), name);
+        if (rc != CTK_OK) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamSynchronize(s); return rc; }
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    h->stream_ms[0] = io.ms_read; h->stream_ms[1] = io.ms_write; h->stream_ms[2] = io.ms_in; h->stream_ms[3] = io.ms_out;
+    h->ms[CTK_T_H2D] = io.ms_in; h->ms[CTK_T_D2H] = io.ms_out; h->ms[CTK_T_TOTAL] = now_ms() - t_call;
+    return CTK_OK;
+}
+
+extern "C" int ctk_anom_stream_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                                   const int64_t *starts, int64_t nseg, const float *clim_in, float *anom_out, float *clim_out, int64_t chunk_steps)
+{
+    StreamIO io;
+    io.host_in = x; io.host_out_v = anom_out;
+    return anom_stream_impl<float>(h, io, T, ny, nx, group, ngroups, window, smooth, starts, nseg, clim_in, clim_out, chunk_steps, "ctk_anom_stream_f32");
+}
+extern "C" int ctk_anom_stream_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                                   const int64_t *starts, int64_t nseg, const double *clim_in, double *anom_out, double *clim_out, int64_t chunk_steps)
+{
+    StreamIO io;
+    io.host_in = x; io.host_out_v = anom_out;
+    return anom_stream_impl<double>(h, io, T, ny, nx, group, ngroups, window, smooth, starts, nseg, clim_in, clim_out, chunk_steps, "ctk_anom_stream_f64");
+}
+extern "C" int ctk_anom_stream_cb(ctk_handle *h, int elem_bytes, int64_t T, int ny, int nx, ctk_read_chunk_fn reader, void *reader_user, const int32_t *group,
+                                  int ngroups, int window, int smooth, const int64_t *starts, int64_t nseg, const void *clim_in, void *clim_out,
+                                  ctk_write_values_fn writer, void *writer_user, int64_t chunk_steps)
+{
+    if (elem_bytes != 4 && elem_bytes != 8) return ctk_set_error(CTK_E_INVALID, "ctk_anom_stream_cb: elem_bytes must be 4 (float32) or 8 (float64)");
+    if (h && !reader) return ctk_set_error(CTK_E_INVALID, "ctk_anom_stream_cb: null reader");
+    StreamIO io;
+    io.read = reader; io.read_user = reader_user; io.write_v = writer; io.write_user = writer_user;
+    if (elem_bytes == 8)
+        return anom_stream_impl<double>(h, io, T, ny, nx, group, ngroups, window, smooth, starts, nseg, (const double *)clim_in, (double *)clim_out, chunk_steps, "ctk_anom_stream_cb");
+    return anom_stream_impl<float>(h, io, T, ny, nx, group, ngroups, window, smooth, starts, nseg, (const float *)clim_in, (float *)clim_out, chunk_steps, "ctk_anom_stream_cb");
+}

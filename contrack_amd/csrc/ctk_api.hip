@@ -225,6 +225,8 @@ struct StreamIO {
     int32_t *host_out = nullptr;
     ctk_write_chunk_fn write = nullptr;
     void *write_user = nullptr;
+    void *host_out_v = nullptr;                    // ctk_anom_stream_*: the sink holds values of the slab's type, as an array or
+    ctk_write_values_fn write_v = nullptr;         // through a writer of values
     int64_t chunk = 0;                             // timesteps per chunk
     size_t esz = 4;
     double ms_read = 0, ms_write = 0, ms_in = 0, ms_out = 0;
@@ -277,6 +279,8 @@ struct ctk_handle {
     bool guard_on = false;                         // kernels behind the resolver check the device counters before touching the tables
     // calc_anom / percentile (ctk_anom.hip): resident anomaly slab, climatology, scratch
     DevBuf an_out, an_clim, an_raw, an_idx;
+    DevBuf an_acc, an_valid;                       // ctk_anom_stream_*: float64 sums + int32 counts per (group, pixel); ctk_anom_seg_*: window-inside-segment per step
+    int an_form = -1;                              // kernel form the last ctk_anom_seg_* / ctk_anom_stream_* call took (CtkAnomForm; -1: none yet)
     int64_t an_T = -1; int an_ny = 0, an_nx = 0; bool an_f64 = false;
     uint64_t an_gen = 0;                           // bumped whenever the resident slab is written or dropped: WHICH slab is resident
     int64_t an_pct_n = -1;                         // an_raw holds the per-pixel quantiles of the last ctk_percentile_* call (-1: it does not)
@@ -567,7 +571,7 @@ extern "C" void ctk_destroy(ctk_handle *h)
                       &h->rv_cand_cnt, &h->rv_cand_off, &h->rv_cand, &h->rv_cand_scratch, &h->rv_seam_res, &h->rv_scalars, &h->rv_mark, &h->rv_inv, &h->rv_ff,
                       &h->lc_rows, &h->lc_cnt, &h->lc_wlo, &h->lc_whi, &h->lc_w, &h->rv_dmap, &h->rv_dorig, &h->rv_dbox, &h->rv_inex, &h->rv_touch, &h->io_in, &h->io_out,
                       &h->sh_mask_next, &h->sh_send, &h->sh_recv, &h->sh_prev, &h->sh_elist, &h->sh_ovr_slot, &h->sh_ovr_val,
-                      &h->sh_amb_list, &h->sh_counts, &h->sh_cl_shared, &h->sh_cl_sent, &h->chunk_vals, &h->lc_work, &h->lc_ovf, &h->lc_ekeys, &h->lc_offs, &h->lc_sw, &h->lc_sp, &h->lc_out, &h->lc_cross, &h->lc_gtab, &h->lc_occ, &h->lc_cp, &h->an_out, &h->an_clim, &h->an_raw, &h->an_idx, &h->sd_parent, &h->sd_tmin, &h->sd_tmax, &h->sd_root, &h->sd_nops, &h->sd_lbox, &h->rv_pstate, &h->ci_bsum, &h->scan_bsum,
+                      &h->sh_amb_list, &h->sh_counts, &h->sh_cl_shared, &h->sh_cl_sent, &h->chunk_vals, &h->lc_work, &h->lc_ovf, &h->lc_ekeys, &h->lc_offs, &h->lc_sw, &h->lc_sp, &h->lc_out, &h->lc_cross, &h->lc_gtab, &h->lc_occ, &h->lc_cp, &h->an_out, &h->an_clim, &h->an_raw, &h->an_idx, &h->an_acc, &h->an_valid, &h->sd_parent, &h->sd_tmin, &h->sd_tmax, &h->sd_root, &h->sd_nops, &h->sd_lbox, &h->rv_pstate, &h->ci_bsum, &h->scan_bsum,
                       &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order, &h->fq_counts, &h->fq_group, &h->seg_edge, &h->pc_hist, &h->pc_buf, &h->pf_out, &h->pf_idx};
     for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (h->h_blob) (void)hipHostFree(h->h_blob);
@@ -934,11 +938,9 @@ static int segment_table(ctk_handle *h, int64_t T)
 }
 
 // Segment starts given as an ARGUMENT of a call (the streaming and time-shard entries, ctk_track_*_seg_*): the rules of
-// ctk_set_segments, the last start below the `T_total` steps of the whole slab, and no sticky segments on the handle beside them.
-static int segment_args_check(const ctk_handle *h, const char *who, const int64_t *starts, int64_t nseg, int64_t T_total)
+// ctk_set_segments and the last start below the `T_total` steps of the whole slab (also ctk_anom_seg_* / ctk_anom_stream_*).
+static int segment_starts_check(const char *who, const int64_t *starts, int64_t nseg, int64_t T_total)
 {
-    if (!h->seg_starts.empty())
-        return ctk_set_error(CTK_E_INVALID, "%s: segments are set on this handle (ctk_set_segments) and given as an argument; clear the handle's first", who);
     if (nseg < 0 || (nseg > 0 && !starts)) return ctk_set_error(CTK_E_INVALID, "%s: bad segment arguments (nseg=%lld)", who, (long long)nseg);
     if (nseg == 0) return CTK_OK;
     if (starts[0] != 0) return ctk_set_error(CTK_E_INVALID, "%s: segment starts[0] = %lld, must be 0", who, (long long)starts[0]);
@@ -949,6 +951,13 @@ static int segment_args_check(const ctk_handle *h, const char *who, const int64_
     if (starts[nseg - 1] >= T_total)
         return ctk_set_error(CTK_E_INVALID, "%s: the last segment starts at step %lld, the slab has %lld steps", who, (long long)starts[nseg - 1], (long long)T_total);
     return CTK_OK;
+}
+// ... for the track entries: and no sticky segments on the handle beside them
+static int segment_args_check(const ctk_handle *h, const char *who, const int64_t *starts, int64_t nseg, int64_t T_total)
+{
+    if (!h->seg_starts.empty())
+        return ctk_set_error(CTK_E_INVALID, "%s: segments are set on this handle (ctk_set_segments) and given as an argument; clear the handle's first", who);
+    return segment_starts_check(who, starts, nseg, T_total);
 }
 
 // The edge table of the (checked) starts `st` over a slab of T_total steps; the steps [t_begin, t_begin + T) of it -- a time shard, or
@@ -3679,6 +3688,7 @@ extern "C" int ctk_lifecycle_rows(ctk_handle *h, ctk_life_row *rows, int64_t cap
 
 #include "ctk_sharded.hip"
 #include "ctk_anom.hip"
+#include "ctk_anom_seg.hip"
 #include "ctk_freq.hip"
 #include "ctk_pctl.hip"
 #include "ctk_pfield.hip"

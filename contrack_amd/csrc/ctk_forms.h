@@ -455,3 +455,38 @@ inline CtkPfieldPlan ctk_pfield_plan(int keybytes, int64_t max_pool_steps, int G
     }
     return p;
 }
+
+// ------------------------------------------------------------------------------------------------
+// segmented anomalies (ctk_anom_seg.hip): k_anom_ring keeps the last `smooth` raw anomalies of a thread's pixel in LDS while it walks
+// its time tile; k_anom_plain re-reads the window from memory for a smoothing whose ring does not fit
+// ------------------------------------------------------------------------------------------------
+#define CTK_ANOM_THREADS 256
+#define CTK_ANOM_RING_BYTES 32768     // ring of a workgroup: five workgroups (20 waves) per CU; float32 smooth <= 32, float64 <= 16
+#define CTK_ANOM_TILE_MIN 32          // output steps per workgroup: the ring form reads smooth - 1 halo steps per tile on top of them
+#define CTK_ANOM_TILE_MAX 256
+#define CTK_ANOM_WAVES 16384          // waves that fill 256 CUs several times over (as k_freq)
+enum CtkAnomForm { CTK_ANOM_PLAIN = 0, CTK_ANOM_RING = 1 };
+struct CtkAnomPlan {
+    int form;                     // CtkAnomForm
+    size_t lds;                   // dynamic LDS of the launch (ring form)
+    int64_t tile;                 // output steps per workgroup
+    unsigned gx, gy;
+};
+// nt output steps of a plane of npix pixels
+inline CtkAnomPlan ctk_anom_plan(int elem_bytes, int smooth, int64_t nt, int64_t npix)
+{
+    CtkAnomPlan p = {};
+    p.lds = (size_t)smooth * CTK_ANOM_THREADS * (size_t)elem_bytes;
+    p.form = p.lds <= CTK_ANOM_RING_BYTES ? CTK_ANOM_RING : CTK_ANOM_PLAIN;
+    if (p.form == CTK_ANOM_PLAIN) p.lds = 0;
+    const int64_t waves = (npix + 63) / 64;
+    // the longest tile that still leaves CTK_ANOM_WAVES waves, at least 8 x the halo so that it stays below an eighth of the reads
+    int64_t tile = std::max<int64_t>(1, nt * waves / CTK_ANOM_WAVES);
+    tile = std::min<int64_t>(CTK_ANOM_TILE_MAX, std::max<int64_t>(tile, std::max<int64_t>(CTK_ANOM_TILE_MIN, 8 * (int64_t)(smooth - 1))));
+    if (p.form == CTK_ANOM_PLAIN) tile = CTK_ANOM_TILE_MIN;
+    tile = std::max(tile, (nt + 65534) / 65535);                                       // gridDim.y <= 65535
+    p.tile = tile;
+    p.gx = (unsigned)((npix + CTK_ANOM_THREADS - 1) / CTK_ANOM_THREADS);
+    p.gy = (unsigned)std::max<int64_t>(1, (nt + tile - 1) / tile);
+    return p;
+}

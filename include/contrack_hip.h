@@ -433,6 +433,36 @@ int ctk_anom_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, const
                  const float *clim_in, float *anom_out, float *clim_out, int keep_resident);
 int ctk_anom_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
                  const double *clim_in, double *anom_out, double *clim_out, int keep_resident);
+/* ctk_anom_* over independent time segments (ensemble members, seasons): starts / nseg follow the rules of ctk_set_segments (0 first,
+ * strictly increasing) with the last start below T -- CTK_E_INVALID with a message otherwise, the handle stays usable; NULL / 0 is
+ * one segment.  The climatology is unchanged: pooled over every timestep of a group whatever its segment, summed in rising t.  The
+ * smoothing stays inside a segment: anom[t] is the mean over [t - smooth / 2, t + (smooth - 1) / 2] only if that window lies inside t's
+ * segment, NaN otherwise (as ctk_anom_* where the window leaves the axis).  Sums and rounding places are ctk_anom_*'s: one segment
+ * gives its bits.  keep_resident as in ctk_anom_*.  Each step of x, group and clim is read once per tile of output steps (plus the
+ * smooth - 1 steps around the tile) instead of `smooth` times per output while the last `smooth` raw anomalies of a pixel fit the
+ * workgroup's LDS (float32: smooth <= 32, float64: <= 16; ctk_anom_plan, csrc/ctk_forms.h), a plain form beyond. */
+int ctk_anom_seg_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                     const float *clim_in, float *anom_out, float *clim_out, int keep_resident, const int64_t *starts, int64_t nseg);
+int ctk_anom_seg_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                     const double *clim_in, double *anom_out, double *clim_out, int keep_resident, const int64_t *starts, int64_t nseg);
+/* ... streamed: the slab passes through chunk-sized device buffers and is never held in HBM -- a few chunks, ngroups * ny * nx * 12
+ * bytes of float64 sums and int32 counts, and the climatology.  ctk_anom_stream_f32 / _f64: host array in, host array out (anom_out
+ * NULL: the climatology only); ctk_anom_stream_cb: a reader (ctk_read_chunk_fn, elements of elem_bytes) and a writer of values, which
+ * receives the anomalies of [t0, t0 + nt) in pinned memory valid during the call (writer NULL: the climatology only).
+ *   pass 1 (skipped when clim_in is given): the chunks in increasing t0 are added into the sums; group means, then the rolling mean;
+ *   pass 2 (skipped without a sink): the chunks again; the smooth - 1 steps between neighbouring chunks stay on the device.
+ * The reader sees two passes without clim_in and one with it, each over non-overlapping ranges in increasing t0 that cover every
+ * step once; the writer gets every step once in increasing t0 (its chunks lag the reader's by (smooth - 1) / 2 steps, the last one
+ * closes the gap).  A nonzero return of either callback ends the call with CTK_E_INVALID.  chunk_steps = 0: about 256 MB per chunk;
+ * a chunk_steps below smooth - 1 is raised to smooth - 1.  Result: ctk_anom_seg_* on the whole slab bit for bit, for every chunk_steps. */
+typedef int (*ctk_write_values_fn)(void *user, int64_t t0, int64_t nt, const void *src);
+int ctk_anom_stream_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                        const int64_t *starts, int64_t nseg, const float *clim_in, float *anom_out, float *clim_out, int64_t chunk_steps);
+int ctk_anom_stream_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                        const int64_t *starts, int64_t nseg, const double *clim_in, double *anom_out, double *clim_out, int64_t chunk_steps);
+int ctk_anom_stream_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, int64_t T, int ny, int nx, ctk_read_chunk_fn reader, void *reader_user,
+                       const int32_t *group, int ngroups, int window, int smooth, const int64_t *starts, int64_t nseg, const void *clim_in,
+                       void *clim_out, ctk_write_values_fn writer, void *writer_user, int64_t chunk_steps);
 int ctk_resident_anom(ctk_handle *h, int64_t *T, int *ny, int *nx, int *is_f64);       /* T = -1: nothing resident */
 /* identity of the resident slab: changes whenever a ctk_anom_* call writes anomalies or ctk_release_io drops them.  Remember it
  * after the call that left YOUR slab resident and use the slab only while it is unchanged. */

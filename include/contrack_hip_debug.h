@@ -144,6 +144,10 @@ int ctk_debug_percentile_groups_sweeps(ctk_handle *h, int64_t *sweeps);
 int ctk_debug_time_percentile_groups(ctk_handle *h, const float *x_dev, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group, int ngroups,
                                      int window, double q, int reps, double *out, double *ms12);
 
+/* test hook: the kernel form of the last ctk_anom_seg_* / ctk_anom_stream_* launch on this handle: 1 the LDS ring (k_anom_ring), 0 the
+ * plain form (k_anom_plain), -1 none yet (ctk_anom_plan, csrc/ctk_forms.h) */
+int ctk_debug_anom_form(ctk_handle *h, int64_t *form);
+
 /* what ctk_pfield_plan (csrc/ctk_forms.h) decides for keys of `keybytes` (4 / 8) bytes, a longest pool of max_pool_steps timesteps,
  * ngroups and window: out4 = { form (0 direct, 1 ring), the ring form's cap in pool timesteps, pixels per workgroup, bytes of the ring
  * (0: direct form) }.  Host only: no handle, no GPU. */
