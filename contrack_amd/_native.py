@@ -33,6 +33,7 @@ EXPORTS = [
     "ctk_track_sharded_f32_dev", "ctk_track_sharded_f64_dev",
     "ctk_anom_f32", "ctk_anom_f64", "ctk_resident_anom", "ctk_resident_anom_generation", "ctk_track_resident", "ctk_percentile_f32", "ctk_percentile_f64", "ctk_debug_percentile_values",
     "ctk_lifecycle_f32", "ctk_lifecycle_f64", "ctk_lifecycle_f32_dev", "ctk_lifecycle_f64_dev", "ctk_lifecycle_rows", "ctk_lifecycle_exact",
+    "ctk_debug_lifecycle_plan", "ctk_debug_lifecycle_path",
     "ctk_track_stream_f32", "ctk_track_stream_f64", "ctk_track_stream_cb", "ctk_stream_times",
     "ctk_set_threshold_field", "ctk_set_segments",
     "ctk_track_stream_seg_f32", "ctk_track_stream_seg_f64", "ctk_track_stream_seg_cb", "ctk_track_sharded_seg_f32_dev", "ctk_track_sharded_seg_f64_dev",
@@ -80,6 +81,14 @@ def debug_percentile_field_plan(keybytes, max_pool_steps, ngroups, window):
     v = np.zeros(4, dtype=np.int64)
     check(lib().ctk_debug_percentile_field_plan(int(keybytes), int(max_pool_steps), int(ngroups), int(window), v.ctypes.data))
     return dict(form=int(v[0]), cap=int(v[1]), tile=int(v[2]), ring_bytes=int(v[3]))
+
+
+def debug_lifecycle_plan(T, ny, nx, f64=False, flag_align=0, field_align=0):
+    """ctk_debug_lifecycle_plan: what ctk_life_plan (csrc/ctk_forms.h) decides for slabs that start flag_align / field_align bytes past
+    a 32-byte boundary, as a dict (rw rows per wave, nsx strips per row, nby workgroups per strip, vec, ks); no handle, no GPU"""
+    v = np.zeros(5, dtype=np.int64)
+    check(lib().ctk_debug_lifecycle_plan(int(T), int(ny), int(nx), int(bool(f64)), int(flag_align), int(field_align), v.ctypes.data))
+    return dict(rw=int(v[0]), nsx=int(v[1]), nby=int(v[2]), vec=int(v[3]), ks=int(v[4]))
 
 
 def forms(T, ny, nx, nt=None, aligned16=True, async_passes=24, n_cus=256, **query):
@@ -192,6 +201,8 @@ def lib():
         getattr(L, name).argtypes = [p, p, p, i64, i32, i32, p, C.POINTER(i64)]
     L.ctk_lifecycle_rows.argtypes = [p, p, i64]
     L.ctk_lifecycle_exact.argtypes = [p, p, i64, p]
+    L.ctk_debug_lifecycle_plan.argtypes = [i64, i32, i32, i32, i64, i64, p]
+    L.ctk_debug_lifecycle_path.argtypes = [p, p, p, i64]
     for name in ("ctk_anom_f32", "ctk_anom_f64"):
         getattr(L, name).argtypes = [p, p, i64, i32, i32, p, i32, i32, i32, p, p, p, i32]
     for name in ("ctk_anom_seg_f32", "ctk_anom_seg_f64"):
@@ -1207,6 +1218,14 @@ class Tracker:
         out = np.empty(len(idx), dtype=LIFE_EXACT)
         check(lib().ctk_lifecycle_exact(self._h, idx.ctypes.data, len(idx), out.ctypes.data))
         return out
+
+    def debug_lifecycle_path(self, T):
+        """test hook: the path of the last lifecycle call (of T time steps) as (dict(rw, nsx, nby, vec, given_up, launches, attempts,
+        sort), steps) -- steps[t]: rounds of k_lifecycle time step t took part in, 0 = the strip kernels held it"""
+        v = np.zeros(8, dtype=np.int64)
+        steps = np.zeros(max(int(T), 1), dtype=np.uint8)
+        check(lib().ctk_debug_lifecycle_path(self._h, v.ctypes.data, steps.ctypes.data, int(T)))
+        return dict(zip("rw nsx nby vec given_up launches attempts sort".split(), (int(x) for x in v))), steps[:int(T)]
 
     def lifecycle_dev(self, flag_dev, field_dev, T, ny, nx, wrow, f64=False):
         wrow = np.ascontiguousarray(wrow, dtype=np.float32)

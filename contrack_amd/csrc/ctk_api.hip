@@ -261,7 +261,11 @@ struct ctk_handle {
     DevBuf lc_rows, lc_cnt, lc_wlo, lc_whi, lc_w, lc_work, lc_ovf, lc_ekeys, lc_offs, lc_sw, lc_sp, lc_out, lc_cross, lc_gtab, lc_occ, lc_cp;
     const int32_t *lc_flag = nullptr; const void *lc_field = nullptr;       // slabs of the last ctk_lifecycle_* call (for the exact rows)
     bool lc_f64 = false; int64_t lc_T = 0; int lc_ny = 0, lc_nx = 0;
-    DevBuf chunk_vals;                             // run values in the chunk order of k_relabel_v4
+    // which path the time steps of the last ctk_lifecycle_* call took (ctk_debug_lifecycle_path); lc_path_T < 0: no finished call
+    int64_t lc_path_T = -1; CtkLifePlan lc_plan = {0, 0, 0, 0, 0};
+    int64_t lc_given_up = 0, lc_fb_launches = 0; int lc_attempts = 0, lc_sort = 0;
+    std::vector<uint8_t> lc_rounds;                // per time step: rounds of k_lifecycle it took part in
+    DevBuf chunk_vals;                            // run values in the chunk order of k_relabel_v4
     // fused one-call path (ctk_seam_dev.hip): clusters of candidate labels, cluster root per group record; the pass runs without a
     // host hand-off and is validated from a device-written block of scalars after its only synchronisation
     DevBuf sd_parent, sd_tmin, sd_tmax, sd_root, sd_nops, sd_lbox, rv_pstate, ci_bsum, scan_bsum;
@@ -3411,17 +3415,7 @@ extern "C" int ctk_debug_label2d(ctk_handle *h, int before_seam, int32_t *lab)
 // ------------------------------------------------------------------------------------------------
 static_assert(sizeof(ctk_life_row) == sizeof(CtkLifeRowDev), "row layouts must agree");
 
-// Rows per wave of k_life_strips: four waves (one workgroup) cover a band of the strip, `g` bands cover the ny rows without idle
-// waves at the end (181 rows: 4 x 46; 721 rows: 20 x 37).  Measured (us, 2707 x 181 x 360 | 480 x 721 x 1440): 16 rows 316 | 509,
-// 23: 291 | 474, 31: 379 (a quarter of the waves idle) | 441, 37: | 436, 46: 281 | 458, 61: | 433 -- long streams per wave, as long
-// as the launch keeps a few thousand workgroups.
-static int life_rows_per_wave(int64_t T, int ny, int nx)
-{
-    const int64_t nsx = (nx + LB_SW - 1) / LB_SW;
-    int g = std::max(1, (ny + 80) / 160);
-    while (T * nsx * g < 2048 && (ny + 4 * g - 1) / (4 * g) > 8) g++;
-    return std::max(1, (ny + 4 * g - 1) / (4 * g));
-}
+static_assert(CTK_LIFE_SW == LB_SW && CTK_LIFE_WAVES == LB_THREADS / 64, "ctk_forms.h restates the strip shape of ctk_lifecycle.hip");
 
 static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void *field_dev, bool f64, int64_t T, int ny, int nx, const float *wrow,
                               int64_t *nrows)
@@ -3432,8 +3426,12 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
     if (ny > 65535 || nx > 65535 || T > 4000000) return ctk_set_error(CTK_E_RANGE, "ctk_lifecycle: grid %d x %d x %lld beyond the supported size", ny, nx, (long long)T);
     HIPCHK(hipSetDevice(h->device));
     h->lc_host.clear();
+    h->lc_path_T = -1;
+    h->lc_plan = CtkLifePlan{0, 0, 0, 0, 0};
+    h->lc_given_up = 0; h->lc_fb_launches = 0; h->lc_attempts = 0; h->lc_sort = 0;
+    h->lc_rounds.assign((size_t)T, 0);
     if (nrows) *nrows = 0;
-    if (T == 0) return CTK_OK;
+    if (T == 0) { h->lc_path_T = 0; return CTK_OK; }
     std::vector<int64_t> wlo(ny), whi(ny);
     int32_t wshift = 0, limb_bits = 0;
     CTKCHK(ctk_weights_to_limbs(wrow, ny, (int64_t)ny * nx, wlo.data(), whi.data(), &wshift, &limb_bits));
@@ -3446,7 +3444,9 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
     HIPCHK(hipMemcpyAsync(h->lc_w.p, wrow, (size_t)ny * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));          // wlo / whi are stack-lifetime vectors
     const int nxw = (nx + 31) / 32;
-    const int ks = std::max(1, std::min(32, 32768 / (nxw * 4)));
+    const CtkLifePlan plan = ctk_life_plan(T, ny, nx, f64, (uintptr_t)flag_dev, (uintptr_t)field_dev);
+    h->lc_plan = plan;
+    const int ks = plan.ks;
     size_t cap = std::max<size_t>(h->lc_rows.cap / sizeof(CtkLifeRowDev), (size_t)T * 16 + 1024);
     unsigned long long cnt[2] = {0, 0};
     h->lc_flag = flag_dev; h->lc_field = field_dev; h->lc_f64 = f64; h->lc_T = T; h->lc_ny = ny; h->lc_nx = nx;
@@ -3466,8 +3466,7 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
     };
     // Banded form first (every byte read once, T x chunks workgroups); the time steps it gives up (more ids than its tables
     // hold) are redone by k_lifecycle, which splits further by residue classes of the ids.
-    const int rw = life_rows_per_wave(T, ny, nx);
-    const int nsx = (nx + LB_SW - 1) / LB_SW, nby = (ny + rw * (LB_THREADS / 64) - 1) / (rw * (LB_THREADS / 64)), nb = nsx * nby;
+    const int rw = plan.rw, nsx = plan.nsx, nby = plan.nby, nb = nsx * nby;
     const size_t gkey_bytes = (size_t)T * LB_GH * 4, gacc_bytes = (size_t)T * LB_GH * sizeof(CtkLifeAcc);
     const size_t occ_bytes = (size_t)T * LB_KS * nxw * 4, cp_bytes = (size_t)T * LB_KS * nx * 8;
     if ((uint64_t)T * (uint64_t)nb > 0x7fffffffull) return ctk_set_error(CTK_E_RANGE, "ctk_lifecycle: %lld time steps x %d chunks beyond one launch", (long long)T, nb);
@@ -3478,6 +3477,9 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
     int32_t *gkey = P<int32_t>(h->lc_gtab);
     CtkLifeAcc *gacc = (CtkLifeAcc *)((char *)h->lc_gtab.p + gkey_bytes);
     for (int attempt = 0; attempt < 2; ++attempt) {
+        h->lc_attempts = attempt + 1;                 // (what follows describes the attempt whose rows are returned)
+        h->lc_given_up = 0; h->lc_fb_launches = 0;
+        std::fill(h->lc_rounds.begin(), h->lc_rounds.end(), (uint8_t)0);
         CTKCHK(ensure(h, h->lc_rows, cap * sizeof(CtkLifeRowDev)));
         cap = h->lc_rows.cap / sizeof(CtkLifeRowDev);
         CTKCHK(ensure(h, h->lc_ovf, (size_t)T));
@@ -3488,7 +3490,7 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
         HIPCHK(hipMemsetAsync(h->lc_cp.p, 0, cp_bytes, h->stream));
         k_life_seam<<<(unsigned)T, 64, 0, h->stream>>>(flag_dev, ny, nx, P<int32_t>(h->lc_cross), P<unsigned char>(h->lc_ovf));
         {
-            const bool vec = (nx & 3) == 0 && (((uintptr_t)flag_dev) & 15u) == 0 && (((uintptr_t)field_dev) & (f64 ? 31u : 15u)) == 0;
+            const bool vec = plan.vec != 0;
             const unsigned grid = (unsigned)(T * nb);
 #define CTK_LIFE_STRIPS(VT, VEC)                                                                                                                       \
     k_life_strips<VT, VEC><<<grid, LB_THREADS, 0, h->stream>>>(flag_dev, (const VT *)field_dev, ny, nx, nxw, nsx, nby, rw, P<int64_t>(h->lc_wlo),      \
@@ -3509,6 +3511,7 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
             std::vector<unsigned char> ov((size_t)T);
             HIPCHK(hipMemcpy(ov.data(), h->lc_ovf.p, (size_t)T, hipMemcpyDeviceToHost));
             for (int64_t t = 0; t < T; ++t) if (ov[(size_t)t]) { work.push_back((int32_t)t); work.push_back(1); work.push_back(0); }
+            h->lc_given_up = (int64_t)(work.size() / 3);
         }
         while (!work.empty()) {
             const size_t items = work.size() / 3;
@@ -3520,6 +3523,12 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
             unsigned long long zero = 0;
             HIPCHK(hipMemcpyAsync(P<unsigned long long>(h->lc_cnt) + 1, &zero, 8, hipMemcpyHostToDevice, h->stream));
             CTKCHK(launch(P<int32_t>(h->lc_work), (unsigned)items));
+            h->lc_fb_launches++;
+            for (size_t i = 0; i < items; ++i) {          // (the items of one time step follow each other)
+                if (i && work[3 * i] == work[3 * (i - 1)]) continue;
+                uint8_t &r = h->lc_rounds[(size_t)work[3 * i]];
+                if (r < 255) r++;
+            }
             HIPCHK(hipMemcpyAsync(cnt, h->lc_cnt.p, 16, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
             std::vector<int32_t> next;
@@ -3546,7 +3555,8 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
     int32_t lmin = INT32_MAX, lmax = INT32_MIN;
     for (size_t i = 0; i < n; ++i) { lmin = std::min(lmin, land[i].label); lmax = std::max(lmax, land[i].label); }
     const uint64_t lrange = n ? (uint64_t)((int64_t)lmax - (int64_t)lmin) + 1 : 0;
-    if (n && lrange <= 8 * (uint64_t)n + 65536) {
+    h->lc_sort = (!n || lrange <= 8 * (uint64_t)n + 65536) ? 0 : 1;
+    if (!h->lc_sort) {
         std::vector<uint32_t> &cnt = h->lc_cnt_host;
         cnt.assign((size_t)T + 1, 0);
         for (size_t i = 0; i < n; ++i) cnt[(size_t)land[i].t + 1]++;
@@ -3565,6 +3575,28 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
         for (size_t i = 0; i < n; ++i) h->lc_host[i] = land[keys[i].second];
     }
     if (nrows) *nrows = (int64_t)n;
+    h->lc_path_T = T;
+    return CTK_OK;
+}
+
+// test hook, GPU-free: ctk_life_plan for slabs whose device addresses are flag_align / field_align bytes past a 32-byte boundary
+extern "C" int ctk_debug_lifecycle_plan(int64_t T, int ny, int nx, int f64, int64_t flag_align, int64_t field_align, int64_t *out5)
+{
+    if (!out5 || T < 1 || ny < 1 || nx < 1 || flag_align < 0 || field_align < 0) return ctk_set_error(CTK_E_INVALID, "ctk_debug_lifecycle_plan: bad arguments");
+    const CtkLifePlan p = ctk_life_plan(T, ny, nx, f64 != 0, (uintptr_t)flag_align, (uintptr_t)field_align);
+    out5[0] = p.rw; out5[1] = p.nsx; out5[2] = p.nby; out5[3] = p.vec; out5[4] = p.ks;
+    return CTK_OK;
+}
+
+// test hook: the path of the last ctk_lifecycle_* call on this handle
+extern "C" int ctk_debug_lifecycle_path(ctk_handle *h, int64_t *out8, uint8_t *steps, int64_t T)
+{
+    if (!h || !out8 || (T > 0 && !steps)) return ctk_set_error(CTK_E_INVALID, "ctk_debug_lifecycle_path: null argument");
+    if (h->lc_path_T < 0) return ctk_set_error(CTK_E_STATE, "ctk_debug_lifecycle_path needs a finished ctk_lifecycle_* call first");
+    if (T != h->lc_path_T) return ctk_set_error(CTK_E_INVALID, "ctk_debug_lifecycle_path: %lld time steps asked for, the last call had %lld", (long long)T, (long long)h->lc_path_T);
+    out8[0] = h->lc_plan.rw; out8[1] = h->lc_plan.nsx; out8[2] = h->lc_plan.nby; out8[3] = h->lc_plan.vec;
+    out8[4] = h->lc_given_up; out8[5] = h->lc_fb_launches; out8[6] = h->lc_attempts; out8[7] = h->lc_sort;
+    if (T > 0) memcpy(steps, h->lc_rounds.data(), (size_t)T);
     return CTK_OK;
 }
 

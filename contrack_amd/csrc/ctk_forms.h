@@ -457,6 +457,46 @@ inline CtkPfieldPlan ctk_pfield_plan(int keybytes, int64_t max_pool_steps, int G
 }
 
 // ------------------------------------------------------------------------------------------------
+// run_lifecycle reductions (ctk_lifecycle.hip): the strip form k_life_seam / k_life_strips<VT, VEC> / k_life_finish, and k_lifecycle for
+// the time steps the strip form gives up.  (CTK_LIFE_SW and CTK_LIFE_WAVES restate LB_SW and LB_THREADS / 64 of ctk_lifecycle.hip;
+// ctk_api.hip asserts that they agree.)
+// ------------------------------------------------------------------------------------------------
+#define CTK_LIFE_SW 256           // columns per strip: one wave, four per lane
+#define CTK_LIFE_WAVES 4          // waves (bands of rw rows) per workgroup
+#define CTK_LIFE_KS_MAX 32        // k_lifecycle: column bit sets of seam-crossing ids, at most
+#define CTK_LIFE_KS_BYTES 32768   // ... and their dynamic LDS
+struct CtkLifePlan {
+    int rw;                       // rows per wave of k_life_strips
+    int nsx, nby;                 // strips per row, workgroups per strip: nsx * nby workgroups per time step
+    int vec;                      // k_life_strips<VT, true>: one 16- / 32-byte request per lane and row
+    int ks;                       // seam-crossing ids per pass of k_lifecycle
+};
+// Rows per wave of k_life_strips: four waves (one workgroup) cover a band of the strip, `g` bands cover the ny rows without idle
+// waves at the end (181 rows: 4 x 46; 721 rows: 20 x 37).  Measured (us, 2707 x 181 x 360 | 480 x 721 x 1440): 16 rows 316 | 509,
+// 23: 291 | 474, 31: 379 (a quarter of the waves idle) | 441, 37: | 436, 46: 281 | 458, 61: | 433 -- long streams per wave, as long
+// as the launch keeps a few thousand workgroups.
+inline int ctk_life_rows_per_wave(int64_t T, int ny, int nx)
+{
+    const int64_t nsx = (nx + CTK_LIFE_SW - 1) / CTK_LIFE_SW;
+    int g = std::max(1, (ny + 80) / 160);
+    while (T * nsx * g < 2048 && (ny + 4 * g - 1) / (4 * g) > 8) g++;
+    return std::max(1, (ny + 4 * g - 1) / (4 * g));
+}
+// flag_ptr / field_ptr: the device addresses of the two slabs (only their alignment matters: VEC needs nx a multiple of 4, the flags
+// on 16 bytes and the field on 16 (float32) or 32 (float64), so that every row of every plane starts on a whole request)
+inline CtkLifePlan ctk_life_plan(int64_t T, int ny, int nx, bool f64, uintptr_t flag_ptr, uintptr_t field_ptr)
+{
+    CtkLifePlan p;
+    p.rw = ctk_life_rows_per_wave(T, ny, nx);
+    p.nsx = (nx + CTK_LIFE_SW - 1) / CTK_LIFE_SW;
+    p.nby = (ny + p.rw * CTK_LIFE_WAVES - 1) / (p.rw * CTK_LIFE_WAVES);
+    p.vec = ((nx & 3) == 0 && (flag_ptr & 15u) == 0 && (field_ptr & (f64 ? 31u : 15u)) == 0) ? 1 : 0;
+    const int nxw = (nx + 31) / 32;
+    p.ks = std::max(1, std::min(CTK_LIFE_KS_MAX, CTK_LIFE_KS_BYTES / (nxw * 4)));
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------
 // segmented anomalies (ctk_anom_seg.hip): k_anom_ring keeps the last `smooth` raw anomalies of a thread's pixel in LDS while it walks
 // its time tile; k_anom_plain re-reads the window from memory for a smoothing whose ring does not fit
 // ------------------------------------------------------------------------------------------------

@@ -289,7 +289,7 @@ __global__ __launch_bounds__(LC_THREADS) void k_lifecycle(const int32_t *__restr
 // ------------------------------------------------------------------------------------------------
 #define LB_THREADS 256
 #define LB_SW 256         // columns per strip: one wave, four per lane
-// (rows per wave: a launch parameter -- life_rows_per_wave in ctk_api.hip; a workgroup = 4 waves = 4 x that many rows of one strip)
+// (rows per wave: a launch parameter -- ctk_life_plan in ctk_forms.h; a workgroup = 4 waves = 4 x that many rows of one strip)
 #define LB_LH 128         // LDS hash slots per chunk (<= LB_LN ids)
 #define LB_LN 64
 #define LB_GH 256         // global hash slots per time step (<= LB_GN ids)

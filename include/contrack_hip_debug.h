@@ -161,6 +161,18 @@ int ctk_debug_percentile_field_form(ctk_handle *h, int64_t *out2);
 int ctk_debug_time_percentile_field(ctk_handle *h, const void *x_dev, int is_f64, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group,
                                     int ngroups, int window, double q, int reps, double *out, double *out_direct, double *ms4);
 
+/* what ctk_life_plan (csrc/ctk_forms.h) decides for a ctk_lifecycle_* call over T time steps of (ny, nx) planes, float64 field if f64,
+ * whose flag / field slabs start flag_align / field_align bytes past a 32-byte boundary: out5 = { rows per wave of k_life_strips,
+ * strips per row, workgroups per strip, 1 if the vector form k_life_strips<VT, true> runs, seam-crossing ids one pass of k_lifecycle
+ * holds }.  Host only: no handle, no GPU. */
+int ctk_debug_lifecycle_plan(int64_t T, int ny, int nx, int f64, int64_t flag_align, int64_t field_align, int64_t *out5);
+/* test hook: the path of the last ctk_lifecycle_* call on this handle (an error if none finished, or if it had another T).
+ * out8 = { rows per wave, strips per row, workgroups per strip, vector form (as above), time steps the strip form gave up, launches of
+ * k_lifecycle, attempts (2: the row table was too small and everything ran again; the other figures describe the last attempt),
+ * row order (0 two counting sorts, 1 comparison sort) }; steps[t]: the rounds of k_lifecycle time step t took part in -- 0 the strip
+ * form held it, 1 one pass over all its ids, 2 its ids split into two residue classes, 3 into four, ... */
+int ctk_debug_lifecycle_path(ctk_handle *h, int64_t *out8, uint8_t *steps, int64_t T);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,8 +131,9 @@ def test_hip_lifecycle_on_tracked_slab(tracker, f64):
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape,thr,pers", [((6, 721, 1440), 160.0, 2), ((24, 181, 360), 160.0, 3), ((8, 192, 288), 150.0, 2)])
 def test_hip_lifecycle_on_baseline_grids(tracker, shape, thr, pers):
-    """the grids of BASELINE.json (0.25 deg: six 256-column strips x twelve 64-row bands per plane; 1 deg; CESM): frame identical to
-    the scipy port's in every column, with the rows on rounding boundaries re-evaluated on the device"""
+    """the grids of BASELINE.json (0.25 deg: six 256-column strips x 23 bands of 4 x 8 rows per plane -- few time steps keep the rows
+    per wave at 8; the production forms, 37 and 46 rows per wave, are in tests/test_gpu_lifecycle_forms.py; 1 deg; CESM): frame
+    identical to the scipy port's in every column, with the rows on rounding boundaries re-evaluated on the device"""
     from contrack_amd import synth
     T, ny, nx = shape
     anom = synth.smooth_field(T, ny, nx, seed=9)
