@@ -34,6 +34,7 @@ EXPORTS = [
     "ctk_anom_f32", "ctk_anom_f64", "ctk_resident_anom", "ctk_resident_anom_generation", "ctk_track_resident", "ctk_percentile_f32", "ctk_percentile_f64", "ctk_debug_percentile_values",
     "ctk_lifecycle_f32", "ctk_lifecycle_f64", "ctk_lifecycle_f32_dev", "ctk_lifecycle_f64_dev", "ctk_lifecycle_rows", "ctk_lifecycle_exact",
     "ctk_debug_lifecycle_plan", "ctk_debug_lifecycle_path",
+    "ctk_lifecycle_stream_f32", "ctk_lifecycle_stream_f64", "ctk_lifecycle_stream_cb", "ctk_lifecycle_stream_exact",
     "ctk_track_stream_f32", "ctk_track_stream_f64", "ctk_track_stream_cb", "ctk_stream_times",
     "ctk_set_threshold_field", "ctk_set_segments",
     "ctk_track_stream_seg_f32", "ctk_track_stream_seg_f64", "ctk_track_stream_seg_cb", "ctk_track_sharded_seg_f32_dev", "ctk_track_sharded_seg_f64_dev",
@@ -45,6 +46,7 @@ EXPORTS = [
 
 READ_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)       # ctk_read_chunk_fn
 WRITE_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)      # ctk_write_chunk_fn, ctk_write_values_fn
+LIFE_PICK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64))      # ctk_life_pick_fn
 
 # ctk_life_row (include/contrack_hip.h)
 LIFE_ROW = np.dtype([("t", "<i4"), ("label", "<i4"), ("shift", "<i4"), ("pad", "<i4"),
@@ -201,6 +203,10 @@ def lib():
         getattr(L, name).argtypes = [p, p, p, i64, i32, i32, p, C.POINTER(i64)]
     L.ctk_lifecycle_rows.argtypes = [p, p, i64]
     L.ctk_lifecycle_exact.argtypes = [p, p, i64, p]
+    for name in ("ctk_lifecycle_stream_f32", "ctk_lifecycle_stream_f64"):
+        getattr(L, name).argtypes = [p, p, p, i64, i32, i32, p, i64, LIFE_PICK_FN, p, C.POINTER(i64), C.POINTER(i64)]
+    L.ctk_lifecycle_stream_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, READ_CHUNK_FN, p, p, i64, LIFE_PICK_FN, p, C.POINTER(i64), C.POINTER(i64)]
+    L.ctk_lifecycle_stream_exact.argtypes = [p, p, p, i64]
     L.ctk_debug_lifecycle_plan.argtypes = [i64, i32, i32, i32, i64, i64, p]
     L.ctk_debug_lifecycle_path.argtypes = [p, p, p, i64]
     for name in ("ctk_anom_f32", "ctk_anom_f64"):
@@ -1218,6 +1224,97 @@ class Tracker:
         out = np.empty(len(idx), dtype=LIFE_EXACT)
         check(lib().ctk_lifecycle_exact(self._h, idx.ctypes.data, len(idx), out.ctypes.data))
         return out
+
+    def lifecycle_stream(self, flag_source, field_source, wrow, shape=None, dtype=None, chunk_steps=0, pick=None):
+        """`lifecycle` with both slabs passing through chunk-sized device buffers (ctk_lifecycle_stream_*; device footprint: two
+        chunks of each slab and the tables of one chunk).
+
+        flag_source:  an int32 (T, ny, nx) array (np.memmap included) or a callable reader(t0, nt, out) that fills `out`, an int32
+                      (nt, ny, nx) view of pinned memory, with the time steps [t0, t0 + nt);
+        field_source: a float32 / float64 array of the same shape or such a reader of values -- with a reader on either side
+                      `shape` = (T, ny, nx) is required, with a field reader `dtype` too.  The flag reader is called first;
+        chunk_steps:  time steps per chunk, 0: about 256 MB of field;
+        pick:         None, or pick(rows) -> indices: called once per chunk with that chunk's LIFE_ROW records (sorted by (label, t),
+                      t global), returns the ascending indices of the rows to re-evaluate in the reference's summation orders
+                      while the chunk is on the device (contrack.fragile_rows is the rule run_lifecycle uses).
+        Returns (rows, exact_idx, exact): all LIFE_ROW records sorted by (label, t), the picked rows as ascending indices into
+        them, and their LIFE_EXACT records."""
+        L = lib()
+        arrays = not callable(flag_source) and not callable(field_source)
+        if not callable(flag_source):
+            flag_source = flag_source if isinstance(flag_source, np.memmap) and flag_source.dtype == np.int32 else np.ascontiguousarray(flag_source, dtype=np.int32)
+            if flag_source.ndim != 3:
+                raise ValueError("flag must be (time, lat, lon)")
+        if not callable(field_source):
+            if not isinstance(field_source, np.memmap) or field_source.dtype not in (np.float32, np.float64):
+                field_source = np.ascontiguousarray(field_source, dtype=np.float64 if np.asarray(field_source).dtype == np.float64 else np.float32)
+            if field_source.ndim != 3:
+                raise ValueError("field must be (time, lat, lon)")
+        if shape is None:
+            have = [a.shape for a in (flag_source, field_source) if not callable(a)]
+            if not have:
+                raise ValueError("reader callbacks need shape=(T, ny, nx) and dtype")
+            shape = have[0]
+        T, ny, nx = (int(v) for v in shape)
+        for a in (flag_source, field_source):
+            if not callable(a) and a.shape != (T, ny, nx):
+                raise ValueError("flag and field must share one (time, lat, lon) shape")
+        if callable(field_source):
+            if dtype is None:
+                raise ValueError("a field reader needs dtype")
+            dt = np.dtype(dtype)
+        else:
+            dt = field_source.dtype
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("the field must be float32 or float64")
+        wrow = np.ascontiguousarray(wrow, dtype=np.float32)
+        if wrow.shape != (ny,):
+            raise ValueError("wrow must have shape (ny,)")
+        errors = []
+
+        def guarded(body):
+            def call(*a):
+                try:
+                    body(*a)
+                    return 0
+                except BaseException as e:                # an exception must not cross the C frames
+                    errors.append(e)
+                    return 1
+            return call
+
+        def reader_of(source, ctype):
+            def rd(_user, t0, nt, dst):
+                view = np.ctypeslib.as_array(C.cast(dst, C.POINTER(ctype)), shape=(nt, ny, nx))
+                if callable(source):
+                    source(int(t0), int(nt), view)
+                else:
+                    view[...] = source[t0:t0 + nt]
+            return READ_CHUNK_FN(guarded(rd))
+
+        def pk(_user, rows, n, idx, nidx):
+            view = np.ctypeslib.as_array(C.cast(rows, C.POINTER(C.c_byte)), shape=(n * LIFE_ROW.itemsize,)).view(LIFE_ROW)
+            chosen = np.ascontiguousarray(pick(view), dtype=np.int64).reshape(-1)
+            if len(chosen) > n:
+                raise ValueError("pick returned more indices than rows")
+            np.ctypeslib.as_array(C.cast(idx, C.POINTER(C.c_int64)), shape=(max(int(n), 1),))[:len(chosen)] = chosen
+            nidx[0] = len(chosen)
+        pcb = LIFE_PICK_FN(guarded(pk)) if pick is not None else LIFE_PICK_FN()          # (a NULL pointer: no rows are picked)
+        n, nx_ = C.c_int64(0), C.c_int64(0)
+        tail = (wrow.ctypes.data, int(chunk_steps), pcb, None, C.byref(n), C.byref(nx_))
+        if arrays:
+            fn = L.ctk_lifecycle_stream_f64 if dt == np.float64 else L.ctk_lifecycle_stream_f32
+            rc = fn(self._h, flag_source.ctypes.data, field_source.ctypes.data, T, ny, nx, *tail)
+        else:
+            fcb, vcb = reader_of(flag_source, C.c_int32), reader_of(field_source, C.c_float if dt == np.float32 else C.c_double)
+            rc = L.ctk_lifecycle_stream_cb(self._h, dt.itemsize, T, ny, nx, fcb, None, vcb, None, *tail)
+        if errors:
+            raise errors[0]
+        check(rc)
+        rows = self._life_rows(int(n.value))
+        idx = np.empty(int(nx_.value), dtype=np.int64)
+        exact = np.empty(int(nx_.value), dtype=LIFE_EXACT)
+        check(L.ctk_lifecycle_stream_exact(self._h, idx.ctypes.data, exact.ctypes.data, len(idx)))
+        return rows, idx, exact
 
     def debug_lifecycle_path(self, T):
         """test hook: the path of the last lifecycle call (of T time steps) as (dict(rw, nsx, nby, vec, given_up, launches, attempts,

@@ -211,32 +211,36 @@ def frequency_percent(counts, n):
         return counts.astype(np.float64) / n * 100
 
 
-def frequency_numpy(flag, group=None, above=0, percent=True, device=None):
+def frequency_numpy(flag, group=None, above=0, percent=True, device=None, chunk_steps=None, shape=None):
     """the blocking frequency of README.rst:159-160 on a (time, lat, lon) integer flag slab:
         np.where(flag > above, 1, 0).sum(axis=0) / T * 100           (above = 1 is the README's expression)
     per group of timesteps when `group` (one id in [0, G) per timestep, any order in time) is given.  The count runs on the GPU
     (ctk_frequency); int32 and narrower flags are read as they are, wider ones are converted to int32 chunk by chunk (an id beyond
     int32 raises ValueError).  Returns float64 percent (G, ny, nx) -- (ny, nx) without `group` -- or, with percent=False, int64
-    counts of the same shape."""
-    flag = np.asarray(flag)
-    if flag.ndim != 3:
-        raise ValueError("flag must be (time, lat, lon)")
-    if flag.dtype.kind not in "iub":
-        raise ValueError("flag must be an integer field")
-    T, ny, nx = flag.shape
+    counts of the same shape.  chunk_steps: time steps per chunk on their way through the device (None or 0: about 256 MB); with
+    shape=(T, ny, nx) `flag` may be a reader(t0, nt, out) that fills an int32 (nt, ny, nx) buffer (ctk_frequency_cb)."""
+    steps = 0 if chunk_steps is None else int(chunk_steps)
     trk = _tracker(device)
-    ids, G = _native._groups(group, T)
-    if flag.dtype.itemsize < 4 or flag.dtype == np.int32:
-        counts = trk.frequency(flag, ids, G, above)
+    if callable(flag):
+        if shape is None:
+            raise ValueError("a reader needs shape=(T, ny, nx)")
+        T = int(shape[0])
+        ids, G = _native._groups(group, T)
+        counts = trk.frequency_cb(flag, shape, ids, G, above, steps)
     else:
-        lo, hi = np.iinfo(np.int32).min, np.iinfo(np.int32).max
-
-        def reader(t0, nt, out):
-            part = flag[t0:t0 + nt]
-            if part.size and (part.max() > hi or part.min() < lo):
-                raise ValueError("flag ids beyond int32")
-            out[...] = part
-        counts = trk.frequency_cb(reader, flag.shape, ids, G, above)
+        flag = np.asarray(flag)
+        if flag.ndim != 3:
+            raise ValueError("flag must be (time, lat, lon)")
+        if flag.dtype.kind not in "iub":
+            raise ValueError("flag must be an integer field")
+        T, ny, nx = flag.shape
+        ids, G = _native._groups(group, T)
+        if flag.dtype.itemsize < 4 or flag.dtype == np.int32:
+            counts = trk.frequency(flag, ids, G, above, steps)
+        else:
+            def reader(t0, nt, out):
+                out[...] = _int32_chunk(flag[t0:t0 + nt])
+            counts = trk.frequency_cb(reader, flag.shape, ids, G, above, steps)
     counts = counts.astype(np.int64)
     out = frequency_percent(counts, np.bincount(ids, minlength=G) if ids is not None else [T]) if percent else counts
     return out[0] if group is None else out
@@ -321,15 +325,43 @@ def _check_percentile_args(q, window):
 # the class
 # ------------------------------------------------------------------------------------------------
 
-def lifecycle_columns(rows, lat, lon, dates, tracker=None):
+def fragile_rows(rows):
+    """indices of the ctk_life_row records whose result sits on a rounding boundary: a centre of mass that is an integer up to
+    rounding (contours one pixel wide or high: int() then gives the cell or its neighbour) or an intensity / area at the edge of
+    two decimals.  These rows -- a few per cent in practice -- are re-evaluated on the device in the reference's own summation
+    orders: after the call by lifecycle_columns(tracker=...), or chunk by chunk as the `pick` of Tracker.lifecycle_stream."""
+    if not len(rows):
+        return np.empty(0, dtype=np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        intensity = rows["swv"] / rows["area"]                                                          # :876
+        com_y, com_x = rows["swvy"] / rows["swv"], rows["swvx"] / rows["swv"]                           # ndimage.center_of_mass
+    area = rows["area"]
+
+    def near_int(v):
+        return np.abs(v - np.rint(v)) <= 1e-9 * np.maximum(1.0, np.abs(v))
+
+    def near_half(v, rel):                              # v * 100 close to k + 0.5: round(v, 2) could go either way
+        s = np.abs(v) * 100.0
+        return np.abs(s - np.floor(s) - 0.5) <= rel * np.maximum(1.0, s)
+    # The area is a sum of POSITIVE float64 terms: the device's value (exact integers, rounded once) and numpy's pairwise sum
+    # differ by less than 5e-15 of it (depth of the pairwise tree x 2^-53) -- 1e-11 is generous, while 1e-6 would flag every
+    # contour beyond 5000 km^2 (a quarter of all rows).  Sums of field values can cancel: their window stays wide.
+    with np.errstate(invalid="ignore"):
+        fragile = near_int(com_y) | near_int(com_x) | near_half(intensity, 1e-6) | near_half(area, 1e-11) | ~np.isfinite(com_y) | ~np.isfinite(com_x)
+    return np.nonzero(fragile)[0]
+
+
+def lifecycle_columns(rows, lat, lon, dates, tracker=None, exact=None, period=None):
     """ctk_life_row records -> the columns of the reference's frame (contrack.py:876-906), rows sorted by (Flag, Date):
     dict of arrays Flag, Date, Longitude, Latitude, Intensity, Size.
 
     The device sums are float64 but in another order than the reference's (np.sum pairwise, np.bincount sequential).  That shows
-    only where a result sits on a rounding boundary: a centre of mass that is an integer up to rounding (contours one pixel wide
-    or high: int() then gives the cell or its neighbour) or a value at the edge of two decimals.  With the Tracker that produced
-    `rows` at hand those rows -- a few per cent in practice -- are re-evaluated ON THE DEVICE in the reference's own summation orders
-    (ctk_lifecycle_exact)."""
+    only where a result sits on a rounding boundary (fragile_rows).  With the Tracker that produced `rows` at hand (tracker=) those
+    rows are re-evaluated ON THE DEVICE in the reference's own summation orders (ctk_lifecycle_exact); a streamed call has done
+    that chunk by chunk and hands over exact=(idx, records), the indices into `rows` and their ctk_life_exact records.
+
+    period: the slab is a member dimension flattened to steps m * period + t; `dates` are the labels of ONE member's steps, the
+    column 'Member' (the position m) is added and the rows are sorted by (Flag, Member, Date)."""
     nx, ny = len(lon), len(lat)
     if (rows["shift"] == -2).any():
         raise ValueError("attempt to get argmax of an empty sequence")                                  # np.argmax(np.diff(.)), :883
@@ -337,26 +369,19 @@ def lifecycle_columns(rows, lat, lon, dates, tracker=None):
         intensity = rows["swv"] / rows["area"]                                                          # :876
         com_y, com_x = rows["swvy"] / rows["swv"], rows["swvx"] / rows["swv"]                           # ndimage.center_of_mass
     area = rows["area"].copy()
-    if tracker is not None and len(rows):
-        def near_int(v):
-            return np.abs(v - np.rint(v)) <= 1e-9 * np.maximum(1.0, np.abs(v))
-
-        def near_half(v, rel):                              # v * 100 close to k + 0.5: round(v, 2) could go either way
-            s = np.abs(v) * 100.0
-            return np.abs(s - np.floor(s) - 0.5) <= rel * np.maximum(1.0, s)
-        # The area is a sum of POSITIVE float64 terms: the device's value (exact integers, rounded once) and numpy's pairwise sum
-        # differ by less than 5e-15 of it (depth of the pairwise tree x 2^-53) -- 1e-11 is generous, while 1e-6 would flag every
-        # contour beyond 5000 km^2 (a quarter of all rows).  Sums of field values can cancel: their window stays wide.
-        with np.errstate(invalid="ignore"):
-            fragile = near_int(com_y) | near_int(com_x) | near_half(intensity, 1e-6) | near_half(area, 1e-11) | ~np.isfinite(com_y) | ~np.isfinite(com_x)
-        idx = np.nonzero(fragile)[0]
+    idx, ex = np.empty(0, dtype=np.int64), None
+    if exact is not None:
+        idx, ex = np.asarray(exact[0], dtype=np.int64), exact[1]
+    elif tracker is not None and len(rows):
+        idx = fragile_rows(rows)
         if len(idx):
             ex = tracker.lifecycle_exact(idx)
-            intensity, com_y, com_x = intensity.copy(), com_y.copy(), com_x.copy()
-            with np.errstate(divide="ignore", invalid="ignore"):
-                area[idx] = ex["area"]
-                intensity[idx] = ex["swv"] / ex["area"]
-                com_y[idx], com_x[idx] = ex["sy"] / ex["s"], ex["sx"] / ex["s"]
+    if len(idx):
+        intensity, com_y, com_x = intensity.copy(), com_y.copy(), com_x.copy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            area[idx] = ex["area"]
+            intensity[idx] = ex["swv"] / ex["area"]
+            com_y[idx], com_x[idx] = ex["sy"] / ex["s"], ex["sx"] / ex["s"]
     if not (np.isfinite(com_y).all() and np.isfinite(com_x).all()):
         raise ValueError("cannot convert float NaN to integer")                                         # int(center_of_mass[..]), :886
     iy, ix = np.trunc(com_y).astype(np.int64), np.trunc(com_x).astype(np.int64)
@@ -366,22 +391,71 @@ def lifecycle_columns(rows, lat, lon, dates, tracker=None):
     ix = np.where(ix < 0, ix + nx, ix)                                                                  # Python indexing of the rolled axis
     lon_of = np.asarray(lon)[(ix + shift) % nx]                                                         # np.roll(lon, -shift)[ix], :884-887
     lat_of = np.asarray(lat)[iy]
-    date = np.asarray(dates, dtype=object)[rows["t"]] if len(rows) else np.empty(0, dtype=object)
+    step = rows["t"] if period is None else rows["t"] % int(period)
+    date = np.asarray(dates, dtype=object)[step] if len(rows) else np.empty(0, dtype=object)
     cols = dict(Flag=rows["label"].astype(np.int64), Date=date,
                 Longitude=np.trunc(lon_of).astype(np.int64), Latitude=np.trunc(lat_of).astype(np.int64),           # int(), :886-895
                 Intensity=np.round(intensity, 2), Size=np.round(area, 2))                               # round(np.float64, 2), :899-900
-    # the library returns (label, t) order; the reference sorts by the date STRING, which differs when the time axis
-    # is not increasing
-    order = sorted(range(len(rows)), key=lambda i: (cols["Flag"][i], cols["Date"][i])) \
-        if any(a > b for a, b in zip(dates, dates[1:])) else None
-    return cols if order is None else {k: v[order] for k, v in cols.items()}
+    if period is not None:
+        cols["Member"] = (rows["t"] // int(period)).astype(np.int64)
+    # the library returns (label, t) order -- (label, member, step of the member) for a flattened member dimension; the reference
+    # sorts by the date STRING, which differs when the time axis is not increasing
+    if any(a > b for a, b in zip(dates, dates[1:])):
+        member = cols["Member"] if period is not None else np.zeros(len(rows), dtype=np.int64)
+        order = sorted(range(len(rows)), key=lambda i: (cols["Flag"][i], member[i], cols["Date"][i]))
+        cols = {k: v[order] for k, v in cols.items()}
+    return cols
 
 
-def lifecycle_frame(rows, lat, lon, dates, tracker=None):
+def lifecycle_frame(rows, lat, lon, dates, tracker=None, exact=None):
     """the same as a list of (Flag, Date, Longitude, Latitude, Intensity, Size) tuples"""
-    c = lifecycle_columns(rows, lat, lon, dates, tracker)
+    c = lifecycle_columns(rows, lat, lon, dates, tracker, exact)
     return [(int(f), d, int(lo), int(la), float(it), float(sz)) for f, d, lo, la, it, sz in
             zip(c["Flag"], c["Date"], c["Longitude"], c["Latitude"], c["Intensity"], c["Size"])]
+
+
+def _int32_chunk(part):
+    """a chunk of integer flags on its way into an int32 buffer: ids beyond int32 are an error, never a wrap-around"""
+    part = np.asarray(part)
+    if part.dtype.kind not in "iub":
+        raise ValueError("flag must be an integer field")
+    if part.size and (part.dtype.itemsize > 4 or part.dtype == np.uint32) and \
+            (part.max() > np.iinfo(np.int32).max or part.min() < np.iinfo(np.int32).min):              # (nothing to check for int32 and narrower)
+        raise ValueError("flag ids beyond int32")
+    return part
+
+
+def lifecycle_numpy(flag, field, wrow, lat, lon, dates, chunk_steps=None, device=None, shape=None, dtype=None, period=None):
+    """the columns of run_lifecycle's frame (lifecycle_columns) for a (time, lat, lon) integer flag slab and a float field of the
+    same shape.  chunk_steps None: both slabs go to the device whole (field None: the anomaly slab resident there, `dtype` its
+    type).  Otherwise they pass through chunk-sized device buffers, that many time steps at a time (0: about 256 MB of field):
+    arrays (np.memmap included; flags wider than int32 are narrowed chunk by chunk, an id beyond int32 raises ValueError from the
+    chunk that holds it) or readers reader(t0, nt, out) with shape=(T, ny, nx) and the field's dtype; the rounding-boundary rows
+    are re-evaluated while their chunk is on the device.  period: see lifecycle_columns."""
+    trk = _tracker(device)
+    if chunk_steps is None:
+        flag = _int32_chunk(flag)
+        rows = trk.lifecycle(flag, None, wrow, resident_f64=np.dtype(dtype) == np.float64) if field is None else trk.lifecycle(flag, field, wrow)
+        return lifecycle_columns(rows, lat, lon, dates, tracker=trk, period=period)
+    if callable(flag):
+        flag_source = flag
+    else:
+        if not isinstance(flag, np.memmap):
+            flag = np.asarray(flag)
+        if flag.dtype.kind not in "iub":
+            raise ValueError("flag must be an integer field")
+        if shape is None:
+            shape = flag.shape
+        flag_source = flag
+        if flag.dtype != np.int32:
+            def flag_source(t0, nt, out, slab=flag):
+                out[...] = _int32_chunk(slab[t0:t0 + nt])
+    if not callable(field):
+        if field.dtype != np.float64:
+            field = field.astype(np.float32, copy=False)
+        dtype = field.dtype
+    rows, idx, ex = trk.lifecycle_stream(flag_source, field, wrow, shape=shape, dtype=dtype, chunk_steps=int(chunk_steps), pick=fragile_rows)
+    return lifecycle_columns(rows, lat, lon, dates, exact=(idx, ex), period=period)
 
 
 INT64_FLAG_FROM = 2 ** 31 - 2       # elements from which scipy.ndimage.label (and the reference's 'flag') switch to int64
@@ -1010,28 +1084,32 @@ class contrack(object):
             starts = None if segments is None else segment_starts(segments, T)
         return member, starts, T
 
-    def _time_reader(self, da, dims):
-        """(reader(t0, nt, out), (T, ny, nx), dtype) of a 3-D variable read slice by slice along time (isel where there is one)"""
+    def _time_reader(self, da, dims, integer=False):
+        """(reader(t0, nt, out), (T, ny, nx), dtype) of a 3-D variable read slice by slice along time (isel where there is one).
+        integer: a flag variable -- int32 buffers, every slice checked on its way in (_int32_chunk)"""
         tname = self._time_name
         sort = [dims.index(d) for d in (tname, self._latitude_name, self._longitude_name)]
         shape = tuple(da.shape[i] for i in sort)
-        dtype = np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
+        dtype = np.dtype(np.int32) if integer else np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
+        narrow = _int32_chunk if integer else (lambda a: a)
 
         def reader(t0, nt, out):
             part = da.isel(**{tname: slice(t0, t0 + nt)}) if hasattr(da, "isel") else None
             arr = np.asarray(part.data if part is not None else np.asarray(da.data).take(range(t0, t0 + nt), axis=dims.index(tname)))
-            out[...] = arr.transpose(sort)
+            out[...] = narrow(arr).transpose(sort)
         return reader, shape, dtype
 
-    def _member_reader(self, da, dims, member, only=None):
+    def _member_reader(self, da, dims, member, only=None, integer=False):
         """(reader, (M * T, ny, nx), dtype) of a 4-D variable: flat step m * T + t of the (M * T, lat, lon) series is step t of member
-        m, read as isel(member=m, time=slice) -- a chunk that spans two members in two pieces.  only=m: that member alone, (T, ny, nx)."""
+        m, read as isel(member=m, time=slice) -- a chunk that spans two members in two pieces.  only=m: that member alone, (T, ny, nx).
+        integer: as in _time_reader."""
         tname = self._time_name
         M, T = da.shape[dims.index(member)], da.shape[dims.index(tname)]
         dims3 = tuple(d for d in dims if d != member)                             # what isel(member=m) leaves
         sort3 = [dims3.index(d) for d in (tname, self._latitude_name, self._longitude_name)]
         shape = ((M if only is None else 1) * T,) + tuple(da.shape[dims.index(d)] for d in (self._latitude_name, self._longitude_name))
-        dtype = np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
+        dtype = np.dtype(np.int32) if integer else np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
+        narrow = _int32_chunk if integer else (lambda a: a)
 
         def reader(t0, nt, out):
             done = 0
@@ -1039,7 +1117,7 @@ class contrack(object):
                 m, t = divmod(t0 + done, T)
                 n = min(nt - done, T - t)
                 part = da.isel(**{member: m if only is None else only, tname: slice(t, t + n)})
-                out[done:done + n] = np.asarray(part.data).transpose(sort3)
+                out[done:done + n] = narrow(np.asarray(part.data)).transpose(sort3)
                 done += n
         return reader, shape, dtype
 
@@ -1188,29 +1266,89 @@ class contrack(object):
         return call(thr) if field is None else _track_field(trk, field[0], field[1], call)
 
     # ---- blocking frequency (README.rst:159-160), consumer of `flag` ------------------------------------------------------
-    def calc_frequency(self, flag='flag', groupby=None, above=0):
+    def _consumer_dims(self, name, what="flag variable"):
+        """(dims, member) of a variable run_lifecycle / calc_frequency consume: time, lat, lon in any order and at most one more
+        dimension (its name, else None) -- the member dimension run_contrack(segments=<dim>) tracks over"""
+        dims = tuple(self.ds[name].dims)
+        names = (self._time_name, self._latitude_name, self._longitude_name)
+        extra = [d for d in dims if d not in names]
+        if any(d not in dims for d in names) or len(extra) > 1 or len(set(dims)) != len(dims):
+            raise ValueError("the {} {!r} must have the dimensions {} and at most one more (a member dimension), it has {}".format(what, name, names, dims))
+        return dims, (extra[0] if extra else None)
+
+    def _dim_values(self, name, size):
+        """the coordinate of a dimension, or its indices if it has none"""
+        try:
+            vals = np.asarray(self.ds[name].data)
+        except (KeyError, AttributeError):
+            return np.arange(size)
+        return vals if vals.shape == (size,) else np.arange(size)
+
+    def _flat_slab(self, da, dims, member):
+        """the variable as (time, lat, lon), or with a member dimension as (member * time, lat, lon): flat step m * T + t"""
+        names = (self._time_name, self._latitude_name, self._longitude_name)
+        if member is None:
+            return np.asarray(da.data).transpose([dims.index(d) for d in names])
+        arr = np.asarray(da.data).transpose([dims.index(d) for d in (member,) + names])
+        return arr.reshape((-1,) + arr.shape[2:])
+
+    def calc_frequency(self, flag='flag', groupby=None, above=0, chunk_steps=None, pool=False):
         """percentage of time steps with flag > above at every grid point: xr.where(ds[flag] > above, 1, 0).sum(dim='time') /
         ntime * 100 -- the README's blocking frequency with above=1 -- or, with groupby ('month', 'season', 'year', ...), the same
         per value of time.<groupby> (ascending; seasons as xarray orders them: DJF, JJA, MAM, SON), as groupby(...).sum() /
         group size * 100.  Returns a labelled float64 array ('%') over the variable's own spatial dims, the group dim in the time
-        dim's place; it is not added to the dataset.  The count runs on the GPU (frequency_numpy)."""
+        dim's place; it is not added to the dataset.  The count runs on the GPU (frequency_numpy).
+        A 4-D flag (extension: time, lat, lon and a member dimension in any order, what run_contrack(segments=<dim>) writes) gives
+        the frequency of every member, the member dimension in its place, each group's size counted inside one member; pool=True
+        pools the members (the member dimension is dropped, a group's size is its size x members).  pool is ignored for a 3-D flag.
+        chunk_steps (extension): the flag is read slice by slice (`isel`, a chunk that spans two members in two pieces) and passes
+        through chunk-sized device buffers; the slab is never built on the host.  Same bits."""
         self._ensure_set_up()
         da = self.ds[flag]
-        dims = tuple(da.dims)
+        dims, member = self._consumer_dims(flag)
         names = (self._time_name, self._latitude_name, self._longitude_name)
-        slab = np.asarray(da.data).transpose([dims.index(d) for d in names])
         if groupby is None:
             ids, uniq = None, None
         else:
             ids, uniq = self._group_ids(groupby)
-        freq = frequency_numpy(slab, ids, above=above)
-        if groupby is None:
-            out_dims = tuple(d for d in dims if d != self._time_name)
-            data = freq.transpose([names[1:].index(d) for d in out_dims])
+        if member is None and chunk_steps is None:
+            slab = np.asarray(da.data).transpose([dims.index(d) for d in names])
+            freq = frequency_numpy(slab, ids, above=above)
         else:
-            out_dims = tuple(groupby if d == self._time_name else d for d in dims)
-            data = freq.transpose([((groupby,) + names[1:]).index(d) for d in out_dims])
+            if np.dtype(da.dtype).kind not in "iub":
+                raise ValueError("flag must be an integer field")
+            T = da.shape[dims.index(self._time_name)]
+            M = 1 if member is None else da.shape[dims.index(member)]
+            G = 1 if ids is None else len(uniq)
+            per_member = member is not None and not pool
+            gids = np.zeros(T, dtype=np.int32) if ids is None else ids
+            if per_member:                                       # the library sees group m * G + g
+                gids = (np.arange(M, dtype=np.int32)[:, None] * G + gids[None, :]).reshape(-1)
+            else:
+                gids = np.tile(gids, M)
+            if chunk_steps is None:
+                source, shape = self._flat_slab(da, dims, member), None
+            elif member is None:
+                source, shape, _ = self._time_reader(da, dims, integer=True)
+            else:
+                source, shape, _ = self._member_reader(da, dims, member, integer=True)
+            counts = frequency_numpy(source, gids if (per_member or ids is not None) else None, above=above, percent=False, chunk_steps=chunk_steps, shape=shape)
+            counts = counts.reshape((-1,) + counts.shape[-2:])
+            n = np.bincount(ids, minlength=G) if ids is not None else np.array([T])
+            n = np.tile(n, M) if per_member else n * M               # a group's size inside one member / over all of them
+            freq = frequency_percent(counts, n)
+            if per_member:
+                freq = freq.reshape((M, G) + freq.shape[1:])
+            if ids is None:
+                freq = freq[:, 0] if per_member else freq[0]
+        lead = ((member,) if member is not None and not pool else ()) + ((groupby,) if groupby is not None else ())
+        have = lead + names[1:]                                      # the axes of freq
+        gone = ((self._time_name,) if groupby is None else ()) + ((member,) if member is not None and pool else ())
+        out_dims = tuple(groupby if d == self._time_name else d for d in dims if d not in gone)
+        data = freq.transpose([have.index(d) for d in out_dims])
         coords = {} if groupby is None else {groupby: uniq}
+        if member in lead:
+            coords[member] = self._dim_values(member, da.shape[dims.index(member)])
         for name in (self._latitude_name, self._longitude_name):
             coords[name] = np.asarray(self.ds[name].data)
         attrs = {'units': '%', 'long_name': 'contrack frequency', 'standard_name': 'contrack frequency',
@@ -1231,7 +1369,7 @@ class contrack(object):
                 return [pd.Timestamp(v).strftime('%Y%m%d_%H') for v in vals]
             return [str(v) for v in vals]
 
-    def run_lifecycle(self, flag, variable):
+    def run_lifecycle(self, flag, variable, chunk_steps=None):
         """Intensity, size and centre of mass of every flagged contour at every time step.
 
         flag: name of the flag variable (output of run_contrack); variable: field used for intensity and centre of
@@ -1240,33 +1378,52 @@ class contrack(object):
 
         The per-(time step, id) sums run on the GPU (ctk_lifecycle_*, include/contrack_hip.h); the divisions,
         int() truncations, coordinate look-ups and rounding of contrack.py:876-901 are done here on the few
-        resulting rows."""
+        resulting rows.
+
+        A 4-D flag (extension: time, lat, lon and one member dimension in any order, what run_contrack(segments=<dim>) writes;
+        `variable` must have the same dims) is taken member after member: the frame gets a seventh column, named after that
+        dimension, with the member's coordinate value (its index if the dimension has no coordinate), and is sorted by (Flag,
+        member, Date) -- the reference's order for ids that are unique over the members, as run_contrack's are.
+        chunk_steps (extension): both variables are read slice by slice (`isel`, a chunk that spans two members in two pieces) and
+        pass through chunk-sized device buffers, that many time steps at a time (0: about 256 MB of field); neither slab is built
+        on the host or the device.  Flags wider than int32 are narrowed chunk by chunk; an id beyond int32 raises ValueError."""
         import pandas as pd
         logger.info("\nRun Lifecycle \n########### \n    flag:    {}\n    variable:    {}".format(flag, variable))
         self._ensure_set_up()
-        names = (self._time_name, self._latitude_name, self._longitude_name)
-
-        def slab(name):
-            da = self.ds[name]
-            return np.asarray(da.data).transpose([tuple(da.dims).index(d) for d in names])
-
-        flags, field = slab(flag), slab(variable)
-        if flags.dtype.kind not in "iub":
+        fda, vda = self.ds[flag], self.ds[variable]
+        fdims, member = self._consumer_dims(flag)
+        vdims = tuple(vda.dims)
+        if sorted(vdims) != sorted(fdims):
+            raise ValueError("the variable {!r} has dims {}, the flag variable {!r} has {}: they must be the same".format(variable, vdims, flag, fdims))
+        if np.dtype(fda.dtype).kind not in "iub":
             raise ValueError("flag variable {!r} is not an integer field".format(flag))
-        if flags.size and (flags.dtype.itemsize > 4 or flags.dtype == np.uint32) and \
-                (flags.max() > np.iinfo(np.int32).max or flags.min() < np.iinfo(np.int32).min):      # (nothing to check for int32 and narrower)
-            raise ValueError("flag ids beyond int32")
-        if field.dtype != np.float64:
-            field = field.astype(np.float32, copy=False)
         lat = np.asarray(self.ds[self._latitude_name].data)
         lon = np.asarray(self.ds[self._longitude_name].data)
         wrow = row_weights(lat, self._dlat, self._dlon)                                                 # contrack.py:847-848
-        trk = _tracker()
-        resident = self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, field.shape, field.dtype == np.float64)
-        # (the anomaly slab calc_anom left in HBM: only the flags cross PCIe)
-        rows = trk.lifecycle(flags, None, wrow, resident_f64=field.dtype == np.float64) if resident else trk.lifecycle(flags, field, wrow)
-        return pd.DataFrame(lifecycle_columns(rows, lat, lon, self._time_labels(), _tracker()),
-                            columns=['Flag', 'Date', 'Longitude', 'Latitude', 'Intensity', 'Size'])
+        T = fda.shape[fdims.index(self._time_name)]
+        period = None if member is None else T
+        vtype = np.dtype(np.float64) if np.dtype(vda.dtype) == np.float64 else np.dtype(np.float32)
+        if chunk_steps is None:
+            flags, field = self._flat_slab(fda, fdims, member), self._flat_slab(vda, vdims, member)
+            if field.dtype != np.float64:
+                field = field.astype(np.float32, copy=False)
+            # (the anomaly slab calc_anom left in HBM: only the flags cross PCIe)
+            resident = self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, field.shape, field.dtype == np.float64)
+            cols = lifecycle_numpy(flags, None if resident else field, wrow, lat, lon, self._time_labels(), dtype=field.dtype, period=period)
+        else:
+            if member is None:
+                fread, shape, _ = self._time_reader(fda, fdims, integer=True)
+                vread = self._time_reader(vda, vdims)[0]
+            else:
+                fread, shape, _ = self._member_reader(fda, fdims, member, integer=True)
+                vread = self._member_reader(vda, vdims, member)[0]
+            # (a variable of any other type than float64 becomes float32 in the copy into the chunk buffer, as in the resident call)
+            cols = lifecycle_numpy(fread, vread, wrow, lat, lon, self._time_labels(), chunk_steps=chunk_steps, shape=shape, dtype=vtype, period=period)
+        columns = ['Flag', 'Date', 'Longitude', 'Latitude', 'Intensity', 'Size']
+        if member is not None:
+            cols[member] = self._dim_values(member, fda.shape[fdims.index(member)])[cols.pop("Member")]
+            columns.append(member)
+        return pd.DataFrame(cols, columns=columns)
 
     # ---- utility (contrack.py:912-949) ---------------------------------------------------------------------------
     def greatcircle_dist(self, lon1, lat1, lon2, lat2):

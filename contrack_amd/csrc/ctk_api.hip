@@ -227,6 +227,14 @@ struct StreamIO {
     void *write_user = nullptr;
     void *host_out_v = nullptr;                    // ctk_anom_stream_*: the sink holds values of the slab's type, as an array or
     ctk_write_values_fn write_v = nullptr;         // through a writer of values
+    // a second slab that travels with the first, chunk by chunk (ctk_lifecycle_stream_*: the int32 flags beside the field): read before
+    // the first, through the output side's buffers (io_out, pin_out), which such a call does not need otherwise; esz2 = 0: none
+    const void *host_in2 = nullptr;
+    ctk_read_chunk_fn read2 = nullptr;
+    void *read2_user = nullptr;
+    size_t esz2 = 0;
+    const void *dev2 = nullptr;                    // where the second slab's chunk lies while `consume` runs
+    bool ahead = false;                            // `consume` waits for its results on the host: chunk k+1 is sent off BEFORE chunk k is consumed
     int64_t chunk = 0;                             // timesteps per chunk
     size_t esz = 4;
     double ms_read = 0, ms_write = 0, ms_in = 0, ms_out = 0;
@@ -265,6 +273,9 @@ struct ctk_handle {
     int64_t lc_path_T = -1; CtkLifePlan lc_plan = {0, 0, 0, 0, 0};
     int64_t lc_given_up = 0, lc_fb_launches = 0; int lc_attempts = 0, lc_sort = 0;
     std::vector<uint8_t> lc_rounds;                // per time step: rounds of k_lifecycle it took part in
+    bool lc_streamed = false;                      // the last call was ctk_lifecycle_stream_*: no slab is left for ctk_lifecycle_exact
+    std::vector<int64_t> lx_idx;                   // ... the rows its pick chose (indices into lc_host) and their exact records
+    std::vector<ctk_life_exact> lx_rec;
     DevBuf chunk_vals;                            // run values in the chunk order of k_relabel_v4
     // fused one-call path (ctk_seam_dev.hip): clusters of candidate labels, cluster root per group record; the pass runs without a
     // host hand-off and is validated from a device-written block of scalars after its only synchronisation
@@ -3145,21 +3156,48 @@ static int stream_setup(ctk_handle *h, size_t in_bytes, size_t out_bytes, bool p
     return CTK_OK;
 }
 
-// input phase: chunk k+1 travels (reader + H2D on the copy stream) while `consume` (k_threshold) works on chunk k
+// input phase: chunk k+1 travels (reader + H2D on the copy stream) while `consume` (k_threshold) works on chunk k.  A `consume` that
+// only queues work returns at once and the loop goes on to the next chunk; one that waits for the device (io.ahead) is called after
+// the next chunk has been sent off.
 static int stream_in(ctk_handle *h, bool f64, int64_t T, int ny, int nx, const std::function<int(const void *, int64_t, int64_t)> &consume)
 {
     StreamIO &io = *h->sio;
     const size_t plane = (size_t)ny * nx * io.esz, cbytes = (size_t)io.chunk * plane;
     (void)f64;
+    const size_t plane2 = (size_t)ny * nx * io.esz2, cbytes2 = (size_t)io.chunk * plane2;
     CTKCHK(stream_setup(h, cbytes, 0, io.read != nullptr));
+    if (io.esz2) CTKCHK(stream_setup(h, 0, cbytes2, io.read2 != nullptr));
     const double t_in = now_ms();
     io.passes_in++;
+    struct Chunk { int b = 0; int64_t t0 = 0, nt = 0; const void *dev = nullptr, *dev2 = nullptr; } prev;
+    auto use = [&](const Chunk &c) -> int {
+        HIPCHK(hipStreamWaitEvent(h->stream, h->ev_h2d[c.b], 0));
+        io.dev2 = c.dev2;
+        CTKCHK(consume(c.dev, c.t0, c.nt));
+        HIPCHK(hipEventRecord(h->ev_thr[c.b], h->stream));
+        return CTK_OK;
+    };
     int k = 0;
     for (int64_t t0 = 0; t0 < T; t0 += io.chunk, k++) {
         const int b = k & 1;
         const int64_t nt = std::min<int64_t>(io.chunk, T - t0);
         char *dev = (char *)h->io_in.p + (size_t)b * cbytes;
+        Chunk cur;
+        cur.b = b; cur.t0 = t0; cur.nt = nt; cur.dev = dev;
         if (k >= 2) HIPCHK(hipEventSynchronize(h->ev_thr[b]));                 // the device buffer (and its pinned twin) is free again
+        if (io.esz2) {
+            char *dev2 = (char *)h->io_out.p + (size_t)b * cbytes2;
+            const void *src2 = (const char *)io.host_in2 + (size_t)t0 * plane2;
+            if (io.read2) {
+                const double r0 = now_ms();
+                const int rc = io.read2(io.read2_user, t0, nt, h->pin_out[b]);
+                io.ms_read += now_ms() - r0;
+                if (rc) return ctk_set_error(CTK_E_INVALID, "the reader of the second slab returned %d for timesteps [%lld, %lld)", rc, (long long)t0, (long long)(t0 + nt));
+                src2 = h->pin_out[b];
+            }
+            HIPCHK(hipMemcpyAsync(dev2, src2, (size_t)nt * plane2, hipMemcpyHostToDevice, h->copy_stream));
+            cur.dev2 = dev2;
+        }
         if (io.read) {
             const double r0 = now_ms();
             const int rc = io.read(io.read_user, t0, nt, h->pin_in[b]);
@@ -3171,10 +3209,12 @@ static int stream_in(ctk_handle *h, bool f64, int64_t T, int ny, int nx, const s
             HIPCHK(hipMemcpyAsync(dev, (const char *)io.host_in + (size_t)t0 * plane, (size_t)nt * plane, hipMemcpyHostToDevice, h->copy_stream));
         }
         HIPCHK(hipEventRecord(h->ev_h2d[b], h->copy_stream));
-        HIPCHK(hipStreamWaitEvent(h->stream, h->ev_h2d[b], 0));
-        CTKCHK(consume(dev, t0, nt));
-        HIPCHK(hipEventRecord(h->ev_thr[b], h->stream));
+        if (io.ahead) {                                  // chunk k is on its way: now the chunk before it
+            if (k > 0) CTKCHK(use(prev));
+            prev = cur;
+        } else CTKCHK(use(cur));
     }
+    if (io.ahead && k > 0) CTKCHK(use(prev));
     io.ms_in += now_ms() - t_in;
     return CTK_OK;
 }
@@ -3417,24 +3457,25 @@ static_assert(sizeof(ctk_life_row) == sizeof(CtkLifeRowDev), "row layouts must a
 
 static_assert(CTK_LIFE_SW == LB_SW && CTK_LIFE_WAVES == LB_THREADS / 64, "ctk_forms.h restates the strip shape of ctk_lifecycle.hip");
 
-static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void *field_dev, bool f64, int64_t T, int ny, int nx, const float *wrow,
-                              int64_t *nrows)
-{
-    if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
-    if (T < 0 || ny < 1 || nx < 1 || !wrow || (T > 0 && (!flag_dev || !field_dev)))
-        return ctk_set_error(CTK_E_INVALID, "ctk_lifecycle: bad shape or null pointer");
-    if (ny > 65535 || nx > 65535 || T > 4000000) return ctk_set_error(CTK_E_RANGE, "ctk_lifecycle: grid %d x %d x %lld beyond the supported size", ny, nx, (long long)T);
-    HIPCHK(hipSetDevice(h->device));
-    h->lc_host.clear();
-    h->lc_path_T = -1;
-    h->lc_plan = CtkLifePlan{0, 0, 0, 0, 0};
-    h->lc_given_up = 0; h->lc_fb_launches = 0; h->lc_attempts = 0; h->lc_sort = 0;
-    h->lc_rounds.assign((size_t)T, 0);
-    if (nrows) *nrows = 0;
-    if (T == 0) { h->lc_path_T = 0; return CTK_OK; }
-    std::vector<int64_t> wlo(ny), whi(ny);
+// One pass of the reductions over the T time steps of a slab in device memory: the whole slab of a resident call, one chunk of a
+// streamed one (ctk_life_stream.hip).  life_launch queues the strip kernels and the copy of their counters, life_settle waits for
+// them, redoes the time steps they gave up and -- once -- everything, if the row table was too small.
+struct LifeRun {
+    const int32_t *flag = nullptr; const void *field = nullptr;
+    bool f64 = false; int64_t T = 0; int ny = 0, nx = 0;
     int32_t wshift = 0, limb_bits = 0;
-    CTKCHK(ctk_weights_to_limbs(wrow, ny, (int64_t)ny * nx, wlo.data(), whi.data(), &wshift, &limb_bits));
+    int64_t t_base = 0;                            // lc_rounds[t_base + t] counts the rounds of this pass's time step t
+    CtkLifePlan plan = {0, 0, 0, 0, 0};
+    size_t cap = 0;                                // rows the table holds
+    unsigned long long cnt[2] = {0, 0};            // rows written | time steps (work items) given up
+    int64_t given_up = 0, fb_launches = 0; int attempts = 0;
+};
+
+// the row weights of a call: limbs and float32 values to the device
+static int life_weights(ctk_handle *h, const float *wrow, int ny, int nx, int32_t *wshift, int32_t *limb_bits)
+{
+    std::vector<int64_t> wlo(ny), whi(ny);
+    CTKCHK(ctk_weights_to_limbs(wrow, ny, (int64_t)ny * nx, wlo.data(), whi.data(), wshift, limb_bits));
     CTKCHK(ensure(h, h->lc_wlo, (size_t)ny * 8));
     CTKCHK(ensure(h, h->lc_whi, (size_t)ny * 8));
     CTKCHK(ensure(h, h->lc_w, (size_t)ny * 4));
@@ -3443,29 +3484,16 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
     HIPCHK(hipMemcpyAsync(h->lc_whi.p, whi.data(), (size_t)ny * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->lc_w.p, wrow, (size_t)ny * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));          // wlo / whi are stack-lifetime vectors
-    const int nxw = (nx + 31) / 32;
-    const CtkLifePlan plan = ctk_life_plan(T, ny, nx, f64, (uintptr_t)flag_dev, (uintptr_t)field_dev);
-    h->lc_plan = plan;
-    const int ks = plan.ks;
-    size_t cap = std::max<size_t>(h->lc_rows.cap / sizeof(CtkLifeRowDev), (size_t)T * 16 + 1024);
-    unsigned long long cnt[2] = {0, 0};
-    h->lc_flag = flag_dev; h->lc_field = field_dev; h->lc_f64 = f64; h->lc_T = T; h->lc_ny = ny; h->lc_nx = nx;
-    auto launch = [&](const int32_t *work, unsigned items) -> int {
-        if (f64)
-            k_lifecycle<double><<<items, LC_THREADS, (size_t)ks * nxw * 4, h->stream>>>(flag_dev, (const double *)field_dev, ny, nx, nxw, ks, P<int64_t>(h->lc_wlo),
-                                                                                        P<int64_t>(h->lc_whi), P<float>(h->lc_w), wshift, limb_bits,
-                                                                                        P<CtkLifeRowDev>(h->lc_rows), cap, P<unsigned long long>(h->lc_cnt), work,
-                                                                                        P<unsigned char>(h->lc_ovf));
-        else
-            k_lifecycle<float><<<items, LC_THREADS, (size_t)ks * nxw * 4, h->stream>>>(flag_dev, (const float *)field_dev, ny, nx, nxw, ks, P<int64_t>(h->lc_wlo),
-                                                                                       P<int64_t>(h->lc_whi), P<float>(h->lc_w), wshift, limb_bits,
-                                                                                       P<CtkLifeRowDev>(h->lc_rows), cap, P<unsigned long long>(h->lc_cnt), work,
-                                                                                       P<unsigned char>(h->lc_ovf));
-        HIPCHK(hipGetLastError());
-        return CTK_OK;
-    };
-    // Banded form first (every byte read once, T x chunks workgroups); the time steps it gives up (more ids than its tables
-    // hold) are redone by k_lifecycle, which splits further by residue classes of the ids.
+    return CTK_OK;
+}
+
+// Banded form (every byte read once, T x chunks workgroups); the time steps it gives up (more ids than its tables hold) are
+// redone by k_lifecycle in life_settle, which splits further by residue classes of the ids.
+static int life_launch(ctk_handle *h, LifeRun &r)
+{
+    const int64_t T = r.T;
+    const int ny = r.ny, nx = r.nx, nxw = (nx + 31) / 32;
+    const CtkLifePlan &plan = r.plan;
     const int rw = plan.rw, nsx = plan.nsx, nby = plan.nby, nb = nsx * nby;
     const size_t gkey_bytes = (size_t)T * LB_GH * 4, gacc_bytes = (size_t)T * LB_GH * sizeof(CtkLifeAcc);
     const size_t occ_bytes = (size_t)T * LB_KS * nxw * 4, cp_bytes = (size_t)T * LB_KS * nx * 8;
@@ -3476,42 +3504,65 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
     CTKCHK(ensure(h, h->lc_cp, cp_bytes));
     int32_t *gkey = P<int32_t>(h->lc_gtab);
     CtkLifeAcc *gacc = (CtkLifeAcc *)((char *)h->lc_gtab.p + gkey_bytes);
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        h->lc_attempts = attempt + 1;                 // (what follows describes the attempt whose rows are returned)
-        h->lc_given_up = 0; h->lc_fb_launches = 0;
-        std::fill(h->lc_rounds.begin(), h->lc_rounds.end(), (uint8_t)0);
-        CTKCHK(ensure(h, h->lc_rows, cap * sizeof(CtkLifeRowDev)));
-        cap = h->lc_rows.cap / sizeof(CtkLifeRowDev);
-        CTKCHK(ensure(h, h->lc_ovf, (size_t)T));
-        HIPCHK(hipMemsetAsync(h->lc_cnt.p, 0, 16, h->stream));
-        HIPCHK(hipMemsetAsync(h->lc_ovf.p, 0, (size_t)T, h->stream));
-        HIPCHK(hipMemsetAsync(h->lc_gtab.p, 0, gkey_bytes + gacc_bytes, h->stream));
-        HIPCHK(hipMemsetAsync(h->lc_occ.p, 0, occ_bytes, h->stream));
-        HIPCHK(hipMemsetAsync(h->lc_cp.p, 0, cp_bytes, h->stream));
-        k_life_seam<<<(unsigned)T, 64, 0, h->stream>>>(flag_dev, ny, nx, P<int32_t>(h->lc_cross), P<unsigned char>(h->lc_ovf));
-        {
-            const bool vec = plan.vec != 0;
-            const unsigned grid = (unsigned)(T * nb);
+    r.attempts++;                                     // (what follows describes the attempt whose rows are returned)
+    r.given_up = 0; r.fb_launches = 0;
+    std::fill(h->lc_rounds.begin() + r.t_base, h->lc_rounds.begin() + r.t_base + T, (uint8_t)0);
+    CTKCHK(ensure(h, h->lc_rows, r.cap * sizeof(CtkLifeRowDev)));
+    r.cap = h->lc_rows.cap / sizeof(CtkLifeRowDev);
+    const size_t cap = r.cap;
+    CTKCHK(ensure(h, h->lc_ovf, (size_t)T));
+    HIPCHK(hipMemsetAsync(h->lc_cnt.p, 0, 16, h->stream));
+    HIPCHK(hipMemsetAsync(h->lc_ovf.p, 0, (size_t)T, h->stream));
+    HIPCHK(hipMemsetAsync(h->lc_gtab.p, 0, gkey_bytes + gacc_bytes, h->stream));
+    HIPCHK(hipMemsetAsync(h->lc_occ.p, 0, occ_bytes, h->stream));
+    HIPCHK(hipMemsetAsync(h->lc_cp.p, 0, cp_bytes, h->stream));
+    k_life_seam<<<(unsigned)T, 64, 0, h->stream>>>(r.flag, ny, nx, P<int32_t>(h->lc_cross), P<unsigned char>(h->lc_ovf));
+    {
+        const bool vec = plan.vec != 0;
+        const unsigned grid = (unsigned)(T * nb);
 #define CTK_LIFE_STRIPS(VT, VEC)                                                                                                                       \
-    k_life_strips<VT, VEC><<<grid, LB_THREADS, 0, h->stream>>>(flag_dev, (const VT *)field_dev, ny, nx, nxw, nsx, nby, rw, P<int64_t>(h->lc_wlo),      \
+    k_life_strips<VT, VEC><<<grid, LB_THREADS, 0, h->stream>>>(r.flag, (const VT *)r.field, ny, nx, nxw, nsx, nby, rw, P<int64_t>(h->lc_wlo),          \
                                                                P<int64_t>(h->lc_whi), P<float>(h->lc_w), P<int32_t>(h->lc_cross), gkey, gacc,         \
                                                                P<unsigned>(h->lc_occ), P<double>(h->lc_cp), P<unsigned char>(h->lc_ovf))
-            if (f64) { if (vec) CTK_LIFE_STRIPS(double, true); else CTK_LIFE_STRIPS(double, false); }
-            else { if (vec) CTK_LIFE_STRIPS(float, true); else CTK_LIFE_STRIPS(float, false); }
+        if (r.f64) { if (vec) CTK_LIFE_STRIPS(double, true); else CTK_LIFE_STRIPS(double, false); }
+        else { if (vec) CTK_LIFE_STRIPS(float, true); else CTK_LIFE_STRIPS(float, false); }
 #undef CTK_LIFE_STRIPS
-        }
-        k_life_finish<<<(unsigned)T, LB_GH, 0, h->stream>>>(nx, nxw, P<int32_t>(h->lc_cross), gkey, gacc, P<unsigned>(h->lc_occ), P<double>(h->lc_cp), wshift,
-                                                            limb_bits, P<CtkLifeRowDev>(h->lc_rows), cap, P<unsigned long long>(h->lc_cnt),
-                                                            P<unsigned char>(h->lc_ovf));
+    }
+    k_life_finish<<<(unsigned)T, LB_GH, 0, h->stream>>>(nx, nxw, P<int32_t>(h->lc_cross), gkey, gacc, P<unsigned>(h->lc_occ), P<double>(h->lc_cp), r.wshift,
+                                                        r.limb_bits, P<CtkLifeRowDev>(h->lc_rows), cap, P<unsigned long long>(h->lc_cnt),
+                                                        P<unsigned char>(h->lc_ovf));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(r.cnt, h->lc_cnt.p, 16, hipMemcpyDeviceToHost, h->stream));
+    return CTK_OK;
+}
+
+static int life_settle(ctk_handle *h, LifeRun &r)
+{
+    const int64_t T = r.T;
+    const int ny = r.ny, nx = r.nx, nxw = (nx + 31) / 32, ks = r.plan.ks;
+    auto launch = [&](const int32_t *work, unsigned items) -> int {
+        if (r.f64)
+            k_lifecycle<double><<<items, LC_THREADS, (size_t)ks * nxw * 4, h->stream>>>(r.flag, (const double *)r.field, ny, nx, nxw, ks, P<int64_t>(h->lc_wlo),
+                                                                                        P<int64_t>(h->lc_whi), P<float>(h->lc_w), r.wshift, r.limb_bits,
+                                                                                        P<CtkLifeRowDev>(h->lc_rows), r.cap, P<unsigned long long>(h->lc_cnt), work,
+                                                                                        P<unsigned char>(h->lc_ovf));
+        else
+            k_lifecycle<float><<<items, LC_THREADS, (size_t)ks * nxw * 4, h->stream>>>(r.flag, (const float *)r.field, ny, nx, nxw, ks, P<int64_t>(h->lc_wlo),
+                                                                                       P<int64_t>(h->lc_whi), P<float>(h->lc_w), r.wshift, r.limb_bits,
+                                                                                       P<CtkLifeRowDev>(h->lc_rows), r.cap, P<unsigned long long>(h->lc_cnt), work,
+                                                                                       P<unsigned char>(h->lc_ovf));
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(cnt, h->lc_cnt.p, 16, hipMemcpyDeviceToHost, h->stream));
+        return CTK_OK;
+    };
+    unsigned long long *cnt = r.cnt;
+    for (;;) {
         HIPCHK(hipStreamSynchronize(h->stream));
         std::vector<int32_t> work;
         if (cnt[1]) {
             std::vector<unsigned char> ov((size_t)T);
             HIPCHK(hipMemcpy(ov.data(), h->lc_ovf.p, (size_t)T, hipMemcpyDeviceToHost));
             for (int64_t t = 0; t < T; ++t) if (ov[(size_t)t]) { work.push_back((int32_t)t); work.push_back(1); work.push_back(0); }
-            h->lc_given_up = (int64_t)(work.size() / 3);
+            r.given_up = (int64_t)(work.size() / 3);
         }
         while (!work.empty()) {
             const size_t items = work.size() / 3;
@@ -3523,11 +3574,11 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
             unsigned long long zero = 0;
             HIPCHK(hipMemcpyAsync(P<unsigned long long>(h->lc_cnt) + 1, &zero, 8, hipMemcpyHostToDevice, h->stream));
             CTKCHK(launch(P<int32_t>(h->lc_work), (unsigned)items));
-            h->lc_fb_launches++;
+            r.fb_launches++;
             for (size_t i = 0; i < items; ++i) {          // (the items of one time step follow each other)
                 if (i && work[3 * i] == work[3 * (i - 1)]) continue;
-                uint8_t &r = h->lc_rounds[(size_t)work[3 * i]];
-                if (r < 255) r++;
+                uint8_t &rd = h->lc_rounds[(size_t)(r.t_base + work[3 * i])];
+                if (rd < 255) rd++;
             }
             HIPCHK(hipMemcpyAsync(cnt, h->lc_cnt.p, 16, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
@@ -3540,23 +3591,26 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
             }
             work.swap(next);
         }
-        if (cnt[0] <= cap) break;
-        if (attempt == 1) return ctk_set_error(CTK_E_INTERNAL, "ctk_lifecycle: row count changed between passes");
-        cap = (size_t)cnt[0];
+        if (cnt[0] <= r.cap) break;
+        if (r.attempts == 2) return ctk_set_error(CTK_E_INTERNAL, "ctk_lifecycle: row count changed between passes");
+        r.cap = (size_t)cnt[0];
+        CTKCHK(life_launch(h, r));
     }
-    const size_t n = (size_t)cnt[0];
-    // rows leave the device in arbitrary order; the reference's frame is sorted by (Flag, Date) (contrack.py:906).
-    // Two stable counting sorts (by t, then by label) when the label range is small, else a comparison sort of keys.
-    CTKCHK(ensure_host(&h->h_cand, &h->h_cand_cap, std::max<size_t>(n, 1) * sizeof(ctk_life_row), true));     // pinned landing area
-    ctk_life_row *land = (ctk_life_row *)h->h_cand;
-    if (n) HIPCHK(hipMemcpy(land, h->lc_rows.p, n * sizeof(ctk_life_row), hipMemcpyDeviceToHost));
+    return CTK_OK;
+}
+
+// rows leave the device in arbitrary order; the reference's frame is sorted by (Flag, Date) (contrack.py:906).
+// Two stable counting sorts (by t, then by label) when the label range is small, else a comparison sort of keys.
+// land[0..n) with t in [0, T) -> out; returns the order taken (0 counting sorts, 1 comparison sort)
+static int life_sort(ctk_handle *h, const ctk_life_row *land, size_t n, int64_t T, std::vector<ctk_life_row> &out)
+{
     h->lc_tmp.resize(n);
-    h->lc_host.resize(n);
+    out.resize(n);
     int32_t lmin = INT32_MAX, lmax = INT32_MIN;
     for (size_t i = 0; i < n; ++i) { lmin = std::min(lmin, land[i].label); lmax = std::max(lmax, land[i].label); }
     const uint64_t lrange = n ? (uint64_t)((int64_t)lmax - (int64_t)lmin) + 1 : 0;
-    h->lc_sort = (!n || lrange <= 8 * (uint64_t)n + 65536) ? 0 : 1;
-    if (!h->lc_sort) {
+    const int order = (!n || lrange <= 8 * (uint64_t)n + 65536) ? 0 : 1;
+    if (!order) {
         std::vector<uint32_t> &cnt = h->lc_cnt_host;
         cnt.assign((size_t)T + 1, 0);
         for (size_t i = 0; i < n; ++i) cnt[(size_t)land[i].t + 1]++;
@@ -3565,15 +3619,71 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
         cnt.assign((size_t)lrange + 1, 0);
         for (size_t i = 0; i < n; ++i) cnt[(size_t)((int64_t)h->lc_tmp[i].label - lmin) + 1]++;
         for (uint64_t k = 0; k < lrange; ++k) cnt[(size_t)k + 1] += cnt[(size_t)k];
-        for (size_t i = 0; i < n; ++i) h->lc_host[cnt[(size_t)((int64_t)h->lc_tmp[i].label - lmin)]++] = h->lc_tmp[i];   // by label, stable
+        for (size_t i = 0; i < n; ++i) out[cnt[(size_t)((int64_t)h->lc_tmp[i].label - lmin)]++] = h->lc_tmp[i];   // by label, stable
     } else {
         std::vector<std::pair<uint64_t, uint32_t>> &keys = h->lc_keys;
         keys.resize(n);
         for (size_t i = 0; i < n; ++i)
             keys[i] = {((uint64_t)((uint32_t)land[i].label ^ 0x80000000u) << 32) | (uint32_t)land[i].t, (uint32_t)i};
         std::sort(keys.begin(), keys.end());
-        for (size_t i = 0; i < n; ++i) h->lc_host[i] = land[keys[i].second];
+        for (size_t i = 0; i < n; ++i) out[i] = land[keys[i].second];
     }
+    return order;
+}
+
+// the rows of a settled pass: from the device into the pinned landing area
+static int life_land(ctk_handle *h, size_t n, ctk_life_row **land)
+{
+    CTKCHK(ensure_host(&h->h_cand, &h->h_cand_cap, std::max<size_t>(n, 1) * sizeof(ctk_life_row), true));     // pinned landing area
+    *land = (ctk_life_row *)h->h_cand;
+    if (n) HIPCHK(hipMemcpy(*land, h->lc_rows.p, n * sizeof(ctk_life_row), hipMemcpyDeviceToHost));
+    return CTK_OK;
+}
+
+static int life_check_shape(int64_t T, int ny, int nx)
+{
+    if (ny > 65535 || nx > 65535 || T > 4000000) return ctk_set_error(CTK_E_RANGE, "ctk_lifecycle: grid %d x %d x %lld beyond the supported size", ny, nx, (long long)T);
+    return CTK_OK;
+}
+
+// a call begins: nothing of the last one is left to ask for
+static void life_reset(ctk_handle *h, int64_t T)
+{
+    h->lc_host.clear();
+    h->lc_path_T = -1;
+    h->lc_plan = CtkLifePlan{0, 0, 0, 0, 0};
+    h->lc_given_up = 0; h->lc_fb_launches = 0; h->lc_attempts = 0; h->lc_sort = 0;
+    h->lc_rounds.assign((size_t)T, 0);
+    h->lc_streamed = false;
+    h->lx_idx.clear(); h->lx_rec.clear();
+}
+
+static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void *field_dev, bool f64, int64_t T, int ny, int nx, const float *wrow,
+                              int64_t *nrows)
+{
+    if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
+    if (T < 0 || ny < 1 || nx < 1 || !wrow || (T > 0 && (!flag_dev || !field_dev)))
+        return ctk_set_error(CTK_E_INVALID, "ctk_lifecycle: bad shape or null pointer");
+    CTKCHK(life_check_shape(T, ny, nx));
+    HIPCHK(hipSetDevice(h->device));
+    life_reset(h, T);
+    if (nrows) *nrows = 0;
+    if (T == 0) { h->lc_path_T = 0; return CTK_OK; }
+    LifeRun r;
+    r.flag = flag_dev; r.field = field_dev; r.f64 = f64; r.T = T; r.ny = ny; r.nx = nx;
+    CTKCHK(life_weights(h, wrow, ny, nx, &r.wshift, &r.limb_bits));
+    r.plan = ctk_life_plan(T, ny, nx, f64, (uintptr_t)flag_dev, (uintptr_t)field_dev);
+    h->lc_plan = r.plan;
+    r.cap = std::max<size_t>(h->lc_rows.cap / sizeof(CtkLifeRowDev), (size_t)T * 16 + 1024);
+    h->lc_flag = flag_dev; h->lc_field = field_dev; h->lc_f64 = f64; h->lc_T = T; h->lc_ny = ny; h->lc_nx = nx;
+    int rc = life_launch(h, r);
+    if (rc == CTK_OK) rc = life_settle(h, r);
+    h->lc_attempts = r.attempts; h->lc_given_up = r.given_up; h->lc_fb_launches = r.fb_launches;
+    CTKCHK(rc);
+    const size_t n = (size_t)r.cnt[0];
+    ctk_life_row *land = nullptr;
+    CTKCHK(life_land(h, n, &land));
+    h->lc_sort = life_sort(h, land, n, T, h->lc_host);
     if (nrows) *nrows = (int64_t)n;
     h->lc_path_T = T;
     return CTK_OK;
@@ -3639,21 +3749,32 @@ extern "C" int ctk_lifecycle_f64(ctk_handle *h, const int32_t *flag, const doubl
 {
     return lifecycle_host_impl(h, flag, field, true, T, ny, nx, wrow, nrows);
 }
+static int life_exact_keys(ctk_handle *h, const int32_t *flag_dev, const void *field_dev, bool f64, int ny, int nx, const std::vector<CtkLifeKey> &keys,
+                           ctk_life_exact *out);
 // the listed rows (indices into the sorted rows of the last ctk_lifecycle_* call) re-evaluated in the reference's own summation orders
 extern "C" int ctk_lifecycle_exact(ctk_handle *h, const int64_t *row_idx, int64_t n, ctk_life_exact *out)
 {
-    static_assert(sizeof(ctk_life_exact) == sizeof(CtkLifeExact), "row layouts must agree");
     if (!h || n < 0 || (n > 0 && (!row_idx || !out))) return ctk_set_error(CTK_E_INVALID, "ctk_lifecycle_exact: bad arguments");
     if (n == 0) return CTK_OK;
+    if (h->lc_streamed) return ctk_set_error(CTK_E_STATE, "ctk_lifecycle_exact: the last call was streamed, its slabs are gone (ctk_lifecycle_stream_exact holds the rows it picked)");
     if (!h->lc_flag || !h->lc_field) return ctk_set_error(CTK_E_STATE, "ctk_lifecycle_exact needs a ctk_lifecycle_* call first");
     HIPCHK(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
     std::vector<CtkLifeKey> keys((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         if (row_idx[i] < 0 || (size_t)row_idx[i] >= h->lc_host.size()) return ctk_set_error(CTK_E_INVALID, "ctk_lifecycle_exact: row %lld out of range", (long long)row_idx[i]);
         const ctk_life_row &r = h->lc_host[(size_t)row_idx[i]];
         keys[(size_t)i] = CtkLifeKey{r.t, r.label, r.shift, r.pad};
     }
+    return life_exact_keys(h, h->lc_flag, h->lc_field, h->lc_f64, h->lc_ny, h->lc_nx, keys, out);
+}
+
+// keys[i]: (t, label, shift, row extent) of a row of the slab at flag_dev / field_dev, t counted from the slab's first plane
+static int life_exact_keys(ctk_handle *h, const int32_t *flag_dev, const void *field_dev, bool f64, int ny, int nx, const std::vector<CtkLifeKey> &keys,
+                           ctk_life_exact *out)
+{
+    static_assert(sizeof(ctk_life_exact) == sizeof(CtkLifeExact), "row layouts must agree");
+    const int64_t n = (int64_t)keys.size();
+    hipStream_t s = h->stream;
     CTKCHK(ensure(h, h->lc_ekeys, (size_t)n * sizeof(CtkLifeKey)));
     CTKCHK(ensure(h, h->lc_offs, (size_t)n * 16));                           // pixel offsets, row-table offsets
     CTKCHK(ensure(h, h->lc_out, (size_t)(n + 1) * sizeof(CtkLifeExact) + (size_t)n * 4));      // the rows | the kernel's failure word | the pixel counts
@@ -3663,8 +3784,8 @@ extern "C" int ctk_lifecycle_exact(ctk_handle *h, const int64_t *row_idx, int64_
     int max_rows = 1;
     for (int64_t i = 0; i < n; ++i) {
         const uint32_t pad = (uint32_t)keys[(size_t)i].pad;
-        const int ya = (int)(pad & 0xffffu), yb = std::min(h->lc_ny - 1, (int)(pad >> 16));
-        if (yb < ya) return ctk_set_error(CTK_E_INTERNAL, "ctk_lifecycle_exact: row %lld has no row extent", (long long)row_idx[i]);
+        const int ya = (int)(pad & 0xffffu), yb = std::min(ny - 1, (int)(pad >> 16));
+        if (yb < ya) return ctk_set_error(CTK_E_INTERNAL, "ctk_lifecycle_exact: row %lld of the list has no row extent", (long long)i);
         offs[(size_t)(n + i)] = rtotal; rtotal += 3 * (uint64_t)(yb - ya + 1);
         max_rows = std::max(max_rows, yb - ya + 1);
     }
@@ -3674,8 +3795,8 @@ extern "C" int ctk_lifecycle_exact(ctk_handle *h, const int64_t *row_idx, int64_
     uint32_t *d_fail = reinterpret_cast<uint32_t *>(P<CtkLifeExact>(h->lc_out) + n);
     uint32_t *d_counts = d_fail + sizeof(CtkLifeExact) / 4;
     const dim3 rgrid((unsigned)n, (unsigned)((max_rows + 3) / 4));           // (x: the listed row, y: four rows of its row extent)
-    k_life_rows<<<rgrid, 256, 0, s>>>(h->lc_flag, P<CtkLifeKey>(h->lc_ekeys), P<uint64_t>(h->lc_offs) + n, h->lc_ny, h->lc_nx, P<uint32_t>(h->lc_sp));
-    k_life_rowscan<<<(unsigned)n, 256, 0, s>>>(P<CtkLifeKey>(h->lc_ekeys), P<uint64_t>(h->lc_offs) + n, h->lc_ny, P<uint32_t>(h->lc_sp), d_counts);
+    k_life_rows<<<rgrid, 256, 0, s>>>(flag_dev, P<CtkLifeKey>(h->lc_ekeys), P<uint64_t>(h->lc_offs) + n, ny, nx, P<uint32_t>(h->lc_sp));
+    k_life_rowscan<<<(unsigned)n, 256, 0, s>>>(P<CtkLifeKey>(h->lc_ekeys), P<uint64_t>(h->lc_offs) + n, ny, P<uint32_t>(h->lc_sp), d_counts);
     HIPCHK(hipGetLastError());
     std::vector<uint32_t> counts((size_t)n);
     HIPCHK(hipMemcpyAsync(counts.data(), d_counts, (size_t)n * 4, hipMemcpyDeviceToHost, s));
@@ -3690,12 +3811,12 @@ extern "C" int ctk_lifecycle_exact(ctk_handle *h, const int64_t *row_idx, int64_
     HIPCHK(hipMemsetAsync(d_fail, 0, 4, s));
     double *d_sw = P<double>(h->lc_sw);
     const size_t st = px / 8;
-    if (h->lc_f64)
-        k_life_lists<double><<<rgrid, 256, 0, s>>>(h->lc_flag, (const double *)h->lc_field, P<float>(h->lc_w), P<CtkLifeKey>(h->lc_ekeys), P<uint64_t>(h->lc_offs), P<uint64_t>(h->lc_offs) + n,
-                                                   h->lc_ny, h->lc_nx, d_sw, d_sw + st, d_sw + 2 * st, d_sw + 3 * st, d_sw + 4 * st, P<uint32_t>(h->lc_sp));
+    if (f64)
+        k_life_lists<double><<<rgrid, 256, 0, s>>>(flag_dev, (const double *)field_dev, P<float>(h->lc_w), P<CtkLifeKey>(h->lc_ekeys), P<uint64_t>(h->lc_offs), P<uint64_t>(h->lc_offs) + n,
+                                                   ny, nx, d_sw, d_sw + st, d_sw + 2 * st, d_sw + 3 * st, d_sw + 4 * st, P<uint32_t>(h->lc_sp));
     else
-        k_life_lists<float><<<rgrid, 256, 0, s>>>(h->lc_flag, (const float *)h->lc_field, P<float>(h->lc_w), P<CtkLifeKey>(h->lc_ekeys), P<uint64_t>(h->lc_offs), P<uint64_t>(h->lc_offs) + n,
-                                                  h->lc_ny, h->lc_nx, d_sw, d_sw + st, d_sw + 2 * st, d_sw + 3 * st, d_sw + 4 * st, P<uint32_t>(h->lc_sp));
+        k_life_lists<float><<<rgrid, 256, 0, s>>>(flag_dev, (const float *)field_dev, P<float>(h->lc_w), P<CtkLifeKey>(h->lc_ekeys), P<uint64_t>(h->lc_offs), P<uint64_t>(h->lc_offs) + n,
+                                                  ny, nx, d_sw, d_sw + st, d_sw + 2 * st, d_sw + 3 * st, d_sw + 4 * st, P<uint32_t>(h->lc_sp));
 #define CTK_LX_LAUNCH(G)                                                                                                                                   \
     k_life_exact<G><<<(unsigned)n, 256 * G, 0, s>>>(P<uint64_t>(h->lc_offs), d_counts, d_sw, d_sw + st, d_sw + 2 * st, d_sw + 3 * st, d_sw + 4 * st,         \
                                                     P<CtkLifeExact>(h->lc_out), d_fail)
@@ -3722,6 +3843,7 @@ extern "C" int ctk_lifecycle_rows(ctk_handle *h, ctk_life_row *rows, int64_t cap
 #include "ctk_anom.hip"
 #include "ctk_anom_seg.hip"
 #include "ctk_freq.hip"
+#include "ctk_life_stream.hip"
 #include "ctk_pctl.hip"
 #include "ctk_pfield.hip"
 

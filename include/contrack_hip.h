@@ -415,6 +415,28 @@ typedef struct ctk_life_exact {
     double area, swv, s, sy, sx;       /* np.sum(w), np.sum(w * v), sum p, sum p * y, sum p * x'   (p = v * w) */
 } ctk_life_exact;
 int ctk_lifecycle_exact(ctk_handle *h, const int64_t *row_idx, int64_t n, ctk_life_exact *out);
+/* ctk_lifecycle_stream_*: the same rows with both slabs passing through chunk-sized device buffers -- two chunks of flags, two of
+ * the field and the per-time-step tables of one chunk are all the device holds, so a flag written by ctk_track_stream_* can be
+ * consumed.  Host arrays (_f32 / _f64) or readers (_cb: ctk_read_chunk_fn, contract and threading rules of ctk_track_stream_cb's
+ * reader; called once per chunk in increasing t0, flag_reader -- int32 elements -- before field_reader, each filling pinned memory
+ * the library owns).  chunk_steps: time steps per chunk, 0: about 256 MB of field; chunk_steps >= T is one chunk.  The upload of
+ * chunk k+1 runs under the reductions of chunk k.
+ * The rounding-boundary rows are chosen while their chunk is still on the device: after a chunk's reductions `pick` gets that
+ * chunk's rows, sorted by (label, t) with t GLOBAL, fills idx[0..*nidx) with ascending indices into them and returns 0 (nonzero
+ * aborts the call with CTK_E_INVALID; pick = NULL: no rows); those rows are re-evaluated as by ctk_lifecycle_exact.
+ * After the call the handle holds all rows as after ctk_lifecycle_* (ctk_lifecycle_rows); ctk_lifecycle_stream_exact copies out the
+ * *nexact picked rows as ascending indices into that sorted order with their records (cap: room in both arrays).
+ * ctk_lifecycle_exact returns CTK_E_STATE after a streamed call -- the slabs are gone -- until the next resident call.  A failing
+ * reader, a failing pick or a device error leaves the handle usable.  ctk_stream_times reports the readers and the input phase. */
+typedef int (*ctk_life_pick_fn)(void *user, const ctk_life_row *rows, int64_t n, int64_t *idx, int64_t *nidx);
+int ctk_lifecycle_stream_f32(ctk_handle *h, const int32_t *flag, const float *field, int64_t T, int ny, int nx, const float *wrow, int64_t chunk_steps,
+                             ctk_life_pick_fn pick, void *pick_user, int64_t *nrows, int64_t *nexact);
+int ctk_lifecycle_stream_f64(ctk_handle *h, const int32_t *flag, const double *field, int64_t T, int ny, int nx, const float *wrow, int64_t chunk_steps,
+                             ctk_life_pick_fn pick, void *pick_user, int64_t *nrows, int64_t *nexact);
+int ctk_lifecycle_stream_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, int64_t T, int ny, int nx, ctk_read_chunk_fn flag_reader,
+                            void *flag_user, ctk_read_chunk_fn field_reader, void *field_user, const float *wrow, int64_t chunk_steps,
+                            ctk_life_pick_fn pick, void *pick_user, int64_t *nrows, int64_t *nexact);
+int ctk_lifecycle_stream_exact(ctk_handle *h, int64_t *row_idx, ctk_life_exact *out, int64_t cap);
 
 /* ---- next rows N2 / N3: the producer of the slab on the device ----------------------------------------------------------
  * ctk_anom_*: contrack.calc_clim / calc_anom (contrack/contrack.py:458-581) on a host slab x (T, ny, nx):
