@@ -24,7 +24,7 @@ EXPORTS = [
     "ctk_track_f32_dev", "ctk_track_f64", "ctk_track_f64_dev", "ctk_release_io", "ctk_shard_label2d", "ctk_shard_label2d_f64", "ctk_shard_halo_size", "ctk_shard_halo_export",
     "ctk_shard_halo_import", "ctk_shard_overlap", "ctk_shard_tables", "ctk_resolve", "ctk_result_free",
     "ctk_result_info", "ctk_result_arrays", "ctk_result_nshards", "ctk_weights_to_limbs", "ctk_shard_extents", "ctk_shard_write",
-    "ctk_shard_count_tracked", "ctk_debug_mask", "ctk_debug_label2d", "ctk_debug_set_pair_capacity", "ctk_debug_set_mailbox", "ctk_debug_set_seam_caps", "ctk_debug_set_spin", "ctk_debug_set_small_threads", "ctk_debug_forms", "ctk_debug_np_sum", "ctk_debug_boundary_resolve", "ctk_debug_boundary_resolve_breaks", "ctk_set_timing", "ctk_get_timings", "ctk_get_timing_sums", "ctk_set_device_resolve", "ctk_set_fused_pass", "ctk_set_result_transfer", "ctk_expand_runs_host", "ctk_set_filter_round", "ctk_get_stats", "ctk_get_stats_n", "ctk_debug_stream_ceiling", "ctk_debug_time_relabel",
+    "ctk_shard_count_tracked", "ctk_debug_mask", "ctk_debug_label2d", "ctk_debug_set_pair_capacity", "ctk_debug_set_mailbox", "ctk_debug_set_seam_caps", "ctk_debug_shard_exchange", "ctk_debug_set_shared_ops_reserve", "ctk_debug_set_spin", "ctk_debug_set_small_threads", "ctk_debug_forms", "ctk_debug_np_sum", "ctk_debug_boundary_resolve", "ctk_debug_boundary_resolve_breaks", "ctk_set_timing", "ctk_get_timings", "ctk_get_timing_sums", "ctk_set_device_resolve", "ctk_set_fused_pass", "ctk_set_result_transfer", "ctk_expand_runs_host", "ctk_set_filter_round", "ctk_get_stats", "ctk_get_stats_n", "ctk_debug_stream_ceiling", "ctk_debug_time_relabel",
     "ctk_dev_malloc", "ctk_dev_free", "ctk_host_alloc", "ctk_host_free", "ctk_host_register", "ctk_host_unregister", "ctk_memcpy_h2d", "ctk_memcpy_d2h", "ctk_sync", "ctk_stream",
     "ctk_synth_fill",
     "ctk_comm_unique_id", "ctk_comm_init_rccl", "ctk_comm_group_create", "ctk_comm_group_destroy", "ctk_comm_init_local", "ctk_comm_init_shm",
@@ -160,6 +160,8 @@ def lib():
     L.ctk_debug_set_pair_capacity.argtypes = [p, C.c_uint32]
     L.ctk_debug_set_mailbox.argtypes = [p, C.c_uint32, C.c_uint32]
     L.ctk_debug_set_seam_caps.argtypes = [p, i32, i32]
+    L.ctk_debug_shard_exchange.argtypes = [p, p]
+    L.ctk_debug_set_shared_ops_reserve.argtypes = [p, i64]
     L.ctk_debug_set_spin.argtypes = [p, dbl, i32]
     L.ctk_debug_set_small_threads.argtypes = [p, i32, i32, i32]
     L.ctk_debug_forms.argtypes = [C.POINTER(FormQuery), C.POINTER(FormPlan)]
@@ -1371,6 +1373,21 @@ class Tracker:
 
     def debug_set_seam_caps(self, labels, ops):
         check(lib().ctk_debug_set_seam_caps(self._h, int(labels), int(ops)))
+
+    def debug_shard_exchange(self):
+        """test hook: what the last track_sharded_dev call on this handle decided at its exchanges (include/contrack_hip_debug.h).
+        form: 0 device; host-driven bits 1 no device attempt, 2 shared operations beyond the reserve, 4 a rank's driver gave up"""
+        v = np.zeros(12, dtype=np.int64)
+        check(lib().ctk_debug_shard_exchange(self._h, v.ctypes.data))
+        lo, hi = (lambda x: int(x) & 0xffffffff), (lambda x: (int(x) >> 32) & 0xffffffff)
+        return dict(capB=int(v[0]), capB_repeats=int(v[1]), nlast=lo(v[2]), nh=hi(v[2]), capC=lo(v[3]), capD=hi(v[3]), x5_repeats=int(v[4]),
+                    sent_records=lo(v[5]), sent_labels=hi(v[5]), ne=int(v[6]), pack_ext_workgroups=int(v[7]), tables_ahead_used=int(v[8]),
+                    form=int(v[9]), shared_ops=int(v[10]), zero_exchanged=int(v[11]))
+
+    def debug_set_shared_ops_reserve(self, n):
+        """test hook: shared-cluster operations the device form of the time-shard path takes (0 = its reserve); the SAME value on every
+        handle of a group"""
+        check(lib().ctk_debug_set_shared_ops_reserve(self._h, int(n)))
 
     def debug_set_spin(self, limit_ms=0.0, stall_mode=0):
         """bounded inter-workgroup waits of the one-launch filter pass: limit (0 = default 200 ms), 1 = head of the chain late, 2 = never"""

@@ -323,6 +323,8 @@ struct ctk_handle {
     size_t h_shard_cap = 0, h_lab_cap = 0, h_seam_cap = 0;
     bool halo_in_zero = false; void *halo_in_zero_p = nullptr; size_t halo_in_zero_cap = 0;     // the halo header of a first shard is already zero
     uint32_t sh_capB = 0, sh_capC = 0, sh_capD = 0;     // agreed capacities of the exchanged records (grow-only)
+    int64_t sh_dbg[12] = {0};                     // ctk_debug_shard_exchange: what the last ctk_track_sharded_* call decided (CTK_SHX_*)
+    bool sh_dbg_valid = false;
     std::vector<std::pair<int32_t, int32_t>> sh_pairs;
     bool halo_valid = false, halo_v2 = false;
     std::vector<ctk_life_row> lc_host, lc_tmp;
@@ -385,6 +387,7 @@ struct ctk_handle {
     uint32_t debug_mail_c = 0, debug_mail_d = 0;  // test hook: pretend the resolver mailbox holds only this many records / labels
     int debug_sd_lab = 0, debug_sd_ops = 0;       // test hook: labels / operations per cluster the device seam driver accepts
     int debug_fail_stage = 0;                     // test hook (ctk_debug_fail_at): the time-shard path fails at this stage, once
+    int64_t debug_sh_gops = 0;                    // test hook (ctk_debug_set_shared_ops_reserve): shared-cluster operations the device form takes
     // bounded inter-workgroup waits of the systolic filter kernels (ResolveDev::spin_limit): ticks of the 100 MHz wall clock after
     // which a wait gives up; no_sys: a wait did give up on this handle -- one launch per filter pass (no waits) from then on
     uint64_t spin_limit = CTK_SPIN_LIMIT_TICKS;

@@ -679,13 +679,29 @@ static void shard_scratch_free(ShardScratch *s) { delete s; }
 // pinned memory -- k_seam_driver, enqueued behind that copy, runs underneath the host's work on them.  mail2[64..69] are written
 // by k_sh_reduce_ext at the end (the caller waits for the stream after the write pass).
 #define CTK_SH_GOPS 16384            // op slots reserved for the shared clusters' operations (more: every rank falls back alike)
+// ctk_debug_shard_exchange: slots of ctk_handle::sh_dbg, stored by the host where it takes the decision (two 32-bit facts per slot:
+// first | second << 32)
+#define CTK_SHX_CAPB      0          // capB at the end of X3
+#define CTK_SHX_CAPB_REDO 1          // repeats of the X3 exchange because capB had to grow
+#define CTK_SHX_NLAST_NH  2          // this rank's nlast | nh << 32
+#define CTK_SHX_CAPCD     3          // capC | capD << 32 at the end of X5
+#define CTK_SHX_X5_REDO   4          // repeats of the X5 exchange
+#define CTK_SHX_SENT      5          // the header this rank sent: shared records | shared labels << 32
+#define CTK_SHX_NE        6          // ids in the extent exchange
+#define CTK_SHX_PE_WGS    7          // workgroups of the k_sh_pack_ext launch
+#define CTK_SHX_PRE_USED  8          // 1 the seam tables initialised ahead were used, 0 k_sh_seam_init ran again, -1 no device attempt
+#define CTK_SHX_FORM      9          // X5 form that finished the call: 0 device; host-driven because: 1 not attempted (grid remembered,
+                                     // T or id range), 2 more shared-cluster operations than the reserve, 4 some rank's device driver gave up
+#define CTK_SHX_NG        10         // shared-cluster operations
+#define CTK_SHX_ZERO_X    11         // 1 no rank saw a background pixel in its sample: the write pass' zero flags were exchanged afterwards
+#define CTK_SHX_PAIR(a, b) ((int64_t)(uint32_t)(a) | ((int64_t)(uint32_t)(b) << 32))
 static int sharded_seam_device(ctk_handle *h, ctk_comm *c, ShardScratch &S, ResolveDev &r, const ResolveIn &in, ResolvePlan &pl, int64_t T, int64_t t_begin,
                                int ny, int nx, int W, int persistence, int64_t NL, int64_t lab0, int64_t lab1, bool any_boundary, uint32_t hint_c,
                                uint32_t hint_d, uint32_t *mail2, bool *too_many_shared_ops, size_t pre_inited, const void *const *pre_ptrs)
 {
     hipStream_t s = h->stream;
     const int rank = c->rank, world = c->world;
-    (void)rank; (void)W;
+    (void)W;
     *too_many_shared_ops = false;
     const size_t NT = (size_t)NL + 2;
     CTKCHK(ensure(h, h->rv_mark, NT)); CTKCHK(ensure(h, h->rv_dmap, NT * 4)); CTKCHK(ensure(h, h->op_first, NT * 4));
@@ -728,6 +744,7 @@ static int sharded_seam_device(ctk_handle *h, ctk_comm *c, ShardScratch &S, Reso
                                     h->sh_cl_shared.p, h->sh_cl_sent.p};
         bool pre_ok = NT <= pre_inited;
         for (int k = 0; k < 10 && pre_ok; k++) pre_ok = pre_ptrs && pre_ptrs[k] == now_ptrs[k];
+        h->sh_dbg[CTK_SHX_PRE_USED] = pre_ok ? 1 : 0;
         if (!pre_ok) k_sh_seam_init<<<(int)std::min<size_t>((NT + 255) / 256, 2048), 256, 0, s>>>(tb, (int64_t)NT, -1, P<uint32_t>(h->counters), scal);
         k_rs_labels_sh<<<pl.gc, 256, 0, s>>>(r, st, P<uint8_t>(h->rv_mark), P<int32_t>(h->ext), NL, P<uint32_t>(h->counters), scal);
         k_fz_mark<<<(int)T, 64, 0, s>>>(r, sd, in.seams, in.seam_cnt, in.seam_off, P<int2>(h->rv_seam_res));
@@ -750,7 +767,8 @@ static int sharded_seam_device(ctk_handle *h, ctk_comm *c, ShardScratch &S, Reso
         uint32_t capC = std::max<uint32_t>(hint_c, 256), capD = (std::max<uint32_t>(hint_d, 256) + 3u) & ~3u;
         size_t sslot = 0;
         bool driver_launched = false;
-        for (int redo = 0;; redo = 1) {
+        int x5_redo = 0;
+        for (int redo = 0;; redo = 1, x5_redo++) {
             sslot = sizeof(ShSeamHeader) + (size_t)capC * sizeof(CtkCand) + (size_t)capD * 28;      // (a multiple of 16: capD is one of 4)
             CTKCHK(ensure_host(&h->h_seam, &h->h_seam_cap, sslot * (size_t)(world + 1), true));
             CTKCHK(ensure(h, h->sh_send, sslot));
@@ -774,6 +792,11 @@ static int sharded_seam_device(ctk_handle *h, ctk_comm *c, ShardScratch &S, Reso
             capC = std::max(capC, mc + mc / 2 + 64); capD = (std::max(capD, md + md / 2 + 64) + 3u) & ~3u;       // same on every rank
         }
         h->sh_capC = capC; h->sh_capD = capD;
+        {
+            const ShSeamHeader *mine = (const ShSeamHeader *)((const unsigned char *)h->h_seam + sslot * (size_t)(rank + 1));
+            h->sh_dbg[CTK_SHX_CAPCD] = CTK_SHX_PAIR(capC, capD); h->sh_dbg[CTK_SHX_X5_REDO] = x5_redo;
+            h->sh_dbg[CTK_SHX_SENT] = CTK_SHX_PAIR(mine->ncand, mine->nlab);
+        }
         if (h->debug_fail_stage == 5) { h->debug_fail_stage = 0; return ctk_set_error(CTK_E_INTERNAL, "injected failure at stage 5 (test hook)"); }
         // merged table of the shared labels (boxes: union over the shards) and the shared candidate groups in (t, y) order
         const double t_host = now_ms();
@@ -818,7 +841,10 @@ static int sharded_seam_device(ctk_handle *h, ctk_comm *c, ShardScratch &S, Reso
     S.elist.erase(std::unique(S.elist.begin(), S.elist.end()), S.elist.end());
     const int32_t ne = (int32_t)S.elist.size();
     const int64_t ng = (int64_t)S.ops_g.size();
-    if (ng > CTK_SH_GOPS) { *too_many_shared_ops = true; return CTK_OK; }      // (the same list on every rank: everybody takes the host-driven form)
+    h->sh_dbg[CTK_SHX_NE] = ne; h->sh_dbg[CTK_SHX_NG] = ng;
+    // (ctk_debug_set_shared_ops_reserve lowers the number compared with, never the allocation; the same value on every rank)
+    const int64_t gops = h->debug_sh_gops > 0 ? std::min<int64_t>(h->debug_sh_gops, CTK_SH_GOPS) : CTK_SH_GOPS;
+    if (ng > gops) { *too_many_shared_ops = true; return CTK_OK; }      // (the same list on every rank: everybody takes the host-driven form)
     // the shared clusters' operations + the list of shared ids -> pinned staging read by the kernels
     const size_t bytes = (size_t)std::max<int64_t>(ng, 1) * (sizeof(CtkOp) + 4 + 8) + (size_t)ne * 4 + 64;
     CTKCHK(ensure_host(&h->h_ops, &h->h_ops_cap, bytes));
@@ -846,6 +872,7 @@ static int sharded_seam_device(ctk_handle *h, ctk_comm *c, ShardScratch &S, Reso
         const int64_t nsample = std::min<int64_t>((int64_t)T * ny * h->W, 16384);
         const uint64_t last_full = (nx & 63) ? ((1ull << (nx & 63)) - 1ull) : ~0ull;
         const int pe_lds = h->debug_mail_d ? (int)std::min<uint32_t>(h->debug_mail_d, SH_PE_LDS) : SH_PE_LDS;      // (ctk_debug_set_mailbox)
+        h->sh_dbg[CTK_SHX_PE_WGS] = ne <= pe_lds ? SH_PE_BLOCKS : 1;
         k_sh_pack_ext<<<ne <= pe_lds ? SH_PE_BLOCKS : 1, 256, 0, s>>>(s_el, ne, P<int32_t>(h->ext), NL, lab0, lab1, persistence, P<uint64_t>(h->mask), nsample, h->W,
                                                                       last_full, P<int32_t>(h->sh_elist), P<int32_t>(h->sh_send), P<uint32_t>(h->counters), pe_lds);
         HIPCHK(hipGetLastError());
@@ -1026,7 +1053,10 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     // component capacity starts at a fixed value and grows by consensus inside the call; for the shared seam records every
     // rank sends what it remembers and all take the maximum.
     uint32_t capB = 256;
-    int it_done = 0, rounds = 0;
+    int it_done = 0, rounds = 0, capb_redo = 0;
+    h->sh_dbg_valid = false;
+    for (int64_t &v : h->sh_dbg) v = 0;
+    h->sh_dbg[CTK_SHX_PRE_USED] = -1;
     uint64_t nc_sum = 0;
     bool first_round = true;
     {
@@ -1130,6 +1160,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
             CTKCHK(ctk_comm_wait_word(c, mail2 + CTK_SHM_STAMP, keep_stamp));
             if (mail2[CTK_SHM_MAXNLAST] <= capB) break;
             if (!first_round) return ctk_set_error(CTK_E_INTERNAL, "boundary component count changed between rounds");
+            capb_redo++;
             capB = mail2[CTK_SHM_MAXNLAST] + mail2[CTK_SHM_MAXNLAST] / 2 + 64;      // same decision on every rank; nothing was imported
                                                                                    // beyond capB, the bits are simply exchanged again
         }
@@ -1199,6 +1230,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     }
     h->stats[CTK_S_EXACT_FIXUPS] = n_fixups;
     h->sh_capB = capB;
+    h->sh_dbg[CTK_SHX_CAPB] = capB; h->sh_dbg[CTK_SHX_CAPB_REDO] = capb_redo;
     const uint32_t hint_c = mail2[CTK_SHM_HINT_C], hint_d = mail2[CTK_SHM_HINT_D];
     SHDBG("X3");
     h->stats[CTK_S_FILTER_PASSES] = it_done; h->stats[CTK_S_FILTER_ROUNDS] = rounds;
@@ -1236,6 +1268,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
         b.last = (const int32_t *)(p + sizeof(BoundHeader)); b.halo = b.last + capB;
         if (b.nlast < 0 || b.nh < 0 || (uint32_t)b.nlast > capB || (uint32_t)b.nh > capB) COLLECTIVE_FAIL(CTK_E_INTERNAL, "boundary record of rank %d is malformed", q);
     }
+    h->sh_dbg[CTK_SHX_NLAST_NH] = CTK_SHX_PAIR(S.bin[(size_t)rank].nlast, S.bin[(size_t)rank].nh);
     INJECT(4);
     if (!boundary_resolve(S.bin, S.bout, h->seg_shard_breaks)) COLLECTIVE_FAIL(CTK_E_INTERNAL, "ctk_track_sharded: the shards' boundary records contradict each other");
     const int64_t NL = S.bout.off[(size_t)world];
@@ -1275,6 +1308,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     }();
     int64_t alive = 0;
     bool zero = false;
+    int64_t host_why = 0;                             // (CTK_SHX_FORM)
     for (int attempt = 0;; attempt++) {
     const bool dev_seam = attempt == 0 && !(h->sh_dev_off_ny == ny && h->sh_dev_off_nx == nx) && T <= 65536 &&
                           NL + 2 < 0x7fffffffll;
@@ -1282,8 +1316,9 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
         bool too_many = false;
         CTKCHK(sharded_seam_device(h, c, S, r, in, pl, T, t_begin, ny, nx, W, persistence, NL, lab0, lab1, any_boundary_label_all, hint_c, hint_d, mail2, &too_many,
                                    seam_pre_n, seam_pre_ptrs));
-        if (too_many) { h->stats[CTK_S_HOST_REASON] |= 16; continue; }       // (decided alike on every rank, nothing of X6 launched yet)
+        if (too_many) { h->stats[CTK_S_HOST_REASON] |= 16; host_why |= 2; continue; }       // (decided alike on every rank, nothing of X6 launched yet)
     } else {
+    if (attempt == 0) host_why |= 1;
     if (attempt > 0) {
         // the first attempt turned the root indices in r.lab into labels and handed out dense ids to the boundary labels: start over
         HIPCHK(hipMemcpyAsync(r.lab, r.lab_root, R * 4, hipMemcpyDeviceToDevice, s));
@@ -1375,10 +1410,13 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     const int32_t *lorig = ho;                         // labels of the groups driven here (all of them without shared groups)
     size_t n_lorig = nd;
     HP(0);
-    uint32_t capC = std::max<uint32_t>(hint_c, 256), capD = std::max<uint32_t>(hint_d, 256);
+    // (capD a multiple of 4 as in the device form: a rank that stays host-driven on this grid takes part in the same all-gather as
+    // ranks in the device form, and the payload size depends on capD)
+    uint32_t capC = std::max<uint32_t>(hint_c, 256), capD = (std::max<uint32_t>(hint_d, 256) + 3u) & ~3u;
     struct SeamHeader { uint32_t ncand, nlab, pad0, pad1; };
     size_t sslot = 0;
     bool local_done = false;
+    int x5_redo = 0;
     auto drive_local = [&]() {
         // this shard's own groups (dense ids renumbered without the shared labels), driven here
         // (sized once, filled by index: a push_back / insert per label was a third of this step's time)
@@ -1425,9 +1463,12 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
             mc = std::max(mc, qh->ncand); md = std::max(md, qh->nlab);
         }
         if (mc <= capC && md <= capD) break;
-        capC = std::max(capC, mc + mc / 2 + 64); capD = std::max(capD, md + md / 2 + 64);       // same on every rank
+        capC = std::max(capC, mc + mc / 2 + 64); capD = (std::max(capD, md + md / 2 + 64) + 3u) & ~3u;       // same on every rank
+        x5_redo++;
     }
     h->sh_capC = capC; h->sh_capD = capD;
+    h->sh_dbg[CTK_SHX_CAPCD] = CTK_SHX_PAIR(capC, capD); h->sh_dbg[CTK_SHX_X5_REDO] = x5_redo;
+    h->sh_dbg[CTK_SHX_SENT] = CTK_SHX_PAIR(nGc, nGd);
     HP(1);
     INJECT(5);
     // merged table of the shared labels (boxes: union over the shards) and the shared candidate groups in (t, y) order
@@ -1473,6 +1514,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     std::sort(S.elist.begin(), S.elist.end());
     S.elist.erase(std::unique(S.elist.begin(), S.elist.end()), S.elist.end());
     const int32_t ne = (int32_t)S.elist.size();
+    h->sh_dbg[CTK_SHX_NE] = ne; h->sh_dbg[CTK_SHX_NG] = (int64_t)S.ops_g.size();
     h->ms[CTK_T_HOST_RESOLVE] += now_ms() - t_host;
     HP(2);
 
@@ -1516,6 +1558,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
             const int64_t nsample = std::min<int64_t>((int64_t)T * ny * W, 16384);
             const uint64_t last_full = (nx & 63) ? ((1ull << (nx & 63)) - 1ull) : ~0ull;
             const int pe_lds = h->debug_mail_d ? (int)std::min<uint32_t>(h->debug_mail_d, SH_PE_LDS) : SH_PE_LDS;      // (ctk_debug_set_mailbox)
+            h->sh_dbg[CTK_SHX_PE_WGS] = ne <= pe_lds ? SH_PE_BLOCKS : 1;
             k_sh_pack_ext<<<ne <= pe_lds ? SH_PE_BLOCKS : 1, 256, 0, s>>>(s_el, ne, P<int32_t>(h->ext), NL, lab0, lab1, persistence, P<uint64_t>(h->mask), nsample, W,
                                                                           last_full, P<int32_t>(h->sh_elist), P<int32_t>(h->sh_send), P<uint32_t>(h->counters), pe_lds);
             HIPCHK(hipGetLastError());
@@ -1548,6 +1591,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     CTKCHK(ctk_comm_wait(c));
     alive = mail2[64];
     zero = mail2[65] != 0;
+    h->sh_dbg[CTK_SHX_ZERO_X] = zero ? 0 : 1;
     if (!zero) {
         CTKCHK(ensure(h, h->sh_send, 64));
         CTKCHK(ensure(h, h->sh_recv, 64 * (size_t)world));
@@ -1564,6 +1608,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
         if (pz & CTK_POISON_OPCAP) h->op_cap_hint = std::max<uint32_t>(h->op_cap_hint * 2, mail2[68] + mail2[68] / 2 + 1024);
         if (pz & CTK_POISON_CLUSTER) { h->sh_dev_off_ny = ny; h->sh_dev_off_nx = nx; }
         h->stats[CTK_S_HOST_REASON] |= 16;
+        host_why |= 4;
         continue;
     }
     if (dev_seam) {
@@ -1577,6 +1622,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     break;
     }   // attempts
     h->last_alive = alive;
+    h->sh_dbg[CTK_SHX_FORM] = host_why; h->sh_dbg_valid = true;
     if (n_tracked) *n_tracked = alive + (zero ? 1 : 0) - 1;              // len(np.unique(flag)) - 1, contrack.py:793
     collect_event_times(h);
     h->state = ST_TABLES;
@@ -1622,6 +1668,21 @@ extern "C" int ctk_debug_fail_at(ctk_handle *h, int stage)
 {
     if (!h || stage < 0) return ctk_set_error(CTK_E_INVALID, "ctk_debug_fail_at: null handle or negative stage");
     h->debug_fail_stage = stage;
+    return CTK_OK;
+}
+
+extern "C" int ctk_debug_shard_exchange(ctk_handle *h, int64_t *out12)
+{
+    if (!h || !out12) return ctk_set_error(CTK_E_INVALID, "ctk_debug_shard_exchange: null handle or output");
+    if (!h->sh_dbg_valid) return ctk_set_error(CTK_E_STATE, "ctk_debug_shard_exchange: no ctk_track_sharded_* call has finished on this handle");
+    memcpy(out12, h->sh_dbg, sizeof(h->sh_dbg));
+    return CTK_OK;
+}
+
+extern "C" int ctk_debug_set_shared_ops_reserve(ctk_handle *h, int64_t n)
+{
+    if (!h || n < 0) return ctk_set_error(CTK_E_INVALID, "ctk_debug_set_shared_ops_reserve: null handle or negative count");
+    h->debug_sh_gops = n;
     return CTK_OK;
 }
 

@@ -49,6 +49,32 @@ int ctk_debug_boundary_resolve_breaks(int world, const int32_t *nlast, const int
  * send the pass to the synchronous path with the host driver, and the grid stays there */
 int ctk_debug_set_seam_caps(ctk_handle *h, int labels, int ops);
 
+/* test hook: facts about the handle's last ctk_track_sharded_* call, stored by the host where it takes each decision (an error if none
+ * has finished).  Slots that hold two 32-bit facts: first | second << 32.
+ *   out12[0]  capB, the capacity for the components of a cut step, at the end of the filter exchange (X3)
+ *   out12[1]  how often that exchange was repeated because capB had to grow
+ *   out12[2]  this rank's nlast | nh << 32 (components of its last step / of the halo it received)
+ *   out12[3]  capC | capD << 32 at the end of the shared seam exchange (X5): group records / labels per rank
+ *   out12[4]  repeats of that exchange
+ *   out12[5]  the header this rank sent there: shared records | shared labels << 32
+ *   out12[6]  ne, the ids of the extent exchange
+ *   out12[7]  workgroups of the k_sh_pack_ext launch
+ *   out12[8]  1 the seam tables initialised ahead of the boundary resolution were used, 0 k_sh_seam_init ran again, -1 the call made
+ *             no device attempt
+ *   out12[9]  the X5 form that finished the call: 0 device; otherwise host-driven, bits: 1 no device attempt (grid remembered as
+ *             host-driven, shard length or id range), 2 more shared-cluster operations than the reserve, 4 some rank's device seam
+ *             driver gave up
+ *   out12[10] ng, the shared-cluster operations
+ *   out12[11] 1 no rank saw a background pixel in the sample of its mask, so the zero flags of the write pass were exchanged afterwards
+ *             (k_sh_count); 0 the sample settled it */
+int ctk_debug_shard_exchange(ctk_handle *h, int64_t *out12);
+
+/* test hook: the time-shard path's device form compares the number of shared-cluster operations with min(n, its reserve of 16384 op
+ * slots) when n > 0 (0 = the reserve itself); beyond, the call is finished host-driven (CTK_S_HOST_REASON bit 4).  The allocation
+ * stays the full reserve.  The decision is taken alike on every rank from the same gathered records, so the hook MUST be set to the
+ * same value on every handle of a group: ranks that disagree would wait in different collectives. */
+int ctk_debug_set_shared_ops_reserve(ctk_handle *h, int64_t n);
+
 /* test hook: cap the device-written mailbox of the resolver hand-off (0 = no cap), so that the explicit-copy path runs; `labels`
  * also caps the list of shared ids the time-shard path's extent exchange keeps in LDS (longer lists: its one-workgroup form) */
 int ctk_debug_set_mailbox(ctk_handle *h, uint32_t cand_records, uint32_t labels);
