@@ -42,6 +42,8 @@ EXPORTS = [
     "ctk_percentile_groups_f32", "ctk_percentile_groups_f64", "ctk_debug_percentile_groups_sweeps", "ctk_debug_time_percentile_groups",
     "ctk_percentile_field_f32", "ctk_percentile_field_f64", "ctk_debug_percentile_field_plan", "ctk_debug_percentile_field_form", "ctk_debug_time_percentile_field",
     "ctk_anom_seg_f32", "ctk_anom_seg_f64", "ctk_anom_stream_f32", "ctk_anom_stream_f64", "ctk_anom_stream_cb", "ctk_debug_anom_form",
+    "ctk_level_mean_f32", "ctk_level_mean_f64", "ctk_level_mean_f32_dev", "ctk_level_mean_f64_dev", "ctk_level_mean_stream_f32", "ctk_level_mean_stream_f64",
+    "ctk_level_mean_stream_cb", "ctk_resident_level_mean", "ctk_resident_level_mean_generation", "ctk_anom_seg_resident", "ctk_debug_level_plan", "ctk_debug_level_form", "ctk_debug_time_level_mean", "ctk_debug_set_level",
 ]
 
 READ_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)       # ctk_read_chunk_fn
@@ -91,6 +93,14 @@ def debug_lifecycle_plan(T, ny, nx, f64=False, flag_align=0, field_align=0):
     v = np.zeros(5, dtype=np.int64)
     check(lib().ctk_debug_lifecycle_plan(int(T), int(ny), int(nx), int(bool(f64)), int(flag_align), int(field_align), v.ctypes.data))
     return dict(rw=int(v[0]), nsx=int(v[1]), nby=int(v[2]), vec=int(v[3]), ks=int(v[4]))
+
+
+def level_plan(elem_bytes, nsel, npix, steps, aligned=True):
+    """ctk_debug_level_plan: what ctk_level_plan (csrc/ctk_forms.h) decides for a level_mean launch, as a dict (vec 1 vector / 0 scalar
+    form, vpt pixels per thread, unroll, bps workgroups per step, blocks, grid, xcd); no handle, no GPU"""
+    v = np.zeros(7, dtype=np.int64)
+    check(lib().ctk_debug_level_plan(int(elem_bytes), int(nsel), int(npix), int(steps), int(bool(aligned)), v.ctypes.data))
+    return dict(vec=int(v[0]), vpt=int(v[1]), unroll=int(v[2]), bps=int(v[3]), blocks=int(v[4]), grid=int(v[5]), xcd=int(v[6]))
 
 
 def forms(T, ny, nx, nt=None, aligned16=True, async_passes=24, n_cus=256, **query):
@@ -219,6 +229,20 @@ def lib():
         getattr(L, name).argtypes = [p, p, i64, i32, i32, p, i32, i32, i32, p, i64, p, p, p, i64]
     L.ctk_anom_stream_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, p, i32, i32, i32, p, i64, p, p, WRITE_CHUNK_FN, p, i64]
     L.ctk_debug_anom_form.argtypes = [p, C.POINTER(i64)]
+    for name in ("ctk_level_mean_f32", "ctk_level_mean_f64"):
+        getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, p, i32, p, i32]
+    for name in ("ctk_level_mean_f32_dev", "ctk_level_mean_f64_dev"):
+        getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, p, i32, p]
+    for name in ("ctk_level_mean_stream_f32", "ctk_level_mean_stream_f64"):
+        getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, p, i32, p, i64, i32]
+    L.ctk_level_mean_stream_cb.argtypes = [p, i32, i64, i32, i32, i32, READ_CHUNK_FN, p, p, i32, WRITE_CHUNK_FN, p, i64, i32]
+    L.ctk_resident_level_mean.argtypes = [p, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.ctk_resident_level_mean_generation.argtypes = [p, C.POINTER(C.c_uint64)]
+    L.ctk_anom_seg_resident.argtypes = [p, p, i32, i32, i32, p, p, p, i32, p, i64]
+    L.ctk_debug_level_plan.argtypes = [i32, i64, i64, i64, i32, p]
+    L.ctk_debug_level_form.argtypes = [p, p]
+    L.ctk_debug_set_level.argtypes = [p, i32, i64]
+    L.ctk_debug_time_level_mean.argtypes = [p, p, i32, i64, i32, i32, i32, p, i32, p, i32, C.POINTER(dbl)]
     L.ctk_resident_anom.argtypes = [p, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.ctk_resident_anom_generation.argtypes = [p, C.POINTER(C.c_uint64)]
     L.ctk_track_resident.argtypes = [p, p, i32, p, dbl, i32, i32, p, C.POINTER(i64)]
@@ -291,6 +315,19 @@ def _groups(group, T, ngroups=None):
         raise ValueError("group ids beyond int32")
     g = np.ascontiguousarray(g, dtype=np.int32)
     return g, (int(g.max()) + 1 if g.size else 1) if ngroups is None else int(ngroups)
+
+
+def _level_weights(weights, nlev):
+    """weights of a level_mean call as a C-contiguous float64 (nlev,) array: each finite and >= 0, one > 0 (checked here, before the
+    library is touched, and again by it)"""
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.ndim != 1 or w.shape[0] != nlev:
+        raise ValueError("weights must hold one value per level (%d), not shape %s" % (nlev, w.shape))
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError("each weight must be finite and >= 0")
+    if not np.any(w > 0):
+        raise ValueError("all weights are zero: no level is selected")
+    return w
 
 
 def _group_ids(group, T):
@@ -946,6 +983,150 @@ class Tracker:
             raise errors[0]
         check(rc)
         return out, cout
+
+    # ---- vertical mean over the selected levels (ctk_level_mean_*) ------------------------------------------------
+    def level_mean(self, x, weights, skipna=False, chunk_steps=None, keep_resident=False, want_out=True):
+        """x (steps, nlev, ny, nx) float32 / float64 (an array or np.memmap); weights: nlev values >= 0, a level of weight 0 is not
+        selected (never read, never uploaded).  Returns the (steps, ny, nx) mean in x's dtype (None without want_out):
+        sum of w[l] * x[:, l] over the selected levels in rising l / sum of those w[l], in float64 (include/contrack_hip.h).
+        skipna: a NaN level of a pixel leaves both sums.  chunk_steps: steps per chunk on their way through the device (None:
+        ctk_level_mean_*, 0: about 256 MB of input); same bits.  keep_resident: the mean stays in HBM for anomalies_resident."""
+        if not isinstance(x, np.memmap):
+            x = np.ascontiguousarray(x)
+        if x.ndim != 4:
+            raise ValueError("x must be (steps, level, lat, lon)")
+        if x.dtype not in (np.float32, np.float64):
+            x = np.ascontiguousarray(x, dtype=np.float64)
+        if not x.flags.c_contiguous:
+            x = np.ascontiguousarray(x)
+        steps, nlev, ny, nx = x.shape
+        w = _level_weights(weights, nlev)
+        if not want_out and not keep_resident:
+            raise ValueError("want_out=False without keep_resident asks for nothing")
+        out = np.empty((steps, ny, nx), dtype=x.dtype) if want_out else None
+        f64 = x.dtype == np.float64
+        head = (self._h, x.ctypes.data, steps, nlev, ny, nx, w.ctypes.data, int(bool(skipna)), _ptr(out))
+        if chunk_steps is None:
+            check((lib().ctk_level_mean_f64 if f64 else lib().ctk_level_mean_f32)(*head, int(bool(keep_resident))))
+        else:
+            check((lib().ctk_level_mean_stream_f64 if f64 else lib().ctk_level_mean_stream_f32)(*head, int(chunk_steps), int(bool(keep_resident))))
+        return out
+
+    def level_mean_cb(self, reader, shape_sel, dtype, weights_sel, skipna=False, sink=None, chunk_steps=0, keep_resident=False):
+        """level_mean with a reader(t0, nt, out) that fills `out`, a (nt, nsel, ny, nx) view of pinned memory, with the SELECTED levels
+        (rising level order) of the steps [t0, t0 + nt); shape_sel = (steps, nsel, ny, nx), weights_sel their nsel non-zero
+        weights.  sink: None (a new array is returned), False (nothing leaves the device: keep_resident), a C-contiguous
+        (steps, ny, nx) array of `dtype`, or a writer(t0, nt, values).  Reader and writer see every step once, in rising order."""
+        if shape_sel is None or dtype is None:
+            raise ValueError("a reader needs shape=(steps, nsel, ny, nx) and dtype")
+        steps, nsel, ny, nx = (int(v) for v in shape_sel)
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("the field must be float32 or float64")
+        w = _level_weights(weights_sel, nsel)
+        if np.any(w == 0):
+            raise ValueError("a reader delivers the selected levels only: every weight must be > 0")
+        out = None
+        if sink is None:
+            out = sink = np.empty((steps, ny, nx), dtype=dt)
+        elif sink is False:
+            sink = None
+            if not keep_resident:
+                raise ValueError("sink=False without keep_resident asks for nothing")
+        elif not callable(sink):
+            if sink.dtype != dt or sink.shape != (steps, ny, nx) or not sink.flags.c_contiguous:
+                raise ValueError("the sink array must be C-contiguous (steps, ny, nx) of the field's dtype")
+            out = sink
+        errors = []
+        ctype = C.c_float if dt == np.float32 else C.c_double
+
+        def rd(_user, t0, nt, dst):
+            try:
+                reader(int(t0), int(nt), np.ctypeslib.as_array(C.cast(dst, C.POINTER(ctype)), shape=(nt, nsel, ny, nx)))
+                return 0
+            except BaseException as e:                    # an exception must not cross the C frames
+                errors.append(e)
+                return 1
+
+        def wr(_user, t0, nt, src):
+            try:
+                view = np.ctypeslib.as_array(C.cast(src, C.POINTER(ctype)), shape=(nt, ny, nx))
+                if callable(sink):
+                    sink(int(t0), int(nt), view)
+                else:
+                    sink[t0:t0 + nt] = view
+                return 0
+            except BaseException as e:
+                errors.append(e)
+                return 1
+        rcb = READ_CHUNK_FN(rd)
+        wcb = WRITE_CHUNK_FN(wr) if sink is not None else C.cast(None, WRITE_CHUNK_FN)
+        rc = lib().ctk_level_mean_stream_cb(self._h, dt.itemsize, steps, nsel, ny, nx, rcb, None, w.ctypes.data, int(bool(skipna)), wcb, None,
+                                            int(chunk_steps or 0), int(bool(keep_resident)))
+        if errors:
+            raise errors[0]
+        check(rc)
+        return out
+
+    def level_mean_dev(self, x_dev, steps, nlev, ny, nx, weights, out_dev, skipna=False, f64=False):
+        """ctk_level_mean_*_dev: x (steps, nlev, ny, nx) and out (steps, ny, nx) in device memory"""
+        w = _level_weights(weights, nlev)
+        fn = lib().ctk_level_mean_f64_dev if f64 else lib().ctk_level_mean_f32_dev
+        check(fn(self._h, x_dev, int(steps), int(nlev), int(ny), int(nx), w.ctypes.data, int(bool(skipna)), out_dev))
+
+    def time_level_mean(self, x_dev, steps, nlev, ny, nx, weights, out_dev, skipna=False, f64=False, reps=5):
+        """measurement (tools/level_probe.py): (best, mean) ms of k_level_mean alone on slabs in device memory, HIP events"""
+        w = _level_weights(weights, nlev)
+        ms = (C.c_double * 2)()
+        check(lib().ctk_debug_time_level_mean(self._h, x_dev, int(bool(f64)), int(steps), int(nlev), int(ny), int(nx), w.ctypes.data, int(bool(skipna)),
+                                              out_dev, int(reps), ms))
+        return float(ms[0]), float(ms[1])
+
+    def debug_set_level(self, xcd=-1, grid_max=0):
+        """for the following level_mean launches -- xcd: how workgroups map to XCDs (0 launch order, 1 one contiguous eighth per XCD,
+        n > 1 tiles of n; -1: the library's rule, ctk_level_plan); grid_max: a lower cap on the workgroups of a launch (0: the rule's)"""
+        check(lib().ctk_debug_set_level(self._h, int(xcd), int(grid_max)))
+
+    def debug_level_form(self):
+        """the form of the last level_mean launch: 1 vector (16 bytes per lane), 0 scalar, -1 none yet"""
+        return self.debug_level_launch()[0]
+
+    def debug_level_launch(self):
+        """(form, workgroups) of the last level_mean launch"""
+        v = np.zeros(2, dtype=np.int64)
+        check(lib().ctk_debug_level_form(self._h, v.ctypes.data))
+        return int(v[0]), int(v[1])
+
+    def resident_level_mean(self):
+        """(steps, ny, nx, is float64) of the vertical mean kept in HBM, or None"""
+        T, ny, nx, f = C.c_int64(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        check(lib().ctk_resident_level_mean(self._h, C.byref(T), C.byref(ny), C.byref(nx), C.byref(f)))
+        return None if T.value < 0 else (int(T.value), int(ny.value), int(nx.value), bool(f.value))
+
+    def resident_level_mean_generation(self):
+        """identity of the resident vertical mean (changes with every level_mean call and with release_io)"""
+        g = C.c_uint64(0)
+        check(lib().ctk_resident_level_mean_generation(self._h, C.byref(g)))
+        return int(g.value)
+
+    def anomalies_resident(self, group, ngroups, window=1, smooth=1, clim=None, segments=None, keep_resident=False, want_anom=True, want_clim=False):
+        """anomalies(..., segments=...) of the resident vertical mean (ctk_anom_seg_resident): nothing crosses PCIe on the way in.
+        Returns (anom or None, clim or None) in the mean's dtype; raises if no mean is resident."""
+        shape = self.resident_level_mean()
+        if shape is None:
+            raise ContrackHipError("no vertical mean is resident on the device")
+        T, ny, nx, f64 = shape
+        dt = np.float64 if f64 else np.float32
+        group = _group_ids(group, T)
+        cin = None if clim is None else np.ascontiguousarray(clim, dtype=dt)
+        if cin is not None and cin.shape != (ngroups, ny, nx):
+            raise ValueError("clim must have shape (ngroups, ny, nx)")
+        anom = np.empty((T, ny, nx), dtype=dt) if want_anom else None
+        cout = np.empty((ngroups, ny, nx), dtype=dt) if want_clim else None
+        st = _seg_starts(segments if segments is not None else [])
+        check(lib().ctk_anom_seg_resident(self._h, group.ctypes.data, int(ngroups), int(window), int(smooth), _ptr(cin), _ptr(anom), _ptr(cout),
+                                          int(bool(keep_resident)), st.ctypes.data if st.size else None, st.shape[0]))
+        return anom, cout
 
     def debug_anom_form(self):
         """the kernel form of the last anomalies(segments=...) / anomalies_stream launch: 1 LDS ring, 0 plain, -1 none yet"""

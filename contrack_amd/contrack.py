@@ -270,6 +270,87 @@ def anomalies_numpy(x, group, ngroups=None, window=1, smooth=1, clim=None, segme
     return trk.anomalies_stream(x, ids, G, window=window, smooth=smooth, clim=clim, chunk_steps=int(chunk_steps), segments=starts, want_clim=True)
 
 
+def level_weights(levels, bounds=None):
+    """float64 weights of a vertical mean over a level coordinate (one per level, 0: not selected): the levels p with
+    min(bounds) <= p <= max(bounds) (bounds None: all of them) get the trapezoid rule over the selected levels in coordinate order --
+    half the distance to each selected neighbour --, so that the weighted mean is the integral of x dp / (p_bottom - p_top), the
+    vertical average of Schwierz et al. (2004) that README.rst:235-240 of the reference cites.  A single selected level gets 1.0.
+    `levels` must be strictly monotonic, in either direction."""
+    p = np.asarray(levels, dtype=np.float64)
+    if p.ndim != 1 or p.size < 1:
+        raise ValueError("levels must be a 1-D coordinate")
+    d = np.diff(p)
+    if not np.all(np.isfinite(p)) or (p.size > 1 and not (np.all(d > 0) or np.all(d < 0))):
+        raise ValueError("the level coordinate must be strictly monotonic")
+    if bounds is None:
+        idx = np.arange(p.size)
+    else:
+        b = np.asarray(bounds, dtype=np.float64).reshape(-1)
+        if b.size != 2:
+            raise ValueError("bounds must be two values")
+        idx = np.flatnonzero((p >= b.min()) & (p <= b.max()))
+    if idx.size == 0:
+        raise ValueError("bounds {} select no level of {}".format(tuple(np.asarray(bounds).tolist()), p.tolist()))
+    w = np.zeros(p.size, dtype=np.float64)
+    if idx.size == 1:
+        w[idx[0]] = 1.0
+        return w
+    half = np.abs(np.diff(p[idx])) / 2                      # (a monotonic coordinate: the selected levels are neighbours)
+    w[idx[:-1]] += half
+    w[idx[1:]] += half
+    return w
+
+
+def _vertical_weights(weights, levels, bounds, nlev):
+    """the weights argument of level_mean_numpy / calc_vertical_mean as nlev float64 values: an array is taken as it is, 'equal'
+    gives 1.0 on every level that `bounds` selects on `levels`, 'pressure' (None with levels) the trapezoid rule (level_weights)"""
+    if weights is None:
+        weights = 'equal' if levels is None else 'pressure'
+    if isinstance(weights, str):
+        if weights not in ('equal', 'pressure'):
+            raise ValueError("weights={!r}: 'pressure', 'equal' or one value per level".format(weights))
+        if levels is None:
+            if weights == 'pressure' or bounds is not None:
+                raise ValueError("weights='pressure' and bounds need the level coordinate (levels=)")
+            return np.ones(nlev, dtype=np.float64)
+        w = level_weights(levels, bounds)
+        if w.shape[0] != nlev:
+            raise ValueError("levels holds {} values, the field has {} levels".format(w.shape[0], nlev))
+        return (w > 0).astype(np.float64) if weights == 'equal' else w
+    return _native._level_weights(weights, nlev)
+
+
+def level_mean_numpy(x, weights=None, levels=None, bounds=None, skipna=False, chunk_steps=None, device=None, shape=None, dtype=None):
+    """the vertical mean of README.rst:235-240 ("vertically averaged between 500-150 hPa") on a (steps, level, lat, lon) float field:
+        sum over the selected levels l of w[l] * x[:, l] / sum of those w[l]        (float64, rising l; include/contrack_hip.h)
+    on the GPU (ctk_level_mean_*).  weights: one value >= 0 per level (0: the level is not selected -- never read, never uploaded),
+    'equal', or 'pressure' (the default with levels=: level_weights(levels, bounds)); without levels every level counts equally.
+    skipna: a NaN level of a pixel leaves both sums.  x: an array or np.memmap, or -- with shape=(steps, nsel, ny, nx) and dtype -- a
+    reader(t0, nt, out) that fills out (nt, nsel, ny, nx) with the SELECTED levels only, in rising level order.  chunk_steps: steps
+    per chunk on their way through the device (0: about 256 MB of input); same bits.  Returns (steps, lat, lon) in x's dtype
+    (float32 kept, anything else float64)."""
+    if callable(x):
+        if shape is None or dtype is None:
+            raise ValueError("a reader needs shape=(steps, nsel, ny, nx) and dtype")
+        if len(shape) != 4:
+            raise ValueError("shape must be (steps, nsel, ny, nx)")
+        nsel = int(shape[1])
+        w = _vertical_weights(weights, levels, bounds, nsel if levels is None else len(np.asarray(levels)))
+        w = w[w > 0]
+        if w.shape[0] != nsel:
+            raise ValueError("the reader delivers {} levels, the weights select {}".format(nsel, w.shape[0]))
+        return _tracker(device).level_mean_cb(x, shape, dtype, w, skipna=skipna, chunk_steps=0 if chunk_steps is None else int(chunk_steps))
+    x = np.asarray(x) if not isinstance(x, np.memmap) else x
+    if x.ndim != 4:
+        raise ValueError("x must be (steps, level, lat, lon)")
+    if x.dtype.kind != "f":
+        if x.dtype.kind not in "iub":
+            raise TypeError("x must be a real numeric array")
+        x = x.astype(np.float64)
+    w = _vertical_weights(weights, levels, bounds, x.shape[1])
+    return _tracker(device).level_mean(x, w, skipna=skipna, chunk_steps=None if chunk_steps is None else int(chunk_steps))
+
+
 def percentile_groups_numpy(anom, rows, group, q, window=1, device=None):
     """the threshold recipe of README.rst:235-240 on a (time, lat, lon) float slab: per group g (one id in [0, G) per timestep,
     G = max(group) + 1, any order in time) the q-quantile of rows[0] <= y < rows[1] pooled over every timestep whose group lies in
@@ -713,6 +794,135 @@ class contrack(object):
             return None
         return self[variable].mean(dim="time")
 
+    # ---- vertical mean over a pressure band (README.rst:235-240, first step of the third recipe) ----------------------------
+    _LEVEL_NAMES = ('level', 'lev', 'plev', 'pressure_level', 'isobaricInhPa')
+    _PRESSURE_UNITS = ('hPa', 'Pa', 'mbar', 'millibars')
+
+    def _get_name_level(self, dims, level_name=None):
+        """the level dimension of a variable with dims `dims`: level_name, the one dimension with a usual name, or the one dimension
+        besides time, latitude and longitude whose coordinate has pressure units"""
+        if level_name is not None:
+            if level_name not in dims:
+                raise ValueError("level_name={!r} is not a dimension of the variable (dims {})".format(level_name, dims))
+            return level_name
+        named = [d for d in dims if d in self._LEVEL_NAMES]
+        if len(named) == 1:
+            return named[0]
+
+        def pressure(d):
+            try:
+                return any(u in self._PRESSURE_UNITS for u in self._units_of(d))
+            except (KeyError, AttributeError):
+                return False
+        rest = [d for d in dims if d not in (self._time_name, self._latitude_name, self._longitude_name) and pressure(d)]
+        if len(rest) == 1:
+            return rest[0]
+        raise ValueError("no level dimension found among the dims {} (one of {} or a coordinate in {}); name it with level_name="
+                         .format(dims, self._LEVEL_NAMES, self._PRESSURE_UNITS))
+
+    def _level_reader(self, da, dims, lev, step_dims, runs):
+        """reader(t0, nt, out) of the selected levels of flat steps [t0, t0 + nt) -- the step dims flattened in their own order --, read
+        as isel(outer step dims = index, innermost step dim = slice, level = slice of one run): out is (nt, nsel, ny, nx)"""
+        sizes = [da.shape[dims.index(d)] for d in step_dims]
+        inner, n_in = step_dims[-1], sizes[-1]
+        left = tuple(d for d in dims if d not in step_dims[:-1])
+        sort = [left.index(d) for d in (inner, lev, self._latitude_name, self._longitude_name)]
+
+        def reader(t0, nt, out):
+            done = 0
+            while done < nt:
+                o, t = divmod(t0 + done, n_in)
+                n = min(nt - done, n_in - t)
+                sel = dict(zip(step_dims[:-1], (int(v) for v in np.unravel_index(o, sizes[:-1])))) if len(sizes) > 1 else {}
+                sel[inner] = slice(t, t + n)
+                k = 0
+                for l0, ln in runs:
+                    sel[lev] = slice(l0, l0 + ln)
+                    out[done:done + n, k:k + ln] = np.asarray(da.isel(**sel).data).transpose(sort)
+                    k += ln
+                done += n
+        return reader
+
+    def calc_vertical_mean(self, variable, bounds=None, level_name=None, weights='pressure', skipna=False, name=None, chunk_steps=None):
+        """adds the variable `name` (default variable + '_vmean'): the mean of `variable` over its level dimension between `bounds`
+        (two coordinate values in either order, inclusive; None: every level) -- "The PV fields are vertically averaged between
+        500-150 hPa" (README.rst:235-240), bounds=(150, 500) -- computed on the GPU (level_mean_numpy).
+        weights: 'pressure' (trapezoid rule over the selected levels of the coordinate, level_weights: the integral over pressure /
+        the depth of the band), 'equal', or one value >= 0 per level (0: not selected; bounds must be None).  skipna: NaN levels of a
+        pixel are left out of its mean.  The level dimension is level_name, the one dimension called level / lev / plev /
+        pressure_level / isobaricInhPa, or the one other dimension whose coordinate has units hPa / Pa / mbar / millibars.  Every
+        other dimension besides latitude and longitude (time, a member dimension ...) counts steps, each reduced on its own; any
+        dim order is accepted, (..., level, lat, lon) avoids a host copy.  The new variable has the variable's dims without the
+        level dimension.
+        chunk_steps: the variable is read slice by slice (`isel` on the step dims and on the selected levels only) and passes
+        through chunk-sized device buffers; the 4-D array is never built on the host.  Without it, for a (time, level, lat, lon)
+        variable in any order, the mean also stays in HBM and a following calc_anom(variable=name) starts from there."""
+        self._ensure_set_up()
+        da = self.ds[variable]
+        dims = tuple(da.dims)
+        lev = self._get_name_level(dims, level_name)
+        for d in (self._latitude_name, self._longitude_name):
+            if d not in dims:
+                raise ValueError("the variable {!r} has no dimension {!r} (dims {})".format(variable, d, dims))
+        nlev = da.shape[dims.index(lev)]
+        if isinstance(weights, str):
+            try:
+                levels = np.asarray(self.ds[lev].data)
+            except (KeyError, AttributeError):
+                levels = None
+            w = _vertical_weights(weights, levels, bounds, nlev)
+        else:
+            if bounds is not None:
+                raise ValueError("explicit weights select the levels themselves: bounds must be None")
+            w = _vertical_weights(weights, None, None, nlev)
+            levels = None
+        sel = np.flatnonzero(w > 0)
+        step_dims = tuple(d for d in dims if d not in (lev, self._latitude_name, self._longitude_name))
+        out_dims = tuple(d for d in dims if d != lev)
+        ny, nx = da.shape[dims.index(self._latitude_name)], da.shape[dims.index(self._longitude_name)]
+        step_shape = tuple(da.shape[dims.index(d)] for d in step_dims)
+        steps = int(np.prod(step_shape)) if step_dims else 1
+        trk = _tracker()
+        resident = chunk_steps is None and step_dims == (self._time_name,)
+        logger.info('Calculating vertical mean of {} over {} of {} levels...'.format(variable, len(sel), nlev))
+        if chunk_steps is not None and step_dims:
+            runs = [(int(r[0]), len(r)) for r in np.split(sel, np.flatnonzero(np.diff(sel) != 1) + 1)]
+            dtype = np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
+            mean = trk.level_mean_cb(self._level_reader(da, dims, lev, step_dims, runs), (steps, len(sel), ny, nx), dtype, w[sel], skipna=skipna,
+                                     chunk_steps=int(chunk_steps))
+        else:
+            sort = [dims.index(d) for d in step_dims + (lev, self._latitude_name, self._longitude_name)]
+            arr = np.asarray(da.data).transpose(sort).reshape((steps, nlev, ny, nx))
+            if arr.dtype.kind != "f":
+                arr = arr.astype(np.float64)
+            mean = trk.level_mean(arr, w, skipna=skipna, keep_resident=resident)
+        if resident:
+            mean.flags.writeable = False                     # (its twin stays in HBM for calc_anom: see _fingerprint)
+        lead = step_dims + (self._latitude_name, self._longitude_name)
+        out = mean.reshape(step_shape + (ny, nx)).transpose([lead.index(d) for d in out_dims])
+        name = variable + '_vmean' if name is None else name
+        attrs = {}
+        if 'units' in da.attrs:
+            attrs['units'] = da.attrs['units']
+        attrs['long_name'] = da.attrs.get('long_name', variable) + ' vertical mean'
+        rule = weights if isinstance(weights, str) else 'given'
+        attrs['history'] = 'Calculated from {} with input attributes: bounds = {}, levels = {}, weights = {}{}.'.format(
+            variable, None if bounds is None else tuple(np.asarray(bounds).tolist()),
+            (np.asarray(levels)[sel].tolist() if levels is not None else sel.tolist()), rule, ', NaN levels skipped' if skipna else '')
+        self.ds[name] = (out_dims, out, attrs)
+        self._vmean_resident = (name, _fingerprint(np.asarray(self.ds[name].data)), trk.resident_level_mean_generation()) if resident else None
+        logger.info('Calculating vertical mean... DONE')
+
+    def _vmean_resident_for(self, variable, slab):
+        """True if `variable` is this instance's vertical mean and its twin is still the mean resident in HBM (slab: its
+        (time, lat, lon) view on the host)"""
+        res = getattr(self, "_vmean_resident", None)
+        if res is None or res[0] != variable or res[1] is None:
+            return False
+        trk = _tracker()
+        return res[1] == _fingerprint(np.asarray(self.ds[variable].data)) and res[2] == trk.resident_level_mean_generation() and \
+            trk.resident_level_mean() == (slab.shape[0], slab.shape[1], slab.shape[2], slab.dtype == np.float64)
+
     # ---- climatology / anomaly (contrack.py:458-581) on the device: SURVEY.md section 8(f) row N2 ------------------------
     def _group_ids(self, groupby):
         """(ids per timestep in 0..G-1, the G group values in ascending order) for time.<groupby> (dayofyear, month, ...)"""
@@ -846,7 +1056,10 @@ class contrack(object):
             self._anom_resident = None
             logger.info('Calculating Anomaly... DONE')
             return
-        anom, _ = _tracker().anomalies(slab, ids, len(uniq), window=window, smooth=smooth, clim=clim_arr, keep_resident=True)
+        if self._vmean_resident_for(variable, slab):         # (the mean calc_vertical_mean left in HBM: nothing to upload, same bits)
+            anom, _ = _tracker().anomalies_resident(ids, len(uniq), window=window, smooth=smooth, clim=clim_arr, keep_resident=True)
+        else:
+            anom, _ = _tracker().anomalies(slab, ids, len(uniq), window=window, smooth=smooth, clim=clim_arr, keep_resident=True)
         anom.flags.writeable = False                         # (its twin stays in HBM for run_contrack: see _fingerprint)
         out = anom.transpose(np.argsort(sort))
         self.ds['anom'] = (dims, out, attrs)

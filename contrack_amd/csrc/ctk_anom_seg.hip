@@ -130,6 +130,15 @@ static int anom_seg_check(const char *who, const void *h, int64_t T, int ny, int
     return segment_starts_check(who, starts, nseg, T);
 }
 
+// the arguments of the resident entries (the slab lies in HBM: T counts planes of an int32 index)
+static int anom_seg_args(const char *who, const void *h, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                         const int64_t *starts, int64_t nseg)
+{
+    CTKCHK(anom_seg_check(who, h, T, ny, nx, group, ngroups, window, smooth, starts, nseg));
+    if (T > 0x7fffffffll) return ctk_set_error(CTK_E_INVALID, "%s: T=%lld timesteps (at most 2^31 - 1)", who, (long long)T);
+    return CTK_OK;
+}
+
 // anomalies of the output steps [o0, o1) on the handle's stream (the window arguments: see the kernels)
 template <typename VT>
 static int launch_anom_seg(ctk_handle *h, const VT *x, int64_t xbase, int64_t xlo, int64_t xhi, const VT *clim, const int32_t *group_dev, const uint8_t *valid_dev,
@@ -146,26 +155,23 @@ static int launch_anom_seg(ctk_handle *h, const VT *x, int64_t xbase, int64_t xl
     return CTK_OK;
 }
 
-// ctk_anom_* with segments: anom_impl's steps, the anomaly kernel replaced
+// ctk_anom_* with segments on a slab in device memory (anom_impl's steps, the anomaly kernel replaced): the uploaded copy of a host
+// slab (anom_seg_impl), or the resident vertical mean (ctk_anom_seg_resident, ctk_level.hip); the caller has checked the arguments
+// (anom_seg_args)
 template <typename VT>
-static int anom_seg_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
-                         const VT *clim_in, VT *anom_out, VT *clim_out, int keep_resident, const int64_t *starts, int64_t nseg)
+static int anom_seg_dev(ctk_handle *h, const VT *x_dev, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                        const VT *clim_in, VT *anom_out, VT *clim_out, int keep_resident, const int64_t *starts, int64_t nseg)
 {
-    if (h && (!x_host || (!anom_out && !clim_out && !keep_resident))) return ctk_set_error(CTK_E_INVALID, "ctk_anom_seg: bad arguments");
-    CTKCHK(anom_seg_check("ctk_anom_seg", h, T, ny, nx, group, ngroups, window, smooth, starts, nseg));
-    if (T > 0x7fffffffll) return ctk_set_error(CTK_E_INVALID, "ctk_anom_seg: T=%lld timesteps (at most 2^31 - 1)", (long long)T);
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const int64_t npix = (int64_t)ny * nx;
     const size_t esz = sizeof(VT), n = (size_t)T * (size_t)npix, cb = (size_t)ngroups * npix * esz;
-    CTKCHK(ensure(h, h->io_in, n * esz));
     CTKCHK(ensure(h, h->an_out, n * esz));
     CTKCHK(ensure(h, h->an_clim, cb));
     h->an_pct_n = -1;                                                  // (an_raw is overwritten below)
     CTKCHK(ensure(h, h->an_raw, cb));
     CTKCHK(ensure(h, h->an_idx, ((size_t)2 * T + ngroups + 2) * 4));
     CTKCHK(ensure(h, h->an_valid, (size_t)T));
-    HIPCHK(hipMemcpy(h->io_in.p, x_host, n * esz, hipMemcpyHostToDevice));
     std::vector<int32_t> idx((size_t)2 * T + ngroups + 1);
     int32_t *tlist = idx.data(), *goff = tlist + T, *grp = goff + ngroups + 1;
     steps_by_group(group, T, ngroups, tlist, goff);
@@ -176,7 +182,7 @@ static int anom_seg_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int
     if (clim_in) {
         HIPCHK(hipMemcpy(h->an_clim.p, clim_in, cb, hipMemcpyHostToDevice));
     } else {
-        k_clim_raw<VT><<<dim3(gx, (unsigned)ngroups), 256, 0, s>>>((const VT *)h->io_in.p, d_tlist, d_goff, npix, (VT *)h->an_raw.p);
+        k_clim_raw<VT><<<dim3(gx, (unsigned)ngroups), 256, 0, s>>>(x_dev, d_tlist, d_goff, npix, (VT *)h->an_raw.p);
         k_clim_roll<VT><<<dim3(gx, (unsigned)std::min(ngroups, 64)), 256, 0, s>>>((const VT *)h->an_raw.p, ngroups, window, npix, (VT *)h->an_clim.p);
         HIPCHK(hipGetLastError());
     }
@@ -186,7 +192,7 @@ static int anom_seg_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int
         anom_window_valid(starts, nseg, T, smooth, valid);
         HIPCHK(hipMemcpy(h->an_valid.p, valid.data(), (size_t)T, hipMemcpyHostToDevice));
         h->an_T = -1; h->an_gen++;                                     // the resident slab (if any) is being overwritten
-        CTKCHK(launch_anom_seg<VT>(h, (const VT *)h->io_in.p, 0, 0, T, (const VT *)h->an_clim.p, d_grp, P<uint8_t>(h->an_valid), npix, smooth, 0, T, (VT *)h->an_out.p));
+        CTKCHK(launch_anom_seg<VT>(h, x_dev, 0, 0, T, (const VT *)h->an_clim.p, d_grp, P<uint8_t>(h->an_valid), npix, smooth, 0, T, (VT *)h->an_out.p));
         HIPCHK(hipStreamSynchronize(s));
         if (keep_resident) { h->an_T = T; h->an_ny = ny; h->an_nx = nx; h->an_f64 = sizeof(VT) == 8; }
         if (anom_out) {
@@ -196,6 +202,19 @@ static int anom_seg_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int
         }
     }
     return CTK_OK;
+}
+
+template <typename VT>
+static int anom_seg_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                         const VT *clim_in, VT *anom_out, VT *clim_out, int keep_resident, const int64_t *starts, int64_t nseg)
+{
+    if (h && (!x_host || (!anom_out && !clim_out && !keep_resident))) return ctk_set_error(CTK_E_INVALID, "ctk_anom_seg: bad arguments");
+    CTKCHK(anom_seg_args("ctk_anom_seg", h, T, ny, nx, group, ngroups, window, smooth, starts, nseg));
+    HIPCHK(hipSetDevice(h->device));
+    const size_t bytes = (size_t)T * (size_t)ny * (size_t)nx * sizeof(VT);
+    CTKCHK(ensure(h, h->io_in, bytes));
+    HIPCHK(hipMemcpy(h->io_in.p, x_host, bytes, hipMemcpyHostToDevice));
+    return anom_seg_dev<VT>(h, (const VT *)h->io_in.p, T, ny, nx, group, ngroups, window, smooth, clim_in, anom_out, clim_out, keep_resident, starts, nseg);
 }
 
 extern "C" int ctk_anom_seg_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,

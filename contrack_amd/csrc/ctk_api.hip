@@ -299,6 +299,14 @@ struct ctk_handle {
     int64_t an_T = -1; int an_ny = 0, an_nx = 0; bool an_f64 = false;
     uint64_t an_gen = 0;                           // bumped whenever the resident slab is written or dropped: WHICH slab is resident
     int64_t an_pct_n = -1;                         // an_raw holds the per-pixel quantiles of the last ctk_percentile_* call (-1: it does not)
+    // vertical mean (ctk_level.hip): the resident mean slab in a buffer of its own (io_in is reused by every tracking call), the table
+    // of weights and level indices of the running call
+    DevBuf lv_out, lv_tab;
+    int64_t lv_T = -1; int lv_ny = 0, lv_nx = 0; bool lv_f64 = false;
+    uint64_t lv_gen = 0;                           // bumped by every ctk_level_mean_* call and by ctk_release_io: WHICH mean is resident
+    int lv_form = -1;                              // form of the last k_level_mean launch (1 vector, 0 scalar; -1: none yet)
+    int lv_xcd_dbg = -1;                           // ctk_debug_set_level: xcd_chunk mode of the launches (-1: ctk_level_plan's)
+    int64_t lv_grid_dbg = 0, lv_grid = 0;          // ... a lower cap on the workgroups of a launch (0: none); workgroups of the last launch
     DevBuf io_in, io_out;                          // device copies of host-array calls (ctk_track_f32 / _f64)
     // streaming entries (ctk_track_stream_*): the slab passes through two chunk-sized device buffers per direction
     struct StreamIO *sio = nullptr;                // set for the duration of a streaming call: where the slab comes from
@@ -589,7 +597,7 @@ extern "C" void ctk_destroy(ctk_handle *h)
                       &h->rv_cand_cnt, &h->rv_cand_off, &h->rv_cand, &h->rv_cand_scratch, &h->rv_seam_res, &h->rv_scalars, &h->rv_mark, &h->rv_inv, &h->rv_ff,
                       &h->lc_rows, &h->lc_cnt, &h->lc_wlo, &h->lc_whi, &h->lc_w, &h->rv_dmap, &h->rv_dorig, &h->rv_dbox, &h->rv_inex, &h->rv_touch, &h->io_in, &h->io_out,
                       &h->sh_mask_next, &h->sh_send, &h->sh_recv, &h->sh_prev, &h->sh_elist, &h->sh_ovr_slot, &h->sh_ovr_val,
-                      &h->sh_amb_list, &h->sh_counts, &h->sh_cl_shared, &h->sh_cl_sent, &h->chunk_vals, &h->lc_work, &h->lc_ovf, &h->lc_ekeys, &h->lc_offs, &h->lc_sw, &h->lc_sp, &h->lc_out, &h->lc_cross, &h->lc_gtab, &h->lc_occ, &h->lc_cp, &h->an_out, &h->an_clim, &h->an_raw, &h->an_idx, &h->an_acc, &h->an_valid, &h->sd_parent, &h->sd_tmin, &h->sd_tmax, &h->sd_root, &h->sd_nops, &h->sd_lbox, &h->rv_pstate, &h->ci_bsum, &h->scan_bsum,
+                      &h->sh_amb_list, &h->sh_counts, &h->sh_cl_shared, &h->sh_cl_sent, &h->chunk_vals, &h->lc_work, &h->lc_ovf, &h->lc_ekeys, &h->lc_offs, &h->lc_sw, &h->lc_sp, &h->lc_out, &h->lc_cross, &h->lc_gtab, &h->lc_occ, &h->lc_cp, &h->an_out, &h->an_clim, &h->an_raw, &h->an_idx, &h->an_acc, &h->an_valid, &h->lv_out, &h->lv_tab, &h->sd_parent, &h->sd_tmin, &h->sd_tmax, &h->sd_root, &h->sd_nops, &h->sd_lbox, &h->rv_pstate, &h->ci_bsum, &h->scan_bsum,
                       &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order, &h->fq_counts, &h->fq_group, &h->seg_edge, &h->pc_hist, &h->pc_buf, &h->pf_out, &h->pf_idx};
     for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (h->h_blob) (void)hipHostFree(h->h_blob);
@@ -3384,8 +3392,9 @@ extern "C" int ctk_release_io(ctk_handle *h)
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
     HIPCHK(hipSetDevice(h->device));
-    for (DevBuf *b : {&h->io_in, &h->io_out, &h->an_out, &h->an_raw}) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+    for (DevBuf *b : {&h->io_in, &h->io_out, &h->an_out, &h->an_raw, &h->lv_out}) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
     h->an_T = -1; h->an_gen++; h->an_pct_n = -1;
+    h->lv_T = -1; h->lv_gen++;
     if (h->bounce) { h->bounce->destroy(); delete h->bounce; h->bounce = nullptr; }
     if (h->rle) { h->rle->crew.shutdown(); h->rle->destroy(); delete h->rle; h->rle = nullptr; }
     stream_teardown(h);
@@ -3849,6 +3858,7 @@ extern "C" int ctk_lifecycle_rows(ctk_handle *h, ctk_life_row *rows, int64_t cap
 #include "ctk_life_stream.hip"
 #include "ctk_pctl.hip"
 #include "ctk_pfield.hip"
+#include "ctk_level.hip"
 
 // device-memory helpers for a ctypes host
 // ------------------------------------------------------------------------------------------------

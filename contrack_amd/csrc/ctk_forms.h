@@ -530,3 +530,59 @@ inline CtkAnomPlan ctk_anom_plan(int elem_bytes, int smooth, int64_t nt, int64_t
     p.gy = (unsigned)std::max<int64_t>(1, (nt + tile - 1) / tile);
     return p;
 }
+
+// ------------------------------------------------------------------------------------------------
+// vertical mean over the selected levels (ctk_level.hip): k_level_mean, one thread per 16 bytes of adjacent pixels of one step (vector
+// form: every level plane starts on a 16-byte boundary) or per pixel (scalar form); a workgroup stays inside one step, so the step of a
+// workgroup is a scalar and `steps` never sits in a grid dimension that ends at 65 535
+// ------------------------------------------------------------------------------------------------
+#define CTK_LEVEL_THREADS 256
+#define CTK_LEVEL_UNROLL 8            // level planes whose loads of a lane are in flight together (then batches of 4, 2, 1 for the rest)
+#define CTK_LEVEL_MAX_SEL 4096        // selected levels of one call (weights and level indices: a device table of 12 bytes each)
+#define CTK_LEVEL_GRID_MAX 0xffffffll   // workgroups of a launch: gridDim.x * blockDim.x must stay below 2^32 work-items (as ctk_threshold_form)
+#define CTK_LEVEL_XCD_MIN 2048       // workgroups from which each XCD takes one contiguous eighth of the launch (xcd_chunk, ctk_kernels.hip)
+struct CtkLevelPlan {
+    int vec;                      // 1: 16-byte nontemporal loads and a 16-byte store, 0: the scalar form
+    int vpt;                      // pixels per thread: 16 / elem_bytes, or 1
+    int unroll;                   // the widest batch of level planes a lane loads before it uses the first
+    int64_t bps;                  // workgroups per step
+    int64_t blocks;               // bps * steps: (step, part of the plane) pairs, walked by ...
+    unsigned grid;                // ... this many workgroups (all of them unless that exceeds what a launch of 256 threads may have)
+    int xcd;                      // xcd_chunk mode of the launch: 1 one contiguous eighth of the workgroups per XCD, 0 launch order
+};
+// `aligned`: the input and output base pointers are multiples of 16; grid_max: CTK_LEVEL_GRID_MAX, or a test's lower cap
+inline CtkLevelPlan ctk_level_plan(int elem_bytes, int64_t nsel, int64_t npix, int64_t steps, bool aligned, int64_t grid_max = CTK_LEVEL_GRID_MAX)
+{
+    CtkLevelPlan p = {};
+    p.vec = aligned && (npix * elem_bytes) % 16 == 0;
+    p.vpt = p.vec ? 16 / elem_bytes : 1;
+    p.unroll = nsel >= CTK_LEVEL_UNROLL ? CTK_LEVEL_UNROLL : nsel >= 4 ? 4 : nsel >= 2 ? 2 : 1;
+    const int64_t lanes = (npix + p.vpt - 1) / p.vpt;
+    p.bps = (lanes + CTK_LEVEL_THREADS - 1) / CTK_LEVEL_THREADS;
+    p.blocks = p.bps * steps;
+    p.grid = (unsigned)std::min<int64_t>(p.blocks, std::min<int64_t>(std::max<int64_t>(grid_max, 1), CTK_LEVEL_GRID_MAX));
+    p.xcd = p.grid >= CTK_LEVEL_XCD_MIN ? 1 : 0;
+    return p;
+}
+// the selected levels (weight != 0) of a call in rising order, as runs of neighbours: run r covers levels [l0, l0 + len) of the input
+// and places [k0, k0 + len) of the compact chunk (nt, nsel, ny, nx) -- one strided copy each.  runs: room for (nlev + 1) / 2 of them.
+struct CtkLevelRun { int64_t l0, k0, len; };
+inline int64_t ctk_level_runs(const double *w, int64_t nlev, CtkLevelRun *runs, int64_t *nsel)
+{
+    int64_t nr = 0, k = 0;
+    for (int64_t l = 0; l < nlev; l++) {
+        if (w[l] == 0.0) continue;
+        if (nr > 0 && runs[nr - 1].l0 + runs[nr - 1].len == l) runs[nr - 1].len++;
+        else { runs[nr].l0 = l; runs[nr].k0 = k; runs[nr].len = 1; nr++; }
+        k++;
+    }
+    *nsel = k;
+    return nr;
+}
+// steps per chunk of the streamed entries: chunk_steps, or (0) about 256 MB of input, at least one step and at most all of them
+inline int64_t ctk_level_chunk(int64_t chunk_steps, int64_t steps, int64_t nsel, size_t plane_bytes)
+{
+    const size_t step_bytes = (size_t)nsel * plane_bytes;
+    int64_t c = chunk_steps > 0 ? chunk_steps : (int64_t)(((size_t)256 << 20) / std::max<size_t>(step_bytes, 1));
+    return std::min<int64_t>(std::max<int64_t>(c, 1), steps);
+}

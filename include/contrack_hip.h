@@ -96,7 +96,8 @@ int ctk_set_threshold_field(ctk_handle *h, const void *field, int elem_bytes, in
 int ctk_set_segments(ctk_handle *h, const int64_t *starts, int64_t nseg);
 
 /* The host-array entries keep device copies of the slab and of the result in the handle between calls (grow-only, so that
- * repeated calls do not reallocate).  ctk_release_io frees them (and the copy lanes): call it after a one-off large slab. */
+ * repeated calls do not reallocate).  ctk_release_io frees them (and the copy lanes, and the resident anomaly and vertical-mean
+ * slabs): call it after a one-off large slab. */
 int ctk_release_io(ctk_handle *h);
 
 /* float64 slabs (xarray often hands float64 anomalies): the compare is evaluated in float64, exactly as
@@ -526,6 +527,53 @@ int ctk_percentile_field_f32(ctk_handle *h, const float *x, int64_t T, int ny, i
                              double q, double *out /* ngroups * (y1 - y0) * nx */);
 int ctk_percentile_field_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group, int ngroups, int window,
                              double q, double *out /* ngroups * (y1 - y0) * nx */);
+
+/* ---- the vertical mean over a pressure band (README.rst:235-240: "The PV fields are vertically averaged between 500-150 hPa") ----
+ * The first step of the README's third recipe, the producer of the slab ctk_anom_* works on.  The reference has no function for it;
+ * tests/level_util.py is the numpy statement of what follows.
+ * x: (steps, nlev, ny, nx), float32 or float64, C-contiguous.  weights: nlev float64, each finite and >= 0, at least one > 0.
+ * A level with weights[l] == 0 is NOT SELECTED: never read, never uploaded, a NaN on it has no effect.  Per step s and pixel p, over
+ * the nsel selected levels in rising l, in float64:
+ *     acc = 0.0 ; ws = 0.0
+ *     acc = acc + weights[l] * (double)x[s][l][p]     -- a rounded multiply, then a rounded add: no fused multiply-add
+ *     ws  = ws + weights[l]
+ *     out[s][p] = (dtype)(acc / ws)                    -- float64 divide, then one rounding to x's dtype
+ * skipna = 0: a NaN on any selected level gives NaN.  skipna != 0: a level whose value is NaN contributes to neither acc nor ws of
+ * that pixel; all selected levels NaN gives NaN (0 / 0).  The bits are those of that loop.  With trapezoid weights over the pressure
+ * coordinate (contrack.level_weights) the mean is the integral of x dp over the band / its depth.
+ * At most 4096 selected levels (CTK_E_INVALID beyond).  CTK_E_INVALID with a message, the handle usable: a null pointer, a size
+ * below 1, a negative or non-finite weight, all weights zero, chunk_steps < 0, nothing to produce (out NULL and keep_resident 0).
+ *
+ * ctk_level_mean_f32_dev / _f64_dev: x and out (steps, ny, nx) in device memory; the unselected levels are skipped in place.
+ * ctk_level_mean_f32 / _f64 and ctk_level_mean_stream_f32 / _f64: host arrays (out may be NULL with keep_resident).  Only the
+ * selected levels are uploaded, neighbouring ones as one strided copy per chunk; the device holds two compact chunks
+ * (nt, nsel, ny, nx) and two output chunks, never steps x nlev planes: chunk k + 1 travels in while the kernel reduces chunk k and
+ * chunk k - 1 leaves.  chunk_steps = 0 (and the entries without it): about 256 MB of input per chunk.  Same bits for every
+ * chunk_steps.
+ * ctk_level_mean_stream_cb: the reader fills (nt, nsel, ny, nx) -- the SELECTED levels only, in rising level order -- for the steps
+ * [t0, t0 + nt); weights_sel are their nsel non-zero weights.  writer (may be NULL with keep_resident) receives the means of
+ * [t0, t0 + nt) in pinned memory valid during the call.  Both are called in increasing t0, once per chunk; a non-zero return ends
+ * the call with CTK_E_INVALID and leaves nothing in flight.
+ * keep_resident != 0: the mean slab stays in HBM in a buffer of its own (the tracking calls do not touch it) for
+ * ctk_anom_seg_resident.  ctk_resident_level_mean: its shape (steps = -1: nothing resident).  Its identity
+ * (ctk_resident_level_mean_generation) changes with every ctk_level_mean_* call and with ctk_release_io, which also frees it. */
+int ctk_level_mean_f32(ctk_handle *h, const float *x, int64_t steps, int nlev, int ny, int nx, const double *weights, int skipna, float *out, int keep_resident);
+int ctk_level_mean_f64(ctk_handle *h, const double *x, int64_t steps, int nlev, int ny, int nx, const double *weights, int skipna, double *out, int keep_resident);
+int ctk_level_mean_f32_dev(ctk_handle *h, const float *x_dev, int64_t steps, int nlev, int ny, int nx, const double *weights, int skipna, float *out_dev);
+int ctk_level_mean_f64_dev(ctk_handle *h, const double *x_dev, int64_t steps, int nlev, int ny, int nx, const double *weights, int skipna, double *out_dev);
+int ctk_level_mean_stream_f32(ctk_handle *h, const float *x, int64_t steps, int nlev, int ny, int nx, const double *weights, int skipna, float *out,
+                              int64_t chunk_steps, int keep_resident);
+int ctk_level_mean_stream_f64(ctk_handle *h, const double *x, int64_t steps, int nlev, int ny, int nx, const double *weights, int skipna, double *out,
+                              int64_t chunk_steps, int keep_resident);
+int ctk_level_mean_stream_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, int64_t steps, int nsel, int ny, int nx, ctk_read_chunk_fn reader,
+                             void *reader_user, const double *weights_sel, int skipna, ctk_write_values_fn writer, void *writer_user, int64_t chunk_steps,
+                             int keep_resident);
+int ctk_resident_level_mean(ctk_handle *h, int64_t *steps, int *ny, int *nx, int *is_f64);       /* steps = -1: nothing resident */
+int ctk_resident_level_mean_generation(ctk_handle *h, uint64_t *generation);
+/* ctk_anom_seg_f32 / _f64 with x taken from the resident mean: shape and dtype are the slab's, clim_in / anom_out / clim_out hold
+ * that dtype; the same kernels, the same bits, the same keep_resident (of the ANOMALY).  CTK_E_INVALID if no mean is resident. */
+int ctk_anom_seg_resident(ctk_handle *h, const int32_t *group, int ngroups, int window, int smooth, const void *clim_in, void *anom_out, void *clim_out,
+                          int keep_resident, const int64_t *starts, int64_t nseg);
 
 /* ---- the blocking-frequency climatology of the reference's tutorial (README.rst:159-160) ---------------------------------------
  *   xr.where(block['flag'] > 1, 1, 0).sum(dim='time') / block.ntime * 100     -- on the int32 flag slab (T, ny, nx), per group:

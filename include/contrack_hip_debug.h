@@ -199,6 +199,23 @@ int ctk_debug_lifecycle_plan(int64_t T, int ny, int nx, int f64, int64_t flag_al
  * form held it, 1 one pass over all its ids, 2 its ids split into two residue classes, 3 into four, ... */
 int ctk_debug_lifecycle_path(ctk_handle *h, int64_t *out8, uint8_t *steps, int64_t T);
 
+/* what ctk_level_plan (csrc/ctk_forms.h) decides for a ctk_level_mean_* launch over `steps` steps of planes of npix pixels of
+ * elem_bytes (4 / 8) with nsel selected levels, `aligned`: both base pointers are multiples of 16.  out7 = { 1 the vector form
+ * (16 bytes per lane) / 0 the scalar form, pixels per thread, the widest batch of level loads in flight, workgroups per step,
+ * workgroups of work (per step x steps), workgroups launched (at most 2^24 - 1; the kernel strides over the rest), 1 if every XCD takes one contiguous eighth of them (0: launch
+ * order) }.  Host only: no handle, no GPU. */
+int ctk_debug_level_plan(int elem_bytes, int64_t nsel, int64_t npix, int64_t steps, int aligned, int64_t *out7);
+/* test hook / experiments for the following k_level_mean launches on this handle: how workgroups map to XCDs (0 launch order, 1 one
+ * contiguous eighth per XCD, n > 1 tiles of n workgroups; -1: the rule above) and a lower cap on the workgroups of a launch, so that
+ * a small case walks the kernel's stride loop (0: the rule's cap, 2^24 - 1: a launch stays below 2^32 work-items) */
+int ctk_debug_set_level(ctk_handle *h, int xcd_mode, int64_t grid_max);
+/* test hook: out2 = { the form of the last k_level_mean launch on this handle (1 vector, 0 scalar, -1 none yet), its workgroups } */
+int ctk_debug_level_form(ctk_handle *h, int64_t *out2);
+/* measurement (tools/level_probe.py): k_level_mean alone on slabs in device memory (the arguments of ctk_level_mean_*_dev; is_f64 != 0:
+ * float64) between HIP events: one launch that is not counted, then `reps` timed ones; ms2 = { best, mean } */
+int ctk_debug_time_level_mean(ctk_handle *h, const void *x_dev, int is_f64, int64_t steps, int nlev, int ny, int nx, const double *weights, int skipna,
+                              void *out_dev, int reps, double *ms2);
+
 #ifdef __cplusplus
 }
 #endif
