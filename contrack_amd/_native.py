@@ -44,6 +44,8 @@ EXPORTS = [
     "ctk_anom_seg_f32", "ctk_anom_seg_f64", "ctk_anom_stream_f32", "ctk_anom_stream_f64", "ctk_anom_stream_cb", "ctk_debug_anom_form",
     "ctk_level_mean_f32", "ctk_level_mean_f64", "ctk_level_mean_f32_dev", "ctk_level_mean_f64_dev", "ctk_level_mean_stream_f32", "ctk_level_mean_stream_f64",
     "ctk_level_mean_stream_cb", "ctk_resident_level_mean", "ctk_resident_level_mean_generation", "ctk_anom_seg_resident", "ctk_debug_level_plan", "ctk_debug_level_form", "ctk_debug_time_level_mean", "ctk_debug_set_level",
+    "ctk_composite_f32_dev", "ctk_composite_f64_dev", "ctk_composite_f32", "ctk_composite_f64", "ctk_composite_cb",
+    "ctk_debug_composite_plan", "ctk_debug_set_composite", "ctk_debug_composite_launch", "ctk_debug_time_composite",
 ]
 
 READ_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)       # ctk_read_chunk_fn
@@ -65,6 +67,11 @@ class ContrackHipError(RuntimeError):
 
 class CommError(ContrackHipError):
     """CTK_E_COMM: another rank of the time-shard path gave up, died or did not arrive in time; the communicator is retired"""
+
+
+class InvalidArgumentError(ContrackHipError, ValueError):
+    """CTK_E_INVALID / CTK_E_RANGE from the composite entries: a ContrackHipError that `except ValueError` catches as well, as it
+    catches the same mistakes of the frequency entries"""
 
 
 class FormQuery(C.Structure):
@@ -101,6 +108,14 @@ def level_plan(elem_bytes, nsel, npix, steps, aligned=True):
     v = np.zeros(7, dtype=np.int64)
     check(lib().ctk_debug_level_plan(int(elem_bytes), int(nsel), int(npix), int(steps), int(bool(aligned)), v.ctypes.data))
     return dict(vec=int(v[0]), vpt=int(v[1]), unroll=int(v[2]), bps=int(v[3]), blocks=int(v[4]), grid=int(v[5]), xcd=int(v[6]))
+
+
+def composite_plan(elem_bytes, npix, unroll=-1):
+    """ctk_debug_composite_plan: what ctk_composite_plan (csrc/ctk_forms.h) decides for a k_composite launch, as a dict (unroll: the
+    widest batch of time steps, blocks, grid); unroll: what debug_set_composite would force; no handle, no GPU"""
+    v = np.zeros(3, dtype=np.int64)
+    check(lib().ctk_debug_composite_plan(int(elem_bytes), int(npix), int(unroll), v.ctypes.data))
+    return dict(unroll=int(v[0]), blocks=int(v[1]), grid=int(v[2]))
 
 
 def forms(T, ny, nx, nt=None, aligned16=True, async_passes=24, n_cus=256, **query):
@@ -147,6 +162,15 @@ def lib():
     L.ctk_frequency.argtypes = [p, p, i64, i32, i32, p, i32, C.c_int32, p, i64]
     L.ctk_frequency_cb.argtypes = [p, i64, i32, i32, READ_CHUNK_FN, p, p, i32, C.c_int32, p, i64]
     L.ctk_debug_set_freq.argtypes = [p, i64, i32]
+    for fn in (L.ctk_composite_f32_dev, L.ctk_composite_f64_dev):
+        fn.argtypes = [p, p, p, i64, i32, i32, p, i32, C.c_int32, i32, p, p, i32]
+    for fn in (L.ctk_composite_f32, L.ctk_composite_f64):
+        fn.argtypes = [p, p, p, i64, i32, i32, p, i32, C.c_int32, i32, p, p, i64]
+    L.ctk_composite_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, READ_CHUNK_FN, p, p, i32, C.c_int32, i32, p, p, i64]
+    L.ctk_debug_composite_plan.argtypes = [i32, i64, i32, p]
+    L.ctk_debug_set_composite.argtypes = [p, i32]
+    L.ctk_debug_composite_launch.argtypes = [p, p]
+    L.ctk_debug_time_composite.argtypes = [p, p, p, i32, i64, i32, i32, p, i32, C.c_int32, i32, p, p, i32, C.POINTER(dbl)]
     L.ctk_debug_time_freq.argtypes = [p, p, i64, i32, i32, p, i32, C.c_int32, p, i32, C.POINTER(dbl)]
     L.ctk_shard_label2d.argtypes = [p, p, i64, i32, i32, p, i32, p, i32]
     L.ctk_shard_label2d_f64.argtypes = [p, p, i64, i32, i32, p, i32, p, i32]
@@ -347,6 +371,18 @@ def _above(above):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data
+
+
+def _check_composite(rc):
+    """check() for the composite entries: a bad argument is an InvalidArgumentError"""
+    if rc in (-1, -4):
+        raise InvalidArgumentError("libcontrack_hip rc=%d: %s" % (rc, lib().ctk_last_error().decode("utf-8", "replace")))
+    check(rc)
+
+
+def _field_dtype(x):
+    """float64 stays, everything else is taken as float32 (as run_lifecycle takes its field)"""
+    return np.dtype(np.float64) if np.dtype(x) == np.float64 else np.dtype(np.float32)
 
 
 def check(rc):
@@ -871,6 +907,111 @@ class Tracker:
         g, G = _groups(group, T, ngroups)
         ms = (C.c_double * 2)()
         check(lib().ctk_debug_time_freq(self._h, flag_dev, int(T), int(ny), int(nx), _ptr(g), G, _above(above), counts_dev, int(reps), ms))
+        return float(ms[0]), float(ms[1])
+
+
+    # ---- composite over flagged time steps (the step after README.rst:156-164) ---------------------------------------
+    def composite(self, flag, x, group=None, ngroups=None, above=0, skipna=False, chunk_steps=0, resident_f64=False):
+        """(sum, n): sum[g, y, x] = the float64 sum, in time order, of x[t, y, x] over the t with group[t] == g and flag[t, y, x] >
+        above (with skipna: and x not NaN), n[g, y, x] how many there were, of an int32 (T, ny, nx) flag slab and a float32 /
+        float64 field slab of the same shape in host memory (ctk_composite_f32 / _f64: chunks of `chunk_steps` time steps of both
+        pass through the device, 0: about 256 MB of field each).  x None: the anomaly slab anomalies(keep_resident=True) left on
+        the device (resident_f64: its type).  Returns float64 and uint32 (ngroups, ny, nx)."""
+        flag = np.asarray(flag)
+        if flag.ndim != 3:
+            raise ValueError("flag must be (time, lat, lon)")
+        if flag.dtype != np.int32 and (flag.dtype.kind not in "iub" or flag.dtype.itemsize > 4 or flag.dtype == np.uint32):
+            raise ValueError("flag must be int32 here (wider ids: composite_cb, or contrack.composite_numpy)")
+        flag = np.ascontiguousarray(flag, dtype=np.int32)
+        T, ny, nx = flag.shape
+        if x is None:
+            f64 = bool(resident_f64)
+        else:
+            x = np.ascontiguousarray(x, dtype=_field_dtype(np.asarray(x).dtype))
+            if x.shape != flag.shape:
+                raise ValueError("the field has shape %s, the flag %s" % (x.shape, flag.shape))
+            f64 = x.dtype == np.float64
+        g, G = _groups(group, T, ngroups)
+        s = np.empty((max(G, 1), ny, nx), dtype=np.float64)
+        n = np.empty((max(G, 1), ny, nx), dtype=np.uint32)
+        fn = lib().ctk_composite_f64 if f64 else lib().ctk_composite_f32
+        _check_composite(fn(self._h, flag.ctypes.data, _ptr(x), T, ny, nx, _ptr(g), G, _above(above), int(bool(skipna)), s.ctypes.data, n.ctypes.data,
+                            int(chunk_steps)))
+        return s, n
+
+    def composite_cb(self, flag_reader, field_reader, shape, dtype, group=None, ngroups=None, above=0, skipna=False, chunk_steps=0):
+        """the same with both slabs read chunk by chunk: flag_reader(t0, nt, out) fills an int32 (nt, ny, nx) view of pinned memory
+        with the time steps [t0, t0 + nt), field_reader one of `dtype` (float32 / float64); the flag reader is called first.
+        field_reader None: the resident anomaly slab of `dtype`."""
+        T, ny, nx = (int(v) for v in shape)
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("the field must be float32 or float64")
+        g, G = _groups(group, T, ngroups)
+        s = np.empty((max(G, 1), ny, nx), dtype=np.float64)
+        n = np.empty((max(G, 1), ny, nx), dtype=np.uint32)
+        errors = []
+
+        def wrap(reader, ctype):
+            def rd(_user, t0, nt, dst):
+                try:
+                    reader(int(t0), int(nt), np.ctypeslib.as_array(C.cast(dst, C.POINTER(ctype)), shape=(nt, ny, nx)))
+                    return 0
+                except BaseException as e:                # an exception must not cross the C frames
+                    errors.append(e)
+                    return 1
+            return READ_CHUNK_FN(rd)
+        fcb = wrap(flag_reader, C.c_int32)
+        xcb = wrap(field_reader, C.c_float if dt == np.float32 else C.c_double) if field_reader is not None else C.cast(None, READ_CHUNK_FN)
+        rc = lib().ctk_composite_cb(self._h, dt.itemsize, T, ny, nx, fcb, None, xcb, None, _ptr(g), G, _above(above), int(bool(skipna)),
+                                    s.ctypes.data, n.ctypes.data, int(chunk_steps))
+        if errors:
+            raise errors[0]
+        _check_composite(rc)
+        return s, n
+
+    def composite_dev(self, flag_dev, x_dev, T, ny, nx, group=None, ngroups=None, above=0, skipna=False, f64=False, sum_dev=None, n_dev=None,
+                      accumulate=False):
+        """ctk_composite_*_dev on an int32 flag and a float32 (f64: float64) field in device memory; x_dev None: the resident anomaly
+        slab.  sum_dev / n_dev None: (sum, n) are returned; else they are written to (accumulate: continued from) those device
+        buffers of ngroups * ny * nx float64 / uint32 and None is returned."""
+        g, G = _groups(group, T, ngroups)
+        fn = lib().ctk_composite_f64_dev if f64 else lib().ctk_composite_f32_dev
+        args = (self._h, flag_dev, x_dev, int(T), int(ny), int(nx), _ptr(g), G, _above(above), int(bool(skipna)))
+        if (sum_dev is None) != (n_dev is None):
+            raise ValueError("sum_dev and n_dev go together")
+        if sum_dev is not None:
+            _check_composite(fn(*args, sum_dev, n_dev, int(bool(accumulate))))
+            return None
+        s = np.empty((max(G, 1), int(ny), int(nx)), dtype=np.float64)
+        n = np.empty((max(G, 1), int(ny), int(nx)), dtype=np.uint32)
+        ds, dn = self.malloc(max(s.nbytes, 8)), self.malloc(max(n.nbytes, 4))
+        try:
+            _check_composite(fn(*args, ds, dn, 0))
+            self.d2h(s, ds)
+            self.d2h(n, dn)
+        finally:
+            self.free(ds)
+            self.free(dn)
+        return s, n
+
+    def debug_set_composite(self, unroll=-1):
+        """test hook for the following composite launches: the widest batch of time steps, -1 the rule (ctk_composite_plan)"""
+        check(lib().ctk_debug_set_composite(self._h, int(unroll)))
+
+    def debug_composite_launch(self):
+        """(widest batch, workgroups) of the last composite launch; (0, 0): none yet"""
+        v = np.zeros(2, dtype=np.int64)
+        check(lib().ctk_debug_composite_launch(self._h, v.ctypes.data))
+        return int(v[0]), int(v[1])
+
+    def time_composite(self, flag_dev, x_dev, T, ny, nx, sum_dev, n_dev, group=None, ngroups=None, above=0, skipna=False, f64=False, reps=5):
+        """k_composite alone between HIP events (sum_dev / n_dev: device buffers of ngroups * ny * nx float64 / uint32): (best, mean)
+        ms per launch"""
+        g, G = _groups(group, T, ngroups)
+        ms = (C.c_double * 2)()
+        check(lib().ctk_debug_time_composite(self._h, flag_dev, x_dev, int(bool(f64)), int(T), int(ny), int(nx), _ptr(g), G, _above(above),
+                                             int(bool(skipna)), sum_dev, n_dev, int(reps), ms))
         return float(ms[0]), float(ms[1])
 
     # ---- calc_anom / percentile threshold on the device ---------------------------------------------------------

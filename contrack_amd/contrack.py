@@ -246,6 +246,58 @@ def frequency_numpy(flag, group=None, above=0, percent=True, device=None, chunk_
     return out[0] if group is None else out
 
 
+def composite_mean(sum, n):
+    """sum / n in float64, NaN where n == 0 (numpy's 0 / 0): the mean of a composite from what composite_numpy returns"""
+    sum = np.asarray(sum, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(np.asarray(n) == 0, np.nan, sum / np.asarray(n))
+
+
+def composite_numpy(flag, x, group=None, above=0, skipna=False, chunk_steps=None, device=None, shape=None, dtype=None):
+    """the composite of a float field over the flagged time steps, ds[var].where(ds[flag] > above).groupby(...).sum('time') with
+    its count: (sum, n), sum[g] the float64 sum IN TIME ORDER of x[t] over the steps t of group g with flag[t] > above (skipna: and
+    x[t] not NaN) at every grid point, n[g] (uint32) how many there were; composite_mean(sum, n) is the mean.  flag (time, lat,
+    lon) integer, x of the same shape (float64 stays, everything else is taken as float32); group: one id in [0, G) per time step,
+    any order in time, None: one group (the leading axis is then dropped).  The sums run on the GPU (ctk_composite_*) and are the
+    same bits whatever chunk_steps: time steps per chunk on both slabs' way through the device (None or 0: about 256 MB of field).
+    x None: the anomaly slab calc_anom left on the device (`dtype` its type), only the flags travel.  With shape=(T, ny, nx) and
+    dtype, flag and x may be readers reader(t0, nt, out) (ctk_composite_cb); flags wider than int32 are narrowed chunk by chunk
+    (an id beyond int32 raises ValueError)."""
+    steps = 0 if chunk_steps is None else int(chunk_steps)
+    if callable(flag) or callable(x):
+        if shape is None or (dtype is None and (x is None or callable(x))):
+            raise ValueError("a reader needs shape=(T, ny, nx) and the field's dtype")
+    if not callable(flag):
+        flag = flag if isinstance(flag, np.memmap) else np.asarray(flag)
+        if flag.ndim != 3:
+            raise ValueError("flag must be (time, lat, lon)")
+        if flag.dtype.kind not in "iub":
+            raise ValueError("flag must be an integer field")
+        if shape is None:
+            shape = flag.shape
+    if x is not None and not callable(x):
+        x = x if isinstance(x, np.memmap) else np.asarray(x)
+        if tuple(x.shape) != tuple(int(v) for v in shape):
+            raise ValueError("the field has shape {}, the flag {}".format(x.shape, tuple(shape)))
+        dtype = _native._field_dtype(x.dtype)
+    dtype = np.dtype(dtype if dtype is not None else np.float32)
+    T = int(shape[0])
+    ids, G = _native._groups(group, T)
+    trk = _tracker(device)
+    if not callable(flag) and not callable(x) and (flag.dtype.itemsize < 4 or flag.dtype == np.int32):
+        s, n = trk.composite(flag, x, ids, G, above, skipna, steps, resident_f64=dtype == np.float64)
+    else:
+        fread, xread = flag, x
+        if not callable(flag):
+            def fread(t0, nt, out, slab=flag):
+                out[...] = _int32_chunk(slab[t0:t0 + nt])
+        if x is not None and not callable(x):
+            def xread(t0, nt, out, slab=x):
+                out[...] = slab[t0:t0 + nt]
+        s, n = trk.composite_cb(fread, xread, shape, dtype, ids, G, above, skipna, steps)
+    return (s[0], n[0]) if group is None else (s, n)
+
+
 def anomalies_numpy(x, group, ngroups=None, window=1, smooth=1, clim=None, segments=None, chunk_steps=None, device=None):
     """calc_clim / calc_anom on a (time, lat, lon) float slab: `group` holds one id in [0, G) per timestep (G = ngroups, or
     max(group) + 1), the climatology is the mean per group smoothed over `window` groups (or `clim`, (G, ny, nx)), the anomaly is
@@ -1568,6 +1620,87 @@ class contrack(object):
                  'history': ' '.join(['Calculated from {} with input attributes:', 'flag > {},', 'groupby = {}.']).format(
                      flag, above, groupby)}
         return self._wrap(da, np.ascontiguousarray(data), out_dims, coords, attrs, name='frequency')
+
+    # ---- composite over the flagged time steps: what a study computes after the frequency map (README.rst:156-164) ----------
+    def calc_composite(self, variable, flag='flag', groupby=None, above=0, skipna=False, stat='mean', chunk_steps=None, pool=False, return_count=False):
+        """mean (stat='mean') or sum (stat='sum') of `variable` over the time steps with flag > above at every grid point:
+        ds[variable].where(ds[flag] > above).mean('time') -- or, with groupby ('month', 'season', 'year', ...), the same per value
+        of time.<groupby>, ordered as calc_frequency orders them.  The sums are float64 and added in time order on the GPU
+        (composite_numpy), so the result is reproducible bit for bit; a grid point that is never flagged gives NaN (mean) or 0
+        (sum).  skipna: a NaN value is not counted; without it one makes the result NaN.  Returns a labelled float64 array over the
+        variable's spatial dims, the group dim in the time dim's place, with the variable's units; it is not added to the dataset.
+        return_count=True: (composite, n), n the uint32 count of selected steps with the same dims.
+        A 4-D flag (time, lat, lon and a member dimension in any order, what run_contrack(segments=<dim>) writes; `variable` must
+        have the same dims) gives one composite per member, the member dimension in its place; pool=True pools the members (the
+        member dimension is dropped; the order of the additions is member after member, each in time order).
+        chunk_steps: both variables are read slice by slice (`isel`, a chunk that spans two members in two pieces) and pass
+        through chunk-sized device buffers; neither slab is built on the host.  Same bits.  When `variable` is the anomaly
+        calc_anom left in HBM, only the flags are uploaded."""
+        self._ensure_set_up()
+        if stat not in ('mean', 'sum'):
+            raise ValueError("stat must be 'mean' or 'sum', not {!r}".format(stat))
+        fda, vda = self.ds[flag], self.ds[variable]
+        dims, member = self._consumer_dims(flag)
+        vdims = tuple(vda.dims)
+        if sorted(vdims) != sorted(dims) or any(vda.shape[vdims.index(d)] != fda.shape[dims.index(d)] for d in dims):
+            raise ValueError("the variable {!r} has dims {}, the flag variable {!r} has {}: they must be the same".format(variable, vdims, flag, dims))
+        if np.dtype(fda.dtype).kind not in "iub":
+            raise ValueError("flag variable {!r} is not an integer field".format(flag))
+        names = (self._time_name, self._latitude_name, self._longitude_name)
+        ids, uniq = (None, None) if groupby is None else self._group_ids(groupby)
+        T = fda.shape[dims.index(self._time_name)]
+        M = 1 if member is None else fda.shape[dims.index(member)]
+        G = 1 if ids is None else len(uniq)
+        per_member = member is not None and not pool
+        gids = np.zeros(T, dtype=np.int32) if ids is None else ids
+        if per_member:                                           # the library sees group m * G + g
+            gids = (np.arange(M, dtype=np.int32)[:, None] * G + gids[None, :]).reshape(-1)
+        else:
+            gids = np.tile(gids, M)
+        group = gids if (per_member or ids is not None) else None
+        vtype = _native._field_dtype(vda.dtype)
+        if chunk_steps is None:
+            flags, field = self._flat_slab(fda, dims, member), self._flat_slab(vda, vdims, member)
+            field = field.astype(vtype, copy=False)
+            resident = self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, field.shape, vtype == np.float64)
+            s, n = composite_numpy(flags, None if resident else field, group, above=above, skipna=skipna, dtype=vtype)
+        else:
+            if member is None:
+                fread, shape, _ = self._time_reader(fda, dims, integer=True)
+                vread = self._time_reader(vda, vdims)[0]
+            else:
+                fread, shape, _ = self._member_reader(fda, dims, member, integer=True)
+                vread = self._member_reader(vda, vdims, member)[0]
+            s, n = composite_numpy(fread, vread, group, above=above, skipna=skipna, chunk_steps=chunk_steps, shape=shape, dtype=vtype)
+        s, n = s.reshape((-1,) + s.shape[-2:]), n.reshape((-1,) + n.shape[-2:])
+        out = composite_mean(s, n) if stat == 'mean' else s
+        lead = ((member,) if per_member else ()) + ((groupby,) if groupby is not None else ())
+        have = lead + names[1:]
+        gone = ((self._time_name,) if groupby is None else ()) + ((member,) if member is not None and pool else ())
+        out_dims = tuple(groupby if d == self._time_name else d for d in dims if d not in gone)
+
+        def shaped(a):
+            if per_member:
+                a = a.reshape((M, G) + a.shape[1:])
+            if ids is None:
+                a = a[:, 0] if per_member else a[0]
+            return np.ascontiguousarray(a.transpose([have.index(d) for d in out_dims]))
+        coords = {} if groupby is None else {groupby: uniq}
+        if member in lead:
+            coords[member] = self._dim_values(member, M)
+        for name in (self._latitude_name, self._longitude_name):
+            coords[name] = np.asarray(self.ds[name].data)
+        attrs = {'long_name': 'contrack composite', 'standard_name': 'contrack composite',
+                 'history': ' '.join(['Calculated from {} with input attributes:', 'flag = {} > {},', 'groupby = {},', 'stat = {},', 'skipna = {}.']).format(
+                     variable, flag, above, groupby, stat, skipna)}
+        units = getattr(vda, 'attrs', {}).get('units')
+        if units is not None:
+            attrs['units'] = units
+        res = self._wrap(vda, shaped(out), out_dims, coords, attrs, name='composite')
+        if not return_count:
+            return res
+        cattrs = {'long_name': 'contrack composite count', 'units': '1', 'history': attrs['history']}
+        return res, self._wrap(vda, shaped(n), out_dims, coords, cattrs, name='count')
 
     # ---- life cycle (contrack.py:798-906), consumer of `flag` (SURVEY.md section 8(f) N1) ----------------------------
     def _time_labels(self):

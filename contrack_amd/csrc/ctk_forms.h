@@ -586,3 +586,40 @@ inline int64_t ctk_level_chunk(int64_t chunk_steps, int64_t steps, int64_t nsel,
     int64_t c = chunk_steps > 0 ? chunk_steps : (int64_t)(((size_t)256 << 20) / std::max<size_t>(step_bytes, 1));
     return std::min<int64_t>(std::max<int64_t>(c, 1), steps);
 }
+
+// ------------------------------------------------------------------------------------------------
+// composite over flagged time steps (ctk_composite.hip): k_composite, one lane per pixel for ALL time steps of a launch -- T is never
+// split, the float64 sums are added in time order.  What keeps the kernel busy is loads in flight: about pixels * (4 + elem_bytes) *
+// unroll bytes, against CTK_COMPOSITE_FLIGHT chip-wide (256 CUs of ~32 KiB each).  A 1-degree plane needs the longest batch of steps;
+// a quarter-degree plane fills the chip by itself, and there the batch only spreads the one dependent trip (flags, then the field of
+// the lanes that passed) over more steps: 8 and 16 measured the same, 4 a sixth slower (profiles/NOTES.md).
+// ------------------------------------------------------------------------------------------------
+#define CTK_COMPOSITE_THREADS 256
+#define CTK_COMPOSITE_UNROLL_MAX 16            // time steps whose loads of a lane are in flight together (then 8, 4, 2, 1 for the rest)
+#define CTK_COMPOSITE_UNROLL_MIN 8
+#define CTK_COMPOSITE_FLIGHT (8ll << 20)       // bytes in flight that fill the chip
+#define CTK_COMPOSITE_GRID_MAX 0xffffffll      // workgroups of a launch: gridDim.x * blockDim.x stays below 2^32 work-items (as CTK_LEVEL_GRID_MAX)
+struct CtkCompositePlan {
+    int unroll;                   // the widest batch of time steps a lane loads before it uses the first (a power of two)
+    int64_t blocks;               // parts of the plane of 256 pixels each, walked by ...
+    unsigned grid;                // ... this many workgroups
+};
+// unroll: a test's choice (ctk_debug_set_composite), rounded down to a power of two and capped; -1 the rule
+inline CtkCompositePlan ctk_composite_plan(int elem_bytes, int64_t npix, int unroll = -1)
+{
+    CtkCompositePlan p = {};
+    const int64_t want = CTK_COMPOSITE_FLIGHT / std::max<int64_t>(npix * (4 + elem_bytes), 1);
+    int u = CTK_COMPOSITE_UNROLL_MAX;
+    while (u > CTK_COMPOSITE_UNROLL_MIN && u > want) u >>= 1;
+    if (unroll > 0) { u = 1; while (u * 2 <= unroll && u * 2 <= CTK_COMPOSITE_UNROLL_MAX) u <<= 1; }
+    p.unroll = u;
+    p.blocks = (npix + CTK_COMPOSITE_THREADS - 1) / CTK_COMPOSITE_THREADS;
+    p.grid = (unsigned)std::min<int64_t>(p.blocks, CTK_COMPOSITE_GRID_MAX);
+    return p;
+}
+// steps per chunk of the host entries: chunk_steps, or (0) about 256 MB of field, at least one step and at most all of them
+inline int64_t ctk_composite_chunk(int64_t chunk_steps, int64_t T, size_t plane_bytes)
+{
+    int64_t c = chunk_steps > 0 ? chunk_steps : (int64_t)(((size_t)256 << 20) / std::max<size_t>(plane_bytes, 1));
+    return std::min<int64_t>(std::max<int64_t>(c, 1), T);
+}

@@ -591,6 +591,38 @@ int ctk_frequency(ctk_handle *h, const int32_t *flag, int64_t T, int ny, int nx,
 int ctk_frequency_cb(ctk_handle *h, int64_t T, int ny, int nx, ctk_read_chunk_fn reader, void *reader_user, const int32_t *group, int ngroups,
                      int32_t above, uint32_t *counts /* host */, int64_t chunk_steps);
 
+/* ---- composites: the step after the frequency map of the reference's tutorial (README.rst:156-164) ------------------------------
+ * The tutorial ends with the blocking frequency; the composite is what a study computes next: the mean of a field (the tracked
+ * anomaly itself, temperature, precipitation) over the time steps at which a grid point is blocked, in all or per group:
+ *   ds[var].where(ds[flag] > above).groupby(...).mean('time')
+ * On the int32 flag slab and a float32 / float64 field slab over the same T time steps, per grid point p, for t = 0 .. T-1 RISING:
+ *   if flag[t][p] > above (and, with skipna, x[t][p] is not NaN):  sum[group[t]][p] += (double)x[t][p];  n[group[t]][p] += 1
+ * sum starts at +0.0 (float64), n at 0 (uint32); an unselected step adds nothing (not + 0.0); without skipna a selected NaN makes the
+ * sum NaN; +inf and -inf make NaN.  The additions of a pixel happen in time order and T is never split over threads, so the sums are
+ * reproducible bit for bit whatever the kernel form or the chunking (k_composite, ctk_composite.hip).  The caller divides:
+ * mean = sum / n in float64, NaN where n == 0.  group: T host ints in [0, ngroups), any order in time; NULL = one group.
+ * ctk_composite_*_dev: both slabs in HBM; x_dev == NULL: the anomaly slab ctk_anom_* left resident on this handle (its shape and type
+ * must be the call's: CTK_E_STATE otherwise).  accumulate = 1 continues from the given accumulators (a caller's own chunks, later
+ * time shards: the time order is then the order of the calls), 0 starts from zero.
+ * ctk_composite_f32 / _f64: host arrays; both slabs pass through chunk-sized device buffers, two chunks of flags and two of the field,
+ * chunk k+1 uploaded while chunk k is reduced (chunk_steps = 0: about 256 MB of field per chunk); the accumulators stay in HBM until
+ * the last chunk.  x == NULL: the resident anomaly slab, only the flags cross PCIe.
+ * ctk_composite_cb: two readers (ctk_read_chunk_fn: int32 flags, field elements of elem_bytes), contract and threading rules of
+ * ctk_lifecycle_stream_cb's; the flag reader is called before the field reader for every chunk; field_reader == NULL: the resident
+ * anomaly slab of elem_bytes.  T must stay below 2^32 (uint32 counts). */
+int ctk_composite_f32_dev(ctk_handle *h, const int32_t *flag_dev, const float *x_dev, int64_t T, int ny, int nx, const int32_t *group, int ngroups,
+                          int32_t above, int skipna, double *sum_dev /* [ngroups][ny][nx] */, uint32_t *n_dev /* [ngroups][ny][nx] */,
+                          int accumulate /* 0: start from zero, 1: continue */);
+int ctk_composite_f64_dev(ctk_handle *h, const int32_t *flag_dev, const double *x_dev, int64_t T, int ny, int nx, const int32_t *group, int ngroups,
+                          int32_t above, int skipna, double *sum_dev, uint32_t *n_dev, int accumulate);
+int ctk_composite_f32(ctk_handle *h, const int32_t *flag, const float *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int32_t above,
+                      int skipna, double *sum /* host [ngroups][ny][nx] */, uint32_t *n /* host */, int64_t chunk_steps);
+int ctk_composite_f64(ctk_handle *h, const int32_t *flag, const double *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int32_t above,
+                      int skipna, double *sum, uint32_t *n, int64_t chunk_steps);
+int ctk_composite_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, int64_t T, int ny, int nx, ctk_read_chunk_fn flag_reader, void *flag_user,
+                     ctk_read_chunk_fn field_reader, void *field_user, const int32_t *group, int ngroups, int32_t above, int skipna, double *sum,
+                     uint32_t *n, int64_t chunk_steps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -216,6 +216,21 @@ int ctk_debug_level_form(ctk_handle *h, int64_t *out2);
 int ctk_debug_time_level_mean(ctk_handle *h, const void *x_dev, int is_f64, int64_t steps, int nlev, int ny, int nx, const double *weights, int skipna,
                               void *out_dev, int reps, double *ms2);
 
+/* what ctk_composite_plan (csrc/ctk_forms.h) decides for a k_composite launch over planes of npix pixels and a field of elem_bytes
+ * (4 / 8); unroll: what ctk_debug_set_composite would force (-1: the rule).  out3 = { the widest batch of time steps in flight,
+ * workgroups of work (256 pixels each), workgroups launched (at most 2^24 - 1; the kernel strides over the rest) }.  Host only: no
+ * handle, no GPU. */
+int ctk_debug_composite_plan(int elem_bytes, int64_t npix, int unroll, int64_t *out3);
+/* test hook for the following k_composite launches on this handle: the widest batch of time steps (rounded down to a power of two,
+ * at most 16), -1 the rule */
+int ctk_debug_set_composite(ctk_handle *h, int unroll);
+/* test hook: out2 = { the widest batch of the last k_composite launch on this handle (0: none yet), its workgroups } */
+int ctk_debug_composite_launch(ctk_handle *h, int64_t *out2);
+/* measurement (tools/composite_probe.py): k_composite alone on slabs in device memory (is_f64 != 0: a float64 field) between HIP
+ * events: one launch from zeroed accumulators that is not counted, then `reps` timed ones that continue from them; ms2 = { best, mean } */
+int ctk_debug_time_composite(ctk_handle *h, const int32_t *flag_dev, const void *x_dev, int is_f64, int64_t T, int ny, int nx, const int32_t *group,
+                             int ngroups, int32_t above, int skipna, double *sum_dev, uint32_t *n_dev, int reps, double *ms2);
+
 #ifdef __cplusplus
 }
 #endif
