@@ -2765,6 +2765,7 @@ static int track_dev_impl(ctk_handle *h, const void *anom_dev, bool f64, int64_t
         h->ms[CTK_T_HOST_RESOLVE] += now_ms() - t1;
         h->stats[CTK_S_AMBIGUOUS] = res->n_ambiguous;
         h->stats[CTK_S_EXACT_FIXUPS] = res->n_exact;
+        h->stats[CTK_S_OPS] = res->nops;                          // (the host resolver's own seam merge: ctk_resolve.cpp, step 4b)
         int rc = ctk_shard_extents(h, res, 0, 0, nullptr, nullptr);
         ctk_result_free(res);
         CTKCHK(rc);
