@@ -41,7 +41,7 @@ EXPORTS = [
     "ctk_frequency_dev", "ctk_frequency", "ctk_frequency_cb", "ctk_debug_set_freq", "ctk_debug_time_freq",
     "ctk_percentile_groups_f32", "ctk_percentile_groups_f64", "ctk_debug_percentile_groups_sweeps", "ctk_debug_time_percentile_groups",
     "ctk_percentile_field_f32", "ctk_percentile_field_f64", "ctk_debug_percentile_field_plan", "ctk_debug_percentile_field_form", "ctk_debug_time_percentile_field",
-    "ctk_anom_seg_f32", "ctk_anom_seg_f64", "ctk_anom_stream_f32", "ctk_anom_stream_f64", "ctk_anom_stream_cb", "ctk_debug_anom_form",
+    "ctk_anom_seg_f32", "ctk_anom_seg_f64", "ctk_anom_stream_f32", "ctk_anom_stream_f64", "ctk_anom_stream_cb", "ctk_debug_anom_form", "ctk_debug_anom_plan", "ctk_debug_set_anom", "ctk_debug_anom_launch",
     "ctk_level_mean_f32", "ctk_level_mean_f64", "ctk_level_mean_f32_dev", "ctk_level_mean_f64_dev", "ctk_level_mean_stream_f32", "ctk_level_mean_stream_f64",
     "ctk_level_mean_stream_cb", "ctk_resident_level_mean", "ctk_resident_level_mean_generation", "ctk_anom_seg_resident", "ctk_debug_level_plan", "ctk_debug_level_form", "ctk_debug_time_level_mean", "ctk_debug_set_level",
     "ctk_composite_f32_dev", "ctk_composite_f64_dev", "ctk_composite_f32", "ctk_composite_f64", "ctk_composite_cb",
@@ -100,6 +100,14 @@ def debug_lifecycle_plan(T, ny, nx, f64=False, flag_align=0, field_align=0):
     v = np.zeros(5, dtype=np.int64)
     check(lib().ctk_debug_lifecycle_plan(int(T), int(ny), int(nx), int(bool(f64)), int(flag_align), int(field_align), v.ctypes.data))
     return dict(rw=int(v[0]), nsx=int(v[1]), nby=int(v[2]), vec=int(v[3]), ks=int(v[4]))
+
+
+def anom_plan(elem_bytes, smooth, nt, npix, waves_wanted=0, grid_y_max=0):
+    """ctk_debug_anom_plan: what ctk_anom_plan (csrc/ctk_forms.h) decides for an anomaly launch of nt output steps, as a dict (form 1 LDS
+    ring / 0 plain, lds bytes, tile output steps per workgroup, gx, gy); waves_wanted / grid_y_max: 0 the rule's.  Host only."""
+    v = np.zeros(5, dtype=np.int64)
+    check(lib().ctk_debug_anom_plan(int(elem_bytes), int(smooth), int(nt), int(npix), int(waves_wanted), int(grid_y_max), v.ctypes.data))
+    return dict(zip(("form", "lds", "tile", "gx", "gy"), (int(a) for a in v)))
 
 
 def level_plan(elem_bytes, nsel, npix, steps, aligned=True):
@@ -253,6 +261,9 @@ def lib():
         getattr(L, name).argtypes = [p, p, i64, i32, i32, p, i32, i32, i32, p, i64, p, p, p, i64]
     L.ctk_anom_stream_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, p, i32, i32, i32, p, i64, p, p, WRITE_CHUNK_FN, p, i64]
     L.ctk_debug_anom_form.argtypes = [p, C.POINTER(i64)]
+    L.ctk_debug_anom_plan.argtypes = [i32, i32, i64, i64, i64, i64, p]
+    L.ctk_debug_set_anom.argtypes = [p, i64, i64]
+    L.ctk_debug_anom_launch.argtypes = [p, p]
     for name in ("ctk_level_mean_f32", "ctk_level_mean_f64"):
         getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, p, i32, p, i32]
     for name in ("ctk_level_mean_f32_dev", "ctk_level_mean_f64_dev"):
@@ -1274,6 +1285,17 @@ class Tracker:
         v = C.c_int64(0)
         check(lib().ctk_debug_anom_form(self._h, C.byref(v)))
         return int(v.value)
+
+    def debug_set_anom(self, waves_wanted=0, grid_y_max=0):
+        """for the following anomalies(segments=...) / anomalies_stream / anomalies_resident launches: ctk_anom_plan's waves_wanted and
+        grid_y_max (0: the rule's), so that a small slab reaches the tile edges"""
+        check(lib().ctk_debug_set_anom(self._h, int(waves_wanted), int(grid_y_max)))
+
+    def debug_anom_launch(self):
+        """dict of the last anomaly launch (form, tile, gx, gy, lds, o0, o1) and `launches`, their number in the last call"""
+        v = np.zeros(8, dtype=np.int64)
+        check(lib().ctk_debug_anom_launch(self._h, v.ctypes.data))
+        return dict(zip(("form", "tile", "gx", "gy", "lds", "o0", "o1", "launches"), (int(a) for a in v)))
 
     def resident_anom(self):
         T, ny, nx, f = C.c_int64(0), C.c_int(0), C.c_int(0), C.c_int(0)

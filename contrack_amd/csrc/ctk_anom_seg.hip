@@ -144,8 +144,11 @@ template <typename VT>
 static int launch_anom_seg(ctk_handle *h, const VT *x, int64_t xbase, int64_t xlo, int64_t xhi, const VT *clim, const int32_t *group_dev, const uint8_t *valid_dev,
                            int64_t npix, int smooth, int64_t o0, int64_t o1, VT *out)
 {
-    const CtkAnomPlan pl = ctk_anom_plan((int)sizeof(VT), smooth, o1 - o0, npix);
+    const CtkAnomPlan pl = ctk_anom_plan((int)sizeof(VT), smooth, o1 - o0, npix, h->an_waves_dbg > 0 ? h->an_waves_dbg : CTK_ANOM_WAVES,
+                                         h->an_gy_dbg > 0 ? std::min<int64_t>(h->an_gy_dbg, 65535) : 65535);
     h->an_form = pl.form;
+    h->an_last[0] = pl.tile; h->an_last[1] = pl.gx; h->an_last[2] = pl.gy; h->an_last[3] = (int64_t)pl.lds; h->an_last[4] = o0; h->an_last[5] = o1;
+    h->an_launches++;
     const dim3 grid(pl.gx, pl.gy);
     if (pl.form == CTK_ANOM_RING)
         k_anom_ring<VT><<<grid, CTK_ANOM_THREADS, pl.lds, h->stream>>>(x, xbase, xlo, xhi, clim, group_dev, valid_dev, npix, smooth, o0, o1, pl.tile, out);
@@ -164,6 +167,7 @@ static int anom_seg_dev(ctk_handle *h, const VT *x_dev, int64_t T, int ny, int n
 {
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
+    h->an_launches = 0;
     const int64_t npix = (int64_t)ny * nx;
     const size_t esz = sizeof(VT), n = (size_t)T * (size_t)npix, cb = (size_t)ngroups * npix * esz;
     CTKCHK(ensure(h, h->an_out, n * esz));
@@ -233,6 +237,37 @@ extern "C" int ctk_debug_anom_form(ctk_handle *h, int64_t *form)
 {
     if (!h || !form) return ctk_set_error(CTK_E_INVALID, "null argument");
     *form = h->an_form;
+    return CTK_OK;
+}
+
+// test hook for the following launch_anom_seg on this handle: ctk_anom_plan's waves_wanted and grid_y_max (0: the rule's CTK_ANOM_WAVES and
+// 65535; grid_y_max above 65535 stays 65535), so that a small slab reaches the tile edges
+extern "C" int ctk_debug_set_anom(ctk_handle *h, int64_t waves_wanted, int64_t grid_y_max)
+{
+    if (!h || waves_wanted < 0 || grid_y_max < 0) return ctk_set_error(CTK_E_INVALID, "ctk_debug_set_anom: bad argument");
+    h->an_waves_dbg = waves_wanted;
+    h->an_gy_dbg = grid_y_max;
+    return CTK_OK;
+}
+
+// what ctk_anom_plan decides (host only: no handle, no GPU); waves_wanted / grid_y_max as ctk_debug_set_anom; out5 = {form, lds, tile, gx, gy}
+extern "C" int ctk_debug_anom_plan(int elem_bytes, int smooth, int64_t nt, int64_t npix, int64_t waves_wanted, int64_t grid_y_max, int64_t *out5)
+{
+    if (!out5 || (elem_bytes != 4 && elem_bytes != 8) || smooth < 1 || nt < 1 || npix < 1 || waves_wanted < 0 || grid_y_max < 0)
+        return ctk_set_error(CTK_E_INVALID, "ctk_debug_anom_plan: bad arguments");
+    const CtkAnomPlan p = ctk_anom_plan(elem_bytes, smooth, nt, npix, waves_wanted > 0 ? waves_wanted : CTK_ANOM_WAVES,
+                                        grid_y_max > 0 ? std::min<int64_t>(grid_y_max, 65535) : 65535);
+    out5[0] = p.form; out5[1] = (int64_t)p.lds; out5[2] = p.tile; out5[3] = p.gx; out5[4] = p.gy;
+    return CTK_OK;
+}
+
+// test hook: out8 = {form, tile, gx, gy, lds, o0, o1} of the last launch_anom_seg on this handle (form -1: none yet) and the number of
+// such launches the last ctk_anom_seg_* / ctk_anom_stream_* / ctk_anom_seg_resident call made
+extern "C" int ctk_debug_anom_launch(ctk_handle *h, int64_t *out8)
+{
+    if (!h || !out8) return ctk_set_error(CTK_E_INVALID, "null argument");
+    out8[0] = h->an_form; out8[1] = h->an_last[0]; out8[2] = h->an_last[1]; out8[3] = h->an_last[2]; out8[4] = h->an_last[3]; out8[5] = h->an_last[4];
+    out8[6] = h->an_last[5]; out8[7] = h->an_launches;
     return CTK_OK;
 }
 
@@ -320,6 +355,7 @@ static int anom_stream_impl(ctk_handle *h, StreamIO &io, int64_t T, int ny, int 
     CTKCHK(anom_seg_check(name, h, T, ny, nx, group, ngroups, window, smooth, starts, nseg));
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
+    h->an_launches = 0;
     const int64_t npix = (int64_t)ny * nx;
     const size_t plane = (size_t)npix * sizeof(VT), cb = (size_t)ngroups * plane, ng = (size_t)ngroups * (size_t)npix;
     io.esz = sizeof(VT);

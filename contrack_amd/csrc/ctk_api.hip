@@ -296,6 +296,9 @@ struct ctk_handle {
     DevBuf an_out, an_clim, an_raw, an_idx;
     DevBuf an_acc, an_valid;                       // ctk_anom_stream_*: float64 sums + int32 counts per (group, pixel); ctk_anom_seg_*: window-inside-segment per step
     int an_form = -1;                              // kernel form the last ctk_anom_seg_* / ctk_anom_stream_* call took (CtkAnomForm; -1: none yet)
+    int64_t an_waves_dbg = 0, an_gy_dbg = 0;       // ctk_debug_set_anom: waves_wanted / grid_y_max of ctk_anom_plan for the launches (0: the rule's)
+    int64_t an_last[6] = {0, 0, 0, 0, 0, 0};       // the last launch_anom_seg: tile, gx, gy, lds, o0, o1 ...
+    int64_t an_launches = 0;                       // ... and how many of them the last ctk_anom_seg_* / ctk_anom_stream_* call made
     int64_t an_T = -1; int an_ny = 0, an_nx = 0; bool an_f64 = false;
     uint64_t an_gen = 0;                           // bumped whenever the resident slab is written or dropped: WHICH slab is resident
     int64_t an_pct_n = -1;                         // an_raw holds the per-pixel quantiles of the last ctk_percentile_* call (-1: it does not)

@@ -512,19 +512,20 @@ struct CtkAnomPlan {
     int64_t tile;                 // output steps per workgroup
     unsigned gx, gy;
 };
-// nt output steps of a plane of npix pixels
-inline CtkAnomPlan ctk_anom_plan(int elem_bytes, int smooth, int64_t nt, int64_t npix)
+// nt output steps of a plane of npix pixels; waves_wanted: CTK_ANOM_WAVES, grid_y_max: 65535 -- or a test's values, which reach the
+// tile edges on small slabs (ctk_debug_set_anom)
+inline CtkAnomPlan ctk_anom_plan(int elem_bytes, int smooth, int64_t nt, int64_t npix, int64_t waves_wanted = CTK_ANOM_WAVES, int64_t grid_y_max = 65535)
 {
     CtkAnomPlan p = {};
     p.lds = (size_t)smooth * CTK_ANOM_THREADS * (size_t)elem_bytes;
     p.form = p.lds <= CTK_ANOM_RING_BYTES ? CTK_ANOM_RING : CTK_ANOM_PLAIN;
     if (p.form == CTK_ANOM_PLAIN) p.lds = 0;
     const int64_t waves = (npix + 63) / 64;
-    // the longest tile that still leaves CTK_ANOM_WAVES waves, at least 8 x the halo so that it stays below an eighth of the reads
-    int64_t tile = std::max<int64_t>(1, nt * waves / CTK_ANOM_WAVES);
+    // the longest tile that still leaves waves_wanted waves, at least 8 x the halo so that it stays below an eighth of the reads
+    int64_t tile = std::max<int64_t>(1, nt * waves / waves_wanted);
     tile = std::min<int64_t>(CTK_ANOM_TILE_MAX, std::max<int64_t>(tile, std::max<int64_t>(CTK_ANOM_TILE_MIN, 8 * (int64_t)(smooth - 1))));
     if (p.form == CTK_ANOM_PLAIN) tile = CTK_ANOM_TILE_MIN;
-    tile = std::max(tile, (nt + 65534) / 65535);                                       // gridDim.y <= 65535
+    tile = std::max(tile, (nt + grid_y_max - 1) / grid_y_max);                         // gridDim.y <= 65535
     p.tile = tile;
     p.gx = (unsigned)((npix + CTK_ANOM_THREADS - 1) / CTK_ANOM_THREADS);
     p.gy = (unsigned)std::max<int64_t>(1, (nt + tile - 1) / tile);

@@ -173,6 +173,17 @@ int ctk_debug_time_percentile_groups(ctk_handle *h, const float *x_dev, int64_t 
 /* test hook: the kernel form of the last ctk_anom_seg_* / ctk_anom_stream_* launch on this handle: 1 the LDS ring (k_anom_ring), 0 the
  * plain form (k_anom_plain), -1 none yet (ctk_anom_plan, csrc/ctk_forms.h) */
 int ctk_debug_anom_form(ctk_handle *h, int64_t *form);
+/* what ctk_anom_plan (csrc/ctk_forms.h) decides for nt output steps of a plane of npix pixels (host only: no handle, no GPU);
+ * waves_wanted / grid_y_max: 0 the rule's 16 384 and 65 535, or a test's values; out5 = { form, dynamic LDS in bytes, tile (output steps
+ * per workgroup), gridDim.x, gridDim.y } */
+int ctk_debug_anom_plan(int elem_bytes, int smooth, int64_t nt, int64_t npix, int64_t waves_wanted, int64_t grid_y_max, int64_t *out5);
+/* test hook for the following anomaly launches of ctk_anom_seg_* / ctk_anom_stream_* / ctk_anom_seg_resident on this handle: the same two
+ * values (0: the rule's; negative: refused; grid_y_max above 65 535 stays 65 535), so that a small slab reaches the tile edges */
+int ctk_debug_set_anom(ctk_handle *h, int64_t waves_wanted, int64_t grid_y_max);
+/* test hook: out8 = { form, tile, gridDim.x, gridDim.y, LDS bytes, o0, o1 } of the last anomaly launch on this handle (output steps
+ * [o0, o1); form -1: none yet), then the number of such launches the last of those calls made (a streamed chunk that completes no
+ * output step launches nothing) */
+int ctk_debug_anom_launch(ctk_handle *h, int64_t *out8);
 
 /* what ctk_pfield_plan (csrc/ctk_forms.h) decides for keys of `keybytes` (4 / 8) bytes, a longest pool of max_pool_steps timesteps,
  * ngroups and window: out4 = { form (0 direct, 1 ring), the ring form's cap in pool timesteps, pixels per workgroup, bytes of the ring

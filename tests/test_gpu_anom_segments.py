@@ -9,6 +9,8 @@ from contrack_amd import _native
 from contrack_amd.contrack import anomalies_numpy
 from oracle import anom_port
 
+from anom_forms import expected, same                # (the yardstick, shared with tests/test_gpu_anom_seg_forms.py)
+
 pytestmark = pytest.mark.gpu
 
 RING, PLAIN = 1, 0                 # Tracker.debug_anom_form: CtkAnomForm of csrc/ctk_forms.h
@@ -33,17 +35,6 @@ def _field(rng, T, ny, nx, dtype, nans):          # (the recipe of tests/test_gp
 def _groups(T, ngroups=12, run=3):
     """ids that change every `run` steps, from an offset that puts the boundaries off the round numbers the tests break at"""
     return (((np.arange(T) + 17) // run) % ngroups).astype(np.int32), ngroups
-
-
-def expected(x, group, G, window, smooth, starts, clim=None):
-    clim = anom_port.calc_clim(x, group, G, window) if clim is None else clim
-    edges = list(starts) + [x.shape[0]]
-    parts = [anom_port.calc_anom(x[s:e], group[s:e], G, window, smooth, clim=clim) for s, e in zip(edges[:-1], edges[1:])]
-    return np.concatenate(parts), clim.astype(x.dtype)
-
-
-def same(a, b):
-    return a.dtype == b.dtype and np.array_equal(a, b, equal_nan=True)
 
 
 # ---- 1. one segment is ctk_anom_*, bit for bit, in both kernel forms ---------------------------------------------------------
