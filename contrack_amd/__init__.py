@@ -6,6 +6,7 @@ entry underneath it, `frequency_numpy` the blocking frequency (README.rst:159-16
 `composite_numpy` / `composite_mean` the mean of a field over the flagged time steps,
 `anomalies_numpy` the climatology and anomalies that produce its input (over time segments, optionally streamed),
 `percentile_field_numpy` the per-grid-point percentile threshold field per group of timesteps,
+`std_field_numpy` the per-grid-point standard-deviation threshold field per group of timesteps,
 `level_mean_numpy` the vertical mean over a pressure band that comes before them (weights: `level_weights`).
 Compute goes through hand-written HIP kernels behind a ctypes C ABI
 (include/contrack_hip.h); there is no CPU fallback.
@@ -14,7 +15,7 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name in ("contrack", "track_numpy", "frequency_numpy", "composite_numpy", "composite_mean", "anomalies_numpy", "percentile_field_numpy", "level_mean_numpy", "level_weights", "row_weights", "prepare_thresholds"):
+    if name in ("contrack", "track_numpy", "frequency_numpy", "composite_numpy", "composite_mean", "anomalies_numpy", "percentile_field_numpy", "std_field_numpy", "level_mean_numpy", "level_weights", "row_weights", "prepare_thresholds"):
         import importlib
         _m = importlib.import_module(".contrack", __name__)     # (`from . import contrack` would ask __getattr__ for 'contrack' first)
         return getattr(_m, name)

@@ -41,6 +41,7 @@ EXPORTS = [
     "ctk_frequency_dev", "ctk_frequency", "ctk_frequency_cb", "ctk_debug_set_freq", "ctk_debug_time_freq",
     "ctk_percentile_groups_f32", "ctk_percentile_groups_f64", "ctk_debug_percentile_groups_sweeps", "ctk_debug_time_percentile_groups",
     "ctk_percentile_field_f32", "ctk_percentile_field_f64", "ctk_debug_percentile_field_plan", "ctk_debug_percentile_field_form", "ctk_debug_time_percentile_field",
+    "ctk_std_field_f32", "ctk_std_field_f64", "ctk_debug_std_field_plan", "ctk_debug_std_field_form", "ctk_debug_time_std_field",
     "ctk_anom_seg_f32", "ctk_anom_seg_f64", "ctk_anom_stream_f32", "ctk_anom_stream_f64", "ctk_anom_stream_cb", "ctk_debug_anom_form", "ctk_debug_anom_plan", "ctk_debug_set_anom", "ctk_debug_anom_launch",
     "ctk_level_mean_f32", "ctk_level_mean_f64", "ctk_level_mean_f32_dev", "ctk_level_mean_f64_dev", "ctk_level_mean_stream_f32", "ctk_level_mean_stream_f64",
     "ctk_level_mean_stream_cb", "ctk_resident_level_mean", "ctk_resident_level_mean_generation", "ctk_anom_seg_resident", "ctk_debug_level_plan", "ctk_debug_level_form", "ctk_debug_time_level_mean", "ctk_debug_set_level",
@@ -92,6 +93,15 @@ def debug_percentile_field_plan(keybytes, max_pool_steps, ngroups, window):
     v = np.zeros(4, dtype=np.int64)
     check(lib().ctk_debug_percentile_field_plan(int(keybytes), int(max_pool_steps), int(ngroups), int(window), v.ctypes.data))
     return dict(form=int(v[0]), cap=int(v[1]), tile=int(v[2]), ring_bytes=int(v[3]))
+
+
+def debug_std_field_plan(ngroups, window=1, skipna=True):
+    """ctk_debug_std_field_plan: what ctk_std_plan (csrc/ctk_forms.h) decides, as a dict (tile: pixels per workgroup, 0 where even 8 do
+    not fit; planes accumulated; dynamic LDS bytes; max_groups: the most groups a window below the group count may have); no handle,
+    no GPU"""
+    v = np.zeros(4, dtype=np.int64)
+    check(lib().ctk_debug_std_field_plan(int(ngroups), int(window), int(bool(skipna)), v.ctypes.data))
+    return dict(tile=int(v[0]), planes=int(v[1]), lds_bytes=int(v[2]), max_groups=int(v[3]))
 
 
 def debug_lifecycle_plan(T, ny, nx, f64=False, flag_align=0, field_align=0):
@@ -293,6 +303,11 @@ def lib():
     L.ctk_debug_percentile_field_plan.argtypes = [i32, i64, i32, i32, p]
     L.ctk_debug_percentile_field_form.argtypes = [p, p]
     L.ctk_debug_time_percentile_field.argtypes = [p, p, i32, i64, i32, i32, i32, i32, p, i32, i32, dbl, i32, p, p, p]
+    for name in ("ctk_std_field_f32", "ctk_std_field_f64"):
+        getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, i32, p, i32, i32, i32, i32, p, p, p]
+    L.ctk_debug_std_field_plan.argtypes = [i32, i32, i32, p]
+    L.ctk_debug_std_field_form.argtypes = [p, p]
+    L.ctk_debug_time_std_field.argtypes = [p, p, i32, i64, i32, i32, i32, i32, p, i32, i32, i32, i32, i32, p, p]
     L.ctk_comm_unique_id.argtypes = [p]
     L.ctk_comm_init_rccl.argtypes = [p, p, i32, i32, pp]
     L.ctk_comm_group_create.argtypes = [i32, pp]
@@ -1402,6 +1417,38 @@ class Tracker:
         check(lib().ctk_debug_time_percentile_field(self._h, x_dev, int(bool(f64)), int(T), int(ny), int(nx), int(y0), int(y1), group.ctypes.data,
                                                     int(ngroups), int(window), float(q), int(reps), _ptr(a), _ptr(b), ms))
         return a, b, float(ms[0]), float(ms[1]), float(ms[2]), int(ms[3])
+
+    def std_field(self, x, y0, y1, group, ngroups, window=1, ddof=0, skipna=True, want_mean=False, want_n=False):
+        """per group g and grid point of rows [y0, y1) the standard deviation over every timestep whose group lies in the centred,
+        circular window of `window` groups around g, taken in time order: the two-pass float64 loop of ctk_std_field_*
+        (include/contrack_hip.h; np.nanstd / np.std of the pool with `ddof` on planes of two or more points; NaN where
+        count - ddof <= 0); x (T, ny, nx) float32 / float64, or None: the resident anomaly slab.  group: T ids in [0, ngroups).
+        Returns float64 (ngroups, y1 - y0, nx) -- with want_mean / want_n a tuple (std, mean float64 or None, count uint32 or None)."""
+        ptr, T, ny, nx, f64, _keep = self._slab_or_resident(x)
+        group = _group_ids(group, T)
+        shape = (max(int(ngroups), 0), max(int(y1) - int(y0), 0), nx)
+        out = np.empty(shape, dtype=np.float64)
+        mean = np.empty(shape, dtype=np.float64) if want_mean else None
+        n = np.empty(shape, dtype=np.uint32) if want_n else None
+        fn = lib().ctk_std_field_f64 if f64 else lib().ctk_std_field_f32
+        check(fn(self._h, ptr, T, ny, nx, int(y0), int(y1), group.ctypes.data, int(ngroups), int(window), int(ddof), int(bool(skipna)),
+                 out.ctypes.data, _ptr(mean), _ptr(n)))
+        return (out, mean, n) if want_mean or want_n else out
+
+    def debug_std_field_form(self):
+        """test hook: (pixels per workgroup, longest pool in timesteps) of the last std_field() call; tile -1: none yet"""
+        v = np.zeros(2, dtype=np.int64)
+        check(lib().ctk_debug_std_field_form(self._h, v.ctypes.data))
+        return int(v[0]), int(v[1])
+
+    def time_std_field(self, x_dev, T, ny, nx, y0, y1, group, ngroups, window=1, ddof=0, skipna=True, reps=3, f64=False, want_field=True):
+        """measurement on a slab in device memory (tools/std_probe.py): (the field or None, ms per call, pixels per workgroup)"""
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        a = np.empty((int(ngroups), int(y1) - int(y0), int(nx)), dtype=np.float64) if want_field else None
+        ms = (C.c_double * 2)()
+        check(lib().ctk_debug_time_std_field(self._h, x_dev, int(bool(f64)), int(T), int(ny), int(nx), int(y0), int(y1), group.ctypes.data,
+                                             int(ngroups), int(window), int(ddof), int(bool(skipna)), int(reps), _ptr(a), ms))
+        return a, float(ms[0]), int(ms[1])
 
     def debug_percentile_values(self, n):
         """test hook: the n per-grid-point quantiles (band, row-major) of the last percentile() call"""

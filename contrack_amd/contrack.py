@@ -447,6 +447,43 @@ def percentile_field_numpy(anom, rows, group, q, window=1, device=None):
     return _tracker(device).percentile_field(anom, y0, y1, ids, G, q, window)
 
 
+def std_field_numpy(anom, rows, group, window=1, ddof=0, skipna=True, device=None):
+    """the array-level twin of contrack.std_field: per group g (one id in [0, G) per timestep, G = max(group) + 1, any order in time;
+    None: one group) and grid point of rows[0] <= y < rows[1] the standard deviation over every timestep whose group lies in the
+    centred window of `window` groups around g, circular over the groups, the pool taken in time order:
+        np.nanstd(anom[np.isin(group, [(g + d) % G for d in range(-(window // 2), (window - 1) // 2 + 1)]), rows[0]:rows[1]]
+                  .astype(np.float64), axis=0, ddof=ddof)                  (skipna False: np.std)
+    bit for bit on bands of two or more points (ctk_std_field_*, include/contrack_hip.h: the two-pass float64 loop is the statement;
+    NaN where count - ddof <= 0).  Returns float64 (G, rows[1] - rows[0], nx)."""
+    anom = np.asarray(anom)
+    if anom.ndim != 3:
+        raise ValueError("anom must be (time, lat, lon)")
+    y0, y1 = (int(v) for v in rows)
+    if not 0 <= y0 < y1 <= anom.shape[1]:
+        raise ValueError("rows {} are not rows of a grid of {}".format((y0, y1), anom.shape[1]))
+    ids, G = _native._groups(group, anom.shape[0])
+    if ids is None:
+        ids, G = np.zeros(anom.shape[0], dtype=np.int32), 1
+    _check_std_args(window, ddof, G, skipna)
+    if anom.dtype.kind != "f":
+        anom = anom.astype(np.float64)
+    return _tracker(device).std_field(anom, y0, y1, ids, G, int(window), int(ddof), bool(skipna))
+
+
+def _check_std_args(window, ddof, ngroups=None, skipna=True):
+    """what the std entries refuse before any device call: a window or ddof that is no whole number in range, more groups than the
+    kernel's accumulators hold (ctk_std_plan, csrc/ctk_forms.h -- asked of the library on the host, no GPU)"""
+    if int(window) != window or int(window) < 1:
+        raise ValueError("window = {} (a whole number of groups, at least 1)".format(window))
+    if int(ddof) != ddof or int(ddof) < 0:
+        raise ValueError("ddof = {} (a whole number, at least 0)".format(ddof))
+    if ngroups is not None:
+        plan = _native.debug_std_field_plan(int(ngroups), int(window), bool(skipna))
+        if plan["tile"] == 0:
+            raise ValueError("{} groups with a window of {}: at most {} groups fit {}".format(
+                ngroups, window, plan["max_groups"], "with counts (skipna)" if skipna else "without counts"))
+
+
 def _check_percentile_args(q, window):
     if not (0.0 <= float(q) <= 1.0):
         raise ValueError("q = {} is not in [0, 1]".format(q))
@@ -1248,6 +1285,78 @@ class contrack(object):
             coords[name] = np.asarray(self.ds[name].data)
         return self._wrap(da, vals, (groupby, self._latitude_name, self._longitude_name), coords, attrs,
                           name='{}_q{:g}_field'.format(variable, float(q) * 100))
+
+    def _std_band(self, variable, groupby, window, lat_bounds, ddof, skipna, segments):
+        """(std planes of the band float64 (G, rows, nx), (y0, y1), the G group values or None, the (steps, lat, lon) shape, the band's
+        bounds) for std_field and std_threshold: the arguments checked, the slab chosen (host or resident) as the percentile entries do"""
+        _check_std_args(window, ddof)
+        self._ensure_set_up()
+        slab, M = self._slab_pooled(variable, segments)
+        lat = np.asarray(self.ds[self._latitude_name].data, dtype=np.float64)
+        bounds = (lat.min(), lat.max()) if lat_bounds is None else lat_bounds
+        rows = np.nonzero((lat >= min(bounds)) & (lat <= max(bounds)))[0]
+        if len(rows) == 0 or not np.array_equal(rows, np.arange(rows[0], rows[-1] + 1)):
+            raise ValueError("latitude band {} selects no contiguous rows".format(lat_bounds))
+        if slab.dtype.kind != "f":
+            slab = slab.astype(np.float64)
+        if groupby is None:
+            ids, uniq = np.zeros(self._dim_size(self._time_name), dtype=np.int32), None
+        else:
+            ids, uniq = self._group_ids(groupby)
+        G = 1 if uniq is None else len(uniq)
+        _check_std_args(window, ddof, G, skipna)
+        if M > 1:
+            ids = np.tile(ids, M)
+        resident = segments is None and self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, slab.shape, slab.dtype != np.float32)
+        y0, y1 = int(rows[0]), int(rows[-1]) + 1
+        band = _tracker().std_field(None if resident else slab, y0, y1, ids, G, int(window), int(ddof), bool(skipna))
+        return band, (y0, y1), uniq, slab.shape, (float(min(bounds)), float(max(bounds)))
+
+    def _std_attrs(self, variable, long_name, k, ddof, window, bounds, groupby):
+        attrs = {'long_name': long_name.format(variable), 'k': float(k), 'ddof': int(ddof), 'window': int(window), 'lat_bounds': bounds,
+                 'history': ' '.join(['Calculated from {} with input attributes:', 'k = {},', 'ddof = {},', 'latitude band = {},', 'groupby = {},',
+                                      'window = {} groups.']).format(variable, k, ddof, bounds, groupby, window)}
+        if 'units' in getattr(self.ds[variable], "attrs", {}):
+            attrs['units'] = self.ds[variable].attrs['units']
+        return attrs
+
+    def std_field(self, variable='anom', k=1.0, groupby='dayofyear', window=1, lat_bounds=None, ddof=0, skipna=True, segments=None):
+        """the "k standard deviations of the local anomaly" threshold (the std_dev half of the reference's open item,
+        contrack.py:9-10): per value of time.<groupby> and per grid point k times the standard deviation over every timestep whose
+        group lies in the centred window of `window` groups around it (circular: 1 January sees late December), in time order --
+        block[variable].groupby('time.' + groupby).std('time') with a window, as np.nanstd (skipna False: np.std) with `ddof` in
+        float64 gives it, evaluated exactly on the GPU (ctk_std_field_*, include/contrack_hip.h); the multiplication by k is numpy's,
+        on the result; k may be negative (gorl='<=').  Returns a labelled array over (groupby, latitude, longitude) on the whole grid
+        (the group values present, ascending); rows outside lat_bounds (None: every row) are NaN and are never flagged.  With
+        groupby='dayofyear' it can be given to run_contrack(threshold=...) as it is.  groupby=None: one pool, an array over
+        (latitude, longitude), whose values (np.asarray(field.data)) run_contrack(threshold=...) broadcasts over time (labelled, it
+        asks for a 'dayofyear' dimension, as xarray's grouped compare does).
+        segments (extension): the name of a member dimension of a 4-D variable; the members are pooled as in percentile_threshold,
+        in the time order of the flattened (member * time, lat, lon) slab."""
+        band, (y0, y1), uniq, shape, bounds = self._std_band(variable, groupby, window, lat_bounds, ddof, skipna, segments)
+        vals = np.full((band.shape[0],) + tuple(shape[1:]), np.nan)
+        vals[:, y0:y1] = float(k) * band
+        attrs = self._std_attrs(variable, '{} standard-deviation threshold field', k, ddof, window, bounds, groupby)
+        coords = {} if groupby is None else {groupby: uniq}
+        for name in (self._latitude_name, self._longitude_name):
+            coords[name] = np.asarray(self.ds[name].data)
+        dims = (self._latitude_name, self._longitude_name)
+        return self._wrap(self.ds[variable], vals[0] if groupby is None else vals, dims if groupby is None else (groupby,) + dims, coords, attrs,
+                          name='{}_std_field'.format(variable))
+
+    def std_threshold(self, variable='anom', k=1.0, lat_bounds=(50, 80), groupby=None, window=1, ddof=0, skipna=True, segments=None):
+        """the scalar recipe in the shape of the reference's README (README.rst:150-151): k times
+        block[variable].sel(latitude=band).std(dim='time').mean() -- the mean over the latitude band (np.mean on the host, float64) of
+        the per-grid-point standard deviation over time that std_field computes on the GPU.  Returns a float; with groupby
+        ('dayofyear', 'month', ...) a 1-D labelled array over `groupby` (the values present, ascending) of k * the band mean of every
+        group's plane, pooled over the centred window of `window` groups -- with groupby='dayofyear' it can be given to
+        run_contrack(threshold=...) as it is."""
+        band, _rows, uniq, _shape, bounds = self._std_band(variable, groupby, window, lat_bounds, ddof, skipna, segments)
+        vals = np.array([float(k) * np.mean(plane) for plane in band])
+        if groupby is None:
+            return float(vals[0])
+        attrs = self._std_attrs(variable, '{} standard-deviation threshold', k, ddof, window, bounds, groupby)
+        return self._wrap(self.ds[variable], vals, (groupby,), {groupby: uniq}, attrs, name='{}_std'.format(variable))
 
     # ---- the hot path (contrack.py:583-796) -----------------------------------------------------------------
     def _dayofyear(self):

@@ -385,6 +385,9 @@ struct ctk_handle {
     // percentile field (ctk_pfield.hip): the G planes of the last call; pool starts, pool lengths, the step list; its form and longest pool
     DevBuf pf_out, pf_idx;
     int pf_form = -1; int64_t pf_max_pool = 0;
+    // standard-deviation field (ctk_std.hip): the planes of the last call (std, mean, counts); group ids and pool lengths; its tile and longest pool
+    DevBuf sf_out, sf_idx;
+    int sf_tile = -1; int64_t sf_max_pool = 0;
     int64_t fq_slice_dbg = 0; int fq_nt = -1;
     int w_minlsb = 0;                            // lowest set bit over the integer row weights
     int64_t last_alive = 0, last_nlab = 0;
@@ -605,7 +608,7 @@ extern "C" void ctk_destroy(ctk_handle *h)
                       &h->lc_rows, &h->lc_cnt, &h->lc_wlo, &h->lc_whi, &h->lc_w, &h->rv_dmap, &h->rv_dorig, &h->rv_dbox, &h->rv_inex, &h->rv_touch, &h->io_in, &h->io_out,
                       &h->sh_mask_next, &h->sh_send, &h->sh_recv, &h->sh_prev, &h->sh_elist, &h->sh_ovr_slot, &h->sh_ovr_val,
                       &h->sh_amb_list, &h->sh_counts, &h->sh_cl_shared, &h->sh_cl_sent, &h->chunk_vals, &h->lc_work, &h->lc_ovf, &h->lc_ekeys, &h->lc_offs, &h->lc_sw, &h->lc_sp, &h->lc_out, &h->lc_cross, &h->lc_gtab, &h->lc_occ, &h->lc_cp, &h->an_out, &h->an_clim, &h->an_raw, &h->an_idx, &h->an_acc, &h->an_valid, &h->lv_out, &h->lv_tab, &h->sd_parent, &h->sd_tmin, &h->sd_tmax, &h->sd_root, &h->sd_nops, &h->sd_lbox, &h->rv_pstate, &h->ci_bsum, &h->scan_bsum,
-                      &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order, &h->fq_counts, &h->fq_group, &h->cp_sum, &h->cp_n, &h->seg_edge, &h->pc_hist, &h->pc_buf, &h->pf_out, &h->pf_idx};
+                      &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order, &h->fq_counts, &h->fq_group, &h->cp_sum, &h->cp_n, &h->seg_edge, &h->pc_hist, &h->pc_buf, &h->pf_out, &h->pf_idx, &h->sf_out, &h->sf_idx};
     for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (h->h_blob) (void)hipHostFree(h->h_blob);
     if (h->h_small) (void)hipHostFree(h->h_small);
@@ -3866,6 +3869,7 @@ extern "C" int ctk_lifecycle_rows(ctk_handle *h, ctk_life_row *rows, int64_t cap
 #include "ctk_life_stream.hip"
 #include "ctk_pctl.hip"
 #include "ctk_pfield.hip"
+#include "ctk_std.hip"
 #include "ctk_level.hip"
 #include "ctk_composite.hip"
 

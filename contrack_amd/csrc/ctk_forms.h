@@ -457,6 +457,40 @@ inline CtkPfieldPlan ctk_pfield_plan(int keybytes, int64_t max_pool_steps, int G
 }
 
 // ------------------------------------------------------------------------------------------------
+// standard-deviation field per group and grid point (ctk_std.hip): k_std_field keeps the accumulators of ALL planes of its pixel tile
+// in LDS -- per (plane, pixel) a float64 sum that becomes the mean in place, a float64 sum of squares and, when NaNs are skipped, a
+// uint32 count -- beside CTK_STD_STAGE staged timesteps of the tile (reserved at 8 bytes per value for either dtype)
+// ------------------------------------------------------------------------------------------------
+#define CTK_STD_LDS_BYTES 163840      // what a workgroup may declare on gfx950
+#define CTK_STD_THREADS 512           // owners per pixel = 512 / pixel tile: owner s of a pixel holds the planes h with h % owners == s
+#define CTK_STD_STAGE 64              // timesteps staged per round
+#define CTK_STD_MIN_TILE 8            // the pixel tile is 32, 16 or 8 -- the widest whose accumulators fit
+#define CTK_STD_MAX_TILE 32
+constexpr int64_t ctk_std_acc_bytes(int skipna) { return 16 + (skipna ? 4 : 0); }
+constexpr int64_t ctk_std_stage_bytes(int tile) { return (int64_t)CTK_STD_STAGE * tile * 8; }
+// planes a workgroup of `tile` pixels holds
+constexpr int64_t ctk_std_planes_max(int tile, int skipna) { return (CTK_STD_LDS_BYTES - ctk_std_stage_bytes(tile)) / ((int64_t)tile * ctk_std_acc_bytes(skipna)); }
+struct CtkStdPlan {
+    int tile;                     // pixels per workgroup; 0: even CTK_STD_MIN_TILE pixels do not fit
+    int planes;                   // planes accumulated: G, or 1 when the window covers every group (the plane is replicated)
+    int64_t lds_bytes;            // dynamic LDS of the launch (0 with tile 0)
+    int64_t max_groups;           // the most groups a window below the group count may have: 998 with counts, 1 248 without
+};
+inline CtkStdPlan ctk_std_plan(int G, int W, int skipna)
+{
+    CtkStdPlan p = {};
+    p.planes = W >= G ? 1 : G;
+    p.max_groups = ctk_std_planes_max(CTK_STD_MIN_TILE, skipna);
+    for (int tile = CTK_STD_MAX_TILE; tile >= CTK_STD_MIN_TILE; tile /= 2)
+        if (p.planes <= ctk_std_planes_max(tile, skipna)) {
+            p.tile = tile;
+            p.lds_bytes = (int64_t)p.planes * tile * ctk_std_acc_bytes(skipna) + ctk_std_stage_bytes(tile);
+            break;
+        }
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------
 // run_lifecycle reductions (ctk_lifecycle.hip): the strip form k_life_seam / k_life_strips<VT, VEC> / k_life_finish, and k_lifecycle for
 // the time steps the strip form gives up.  (CTK_LIFE_SW and CTK_LIFE_WAVES restate LB_SW and LB_THREADS / 64 of ctk_lifecycle.hip;
 // ctk_api.hip asserts that they agree.)

@@ -527,6 +527,31 @@ int ctk_percentile_field_f32(ctk_handle *h, const float *x, int64_t T, int ny, i
                              double q, double *out /* ngroups * (y1 - y0) * nx */);
 int ctk_percentile_field_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group, int ngroups, int window,
                              double q, double *out /* ngroups * (y1 - y0) * nx */);
+/* contrack.py:9-10 ("take 90th percentile or std_dev from anom field for threshold"), the std_dev half: the temporal standard deviation
+ * AT EACH GRID POINT of rows [y0, y1), per group, over the pool of ctk_percentile_field_* TAKEN IN TIME ORDER,
+ *   pool(g, y, x') = ( x[t, y, x'] : t rising, group[t] in { (g + d) mod ngroups : -(window / 2) <= d <= (window - 1) / 2 } )
+ * (x[np.isin(group, members)]: window >= ngroups pools every timestep for every group -- one plane is computed and replicated), as
+ * this two-pass loop in float64, which is the statement:
+ *   s = 0; c = 0;  for v in pool:  (skipna and v is NaN) ? v = 0 : c += 1;   s = s + v
+ *   m = s / (double)c
+ *   q = 0;         for v in pool:  skip if (skipna and v is NaN);  d = v - m;  q = q + d * d       (product and sum rounded separately)
+ *   out_std = c - ddof > 0 ? sqrt(q / (double)(c - ddof)) : NaN;   out_mean = m;   out_n = c
+ * On C-contiguous (n, ny, nx) pools of two or more grid points these are the bits of np.nanstd(pool, axis=0, ddof=ddof) (skipna) and
+ * np.std(pool.astype(np.float64), axis=0, ddof=ddof) (numpy 2.2).  A ONE-point plane is different: numpy reduces it pairwise and the
+ * loop does not match it -- the loop is what this entry computes.  One NaN rule for both modes, np.nanstd's: c - ddof <= 0 gives NaN
+ * (plain np.std gives inf there when q > 0); an empty or all-NaN pool gives NaN in out_std and out_mean.  Infinities need no rule:
+ * inf - inf makes the NaN numpy makes.  x = NULL: the resident anomaly slab (shape and dtype must match).  out_mean / out_n may be
+ * NULL.  One kernel (csrc/ctk_std.hip) holds the accumulators of every group for 32, 16 or 8 grid points in LDS (ctk_std_plan,
+ * csrc/ctk_forms.h) and gives each ONE writing thread, so each sees its values in time order; the slab is read twice.  Device memory:
+ * the ngroups planes asked for (8 + 8 + 4 bytes per value), T + ngroups ints.  CTK_E_INVALID: bad arguments (checked before any device
+ * call), ddof < 0, T >= 2^31 (counts are uint32), a window below ngroups with more than 998 groups (skipna) or 1 248 groups (without):
+ * the accumulators of 8 grid points no longer fit in LDS and there is no other form. */
+int ctk_std_field_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group, int ngroups, int window,
+                      int ddof, int skipna, double *out_std /* ngroups * (y1 - y0) * nx */, double *out_mean /* the same, or NULL */,
+                      uint32_t *out_n /* the same, or NULL */);
+int ctk_std_field_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group, int ngroups, int window,
+                      int ddof, int skipna, double *out_std /* ngroups * (y1 - y0) * nx */, double *out_mean /* the same, or NULL */,
+                      uint32_t *out_n /* the same, or NULL */);
 
 /* ---- the vertical mean over a pressure band (README.rst:235-240: "The PV fields are vertically averaged between 500-150 hPa") ----
  * The first step of the README's third recipe, the producer of the slab ctk_anom_* works on.  The reference has no function for it;

@@ -198,6 +198,18 @@ int ctk_debug_percentile_field_form(ctk_handle *h, int64_t *out2);
 int ctk_debug_time_percentile_field(ctk_handle *h, const void *x_dev, int is_f64, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group,
                                     int ngroups, int window, double q, int reps, double *out, double *out_direct, double *ms4);
 
+/* what ctk_std_plan (csrc/ctk_forms.h) decides for ngroups, window and skipna: out4 = { pixels per workgroup (0: the accumulators of
+ * even 8 pixels do not fit -- ctk_std_field_* refuses the call), planes accumulated (1 when window >= ngroups), dynamic LDS of the
+ * launch in bytes, the most groups a window below the group count may have }.  Host only: no handle, no GPU. */
+int ctk_debug_std_field_plan(int ngroups, int window, int skipna, int64_t *out4);
+/* test hook: out2 = { pixels per workgroup of the last ctk_std_field_* call on this handle (-1: none yet), its longest pool in timesteps } */
+int ctk_debug_std_field_form(ctk_handle *h, int64_t *out2);
+/* measurement (tools/std_probe.py) on a slab in device memory (is_f64 != 0: float64): ms2 = { ctk_std_field's device work per call
+ * (best of reps, host clock: upload of the ids, every kernel, synchronisation; the download of the field is outside), pixels per
+ * workgroup }; out_std (may be NULL): the field, ngroups * (y1 - y0) * nx */
+int ctk_debug_time_std_field(ctk_handle *h, const void *x_dev, int is_f64, int64_t T, int ny, int nx, int y0, int y1, const int32_t *group,
+                             int ngroups, int window, int ddof, int skipna, int reps, double *out_std, double *ms2);
+
 /* what ctk_life_plan (csrc/ctk_forms.h) decides for a ctk_lifecycle_* call over T time steps of (ny, nx) planes, float64 field if f64,
  * whose flag / field slabs start flag_align / field_align bytes past a 32-byte boundary: out5 = { rows per wave of k_life_strips,
  * strips per row, workgroups per strip, 1 if the vector form k_life_strips<VT, true> runs, seam-crossing ids one pass of k_lifecycle
