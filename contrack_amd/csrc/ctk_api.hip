@@ -1387,7 +1387,15 @@ static int label2d_rowcount(ctk_handle *h, Label2dCall &c)
     c.scan_stamp = (uint32_t)(h->pass_no & 0x7fffffffu) | 0x80000000u;
     Timer tm(h, CTK_KI_ROWCOUNT);
     const int rc_threads = ctk_rowcount_threads(T, c.ny, c.W);
-    if (T > 0) k_rowcount<<<(int)T, rc_threads, 0, h->stream>>>(P<uint64_t>(h->mask), c.ny, c.W, P<uint16_t>(h->wstart), P<uint32_t>(h->rowstart), P<uint32_t>(h->tcount));
+    if (T > 0) {
+        auto *rowcount = k_rowcount<8>;
+        switch (ctk_rowcount_groups(rc_threads, c.ny, c.W)) {
+        case 4: rowcount = k_rowcount<4>; break;
+        case 6: rowcount = k_rowcount<6>; break;
+        default: break;
+        }
+        rowcount<<<(int)T, rc_threads, 0, h->stream>>>(P<uint64_t>(h->mask), c.ny, c.W, P<uint16_t>(h->wstart), P<uint32_t>(h->rowstart), P<uint32_t>(h->tcount));
+    }
     c.rc_launched = T > 0 ? rc_threads : 0;
     CTKCHK(launch_scan_u32(h, P<uint32_t>(h->tcount), T, P<uint32_t>(h->run_base), h->h_mail1, c.scan_stamp));
     HIPCHK(hipGetLastError());

@@ -80,6 +80,16 @@ inline int ctk_rowcount_threads(int64_t T, int ny, int W)
 {
     return (W <= 64 && ny <= RC_ROWS && ny > 256 && T <= 2048) ? 512 : ((T > 65536 && (int64_t)ny * W <= 2048) ? 128 : 256);
 }
+// row groups k_rowcount's first form keeps in flight (its instance k_rowcount<RCU>): as many as the plane needs in ONE step of its waves,
+// of 4 / 6 / 8 -- 181 x 360 with 256 threads: ten rows a wave and group, five groups, RCU = 6, 60 VGPRs instead of the 73 of RCU = 8:
+// eight workgroups per CU, what the kernel's SGPR limit was set for, instead of six; k_rowcount 14.3 -> 12.1 us at 2707 x 181 x 360 (NOTES).
+// (The other forms do not use it.)
+inline int ctk_rowcount_groups(int threads, int ny, int W)
+{
+    if (W > 64) return 8;
+    const int per_group = (threads / 64) * (64 / W), need = (ny + per_group - 1) / per_group;
+    return need <= 4 ? 4 : need <= 6 ? 6 : 8;
+}
 
 // ------------------------------------------------------------------------------------------------
 // 2-D labelling.  The variants take disjoint sets of timesteps (by run count; nruns == 0 goes to the small one).
@@ -161,7 +171,10 @@ inline CtkLabelPlan ctk_label_plan(int64_t T, int ny, const CtkLabelShape &sh, u
 // many small planes (throughput regime): two waves per plane, ten workgroups per CU at 101 VGPRs -- 438 000 x 192 x 288: 3.95 -> 3.50 ms
 // (eight words per thread in one step: 169 VGPRs, 5.5 ms)
 // (small planes in long shards: room for five waves per SIMD -- 96 VGPRs, 14 of the 105 in scratch -- 3.49 -> 3.05 ms at 438 000 x 192 x 288;
-// at 2707 x 181 x 360, one round of latency chains, the same costs <5, 256> ten of its 36 us: only here)
+// at 2707 x 181 x 360 the same costs <5, 256> ten of its 36 us: only here.  <5, 256> itself is NOT one round there: 121 VGPRs hold four
+// workgroups on a CU, 1024 planes of the 2707 at a time -- 2.6 rounds of about 11 us behind a 2.5 us launch.  Six workgroups per CU
+// -- 79 VGPRs, by handing the words with common pixels to the lanes of their wave -- were built and measured slower, 40.4 us: NOTES,
+// "k_overlap: wave-level hand-over"; tools/kernel_resources.py prints what every instance takes)
 inline int ctk_overlap_form(int64_t T, int ny, int W)
 {
     const int nwords = ny * W, per = (nwords + 255) / 256;                             // words per thread if one step is to cover all

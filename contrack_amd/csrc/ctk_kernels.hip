@@ -519,6 +519,7 @@ __global__ __launch_bounds__(256) void k_thr_field_prep(const double *__restrict
 //   wstart[row][w] = run starts in words < w of the row      rowstart[t][y] = first run of row y
 //   tcount[t]      = runs of the timestep
 // ------------------------------------------------------------------------------------------------
+template <int RCU /* row groups the first form keeps in flight: ctk_rowcount_groups (ctk_forms.h) */>
 __global__ __launch_bounds__(1024) CTK_SGPR_8WAVES void k_rowcount(const uint64_t *__restrict__ mask, int ny, int W, uint16_t *__restrict__ wstart,
                                                   uint32_t *__restrict__ rowstart, uint32_t *__restrict__ tcount)
 {
@@ -532,7 +533,6 @@ __global__ __launch_bounds__(1024) CTK_SGPR_8WAVES void k_rowcount(const uint64_
         // form below walks the rows 256 / W at a time with a block scan -- two barriers -- per step: a chain of 65 of them for a
         // 721 x 1440 plane, 68 us; 0.8 ms on the 14 600-step slab.)
         __shared__ uint32_t rowtot[RC_ROWS];
-        constexpr int RCU = 8;
         const int lane = tid & 63, wv = tid >> 6;
         const int rpw = 64 / W;                                    // rows per wave step
         const int seg = lane / W, wl = lane - seg * W;             // row of the step and word of the row this lane holds
@@ -1348,8 +1348,11 @@ __global__ __launch_bounds__(THREADS, WPE) void k_overlap(std::conditional_t<SEG
     // One thread per mask word, OVB words per thread and step.  The work on a word is a chain of dependent loads (the two mask
     // words -> neighbours, run prefixes, row starts, weights -> the two runs' components); written word by word that is three
     // round trips to L2 per word, most of this kernel's time.  Here every load of a level is issued for all OVB words before the
-    // first is used: three round trips per OVB words.  (Words without common pixels -- nine of ten -- load their tables in vain:
-    // L2 hits next to data that is read anyway.)
+    // first is used: three round trips per OVB words.  (Words without common pixels load their tables in vain: L2 hits next to data
+    // that is read anyway.  On the bench field they are six of ten, not nine -- a tenth of the PIXELS is set, and 40 % of the words
+    // hold a common one, 108 of the 320 of a wave's step -- so handing the others' words to the lanes of the wave, 64 at a time, takes
+    // two or three level-2 trips one after the other where this takes one: built and measured, 36.4 -> 40.4 us at six workgroups per
+    // CU; profiles/NOTES.md, "k_overlap: wave-level hand-over".)
     auto insert = [&](uint32_t cc, uint32_t cd, int64_t lo, int64_t hi) {
         const unsigned long long key = ((unsigned long long)cc << 32) | cd;
         uint32_t h = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 40) & (CTK_HASH_SLOTS - 1);
