@@ -39,7 +39,7 @@ EXPORTS = [
     "ctk_set_threshold_field", "ctk_set_segments",
     "ctk_track_stream_seg_f32", "ctk_track_stream_seg_f64", "ctk_track_stream_seg_cb", "ctk_track_sharded_seg_f32_dev", "ctk_track_sharded_seg_f64_dev",
     "ctk_frequency_dev", "ctk_frequency", "ctk_frequency_cb", "ctk_debug_set_freq", "ctk_debug_time_freq",
-    "ctk_percentile_groups_f32", "ctk_percentile_groups_f64", "ctk_debug_percentile_groups_sweeps", "ctk_debug_time_percentile_groups",
+    "ctk_percentile_groups_f32", "ctk_percentile_groups_f64", "ctk_debug_percentile_groups_sweeps", "ctk_debug_percentile_groups_plan", "ctk_debug_percentile_groups_state", "ctk_debug_time_percentile_groups",
     "ctk_percentile_field_f32", "ctk_percentile_field_f64", "ctk_debug_percentile_field_plan", "ctk_debug_percentile_field_form", "ctk_debug_time_percentile_field",
     "ctk_std_field_f32", "ctk_std_field_f64", "ctk_debug_std_field_plan", "ctk_debug_std_field_form", "ctk_debug_time_std_field",
     "ctk_anom_seg_f32", "ctk_anom_seg_f64", "ctk_anom_stream_f32", "ctk_anom_stream_f64", "ctk_anom_stream_cb", "ctk_debug_anom_form", "ctk_debug_anom_plan", "ctk_debug_set_anom", "ctk_debug_anom_launch",
@@ -84,7 +84,7 @@ class FormQuery(C.Structure):
 class FormPlan(C.Structure):
     """ctk_form_plan of include/contrack_hip_debug.h"""
     _fields_ = [(n, C.c_int64) for n in (
-        "thr_kind thr_u7 thr_rbt thr_grid rowcount_threads v0b v0_ok v0_runs need_glb spec_launched spec_bits missing missing_bits next_spec overlap_form extent_form write_kernel write_rb write_sub write_kb write_batched write_lds write_grid write_shape chunk_copy runval_threads compact_init_threads count_staged count_fused filter_sys filter_passes filter_blk filter_two_pc filter_nb filter_unite filter_merged filter_bits filter_bits_sync round_blk round_two_pc round_nb").split()]
+        "thr_kind thr_u7 thr_rbt thr_grid rowcount_threads v0b v0_ok v0_runs need_glb spec_launched spec_bits missing missing_bits next_spec overlap_form extent_form write_kernel write_rb write_sub write_kb write_batched write_lds write_grid write_shape chunk_copy runval_threads compact_init_threads count_staged count_fused filter_sys filter_passes filter_blk filter_two_pc filter_nb filter_unite filter_merged filter_bits filter_bits_sync round_blk round_two_pc round_nb rowcount_groups").split()]
 
 
 def debug_percentile_field_plan(keybytes, max_pool_steps, ngroups, window):
@@ -93,6 +93,19 @@ def debug_percentile_field_plan(keybytes, max_pool_steps, ngroups, window):
     v = np.zeros(4, dtype=np.int64)
     check(lib().ctk_debug_percentile_field_plan(int(keybytes), int(max_pool_steps), int(ngroups), int(window), v.ctypes.data))
     return dict(form=int(v[0]), cap=int(v[1]), tile=int(v[2]), ring_bytes=int(v[3]))
+
+
+PCTL_REFUSALS = ("fine", "window", "slots", "band", "day")
+
+
+def debug_percentile_groups_plan(keybits, nband, ngroups, window, max_steps_of_a_group=1):
+    """ctk_debug_percentile_groups_plan: what ctk_pctl_form and ctk_pctl_refusal (csrc/ctk_forms.h) decide, as a dict (levels, sweeps,
+    stride, chunk, chunks, shift and bits of every level, refusal as one of PCTL_REFUSALS); no handle, no GPU"""
+    v = np.zeros(22, dtype=np.int64)
+    check(lib().ctk_debug_percentile_groups_plan(int(keybits), int(nband), int(ngroups), int(window), int(max_steps_of_a_group), v.ctypes.data))
+    n = int(v[0])
+    return dict(levels=n, sweeps=int(v[1]), stride=int(v[2]), chunk=int(v[3]), chunks=int(v[4]), shift=v[5:5 + n].tolist(), bits=v[13:13 + n].tolist(),
+                refusal=PCTL_REFUSALS[int(v[21])])
 
 
 def debug_std_field_plan(ngroups, window=1, skipna=True):
@@ -297,6 +310,8 @@ def lib():
     for name in ("ctk_percentile_groups_f32", "ctk_percentile_groups_f64"):
         getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, i32, p, i32, i32, dbl, p]
     L.ctk_debug_percentile_groups_sweeps.argtypes = [p, C.POINTER(i64)]
+    L.ctk_debug_percentile_groups_plan.argtypes = [i32, i64, i32, i32, i64, p]
+    L.ctk_debug_percentile_groups_state.argtypes = [p, i32, p, p, p]
     L.ctk_debug_time_percentile_groups.argtypes = [p, p, i64, i32, i32, i32, i32, p, i32, i32, dbl, i32, p, p]
     for name in ("ctk_percentile_field_f32", "ctk_percentile_field_f64"):
         getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, i32, p, i32, i32, dbl, p]
@@ -1371,6 +1386,12 @@ class Tracker:
         check(fn(self._h, ptr, T, ny, nx, int(y0), int(y1), group.ctypes.data, int(ngroups), int(window), float(q), out.ctypes.data))
         return out
 
+    def debug_percentile_groups_state(self, ngroups):
+        """test hook: (nu_day uint32, need uint32, n_of uint64), ngroups entries each, of the last percentile_groups() call"""
+        nu, need, n = np.zeros(ngroups, np.uint32), np.zeros(ngroups, np.uint32), np.zeros(ngroups, np.uint64)
+        check(lib().ctk_debug_percentile_groups_state(self._h, int(ngroups), nu.ctypes.data, need.ctypes.data, n.ctypes.data))
+        return nu, need, n
+
     def debug_percentile_groups_sweeps(self):
         """test hook: band reads of the last percentile_groups() call"""
         n = C.c_int64(0)
@@ -1750,13 +1771,13 @@ class Tracker:
         return v is None or (mt is not None and int(mt.group(0)) != 0)
 
     def stats(self):
-        v = np.zeros(36, dtype=np.int64)
-        check(lib().ctk_get_stats_n(self._h, v.ctypes.data, 36))
+        v = np.zeros(37, dtype=np.int64)
+        check(lib().ctk_get_stats_n(self._h, v.ctypes.data, 37))
         names = ["runs", "max_runs_per_step", "components", "pairs", "seam_rows_to_driver", "labels_3d", "seam_ops",
                  "filter_passes", "host_path", "seam_loop_ns", "seam_folds", "seam_copy_ns", "ungrouped_pairs", "pair_table_regrows", "filter_rounds",
                  "ambiguous_decisions", "exact_fixups", "shared_seam_rows", "off_fused_path_reason", "relabel_kernel", "fused_pass", "x4_speculated", "result_as_runs", "mask_allocations_tried", "mask_ratio_x1000",
                  "mask_check_us", "mask_spacer_mb", "label_forms", "overlap_form", "rowcount_threads",
-                 "filter_forms", "extent_form", "runval_form", "relabel_shape", "count_form", "device_cus"]
+                 "filter_forms", "extent_form", "runval_form", "relabel_shape", "count_form", "device_cus", "rowcount_groups"]
         return dict(zip(names, v.tolist()))
 
     def debug_set_pair_capacity(self, records):

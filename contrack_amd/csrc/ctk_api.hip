@@ -382,6 +382,7 @@ struct ctk_handle {
     // percentile per group (ctk_pctl.hip): histograms per (day, distinct prefix); ranks, prefixes, lists, ids; band sweeps of the last call
     DevBuf pc_hist, pc_buf;
     int64_t pc_sweeps = 0;
+    int pc_groups = 0; size_t pc_slots = 0;        // the last ctk_percentile_groups_* launch: G and the histogram slots, which fix pc_buf's layout (0: none yet)
     // percentile field (ctk_pfield.hip): the G planes of the last call; pool starts, pool lengths, the step list; its form and longest pool
     DevBuf pf_out, pf_idx;
     int pf_form = -1; int64_t pf_max_pool = 0;
@@ -797,6 +798,7 @@ extern "C" int ctk_debug_forms(const ctk_form_query *q, ctk_form_plan *p)
     p->filter_unite = fp.unite; p->filter_merged = fp.merged; p->filter_bits = fp.bits; p->filter_bits_sync = ctk_filter_bits_sync(T, q->seg != 0);
     const CtkFilterRound fr = ctk_filter_round(T, (int)q->async_passes, q->no_sys != 0, (int)q->n_cus);
     p->round_blk = fr.blk; p->round_two_pc = fr.two_pc; p->round_nb = fr.nb;
+    p->rowcount_groups = ctk_rowcount_groups((int)p->rowcount_threads, ny, W);
     return CTK_OK;
 }
 
@@ -1078,7 +1080,7 @@ struct Label2dCall {
     CtkLabelShape shape;
     bool spec;                              // a speculative labelling launch was made
     CtkVariantSet launched;
-    int rc_launched; int64_t label_forms;   // (CTK_S_ROWCOUNT_THREADS, CTK_S_LABEL_FORMS: recorded after the statistics are reset)
+    int rc_launched, rc_groups; int64_t label_forms;   // (CTK_S_ROWCOUNT_THREADS, CTK_S_ROWCOUNT_GROUPS, CTK_S_LABEL_FORMS: recorded after the statistics are reset)
 };
 
 static int label2d_begin(ctk_handle *h, Label2dCall &c, int has_prev)
@@ -1106,7 +1108,7 @@ static int label2d_begin(ctk_handle *h, Label2dCall &c, int has_prev)
     c.shape = ctk_label_shape(T, ny, c.W);
     c.spec = false;
     c.launched = {false, false, false, false, false, false};
-    c.rc_launched = 0; c.label_forms = 0;
+    c.rc_launched = 0; c.rc_groups = 0; c.label_forms = 0;
     return CTK_OK;
 }
 
@@ -1381,22 +1383,24 @@ static int label2d_threshold(ctk_handle *h, const Label2dCall &c)
 // runs per row, word and timestep, and their scan.  The host learns the run totals from the scan kernel's block of scalars in
 // pinned memory and knows that it is complete by the stamp the kernel writes last (an event record after the kernel is a command
 // of its own: 5 us of stream time).
+struct RowcountInstance { void (*fn)(const uint64_t *, int, int, uint16_t *, uint32_t *, uint32_t *); int rcu; };
+template <int RCU> static RowcountInstance rowcount_instance() { return {k_rowcount<RCU>, RCU}; }
 static int label2d_rowcount(ctk_handle *h, Label2dCall &c)
 {
     const int64_t T = c.T;
     c.scan_stamp = (uint32_t)(h->pass_no & 0x7fffffffu) | 0x80000000u;
     Timer tm(h, CTK_KI_ROWCOUNT);
     const int rc_threads = ctk_rowcount_threads(T, c.ny, c.W);
-    if (T > 0) {
-        auto *rowcount = k_rowcount<8>;
-        switch (ctk_rowcount_groups(rc_threads, c.ny, c.W)) {
-        case 4: rowcount = k_rowcount<4>; break;
-        case 6: rowcount = k_rowcount<6>; break;
-        default: break;
-        }
-        rowcount<<<(int)T, rc_threads, 0, h->stream>>>(P<uint64_t>(h->mask), c.ny, c.W, P<uint16_t>(h->wstart), P<uint32_t>(h->rowstart), P<uint32_t>(h->tcount));
+    const int rc_groups = ctk_rowcount_groups(rc_threads, c.ny, c.W);
+    RowcountInstance ki = rowcount_instance<8>();
+    switch (rc_groups) {
+    case 4: ki = rowcount_instance<4>(); break;
+    case 6: ki = rowcount_instance<6>(); break;
+    default: break;
     }
+    if (T > 0) ki.fn<<<(int)T, rc_threads, 0, h->stream>>>(P<uint64_t>(h->mask), c.ny, c.W, P<uint16_t>(h->wstart), P<uint32_t>(h->rowstart), P<uint32_t>(h->tcount));
     c.rc_launched = T > 0 ? rc_threads : 0;
+    c.rc_groups = (T > 0 && ctk_rowcount_first_form(c.ny, c.W)) ? ki.rcu : 0;   // (the launched instance's own RCU: what the switch made of rc_groups)
     CTKCHK(launch_scan_u32(h, P<uint32_t>(h->tcount), T, P<uint32_t>(h->run_base), h->h_mail1, c.scan_stamp));
     HIPCHK(hipGetLastError());
     return CTK_OK;
@@ -1549,7 +1553,7 @@ static int label2d_finish_labels(ctk_handle *h, Label2dCall &c)
         h->spec_set = p.next;
         h->spec_ny = c.ny; h->spec_nx = c.nx; h->spec_T = c.T;
     }
-    h->stats[CTK_S_LABEL_FORMS] = c.label_forms; h->stats[CTK_S_ROWCOUNT_THREADS] = c.rc_launched; h->stats[CTK_S_DEVICE_CUS] = h->n_cus;
+    h->stats[CTK_S_LABEL_FORMS] = c.label_forms; h->stats[CTK_S_ROWCOUNT_THREADS] = c.rc_launched; h->stats[CTK_S_ROWCOUNT_GROUPS] = c.rc_groups; h->stats[CTK_S_DEVICE_CUS] = h->n_cus;
     return CTK_OK;
 }
 

@@ -90,6 +90,8 @@ inline int ctk_rowcount_groups(int threads, int ny, int W)
     const int per_group = (threads / 64) * (64 / W), need = (ny + per_group - 1) / per_group;
     return need <= 4 ? 4 : need <= 6 ? 6 : 8;
 }
+// the plane takes k_rowcount's first form, the only one that reads RCU (the kernel's own guard)
+inline bool ctk_rowcount_first_form(int ny, int W) { return W <= 64 && ny <= RC_ROWS; }
 
 // ------------------------------------------------------------------------------------------------
 // 2-D labelling.  The variants take disjoint sets of timesteps (by run count; nruns == 0 goes to the small one).
@@ -424,6 +426,19 @@ inline CtkPctlForm ctk_pctl_form(int keybits, int64_t nband, int G, int W)
 }
 // per-day histogram counters are uint32: a day's timesteps x band pixels must stay below 2^32
 inline bool ctk_pctl_day_fits(int64_t steps_of_day, int64_t nband) { return steps_of_day == 0 || nband <= (int64_t)0xffffffffll / steps_of_day; }
+// what ctk_percentile_groups_* refuses by size (pctl_validate and ctk_debug_percentile_groups_plan ask here), first reason met:
+// a window below the group count wider than the LDS list of a day's prefixes; more histograms than CTK_PCTL_MAX_SLOTS; more sweep
+// workgroups per timestep than gridDim.y holds; a group whose timesteps x band values overflow its uint32 counters
+enum CtkPctlRefusal { CTK_PCTL_FINE = 0, CTK_PCTL_REFUSE_WINDOW = 1, CTK_PCTL_REFUSE_SLOTS = 2, CTK_PCTL_REFUSE_BAND = 3, CTK_PCTL_REFUSE_DAY = 4 };
+inline int ctk_pctl_refusal(int64_t nband, int G, int W, int64_t max_steps_of_a_group)
+{
+    if (W < G && W > CTK_PCTL_MAX_WINDOW) return CTK_PCTL_REFUSE_WINDOW;
+    const CtkPctlForm f = ctk_pctl_form(32, nband, G, W);
+    if ((uint64_t)G * (uint64_t)f.stride > (uint64_t)CTK_PCTL_MAX_SLOTS) return CTK_PCTL_REFUSE_SLOTS;
+    if ((nband + CTK_PCTL_CHUNK - 1) / CTK_PCTL_CHUNK > 65535) return CTK_PCTL_REFUSE_BAND;
+    if (!ctk_pctl_day_fits(max_steps_of_a_group, nband)) return CTK_PCTL_REFUSE_DAY;
+    return CTK_PCTL_FINE;
+}
 
 // ------------------------------------------------------------------------------------------------
 // percentile field per group and grid point (ctk_pfield.hip): a radix selection per (group, pixel)

@@ -298,20 +298,22 @@ __global__ __launch_bounds__(256) void k_pctl_read(const VT *__restrict__ x, int
 static int pctl_validate(const ctk_handle *h, const PctlArgs &a, const double *out, const char *name)
 {
     CTKCHK(pctl_validate_common(h, a, out, name));
-    if (a.window < a.ngroups && a.window > CTK_PCTL_MAX_WINDOW)
-        return ctk_set_error(CTK_E_INVALID, "%s: a window of %d groups (below the %d groups) exceeds %d", name, a.window, a.ngroups, CTK_PCTL_MAX_WINDOW);
     std::vector<int64_t> steps((size_t)a.ngroups, 0);
     for (int64_t t = 0; t < a.T; t++) steps[(size_t)a.group[t]]++;
+    const int gmax = (int)(std::max_element(steps.begin(), steps.end()) - steps.begin());
     const int64_t nband = a.nband();
-    for (int g = 0; g < a.ngroups; g++)
-        if (!ctk_pctl_day_fits(steps[(size_t)g], nband))
-            return ctk_set_error(CTK_E_INVALID, "%s: group %d has %lld timesteps of %lld band values: its uint32 counters would overflow (2^32)", name, g,
-                                 (long long)steps[(size_t)g], (long long)nband);
-    const CtkPctlForm f = ctk_pctl_form(32, nband, a.ngroups, a.window);
-    if ((uint64_t)a.ngroups * (uint64_t)f.stride > CTK_PCTL_MAX_SLOTS)
+    switch (ctk_pctl_refusal(nband, a.ngroups, a.window, steps[(size_t)gmax])) {               // (the size rules: ctk_forms.h)
+    case CTK_PCTL_REFUSE_WINDOW:
+        return ctk_set_error(CTK_E_INVALID, "%s: a window of %d groups (below the %d groups) exceeds %d", name, a.window, a.ngroups, CTK_PCTL_MAX_WINDOW);
+    case CTK_PCTL_REFUSE_SLOTS:
         return ctk_set_error(CTK_E_INVALID, "%s: %d groups x a window of %d need %lld histograms of 8 KB, more than the %lld (4 GB) this entry takes", name, a.ngroups,
-                             a.window, (long long)a.ngroups * f.stride, (long long)CTK_PCTL_MAX_SLOTS);
-    if ((nband + CTK_PCTL_CHUNK - 1) / CTK_PCTL_CHUNK > 65535) return ctk_set_error(CTK_E_INVALID, "%s: a band of %lld values is too large", name, (long long)nband);
+                             a.window, (long long)a.ngroups * ctk_pctl_form(32, nband, a.ngroups, a.window).stride, (long long)CTK_PCTL_MAX_SLOTS);
+    case CTK_PCTL_REFUSE_BAND: return ctk_set_error(CTK_E_INVALID, "%s: a band of %lld values is too large", name, (long long)nband);
+    case CTK_PCTL_REFUSE_DAY:
+        return ctk_set_error(CTK_E_INVALID, "%s: group %d has %lld timesteps of %lld band values: its uint32 counters would overflow (2^32)", name, gmax,
+                             (long long)steps[(size_t)gmax], (long long)nband);
+    default: break;
+    }
     return CTK_OK;
 }
 
@@ -337,6 +339,7 @@ static int pctl_launch(ctk_handle *h, const VT *x_dev, const PctlArgs &a, const 
     uint32_t *hist = P<uint32_t>(h->pc_hist);
     const dim3 sweep_grid((unsigned)a.T, f.chunks), zero_grid((unsigned)G, (unsigned)f.stride);
     h->pc_sweeps = 0;
+    h->pc_groups = G; h->pc_slots = slots;                                     // (ctk_debug_percentile_groups_state reads pc_buf by them)
     for (int l = 0; l < f.levels; l++) {
         const bool first = l == 0, last = l == f.levels - 1;
         k_pctl_zero<<<zero_grid, 256, 0, s>>>(hist, nu, f.stride, first ? 1 : 0);
@@ -392,6 +395,38 @@ extern "C" int ctk_debug_percentile_groups_sweeps(ctk_handle *h, int64_t *sweeps
 {
     if (!h || !sweeps) return ctk_set_error(CTK_E_INVALID, "null argument");
     *sweeps = h->pc_sweeps;
+    return CTK_OK;
+}
+
+// test hook, no handle, no device: the plan of ctk_pctl_form and the refusal of ctk_pctl_refusal (ctk_forms.h) for keys of `keybits`
+// bits, a band of nband values, ngroups, window and the most timesteps a group owns.  out22 = { levels, sweeps, stride, chunk, chunks,
+// shift[8], bits[8] (0 beyond levels), refusal: 0 fine, 1 the window, 2 the histogram slots, 3 the band, 4 a day's counters }
+extern "C" int ctk_debug_percentile_groups_plan(int keybits, int64_t nband, int ngroups, int window, int64_t max_steps_of_a_group, int64_t *out22)
+{
+    if (!out22 || (keybits != 32 && keybits != 64) || nband < 1 || ngroups < 1 || window < 1 || max_steps_of_a_group < 0)
+        return ctk_set_error(CTK_E_INVALID, "ctk_debug_percentile_groups_plan: bad arguments");
+    const CtkPctlForm f = ctk_pctl_form(keybits, nband, ngroups, window);
+    out22[0] = f.levels; out22[1] = f.sweeps; out22[2] = f.stride; out22[3] = f.chunk; out22[4] = (nband + f.chunk - 1) / f.chunk;
+    for (int l = 0; l < 8; l++) { out22[5 + l] = l < f.levels ? f.shift[l] : 0; out22[13 + l] = l < f.levels ? f.bits[l] : 0; }
+    out22[21] = ctk_pctl_refusal(nband, ngroups, window, max_steps_of_a_group);
+    return CTK_OK;
+}
+
+// test hook: what the last ctk_percentile_groups_* call on this handle left in pc_buf, per group: nu_day (the distinct selected keys of
+// the day's targets, after the last k_pctl_lists), need (the closing sweep supplies the group's next larger key), n_of (its pool)
+extern "C" int ctk_debug_percentile_groups_state(ctk_handle *h, int ngroups, uint32_t *nu_day, uint32_t *need, uint64_t *n_of)
+{
+    if (!h || !nu_day || !need || !n_of) return ctk_set_error(CTK_E_INVALID, "ctk_debug_percentile_groups_state: null argument");
+    if (h->pc_groups < 1) return ctk_set_error(CTK_E_STATE, "ctk_debug_percentile_groups_state: no ctk_percentile_groups_* call has run on this handle");
+    if (ngroups != h->pc_groups) return ctk_set_error(CTK_E_INVALID, "ctk_debug_percentile_groups_state: ngroups=%d, the last call had %d", ngroups, h->pc_groups);
+    HIPCHK(hipSetDevice(h->device));
+    const size_t G = (size_t)h->pc_groups;
+    const uint64_t *n_dev = P<uint64_t>(h->pc_buf);                            // (the layout of pctl_launch)
+    const uint32_t *nu_dev = (const uint32_t *)(n_dev + 6 * G + 1 + 2 * h->pc_slots);
+    HIPCHK(hipMemcpyAsync(n_of, n_dev, G * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(nu_day, nu_dev, G * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(need, nu_dev + G, G * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return CTK_OK;
 }
 

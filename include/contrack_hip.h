@@ -351,6 +351,9 @@ int ctk_get_stats(ctk_handle *h, int64_t *out /* [CTK_NSTATS] */);
 #define CTK_S_COUNT_FORM    34    /* bit mask of the alive-count kernels the last call launched: 1 k_count_alive_f, 2 k_count_alive_1,
                                    * 4 k_count_alive in the fused pass; 8 k_count_alive_1, 16 k_count_alive in ctk_shard_write */
 #define CTK_S_DEVICE_CUS    35    /* compute units of the handle's device (the k_rs_pass_blk_2pc edge: more workgroups than CUs) */
+#define CTK_S_ROWCOUNT_GROUPS 36  /* row groups the last k_rowcount launch kept in flight: the RCU of the instance k_rowcount<RCU> it ran (4, 6
+                                   * or 8); 0 where the plane took one of the kernel's other two forms (more than 64 words a row, or
+                                   * more than 2048 rows), which do not read it */
 #define CTK_NSTATS_ALL      40
 int ctk_get_stats_n(ctk_handle *h, int64_t *out, int n);
 int ctk_get_timings(ctk_handle *h, double *ms /* [CTK_NTIMERS] */);

@@ -110,9 +110,10 @@ int ctk_debug_set_small_threads(ctk_handle *h, int extent, int run_values, int c
  * (the previous call's speculative set / what ran speculatively on buffers that were large enough).
  * Plan: thr_kind 0 v7, 1 v6, 2 generic float32, 3 generic float64, 4 field vector, 5 field generic; *_bits as in CTK_S_LABEL_FORMS /
  * CTK_S_FILTER_FORMS; overlap_form, extent_form, write_kernel, write_shape, count_* as the statistics of the same name report them;
- * filter_unite 0 inside the pass kernel, 1 k_rs_unite_slots, 2 k_rs_unite. */
+ * filter_unite 0 inside the pass kernel, 1 k_rs_unite_slots, 2 k_rs_unite; rowcount_groups: ctk_rowcount_groups for rowcount_threads,
+ * the RCU of k_rowcount<RCU> (CTK_S_ROWCOUNT_GROUPS reports it for the kernel's first form, 0 for the other two). */
 typedef struct ctk_form_query { int64_t T, nt, ny, nx, f64, aligned16, field, max_runs_step, total_runs, n_labels, last_nlab, async_passes, no_sys, n_cus, seg, pslot, path, forced_extent, forced_run_values, forced_compact_init, spec_set, launched; } ctk_form_query;
-typedef struct ctk_form_plan { int64_t thr_kind, thr_u7, thr_rbt, thr_grid, rowcount_threads, v0b, v0_ok, v0_runs, need_glb, spec_launched, spec_bits, missing, missing_bits, next_spec, overlap_form, extent_form, write_kernel, write_rb, write_sub, write_kb, write_batched, write_lds, write_grid, write_shape, chunk_copy, runval_threads, compact_init_threads, count_staged, count_fused, filter_sys, filter_passes, filter_blk, filter_two_pc, filter_nb, filter_unite, filter_merged, filter_bits, filter_bits_sync, round_blk, round_two_pc, round_nb; } ctk_form_plan;
+typedef struct ctk_form_plan { int64_t thr_kind, thr_u7, thr_rbt, thr_grid, rowcount_threads, v0b, v0_ok, v0_runs, need_glb, spec_launched, spec_bits, missing, missing_bits, next_spec, overlap_form, extent_form, write_kernel, write_rb, write_sub, write_kb, write_batched, write_lds, write_grid, write_shape, chunk_copy, runval_threads, compact_init_threads, count_staged, count_fused, filter_sys, filter_passes, filter_blk, filter_two_pc, filter_nb, filter_unite, filter_merged, filter_bits, filter_bits_sync, round_blk, round_two_pc, round_nb, rowcount_groups; } ctk_form_plan;
 int ctk_debug_forms(const ctk_form_query *q, ctk_form_plan *p);
 
 /* filter passes launched per round before convergence is checked on the host (default 10, 1..32)   */
@@ -163,6 +164,20 @@ int ctk_debug_percentile_values(ctk_handle *h, double *out, int64_t n);
 
 /* test hook: how often the last ctk_percentile_groups_* call on this handle read the band (launches of k_pctl_sweep and k_pctl_close) */
 int ctk_debug_percentile_groups_sweeps(ctk_handle *h, int64_t *sweeps);
+/* what ctk_pctl_form and ctk_pctl_refusal (csrc/ctk_forms.h) decide for a ctk_percentile_groups_* call on keys of `keybits` (32 / 64)
+ * bits, a band of nband values, ngroups, window and a group of at most max_steps_of_a_group timesteps: out22 = { levels, sweeps
+ * (levels + the closing sweep), stride (histogram slots per day), chunk (band values per sweep workgroup), chunks (workgroups per
+ * timestep), shift[8], bits[8] (digit l is (key >> shift[l]) & ((1 << bits[l]) - 1); 0 beyond levels), refusal }.  refusal: what
+ * the entry answers CTK_E_INVALID for -- 0 nothing, 1 a window below the group count above 1024, 2 ngroups x stride above 2^19
+ * histograms, 3 more than 65 535 chunks, 4 a group whose timesteps x band values do not fit its uint32 counters -- the first of
+ * these that holds; the entry asks the same function.  Host only: no handle, no GPU. */
+int ctk_debug_percentile_groups_plan(int keybits, int64_t nband, int ngroups, int window, int64_t max_steps_of_a_group, int64_t *out22);
+/* test hook: intermediate values of the last ctk_percentile_groups_* call on this handle, ngroups entries each, copied from the
+ * handle's workspace: nu_day[d] = the distinct selected keys among the targets of day d (the groups whose window holds d), as the
+ * last k_pctl_lists counted them (1 where the window covers every group); need[g] = 1 where group g takes its next larger key from
+ * the closing sweep (its rank and the next one straddle the last digit's histogram); n_of[g] = the non-NaN values of its pool.
+ * An error if no such call has run on the handle or ngroups differs from that call's. */
+int ctk_debug_percentile_groups_state(ctk_handle *h, int ngroups, uint32_t *nu_day, uint32_t *need, uint64_t *n_of);
 /* measurement (tools/pctl_probe.py) on a float32 slab in device memory: ms12 = { ctk_percentile_groups per call (best of reps, host
  * clock: upload of the ids, every kernel, download, synchronisation), one plain 16-byte read stream over the band with the sweeps'
  * grid (best of reps, HIP events), the scalar percentile's kernels (k_quantile + k_nanmean, once, HIP events), then the band sweeps

@@ -1,12 +1,12 @@
 """Which row-count, 2-D labelling and overlap kernel forms a call launches: a restatement of the rules in
-contrack_amd/csrc/ctk_forms.h (ctk_rowcount_threads, ctk_label_shape for v0b / v0_ok / v0_runs, ctk_label_speculative, ctk_label_plan
+contrack_amd/csrc/ctk_forms.h (ctk_rowcount_threads, ctk_rowcount_groups, ctk_label_shape for v0b / v0_ok / v0_runs, ctk_label_speculative, ctk_label_plan
 for the launch after the run scan and the next call's speculative set, ctk_label_form_bits, ctk_overlap_form), of the protocol around
 them in contrack_amd/csrc/ctk_api.hip (label2d_speculate, label2d_regrow's capacity check, label2d_finish_labels, launch_label2d) and
 of the instances' own guards in contrack_amd/csrc/ctk_kernels.hip (k_label2d_lds: the planes it takes by RUNS / RUNS_BELOW / NYCAP, its
 staged mask; k_label2d_glb; label2d_body's component tables in LDS).
 Host-only.  Kept in step with the C++ by tests/test_label_forms.py which compares it with the library itself (ctk_debug_forms), and, on
 the GPU, by the statistics CTK_S_LABEL_FORMS,
-CTK_S_OVERLAP_FORM and CTK_S_ROWCOUNT_THREADS that tests/test_gpu_label_forms.py asserts.
+CTK_S_OVERLAP_FORM, CTK_S_ROWCOUNT_THREADS and CTK_S_ROWCOUNT_GROUPS that tests/test_gpu_label_forms.py asserts.
 
 It also builds the planes that reach the forms: 0/1 planes with a prescribed number of runs, 2-D components (no wrap), seam rows
 and, for the pair edges, distinct overlapping (c, d) pairs with the next plane."""
@@ -45,6 +45,28 @@ def rowcount_threads(T, ny, W):
     if W <= 64 and ny <= RC_ROWS and ny > 256 and T <= 2048:
         return 512
     return 128 if (T > 65536 and ny * W <= 2048) else 256
+
+
+def rowcount_groups(threads, ny, W):
+    """ctk_rowcount_groups (ctk_forms.h): the RCU of k_rowcount<RCU>, the row groups its first form keeps in flight -- as many as the
+    plane needs in one step of its waves, of 4 / 6 / 8; a wave takes 64 // W whole rows of a group"""
+    if W > 64:
+        return 8
+    per_group = (threads // 64) * (64 // W)
+    need = (ny + per_group - 1) // per_group
+    return 4 if need <= 4 else 6 if need <= 6 else 8
+
+
+def rowcount_groups_stat(T, ny, W):
+    """CTK_S_ROWCOUNT_GROUPS: the RCU of the instance launched; 0 where the plane takes one of the kernel's other two forms (or
+    nothing is launched)"""
+    if T == 0 or W > 64 or ny > RC_ROWS:
+        return 0
+    return rowcount_groups(rowcount_threads(T, ny, W), ny, W)
+
+
+def rowcount_name(T, ny, W):
+    return "rowcount<%d,%d>" % (rowcount_threads(T, ny, W), rowcount_groups_stat(T, ny, W))
 
 
 def _v0(T, ny, W):
@@ -190,7 +212,7 @@ def forms_reached(T, ny, nx, runs, comps, seg=(False,)):
     W = (nx + 63) // 64
     runs = np.asarray(runs)
     prefer_one = T <= 512 and int(runs.max()) > 1024
-    out = {"rowcount<%d>" % rowcount_threads(T, ny, W)}
+    out = {"rowcount<%d>" % rowcount_threads(T, ny, W), rowcount_name(T, ny, W)}
     out |= {overlap_name(overlap_form(T, ny, W, s)) for s in seg}
     for r, c in set(zip(runs.tolist(), np.asarray(comps).tolist())):
         v = label_variant(T, ny, nx, r, prefer_one)
@@ -210,6 +232,9 @@ def _all_forms():
     f |= {v + ":global_mask" for v in ("v1", "v2", "v3", "one")}
     f |= {overlap_name(s * 1000000 + a * 10000 + b * 10 + c) for a, b, c in OVERLAP for s in (0, 1)}
     f |= {"rowcount<%d>" % n for n in ROWCOUNT}
+    # <threads,RCU> of the first form; RCU 0: the other two forms.  (128 threads with RCU 6 or 8 need a shard of more than 65536
+    # planes of at least 257 x 128: eight times the long shard below; no case reaches them)
+    f |= {"rowcount<%d,%d>" % (n, u) for n in (512, 256) for u in (4, 6, 8)} | {"rowcount<128,4>", "rowcount<256,0>"}
     return frozenset(f)
 
 
@@ -398,6 +423,21 @@ for _ny, _f in ((1024, "v1"), (1025, "glb"), (2048, "rowcount<512>"), (2049, "ro
     _case("grid_ny_%d" % _ny, 4, _ny, 64, _edges((100, 900), 60), _cycle(["r100", "r900_", "r900", "r100_"]), {_f})
 _case("lattice_721x1440", 2, 721, 1440, {"a": ("lattice",), "b": ("bars", "a")}, _cycle(["a", "b"]), {"glb"})
 
+# ---- k_rowcount<RCU>: the 4 | 5 and 6 | 7 edges of the row groups a plane needs, and past 8 (a second, partial outer trip) ------------
+# plane "a": full-height stacks in the word-boundary bands (runs across a boundary in every row, the last included) and seam rows;
+# "b": one-row stacks and a seam row (x = nx - 1: the last word) in the LAST row; "c": that row filled from first to last pixel
+def _rcu_planes(ny, nx):
+    k = min((nx + 63) // 64 + 3, len(_bands(nx, 2, nx - 3)))
+    return {"a": ("stack", 4 + k * ny, k + 2, 2, 0), "b": ("stack", 2 + k, k + 2, 1, ny - 1), "c": ("bars", "b")}
+
+
+RCU_EDGES = [(360, 160, 256, 4), (360, 161, 256, 6), (360, 240, 256, 6), (360, 241, 256, 8), (360, 256, 256, 8), (360, 257, 512, 4),
+             (360, 320, 512, 4), (360, 321, 512, 6), (360, 480, 512, 6), (360, 481, 512, 8), (360, 640, 512, 8), (360, 641, 512, 8),
+             (1440, 32, 256, 4), (1440, 33, 256, 6), (1440, 48, 256, 6), (1440, 49, 256, 8), (1440, 64, 256, 8), (1440, 65, 256, 8),
+             (130, 721, 512, 6), (4160, 20, 256, 0)]             # (nx, ny, threads, CTK_S_ROWCOUNT_GROUPS), T = 4
+for _nx, _ny, _thr, _rcu in RCU_EDGES:
+    _case("rcu_%dx%d" % (_ny, _nx), 4, _ny, _nx, _rcu_planes(_ny, _nx), _cycle(["a", "b", "c", "a"]), {"rowcount<%d,%d>" % (_thr, _rcu)}, seg=False)
+
 # ---- pair edges: dots and the bars over them (one pair per dot, in both orders) -----------------------------------------------
 for _p in (128, 129, 600):
     _case("pairs_%d" % _p, 6, 192, 288, {"d": ("stack", _p, _p, 0, 0), "b": ("bars", "d")}, _cycle(["d", "b"]), {"v1"})
@@ -414,7 +454,7 @@ def long_schedule(busy_keys, t0=30000, n=400):
 
 _case("long_shard", LONG_T, 32, 128, dict(QUIET, **LONG_BUSY), long_schedule(["a", "b", "c", "d", "e", "f"]),
       {"v1_832", "v1hi_832", "v1_832:staged", "v1hi_832:staged", "v1_832:tables_lds", "v1_832:tables_global", "v1hi_832:tables_lds",
-       "v1hi_832:tables_global", "rowcount<128>", "overlap<4,128,5>", "overlap<4,128,5,SEG>"}, slow=True)
+       "v1hi_832:tables_global", "rowcount<128>", "rowcount<128,4>", "overlap<4,128,5>", "overlap<4,128,5,SEG>"}, slow=True)
 # the same shard without planes above 832 runs: no v1hi (the speculation test alternates the two)
 LONG_QUIET_KEYS = ["a", "b"]
 

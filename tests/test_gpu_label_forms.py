@@ -2,8 +2,11 @@
 outputs (mask, 2-D labels before and after the seam merge, component / pair / seam tables: tests/staged_util.py), the one-call
 flags of `track` and of `track_dev` twice on the same handle (the second call launches speculatively), and a call with a segment
 break (the SEG builds of k_overlap, against tests/segment_util.expected).  The planes come from tests/label_forms.py, which
-restates the selection; after every call the statistics CTK_S_LABEL_FORMS, CTK_S_OVERLAP_FORM and CTK_S_ROWCOUNT_THREADS must
-name the forms the restatement predicts, so a case that misses its form fails whatever its flags."""
+restates the selection; after every call the statistics CTK_S_LABEL_FORMS, CTK_S_OVERLAP_FORM, CTK_S_ROWCOUNT_THREADS and
+CTK_S_ROWCOUNT_GROUPS must name the forms the restatement predicts, so a case that misses its form fails whatever its flags.
+The rcu_* cases sit on the 4 | 5, 6 | 7 and 8 | 9 edges of the row groups a plane needs of k_rowcount<RCU>, with 256 and 512
+threads, on the staged and the fused path.  Not covered: the 128-thread form with RCU 6 or 8 -- it needs more than 65536 planes
+of at least 257 x 128, eight times the long shard below (tests/test_label_forms.py pins its rule on the host)."""
 import numpy as np
 import pytest
 
@@ -41,6 +44,8 @@ def _expect_forms(trk, model, shape, runs, seg):
     want = model.label2d(T, ny, nx, runs)
     assert st["label_forms"] == want, "label forms %#x, predicted %#x" % (st["label_forms"], want)
     assert st["rowcount_threads"] == lf.rowcount_threads(T, ny, W)
+    assert st["rowcount_groups"] == lf.rowcount_groups_stat(T, ny, W), \
+        "k_rowcount<%d> ran, predicted %s" % (st["rowcount_groups"], lf.rowcount_name(T, ny, W))
     assert st["overlap_form"] == lf.overlap_form(T, ny, W, seg), \
         "%s, predicted %s" % (lf.overlap_name(st["overlap_form"]), lf.overlap_name(lf.overlap_form(T, ny, W, seg)))
     return st

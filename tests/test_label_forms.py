@@ -34,6 +34,43 @@ def test_restatement_edges():
     assert lf.overlap_form(8, 32, 2, True) == 1042561 and lf.overlap_form(65537, 32, 2, False) == 41285
     assert [lf.rowcount_threads(4, ny, 1) for ny in (256, 257, 2048, 2049)] == [256, 512, 512, 256]
     assert lf.rowcount_threads(2049, 721, 23) == 256 and lf.rowcount_threads(65537, 32, 2) == 128
+    # k_rowcount<RCU>: a group is one step of the workgroup's waves, threads / 64 waves x 64 // W rows; need = groups of the plane
+    rcu = lambda ny, W, T=4: (lf.rowcount_threads(T, ny, W), lf.rowcount_groups(lf.rowcount_threads(T, ny, W), ny, W))
+    assert [rcu(ny, 6) for ny in (160, 161, 240, 241, 256)] == [(256, 4), (256, 6), (256, 6), (256, 8), (256, 8)]            # 40 rows a group: need 4 | 5, 6 | 7, 7
+    assert [rcu(ny, 6) for ny in (257, 320, 321, 480, 481, 640, 641)] == [(512, 4), (512, 4), (512, 6), (512, 6), (512, 8), (512, 8), (512, 8)]   # 80 rows: 4, 4 | 5, 6 | 7, 8 | 9
+    assert [rcu(ny, 23) for ny in (32, 33, 48, 49, 64, 65)] == [(256, 4), (256, 6), (256, 6), (256, 8), (256, 8), (256, 8)]  # 8 rows a group (64 // 23 = 2 a wave)
+    assert rcu(721, 3) == (512, 6)                       # 21 rows a wave step (64 % 3: a lane idle), 168 a group: need 5
+    assert rcu(257, 2, 65537) == (128, 6) and rcu(32, 2, 65537) == (128, 4)
+    assert rcu(20, 65) == (256, 8) and rcu(2049, 1) == (256, 8) and rcu(2048, 1) == (512, 4)
+    # the statistic: the RCU of the first form only
+    assert lf.rowcount_groups_stat(4, 20, 65) == 0 and lf.rowcount_groups_stat(4, 2049, 1) == 0 and lf.rowcount_groups_stat(0, 160, 6) == 0
+    assert lf.rowcount_groups_stat(4, 2048, 1) == 4 and lf.rowcount_groups_stat(4, 20, 64) == 6 and lf.rowcount_groups_stat(4, 641, 6) == 8
+    assert lf.rowcount_name(4, 161, 6) == "rowcount<256,6>" and lf.rowcount_name(4, 20, 65) == "rowcount<256,0>"
+
+
+def test_rcu_cases_sit_on_the_edges():
+    """the rcu_* cases: the restatement gives the threads and the RCU the table of edges names; their planes have runs in the last
+    row, in the last word of a row and across word boundaries in the rows of the last, partial group (and of a partial second trip)"""
+    for nx, ny, thr, stat in lf.RCU_EDGES:
+        c = lf.CASE_BY_NAME["rcu_%dx%d" % (ny, nx)]
+        W = (nx + 63) // 64
+        assert (c["T"], lf.rowcount_threads(4, ny, W), lf.rowcount_groups_stat(4, ny, W)) == (4, thr, stat), c["name"]
+        pl = lf.planes_of(c)
+        assert set(lf.schedule_of(c)) == {"a", "b", "c"}
+        a, b, full = pl["a"].astype(bool), pl["b"].astype(bool), pl["c"].astype(bool)
+        assert b[ny - 1, nx - 1] and b[ny - 1].sum() > 2 and not b[:ny - 1].any()       # the last row, its last word
+        assert full[ny - 1].all() and not full[:ny - 1].any()                            # one run over every word of the last row
+        cross = lambda m: (m[:, 63::64][:, :(nx - 1) // 64] & m[:, 64::64][:, :(nx - 1) // 64]).any(axis=1)
+        crossing = cross(a) | cross(full)                # (nx = 130: its one boundary band, 127 .. 128, lies beyond nx - 3: the last row alone crosses)
+        assert crossing[ny - 1]
+        if stat:
+            per_group = (thr // 64) * (64 // W)
+            tail = range((ny - 1) // per_group * per_group, ny)                          # rows of the last group
+            assert all(a[y].any() for y in range(ny)) and (nx == 130 or all(crossing[y] for y in tail)), c["name"]
+            need = (ny + per_group - 1) // per_group
+            assert (need > 8) == (c["name"] in ("rcu_641x360", "rcu_65x1440")), c["name"]      # the second outer trip, partial
+    names = {lf.rowcount_name(c["T"], c["ny"], (c["nx"] + 63) // 64) for c in lf.CASES}
+    assert {"rowcount<%d,%d>" % (t, u) for t in (256, 512) for u in (4, 6, 8)} | {"rowcount<256,0>", "rowcount<128,4>"} == names
 
 
 @pytest.mark.parametrize("case", lf.CASES, ids=lambda c: c["name"])
@@ -132,6 +169,8 @@ _EDGE_T = (1, 512, 513, 1024, 1025, 2048, 2049, 65536, 65537)
 _EDGE_GRIDS = [(ny, 64 * W) for ny, W in ((960, 1), (961, 1), (240, 4), (31, 31), (192, 5), (193, 5), (1088, 1), (1089, 1), (33, 33), (256, 4), (257, 4), (136, 8),
                                            (137, 8), (2048, 1), (2049, 1), (128, 16), (129, 16), (8191, 1), (8192, 1), (128, 64), (127, 65),
                                            (32, 2), (1024, 1), (1025, 1), (181, 6), (721, 23))] + [(181, 360), (192, 288), (721, 1440)]
+# k_rowcount<RCU>: need of 4 | 5, 6 | 7, 8 | 9 groups with 128, 256 and 512 threads (W = 1: 128, 256 and 512 rows a group; W = 2: 64 with 128 threads)
+_EDGE_GRIDS += [(ny, 64) for ny in (512, 513, 768, 769, 1280, 1281, 1536, 1537)] + [(ny, 128) for ny in (256, 257, 384, 385, 512, 513)] + [(721, 130), (20, 4160)]
 
 
 def test_shape_rules_agree_with_the_library():
@@ -142,6 +181,7 @@ def test_shape_rules_agree_with_the_library():
             for seg in (False, True):
                 p = _native.forms(T, ny, nx, seg=seg)
                 assert p["rowcount_threads"] == lf.rowcount_threads(T, ny, W), (T, ny, nx)
+                assert p["rowcount_groups"] == lf.rowcount_groups(p["rowcount_threads"], ny, W), (T, ny, nx)
                 assert (bool(p["v0b"]), bool(p["v0_ok"]), p["v0_runs"]) == lf._v0(T, ny, W), (T, ny, nx)
                 assert p["overlap_form"] == lf.overlap_form(T, ny, W, seg), (T, ny, nx, seg)
 
