@@ -39,6 +39,7 @@ EXPORTS = [
     "ctk_set_threshold_field", "ctk_set_segments",
     "ctk_track_stream_seg_f32", "ctk_track_stream_seg_f64", "ctk_track_stream_seg_cb", "ctk_track_sharded_seg_f32_dev", "ctk_track_sharded_seg_f64_dev",
     "ctk_frequency_dev", "ctk_frequency", "ctk_frequency_cb", "ctk_debug_set_freq", "ctk_debug_time_freq",
+    "ctk_spells_dev", "ctk_spells", "ctk_spells_cb", "ctk_debug_set_spell", "ctk_debug_time_spell",
     "ctk_percentile_groups_f32", "ctk_percentile_groups_f64", "ctk_debug_percentile_groups_sweeps", "ctk_debug_percentile_groups_plan", "ctk_debug_percentile_groups_state", "ctk_debug_time_percentile_groups",
     "ctk_percentile_field_f32", "ctk_percentile_field_f64", "ctk_debug_percentile_field_plan", "ctk_debug_percentile_field_form", "ctk_debug_time_percentile_field",
     "ctk_std_field_f32", "ctk_std_field_f64", "ctk_debug_std_field_plan", "ctk_debug_std_field_form", "ctk_debug_time_std_field",
@@ -193,6 +194,12 @@ def lib():
     L.ctk_frequency.argtypes = [p, p, i64, i32, i32, p, i32, C.c_int32, p, i64]
     L.ctk_frequency_cb.argtypes = [p, i64, i32, i32, READ_CHUNK_FN, p, p, i32, C.c_int32, p, i64]
     L.ctk_debug_set_freq.argtypes = [p, i64, i32]
+    spell_args = [p, i32, p, i64, C.c_int32, i32, i64, p, p, p]                 # group, ngroups, seg_starts, nseg, above, by_id, min_duration, 3 maps
+    L.ctk_spells_dev.argtypes = [p, p, i64, i32, i32] + spell_args
+    L.ctk_spells.argtypes = [p, p, i64, i32, i32] + spell_args + [i64]
+    L.ctk_spells_cb.argtypes = [p, i64, i32, i32, READ_CHUNK_FN, p] + spell_args + [i64]
+    L.ctk_debug_set_spell.argtypes = [p, i64]
+    L.ctk_debug_time_spell.argtypes = [p, p, i64, i32, i32] + spell_args + [i32, C.POINTER(dbl)]
     for fn in (L.ctk_composite_f32_dev, L.ctk_composite_f64_dev):
         fn.argtypes = [p, p, p, i64, i32, i32, p, i32, C.c_int32, i32, p, p, i32]
     for fn in (L.ctk_composite_f32, L.ctk_composite_f64):
@@ -412,6 +419,39 @@ def _above(above):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data
+
+
+def _spell_args(T, group=None, ngroups=None, segments=None, by_id=True, min_duration=1):
+    """the arguments the spell entries share, checked before the library is touched (it checks them again): (group ids int32 or
+    None, G, segment starts int64 or None, by_id 0 / 1, min_duration).  ValueError names the value that is wrong."""
+    T = int(T)
+    if T < 1:
+        raise ValueError("bad shape: T=%d" % T)
+    if T > 2 ** 32 - 1:
+        raise ValueError("T=%d timesteps do not fit the uint32 durations (at most 2^32 - 1)" % T)
+    g, G = _groups(group, T, ngroups)
+    if G < 1:
+        raise ValueError("ngroups=%d (at least 1)" % G)
+    if g is not None and g.size and (g.min() < 0 or g.max() >= G):
+        raise ValueError("group ids must lie in [0, %d): found %d .. %d" % (G, g.min(), g.max()))
+    st = None
+    if segments is not None:
+        st = _seg_starts(segments)
+        if st.size == 0 or st[0] != 0:
+            raise ValueError("the first segment must start at step 0 (segments = %s)" % (st[:1].tolist(),))
+        if np.any(np.diff(st) <= 0):
+            raise ValueError("segment starts must be strictly increasing")
+        if st[-1] >= T:
+            raise ValueError("segment start %d lies beyond the %d time steps" % (st[-1], T))
+    if isinstance(by_id, (bool, np.bool_)):
+        by_id = int(by_id)
+    if not isinstance(by_id, (int, np.integer)) or by_id not in (0, 1):
+        raise ValueError("by_id=%r (True / False or 1 / 0)" % (by_id,))
+    if isinstance(min_duration, (bool, np.bool_)) or not isinstance(min_duration, (int, np.integer)):
+        raise ValueError("min_duration=%r must be an integer" % (min_duration,))
+    if min_duration < 1 or min_duration > 2 ** 63 - 1:
+        raise ValueError("min_duration=%d (at least 1)" % min_duration)
+    return g, G, st, int(by_id), int(min_duration)
 
 
 def _check_composite(rc):
@@ -950,6 +990,77 @@ class Tracker:
         check(lib().ctk_debug_time_freq(self._h, flag_dev, int(T), int(ny), int(nx), _ptr(g), G, _above(above), counts_dev, int(reps), ms))
         return float(ms[0]), float(ms[1])
 
+    # ---- blocked spells per grid point: events, steps, longest (ctk_spell.hip) -----------------------------------------
+    def spells(self, flag, group=None, ngroups=None, above=0, by_id=True, min_duration=1, segments=None, chunk_steps=0):
+        """(events, steps, longest), uint32 (ngroups, ny, nx), of an int32 (T, ny, nx) host slab (ctk_spells: chunks of `chunk_steps`
+        timesteps pass through the device, 0: about 256 MB each).  A spell is a maximal run of steps with flag > above (by_id: and
+        the same id) inside one segment; it belongs to the group of its first step and counts if it lasts min_duration steps or
+        more.  group None: one group.  segments None: one segment, else the first step of every segment (0 first)."""
+        flag = np.asarray(flag)
+        if flag.ndim != 3:
+            raise ValueError("flag must be (time, lat, lon)")
+        if flag.dtype != np.int32:
+            if flag.dtype.kind not in "iub" or flag.dtype.itemsize > 4 or flag.dtype == np.uint32:
+                raise ValueError("flag must be int32 here (wider ids: spells_cb, or contrack.spells_numpy)")
+        T, ny, nx = flag.shape
+        g, G, st, by, md = _spell_args(T, group, ngroups, segments, by_id, min_duration)
+        flag = np.ascontiguousarray(flag, dtype=np.int32)
+        out = np.empty((3, G, ny, nx), dtype=np.uint32)
+        check(lib().ctk_spells(self._h, flag.ctypes.data, T, ny, nx, _ptr(g), G, _ptr(st), 0 if st is None else st.shape[0], _above(above), by, md,
+                               out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, int(chunk_steps)))
+        return out[0], out[1], out[2]
+
+    def spells_cb(self, reader, shape, group=None, ngroups=None, above=0, by_id=True, min_duration=1, segments=None, chunk_steps=0):
+        """the same with the flag read chunk by chunk: reader(t0, nt, out) fills `out`, an int32 (nt, ny, nx) view of pinned memory,
+        with the timesteps [t0, t0 + nt)"""
+        T, ny, nx = (int(v) for v in shape)
+        g, G, st, by, md = _spell_args(T, group, ngroups, segments, by_id, min_duration)
+        out = np.empty((3, G, ny, nx), dtype=np.uint32)
+        errors = []
+
+        def rd(_user, t0, nt, dst):
+            try:
+                reader(int(t0), int(nt), np.ctypeslib.as_array(C.cast(dst, C.POINTER(C.c_int32)), shape=(nt, ny, nx)))
+                return 0
+            except BaseException as e:                    # an exception must not cross the C frames
+                errors.append(e)
+                return 1
+        rcb = READ_CHUNK_FN(rd)
+        rc = lib().ctk_spells_cb(self._h, T, ny, nx, rcb, None, _ptr(g), G, _ptr(st), 0 if st is None else st.shape[0], _above(above), by, md,
+                                 out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, int(chunk_steps))
+        if errors:
+            raise errors[0]
+        check(rc)
+        return out[0], out[1], out[2]
+
+    def spells_dev(self, flag_dev, T, ny, nx, group=None, ngroups=None, above=0, by_id=True, min_duration=1, segments=None):
+        """ctk_spells_dev on an int32 flag in device memory: (events, steps, longest), uint32 (ngroups, ny, nx)"""
+        T, ny, nx = int(T), int(ny), int(nx)
+        g, G, st, by, md = _spell_args(T, group, ngroups, segments, by_id, min_duration)
+        out = np.empty((3, G, ny, nx), dtype=np.uint32)
+        d = self.malloc(max(out.nbytes, 4))
+        try:
+            check(lib().ctk_spells_dev(self._h, flag_dev, T, ny, nx, _ptr(g), G, _ptr(st), 0 if st is None else st.shape[0], _above(above), by, md,
+                                       d, d.value + out[0].nbytes, d.value + 2 * out[0].nbytes))
+            self.d2h(out, d)
+        finally:
+            self.free(d)
+        return out[0], out[1], out[2]
+
+    def set_spell_debug(self, slice_steps=0):
+        """k_spell experiments and tests: timesteps per slice (0: the library's rule)"""
+        check(lib().ctk_debug_set_spell(self._h, int(slice_steps)))
+
+    def time_spells(self, flag_dev, T, ny, nx, maps_dev, group=None, ngroups=None, above=0, by_id=True, min_duration=1, segments=None, reps=10):
+        """k_spell alone between HIP events (maps_dev: device buffer of 3 * ngroups * ny * nx uint32): (best, mean) ms per launch"""
+        T, ny, nx = int(T), int(ny), int(nx)
+        g, G, st, by, md = _spell_args(T, group, ngroups, segments, by_id, min_duration)
+        ms = (C.c_double * 2)()
+        one = G * ny * nx * 4
+        maps_dev = maps_dev.value if isinstance(maps_dev, C.c_void_p) else int(maps_dev)
+        check(lib().ctk_debug_time_spell(self._h, flag_dev, T, ny, nx, _ptr(g), G, _ptr(st), 0 if st is None else st.shape[0], _above(above), by, md,
+                                         maps_dev, maps_dev + one, maps_dev + 2 * one, int(reps), ms))
+        return float(ms[0]), float(ms[1])
 
     # ---- composite over flagged time steps (the step after README.rst:156-164) ---------------------------------------
     def composite(self, flag, x, group=None, ngroups=None, above=0, skipna=False, chunk_steps=0, resident_f64=False):

@@ -246,6 +246,53 @@ def frequency_numpy(flag, group=None, above=0, percent=True, device=None, chunk_
     return out[0] if group is None else out
 
 
+def spell_duration(steps, events):
+    """steps / events in float64, NaN where events == 0 (numpy's 0 / 0): the mean duration of the spells spells_numpy counted"""
+    steps, events = np.asarray(steps), np.asarray(events)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return steps.astype(np.float64) / events.astype(np.float64)
+
+
+def spells_numpy(flag, group=None, above=0, by_id=True, min_duration=1, segments=None, chunk_steps=None, device=None, shape=None):
+    """blocked spells per grid point of a (time, lat, lon) integer flag slab.  At a grid point, step t continues step t - 1 iff t is
+    not a segment start, both flags are > above and, with by_id, they are the same id.  A spell is a maximal chain of continuing
+    steps; it belongs to the group of its first step (a block that starts on 27 February is a DJF event) and counts if it lasts
+    min_duration steps or more; one cut by the end of the slab or of a segment counts with the length it has.  Returns int64
+    (events, steps, longest): the number of spells, the sum of their durations and the longest one, (G, ny, nx) each -- (ny, nx)
+    without `group` (one id in [0, G) per timestep, any order in time).  The mean duration is spell_duration(steps, events).
+    segments: None, or the first step of every independent time segment (0 first, strictly increasing, below T).  The scan runs
+    on the GPU (ctk_spells); int32 and narrower flags are read as they are, wider ones are converted to int32 chunk by chunk (an id
+    beyond int32 raises ValueError).  chunk_steps: time steps per chunk on their way through the device (None or 0: about 256 MB);
+    with shape=(T, ny, nx) `flag` may be a reader(t0, nt, out) that fills an int32 (nt, ny, nx) buffer (ctk_spells_cb)."""
+    steps = 0 if chunk_steps is None else int(chunk_steps)
+    if steps < 0:
+        raise ValueError("chunk_steps={} (at least 0)".format(steps))
+    _native._above(above)
+    if callable(flag):
+        if shape is None:
+            raise ValueError("a reader needs shape=(T, ny, nx)")
+        T = int(shape[0])
+        ids, G, st, by, md = _native._spell_args(T, group, None, segments, by_id, min_duration)
+        out = _tracker(device).spells_cb(flag, shape, ids, G, above, by, md, st, steps)
+    else:
+        flag = np.asarray(flag)
+        if flag.ndim != 3:
+            raise ValueError("flag must be (time, lat, lon)")
+        if flag.dtype.kind not in "iub":
+            raise ValueError("flag must be an integer field")
+        T = flag.shape[0]
+        ids, G, st, by, md = _native._spell_args(T, group, None, segments, by_id, min_duration)
+        trk = _tracker(device)
+        if flag.dtype.itemsize < 4 or flag.dtype == np.int32:
+            out = trk.spells(flag, ids, G, above, by, md, st, steps)
+        else:
+            def reader(t0, nt, out):
+                out[...] = _int32_chunk(flag[t0:t0 + nt])
+            out = trk.spells_cb(reader, flag.shape, ids, G, above, by, md, st, steps)
+    out = tuple(a.astype(np.int64) for a in out)
+    return tuple(a[0] for a in out) if group is None else out
+
+
 def composite_mean(sum, n):
     """sum / n in float64, NaN where n == 0 (numpy's 0 / 0): the mean of a composite from what composite_numpy returns"""
     sum = np.asarray(sum, dtype=np.float64)
@@ -1729,6 +1776,76 @@ class contrack(object):
                  'history': ' '.join(['Calculated from {} with input attributes:', 'flag > {},', 'groupby = {}.']).format(
                      flag, above, groupby)}
         return self._wrap(da, np.ascontiguousarray(data), out_dims, coords, attrs, name='frequency')
+
+    # ---- blocked spells per grid point: the maps beside the frequency map of a blocking climatology ---------------------------
+    def calc_spells(self, flag='flag', groupby=None, above=0, by_id=True, min_duration=1, segments=None, chunk_steps=None, pool=False):
+        """blocked spells at every grid point: a spell is a maximal run of consecutive time steps with flag > above (by_id: and the
+        same id) that no segment break cuts; it counts if it lasts min_duration steps or more and belongs to the group (groupby:
+        'month', 'season', 'year', ... as calc_frequency) of its FIRST step.  Returns a dict of labelled arrays over the flag
+        variable's own spatial dims, the group dim in the time dim's place: 'events' (number of spells, '1'), 'steps' (sum of their
+        durations), 'longest' (the longest one) -- int64, 'timesteps' -- and 'duration' (steps / events in float64, NaN where
+        there is no event).  Nothing is added to the dataset.  The scan runs on the GPU (spells_numpy).
+        segments: what run_contrack takes -- None, 'gaps' (a break wherever the time axis has a gap: what a DJF-only dataset
+        needs, so that no spell bridges February and December), an array of segment starts, or the name of the member dimension
+        (which changes nothing: its members are segments anyway).  A 4-D flag (time, lat, lon and a
+        member dimension in any order) gives the maps of every member, the member dimension in its place, every member a segment
+        of its own; pool=True pools the members (events and steps add up, longest is the maximum).  pool is ignored for a 3-D flag.
+        chunk_steps: the flag is read slice by slice (`isel`, a chunk that spans two members in two pieces) and passes through
+        chunk-sized device buffers; the slab is never built on the host.  Same numbers."""
+        self._ensure_set_up()
+        da = self.ds[flag]
+        dims, member = self._consumer_dims(flag)
+        names = (self._time_name, self._latitude_name, self._longitude_name)
+        if np.dtype(da.dtype).kind not in "iub":
+            raise ValueError("flag variable {!r} is not an integer field".format(flag))
+        seg_member, starts, T = self._segment_args(flag, da, dims, segments)
+        if seg_member is not None:                               # (the member dimension by name: its members are segments anyway)
+            starts = None
+        ids, uniq = (None, None) if groupby is None else self._group_ids(groupby)
+        M = 1 if member is None else da.shape[dims.index(member)]
+        G = 1 if ids is None else len(uniq)
+        per_member = member is not None and not pool
+        gids = np.zeros(T, dtype=np.int32) if ids is None else ids
+        if per_member:                                           # the library sees group m * G + g
+            gids = (np.arange(M, dtype=np.int32)[:, None] * G + gids[None, :]).reshape(-1)
+        else:
+            gids = np.tile(gids, M)
+        group = gids if (per_member or ids is not None) else None
+        if member is not None:                                   # every member a segment of its own, with the breaks inside it
+            inner = np.zeros(1, dtype=np.int64) if starts is None else starts
+            starts = (np.arange(M, dtype=np.int64)[:, None] * T + inner[None, :]).reshape(-1)
+        if chunk_steps is None:
+            source, shape = self._flat_slab(da, dims, member), None
+        elif member is None:
+            source, shape, _ = self._time_reader(da, dims, integer=True)
+        else:
+            source, shape, _ = self._member_reader(da, dims, member, integer=True)
+        maps = spells_numpy(source, group, above=above, by_id=by_id, min_duration=min_duration, segments=starts, chunk_steps=chunk_steps, shape=shape)
+        maps = [a.reshape((-1,) + a.shape[-2:]) for a in maps]
+        maps.append(spell_duration(maps[1], maps[0]))
+        lead = ((member,) if per_member else ()) + ((groupby,) if groupby is not None else ())
+        have = lead + names[1:]
+        gone = ((self._time_name,) if groupby is None else ()) + ((member,) if member is not None and pool else ())
+        out_dims = tuple(groupby if d == self._time_name else d for d in dims if d not in gone)
+
+        def shaped(a):
+            if per_member:
+                a = a.reshape((M, G) + a.shape[1:])
+            if ids is None:
+                a = a[:, 0] if per_member else a[0]
+            return np.ascontiguousarray(a.transpose([have.index(d) for d in out_dims]))
+        coords = {} if groupby is None else {groupby: uniq}
+        if member in lead:
+            coords[member] = self._dim_values(member, M)
+        for name in (self._latitude_name, self._longitude_name):
+            coords[name] = np.asarray(self.ds[name].data)
+        history = ' '.join(['Calculated from {} with input attributes:', 'flag > {},', 'groupby = {},', 'by_id = {},', 'min_duration = {}.']).format(
+            flag, above, groupby, bool(by_id), min_duration)
+        out = {}
+        for key, a, units in zip(('events', 'steps', 'longest', 'duration'), maps, ('1', 'timesteps', 'timesteps', 'timesteps')):
+            attrs = {'units': units, 'long_name': 'contrack spell ' + key, 'standard_name': 'contrack spell ' + key, 'history': history}
+            out[key] = self._wrap(da, shaped(a), out_dims, coords, attrs, name=key)
+        return out
 
     # ---- composite over the flagged time steps: what a study computes after the frequency map (README.rst:156-164) ----------
     def calc_composite(self, variable, flag='flag', groupby=None, above=0, skipna=False, stat='mean', chunk_steps=None, pool=False, return_count=False):

@@ -375,6 +375,11 @@ struct ctk_handle {
     bool seg_shard_breaks = false;                       // a time-shard call with more than one segment (every rank alike) is running
     // blocking frequency (ctk_freq.hip): counts of the host entries, group ids; experiments (ctk_debug_set_freq)
     DevBuf fq_counts, fq_group;
+    // blocked spells (ctk_spell.hip): the three maps of the host entries, the per-step words (group id, bit 31: segment start) and
+    // their host copy, the two per-pixel carries; the test hook's slice (ctk_debug_set_spell; 0: the rule of spell_slice)
+    DevBuf sp_out, sp_words, sp_carry;
+    std::vector<uint32_t> sp_words_host;
+    int64_t sp_slice_dbg = 0;
     // composite over flagged steps (ctk_composite.hip): float64 sums and uint32 counts of the host entries; the test hook's batch
     // (ctk_debug_set_composite; -1: the rule of ctk_composite_plan), the batch and the workgroups of the last launch
     DevBuf cp_sum, cp_n;
@@ -609,7 +614,7 @@ extern "C" void ctk_destroy(ctk_handle *h)
                       &h->lc_rows, &h->lc_cnt, &h->lc_wlo, &h->lc_whi, &h->lc_w, &h->rv_dmap, &h->rv_dorig, &h->rv_dbox, &h->rv_inex, &h->rv_touch, &h->io_in, &h->io_out,
                       &h->sh_mask_next, &h->sh_send, &h->sh_recv, &h->sh_prev, &h->sh_elist, &h->sh_ovr_slot, &h->sh_ovr_val,
                       &h->sh_amb_list, &h->sh_counts, &h->sh_cl_shared, &h->sh_cl_sent, &h->chunk_vals, &h->lc_work, &h->lc_ovf, &h->lc_ekeys, &h->lc_offs, &h->lc_sw, &h->lc_sp, &h->lc_out, &h->lc_cross, &h->lc_gtab, &h->lc_occ, &h->lc_cp, &h->an_out, &h->an_clim, &h->an_raw, &h->an_idx, &h->an_acc, &h->an_valid, &h->lv_out, &h->lv_tab, &h->sd_parent, &h->sd_tmin, &h->sd_tmax, &h->sd_root, &h->sd_nops, &h->sd_lbox, &h->rv_pstate, &h->ci_bsum, &h->scan_bsum,
-                      &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order, &h->fq_counts, &h->fq_group, &h->cp_sum, &h->cp_n, &h->seg_edge, &h->pc_hist, &h->pc_buf, &h->pf_out, &h->pf_idx, &h->sf_out, &h->sf_idx};
+                      &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order, &h->fq_counts, &h->fq_group, &h->sp_out, &h->sp_words, &h->sp_carry, &h->cp_sum, &h->cp_n, &h->seg_edge, &h->pc_hist, &h->pc_buf, &h->pf_out, &h->pf_idx, &h->sf_out, &h->sf_idx};
     for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (h->h_blob) (void)hipHostFree(h->h_blob);
     if (h->h_small) (void)hipHostFree(h->h_small);
@@ -3878,6 +3883,7 @@ extern "C" int ctk_lifecycle_rows(ctk_handle *h, ctk_life_row *rows, int64_t cap
 #include "ctk_anom.hip"
 #include "ctk_anom_seg.hip"
 #include "ctk_freq.hip"
+#include "ctk_spell.hip"
 #include "ctk_life_stream.hip"
 #include "ctk_pctl.hip"
 #include "ctk_pfield.hip"

@@ -619,6 +619,30 @@ int ctk_frequency(ctk_handle *h, const int32_t *flag, int64_t T, int ny, int nx,
 int ctk_frequency_cb(ctk_handle *h, int64_t T, int ny, int nx, ctk_read_chunk_fn reader, void *reader_user, const int32_t *group, int ngroups,
                      int32_t above, uint32_t *counts /* host */, int64_t chunk_steps);
 
+/* ---- blocked spells per grid point: events, their durations, the longest one (the maps beside the frequency map) ----------------
+ * On the int32 flag slab (T, ny, nx): at pixel p, step t CONTINUES step t-1 iff t is not a segment start, flag[t-1][p] > above and
+ * flag[t][p] > above and, with by_id = 1, flag[t-1][p] == flag[t][p].  A spell is a maximal chain of continuing steps that starts at a
+ * step with flag > above; its duration d is its number of steps and its group is group[onset], the group of its first step, even
+ * if it runs on into another group.  A spell cut by the end of the slab or of a segment counts with the length it has.  Over the
+ * spells with d >= min_duration (>= 1):
+ *   events[g][y][x] = their number,  steps[g][y][x] = the sum of their durations,  longest[g][y][x] = the longest (0: none)
+ * all exact uint32; the caller divides: mean duration = steps / events in float64.  group: T host ints in [0, ngroups), any order
+ * in time, NULL = one group (ngroups = 1).  seg_starts: nseg first steps of independent time segments with the meaning of
+ * ctk_set_segments (0 first, strictly increasing, below T), given with the call; NULL / 0: one segment.  One read of the slab
+ * (k_spell, ctk_spell.hip) whatever the slice and chunk lengths: the result does not depend on them.
+ * ctk_spells_dev: flag in HBM.  ctk_spells / _cb: a host array or a reader callback (ctk_read_chunk_fn, int32 elements) through two
+ * chunk-sized device buffers as ctk_frequency / _cb (chunk_steps = 0: about 256 MB per chunk); a run that is open at the end of a
+ * chunk is carried to the next one in HBM.  T must stay below 2^32 (uint32 durations). */
+int ctk_spells_dev(ctk_handle *h, const int32_t *flag_dev, int64_t T, int ny, int nx, const int32_t *group, int ngroups, const int64_t *seg_starts,
+                   int64_t nseg, int32_t above, int by_id /* 0 / 1 */, int64_t min_duration, uint32_t *events_dev /* [ngroups][ny][nx] */,
+                   uint32_t *steps_dev, uint32_t *longest_dev);
+int ctk_spells(ctk_handle *h, const int32_t *flag, int64_t T, int ny, int nx, const int32_t *group, int ngroups, const int64_t *seg_starts, int64_t nseg,
+               int32_t above, int by_id, int64_t min_duration, uint32_t *events /* host [ngroups][ny][nx] */, uint32_t *steps, uint32_t *longest,
+               int64_t chunk_steps);
+int ctk_spells_cb(ctk_handle *h, int64_t T, int ny, int nx, ctk_read_chunk_fn reader, void *reader_user, const int32_t *group, int ngroups,
+                  const int64_t *seg_starts, int64_t nseg, int32_t above, int by_id, int64_t min_duration, uint32_t *events /* host */, uint32_t *steps,
+                  uint32_t *longest, int64_t chunk_steps);
+
 /* ---- composites: the step after the frequency map of the reference's tutorial (README.rst:156-164) ------------------------------
  * The tutorial ends with the blocking frequency; the composite is what a study computes next: the mean of a field (the tracked
  * anomaly itself, temperature, precipitation) over the time steps at which a grid point is blocked, in all or per group:

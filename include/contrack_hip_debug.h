@@ -158,6 +158,14 @@ int ctk_debug_set_freq(ctk_handle *h, int64_t slice, int nt);
 int ctk_debug_time_freq(ctk_handle *h, const int32_t *flag_dev, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int32_t above,
                         uint32_t *counts_dev, int reps, double *ms2);
 
+/* k_spell experiments and tests (tools/spell_probe.py): timesteps per slice (0: the library's rule) */
+int ctk_debug_set_spell(ctk_handle *h, int64_t slice);
+/* k_spell alone (one chunk of T steps, without k_spell_close) between HIP events: one launch on zeroed maps, then `reps` timed launches
+ * that add to them; ms2 = {best, mean} */
+int ctk_debug_time_spell(ctk_handle *h, const int32_t *flag_dev, int64_t T, int ny, int nx, const int32_t *group, int ngroups, const int64_t *seg_starts,
+                         int64_t nseg, int32_t above, int by_id, int64_t min_duration, uint32_t *events_dev, uint32_t *steps_dev, uint32_t *longest_dev,
+                         int reps, double *ms2);
+
 /* test hook: the per-grid-point quantiles of the last ctk_percentile_* call on this handle, n = the band's pixels ((y1 - y0) * nx, row
  * major), before their mean is taken; an error if no result is held (a ctk_anom_* call or ctk_release_io in between) or n differs */
 int ctk_debug_percentile_values(ctk_handle *h, double *out, int64_t n);
