@@ -1744,7 +1744,9 @@ class Tracker:
         return self._life_rows(int(n.value))
 
     def lifecycle_exact(self, row_idx):
-        """rows of the LAST lifecycle call (indices into its sorted rows) in the reference's own summation orders: LIFE_EXACT"""
+        """rows of the LAST lifecycle call (indices into its sorted rows) in the reference's own summation orders: LIFE_EXACT.
+        Raises ContrackHipError (CTK_E_STATE) when a later call on this Tracker has overwritten or released the slabs of that call:
+        any host-array or streamed entry, release_io, or -- after field=None -- an anomaly call (include/contrack_hip.h)"""
         idx = np.ascontiguousarray(row_idx, dtype=np.int64)
         out = np.empty(len(idx), dtype=LIFE_EXACT)
         check(lib().ctk_lifecycle_exact(self._h, idx.ctypes.data, len(idx), out.ctypes.data))

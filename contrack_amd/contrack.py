@@ -576,6 +576,8 @@ def lifecycle_columns(rows, lat, lon, dates, tracker=None, exact=None, period=No
     only where a result sits on a rounding boundary (fragile_rows).  With the Tracker that produced `rows` at hand (tracker=) those
     rows are re-evaluated ON THE DEVICE in the reference's own summation orders (ctk_lifecycle_exact); a streamed call has done
     that chunk by chunk and hands over exact=(idx, records), the indices into `rows` and their ctk_life_exact records.
+    The Tracker must not have been used for another host-array or streamed call (nor release_io) since it produced `rows`: the
+    slabs are gone then and the library's state error is raised -- never the unrefined values.
 
     period: the slab is a member dimension flattened to steps m * period + t; `dates` are the labels of ONE member's steps, the
     column 'Member' (the position m) is added and the rows are sorted by (Flag, Member, Date)."""

@@ -137,7 +137,7 @@ static int pctl_slab(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx,
 {
     if (x_host) {
         const size_t bytes = (size_t)T * (size_t)ny * (size_t)nx * sizeof(VT);
-        CTKCHK(ensure(h, h->io_in, bytes));
+        CTKCHK(claim_io(h, h->io_in, bytes));
         HIPCHK(hipMemcpyAsync(h->io_in.p, x_host, bytes, hipMemcpyHostToDevice, h->stream));
         *x_dev = (const VT *)h->io_in.p;
     } else {
@@ -176,8 +176,7 @@ static int anom_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx,
     hipStream_t s = h->stream;
     const int64_t npix = (int64_t)ny * nx;
     const size_t esz = sizeof(VT), n = (size_t)T * (size_t)npix;
-    CTKCHK(ensure(h, h->io_in, n * esz));
-    CTKCHK(ensure(h, h->an_out, n * esz));
+    CTKCHK(claim_io(h, h->io_in, n * esz));
     CTKCHK(ensure(h, h->an_clim, (size_t)ngroups * npix * esz));
     h->an_pct_n = -1;                                                  // (an_raw is overwritten below)
     CTKCHK(ensure(h, h->an_raw, (size_t)ngroups * npix * esz));
@@ -201,6 +200,7 @@ static int anom_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx,
     if (clim_out) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipMemcpy(clim_out, h->an_clim.p, (size_t)ngroups * npix * esz, hipMemcpyDeviceToHost)); }
     if (anom_out || keep_resident) {
         h->an_T = -1; h->an_gen++;                                     // the resident slab (if any) is being overwritten
+        CTKCHK(ensure(h, h->an_out, n * esz));                         // (only here: a climatology-only call leaves an_out alone)
         const int tseg = 32;
         k_anom<VT><<<dim3(gx, (unsigned)((T + tseg - 1) / tseg)), 256, 0, s>>>((const VT *)h->io_in.p, (const VT *)h->an_clim.p, d_grp, T, npix, smooth, tseg,
                                                                              (VT *)h->an_out.p);

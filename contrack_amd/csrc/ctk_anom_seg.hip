@@ -170,7 +170,6 @@ static int anom_seg_dev(ctk_handle *h, const VT *x_dev, int64_t T, int ny, int n
     h->an_launches = 0;
     const int64_t npix = (int64_t)ny * nx;
     const size_t esz = sizeof(VT), n = (size_t)T * (size_t)npix, cb = (size_t)ngroups * npix * esz;
-    CTKCHK(ensure(h, h->an_out, n * esz));
     CTKCHK(ensure(h, h->an_clim, cb));
     h->an_pct_n = -1;                                                  // (an_raw is overwritten below)
     CTKCHK(ensure(h, h->an_raw, cb));
@@ -196,6 +195,7 @@ static int anom_seg_dev(ctk_handle *h, const VT *x_dev, int64_t T, int ny, int n
         anom_window_valid(starts, nseg, T, smooth, valid);
         HIPCHK(hipMemcpy(h->an_valid.p, valid.data(), (size_t)T, hipMemcpyHostToDevice));
         h->an_T = -1; h->an_gen++;                                     // the resident slab (if any) is being overwritten
+        CTKCHK(ensure(h, h->an_out, n * esz));                         // (only here: a climatology-only call leaves an_out alone)
         CTKCHK(launch_anom_seg<VT>(h, x_dev, 0, 0, T, (const VT *)h->an_clim.p, d_grp, P<uint8_t>(h->an_valid), npix, smooth, 0, T, (VT *)h->an_out.p));
         HIPCHK(hipStreamSynchronize(s));
         if (keep_resident) { h->an_T = T; h->an_ny = ny; h->an_nx = nx; h->an_f64 = sizeof(VT) == 8; }
@@ -216,7 +216,7 @@ static int anom_seg_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int
     CTKCHK(anom_seg_args("ctk_anom_seg", h, T, ny, nx, group, ngroups, window, smooth, starts, nseg));
     HIPCHK(hipSetDevice(h->device));
     const size_t bytes = (size_t)T * (size_t)ny * (size_t)nx * sizeof(VT);
-    CTKCHK(ensure(h, h->io_in, bytes));
+    CTKCHK(claim_io(h, h->io_in, bytes));
     HIPCHK(hipMemcpy(h->io_in.p, x_host, bytes, hipMemcpyHostToDevice));
     return anom_seg_dev<VT>(h, (const VT *)h->io_in.p, T, ny, nx, group, ngroups, window, smooth, clim_in, anom_out, clim_out, keep_resident, starts, nseg);
 }

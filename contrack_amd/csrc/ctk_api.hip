@@ -268,6 +268,9 @@ struct ctk_handle {
     // run_lifecycle reductions
     DevBuf lc_rows, lc_cnt, lc_wlo, lc_whi, lc_w, lc_work, lc_ovf, lc_ekeys, lc_offs, lc_sw, lc_sp, lc_out, lc_cross, lc_gtab, lc_occ, lc_cp;
     const int32_t *lc_flag = nullptr; const void *lc_field = nullptr;       // slabs of the last ctk_lifecycle_* call (for the exact rows)
+    // ... which live in io_out / io_in (or an_out) after a host-array call: lc_own 1, lc_own 2 with the resident anomaly slab as the field;
+    // then ctk_lifecycle_exact reads them only while io_gen (and an_gen) are what the call left.  0: the caller's own device pointers
+    int lc_own = 0; uint64_t lc_io_gen = 0, lc_an_gen = 0;
     bool lc_f64 = false; int64_t lc_T = 0; int lc_ny = 0, lc_nx = 0;
     // which path the time steps of the last ctk_lifecycle_* call took (ctk_debug_lifecycle_path); lc_path_T < 0: no finished call
     int64_t lc_path_T = -1; CtkLifePlan lc_plan = {0, 0, 0, 0, 0};
@@ -311,6 +314,7 @@ struct ctk_handle {
     int lv_xcd_dbg = -1;                           // ctk_debug_set_level: xcd_chunk mode of the launches (-1: ctk_level_plan's)
     int64_t lv_grid_dbg = 0, lv_grid = 0;          // ... a lower cap on the workgroups of a launch (0: none); workgroups of the last launch
     DevBuf io_in, io_out;                          // device copies of host-array calls (ctk_track_f32 / _f64)
+    uint64_t io_gen = 0;                           // bumped by claim_io and ctk_release_io: WHOSE data io_in / io_out hold
     // streaming entries (ctk_track_stream_*): the slab passes through two chunk-sized device buffers per direction
     struct StreamIO *sio = nullptr;                // set for the duration of a streaming call: where the slab comes from
     hipStream_t copy_stream = nullptr;
@@ -498,6 +502,13 @@ struct ActiveComm {                        // scope of ctk_handle::active_comm
     ActiveComm(ctk_handle *h_, ctk_comm *c) : h(h_) { h->active_comm = (c && c->world > 1) ? c : nullptr; }
     ~ActiveComm() { h->active_comm = nullptr; }
 };
+
+// every entry that writes io_in / io_out takes them through here: what an earlier call left in them is no longer that call's
+static int claim_io(ctk_handle *h, DevBuf &b, size_t need)
+{
+    h->io_gen++;
+    return ensure(h, b, need);
+}
 
 template <typename T>
 T *P(const DevBuf &b) { return (T *)b.p; }
@@ -3075,7 +3086,7 @@ static int deliver_runs(ctk_handle *h, int persistence, int32_t *flag, int *wrot
     for (size_t bi = 0; bi < nb; bi++) {
         if (!cx[bi]) continue;
         const RleBlock &c = blocks[bi];
-        CTKCHK(ensure(h, h->io_out, (size_t)c.nt * plane * 4));
+        CTKCHK(claim_io(h, h->io_out, (size_t)c.nt * plane * 4));
         h->rle_out = false;
         const int rc = launch_relabel(h, persistence, P<int32_t>(h->io_out), true, nullptr, c.t0, c.nt);
         h->rle_out = true;
@@ -3107,7 +3118,7 @@ static int track_to_host(ctk_handle *h, const void *a_dev, bool f64, int64_t T, 
     int rc;
     for (int attempt = 0; attempt < 2; attempt++) {
         // the dense result lives in the handle (grow-only); with the run transfer only the blocks of complex components ever need it
-        CTKCHK(ensure(h, h->io_out, want_runs ? 256 : std::max<size_t>(n * 4, 256)));
+        CTKCHK(claim_io(h, h->io_out, want_runs ? 256 : std::max<size_t>(n * 4, 256)));
         f_dev = P<int32_t>(h->io_out);
         h->stats[CTK_S_RLE_OUT] = 0;
         h->rle_out = want_runs;
@@ -3147,7 +3158,7 @@ static int track_host_impl(ctk_handle *h, const void *anom, bool f64, int64_t T,
     void *a_dev = nullptr;
     if (n) {
         // the device copy of the caller's slab lives in the handle (grow-only), like every other buffer
-        CTKCHK(ensure(h, h->io_in, n * esz));
+        CTKCHK(claim_io(h, h->io_in, n * esz));
         a_dev = h->io_in.p;
     }
     const double e0 = now_ms();
@@ -3174,8 +3185,8 @@ static int stream_setup(ctk_handle *h, size_t in_bytes, size_t out_bytes, bool p
     for (int b = 0; b < 2; b++)
         for (hipEvent_t *e : {&h->ev_h2d[b], &h->ev_thr[b], &h->ev_rel[b], &h->ev_d2h[b]})
             if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    if (in_bytes) CTKCHK(ensure(h, h->io_in, 2 * in_bytes));
-    if (out_bytes) CTKCHK(ensure(h, h->io_out, 2 * out_bytes));
+    if (in_bytes) CTKCHK(claim_io(h, h->io_in, 2 * in_bytes));
+    if (out_bytes) CTKCHK(claim_io(h, h->io_out, 2 * out_bytes));
     if (pinned) {
         if (in_bytes > h->pin_in_cap) {
             for (int b = 0; b < 2; b++) { if (h->pin_in[b]) (void)hipHostFree(h->pin_in[b]); h->pin_in[b] = nullptr; }
@@ -3423,6 +3434,7 @@ extern "C" int ctk_release_io(ctk_handle *h)
     for (DevBuf *b : {&h->io_in, &h->io_out, &h->an_out, &h->an_raw, &h->lv_out}) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
     h->an_T = -1; h->an_gen++; h->an_pct_n = -1;
     h->lv_T = -1; h->lv_gen++;
+    h->io_gen++; h->lc_flag = nullptr; h->lc_field = nullptr;          // (the exact rows of a lifecycle call read those slabs)
     if (h->bounce) { h->bounce->destroy(); delete h->bounce; h->bounce = nullptr; }
     if (h->rle) { h->rle->crew.shutdown(); h->rle->destroy(); delete h->rle; h->rle = nullptr; }
     stream_teardown(h);
@@ -3698,8 +3710,9 @@ static void life_reset(ctk_handle *h, int64_t T)
     h->lx_idx.clear(); h->lx_rec.clear();
 }
 
+// own: where the slabs live (ctk_handle::lc_own); the host-array entry passes 1 or 2 after its uploads
 static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void *field_dev, bool f64, int64_t T, int ny, int nx, const float *wrow,
-                              int64_t *nrows)
+                              int64_t *nrows, int own = 0)
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
     if (T < 0 || ny < 1 || nx < 1 || !wrow || (T > 0 && (!flag_dev || !field_dev)))
@@ -3716,6 +3729,7 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
     h->lc_plan = r.plan;
     r.cap = std::max<size_t>(h->lc_rows.cap / sizeof(CtkLifeRowDev), (size_t)T * 16 + 1024);
     h->lc_flag = flag_dev; h->lc_field = field_dev; h->lc_f64 = f64; h->lc_T = T; h->lc_ny = ny; h->lc_nx = nx;
+    h->lc_own = own; h->lc_io_gen = h->io_gen; h->lc_an_gen = h->an_gen;
     int rc = life_launch(h, r);
     if (rc == CTK_OK) rc = life_settle(h, r);
     h->lc_attempts = r.attempts; h->lc_given_up = r.given_up; h->lc_fb_launches = r.fb_launches;
@@ -3761,16 +3775,16 @@ static int lifecycle_host_impl(ctk_handle *h, const int32_t *flag, const void *f
     const size_t n = (size_t)T * ny * nx, esz = f64 ? 8 : 4;
     void *f_dev = nullptr, *v_dev = nullptr;
     if (n) {
-        CTKCHK(ensure(h, h->io_out, n * 4));                     // the flag slab (the tracker's own result buffer, if it ran here)
+        CTKCHK(claim_io(h, h->io_out, n * 4));                     // the flag slab (the tracker's own result buffer, if it ran here)
         f_dev = h->io_out.p;
         HIPCHK(hipMemcpy(f_dev, flag, n * 4, hipMemcpyHostToDevice));
         if (field) {
-            CTKCHK(ensure(h, h->io_in, n * esz));
+            CTKCHK(claim_io(h, h->io_in, n * esz));
             v_dev = h->io_in.p;
             HIPCHK(hipMemcpy(v_dev, field, n * esz, hipMemcpyHostToDevice));
         } else v_dev = h->an_out.p;
     }
-    return lifecycle_dev_impl(h, (const int32_t *)f_dev, v_dev, f64, T, ny, nx, wrow, nrows);
+    return lifecycle_dev_impl(h, (const int32_t *)f_dev, v_dev, f64, T, ny, nx, wrow, nrows, field ? 1 : 2);
 }
 
 extern "C" int ctk_lifecycle_f32_dev(ctk_handle *h, const int32_t *flag_dev, const float *field_dev, int64_t T, int ny, int nx, const float *wrow, int64_t *nrows)
@@ -3797,6 +3811,8 @@ extern "C" int ctk_lifecycle_exact(ctk_handle *h, const int64_t *row_idx, int64_
     if (!h || n < 0 || (n > 0 && (!row_idx || !out))) return ctk_set_error(CTK_E_INVALID, "ctk_lifecycle_exact: bad arguments");
     if (n == 0) return CTK_OK;
     if (h->lc_streamed) return ctk_set_error(CTK_E_STATE, "ctk_lifecycle_exact: the last call was streamed, its slabs are gone (ctk_lifecycle_stream_exact holds the rows it picked)");
+    if (h->lc_own && (h->lc_io_gen != h->io_gen || (h->lc_own == 2 && h->lc_an_gen != h->an_gen)))
+        return ctk_set_error(CTK_E_STATE, "ctk_lifecycle_exact: a later call on this handle overwrote or released the slabs of the last ctk_lifecycle_* call; run it again first");
     if (!h->lc_flag || !h->lc_field) return ctk_set_error(CTK_E_STATE, "ctk_lifecycle_exact needs a ctk_lifecycle_* call first");
     HIPCHK(hipSetDevice(h->device));
     std::vector<CtkLifeKey> keys((size_t)n);

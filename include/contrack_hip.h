@@ -413,8 +413,12 @@ int ctk_lifecycle_rows(ctk_handle *h, ctk_life_row *rows, int64_t cap);
  * boundary (a centre of mass that is an integer up to rounding, a value at the edge of two decimals).  The caller picks those rows
  * (indices into the sorted rows) and gets them in the reference's own orders: np.sum (pairwise) for weight_grid[mask] and
  * weight_grid[mask] * variable[mask] (contrack.py:874-875), np.bincount (sequential, raster order of the rolled plane) inside
- * ndimage.center_of_mass (:886 / :892).  Valid until the next ctk_lifecycle_* call on the handle; for the *_dev entries the
- * caller's device slabs must still be alive. */
+ * ndimage.center_of_mass (:886 / :892).  Valid until the next ctk_lifecycle_* call on the handle, and only while the slabs of that
+ * call are still what it left: the host-array entries keep theirs in the handle's staging buffers (the field = NULL form reads the
+ * resident anomaly slab), so any later entry that takes a host array or streams through the handle, any ctk_anom_* call after a
+ * field = NULL call, and ctk_release_io make ctk_lifecycle_exact return CTK_E_STATE ("a later call ... overwrote or released the
+ * slabs") until the next resident ctk_lifecycle_* call.  Entries that work on the caller's device pointers alone (*_dev) do not.
+ * For the *_dev entries the slabs stay the caller's: they must be alive and unchanged when ctk_lifecycle_exact runs. */
 typedef struct ctk_life_exact {
     double area, swv, s, sy, sx;       /* np.sum(w), np.sum(w * v), sum p, sum p * y, sum p * x'   (p = v * w) */
 } ctk_life_exact;
