@@ -5,6 +5,7 @@ same 'flag' output variable as steidani/ConTrack's contrack.contrack); `track_nu
 entry underneath it, `frequency_numpy` the blocking frequency (README.rst:159-160 of the reference) of its `flag`,
 `spells_numpy` / `spell_duration` the blocked spells per grid point (events, their durations, the longest one),
 `composite_numpy` / `composite_mean` the mean of a field over the flagged time steps,
+`centred_numpy` / `lifecycle_bins` the composite of a field in a window that moves with the blocks' centres, per life-cycle age,
 `anomalies_numpy` the climatology and anomalies that produce its input (over time segments, optionally streamed),
 `percentile_field_numpy` the per-grid-point percentile threshold field per group of timesteps,
 `std_field_numpy` the per-grid-point standard-deviation threshold field per group of timesteps,
@@ -16,7 +17,7 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name in ("contrack", "track_numpy", "frequency_numpy", "spells_numpy", "spell_duration", "composite_numpy", "composite_mean", "anomalies_numpy", "percentile_field_numpy", "std_field_numpy", "level_mean_numpy", "level_weights", "row_weights", "prepare_thresholds"):
+    if name in ("contrack", "track_numpy", "frequency_numpy", "spells_numpy", "spell_duration", "composite_numpy", "composite_mean", "centred_numpy", "centred_stamps", "lifecycle_bins", "anomalies_numpy", "percentile_field_numpy", "std_field_numpy", "level_mean_numpy", "level_weights", "row_weights", "prepare_thresholds"):
         import importlib
         _m = importlib.import_module(".contrack", __name__)     # (`from . import contrack` would ask __getattr__ for 'contrack' first)
         return getattr(_m, name)

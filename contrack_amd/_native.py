@@ -48,6 +48,8 @@ EXPORTS = [
     "ctk_level_mean_stream_cb", "ctk_resident_level_mean", "ctk_resident_level_mean_generation", "ctk_anom_seg_resident", "ctk_debug_level_plan", "ctk_debug_level_form", "ctk_debug_time_level_mean", "ctk_debug_set_level",
     "ctk_composite_f32_dev", "ctk_composite_f64_dev", "ctk_composite_f32", "ctk_composite_f64", "ctk_composite_cb",
     "ctk_debug_composite_plan", "ctk_debug_set_composite", "ctk_debug_composite_launch", "ctk_debug_time_composite",
+    "ctk_centred_f32_dev", "ctk_centred_f64_dev", "ctk_centred_f32", "ctk_centred_f64", "ctk_centred_cb",
+    "ctk_debug_centred_plan", "ctk_debug_set_centred", "ctk_debug_centred_launch", "ctk_debug_time_centred",
 ]
 
 READ_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)       # ctk_read_chunk_fn
@@ -150,6 +152,16 @@ def composite_plan(elem_bytes, npix, unroll=-1):
     return dict(unroll=int(v[0]), blocks=int(v[1]), grid=int(v[2]))
 
 
+def centred_plan(elem_bytes, nbins, hy, hx, max_bin=0, kept=None, form=-1, unroll=-1, threads=-1):
+    """ctk_debug_centred_plan: what ctk_centred_plan (csrc/ctk_forms.h) decides for a centred launch whose longest bin has max_bin
+    stamps and whose bins together have `kept` (None: max_bin, one bin), as a dict (form: 0 plain / 1 fed, unroll: the batch of stamps of a lane or a feeder wave, threads: cells of a bin per
+    workgroup, parts: workgroups per bin, blocks, grid); form, unroll, threads: what debug_set_centred would force; no handle, no GPU"""
+    v = np.zeros(6, dtype=np.int64)
+    check(lib().ctk_debug_centred_plan(int(elem_bytes), int(nbins), int(hy), int(hx), int(max_bin), int(max_bin if kept is None else kept), int(form),
+                                       int(unroll), int(threads), v.ctypes.data))
+    return dict(form=int(v[5]), unroll=int(v[0]), threads=int(v[1]), parts=int(v[2]), blocks=int(v[3]), grid=int(v[4]))
+
+
 def forms(T, ny, nx, nt=None, aligned16=True, async_passes=24, n_cus=256, **query):
     """ctk_debug_forms: what the library's launch rules (csrc/ctk_forms.h) decide for these numbers, as a dict; no handle, no GPU.
     nt defaults to T; every other field of FormQuery defaults to 0."""
@@ -210,6 +222,16 @@ def lib():
     L.ctk_debug_composite_launch.argtypes = [p, p]
     L.ctk_debug_time_composite.argtypes = [p, p, p, i32, i64, i32, i32, p, i32, C.c_int32, i32, p, p, i32, C.POINTER(dbl)]
     L.ctk_debug_time_freq.argtypes = [p, p, i64, i32, i32, p, i32, C.c_int32, p, i32, C.POINTER(dbl)]
+    stamp_args = [i64, p, p, p, p, i32, i32, i32, i32, i32]                   # R, t, row, col, bin, nbins, hy, hx, wrap, skipna
+    for fn in (L.ctk_centred_f32_dev, L.ctk_centred_f64_dev):
+        fn.argtypes = [p, p, i64, i32, i32] + stamp_args + [p, p, i32]
+    for fn in (L.ctk_centred_f32, L.ctk_centred_f64):
+        fn.argtypes = [p, p, i64, i32, i32] + stamp_args + [p, p, i64]
+    L.ctk_centred_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p] + stamp_args + [p, p, i64]
+    L.ctk_debug_centred_plan.argtypes = [i32, i32, i32, i32, i64, i64, i32, i32, i32, p]
+    L.ctk_debug_set_centred.argtypes = [p, i32, i32, i32]
+    L.ctk_debug_centred_launch.argtypes = [p, p]
+    L.ctk_debug_time_centred.argtypes = [p, p, i32, i64, i32, i32] + stamp_args + [p, p, i32, i32, C.POINTER(dbl)]
     L.ctk_shard_label2d.argtypes = [p, p, i64, i32, i32, p, i32, p, i32]
     L.ctk_shard_label2d_f64.argtypes = [p, p, i64, i32, i32, p, i32, p, i32]
     L.ctk_shard_halo_size.argtypes = [p, C.POINTER(sz)]
@@ -459,6 +481,36 @@ def _check_composite(rc):
     if rc in (-1, -4):
         raise InvalidArgumentError("libcontrack_hip rc=%d: %s" % (rc, lib().ctk_last_error().decode("utf-8", "replace")))
     check(rc)
+
+
+def _stamps(t, row, col, bin, nbins, hy, hx):
+    """the stamp arguments of the centred entries as the library takes them: (R, t int64, row, col, bin int32, nbins, hy, hx).  bin
+    None: one bin.  The library checks the values against the grid; here only what the conversions could hide."""
+    arrs = []
+    for name, a in (("t", t), ("row", row), ("col", col), ("bin", np.zeros(np.shape(t), np.int32) if bin is None else bin)):
+        a = np.asarray(a)
+        if a.ndim != 1:
+            raise ValueError("%s must be one-dimensional" % name)
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError("%s must be integers (dtype %s)" % (name, a.dtype))
+        lim = np.iinfo(np.int64 if name == "t" else np.int32)
+        if a.size and (int(a.max()) > lim.max or int(a.min()) < lim.min):
+            raise ValueError("%s does not fit %s" % (name, "int64" if name == "t" else "int32"))
+        arrs.append(np.ascontiguousarray(a, dtype=np.int64 if name == "t" else np.int32))
+    R = arrs[0].shape[0]
+    if any(a.shape[0] != R for a in arrs):
+        raise ValueError("t, row, col and bin must have one length (%s)" % ", ".join(str(a.shape[0]) for a in arrs))
+    if nbins is None:
+        nbins = 1 if bin is None else (max(int(arrs[3].max()) + 1, 1) if R else 1)
+    for name, v in (("nbins", nbins), ("hy", hy), ("hx", hx)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s=%r must be an integer" % (name, v))
+        if abs(int(v)) > np.iinfo(np.int32).max:
+            raise ValueError("%s=%d does not fit int32" % (name, v))
+    nbins, hy, hx = int(nbins), int(hy), int(hx)
+    if nbins < 1 or hy < 0 or hx < 0 or nbins * (2 * hy + 1) * (2 * hx + 1) >= 2 ** 31:
+        raise InvalidArgumentError("nbins=%d hy=%d hx=%d: nbins >= 1, half widths >= 0 and nbins * (2 hy + 1) * (2 hx + 1) < 2^31" % (nbins, hy, hx))
+    return (R,) + tuple(arrs) + (nbins, hy, hx)
 
 
 def _field_dtype(x):
@@ -1164,6 +1216,114 @@ class Tracker:
         ms = (C.c_double * 2)()
         check(lib().ctk_debug_time_composite(self._h, flag_dev, x_dev, int(bool(f64)), int(T), int(ny), int(nx), _ptr(g), G, _above(above),
                                              int(bool(skipna)), sum_dev, n_dev, int(reps), ms))
+        return float(ms[0]), float(ms[1])
+
+    # ---- block-centred composite (the step after README.rst:198-228) --------------------------------------------------
+    def centred(self, x, t, row, col, bin, nbins, hy, hx, wrap=True, skipna=False, chunk_steps=0, resident_f64=False, shape=None):
+        """(sum, n): for the stamps r in the order given (t non-decreasing) with bin[r] >= 0, sum[bin[r], j + hy, i + hx] += the
+        float64 value of x[t[r], row[r] + j, col[r] + i] for j in -hy..hy, i in -hx..hx -- rows outside the grid not counted, columns
+        wrapped (wrap) or not counted, with skipna NaN not counted -- and n how many there were, of a float32 / float64 (T, ny, nx)
+        field in host memory (ctk_centred_f32 / _f64: chunks of `chunk_steps` time steps pass through the device, 0: about 256 MB
+        each; chunks without stamps and latitude rows no window touches do not travel).  x None: the anomaly slab
+        anomalies(keep_resident=True) left on the device (resident_f64: its type; shape: the (T, ny, nx) the caller expects of it,
+        None: whatever it has).  bin None:
+        one bin.  Returns float64 and uint32 (nbins, 2 hy + 1, 2 hx + 1)."""
+        if x is None:
+            f64 = bool(resident_f64)
+            T, ny, nx = (int(v) for v in shape) if shape is not None else self.resident_anom_shape()
+        else:
+            x = np.asarray(x)
+            if x.ndim != 3:
+                raise ValueError("the field must be (time, lat, lon)")
+            x = np.ascontiguousarray(x, dtype=_field_dtype(x.dtype))
+            T, ny, nx = x.shape
+            f64 = x.dtype == np.float64
+        R, t, row, col, bin, nbins, hy, hx = _stamps(t, row, col, bin, nbins, hy, hx)
+        s = np.empty((nbins, 2 * hy + 1, 2 * hx + 1), dtype=np.float64)
+        n = np.empty(s.shape, dtype=np.uint32)
+        fn = lib().ctk_centred_f64 if f64 else lib().ctk_centred_f32
+        _check_composite(fn(self._h, _ptr(x), T, ny, nx, R, _ptr(t), _ptr(row), _ptr(col), _ptr(bin), nbins, hy, hx, int(bool(wrap)), int(bool(skipna)),
+                            s.ctypes.data, n.ctypes.data, int(chunk_steps)))
+        return s, n
+
+    def resident_anom_shape(self):
+        """(T, ny, nx) of the anomaly slab kept on the device; (1, 1, 1) when there is none (an entry that needs it then raises the
+        library's state error)"""
+        res = self.resident_anom()
+        return (1, 1, 1) if res is None else res[:3]
+
+    def centred_cb(self, field_reader, shape, dtype, t, row, col, bin, nbins, hy, hx, wrap=True, skipna=False, chunk_steps=0):
+        """the same with the field read chunk by chunk: field_reader(t0, nt, out) fills a (nt, ny, nx) view of pinned memory of
+        `dtype` (float32 / float64) with the time steps [t0, t0 + nt); it is not called for a chunk none of whose steps carries a
+        stamp with bin >= 0.  field_reader None: the resident anomaly slab of `dtype`."""
+        T, ny, nx = (int(v) for v in shape)
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("the field must be float32 or float64")
+        R, t, row, col, bin, nbins, hy, hx = _stamps(t, row, col, bin, nbins, hy, hx)
+        s = np.empty((nbins, 2 * hy + 1, 2 * hx + 1), dtype=np.float64)
+        n = np.empty(s.shape, dtype=np.uint32)
+        errors = []
+        ctype = C.c_float if dt == np.float32 else C.c_double
+
+        def rd(_user, t0, nt, dst):
+            try:
+                field_reader(int(t0), int(nt), np.ctypeslib.as_array(C.cast(dst, C.POINTER(ctype)), shape=(nt, ny, nx)))
+                return 0
+            except BaseException as e:                    # an exception must not cross the C frames
+                errors.append(e)
+                return 1
+        xcb = READ_CHUNK_FN(rd) if field_reader is not None else C.cast(None, READ_CHUNK_FN)
+        rc = lib().ctk_centred_cb(self._h, dt.itemsize, T, ny, nx, xcb, None, R, _ptr(t), _ptr(row), _ptr(col), _ptr(bin), nbins, hy, hx, int(bool(wrap)),
+                                  int(bool(skipna)), s.ctypes.data, n.ctypes.data, int(chunk_steps))
+        if errors:
+            raise errors[0]
+        _check_composite(rc)
+        return s, n
+
+    def centred_dev(self, x_dev, T, ny, nx, t, row, col, bin, nbins, hy, hx, wrap=True, skipna=False, f64=False, sum_dev=None, n_dev=None,
+                    accumulate=False):
+        """ctk_centred_*_dev on a float32 (f64: float64) field in device memory; x_dev None: the resident anomaly slab.  sum_dev /
+        n_dev None: (sum, n) are returned; else they are written to (accumulate: continued from) those device buffers of nbins *
+        (2 hy + 1) * (2 hx + 1) float64 / uint32 and None is returned."""
+        R, t, row, col, bin, nbins, hy, hx = _stamps(t, row, col, bin, nbins, hy, hx)
+        fn = lib().ctk_centred_f64_dev if f64 else lib().ctk_centred_f32_dev
+        args = (self._h, x_dev, int(T), int(ny), int(nx), R, _ptr(t), _ptr(row), _ptr(col), _ptr(bin), nbins, hy, hx, int(bool(wrap)), int(bool(skipna)))
+        if (sum_dev is None) != (n_dev is None):
+            raise ValueError("sum_dev and n_dev go together")
+        if sum_dev is not None:
+            _check_composite(fn(*args, sum_dev, n_dev, int(bool(accumulate))))
+            return None
+        s = np.empty((nbins, 2 * hy + 1, 2 * hx + 1), dtype=np.float64)
+        n = np.empty(s.shape, dtype=np.uint32)
+        ds, dn = self.malloc(max(s.nbytes, 8)), self.malloc(max(n.nbytes, 4))
+        try:
+            _check_composite(fn(*args, ds, dn, 0))
+            self.d2h(s, ds)
+            self.d2h(n, dn)
+        finally:
+            self.free(ds)
+            self.free(dn)
+        return s, n
+
+    def debug_set_centred(self, form=-1, unroll=-1, threads=-1):
+        """test hook for the following centred launches: the form (0 plain, 1 fed) and, for the plain form, the widest batch of
+        stamps and the cells per workgroup; -1 the rule (ctk_centred_plan)"""
+        check(lib().ctk_debug_set_centred(self._h, int(form), int(unroll), int(threads)))
+
+    def debug_centred_launch(self):
+        """(form, batch, cells per workgroup, workgroups) of the last centred launch; (0, 0, 0, 0): none yet"""
+        v = np.zeros(4, dtype=np.int64)
+        check(lib().ctk_debug_centred_launch(self._h, v.ctypes.data))
+        return int(v[3]), int(v[0]), int(v[1]), int(v[2])
+
+    def time_centred(self, x_dev, T, ny, nx, t, row, col, bin, nbins, hy, hx, sum_dev, n_dev, wrap=True, skipna=False, f64=False, floor=False, reps=5):
+        """the centred kernel alone (the rule's form, or the one debug_set_centred forces) between HIP events (sum_dev / n_dev: device buffers of nbins * (2 hy + 1) * (2 hx + 1) float64 / uint32):
+        (best, mean) ms per launch.  floor: the plain unordered gather of the same windows instead, which keeps nothing"""
+        R, t, row, col, bin, nbins, hy, hx = _stamps(t, row, col, bin, nbins, hy, hx)
+        ms = (C.c_double * 2)()
+        check(lib().ctk_debug_time_centred(self._h, x_dev, int(bool(f64)), int(T), int(ny), int(nx), R, _ptr(t), _ptr(row), _ptr(col), _ptr(bin), nbins, hy, hx,
+                                           int(bool(wrap)), int(bool(skipna)), sum_dev, n_dev, int(bool(floor)), int(reps), ms))
         return float(ms[0]), float(ms[1])
 
     # ---- calc_anom / percentile threshold on the device ---------------------------------------------------------

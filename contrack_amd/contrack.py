@@ -345,6 +345,114 @@ def composite_numpy(flag, x, group=None, above=0, skipna=False, chunk_steps=None
     return (s[0], n[0]) if group is None else (s, n)
 
 
+def centred_stamps(t, row, col, bin=None):
+    """the stamps of a block-centred composite as the library takes them: (t int64, row, col, bin int32) sorted STABLY by t -- the
+    given order is kept among equal t -- which is the order of the additions.  bin None: one bin (all zeros)."""
+    t = np.asarray(t)
+    if t.ndim != 1:
+        raise ValueError("t must be one-dimensional")
+    arrs = [t, np.asarray(row), np.asarray(col), np.zeros(t.shape, dtype=np.int32) if bin is None else np.asarray(bin)]
+    for name, a in zip(("t", "row", "col", "bin"), arrs):
+        if a.shape != t.shape:
+            raise ValueError("t, row, col and bin must have one length: {} has shape {}, t {}".format(name, a.shape, t.shape))
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError("{} must be integers (dtype {})".format(name, a.dtype))
+    order = np.argsort(arrs[0], kind="stable")
+    return tuple(a[order] for a in arrs)
+
+
+def centred_numpy(x, t, row, col, bin=None, nbins=None, half=(0, 0), wrap=True, skipna=False, chunk_steps=None, device=None, shape=None, dtype=None):
+    """the composite of a float field in a window that moves with a list of stamps: (sum, n), both (nbins, 2 hy + 1, 2 hx + 1) with
+    half = (hy, hx) in grid points.  For every stamp r with bin[r] >= 0, in time order (stamps of one time step in the order
+    given), and every j in -hy..hy, i in -hx..hx, sum[bin[r], j + hy, i + hx] += float64(x[t[r], row[r] + j, col[r] + i]) and n
+    += 1; a row outside the grid is not counted (no step over a pole), a column outside it is wrapped (wrap, the default: longitude
+    is periodic) or not counted, with skipna a NaN is not counted.  composite_mean(sum, n) is the mean.  The sums run on the GPU
+    (ctk_centred_*), are float64 added in that fixed order and so the same bits whatever chunk_steps: time steps per chunk on the
+    field's way through the device (None or 0: about 256 MB); chunks without stamps and latitude rows no window touches do not
+    travel.  x: an array (np.memmap included; float64 stays, everything else is taken as float32), a reader reader(t0, nt, out)
+    with shape=(T, ny, nx) and dtype -- it is not called for a chunk without stamps -- or None: the anomaly slab calc_anom left
+    on the device (`dtype` its type).  bin None: one bin; nbins None: max(bin) + 1."""
+    steps = 0 if chunk_steps is None else int(chunk_steps)
+    hy, hx = half
+    if callable(x) and (shape is None or dtype is None):
+        raise ValueError("a reader needs shape=(T, ny, nx) and the field's dtype")
+    t, row, col, bin = centred_stamps(t, row, col, bin)
+    if nbins is None:
+        nbins = max(int(bin.max()) + 1, 1) if bin.size else 1
+    trk = _tracker(device)
+    if callable(x):
+        return trk.centred_cb(x, shape, np.dtype(dtype), t, row, col, bin, nbins, hy, hx, wrap, skipna, steps)
+    if x is None:
+        return trk.centred(None, t, row, col, bin, nbins, hy, hx, wrap, skipna, steps, resident_f64=np.dtype(dtype if dtype is not None else np.float32) == np.float64,
+                           shape=shape)
+    x = x if isinstance(x, np.memmap) else np.asarray(x)
+    if x.ndim != 3:
+        raise ValueError("the field must be (time, lat, lon)")
+    if isinstance(x, np.memmap) and (x.dtype != _native._field_dtype(x.dtype) or not x.flags.c_contiguous):
+        def reader(t0, nt, out, slab=x):                   # (converted chunk by chunk, never as a whole)
+            out[...] = slab[t0:t0 + nt]
+        return trk.centred_cb(reader, x.shape, _native._field_dtype(x.dtype), t, row, col, bin, nbins, hy, hx, wrap, skipna, steps)
+    return trk.centred(x, t, row, col, bin, nbins, hy, hx, wrap, skipna, steps)
+
+
+def lifecycle_bins(block, step, by, nbins=None, max_age=None):
+    """(bin int32, nbins): the life-cycle age bin of every row of a life-cycle frame (or a selection of it), for centred_numpy.
+    block: a hashable key per row (the Flag, or (Flag, member) as a sequence of tuples or an (R, 2) array); step: the row's
+    position on the time axis.  Per block, among the rows given: age = step - the block's first step, duration = last step - first
+    step + 1.
+      by='age'         bin = age (time steps since onset); rows beyond max_age get -1 (dropped).  max_age defaults to nbins - 1 if
+                       nbins is given, else to the largest age present; nbins = max_age + 1
+      by='to_lysis'    bin = the block's last step - step (time steps before decay), capped the same way
+      by='normalized'  bin = (age * nbins) // duration in integers: nbins equal parts of the life cycle (nbins is required; a block
+                       shorter than nbins steps leaves bins empty)
+      by=None          one bin
+      by an integer array: taken as given; negative means dropped; nbins defaults to max + 1"""
+    step = np.asarray(step)
+    if step.ndim != 1 or (step.size and step.dtype.kind not in "iu"):
+        raise ValueError("step must be a one-dimensional integer array")
+    step = step.astype(np.int64)
+    R = step.shape[0]
+    if by is None:
+        return np.zeros(R, dtype=np.int32), 1
+    if not isinstance(by, str):
+        b = np.asarray(by)
+        if b.shape != step.shape or (b.size and b.dtype.kind not in "iu"):
+            raise ValueError("by as an array must hold one integer per row")
+        if nbins is None:
+            nbins = max(int(b.max()) + 1, 1) if R else 1
+        if R and (int(b.max()) >= nbins or int(b.min()) < np.iinfo(np.int32).min):
+            raise ValueError("a bin of {} with nbins = {}".format(int(b.max()), nbins))
+        return b.astype(np.int32), int(nbins)
+    if by not in ("age", "to_lysis", "normalized"):
+        raise ValueError("by must be None, 'age', 'to_lysis', 'normalized' or an integer array, not {!r}".format(by))
+    keys = block.tolist() if isinstance(block, np.ndarray) else list(block)
+    keys = [tuple(k) if isinstance(k, (list, tuple, np.ndarray)) else k for k in keys]
+    if len(keys) != R:
+        raise ValueError("block has {} keys, step {} rows".format(len(keys), R))
+    seen = {}
+    code = np.array([seen.setdefault(k, len(seen)) for k in keys], dtype=np.int64)
+    first = np.full(len(seen), np.iinfo(np.int64).max, dtype=np.int64)
+    last = np.full(len(seen), np.iinfo(np.int64).min, dtype=np.int64)
+    np.minimum.at(first, code, step)
+    np.maximum.at(last, code, step)
+    age = step - first[code] if R else step
+    if by == "normalized":
+        if nbins is None or int(nbins) < 1:
+            raise ValueError("by='normalized' needs nbins >= 1")
+        nbins = int(nbins)
+        b = (age * nbins) // (last[code] - first[code] + 1) if R else age
+        return b.astype(np.int32), nbins
+    b = age if by == "age" else (last[code] - step if R else step)
+    if max_age is None:
+        max_age = int(nbins) - 1 if nbins is not None else (int(b.max()) if R else 0)
+    max_age = int(max_age)
+    if max_age < 0 or max_age >= np.iinfo(np.int32).max:
+        raise ValueError("max_age = {}".format(max_age))
+    if nbins is not None and int(nbins) != max_age + 1:
+        raise ValueError("nbins = {} but max_age + 1 = {}".format(nbins, max_age + 1))
+    return np.where(b > max_age, -1, b).astype(np.int32), max_age + 1
+
+
 def anomalies_numpy(x, group, ngroups=None, window=1, smooth=1, clim=None, segments=None, chunk_steps=None, device=None):
     """calc_clim / calc_anom on a (time, lat, lon) float slab: `group` holds one id in [0, G) per timestep (G = ngroups, or
     max(group) + 1), the climatology is the mean per group smoothed over `window` groups (or `clim`, (G, ny, nx)), the anomaly is
@@ -568,7 +676,7 @@ def fragile_rows(rows):
     return np.nonzero(fragile)[0]
 
 
-def lifecycle_columns(rows, lat, lon, dates, tracker=None, exact=None, period=None):
+def lifecycle_columns(rows, lat, lon, dates, tracker=None, exact=None, period=None, indices=False):
     """ctk_life_row records -> the columns of the reference's frame (contrack.py:876-906), rows sorted by (Flag, Date):
     dict of arrays Flag, Date, Longitude, Latitude, Intensity, Size.
 
@@ -580,7 +688,10 @@ def lifecycle_columns(rows, lat, lon, dates, tracker=None, exact=None, period=No
     slabs are gone then and the library's state error is raised -- never the unrefined values.
 
     period: the slab is a member dimension flattened to steps m * period + t; `dates` are the labels of ONE member's steps, the
-    column 'Member' (the position m) is added and the rows are sorted by (Flag, Member, Date)."""
+    column 'Member' (the position m) is added and the rows are sorted by (Flag, Member, Date).
+
+    indices: three more int64 columns -- Step, the position on the time axis (of the member's own), and Row, Col, the grid indices
+    whose coordinates the truncated Latitude and Longitude came from."""
     nx, ny = len(lon), len(lat)
     if (rows["shift"] == -2).any():
         raise ValueError("attempt to get argmax of an empty sequence")                                  # np.argmax(np.diff(.)), :883
@@ -617,6 +728,10 @@ def lifecycle_columns(rows, lat, lon, dates, tracker=None, exact=None, period=No
                 Intensity=np.round(intensity, 2), Size=np.round(area, 2))                               # round(np.float64, 2), :899-900
     if period is not None:
         cols["Member"] = (rows["t"] // int(period)).astype(np.int64)
+    if indices:
+        cols["Step"] = np.asarray(step, dtype=np.int64)
+        cols["Row"] = np.where(iy < 0, iy + ny, iy)                                                     # (Python indexing, as lat[iy])
+        cols["Col"] = (ix + shift) % nx
     # the library returns (label, t) order -- (label, member, step of the member) for a flattened member dimension; the reference
     # sorts by the date STRING, which differs when the time axis is not increasing
     if any(a > b for a, b in zip(dates, dates[1:])):
@@ -644,18 +759,18 @@ def _int32_chunk(part):
     return part
 
 
-def lifecycle_numpy(flag, field, wrow, lat, lon, dates, chunk_steps=None, device=None, shape=None, dtype=None, period=None):
+def lifecycle_numpy(flag, field, wrow, lat, lon, dates, chunk_steps=None, device=None, shape=None, dtype=None, period=None, indices=False):
     """the columns of run_lifecycle's frame (lifecycle_columns) for a (time, lat, lon) integer flag slab and a float field of the
     same shape.  chunk_steps None: both slabs go to the device whole (field None: the anomaly slab resident there, `dtype` its
     type).  Otherwise they pass through chunk-sized device buffers, that many time steps at a time (0: about 256 MB of field):
     arrays (np.memmap included; flags wider than int32 are narrowed chunk by chunk, an id beyond int32 raises ValueError from the
     chunk that holds it) or readers reader(t0, nt, out) with shape=(T, ny, nx) and the field's dtype; the rounding-boundary rows
-    are re-evaluated while their chunk is on the device.  period: see lifecycle_columns."""
+    are re-evaluated while their chunk is on the device.  period, indices: see lifecycle_columns."""
     trk = _tracker(device)
     if chunk_steps is None:
         flag = _int32_chunk(flag)
         rows = trk.lifecycle(flag, None, wrow, resident_f64=np.dtype(dtype) == np.float64) if field is None else trk.lifecycle(flag, field, wrow)
-        return lifecycle_columns(rows, lat, lon, dates, tracker=trk, period=period)
+        return lifecycle_columns(rows, lat, lon, dates, tracker=trk, period=period, indices=indices)
     if callable(flag):
         flag_source = flag
     else:
@@ -674,7 +789,7 @@ def lifecycle_numpy(flag, field, wrow, lat, lon, dates, chunk_steps=None, device
             field = field.astype(np.float32, copy=False)
         dtype = field.dtype
     rows, idx, ex = trk.lifecycle_stream(flag_source, field, wrow, shape=shape, dtype=dtype, chunk_steps=int(chunk_steps), pick=fragile_rows)
-    return lifecycle_columns(rows, lat, lon, dates, exact=(idx, ex), period=period)
+    return lifecycle_columns(rows, lat, lon, dates, exact=(idx, ex), period=period, indices=indices)
 
 
 INT64_FLAG_FROM = 2 ** 31 - 2       # elements from which scipy.ndimage.label (and the reference's 'flag') switch to int64
@@ -1943,7 +2058,7 @@ class contrack(object):
                 return [pd.Timestamp(v).strftime('%Y%m%d_%H') for v in vals]
             return [str(v) for v in vals]
 
-    def run_lifecycle(self, flag, variable, chunk_steps=None):
+    def run_lifecycle(self, flag, variable, chunk_steps=None, indices=False):
         """Intensity, size and centre of mass of every flagged contour at every time step.
 
         flag: name of the flag variable (output of run_contrack); variable: field used for intensity and centre of
@@ -1960,7 +2075,10 @@ class contrack(object):
         member, Date) -- the reference's order for ids that are unique over the members, as run_contrack's are.
         chunk_steps (extension): both variables are read slice by slice (`isel`, a chunk that spans two members in two pieces) and
         pass through chunk-sized device buffers, that many time steps at a time (0: about 256 MB of field); neither slab is built
-        on the host or the device.  Flags wider than int32 are narrowed chunk by chunk; an id beyond int32 raises ValueError."""
+        on the host or the device.  Flags wider than int32 are narrowed chunk by chunk; an id beyond int32 raises ValueError.
+        indices=True (extension): three more int64 columns after those -- 'Step', the row's position on the time axis, and 'Row',
+        'Col', the grid indices whose coordinates the truncated 'Latitude' and 'Longitude' came from: what
+        calc_centred_composite takes its windows from."""
         import pandas as pd
         logger.info("\nRun Lifecycle \n########### \n    flag:    {}\n    variable:    {}".format(flag, variable))
         self._ensure_set_up()
@@ -1983,7 +2101,7 @@ class contrack(object):
                 field = field.astype(np.float32, copy=False)
             # (the anomaly slab calc_anom left in HBM: only the flags cross PCIe)
             resident = self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, field.shape, field.dtype == np.float64)
-            cols = lifecycle_numpy(flags, None if resident else field, wrow, lat, lon, self._time_labels(), dtype=field.dtype, period=period)
+            cols = lifecycle_numpy(flags, None if resident else field, wrow, lat, lon, self._time_labels(), dtype=field.dtype, period=period, indices=indices)
         else:
             if member is None:
                 fread, shape, _ = self._time_reader(fda, fdims, integer=True)
@@ -1992,12 +2110,109 @@ class contrack(object):
                 fread, shape, _ = self._member_reader(fda, fdims, member, integer=True)
                 vread = self._member_reader(vda, vdims, member)[0]
             # (a variable of any other type than float64 becomes float32 in the copy into the chunk buffer, as in the resident call)
-            cols = lifecycle_numpy(fread, vread, wrow, lat, lon, self._time_labels(), chunk_steps=chunk_steps, shape=shape, dtype=vtype, period=period)
+            cols = lifecycle_numpy(fread, vread, wrow, lat, lon, self._time_labels(), chunk_steps=chunk_steps, shape=shape, dtype=vtype, period=period,
+                                   indices=indices)
         columns = ['Flag', 'Date', 'Longitude', 'Latitude', 'Intensity', 'Size']
         if member is not None:
             cols[member] = self._dim_values(member, fda.shape[fdims.index(member)])[cols.pop("Member")]
             columns.append(member)
+        if indices:
+            columns += ['Step', 'Row', 'Col']
         return pd.DataFrame(cols, columns=columns)
+
+    def calc_centred_composite(self, variable, frame, half_width=(20., 40.), by=None, nbins=None, max_age=None, stat='mean', skipna=False, wrap=True,
+                               chunk_steps=None, return_count=False):
+        """mean (stat='mean') or sum (stat='sum') of `variable` in a window that moves with the blocks' centres, per bin of the life
+        cycle: the composite in the block's own frame of reference.  frame: run_lifecycle's DataFrame or any row selection of it (a
+        sector, a season, the long-lived blocks); every row is one stamp, the window of +-half_width = (degrees latitude, degrees
+        longitude) around its centre at its time step (hy = round(degrees / grid spacing) grid points).  With the columns 'Step',
+        'Row', 'Col' of run_lifecycle(indices=True) the centres are taken as they are; without them 'Date' is looked up among the
+        time labels (which must be unique) and 'Latitude' / 'Longitude' go to the nearest grid index -- the reference's int()
+        truncation of those two makes that up to one degree off the centre that was computed.
+        by: None (one bin); 'age' (time steps since the block's first row), 'to_lysis' (time steps before its last), 'normalized'
+        (nbins equal parts of its life cycle) as lifecycle_bins computes them among the rows GIVEN, with nbins / max_age; the name
+        of an integer column of the frame; or an integer array, one bin per row (negative: the row is dropped).
+        A row outside the grid's latitudes is not counted (no step over a pole); wrap=True, the default, treats longitude as
+        periodic, as run_contrack does.  skipna: a NaN value is not counted; without it one makes its cell NaN.  The sums are
+        float64 and added in a fixed order on the GPU (centred_numpy: time order, rows of one time step in the frame's order), so
+        the result is reproducible bit for bit; a cell no window reached gives NaN (mean) or 0 (sum).
+        Returns a labelled float64 array, not added to the dataset, with dims (by if it is a string else 'bin', 'rel_' + latitude
+        name, 'rel_' + longitude name), the offsets in degrees as coordinates, the variable's units; return_count=True: (composite,
+        n), n the uint32 count per cell.
+        A 4-D variable (a member dimension) needs the frame's member column; the members are taken one after the other.
+        chunk_steps: the variable is read slice by slice (`isel`) and passes through chunk-sized device buffers; chunks without
+        stamps are not read.  Same bits.  When `variable` is the anomaly calc_anom left in HBM, no field bytes are uploaded."""
+        self._ensure_set_up()
+        if stat not in ('mean', 'sum'):
+            raise ValueError("stat must be 'mean' or 'sum', not {!r}".format(stat))
+        vda = self.ds[variable]
+        dims, member = self._consumer_dims(variable, what="variable")
+        T = vda.shape[dims.index(self._time_name)]
+        lat = np.asarray(self.ds[self._latitude_name].data)
+        lon = np.asarray(self.ds[self._longitude_name].data)
+        have = list(frame.columns)
+        column = lambda name: np.asarray(frame[name])                              # noqa: E731
+        if all(c in have for c in ('Step', 'Row', 'Col')):
+            step, row, col = (column(c).astype(np.int64) for c in ('Step', 'Row', 'Col'))
+        else:
+            labels = self._time_labels()
+            where = {d: i for i, d in enumerate(labels)}
+            if len(where) != len(labels):
+                raise ValueError("the time labels are not unique: the frame's 'Date' does not name a time step (use run_lifecycle(indices=True))")
+            try:
+                step = np.array([where[str(d)] for d in column('Date')], dtype=np.int64)
+            except KeyError as e:
+                raise ValueError("the frame's Date {} is not a time label of the dataset".format(e))
+            row = np.abs(lat[None, :].astype(np.float64) - column('Latitude').astype(np.float64)[:, None]).argmin(axis=1).astype(np.int64)
+            col = np.abs(lon[None, :].astype(np.float64) - column('Longitude').astype(np.float64)[:, None]).argmin(axis=1).astype(np.int64)
+        t = step
+        block = column('Flag') if 'Flag' in have else np.zeros(len(step), dtype=np.int64)
+        if member is not None:
+            if member not in have:
+                raise ValueError("the variable {!r} has the member dimension {!r}: the frame needs that column".format(variable, member))
+            M = vda.shape[dims.index(member)]
+            index = {v: m for m, v in enumerate(self._dim_values(member, M).tolist())}
+            try:
+                m_of = np.array([index[v] for v in column(member).tolist()], dtype=np.int64)
+            except KeyError as e:
+                raise ValueError("the frame's {} {} is not a value of that dimension".format(member, e))
+            t = m_of * T + step                                                    # the flattening the other consumers use
+            block = list(zip(block.tolist(), m_of.tolist()))
+        if isinstance(by, str) and by not in ('age', 'to_lysis', 'normalized'):
+            if by not in have:
+                raise ValueError("by = {!r} is neither 'age', 'to_lysis', 'normalized' nor a column of the frame".format(by))
+            bins, nb = lifecycle_bins(block, step, column(by), nbins=nbins)
+        else:
+            bins, nb = lifecycle_bins(block, step, by, nbins=nbins, max_age=max_age)
+        dlat, dlon = (float(np.atleast_1d(d)[0]) for d in (self._dlat, self._dlon))
+        half = (int(round(float(half_width[0]) / dlat)), int(round(float(half_width[1]) / dlon)))
+        vtype = _native._field_dtype(vda.dtype)
+        if chunk_steps is None:
+            field = self._flat_slab(vda, dims, member).astype(vtype, copy=False)
+            resident = self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, field.shape, vtype == np.float64)
+            s, n = centred_numpy(None if resident else field, t, row, col, bins, nb, half, wrap=wrap, skipna=skipna, shape=field.shape, dtype=vtype)
+        else:
+            vread, shape, _ = self._time_reader(vda, dims) if member is None else self._member_reader(vda, dims, member)
+            s, n = centred_numpy(vread, t, row, col, bins, nb, half, wrap=wrap, skipna=skipna, chunk_steps=chunk_steps, shape=shape, dtype=vtype)
+        out = composite_mean(s, n) if stat == 'mean' else s
+        bdim = by if isinstance(by, str) else 'bin'
+        out_dims = (bdim, 'rel_' + self._latitude_name, 'rel_' + self._longitude_name)
+        step_lat = float(lat[1] - lat[0]) if len(lat) > 1 else dlat
+        step_lon = float(lon[1] - lon[0]) if len(lon) > 1 else dlon
+        coords = {bdim: np.arange(nb), out_dims[1]: np.arange(-half[0], half[0] + 1) * step_lat, out_dims[2]: np.arange(-half[1], half[1] + 1) * step_lon}
+        attrs = {'long_name': 'contrack centred composite', 'standard_name': 'contrack centred composite',
+                 'history': ' '.join(['Calculated from {} with input attributes:', 'stamps = {} of {} rows,', 'half_width = {},', 'by = {},', 'stat = {},',
+                                      'skipna = {},', 'wrap = {}.']).format(
+                     variable, int(np.count_nonzero(bins >= 0)), len(bins), tuple(half_width), by if by is None or isinstance(by, str) else 'bins given', stat,
+                     skipna, wrap)}
+        units = getattr(vda, 'attrs', {}).get('units')
+        if units is not None:
+            attrs['units'] = units
+        res = self._wrap(vda, out, out_dims, coords, attrs, name='centred_composite')
+        if not return_count:
+            return res
+        cattrs = {'long_name': 'contrack centred composite count', 'units': '1', 'history': attrs['history']}
+        return res, self._wrap(vda, n, out_dims, coords, cattrs, name='count')
 
     # ---- utility (contrack.py:912-949) ---------------------------------------------------------------------------
     def greatcircle_dist(self, lon1, lat1, lon2, lat2):

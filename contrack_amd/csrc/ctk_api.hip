@@ -388,6 +388,11 @@ struct ctk_handle {
     // (ctk_debug_set_composite; -1: the rule of ctk_composite_plan), the batch and the workgroups of the last launch
     DevBuf cp_sum, cp_n;
     int cp_unroll_dbg = -1, cp_unroll = 0; int64_t cp_grid = 0;
+    // block-centred composite (ctk_centred.hip): sums and counts of the host entries; the stamps in bin order with the bin offsets of
+    // every chunk; the test hook's form, batch and workgroup width (ctk_debug_set_centred; -1: the rule of ctk_centred_plan), those of
+    // the last launch and its workgroups
+    DevBuf ce_sum, ce_n, ce_idx;
+    int ce_form_dbg = -1, ce_unroll_dbg = -1, ce_threads_dbg = -1, ce_form = 0, ce_unroll = 0, ce_threads = 0; int64_t ce_grid = 0;
     // percentile per group (ctk_pctl.hip): histograms per (day, distinct prefix); ranks, prefixes, lists, ids; band sweeps of the last call
     DevBuf pc_hist, pc_buf;
     int64_t pc_sweeps = 0;
@@ -625,7 +630,7 @@ extern "C" void ctk_destroy(ctk_handle *h)
                       &h->lc_rows, &h->lc_cnt, &h->lc_wlo, &h->lc_whi, &h->lc_w, &h->rv_dmap, &h->rv_dorig, &h->rv_dbox, &h->rv_inex, &h->rv_touch, &h->io_in, &h->io_out,
                       &h->sh_mask_next, &h->sh_send, &h->sh_recv, &h->sh_prev, &h->sh_elist, &h->sh_ovr_slot, &h->sh_ovr_val,
                       &h->sh_amb_list, &h->sh_counts, &h->sh_cl_shared, &h->sh_cl_sent, &h->chunk_vals, &h->lc_work, &h->lc_ovf, &h->lc_ekeys, &h->lc_offs, &h->lc_sw, &h->lc_sp, &h->lc_out, &h->lc_cross, &h->lc_gtab, &h->lc_occ, &h->lc_cp, &h->an_out, &h->an_clim, &h->an_raw, &h->an_idx, &h->an_acc, &h->an_valid, &h->lv_out, &h->lv_tab, &h->sd_parent, &h->sd_tmin, &h->sd_tmax, &h->sd_root, &h->sd_nops, &h->sd_lbox, &h->rv_pstate, &h->ci_bsum, &h->scan_bsum,
-                      &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order, &h->fq_counts, &h->fq_group, &h->sp_out, &h->sp_words, &h->sp_carry, &h->cp_sum, &h->cp_n, &h->seg_edge, &h->pc_hist, &h->pc_buf, &h->pf_out, &h->pf_idx, &h->sf_out, &h->sf_idx};
+                      &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order, &h->fq_counts, &h->fq_group, &h->sp_out, &h->sp_words, &h->sp_carry, &h->cp_sum, &h->cp_n, &h->ce_sum, &h->ce_n, &h->ce_idx, &h->seg_edge, &h->pc_hist, &h->pc_buf, &h->pf_out, &h->pf_idx, &h->sf_out, &h->sf_idx};
     for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (h->h_blob) (void)hipHostFree(h->h_blob);
     if (h->h_small) (void)hipHostFree(h->h_small);
@@ -3906,6 +3911,7 @@ extern "C" int ctk_lifecycle_rows(ctk_handle *h, ctk_life_row *rows, int64_t cap
 #include "ctk_std.hip"
 #include "ctk_level.hip"
 #include "ctk_composite.hip"
+#include "ctk_centred.hip"
 
 // device-memory helpers for a ctypes host
 // ------------------------------------------------------------------------------------------------

@@ -686,3 +686,67 @@ inline int64_t ctk_composite_chunk(int64_t chunk_steps, int64_t T, size_t plane_
     int64_t c = chunk_steps > 0 ? chunk_steps : (int64_t)(((size_t)256 << 20) / std::max<size_t>(plane_bytes, 1));
     return std::min<int64_t>(std::max<int64_t>(c, 1), T);
 }
+
+// ------------------------------------------------------------------------------------------------
+// block-centred composite (ctk_centred.hip): one lane per cell (j, i) of the window for ALL stamps of the workgroup's bin -- a bin's
+// stamps are never split, the float64 sums are added in stamp order.  There are few cells (a 41 x 81 window is 3321) and each is a
+// chain of dependent adds behind gathers.  Two forms:
+//   plain (k_centred): the lane gathers for itself, a batch of stamps whose loads it has in flight together -- 128 bytes of values per
+//     lane, 32 float32 or 16 float64.  The workgroups are single waves while there are few of them (every CU gets one before any gets
+//     two); past CTK_CENTRED_SMALL_GROUPS of them the chip is full and they are 256 cells wide.
+//   fed (k_centred_fed): 64 cells per workgroup of 16 waves; 15 feeder waves gather 15 x 32 bytes per cell into LDS, the owner wave adds
+//     them in order while the feeders fetch the next 120 (60) stamps: what k_life_exact does for its chains.
+// Which one: the plain form's time is its longest chain -- the longest bin, one scalar and one vector memory latency per batch of 32
+// stamps, 5.8 us measured, 181 ns per stamp -- unless the chip is full, and then 0.076 ns per (wave of cells x stamp).  The fed form
+// walks a bin at 23 ns per stamp, and costs 0.082 ns per (wave of cells x stamp) plus 3.3 ns per workgroup: sixteen waves for 64
+// cells are a poor trade when a bin has a dozen stamps.  The rule takes the smaller of the two estimates (MI355X, float32, both probe
+// workloads with one bin, 16 bins and ~400 bins: the estimate picks the faster form in all six, profiles/NOTES.md); a bin shorter
+// than CTK_CENTRED_FED_STAMPS -- little more than one round of the feeders -- stays with the plain form.
+// ------------------------------------------------------------------------------------------------
+#define CTK_CENTRED_THREADS_MIN 64
+#define CTK_CENTRED_THREADS_MAX 256
+#define CTK_CENTRED_UNROLL_MAX 32              // stamps whose loads of a lane are in flight together (then 16, 8, 4, 2, 1 for the rest)
+#define CTK_CENTRED_BATCH_BYTES 128            // of values per lane in flight
+#define CTK_CENTRED_SMALL_GROUPS 2048          // 256 CUs x 8 workgroups
+#define CTK_CENTRED_GRID_MAX 0xffffffll
+#define CTK_CENTRED_FED_WAVES 16               // one owner and 15 feeders
+#define CTK_CENTRED_FED_BYTES 32               // of values per feeder lane and round: 8 float32 or 4 float64 stamps
+#define CTK_CENTRED_FED_STAMPS 128
+#define CTK_CENTRED_PLAIN_NS_STAMP 181.0       // per stamp of the longest bin
+#define CTK_CENTRED_PLAIN_NS_WORK 0.076        // per (wave of cells x stamp)
+#define CTK_CENTRED_FED_NS_STAMP 23.0
+#define CTK_CENTRED_FED_NS_WORK 0.082
+#define CTK_CENTRED_FED_NS_GROUP 3.3           // per workgroup
+struct CtkCentredPlan {
+    int form;                     // 0 plain, 1 fed
+    int unroll;                   // plain: the widest batch of stamps a lane loads before it adds the first (a power of two); fed: stamps per feeder and round
+    int threads;                  // cells of one bin per workgroup (64, 128 or 256; fed: 64)
+    int64_t parts;                // workgroups per bin
+    int64_t blocks;               // nbins * parts, walked by ...
+    unsigned grid;                // ... this many workgroups
+};
+// wcells: (2 hy + 1) * (2 hx + 1); max_bin: the stamps of the longest bin; kept: the stamps of all bins.  form, unroll, threads: a
+// test's choice (ctk_debug_set_centred; unroll and threads rounded down to a power of two and clamped, and without effect on the fed
+// form); -1 the rule
+inline CtkCentredPlan ctk_centred_plan(int elem_bytes, int64_t nbins, int64_t wcells, int64_t max_bin, int64_t kept, int form = -1, int unroll = -1,
+                                       int threads = -1)
+{
+    CtkCentredPlan p = {};
+    const int64_t per_bin = (wcells + CTK_CENTRED_THREADS_MIN - 1) / CTK_CENTRED_THREADS_MIN, waves = nbins * per_bin;
+    const double work = (double)kept * (double)per_bin;
+    const double plain_ns = std::max((double)max_bin * CTK_CENTRED_PLAIN_NS_STAMP, work * CTK_CENTRED_PLAIN_NS_WORK);
+    const double fed_ns = std::max((double)max_bin * CTK_CENTRED_FED_NS_STAMP, work * CTK_CENTRED_FED_NS_WORK + (double)waves * CTK_CENTRED_FED_NS_GROUP);
+    p.form = form >= 0 ? (form != 0) : (max_bin >= CTK_CENTRED_FED_STAMPS && fed_ns < plain_ns);
+    int u = CTK_CENTRED_BATCH_BYTES / std::max(elem_bytes, 4);
+    if (unroll > 0) { u = 1; while (u * 2 <= unroll && u * 2 <= CTK_CENTRED_UNROLL_MAX) u <<= 1; }
+    int th = CTK_CENTRED_THREADS_MIN;
+    if (waves > CTK_CENTRED_SMALL_GROUPS) th = CTK_CENTRED_THREADS_MAX;
+    if (threads > 0) { th = CTK_CENTRED_THREADS_MIN; while (th * 2 <= threads && th * 2 <= CTK_CENTRED_THREADS_MAX) th <<= 1; }
+    if (p.form) { u = CTK_CENTRED_FED_BYTES / std::max(elem_bytes, 4); th = CTK_CENTRED_THREADS_MIN; }
+    p.unroll = std::min(u, CTK_CENTRED_UNROLL_MAX);
+    p.threads = th;
+    p.parts = (wcells + th - 1) / th;
+    p.blocks = nbins * p.parts;
+    p.grid = (unsigned)std::min<int64_t>(p.blocks, CTK_CENTRED_GRID_MAX);
+    return p;
+}

@@ -679,6 +679,48 @@ int ctk_composite_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */,
                      ctk_read_chunk_fn field_reader, void *field_user, const int32_t *group, int ngroups, int32_t above, int skipna, double *sum,
                      uint32_t *n, int64_t chunk_steps);
 
+/* ---- block-centred composites: the step after the tracks of the reference's tutorial (README.rst:198-228) ------------------------
+ * The tutorial ends with the tracks and the genesis points of the life-cycle frame; a blocking study then composites in the block's
+ * own frame of reference: a field in a window that moves with the block's centre, averaged over the blocks per day since onset, per
+ * day before decay or per fifth of the life cycle.  On a field x (T, ny, nx), float32 or float64, and R stamps in struct-of-arrays
+ * form -- t[r] (int64), row[r], col[r], bin[r] (int32) -- with nbins bins, half widths hy >= 0 and hx >= 0 in grid points, wrap (0 / 1)
+ * and skipna (0 / 1), the outputs sum[nbins][2 hy + 1][2 hx + 1] (float64, from +0.0) and n[...] (uint32) of the same shape are
+ *   for r = 0 .. R-1, RISING (the order of the arrays as given):
+ *       if bin[r] < 0: continue                                     -- a stamp the caller dropped
+ *       for j in -hy..hy, i in -hx..hx:
+ *           y = row[r] + j;   if y < 0 or y >= ny: continue         -- no step over a pole: not counted
+ *           c = col[r] + i;   wrap: c = c mod nx;   else if c < 0 or c >= nx: continue
+ *           v = (double)x[t[r]][y][c]                               -- a plain conversion, denormals kept
+ *           if skipna and v is NaN: continue
+ *           sum[bin[r]][j + hy][i + hx] = sum[...] + v;   n[...] += 1
+ * Without skipna a NaN makes its cell NaN.  The caller divides: mean = sum / n in float64, NaN where n == 0.  A cell meets the stamps
+ * of its bin in the order given and they are never split over threads, so the sums are reproducible bit for bit whatever the kernel
+ * form or the chunking (k_centred, ctk_centred.hip).
+ * Arguments: t must be non-decreasing (which keeps the order of the additions independent of the chunking), 0 <= t < T,
+ * 0 <= row < ny, 0 <= col < nx, bin < nbins, nbins >= 1, R < 2^32, nbins * (2 hy + 1) * (2 hx + 1) < 2^31: CTK_E_INVALID; with wrap
+ * 2 hx + 1 <= nx (a wider window would count a column twice): CTK_E_RANGE.  R == 0 is valid and gives zeros.
+ * ctk_centred_*_dev: the slab in HBM, the stamps host arrays; x_dev == NULL: the anomaly slab ctk_anom_* left resident on this handle
+ * (its shape and type must be the call's: CTK_E_STATE otherwise).  accumulate = 1 continues from the given accumulators (a caller's
+ * own pieces: the order of the additions is then the order of the calls), 0 starts from zero.
+ * ctk_centred_f32 / _f64: the field a host array; it passes through two chunk-sized device buffers, chunk k+1 uploaded while chunk k
+ * is reduced (chunk_steps = 0: about 256 MB of field per chunk).  A chunk none of whose time steps carries a stamp with bin >= 0 is
+ * neither read nor uploaded, and of the others only the latitude rows [min(row) - hy, max(row) + hy] of that chunk's stamps, clipped
+ * to the grid, travel, as one strided copy per chunk.  x == NULL: the resident anomaly slab, no field bytes cross PCIe.
+ * ctk_centred_cb: a reader (ctk_read_chunk_fn: field elements of elem_bytes, whole planes), contract and threading rules of
+ * ctk_composite_cb's; it is not called for a chunk without stamps; field_reader == NULL: the resident anomaly slab of elem_bytes. */
+int ctk_centred_f32_dev(ctk_handle *h, const float *x_dev, int64_t T, int ny, int nx, int64_t R, const int64_t *t /* host [R] */, const int32_t *row,
+                        const int32_t *col, const int32_t *bin, int nbins, int hy, int hx, int wrap, int skipna,
+                        double *sum_dev /* [nbins][2 hy + 1][2 hx + 1] */, uint32_t *n_dev, int accumulate /* 0: start from zero, 1: continue */);
+int ctk_centred_f64_dev(ctk_handle *h, const double *x_dev, int64_t T, int ny, int nx, int64_t R, const int64_t *t, const int32_t *row, const int32_t *col,
+                        const int32_t *bin, int nbins, int hy, int hx, int wrap, int skipna, double *sum_dev, uint32_t *n_dev, int accumulate);
+int ctk_centred_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, int64_t R, const int64_t *t, const int32_t *row, const int32_t *col,
+                    const int32_t *bin, int nbins, int hy, int hx, int wrap, int skipna, double *sum /* host */, uint32_t *n /* host */, int64_t chunk_steps);
+int ctk_centred_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, int64_t R, const int64_t *t, const int32_t *row, const int32_t *col,
+                    const int32_t *bin, int nbins, int hy, int hx, int wrap, int skipna, double *sum, uint32_t *n, int64_t chunk_steps);
+int ctk_centred_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, int64_t T, int ny, int nx, ctk_read_chunk_fn field_reader, void *field_user,
+                   int64_t R, const int64_t *t, const int32_t *row, const int32_t *col, const int32_t *bin, int nbins, int hy, int hx, int wrap, int skipna,
+                   double *sum, uint32_t *n, int64_t chunk_steps);
+
 #ifdef __cplusplus
 }
 #endif

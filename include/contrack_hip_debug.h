@@ -277,6 +277,25 @@ int ctk_debug_composite_launch(ctk_handle *h, int64_t *out2);
 int ctk_debug_time_composite(ctk_handle *h, const int32_t *flag_dev, const void *x_dev, int is_f64, int64_t T, int ny, int nx, const int32_t *group,
                              int ngroups, int32_t above, int skipna, double *sum_dev, uint32_t *n_dev, int reps, double *ms2);
 
+/* what ctk_centred_plan (csrc/ctk_forms.h) decides for a centred launch over nbins bins of a (2 hy + 1) x (2 hx + 1) window, the
+ * longest bin max_bin stamps and all bins together kept stamps, a field of elem_bytes (4 / 8); form, unroll, threads: what ctk_debug_set_centred would force (-1: the
+ * rule).  out6 = { the batch: stamps a lane (plain form) or a feeder wave (fed form) has in flight, cells of a bin per workgroup (64 /
+ * 128 / 256), workgroups of work per bin, workgroups of work in all, workgroups launched (at most 2^24 - 1; the kernels stride over
+ * the rest), the form: 0 plain (k_centred), 1 fed (k_centred_fed) }.  Host only: no handle, no GPU. */
+int ctk_debug_centred_plan(int elem_bytes, int nbins, int hy, int hx, int64_t max_bin, int64_t kept, int form, int unroll, int threads, int64_t *out6);
+/* test hook for the following centred launches on this handle: the form (0 plain, 1 fed), and for the plain form the widest batch of
+ * stamps (rounded down to a power of two, at most 32) and the cells per workgroup (rounded down to 64 / 128 / 256); -1 the rule */
+int ctk_debug_set_centred(ctk_handle *h, int form, int unroll, int threads);
+/* test hook: out4 = { the batch of the last centred launch on this handle (0: none yet), its cells per workgroup, its workgroups, its form } */
+int ctk_debug_centred_launch(ctk_handle *h, int64_t *out4);
+/* measurement (tools/centred_probe.py): the centred kernel alone (k_centred or k_centred_fed, as the rule or ctk_debug_set_centred decides) on a slab in device memory (is_f64 != 0: a float64 field; the stamps are host
+ * arrays as in ctk_centred_*_dev) between HIP events: one launch from zeroed accumulators that is not counted, then `reps` timed ones
+ * that continue from them; ms2 = { best, mean }.  floor != 0: instead of k_centred the yardstick kernel, a plain gather of the same
+ * windows with one lane per (stamp, cell), in no order, that keeps nothing (sum_dev is its sink). */
+int ctk_debug_time_centred(ctk_handle *h, const void *x_dev, int is_f64, int64_t T, int ny, int nx, int64_t R, const int64_t *t, const int32_t *row,
+                           const int32_t *col, const int32_t *bin, int nbins, int hy, int hx, int wrap, int skipna, double *sum_dev, uint32_t *n_dev,
+                           int floor, int reps, double *ms2);
+
 #ifdef __cplusplus
 }
 #endif
