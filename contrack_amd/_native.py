@@ -530,6 +530,81 @@ def check(rc):
         raise ContrackHipError("libcontrack_hip rc=%d: %s" % (rc, msg))
 
 
+class _Trampolines:
+    """The Python callbacks of ONE call into the library.  An exception must not cross the C frames: a callback that raises
+    returns non-zero to the library (which gives up) and the exception is kept; finish() re-raises the first one kept, in preference
+    to the library's return code.  The object owns the ctypes callback objects it made: it must live as long as the C call."""
+
+    def __init__(self):
+        self.errors = []
+        self._keep = []
+
+    def wrap(self, fntype, body):
+        """body(*the C arguments) as a callback of `fntype` that returns 0, or 1 after an exception"""
+        def call(*a):
+            try:
+                body(*a)
+                return 0
+            except BaseException as e:
+                self.errors.append(e)
+                return 1
+        cb = fntype(call)
+        self._keep.append(cb)
+        return cb
+
+    @staticmethod
+    def _view(ptr, ctype, nt, step_shape):
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(nt,) + tuple(step_shape))
+
+    def reader(self, source, ctype, step_shape):
+        """READ_CHUNK_FN that fills the chunk [t0, t0 + nt), an (nt,) + step_shape view of `ctype`, from `source`: a callable
+        source(t0, nt, out) or an array indexed by time.  None: the NULL reader."""
+        if source is None:
+            return C.cast(None, READ_CHUNK_FN)
+
+        def rd(_user, t0, nt, dst):
+            view = self._view(dst, ctype, nt, step_shape)
+            if callable(source):
+                source(int(t0), int(nt), view)
+            else:
+                view[...] = source[t0:t0 + nt]
+        return self.wrap(READ_CHUNK_FN, rd)
+
+    def writer(self, sink, ctype, step_shape):
+        """WRITE_CHUNK_FN that hands the chunk [t0, t0 + nt) to `sink`: a callable sink(t0, nt, values) or an array indexed by
+        time.  None: the NULL writer."""
+        if sink is None:
+            return C.cast(None, WRITE_CHUNK_FN)
+
+        def wr(_user, t0, nt, src):
+            view = self._view(src, ctype, nt, step_shape)
+            if callable(sink):
+                sink(int(t0), int(nt), view)
+            else:
+                sink[t0:t0 + nt] = view
+        return self.wrap(WRITE_CHUNK_FN, wr)
+
+    def finish(self, rc, check=check):
+        if self.errors:
+            raise self.errors[0]
+        check(rc)
+
+
+def _float_ctype(dt):
+    return C.c_float if dt == np.float32 else C.c_double
+
+
+def _flag_i32(flag, wider_hint):
+    """the flag slab of an array entry as C-contiguous int32 (time, lat, lon); narrower integers are widened, wider ones are
+    refused: `wider_hint` names the entries that take them"""
+    flag = np.asarray(flag)
+    if flag.ndim != 3:
+        raise ValueError("flag must be (time, lat, lon)")
+    if flag.dtype != np.int32 and (flag.dtype.kind not in "iub" or flag.dtype.itemsize > 4 or flag.dtype == np.uint32):
+        raise ValueError("flag must be int32 here (wider ids: %s)" % wider_hint)
+    return np.ascontiguousarray(flag, dtype=np.int32)
+
+
 def device_count():
     return int(lib().ctk_device_count())
 
@@ -935,37 +1010,10 @@ class Tracker:
                 fn = L.ctk_track_stream_seg_f64 if dt == np.float64 else L.ctk_track_stream_seg_f32
             check(fn(self._h, source.ctypes.data, T, ny, nx, *tail, sink.ctypes.data, C.byref(n), int(chunk_steps), *seg))
             return out, int(n.value)
-        errors = []
-
-        def rd(_user, t0, nt, dst):
-            try:
-                view = np.ctypeslib.as_array(C.cast(dst, C.POINTER(C.c_float if dt == np.float32 else C.c_double)), shape=(nt, ny, nx))
-                if callable(source):
-                    source(int(t0), int(nt), view)
-                else:
-                    view[...] = source[t0:t0 + nt]
-                return 0
-            except BaseException as e:                    # an exception must not cross the C frames
-                errors.append(e)
-                return 1
-
-        def wr(_user, t0, nt, src):
-            try:
-                view = np.ctypeslib.as_array(C.cast(src, C.POINTER(C.c_int32)), shape=(nt, ny, nx))
-                if callable(sink):
-                    sink(int(t0), int(nt), view)
-                else:
-                    sink[t0:t0 + nt] = view
-                return 0
-            except BaseException as e:
-                errors.append(e)
-                return 1
-        rcb, wcb = READ_CHUNK_FN(rd), WRITE_CHUNK_FN(wr)
+        tr = _Trampolines()
+        rcb, wcb = tr.reader(source, _float_ctype(dt), (ny, nx)), tr.writer(sink, C.c_int32, (ny, nx))
         fn = L.ctk_track_stream_cb if st is None else L.ctk_track_stream_seg_cb
-        rc = fn(self._h, dt.itemsize, T, ny, nx, rcb, None, *tail, wcb, None, C.byref(n), int(chunk_steps), *seg)
-        if errors:
-            raise errors[0]
-        check(rc)
+        tr.finish(fn(self._h, dt.itemsize, T, ny, nx, rcb, None, *tail, wcb, None, C.byref(n), int(chunk_steps), *seg))
         return out, int(n.value)
 
     def stream_times(self):
@@ -979,13 +1027,7 @@ class Tracker:
         """counts[g, y, x] = #{t : group[t] == g and flag[t, y, x] > above} of an int32 (T, ny, nx) host slab (ctk_frequency: chunks
         of `chunk_steps` timesteps pass through the device, 0: about 256 MB each).  group None: one group.  ngroups None:
         max(group) + 1.  Returns uint32 (ngroups, ny, nx)."""
-        flag = np.asarray(flag)
-        if flag.ndim != 3:
-            raise ValueError("flag must be (time, lat, lon)")
-        if flag.dtype != np.int32:
-            if flag.dtype.kind not in "iub" or flag.dtype.itemsize > 4 or flag.dtype == np.uint32:
-                raise ValueError("flag must be int32 here (wider ids: frequency_cb, or contrack.frequency_numpy)")
-        flag = np.ascontiguousarray(flag, dtype=np.int32)
+        flag = _flag_i32(flag, "frequency_cb, or contrack.frequency_numpy")
         T, ny, nx = flag.shape
         g, G = _groups(group, T, ngroups)
         counts = np.empty((max(G, 1), ny, nx), dtype=np.uint32)
@@ -998,20 +1040,9 @@ class Tracker:
         T, ny, nx = (int(v) for v in shape)
         g, G = _groups(group, T, ngroups)
         counts = np.empty((max(G, 1), ny, nx), dtype=np.uint32)
-        errors = []
-
-        def rd(_user, t0, nt, dst):
-            try:
-                reader(int(t0), int(nt), np.ctypeslib.as_array(C.cast(dst, C.POINTER(C.c_int32)), shape=(nt, ny, nx)))
-                return 0
-            except BaseException as e:                    # an exception must not cross the C frames
-                errors.append(e)
-                return 1
-        rcb = READ_CHUNK_FN(rd)
-        rc = lib().ctk_frequency_cb(self._h, T, ny, nx, rcb, None, _ptr(g), G, _above(above), counts.ctypes.data, int(chunk_steps))
-        if errors:
-            raise errors[0]
-        check(rc)
+        tr = _Trampolines()
+        rcb = tr.reader(reader, C.c_int32, (ny, nx))
+        tr.finish(lib().ctk_frequency_cb(self._h, T, ny, nx, rcb, None, _ptr(g), G, _above(above), counts.ctypes.data, int(chunk_steps)))
         return counts
 
     def frequency_dev(self, flag_dev, T, ny, nx, group=None, ngroups=None, above=0, counts_dev=None, accumulate=False):
@@ -1022,12 +1053,7 @@ class Tracker:
             check(lib().ctk_frequency_dev(self._h, flag_dev, int(T), int(ny), int(nx), _ptr(g), G, _above(above), counts_dev, int(bool(accumulate))))
             return None
         counts = np.empty((max(G, 1), int(ny), int(nx)), dtype=np.uint32)
-        d = self.malloc(max(counts.nbytes, 4))
-        try:
-            check(lib().ctk_frequency_dev(self._h, flag_dev, int(T), int(ny), int(nx), _ptr(g), G, _above(above), d, 0))
-            self.d2h(counts, d)
-        finally:
-            self.free(d)
+        self._download([counts], lambda d: check(lib().ctk_frequency_dev(self._h, flag_dev, int(T), int(ny), int(nx), _ptr(g), G, _above(above), d, 0)))
         return counts
 
     def debug_set_freq(self, slice_steps=0, nt=None):
@@ -1048,15 +1074,9 @@ class Tracker:
         timesteps pass through the device, 0: about 256 MB each).  A spell is a maximal run of steps with flag > above (by_id: and
         the same id) inside one segment; it belongs to the group of its first step and counts if it lasts min_duration steps or
         more.  group None: one group.  segments None: one segment, else the first step of every segment (0 first)."""
-        flag = np.asarray(flag)
-        if flag.ndim != 3:
-            raise ValueError("flag must be (time, lat, lon)")
-        if flag.dtype != np.int32:
-            if flag.dtype.kind not in "iub" or flag.dtype.itemsize > 4 or flag.dtype == np.uint32:
-                raise ValueError("flag must be int32 here (wider ids: spells_cb, or contrack.spells_numpy)")
+        flag = _flag_i32(flag, "spells_cb, or contrack.spells_numpy")
         T, ny, nx = flag.shape
         g, G, st, by, md = _spell_args(T, group, ngroups, segments, by_id, min_duration)
-        flag = np.ascontiguousarray(flag, dtype=np.int32)
         out = np.empty((3, G, ny, nx), dtype=np.uint32)
         check(lib().ctk_spells(self._h, flag.ctypes.data, T, ny, nx, _ptr(g), G, _ptr(st), 0 if st is None else st.shape[0], _above(above), by, md,
                                out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, int(chunk_steps)))
@@ -1068,21 +1088,10 @@ class Tracker:
         T, ny, nx = (int(v) for v in shape)
         g, G, st, by, md = _spell_args(T, group, ngroups, segments, by_id, min_duration)
         out = np.empty((3, G, ny, nx), dtype=np.uint32)
-        errors = []
-
-        def rd(_user, t0, nt, dst):
-            try:
-                reader(int(t0), int(nt), np.ctypeslib.as_array(C.cast(dst, C.POINTER(C.c_int32)), shape=(nt, ny, nx)))
-                return 0
-            except BaseException as e:                    # an exception must not cross the C frames
-                errors.append(e)
-                return 1
-        rcb = READ_CHUNK_FN(rd)
-        rc = lib().ctk_spells_cb(self._h, T, ny, nx, rcb, None, _ptr(g), G, _ptr(st), 0 if st is None else st.shape[0], _above(above), by, md,
-                                 out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, int(chunk_steps))
-        if errors:
-            raise errors[0]
-        check(rc)
+        tr = _Trampolines()
+        rcb = tr.reader(reader, C.c_int32, (ny, nx))
+        tr.finish(lib().ctk_spells_cb(self._h, T, ny, nx, rcb, None, _ptr(g), G, _ptr(st), 0 if st is None else st.shape[0], _above(above), by, md,
+                                      out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, int(chunk_steps)))
         return out[0], out[1], out[2]
 
     def spells_dev(self, flag_dev, T, ny, nx, group=None, ngroups=None, above=0, by_id=True, min_duration=1, segments=None):
@@ -1090,13 +1099,8 @@ class Tracker:
         T, ny, nx = int(T), int(ny), int(nx)
         g, G, st, by, md = _spell_args(T, group, ngroups, segments, by_id, min_duration)
         out = np.empty((3, G, ny, nx), dtype=np.uint32)
-        d = self.malloc(max(out.nbytes, 4))
-        try:
-            check(lib().ctk_spells_dev(self._h, flag_dev, T, ny, nx, _ptr(g), G, _ptr(st), 0 if st is None else st.shape[0], _above(above), by, md,
-                                       d, d.value + out[0].nbytes, d.value + 2 * out[0].nbytes))
-            self.d2h(out, d)
-        finally:
-            self.free(d)
+        self._download([out], lambda d: check(lib().ctk_spells_dev(self._h, flag_dev, T, ny, nx, _ptr(g), G, _ptr(st), 0 if st is None else st.shape[0],
+                                                                  _above(above), by, md, d, d.value + out[0].nbytes, d.value + 2 * out[0].nbytes)))
         return out[0], out[1], out[2]
 
     def set_spell_debug(self, slice_steps=0):
@@ -1121,12 +1125,7 @@ class Tracker:
         float64 field slab of the same shape in host memory (ctk_composite_f32 / _f64: chunks of `chunk_steps` time steps of both
         pass through the device, 0: about 256 MB of field each).  x None: the anomaly slab anomalies(keep_resident=True) left on
         the device (resident_f64: its type).  Returns float64 and uint32 (ngroups, ny, nx)."""
-        flag = np.asarray(flag)
-        if flag.ndim != 3:
-            raise ValueError("flag must be (time, lat, lon)")
-        if flag.dtype != np.int32 and (flag.dtype.kind not in "iub" or flag.dtype.itemsize > 4 or flag.dtype == np.uint32):
-            raise ValueError("flag must be int32 here (wider ids: composite_cb, or contrack.composite_numpy)")
-        flag = np.ascontiguousarray(flag, dtype=np.int32)
+        flag = _flag_i32(flag, "composite_cb, or contrack.composite_numpy")
         T, ny, nx = flag.shape
         if x is None:
             f64 = bool(resident_f64)
@@ -1154,24 +1153,10 @@ class Tracker:
         g, G = _groups(group, T, ngroups)
         s = np.empty((max(G, 1), ny, nx), dtype=np.float64)
         n = np.empty((max(G, 1), ny, nx), dtype=np.uint32)
-        errors = []
-
-        def wrap(reader, ctype):
-            def rd(_user, t0, nt, dst):
-                try:
-                    reader(int(t0), int(nt), np.ctypeslib.as_array(C.cast(dst, C.POINTER(ctype)), shape=(nt, ny, nx)))
-                    return 0
-                except BaseException as e:                # an exception must not cross the C frames
-                    errors.append(e)
-                    return 1
-            return READ_CHUNK_FN(rd)
-        fcb = wrap(flag_reader, C.c_int32)
-        xcb = wrap(field_reader, C.c_float if dt == np.float32 else C.c_double) if field_reader is not None else C.cast(None, READ_CHUNK_FN)
-        rc = lib().ctk_composite_cb(self._h, dt.itemsize, T, ny, nx, fcb, None, xcb, None, _ptr(g), G, _above(above), int(bool(skipna)),
-                                    s.ctypes.data, n.ctypes.data, int(chunk_steps))
-        if errors:
-            raise errors[0]
-        _check_composite(rc)
+        tr = _Trampolines()
+        fcb, xcb = tr.reader(flag_reader, C.c_int32, (ny, nx)), tr.reader(field_reader, _float_ctype(dt), (ny, nx))
+        tr.finish(lib().ctk_composite_cb(self._h, dt.itemsize, T, ny, nx, fcb, None, xcb, None, _ptr(g), G, _above(above), int(bool(skipna)),
+                                         s.ctypes.data, n.ctypes.data, int(chunk_steps)), _check_composite)
         return s, n
 
     def composite_dev(self, flag_dev, x_dev, T, ny, nx, group=None, ngroups=None, above=0, skipna=False, f64=False, sum_dev=None, n_dev=None,
@@ -1189,14 +1174,7 @@ class Tracker:
             return None
         s = np.empty((max(G, 1), int(ny), int(nx)), dtype=np.float64)
         n = np.empty((max(G, 1), int(ny), int(nx)), dtype=np.uint32)
-        ds, dn = self.malloc(max(s.nbytes, 8)), self.malloc(max(n.nbytes, 4))
-        try:
-            _check_composite(fn(*args, ds, dn, 0))
-            self.d2h(s, ds)
-            self.d2h(n, dn)
-        finally:
-            self.free(ds)
-            self.free(dn)
+        self._download([s, n], lambda ds, dn: _check_composite(fn(*args, ds, dn, 0)))
         return s, n
 
     def debug_set_composite(self, unroll=-1):
@@ -1263,22 +1241,10 @@ class Tracker:
         R, t, row, col, bin, nbins, hy, hx = _stamps(t, row, col, bin, nbins, hy, hx)
         s = np.empty((nbins, 2 * hy + 1, 2 * hx + 1), dtype=np.float64)
         n = np.empty(s.shape, dtype=np.uint32)
-        errors = []
-        ctype = C.c_float if dt == np.float32 else C.c_double
-
-        def rd(_user, t0, nt, dst):
-            try:
-                field_reader(int(t0), int(nt), np.ctypeslib.as_array(C.cast(dst, C.POINTER(ctype)), shape=(nt, ny, nx)))
-                return 0
-            except BaseException as e:                    # an exception must not cross the C frames
-                errors.append(e)
-                return 1
-        xcb = READ_CHUNK_FN(rd) if field_reader is not None else C.cast(None, READ_CHUNK_FN)
-        rc = lib().ctk_centred_cb(self._h, dt.itemsize, T, ny, nx, xcb, None, R, _ptr(t), _ptr(row), _ptr(col), _ptr(bin), nbins, hy, hx, int(bool(wrap)),
-                                  int(bool(skipna)), s.ctypes.data, n.ctypes.data, int(chunk_steps))
-        if errors:
-            raise errors[0]
-        _check_composite(rc)
+        tr = _Trampolines()
+        xcb = tr.reader(field_reader, _float_ctype(dt), (ny, nx))
+        tr.finish(lib().ctk_centred_cb(self._h, dt.itemsize, T, ny, nx, xcb, None, R, _ptr(t), _ptr(row), _ptr(col), _ptr(bin), nbins, hy, hx,
+                                       int(bool(wrap)), int(bool(skipna)), s.ctypes.data, n.ctypes.data, int(chunk_steps)), _check_composite)
         return s, n
 
     def centred_dev(self, x_dev, T, ny, nx, t, row, col, bin, nbins, hy, hx, wrap=True, skipna=False, f64=False, sum_dev=None, n_dev=None,
@@ -1296,14 +1262,7 @@ class Tracker:
             return None
         s = np.empty((nbins, 2 * hy + 1, 2 * hx + 1), dtype=np.float64)
         n = np.empty(s.shape, dtype=np.uint32)
-        ds, dn = self.malloc(max(s.nbytes, 8)), self.malloc(max(n.nbytes, 4))
-        try:
-            _check_composite(fn(*args, ds, dn, 0))
-            self.d2h(s, ds)
-            self.d2h(n, dn)
-        finally:
-            self.free(ds)
-            self.free(dn)
+        self._download([s, n], lambda ds, dn: _check_composite(fn(*args, ds, dn, 0)))
         return s, n
 
     def debug_set_centred(self, form=-1, unroll=-1, threads=-1):
@@ -1403,38 +1362,9 @@ class Tracker:
             fn = L.ctk_anom_stream_f64 if dt == np.float64 else L.ctk_anom_stream_f32
             check(fn(self._h, source.ctypes.data, T, ny, nx, *mid, _ptr(sink), _ptr(cout), int(chunk_steps)))
             return out, cout
-        errors = []
-        ctype = C.c_float if dt == np.float32 else C.c_double
-
-        def rd(_user, t0, nt, dst):
-            try:
-                view = np.ctypeslib.as_array(C.cast(dst, C.POINTER(ctype)), shape=(nt, ny, nx))
-                if callable(source):
-                    source(int(t0), int(nt), view)
-                else:
-                    view[...] = source[t0:t0 + nt]
-                return 0
-            except BaseException as e:                    # an exception must not cross the C frames
-                errors.append(e)
-                return 1
-
-        def wr(_user, t0, nt, src):
-            try:
-                view = np.ctypeslib.as_array(C.cast(src, C.POINTER(ctype)), shape=(nt, ny, nx))
-                if callable(sink):
-                    sink(int(t0), int(nt), view)
-                else:
-                    sink[t0:t0 + nt] = view
-                return 0
-            except BaseException as e:
-                errors.append(e)
-                return 1
-        rcb = READ_CHUNK_FN(rd)
-        wcb = WRITE_CHUNK_FN(wr) if sink is not None else C.cast(None, WRITE_CHUNK_FN)
-        rc = L.ctk_anom_stream_cb(self._h, dt.itemsize, T, ny, nx, rcb, None, *mid, _ptr(cout), wcb, None, int(chunk_steps))
-        if errors:
-            raise errors[0]
-        check(rc)
+        tr = _Trampolines()
+        rcb, wcb = tr.reader(source, _float_ctype(dt), (ny, nx)), tr.writer(sink, _float_ctype(dt), (ny, nx))
+        tr.finish(L.ctk_anom_stream_cb(self._h, dt.itemsize, T, ny, nx, rcb, None, *mid, _ptr(cout), wcb, None, int(chunk_steps)))
         return out, cout
 
     # ---- vertical mean over the selected levels (ctk_level_mean_*) ------------------------------------------------
@@ -1490,35 +1420,10 @@ class Tracker:
             if sink.dtype != dt or sink.shape != (steps, ny, nx) or not sink.flags.c_contiguous:
                 raise ValueError("the sink array must be C-contiguous (steps, ny, nx) of the field's dtype")
             out = sink
-        errors = []
-        ctype = C.c_float if dt == np.float32 else C.c_double
-
-        def rd(_user, t0, nt, dst):
-            try:
-                reader(int(t0), int(nt), np.ctypeslib.as_array(C.cast(dst, C.POINTER(ctype)), shape=(nt, nsel, ny, nx)))
-                return 0
-            except BaseException as e:                    # an exception must not cross the C frames
-                errors.append(e)
-                return 1
-
-        def wr(_user, t0, nt, src):
-            try:
-                view = np.ctypeslib.as_array(C.cast(src, C.POINTER(ctype)), shape=(nt, ny, nx))
-                if callable(sink):
-                    sink(int(t0), int(nt), view)
-                else:
-                    sink[t0:t0 + nt] = view
-                return 0
-            except BaseException as e:
-                errors.append(e)
-                return 1
-        rcb = READ_CHUNK_FN(rd)
-        wcb = WRITE_CHUNK_FN(wr) if sink is not None else C.cast(None, WRITE_CHUNK_FN)
-        rc = lib().ctk_level_mean_stream_cb(self._h, dt.itemsize, steps, nsel, ny, nx, rcb, None, w.ctypes.data, int(bool(skipna)), wcb, None,
-                                            int(chunk_steps or 0), int(bool(keep_resident)))
-        if errors:
-            raise errors[0]
-        check(rc)
+        tr = _Trampolines()
+        rcb, wcb = tr.reader(reader, _float_ctype(dt), (nsel, ny, nx)), tr.writer(sink, _float_ctype(dt), (ny, nx))
+        tr.finish(lib().ctk_level_mean_stream_cb(self._h, dt.itemsize, steps, nsel, ny, nx, rcb, None, w.ctypes.data, int(bool(skipna)), wcb, None,
+                                                 int(chunk_steps or 0), int(bool(keep_resident))))
         return out
 
     def level_mean_dev(self, x_dev, steps, nlev, ny, nx, weights, out_dev, skipna=False, f64=False):
@@ -1798,6 +1703,20 @@ class Tracker:
     def free(self, p):
         check(lib().ctk_dev_free(self._h, p))
 
+    def _download(self, outs, call):
+        """call(*buffers) with one fresh device buffer per host array of `outs`, then the buffers copied into those arrays; they are
+        freed on every path"""
+        devs = []
+        try:
+            for a in outs:
+                devs.append(self.malloc(max(a.nbytes, a.itemsize)))
+            call(*devs)
+            for a, d in zip(outs, devs):
+                self.d2h(a, d)
+        finally:
+            for d in devs:
+                self.free(d)
+
     def h2d(self, dst, arr):
         arr = np.ascontiguousarray(arr)
         check(lib().ctk_memcpy_h2d(self._h, dst, arr.ctypes.data, arr.nbytes))
@@ -1957,26 +1876,7 @@ class Tracker:
         wrow = np.ascontiguousarray(wrow, dtype=np.float32)
         if wrow.shape != (ny,):
             raise ValueError("wrow must have shape (ny,)")
-        errors = []
-
-        def guarded(body):
-            def call(*a):
-                try:
-                    body(*a)
-                    return 0
-                except BaseException as e:                # an exception must not cross the C frames
-                    errors.append(e)
-                    return 1
-            return call
-
-        def reader_of(source, ctype):
-            def rd(_user, t0, nt, dst):
-                view = np.ctypeslib.as_array(C.cast(dst, C.POINTER(ctype)), shape=(nt, ny, nx))
-                if callable(source):
-                    source(int(t0), int(nt), view)
-                else:
-                    view[...] = source[t0:t0 + nt]
-            return READ_CHUNK_FN(guarded(rd))
+        tr = _Trampolines()
 
         def pk(_user, rows, n, idx, nidx):
             view = np.ctypeslib.as_array(C.cast(rows, C.POINTER(C.c_byte)), shape=(n * LIFE_ROW.itemsize,)).view(LIFE_ROW)
@@ -1985,18 +1885,16 @@ class Tracker:
                 raise ValueError("pick returned more indices than rows")
             np.ctypeslib.as_array(C.cast(idx, C.POINTER(C.c_int64)), shape=(max(int(n), 1),))[:len(chosen)] = chosen
             nidx[0] = len(chosen)
-        pcb = LIFE_PICK_FN(guarded(pk)) if pick is not None else LIFE_PICK_FN()          # (a NULL pointer: no rows are picked)
+        pcb = tr.wrap(LIFE_PICK_FN, pk) if pick is not None else LIFE_PICK_FN()          # (a NULL pointer: no rows are picked)
         n, nx_ = C.c_int64(0), C.c_int64(0)
         tail = (wrow.ctypes.data, int(chunk_steps), pcb, None, C.byref(n), C.byref(nx_))
         if arrays:
             fn = L.ctk_lifecycle_stream_f64 if dt == np.float64 else L.ctk_lifecycle_stream_f32
             rc = fn(self._h, flag_source.ctypes.data, field_source.ctypes.data, T, ny, nx, *tail)
         else:
-            fcb, vcb = reader_of(flag_source, C.c_int32), reader_of(field_source, C.c_float if dt == np.float32 else C.c_double)
+            fcb, vcb = tr.reader(flag_source, C.c_int32, (ny, nx)), tr.reader(field_source, _float_ctype(dt), (ny, nx))
             rc = L.ctk_lifecycle_stream_cb(self._h, dt.itemsize, T, ny, nx, fcb, None, vcb, None, *tail)
-        if errors:
-            raise errors[0]
-        check(rc)
+        tr.finish(rc)
         rows = self._life_rows(int(n.value))
         idx = np.empty(int(nx_.value), dtype=np.int64)
         exact = np.empty(int(nx_.value), dtype=LIFE_EXACT)

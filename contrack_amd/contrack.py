@@ -202,6 +202,27 @@ def season_of_month(month):
     return SEASONS[month.astype(np.int64) - 1]
 
 
+def _flag_source(flag, shape=None):
+    """the flag slab of a *_numpy call as the binding takes it: (source, shape, is_array).  An integer (time, lat, lon) array goes as
+    it is when int32 or narrower; a wider one goes through a reader that narrows it chunk by chunk (an id beyond int32 raises
+    ValueError from the chunk that holds it); a reader(t0, nt, out) needs shape=(T, ny, nx)."""
+    if callable(flag):
+        if shape is None:
+            raise ValueError("a reader needs shape=(T, ny, nx)")
+        return flag, shape, False
+    flag = flag if isinstance(flag, np.memmap) else np.asarray(flag)
+    if flag.ndim != 3:
+        raise ValueError("flag must be (time, lat, lon)")
+    if flag.dtype.kind not in "iub":
+        raise ValueError("flag must be an integer field")
+    if flag.dtype.itemsize < 4 or flag.dtype == np.int32:
+        return flag, flag.shape, True
+
+    def reader(t0, nt, out):
+        out[...] = _int32_chunk(flag[t0:t0 + nt])
+    return reader, flag.shape, False
+
+
 def frequency_percent(counts, n):
     """counts (G, ...) / n[g] * 100 in float64, divided first as xr.where(...).sum('time') / ntime * 100 does (README.rst:159-160);
     an empty group (n[g] == 0) gives NaN, numpy's 0 / 0"""
@@ -221,26 +242,10 @@ def frequency_numpy(flag, group=None, above=0, percent=True, device=None, chunk_
     shape=(T, ny, nx) `flag` may be a reader(t0, nt, out) that fills an int32 (nt, ny, nx) buffer (ctk_frequency_cb)."""
     steps = 0 if chunk_steps is None else int(chunk_steps)
     trk = _tracker(device)
-    if callable(flag):
-        if shape is None:
-            raise ValueError("a reader needs shape=(T, ny, nx)")
-        T = int(shape[0])
-        ids, G = _native._groups(group, T)
-        counts = trk.frequency_cb(flag, shape, ids, G, above, steps)
-    else:
-        flag = np.asarray(flag)
-        if flag.ndim != 3:
-            raise ValueError("flag must be (time, lat, lon)")
-        if flag.dtype.kind not in "iub":
-            raise ValueError("flag must be an integer field")
-        T, ny, nx = flag.shape
-        ids, G = _native._groups(group, T)
-        if flag.dtype.itemsize < 4 or flag.dtype == np.int32:
-            counts = trk.frequency(flag, ids, G, above, steps)
-        else:
-            def reader(t0, nt, out):
-                out[...] = _int32_chunk(flag[t0:t0 + nt])
-            counts = trk.frequency_cb(reader, flag.shape, ids, G, above, steps)
+    source, shape, is_array = _flag_source(flag, shape)
+    T = int(shape[0])
+    ids, G = _native._groups(group, T)
+    counts = trk.frequency(source, ids, G, above, steps) if is_array else trk.frequency_cb(source, shape, ids, G, above, steps)
     counts = counts.astype(np.int64)
     out = frequency_percent(counts, np.bincount(ids, minlength=G) if ids is not None else [T]) if percent else counts
     return out[0] if group is None else out
@@ -268,27 +273,10 @@ def spells_numpy(flag, group=None, above=0, by_id=True, min_duration=1, segments
     if steps < 0:
         raise ValueError("chunk_steps={} (at least 0)".format(steps))
     _native._above(above)
-    if callable(flag):
-        if shape is None:
-            raise ValueError("a reader needs shape=(T, ny, nx)")
-        T = int(shape[0])
-        ids, G, st, by, md = _native._spell_args(T, group, None, segments, by_id, min_duration)
-        out = _tracker(device).spells_cb(flag, shape, ids, G, above, by, md, st, steps)
-    else:
-        flag = np.asarray(flag)
-        if flag.ndim != 3:
-            raise ValueError("flag must be (time, lat, lon)")
-        if flag.dtype.kind not in "iub":
-            raise ValueError("flag must be an integer field")
-        T = flag.shape[0]
-        ids, G, st, by, md = _native._spell_args(T, group, None, segments, by_id, min_duration)
-        trk = _tracker(device)
-        if flag.dtype.itemsize < 4 or flag.dtype == np.int32:
-            out = trk.spells(flag, ids, G, above, by, md, st, steps)
-        else:
-            def reader(t0, nt, out):
-                out[...] = _int32_chunk(flag[t0:t0 + nt])
-            out = trk.spells_cb(reader, flag.shape, ids, G, above, by, md, st, steps)
+    source, shape, is_array = _flag_source(flag, shape)
+    ids, G, st, by, md = _native._spell_args(int(shape[0]), group, None, segments, by_id, min_duration)
+    trk = _tracker(device)
+    out = trk.spells(source, ids, G, above, by, md, st, steps) if is_array else trk.spells_cb(source, shape, ids, G, above, by, md, st, steps)
     out = tuple(a.astype(np.int64) for a in out)
     return tuple(a[0] for a in out) if group is None else out
 
@@ -314,14 +302,8 @@ def composite_numpy(flag, x, group=None, above=0, skipna=False, chunk_steps=None
     if callable(flag) or callable(x):
         if shape is None or (dtype is None and (x is None or callable(x))):
             raise ValueError("a reader needs shape=(T, ny, nx) and the field's dtype")
-    if not callable(flag):
-        flag = flag if isinstance(flag, np.memmap) else np.asarray(flag)
-        if flag.ndim != 3:
-            raise ValueError("flag must be (time, lat, lon)")
-        if flag.dtype.kind not in "iub":
-            raise ValueError("flag must be an integer field")
-        if shape is None:
-            shape = flag.shape
+    fread, fshape, is_array = _flag_source(flag, shape)
+    shape = fshape if shape is None else shape
     if x is not None and not callable(x):
         x = x if isinstance(x, np.memmap) else np.asarray(x)
         if tuple(x.shape) != tuple(int(v) for v in shape):
@@ -331,13 +313,10 @@ def composite_numpy(flag, x, group=None, above=0, skipna=False, chunk_steps=None
     T = int(shape[0])
     ids, G = _native._groups(group, T)
     trk = _tracker(device)
-    if not callable(flag) and not callable(x) and (flag.dtype.itemsize < 4 or flag.dtype == np.int32):
-        s, n = trk.composite(flag, x, ids, G, above, skipna, steps, resident_f64=dtype == np.float64)
+    if is_array and not callable(x):
+        s, n = trk.composite(fread, x, ids, G, above, skipna, steps, resident_f64=dtype == np.float64)
     else:
-        fread, xread = flag, x
-        if not callable(flag):
-            def fread(t0, nt, out, slab=flag):
-                out[...] = _int32_chunk(slab[t0:t0 + nt])
+        xread = x
         if x is not None and not callable(x):
             def xread(t0, nt, out, slab=x):
                 out[...] = slab[t0:t0 + nt]
@@ -1830,6 +1809,44 @@ class contrack(object):
         arr = np.asarray(da.data).transpose([dims.index(d) for d in (member,) + names])
         return arr.reshape((-1,) + arr.shape[2:])
 
+    @staticmethod
+    def _group_plan(ids, uniq, T, M=None, pool=False):
+        """the groups of a map over the flat slab (_flat_slab) as the library takes them: (group, G, per_member).  ids: one group id
+        per time step (uniq: the groups' values) or None; M: the size of the member dimension, None without one.  Members that are
+        not pooled keep maps of their own: the library sees group m * G + g at flat step m * T + t.  group None: one group."""
+        G = 1 if ids is None else len(uniq)
+        per_member = M is not None and not pool
+        gids = np.zeros(T, dtype=np.int32) if ids is None else ids
+        if per_member:
+            gids = (np.arange(M, dtype=np.int32)[:, None] * G + gids[None, :]).reshape(-1)
+        else:
+            gids = np.tile(gids, 1 if M is None else M)
+        return (gids if (per_member or ids is not None) else None), G, per_member
+
+    def _map_layout(self, dims, member, pool, groupby, uniq, M, G):
+        """what a grouped map looks like as a labelled array: (out_dims, coords, shaped).  out_dims: the variable's own dims, the
+        group dim in the time dim's place (no groupby: gone) and a pooled member dim gone; shaped(a) brings the library's
+        (M * G or G, lat, lon) result into them."""
+        names = (self._time_name, self._latitude_name, self._longitude_name)
+        per_member = member is not None and not pool
+        lead = ((member,) if per_member else ()) + ((groupby,) if groupby is not None else ())
+        have = lead + names[1:]                                      # the axes of the result once shaped
+        gone = ((self._time_name,) if groupby is None else ()) + ((member,) if member is not None and pool else ())
+        out_dims = tuple(groupby if d == self._time_name else d for d in dims if d not in gone)
+
+        def shaped(a):
+            if per_member:
+                a = a.reshape((M, G) + a.shape[1:])
+            if groupby is None:
+                a = a[:, 0] if per_member else a[0]
+            return np.ascontiguousarray(a.transpose([have.index(d) for d in out_dims]))
+        coords = {} if groupby is None else {groupby: uniq}
+        if per_member:
+            coords[member] = self._dim_values(member, M)
+        for name in names[1:]:
+            coords[name] = np.asarray(self.ds[name].data)
+        return out_dims, coords, shaped
+
     def calc_frequency(self, flag='flag', groupby=None, above=0, chunk_steps=None, pool=False):
         """percentage of time steps with flag > above at every grid point: xr.where(ds[flag] > above, 1, 0).sum(dim='time') /
         ntime * 100 -- the README's blocking frequency with above=1 -- or, with groupby ('month', 'season', 'year', ...), the same
@@ -1844,55 +1861,27 @@ class contrack(object):
         self._ensure_set_up()
         da = self.ds[flag]
         dims, member = self._consumer_dims(flag)
-        names = (self._time_name, self._latitude_name, self._longitude_name)
-        if groupby is None:
-            ids, uniq = None, None
+        if np.dtype(da.dtype).kind not in "iub":
+            raise ValueError("flag must be an integer field")
+        ids, uniq = (None, None) if groupby is None else self._group_ids(groupby)
+        T = da.shape[dims.index(self._time_name)]
+        M = None if member is None else da.shape[dims.index(member)]
+        group, G, per_member = self._group_plan(ids, uniq, T, M, pool)
+        if chunk_steps is None:
+            source, shape = self._flat_slab(da, dims, member), None
+        elif member is None:
+            source, shape, _ = self._time_reader(da, dims, integer=True)
         else:
-            ids, uniq = self._group_ids(groupby)
-        if member is None and chunk_steps is None:
-            slab = np.asarray(da.data).transpose([dims.index(d) for d in names])
-            freq = frequency_numpy(slab, ids, above=above)
-        else:
-            if np.dtype(da.dtype).kind not in "iub":
-                raise ValueError("flag must be an integer field")
-            T = da.shape[dims.index(self._time_name)]
-            M = 1 if member is None else da.shape[dims.index(member)]
-            G = 1 if ids is None else len(uniq)
-            per_member = member is not None and not pool
-            gids = np.zeros(T, dtype=np.int32) if ids is None else ids
-            if per_member:                                       # the library sees group m * G + g
-                gids = (np.arange(M, dtype=np.int32)[:, None] * G + gids[None, :]).reshape(-1)
-            else:
-                gids = np.tile(gids, M)
-            if chunk_steps is None:
-                source, shape = self._flat_slab(da, dims, member), None
-            elif member is None:
-                source, shape, _ = self._time_reader(da, dims, integer=True)
-            else:
-                source, shape, _ = self._member_reader(da, dims, member, integer=True)
-            counts = frequency_numpy(source, gids if (per_member or ids is not None) else None, above=above, percent=False, chunk_steps=chunk_steps, shape=shape)
-            counts = counts.reshape((-1,) + counts.shape[-2:])
-            n = np.bincount(ids, minlength=G) if ids is not None else np.array([T])
-            n = np.tile(n, M) if per_member else n * M               # a group's size inside one member / over all of them
-            freq = frequency_percent(counts, n)
-            if per_member:
-                freq = freq.reshape((M, G) + freq.shape[1:])
-            if ids is None:
-                freq = freq[:, 0] if per_member else freq[0]
-        lead = ((member,) if member is not None and not pool else ()) + ((groupby,) if groupby is not None else ())
-        have = lead + names[1:]                                      # the axes of freq
-        gone = ((self._time_name,) if groupby is None else ()) + ((member,) if member is not None and pool else ())
-        out_dims = tuple(groupby if d == self._time_name else d for d in dims if d not in gone)
-        data = freq.transpose([have.index(d) for d in out_dims])
-        coords = {} if groupby is None else {groupby: uniq}
-        if member in lead:
-            coords[member] = self._dim_values(member, da.shape[dims.index(member)])
-        for name in (self._latitude_name, self._longitude_name):
-            coords[name] = np.asarray(self.ds[name].data)
+            source, shape, _ = self._member_reader(da, dims, member, integer=True)
+        counts = frequency_numpy(source, group, above=above, percent=False, chunk_steps=chunk_steps, shape=shape)
+        counts = counts.reshape((-1,) + counts.shape[-2:])
+        n = np.bincount(ids, minlength=G) if ids is not None else np.array([T])
+        n = np.tile(n, M) if per_member else n * (M or 1)        # a group's size inside one member / over all of them
+        out_dims, coords, shaped = self._map_layout(dims, member, pool, groupby, uniq, M, G)
         attrs = {'units': '%', 'long_name': 'contrack frequency', 'standard_name': 'contrack frequency',
                  'history': ' '.join(['Calculated from {} with input attributes:', 'flag > {},', 'groupby = {}.']).format(
                      flag, above, groupby)}
-        return self._wrap(da, np.ascontiguousarray(data), out_dims, coords, attrs, name='frequency')
+        return self._wrap(da, shaped(frequency_percent(counts, n)), out_dims, coords, attrs, name='frequency')
 
     # ---- blocked spells per grid point: the maps beside the frequency map of a blocking climatology ---------------------------
     def calc_spells(self, flag='flag', groupby=None, above=0, by_id=True, min_duration=1, segments=None, chunk_steps=None, pool=False):
@@ -1912,22 +1901,14 @@ class contrack(object):
         self._ensure_set_up()
         da = self.ds[flag]
         dims, member = self._consumer_dims(flag)
-        names = (self._time_name, self._latitude_name, self._longitude_name)
         if np.dtype(da.dtype).kind not in "iub":
             raise ValueError("flag variable {!r} is not an integer field".format(flag))
         seg_member, starts, T = self._segment_args(flag, da, dims, segments)
         if seg_member is not None:                               # (the member dimension by name: its members are segments anyway)
             starts = None
         ids, uniq = (None, None) if groupby is None else self._group_ids(groupby)
-        M = 1 if member is None else da.shape[dims.index(member)]
-        G = 1 if ids is None else len(uniq)
-        per_member = member is not None and not pool
-        gids = np.zeros(T, dtype=np.int32) if ids is None else ids
-        if per_member:                                           # the library sees group m * G + g
-            gids = (np.arange(M, dtype=np.int32)[:, None] * G + gids[None, :]).reshape(-1)
-        else:
-            gids = np.tile(gids, M)
-        group = gids if (per_member or ids is not None) else None
+        M = None if member is None else da.shape[dims.index(member)]
+        group, G, per_member = self._group_plan(ids, uniq, T, M, pool)
         if member is not None:                                   # every member a segment of its own, with the breaks inside it
             inner = np.zeros(1, dtype=np.int64) if starts is None else starts
             starts = (np.arange(M, dtype=np.int64)[:, None] * T + inner[None, :]).reshape(-1)
@@ -1940,22 +1921,7 @@ class contrack(object):
         maps = spells_numpy(source, group, above=above, by_id=by_id, min_duration=min_duration, segments=starts, chunk_steps=chunk_steps, shape=shape)
         maps = [a.reshape((-1,) + a.shape[-2:]) for a in maps]
         maps.append(spell_duration(maps[1], maps[0]))
-        lead = ((member,) if per_member else ()) + ((groupby,) if groupby is not None else ())
-        have = lead + names[1:]
-        gone = ((self._time_name,) if groupby is None else ()) + ((member,) if member is not None and pool else ())
-        out_dims = tuple(groupby if d == self._time_name else d for d in dims if d not in gone)
-
-        def shaped(a):
-            if per_member:
-                a = a.reshape((M, G) + a.shape[1:])
-            if ids is None:
-                a = a[:, 0] if per_member else a[0]
-            return np.ascontiguousarray(a.transpose([have.index(d) for d in out_dims]))
-        coords = {} if groupby is None else {groupby: uniq}
-        if member in lead:
-            coords[member] = self._dim_values(member, M)
-        for name in (self._latitude_name, self._longitude_name):
-            coords[name] = np.asarray(self.ds[name].data)
+        out_dims, coords, shaped = self._map_layout(dims, member, pool, groupby, uniq, M, G)
         history = ' '.join(['Calculated from {} with input attributes:', 'flag > {},', 'groupby = {},', 'by_id = {},', 'min_duration = {}.']).format(
             flag, above, groupby, bool(by_id), min_duration)
         out = {}
@@ -1989,18 +1955,10 @@ class contrack(object):
             raise ValueError("the variable {!r} has dims {}, the flag variable {!r} has {}: they must be the same".format(variable, vdims, flag, dims))
         if np.dtype(fda.dtype).kind not in "iub":
             raise ValueError("flag variable {!r} is not an integer field".format(flag))
-        names = (self._time_name, self._latitude_name, self._longitude_name)
         ids, uniq = (None, None) if groupby is None else self._group_ids(groupby)
         T = fda.shape[dims.index(self._time_name)]
-        M = 1 if member is None else fda.shape[dims.index(member)]
-        G = 1 if ids is None else len(uniq)
-        per_member = member is not None and not pool
-        gids = np.zeros(T, dtype=np.int32) if ids is None else ids
-        if per_member:                                           # the library sees group m * G + g
-            gids = (np.arange(M, dtype=np.int32)[:, None] * G + gids[None, :]).reshape(-1)
-        else:
-            gids = np.tile(gids, M)
-        group = gids if (per_member or ids is not None) else None
+        M = None if member is None else fda.shape[dims.index(member)]
+        group, G, per_member = self._group_plan(ids, uniq, T, M, pool)
         vtype = _native._field_dtype(vda.dtype)
         if chunk_steps is None:
             flags, field = self._flat_slab(fda, dims, member), self._flat_slab(vda, vdims, member)
@@ -2017,22 +1975,7 @@ class contrack(object):
             s, n = composite_numpy(fread, vread, group, above=above, skipna=skipna, chunk_steps=chunk_steps, shape=shape, dtype=vtype)
         s, n = s.reshape((-1,) + s.shape[-2:]), n.reshape((-1,) + n.shape[-2:])
         out = composite_mean(s, n) if stat == 'mean' else s
-        lead = ((member,) if per_member else ()) + ((groupby,) if groupby is not None else ())
-        have = lead + names[1:]
-        gone = ((self._time_name,) if groupby is None else ()) + ((member,) if member is not None and pool else ())
-        out_dims = tuple(groupby if d == self._time_name else d for d in dims if d not in gone)
-
-        def shaped(a):
-            if per_member:
-                a = a.reshape((M, G) + a.shape[1:])
-            if ids is None:
-                a = a[:, 0] if per_member else a[0]
-            return np.ascontiguousarray(a.transpose([have.index(d) for d in out_dims]))
-        coords = {} if groupby is None else {groupby: uniq}
-        if member in lead:
-            coords[member] = self._dim_values(member, M)
-        for name in (self._latitude_name, self._longitude_name):
-            coords[name] = np.asarray(self.ds[name].data)
+        out_dims, coords, shaped = self._map_layout(dims, member, pool, groupby, uniq, M, G)
         attrs = {'long_name': 'contrack composite', 'standard_name': 'contrack composite',
                  'history': ' '.join(['Calculated from {} with input attributes:', 'flag = {} > {},', 'groupby = {},', 'stat = {},', 'skipna = {}.']).format(
                      variable, flag, above, groupby, stat, skipna)}

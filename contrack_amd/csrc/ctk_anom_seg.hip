@@ -359,8 +359,7 @@ static int anom_stream_impl(ctk_handle *h, StreamIO &io, int64_t T, int ny, int 
     const int64_t npix = (int64_t)ny * nx;
     const size_t plane = (size_t)npix * sizeof(VT), cb = (size_t)ngroups * plane, ng = (size_t)ngroups * (size_t)npix;
     io.esz = sizeof(VT);
-    io.chunk = chunk_steps > 0 ? chunk_steps : std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / plane));
-    io.chunk = std::min<int64_t>(std::max<int64_t>(io.chunk, std::max<int64_t>(smooth - 1, 1)), T);       // (at least the halo: see pass 2)
+    io.chunk = ctk_stream_chunk(chunk_steps, T, plane, std::max<int64_t>(smooth - 1, 1));                 // (at least the halo: see pass 2)
     const double t_call = now_ms();
     CTKCHK(ensure(h, h->an_clim, cb));
     h->an_pct_n = -1;                                                  // (an_raw is overwritten below)
@@ -370,8 +369,6 @@ static int anom_stream_impl(ctk_handle *h, StreamIO &io, int64_t T, int ny, int 
     if (sink) CTKCHK(stream_setup(h, 0, (size_t)(io.chunk + smooth) * plane, io.write_v != nullptr));
     HIPCHK(hipMemcpy(h->an_idx.p, group, (size_t)T * 4, hipMemcpyHostToDevice));
     const int32_t *d_grp = P<int32_t>(h->an_idx);
-    struct Sio { ctk_handle *h; ~Sio() { h->sio = nullptr; } } sio{h};
-    h->sio = &io;
     const unsigned gx = (unsigned)((npix + 255) / 256);
     if (clim_in) {
         HIPCHK(hipMemcpy(h->an_clim.p, clim_in, cb, hipMemcpyHostToDevice));
@@ -381,12 +378,11 @@ static int anom_stream_impl(ctk_handle *h, StreamIO &io, int64_t T, int ny, int 
         int32_t *counts = (int32_t *)(sums + ng);
         HIPCHK(hipMemsetAsync(sums, 0, ng * 12, s));
         const unsigned gy = (unsigned)std::min(ngroups, 32);
-        const int rc = stream_in(h, sizeof(VT) == 8, T, ny, nx, [&](const void *chunk, int64_t c0, int64_t nt) -> int {
+        CTKCHK(stream_consume(h, io, sizeof(VT) == 8, T, ny, nx, [&](const void *chunk, int64_t c0, int64_t nt) -> int {
             k_clim_acc<VT><<<dim3(gx, gy), 256, 0, s>>>((const VT *)chunk, d_grp + c0, nt, npix, sums, counts);
             HIPCHK(hipGetLastError());
             return CTK_OK;
-        });
-        if (rc != CTK_OK) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamSynchronize(s); return rc; }      // (a reader gave up: nothing stays in flight)
+        }));
         k_clim_fin<VT><<<(unsigned)((ng + 255) / 256), 256, 0, s>>>(sums, counts, (int64_t)ng, (VT *)h->an_raw.p);
         k_clim_roll<VT><<<dim3(gx, (unsigned)std::min(ngroups, 64)), 256, 0, s>>>((const VT *)h->an_raw.p, ngroups, window, npix, (VT *)h->an_clim.p);
         HIPCHK(hipGetLastError());

@@ -380,7 +380,7 @@ struct ctk_handle {
     // blocking frequency (ctk_freq.hip): counts of the host entries, group ids; experiments (ctk_debug_set_freq)
     DevBuf fq_counts, fq_group;
     // blocked spells (ctk_spell.hip): the three maps of the host entries, the per-step words (group id, bit 31: segment start) and
-    // their host copy, the two per-pixel carries; the test hook's slice (ctk_debug_set_spell; 0: the rule of spell_slice)
+    // their host copy, the two per-pixel carries; the test hook's slice (ctk_debug_set_spell; 0: the rule of ctk_time_slice)
     DevBuf sp_out, sp_words, sp_carry;
     std::vector<uint32_t> sp_words_host;
     int64_t sp_slice_dbg = 0;
@@ -898,6 +898,52 @@ extern "C" int ctk_get_timings(ctk_handle *h, double *ms)
 // ------------------------------------------------------------------------------------------------
 static int stream_in(ctk_handle *h, bool f64, int64_t T, int ny, int nx, const std::function<int(const void *, int64_t, int64_t)> &consume);
 static int stream_out(ctk_handle *h, int persistence, const int32_t *chunk_vals);
+
+// A read-only pass over a streamed slab (the map consumers, the climatology pass, the life cycle): `io` is the handle's source while
+// stream_in runs and on no path longer, the handle gets the pass's stream timings, and a failed chunk -- a reader that gave up -- leaves
+// nothing of the call in flight: a chunk may still be on its way into a buffer.  A pass that succeeds is not waited for here.
+static int stream_consume(ctk_handle *h, StreamIO &io, bool f64, int64_t T, int ny, int nx, const std::function<int(const void *, int64_t, int64_t)> &consume)
+{
+    struct Sio { ctk_handle *h; ~Sio() { h->sio = nullptr; } } sio{h};
+    h->sio = &io;
+    const int rc = stream_in(h, f64, T, ny, nx, consume);
+    h->stream_ms[0] = io.ms_read; h->stream_ms[1] = io.ms_write; h->stream_ms[2] = io.ms_in; h->stream_ms[3] = io.ms_out;
+    if (rc != CTK_OK) {
+        if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
+        (void)hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+// A kernel alone between HIP events on the handle's stream (the ctk_debug_time_* hooks of the probes in tools/): one untimed launch,
+// then `reps` launches between reps + 1 events; ms2 = {best, mean} per launch.  The stream is idle and the events are gone when it
+// returns, also after an error; `who` names the hook in the error text.
+static int time_launches(ctk_handle *h, const char *who, int reps, double *ms2, const std::function<int()> &launch)
+{
+    std::vector<hipEvent_t> ev((size_t)reps + 1, nullptr);
+    int rc = CTK_OK;
+    for (auto &e : ev)
+        if (hipEventCreate(&e) != hipSuccess) { rc = ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed"); break; }
+    if (rc == CTK_OK) rc = launch();                                                // (warm-up)
+    for (int r = 0; r < reps && rc == CTK_OK; r++) {
+        if (hipEventRecord(ev[r], h->stream) != hipSuccess) rc = ctk_set_error(CTK_E_NODEVICE, "hipEventRecord failed");
+        if (rc == CTK_OK) rc = launch();
+    }
+    if (rc == CTK_OK && (hipEventRecord(ev[reps], h->stream) != hipSuccess || hipEventSynchronize(ev[reps]) != hipSuccess))
+        rc = ctk_set_error(CTK_E_NODEVICE, "%s: event wait failed", who);
+    if (rc == CTK_OK) {
+        double best = 1e30, sum = 0;
+        for (int r = 0; r < reps; r++) {
+            float m = 0;
+            (void)hipEventElapsedTime(&m, ev[r], ev[r + 1]);
+            best = std::min(best, (double)m); sum += m;
+        }
+        ms2[0] = best; ms2[1] = sum / reps;
+    }
+    (void)hipStreamSynchronize(h->stream);
+    for (auto e : ev) if (e) (void)hipEventDestroy(e);
+    return rc;
+}
 
 static bool async_wanted(ctk_handle *h);
 // exclusive scan of n uint32 items into out[0 .. n] (out[n] = the total): one workgroup for short shards, block sums + one workgroup
@@ -3344,8 +3390,7 @@ static int track_stream_impl(ctk_handle *h, StreamIO &io, bool f64, int64_t T, i
     HIPCHK(hipSetDevice(h->device));
     io.esz = f64 ? 8 : 4;
     const size_t plane = (size_t)ny * nx * io.esz;
-    io.chunk = chunk_steps > 0 ? chunk_steps : std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / plane));
-    io.chunk = std::max<int64_t>(1, std::min<int64_t>(io.chunk, std::max<int64_t>(T, 1)));
+    io.chunk = ctk_stream_chunk(chunk_steps, std::max<int64_t>(T, 1), plane);
     const double t0 = now_ms();
     h->sio = &io;
     // an array as the sink: the result needs no chunks -- the run tables of the whole slab are resident when the pass is over

@@ -394,7 +394,7 @@ static int centred_stream_impl(ctk_handle *h, StreamIO &io, bool f64, int64_t T,
         CTKCHK(centred_slab(h, c, res_dev, f64, sdev, ndev, 0));
     } else {
         io.esz = esz;
-        io.chunk = ctk_composite_chunk(chunk_steps, T, plane);
+        io.chunk = ctk_stream_chunk(chunk_steps, T, plane);
         // the chunks that carry stamps, their bands and their stamps (t is non-decreasing: one walk)
         CentredCsr csr;
         std::vector<CentredPiece> pieces;
@@ -532,12 +532,8 @@ extern "C" int ctk_debug_time_centred(ctk_handle *h, const void *x_dev, int is_f
     CentredCsr csr;
     const size_t o = csr.append(c, 0, R, 0, ny, 0);
     if (csr.st.empty()) return ctk_set_error(CTK_E_INVALID, "ctk_debug_time_centred: no stamp with bin >= 0");
-    std::vector<hipEvent_t> ev((size_t)reps + 1, nullptr);
-    int rc = CTK_OK;
-    for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { rc = ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed"); break; }
-    if (rc == CTK_OK) rc = csr.upload(h);
-    if (rc == CTK_OK) rc = centred_zero(h, c, sum_dev, n_dev);
+    CTKCHK(csr.upload(h));
+    CTKCHK(centred_zero(h, c, sum_dev, n_dev));
     auto launch = [&]() -> int {
         if (!floor) return launch_centred(h, c, x_dev, f64, csr.off_dev(h, o), csr.longest[0], csr.kept[0], sum_dev, n_dev);
         CentredArgs a = {};
@@ -550,23 +546,5 @@ extern "C" int ctk_debug_time_centred(ctk_handle *h, const void *x_dev, int is_f
         HIPCHK(hipGetLastError());
         return CTK_OK;
     };
-    if (rc == CTK_OK) rc = launch();                                                // (warm-up)
-    for (int r = 0; r < reps && rc == CTK_OK; r++) {
-        if (hipEventRecord(ev[r], h->stream) != hipSuccess) rc = ctk_set_error(CTK_E_NODEVICE, "hipEventRecord failed");
-        if (rc == CTK_OK) rc = launch();
-    }
-    if (rc == CTK_OK && (hipEventRecord(ev[reps], h->stream) != hipSuccess || hipEventSynchronize(ev[reps]) != hipSuccess))
-        rc = ctk_set_error(CTK_E_NODEVICE, "ctk_debug_time_centred: event wait failed");
-    if (rc == CTK_OK) {
-        double best = 1e30, tot = 0;
-        for (int r = 0; r < reps; r++) {
-            float m = 0;
-            (void)hipEventElapsedTime(&m, ev[r], ev[r + 1]);
-            best = std::min(best, (double)m); tot += m;
-        }
-        ms2[0] = best; ms2[1] = tot / reps;
-    }
-    (void)hipStreamSynchronize(h->stream);
-    for (auto e : ev) if (e) (void)hipEventDestroy(e);
-    return rc;
+    return time_launches(h, "ctk_debug_time_centred", reps, ms2, launch);
 }

@@ -182,7 +182,7 @@ static int comp_stream_impl(ctk_handle *h, StreamIO &io, bool f64, bool resident
     const size_t esz = f64 ? 8 : 4;
     io.esz = resident ? 4 : esz;
     io.esz2 = resident ? 0 : 4;
-    io.chunk = ctk_composite_chunk(chunk_steps, T, (size_t)npix * esz);
+    io.chunk = ctk_stream_chunk(chunk_steps, T, (size_t)npix * esz);
     const size_t cells = (size_t)ngroups * npix;
     CTKCHK(ensure(h, h->cp_sum, cells * 8));
     CTKCHK(ensure(h, h->cp_n, cells * 4));
@@ -190,20 +190,11 @@ static int comp_stream_impl(ctk_handle *h, StreamIO &io, bool f64, bool resident
     uint32_t *ndev = P<uint32_t>(h->cp_n);
     CTKCHK(comp_zero(h, sdev, ndev, ngroups, npix));
     const double t0 = now_ms();
-    h->sio = &io;
-    const int rc = stream_in(h, f64, T, ny, nx, [&](const void *chunk, int64_t c0, int64_t nt) -> int {
+    CTKCHK(stream_consume(h, io, f64, T, ny, nx, [&](const void *chunk, int64_t c0, int64_t nt) -> int {
         const int32_t *fl = resident ? (const int32_t *)chunk : (const int32_t *)io.dev2;
         const void *xv = resident ? (const void *)((const char *)res_dev + (size_t)c0 * npix * esz) : chunk;
         return launch_composite(h, fl, xv, f64, nt, npix, group_dev ? group_dev + c0 : nullptr, above, skipna, sdev, ndev);
-    });
-    h->sio = nullptr;
-    h->stream_ms[0] = io.ms_read; h->stream_ms[1] = 0; h->stream_ms[2] = io.ms_in; h->stream_ms[3] = 0;
-    if (rc != CTK_OK) {
-        // a chunk may still be on its way into a buffer: nothing of this call is in flight when it returns
-        (void)hipStreamSynchronize(h->copy_stream);
-        (void)hipStreamSynchronize(h->stream);
-        return rc;
-    }
+    }));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(sum, sdev, cells * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(n, ndev, cells * 4, hipMemcpyDeviceToHost));
@@ -279,28 +270,7 @@ extern "C" int ctk_debug_time_composite(ctk_handle *h, const int32_t *flag_dev, 
     if ((int64_t)(reps + 1) * T > 0xffffffffll) return ctk_set_error(CTK_E_INVALID, "ctk_debug_time_composite: (reps + 1) * T counts overflow uint32");
     const int64_t npix = (int64_t)ny * nx;
     const bool f64 = is_f64 != 0;
-    std::vector<hipEvent_t> ev((size_t)reps + 1, nullptr);
-    int rc = CTK_OK;
-    for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { rc = ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed"); break; }
-    if (rc == CTK_OK) rc = comp_zero(h, sum_dev, n_dev, ngroups, npix);
-    if (rc == CTK_OK) rc = launch_composite(h, flag_dev, x_dev, f64, T, npix, group_dev, above, skipna, sum_dev, n_dev);           // (warm-up)
-    for (int r = 0; r < reps && rc == CTK_OK; r++) {
-        if (hipEventRecord(ev[r], h->stream) != hipSuccess) rc = ctk_set_error(CTK_E_NODEVICE, "hipEventRecord failed");
-        if (rc == CTK_OK) rc = launch_composite(h, flag_dev, x_dev, f64, T, npix, group_dev, above, skipna, sum_dev, n_dev);
-    }
-    if (rc == CTK_OK && (hipEventRecord(ev[reps], h->stream) != hipSuccess || hipEventSynchronize(ev[reps]) != hipSuccess))
-        rc = ctk_set_error(CTK_E_NODEVICE, "ctk_debug_time_composite: event wait failed");
-    if (rc == CTK_OK) {
-        double best = 1e30, tot = 0;
-        for (int r = 0; r < reps; r++) {
-            float m = 0;
-            (void)hipEventElapsedTime(&m, ev[r], ev[r + 1]);
-            best = std::min(best, (double)m); tot += m;
-        }
-        ms2[0] = best; ms2[1] = tot / reps;
-    }
-    (void)hipStreamSynchronize(h->stream);
-    for (auto e : ev) if (e) (void)hipEventDestroy(e);
-    return rc;
+    CTKCHK(comp_zero(h, sum_dev, n_dev, ngroups, npix));
+    return time_launches(h, "ctk_debug_time_composite", reps, ms2,
+                         [&]() { return launch_composite(h, flag_dev, x_dev, f64, T, npix, group_dev, above, skipna, sum_dev, n_dev); });
 }

@@ -642,12 +642,24 @@ inline int64_t ctk_level_runs(const double *w, int64_t nlev, CtkLevelRun *runs, 
     *nsel = k;
     return nr;
 }
-// steps per chunk of the streamed entries: chunk_steps, or (0) about 256 MB of input, at least one step and at most all of them
-inline int64_t ctk_level_chunk(int64_t chunk_steps, int64_t steps, int64_t nsel, size_t plane_bytes)
+
+// ------------------------------------------------------------------------------------------------
+// rules every streamed entry shares
+// ------------------------------------------------------------------------------------------------
+// steps per chunk: chunk_steps, or (0) about 256 MB of input -- step_bytes is what one step brings in, a plane or the selected levels of
+// one --, at least min_steps (the anomaly stream: its halo) and at most all T of them
+inline int64_t ctk_stream_chunk(int64_t chunk_steps, int64_t T, size_t step_bytes, int64_t min_steps = 1)
 {
-    const size_t step_bytes = (size_t)nsel * plane_bytes;
-    int64_t c = chunk_steps > 0 ? chunk_steps : (int64_t)(((size_t)256 << 20) / std::max<size_t>(step_bytes, 1));
-    return std::min<int64_t>(std::max<int64_t>(c, 1), steps);
+    const int64_t c = chunk_steps > 0 ? chunk_steps : (int64_t)(((size_t)256 << 20) / std::max<size_t>(step_bytes, 1));
+    return std::min<int64_t>(std::max<int64_t>(c, min_steps), T);
+}
+// timesteps per slice (blockIdx.y) of the kernels that give a thread 4 pixels and a slice of the T steps (k_freq, k_spell): `forced` (a
+// debug override) or as many as fill the chip with `waves` waves, within [slice_min, slice_max]; and gridDim.y <= 65535
+inline int64_t ctk_time_slice(int64_t forced, int64_t T, int64_t npix, int64_t slice_min, int64_t slice_max, int64_t waves)
+{
+    const int64_t per_slice = (npix + 255) / 256;                                   // waves per slice (4 pixels per lane)
+    const int64_t s = forced > 0 ? forced : std::min(slice_max, std::max(slice_min, (T * per_slice + waves - 1) / waves));
+    return std::max(s, (T + 65534) / 65535);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -679,12 +691,6 @@ inline CtkCompositePlan ctk_composite_plan(int elem_bytes, int64_t npix, int unr
     p.blocks = (npix + CTK_COMPOSITE_THREADS - 1) / CTK_COMPOSITE_THREADS;
     p.grid = (unsigned)std::min<int64_t>(p.blocks, CTK_COMPOSITE_GRID_MAX);
     return p;
-}
-// steps per chunk of the host entries: chunk_steps, or (0) about 256 MB of field, at least one step and at most all of them
-inline int64_t ctk_composite_chunk(int64_t chunk_steps, int64_t T, size_t plane_bytes)
-{
-    int64_t c = chunk_steps > 0 ? chunk_steps : (int64_t)(((size_t)256 << 20) / std::max<size_t>(plane_bytes, 1));
-    return std::min<int64_t>(std::max<int64_t>(c, 1), T);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -69,26 +69,14 @@ __global__ __launch_bounds__(256) void k_freq(const int32_t *__restrict__ flag, 
 // ------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------
-constexpr int64_t kFreqSliceMax = 64;        // timesteps per slice once the chip is full (profiles/NOTES.md: the sweep)
+constexpr int64_t kSliceMax = 64;            // timesteps per slice of k_freq and k_spell once the chip is full (profiles/NOTES.md: the sweeps)
+constexpr int64_t kSliceWaves = 16384;       // waves that fill 256 CUs several times over
 constexpr int64_t kFreqSliceMin = 8;
-constexpr int64_t kFreqWaves = 16384;        // waves that fill 256 CUs several times over
-
-static int64_t freq_slice(const ctk_handle *h, int64_t T, int64_t npix)
-{
-    int64_t s;
-    if (h->fq_slice_dbg > 0) {
-        s = h->fq_slice_dbg;
-    } else {
-        const int64_t waves = (npix + 255) / 256;                                   // waves per slice (4 pixels per lane)
-        s = std::min(kFreqSliceMax, std::max(kFreqSliceMin, (T * waves + kFreqWaves - 1) / kFreqWaves));
-    }
-    return std::max(s, (T + 65534) / 65535);                                        // gridDim.y <= 65535
-}
 
 // counts += k_freq(flag[0..T)) on the handle's stream; group_dev: T device ints (nullptr: one group)
 static int launch_freq(ctk_handle *h, const int32_t *flag_dev, int64_t T, int64_t npix, const int32_t *group_dev, int32_t above, uint32_t *counts_dev)
 {
-    const int64_t slice = freq_slice(h, T, npix);
+    const int64_t slice = ctk_time_slice(h->fq_slice_dbg, T, npix, kFreqSliceMin, kSliceMax, kSliceWaves);
     const int64_t bx = ((npix + 3) / 4 + 255) / 256;
     if (bx > 0x7fffffffll) return ctk_set_error(CTK_E_RANGE, "ctk_frequency: a plane of %lld pixels is too large", (long long)npix);
     const dim3 grid((unsigned)bx, (unsigned)((T + slice - 1) / slice));
@@ -106,8 +94,9 @@ static int launch_freq(ctk_handle *h, const int32_t *flag_dev, int64_t T, int64_
     return CTK_OK;
 }
 
-// arguments shared by the three entries; the group ids go to the device (fq_group) when there are several groups
-static int freq_prepare(ctk_handle *h, const char *name, int64_t T, int ny, int nx, const int32_t *group, int ngroups, const int32_t **group_dev)
+// the arguments every grouped map over a slab shares (frequency, composite, spells): handle, shape, T within the uint32 maps, group ids
+// in [0, ngroups); the handle's device is current afterwards
+static int group_args_check(ctk_handle *h, const char *name, int64_t T, int ny, int nx, const int32_t *group, int ngroups)
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "%s: null handle", name);
     if (T < 1 || ny < 1 || nx < 1) return ctk_set_error(CTK_E_INVALID, "%s: bad shape (T=%lld ny=%d nx=%d)", name, (long long)T, ny, nx);
@@ -118,6 +107,13 @@ static int freq_prepare(ctk_handle *h, const char *name, int64_t T, int ny, int 
         for (int64_t t = 0; t < T; t++)
             if (group[t] < 0 || group[t] >= ngroups) return ctk_set_error(CTK_E_INVALID, "%s: group[%lld] = %d is not in [0, %d)", name, (long long)t, group[t], ngroups);
     HIPCHK(hipSetDevice(h->device));
+    return CTK_OK;
+}
+
+// ... and the group ids go to the device (fq_group) when there are several groups
+static int freq_prepare(ctk_handle *h, const char *name, int64_t T, int ny, int nx, const int32_t *group, int ngroups, const int32_t **group_dev)
+{
+    CTKCHK(group_args_check(h, name, T, ny, nx, group, ngroups));
     *group_dev = nullptr;
     if (group && ngroups > 1) {                                     // (one group: every id is 0, the kernel needs none)
         CTKCHK(ensure(h, h->fq_group, (size_t)T * 4));
@@ -152,19 +148,14 @@ static int freq_stream_impl(ctk_handle *h, StreamIO &io, int64_t T, int ny, int 
     const int64_t npix = (int64_t)ny * nx;
     const size_t plane = (size_t)npix * 4, cbytes = (size_t)ngroups * plane;
     io.esz = 4;
-    io.chunk = chunk_steps > 0 ? chunk_steps : std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / plane));
-    io.chunk = std::max<int64_t>(1, std::min<int64_t>(io.chunk, T));
+    io.chunk = ctk_stream_chunk(chunk_steps, T, plane);
     CTKCHK(ensure(h, h->fq_counts, cbytes));
     uint32_t *cdev = P<uint32_t>(h->fq_counts);
     HIPCHK(hipMemsetAsync(cdev, 0, cbytes, h->stream));
     const double t0 = now_ms();
-    h->sio = &io;
-    const int rc = stream_in(h, false, T, ny, nx, [&](const void *chunk, int64_t c0, int64_t nt) -> int {
+    CTKCHK(stream_consume(h, io, false, T, ny, nx, [&](const void *chunk, int64_t c0, int64_t nt) -> int {
         return launch_freq(h, (const int32_t *)chunk, nt, npix, group_dev ? group_dev + c0 : nullptr, above, cdev);
-    });
-    h->sio = nullptr;
-    h->stream_ms[0] = io.ms_read; h->stream_ms[1] = 0; h->stream_ms[2] = io.ms_in; h->stream_ms[3] = 0;
-    CTKCHK(rc);
+    }));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(counts, cdev, cbytes, hipMemcpyDeviceToHost));
     h->ms[CTK_T_H2D] = io.ms_in; h->ms[CTK_T_TOTAL] = now_ms() - t0;
@@ -189,7 +180,7 @@ extern "C" int ctk_frequency_cb(ctk_handle *h, int64_t T, int ny, int nx, ctk_re
     return freq_stream_impl(h, io, T, ny, nx, group, ngroups, above, counts, chunk_steps, "ctk_frequency_cb");
 }
 
-// experiments (tools/freq_probe.py): timesteps per slice (0: the rule of freq_slice) and the 16-byte loads (0 plain, 1 nontemporal,
+// experiments (tools/freq_probe.py): timesteps per slice (0: the rule of ctk_time_slice) and the 16-byte loads (0 plain, 1 nontemporal,
 // -1 the default: nontemporal)
 extern "C" int ctk_debug_set_freq(ctk_handle *h, int64_t slice, int nt)
 {
@@ -209,28 +200,6 @@ extern "C" int ctk_debug_time_freq(ctk_handle *h, const int32_t *flag_dev, int64
     CTKCHK(freq_prepare(h, "ctk_debug_time_freq", T, ny, nx, group, ngroups, &group_dev));
     if ((int64_t)(reps + 1) * T > 0xffffffffll) return ctk_set_error(CTK_E_INVALID, "ctk_debug_time_freq: (reps + 1) * T counts overflow uint32");
     const int64_t npix = (int64_t)ny * nx;
-    std::vector<hipEvent_t> ev((size_t)reps + 1, nullptr);
-    int rc = CTK_OK;
-    for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { rc = ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed"); break; }
-    if (rc == CTK_OK && hipMemsetAsync(counts_dev, 0, (size_t)ngroups * npix * 4, h->stream) != hipSuccess) rc = ctk_set_error(CTK_E_NODEVICE, "hipMemsetAsync failed");
-    if (rc == CTK_OK) rc = launch_freq(h, flag_dev, T, npix, group_dev, above, counts_dev);           // (warm-up)
-    for (int r = 0; r < reps && rc == CTK_OK; r++) {
-        if (hipEventRecord(ev[r], h->stream) != hipSuccess) rc = ctk_set_error(CTK_E_NODEVICE, "hipEventRecord failed");
-        if (rc == CTK_OK) rc = launch_freq(h, flag_dev, T, npix, group_dev, above, counts_dev);
-    }
-    if (rc == CTK_OK && (hipEventRecord(ev[reps], h->stream) != hipSuccess || hipEventSynchronize(ev[reps]) != hipSuccess))
-        rc = ctk_set_error(CTK_E_NODEVICE, "ctk_debug_time_freq: event wait failed");
-    if (rc == CTK_OK) {
-        double best = 1e30, sum = 0;
-        for (int r = 0; r < reps; r++) {
-            float m = 0;
-            (void)hipEventElapsedTime(&m, ev[r], ev[r + 1]);
-            best = std::min(best, (double)m); sum += m;
-        }
-        ms2[0] = best; ms2[1] = sum / reps;
-    }
-    (void)hipStreamSynchronize(h->stream);
-    for (auto e : ev) if (e) (void)hipEventDestroy(e);
-    return rc;
+    HIPCHK(hipMemsetAsync(counts_dev, 0, (size_t)ngroups * npix * 4, h->stream));
+    return time_launches(h, "ctk_debug_time_freq", reps, ms2, [&]() { return launch_freq(h, flag_dev, T, npix, group_dev, above, counts_dev); });
 }

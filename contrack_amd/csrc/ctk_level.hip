@@ -281,7 +281,7 @@ static int level_stream_impl(ctk_handle *h, StreamIO &io, int64_t steps, int64_t
     const int64_t npix = (int64_t)ny * nx;
     const size_t plane = (size_t)npix * sizeof(VT);
     io.esz = sizeof(VT);
-    io.chunk = ctk_level_chunk(chunk_steps, steps, K, plane);
+    io.chunk = ctk_stream_chunk(chunk_steps, steps, (size_t)K * plane);
     const double t_call = now_ms();
     h->lv_T = -1; h->lv_gen++;                                         // the resident mean (if any) is dropped or about to be overwritten
     CTKCHK(stream_setup(h, (size_t)io.chunk * (size_t)K * plane, 0, io.read != nullptr));

@@ -72,8 +72,7 @@ static int life_stream_impl(ctk_handle *h, StreamIO &io, bool f64, int64_t T, in
     io.esz2 = 4;
     io.ahead = true;
     const size_t plane = (size_t)ny * nx * io.esz;
-    io.chunk = chunk_steps > 0 ? chunk_steps : std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / plane));
-    io.chunk = std::max<int64_t>(1, std::min<int64_t>(io.chunk, T));
+    io.chunk = ctk_stream_chunk(chunk_steps, T, plane);
     int32_t wshift = 0, limb_bits = 0;
     CTKCHK(life_weights(h, wrow, ny, nx, &wshift, &limb_bits));
     h->lc_f64 = f64; h->lc_T = T; h->lc_ny = ny; h->lc_nx = nx;
@@ -83,28 +82,17 @@ static int life_stream_impl(ctk_handle *h, StreamIO &io, bool f64, int64_t T, in
     std::vector<CtkLifeKey> keys;
     std::vector<ctk_life_exact> recs;
     const double t0 = now_ms();
-    int rc;
-    {
-        struct Sio { ctk_handle *h; ~Sio() { h->sio = nullptr; } } sio{h};
-        h->sio = &io;
-        bool first = true;
-        rc = stream_in(h, f64, T, ny, nx, [&](const void *chunk, int64_t c0, int64_t nt) -> int {
-            LifeRun r;
-            r.flag = (const int32_t *)io.dev2; r.field = chunk; r.f64 = f64; r.T = nt; r.ny = ny; r.nx = nx;
-            r.wshift = wshift; r.limb_bits = limb_bits; r.t_base = c0;
-            const int crc = life_stream_chunk(h, r, first, pick, pick_user, sorted, idx, keys, recs, all, picked);
-            first = false;
-            return crc;
-        });
-    }
-    h->stream_ms[0] = io.ms_read; h->stream_ms[1] = 0; h->stream_ms[2] = io.ms_in; h->stream_ms[3] = 0;
+    bool first = true;
+    const int rc = stream_consume(h, io, f64, T, ny, nx, [&](const void *chunk, int64_t c0, int64_t nt) -> int {
+        LifeRun r;
+        r.flag = (const int32_t *)io.dev2; r.field = chunk; r.f64 = f64; r.T = nt; r.ny = ny; r.nx = nx;
+        r.wshift = wshift; r.limb_bits = limb_bits; r.t_base = c0;
+        const int crc = life_stream_chunk(h, r, first, pick, pick_user, sorted, idx, keys, recs, all, picked);
+        first = false;
+        return crc;
+    });
     h->ms[CTK_T_H2D] = io.ms_in; h->ms[CTK_T_TOTAL] = now_ms() - t0;
-    if (rc != CTK_OK) {
-        // a chunk may still be on its way into a buffer: nothing of this call is in flight when it returns
-        (void)hipStreamSynchronize(h->copy_stream);
-        (void)hipStreamSynchronize(h->stream);
-        return rc;
-    }
+    CTKCHK(rc);
     // the chunks' rows, each sorted, become the slab's: the same sort as a resident call's, over all T steps
     h->lc_sort = life_sort(h, all.data(), all.size(), T, h->lc_host);
     // (label, t) is unique per row: the picked rows, put into the same order, are found in one pass over the sorted rows

@@ -185,26 +185,12 @@ __global__ __launch_bounds__(256) void k_spell_close(const SpellArgs a)
 // ------------------------------------------------------------------------------------------------
 // The look-back costs one plane per slice and a follow-up reads single pixels, so short slices are dearer than in k_freq
 // (profiles/NOTES.md: the sweep)
-constexpr int64_t kSpellSliceMax = 64;       // timesteps per slice once the chip is full
-constexpr int64_t kSpellSliceMin = 16;
-constexpr int64_t kSpellWaves = 16384;       // waves that fill 256 CUs several times over
-
-static int64_t spell_slice(const ctk_handle *h, int64_t T, int64_t npix)
-{
-    int64_t s;
-    if (h->sp_slice_dbg > 0) {
-        s = h->sp_slice_dbg;
-    } else {
-        const int64_t waves = (npix + 255) / 256;                                   // waves per slice (4 pixels per lane)
-        s = std::min(kSpellSliceMax, std::max(kSpellSliceMin, (T * waves + kSpellWaves - 1) / kSpellWaves));
-    }
-    return std::max(s, (T + 65534) / 65535);                                        // gridDim.y <= 65535
-}
+constexpr int64_t kSpellSliceMin = 16;       // (the other two numbers of the rule: k_freq's, ctk_freq.hip)
 
 // one chunk: a.flag[0..a.nt) with the carry of the chunk before (a.carry_in) -> publishes, a.carry_out
 static int launch_spell(ctk_handle *h, SpellArgs a)
 {
-    a.slice = spell_slice(h, a.nt, a.npix);
+    a.slice = ctk_time_slice(h->sp_slice_dbg, a.nt, a.npix, kSpellSliceMin, kSliceMax, kSliceWaves);
     const int64_t bx = ((a.npix + 3) / 4 + 255) / 256;
     if (bx > 0x7fffffffll) return ctk_set_error(CTK_E_RANGE, "ctk_spells: a plane of %lld pixels is too large", (long long)a.npix);
     const dim3 grid((unsigned)bx, (unsigned)((a.nt + a.slice - 1) / a.slice));
@@ -232,26 +218,10 @@ static int launch_spell_close(ctk_handle *h, const SpellArgs &a)
 static int spell_prepare(ctk_handle *h, const char *name, int64_t T, int ny, int nx, const int32_t *group, int ngroups, const int64_t *seg_starts,
                          int64_t nseg, int by_id, int64_t min_duration, SpellArgs *a)
 {
-    if (!h) return ctk_set_error(CTK_E_INVALID, "%s: null handle", name);
-    if (T < 1 || ny < 1 || nx < 1) return ctk_set_error(CTK_E_INVALID, "%s: bad shape (T=%lld ny=%d nx=%d)", name, (long long)T, ny, nx);
-    if (T > 0xffffffffll) return ctk_set_error(CTK_E_INVALID, "%s: T=%lld timesteps do not fit the uint32 durations (at most 2^32 - 1)", name, (long long)T);
-    if (ngroups < 1) return ctk_set_error(CTK_E_INVALID, "%s: ngroups=%d (at least 1)", name, ngroups);
-    if (!group && ngroups != 1) return ctk_set_error(CTK_E_INVALID, "%s: group is NULL but ngroups=%d (NULL means one group)", name, ngroups);
+    CTKCHK(group_args_check(h, name, T, ny, nx, group, ngroups));
     if (by_id != 0 && by_id != 1) return ctk_set_error(CTK_E_INVALID, "%s: by_id=%d (0 or 1)", name, by_id);
     if (min_duration < 1) return ctk_set_error(CTK_E_INVALID, "%s: min_duration=%lld (at least 1)", name, (long long)min_duration);
-    if (nseg < 0 || (nseg > 0 && !seg_starts)) return ctk_set_error(CTK_E_INVALID, "%s: nseg=%lld with%s segment starts", name, (long long)nseg, seg_starts ? "" : " NULL");
-    if (group)
-        for (int64_t t = 0; t < T; t++)
-            if (group[t] < 0 || group[t] >= ngroups) return ctk_set_error(CTK_E_INVALID, "%s: group[%lld] = %d is not in [0, %d)", name, (long long)t, group[t], ngroups);
-    if (nseg > 0) {
-        if (seg_starts[0] != 0) return ctk_set_error(CTK_E_INVALID, "%s: seg_starts[0] = %lld, must be 0", name, (long long)seg_starts[0]);
-        for (int64_t k = 1; k < nseg; k++)
-            if (seg_starts[k] <= seg_starts[k - 1])
-                return ctk_set_error(CTK_E_INVALID, "%s: segment starts must be strictly increasing (seg_starts[%lld] = %lld after %lld)", name, (long long)k,
-                                     (long long)seg_starts[k], (long long)seg_starts[k - 1]);
-        if (seg_starts[nseg - 1] >= T) return ctk_set_error(CTK_E_INVALID, "%s: segment start %lld beyond the %lld timesteps", name, (long long)seg_starts[nseg - 1], (long long)T);
-    }
-    HIPCHK(hipSetDevice(h->device));
+    CTKCHK(segment_starts_check(name, seg_starts, nseg, T));
     const int64_t npix = (int64_t)ny * nx;
     *a = SpellArgs();
     a->npix = npix;
@@ -315,8 +285,7 @@ static int spell_stream_impl(ctk_handle *h, StreamIO &io, int64_t T, int ny, int
     const int64_t npix = a.npix;
     const size_t plane = (size_t)npix * 4, obytes = (size_t)ngroups * plane;
     io.esz = 4;
-    io.chunk = chunk_steps > 0 ? chunk_steps : std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / plane));
-    io.chunk = std::max<int64_t>(1, std::min<int64_t>(io.chunk, T));
+    io.chunk = ctk_stream_chunk(chunk_steps, T, plane);
     CTKCHK(ensure(h, h->sp_out, 3 * obytes));
     uint32_t *odev = P<uint32_t>(h->sp_out);
     HIPCHK(hipMemsetAsync(odev, 0, 3 * obytes, h->stream));
@@ -326,17 +295,13 @@ static int spell_stream_impl(ctk_handle *h, StreamIO &io, int64_t T, int ny, int
     const bool none = min_duration > T;                             // (no spell is longer than the slab; the slab is still read)
     const double t0 = now_ms();
     int64_t k = 0;
-    h->sio = &io;
-    const int rc = stream_in(h, false, T, ny, nx, [&](const void *chunk, int64_t c0, int64_t nt) -> int {
+    CTKCHK(stream_consume(h, io, false, T, ny, nx, [&](const void *chunk, int64_t c0, int64_t nt) -> int {
         if (none) return CTK_OK;
         a.flag = (const int32_t *)chunk; a.nt = nt;
         a.words = words ? (const int32_t *)(words + c0) : nullptr;
         spell_carries(h, &a, k++);
         return launch_spell(h, a);
-    });
-    h->sio = nullptr;
-    h->stream_ms[0] = io.ms_read; h->stream_ms[1] = 0; h->stream_ms[2] = io.ms_in; h->stream_ms[3] = 0;
-    CTKCHK(rc);
+    }));
     if (!none) {
         spell_carries(h, &a, k);
         CTKCHK(launch_spell_close(h, a));
@@ -368,7 +333,7 @@ extern "C" int ctk_spells_cb(ctk_handle *h, int64_t T, int ny, int nx, ctk_read_
     return spell_stream_impl(h, io, T, ny, nx, group, ngroups, seg_starts, nseg, above, by_id, min_duration, events, steps, longest, chunk_steps, "ctk_spells_cb");
 }
 
-// experiments and tests (tools/spell_probe.py): timesteps per slice (0: the rule of spell_slice)
+// experiments and tests (tools/spell_probe.py): timesteps per slice (0: the rule of ctk_time_slice)
 extern "C" int ctk_debug_set_spell(ctk_handle *h, int64_t slice)
 {
     if (!h || slice < 0) return ctk_set_error(CTK_E_INVALID, "ctk_debug_set_spell: null handle or negative slice");
@@ -390,30 +355,8 @@ extern "C" int ctk_debug_time_spell(ctk_handle *h, const int32_t *flag_dev, int6
     a.flag = flag_dev; a.nt = T; a.above = above;
     a.events = events_dev; a.steps = steps_dev; a.longest = longest_dev;
     spell_carries(h, &a, 0);
-    std::vector<hipEvent_t> ev((size_t)reps + 1, nullptr);
-    int rc = CTK_OK;
-    for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { rc = ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed"); break; }
-    if (rc == CTK_OK && (hipMemsetAsync(events_dev, 0, obytes, h->stream) != hipSuccess || hipMemsetAsync(steps_dev, 0, obytes, h->stream) != hipSuccess ||
-                         hipMemsetAsync(longest_dev, 0, obytes, h->stream) != hipSuccess))
-        rc = ctk_set_error(CTK_E_NODEVICE, "hipMemsetAsync failed");
-    if (rc == CTK_OK) rc = launch_spell(h, a);                                                        // (warm-up)
-    for (int r = 0; r < reps && rc == CTK_OK; r++) {
-        if (hipEventRecord(ev[r], h->stream) != hipSuccess) rc = ctk_set_error(CTK_E_NODEVICE, "hipEventRecord failed");
-        if (rc == CTK_OK) rc = launch_spell(h, a);
-    }
-    if (rc == CTK_OK && (hipEventRecord(ev[reps], h->stream) != hipSuccess || hipEventSynchronize(ev[reps]) != hipSuccess))
-        rc = ctk_set_error(CTK_E_NODEVICE, "ctk_debug_time_spell: event wait failed");
-    if (rc == CTK_OK) {
-        double best = 1e30, sum = 0;
-        for (int r = 0; r < reps; r++) {
-            float m = 0;
-            (void)hipEventElapsedTime(&m, ev[r], ev[r + 1]);
-            best = std::min(best, (double)m); sum += m;
-        }
-        ms2[0] = best; ms2[1] = sum / reps;
-    }
-    (void)hipStreamSynchronize(h->stream);
-    for (auto e : ev) if (e) (void)hipEventDestroy(e);
-    return rc;
+    HIPCHK(hipMemsetAsync(events_dev, 0, obytes, h->stream));
+    HIPCHK(hipMemsetAsync(steps_dev, 0, obytes, h->stream));
+    HIPCHK(hipMemsetAsync(longest_dev, 0, obytes, h->stream));
+    return time_launches(h, "ctk_debug_time_spell", reps, ms2, [&]() { return launch_spell(h, a); });
 }

@@ -232,8 +232,8 @@ def test_library_refusals_name_the_value(trk):
 
     assert call()[0] == 0
     for kw, word in ((dict(md=0), "min_duration=0"), (dict(by_id=2), "by_id=2"), (dict(T=0), "T=0"), (dict(nx=0), "nx=0"), (dict(T=2 ** 32), "T=4294967296"),
-                     (dict(G=1), "group[1] = 1"), (dict(group=None), "ngroups=2"), (dict(G=0), "ngroups=0"), (dict(seg=[1, 3]), "seg_starts[0] = 1"),
-                     (dict(seg=[0, 3, 3]), "seg_starts[2] = 3"), (dict(seg=[0, 8]), "start 8"), (dict(ev=None), "null buffer"), (dict(chunk=-2), "chunk_steps=-2")):
+                     (dict(G=1), "group[1] = 1"), (dict(group=None), "ngroups=2"), (dict(G=0), "ngroups=0"), (dict(seg=[1, 3]), "starts[0] = 1"),
+                     (dict(seg=[0, 3, 3]), "starts[2] = 3"), (dict(seg=[0, 8]), "starts at step 8, the slab has 8 steps"), (dict(ev=None), "null buffer"), (dict(chunk=-2), "chunk_steps=-2")):
         rc, msg = call(**kw)
         assert rc == -1 and word in msg, (kw, rc, msg)
     assert L.ctk_spells(None, flag.ctypes.data, 8, 2, 3, None, 1, None, 0, 0, 1, 1, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, 0) == -1
