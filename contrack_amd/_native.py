@@ -50,6 +50,7 @@ EXPORTS = [
     "ctk_debug_composite_plan", "ctk_debug_set_composite", "ctk_debug_composite_launch", "ctk_debug_time_composite",
     "ctk_centred_f32_dev", "ctk_centred_f64_dev", "ctk_centred_f32", "ctk_centred_f64", "ctk_centred_cb",
     "ctk_debug_centred_plan", "ctk_debug_set_centred", "ctk_debug_centred_launch", "ctk_debug_time_centred",
+    "ctk_band_dev", "ctk_band_f32", "ctk_band_f64", "ctk_band_cb", "ctk_debug_band_plan", "ctk_debug_set_band", "ctk_debug_band_launch", "ctk_debug_time_band",
 ]
 
 READ_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)       # ctk_read_chunk_fn
@@ -78,6 +79,17 @@ class InvalidArgumentError(ContrackHipError, ValueError):
     catches the same mistakes of the frequency entries"""
 
 
+class BandSpec(C.Structure):
+    """ctk_band_spec of include/contrack_hip.h"""
+    _fields_ = [("y0", C.c_int32), ("y1", C.c_int32), ("above", C.c_int32), ("nsect", C.c_int32), ("w", C.c_void_p), ("sectors", C.c_void_p),
+                ("columns", C.c_int32), ("resident", C.c_int32), ("resident_gen", C.c_uint64)]
+
+
+class BandOut(C.Structure):
+    """ctk_band_out of include/contrack_hip.h"""
+    _fields_ = [(n, C.c_void_p) for n in "cnt area wx sec_cnt sec_area sec_wx".split()]
+
+
 class FormQuery(C.Structure):
     """ctk_form_query of include/contrack_hip_debug.h"""
     _fields_ = [(n, C.c_int64) for n in (
@@ -88,6 +100,14 @@ class FormPlan(C.Structure):
     """ctk_form_plan of include/contrack_hip_debug.h"""
     _fields_ = [(n, C.c_int64) for n in (
         "thr_kind thr_u7 thr_rbt thr_grid rowcount_threads v0b v0_ok v0_runs need_glb spec_launched spec_bits missing missing_bits next_spec overlap_form extent_form write_kernel write_rb write_sub write_kb write_batched write_lds write_grid write_shape chunk_copy runval_threads compact_init_threads count_staged count_fused filter_sys filter_passes filter_blk filter_two_pc filter_nb filter_unite filter_merged filter_bits filter_bits_sync round_blk round_two_pc round_nb rowcount_groups").split()]
+
+
+def debug_band_plan(T, nx, aligned16=True, form=-1, rows=-1):
+    """ctk_debug_band_plan: what ctk_band_plan (csrc/ctk_forms.h) decides, as a dict (form 0 vector / 1 general, rows in flight, threads
+    per step, workgroups); no handle, no GPU"""
+    v = np.zeros(4, dtype=np.int64)
+    check(lib().ctk_debug_band_plan(int(T), int(nx), int(bool(aligned16)), int(form), int(rows), v.ctypes.data))
+    return dict(form=int(v[0]), rows=int(v[1]), quads=int(v[2]), grid=int(v[3]))
 
 
 def debug_percentile_field_plan(keybytes, max_pool_steps, ngroups, window):
@@ -232,6 +252,15 @@ def lib():
     L.ctk_debug_set_centred.argtypes = [p, i32, i32, i32]
     L.ctk_debug_centred_launch.argtypes = [p, p]
     L.ctk_debug_time_centred.argtypes = [p, p, i32, i64, i32, i32] + stamp_args + [p, p, i32, i32, C.POINTER(dbl)]
+    band_tail = [C.POINTER(BandSpec), C.POINTER(BandOut)]
+    L.ctk_band_dev.argtypes = [p, p, p, i32, i64, i32, i32] + band_tail
+    for fn in (L.ctk_band_f32, L.ctk_band_f64):
+        fn.argtypes = [p, p, p, i64, i32, i32] + band_tail + [i64]
+    L.ctk_band_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, READ_CHUNK_FN, p] + band_tail + [i64]
+    L.ctk_debug_band_plan.argtypes = [i64, i32, i32, i32, i32, p]
+    L.ctk_debug_set_band.argtypes = [p, i32, i32]
+    L.ctk_debug_band_launch.argtypes = [p, p]
+    L.ctk_debug_time_band.argtypes = [p, p, p, i32, i64, i32, i32] + band_tail + [i32, C.POINTER(dbl)]
     L.ctk_shard_label2d.argtypes = [p, p, i64, i32, i32, p, i32, p, i32]
     L.ctk_shard_label2d_f64.argtypes = [p, p, i64, i32, i32, p, i32, p, i32]
     L.ctk_shard_halo_size.argtypes = [p, C.POINTER(sz)]
@@ -511,6 +540,65 @@ def _stamps(t, row, col, bin, nbins, hy, hx):
     if nbins < 1 or hy < 0 or hx < 0 or nbins * (2 * hy + 1) * (2 * hx + 1) >= 2 ** 31:
         raise InvalidArgumentError("nbins=%d hy=%d hx=%d: nbins >= 1, half widths >= 0 and nbins * (2 hy + 1) * (2 hx + 1) < 2^31" % (nbins, hy, hx))
     return (R,) + tuple(arrs) + (nbins, hy, hx)
+
+
+def _band_args(T, ny, nx, rows, weights, sectors, columns, above):
+    """the arguments the band entries share, checked before the library is touched (it checks them again): (y0, y1, weights float64
+    (ny,), sectors int32 (nsect, 2), above).  ValueError names the value that is wrong."""
+    T, ny, nx = int(T), int(ny), int(nx)
+    if T < 1 or ny < 1 or nx < 1:
+        raise ValueError("bad shape (T=%d ny=%d nx=%d)" % (T, ny, nx))
+    if ny * nx > 2 ** 32 - 1:
+        raise ValueError("a plane of ny * nx = %d pixels does not fit the uint32 counts (at most 2^32 - 1)" % (ny * nx))
+    try:
+        y0, y1 = (int(v) for v in rows)
+    except (TypeError, ValueError):
+        raise ValueError("rows must be (y0, y1), not %r" % (rows,))
+    if not 0 <= y0 < y1 <= ny:
+        raise ValueError("the band [%d, %d) is not inside the %d rows" % (y0, y1, ny))
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (ny,):
+        raise ValueError("weights must hold one value per row (%d), not shape %s" % (ny, w.shape))
+    if not np.all(np.isfinite(w)):
+        raise ValueError("each weight must be finite")
+    sec = np.zeros((0, 2), dtype=np.int32) if sectors is None else np.asarray(sectors)
+    if sec.size == 0:
+        sec = np.zeros((0, 2), dtype=np.int32)
+    if sec.ndim != 2 or sec.shape[1] != 2 or sec.dtype.kind not in "iu":
+        raise ValueError("sectors must be integer pairs (x0, len)")
+    for k, (x0, ln) in enumerate(sec.tolist()):
+        if not (0 <= x0 < nx and 1 <= ln <= nx):
+            raise ValueError("sector %d = (x0=%d, len=%d) needs 0 <= x0 < %d and 1 <= len <= %d" % (k, x0, ln, nx, nx))
+    if not columns and sec.shape[0] == 0:
+        raise ValueError("neither the column tables nor a sector is asked for")
+    return y0, y1, w, np.ascontiguousarray(sec, dtype=np.int32), _above(above)
+
+
+class _BandCall:
+    """the ctypes structures of ONE call of a band entry, made from checked arguments (_band_args): spec, the host outputs as a dict of
+    arrays, their structure"""
+
+    def __init__(self, T, ny, nx, rows, weights, sectors, columns, above, field, resident_gen=None):
+        y0, y1, w, sec, above = _band_args(T, ny, nx, rows, weights, sectors, columns, above)
+        T, ny, nx = int(T), int(ny), int(nx)
+        self.T, self.ny, self.nx, self.nsect, self.field, self.columns = T, ny, nx, sec.shape[0], bool(field), bool(columns)
+        self._keep = (w, sec)
+        self.spec = BandSpec(y0, y1, above, sec.shape[0], w.ctypes.data, sec.ctypes.data if sec.shape[0] else None, int(bool(columns)),
+                             int(resident_gen is not None), 0 if resident_gen is None else int(resident_gen))
+        self.arrays = {}
+        if columns:
+            self.arrays.update(cnt=np.empty((T, nx), np.uint32), area=np.empty((T, nx), np.float64))
+            if field:
+                self.arrays["wx"] = np.empty((T, nx), np.float64)
+        if self.nsect:
+            self.arrays.update(sec_cnt=np.empty((T, self.nsect), np.uint32), sec_area=np.empty((T, self.nsect), np.float64))
+            if field:
+                self.arrays["sec_wx"] = np.empty((T, self.nsect), np.float64)
+
+    def out(self, pointers=None):
+        """ctk_band_out of the host arrays, or of `pointers` (name -> device address)"""
+        src = {k: a.ctypes.data for k, a in self.arrays.items()} if pointers is None else pointers
+        return BandOut(*[src.get(n) for n in "cnt area wx sec_cnt sec_area sec_wx".split()])
 
 
 def _field_dtype(x):
@@ -1194,6 +1282,84 @@ class Tracker:
         ms = (C.c_double * 2)()
         check(lib().ctk_debug_time_composite(self._h, flag_dev, x_dev, int(bool(f64)), int(T), int(ny), int(nx), _ptr(g), G, _above(above),
                                              int(bool(skipna)), sum_dev, n_dev, int(reps), ms))
+        return float(ms[0]), float(ms[1])
+
+    # ---- reductions over space per step: Hovmoeller columns and sector series (ctk_band.hip) ----------------------------
+    def band(self, flag, rows, weights, x=None, sectors=None, columns=True, above=0, chunk_steps=0, resident_gen=None, resident_f64=False):
+        """per step t of an int32 (T, ny, nx) host slab and column c, over the rows [y0, y1) = `rows` with flag > above: cnt (uint32),
+        area = the float64 sum of weights[y] in rising y and, with a float32 / float64 field x of the same shape, wx = the same sum of
+        weights[y] * x; per sector (x0, len) of `sectors` -- the columns x0, x0 + 1, ... modulo nx -- sec_cnt, sec_area, sec_wx: the
+        column values added in that order (ctk_band_f32 / _f64: chunks of `chunk_steps` time steps pass through the device, 0: about
+        256 MB each).  columns False: only the sector tables come back.  resident_gen: the field is the anomaly slab
+        anomalies(keep_resident=True) left on the device, of that resident_generation() (resident_f64: its type).  Returns a dict of
+        (T, nx) and (T, nsect) arrays."""
+        flag = _flag_i32(flag, "band_cb, or contrack.band_numpy")
+        T, ny, nx = flag.shape
+        if x is not None:
+            x = np.ascontiguousarray(x, dtype=_field_dtype(np.asarray(x).dtype))
+            if x.shape != flag.shape:
+                raise ValueError("the field has shape %s, the flag %s" % (x.shape, flag.shape))
+            if resident_gen is not None:
+                raise ValueError("a field is given and the resident anomaly slab is named as well")
+        f64 = x.dtype == np.float64 if x is not None else bool(resident_f64)
+        call = _BandCall(T, ny, nx, rows, weights, sectors, columns, above, x is not None or resident_gen is not None, resident_gen)
+        if int(chunk_steps) < 0:
+            raise ValueError("chunk_steps=%d (at least 0)" % int(chunk_steps))
+        fn = lib().ctk_band_f64 if f64 else lib().ctk_band_f32
+        check(fn(self._h, flag.ctypes.data, _ptr(x), T, ny, nx, C.byref(call.spec), C.byref(call.out()), int(chunk_steps)))
+        return call.arrays
+
+    def band_cb(self, flag_reader, field_reader, shape, dtype, rows, weights, sectors=None, columns=True, above=0, chunk_steps=0, resident_gen=None):
+        """the same with the slabs read chunk by chunk: flag_reader(t0, nt, out) fills an int32 (nt, ny, nx) view of pinned memory
+        with the time steps [t0, t0 + nt), field_reader one of `dtype` (float32 / float64); the flag reader is called first.
+        field_reader None: no field, or with resident_gen the resident anomaly slab of `dtype`."""
+        T, ny, nx = (int(v) for v in shape)
+        field = field_reader is not None or resident_gen is not None
+        dt = np.dtype(dtype if dtype is not None else np.float32)
+        if field and dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("the field must be float32 or float64")
+        if field_reader is not None and resident_gen is not None:
+            raise ValueError("a field is given and the resident anomaly slab is named as well")
+        call = _BandCall(T, ny, nx, rows, weights, sectors, columns, above, field, resident_gen)
+        if int(chunk_steps) < 0:
+            raise ValueError("chunk_steps=%d (at least 0)" % int(chunk_steps))
+        tr = _Trampolines()
+        fcb = tr.reader(flag_reader, C.c_int32, (ny, nx))
+        xcb = tr.reader(field_reader, _float_ctype(dt) if field else C.c_float, (ny, nx))
+        tr.finish(lib().ctk_band_cb(self._h, dt.itemsize, T, ny, nx, fcb, None, xcb, None, C.byref(call.spec), C.byref(call.out()), int(chunk_steps)))
+        return call.arrays
+
+    def band_dev(self, flag_dev, x_dev, T, ny, nx, rows, weights, sectors=None, columns=True, above=0, f64=False, resident_gen=None):
+        """ctk_band_dev on an int32 flag and a float32 (f64: float64) field in device memory (x_dev None: no field, or with
+        resident_gen the resident anomaly slab): the same dict of arrays"""
+        field = x_dev is not None or resident_gen is not None
+        call = _BandCall(T, ny, nx, rows, weights, sectors, columns, above, field, resident_gen)
+        names = list(call.arrays)
+
+        def run(*devs):
+            out = call.out({n: (d.value if isinstance(d, C.c_void_p) else int(d)) for n, d in zip(names, devs)})
+            check(lib().ctk_band_dev(self._h, flag_dev, x_dev, 8 if f64 else 4, call.T, call.ny, call.nx, C.byref(call.spec), C.byref(out)))
+        self._download([call.arrays[n] for n in names], run)
+        return call.arrays
+
+    def debug_set_band(self, form=-1, rows=-1):
+        """test hook for the following band launches: the form (0 the 16-byte form where it is legal, 1 the general form) and the
+        widest batch of rows in flight; -1 the rule (ctk_band_plan)"""
+        check(lib().ctk_debug_set_band(self._h, int(form), int(rows)))
+
+    def debug_band_launch(self):
+        """(form, widest batch of rows, workgroups) of the last band launch; form -1: none yet"""
+        v = np.zeros(3, dtype=np.int64)
+        check(lib().ctk_debug_band_launch(self._h, v.ctypes.data))
+        return int(v[0]), int(v[1]), int(v[2])
+
+    def time_band(self, flag_dev, x_dev, T, ny, nx, rows, weights, out_dev, sectors=None, columns=True, above=0, f64=False, reps=5):
+        """k_band (with sectors: and k_band_sect) alone between HIP events; out_dev: name -> device address of the tables the request
+        needs (cnt, area, wx, sec_cnt, sec_area, sec_wx): (best, mean) ms per launch"""
+        call = _BandCall(T, ny, nx, rows, weights, sectors, columns, above, x_dev is not None)
+        out = call.out({k: (v.value if isinstance(v, C.c_void_p) else int(v)) for k, v in out_dev.items()})
+        ms = (C.c_double * 2)()
+        check(lib().ctk_debug_time_band(self._h, flag_dev, x_dev, 8 if f64 else 4, call.T, call.ny, call.nx, C.byref(call.spec), C.byref(out), int(reps), ms))
         return float(ms[0]), float(ms[1])
 
     # ---- block-centred composite (the step after README.rst:198-228) --------------------------------------------------

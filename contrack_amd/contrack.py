@@ -324,6 +324,94 @@ def composite_numpy(flag, x, group=None, above=0, skipna=False, chunk_steps=None
     return (s[0], n[0]) if group is None else (s, n)
 
 
+def lon_sector(lon, west, east):
+    """the columns of a longitude sector as band_numpy takes them: (x0, len), the len columns x0, x0 + 1, ... modulo nx whose longitude
+    lies between `west` and `east` going EAST from west.  lon: the longitude coordinate, ascending, on a 0...360 or a -180...180 grid;
+    the bounds may use either convention (all values are compared modulo 360); west > east is a sector that wraps, bounds a whole
+    turn apart (0 and 360, -180 and 180) are the full circle, west == east is the one column at that longitude.  ValueError for a
+    sector that selects no column."""
+    lon = np.asarray(lon, dtype=np.float64).reshape(-1)
+    west, east = float(west), float(east)
+    if lon.size == 0 or not (np.isfinite(west) and np.isfinite(east)) or np.any(np.diff(lon) <= 0):
+        raise ValueError("lon must be a non-empty ascending coordinate and the bounds finite")
+    span = east - west
+    span = 360.0 if (span != 0 and span % 360.0 == 0) else span % 360.0
+    sel = np.mod(lon - west, 360.0) <= span
+    n = int(np.count_nonzero(sel))
+    if n == 0:
+        raise ValueError("the sector ({}, {}) selects no column".format(west, east))
+    if n == lon.size:
+        return 0, n
+    first = np.nonzero(sel & ~np.roll(sel, 1))[0]
+    if len(first) != 1:
+        raise ValueError("the sector ({}, {}) does not select neighbouring columns of this longitude coordinate".format(west, east))
+    return int(first[0]), n
+
+
+def band_total(weights, rows, sectors=None):
+    """what band_numpy gives where every pixel of the band is flagged -- the denominator of a fraction: the float64 sum of
+    weights[y0:y1] in rising y (one column), or with sectors the (nsect,) sums of that value over each sector's len columns"""
+    w = np.asarray(weights, dtype=np.float64)
+    y0, y1 = (int(v) for v in rows)
+    col = np.float64(0.0)
+    for y in range(y0, y1):
+        col = col + w[y]
+    if sectors is None:
+        return col
+    out = np.zeros(len(sectors), dtype=np.float64)
+    for s, (_x0, ln) in enumerate(sectors):
+        for _ in range(int(ln)):
+            out[s] = out[s] + col
+    return out
+
+
+def band_fraction(area, total):
+    """area / total in float64 (total: band_total's scalar, or its (nsect,) array against (..., nsect) areas); numpy's NaN / inf
+    where the total is 0"""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.asarray(area, dtype=np.float64) / np.asarray(total, dtype=np.float64)
+
+
+def band_numpy(flag, rows, weights, x=None, sectors=None, columns=True, above=0, chunk_steps=None, device=None, shape=None, dtype=None,
+               resident_gen=None):
+    """the reductions over space that keep the time axis, on a (time, lat, lon) integer flag slab: per time step t and column c, over
+    the latitude rows [y0, y1) = `rows` with flag > above,
+        cnt[t, c] (uint32) how many,  area[t, c] the float64 sum of weights[y] IN RISING y,  wx[t, c] that of weights[y] * x[t, y, c]
+    (wx only with a field x of the same shape: float64 stays, everything else is taken as float32; a value at an unflagged pixel
+    reaches nothing, a NaN at a flagged one propagates) -- the columns of a time-longitude (Hovmoeller) diagram -- and per sector
+    (x0, len) of `sectors` (see lon_sector; the columns x0, x0 + 1, ... modulo nx) sec_cnt, sec_area, sec_wx[t, s]: the column
+    values added in that column order -- a blocked-area series.  weights: float64 (ny,), e.g. row_weights(lat, dlat, dlon) for km^2.
+    Returns a dict of (T, nx) and (T, nsect) arrays; columns=False: the sector tables only (the column tables then never leave the
+    device).  The sums run on the GPU (ctk_band_*) and are the same bits whatever chunk_steps: time steps per chunk on the slabs' way
+    through the device (None or 0: about 256 MB).  With shape=(T, ny, nx) (and dtype for a field) flag and x may be readers
+    reader(t0, nt, out) (ctk_band_cb); flags wider than int32 are narrowed chunk by chunk (an id beyond int32 raises ValueError).
+    resident_gen: the field is the anomaly slab calc_anom left on the device (`dtype` its type) of that generation
+    (Tracker.resident_generation()); only the flags travel, and a slab that was replaced since is refused."""
+    steps = 0 if chunk_steps is None else int(chunk_steps)
+    if steps < 0:
+        raise ValueError("chunk_steps={} (at least 0)".format(steps))
+    if callable(flag) or callable(x):
+        if shape is None or (callable(x) and dtype is None):
+            raise ValueError("a reader needs shape=(T, ny, nx) and the field's dtype")
+    fread, fshape, is_array = _flag_source(flag, shape)
+    shape = tuple(int(v) for v in (fshape if shape is None else shape))
+    if x is not None and not callable(x):
+        x = x if isinstance(x, np.memmap) else np.asarray(x)
+        if tuple(x.shape) != shape:
+            raise ValueError("the field has shape {}, the flag {}".format(x.shape, shape))
+        dtype = _native._field_dtype(x.dtype)
+    dtype = np.dtype(dtype if dtype is not None else np.float32)
+    _native._band_args(shape[0], shape[1], shape[2], rows, weights, sectors, columns, above)
+    trk = _tracker(device)
+    if is_array and not callable(x):
+        return trk.band(fread, rows, weights, x, sectors, columns, above, steps, resident_gen=resident_gen, resident_f64=dtype == np.float64)
+    xread = x
+    if x is not None and not callable(x):
+        def xread(t0, nt, out, slab=x):
+            out[...] = slab[t0:t0 + nt]
+    return trk.band_cb(fread, xread, shape, dtype, rows, weights, sectors, columns, above, steps, resident_gen=resident_gen)
+
+
 def centred_stamps(t, row, col, bin=None):
     """the stamps of a block-centred composite as the library takes them: (t int64, row, col, bin int32) sorted STABLY by t -- the
     given order is kept among equal t -- which is the order of the additions.  bin None: one bin (all zeros)."""
@@ -1987,6 +2075,142 @@ class contrack(object):
             return res
         cattrs = {'long_name': 'contrack composite count', 'units': '1', 'history': attrs['history']}
         return res, self._wrap(vda, shaped(n), out_dims, coords, cattrs, name='count')
+
+    # ---- reductions over space that keep the time axis: Hovmoeller diagram and blocked-area series ---------------------------
+    def _band_tables(self, flag, lat_bounds, above, variable, chunk_steps, sectors, columns):
+        """what calc_hovmoller and calc_blocked_area share: band_numpy over the flat slab of `flag` (and of `variable`), as
+        (tables, dims, member, M, T, (y0, y1), weights, bounds, fda)"""
+        self._ensure_set_up()
+        fda = self.ds[flag]
+        dims, member = self._consumer_dims(flag)
+        if np.dtype(fda.dtype).kind not in "iub":
+            raise ValueError("flag variable {!r} is not an integer field".format(flag))
+        lat = np.asarray(self.ds[self._latitude_name].data, dtype=np.float64)
+        bounds = (lat.min(), lat.max()) if lat_bounds is None else lat_bounds
+        rows = np.nonzero((lat >= min(bounds)) & (lat <= max(bounds)))[0]
+        if len(rows) == 0 or not np.array_equal(rows, np.arange(rows[0], rows[-1] + 1)):
+            raise ValueError("latitude band {} selects no contiguous rows".format(lat_bounds))
+        y01 = (int(rows[0]), int(rows[-1]) + 1)
+        weights = row_weights(np.asarray(self.ds[self._latitude_name].data), self._dlat, self._dlon).astype(np.float64)     # contrack.py:846-848
+        T = fda.shape[dims.index(self._time_name)]
+        M = None if member is None else fda.shape[dims.index(member)]
+        vda = vdims = vtype = None
+        if variable is not None:
+            vda = self.ds[variable]
+            vdims = tuple(vda.dims)
+            if sorted(vdims) != sorted(dims) or any(vda.shape[vdims.index(d)] != fda.shape[dims.index(d)] for d in dims):
+                raise ValueError("the variable {!r} has dims {}, the flag variable {!r} has {}: they must be the same".format(variable, vdims, flag, dims))
+            vtype = _native._field_dtype(vda.dtype)
+        if chunk_steps is None:
+            flags = self._flat_slab(fda, dims, member)
+            field, gen = None, None
+            if vda is not None:
+                field = self._flat_slab(vda, vdims, member).astype(vtype, copy=False)
+                # (the anomaly slab calc_anom left in HBM: only the flags cross PCIe)
+                if self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, field.shape, vtype == np.float64):
+                    field, gen = None, self._anom_resident[1]
+            tables = band_numpy(flags, y01, weights, field, sectors, columns, above=above, dtype=vtype, resident_gen=gen)
+        else:
+            if member is None:
+                fread, shape, _ = self._time_reader(fda, dims, integer=True)
+                vread = None if vda is None else self._time_reader(vda, vdims)[0]
+            else:
+                fread, shape, _ = self._member_reader(fda, dims, member, integer=True)
+                vread = None if vda is None else self._member_reader(vda, vdims, member)[0]
+            tables = band_numpy(fread, y01, weights, vread, sectors, columns, above=above, chunk_steps=chunk_steps, shape=shape, dtype=vtype)
+        return tables, dims, member, M, T, y01, weights, (float(min(bounds)), float(max(bounds))), fda
+
+    def _band_layout(self, dims, member, M, T, last, last_values):
+        """(out_dims, coords, shaped) of a (M * T or T, n) table as a labelled array: the flag variable's own dims without the latitude,
+        `last` (the longitude dim, or 'sector') in the longitude's place"""
+        have = ((member,) if member is not None else ()) + (self._time_name, last)
+        out_dims = tuple(last if d == self._longitude_name else d for d in dims if d != self._latitude_name)
+
+        def shaped(a):
+            a = a.reshape(((M,) if member is not None else ()) + (T, a.shape[-1]))
+            return np.ascontiguousarray(a.transpose([have.index(d) for d in out_dims]))
+        coords = {self._time_name: np.asarray(self.ds[self._time_name].data), last: last_values}
+        if member is not None:
+            coords[member] = self._dim_values(member, M)
+        return out_dims, coords, shaped
+
+    def calc_hovmoller(self, flag='flag', lat_bounds=(50, 75), stat='fraction', above=0, variable=None, chunk_steps=None):
+        """time-longitude (Hovmoeller) diagram of a latitude band: per time step and longitude, over the rows inside lat_bounds (None:
+        every row) with flag > above,
+            stat='fraction'   the blocked share of the band's area (area / the band's whole area, '1'),
+            stat='area'       the blocked area in km^2, summed with the reference's area weights (contrack.py:846-848, :874),
+            stat='count'      the number of blocked grid points (uint32),
+            stat='any'        whether any is blocked (bool),
+            stat='intensity'  the area-weighted mean of `variable` over the blocked grid points, NaN where none is.
+        Returns a labelled array over (time, longitude) -- the flag variable's own dims without the latitude, a member dimension (a
+        4-D flag, what run_contrack(segments=<dim>) writes) in its place; it is not added to the dataset.  The sums run on the GPU in
+        rising latitude (band_numpy) and are reproducible bit for bit.  chunk_steps: the variables are read slice by slice and pass
+        through chunk-sized device buffers; no slab is built on the host.  Same bits.  When `variable` is the anomaly calc_anom left
+        in HBM, only the flags are uploaded."""
+        stats = ('fraction', 'area', 'count', 'any', 'intensity')
+        if stat not in stats:
+            raise ValueError("stat must be one of {}, not {!r}".format(stats, stat))
+        if stat == 'intensity' and variable is None:
+            raise ValueError("stat='intensity' needs a variable")
+        tables, dims, member, M, T, y01, weights, bounds, fda = self._band_tables(
+            flag, lat_bounds, above, variable if stat == 'intensity' else None, chunk_steps, None, True)
+        units = '1'
+        if stat == 'fraction':
+            out = band_fraction(tables['area'], band_total(weights, y01))
+        elif stat == 'area':
+            out, units = tables['area'], 'km2'
+        elif stat == 'count':
+            out = tables['cnt']
+        elif stat == 'any':
+            out = tables['cnt'] > 0
+        else:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                out = np.where(tables['cnt'] == 0, np.nan, tables['wx'] / tables['area'])
+            units = getattr(self.ds[variable], 'attrs', {}).get('units')
+        out_dims, coords, shaped = self._band_layout(dims, member, M, T, self._longitude_name, np.asarray(self.ds[self._longitude_name].data))
+        attrs = {'long_name': 'contrack hovmoller ' + stat, 'standard_name': 'contrack hovmoller ' + stat, 'lat_bounds': bounds, 'above': int(above),
+                 'history': ' '.join(['Calculated from {} with input attributes:', 'flag > {},', 'latitude band = {},', 'stat = {},', 'variable = {}.']).format(
+                     flag, above, bounds, stat, variable if stat == 'intensity' else None)}
+        if units is not None:
+            attrs['units'] = units
+        return self._wrap(fda, shaped(out), out_dims, coords, attrs, name='hovmoller')
+
+    def calc_blocked_area(self, flag='flag', lat_bounds=None, sectors=None, above=0, variable=None, chunk_steps=None):
+        """blocked area per time step of longitude sectors of a latitude band (lat_bounds; None: every row).  sectors: a dict name ->
+        (west, east) in degrees east, either longitude convention, west > east a sector that wraps (lon_sector); None: one sector
+        'all', the full circle.  Returns a dict of labelled arrays over (time, 'sector') -- a member dimension of a 4-D flag in its
+        place --: 'area' (km^2 with the reference's area weights, contrack.py:846-848, :874), 'fraction' (area / the sector's whole
+        area), 'count' (grid points, uint32) and, with `variable`, 'intensity' (its area-weighted mean over the blocked grid points,
+        NaN where none is).  Nothing is added to the dataset.  The sums run on the GPU (band_numpy: rising latitude inside a column,
+        the sector's columns from west to east) and are reproducible bit for bit; only the (time, sector) tables leave the device.
+        chunk_steps and the resident anomaly: as calc_hovmoller."""
+        self._ensure_set_up()
+        lon = np.asarray(self.ds[self._longitude_name].data)
+        if sectors is None:
+            names, pairs = ['all'], [(0, len(lon))]
+        else:
+            names = list(sectors)
+            if not names:
+                raise ValueError("sectors is empty")
+            pairs = [lon_sector(lon, *sectors[k]) for k in names]
+        tables, dims, member, M, T, y01, weights, bounds, fda = self._band_tables(flag, lat_bounds, above, variable, chunk_steps, pairs, False)
+        maps = [('area', tables['sec_area'], 'km2'), ('fraction', band_fraction(tables['sec_area'], band_total(weights, y01, pairs)), '1'),
+                ('count', tables['sec_cnt'], '1')]
+        if variable is not None:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                inten = np.where(tables['sec_cnt'] == 0, np.nan, tables['sec_wx'] / tables['sec_area'])
+            maps.append(('intensity', inten, getattr(self.ds[variable], 'attrs', {}).get('units')))
+        out_dims, coords, shaped = self._band_layout(dims, member, M, T, 'sector', np.asarray(names))
+        history = ' '.join(['Calculated from {} with input attributes:', 'flag > {},', 'latitude band = {},', 'sectors = {},', 'variable = {}.']).format(
+            flag, above, bounds, {k: (tuple(sectors[k]) if sectors is not None else 'full circle') for k in names}, variable)
+        out = {}
+        for key, a, units in maps:
+            attrs = {'long_name': 'contrack blocked ' + key, 'standard_name': 'contrack blocked ' + key, 'lat_bounds': bounds, 'above': int(above),
+                     'history': history}
+            if units is not None:
+                attrs['units'] = units
+            out[key] = self._wrap(fda, shaped(a), out_dims, coords, attrs, name=key)
+        return out
 
     # ---- life cycle (contrack.py:798-906), consumer of `flag` (SURVEY.md section 8(f) N1) ----------------------------
     def _time_labels(self):

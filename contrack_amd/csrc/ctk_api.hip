@@ -393,6 +393,12 @@ struct ctk_handle {
     // the last launch and its workgroups
     DevBuf ce_sum, ce_n, ce_idx;
     int ce_form_dbg = -1, ce_unroll_dbg = -1, ce_threads_dbg = -1, ce_form = 0, ce_unroll = 0, ce_threads = 0; int64_t ce_grid = 0;
+    // reductions over space per step (ctk_band.hip): the column tables and the sector tables of one chunk, the weights and sectors of
+    // the running call; the test hook's form and batch of rows (ctk_debug_set_band; -1: the rule of ctk_band_plan), those of the last
+    // launch (form -1: none yet) and its workgroups
+    DevBuf bd_cols, bd_sec, bd_tab;
+    int bd_form_dbg = -1, bd_rows_dbg = -1, bd_form = -1, bd_rows = 0; int64_t bd_grid = 0;
+    void *bd_pin[2] = {nullptr, nullptr}; size_t bd_pin_cap = 0;      // pinned twins of the two table sets of a streamed call
     // percentile per group (ctk_pctl.hip): histograms per (day, distinct prefix); ranks, prefixes, lists, ids; band sweeps of the last call
     DevBuf pc_hist, pc_buf;
     int64_t pc_sweeps = 0;
@@ -630,11 +636,12 @@ extern "C" void ctk_destroy(ctk_handle *h)
                       &h->lc_rows, &h->lc_cnt, &h->lc_wlo, &h->lc_whi, &h->lc_w, &h->rv_dmap, &h->rv_dorig, &h->rv_dbox, &h->rv_inex, &h->rv_touch, &h->io_in, &h->io_out,
                       &h->sh_mask_next, &h->sh_send, &h->sh_recv, &h->sh_prev, &h->sh_elist, &h->sh_ovr_slot, &h->sh_ovr_val,
                       &h->sh_amb_list, &h->sh_counts, &h->sh_cl_shared, &h->sh_cl_sent, &h->chunk_vals, &h->lc_work, &h->lc_ovf, &h->lc_ekeys, &h->lc_offs, &h->lc_sw, &h->lc_sp, &h->lc_out, &h->lc_cross, &h->lc_gtab, &h->lc_occ, &h->lc_cp, &h->an_out, &h->an_clim, &h->an_raw, &h->an_idx, &h->an_acc, &h->an_valid, &h->lv_out, &h->lv_tab, &h->sd_parent, &h->sd_tmin, &h->sd_tmax, &h->sd_root, &h->sd_nops, &h->sd_lbox, &h->rv_pstate, &h->ci_bsum, &h->scan_bsum,
-                      &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order, &h->fq_counts, &h->fq_group, &h->sp_out, &h->sp_words, &h->sp_carry, &h->cp_sum, &h->cp_n, &h->ce_sum, &h->ce_n, &h->ce_idx, &h->seg_edge, &h->pc_hist, &h->pc_buf, &h->pf_out, &h->pf_idx, &h->sf_out, &h->sf_idx};
+                      &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order, &h->fq_counts, &h->fq_group, &h->sp_out, &h->sp_words, &h->sp_carry, &h->cp_sum, &h->cp_n, &h->ce_sum, &h->ce_n, &h->ce_idx, &h->bd_cols, &h->bd_sec, &h->bd_tab, &h->seg_edge, &h->pc_hist, &h->pc_buf, &h->pf_out, &h->pf_idx, &h->sf_out, &h->sf_idx};
     for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (h->h_blob) (void)hipHostFree(h->h_blob);
     if (h->h_small) (void)hipHostFree(h->h_small);
     if (h->h_cand) (void)hipHostFree(h->h_cand);
+    for (int b = 0; b < 2; b++) if (h->bd_pin[b]) (void)hipHostFree(h->bd_pin[b]);
     if (h->h_ops) (void)hipHostFree(h->h_ops);
     if (h->h_mail) (void)hipHostFree(h->h_mail);
     if (h->bounce) { h->bounce->destroy(); delete h->bounce; }
@@ -3957,6 +3964,7 @@ extern "C" int ctk_lifecycle_rows(ctk_handle *h, ctk_life_row *rows, int64_t cap
 #include "ctk_level.hip"
 #include "ctk_composite.hip"
 #include "ctk_centred.hip"
+#include "ctk_band.hip"
 
 // device-memory helpers for a ctypes host
 // ------------------------------------------------------------------------------------------------

@@ -694,6 +694,35 @@ inline CtkCompositePlan ctk_composite_plan(int elem_bytes, int64_t npix, int unr
 }
 
 // ------------------------------------------------------------------------------------------------
+// reductions over space per time step (ctk_band.hip): k_band, one thread per (step, 4 neighbouring columns) for ALL rows of the band
+// -- the rows of a column are never split, the float64 sums are added in rising latitude.  The vector form (16-byte nontemporal
+// loads) needs whole quads per row and a 16-byte aligned flag pointer; every other shape and alignment takes the general form, which
+// pads the columns beyond the row.  rows: the widest batch of rows whose loads a thread has in flight before it adds the first.
+// ------------------------------------------------------------------------------------------------
+#define CTK_BAND_THREADS 256
+#define CTK_BAND_ROWS 8                        // the rule's batch of rows (then 4, 2, 1 for the rest of the band)
+#define CTK_BAND_ROWS_MAX 16
+struct CtkBandPlan {
+    bool vec;                     // the 16-byte form
+    int rows;                     // the widest batch of rows in flight (a power of two)
+    int64_t quads;                // threads per step: ceil(nx / 4)
+    unsigned grid;                // workgroups: ceil(T * quads / 256) (the entries refuse a T that does not fit)
+};
+// form: a test's choice (ctk_debug_set_band: 0 the vector form where it is legal, 1 the general form), rows: its batch, rounded down
+// to a power of two and capped; -1 the rule
+inline CtkBandPlan ctk_band_plan(int64_t T, int nx, bool aligned16, int form = -1, int rows = -1)
+{
+    CtkBandPlan p = {};
+    p.vec = nx % 4 == 0 && aligned16 && form != 1;
+    int r = CTK_BAND_ROWS;
+    if (rows > 0) { r = 1; while (r * 2 <= rows && r * 2 <= CTK_BAND_ROWS_MAX) r <<= 1; }
+    p.rows = r;
+    p.quads = ((int64_t)nx + 3) / 4;
+    p.grid = (unsigned)((T * p.quads + CTK_BAND_THREADS - 1) / CTK_BAND_THREADS);
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------
 // block-centred composite (ctk_centred.hip): one lane per cell (j, i) of the window for ALL stamps of the workgroup's bin -- a bin's
 // stamps are never split, the float64 sums are added in stamp order.  There are few cells (a 41 x 81 window is 3321) and each is a
 // chain of dependent adds behind gathers.  Two forms:

@@ -721,6 +721,56 @@ int ctk_centred_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, i
                    int64_t R, const int64_t *t, const int32_t *row, const int32_t *col, const int32_t *bin, int nbins, int hy, int hx, int wrap, int skipna,
                    double *sum, uint32_t *n, int64_t chunk_steps);
 
+/* ---- reductions over space per time step: the time-longitude (Hovmoeller) diagram of a latitude band, the blocked area of a sector --
+ * Every other consumer of the flag reduces over time or per contour; these reduce over SPACE and keep the time axis: how much of a
+ * latitude band is blocked per step and longitude, and the blocked area (and the mean intensity over it) of a longitude sector per
+ * step -- the daily index a study correlates with other series.  On the int32 flag slab (T, ny, nx), the rows [y0, y1), float64 row
+ * weights w[ny] (finite, any sign) and optionally a float32 / float64 field x of the same shape, per step t and column c:
+ *   cnt[t][c]  = #{y in [y0, y1) : flag[t][y][c] > above}                                                            (uint32)
+ *   area[t][c] = from +0.0, for y = y0 .. y1 - 1 RISING:  if flag[t][y][c] > above:  s = s + w[y]                     (float64)
+ *   wx[t][c]   = the same walk with  s = s + (w[y] * (double)x[t][y][c])   -- the product rounded to float64, then added
+ * With the weights 111 dlat * 111 dlon * cos(lat) the reference's life cycle uses (contrack.py:846-848) `area` is in km^2 and adds up
+ * to what the reference calls a contour's Size (contrack.py:874); wx / area is the area-weighted mean of the field.  A value of x at
+ * an unflagged pixel is never read; a NaN or inf at a flagged pixel propagates as in np.sum (the sign bit of a NaN born from
+ * inf - inf is the hardware's).  Sectors: nsect >= 0 pairs (x0, len), 0 <= x0 < nx, 1 <= len <= nx, the columns x0, x0 + 1, ...
+ * modulo nx (len == nx: the full circle; sectors may overlap):
+ *   sec_cnt[t][s] = the sum of the column counts;  sec_area[t][s], sec_wx[t][s] = from +0.0, the column values added in that order
+ * No sum is split over threads or added atomically, so all outputs are the same bits whatever the kernel form, the chunking, the
+ * pointer alignment or the source (k_band, k_band_sect: ctk_band.hip).  ny * nx must stay below 2^32 (uint32 counts): CTK_E_RANGE.
+ * ctk_band_spec.columns != 0 asks for the column tables, nsect > 0 for the sector tables; neither: CTK_E_INVALID.  With sectors only
+ * the column tables stay in a chunk-sized buffer of the handle and never cross PCIe.  wx / sec_wx are written only with a field.
+ * resident != 0: the field is the anomaly slab ctk_anom_* left resident on this handle -- its shape and type must be the call's and
+ * its generation (ctk_resident_anom_generation) must be resident_gen, which tells the slab the caller means from a later one:
+ * CTK_E_STATE otherwise; only the flags travel then.
+ * ctk_band_dev: the slabs in HBM (x_dev NULL without resident: no field; elem_bytes 4 / 8 is the field's), the outputs device pointers.
+ * ctk_band_f32 / _f64: host arrays (x NULL: no field, or the resident slab of that type); the slabs pass through chunk-sized device
+ * buffers, chunk k+1 uploaded while chunk k is reduced (chunk_steps = 0: about 256 MB per chunk), the tables of chunk k go to row c0
+ * of the outputs.  ctk_band_cb: readers (ctk_read_chunk_fn: int32 flags, field elements of elem_bytes), contract and threading rules
+ * of ctk_composite_cb's; the flag reader is called before the field reader for every chunk; field_reader NULL: no field, or the
+ * resident slab of elem_bytes. */
+typedef struct ctk_band_spec {
+    int32_t y0, y1;                 /* the band: rows [y0, y1), 0 <= y0 < y1 <= ny */
+    int32_t above;
+    int32_t nsect;                  /* sectors, >= 0 */
+    const double *w;                /* host [ny] */
+    const int32_t *sectors;         /* host [nsect][2]: x0, len */
+    int32_t columns;                /* != 0: the column tables are wanted */
+    int32_t resident;               /* != 0: the field is the resident anomaly slab ... */
+    uint64_t resident_gen;          /* ... of this generation */
+} ctk_band_spec;
+typedef struct ctk_band_out {
+    uint32_t *cnt; double *area, *wx;                   /* [T][nx], with columns */
+    uint32_t *sec_cnt; double *sec_area, *sec_wx;       /* [T][nsect], with nsect > 0 */
+} ctk_band_out;
+int ctk_band_dev(ctk_handle *h, const int32_t *flag_dev, const void *x_dev, int elem_bytes /* 4: float32, 8: float64 */, int64_t T, int ny, int nx,
+                 const ctk_band_spec *spec, const ctk_band_out *out_dev);
+int ctk_band_f32(ctk_handle *h, const int32_t *flag, const float *x, int64_t T, int ny, int nx, const ctk_band_spec *spec, const ctk_band_out *out,
+                 int64_t chunk_steps);
+int ctk_band_f64(ctk_handle *h, const int32_t *flag, const double *x, int64_t T, int ny, int nx, const ctk_band_spec *spec, const ctk_band_out *out,
+                 int64_t chunk_steps);
+int ctk_band_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, int64_t T, int ny, int nx, ctk_read_chunk_fn flag_reader, void *flag_user,
+                ctk_read_chunk_fn field_reader, void *field_user, const ctk_band_spec *spec, const ctk_band_out *out, int64_t chunk_steps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -296,6 +296,20 @@ int ctk_debug_time_centred(ctk_handle *h, const void *x_dev, int is_f64, int64_t
                            const int32_t *col, const int32_t *bin, int nbins, int hy, int hx, int wrap, int skipna, double *sum_dev, uint32_t *n_dev,
                            int floor, int reps, double *ms2);
 
+/* what ctk_band_plan (csrc/ctk_forms.h) decides for a k_band launch over T steps of rows of nx columns, aligned16: the flag pointer is
+ * a multiple of 16; form, rows: what ctk_debug_set_band would force (-1: the rule).  out4 = { the form: 0 vector (16-byte loads), 1
+ * general; the widest batch of rows in flight; threads per step; workgroups }.  Host only: no handle, no GPU. */
+int ctk_debug_band_plan(int64_t T, int nx, int aligned16, int form, int rows, int64_t *out4);
+/* test hook for the following k_band launches on this handle: the form (0 the vector form where nx % 4 == 0 and the pointer allow it,
+ * 1 the general form) and the widest batch of rows in flight (rounded down to a power of two, at most 16); -1 the rule */
+int ctk_debug_set_band(ctk_handle *h, int form, int rows);
+/* test hook: out3 = { the form of the last k_band launch on this handle (-1: none yet), its widest batch of rows, its workgroups } */
+int ctk_debug_band_launch(ctk_handle *h, int64_t *out3);
+/* measurement (tools/band_probe.py): k_band -- and k_band_sect when the spec has sectors -- alone on slabs in device memory (the
+ * arguments of ctk_band_dev) between HIP events: one launch that is not counted, then `reps` timed ones; ms2 = { best, mean } */
+int ctk_debug_time_band(ctk_handle *h, const int32_t *flag_dev, const void *x_dev, int elem_bytes, int64_t T, int ny, int nx, const ctk_band_spec *spec,
+                        const ctk_band_out *out_dev, int reps, double *ms2);
+
 #ifdef __cplusplus
 }
 #endif
