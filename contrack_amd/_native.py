@@ -26,7 +26,7 @@ EXPORTS = [
     "ctk_result_info", "ctk_result_arrays", "ctk_result_nshards", "ctk_weights_to_limbs", "ctk_shard_extents", "ctk_shard_write",
     "ctk_shard_count_tracked", "ctk_debug_mask", "ctk_debug_label2d", "ctk_debug_set_pair_capacity", "ctk_debug_set_mailbox", "ctk_debug_set_seam_caps", "ctk_debug_shard_exchange", "ctk_debug_set_shared_ops_reserve", "ctk_debug_set_spin", "ctk_debug_set_small_threads", "ctk_debug_forms", "ctk_debug_np_sum", "ctk_debug_boundary_resolve", "ctk_debug_boundary_resolve_breaks", "ctk_set_timing", "ctk_get_timings", "ctk_get_timing_sums", "ctk_set_device_resolve", "ctk_set_fused_pass", "ctk_set_result_transfer", "ctk_expand_runs_host", "ctk_set_filter_round", "ctk_get_stats", "ctk_get_stats_n", "ctk_debug_stream_ceiling", "ctk_debug_time_relabel",
     "ctk_dev_malloc", "ctk_dev_free", "ctk_host_alloc", "ctk_host_free", "ctk_host_register", "ctk_host_unregister", "ctk_memcpy_h2d", "ctk_memcpy_d2h", "ctk_sync", "ctk_stream",
-    "ctk_synth_fill",
+    "ctk_synth_fill", "ctk_debug_live",
     "ctk_comm_unique_id", "ctk_comm_init_rccl", "ctk_comm_group_create", "ctk_comm_group_destroy", "ctk_comm_init_local", "ctk_comm_init_shm",
     "ctk_comm_destroy", "ctk_comm_rank", "ctk_comm_world", "ctk_comm_barrier", "ctk_comm_allgather_host", "ctk_comm_ops",
     "ctk_comm_set_timeout", "ctk_comm_rccl_library", "ctk_comm_failed", "ctk_comm_abort_rank", "ctk_debug_fail_at", "ctk_synth_fill_window", "ctk_checksum_i32_dev", "ctk_dev_memset", "ctk_check_flag_dev",
@@ -192,6 +192,13 @@ def forms(T, ny, nx, nt=None, aligned16=True, async_passes=24, n_cus=256, **quer
     return {n: getattr(p, n) for n, _ in FormPlan._fields_}
 
 
+def debug_live():
+    """ctk_debug_live: (device buffers, pinned buffers, events, streams) the library holds in this process; no handle, no GPU."""
+    out = (C.c_int64 * 4)()
+    check(lib().ctk_debug_live(out))
+    return tuple(out)
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -288,6 +295,7 @@ def lib():
     L.ctk_debug_set_spin.argtypes = [p, dbl, i32]
     L.ctk_debug_set_small_threads.argtypes = [p, i32, i32, i32]
     L.ctk_debug_forms.argtypes = [C.POINTER(FormQuery), C.POINTER(FormPlan)]
+    L.ctk_debug_live.argtypes = [C.POINTER(C.c_int64)]
     L.ctk_debug_np_sum.argtypes = [p, sz]
     L.ctk_debug_np_sum.restype = dbl
     L.ctk_debug_boundary_resolve.argtypes = [i32, p, p, p, p, p, p, p, p, p]

@@ -208,7 +208,7 @@ static int anom_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx,
         HIPCHK(hipStreamSynchronize(s));
         h->an_T = T; h->an_ny = ny; h->an_nx = nx; h->an_f64 = sizeof(VT) == 8;
         if (anom_out) {
-            if (!h->bounce) h->bounce = new (std::nothrow) BouncePool();
+            if (!h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
             if (!h->bounce || !bounce_copy(*h->bounce, h->device, h->an_out.p, anom_out, n * esz, false))
                 HIPCHK(hipMemcpy(anom_out, h->an_out.p, n * esz, hipMemcpyDeviceToHost));
         }

@@ -200,7 +200,7 @@ static int anom_seg_dev(ctk_handle *h, const VT *x_dev, int64_t T, int ny, int n
         HIPCHK(hipStreamSynchronize(s));
         if (keep_resident) { h->an_T = T; h->an_ny = ny; h->an_nx = nx; h->an_f64 = sizeof(VT) == 8; }
         if (anom_out) {
-            if (!h->bounce) h->bounce = new (std::nothrow) BouncePool();
+            if (!h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
             if (!h->bounce || !bounce_copy(*h->bounce, h->device, h->an_out.p, anom_out, n * esz, false))
                 HIPCHK(hipMemcpy(anom_out, h->an_out.p, n * esz, hipMemcpyDeviceToHost));
         }
@@ -282,7 +282,7 @@ static int anom_stream_pass2(ctk_handle *h, StreamIO &io, int64_t T, int64_t npi
     const size_t wbytes = (size_t)(chunk + halo) * plane, obytes = (size_t)(chunk + smooth) * plane;
     const double t_pass = now_ms();
     io.passes_in++;
-    if (io.host_out_v && !h->bounce) h->bounce = new (std::nothrow) BouncePool();
+    if (io.host_out_v && !h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
     struct Pending { int64_t t0 = -1, nt = 0; int b = 0; } pend;
     auto drain = [&](const Pending &q) -> int {                                  // output chunk q leaves the device
         if (q.t0 < 0) return CTK_OK;

@@ -9,6 +9,7 @@
 #include "ctk_comm.h"
 #include "ctk_forms.h"
 #include "ctk_select.h"
+#include "ctk_own.h"
 #include "../../include/contrack_hip_debug.h"
 
 #include <chrono>
@@ -23,6 +24,7 @@
 #include <atomic>
 #include <thread>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <condition_variable>
 #include <string>
@@ -72,13 +74,9 @@ static double now_ms_fwd() { return std::chrono::duration<double, std::milli>(st
 
 struct ShardScratch;
 static void shard_scratch_free(ShardScratch *s);            // ctk_sharded.hip
+struct ShardScratchFree { void operator()(ShardScratch *s) const { shard_scratch_free(s); } };
 
 namespace {
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
 
 enum State { ST_IDLE = 0, ST_LABELLED, ST_OVERLAPPED, ST_TABLES, ST_EXTENTS };
 
@@ -89,9 +87,17 @@ enum State { ST_IDLE = 0, ST_LABELLED, ST_OVERLAPPED, ST_TABLES, ST_EXTENTS };
 
 // pinned (CPU-cacheable) bounce buffers of the host-array entries' device -> host copy (bounce_copy)
 struct BounceLane {
-    void *pin[2] = {nullptr, nullptr};
-    hipStream_t st = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Stream st;                                     // (first: it goes last, after what was queued on it)
+    PinBuf pin[2];
+    Event ev[2];
+    bool create(size_t bytes)
+    {
+        bool ok = true;
+        for (int b = 0; b < 2 && ok; b++)
+            ok = pin[b].alloc(bytes, hipHostMallocNonCoherent) == hipSuccess && ev[b].create(hipEventDisableTiming) == hipSuccess;
+        return ok && st.create(hipStreamNonBlocking) == hipSuccess;
+    }
+    void release() { for (int b = 0; b < 2; b++) { pin[b].release(); ev[b].release(); } st.release(); }
 };
 constexpr int kLanes = 8;
 constexpr size_t kBounce = (size_t)8 << 20;
@@ -99,31 +105,14 @@ constexpr size_t kBounce = (size_t)8 << 20;
 struct BouncePool {
     BounceLane lane[kLanes];
     bool ready = false;
+    ~BouncePool() { for (BounceLane &l : lane) l.release(); }      // (lane by lane, in order)
     bool init()
     {
         if (ready) return true;
-        for (int i = 0; i < kLanes; i++) {
-            bool ok = true;
-            for (int b = 0; b < 2 && ok; b++)
-                ok = hipHostMalloc(&lane[i].pin[b], kBounce, hipHostMallocNonCoherent) == hipSuccess && hipEventCreateWithFlags(&lane[i].ev[b], hipEventDisableTiming) == hipSuccess;
-            ok = ok && hipStreamCreateWithFlags(&lane[i].st, hipStreamNonBlocking) == hipSuccess;
-            if (!ok) { destroy(); return false; }                // nothing half-built is left behind
-        }
+        for (BounceLane &l : lane)
+            if (!l.create(kBounce)) { for (BounceLane &x : lane) x.release(); return false; }      // nothing half-built is left behind
         ready = true;
         return true;
-    }
-    void destroy()
-    {
-        for (int i = 0; i < kLanes; i++) {
-            for (int b = 0; b < 2; b++) {
-                if (lane[i].pin[b]) (void)hipHostFree(lane[i].pin[b]);
-                if (lane[i].ev[b]) (void)hipEventDestroy(lane[i].ev[b]);
-                lane[i].pin[b] = nullptr; lane[i].ev[b] = nullptr;
-            }
-            if (lane[i].st) (void)hipStreamDestroy(lane[i].st);
-            lane[i].st = nullptr;
-        }
-        ready = false;
     }
 };
 
@@ -187,33 +176,17 @@ struct RlePool {
     LaneCrew crew;
     bool ready = false;
     size_t cap = 0;                                 // bytes per buffer: kRleBuf, or one timestep's tables if those are larger
+    ~RlePool() { crew.shutdown(); drop(); }         // (the lanes' threads stop before the lanes go, lane by lane in order)
+    void drop() { for (BounceLane &l : lane) l.release(); ready = false; }
     bool init(size_t need)
     {
         if (ready && need <= cap) return true;
-        destroy();
+        drop();
         cap = std::max(kRleBuf, (need + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1));
-        for (int i = 0; i < kRleLanes; i++) {
-            bool ok = true;
-            for (int b = 0; b < 2 && ok; b++)
-                ok = hipHostMalloc(&lane[i].pin[b], cap, hipHostMallocNonCoherent) == hipSuccess && hipEventCreateWithFlags(&lane[i].ev[b], hipEventDisableTiming) == hipSuccess;
-            ok = ok && hipStreamCreateWithFlags(&lane[i].st, hipStreamNonBlocking) == hipSuccess;
-            if (!ok) { destroy(); return false; }
-        }
+        for (BounceLane &l : lane)
+            if (!l.create(cap)) { drop(); return false; }
         ready = true;
         return true;
-    }
-    void destroy()
-    {
-        for (int i = 0; i < kRleLanes; i++) {
-            for (int b = 0; b < 2; b++) {
-                if (lane[i].pin[b]) (void)hipHostFree(lane[i].pin[b]);
-                if (lane[i].ev[b]) (void)hipEventDestroy(lane[i].ev[b]);
-                lane[i].pin[b] = nullptr; lane[i].ev[b] = nullptr;
-            }
-            if (lane[i].st) (void)hipStreamDestroy(lane[i].st);
-            lane[i].st = nullptr;
-        }
-        ready = false;
     }
 };
 
@@ -241,13 +214,16 @@ struct StreamIO {
     int64_t passes_in = 0;                         // how often the input was streamed (2: the call had to re-read it)
 };
 
+// Every GPU resource below is an owner of ctk_own.h and goes with the handle: ctk_destroy names none of them.  Members are destroyed
+// in reverse order of declaration, so the streams stay declared ahead of everything that is enqueued on them.
 struct ctk_handle {
     int device = 0;
     int n_cus = 256;                              // compute units of the device (grids of the persistent kernels)
-    hipStream_t stream = nullptr;
-    hipStream_t side[2] = {nullptr, nullptr};      // the labelling variants of one shard run concurrently
-    hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
-    hipEvent_t ev_scan = nullptr;                 // after the run scan of stage 1 (the host waits for it, not for the stream)
+    Stream stream;
+    Stream side[2];                                // the labelling variants of one shard run concurrently
+    Stream copy_stream;                            // the streaming entries' copies (stream_setup)
+    Event ev_fork, ev_join[2];
+    Event ev_scan;                                // after the run scan of stage 1 (the host waits for it, not for the stream)
     State state = ST_IDLE;
     // geometry of the current shard
     int64_t T = 0;
@@ -283,7 +259,8 @@ struct ctk_handle {
     // fused one-call path (ctk_seam_dev.hip): clusters of candidate labels, cluster root per group record; the pass runs without a
     // host hand-off and is validated from a device-written block of scalars after its only synchronisation
     DevBuf sd_parent, sd_tmin, sd_tmax, sd_root, sd_nops, sd_lbox, rv_pstate, ci_bsum, scan_bsum;
-    uint32_t *h_amail = nullptr;                   // pinned: AsyncMail scalars
+    uint32_t *h_amail = nullptr;                   // pinned: AsyncMail scalars (the typed view of amail_pin)
+    PinBuf amail_pin;
     uint32_t op_cap_hint = 4096;                   // operation slots of the next fused pass (grows with what the passes needed)
     uint32_t nd_hint = 4096;                       // dense candidate labels of the last pass: grid of k_seam_driver
     int async_passes = 24;                         // filter passes the next fused pass launches.  Before any pass has said how long this kind of slab's
@@ -317,13 +294,11 @@ struct ctk_handle {
     uint64_t io_gen = 0;                           // bumped by claim_io and ctk_release_io: WHOSE data io_in / io_out hold
     // streaming entries (ctk_track_stream_*): the slab passes through two chunk-sized device buffers per direction
     struct StreamIO *sio = nullptr;                // set for the duration of a streaming call: where the slab comes from
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_thr[2] = {nullptr, nullptr}, ev_rel[2] = {nullptr, nullptr}, ev_d2h[2] = {nullptr, nullptr};
-    void *pin_in[2] = {nullptr, nullptr}, *pin_out[2] = {nullptr, nullptr};
-    size_t pin_in_cap = 0, pin_out_cap = 0;
+    Event ev_h2d[2], ev_thr[2], ev_rel[2], ev_d2h[2];
+    PinPair pin_in, pin_out;
     double stream_ms[4] = {0, 0, 0, 0};
-    BouncePool *bounce = nullptr;                  // created on first use
-    RlePool *rle = nullptr;                        // created on first use (deliver_runs)
+    std::unique_ptr<BouncePool> bounce;            // created on first use
+    std::unique_ptr<RlePool> rle;                  // created on first use (deliver_runs)
     std::vector<uint32_t> rle_run_base;            // host copy of run_base (deliver_runs)
     std::vector<RleBlock> rle_blocks;
     bool rle_out = false;                          // this call's result leaves the device as run tables: launch_relabel is a no-op
@@ -332,10 +307,10 @@ struct ctk_handle {
     DevBuf sh_mask_next, sh_send, sh_recv, sh_prev, sh_elist, sh_ovr_slot, sh_ovr_val, sh_amb_list, sh_counts, sh_cl_shared, sh_cl_sent;
     uint32_t sh_stamp_seq = 0;
     int sh_dev_off_ny = -1, sh_dev_off_nx = -1;   // grid whose clusters did not fit the device seam driver on the time-shard path: host-driven from then on
-    struct ShardScratch *shard = nullptr;
-    uint32_t *h_mail2 = nullptr;                   // pinned, device-written scalars
-    void *h_shard = nullptr, *h_lab = nullptr, *h_seam = nullptr;        // pinned: gathered boundary records / label tables / shared seam groups
-    size_t h_shard_cap = 0, h_lab_cap = 0, h_seam_cap = 0;
+    std::unique_ptr<ShardScratch, ShardScratchFree> shard;
+    uint32_t *h_mail2 = nullptr;                   // pinned, device-written scalars (the typed view of mail2_pin)
+    PinBuf mail2_pin;
+    PinBuf h_shard, h_lab, h_seam;                 // pinned: gathered boundary records / label tables / shared seam groups
     bool halo_in_zero = false; void *halo_in_zero_p = nullptr; size_t halo_in_zero_cap = 0;     // the halo header of a first shard is already zero
     uint32_t sh_capB = 0, sh_capC = 0, sh_capD = 0;     // agreed capacities of the exchanged records (grow-only)
     int64_t sh_dbg[12] = {0};                     // ctk_debug_shard_exchange: what the last ctk_track_sharded_* call decided (CTK_SHX_*)
@@ -345,13 +320,12 @@ struct ctk_handle {
     std::vector<ctk_life_row> lc_host, lc_tmp;
     std::vector<std::pair<uint64_t, uint32_t>> lc_keys;
     std::vector<uint32_t> lc_cnt_host;
-    void *h_cand = nullptr;          // pinned: candidates + boxes download
-    size_t h_cand_cap = 0;
-    void *h_ops = nullptr;           // pinned: op upload staging
-    void *h_mail = nullptr;          // pinned: device-written mailbox of the resolver (scalars, candidates, dense tables)
-    uint32_t *h_mail1 = nullptr;     // pinned, device-written: [0..3] run scan of stage 1, [8..9] alive ids / background written
-    void *h_stage = nullptr;         // pinned: thresholds + weight limbs on their way to the device
-    size_t h_stage_cap = 0;
+    PinBuf h_cand;                   // pinned: candidates + boxes download
+    PinBuf h_ops;                    // pinned: op upload staging
+    PinBuf h_mail;                   // pinned: device-written mailbox of the resolver (scalars, candidates, dense tables)
+    uint32_t *h_mail1 = nullptr;     // pinned, device-written: [0..3] run scan of stage 1, [8..9] alive ids / background written (the typed view of mail1_pin)
+    PinBuf mail1_pin;
+    PinBuf h_stage;                  // pinned: thresholds + weight limbs on their way to the device
     uint32_t rb_last = 0, rb_total = 0;   // run_base[T-1], run_base[T]
     // what the device copies of thresholds / weight limbs were made from
     std::vector<double> c_thr; std::vector<float> c_w;
@@ -398,7 +372,7 @@ struct ctk_handle {
     // launch (form -1: none yet) and its workgroups
     DevBuf bd_cols, bd_sec, bd_tab;
     int bd_form_dbg = -1, bd_rows_dbg = -1, bd_form = -1, bd_rows = 0; int64_t bd_grid = 0;
-    void *bd_pin[2] = {nullptr, nullptr}; size_t bd_pin_cap = 0;      // pinned twins of the two table sets of a streamed call
+    PinPair bd_pin;                               // pinned twins of the two table sets of a streamed call
     // percentile per group (ctk_pctl.hip): histograms per (day, distinct prefix); ranks, prefixes, lists, ids; band sweeps of the last call
     DevBuf pc_hist, pc_buf;
     int64_t pc_sweeps = 0;
@@ -418,7 +392,6 @@ struct ctk_handle {
     CtkVariantSet spec_set = {false, false, false, false, false, false};
     int spec_ny = -1, spec_nx = -1; int64_t spec_T = -1;
     size_t mail_cap_c = 0, mail_cap_d = 0, mail_want_c = 0, mail_want_d = 0;
-    size_t h_ops_cap = 0;
     const int32_t *d_op_next = nullptr;
     int use_device_resolve = 1;
     int filter_round = CTK_JACOBI_ROUND;          // filter passes launched before convergence is checked
@@ -455,17 +428,16 @@ struct ctk_handle {
     double ms_sum[CTK_NTIMERS] = {0};                  // HIP-event times of the kernel groups summed over the calls since the last reset
     int64_t ms_cnt[CTK_NTIMERS] = {0};                 // ... and how many calls measured each group (ctk_get_timing_sums)
     // host (pinned) buffers
-    void *h_blob = nullptr;
-    size_t h_blob_cap = 0, h_blob_bytes = 0;
-    void *h_small = nullptr;         // pinned scratch: counters, run_base download
-    size_t h_small_cap = 0;
+    PinBuf h_blob;
+    size_t h_blob_bytes = 0;
+    PinBuf h_small;                  // pinned scratch: counters, run_base download
     // results kept between extents and write
     int64_t n_labels = 0, t_begin = 0;
     int32_t nops = 0;
     // timing
     int timing = 0;
     uint64_t pass_no = 0;                        // stage-1 launches so far (level-1 timing alternates between the two streaming kernels)
-    hipEvent_t ev[CTK_K_COUNT + 2][2];           // + one internal pair: stage-1 row count / run scan, reported inside CTK_K_SCAN
+    Event ev[CTK_K_COUNT + 2][2];                // + one internal pair: stage-1 row count / run scan, reported inside CTK_K_SCAN
     bool ev_used[CTK_K_COUNT + 2];
     double ms[CTK_NTIMERS];
     bool ev_ready = false;
@@ -479,32 +451,23 @@ int ensure(ctk_handle *h, DevBuf &b, size_t need)
     if (b.cap >= need) return CTK_OK;
     // hipFree waits for the device: with a collective in flight that wait must be the communicator's guarded one
     if (b.p && h && h->active_comm) { if (int rc = ctk_comm_wait(h->active_comm)) return rc; }
-    if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
-    size_t cap = need + need / 8 + 256;                   // a little head room: sizes vary between calls
-    hipError_t e = hipMalloc(&b.p, cap);
-    if (e != hipSuccess) {
-        e = hipMalloc(&b.p, need);
-        cap = need;
-        if (e != hipSuccess) {
-            b.p = nullptr;
-            return ctk_set_error(CTK_E_NOMEM, "hipMalloc(%zu bytes) failed: %s", need, hipGetErrorString(e));
-        }
-    }
-    b.cap = cap;
-    (void)h;
+    b.release();
+    hipError_t e = b.alloc(need + need / 8 + 256);        // a little head room: sizes vary between calls
+    if (e != hipSuccess) e = b.alloc(need);
+    if (e != hipSuccess) return ctk_set_error(CTK_E_NOMEM, "hipMalloc(%zu bytes) failed: %s", need, hipGetErrorString(e));
     return CTK_OK;
 }
 
 // non_coherent: coarse-grained pinned memory -- cached on the CPU (the default, fine-grained mapping makes CPU
 // reads several times slower); its contents are valid for the host after a stream synchronisation.
-int ensure_host(void **p, size_t *cap, size_t need, bool non_coherent = false)
+int ensure_host(ctk_handle *h, PinBuf &b, size_t need, bool non_coherent = false)
 {
-    if (*cap >= need && *p) return CTK_OK;
-    if (*p) { (void)hipHostFree(*p); *p = nullptr; *cap = 0; }
-    size_t c = need + need / 4 + 4096;
-    hipError_t e = hipHostMalloc(p, c, non_coherent ? hipHostMallocNonCoherent : hipHostMallocDefault);
-    if (e != hipSuccess) { *p = nullptr; return ctk_set_error(CTK_E_NOMEM, "hipHostMalloc(%zu bytes) failed: %s", c, hipGetErrorString(e)); }
-    *cap = c;
+    if (b.cap >= need && b.p) return CTK_OK;
+    if (b.p && h && h->active_comm) { if (int rc = ctk_comm_wait(h->active_comm)) return rc; }      // (hipHostFree waits for the device, as hipFree does)
+    b.release();
+    const size_t c = need + need / 4 + 4096;
+    const hipError_t e = b.alloc(c, non_coherent ? hipHostMallocNonCoherent : hipHostMallocDefault);
+    if (e != hipSuccess) return ctk_set_error(CTK_E_NOMEM, "hipHostMalloc(%zu bytes) failed: %s", c, hipGetErrorString(e));
     return CTK_OK;
 }
 
@@ -572,14 +535,10 @@ double now_ms()
 static void stream_teardown(ctk_handle *h)
 {
     for (int b = 0; b < 2; b++) {
-        if (h->pin_in[b]) (void)hipHostFree(h->pin_in[b]);
-        if (h->pin_out[b]) (void)hipHostFree(h->pin_out[b]);
-        h->pin_in[b] = nullptr; h->pin_out[b] = nullptr;
-        for (hipEvent_t *e : {&h->ev_h2d[b], &h->ev_thr[b], &h->ev_rel[b], &h->ev_d2h[b]}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+        h->pin_in.b[b].release(); h->pin_out.b[b].release();
+        for (Event *e : {&h->ev_h2d[b], &h->ev_thr[b], &h->ev_rel[b], &h->ev_d2h[b]}) e->release();
     }
-    h->pin_in_cap = h->pin_out_cap = 0;
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    h->copy_stream = nullptr;
+    h->copy_stream.release();
 }
 
 extern "C" int ctk_version(void) { return 100; }
@@ -607,14 +566,13 @@ extern "C" int ctk_create(ctk_handle **out, int device)
     if (!h) return ctk_set_error(CTK_E_NOMEM, "ctk_create: out of memory");
     h->device = device;
     { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) h->n_cus = cu; }
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return ctk_set_error(CTK_E_NODEVICE, "hipStreamCreate failed"); }
+    if (h->stream.create(hipStreamNonBlocking) != hipSuccess) { delete h; return ctk_set_error(CTK_E_NODEVICE, "hipStreamCreate failed"); }
     for (int k = 0; k < 2; k++) {
-        if (hipStreamCreateWithFlags(&h->side[k], hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_join[k], hipEventDisableTiming) != hipSuccess) { ctk_destroy(h); return ctk_set_error(CTK_E_NODEVICE, "hipStreamCreate failed"); }
+        if (h->side[k].create(hipStreamNonBlocking) != hipSuccess || h->ev_join[k].create(hipEventDisableTiming) != hipSuccess) { ctk_destroy(h); return ctk_set_error(CTK_E_NODEVICE, "hipStreamCreate failed"); }
     }
-    if (hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_scan, hipEventDisableTiming) != hipSuccess) { ctk_destroy(h); return ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed"); }
-    if (hipHostMalloc((void **)&h->h_mail1, 256, hipHostMallocDefault) != hipSuccess) { ctk_destroy(h); return ctk_set_error(CTK_E_NOMEM, "hipHostMalloc failed"); }
+    if (h->ev_fork.create(hipEventDisableTiming) != hipSuccess || h->ev_scan.create(hipEventDisableTiming) != hipSuccess) { ctk_destroy(h); return ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed"); }
+    if (h->mail1_pin.alloc(256, hipHostMallocDefault) != hipSuccess) { ctk_destroy(h); return ctk_set_error(CTK_E_NOMEM, "hipHostMalloc failed"); }
+    h->h_mail1 = (uint32_t *)h->mail1_pin.p;
     memset(h->h_mail1, 0, 256);
     memset(h->ms, 0, sizeof(h->ms));
     memset(h->ev_used, 0, sizeof(h->ev_used));
@@ -626,40 +584,8 @@ extern "C" void ctk_destroy(ctk_handle *h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    DevBuf *bufs[] = {&h->mask, &h->wstart, &h->rowstart, &h->tcount, &h->run_base, &h->ncomp, &h->cprefix, &h->thr32, &h->wlo, &h->whi,
-                      &h->counters, &h->run_comp, &h->run_val, &h->cs_mrep, &h->cs_box, &h->cs_area, &h->d_mrep, &h->d_box, &h->d_area,
-                      &h->comp_label, &h->g_x0, &h->g_x1, &h->g_y, &h->g_parent, &h->g_root, &h->g_idmap, &h->g_rs, &h->pairs, &h->seams,
-                      &h->ext, &h->ops, &h->op_first, &h->op_next, &h->op_stage, &h->halo_in, &h->halo_out, &h->dbg, &h->seam_cnt, &h->seam_off, &h->d_seams,
-                      &h->d_comp_t, &h->pair_base, &h->pair_cnt, &h->rv_tdirty, &h->d_blob, &h->seam_rowoff, &h->rv_prc, &h->rv_prd, &h->rv_pgc, &h->rv_pgd, &h->rv_F, &h->rv_B, &h->rv_keep0, &h->rv_keep1,
-                      &h->rv_changed, &h->rv_parent, &h->rv_isroot, &h->rv_rank, &h->rv_lab, &h->rv_lab_root, &h->rv_lbox, &h->rv_bsum, &h->rv_boff,
-                      &h->rv_cand_cnt, &h->rv_cand_off, &h->rv_cand, &h->rv_cand_scratch, &h->rv_seam_res, &h->rv_scalars, &h->rv_mark, &h->rv_inv, &h->rv_ff,
-                      &h->lc_rows, &h->lc_cnt, &h->lc_wlo, &h->lc_whi, &h->lc_w, &h->rv_dmap, &h->rv_dorig, &h->rv_dbox, &h->rv_inex, &h->rv_touch, &h->io_in, &h->io_out,
-                      &h->sh_mask_next, &h->sh_send, &h->sh_recv, &h->sh_prev, &h->sh_elist, &h->sh_ovr_slot, &h->sh_ovr_val,
-                      &h->sh_amb_list, &h->sh_counts, &h->sh_cl_shared, &h->sh_cl_sent, &h->chunk_vals, &h->lc_work, &h->lc_ovf, &h->lc_ekeys, &h->lc_offs, &h->lc_sw, &h->lc_sp, &h->lc_out, &h->lc_cross, &h->lc_gtab, &h->lc_occ, &h->lc_cp, &h->an_out, &h->an_clim, &h->an_raw, &h->an_idx, &h->an_acc, &h->an_valid, &h->lv_out, &h->lv_tab, &h->sd_parent, &h->sd_tmin, &h->sd_tmax, &h->sd_root, &h->sd_nops, &h->sd_lbox, &h->rv_pstate, &h->ci_bsum, &h->scan_bsum,
-                      &h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order, &h->fq_counts, &h->fq_group, &h->sp_out, &h->sp_words, &h->sp_carry, &h->cp_sum, &h->cp_n, &h->ce_sum, &h->ce_n, &h->ce_idx, &h->bd_cols, &h->bd_sec, &h->bd_tab, &h->seg_edge, &h->pc_hist, &h->pc_buf, &h->pf_out, &h->pf_idx, &h->sf_out, &h->sf_idx};
-    for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->p);
-    if (h->h_blob) (void)hipHostFree(h->h_blob);
-    if (h->h_small) (void)hipHostFree(h->h_small);
-    if (h->h_cand) (void)hipHostFree(h->h_cand);
-    for (int b = 0; b < 2; b++) if (h->bd_pin[b]) (void)hipHostFree(h->bd_pin[b]);
-    if (h->h_ops) (void)hipHostFree(h->h_ops);
-    if (h->h_mail) (void)hipHostFree(h->h_mail);
-    if (h->bounce) { h->bounce->destroy(); delete h->bounce; }
-    if (h->rle) { h->rle->crew.shutdown(); h->rle->destroy(); delete h->rle; }
-    stream_teardown(h);
-    if (h->h_mail1) (void)hipHostFree(h->h_mail1);
-    if (h->h_stage) (void)hipHostFree(h->h_stage);
-    if (h->h_mail2) (void)hipHostFree(h->h_mail2);
-    if (h->h_amail) (void)hipHostFree(h->h_amail);
-    if (h->h_shard) (void)hipHostFree(h->h_shard);
-    if (h->h_lab) (void)hipHostFree(h->h_lab);
-    if (h->h_seam) (void)hipHostFree(h->h_seam);
-    shard_scratch_free(h->shard);
-    if (h->ev_ready) for (int k = 0; k <= CTK_KI_ROWCOUNT; k++) { (void)hipEventDestroy(h->ev[k][0]); (void)hipEventDestroy(h->ev[k][1]); }
-    for (int k = 0; k < 2; k++) { if (h->side[k]) (void)hipStreamDestroy(h->side[k]); if (h->ev_join[k]) (void)hipEventDestroy(h->ev_join[k]); }
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_scan) (void)hipEventDestroy(h->ev_scan);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->rle.reset();                                // the lanes' host threads stop before any buffer goes
+    h->bounce.reset();
     delete h;
 }
 
@@ -668,7 +594,7 @@ extern "C" int ctk_set_timing(ctk_handle *h, int enable)
     if (!h || enable < 0 || enable > 2) return ctk_set_error(CTK_E_INVALID, "ctk_set_timing: null handle or level not in 0..2");
     HIPCHK(hipSetDevice(h->device));
     if (enable && !h->ev_ready) {
-        for (int k = 0; k <= CTK_KI_ROWCOUNT; k++) { HIPCHK(hipEventCreate(&h->ev[k][0])); HIPCHK(hipEventCreate(&h->ev[k][1])); }
+        for (int k = 0; k <= CTK_KI_ROWCOUNT; k++) { HIPCHK(h->ev[k][0].create()); HIPCHK(h->ev[k][1].create()); }
         h->ev_ready = true;
     }
     h->timing = enable;
@@ -761,9 +687,9 @@ extern "C" int ctk_debug_time_relabel(ctk_handle *h, int32_t *flag_dev, int pers
     if (!h || !flag_dev || !ms || reps < 1 || variant < 0 || variant > 1) return ctk_set_error(CTK_E_INVALID, "ctk_debug_time_relabel: bad argument");
     if (h->state != ST_TABLES) return ctk_set_error(CTK_E_STATE, "ctk_debug_time_relabel needs a finished pass");
     HIPCHK(hipSetDevice(h->device));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed"); }
+    Event e0, e1;
+    HIPCHK(e0.create());
+    if (e1.create() != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed");
     int rows = 0;
     const int32_t *cv = chunk_vals_for(h, flag_dev, &rows);
     const int keep_variant = h->rel_variant, keep_xcd = h->xcd_rel_tuned;
@@ -781,7 +707,6 @@ extern "C" int ctk_debug_time_relabel(ctk_handle *h, int32_t *flag_dev, int pers
         ms[r] = f;
     }
     h->rel_variant = keep_variant; h->xcd_rel_tuned = keep_xcd;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (rc != CTK_OK) return rc;
     if (err != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "ctk_debug_time_relabel: %s", hipGetErrorString(err));
     return CTK_OK;
@@ -827,6 +752,14 @@ extern "C" int ctk_debug_forms(const ctk_form_query *q, ctk_form_plan *p)
     const CtkFilterRound fr = ctk_filter_round(T, (int)q->async_passes, q->no_sys != 0, (int)q->n_cus);
     p->round_blk = fr.blk; p->round_two_pc = fr.two_pc; p->round_nb = fr.nb;
     p->rowcount_groups = ctk_rowcount_groups((int)p->rowcount_threads, ny, W);
+    return CTK_OK;
+}
+
+// device buffers, pinned buffers, events and streams the owners of ctk_own.h hold in this process; no handle, no device
+extern "C" int ctk_debug_live(int64_t *out4)
+{
+    if (!out4) return ctk_set_error(CTK_E_INVALID, "ctk_debug_live: null argument");
+    for (int i = 0; i < CTK_LIVE_KINDS; i++) out4[i] = g_ctk_live[i].load();
     return CTK_OK;
 }
 
@@ -927,29 +860,25 @@ static int stream_consume(ctk_handle *h, StreamIO &io, bool f64, int64_t T, int 
 // returns, also after an error; `who` names the hook in the error text.
 static int time_launches(ctk_handle *h, const char *who, int reps, double *ms2, const std::function<int()> &launch)
 {
-    std::vector<hipEvent_t> ev((size_t)reps + 1, nullptr);
-    int rc = CTK_OK;
-    for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { rc = ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed"); break; }
-    if (rc == CTK_OK) rc = launch();                                                // (warm-up)
-    for (int r = 0; r < reps && rc == CTK_OK; r++) {
-        if (hipEventRecord(ev[r], h->stream) != hipSuccess) rc = ctk_set_error(CTK_E_NODEVICE, "hipEventRecord failed");
-        if (rc == CTK_OK) rc = launch();
+    std::vector<Event> ev((size_t)reps + 1);
+    struct Idle { hipStream_t s; ~Idle() { (void)hipStreamSynchronize(s); } } idle{h->stream};       // (declared after the events: it runs before they go)
+    for (Event &e : ev)
+        if (e.create() != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed");
+    CTKCHK(launch());                                                               // (warm-up)
+    for (int r = 0; r < reps; r++) {
+        if (hipEventRecord(ev[r], h->stream) != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "hipEventRecord failed");
+        CTKCHK(launch());
     }
-    if (rc == CTK_OK && (hipEventRecord(ev[reps], h->stream) != hipSuccess || hipEventSynchronize(ev[reps]) != hipSuccess))
-        rc = ctk_set_error(CTK_E_NODEVICE, "%s: event wait failed", who);
-    if (rc == CTK_OK) {
-        double best = 1e30, sum = 0;
-        for (int r = 0; r < reps; r++) {
-            float m = 0;
-            (void)hipEventElapsedTime(&m, ev[r], ev[r + 1]);
-            best = std::min(best, (double)m); sum += m;
-        }
-        ms2[0] = best; ms2[1] = sum / reps;
+    if (hipEventRecord(ev[reps], h->stream) != hipSuccess || hipEventSynchronize(ev[reps]) != hipSuccess)
+        return ctk_set_error(CTK_E_NODEVICE, "%s: event wait failed", who);
+    double best = 1e30, sum = 0;
+    for (int r = 0; r < reps; r++) {
+        float m = 0;
+        (void)hipEventElapsedTime(&m, ev[r], ev[r + 1]);
+        best = std::min(best, (double)m); sum += m;
     }
-    (void)hipStreamSynchronize(h->stream);
-    for (auto e : ev) if (e) (void)hipEventDestroy(e);
-    return rc;
+    ms2[0] = best; ms2[1] = sum / reps;
+    return CTK_OK;
 }
 
 static bool async_wanted(ctk_handle *h);
@@ -980,10 +909,7 @@ extern "C" int ctk_set_threshold_field(ctk_handle *h, const void *field, int ele
     h->fld_T = -1; h->fld_prep_op = -1; h->fld_order_chunk = -1;
     h->c_thr_valid = false;
     if (!field) {
-        for (DevBuf *b : {&h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order}) {
-            if (b->p) (void)hipFree(b->p);
-            *b = DevBuf();
-        }
+        for (DevBuf *b : {&h->fld_raw, &h->fld_f32, &h->fld_pos, &h->fld_order}) b->release();
         h->fld_pos_host.clear();
         return CTK_OK;
     }
@@ -1204,9 +1130,9 @@ static int label2d_stage_inputs(ctk_handle *h, Label2dCall &c)
     int64_t *wlo = nullptr;
     c.w_bytes = (size_t)ny * 16 + ((size_t)ny + 2) * 4;
     if (!c.same_thr || !c.same_w) {
-        CTKCHK(ensure_host(&h->h_stage, &h->h_stage_cap, thr_bytes + c.w_bytes));
-        thr32 = (double *)h->h_stage;
-        wlo = (int64_t *)((char *)h->h_stage + thr_bytes);
+        CTKCHK(ensure_host(h, h->h_stage, thr_bytes + c.w_bytes));
+        thr32 = (double *)h->h_stage.p;
+        wlo = (int64_t *)((char *)h->h_stage.p + thr_bytes);
     }
     c.thr32 = thr32; c.wlo = wlo;
     if (!c.same_thr) {
@@ -1266,7 +1192,7 @@ static int label2d_upload(ctk_handle *h, Label2dCall &c)
     CTKCHK(ensure(h, h->thr32, (size_t)T * 8));
     CTKCHK(ensure(h, h->wlo, c.w_bytes));                             // wlo[ny] whi[ny] next_tiny[ny+1] in one allocation
     CTKCHK(ensure(h, h->counters, CTK_CNT_WORDS * 4));
-    CTKCHK(ensure_host(&h->h_small, &h->h_small_cap, (size_t)(T + 1) * 4 + 1024));     // run_base copy + scalar downloads
+    CTKCHK(ensure_host(h, h->h_small, (size_t)(T + 1) * 4 + 1024));     // run_base copy + scalar downloads
 
     // (the device counters are zeroed by the first threshold launch of the pass; k_rowcount writes every tcount[t])
     if (T == 0) HIPCHK(hipMemsetAsync(h->counters.p, 0, CTK_CNT_ZEROED * 4, s));
@@ -1367,8 +1293,8 @@ static int mask_placement_check(ctk_handle *h, const Label2dCall &c)
     h->mask_check_pending = false;
     h->mask_spacer_gb = 0.0;
     struct CheckTime { ctk_handle *h; double t0; ~CheckTime() { h->mask_check_ms = now_ms() - t0; } } check_time{h, now_ms()};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
+    Event e0, e1;
+    if (e0.create() == hipSuccess && e1.create() == hipSuccess) {
         const size_t mbytes = (size_t)c.nrows * c.W * 8;
         auto time_it = [&](double *ms) -> int {
             CTKCHK(launch_threshold(h, c, anom_dev, 0, nt_probe));
@@ -1389,7 +1315,6 @@ static int mask_placement_check(ctk_handle *h, const Label2dCall &c)
         h->thr_nostore = true;                                                  // the yardstick: the same kernel without its stores
         rc = time_it(&ro_ms);
         h->thr_nostore = false;
-        DevBuf best = h->mask;
         if (rc == CTK_OK) rc = time_it(&best_ms);
         h->mask_tries = 1;
         // Is the device ours?  With other work on it (other handles tracking their members at the same time) the times mean
@@ -1414,33 +1339,30 @@ static int mask_placement_check(ctk_handle *h, const Label2dCall &c)
         // round's handles and cost 1.3-6 ms of the handle's second call, once 32 ms: hipMalloc / hipFree of the spacer synchronise
         // the device.)  CTK_MASK_TRIES=1: the one retry described above, opt-in.
         const int max_tries = ctk_env().mask_tries;
-        std::vector<void *> held;                                               // the spacer and the rejected mask: freed when the search is over
-        struct FreeHeld { std::vector<void *> &v; ~FreeHeld() { for (void *q : v) (void)hipFree(q); } } free_held{held};
+        std::vector<DevBuf> held;                                               // the spacer and the rejected mask: freed when the search is over
         for (int k = 0; rc == CTK_OK && k < max_tries && best_ms > accept * ro_ms; k++) {
             // (never into the last quarter of the device: other handles allocate their work spaces at the same time)
             size_t mem_free = 0, mem_total = 0;
             const size_t spacer = (size_t)1 << 30;
             if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess || mem_free < spacer + mbytes + mem_total / 4) { (void)hipGetLastError(); break; }
-            void *sp = nullptr;
-            if (hipMalloc(&sp, spacer) == hipSuccess) { held.push_back(sp); h->mask_spacer_gb = 1.0; }
-            else { (void)hipGetLastError(); break; }
+            DevBuf sp;
+            if (sp.alloc(spacer) != hipSuccess) { (void)hipGetLastError(); break; }
+            held.push_back(std::move(sp)); h->mask_spacer_gb = 1.0;
             DevBuf nb;
             if (ensure(h, nb, mbytes) != CTK_OK) break;                         // (no memory for another try: keep what there is)
-            h->mask = nb;
+            h->mask.swap(nb);                                                   // the candidate is the handle's mask while it is timed
             double ms = 0.0;
             rc = time_it(&ms);
             h->mask_tries++;
-            if (rc == CTK_OK && ms < best_ms) { held.push_back(best.p); best = nb; best_ms = ms; }
-            else held.push_back(nb.p);
-            h->mask = best;
+            if (rc == CTK_OK && ms < best_ms) best_ms = ms;
+            else h->mask.swap(nb);                                              // (no better: the mask there was comes back)
+            held.push_back(std::move(nb));                                      // the loser of the two
         }
-        h->mask = best;
         h->mask_ratio = ro_ms > 0 ? best_ms / ro_ms : 0.0;
         if (ctk_env().hosttrace) fprintf(stderr, "mask placement: %d allocation(s) tried, threshold kernel on a %lld-step window %.4f ms = %.3f x its time without stores (%.4f), mask at %p, slab at %p\n", h->mask_tries, (long long)nt_probe, best_ms, h->mask_ratio, ro_ms, h->mask.p, anom_dev);
-        if (rc != CTK_OK) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rc; }
+        for (DevBuf &b : held) b.release();                                     // (in the order they were taken)
+        if (rc != CTK_OK) return rc;
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     return CTK_OK;
 }
 
@@ -1865,7 +1787,7 @@ static int build_tables_blob(ctk_handle *h, bool to_device, const void **blob, s
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const double t0 = now_ms();
-    uint32_t *hc = (uint32_t *)h->h_small + (h->T + 2);                       // after the run_base copy
+    uint32_t *hc = (uint32_t *)h->h_small.p + (h->T + 2);                       // after the run_base copy
     uint32_t cnt[CTK_CNT_N], ctot = 0, stot = 0;
     // seam rows: row-indexed scratch -> dense (t, y) order
     CTKCHK(launch_scan_u32(h, P<uint32_t>(h->seam_cnt), h->T, P<uint32_t>(h->seam_off)));
@@ -1905,7 +1827,7 @@ static int build_tables_blob(ctk_handle *h, bool to_device, const void **blob, s
     const size_t bytes = ctk_blob_bytes(T, NC, NP, NS);
     char *p;
     if (to_device) { CTKCHK(ensure(h, h->d_blob, bytes)); p = (char *)h->d_blob.p; }
-    else { CTKCHK(ensure_host(&h->h_blob, &h->h_blob_cap, bytes)); p = (char *)h->h_blob; }
+    else { CTKCHK(ensure_host(h, h->h_blob, bytes)); p = (char *)h->h_blob.p; }
     const hipMemcpyKind kind = to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     CtkBlobHeader hdr;
     memset(&hdr, 0, sizeof(hdr));
@@ -1931,7 +1853,7 @@ static int build_tables_blob(ctk_handle *h, bool to_device, const void **blob, s
     if (T) HIPCHK(hipMemcpyAsync(p, h->pair_cnt.p, (size_t)T * 4, kind, s));
     HIPCHK(hipStreamSynchronize(s));
     h->h_blob_bytes = bytes;
-    *blob = to_device ? h->d_blob.p : h->h_blob;
+    *blob = to_device ? h->d_blob.p : h->h_blob.p;
     *nbytes = bytes;
     h->ms[CTK_T_D2H] += now_ms() - t0;
     h->state = ST_TABLES;
@@ -1965,9 +1887,9 @@ static int upload_ops(ctk_handle *h, const CtkOp *ops, int64_t nops, int64_t n_l
     h->nops = (int32_t)nops;
     if (!nops) return CTK_OK;
     const size_t bytes = (size_t)nops * (sizeof(CtkOp) + 4 + 8);
-    CTKCHK(ensure_host(&h->h_ops, &h->h_ops_cap, bytes));
+    CTKCHK(ensure_host(h, h->h_ops, bytes));
     CTKCHK(ensure(h, h->ops, bytes));
-    CtkOp *s_ops = (CtkOp *)h->h_ops;
+    CtkOp *s_ops = (CtkOp *)h->h_ops.p;
     int32_t *s_next = (int32_t *)(s_ops + nops), *s_label = s_next + nops, *s_first = s_label + nops;
     memcpy(s_ops, ops, (size_t)nops * sizeof(CtkOp));
     std::vector<int32_t> &last = h->sd_last;                                   // scratch: last op seen per `hi`
@@ -1979,7 +1901,7 @@ static int upload_ops(ctk_handle *h, const CtkOp *ops, int64_t nops, int64_t n_l
         if (last[(size_t)hi] >= 0) s_next[last[(size_t)hi]] = i; else { s_label[nf] = hi; s_first[nf] = i; nf++; }
         last[(size_t)hi] = i;
     }
-    HIPCHK(hipMemcpyAsync(h->ops.p, h->h_ops, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->ops.p, h->h_ops.p, bytes, hipMemcpyHostToDevice, s));
     const int32_t *d_next = (const int32_t *)(P<CtkOp>(h->ops) + nops);
     h->d_op_next = d_next;
     k_scatter_i32<<<(int)((nf + 255) / 256), 256, 0, s>>>(d_next + nops, d_next + 2 * nops, (int)nf, P<int32_t>(h->op_first));
@@ -1995,9 +1917,9 @@ static int upload_ops_dense(ctk_handle *h, const std::vector<CtkOp> &ops, const 
     const int64_t nops = (int64_t)ops.size();
     h->nops = (int32_t)nops;
     const size_t bytes = (size_t)std::max<int64_t>(nops, 1) * (sizeof(CtkOp) + 4 + 8);
-    CTKCHK(ensure_host(&h->h_ops, &h->h_ops_cap, bytes));
+    CTKCHK(ensure_host(h, h->h_ops, bytes));
     CTKCHK(ensure(h, h->ops, bytes));
-    CtkOp *s_ops = (CtkOp *)h->h_ops;
+    CtkOp *s_ops = (CtkOp *)h->h_ops.p;
     int32_t *s_next = (int32_t *)(s_ops + nops), *s_label = s_next + nops, *s_first = s_label + nops;
     int32_t nf = 0;
     if (nops) {
@@ -2009,7 +1931,7 @@ static int upload_ops_dense(ctk_handle *h, const std::vector<CtkOp> &ops, const 
     int32_t *d_next = (int32_t *)(P<CtkOp>(h->ops) + nops);
     h->d_op_next = d_next;
     const int64_t work = std::max<int64_t>(nops * 9, h->n_labels + 1);
-    k_ops_ingest<<<(int)std::min<int64_t>((work + 255) / 256, 1024), 256, 0, s>>>((const int32_t *)h->h_ops, nops, nf, P<int32_t>(h->ops), P<int32_t>(h->op_first),
+    k_ops_ingest<<<(int)std::min<int64_t>((work + 255) / 256, 1024), 256, 0, s>>>((const int32_t *)h->h_ops.p, nops, nf, P<int32_t>(h->ops), P<int32_t>(h->op_first),
                                                                                   P<int32_t>(h->ext), h->n_labels, P<uint32_t>(h->counters));
     HIPCHK(hipGetLastError());
     return CTK_OK;
@@ -2166,17 +2088,14 @@ static int rs_prepare(ctk_handle *h, const ResolveIn &in, double overlap, int tw
     // mailbox in pinned host memory: the last resolver kernel writes scalars, candidate records and dense label tables
     // there itself -- one stream synchronisation, no copy commands.  Capacities follow the previous calls; a call that
     // needs more falls back to explicit copies and enlarges the mailbox for the next one.
-    if (h->mail_want_c > h->mail_cap_c || h->mail_want_d > h->mail_cap_d || !h->h_mail) {
+    if (h->mail_want_c > h->mail_cap_c || h->mail_want_d > h->mail_cap_d || !h->h_mail.p) {
         h->mail_cap_c = std::max<size_t>(std::max<size_t>(h->mail_want_c, h->mail_cap_c), 4096);
         h->mail_cap_d = std::max<size_t>(std::max<size_t>(h->mail_want_d, h->mail_cap_d), 8192);
-        size_t cap = 0;
-        if (h->h_mail && h->active_comm) CTKCHK(ctk_comm_wait(h->active_comm));       // (hipHostFree waits for the device)
-        if (h->h_mail) { (void)hipHostFree(h->h_mail); h->h_mail = nullptr; }
-        CTKCHK(ensure_host(&h->h_mail, &cap, CTK_MAIL_SCALARS * 4 + h->mail_cap_c * sizeof(CtkCand) + h->mail_cap_d * 28, true));
+        CTKCHK(ensure_host(h, h->h_mail, CTK_MAIL_SCALARS * 4 + h->mail_cap_c * sizeof(CtkCand) + h->mail_cap_d * 28, true));
     }
     CandMail mail;
-    mail.scal = (uint32_t *)h->h_mail;
-    mail.cand = (CtkCand *)((char *)h->h_mail + CTK_MAIL_SCALARS * 4);
+    mail.scal = (uint32_t *)h->h_mail.p;
+    mail.cand = (CtkCand *)((char *)h->h_mail.p + CTK_MAIL_SCALARS * 4);
     mail.dorig = (int32_t *)((char *)mail.cand + h->mail_cap_c * sizeof(CtkCand));
     mail.dbox = mail.dorig + h->mail_cap_d;
     mail.cap_c = (uint32_t)h->mail_cap_c; mail.cap_d = (uint32_t)h->mail_cap_d;
@@ -2588,7 +2507,7 @@ static int resolve_async(ctk_handle *h, double overlap, int twosided, int persis
     CTKCHK(ensure(h, h->ops, (size_t)op_cap * (sizeof(CtkOp) + 4)));
     // ids <= components <= runs: R + 1 is the offset of the second half of ext (only the entries of real ids are ever touched)
     CTKCHK(ensure(h, h->ext, (R + 1) * 8));
-    if (!h->h_amail) { HIPCHK(hipHostMalloc((void **)&h->h_amail, CTK_AM_WORDS * 4, hipHostMallocDefault)); }
+    if (!h->h_amail) { HIPCHK(h->amail_pin.alloc(CTK_AM_WORDS * 4, hipHostMallocDefault)); h->h_amail = (uint32_t *)h->amail_pin.p; }
     memset(h->h_amail, 0, CTK_AM_WORDS * 4);
     h->n_labels = (int64_t)R; h->t_begin = 0;
     r.cl_parent = P<uint32_t>(h->sd_parent); r.cl_tmin = P<int32_t>(h->sd_tmin); r.cl_tmax = P<int32_t>(h->sd_tmax); r.cl_nops = P<uint32_t>(h->sd_nops);
@@ -2768,8 +2687,8 @@ static void tune_relabel(ctk_handle *h, int persistence, int32_t *flag_dev)
     // (beyond 8 GB nothing is timed: by the shape -- one contiguous eighth per XCD won on every narrow grid it was timed on (2707 x 181 x 360:
     // -5 ... -8 %; 438 000 x 192 x 288, round 6: 18.75 -> 18.07 ms), the launch order on 1440-wide ones)
     if ((size_t)h->T * h->ny * h->nx * 4 > ((size_t)8 << 30)) { h->xcd_rel_tuned = h->nx < 1024 ? 1 : -1; return; }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { if (e0) (void)hipEventDestroy(e0); return; }
+    Event e0, e1;
+    if (e0.create() != hipSuccess || e1.create() != hipSuccess) return;
     int rows = 0;
     const int32_t *cv = chunk_vals_for(h, flag_dev, &rows);
     const int modes[3] = {0, 1, 16};
@@ -2789,7 +2708,6 @@ static void tune_relabel(ctk_handle *h, int persistence, int32_t *flag_dev)
     }
     h->xcd_rel_tuned = ok ? best_mode : -1;
     if (ctk_env().hosttrace) fprintf(stderr, "write kernel: chunk -> XCD mode %d, %.2f TB/s\n", h->xcd_rel_tuned, (double)h->T * h->ny * h->nx * 4 / 1e9 / (0.5 * best));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     (void)hipStreamSynchronize(h->stream);
 }
 
@@ -2904,7 +2822,7 @@ bool bounce_copy(BouncePool &pool, int device, void *dev, void *host, size_t byt
             if (hipEventSynchronize(L.ev[bb]) != hipSuccess) ok = false;
             if (!to_device) {
                 const size_t off = pending[bb] * kBounce, len = std::min(kBounce, bytes - off);
-                memcpy((char *)host + off, L.pin[bb], len);
+                memcpy((char *)host + off, L.pin[bb].p, len);
             }
             pending[bb] = (size_t)-1;
         };
@@ -2912,10 +2830,10 @@ bool bounce_copy(BouncePool &pool, int device, void *dev, void *host, size_t byt
             drain(b);                                                             // the buffer is free again
             const size_t off = c * kBounce, len = std::min(kBounce, bytes - off);
             if (to_device) {
-                memcpy(L.pin[b], (const char *)host + off, len);
-                if (hipMemcpyAsync((char *)dev + off, L.pin[b], len, hipMemcpyHostToDevice, L.st) != hipSuccess) ok = false;
+                memcpy(L.pin[b].p, (const char *)host + off, len);
+                if (hipMemcpyAsync((char *)dev + off, L.pin[b].p, len, hipMemcpyHostToDevice, L.st) != hipSuccess) ok = false;
             } else {
-                if (hipMemcpyAsync(L.pin[b], (const char *)dev + off, len, hipMemcpyDeviceToHost, L.st) != hipSuccess) ok = false;
+                if (hipMemcpyAsync(L.pin[b].p, (const char *)dev + off, len, hipMemcpyDeviceToHost, L.st) != hipSuccess) ok = false;
             }
             if (hipEventRecord(L.ev[b], L.st) != hipSuccess) ok = false;
             pending[b] = c;
@@ -3091,7 +3009,7 @@ static int deliver_runs(ctk_handle *h, int persistence, int32_t *flag, int *wrot
     rb.resize((size_t)T + 1);
     HIPCHK(hipMemcpy(rb.data(), h->run_base.p, (size_t)(T + 1) * 4, hipMemcpyDeviceToHost));
     std::vector<RleBlock> &blocks = h->rle_blocks;
-    if (!h->rle) h->rle = new (std::nothrow) RlePool();
+    if (!h->rle) h->rle.reset(new (std::nothrow) RlePool());
     // What can go wrong HERE leaves the device pass intact: the caller repeats it with the dense result (CTK_RLE_UNAVAILABLE; until round 5
     // a shortage of pinned memory failed the whole call -- advisor finding).  rle_mode 2: a test hook that takes this exit.
     if (h->rle_mode == 2) { (void)ctk_set_error(CTK_E_NOMEM, "result transfer: made unavailable (test hook)"); return CTK_RLE_UNAVAILABLE; }
@@ -3111,7 +3029,7 @@ static int deliver_runs(ctk_handle *h, int persistence, int32_t *flag, int *wrot
         auto fetch = [&](size_t bi, int b) {
             const RleBlock &c = blocks[bi];
             const size_t nrow = (size_t)c.nt * ny;
-            unsigned char *dst = (unsigned char *)L.pin[b];
+            unsigned char *dst = (unsigned char *)L.pin[b].p;
             bool good = hipMemcpyAsync(dst, d_mask + (size_t)c.t0 * ny * W, nrow * W * 8, hipMemcpyDeviceToHost, L.st) == hipSuccess;
             good = good && hipMemcpyAsync(dst + nrow * W * 8, d_rowstart + (size_t)c.t0 * ny, nrow * 4, hipMemcpyDeviceToHost, L.st) == hipSuccess;
             if (c.nr) good = good && hipMemcpyAsync(dst + nrow * W * 8 + ((nrow * 4 + 7) & ~(size_t)7), d_rv + c.r0, (size_t)c.nr * 4, hipMemcpyDeviceToHost, L.st) == hipSuccess;
@@ -3127,7 +3045,7 @@ static int deliver_runs(ctk_handle *h, int persistence, int32_t *flag, int *wrot
             if (hipEventSynchronize(L.ev[b]) != hipSuccess) { ok = false; break; }
             const double w1 = now_ms();
             bool z = false, c1 = false;
-            rle_expand_block((const unsigned char *)L.pin[b], blocks[bi], rb.data(), ny, nx, W, flag, scratch.data(), z, c1);
+            rle_expand_block((const unsigned char *)L.pin[b].p, blocks[bi], rb.data(), ny, nx, W, flag, scratch.data(), z, c1);
             if (ctk_env().hosttrace) { wait_us += (int64_t)((w1 - w0) * 1e3); exp_us += (int64_t)((now_ms() - w1) * 1e3); }
             if (z) zero = true;
             if (c1) cx[bi] = 1;
@@ -3198,7 +3116,7 @@ static int track_to_host(ctk_handle *h, const void *a_dev, bool f64, int64_t T, 
         break;
     }
     // the parallel copy; plain hipMemcpy for small results / if the lanes fail
-    if (!h->bounce) h->bounce = new (std::nothrow) BouncePool();
+    if (!h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
     if (!h->bounce || !bounce_copy(*h->bounce, h->device, f_dev, flag, n * 4, false)) {
         hipError_t e = hipMemcpy(flag, f_dev, n * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "D2H copy failed: %s", hipGetErrorString(e));
@@ -3239,27 +3157,14 @@ static int track_host_impl(ctk_handle *h, const void *anom, bool f64, int64_t T,
 // ------------------------------------------------------------------------------------------------
 static int stream_setup(ctk_handle *h, size_t in_bytes, size_t out_bytes, bool pinned)
 {
-    if (!h->copy_stream) HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    HIPCHK(h->copy_stream.create(hipStreamNonBlocking));
     for (int b = 0; b < 2; b++)
-        for (hipEvent_t *e : {&h->ev_h2d[b], &h->ev_thr[b], &h->ev_rel[b], &h->ev_d2h[b]})
-            if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        for (Event *e : {&h->ev_h2d[b], &h->ev_thr[b], &h->ev_rel[b], &h->ev_d2h[b]}) HIPCHK(e->create(hipEventDisableTiming));
     if (in_bytes) CTKCHK(claim_io(h, h->io_in, 2 * in_bytes));
     if (out_bytes) CTKCHK(claim_io(h, h->io_out, 2 * out_bytes));
     if (pinned) {
-        if (in_bytes > h->pin_in_cap) {
-            for (int b = 0; b < 2; b++) { if (h->pin_in[b]) (void)hipHostFree(h->pin_in[b]); h->pin_in[b] = nullptr; }
-            h->pin_in_cap = 0;
-            for (int b = 0; b < 2; b++)
-                if (hipHostMalloc(&h->pin_in[b], in_bytes, hipHostMallocNonCoherent) != hipSuccess) return ctk_set_error(CTK_E_NOMEM, "pinned chunk buffer (%zu bytes)", in_bytes);
-            h->pin_in_cap = in_bytes;
-        }
-        if (out_bytes > h->pin_out_cap) {
-            for (int b = 0; b < 2; b++) { if (h->pin_out[b]) (void)hipHostFree(h->pin_out[b]); h->pin_out[b] = nullptr; }
-            h->pin_out_cap = 0;
-            for (int b = 0; b < 2; b++)
-                if (hipHostMalloc(&h->pin_out[b], out_bytes, hipHostMallocNonCoherent) != hipSuccess) return ctk_set_error(CTK_E_NOMEM, "pinned chunk buffer (%zu bytes)", out_bytes);
-            h->pin_out_cap = out_bytes;
-        }
+        if (h->pin_in.grow(in_bytes, hipHostMallocNonCoherent) != hipSuccess) return ctk_set_error(CTK_E_NOMEM, "pinned chunk buffer (%zu bytes)", in_bytes);
+        if (h->pin_out.grow(out_bytes, hipHostMallocNonCoherent) != hipSuccess) return ctk_set_error(CTK_E_NOMEM, "pinned chunk buffer (%zu bytes)", out_bytes);
     }
     return CTK_OK;
 }
@@ -3340,7 +3245,7 @@ static int stream_out(ctk_handle *h, int persistence, const int32_t *chunk_vals)
         const uintptr_t a0 = ((uintptr_t)io.host_out + ((uintptr_t)2 << 20) - 1) & ~(((uintptr_t)2 << 20) - 1);
         const uintptr_t a1 = ((uintptr_t)io.host_out + (size_t)T * plane) & ~(((uintptr_t)2 << 20) - 1);
         if (a1 > a0) (void)madvise((void *)a0, a1 - a0, MADV_HUGEPAGE);
-        if (!h->bounce) h->bounce = new (std::nothrow) BouncePool();
+        if (!h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
     }
     struct Pending { int64_t t0 = -1, nt = 0; int b = 0; } pend;
     auto drain = [&](const Pending &p) -> int {                                 // chunk p leaves the device
@@ -3488,12 +3393,12 @@ extern "C" int ctk_release_io(ctk_handle *h)
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
     HIPCHK(hipSetDevice(h->device));
-    for (DevBuf *b : {&h->io_in, &h->io_out, &h->an_out, &h->an_raw, &h->lv_out}) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+    for (DevBuf *b : {&h->io_in, &h->io_out, &h->an_out, &h->an_raw, &h->lv_out}) b->release();
     h->an_T = -1; h->an_gen++; h->an_pct_n = -1;
     h->lv_T = -1; h->lv_gen++;
     h->io_gen++; h->lc_flag = nullptr; h->lc_field = nullptr;          // (the exact rows of a lifecycle call read those slabs)
-    if (h->bounce) { h->bounce->destroy(); delete h->bounce; h->bounce = nullptr; }
-    if (h->rle) { h->rle->crew.shutdown(); h->rle->destroy(); delete h->rle; h->rle = nullptr; }
+    h->bounce.reset();
+    h->rle.reset();
     stream_teardown(h);
     return CTK_OK;
 }
@@ -3743,8 +3648,8 @@ static int life_sort(ctk_handle *h, const ctk_life_row *land, size_t n, int64_t 
 // the rows of a settled pass: from the device into the pinned landing area
 static int life_land(ctk_handle *h, size_t n, ctk_life_row **land)
 {
-    CTKCHK(ensure_host(&h->h_cand, &h->h_cand_cap, std::max<size_t>(n, 1) * sizeof(ctk_life_row), true));     // pinned landing area
-    *land = (ctk_life_row *)h->h_cand;
+    CTKCHK(ensure_host(h, h->h_cand, std::max<size_t>(n, 1) * sizeof(ctk_life_row), true));     // pinned landing area
+    *land = (ctk_life_row *)h->h_cand.p;
     if (n) HIPCHK(hipMemcpy(*land, h->lc_rows.p, n * sizeof(ctk_life_row), hipMemcpyDeviceToHost));
     return CTK_OK;
 }
@@ -4091,9 +3996,9 @@ extern "C" int ctk_debug_stream_ceiling(ctk_handle *h, void *p_dev, size_t nbyte
     if (!h || !p_dev || !best_ms || nbytes < 16 || (((uintptr_t)p_dev) & 15) || reps < 1) return ctk_set_error(CTK_E_INVALID, "ctk_debug_stream_ceiling: bad argument");
     HIPCHK(hipSetDevice(h->device));
     CTKCHK(ensure(h, h->dbg, 64));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed"); }
+    Event e0, e1;
+    HIPCHK(e0.create());
+    if (e1.create() != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed");
     const int64_t n16 = (int64_t)(nbytes / 16);
     const unsigned grid = (unsigned)((n16 + 2047) / 2048);
     double best = 1e30;
@@ -4108,7 +4013,6 @@ extern "C" int ctk_debug_stream_ceiling(ctk_handle *h, void *p_dev, size_t nbyte
         if (err == hipSuccess) err = hipEventElapsedTime(&f, e0, e1);
         if (r > 0 && f < best) best = f;
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (err != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "ctk_debug_stream_ceiling: %s", hipGetErrorString(err));
     *best_ms = best;
     return CTK_OK;
@@ -4122,10 +4026,10 @@ extern "C" int ctk_check_flag_dev(ctk_handle *h, const float *anom_dev, const in
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const size_t tab = (size_t)(max_id + 1) * 4;
-    void *d_thr = nullptr, *d_tab = nullptr;
-    struct Free { void *&a, *&b; ~Free() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } fr{d_thr, d_tab};
-    HIPCHK(hipMalloc(&d_thr, (size_t)std::max<int64_t>(T, 1) * 8));
-    HIPCHK(hipMalloc(&d_tab, 2 * tab));
+    DevBuf tab_buf, thr_buf;                                                    // (freed thresholds first)
+    HIPCHK(thr_buf.alloc((size_t)std::max<int64_t>(T, 1) * 8));
+    HIPCHK(tab_buf.alloc(2 * tab));
+    void *const d_thr = thr_buf.p, *const d_tab = tab_buf.p;
     CTKCHK(ensure(h, h->dbg, 64));
     HIPCHK(hipMemsetAsync(h->dbg.p, 0, 48, s));
     if (T > 0) HIPCHK(hipMemcpyAsync(d_thr, thr, (size_t)T * 8, hipMemcpyHostToDevice, s));

@@ -289,21 +289,14 @@ extern "C" int ctk_band_dev(ctk_handle *h, const int32_t *flag_dev, const void *
 struct BandPiece { void *dst; const void *dev; size_t pin_off, bytes; };
 struct BandWayOut {
     ctk_handle *h;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Event ev[2];
     std::vector<BandPiece> pend[2];
     double ms = 0;
     explicit BandWayOut(ctk_handle *hh) : h(hh) {}
-    ~BandWayOut() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
     int init(size_t bytes_per_set)
     {
-        for (auto &e : ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        if (bytes_per_set > h->bd_pin_cap) {
-            for (int b = 0; b < 2; b++) { if (h->bd_pin[b]) (void)hipHostFree(h->bd_pin[b]); h->bd_pin[b] = nullptr; }
-            h->bd_pin_cap = 0;
-            for (int b = 0; b < 2; b++)
-                if (hipHostMalloc(&h->bd_pin[b], bytes_per_set, hipHostMallocDefault) != hipSuccess) return ctk_set_error(CTK_E_NOMEM, "pinned table buffer (%zu bytes)", bytes_per_set);
-            h->bd_pin_cap = bytes_per_set;
-        }
+        for (Event &e : ev) HIPCHK(e.create(hipEventDisableTiming));
+        if (h->bd_pin.grow(bytes_per_set, hipHostMallocDefault) != hipSuccess) return ctk_set_error(CTK_E_NOMEM, "pinned table buffer (%zu bytes)", bytes_per_set);
         return CTK_OK;
     }
     // the pieces of set b that are still on their way reach the caller's arrays

@@ -208,7 +208,7 @@ static int level_stream_chunks(ctk_handle *h, StreamIO &io, const LevelSel &sel,
     const bool sink = io.host_out_v || io.write_v;
     const double t_pass = now_ms();
     io.passes_in++;
-    if (io.host_out_v && !h->bounce) h->bounce = new (std::nothrow) BouncePool();
+    if (io.host_out_v && !h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
     struct Pending { int64_t t0 = -1, nt = 0; int b = 0; char *dev = nullptr; } pend;
     auto drain = [&](const Pending &q) -> int {                                  // output chunk q leaves the device
         if (q.t0 < 0) return CTK_OK;
@@ -417,9 +417,9 @@ extern "C" int ctk_debug_time_level_mean(ctk_handle *h, const void *x_dev, int i
     const double *w_dev = nullptr;
     const int32_t *lev_dev = nullptr;
     CTKCHK(level_table(h, sel, false, &w_dev, &lev_dev));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed"); }
+    Event e0, e1;
+    HIPCHK(e0.create());
+    if (e1.create() != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed");
     double best = 1e30, sum = 0.0;
     int rc = CTK_OK;
     hipError_t err = hipSuccess;
@@ -433,7 +433,6 @@ extern "C" int ctk_debug_time_level_mean(ctk_handle *h, const void *x_dev, int i
         if (err == hipSuccess) err = hipEventElapsedTime(&f, e0, e1);
         if (r > 0) { best = std::min(best, (double)f); sum += f; }
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (rc != CTK_OK) return rc;
     if (err != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "ctk_debug_time_level_mean: %s", hipGetErrorString(err));
     ms2[0] = best; ms2[1] = sum / reps;

@@ -320,7 +320,7 @@ static int pctl_validate(const ctk_handle *h, const PctlArgs &a, const double *o
 // the whole selection on a slab in device memory, on the handle's stream; the G results are left in device memory (*out_dev).
 // ev (measurement): events recorded before (ev[2 i]) and after (ev[2 i + 1]) band sweep i
 template <typename VT, typename KT>
-static int pctl_launch(ctk_handle *h, const VT *x_dev, const PctlArgs &a, const double **out_dev, hipEvent_t *ev = nullptr)
+static int pctl_launch(ctk_handle *h, const VT *x_dev, const PctlArgs &a, const double **out_dev, const Event *ev = nullptr)
 {
     hipStream_t s = h->stream;
     const int G = a.ngroups, W = a.window;
@@ -455,10 +455,10 @@ extern "C" int ctk_debug_time_percentile_groups(ctk_handle *h, const float *x_de
     }
     ms12[0] = best;
     const CtkPctlForm f = ctk_pctl_form(32, nband, ngroups, window);
-    hipEvent_t ev[16] = {};
+    Event ev[16];
     int rc = CTK_OK;
-    for (auto &e : ev)
-        if (rc == CTK_OK && hipEventCreate(&e) != hipSuccess) rc = ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed");
+    for (Event &e : ev)
+        if (rc == CTK_OK && e.create() != hipSuccess) rc = ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed");
     auto elapsed = [&](hipEvent_t e0, hipEvent_t e1, double *ms) {
         float m = 0;
         if (rc == CTK_OK && (hipEventSynchronize(e1) != hipSuccess || hipGetLastError() != hipSuccess || hipEventElapsedTime(&m, e0, e1) != hipSuccess))
@@ -491,6 +491,5 @@ extern "C" int ctk_debug_time_percentile_groups(ctk_handle *h, const float *x_de
         elapsed(ev[0], ev[1], &ms12[2]);
     }
     (void)hipStreamSynchronize(s);
-    for (auto e : ev) if (e) (void)hipEventDestroy(e);
     return rc;
 }

@@ -219,10 +219,10 @@ static int time_pfield_impl(ctk_handle *h, const VT *x_dev, const PctlArgs &a, i
     const int64_t chunk = CTK_PCTL_CHUNK;
     const unsigned chunks = (unsigned)((nband + chunk - 1) / chunk);
     if (chunks > 65535) return ctk_set_error(CTK_E_INVALID, "ctk_debug_time_percentile_field: a band of %lld values is too large for the read stream", (long long)nband);
-    hipEvent_t ev[2] = {};
+    Event ev[2];
     int rc = CTK_OK;
-    for (auto &e : ev)
-        if (rc == CTK_OK && hipEventCreate(&e) != hipSuccess) rc = ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed");
+    for (Event &e : ev)
+        if (rc == CTK_OK && e.create() != hipSuccess) rc = ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed");
     uint64_t *sink = P<uint64_t>(h->pf_idx);                                    // (8 bytes in front of the lists)
     double best = 1e30;
     for (int r = 0; r <= reps && rc == CTK_OK; r++) {
@@ -236,7 +236,6 @@ static int time_pfield_impl(ctk_handle *h, const VT *x_dev, const PctlArgs &a, i
     }
     ms4[2] = best;
     (void)hipStreamSynchronize(s);
-    for (auto e : ev) if (e) (void)hipEventDestroy(e);
     return rc;
 }
 

@@ -732,7 +732,7 @@ static int sharded_seam_device(ctk_handle *h, ctk_comm *c, ShardScratch &S, Reso
     sd.lab_cap = h->debug_sd_lab ? std::min(h->debug_sd_lab, SD_LAB) : SD_LAB; sd.ops_cap = h->debug_sd_ops ? std::min(h->debug_sd_ops, 64) : 64;
     h->d_op_next = sd.op_next;
     h->nops = 1;                                                       // (nonzero: the folds look at the chains)
-    const int32_t *st = (const int32_t *)h->h_lab;
+    const int32_t *st = (const int32_t *)h->h_lab.p;
     {
         Timer tm(h, CTK_K_RESOLVE);
         ShSeamTabs tb;
@@ -770,10 +770,10 @@ static int sharded_seam_device(ctk_handle *h, ctk_comm *c, ShardScratch &S, Reso
         int x5_redo = 0;
         for (int redo = 0;; redo = 1, x5_redo++) {
             sslot = sizeof(ShSeamHeader) + (size_t)capC * sizeof(CtkCand) + (size_t)capD * 28;      // (a multiple of 16: capD is one of 4)
-            CTKCHK(ensure_host(&h->h_seam, &h->h_seam_cap, sslot * (size_t)(world + 1), true));
+            CTKCHK(ensure_host(h, h->h_seam, sslot * (size_t)(world + 1), true));
             CTKCHK(ensure(h, h->sh_send, sslot));
             CTKCHK(ensure(h, h->sh_recv, sslot * (size_t)world));
-            unsigned char *sb = (unsigned char *)h->h_seam;
+            unsigned char *sb = (unsigned char *)h->h_seam.p;
             const uint32_t stamp = (uint32_t)((h->pass_no << 4) | (uint32_t)(redo ? 2 + (capC & 7u) : 1)) | 0x80000000u;
             mail2[100] = 0;
             k_sh_pack_shared<<<1, 1024, 0, s>>>(r, sd, st, P<uint8_t>(h->sh_cl_sent), capC, capD, (unsigned char *)h->sh_send.p, P<uint32_t>(h->seam_off), scal, redo);
@@ -793,14 +793,14 @@ static int sharded_seam_device(ctk_handle *h, ctk_comm *c, ShardScratch &S, Reso
         }
         h->sh_capC = capC; h->sh_capD = capD;
         {
-            const ShSeamHeader *mine = (const ShSeamHeader *)((const unsigned char *)h->h_seam + sslot * (size_t)(rank + 1));
+            const ShSeamHeader *mine = (const ShSeamHeader *)((const unsigned char *)h->h_seam.p + sslot * (size_t)(rank + 1));
             h->sh_dbg[CTK_SHX_CAPCD] = CTK_SHX_PAIR(capC, capD); h->sh_dbg[CTK_SHX_X5_REDO] = x5_redo;
             h->sh_dbg[CTK_SHX_SENT] = CTK_SHX_PAIR(mine->ncand, mine->nlab);
         }
         if (h->debug_fail_stage == 5) { h->debug_fail_stage = 0; return ctk_set_error(CTK_E_INTERNAL, "injected failure at stage 5 (test hook)"); }
         // merged table of the shared labels (boxes: union over the shards) and the shared candidate groups in (t, y) order
         const double t_host = now_ms();
-        const unsigned char *gb = (const unsigned char *)h->h_seam + sslot;
+        const unsigned char *gb = (const unsigned char *)h->h_seam.p + sslot;
         std::vector<std::pair<int32_t, int32_t>> &tmp = h->sh_pairs;      // (label, position) for the merge
         tmp.clear();
         for (int q = 0; q < world; q++) {
@@ -847,8 +847,8 @@ static int sharded_seam_device(ctk_handle *h, ctk_comm *c, ShardScratch &S, Reso
     if (ng > gops) { *too_many_shared_ops = true; return CTK_OK; }      // (the same list on every rank: everybody takes the host-driven form)
     // the shared clusters' operations + the list of shared ids -> pinned staging read by the kernels
     const size_t bytes = (size_t)std::max<int64_t>(ng, 1) * (sizeof(CtkOp) + 4 + 8) + (size_t)ne * 4 + 64;
-    CTKCHK(ensure_host(&h->h_ops, &h->h_ops_cap, bytes));
-    CtkOp *s_ops = (CtkOp *)h->h_ops;
+    CTKCHK(ensure_host(h, h->h_ops, bytes));
+    CtkOp *s_ops = (CtkOp *)h->h_ops.p;
     int32_t *s_next = (int32_t *)(s_ops + ng), *s_label = s_next + ng, *s_first = s_label + ng, *s_el = s_first + ng;
     int32_t nf = 0;
     if (ng) memcpy(s_ops, S.ops_g.data(), (size_t)ng * sizeof(CtkOp));
@@ -859,7 +859,7 @@ static int sharded_seam_device(ctk_handle *h, ctk_comm *c, ShardScratch &S, Reso
     if (ne) memcpy(s_el, S.elist.data(), (size_t)ne * 4);
     h->stats[CTK_S_OPS] = ng;                                          // (+ the device's own, added when the pass has ended)
     if (ng) {
-        k_sh_ops_append<<<(int)std::min<int64_t>((ng * 8 + 255) / 256, 256), 256, 0, s>>>((const int32_t *)h->h_ops, (int32_t)ng, nf, (uint32_t)cap_dev, sd.ops, sd.op_next, r.op_first);
+        k_sh_ops_append<<<(int)std::min<int64_t>((ng * 8 + 255) / 256, 256), 256, 0, s>>>((const int32_t *)h->h_ops.p, (int32_t)ng, nf, (uint32_t)cap_dev, sd.ops, sd.op_next, r.op_first);
         HIPCHK(hipGetLastError());
     }
     h->state = ST_TABLES;
@@ -918,7 +918,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     const bool cut_prev = rank > 0, cut_next = rank + 1 < world;
     const uint8_t *seg_host = h->seg_cur ? h->seg_cur_host : nullptr;
     const bool has_prev = cut_prev && !(seg_host && (seg_host[0] & 1u)), has_next = cut_next && !(seg_host && (seg_host[T - 1] & 2u));
-    if (!h->shard) h->shard = new (std::nothrow) ShardScratch();
+    if (!h->shard) h->shard.reset(new (std::nothrow) ShardScratch());
     if (!h->shard) return ctk_set_error(CTK_E_NOMEM, "out of memory");
     ShardScratch &S = *h->shard;
     S.ovr_prev.clear();
@@ -1045,7 +1045,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     const int gc = pl.gc, gp = pl.gp, nsb = pl.nsb;
 
     // pinned scalars the device writes for the host
-    if (!h->h_mail2) { HIPCHK(hipHostMalloc((void **)&h->h_mail2, 4096, hipHostMallocDefault)); memset(h->h_mail2, 0, 4096); }
+    if (!h->h_mail2) { HIPCHK(h->mail2_pin.alloc(4096, hipHostMallocDefault)); h->h_mail2 = (uint32_t *)h->mail2_pin.p; memset(h->h_mail2, 0, 4096); }
     uint32_t *mail2 = h->h_mail2;
 
     // ---- X3: overlap filter with boundary exchange --------------------------------------------------------------------
@@ -1142,7 +1142,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
             const size_t slot = kslot + bslot;
             CTKCHK(ensure(h, h->sh_send, slot));
             CTKCHK(ensure(h, h->sh_recv, slot * (size_t)world));
-            CTKCHK(ensure_host(&h->h_shard, &h->h_shard_cap, bslot * (size_t)world + 4096, true));
+            CTKCHK(ensure_host(h, h->h_shard, bslot * (size_t)world + 4096, true));
             if (h->sh_prev.cap < slot * (size_t)world) { CTKCHK(ensure(h, h->sh_prev, slot * (size_t)world)); if (!first_round) return ctk_set_error(CTK_E_INTERNAL, "boundary buffer grew between rounds"); }
             const uint32_t keep_stamp = (++h->sh_stamp_seq) | 0x80000000u;
             mail2[CTK_SHM_STAMP] = 0;
@@ -1153,7 +1153,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
             void *gath = world == 1 ? h->sh_send.p : h->sh_recv.p;
             CTKCHK(ctk_comm_allgather(c, h->sh_send.p, gath, slot));
             k_sh_unpack_keep<<<1, 256, 0, s>>>(r, (const unsigned char *)gath, (unsigned char *)h->sh_prev.p, first_round ? 1 : 0, redo, slot, capB, rank, world,
-                                               it_done + npass, P<uint8_t>(h->rv_tdirty), mail2, spec ? kslot : 0, bslot, (uint32_t *)h->h_shard,
+                                               it_done + npass, P<uint8_t>(h->rv_tdirty), mail2, spec ? kslot : 0, bslot, (uint32_t *)h->h_shard.p,
                                                pslot ? in.pair_cnt : nullptr, keep_stamp);
             HIPCHK(hipGetLastError());
             // (not a drain of the stream: the kernel's stamp in pinned memory arrives several microseconds before the completion signal)
@@ -1216,9 +1216,9 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
                 }
             fix_changed = S.ovr_prev.size() != S.ovr.size() || memcmp(S.ovr_prev.data(), S.ovr.data(), S.ovr.size() * 8) != 0;
             if (fix_changed) {
-                CTKCHK(ensure_host(&h->h_lab, &h->h_lab_cap, S.ovr.size() * 8 + 64));
-                memcpy(h->h_lab, S.ovr.data(), S.ovr.size() * 8);
-                HIPCHK(hipMemcpyAsync(h->sh_ovr_val.p, h->h_lab, S.ovr.size() * 8, hipMemcpyHostToDevice, s));
+                CTKCHK(ensure_host(h, h->h_lab, S.ovr.size() * 8 + 64));
+                memcpy(h->h_lab.p, S.ovr.data(), S.ovr.size() * 8);
+                HIPCHK(hipMemcpyAsync(h->sh_ovr_val.p, h->h_lab.p, S.ovr.size() * 8, hipMemcpyHostToDevice, s));
                 k_exact_apply<<<(int)((nflag + 255) / 256), 256, 0, s>>>(r, nflag, it_done, P<uint8_t>(h->rv_tdirty));
                 HIPCHK(hipGetLastError());
                 CTKCHK(ctk_comm_wait(c));                                 // (h_lab is reused below)
@@ -1241,7 +1241,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     const size_t bslot = sizeof(BoundHeader) + (size_t)capB * 8;
     CTKCHK(ensure(h, h->sh_send, bslot));
     CTKCHK(ensure(h, h->sh_recv, bslot * (size_t)world));
-    CTKCHK(ensure_host(&h->h_shard, &h->h_shard_cap, bslot * (size_t)world + 4096, true));
+    CTKCHK(ensure_host(h, h->h_shard, bslot * (size_t)world + 4096, true));
     h->stats[CTK_S_X4_SPECULATED] = spec ? 1 : 0;
     if (!spec) {                                      // (the last round did not carry the boundary records: X4 as an exchange of its own)
         {
@@ -1256,12 +1256,12 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
         }
         SHDBG("pack boundary");
         CTKCHK(ctk_comm_allgather(c, h->sh_send.p, h->sh_recv.p, bslot));
-        HIPCHK(hipMemcpyAsync(h->h_shard, h->sh_recv.p, bslot * (size_t)world, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h->h_shard.p, h->sh_recv.p, bslot * (size_t)world, hipMemcpyDeviceToHost, s));
         CTKCHK(ctk_comm_wait(c));
     }
     S.bin.assign((size_t)world, BoundaryIn());
     for (int q = 0; q < world; q++) {
-        const unsigned char *p = (const unsigned char *)h->h_shard + (size_t)q * bslot;
+        const unsigned char *p = (const unsigned char *)h->h_shard.p + (size_t)q * bslot;
         const BoundHeader *hd = (const BoundHeader *)p;
         BoundaryIn &b = S.bin[(size_t)q];
         b.nlast = hd->nlast; b.nh = hd->nh; b.nroots = hd->nroots;
@@ -1285,8 +1285,8 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     {
         const std::vector<int32_t> &A = S.bout.absorbed[(size_t)rank], &AL = S.bout.absorbed_label[(size_t)rank], &HL = S.bout.halo_label[(size_t)rank];
         const size_t words = 4 + 2 * A.size() + HL.size() + S.marks.size();
-        CTKCHK(ensure_host(&h->h_lab, &h->h_lab_cap, words * 4 + 64));
-        int32_t *st = (int32_t *)h->h_lab;
+        CTKCHK(ensure_host(h, h->h_lab, words * 4 + 64));
+        int32_t *st = (int32_t *)h->h_lab.p;
         *(int64_t *)st = lab0; st[2] = (int32_t)A.size(); st[3] = (int32_t)S.marks.size();
         int32_t *p = st + 4;
         if (!A.empty()) { memcpy(p, A.data(), A.size() * 4); p += A.size(); memcpy(p, AL.data(), A.size() * 4); p += A.size(); }
@@ -1335,7 +1335,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     {
         Timer tm(h, CTK_K_RESOLVE);
         k_sh_clear_tables<<<(int)std::min<int64_t>((NL + 2 + 255) / 256, 2048), 256, 0, s>>>(P<uint8_t>(h->rv_mark), P<uint32_t>(h->rv_dmap), P<int32_t>(h->op_first), NL + 2);
-        k_rs_labels_sh<<<gc, 256, 0, s>>>(r, (const int32_t *)h->h_lab, P<uint8_t>(h->rv_mark));
+        k_rs_labels_sh<<<gc, 256, 0, s>>>(r, (const int32_t *)h->h_lab.p, P<uint8_t>(h->rv_mark));
         k_rs_cand_mark<<<(int)T, 256, 0, s>>>(r, in.seams, in.seam_cnt, in.seam_off, ny, P<uint8_t>(h->rv_mark), P<int2>(h->rv_seam_res));
         k_rs_cand_groups<<<(int)((T + FZ_TW - 1) / FZ_TW), 64 * FZ_TW, 0, s>>>(r, in.seams, in.seam_cnt, in.seam_off, P<int2>(h->rv_seam_res), P<uint8_t>(h->rv_mark), ny, t_begin,
                                                P<uint32_t>(h->rv_cand_cnt), P<CtkCand>(h->rv_cand_scratch));
@@ -1436,10 +1436,10 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     if (!any_boundary_label) h->sd.run(hc, ncand, ho, hbx, (int64_t)nd, nx, S.ops_l);
     for (; any_boundary_label;) {
         sslot = sizeof(SeamHeader) + (size_t)capC * sizeof(CtkCand) + (size_t)capD * 28;
-        CTKCHK(ensure_host(&h->h_seam, &h->h_seam_cap, sslot * (size_t)(world + 1), true));
+        CTKCHK(ensure_host(h, h->h_seam, sslot * (size_t)(world + 1), true));
         CTKCHK(ensure(h, h->sh_send, sslot));
         CTKCHK(ensure(h, h->sh_recv, sslot * (size_t)world));
-        unsigned char *sb = (unsigned char *)h->h_seam;
+        unsigned char *sb = (unsigned char *)h->h_seam.p;
         SeamHeader sh; sh.ncand = (uint32_t)nGc; sh.nlab = (uint32_t)nGd; sh.pad0 = 0; sh.pad1 = 0;
         memcpy(sb, &sh, sizeof(sh));
         if ((uint32_t)nGc <= capC && nGd <= capD) {
@@ -1474,7 +1474,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
     // merged table of the shared labels (boxes: union over the shards) and the shared candidate groups in (t, y) order
     S.glabel.clear(); S.gbox.clear(); S.gcand.clear();
     if (any_boundary_label) {
-        const unsigned char *gb = (const unsigned char *)h->h_seam + sslot;
+        const unsigned char *gb = (const unsigned char *)h->h_seam.p + sslot;
         std::vector<std::pair<int32_t, int32_t>> &tmp = h->sh_pairs;      // (label, position) for the merge
         tmp.clear();
         for (int q = 0; q < world; q++) {
@@ -1523,9 +1523,9 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
         const int64_t ng = (int64_t)S.ops_g.size(), nl = (int64_t)S.ops_l.size(), nops = ng + nl;
         h->nops = (int32_t)nops;
         const size_t bytes = (size_t)std::max<int64_t>(nops, 1) * (sizeof(CtkOp) + 4 + 8) + (size_t)ne * 4 + 64;
-        CTKCHK(ensure_host(&h->h_ops, &h->h_ops_cap, bytes));
+        CTKCHK(ensure_host(h, h->h_ops, bytes));
         CTKCHK(ensure(h, h->ops, bytes));
-        CtkOp *s_ops = (CtkOp *)h->h_ops;
+        CtkOp *s_ops = (CtkOp *)h->h_ops.p;
         int32_t *s_next = (int32_t *)(s_ops + nops), *s_label = s_next + nops, *s_first = s_label + nops, *s_el = s_first + nops;
         int32_t nf = 0;
         if (ng) memcpy(s_ops, S.ops_g.data(), (size_t)ng * sizeof(CtkOp));
@@ -1540,7 +1540,7 @@ static int track_sharded_impl(ctk_handle *h, ctk_comm *c, const void *anom_dev, 
         int32_t *d_next = (int32_t *)(P<CtkOp>(h->ops) + nops);
         h->d_op_next = d_next;
         const int64_t work = std::max<int64_t>(nops * 9, NL + 1);
-        k_ops_ingest<<<(int)std::min<int64_t>((work + 255) / 256, 1024), 256, 0, s>>>((const int32_t *)h->h_ops, nops, nf, P<int32_t>(h->ops), P<int32_t>(h->op_first),
+        k_ops_ingest<<<(int)std::min<int64_t>((work + 255) / 256, 1024), 256, 0, s>>>((const int32_t *)h->h_ops.p, nops, nf, P<int32_t>(h->ops), P<int32_t>(h->op_first),
                                                                                       P<int32_t>(h->ext), NL, P<uint32_t>(h->counters));
         HIPCHK(hipGetLastError());
         h->state = ST_TABLES;

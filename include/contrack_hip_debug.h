@@ -116,6 +116,11 @@ typedef struct ctk_form_query { int64_t T, nt, ny, nx, f64, aligned16, field, ma
 typedef struct ctk_form_plan { int64_t thr_kind, thr_u7, thr_rbt, thr_grid, rowcount_threads, v0b, v0_ok, v0_runs, need_glb, spec_launched, spec_bits, missing, missing_bits, next_spec, overlap_form, extent_form, write_kernel, write_rb, write_sub, write_kb, write_batched, write_lds, write_grid, write_shape, chunk_copy, runval_threads, compact_init_threads, count_staged, count_fused, filter_sys, filter_passes, filter_blk, filter_two_pc, filter_nb, filter_unite, filter_merged, filter_bits, filter_bits_sync, round_blk, round_two_pc, round_nb, rowcount_groups; } ctk_form_plan;
 int ctk_debug_forms(const ctk_form_query *q, ctk_form_plan *p);
 
+/* resources the library's owning types (csrc/ctk_own.h) hold in this process right now, over all handles:
+ * out4 = { device buffers, pinned host buffers, events, streams }.  Memory from ctk_dev_malloc / ctk_host_alloc is the caller's and
+ * is not counted.  No handle, no device. */
+int ctk_debug_live(int64_t *out4);
+
 /* filter passes launched per round before convergence is checked on the host (default 10, 1..32)   */
 int ctk_set_filter_round(ctk_handle *h, int passes);
 
