@@ -26,7 +26,7 @@ EXPORTS = [
     "ctk_result_info", "ctk_result_arrays", "ctk_result_nshards", "ctk_weights_to_limbs", "ctk_shard_extents", "ctk_shard_write",
     "ctk_shard_count_tracked", "ctk_debug_mask", "ctk_debug_label2d", "ctk_debug_set_pair_capacity", "ctk_debug_set_mailbox", "ctk_debug_set_seam_caps", "ctk_debug_shard_exchange", "ctk_debug_set_shared_ops_reserve", "ctk_debug_set_spin", "ctk_debug_set_small_threads", "ctk_debug_forms", "ctk_debug_np_sum", "ctk_debug_boundary_resolve", "ctk_debug_boundary_resolve_breaks", "ctk_set_timing", "ctk_get_timings", "ctk_get_timing_sums", "ctk_set_device_resolve", "ctk_set_fused_pass", "ctk_set_result_transfer", "ctk_expand_runs_host", "ctk_set_filter_round", "ctk_get_stats", "ctk_get_stats_n", "ctk_debug_stream_ceiling", "ctk_debug_time_relabel",
     "ctk_dev_malloc", "ctk_dev_free", "ctk_host_alloc", "ctk_host_free", "ctk_host_register", "ctk_host_unregister", "ctk_memcpy_h2d", "ctk_memcpy_d2h", "ctk_sync", "ctk_stream",
-    "ctk_synth_fill", "ctk_debug_live",
+    "ctk_synth_fill", "ctk_debug_live", "ctk_debug_io_bytes",
     "ctk_comm_unique_id", "ctk_comm_init_rccl", "ctk_comm_group_create", "ctk_comm_group_destroy", "ctk_comm_init_local", "ctk_comm_init_shm",
     "ctk_comm_destroy", "ctk_comm_rank", "ctk_comm_world", "ctk_comm_barrier", "ctk_comm_allgather_host", "ctk_comm_ops",
     "ctk_comm_set_timeout", "ctk_comm_rccl_library", "ctk_comm_failed", "ctk_comm_abort_rank", "ctk_debug_fail_at", "ctk_synth_fill_window", "ctk_checksum_i32_dev", "ctk_dev_memset", "ctk_check_flag_dev",
@@ -373,6 +373,7 @@ def lib():
     for name in ("ctk_percentile_f32", "ctk_percentile_f64"):
         getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, i32, dbl, C.POINTER(dbl)]
     L.ctk_debug_percentile_values.argtypes = [p, p, i64]
+    L.ctk_debug_io_bytes.argtypes = [p, p]
     for name in ("ctk_percentile_groups_f32", "ctk_percentile_groups_f64"):
         getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, i32, p, i32, i32, dbl, p]
     L.ctk_debug_percentile_groups_sweeps.argtypes = [p, C.POINTER(i64)]
@@ -1826,6 +1827,13 @@ class Tracker:
         v = np.empty(int(n), dtype=np.float64)
         check(lib().ctk_debug_percentile_values(self._h, v.ctypes.data, int(n)))
         return v
+
+    def debug_io_bytes(self):
+        """test hook: the capacities in bytes of the staging buffers the entries share, as a dict: io_in, io_out, and one buffer of the
+        pinned pairs pin_in, pin_out (0: not allocated)"""
+        v = np.zeros(4, dtype=np.int64)
+        check(lib().ctk_debug_io_bytes(self._h, v.ctypes.data))
+        return dict(zip(("io_in", "io_out", "pin_in", "pin_out"), (int(b) for b in v)))
 
     def release_io(self):
         """free the device copies of slab / result that the host-array calls keep in the handle"""

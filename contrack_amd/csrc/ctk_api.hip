@@ -763,6 +763,15 @@ extern "C" int ctk_debug_live(int64_t *out4)
     return CTK_OK;
 }
 
+// capacities in bytes of the staging buffers every host-array and streamed entry shares: io_in, io_out, one buffer of the pin_in pair, one
+// of the pin_out pair (0: not allocated, or released by ctk_release_io).  No device call.
+extern "C" int ctk_debug_io_bytes(ctk_handle *h, int64_t *out4)
+{
+    if (!h || !out4) return ctk_set_error(CTK_E_INVALID, "ctk_debug_io_bytes: null argument");
+    out4[0] = (int64_t)h->io_in.cap; out4[1] = (int64_t)h->io_out.cap; out4[2] = (int64_t)h->pin_in.cap(); out4[3] = (int64_t)h->pin_out.cap();
+    return CTK_OK;
+}
+
 extern "C" int ctk_debug_set_spin(ctk_handle *h, double limit_ms, int stall_mode)
 {
     if (!h || stall_mode < 0 || stall_mode > 2 || limit_ms < 0) return ctk_set_error(CTK_E_INVALID, "ctk_debug_set_spin: null handle, negative limit or stall mode not in 0..2");

@@ -121,6 +121,12 @@ int ctk_debug_forms(const ctk_form_query *q, ctk_form_plan *p);
  * is not counted.  No handle, no device. */
 int ctk_debug_live(int64_t *out4);
 
+/* test hook: the capacities in bytes of the staging buffers that the host-array and streamed entries of one handle share:
+ * out4 = { io_in, io_out, one buffer of the pinned input pair, one buffer of the pinned output pair }; 0: not allocated (or released by
+ * ctk_release_io).  The device buffers are grow-only with head room (a buffer that must grow to `need` bytes gets need + need / 8 + 256),
+ * the pinned pairs grow to exactly the bytes asked for.  No device call. */
+int ctk_debug_io_bytes(ctk_handle *h, int64_t *out4);
+
 /* filter passes launched per round before convergence is checked on the host (default 10, 1..32)   */
 int ctk_set_filter_round(ctk_handle *h, int passes);
 

@@ -19,15 +19,21 @@ An operation (`Op`) is a family, its arguments, and the reference function of th
                         documented order restated on those values (band_mean)
     percentile_groups   pctl_util.want;  percentile_field  pfield_util.want_field;  std_field  std_util.want_std
     lifecycle           life_util.numpy_rows for t / label / shift / area, life_util.numpy_exact_rows for the exact records of ALL rows
+    band                band_util.band (area per step, columns, sectors; the resident forms on the anomaly slab of oracle/anom_port.py)
+    centred             centred_util.centred (the reader form also answers for the chunks its reader was asked for)
 Every comparison is exact (bits or integers); there is no tolerance in this module.
 
 `Op.io` is what the call asks of the shared buffers, computed from its arguments as the library computes it (bytes of io_in, io_out
 and of one pinned buffer per direction; 0: not touched).  `Op.needs` / `Op.gives` / `Op.drops` name the resident slabs ("anom",
-"level") it consumes, leaves and invalidates: the seeded generator draws a consumer only while its slab is resident."""
+"level") it consumes, leaves and invalidates: the seeded generator draws a consumer only while its slab is resident.  The runner
+compares `Op.io` with the handle's own capacities after every call (check_io), and `Op.breaks_exact` -- the call claims io_in /
+io_out -- is what decides in exact_rows_follow_their_slabs whether the exact rows of an earlier lifecycle call are stale."""
 import functools
 
 import numpy as np
 
+import band_util
+import centred_util
 import composite_util
 import freq_util
 import label_forms
@@ -205,14 +211,15 @@ def want_anom_of_level(key, dtype="f4", seed=4):
                 _frozen(anom_port.calc_clim(x, g, ANOM["G"], ANOM["window"]).astype(x.dtype)))
 
 
-def band(key):
+def band_rows(key):
+    """the rows [y0, y1) of the percentile entries and of the band entries"""
     ny = SHAPES[key][1]
     return 1, ny - 2
 
 
 def want_quantile_values(x, key, q):
     import warnings
-    y0, y1 = band(key)
+    y0, y1 = band_rows(key)
     with warnings.catch_warnings(), np.errstate(invalid="ignore"):
         warnings.simplefilter("ignore")
         return np.nanquantile(np.asarray(x)[:, y0:y1].astype(np.float64), q, axis=0).ravel()
@@ -319,16 +326,35 @@ def array_io(key, in_bytes=0, out_bytes=0):
 
 
 NO_IO = dict(io_in=0, io_out=0, pin_in=0, pin_out=0)
+BUFFERS = ("io_in", "io_out", "pin_in", "pin_out")
 RUNS_IO_OUT = 256                      # track_to_host claims io_out: 256 bytes while the result travels as run tables (the default)
+
+
+def dense_blocks(key):
+    """a tracking result that leaves as run tables (track_to_host, and track_stream_impl with an array as the sink): deliver_runs
+    claims io_out again for every block of time steps that holds a complex component, with that block's dense bytes -- which blocks
+    do depends on the data; all of them together are the dense result"""
+    T, ny, nx = SHAPES[key]
+    return dict(io_out=T * ny * nx * 4)
 
 
 class Op:
     """one call on the shared handle: run(trk, env) -> value, want() -> reference value, same(value, reference) -> bool"""
 
-    def __init__(self, family, key, run, want, same, io=NO_IO, needs=None, gives=None, drops=(), tracking=False, note="", args=None):
+    def __init__(self, family, key, run, want, same, io=NO_IO, needs=None, gives=None, drops=(), tracking=False, note="", args=None, io_upto=None):
         self.family, self.key, self.run, self.want, self.same, self.io = family, key, run, want, same, dict(io)
         self.needs, self.gives, self.drops, self.tracking, self.note = needs, gives, tuple(drops), tracking, note
         self.args = args or {}
+        # what the call asks of a buffer at the most, where that depends on the data (the dense blocks of a tracking result): `io` is
+        # then the least it asks
+        self.io_upto = dict(io_upto or {})
+
+    @property
+    def breaks_exact(self):
+        """the call claims io_in / io_out (claim_io) or releases them: the exact rows of an earlier host-array lifecycle call are stale
+        after it.  (Not the whole rule: a call that writes or drops the resident anomaly slab also breaks the rows of a lifecycle call
+        with field = None.)"""
+        return bool(self.io["io_in"] or self.io["io_out"]) or self.family == "release_io"
 
     def __repr__(self):
         return "%s[%s%s]" % (self.family, self.key, (" " + self.note) if self.note else "")
@@ -339,6 +365,9 @@ class Env:
 
     def __init__(self):
         self.life = None              # (rows, key of the shape, lat / lon / dates arguments) of the last lifecycle op
+        self.generation = None        # of the resident anomaly slab, as its producer left it
+        self.stale_generation = None  # ... and of the slab the producer before that one left
+        self.level_generation = None
 
 
 def _chunks_reader(source, fail_chunk=None, calls=None):
@@ -382,14 +411,16 @@ STATE_RC = "rc=-6"                     # CTK_E_STATE as _native.check words it
 
 
 def _refusing(fn):
-    """the call must raise ContrackHipError and not a ValueError (that is a bad argument); what it says is compared by the op"""
+    """the call must raise ContrackHipError and not a ValueError (that is a bad argument); what it says is compared by the op.  Any
+    other exception -- a call that was not refused may stumble over what it read -- is handed to the comparison as it is, which then
+    reports the op instead of ending the sequence"""
     def run(trk, env):
         try:
             fn(trk, env)
-        except _state_errors() as e:
-            if isinstance(e, ValueError):
-                raise
-            return StateError(str(e))
+        except Exception as e:                                      # noqa: BLE001
+            if isinstance(e, _state_errors()) and not isinstance(e, ValueError):
+                return StateError(str(e))
+            return e
         return None
     return run
 
@@ -411,7 +442,7 @@ def track(key, dtype="f4", thr=100.0, gorl=">=", wvar=1, per_step=False, pers=2,
         return f.copy(), n
     io = array_io(key, 4 if dtype == "f4" else 8)
     io["io_out"] = RUNS_IO_OUT
-    return Op("track", key, run, lambda: want_track(key, thr, gorl, wvar, pers, per_step, seed), same_flag, io,
+    return Op("track", key, run, lambda: want_track(key, thr, gorl, wvar, pers, per_step, seed), same_flag, io, io_upto=dense_blocks(key),
               tracking=True, note="%s thr=%g%s %s w%d" % (dtype, thr, " per step" if per_step else "", gorl, wvar),
               args=dict(dtype=dtype, thr=thr, gorl=gorl, wvar=wvar, per_step=per_step))
 
@@ -427,7 +458,7 @@ def track_field(key, dtype="f4", seed=1):
         finally:
             trk.clear_threshold_field()
     return Op("track_field", key, run, lambda: want_track_field(key, seed), same_flag, dict(array_io(key, 4 if dtype == "f4" else 8), io_out=RUNS_IO_OUT),
-              tracking=True, note=dtype)
+              io_upto=dense_blocks(key), tracking=True, note=dtype)
 
 
 def track_segments(key, thr=100.0, seed=1):
@@ -439,7 +470,8 @@ def track_segments(key, thr=100.0, seed=1):
             return f.copy(), n
         finally:
             trk.clear_segments()
-    return Op("track_segments", key, run, lambda: want_track_segments(key, thr, seed), same_flag, dict(array_io(key, 4), io_out=RUNS_IO_OUT), tracking=True)
+    return Op("track_segments", key, run, lambda: want_track_segments(key, thr, seed), same_flag, dict(array_io(key, 4), io_out=RUNS_IO_OUT), io_upto=dense_blocks(key),
+              tracking=True)
 
 
 def track_stream(key, dtype="f4", chunk_steps=0, callbacks=False, fail_chunk=None, thr=100.0, seed=1):
@@ -462,7 +494,7 @@ def track_stream(key, dtype="f4", chunk_steps=0, callbacks=False, fail_chunk=Non
     if fail_chunk is not None:
         return Op("track_stream", key, _catching(run, ReaderGaveUp), lambda: None, gave_up, io, note="reader gives up on chunk %d" % fail_chunk,
                   args=dict(fail_chunk=fail_chunk))
-    return Op("track_stream", key, run, lambda: want_track(key, thr, ">=", 1, 2, False, seed), same_flag, io, tracking=True,
+    return Op("track_stream", key, run, lambda: want_track(key, thr, ">=", 1, 2, False, seed), same_flag, io, io_upto=None if callbacks else dense_blocks(key), tracking=True,
               note="%s chunk=%d%s" % (dtype, chunk_steps, " reader+writer" if callbacks else ""), args=dict(dtype=dtype))
 
 
@@ -515,7 +547,7 @@ def track_resident(src, thr=40.0, gorl=">="):
         f, n = trk.track_resident(thresholds(key, thr), CMP[gorl], wrow(key), OVERLAP, 2, TWOSIDED)
         return f.copy(), n
     return Op("track_resident", key, run, lambda: want_track_indicator(indicator(want_anom(*src)[0], thr, gorl), key), same_flag,
-              dict(NO_IO, io_out=RUNS_IO_OUT), needs="anom", tracking=True)
+              dict(NO_IO, io_out=RUNS_IO_OUT), io_upto=dense_blocks(key), needs="anom", tracking=True)
 
 
 # ---- frequency, spells, composite -----------------------------------------------------------------------------------------------
@@ -602,6 +634,250 @@ def composite_resident(src, G=3):
         return trk.composite(resident_flag(src), None, ids, G, 0, True, 0, resident_f64=src[1] == "f8")
     return Op("composite_resident", key, run, lambda: composite_util.composite(resident_flag(src), want_anom(*src)[0], ids, G, 0, True), same_composite,
               stream_io(key, 0, 4), needs="anom")
+
+
+# ---- band: area per step, Hovmoeller columns, sector series ---------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def band_weights(key):
+    return _frozen(band_util.cos_weights(SHAPES[key][1]))
+
+
+def band_sectors(key):
+    nx = SHAPES[key][2]
+    return [(0, 10), (nx - 6, 12)]                         # the second one wraps
+
+
+@functools.lru_cache(maxsize=None)
+def wide_field(key, dtype="f4", seed=0):
+    """values as centred_util.wide_case makes them: a reordered or split float64 sum of these shows in the bits"""
+    T, ny, nx = SHAPES[key]
+    rng = np.random.default_rng(seed)
+    return _frozen((rng.standard_normal((T, ny, nx)) * 10.0 ** rng.uniform(-8, 10, (T, ny, nx))).astype(DT[dtype]))
+
+
+def same_band(got, want):
+    """band_util.same (dtype, shape and bits of every table, and no table too many) as a bool"""
+    try:
+        band_util.same(got, want)
+    except AssertionError as e:
+        same_band.detail = str(e)
+        return False
+    return True
+
+
+def _band_call(trk, how, key, f, x, field, chunk_steps, sects, columns, readers=(None, None), resident_gen=None, resident_f64=False):
+    T, ny, nx = SHAPES[key]
+    rows, w = band_rows(key), band_weights(key)
+    if how == "array":
+        return trk.band(f, rows, w, x, sects, columns, 0, chunk_steps, resident_gen=resident_gen, resident_f64=resident_f64)
+    if how == "cb":
+        return trk.band_cb(readers[0], readers[1], (T, ny, nx), DT[field] if field else None, rows, w, sects, columns, 0, chunk_steps, resident_gen=resident_gen)
+    d, dx = _dev_flag(trk, f), (trk.malloc(x.nbytes) if x is not None else None)
+    try:
+        if x is not None:
+            trk.h2d(dx, x)
+        return trk.band_dev(d, dx, T, ny, nx, rows, w, sects, columns, 0, f64=field == "f8", resident_gen=resident_gen)
+    finally:
+        trk.free(d)
+        if dx is not None:
+            trk.free(dx)
+
+
+def band_io(key, how, field, chunk_steps, travels):
+    """band_stream_impl: a field that travels is the first slab and sets the chunk length, the flags then take io_out (pin_out with a
+    flag reader); otherwise the flags are the only slab.  band_dev claims neither"""
+    if how == "dev":
+        return NO_IO
+    if travels:
+        return stream_io(key, chunk_steps, 4 if field == "f4" else 8, second_bytes=4, reader=how == "cb", reader2=how == "cb")
+    return stream_io(key, chunk_steps, 4, reader=how == "cb")
+
+
+def band(key, how="array", field=None, chunk_steps=0, sectors=True, columns=True, fail_chunk=None, fail_which="flag", seed=2):
+    """fail_which: the reader that gives up on its call `fail_chunk` -- "flag" or "field" """
+    assert how in ("array", "cb", "dev") and field in (None, "f4", "f8") and (sectors or columns) and fail_which in ("flag", "field")
+    sects = band_sectors(key) if sectors else None
+    x = lambda: wide_field(key, field) if field else None                                     # noqa: E731
+
+    def run(trk, env):
+        f = flags(key, seed)
+        readers = (_chunks_reader(f, fail_chunk if fail_which == "flag" else None),
+                   _chunks_reader(x(), fail_chunk if fail_which == "field" else None) if field else None)
+        return _band_call(trk, how, key, f, x(), field, chunk_steps, sects, columns, readers)
+    fam = {"array": "band", "cb": "band_cb", "dev": "band_dev"}[how]
+    io = band_io(key, how, field, chunk_steps, field is not None)
+    note = "%s chunk=%d%s%s" % (field or "no field", chunk_steps, " columns" if columns else "", " sectors" if sectors else "")
+    if fail_chunk is not None:
+        assert how == "cb" and (field or fail_which == "flag")
+        return Op(fam, key, _catching(run, ReaderGaveUp), lambda: None, gave_up, io, note="%s: the %s reader gives up on chunk %d" % (note, fail_which, fail_chunk),
+                  args=dict(fail_chunk=fail_chunk, fail_which=fail_which, how=how))
+    y0, y1 = band_rows(key)
+    return Op(fam, key, run, lambda: band_util.band(flags(key, seed), y0, y1, band_weights(key), 0, x(), sects, columns), same_band, io, note=note,
+              args=dict(dtype=field, how=how, sectors=sectors, columns=columns))
+
+
+def band_resident(src, how="array", chunk_steps=0):
+    """the field is the resident anomaly slab, named by the generation its producer left; the flags are the tracking of that slab.
+    The streamed forms still send the flags through io_in"""
+    key = src[0]
+    sects = band_sectors(key)
+
+    def run(trk, env):
+        f = resident_flag(src)
+        return _band_call(trk, how, key, f, None, src[1], chunk_steps, sects, True, (_chunks_reader(f), None), resident_gen=env.generation, resident_f64=src[1] == "f8")
+    y0, y1 = band_rows(key)
+    return Op("band_resident", key, run, lambda: band_util.band(resident_flag(src), y0, y1, band_weights(key), 0, want_anom(*src)[0], sects, True), same_band,
+              band_io(key, how, src[1], chunk_steps, False), needs="anom", note="%s chunk=%d" % (how, chunk_steps), args=dict(how=how))
+
+
+def band_stale(src, how="array"):
+    """the same call with the generation of the slab that was resident BEFORE the one that is: refused while a slab of the same shape
+    and type is resident, in words that name both generations"""
+    key = src[0]
+
+    def run(trk, env):
+        f = resident_flag(src)
+        stale = env.stale_generation if env.stale_generation is not None else env.generation - 1
+        try:
+            _band_call(trk, how, key, f, None, src[1], 0, band_sectors(key), True, (_chunks_reader(f), None), resident_gen=stale, resident_f64=src[1] == "f8")
+        except _state_errors() as e:
+            if isinstance(e, ValueError):
+                raise
+            return StateError(str(e)), env.generation, stale
+        return None
+
+    def same(got, want):
+        return (got is not None and got[1] != got[2] and refused_with(STATE_RC, "stale generation")(got[0], None)
+                and "is generation %d," % got[1] in str(got[0]) and "stale generation %d" % got[2] in str(got[0]))
+    return Op("band_resident", key, run, lambda: None, same, NO_IO, needs="anom", note="%s names a stale generation" % how, args=dict(how=how, stale_generation=True))
+
+
+# ---- block-centred composite ------------------------------------------------------------------------------------------------------
+CENTRED = dict(nbins=3, hy=2, hx=3)
+N_STAMPS = 40
+
+
+def stamp_gap(key):
+    """the time steps [g0, g1) in which no stamp is kept: half of the slab, in its middle"""
+    T = SHAPES[key][0]
+    return T // 4, T // 4 + T // 2
+
+
+@functools.lru_cache(maxsize=None)
+def stamps(key, seed=0):
+    """(t, row, col, bin) of N_STAMPS stamps: t sorted, bin in [-1, nbins); the rows lie in a few neighbouring rows of the grid, so the
+    windows of a chunk touch a band of fewer than ny rows (the host-array form copies that band alone); the stamps inside stamp_gap
+    all have bin -1, so a chunk that lies in the gap carries stamps but none that is kept"""
+    T, ny, nx = SHAPES[key]
+    rng = np.random.default_rng(100 + seed)
+    g0, g1 = stamp_gap(key)
+    outside = np.concatenate([np.arange(0, g0), np.arange(g1, T)])
+    t = np.sort(np.concatenate([rng.choice(outside, N_STAMPS - 4), rng.integers(g0, g1, 4)])).astype(np.int64)
+    bin = rng.integers(-1, CENTRED["nbins"], N_STAMPS).astype(np.int32)
+    bin[(t >= g0) & (t < g1)] = -1
+    r0, span = ny // 3, max(2, ny // 5)
+    row = rng.integers(r0, r0 + span, N_STAMPS).astype(np.int32)
+    col = rng.integers(0, nx, N_STAMPS).astype(np.int32)
+    return tuple(_frozen(a) for a in (t, row, col, bin))
+
+
+def stamps_none_kept(key, seed=0):
+    """the same stamps with every bin -1: nothing is kept, nothing is read, the composite is all zeros"""
+    t, row, col, bin = stamps(key, seed)
+    return t, row, col, _frozen(np.full_like(bin, -1))
+
+
+def carrying_chunks(key, chunk_steps, esz=4, seed=0, none_kept=False):
+    """centred_stream_impl's walk restated: (chunk length, [(index of a chunk that carries a kept stamp, the rows of the band its
+    windows touch), ...])"""
+    T, ny, nx = SHAPES[key]
+    t, row, col, bin = (stamps_none_kept if none_kept else stamps)(key, seed)
+    c = _chunk(chunk_steps, T, ny * nx * esz)
+    out = []
+    for k in range(-(-T // c)):
+        kept = (t // c == k) & (bin >= 0)
+        if kept.any():
+            lo, hi = int(row[kept].min()), int(row[kept].max())
+            out.append((k, min(hi + CENTRED["hy"], ny - 1) - max(lo - CENTRED["hy"], 0) + 1))
+    return c, out
+
+
+def centred_chunk_lengths(key):
+    """the chunk lengths below 20 at which a centred call has at least two carrying chunks and one chunk that carries none"""
+    T = SHAPES[key][0]
+    return [c for c in range(2, 20) if len(carrying_chunks(key, c)[1]) >= 2 and len(carrying_chunks(key, c)[1]) < -(-T // c)]
+
+
+def centred_io(key, how, esz, chunk_steps, seed=0, none_kept=False):
+    """centred_stream_impl: two buffers of chunk x (the widest band of rows of a carrying chunk, for a reader whole planes) in io_in
+    and for a reader a pinned chunk; nothing at all when no stamp is kept.  The _dev entries claim nothing"""
+    T, ny, nx = SHAPES[key]
+    c, pieces = carrying_chunks(key, chunk_steps, esz, seed, none_kept)
+    io = dict(NO_IO, chunk=c, chunks=-(-T // c), carrying=len(pieces), max_rows=max([r for _, r in pieces], default=0))
+    if how != "dev" and pieces:
+        one = c * (ny if how == "cb" else io["max_rows"]) * nx * esz
+        io.update(io_in=2 * one, pin_in=one if how == "cb" else 0)
+    return io
+
+
+def same_centred(got, want):
+    return got[1].dtype == np.uint32 and np.array_equal(got[1], want[1]) and centred_util.same_bits(got[0], want[0])
+
+
+def centred(key, how="array", dtype="f4", chunk_steps=0, fail_chunk=None, seed=0, none_kept=False):
+    """fail_chunk counts the reader's calls, that is the carrying chunks.  The reader form also reports the reader's calls: exactly
+    the carrying chunks, in order.  none_kept: every stamp is dropped -- the call claims no buffer and reads nothing"""
+    assert how in ("array", "cb", "dev")
+    T, ny, nx = SHAPES[key]
+    esz = 4 if dtype == "f4" else 8
+    kw = dict(CENTRED)
+    the_stamps = lambda: (stamps_none_kept if none_kept else stamps)(key, seed)               # noqa: E731
+
+    def run(trk, env):
+        x = wide_field(key, dtype, seed)
+        t, row, col, bin = the_stamps()
+        if how == "array":
+            return trk.centred(x, t, row, col, bin, chunk_steps=chunk_steps, **kw)
+        if how == "cb":
+            calls = []
+            s, n = trk.centred_cb(_chunks_reader(x, fail_chunk, calls), (T, ny, nx), DT[dtype], t, row, col, bin, chunk_steps=chunk_steps, **kw)
+            return s, n, calls
+        dx = trk.malloc(x.nbytes)
+        try:
+            trk.h2d(dx, x)
+            return trk.centred_dev(dx, T, ny, nx, t, row, col, bin, f64=dtype == "f8", **kw)
+        finally:
+            trk.free(dx)
+    fam = {"array": "centred", "cb": "centred_cb", "dev": "centred_dev"}[how]
+    io = centred_io(key, how, esz, chunk_steps, seed, none_kept)
+    note = "%s chunk=%d%s" % (dtype, chunk_steps, " no stamp kept" if none_kept else "")
+    if fail_chunk is not None:
+        assert how == "cb" and fail_chunk <= io["carrying"]
+        return Op(fam, key, _catching(run, ReaderGaveUp), lambda: None, gave_up, io, note="%s: the reader gives up on carrying chunk %d" % (note, fail_chunk),
+                  args=dict(fail_chunk=fail_chunk, how=how))
+
+    def same(got, want):
+        c, pieces = carrying_chunks(key, chunk_steps, esz, seed, none_kept)
+        return same_centred(got, want) and (how != "cb" or got[2] == [(k * c, min(c, T - k * c)) for k, _ in pieces])
+    return Op(fam, key, run, lambda: centred_util.centred(wide_field(key, dtype, seed), *the_stamps(), **kw), same, io, note=note,
+              args=dict(dtype=dtype, how=how, none_kept=none_kept))
+
+
+def centred_resident(src, how="array", chunk_steps=5):
+    """the field is the resident anomaly slab (NaNs left out: skipna), taken by shape and type alone; one launch over all stamps"""
+    key = src[0]
+    T, ny, nx = SHAPES[key]
+    kw = dict(CENTRED, skipna=True)
+
+    def run(trk, env):
+        t, row, col, bin = stamps(key)
+        if how == "array":
+            return trk.centred(None, t, row, col, bin, chunk_steps=chunk_steps, resident_f64=src[1] == "f8", shape=(T, ny, nx), **kw)
+        if how == "cb":
+            return trk.centred_cb(None, (T, ny, nx), DT[src[1]], t, row, col, bin, chunk_steps=chunk_steps, **kw)
+        return trk.centred_dev(None, T, ny, nx, t, row, col, bin, f64=src[1] == "f8", **kw)
+    return Op("centred_resident", key, run, lambda: centred_util.centred(want_anom(*src)[0], *stamps(key), **kw), same_centred, NO_IO, needs="anom", note=how,
+              args=dict(how=how))
 
 
 # ---- lifecycle ------------------------------------------------------------------------------------------------------------------
@@ -778,7 +1054,7 @@ def anomalies_resident(src):
 
 # ---- percentile and standard-deviation thresholds -------------------------------------------------------------------------------
 def _percentile(trk, env, x, key, q):
-    y0, y1 = band(key)
+    y0, y1 = band_rows(key)
     mean = trk.percentile(x, y0, y1, q)
     return mean, trk.debug_percentile_values((y1 - y0) * SHAPES[key][2])
 
@@ -824,22 +1100,22 @@ def percentile_resident(src, q=0.9):
 
 def percentile_groups(key, dtype="f4", q=0.9, window=3, seed=3):
     def run(trk, env):
-        return trk.percentile_groups(anom_input(key, dtype, seed), *band(key), anom_groups(key), ANOM["G"], q, window)
-    return Op("percentile_groups", key, run, lambda: pctl_util.want(anom_input(key, dtype, seed), band(key), anom_groups(key), ANOM["G"], window, q), same_bits64,
+        return trk.percentile_groups(anom_input(key, dtype, seed), *band_rows(key), anom_groups(key), ANOM["G"], q, window)
+    return Op("percentile_groups", key, run, lambda: pctl_util.want(anom_input(key, dtype, seed), band_rows(key), anom_groups(key), ANOM["G"], window, q), same_bits64,
               array_io(key, 4 if dtype == "f4" else 8), note=dtype, args=dict(dtype=dtype))
 
 
 def percentile_field(key, dtype="f4", q=0.9, window=3, seed=3):
     def run(trk, env):
-        return trk.percentile_field(anom_input(key, dtype, seed), *band(key), anom_groups(key), ANOM["G"], q, window)
-    return Op("percentile_field", key, run, lambda: pfield_util.want_field(anom_input(key, dtype, seed), band(key), anom_groups(key), ANOM["G"], window, q),
+        return trk.percentile_field(anom_input(key, dtype, seed), *band_rows(key), anom_groups(key), ANOM["G"], q, window)
+    return Op("percentile_field", key, run, lambda: pfield_util.want_field(anom_input(key, dtype, seed), band_rows(key), anom_groups(key), ANOM["G"], window, q),
               same_bits64, array_io(key, 4 if dtype == "f4" else 8), note=dtype, args=dict(dtype=dtype))
 
 
 def std_field(key, dtype="f4", window=3, ddof=1, seed=3):
     def run(trk, env):
-        return trk.std_field(anom_input(key, dtype, seed), *band(key), anom_groups(key), ANOM["G"], window, ddof, True, want_mean=True, want_n=True)
-    return Op("std_field", key, run, lambda: std_util.want_std(anom_input(key, dtype, seed), band(key), anom_groups(key), ANOM["G"], window, ddof, True), same_std,
+        return trk.std_field(anom_input(key, dtype, seed), *band_rows(key), anom_groups(key), ANOM["G"], window, ddof, True, want_mean=True, want_n=True)
+    return Op("std_field", key, run, lambda: std_util.want_std(anom_input(key, dtype, seed), band_rows(key), anom_groups(key), ANOM["G"], window, ddof, True), same_std,
               array_io(key, 4 if dtype == "f4" else 8), note=dtype, args=dict(dtype=dtype))
 
 
@@ -881,12 +1157,14 @@ REFUSALS = {                           # what every consumer says when its slab 
     "climatology_resident": ("no vertical mean is resident",),
     "lifecycle_resident": (STATE_RC, "needs a resident anomaly slab"),                # ctk_lifecycle_*: CTK_E_STATE
     "composite_resident": (STATE_RC, "needs a resident anomaly slab"),                # ctk_composite_*: CTK_E_STATE
+    "band_resident": (STATE_RC, "none of this shape and type is resident"),           # ctk_band_*: CTK_E_STATE (band_resident, before the generation)
+    "centred_resident": (STATE_RC, "needs a resident anomaly slab"),                  # ctk_centred_*: CTK_E_STATE (comp_resident)
 }
 
 
 def refuses(op):
     """the same call, which must now be refused in its own words"""
-    return Op(op.family, op.key, _refusing(op.run), lambda: None, refused_with(*REFUSALS[op.family]), NO_IO, note="must refuse", args=dict(refuse=True))
+    return Op(op.family, op.key, _refusing(op.run), lambda: None, refused_with(*REFUSALS[op.family]), NO_IO, note=(op.note + ": must refuse").lstrip(": "), args=dict(op.args, refuse=True))
 
 
 # ---- the written sequences ------------------------------------------------------------------------------------------------------
@@ -895,24 +1173,29 @@ S, O, L = "mult4", "odd", "large"
 
 def io_grows_and_shrinks():
     """array entries of different families: small frequency, large track, small level mean, larger anomalies, small spells, large
-    composite, small lifecycle"""
-    return [frequency(S), track(L), level_mean(S), anomalies(O, "f8"), spells(S), composite(L, dtype="f8"), lifecycle(S)]
+    composite, small lifecycle; among them a band with a float64 field and a centred composite, and a band that asks for the sector
+    tables alone (its column tables stay in the handle: bd_cols, sized by its T steps) after a larger one that asked for both"""
+    return [frequency(S), centred(S), track(L), level_mean(S), band(L, field="f8"), anomalies(O, "f8"), band(O, columns=False), spells(S), composite(L, dtype="f8"),
+            lifecycle(S)]
 
 
 def pinned_chunks_up_and_down():
-    """the reader and writer entries with chunk bytes rising and then falling"""
-    return [frequency(S, "cb", chunk_steps=5), composite(O, "cb", chunk_steps=9), lifecycle_stream(L, "f8", chunk_steps=13, readers=True),
-            level_mean(L, "f8", "cb", chunk_steps=16), track_stream(L, "f4", chunk_steps=11, callbacks=True),
-            anomalies_stream(O, "f4", chunk_steps=8, callbacks=True), spells(S, "cb", chunk_steps=3)]
+    """the reader and writer entries with chunk bytes rising and then falling, across the families"""
+    return [frequency(S, "cb", chunk_steps=5), centred(S, "cb", "f4", chunk_steps=3), composite(O, "cb", chunk_steps=9), band(O, "cb", "f8", chunk_steps=12),
+            lifecycle_stream(L, "f8", chunk_steps=13, readers=True), centred(L, "cb", "f8", chunk_steps=7), level_mean(L, "f8", "cb", chunk_steps=16),
+            band(L, "cb", chunk_steps=21), track_stream(L, "f4", chunk_steps=11, callbacks=True), anomalies_stream(O, "f4", chunk_steps=8, callbacks=True),
+            centred(O, "cb", "f4", chunk_steps=4), spells(S, "cb", chunk_steps=3)]
 
 
 def _resident_consumers(src):
-    return [track_resident(src), lifecycle_resident(src), composite_resident(src), percentile_resident(src)]
+    return ([track_resident(src), lifecycle_resident(src), composite_resident(src), percentile_resident(src)]
+            + [band_resident(src, how, chunk_steps=7 if how != "dev" else 0) for how in ("array", "cb", "dev")] + [centred_resident(src, how) for how in ("array", "cb", "dev")])
 
 
 def resident_anomaly_survives():
     src = (S, "f4", 3, False)
-    between = [frequency(L), spells(O), level_mean(O), percentile(L), percentile_groups(L), percentile_field(O), std_field(L), track(L), lifecycle(O)]
+    between = [frequency(L), spells(O), level_mean(O), percentile(L), percentile_groups(L), percentile_field(O), std_field(L), track(L), lifecycle(O),
+               band(L, field="f4", chunk_steps=16), centred(L, "array", "f8", chunk_steps=7), centred(O, "cb", chunk_steps=4)]
     # climatology-only calls on slabs LARGER than the resident one, from the host and from a resident vertical mean: an_out is not theirs
     clim_only = [climatology(L, "f8"), climatology(L, "f4", segments=True), level_mean(L, "f8", keep=True), climatology_resident(("level", L, "f8", 4))]
     return [anomalies(S, "f4", keep=True)] + between + clim_only + [generation_unchanged(src)] + _resident_consumers(src)
@@ -927,8 +1210,12 @@ def resident_level_mean_survives():
 def invalidated_residents_refuse():
     a, lv = (S, "f4", 3, False), ("level", S, "f4", 4)
     every = lambda: [refuses(op) for op in _resident_consumers(a) + [anomalies_resident(lv), climatology_resident(lv)]]                # noqa: E731
-    return ([anomalies(S, "f4", keep=True), level_mean(S, "f4", keep=True), release_io()] + every() + [track(S)]
-            + [anomalies(S, "f4", keep=True), level_mean(S, "f4", keep=True), anomalies(O), level_mean(O)] + every() + [frequency(O)])
+    seq = ([anomalies(S, "f4", keep=True), level_mean(S, "f4", keep=True), release_io()] + every() + [track(S)]
+           + [anomalies(S, "f4", keep=True), level_mean(S, "f4", keep=True), anomalies(O), level_mean(O)] + every() + [frequency(O)])
+    # a slab of the same shape and type but with other values takes the place of the first: only its generation tells them apart
+    b = (S, "f4", 5, False)
+    return seq + [anomalies(S, "f4", keep=True, seed=3), anomalies(S, "f4", keep=True, seed=5)] + [band_stale(b, how) for how in ("array", "cb", "dev")] + [
+        band_resident(b, "array", chunk_steps=7), band_resident(b, "dev"), centred_resident(b, "array"), centred_resident(b, "dev")]
 
 
 def tracking_caches(key=O):
@@ -939,16 +1226,25 @@ def tracking_caches(key=O):
 
 
 def sticky_settings_do_not_leak(key=S):
-    return [set_sticky(key), frequency(key), spells(key, segments=True), anomalies(key, segments=True), composite(key), lifecycle(key),
-            clear_sticky(), track(key)]
+    return [set_sticky(key), frequency(key), spells(key, segments=True), anomalies(key, segments=True), composite(key), band(key, field="f4", chunk_steps=9),
+            centred(key, chunk_steps=3), lifecycle(key), clear_sticky(), track(key)]
 
 
 def a_failed_stream_then_others():
     T = SHAPES[L][0]
     c = -(-T // 5)                                        # five chunks
-    return [frequency(L, "cb", chunk_steps=c, fail_chunk=3), spells(S, "cb", chunk_steps=4), composite(S),
-            level_mean(L, "f4", "cb", chunk_steps=c, fail_chunk=3), frequency(O, "cb", chunk_steps=6), track(O),
-            track_stream(L, "f4", chunk_steps=c, callbacks=True, fail_chunk=3), anomalies_stream(S, chunk_steps=5), lifecycle(S)]
+    seq = [frequency(L, "cb", chunk_steps=c, fail_chunk=3), spells(S, "cb", chunk_steps=4), composite(S),
+           level_mean(L, "f4", "cb", chunk_steps=c, fail_chunk=3), frequency(O, "cb", chunk_steps=6), track(O),
+           track_stream(L, "f4", chunk_steps=c, callbacks=True, fail_chunk=3), anomalies_stream(S, chunk_steps=5), lifecycle(S)]
+    # a band reader that gives up on chunk 3 of 5: the tables of chunks 1 and 2 are queued for the pinned twins and never land; the
+    # next streamed band call, on another shape, uses the twins and both table sets at once
+    for which in ("flag", "field"):
+        seq += [band(L, "cb", "f4", chunk_steps=c, fail_chunk=3, fail_which=which), band(O, "cb", "f8", chunk_steps=8), composite(S)]
+    # a centred reader that gives up on its third carrying chunk: two chunks are in flight on the tracker's buffers and events
+    seq += [centred(L, "cb", "f4", chunk_steps=7, fail_chunk=3), track_stream(O, "f4", chunk_steps=9, callbacks=True), centred(L, "cb", "f4", chunk_steps=7)]
+    # ... and a centred reader call directly after another family's failed stream
+    seq += [frequency(L, "cb", chunk_steps=c, fail_chunk=3), centred(O, "cb", "f8", chunk_steps=4), lifecycle(S)]
+    return seq
 
 
 def exact_rows_follow_their_slabs():
@@ -956,6 +1252,16 @@ def exact_rows_follow_their_slabs():
     seq = [lifecycle(O), exact_rows_again(), frequency(L, "dev"), spells(L, "dev"), composite(L, "dev"), exact_rows_again()]
     for breaker in (frequency(S), track(S), level_mean(S), anomalies(L), percentile_field(S), release_io()):
         seq += [breaker, exact_rows_stale(), exact_rows_stale(columns=True), lifecycle(O), exact_rows_again()]
+    # band and centred: the streamed forms claim the staging buffers (also a band on the resident slab: its flags travel), the _dev
+    # forms, a centred composite of the resident slab and a centred call none of whose stamps is kept (it skips stream_setup) claim
+    # nothing -- Op.breaks_exact says which, and the rows follow it
+    # (first a call that makes io_in and io_out larger than anything this leg asks of them: no buffer moves under the rows here, so
+    # a library that forgot to make them stale would answer with wrong records, which is what the sequence reports)
+    seq += [anomalies(S, "f4", keep=True), composite(L, dtype="f8"), lifecycle(O), exact_rows_again()]
+    for op in (band(S), band(L, "dev", "f4"), band_resident(src, "array", chunk_steps=7), centred(L, "dev", "f8"), centred(S), centred_resident(src, "dev"),
+               centred(S, "cb", chunk_steps=3), band_resident(src, "dev"), centred_resident(src, "array"), band_resident(src, "cb", chunk_steps=7),
+               centred(L, "array", "f8", chunk_steps=7, none_kept=True), centred(L, "cb", chunk_steps=7, none_kept=True)):
+        seq += [op, exact_rows_stale(), exact_rows_stale(columns=True), lifecycle(O), exact_rows_again()] if op.breaks_exact else [op, exact_rows_again()]
     # field = None: the field is the resident anomaly slab, which any anomaly call writes or drops
     seq += [anomalies(S, "f4", keep=True), lifecycle_resident(src), exact_rows_again(), anomalies_stream(S, chunk_steps=5, callbacks=False), exact_rows_stale(),
             lifecycle_resident(src), exact_rows_again(), anomalies(S, "f4", keep=True), exact_rows_stale(), lifecycle_resident(src), exact_rows_again()]
@@ -973,7 +1279,7 @@ WRITTEN = [io_grows_and_shrinks, pinned_chunks_up_and_down, resident_anomaly_sur
 
 
 # ---- the seeded sequences -------------------------------------------------------------------------------------------------------
-N_SEEDS, N_OPS = 12, 10
+N_SEEDS, N_OPS = 22, 10                # 22 sequences: every one of the 40 families is drawn three times or more (a consumer drawn last is skipped)
 
 
 def _vocabulary():
@@ -982,6 +1288,7 @@ def _vocabulary():
     key = lambda rng: pick(rng, (S, O, L))                                                    # noqa: E731
     dt = lambda rng: pick(rng, ("f4", "f8"))                                                  # noqa: E731
     chunk = lambda rng: int(rng.integers(2, 20))                                              # noqa: E731
+    tables = ((True, True), (True, False), (False, True))                                     # (sectors, columns) of a band call
     return {
         "track": lambda r, s: track(key(r), dt(r), thr=pick(r, (100.0, 130.0)), wvar=pick(r, (1, 2)), per_step=bool(r.integers(2))),
         "track_field": lambda r, s: track_field(key(r), dt(r)),
@@ -999,6 +1306,14 @@ def _vocabulary():
         "composite_cb": lambda r, s: composite(key(r), "cb", dt(r), chunk(r)),
         "composite_dev": lambda r, s: composite(key(r), "dev", dt(r)),
         "composite_resident": lambda r, s: composite_resident(s["anom"]),
+        "band": lambda r, s: band(key(r), "array", pick(r, (None, "f4", "f8")), pick(r, (0, chunk(r))), *pick(r, tables)),
+        "band_cb": lambda r, s: band(key(r), "cb", pick(r, (None, "f4", "f8")), chunk(r), *pick(r, tables)),
+        "band_dev": lambda r, s: band(key(r), "dev", pick(r, (None, "f4", "f8")), 0, *pick(r, tables)),
+        "band_resident": lambda r, s: band_resident(s["anom"], *pick(r, (("array", 0), ("array", chunk(r)), ("cb", chunk(r)), ("dev", 0)))),
+        "centred": lambda r, s: (lambda k: centred(k, "array", dt(r), pick(r, [0] + centred_chunk_lengths(k))))(key(r)),
+        "centred_cb": lambda r, s: (lambda k: centred(k, "cb", dt(r), pick(r, centred_chunk_lengths(k))))(key(r)),
+        "centred_dev": lambda r, s: centred(key(r), "dev", dt(r)),
+        "centred_resident": lambda r, s: centred_resident(s["anom"], pick(r, ("array", "cb", "dev"))),
         "lifecycle": lambda r, s: lifecycle(key(r), dt(r)),
         "lifecycle_stream": lambda r, s: lifecycle_stream(key(r), dt(r), chunk(r), readers=bool(r.integers(2))),
         "lifecycle_resident": lambda r, s: lifecycle_resident(s["anom"]),
@@ -1018,8 +1333,8 @@ def _vocabulary():
     }
 
 
-CONSUMERS = {"track_resident": "anom", "composite_resident": "anom", "lifecycle_resident": "anom", "percentile_resident": "anom", "anomalies_resident": "level",
-             "climatology_resident": "level"}
+CONSUMERS = {"track_resident": "anom", "composite_resident": "anom", "lifecycle_resident": "anom", "percentile_resident": "anom", "band_resident": "anom",
+             "centred_resident": "anom", "anomalies_resident": "level", "climatology_resident": "level"}
 FAMILIES = sorted(_vocabulary())
 
 
@@ -1062,20 +1377,51 @@ def seeded(seed):
 
 
 # ---- running a sequence ---------------------------------------------------------------------------------------------------------
+def grown(cap, need, buf):
+    """the capacity of a shared buffer after a call that asks `need` bytes of it (0: the call does not touch it).  All four are
+    grow-only until ctk_release_io.  io_in / io_out go through claim_io -> ensure (csrc/ctk_api.hip): a buffer that holds the bytes
+    stays; one that does not is released and allocated anew with head room, need + need / 8 + 256 bytes.  The pinned pairs
+    (PinPair::grow, csrc/ctk_own.h) get exactly the bytes asked for."""
+    if need <= cap:
+        return cap
+    return need + need // 8 + 256 if buf.startswith("io_") else need
+
+
+def check_io(cap, op, got, raised=False):
+    """`cap`: the model's capacities before `op`; `got`: Tracker.debug_io_bytes() after it.  The mismatches as (buffer, got, model);
+    `cap` becomes the capacities after the call.  Where the request depends on the data (Op.io_upto) or the call gave up on the way
+    (`raised`: it may have claimed its buffers before), the model is a range and the handle's own figure inside it is taken over."""
+    bad = []
+    for buf in BUFFERS:
+        if op.family == "release_io":
+            lo = hi = 0
+        else:
+            hi = grown(cap[buf], max(op.io[buf], op.io_upto.get(buf, 0)), buf)
+            lo = cap[buf] if raised else grown(cap[buf], op.io[buf], buf)
+        if not lo <= got[buf] <= hi or got[buf] < op.io[buf] * (not raised):
+            bad.append((buf, got[buf], lo if lo == hi else (lo, hi)))
+        cap[buf] = got[buf]
+    return bad
+
+
 def run_sequence(trk, ops, env=None):
     """every operation in order on `trk`, each compared with its reference: the list of failures (empty: all right) as
-    (position, op, what).  After every tracking operation the handle's ambiguous_decisions must be 0."""
+    (position, op, what).  After every tracking operation the handle's ambiguous_decisions must be 0.  After every operation the
+    capacities of the shared buffers (Tracker.debug_io_bytes) are what Op.io says the handle asked for, from the capacities the
+    sequence found: (position, op, "io model", buffer, got, model) otherwise."""
     env = env or Env()
     bad = []
+    cap = trk.debug_io_bytes()
     for i, op in enumerate(ops):
         got = op.run(trk, env)
         if op.gives is not None:
             if op.gives[0] == "anom":
-                env.generation = trk.resident_generation()
+                env.stale_generation, env.generation = env.generation, trk.resident_generation()
             else:
                 env.level_generation = trk.resident_level_mean_generation()
         if not op.same(got, op.want()):
             bad.append((i, repr(op), "differs from its reference", getattr(op.same, "detail", "")))
         if op.tracking and trk.stats()["ambiguous_decisions"] != 0:
             bad.append((i, repr(op), "ambiguous_decisions = %d" % trk.stats()["ambiguous_decisions"]))
+        bad += [(i, repr(op), "io model") + m for m in check_io(cap, op, trk.debug_io_bytes(), raised=isinstance(got, ReaderGaveUp))]
     return bad

@@ -1,7 +1,8 @@
 """Everything a handle takes from the GPU goes back with it: ctk_debug_live (device buffers, pinned buffers, events, streams held by
 the owners of csrc/ctk_own.h in this process) reads the same after Tracker.close() as before Tracker(), after a handle that ran
-every written sequence of tests/handle_sequences.py and one call of each entry family they do not reach -- and after a handle that
-ran nothing.  Other handles of the process (module fixtures of other test files) may be alive meanwhile: only differences are
+every written sequence of tests/handle_sequences.py (which reach every entry family but the time-shard path, the band and centred
+families included), once more a streamed band and a streamed centred call on inputs of their own, and one call of the time-shard
+path -- and after a handle that ran nothing.  Other handles of the process (module fixtures of other test files) may be alive meanwhile: only differences are
 compared.  Every call is also compared with its family's reference, exactly."""
 import gc
 

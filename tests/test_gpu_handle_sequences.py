@@ -1,7 +1,8 @@
 """One handle, every entry family, in the orders a script could choose (tests/handle_sequences.py): the written sequences run in file
 order on ONE module-scoped Tracker -- the handle is as old as the module can make it -- and the seeded sequences share another.  Every
 operation of every sequence is compared with the reference of its family's own test, exactly; after every tracking operation the
-handle's ambiguous_decisions is 0; at the end a plain track of a golden case still equals its golden flag.
+handle's ambiguous_decisions is 0; after every operation the capacities of the four shared staging buffers (ctk_debug_io_bytes) are
+what the sequences' size model says the handle asked for; at the end a plain track of a golden case still equals its golden flag.
 
 exact_rows_follow_their_slabs is the test of ctk_lifecycle_exact's staleness rule (include/contrack_hip.h): the exact rows of a
 host-array lifecycle call are refused with the state error once a later call has written or released the handle's staging buffers
@@ -43,7 +44,7 @@ def oracle_built(oracle_lib):
 
 def _run(trk, ops):
     bad = hs.run_sequence(trk, ops)
-    assert not bad, bad
+    assert not bad, "\n".join(repr(b) for b in bad)              # (one failure per line, none cut short)
 
 
 @pytest.mark.parametrize("sequence", hs.WRITTEN, ids=[f.__name__ for f in hs.WRITTEN])

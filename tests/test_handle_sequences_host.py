@@ -12,6 +12,44 @@ def oracle_built(oracle_lib):
     return oracle_lib
 
 
+def test_written_sequences_reach_every_form_of_band_and_centred():
+    seen = set()
+    for sequence in hs.WRITTEN:
+        for op in sequence():
+            if op.family.split("_")[0] in ("band", "centred") and not op.args.get("refuse") and not op.args.get("fail_chunk") and not op.args.get("stale_generation"):
+                seen.add((op.family, op.args["how"]))
+                if op.family == "centred" and not op.args["none_kept"]:   # the host-array form sends a band of rows, never whole planes (p.rows < ny)
+                    assert 0 < op.io["max_rows"] < hs.SHAPES[op.key][1], op
+                if op.family.startswith("band") and op.args.get("columns") is False:
+                    seen.add((op.family, "sectors only"))
+    want = {("band", "array"), ("band_cb", "cb"), ("band_dev", "dev"), ("band", "sectors only")} | {("band_resident", h) for h in ("array", "cb", "dev")}
+    want |= {("centred", "array"), ("centred_cb", "cb"), ("centred_dev", "dev")} | {("centred_resident", h) for h in ("array", "cb", "dev")}
+    assert want <= seen, sorted(want - seen)
+
+
+def test_the_io_model_of_the_runner():
+    """grown / check_io: head room where claim_io -> ensure gives it, exact bytes for the pinned pairs, grow-only, zero after release_io"""
+    assert hs.grown(0, 1000, "io_in") == 1000 + 125 + 256 and hs.grown(2000, 1000, "io_in") == 2000 and hs.grown(0, 1000, "pin_in") == 1000
+    assert hs.grown(1381, 1381, "io_out") == 1381 and hs.grown(1381, 1382, "io_out") == 1382 + 172 + 256 and hs.grown(500, 0, "io_in") == 500
+    op = hs.frequency("mult4", "cb", chunk_steps=5)
+    cap = dict(hs.NO_IO)
+    got = {b: hs.grown(0, op.io[b], b) for b in hs.BUFFERS}
+    assert hs.check_io(cap, op, got) == [] and cap == got and got["io_in"] > op.io["io_in"] > 0 and got["pin_in"] == op.io["pin_in"] > 0
+    assert hs.check_io(dict(cap), hs.frequency("mult4", "cb", chunk_steps=3), got) == []                      # a smaller request: unchanged
+    short = dict(got, io_in=got["io_in"] - 1)
+    assert hs.check_io(dict(hs.NO_IO), op, short) == [("io_in", short["io_in"], got["io_in"])]
+    assert hs.check_io(dict(hs.NO_IO), op, dict(got, pin_out=8)) == [("pin_out", 8, 0)]                       # a buffer the model says is not touched
+    assert hs.check_io(dict(cap), hs.release_io(), got) != [] and hs.check_io(dict(cap), hs.release_io(), dict(hs.NO_IO)) == []
+    # a tracking result: 256 bytes of io_out, or the dense bytes of the blocks with complex components, whichever the data ask for
+    tr = hs.track("mult4")
+    base = {b: hs.grown(0, tr.io[b], b) for b in hs.BUFFERS}
+    assert hs.check_io(dict(hs.NO_IO), tr, base) == [] and hs.check_io(dict(hs.NO_IO), tr, dict(base, io_out=40000)) == []
+    assert hs.check_io(dict(hs.NO_IO), tr, dict(base, io_out=hs.grown(0, 24 * 19 * 36 * 4, "io_out") + 1)) != []
+    # a call that gave up may or may not have claimed its buffers
+    fail = hs.frequency("mult4", "cb", chunk_steps=5, fail_chunk=2)
+    assert hs.check_io(dict(hs.NO_IO), fail, got, raised=True) == [] and hs.check_io(dict(hs.NO_IO), fail, dict(hs.NO_IO), raised=True) == []
+
+
 def _rises_and_falls(values):
     """some request exceeds everything before it (the buffer must grow) and a later one is smaller (the grown buffer is reused)"""
     values = [v for v in values if v]
@@ -32,24 +70,61 @@ def test_shapes_are_what_the_module_says():
 
 def test_io_grows_and_shrinks_does():
     ops = hs.io_grows_and_shrinks()
-    assert [op.family for op in ops] == ["frequency", "track", "level_mean", "anomalies", "spells", "composite", "lifecycle"]
+    assert [op.family for op in ops] == ["frequency", "centred", "track", "level_mean", "band", "anomalies", "band", "spells", "composite", "lifecycle"]
     for buf in ("io_in", "io_out"):
         assert _rises_and_falls([op.io[buf] for op in ops]), buf
         assert len(_families_touching(ops, buf)) >= 2, buf
+    assert {"band", "centred"} <= _families_touching(ops, "io_in") and "band" in _families_touching(ops, "io_out")
     assert all(op.io["pin_in"] == 0 and op.io["pin_out"] == 0 for op in ops)          # array entries: nothing pinned
+    # the band with a float64 field on the large shape makes io_in grow (the field is the first slab) and puts the flags into io_out
+    bands = [op for op in ops if op.family == "band"]
+    T, ny, nx = hs.SHAPES["large"]
+    assert bands[0].key == "large" and bands[0].args["dtype"] == "f8" and bands[0].io["io_in"] == 2 * T * ny * nx * 8 and bands[0].io["io_out"] == 2 * T * ny * nx * 4
+    assert bands[0].io["io_in"] > max(op.io["io_in"] for op in ops[:ops.index(bands[0])])
+    # ... and the one after it asks for the sector tables alone, on a smaller shape, after one that asked for columns and sectors
+    assert bands[0].args["columns"] and bands[0].args["sectors"] and bands[1].args["sectors"] and not bands[1].args["columns"] and bands[1].key == "odd"
+    assert sorted(bands[1].want()) == ["sec_area", "sec_cnt"]
+    # the centred composite of a host array sends the band of rows its windows touch, not whole planes
+    ce = ops[1]
+    T, ny, nx = hs.SHAPES[ce.key]
+    assert ce.key == "mult4" and 0 < ce.io["max_rows"] < ny and ce.io["io_in"] == 2 * ce.io["chunk"] * ce.io["max_rows"] * nx * 4
 
 
 def test_pinned_chunks_up_and_down_does():
     ops = hs.pinned_chunks_up_and_down()
-    assert [op.family for op in ops] == ["frequency_cb", "composite_cb", "lifecycle_stream", "level_mean_cb", "track_stream", "anomalies_stream", "spells_cb"]
+    assert [op.family for op in ops] == ["frequency_cb", "centred_cb", "composite_cb", "band_cb", "lifecycle_stream", "centred_cb", "level_mean_cb", "band_cb",
+                                         "track_stream", "anomalies_stream", "centred_cb", "spells_cb"]
     for buf in ("pin_in", "pin_out", "io_in", "io_out"):
         assert _rises_and_falls([op.io[buf] for op in ops]), (buf, [op.io[buf] for op in ops])
         assert len(_families_touching(ops, buf)) >= 2, buf
+    assert {"band_cb", "centred_cb"} <= _families_touching(ops, "pin_in") and {"band_cb", "centred_cb"} <= _families_touching(ops, "io_in")
+    assert "band_cb" in _families_touching(ops, "pin_out") and "band_cb" in _families_touching(ops, "io_out")
     assert all(op.io["chunks"] >= 2 for op in ops)                                   # both buffers of every pair are used
+    # one band call with both readers (the flags go through pin_out), one with the flag reader alone (they go through pin_in)
+    both, alone = [op for op in ops if op.family == "band_cb"]
+    assert both.args["dtype"] == "f8" and both.io["pin_out"] == both.io["chunk"] * 9 * 65 * 4 and both.io["pin_in"] == 2 * both.io["pin_out"]
+    assert alone.args["dtype"] is None and alone.io["pin_out"] == 0 and alone.io["pin_in"] == alone.io["chunk"] * 31 * 60 * 4 and alone.io["chunks"] >= 3
+    # the centred calls: three carrying chunks or more (the buffer of the first is used again), and a chunk that is never read
+    pins = [op.io["pin_in"] for op in ops if op.family == "centred_cb"]
+    assert pins[1] > pins[0] and pins[1] > pins[2]                                   # up and down within the family as well
+    for op in ops:
+        if op.family == "centred_cb":
+            _a_chunk_without_kept_stamps(op)
+
+
+def _a_chunk_without_kept_stamps(op, carrying=3):
+    """read from the stamps and the chunk length: at least `carrying` chunks hold a kept stamp, and some chunk holds stamps but none
+    that is kept"""
+    T = hs.SHAPES[op.key][0]
+    t, row, col, bin = hs.stamps(op.key)
+    c = op.io["chunk"]
+    kept = sorted({int(k) for k in t[bin >= 0] // c})
+    assert len(kept) == op.io["carrying"] >= carrying and op.io["chunks"] == -(-T // c) > len(kept)
+    assert {int(k) for k in t[bin < 0] // c} - set(kept)
 
 
 def test_resident_sequences_keep_their_slab_in_the_model():
-    for seq, slab_name, n_consumers in ((hs.resident_anomaly_survives(), "anom", 4), (hs.resident_level_mean_survives(), "level", 1)):
+    for seq, slab_name, n_consumers in ((hs.resident_anomaly_survives(), "anom", 10), (hs.resident_level_mean_survives(), "level", 1)):
         state = {"anom": None, "level": None}
         hs.apply_residency(state, seq[0])
         assert state[slab_name] is not None
@@ -64,8 +139,15 @@ def test_resident_sequences_keep_their_slab_in_the_model():
         assert max(op.io["io_in"] for op in between) > seq[0].io["io_in"] and {op.key for op in between} - {seq[0].key}
     seq = hs.resident_anomaly_survives()
     fams = [op.family for op in seq]
-    for f in ("frequency", "spells", "level_mean", "percentile", "percentile_groups", "percentile_field", "std_field", "track", "lifecycle"):
+    for f in ("frequency", "spells", "level_mean", "percentile", "percentile_groups", "percentile_field", "std_field", "track", "lifecycle", "band", "centred", "centred_cb"):
         assert f in fams, f
+    # the band and centred calls in between are streamed (they claim the staging buffers), on larger shapes than the resident slab's,
+    # and the band carries a field; the consumers reach every form of both families
+    for op in seq:
+        if op.family in ("band", "centred", "centred_cb") and op.needs is None:
+            assert op.breaks_exact and np.prod(hs.SHAPES[op.key]) > np.prod(hs.SHAPES[seq[0].key]) and op.args["dtype"], op
+    for fam in ("band_resident", "centred_resident"):
+        assert [op.args["how"] for op in seq if op.family == fam] == ["array", "cb", "dev"]
     # the climatology-only calls work on slabs larger than the resident one (a buffer sized for theirs would have to grow) and, in
     # the model, neither leave nor drop an anomaly slab
     only = [op for op in seq if op.family in ("climatology", "climatology_resident")]
@@ -84,9 +166,34 @@ def test_invalidated_residents_refuse_in_the_model():
             need = hs.CONSUMERS[op.family]
             assert state[need] is None, (i, op)                   # the model agrees that the slab is gone
             refusals += 1
+        elif op.needs:
+            assert state[op.needs] is not None, (i, op)
         hs.apply_residency(state, op)
-    assert refusals == 12                                         # the six consumers after release_io and after the calls without keep
-    assert not seq[-1].args.get("refuse") and seq[-1].needs is None
+    # the four consumers of before, three forms of band and of centred on the anomaly slab, two consumers of the vertical mean: after
+    # release_io and after the calls without keep
+    assert refusals == 24
+    assert {(op.family, op.args.get("how")) for op in seq if op.args.get("refuse")} >= {(f, h) for f in ("band_resident", "centred_resident") for h in ("array", "cb", "dev")}
+    end = next(i for i, op in enumerate(seq) if not op.args.get("refuse") and op.family == "frequency")
+    assert not any(op.args.get("refuse") for op in seq[end:])
+    # the stale-generation leg: two producers of one shape and type whose slabs differ, the refusals, then the consumers of the NEW slab
+    leg = seq[end + 1:]
+    assert [op.family for op in leg[:2]] == ["anomalies", "anomalies"] and leg[0].gives[1:3] == leg[1].gives[1:3] and leg[0].gives[3] != leg[1].gives[3]
+    a3, a5 = leg[0].want()[0], leg[1].want()[0]
+    assert a3.shape == a5.shape and a3.dtype == a5.dtype and not np.array_equal(a3, a5, equal_nan=True)
+    assert [(op.family, op.args["how"]) for op in leg[2:5]] == [("band_resident", h) for h in ("array", "cb", "dev")] and all(op.args.get("stale_generation") for op in leg[2:5])
+    after = leg[5:]
+    assert {op.family for op in after} == {"band_resident", "centred_resident"} and not any(op.args.get("stale_generation") for op in after)
+    old = leg[0].gives[1:]
+    for op in after:                                              # their references are the new slab's, and differ from the old slab's
+        other = (hs.band_resident if op.family == "band_resident" else hs.centred_resident)(old, op.args["how"])
+        w, wo = op.want(), other.want()
+        if op.family == "band_resident":
+            assert not np.array_equal(w["wx"], wo["wx"])
+        else:
+            assert not np.array_equal(w[0], wo[0])
+    # the words of the refusal, both generations in them
+    msg = "libcontrack_hip rc=-6: ctk_band_f32: the resident anomaly slab is generation 7, the call names the stale generation 6"
+    assert leg[2].same((hs.StateError(msg), 7, 6), None) and not leg[2].same((hs.StateError(msg), 8, 6), None) and not leg[2].same(None, None)
 
 
 def test_tracking_caches_changes_one_thing_at_a_time():
@@ -115,7 +222,8 @@ def test_tracking_caches_changes_one_thing_at_a_time():
 
 def test_sticky_settings_sequence():
     ops = hs.sticky_settings_do_not_leak()
-    assert [op.family for op in ops] == ["set_sticky", "frequency", "spells", "anomalies", "composite", "lifecycle", "clear_sticky", "track"]
+    assert [op.family for op in ops] == ["set_sticky", "frequency", "spells", "anomalies", "composite", "band", "centred", "lifecycle", "clear_sticky", "track"]
+    assert all(op.io["chunks"] >= 2 for op in ops[5:7]) and ops[5].args["dtype"] and ops[6].io["carrying"] >= 2
     key = ops[0].key
     # the call's own segments of spells / anomalies differ from no segments, so a leak or a loss of either would be seen
     assert not all(np.array_equal(a, b) for a, b in zip(ops[2].want(), hs.spells(key).want()))
@@ -126,8 +234,27 @@ def test_sticky_settings_sequence():
 def test_failed_stream_sequence():
     ops = hs.a_failed_stream_then_others()
     failing = [i for i, op in enumerate(ops) if op.args.get("fail_chunk")]
-    assert [ops[i].family for i in failing] == ["frequency_cb", "level_mean_cb", "track_stream"]
-    for i in failing:
+    assert [ops[i].family for i in failing] == ["frequency_cb", "level_mean_cb", "track_stream", "band_cb", "band_cb", "centred_cb", "frequency_cb"]
+    # a band reader gives up on chunk 3 of 5 -- once the flag reader, once the field reader, which is called after the flag reader of
+    # the same chunk --, and the very next call is a streamed band with readers on another shape, of at least three chunks (both
+    # pinned twins and both table sets are used, the first set twice)
+    assert [ops[i].args["fail_which"] for i in failing[3:5]] == ["flag", "field"]
+    for i in failing[3:5]:
+        assert ops[i].args["fail_chunk"] == 3 and ops[i].io["chunks"] == 5 and ops[i].io["pin_out"] > 0
+        nxt = ops[i + 1]
+        assert nxt.family == "band_cb" and not nxt.args.get("fail_chunk") and nxt.key != ops[i].key and nxt.io["chunks"] >= 3 and nxt.args["sectors"] and nxt.args["columns"]
+        assert ops[i + 2].io["pin_in"] == 0 and not ops[i + 2].family.startswith("band")
+    # a centred reader gives up on its third carrying chunk (two are in flight), then the tracker streams, then the same call succeeds
+    i = failing[5]
+    assert ops[i].args["fail_chunk"] == 3 and ops[i].io["carrying"] >= 4
+    assert ops[i + 1].family == "track_stream" and ops[i + 1].io["pin_in"] > 0 and ops[i + 1].io["chunks"] >= 3
+    assert ops[i + 2].family == "centred_cb" and not ops[i + 2].args.get("fail_chunk") and ops[i + 2].key == ops[i].key and ops[i + 2].io == ops[i].io
+    _a_chunk_without_kept_stamps(ops[i + 2], carrying=4)
+    # ... and a centred reader call directly after another family's failed stream
+    i = failing[6]
+    assert ops[i].io["chunks"] == 5 and ops[i + 1].family == "centred_cb" and not ops[i + 1].args.get("fail_chunk") and ops[i + 1].io["pin_in"] > 0
+    _a_chunk_without_kept_stamps(ops[i + 1])
+    for i in failing[:3]:
         assert ops[i].args["fail_chunk"] == 3 and ops[i].io["chunks"] == 5
         nxt, after = ops[i + 1], ops[i + 2]
         assert nxt.io["chunks"] >= 2 and nxt.family.split("_")[0] != ops[i].family.split("_")[0]                 # a streamed call of another family
@@ -150,7 +277,33 @@ def test_exact_rows_sequence():
     assert all(op.io == hs.NO_IO for op in ops[2:5]) and not ops[5].args.get("stale")            # caller buffers only: still fresh
     stale = [i for i, op in enumerate(ops) if op.args.get("stale")]
     breakers = [ops[i - 1].family for i in stale if not ops[i - 1].args.get("stale")]
-    assert breakers == ["frequency", "track", "level_mean", "anomalies", "percentile_field", "release_io", "anomalies_stream", "anomalies", "anomalies_resident"]
+    assert breakers == ["frequency", "track", "level_mean", "anomalies", "percentile_field", "release_io", "band", "band_resident", "centred", "centred_cb", "band_resident",
+                        "anomalies_stream", "anomalies", "anomalies_resident"]
+    # band and centred: Op.breaks_exact -- the call claims io_in / io_out -- decides whether the rows after it are stale or right, and
+    # both kinds occur, of both families
+    new = [(i, op) for i, op in enumerate(ops) if op.family.split("_")[0] in ("band", "centred")]
+    for i, op in new:
+        assert ops[i + 1].family == "lifecycle_exact" and bool(ops[i + 1].args.get("stale")) == op.breaks_exact, (i, op)
+        assert op.breaks_exact == bool(op.io["io_in"] or op.io["io_out"])
+        last = [o for o in ops[:i] if o.family.startswith("lifecycle") and o.family != "lifecycle_exact"][-1]
+        assert last.family == "lifecycle" and last.key == "odd"                                # rows of a host-array call: the io rule alone
+    none_kept = [op for _, op in new if op.args.get("none_kept")]
+    assert [(op.family, op.key) for op in none_kept] == [("centred", "large"), ("centred_cb", "large")]
+    for op in none_kept:                                                                       # streamed forms that claim nothing: no stamp is kept
+        assert not op.breaks_exact and op.io["carrying"] == 0 and op.io["chunks"] > 1 and {k: op.io[k] for k in hs.BUFFERS} == hs.NO_IO
+        assert not op.want()[0].any() and not op.want()[1].any()
+    assert hs.centred("mult4", "cb", chunk_steps=3, none_kept=True).same(hs.centred("mult4", none_kept=True).want() + ([],), hs.centred("mult4", none_kept=True).want())
+    kinds = {(op.family, op.args["how"]): op.breaks_exact for _, op in new if not op.args.get("none_kept")}
+    assert kinds == {("band", "array"): True, ("band_dev", "dev"): False, ("band_resident", "array"): True, ("band_resident", "cb"): True, ("band_resident", "dev"): False,
+                     ("centred", "array"): True, ("centred_cb", "cb"): True, ("centred_dev", "dev"): False, ("centred_resident", "array"): False,
+                     ("centred_resident", "dev"): False}
+    # (the other forms, which no leg of this sequence holds)
+    a = ("mult4", "f4", 3, False)
+    assert hs.band("mult4", "cb").breaks_exact and hs.band("mult4", field="f4").breaks_exact and not hs.centred_resident(a, "cb").breaks_exact
+    # the non-breakers work on slabs larger than the rows' own: a buffer they had claimed would have had to grow
+    for _, op in new:
+        if not op.breaks_exact and op.needs is None:
+            assert np.prod(hs.SHAPES[op.key]) > np.prod(hs.SHAPES["odd"])
     for i in stale:
         b = ops[i - 1] if not ops[i - 1].args.get("stale") else ops[i - 2]
         if b.family == "anomalies_resident":
@@ -160,7 +313,7 @@ def test_exact_rows_sequence():
             assert [op.family for op in ops[:i] if op.family.startswith("lifecycle") and op.family != "lifecycle_exact"][-1] == "lifecycle_resident"
         else:
             assert b.family == "release_io" or b.io["io_in"] > 0                                # each other breaker writes a handle buffer
-    assert sum(1 for op in ops if "lifecycle_columns" in op.note) == 7
+    assert sum(1 for op in ops if "lifecycle_columns" in op.note) == 12
     # the climatology of the (larger) resident mean alone writes neither: the rows after it are asked for again and must be right
     c = fams.index("climatology_resident")
     assert ops[c].io == hs.NO_IO and not ops[c].drops and fams[c - 1] == "lifecycle_exact" and fams[c + 1] == "lifecycle_exact"
@@ -190,7 +343,13 @@ def test_seeded_generator_is_deterministic_and_covers_the_vocabulary():
             count[op.family] += 1
             keys.add(op.key)
             dtypes.add(op.args.get("dtype"))
-    assert min(count.values()) >= 2, sorted(count.items(), key=lambda kv: kv[1])[:5]
+    assert min(count.values()) >= 3, sorted(count.items(), key=lambda kv: kv[1])[:5]
+    # the eight families of band and centred are among them (with the 32 of before: 40)
+    assert len(hs.FAMILIES) == 40 and {f + g for f in ("band", "centred") for g in ("", "_cb", "_dev", "_resident")} <= set(hs.FAMILIES)
+    for q in seqs:
+        for op in q:
+            if op.family in ("centred", "centred_cb") and op.io["chunks"] > 1:
+                _a_chunk_without_kept_stamps(op, carrying=2)
     assert set(hs.SHAPES) <= keys and {"f4", "f8"} <= dtypes
     assert len({repr(q) for q in seqs}) == hs.N_SEEDS
 
@@ -201,7 +360,9 @@ def _one_of_each():
     return [hs.track(k), hs.track(k, "f8", per_step=True), hs.track_field(k), hs.track_segments(k), hs.track_stream(k), hs.track_dev(k), hs.track_resident(a),
             hs.frequency(k), hs.spells(k, segments=True), hs.composite(k), hs.composite_resident(a), hs.lifecycle(k), hs.lifecycle_stream(k),
             hs.lifecycle_resident(a), hs.level_mean(k), hs.anomalies(k), hs.anomalies(k, "f8", segments=True), hs.anomalies_stream(k),
-            hs.anomalies_resident(lv), hs.climatology(k), hs.climatology_resident(lv), hs.percentile(k), hs.percentile_resident(a), hs.percentile_groups(k), hs.percentile_field(k), hs.std_field(k)]
+            hs.anomalies_resident(lv), hs.climatology(k), hs.climatology_resident(lv), hs.percentile(k), hs.percentile_resident(a), hs.percentile_groups(k), hs.percentile_field(k), hs.std_field(k),
+            hs.band(k), hs.band(k, field="f8", columns=False), hs.band(k, field="f4", sectors=False), hs.band_resident(a), hs.centred(k), hs.centred(k, dtype="f8"),
+            hs.centred_resident(a)]
 
 
 def test_every_reference_runs_on_the_smallest_shape():
@@ -219,6 +380,32 @@ def test_every_reference_runs_on_the_smallest_shape():
     assert hs.frequency(hs.SMALLEST).want().max() > 1 and hs.spells(hs.SMALLEST).want()[2].max() > 2
     assert len(hs.lifecycle(hs.SMALLEST).want()[0]) > 20 and len(hs.lifecycle_resident((hs.SMALLEST, "f4", 3, False)).want()[0]) > 20
     assert np.isfinite(hs.anomalies(hs.SMALLEST).want()[0]).mean() > 0.8
+    # band: flagged pixels in the rows of the band, both sectors (one wraps), a field whose weighted sums are not all zero
+    bw = hs.band(hs.SMALLEST, field="f8").want()
+    assert sorted(bw) == ["area", "cnt", "sec_area", "sec_cnt", "sec_wx", "wx"] and bw["cnt"].max() > 1 and bw["sec_cnt"].min(axis=0).max() >= 0
+    assert (bw["sec_cnt"] > 0).any(axis=0).all() and np.count_nonzero(bw["wx"]) > 10
+    sects = hs.band_sectors(hs.SMALLEST)
+    assert sects[1][0] + sects[1][1] > nx and hs.band_rows(hs.SMALLEST) == (1, ny - 2)
+    assert hs.same_band(bw, bw) and not hs.same_band(dict(bw, wx=np.nextafter(bw["wx"], np.inf)), bw) and not hs.same_band({k: v for k, v in bw.items() if k != "wx"}, bw)
+    rb = hs.band_resident((hs.SMALLEST, "f4", 3, False)).want()
+    assert rb["cnt"].max() > 0 and np.isfinite(rb["wx"]).all()               # a flagged pixel of the resident slab is above 40: never a NaN
+    # centred: about 40 stamps, sorted, bins from -1, every bin filled; on the wide field another order or a split sum has other bits
+    t, row, col, bin = hs.stamps(hs.SMALLEST)
+    assert 35 <= len(t) <= 45 and np.all(np.diff(t) >= 0) and bin.min() == -1 and set(bin.tolist()) == {-1, 0, 1, 2} and hs.CENTRED == dict(nbins=3, hy=2, hx=3)
+    g0, g1 = hs.stamp_gap(hs.SMALLEST)
+    assert np.all(bin[(t >= g0) & (t < g1)] == -1) and np.any((t >= g0) & (t < g1))
+    x = hs.wide_field(hs.SMALLEST, "f8")
+    cw = hs.centred(hs.SMALLEST, dtype="f8").want()
+    assert cw[1].max() > 3 and hs.same_centred(cw, cw)
+    import centred_util
+    assert not hs.same_centred(centred_util.centred(x, t, row, col, bin, order="falling", **hs.CENTRED), cw)
+    assert not hs.same_centred(centred_util.centred(x, t, row, col, bin, slice=4, **hs.CENTRED), cw)
+    # the reader form also answers for the reader's calls: the carrying chunks, no other
+    op = hs.centred(hs.SMALLEST, "cb", chunk_steps=3)
+    c, pieces = hs.carrying_chunks(hs.SMALLEST, 3)
+    calls = [(k * c, min(c, T - k * c)) for k, _ in pieces]
+    w = op.want()
+    assert op.same((w[0], w[1], calls), w) and not op.same((w[0], w[1], calls + [(T - 1, 1)]), w) and not op.same((w[0], w[1], [(0, T)]), w)
     # the band mean's order: exact on integers, NaNs left out, NaN for none; another order gives other bits on wide values
     assert hs.band_mean(np.arange(3000.0)) == 1499.5 and hs.band_mean([np.nan, 2.0, np.nan, 4.0]) == 3.0 and np.isnan(hs.band_mean([np.nan]))
     wide = np.random.default_rng(0).standard_normal(5000) * 10.0 ** np.random.default_rng(1).uniform(-8, 8, 5000)
