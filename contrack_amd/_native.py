@@ -46,6 +46,8 @@ EXPORTS = [
     "ctk_anom_seg_f32", "ctk_anom_seg_f64", "ctk_anom_stream_f32", "ctk_anom_stream_f64", "ctk_anom_stream_cb", "ctk_debug_anom_form", "ctk_debug_anom_plan", "ctk_debug_set_anom", "ctk_debug_anom_launch",
     "ctk_level_mean_f32", "ctk_level_mean_f64", "ctk_level_mean_f32_dev", "ctk_level_mean_f64_dev", "ctk_level_mean_stream_f32", "ctk_level_mean_stream_f64",
     "ctk_level_mean_stream_cb", "ctk_resident_level_mean", "ctk_resident_level_mean_generation", "ctk_anom_seg_resident", "ctk_debug_level_plan", "ctk_debug_level_form", "ctk_debug_time_level_mean", "ctk_debug_set_level",
+    "ctk_reversal_f32", "ctk_reversal_f64", "ctk_reversal_f32_dev", "ctk_reversal_f64_dev", "ctk_reversal_stream_cb",
+    "ctk_debug_reversal_plan", "ctk_debug_set_reversal", "ctk_debug_reversal_form", "ctk_debug_time_reversal",
     "ctk_composite_f32_dev", "ctk_composite_f64_dev", "ctk_composite_f32", "ctk_composite_f64", "ctk_composite_cb",
     "ctk_debug_composite_plan", "ctk_debug_set_composite", "ctk_debug_composite_launch", "ctk_debug_time_composite",
     "ctk_centred_f32_dev", "ctk_centred_f64_dev", "ctk_centred_f32", "ctk_centred_f64", "ctk_centred_cb",
@@ -162,6 +164,14 @@ def level_plan(elem_bytes, nsel, npix, steps, aligned=True):
     v = np.zeros(7, dtype=np.int64)
     check(lib().ctk_debug_level_plan(int(elem_bytes), int(nsel), int(npix), int(steps), int(bool(aligned)), v.ctypes.data))
     return dict(vec=int(v[0]), vpt=int(v[1]), unroll=int(v[2]), bps=int(v[3]), blocks=int(v[4]), grid=int(v[5]), xcd=int(v[6]))
+
+
+def reversal_plan(elem_bytes, ny, nx, steps, aligned=True):
+    """ctk_debug_reversal_plan: what ctk_reversal_plan (csrc/ctk_forms.h) decides for a reversal launch, as a dict (vec 1 vector / 0
+    scalar form, vpt pixels per thread, bps workgroups per step, blocks, grid, xcd); no handle, no GPU"""
+    v = np.zeros(6, dtype=np.int64)
+    check(lib().ctk_debug_reversal_plan(int(elem_bytes), int(ny), int(nx), int(steps), int(bool(aligned)), v.ctypes.data))
+    return dict(vec=int(v[0]), vpt=int(v[1]), bps=int(v[2]), blocks=int(v[3]), grid=int(v[4]), xcd=int(v[5]))
 
 
 def composite_plan(elem_bytes, npix, unroll=-1):
@@ -367,6 +377,16 @@ def lib():
     L.ctk_debug_level_form.argtypes = [p, p]
     L.ctk_debug_set_level.argtypes = [p, i32, i64]
     L.ctk_debug_time_level_mean.argtypes = [p, p, i32, i64, i32, i32, i32, p, i32, p, i32, C.POINTER(dbl)]
+    rows7 = [p, p, p, p, p, p, p]                                    # eq, po, eq2, dE, tS, tN, tS2
+    for name in ("ctk_reversal_f32", "ctk_reversal_f64"):
+        getattr(L, name).argtypes = [p, p, i64, i32, i32] + rows7 + [i32, p, i64, i32]
+    for name in ("ctk_reversal_f32_dev", "ctk_reversal_f64_dev"):
+        getattr(L, name).argtypes = [p, p, i64, i32, i32] + rows7 + [i32, p]
+    L.ctk_reversal_stream_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p] + rows7 + [i32, WRITE_CHUNK_FN, p, i64, i32]
+    L.ctk_debug_reversal_plan.argtypes = [i32, i64, i64, i64, i32, p]
+    L.ctk_debug_set_reversal.argtypes = [p, i32, i64]
+    L.ctk_debug_reversal_form.argtypes = [p, p]
+    L.ctk_debug_time_reversal.argtypes = [p, p, i32, i64, i32, i32] + rows7 + [i32, p, i32, C.POINTER(dbl)]
     L.ctk_resident_anom.argtypes = [p, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.ctk_resident_anom_generation.argtypes = [p, C.POINTER(C.c_uint64)]
     L.ctk_track_resident.argtypes = [p, p, i32, p, dbl, i32, i32, p, C.POINTER(i64)]
@@ -460,6 +480,24 @@ def _level_weights(weights, nlev):
     if not np.any(w > 0):
         raise ValueError("all weights are zero: no level is selected")
     return w
+
+
+def _reversal_rows(rows, ny):
+    """the row table of a reversal call (a mapping with eq, po, dE, tS, tN and, for the third criterion, eq2 and tS2; see
+    contrack.reversal_rows / reversal_limits) as the seven pointer arguments of ctk_reversal_* and the arrays they point into"""
+    second = rows.get("eq2") is not None
+    if second != (rows.get("tS2") is not None):
+        raise ValueError("eq2 and tS2 go together (both or neither)")
+    keep = []
+    for key, dt in (("eq", np.int32), ("po", np.int32), ("eq2", np.int32), ("dE", np.float64), ("tS", np.float64), ("tN", np.float64), ("tS2", np.float64)):
+        if key in ("eq2", "tS2") and not second:
+            keep.append(None)
+            continue
+        a = np.ascontiguousarray(rows[key], dtype=dt)
+        if a.shape != (ny,):
+            raise ValueError("rows[%r] must hold one value per latitude row (%d), not shape %s" % (key, ny, a.shape))
+        keep.append(a)
+    return [_ptr(a) for a in keep], keep
 
 
 def _group_ids(group, T):
@@ -1641,6 +1679,89 @@ class Tracker:
         g = C.c_uint64(0)
         check(lib().ctk_resident_level_mean_generation(self._h, C.byref(g)))
         return int(g.value)
+
+    # ---- reversal of the meridional gradient (ctk_reversal_*) -----------------------------------------------------
+    def reversal(self, x, rows, mask=False, chunk_steps=0, keep_resident=False, want_out=True):
+        """x (steps, ny, nx) float32 / float64 (an array or np.memmap); rows: the row table (contrack.reversal_rows +
+        reversal_limits: eq, po, dE, tS, tN and, for the third criterion, eq2 and tS2).  Returns the (steps, ny, nx) index in x's
+        dtype (None without want_out): on active rows the equatorward gradient per degree where the pixel is blocked (mask: 1),
+        0 elsewhere (include/contrack_hip.h).  chunk_steps: steps per chunk on their way through the device (0: about 256 MB of
+        input); same bits.  keep_resident: the result stays in HBM as the field to track (track_resident)."""
+        if not isinstance(x, np.memmap):
+            x = np.ascontiguousarray(x)
+        if x.ndim != 3:
+            raise ValueError("x must be (steps, lat, lon)")
+        if x.dtype not in (np.float32, np.float64):
+            x = np.ascontiguousarray(x, dtype=np.float64)
+        if not x.flags.c_contiguous:
+            x = np.ascontiguousarray(x)
+        steps, ny, nx = x.shape
+        ptrs, _keep = _reversal_rows(rows, ny)
+        if not want_out and not keep_resident:
+            raise ValueError("want_out=False without keep_resident asks for nothing")
+        out = np.empty((steps, ny, nx), dtype=x.dtype) if want_out else None
+        fn = lib().ctk_reversal_f64 if x.dtype == np.float64 else lib().ctk_reversal_f32
+        check(fn(self._h, x.ctypes.data, steps, ny, nx, *ptrs, int(bool(mask)), _ptr(out), int(chunk_steps or 0), int(bool(keep_resident))))
+        return out
+
+    def reversal_cb(self, reader, shape, dtype, rows, mask=False, sink=None, chunk_steps=0, keep_resident=False):
+        """reversal with a reader(t0, nt, out) that fills `out`, a (nt, ny, nx) view of pinned memory, with the steps [t0, t0 + nt);
+        shape = (steps, ny, nx).  sink: None (a new array is returned), False (nothing leaves the device: keep_resident), a
+        C-contiguous (steps, ny, nx) array of `dtype`, or a writer(t0, nt, values).  Reader and writer see every step once, in
+        rising order."""
+        if shape is None or dtype is None:
+            raise ValueError("a reader needs shape=(steps, ny, nx) and dtype")
+        steps, ny, nx = (int(v) for v in shape)
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("the field must be float32 or float64")
+        ptrs, _keep = _reversal_rows(rows, ny)
+        out = None
+        if sink is None:
+            out = sink = np.empty((steps, ny, nx), dtype=dt)
+        elif sink is False:
+            sink = None
+            if not keep_resident:
+                raise ValueError("sink=False without keep_resident asks for nothing")
+        elif not callable(sink):
+            if sink.dtype != dt or sink.shape != (steps, ny, nx) or not sink.flags.c_contiguous:
+                raise ValueError("the sink array must be C-contiguous (steps, ny, nx) of the field's dtype")
+            out = sink
+        tr = _Trampolines()
+        rcb, wcb = tr.reader(reader, _float_ctype(dt), (ny, nx)), tr.writer(sink, _float_ctype(dt), (ny, nx))
+        tr.finish(lib().ctk_reversal_stream_cb(self._h, dt.itemsize, steps, ny, nx, rcb, None, *ptrs, int(bool(mask)), wcb, None, int(chunk_steps or 0),
+                                               int(bool(keep_resident))))
+        return out
+
+    def reversal_dev(self, x_dev, steps, ny, nx, rows, out_dev, mask=False, f64=False):
+        """ctk_reversal_*_dev: x and out (steps, ny, nx) in device memory"""
+        ptrs, _keep = _reversal_rows(rows, ny)
+        fn = lib().ctk_reversal_f64_dev if f64 else lib().ctk_reversal_f32_dev
+        check(fn(self._h, x_dev, int(steps), int(ny), int(nx), *ptrs, int(bool(mask)), out_dev))
+
+    def time_reversal(self, x_dev, steps, ny, nx, rows, out_dev, mask=False, f64=False, reps=5):
+        """measurement (tools/reversal_probe.py): (best, mean) ms of k_reversal alone on slabs in device memory, HIP events; rows
+        None: the plain copy kernel over the same two buffers, the yardstick"""
+        ptrs, _keep = ([None] * 7, None) if rows is None else _reversal_rows(rows, ny)
+        ms = (C.c_double * 2)()
+        check(lib().ctk_debug_time_reversal(self._h, x_dev, int(bool(f64)), int(steps), int(ny), int(nx), *ptrs, int(bool(mask)), out_dev, int(reps), ms))
+        return float(ms[0]), float(ms[1])
+
+    def debug_set_reversal(self, xcd=-1, grid_max=0):
+        """for the following reversal launches -- xcd: how workgroups map to XCDs (0 launch order, 1 one contiguous eighth per XCD,
+        n > 1 tiles of n; -1: the library's rule, ctk_reversal_plan); grid_max: a lower cap on the workgroups of a launch (0: the
+        rule's)"""
+        check(lib().ctk_debug_set_reversal(self._h, int(xcd), int(grid_max)))
+
+    def debug_reversal_form(self):
+        """the form of the last reversal launch: 1 vector (16 bytes per lane), 0 scalar, -1 none yet"""
+        return self.debug_reversal_launch()[0]
+
+    def debug_reversal_launch(self):
+        """(form, workgroups) of the last reversal launch"""
+        v = np.zeros(2, dtype=np.int64)
+        check(lib().ctk_debug_reversal_form(self._h, v.ctypes.data))
+        return int(v[0]), int(v[1])
 
     def anomalies_resident(self, group, ngroups, window=1, smooth=1, clim=None, segments=None, keep_resident=False, want_anom=True, want_clim=False):
         """anomalies(..., segments=...) of the resident vertical mean (ctk_anom_seg_resident): nothing crosses PCIe on the way in.

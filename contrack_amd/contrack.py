@@ -625,6 +625,105 @@ def level_mean_numpy(x, weights=None, levels=None, bounds=None, skipna=False, ch
     return _tracker(device).level_mean(x, w, skipna=skipna, chunk_steps=None if chunk_steps is None else int(chunk_steps))
 
 
+_HEMISPHERES = ('both', 'north', 'south')
+_REVERSAL_STATS = ('gradient', 'mask')
+
+
+def reversal_rows(lat, delta=15., lat_bounds=(30, 75), hemisphere='both', second=False):
+    """the partner rows of the gradient-reversal index on the latitude coordinate `lat` (degrees, rising or falling, regular or
+    not), as a dict of (ny,) arrays.  Per row j with s = +1 where lat[j] > 0, else -1 (poleward is +s):
+        eq[j]   the row nearest to lat[j] - s * delta        po[j]   the row nearest to lat[j] + s * delta
+        eq2[j]  the row nearest to lat[j] - 2 * s * delta    (second=True: the third criterion; else eq2 is None)
+    "nearest" accepts a row only if it lies closer to the target than half the largest row spacing; otherwise the row has no
+    partner (nor does a partner count that is the row itself: a delta below the spacing).  A row is ACTIVE if lat_bounds[0] <= |lat[j]| <= lat_bounds[1], its hemisphere is selected ('both', 'north': lat > 0,
+    'south': lat < 0) and every partner it needs exists; inactive rows have eq = po = eq2 = -1.  float64 per active row (0
+    elsewhere): dE = |lat[j] - lat[eq]|, dP = |lat[po] - lat[j]|, dE2 = |lat[eq] - lat[eq2]| -- the actual distances, not delta."""
+    lat = np.asarray(lat, dtype=np.float64)
+    if lat.ndim != 1 or lat.size < 1 or not np.all(np.isfinite(lat)):
+        raise ValueError("lat must be a 1-D coordinate of finite values")
+    if not (np.isfinite(delta) and delta > 0):
+        raise ValueError("delta must be a distance in degrees > 0, not {!r}".format(delta))
+    if hemisphere not in _HEMISPHERES:
+        raise ValueError("hemisphere={!r}: one of {}".format(hemisphere, _HEMISPHERES))
+    b = np.asarray(lat_bounds, dtype=np.float64).reshape(-1)
+    if b.size != 2 or not np.all(np.isfinite(b)) or b[0] > b[1] or b[0] < 0:
+        raise ValueError("lat_bounds must be (low, high) with 0 <= low <= high, in degrees of |latitude|")
+    ny = lat.size
+    half = np.abs(np.diff(lat)).max() / 2 if ny > 1 else 0.0
+
+    def nearest(v):
+        k = int(np.argmin(np.abs(lat - v)))
+        return k if abs(lat[k] - v) < half else -1
+    eq, po, eq2 = (np.full(ny, -1, dtype=np.int32) for _ in range(3))
+    dE, dP, dE2 = (np.zeros(ny, dtype=np.float64) for _ in range(3))
+    for j in range(ny):
+        phi = lat[j]
+        if not (b[0] <= abs(phi) <= b[1]) or (hemisphere == 'north' and not phi > 0) or (hemisphere == 'south' and not phi < 0):
+            continue
+        s = 1.0 if phi > 0 else -1.0
+        e, p = nearest(phi - s * delta), nearest(phi + s * delta)
+        e2 = nearest(phi - 2 * s * delta) if second else 0
+        if e < 0 or p < 0 or e2 < 0 or e == j or p == j or (second and e2 == e):
+            continue
+        eq[j], po[j] = e, p
+        dE[j], dP[j] = abs(lat[j] - lat[e]), abs(lat[p] - lat[j])
+        if second:
+            eq2[j], dE2[j] = e2, abs(lat[e] - lat[e2])
+    return dict(eq=eq, po=po, eq2=eq2 if second else None, dE=dE, dP=dP, dE2=dE2 if second else None)
+
+
+def reversal_limits(rows, ghgs=0., ghgn=-10., ghgs2=None):
+    """the row table of ctk_reversal_* from reversal_rows' partners and the gradient limits per degree: the limits pre-multiplied by
+    the row distances, tS = ghgs * dE, tN = ghgn * dP and (ghgs2 not None: Davini's third criterion, -5) tS2 = ghgs2 * dE2, so that
+    the compares of the kernel need no division"""
+    for name, v in (("ghgs", ghgs), ("ghgn", ghgn)) + ((("ghgs2", ghgs2),) if ghgs2 is not None else ()):
+        if not np.isfinite(v):
+            raise ValueError("{} must be finite, not {!r}".format(name, v))
+    if (ghgs2 is not None) != (rows.get("eq2") is not None):
+        raise ValueError("ghgs2 needs the rows of the third criterion: reversal_rows(..., second=True), and only then")
+    out = dict(eq=rows["eq"], po=rows["po"], eq2=rows["eq2"], dE=rows["dE"], tS=np.float64(ghgs) * rows["dE"], tN=np.float64(ghgn) * rows["dP"], tS2=None)
+    if ghgs2 is not None:
+        out["tS2"] = np.float64(ghgs2) * rows["dE2"]
+    return out
+
+
+def reversal_numpy(z, lat, delta=15., ghgs=0., ghgn=-10., ghgs2=None, lat_bounds=(30, 75), hemisphere='both', stat='gradient', chunk_steps=None,
+                   device=None, shape=None, dtype=None):
+    """the two-dimensional blocking index of the reversal of the meridional height gradient (Tibaldi & Molteni 1990; Scherrer et al.
+    2006; Davini et al. 2012) of a (steps, lat, lon) float field z -- geopotential height in metres, say -- on the GPU
+    (ctk_reversal_*).  Per pixel of an active row (reversal_rows), in float64:
+        dS = z[j] - z[eq] ;  dN = z[po] - z[j] ;  dS2 = z[eq] - z[eq2]
+        blocked = dS / dE > ghgs  and  dN / dP < ghgn  [and dS2 / dE2 < ghgs2]        (evaluated as dS > ghgs * dE ...: no division)
+    stat='gradient': dS / dE where blocked (units per degree), 0 elsewhere; stat='mask': 1 / 0.  Inactive rows are 0; a NaN in any of
+    the rows a pixel reads leaves it unblocked.  ghgs2=-5 is Davini's third criterion.  The result has z's shape and dtype (float32
+    kept, anything else float64): track_numpy(..., threshold=0, gorl='>') tracks it as it is.
+    z: an array or np.memmap, or -- with shape=(steps, ny, nx) and dtype -- a reader(t0, nt, out) that fills out (nt, ny, nx).
+    chunk_steps: steps per chunk on their way through the device (None / 0: about 256 MB of input); same bits.
+    The one-dimensional diagram of Tibaldi & Molteni is band_numpy / calc_hovmoller over a narrow latitude band of the mask."""
+    if stat not in _REVERSAL_STATS:
+        raise ValueError("stat={!r}: one of {}".format(stat, _REVERSAL_STATS))
+    if chunk_steps is not None and int(chunk_steps) < 0:
+        raise ValueError("chunk_steps must be >= 0")
+    rows = reversal_limits(reversal_rows(lat, delta, lat_bounds, hemisphere, ghgs2 is not None), ghgs, ghgn, ghgs2)
+    ny = len(rows["eq"])
+    if callable(z):
+        if shape is None or dtype is None or len(shape) != 3:
+            raise ValueError("a reader needs shape=(steps, ny, nx) and dtype")
+        if int(shape[1]) != ny:
+            raise ValueError("lat holds {} values, the field has {} rows".format(ny, shape[1]))
+        return _tracker(device).reversal_cb(z, shape, dtype, rows, mask=stat == 'mask', chunk_steps=chunk_steps or 0)
+    z = np.asarray(z) if not isinstance(z, np.memmap) else z
+    if z.ndim != 3:
+        raise ValueError("z must be (steps, lat, lon)")
+    if z.shape[1] != ny:
+        raise ValueError("lat holds {} values, the field has {} rows".format(ny, z.shape[1]))
+    if z.dtype.kind != "f":
+        if z.dtype.kind not in "iub":
+            raise TypeError("z must be a real numeric array")
+        z = z.astype(np.float64)
+    return _tracker(device).reversal(z, rows, mask=stat == 'mask', chunk_steps=chunk_steps or 0)
+
+
 def percentile_groups_numpy(anom, rows, group, q, window=1, device=None):
     """the threshold recipe of README.rst:235-240 on a (time, lat, lon) float slab: per group g (one id in [0, G) per timestep,
     G = max(group) + 1, any order in time) the q-quantile of rows[0] <= y < rows[1] pooled over every timestep whose group lies in
@@ -1243,6 +1342,88 @@ class contrack(object):
         return res[1] == _fingerprint(np.asarray(self.ds[variable].data)) and res[2] == trk.resident_level_mean_generation() and \
             trk.resident_level_mean() == (slab.shape[0], slab.shape[1], slab.shape[2], slab.dtype == np.float64)
 
+    # ---- reversal of the meridional height gradient: the second family of blocking indices --------------------------------
+    def _step_reader(self, da, dims, step_dims):
+        """reader(t0, nt, out) of flat steps [t0, t0 + nt) -- the step dims flattened in their own order --, read as isel(outer step
+        dims = index, innermost step dim = slice): out is (nt, ny, nx)"""
+        sizes = [da.shape[dims.index(d)] for d in step_dims]
+        inner, n_in = step_dims[-1], sizes[-1]
+        left = tuple(d for d in dims if d not in step_dims[:-1])
+        sort = [left.index(d) for d in (inner, self._latitude_name, self._longitude_name)]
+
+        def reader(t0, nt, out):
+            done = 0
+            while done < nt:
+                o, t = divmod(t0 + done, n_in)
+                n = min(nt - done, n_in - t)
+                sel = dict(zip(step_dims[:-1], (int(v) for v in np.unravel_index(o, sizes[:-1])))) if len(sizes) > 1 else {}
+                sel[inner] = slice(t, t + n)
+                out[done:done + n] = np.asarray(da.isel(**sel).data).transpose(sort)
+                done += n
+        return reader
+
+    def calc_reversal(self, variable, delta=15., ghgs=0., ghgn=-10., ghgs2=None, lat_bounds=(30, 75), hemisphere='both', stat='gradient', name='reversal',
+                      chunk_steps=None):
+        """adds the variable `name`: the two-dimensional blocking index of the reversal of the meridional gradient of `variable`
+        (geopotential height; Tibaldi & Molteni 1990, Scherrer et al. 2006, Davini et al. 2012), computed on the GPU
+        (reversal_numpy).  A grid point at latitude phi (lat_bounds[0] <= |phi| <= lat_bounds[1], in the selected hemisphere:
+        'both', 'north', 'south') is blocked where the gradient towards the equator over `delta` degrees exceeds ghgs and the
+        gradient towards the pole stays below ghgn (units per degree; the defaults 0 and -10 m / degree are Tibaldi & Molteni's);
+        ghgs2 (Davini's third criterion: -5) also asks the gradient between phi - delta and phi - 2 delta to stay below ghgs2.  The
+        rows nearest to phi -+ delta are taken and the gradients use their actual distance (reversal_rows).
+        stat='gradient': the equatorward gradient where blocked, 0 elsewhere (units `<units> / degree`); stat='mask': 1 / 0 (units 1).
+        run_contrack(variable=name, threshold=0, gorl='>', ...) then tracks the blocked regions: spatial coherence, overlap and
+        persistence are the tracker's.  Every dimension besides latitude and longitude (time, a member dimension ...) counts steps,
+        each on its own; any dim order is accepted and kept.
+        chunk_steps: the variable is read slice by slice (`isel` on the step dims) and passes through chunk-sized device buffers;
+        the host slab is never built.  Without it, for a (time, lat, lon) variable in any order, the result also stays in HBM and
+        a following run_contrack(variable=name) starts from there (its host twin is read-only, as calc_anom's).
+        Not here: the longitudinal-extent criterion; the one-dimensional diagram of Tibaldi & Molteni is
+        calc_hovmoller(flag, lat_bounds=<a narrow band>) of the tracked mask."""
+        self._ensure_set_up()
+        if stat not in _REVERSAL_STATS:
+            raise ValueError("stat={!r}: one of {}".format(stat, _REVERSAL_STATS))
+        if chunk_steps is not None and int(chunk_steps) < 0:
+            raise ValueError("chunk_steps must be >= 0")
+        da = self.ds[variable]
+        dims = tuple(da.dims)
+        for d in (self._latitude_name, self._longitude_name):
+            if d not in dims:
+                raise ValueError("the variable {!r} has no dimension {!r} (dims {})".format(variable, d, dims))
+        lat = np.asarray(self.ds[self._latitude_name].data)
+        rows = reversal_limits(reversal_rows(lat, delta, lat_bounds, hemisphere, ghgs2 is not None), ghgs, ghgn, ghgs2)
+        step_dims = tuple(d for d in dims if d not in (self._latitude_name, self._longitude_name))
+        ny, nx = da.shape[dims.index(self._latitude_name)], da.shape[dims.index(self._longitude_name)]
+        step_shape = tuple(da.shape[dims.index(d)] for d in step_dims)
+        steps = int(np.prod(step_shape)) if step_dims else 1
+        trk = _tracker()
+        resident = chunk_steps is None and step_dims == (self._time_name,)
+        logger.info('Calculating gradient reversal of {} on {} of {} rows...'.format(variable, int(np.count_nonzero(rows["eq"] >= 0)), ny))
+        if chunk_steps is not None and step_dims:
+            dtype = np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
+            res = trk.reversal_cb(self._step_reader(da, dims, step_dims), (steps, ny, nx), dtype, rows, mask=stat == 'mask', chunk_steps=int(chunk_steps))
+        else:
+            sort = [dims.index(d) for d in step_dims + (self._latitude_name, self._longitude_name)]
+            arr = np.asarray(da.data).transpose(sort).reshape((steps, ny, nx))
+            if arr.dtype.kind != "f":
+                arr = arr.astype(np.float64)
+            res = trk.reversal(arr, rows, mask=stat == 'mask', keep_resident=resident)
+        if resident:
+            res.flags.writeable = False                      # (its twin stays in HBM for run_contrack: see _fingerprint)
+        lead = step_dims + (self._latitude_name, self._longitude_name)
+        out = res.reshape(step_shape + (ny, nx)).transpose([lead.index(d) for d in dims])
+        units = da.attrs.get('units')
+        attrs = {'units': '1' if stat == 'mask' else '{} / degree'.format(units) if units else 'degree-1',
+                 'long_name': da.attrs.get('long_name', variable) + (' gradient reversal mask' if stat == 'mask' else ' reversed equatorward gradient'),
+                 'history': 'Calculated from {} with input attributes: delta = {}, ghgs = {}, ghgn = {}, ghgs2 = {}, lat_bounds = {}, hemisphere = {}, '
+                            'stat = {}.'.format(variable, delta, ghgs, ghgn, ghgs2, tuple(np.asarray(lat_bounds).tolist()), hemisphere, stat)}
+        self.ds[name] = (dims, out, attrs)
+        if resident:
+            # (the resident slot now holds this field: the record of calc_anom's slab, if any, is replaced with it)
+            self._anom_resident = (_fingerprint(np.asarray(self.ds[name].data)), trk.resident_generation())
+            self._anom_resident_name = name
+        logger.info('Calculating gradient reversal... DONE')
+
     # ---- climatology / anomaly (contrack.py:458-581) on the device: SURVEY.md section 8(f) row N2 ------------------------
     def _group_ids(self, groupby):
         """(ids per timestep in 0..G-1, the G group values in ascending order) for time.<groupby> (dayofyear, month, ...)"""
@@ -1373,7 +1554,7 @@ class contrack(object):
                                       'climatology = {}.']).format(variable, smooth, clim_txt)}
         if segments is not None or chunk_steps is not None:
             self.ds['anom'] = (tuple(da.dims), self._anom_segments(variable, ids, len(uniq), window, smooth, clim_arr, segments, chunk_steps, pool, attrs), attrs)
-            self._anom_resident = None
+            self._anom_resident, self._anom_resident_name = None, 'anom'
             logger.info('Calculating Anomaly... DONE')
             return
         if self._vmean_resident_for(variable, slab):         # (the mean calc_vertical_mean left in HBM: nothing to upload, same bits)
@@ -1386,6 +1567,7 @@ class contrack(object):
         # (fingerprint of the host twin, identity of the slab in HBM: another instance's calc_anom on the shared handle changes
         # the second and this instance's run_contrack goes back to its own host array)
         self._anom_resident = (_fingerprint(np.asarray(self.ds['anom'].data)), _tracker().resident_generation())
+        self._anom_resident_name = 'anom'
         logger.info('Calculating Anomaly... DONE')
 
     def _anom_segments(self, variable, ids, G, window, smooth, clim_arr, segments, chunk_steps, pool, attrs):
@@ -1417,10 +1599,12 @@ class contrack(object):
         sort = [dims.index(d) for d in (self._time_name, self._latitude_name, self._longitude_name)]
         return anom.transpose(np.argsort(sort))
 
-    def _resident_for(self, variable, arr, shape, is_f64):
-        """True if `variable` is this instance's anomaly and its twin is still the slab resident in HBM"""
+    def _resident_for(self, variable, arr, shape, is_f64, name='anom'):
+        """True if `variable` is the field to track this instance left in HBM -- `name`: 'anom' for every consumer of calc_anom's
+        slab; run_contrack passes the name the last producer recorded (calc_anom: 'anom', calc_reversal: its variable) -- and its
+        host twin is still the slab resident there"""
         res = getattr(self, "_anom_resident", None)
-        if variable != 'anom' or res is None or res[0] is None:
+        if variable != name or getattr(self, "_anom_resident_name", 'anom') != name or res is None or res[0] is None:
             return False
         trk = _tracker()
         return res[0] == _fingerprint(np.asarray(arr)) and res[1] == trk.resident_generation() and \
@@ -1786,8 +1970,8 @@ class contrack(object):
         else:
             slab = np.asarray(da.data).transpose(sort)
             thr, field = self._threshold_args(threshold, da.shape, sort, slab.shape[0], slab.dtype)
-            if self._resident_for(variable, da.data, slab.shape, slab.dtype != np.float32):
-                # calc_anom left this very slab in HBM: no host-to-device copy
+            if self._resident_for(variable, da.data, slab.shape, slab.dtype != np.float32, name=getattr(self, "_anom_resident_name", 'anom')):
+                # calc_anom (or calc_reversal) left this very slab in HBM: no host-to-device copy
                 call = lambda t: trk.track_resident(t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided)
             elif slab.dtype == np.float32:
                 call = lambda t: trk.track(np.ascontiguousarray(slab), t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided)

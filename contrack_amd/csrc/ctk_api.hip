@@ -290,6 +290,12 @@ struct ctk_handle {
     int lv_form = -1;                              // form of the last k_level_mean launch (1 vector, 0 scalar; -1: none yet)
     int lv_xcd_dbg = -1;                           // ctk_debug_set_level: xcd_chunk mode of the launches (-1: ctk_level_plan's)
     int64_t lv_grid_dbg = 0, lv_grid = 0;          // ... a lower cap on the workgroups of a launch (0: none); workgroups of the last launch
+    // reversal of the meridional gradient (ctk_reversal.hip): the row table of the running call (four float64 and three int32 per row);
+    // the form of the last k_reversal launch (1 vector, 0 scalar; -1: none yet) and its workgroups; ctk_debug_set_reversal's xcd_chunk
+    // mode (-1: ctk_reversal_plan's) and lower cap on the workgroups of a launch (0: none)
+    DevBuf gr_tab;
+    int gr_form = -1, gr_xcd_dbg = -1;
+    int64_t gr_grid = 0, gr_grid_dbg = 0;
     DevBuf io_in, io_out;                          // device copies of host-array calls (ctk_track_f32 / _f64)
     uint64_t io_gen = 0;                           // bumped by claim_io and ctk_release_io: WHOSE data io_in / io_out hold
     // streaming entries (ctk_track_stream_*): the slab passes through two chunk-sized device buffers per direction
@@ -3402,7 +3408,7 @@ extern "C" int ctk_release_io(ctk_handle *h)
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
     HIPCHK(hipSetDevice(h->device));
-    for (DevBuf *b : {&h->io_in, &h->io_out, &h->an_out, &h->an_raw, &h->lv_out}) b->release();
+    for (DevBuf *b : {&h->io_in, &h->io_out, &h->an_out, &h->an_raw, &h->lv_out, &h->gr_tab}) b->release();
     h->an_T = -1; h->an_gen++; h->an_pct_n = -1;
     h->lv_T = -1; h->lv_gen++;
     h->io_gen++; h->lc_flag = nullptr; h->lc_field = nullptr;          // (the exact rows of a lifecycle call read those slabs)
@@ -3876,6 +3882,7 @@ extern "C" int ctk_lifecycle_rows(ctk_handle *h, ctk_life_row *rows, int64_t cap
 #include "ctk_pfield.hip"
 #include "ctk_std.hip"
 #include "ctk_level.hip"
+#include "ctk_reversal.hip"
 #include "ctk_composite.hip"
 #include "ctk_centred.hip"
 #include "ctk_band.hip"

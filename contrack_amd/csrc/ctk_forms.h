@@ -644,6 +644,52 @@ inline int64_t ctk_level_runs(const double *w, int64_t nlev, CtkLevelRun *runs, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// reversal of the meridional gradient (ctk_reversal.hip): k_reversal, a stencil in latitude -- one thread per 16 bytes of adjacent
+// longitudes of one row of one step (vector form: every ROW starts on a 16-byte boundary, so a lane never straddles two rows) or per
+// pixel (scalar form: an odd row length, an offset pointer).  A workgroup stays inside one step, as k_level_mean's does.  A row is
+// read by its own lanes and by those of up to three other rows of the same plane, 0.26 MB at 1 degree and 4 MB at a quarter degree:
+// from CTK_LEVEL_XCD_MIN workgroups on every XCD takes one contiguous eighth of the launch (xcd_chunk), so the rows of a plane meet
+// in ONE L2 instead of eight (profiles/NOTES.md, "k_reversal").
+// ------------------------------------------------------------------------------------------------
+#define CTK_REVERSAL_THREADS 256
+struct CtkReversalPlan {
+    int vec;                      // 1: 16-byte loads and a 16-byte store per lane, 0: the scalar form
+    int vpt;                      // pixels per thread: 16 / elem_bytes, or 1
+    int64_t bps;                  // workgroups per step
+    int64_t blocks;               // bps * steps: (step, part of the plane) pairs, walked by ...
+    unsigned grid;                // ... this many workgroups (CTK_LEVEL_GRID_MAX at most: a launch stays below 2^32 work-items)
+    int xcd;                      // xcd_chunk mode of the launch: 1 one contiguous eighth of the workgroups per XCD, 0 launch order
+};
+// `aligned`: the input and output base pointers are multiples of 16; grid_max: CTK_LEVEL_GRID_MAX, or a test's lower cap
+inline CtkReversalPlan ctk_reversal_plan(int elem_bytes, int64_t ny, int64_t nx, int64_t steps, bool aligned, int64_t grid_max = CTK_LEVEL_GRID_MAX)
+{
+    CtkReversalPlan p = {};
+    p.vec = aligned && (nx * elem_bytes) % 16 == 0;
+    p.vpt = p.vec ? 16 / elem_bytes : 1;
+    const int64_t lanes = ny * (nx / p.vpt);                                      // (vector form: nx is a multiple of vpt)
+    p.bps = (lanes + CTK_REVERSAL_THREADS - 1) / CTK_REVERSAL_THREADS;
+    p.blocks = p.bps * steps;
+    p.grid = (unsigned)std::min<int64_t>(p.blocks, std::min<int64_t>(std::max<int64_t>(grid_max, 1), CTK_LEVEL_GRID_MAX));
+    p.xcd = p.grid >= CTK_LEVEL_XCD_MIN ? 1 : 0;
+    return p;
+}
+// rows [r0, r1) that some active row reads (itself and its partners) and rows [a0, a1) spanned by the active rows: what a host-array
+// call uploads and downloads of every plane.  eq2 may be null.  No active row: all four are 0.
+struct CtkReversalRows { int r0, r1, a0, a1; };
+inline CtkReversalRows ctk_reversal_rows(const int32_t *eq, const int32_t *po, const int32_t *eq2, int ny)
+{
+    CtkReversalRows r = {ny, 0, ny, 0};
+    for (int j = 0; j < ny; j++) {
+        if (eq[j] < 0) continue;
+        r.a0 = std::min(r.a0, j); r.a1 = std::max(r.a1, j + 1);
+        const int rows[4] = {j, (int)eq[j], (int)po[j], eq2 ? (int)eq2[j] : j};
+        for (int k = 0; k < 4; k++) { r.r0 = std::min(r.r0, rows[k]); r.r1 = std::max(r.r1, rows[k] + 1); }
+    }
+    if (r.a1 == 0) r = {0, 0, 0, 0};
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------------
 // rules every streamed entry shares
 // ------------------------------------------------------------------------------------------------
 // steps per chunk: chunk_steps, or (0) about 256 MB of input -- step_bytes is what one step brings in, a plane or the selected levels of

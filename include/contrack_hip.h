@@ -494,7 +494,9 @@ int ctk_anom_stream_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 *
                        const int32_t *group, int ngroups, int window, int smooth, const int64_t *starts, int64_t nseg, const void *clim_in,
                        void *clim_out, ctk_write_values_fn writer, void *writer_user, int64_t chunk_steps);
 int ctk_resident_anom(ctk_handle *h, int64_t *T, int *ny, int *nx, int *is_f64);       /* T = -1: nothing resident */
-/* identity of the resident slab: changes whenever a ctk_anom_* call writes anomalies or ctk_release_io drops them.  Remember it
+/* The resident slot holds THE FIELD TO TRACK, whichever producer wrote it last: the anomalies of ctk_anom_* or the gradient-reversal
+ * index of ctk_reversal_* (below), each with keep_resident.  ctk_resident_anom reports its shape.
+ * Identity of the resident slab: changes whenever one of those calls writes the slot or ctk_release_io drops it.  Remember it
  * after the call that left YOUR slab resident and use the slab only while it is unchanged. */
 int ctk_resident_anom_generation(ctk_handle *h, uint64_t *generation);
 /* ctk_track_f32 / _f64 on the resident anomaly slab (flag: host int32 (T, ny, nx)) */
@@ -606,6 +608,55 @@ int ctk_resident_level_mean_generation(ctk_handle *h, uint64_t *generation);
  * that dtype; the same kernels, the same bits, the same keep_resident (of the ANOMALY).  CTK_E_INVALID if no mean is resident. */
 int ctk_anom_seg_resident(ctk_handle *h, const int32_t *group, int ngroups, int window, int smooth, const void *clim_in, void *anom_out, void *clim_out,
                           int keep_resident, const int64_t *starts, int64_t nseg);
+
+/* ---- the reversal of the meridional height gradient: the second family of blocking indices -------------------------------------
+ * Tibaldi & Molteni (1990) in one dimension, Scherrer et al. (2006) and Davini et al. (2012) in two.  The reference has no function
+ * for it; tests/reversal_util.py is the numpy statement of what follows.
+ * x: (steps, ny, nx), float32 or float64, C-contiguous -- geopotential height in metres, say.  The caller describes the latitude
+ * coordinate with a ROW TABLE of ny entries (contrack.reversal_rows builds it from lat[ny], a distance delta in degrees and the
+ * gradient limits ghgs, ghgn, ghgs2 per degree):
+ *     eq[j]   the row nearest to lat[j] - s * delta (s = +1 north of the equator, -1 south of it and on it): the equatorward partner;
+ *             -1: row j is INACTIVE (outside the latitude band or the hemisphere asked for, or a partner is missing)
+ *     po[j]   the row nearest to lat[j] + s * delta: the poleward partner
+ *     eq2[j]  the row nearest to lat[j] - 2 * s * delta (the third criterion of Davini et al.; eq2 and tS2 NULL: two criteria)
+ *     dE[j] = |lat[j] - lat[eq[j]]| in degrees, the ACTUAL distance of the two rows, finite and > 0
+ *     tS[j] = ghgs * dE[j],  tN[j] = ghgn * |lat[po[j]] - lat[j]|,  tS2[j] = ghgs2 * |lat[eq[j]] - lat[eq2[j]]|: the limits, finite
+ * Per step and pixel of an active row, in float64 with no fused multiply-add (z[r] the pixel's column in row r):
+ *     dS = (double)z[j] - (double)z[eq[j]] ;  dN = (double)z[po[j]] - (double)z[j] ;  dS2 = (double)z[eq[j]] - (double)z[eq2[j]]
+ *     blocked = dS > tS[j]  and  dN < tN[j]  [and dS2 < tS2[j]]          -- a NaN anywhere: every compare false, not blocked
+ *     mask == 0 ('gradient'): out = blocked ? (dtype)(dS / dE[j]) : 0    -- the equatorward gradient per degree, one rounding
+ *     mask != 0:              out = blocked ? 1 : 0
+ * The compares use no division; the divide happens only where a pixel is blocked.  Inactive rows are 0 and nothing of x is read for
+ * them.  out has x's shape and dtype: ctk_track_* with threshold 0 and the op '>' tracks it as it is.
+ * CTK_E_INVALID with a message, the handle usable: a null pointer, a size below 1, steps < 1, a partner index outside [-1, ny), an
+ * active row with a negative partner, a dE that is not finite and > 0, a limit that is not finite (both on active rows), eq2 without
+ * tS2 or the reverse, a plane of 2^31 pixels or more, chunk_steps < 0, nothing to produce (out NULL and keep_resident 0).
+ *
+ * ctk_reversal_f32_dev / _f64_dev: x and out in device memory.
+ * ctk_reversal_f32 / _f64: host arrays (out may be NULL with keep_resident).  Of every plane only the rows some active row reads
+ * are uploaded (one strided copy per chunk) and only the rows the active rows span are downloaded; the rest of out is zeroed on the
+ * host.  Two input and two output chunks: chunk k + 1 travels in while the kernel works on chunk k and chunk k - 1 leaves.
+ * chunk_steps = 0: about 256 MB of input per chunk.  Same bits for every chunk_steps.
+ * ctk_reversal_stream_cb: the reader fills whole planes (nt, ny, nx) for the steps [t0, t0 + nt), the writer (may be NULL with
+ * keep_resident) receives whole planes in pinned memory valid during the call; both are called in increasing t0, once per chunk; a
+ * non-zero return ends the call with CTK_E_INVALID and leaves nothing in flight.
+ * keep_resident != 0: the full-plane result stays in HBM in the resident slot of THE FIELD TO TRACK -- the slot ctk_anom_* with
+ * keep_resident fills, whichever producer wrote it last.  ctk_track_resident, ctk_percentile_* with x = NULL and the `resident`
+ * consumers run on it unchanged; ctk_resident_anom reports its shape, ctk_resident_anom_generation a new identity.  A failing call
+ * leaves an earlier resident slab alone (argument errors) or dropped, never half written and reported. */
+int ctk_reversal_f32(ctk_handle *h, const float *x, int64_t steps, int ny, int nx, const int32_t *eq, const int32_t *po, const int32_t *eq2 /* or NULL */,
+                     const double *dE, const double *tS, const double *tN, const double *tS2 /* or NULL */, int mask, float *out /* or NULL */,
+                     int64_t chunk_steps, int keep_resident);
+int ctk_reversal_f64(ctk_handle *h, const double *x, int64_t steps, int ny, int nx, const int32_t *eq, const int32_t *po, const int32_t *eq2 /* or NULL */,
+                     const double *dE, const double *tS, const double *tN, const double *tS2 /* or NULL */, int mask, double *out /* or NULL */,
+                     int64_t chunk_steps, int keep_resident);
+int ctk_reversal_f32_dev(ctk_handle *h, const float *x_dev, int64_t steps, int ny, int nx, const int32_t *eq, const int32_t *po, const int32_t *eq2 /* or NULL */,
+                         const double *dE, const double *tS, const double *tN, const double *tS2 /* or NULL */, int mask, float *out_dev);
+int ctk_reversal_f64_dev(ctk_handle *h, const double *x_dev, int64_t steps, int ny, int nx, const int32_t *eq, const int32_t *po, const int32_t *eq2 /* or NULL */,
+                         const double *dE, const double *tS, const double *tN, const double *tS2 /* or NULL */, int mask, double *out_dev);
+int ctk_reversal_stream_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, int64_t steps, int ny, int nx, ctk_read_chunk_fn reader, void *reader_user,
+                           const int32_t *eq, const int32_t *po, const int32_t *eq2 /* or NULL */, const double *dE, const double *tS, const double *tN,
+                           const double *tS2 /* or NULL */, int mask, ctk_write_values_fn writer, void *writer_user, int64_t chunk_steps, int keep_resident);
 
 /* ---- the blocking-frequency climatology of the reference's tutorial (README.rst:159-160) ---------------------------------------
  *   xr.where(block['flag'] > 1, 1, 0).sum(dim='time') / block.ntime * 100     -- on the int32 flag slab (T, ny, nx), per group:

@@ -273,6 +273,22 @@ int ctk_debug_level_form(ctk_handle *h, int64_t *out2);
 int ctk_debug_time_level_mean(ctk_handle *h, const void *x_dev, int is_f64, int64_t steps, int nlev, int ny, int nx, const double *weights, int skipna,
                               void *out_dev, int reps, double *ms2);
 
+/* what ctk_reversal_plan (csrc/ctk_forms.h) decides for a ctk_reversal_* launch over `steps` steps of planes of ny rows of nx pixels
+ * of elem_bytes (4 / 8), `aligned`: both base pointers are multiples of 16.  out6 = { 1 the vector form (16 bytes per lane; every row
+ * starts on a 16-byte boundary) / 0 the scalar form, pixels per thread, workgroups per step, workgroups of work (per step x steps),
+ * workgroups launched (at most 2^24 - 1; the kernel strides over the rest), 1 if every XCD takes one contiguous eighth of them (0:
+ * launch order) }.  Host only: no handle, no GPU. */
+int ctk_debug_reversal_plan(int elem_bytes, int64_t ny, int64_t nx, int64_t steps, int aligned, int64_t *out6);
+/* test hook / experiments for the following k_reversal launches on this handle: as ctk_debug_set_level */
+int ctk_debug_set_reversal(ctk_handle *h, int xcd_mode, int64_t grid_max);
+/* test hook: out2 = { the form of the last k_reversal launch on this handle (1 vector, 0 scalar, -1 none yet), its workgroups } */
+int ctk_debug_reversal_form(ctk_handle *h, int64_t *out2);
+/* measurement (tools/reversal_probe.py): k_reversal alone on slabs in device memory (the arguments of ctk_reversal_*_dev; is_f64 != 0:
+ * float64) between HIP events: one launch that is not counted, then `reps` timed ones; ms2 = { best, mean }.  eq == NULL: a plain
+ * copy kernel (one 16-byte load and one 16-byte store per lane) over the same two buffers instead, the yardstick. */
+int ctk_debug_time_reversal(ctk_handle *h, const void *x_dev, int is_f64, int64_t steps, int ny, int nx, const int32_t *eq, const int32_t *po, const int32_t *eq2,
+                            const double *dE, const double *tS, const double *tN, const double *tS2, int mask, void *out_dev, int reps, double *ms2);
+
 /* what ctk_composite_plan (csrc/ctk_forms.h) decides for a k_composite launch over planes of npix pixels and a field of elem_bytes
  * (4 / 8); unroll: what ctk_debug_set_composite would force (-1: the rule).  out3 = { the widest batch of time steps in flight,
  * workgroups of work (256 pixels each), workgroups launched (at most 2^24 - 1; the kernel strides over the rest) }.  Host only: no
