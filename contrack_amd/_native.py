@@ -729,6 +729,38 @@ def _float_ctype(dt):
     return C.c_float if dt == np.float32 else C.c_double
 
 
+def _float_array(x, rank, wrong_rank):
+    """x as a C-contiguous float32 / float64 array of `rank` dimensions: an np.memmap stays one, another dtype becomes float64;
+    wrong_rank: the ValueError's text"""
+    if not isinstance(x, np.memmap):
+        x = np.ascontiguousarray(x)
+    if x.ndim != rank:
+        raise ValueError(wrong_rank)
+    if x.dtype not in (np.float32, np.float64):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+    if not x.flags.c_contiguous:
+        x = np.ascontiguousarray(x)
+    return x
+
+
+def _value_sink(sink, shape, dt, steps, what, instead, has_instead):
+    """The `sink` of a streamed producer (level_mean_cb, reversal_cb, anomalies_stream): None (a new array), False (nothing, if the
+    call yields `instead`), a C-contiguous array of `shape` and `dt`, or a writer(t0, nt, values).  Returns (the array the call
+    returns or None, what the library writes to or None); steps / what / instead: the words of the ValueError texts."""
+    if sink is None:
+        out = np.empty(shape, dtype=dt)
+        return out, out
+    if sink is False:
+        if not has_instead:
+            raise ValueError("sink=False without %s asks for nothing" % instead)
+        return None, None
+    if callable(sink):
+        return None, sink
+    if sink.dtype != dt or sink.shape != tuple(shape) or not sink.flags.c_contiguous:
+        raise ValueError("the sink array must be C-contiguous (%s, ny, nx) of the %s's dtype" % (steps, what))
+    return sink, sink
+
+
 def _flag_i32(flag, wider_hint):
     """the flag slab of an array entry as C-contiguous int32 (time, lat, lon); narrower integers are widened, wider ones are
     refused: `wider_hint` names the entries that take them"""
@@ -1544,11 +1576,7 @@ class Tracker:
             T, ny, nx = (int(v) for v in shape)
             dt = np.dtype(dtype)
         else:
-            source = np.ascontiguousarray(source) if not isinstance(source, np.memmap) else source
-            if source.dtype not in (np.float32, np.float64):
-                source = np.ascontiguousarray(source, dtype=np.float64)
-            if source.ndim != 3:
-                raise ValueError("the slab must be (time, lat, lon)")
+            source = _float_array(source, 3, "the slab must be (time, lat, lon)")
             T, ny, nx = source.shape
             dt = source.dtype
         if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
@@ -1558,17 +1586,7 @@ class Tracker:
         if cin is not None and cin.shape != (ngroups, ny, nx):
             raise ValueError("clim must have shape (ngroups, ny, nx)")
         cout = np.empty((ngroups, ny, nx), dtype=dt) if want_clim else None
-        out = None
-        if sink is None:
-            out = sink = np.empty((T, ny, nx), dtype=dt)
-        elif sink is False:
-            sink = None
-            if cout is None:
-                raise ValueError("sink=False without want_clim asks for nothing")
-        elif not callable(sink):
-            if sink.dtype != dt or sink.shape != (T, ny, nx) or not sink.flags.c_contiguous:
-                raise ValueError("the sink array must be C-contiguous (T, ny, nx) of the slab's dtype")
-            out = sink
+        out, sink = _value_sink(sink, (T, ny, nx), dt, "T", "slab", "want_clim", cout is not None)
         st = _seg_starts(segments if segments is not None else [])
         mid = (group.ctypes.data, int(ngroups), int(window), int(smooth), st.ctypes.data if st.size else None, st.shape[0], _ptr(cin))
         if not callable(source) and not callable(sink):
@@ -1587,14 +1605,7 @@ class Tracker:
         sum of w[l] * x[:, l] over the selected levels in rising l / sum of those w[l], in float64 (include/contrack_hip.h).
         skipna: a NaN level of a pixel leaves both sums.  chunk_steps: steps per chunk on their way through the device (None:
         ctk_level_mean_*, 0: about 256 MB of input); same bits.  keep_resident: the mean stays in HBM for anomalies_resident."""
-        if not isinstance(x, np.memmap):
-            x = np.ascontiguousarray(x)
-        if x.ndim != 4:
-            raise ValueError("x must be (steps, level, lat, lon)")
-        if x.dtype not in (np.float32, np.float64):
-            x = np.ascontiguousarray(x, dtype=np.float64)
-        if not x.flags.c_contiguous:
-            x = np.ascontiguousarray(x)
+        x = _float_array(x, 4, "x must be (steps, level, lat, lon)")
         steps, nlev, ny, nx = x.shape
         w = _level_weights(weights, nlev)
         if not want_out and not keep_resident:
@@ -1622,17 +1633,7 @@ class Tracker:
         w = _level_weights(weights_sel, nsel)
         if np.any(w == 0):
             raise ValueError("a reader delivers the selected levels only: every weight must be > 0")
-        out = None
-        if sink is None:
-            out = sink = np.empty((steps, ny, nx), dtype=dt)
-        elif sink is False:
-            sink = None
-            if not keep_resident:
-                raise ValueError("sink=False without keep_resident asks for nothing")
-        elif not callable(sink):
-            if sink.dtype != dt or sink.shape != (steps, ny, nx) or not sink.flags.c_contiguous:
-                raise ValueError("the sink array must be C-contiguous (steps, ny, nx) of the field's dtype")
-            out = sink
+        out, sink = _value_sink(sink, (steps, ny, nx), dt, "steps", "field", "keep_resident", keep_resident)
         tr = _Trampolines()
         rcb, wcb = tr.reader(reader, _float_ctype(dt), (nsel, ny, nx)), tr.writer(sink, _float_ctype(dt), (ny, nx))
         tr.finish(lib().ctk_level_mean_stream_cb(self._h, dt.itemsize, steps, nsel, ny, nx, rcb, None, w.ctypes.data, int(bool(skipna)), wcb, None,
@@ -1687,14 +1688,7 @@ class Tracker:
         dtype (None without want_out): on active rows the equatorward gradient per degree where the pixel is blocked (mask: 1),
         0 elsewhere (include/contrack_hip.h).  chunk_steps: steps per chunk on their way through the device (0: about 256 MB of
         input); same bits.  keep_resident: the result stays in HBM as the field to track (track_resident)."""
-        if not isinstance(x, np.memmap):
-            x = np.ascontiguousarray(x)
-        if x.ndim != 3:
-            raise ValueError("x must be (steps, lat, lon)")
-        if x.dtype not in (np.float32, np.float64):
-            x = np.ascontiguousarray(x, dtype=np.float64)
-        if not x.flags.c_contiguous:
-            x = np.ascontiguousarray(x)
+        x = _float_array(x, 3, "x must be (steps, lat, lon)")
         steps, ny, nx = x.shape
         ptrs, _keep = _reversal_rows(rows, ny)
         if not want_out and not keep_resident:
@@ -1716,17 +1710,7 @@ class Tracker:
         if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise ValueError("the field must be float32 or float64")
         ptrs, _keep = _reversal_rows(rows, ny)
-        out = None
-        if sink is None:
-            out = sink = np.empty((steps, ny, nx), dtype=dt)
-        elif sink is False:
-            sink = None
-            if not keep_resident:
-                raise ValueError("sink=False without keep_resident asks for nothing")
-        elif not callable(sink):
-            if sink.dtype != dt or sink.shape != (steps, ny, nx) or not sink.flags.c_contiguous:
-                raise ValueError("the sink array must be C-contiguous (steps, ny, nx) of the field's dtype")
-            out = sink
+        out, sink = _value_sink(sink, (steps, ny, nx), dt, "steps", "field", "keep_resident", keep_resident)
         tr = _Trampolines()
         rcb, wcb = tr.reader(reader, _float_ctype(dt), (ny, nx)), tr.writer(sink, _float_ctype(dt), (ny, nx))
         tr.finish(lib().ctk_reversal_stream_cb(self._h, dt.itemsize, steps, ny, nx, rcb, None, *ptrs, int(bool(mask)), wcb, None, int(chunk_steps or 0),

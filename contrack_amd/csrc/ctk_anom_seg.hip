@@ -272,80 +272,6 @@ extern "C" int ctk_debug_anom_launch(ctk_handle *h, int64_t *out8)
 }
 
 // ---- streamed ------------------------------------------------------------------------------------------------------------------
-// pass 2: the chunks pass through two windows [smooth - 1 steps kept from the chunk before | chunk] in io_in and two output buffers in
-// io_out; chunk k + 1 travels while the kernel works on chunk k and chunk k - 1 leaves
-template <typename VT>
-static int anom_stream_pass2(ctk_handle *h, StreamIO &io, int64_t T, int64_t npix, int smooth, const int32_t *group_dev, const uint8_t *valid_dev, const char *name)
-{
-    const size_t plane = (size_t)npix * sizeof(VT);
-    const int64_t chunk = io.chunk, halo = smooth - 1, fwd = (smooth - 1) / 2;
-    const size_t wbytes = (size_t)(chunk + halo) * plane, obytes = (size_t)(chunk + smooth) * plane;
-    const double t_pass = now_ms();
-    io.passes_in++;
-    if (io.host_out_v && !h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
-    struct Pending { int64_t t0 = -1, nt = 0; int b = 0; } pend;
-    auto drain = [&](const Pending &q) -> int {                                  // output chunk q leaves the device
-        if (q.t0 < 0) return CTK_OK;
-        const double d0 = now_ms();
-        char *dev = (char *)h->io_out.p + (size_t)q.b * obytes;
-        HIPCHK(hipEventSynchronize(h->ev_rel[q.b]));
-        if (io.write_v) {
-            HIPCHK(hipMemcpyAsync(h->pin_out[q.b], dev, (size_t)q.nt * plane, hipMemcpyDeviceToHost, h->side[0]));
-            HIPCHK(hipEventRecord(h->ev_d2h[q.b], h->side[0]));
-            HIPCHK(hipEventSynchronize(h->ev_d2h[q.b]));
-            const double w0 = now_ms();
-            const int rc = io.write_v(io.write_user, q.t0, q.nt, h->pin_out[q.b]);
-            io.ms_write += now_ms() - w0;
-            if (rc) return ctk_set_error(CTK_E_INVALID, "%s: the writer returned %d for timesteps [%lld, %lld)", name, rc, (long long)q.t0, (long long)(q.t0 + q.nt));
-        } else {
-            char *dst = (char *)io.host_out_v + (size_t)q.t0 * plane;
-            if (!h->bounce || !bounce_copy(*h->bounce, h->device, dev, dst, (size_t)q.nt * plane, false))
-                HIPCHK(hipMemcpy(dst, dev, (size_t)q.nt * plane, hipMemcpyDeviceToHost));
-        }
-        io.ms_out += now_ms() - d0;
-        return CTK_OK;
-    };
-    int64_t o_done = 0;
-    int k = 0;
-    for (int64_t c0 = 0; c0 < T; c0 += chunk, k++) {
-        const int b = k & 1;
-        const int64_t nt = std::min<int64_t>(chunk, T - c0);
-        const bool last = c0 + nt == T;
-        char *win = (char *)h->io_in.p + (size_t)b * wbytes, *body = win + (size_t)halo * plane;
-        if (k >= 2) HIPCHK(hipEventSynchronize(h->ev_thr[b]));                 // the window (and its pinned twin) is free again
-        if (io.read) {
-            const double r0 = now_ms();
-            const int rc = io.read(io.read_user, c0, nt, h->pin_in[b]);
-            io.ms_read += now_ms() - r0;
-            if (rc) return ctk_set_error(CTK_E_INVALID, "%s: the reader returned %d for timesteps [%lld, %lld)", name, rc, (long long)c0, (long long)(c0 + nt));
-            HIPCHK(hipMemcpyAsync(body, h->pin_in[b], (size_t)nt * plane, hipMemcpyHostToDevice, h->copy_stream));
-        } else {
-            HIPCHK(hipMemcpyAsync(body, (const char *)io.host_in + (size_t)c0 * plane, (size_t)nt * plane, hipMemcpyHostToDevice, h->copy_stream));
-        }
-        HIPCHK(hipEventRecord(h->ev_h2d[b], h->copy_stream));
-        HIPCHK(hipStreamWaitEvent(h->stream, h->ev_h2d[b], 0));
-        // steps [c0 - halo, c0 + nt) are in the window now (the first chunk has nothing in front of it): the outputs whose window ends
-        // inside them, and everything that is left once the last chunk is there
-        const int64_t xlo = k == 0 ? 0 : c0 - halo, o0 = o_done, o1 = last ? T : std::max<int64_t>(o_done, c0 + nt - fwd);
-        if (o1 > o0) {
-            CTKCHK(launch_anom_seg<VT>(h, (const VT *)win, c0 - halo, xlo, c0 + nt, (const VT *)h->an_clim.p, group_dev, valid_dev, npix, smooth, o0, o1,
-                                       (VT *)((char *)h->io_out.p + (size_t)b * obytes)));
-            HIPCHK(hipEventRecord(h->ev_rel[b], h->stream));
-        }
-        // the last `halo` steps in front of the next chunk (a chunk that is not the last has nt == chunk >= halo steps: they lie in its body)
-        if (!last && halo > 0)
-            HIPCHK(hipMemcpyAsync((char *)h->io_in.p + (size_t)(b ^ 1) * wbytes, win + (size_t)nt * plane, (size_t)halo * plane, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(hipEventRecord(h->ev_thr[b], h->stream));
-        CTKCHK(drain(pend));
-        pend = Pending();
-        if (o1 > o0) { pend.t0 = o0; pend.nt = o1 - o0; pend.b = b; }
-        o_done = o1;
-    }
-    CTKCHK(drain(pend));
-    io.ms_in += now_ms() - t_pass - io.ms_out;
-    return CTK_OK;
-}
-
 template <typename VT>
 static int anom_stream_impl(ctk_handle *h, StreamIO &io, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
                             const int64_t *starts, int64_t nseg, const VT *clim_in, VT *clim_out, int64_t chunk_steps, const char *name)
@@ -389,18 +315,42 @@ static int anom_stream_impl(ctk_handle *h, StreamIO &io, int64_t T, int ny, int 
         HIPCHK(hipStreamSynchronize(s));                               // (pass 2 reuses the chunk buffers)
     }
     if (clim_out) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipMemcpy(clim_out, h->an_clim.p, cb, hipMemcpyDeviceToHost)); }
+    int rc = CTK_OK;
     if (sink) {
         std::vector<uint8_t> valid;
         anom_window_valid(starts, nseg, T, smooth, valid);
         CTKCHK(ensure(h, h->an_valid, (size_t)T));
         HIPCHK(hipMemcpy(h->an_valid.p, valid.data(), (size_t)T, hipMemcpyHostToDevice));
-        const int rc = anom_stream_pass2<VT>(h, io, T, npix, smooth, d_grp, P<uint8_t>(h->an_valid), name);
-        if (rc != CTK_OK) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamSynchronize(s); return rc; }
-        HIPCHK(hipStreamSynchronize(s));
+        // pass 2 (stream_produce): the chunks pass through two windows [smooth - 1 steps kept from the chunk before | chunk] in io_in
+        // and two output buffers in io_out
+        const int64_t halo = smooth - 1, fwd = (smooth - 1) / 2;
+        int64_t o_done = 0;
+        Producer p;
+        p.in_bytes = (size_t)(io.chunk + halo) * plane; p.out_step = plane;
+        p.upload = [&](const ProduceIn &c) -> int {
+            const char *src = c.src ? c.src : (const char *)io.host_in + (size_t)c.c0 * plane;
+            HIPCHK(hipMemcpyAsync(c.dev + (size_t)halo * plane, src, (size_t)c.nt * plane, hipMemcpyHostToDevice, h->copy_stream));
+            return CTK_OK;
+        };
+        p.launch = [&](const ProduceIn &c, ProduceOut &o) -> int {
+            // steps [c0 - halo, c0 + nt) are in the window now (the first chunk has nothing in front of it): the outputs whose window
+            // ends inside them, and everything that is left once the last chunk is there
+            const bool last = c.c0 + c.nt == T;
+            const int64_t xlo = c.c0 == 0 ? 0 : c.c0 - halo, o0 = o_done, o1 = last ? T : std::max<int64_t>(o_done, c.c0 + c.nt - fwd);
+            if (o1 > o0) {
+                o.t0 = o0; o.nt = o1 - o0; o.dev = (char *)h->io_out.p + (size_t)c.b * (size_t)(io.chunk + smooth) * plane;
+                CTKCHK(launch_anom_seg<VT>(h, (const VT *)c.dev, c.c0 - halo, xlo, c.c0 + c.nt, (const VT *)h->an_clim.p, d_grp, P<uint8_t>(h->an_valid), npix, smooth,
+                                           o0, o1, (VT *)o.dev));
+            }
+            // the last `halo` steps in front of the next chunk (a chunk that is not the last has nt == chunk >= halo steps: they lie in its body)
+            if (!last && halo > 0)
+                HIPCHK(hipMemcpyAsync((char *)h->io_in.p + (size_t)(c.b ^ 1) * p.in_bytes, c.dev + (size_t)c.nt * plane, (size_t)halo * plane, hipMemcpyDeviceToDevice, h->stream));
+            o_done = o1;
+            return CTK_OK;
+        };
+        rc = stream_produce(h, io, T, name, p);
     }
-    h->stream_ms[0] = io.ms_read; h->stream_ms[1] = io.ms_write; h->stream_ms[2] = io.ms_in; h->stream_ms[3] = io.ms_out;
-    h->ms[CTK_T_H2D] = io.ms_in; h->ms[CTK_T_D2H] = io.ms_out; h->ms[CTK_T_TOTAL] = now_ms() - t_call;
-    return CTK_OK;
+    return stream_produce_end(h, io, rc, t_call);
 }
 
 extern "C" int ctk_anom_stream_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,

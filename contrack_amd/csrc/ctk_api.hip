@@ -854,6 +854,12 @@ extern "C" int ctk_get_timings(ctk_handle *h, double *ms)
 static int stream_in(ctk_handle *h, bool f64, int64_t T, int ny, int nx, const std::function<int(const void *, int64_t, int64_t)> &consume);
 static int stream_out(ctk_handle *h, int persistence, const int32_t *chunk_vals);
 
+// what ctk_stream_timings reports: the reader, the writer, the input side and the output side of the streamed call `io`
+static void stream_ms_set(ctk_handle *h, const StreamIO &io)
+{
+    h->stream_ms[0] = io.ms_read; h->stream_ms[1] = io.ms_write; h->stream_ms[2] = io.ms_in; h->stream_ms[3] = io.ms_out;
+}
+
 // A read-only pass over a streamed slab (the map consumers, the climatology pass, the life cycle): `io` is the handle's source while
 // stream_in runs and on no path longer, the handle gets the pass's stream timings, and a failed chunk -- a reader that gave up -- leaves
 // nothing of the call in flight: a chunk may still be on its way into a buffer.  A pass that succeeds is not waited for here.
@@ -862,7 +868,7 @@ static int stream_consume(ctk_handle *h, StreamIO &io, bool f64, int64_t T, int 
     struct Sio { ctk_handle *h; ~Sio() { h->sio = nullptr; } } sio{h};
     h->sio = &io;
     const int rc = stream_in(h, f64, T, ny, nx, consume);
-    h->stream_ms[0] = io.ms_read; h->stream_ms[1] = io.ms_write; h->stream_ms[2] = io.ms_in; h->stream_ms[3] = io.ms_out;
+    stream_ms_set(h, io);
     if (rc != CTK_OK) {
         if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
         (void)hipStreamSynchronize(h->stream);
@@ -3247,6 +3253,94 @@ static int stream_in(ctk_handle *h, bool f64, int64_t T, int ny, int nx, const s
     return CTK_OK;
 }
 
+// The streamed producers (vertical mean, reversal index, pass 2 of the streamed anomalies): a slab comes in chunk by chunk, a kernel
+// runs on each chunk, a field of the same length leaves.  stream_produce owns the pipeline -- two input chunks in io_in, chunk k + 1
+// travels in while the kernel works on chunk k and the output of chunk k - 1 leaves -- and a producer hands it what differs:
+//   upload    queues the H2D copies of the chunk on copy_stream: from in.src, the pinned chunk the reader filled, or (null) from io.host_in
+//   launch    queues the kernel(s) on the handle's stream, everything that must be done before the input chunk is reused included,
+//             and says which output steps came out and where they lie (out.t0 < 0: none from this chunk)
+//   download  optional: the copy of an output chunk into the host array where it is not whole steps (default: the bounce pool)
+// The caller has called stream_setup; a writer gets the output through pin_out on side[0].
+struct ProduceIn { int b = 0; int64_t c0 = 0, nt = 0; char *dev = nullptr; const char *src = nullptr; };      // chunk [c0, c0 + nt) in buffer b at dev
+struct ProduceOut { int64_t t0 = -1, nt = 0; char *dev = nullptr; };
+struct Producer {
+    size_t in_bytes = 0;                           // of one input buffer, as passed to stream_setup
+    size_t out_step = 0;                           // bytes of one output step
+    std::function<int(const ProduceIn &)> upload;
+    std::function<int(const ProduceIn &, ProduceOut &)> launch;
+    std::function<int(const ProduceOut &, char *dst)> download;
+};
+
+static int stream_produce(ctk_handle *h, StreamIO &io, int64_t steps, const char *name, const Producer &p)
+{
+    const bool sink = io.host_out_v || io.write_v;
+    const double t_pass = now_ms();
+    io.passes_in++;
+    if (io.host_out_v && !h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
+    struct Pending { ProduceOut o; int b = 0; } pend;
+    auto drain = [&](const Pending &q) -> int {                                  // output chunk q leaves the device
+        if (q.o.t0 < 0) return CTK_OK;
+        const double d0 = now_ms();
+        const size_t bytes = (size_t)q.o.nt * p.out_step;
+        HIPCHK(hipEventSynchronize(h->ev_rel[q.b]));
+        if (io.write_v) {
+            HIPCHK(hipMemcpyAsync(h->pin_out[q.b], q.o.dev, bytes, hipMemcpyDeviceToHost, h->side[0]));
+            HIPCHK(hipEventRecord(h->ev_d2h[q.b], h->side[0]));
+            HIPCHK(hipEventSynchronize(h->ev_d2h[q.b]));
+            const double w0 = now_ms();
+            const int rc = io.write_v(io.write_user, q.o.t0, q.o.nt, h->pin_out[q.b]);
+            io.ms_write += now_ms() - w0;
+            if (rc) return ctk_set_error(CTK_E_INVALID, "%s: the writer returned %d for steps [%lld, %lld)", name, rc, (long long)q.o.t0, (long long)(q.o.t0 + q.o.nt));
+        } else {
+            char *dst = (char *)io.host_out_v + (size_t)q.o.t0 * p.out_step;
+            if (p.download) CTKCHK(p.download(q.o, dst));
+            else if (!h->bounce || !bounce_copy(*h->bounce, h->device, q.o.dev, dst, bytes, false))
+                HIPCHK(hipMemcpy(dst, q.o.dev, bytes, hipMemcpyDeviceToHost));
+        }
+        io.ms_out += now_ms() - d0;
+        return CTK_OK;
+    };
+    int k = 0;
+    for (int64_t c0 = 0; c0 < steps; c0 += io.chunk, k++) {
+        ProduceIn in;
+        const int b = in.b = k & 1;
+        in.c0 = c0; in.nt = std::min<int64_t>(io.chunk, steps - c0);
+        in.dev = (char *)h->io_in.p + (size_t)b * p.in_bytes;
+        if (k >= 2) HIPCHK(hipEventSynchronize(h->ev_thr[b]));                 // the input chunk (and its pinned twin) is free again
+        if (io.read) {
+            const double r0 = now_ms();
+            const int rc = io.read(io.read_user, c0, in.nt, h->pin_in[b]);
+            io.ms_read += now_ms() - r0;
+            if (rc) return ctk_set_error(CTK_E_INVALID, "%s: the reader returned %d for steps [%lld, %lld)", name, rc, (long long)c0, (long long)(c0 + in.nt));
+            in.src = (const char *)h->pin_in[b];
+        }
+        CTKCHK(p.upload(in));
+        HIPCHK(hipEventRecord(h->ev_h2d[b], h->copy_stream));
+        HIPCHK(hipStreamWaitEvent(h->stream, h->ev_h2d[b], 0));
+        ProduceOut out;
+        CTKCHK(p.launch(in, out));
+        if (out.t0 >= 0) HIPCHK(hipEventRecord(h->ev_rel[b], h->stream));
+        HIPCHK(hipEventRecord(h->ev_thr[b], h->stream));
+        CTKCHK(drain(pend));                                                    // (the chunk before this one; its output buffer is the other one)
+        pend = Pending();
+        if (sink && out.t0 >= 0) { pend.o = out; pend.b = b; }
+    }
+    CTKCHK(drain(pend));
+    io.ms_in += now_ms() - t_pass - io.ms_out;
+    return CTK_OK;
+}
+
+// the end of a streamed producer's call, rc what its chunks returned: after a failure nothing stays in flight; after a success the
+// stream is idle and the handle has the timings of the call that began at t_call
+static int stream_produce_end(ctk_handle *h, const StreamIO &io, int rc, double t_call)
+{
+    if (rc != CTK_OK) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamSynchronize(h->stream); return rc; }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    stream_ms_set(h, io);
+    h->ms[CTK_T_H2D] = io.ms_in; h->ms[CTK_T_D2H] = io.ms_out; h->ms[CTK_T_TOTAL] = now_ms() - t_call;
+    return CTK_OK;
+}
+
 // output phase: k_relabel writes chunk k+1 into one device buffer while chunk k leaves the other
 static int stream_out(ctk_handle *h, int persistence, const int32_t *chunk_vals)
 {
@@ -3342,7 +3436,7 @@ static int track_stream_impl(ctk_handle *h, StreamIO &io, bool f64, int64_t T, i
     }
     h->sio = nullptr;
     h->rle_out = false;
-    h->stream_ms[0] = io.ms_read; h->stream_ms[1] = io.ms_write; h->stream_ms[2] = io.ms_in; h->stream_ms[3] = io.ms_out;
+    stream_ms_set(h, io);
     h->ms[CTK_T_H2D] = io.ms_in; h->ms[CTK_T_D2H] = io.ms_out; h->ms[CTK_T_TOTAL] = now_ms() - t0;
     return rc;
 }

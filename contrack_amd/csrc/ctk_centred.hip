@@ -448,7 +448,7 @@ static int centred_stream_impl(ctk_handle *h, StreamIO &io, bool f64, int64_t T,
             }();
         }
         io.ms_in += now_ms() - t_in;
-        h->stream_ms[0] = io.ms_read; h->stream_ms[1] = 0; h->stream_ms[2] = io.ms_in; h->stream_ms[3] = 0;
+        stream_ms_set(h, io);                                             // (no writer, no output side: those two stay 0)
         // (also after an error: a chunk may still be on its way into a buffer, and the stamps must have left csr)
         const hipError_t e1 = h->copy_stream ? hipStreamSynchronize(h->copy_stream) : hipSuccess;
         const hipError_t e2 = hipStreamSynchronize(h->stream);

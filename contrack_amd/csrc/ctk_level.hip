@@ -19,7 +19,7 @@
 // Host-array entries: only the selected levels cross PCIe.  Neighbouring selected levels travel as one strided copy per chunk (pitch
 // nlev planes, width `len` planes, one row per step; ctk_level_runs), the device chunk is compact (nt, nsel, ny, nx).  Two input and
 // two output chunks on the handle's copy stream, events and pinned buffers: chunk k + 1 travels in while the kernel reduces chunk k
-// and chunk k - 1 leaves.
+// and chunk k - 1 leaves (stream_produce, ctk_api.hip).
 #pragma once
 
 typedef const __attribute__((address_space(4))) double ctk_const_f64;
@@ -196,74 +196,6 @@ extern "C" int ctk_level_mean_f64_dev(ctk_handle *h, const double *x_dev, int64_
     return level_dev_impl<double>(h, x_dev, steps, nlev, ny, nx, weights, skipna, out_dev, "ctk_level_mean_f64_dev");
 }
 
-// the chunks of the call: io.host_in is the whole (steps, nlev, ny, nx) array (the runs pick its selected levels), io.read a reader of
-// compact chunks (nt, nsel, ny, nx).  The means go to io.host_out_v / io.write_v chunk by chunk and (keep) into lv_out.
-template <typename VT>
-static int level_stream_chunks(ctk_handle *h, StreamIO &io, const LevelSel &sel, int64_t steps, int64_t nlev, int64_t npix, const double *w_dev, const int32_t *lev_dev,
-                               int skipna, bool keep, const char *name)
-{
-    const size_t plane = (size_t)npix * sizeof(VT);
-    const int64_t chunk = io.chunk, K = (int64_t)sel.w.size();
-    const size_t ibytes = (size_t)chunk * (size_t)K * plane, obytes = (size_t)chunk * plane;
-    const bool sink = io.host_out_v || io.write_v;
-    const double t_pass = now_ms();
-    io.passes_in++;
-    if (io.host_out_v && !h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
-    struct Pending { int64_t t0 = -1, nt = 0; int b = 0; char *dev = nullptr; } pend;
-    auto drain = [&](const Pending &q) -> int {                                  // output chunk q leaves the device
-        if (q.t0 < 0) return CTK_OK;
-        const double d0 = now_ms();
-        HIPCHK(hipEventSynchronize(h->ev_rel[q.b]));
-        if (io.write_v) {
-            HIPCHK(hipMemcpyAsync(h->pin_out[q.b], q.dev, (size_t)q.nt * plane, hipMemcpyDeviceToHost, h->side[0]));
-            HIPCHK(hipEventRecord(h->ev_d2h[q.b], h->side[0]));
-            HIPCHK(hipEventSynchronize(h->ev_d2h[q.b]));
-            const double w0 = now_ms();
-            const int rc = io.write_v(io.write_user, q.t0, q.nt, h->pin_out[q.b]);
-            io.ms_write += now_ms() - w0;
-            if (rc) return ctk_set_error(CTK_E_INVALID, "%s: the writer returned %d for steps [%lld, %lld)", name, rc, (long long)q.t0, (long long)(q.t0 + q.nt));
-        } else if (io.host_out_v) {
-            char *dst = (char *)io.host_out_v + (size_t)q.t0 * plane;
-            if (!h->bounce || !bounce_copy(*h->bounce, h->device, q.dev, dst, (size_t)q.nt * plane, false))
-                HIPCHK(hipMemcpy(dst, q.dev, (size_t)q.nt * plane, hipMemcpyDeviceToHost));
-        }
-        io.ms_out += now_ms() - d0;
-        return CTK_OK;
-    };
-    int k = 0;
-    for (int64_t c0 = 0; c0 < steps; c0 += chunk, k++) {
-        const int b = k & 1;
-        const int64_t nt = std::min<int64_t>(chunk, steps - c0);
-        char *in = (char *)h->io_in.p + (size_t)b * ibytes;
-        if (k >= 2) HIPCHK(hipEventSynchronize(h->ev_thr[b]));                 // the input chunk (and its pinned twin) is free again
-        if (io.read) {
-            const double r0 = now_ms();
-            const int rc = io.read(io.read_user, c0, nt, h->pin_in[b]);
-            io.ms_read += now_ms() - r0;
-            if (rc) return ctk_set_error(CTK_E_INVALID, "%s: the reader returned %d for steps [%lld, %lld)", name, rc, (long long)c0, (long long)(c0 + nt));
-            HIPCHK(hipMemcpyAsync(in, h->pin_in[b], (size_t)nt * (size_t)K * plane, hipMemcpyHostToDevice, h->copy_stream));
-        } else if (K == nlev) {
-            HIPCHK(hipMemcpyAsync(in, (const char *)io.host_in + (size_t)c0 * (size_t)nlev * plane, (size_t)nt * (size_t)K * plane, hipMemcpyHostToDevice, h->copy_stream));
-        } else {
-            for (const CtkLevelRun &r : sel.runs)                               // row s of the copy: the run's planes of step c0 + s
-                HIPCHK(hipMemcpy2DAsync(in + (size_t)r.k0 * plane, (size_t)K * plane, (const char *)io.host_in + ((size_t)c0 * (size_t)nlev + (size_t)r.l0) * plane,
-                                        (size_t)nlev * plane, (size_t)r.len * plane, (size_t)nt, hipMemcpyHostToDevice, h->copy_stream));
-        }
-        HIPCHK(hipEventRecord(h->ev_h2d[b], h->copy_stream));
-        HIPCHK(hipStreamWaitEvent(h->stream, h->ev_h2d[b], 0));
-        char *out = keep ? (char *)h->lv_out.p + (size_t)c0 * plane : (char *)h->io_out.p + (size_t)b * obytes;
-        CTKCHK(launch_level<VT>(h, (const VT *)in, K, npix, nt, (int)K, w_dev, lev_dev, sel.wsum, skipna, (VT *)out));
-        HIPCHK(hipEventRecord(h->ev_rel[b], h->stream));
-        HIPCHK(hipEventRecord(h->ev_thr[b], h->stream));
-        CTKCHK(drain(pend));                                                    // (the chunk before this one; its output buffer is the other one)
-        pend = Pending();
-        if (sink) { pend.t0 = c0; pend.nt = nt; pend.b = b; pend.dev = out; }
-    }
-    CTKCHK(drain(pend));
-    io.ms_in += now_ms() - t_pass - io.ms_out;
-    return CTK_OK;
-}
-
 // weights: one per level of the source -- nlev of them for an array (zeros are not selected), the nsel non-zero ones for a reader
 template <typename VT>
 static int level_stream_impl(ctk_handle *h, StreamIO &io, int64_t steps, int64_t nlev, int ny, int nx, const double *weights, int skipna, int64_t chunk_steps,
@@ -294,12 +226,28 @@ static int level_stream_impl(ctk_handle *h, StreamIO &io, int64_t steps, int64_t
     const double *w_dev = nullptr;
     const int32_t *lev_dev = nullptr;
     CTKCHK(level_table(h, sel, true, &w_dev, &lev_dev));
-    const int rc = level_stream_chunks<VT>(h, io, sel, steps, nlev, npix, w_dev, lev_dev, skipna, keep_resident != 0, name);
-    if (rc != CTK_OK) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamSynchronize(h->stream); return rc; }      // (nothing stays in flight)
-    HIPCHK(hipStreamSynchronize(h->stream));
+    // the chunks (stream_produce): io.host_in is the whole (steps, nlev, ny, nx) array (the runs pick its selected levels), io.read a
+    // reader of compact chunks (nt, nsel, ny, nx).  The means go to io.host_out_v / io.write_v chunk by chunk and (keep) into lv_out.
+    Producer p;
+    p.in_bytes = (size_t)io.chunk * (size_t)K * plane; p.out_step = plane;
+    p.upload = [&](const ProduceIn &c) -> int {
+        if (c.src || K == nlev) {
+            const char *src = c.src ? c.src : (const char *)io.host_in + (size_t)c.c0 * (size_t)nlev * plane;
+            HIPCHK(hipMemcpyAsync(c.dev, src, (size_t)c.nt * (size_t)K * plane, hipMemcpyHostToDevice, h->copy_stream));
+            return CTK_OK;
+        }
+        for (const CtkLevelRun &r : sel.runs)                                   // row s of the copy: the run's planes of step c0 + s
+            HIPCHK(hipMemcpy2DAsync(c.dev + (size_t)r.k0 * plane, (size_t)K * plane, (const char *)io.host_in + ((size_t)c.c0 * (size_t)nlev + (size_t)r.l0) * plane,
+                                    (size_t)nlev * plane, (size_t)r.len * plane, (size_t)c.nt, hipMemcpyHostToDevice, h->copy_stream));
+        return CTK_OK;
+    };
+    p.launch = [&](const ProduceIn &c, ProduceOut &o) -> int {
+        o.t0 = c.c0; o.nt = c.nt;
+        o.dev = keep_resident ? (char *)h->lv_out.p + (size_t)c.c0 * plane : (char *)h->io_out.p + (size_t)c.b * (size_t)io.chunk * plane;
+        return launch_level<VT>(h, (const VT *)c.dev, K, npix, c.nt, (int)K, w_dev, lev_dev, sel.wsum, skipna, (VT *)o.dev);
+    };
+    CTKCHK(stream_produce_end(h, io, stream_produce(h, io, steps, name, p), t_call));
     if (keep_resident) { h->lv_T = steps; h->lv_ny = ny; h->lv_nx = nx; h->lv_f64 = sizeof(VT) == 8; }
-    h->stream_ms[0] = io.ms_read; h->stream_ms[1] = io.ms_write; h->stream_ms[2] = io.ms_in; h->stream_ms[3] = io.ms_out;
-    h->ms[CTK_T_H2D] = io.ms_in; h->ms[CTK_T_D2H] = io.ms_out; h->ms[CTK_T_TOTAL] = now_ms() - t_call;
     return CTK_OK;
 }
 
@@ -417,24 +365,8 @@ extern "C" int ctk_debug_time_level_mean(ctk_handle *h, const void *x_dev, int i
     const double *w_dev = nullptr;
     const int32_t *lev_dev = nullptr;
     CTKCHK(level_table(h, sel, false, &w_dev, &lev_dev));
-    Event e0, e1;
-    HIPCHK(e0.create());
-    if (e1.create() != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed");
-    double best = 1e30, sum = 0.0;
-    int rc = CTK_OK;
-    hipError_t err = hipSuccess;
-    for (int r = 0; r < reps + 1 && err == hipSuccess && rc == CTK_OK; r++) {
-        err = hipEventRecord(e0, h->stream);
-        rc = is_f64 ? launch_level<double>(h, (const double *)x_dev, nlev, (int64_t)ny * nx, steps, (int)sel.w.size(), w_dev, lev_dev, sel.wsum, skipna, (double *)out_dev)
-                    : launch_level<float>(h, (const float *)x_dev, nlev, (int64_t)ny * nx, steps, (int)sel.w.size(), w_dev, lev_dev, sel.wsum, skipna, (float *)out_dev);
-        if (err == hipSuccess) err = hipEventRecord(e1, h->stream);
-        if (err == hipSuccess) err = hipEventSynchronize(e1);
-        float f = 0.f;
-        if (err == hipSuccess) err = hipEventElapsedTime(&f, e0, e1);
-        if (r > 0) { best = std::min(best, (double)f); sum += f; }
-    }
-    if (rc != CTK_OK) return rc;
-    if (err != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "ctk_debug_time_level_mean: %s", hipGetErrorString(err));
-    ms2[0] = best; ms2[1] = sum / reps;
-    return CTK_OK;
+    return time_launches(h, "ctk_debug_time_level_mean", reps, ms2, [&]() {
+        return is_f64 ? launch_level<double>(h, (const double *)x_dev, nlev, (int64_t)ny * nx, steps, (int)sel.w.size(), w_dev, lev_dev, sel.wsum, skipna, (double *)out_dev)
+                      : launch_level<float>(h, (const float *)x_dev, nlev, (int64_t)ny * nx, steps, (int)sel.w.size(), w_dev, lev_dev, sel.wsum, skipna, (float *)out_dev);
+    });
 }

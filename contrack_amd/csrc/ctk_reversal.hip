@@ -19,8 +19,8 @@
 // Host-array entries: of every plane only the rows [r0, r1) that some active row reads travel to the device (one strided copy per
 // chunk, the plane as pitch) and only the rows [a0, a1) the active rows span travel back; the rest of `out` is zeroed on the host.
 // The device chunks keep the full-plane layout, so the kernel is the one of the _dev entries.  Two input and two output chunks on the
-// handle's copy stream, as ctk_level.hip.  keep_resident: the full-plane result is written into the resident slot of the field to
-// track (an_out), where ctk_track_resident and the `resident` consumers find it.
+// handle's copy stream (stream_produce, ctk_api.hip).  keep_resident: the full-plane result is written into the resident slot of the
+// field to track (an_out), where ctk_track_resident and the `resident` consumers find it.
 #pragma once
 
 // the row table of a call on the device: dE, tS, tN, tS2 (ny float64 each), then eq, po, eq2 (ny int32 each)
@@ -174,77 +174,6 @@ extern "C" int ctk_reversal_f64_dev(ctk_handle *h, const double *x_dev, int64_t 
     return reversal_dev_impl<double>(h, x_dev, steps, ny, nx, a, out_dev, "ctk_reversal_f64_dev");
 }
 
-// the chunks of the call: io.host_in is the whole (steps, ny, nx) array (rows [r0, r1) of every plane travel), io.read a reader of
-// whole planes.  The results go to io.host_out_v (rows [a0, a1) of every plane; the caller zeroes the rest) / io.write_v (whole
-// planes) chunk by chunk and (keep) into an_out.
-template <typename VT>
-static int reversal_stream_chunks(ctk_handle *h, StreamIO &io, const ReversalTab &tab, const CtkReversalRows &rr, bool second, bool mask, int64_t steps, int ny, int nx,
-                                  bool keep, const char *name)
-{
-    const size_t row = (size_t)nx * sizeof(VT), plane = (size_t)ny * row;
-    const int64_t chunk = io.chunk;
-    const size_t cbytes = (size_t)chunk * plane;
-    const size_t in_off = (size_t)rr.r0 * row, in_w = (size_t)(rr.r1 - rr.r0) * row, out_off = (size_t)rr.a0 * row, out_w = (size_t)(rr.a1 - rr.a0) * row;
-    const bool sink = io.host_out_v || io.write_v;
-    const double t_pass = now_ms();
-    io.passes_in++;
-    if (io.host_out_v && !h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
-    struct Pending { int64_t t0 = -1, nt = 0; int b = 0; char *dev = nullptr; } pend;
-    auto drain = [&](const Pending &q) -> int {                                  // output chunk q leaves the device
-        if (q.t0 < 0) return CTK_OK;
-        const double d0 = now_ms();
-        HIPCHK(hipEventSynchronize(h->ev_rel[q.b]));
-        if (io.write_v) {
-            HIPCHK(hipMemcpyAsync(h->pin_out[q.b], q.dev, (size_t)q.nt * plane, hipMemcpyDeviceToHost, h->side[0]));
-            HIPCHK(hipEventRecord(h->ev_d2h[q.b], h->side[0]));
-            HIPCHK(hipEventSynchronize(h->ev_d2h[q.b]));
-            const double w0 = now_ms();
-            const int rc = io.write_v(io.write_user, q.t0, q.nt, h->pin_out[q.b]);
-            io.ms_write += now_ms() - w0;
-            if (rc) return ctk_set_error(CTK_E_INVALID, "%s: the writer returned %d for steps [%lld, %lld)", name, rc, (long long)q.t0, (long long)(q.t0 + q.nt));
-        } else if (io.host_out_v && out_w) {
-            char *dst = (char *)io.host_out_v + (size_t)q.t0 * plane;
-            if (out_w == plane) {
-                if (!h->bounce || !bounce_copy(*h->bounce, h->device, q.dev, dst, (size_t)q.nt * plane, false))
-                    HIPCHK(hipMemcpy(dst, q.dev, (size_t)q.nt * plane, hipMemcpyDeviceToHost));
-            } else {
-                HIPCHK(hipMemcpy2D(dst + out_off, plane, q.dev + out_off, plane, out_w, (size_t)q.nt, hipMemcpyDeviceToHost));
-            }
-        }
-        io.ms_out += now_ms() - d0;
-        return CTK_OK;
-    };
-    int k = 0;
-    for (int64_t c0 = 0; c0 < steps; c0 += chunk, k++) {
-        const int b = k & 1;
-        const int64_t nt = std::min<int64_t>(chunk, steps - c0);
-        char *in = (char *)h->io_in.p + (size_t)b * cbytes;
-        if (k >= 2) HIPCHK(hipEventSynchronize(h->ev_thr[b]));                 // the input chunk (and its pinned twin) is free again
-        const char *src = (const char *)io.host_in + (size_t)c0 * plane;
-        if (io.read) {
-            const double r0 = now_ms();
-            const int rc = io.read(io.read_user, c0, nt, h->pin_in[b]);
-            io.ms_read += now_ms() - r0;
-            if (rc) return ctk_set_error(CTK_E_INVALID, "%s: the reader returned %d for steps [%lld, %lld)", name, rc, (long long)c0, (long long)(c0 + nt));
-            src = (const char *)h->pin_in[b];
-        }
-        if (in_w == plane) HIPCHK(hipMemcpyAsync(in, src, (size_t)nt * plane, hipMemcpyHostToDevice, h->copy_stream));
-        else if (in_w) HIPCHK(hipMemcpy2DAsync(in + in_off, plane, src + in_off, plane, in_w, (size_t)nt, hipMemcpyHostToDevice, h->copy_stream));      // row s of the copy: rows [r0, r1) of step c0 + s
-        HIPCHK(hipEventRecord(h->ev_h2d[b], h->copy_stream));
-        HIPCHK(hipStreamWaitEvent(h->stream, h->ev_h2d[b], 0));
-        char *out = keep ? (char *)h->an_out.p + (size_t)c0 * plane : (char *)h->io_out.p + (size_t)b * cbytes;
-        CTKCHK(launch_reversal<VT>(h, (const VT *)in, ny, nx, nt, tab, second, mask, (VT *)out));
-        HIPCHK(hipEventRecord(h->ev_rel[b], h->stream));
-        HIPCHK(hipEventRecord(h->ev_thr[b], h->stream));
-        CTKCHK(drain(pend));                                                    // (the chunk before this one; its output buffer is the other one)
-        pend = Pending();
-        if (sink) { pend.t0 = c0; pend.nt = nt; pend.b = b; pend.dev = out; }
-    }
-    CTKCHK(drain(pend));
-    io.ms_in += now_ms() - t_pass - io.ms_out;
-    return CTK_OK;
-}
-
 // rows of every plane of `out` (steps, ny, nx) outside [a0, a1): zero
 static void reversal_zero_rest(void *out, int64_t steps, size_t plane, size_t off, size_t width)
 {
@@ -284,13 +213,32 @@ static int reversal_stream_impl(ctk_handle *h, StreamIO &io, int64_t steps, int 
     // copies write; at 1 degree, one hemisphere, that is three quarters of the array)
     struct Joiner { std::thread t; ~Joiner() { if (t.joinable()) t.join(); } } zero;
     if (io.host_out_v) zero.t = std::thread(reversal_zero_rest, io.host_out_v, steps, plane, (size_t)rr.a0 * row, (size_t)(rr.a1 - rr.a0) * row);
-    const int rc = reversal_stream_chunks<VT>(h, io, tab, rr, a.eq2 != nullptr, a.mask != 0, steps, ny, nx, keep_resident != 0, name);
-    if (rc != CTK_OK) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamSynchronize(h->stream); return rc; }      // (nothing stays in flight)
-    HIPCHK(hipStreamSynchronize(h->stream));
+    // the chunks (stream_produce): io.host_in is the whole (steps, ny, nx) array (rows [r0, r1) of every plane travel), io.read a
+    // reader of whole planes.  The results go to io.host_out_v (rows [a0, a1) of every plane) / io.write_v (whole planes) chunk by
+    // chunk and (keep) into an_out.
+    const size_t in_off = (size_t)rr.r0 * row, in_w = (size_t)(rr.r1 - rr.r0) * row, out_off = (size_t)rr.a0 * row, out_w = (size_t)(rr.a1 - rr.a0) * row;
+    Producer p;
+    p.in_bytes = (size_t)io.chunk * plane; p.out_step = plane;
+    p.upload = [&](const ProduceIn &c) -> int {
+        const char *src = c.src ? c.src : (const char *)io.host_in + (size_t)c.c0 * plane;
+        if (in_w == plane) HIPCHK(hipMemcpyAsync(c.dev, src, (size_t)c.nt * plane, hipMemcpyHostToDevice, h->copy_stream));
+        else if (in_w) HIPCHK(hipMemcpy2DAsync(c.dev + in_off, plane, src + in_off, plane, in_w, (size_t)c.nt, hipMemcpyHostToDevice, h->copy_stream));      // row s of the copy: rows [r0, r1) of step c0 + s
+        return CTK_OK;
+    };
+    p.launch = [&](const ProduceIn &c, ProduceOut &o) -> int {
+        o.t0 = c.c0; o.nt = c.nt;
+        o.dev = keep_resident ? (char *)h->an_out.p + (size_t)c.c0 * plane : (char *)h->io_out.p + (size_t)c.b * (size_t)io.chunk * plane;
+        return launch_reversal<VT>(h, (const VT *)c.dev, ny, nx, c.nt, tab, a.eq2 != nullptr, a.mask != 0, (VT *)o.dev);
+    };
+    if (out_w != plane)
+        p.download = [&](const ProduceOut &o, char *dst) -> int {
+            if (out_w) HIPCHK(hipMemcpy2D(dst + out_off, plane, o.dev + out_off, plane, out_w, (size_t)o.nt, hipMemcpyDeviceToHost));
+            return CTK_OK;
+        };
+    const int rc = stream_produce(h, io, steps, name, p);
     if (zero.t.joinable()) zero.t.join();
+    CTKCHK(stream_produce_end(h, io, rc, t_call));
     if (keep_resident) { h->an_T = steps; h->an_ny = ny; h->an_nx = nx; h->an_f64 = sizeof(VT) == 8; }
-    h->stream_ms[0] = io.ms_read; h->stream_ms[1] = io.ms_write; h->stream_ms[2] = io.ms_in; h->stream_ms[3] = io.ms_out;
-    h->ms[CTK_T_H2D] = io.ms_in; h->ms[CTK_T_D2H] = io.ms_out; h->ms[CTK_T_TOTAL] = now_ms() - t_call;
     return CTK_OK;
 }
 
@@ -370,25 +318,13 @@ extern "C" int ctk_debug_time_reversal(ctk_handle *h, const void *x_dev, int is_
     const int64_t cblocks = (n16 + 255) / 256;
     const unsigned cgrid = (unsigned)std::min<int64_t>(std::max<int64_t>(cblocks, 1), CTK_LEVEL_GRID_MAX);
     const int cxcd = h->gr_xcd_dbg >= 0 ? h->gr_xcd_dbg : (cgrid >= CTK_LEVEL_XCD_MIN ? 1 : 0);
-    Event e0, e1;
-    HIPCHK(e0.create());
-    if (e1.create() != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "hipEventCreate failed");
-    double best = 1e30, sum = 0.0;
-    int rc = CTK_OK;
-    hipError_t err = hipSuccess;
-    for (int r = 0; r < reps + 1 && err == hipSuccess && rc == CTK_OK; r++) {
-        err = hipEventRecord(e0, h->stream);
-        if (!eq) k_reversal_copy<<<cgrid, 256, 0, h->stream>>>((const i32x4 *)x_dev, (i32x4 *)out_dev, n16, cxcd);
-        else rc = is_f64 ? launch_reversal<double>(h, (const double *)x_dev, ny, nx, steps, tab, eq2 != nullptr, mask != 0, (double *)out_dev)
-                         : launch_reversal<float>(h, (const float *)x_dev, ny, nx, steps, tab, eq2 != nullptr, mask != 0, (float *)out_dev);
-        if (err == hipSuccess) err = hipEventRecord(e1, h->stream);
-        if (err == hipSuccess) err = hipEventSynchronize(e1);
-        float f = 0.f;
-        if (err == hipSuccess) err = hipEventElapsedTime(&f, e0, e1);
-        if (r > 0) { best = std::min(best, (double)f); sum += f; }
-    }
-    if (rc != CTK_OK) return rc;
-    if (err != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "ctk_debug_time_reversal: %s", hipGetErrorString(err));
-    ms2[0] = best; ms2[1] = sum / reps;
-    return CTK_OK;
+    return time_launches(h, "ctk_debug_time_reversal", reps, ms2, [&]() -> int {
+        if (!eq) {
+            k_reversal_copy<<<cgrid, 256, 0, h->stream>>>((const i32x4 *)x_dev, (i32x4 *)out_dev, n16, cxcd);
+            HIPCHK(hipGetLastError());
+            return CTK_OK;
+        }
+        return is_f64 ? launch_reversal<double>(h, (const double *)x_dev, ny, nx, steps, tab, eq2 != nullptr, mask != 0, (double *)out_dev)
+                      : launch_reversal<float>(h, (const float *)x_dev, ny, nx, steps, tab, eq2 != nullptr, mask != 0, (float *)out_dev);
+    });
 }

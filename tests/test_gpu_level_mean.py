@@ -248,6 +248,65 @@ def test_reader_that_gives_up_and_argument_errors_leave_the_handle_usable(trk, c
     assert lu.same_bits(trk.level_mean(x, w), want)                           # the handle works
 
 
+def test_writer_that_gives_up_leaves_nothing_resident_and_the_handle_usable(trk, cases):
+    """four chunks of 2, 2, 2 and 1 steps (both buffers reused once); the writer fails on the second"""
+    x, w, want = cases[("float32", "pinned", 0)]
+    sel = np.flatnonzero(w)
+
+    def reader(t0, nt, out):
+        out[...] = x[t0:t0 + nt][:, sel]
+    for keep in (False, True):
+        seen = []
+
+        def writer(t0, nt, values):
+            seen.append(t0)
+            if len(seen) == 2:
+                raise RuntimeError("disk full")
+        with pytest.raises(RuntimeError, match="disk full"):
+            trk.level_mean_cb(reader, (7, len(sel), 9, 65), np.float32, w[sel], sink=writer, chunk_steps=2, keep_resident=keep)
+        assert seen == [0, 2], keep
+        assert trk.resident_level_mean() is None
+    L, h = _native.lib(), trk.handle
+    tr = _native._Trampolines()
+    fill = tr.reader(reader, C.c_float, (len(sel), 9, 65))
+    give_up = _native.WRITE_CHUNK_FN(lambda user, t0, nt, src: 1 if t0 else 0)
+    wv = w[sel].copy()
+    for keep in (0, 1):
+        assert L.ctk_level_mean_stream_cb(h, 4, 7, len(sel), 9, 65, fill, None, wv.ctypes.data, 0, give_up, None, 2, keep) == -1      # CTK_E_INVALID
+        err = L.ctk_last_error()
+        assert b"ctk_level_mean_stream_cb" in err and b"writer returned 1" in err, err
+        assert trk.resident_level_mean() is None
+    assert not tr.errors
+    assert lu.same_bits(trk.level_mean(x, w), want)                           # the handle works
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_writer_together_with_keep_resident(trk, cases, dtype):
+    """the kernel writes the resident mean, and the writer gets every chunk from there through the pinned output chunks"""
+    x, w, want = cases[(dtype, "pinned", 1)]
+    sel = np.flatnonzero(w)
+    asked, chunks = [], []
+
+    def reader(t0, nt, out):
+        asked.append(t0)
+        out[...] = x[t0:t0 + nt][:, sel]
+
+    def writer(t0, nt, values):
+        chunks.append((t0, values.copy()))
+    assert trk.level_mean_cb(reader, (7, len(sel), 9, 65), x.dtype, w[sel], skipna=True, sink=writer, chunk_steps=2, keep_resident=True) is None
+    assert asked == [0, 2, 4, 6] and [t0 for t0, _ in chunks] == asked
+    assert lu.same_bits(np.concatenate([v for _, v in chunks]), want)
+    assert trk.resident_level_mean() == (7, 9, 65, dtype == "float64")
+    group = np.arange(7, dtype=np.int32)                                      # own group per step, climatology 0: the anomaly is the mean itself
+    zero = np.zeros((7, 9, 65), dtype=x.dtype)
+    assert lu.same_bits(trk.anomalies_resident(group, 7, clim=zero)[0], trk.anomalies(want, group, 7, clim=zero)[0])
+    assert lu.same_bits(trk.anomalies_resident(group, 7, clim=zero)[0], want - zero)
+    group, G = (np.arange(7) % 3).astype(np.int32), 3
+    ref = trk.anomalies(want, group, G, window=1, smooth=2, want_clim=True, segments=[0, 3])
+    got = trk.anomalies_resident(group, G, window=1, smooth=2, want_clim=True, segments=[0, 3])
+    assert lu.same_bits(got[0], ref[0]) and lu.same_bits(got[1], ref[1])
+
+
 def test_1024_selected_levels(trk):
     x = lu.field(np.float64, steps=2, nlev=1030, ny=2, nx=3, seed=9)
     w = np.random.default_rng(1).random(1030) + 0.5

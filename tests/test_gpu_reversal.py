@@ -245,6 +245,72 @@ def test_argument_errors_leave_the_handle_usable(trk):
     assert ru.same_bits(trk.reversal(z, tab), want)                              # the handle works
 
 
+@pytest.mark.parametrize("cs", [2, 3])
+def test_writer_that_gives_up_leaves_nothing_resident_and_the_handle_usable(trk, cs):
+    """four chunks of 2, 2, 2, 1 or three of 3, 3, 1 steps (both buffers reused once); the writer fails on the second"""
+    lat = ru.grid(5.0)
+    z = ru.field(lat, 8, steps=7, seed=12)
+    tab = ru.table(lat)
+    want = ru.from_table(z, tab)
+    assert blocked(want, tab)
+
+    def reader(t0, nt, view):
+        view[...] = z[t0:t0 + nt]
+    for keep in (False, True):
+        seen = []
+
+        def writer(t0, nt, values):
+            seen.append(t0)
+            if len(seen) == 2:
+                raise RuntimeError("disk full")
+        with pytest.raises(RuntimeError, match="disk full"):
+            trk.reversal_cb(reader, z.shape, z.dtype, tab, sink=writer, chunk_steps=cs, keep_resident=keep)
+        assert seen == [0, cs], keep
+        if keep:
+            assert trk.resident_anom() is None
+    L, h = _native.lib(), trk.handle
+    tr = _native._Trampolines()
+    fill = tr.reader(reader, C.c_float, (37, 8))
+    give_up = _native.WRITE_CHUNK_FN(lambda user, t0, nt, src: 1 if t0 else 0)
+    ptrs, _keep = _native._reversal_rows(tab, 37)
+    for keep in (0, 1):
+        assert L.ctk_reversal_stream_cb(h, 4, 7, 37, 8, fill, None, *ptrs, 0, give_up, None, cs, keep) == -1      # CTK_E_INVALID
+        err = L.ctk_last_error()
+        assert b"ctk_reversal_stream_cb" in err and b"writer returned 1" in err, err
+        if keep:
+            assert trk.resident_anom() is None
+    assert not tr.errors
+    assert ru.same_bits(trk.reversal(z, tab), want)                              # the handle works
+
+
+@pytest.mark.parametrize("cs", [2, 3])
+def test_writer_together_with_keep_resident(trk, cs):
+    """the kernel writes the resident slot, and the writer gets every chunk from there through the pinned output chunks"""
+    lat = ru.grid(5.0)
+    z = ru.field(lat, 8, steps=7, seed=12)
+    tab = ru.table(lat)
+    want = ru.from_table(z, tab)
+    assert blocked(want, tab)
+    asked, chunks = [], []
+
+    def reader(t0, nt, view):
+        asked.append(t0)
+        view[...] = z[t0:t0 + nt]
+
+    def writer(t0, nt, values):
+        chunks.append((t0, values.copy()))
+    g0 = trk.resident_generation()
+    assert trk.reversal_cb(reader, z.shape, z.dtype, tab, sink=writer, chunk_steps=cs, keep_resident=True) is None
+    assert asked == list(range(0, 7, cs)) and [t0 for t0, _ in chunks] == asked
+    assert ru.same_bits(np.concatenate([v for _, v in chunks]), want)
+    assert trk.resident_anom() == (7, 37, 8, False) and trk.resident_generation() != g0
+    assert trk.percentile(None, 3, 12, 0.9) == trk.percentile(want, 3, 12, 0.9)
+    wrow = row_weights(lat.astype(np.float32), np.float32(5.0), np.float32(5.0))
+    ids, n_ids = track_numpy(want, wrow, 0, ">", 0.0, 1)
+    flag, n = trk.track_resident(np.zeros(7), _native.CMP_OPS[">"], wrow, 0.0, 1)
+    assert n_ids > 0 and n == n_ids and np.array_equal(np.array(flag), ids)
+
+
 # ---- the resident slot ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
 def test_resident_slot(trk, dtype):
