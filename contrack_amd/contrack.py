@@ -980,6 +980,75 @@ def _fingerprint(a):
     return (a.__array_interface__["data"][0], a.shape, str(a.dtype), hash(sample))
 
 
+def _producer_dtype(dtype):
+    """the slab type of the entries that produce a field (run_contrack, calc_clim / calc_anom, calc_vertical_mean, calc_reversal):
+    float32 stays, everything else becomes float64.  The consumers of a field take it by _native._field_dtype instead."""
+    return np.dtype(np.float32) if np.dtype(dtype) == np.float32 else np.dtype(np.float64)
+
+
+class _Steps(object):
+    """a labelled variable as the (steps, lat, lon) series the library takes: `step_dims`, in the order given, count the steps --
+    (time,), (member, time): flat step m * T + t, or every non-spatial dim --, `level` names a level dim kept in front of
+    (lat, lon).  The variable's own dim order is free; slab() is the whole series on the host, reader() reads it slice by slice,
+    restore() brings a (steps, ...) result back into labelled dims."""
+
+    def __init__(self, da, step_dims, lat, lon, level=None):
+        self.da, self.dims, self.step_dims = da, tuple(da.dims), tuple(step_dims)
+        self.tail = ((level,) if level is not None else ()) + (lat, lon)
+        self.step_shape = tuple(da.shape[self.dims.index(d)] for d in self.step_dims)
+        self.steps = int(np.prod(self.step_shape)) if self.step_dims else 1
+        self.shape = (self.steps, da.shape[self.dims.index(lat)], da.shape[self.dims.index(lon)])
+
+    def slab(self, only=None):
+        """the host array (steps, [nlev,] ny, nx): a transpose and a reshape of the variable's data -- a view of it where its dims
+        are already in that order.  only=o: the series of outer step index o alone (a view: member o of (member, time))."""
+        arr = np.asarray(self.da.data).transpose([self.dims.index(d) for d in self.step_dims + self.tail])
+        if only is not None:
+            return arr[np.unravel_index(only, self.step_shape[:-1])]
+        return arr.reshape((self.steps,) + arr.shape[len(self.step_dims):])
+
+    def reader(self, integer=False, only=None, level_runs=None):
+        """reader(t0, nt, out) of the flat steps [t0, t0 + nt): one isel(outer step dims = index, innermost step dim = slice) per run
+        of the innermost step dim the window touches -- a chunk that spans two members in two pieces --, so the flattened slab is
+        never built on the host.  out is (nt, ny, nx); with level_runs, (first level, count) pairs, (nt, nsel, ny, nx) filled by
+        one isel per run of levels.  integer: a flag variable, every piece checked on its way in (_int32_chunk).  only=o: as in
+        slab.  A single step dim without `isel` is read with np.take."""
+        da, outer, inner, n_in = self.da, self.step_dims[:-1], self.step_dims[-1], self.step_shape[-1]
+        left = tuple(d for d in self.dims if d not in outer)                      # what isel(outer step dims = index) leaves
+        sort = [left.index(d) for d in (inner,) + self.tail]
+        narrow = _int32_chunk if integer else (lambda a: a)
+
+        def piece(sel):
+            if outer or hasattr(da, "isel"):
+                return narrow(np.asarray(da.isel(**sel).data)).transpose(sort)
+            t = sel[inner]
+            return narrow(np.asarray(da.data).take(range(t.start, t.stop), axis=self.dims.index(inner))).transpose(sort)
+
+        def reader(t0, nt, out):
+            done = 0
+            while done < nt:
+                o, t = divmod(t0 + done, n_in)
+                n = min(nt - done, n_in - t)
+                sel = dict(zip(outer, (int(v) for v in np.unravel_index(o if only is None else only, self.step_shape[:-1]))))
+                sel[inner] = slice(t, t + n)
+                if level_runs is None:
+                    out[done:done + n] = piece(sel)
+                else:
+                    k = 0
+                    for l0, ln in level_runs:
+                        sel[self.tail[0]] = slice(l0, l0 + ln)
+                        out[done:done + n, k:k + ln] = piece(sel)
+                        k += ln
+                done += n
+        return reader
+
+    def restore(self, arr, out_dims):
+        """a (steps, ...) result whose other axes are the last of ([level,] lat, lon) -> the labelled dim order `out_dims`: the steps
+        reshaped to the step dims, then a transpose (a view of a contiguous `arr`)"""
+        have = self.step_dims + self.tail[len(self.tail) - (arr.ndim - 1):]
+        return arr.reshape(self.step_shape + arr.shape[1:]).transpose([have.index(d) for d in out_dims])
+
+
 class contrack(object):
     """contrack class -- interface of steidani/ConTrack (contrack/contrack.py:49), HIP-accelerated run_contrack."""
 
@@ -1239,28 +1308,22 @@ class contrack(object):
         raise ValueError("no level dimension found among the dims {} (one of {} or a coordinate in {}); name it with level_name="
                          .format(dims, self._LEVEL_NAMES, self._PRESSURE_UNITS))
 
-    def _level_reader(self, da, dims, lev, step_dims, runs):
-        """reader(t0, nt, out) of the selected levels of flat steps [t0, t0 + nt) -- the step dims flattened in their own order --, read
-        as isel(outer step dims = index, innermost step dim = slice, level = slice of one run): out is (nt, nsel, ny, nx)"""
-        sizes = [da.shape[dims.index(d)] for d in step_dims]
-        inner, n_in = step_dims[-1], sizes[-1]
-        left = tuple(d for d in dims if d not in step_dims[:-1])
-        sort = [left.index(d) for d in (inner, lev, self._latitude_name, self._longitude_name)]
+    def _steps(self, da, step_dims, level=None):
+        """the flat-step view (_Steps) of a variable of this dataset; a None among step_dims (no member dimension) is left out"""
+        return _Steps(da, tuple(d for d in step_dims if d is not None), self._latitude_name, self._longitude_name, level)
 
-        def reader(t0, nt, out):
-            done = 0
-            while done < nt:
-                o, t = divmod(t0 + done, n_in)
-                n = min(nt - done, n_in - t)
-                sel = dict(zip(step_dims[:-1], (int(v) for v in np.unravel_index(o, sizes[:-1])))) if len(sizes) > 1 else {}
-                sel[inner] = slice(t, t + n)
-                k = 0
-                for l0, ln in runs:
-                    sel[lev] = slice(l0, l0 + ln)
-                    out[done:done + n, k:k + ln] = np.asarray(da.isel(**sel).data).transpose(sort)
-                    k += ln
-                done += n
-        return reader
+    def _every_step(self, variable, chunk_steps, level=None):
+        """what calc_vertical_mean and calc_reversal share: (da, view, resident, streamed).  view: every dim of the variable besides
+        `level`, latitude and longitude counts steps; resident: the result also stays in HBM (a host call over time alone);
+        streamed: the variable is read slice by slice (view.reader), else as view.slab()"""
+        da = self.ds[variable]
+        dims = tuple(da.dims)
+        for d in (self._latitude_name, self._longitude_name):
+            if d not in dims:
+                raise ValueError("the variable {!r} has no dimension {!r} (dims {})".format(variable, d, dims))
+        view = self._steps(da, tuple(d for d in dims if d not in (level, self._latitude_name, self._longitude_name)), level)
+        resident = chunk_steps is None and view.step_dims == (self._time_name,)
+        return da, view, resident, chunk_steps is not None and bool(view.step_dims)
 
     def calc_vertical_mean(self, variable, bounds=None, level_name=None, weights='pressure', skipna=False, name=None, chunk_steps=None):
         """adds the variable `name` (default variable + '_vmean'): the mean of `variable` over its level dimension between `bounds`
@@ -1277,12 +1340,9 @@ class contrack(object):
         through chunk-sized device buffers; the 4-D array is never built on the host.  Without it, for a (time, level, lat, lon)
         variable in any order, the mean also stays in HBM and a following calc_anom(variable=name) starts from there."""
         self._ensure_set_up()
-        da = self.ds[variable]
-        dims = tuple(da.dims)
+        dims = tuple(self.ds[variable].dims)
         lev = self._get_name_level(dims, level_name)
-        for d in (self._latitude_name, self._longitude_name):
-            if d not in dims:
-                raise ValueError("the variable {!r} has no dimension {!r} (dims {})".format(variable, d, dims))
+        da, view, resident, streamed = self._every_step(variable, chunk_steps, lev)
         nlev = da.shape[dims.index(lev)]
         if isinstance(weights, str):
             try:
@@ -1296,29 +1356,21 @@ class contrack(object):
             w = _vertical_weights(weights, None, None, nlev)
             levels = None
         sel = np.flatnonzero(w > 0)
-        step_dims = tuple(d for d in dims if d not in (lev, self._latitude_name, self._longitude_name))
         out_dims = tuple(d for d in dims if d != lev)
-        ny, nx = da.shape[dims.index(self._latitude_name)], da.shape[dims.index(self._longitude_name)]
-        step_shape = tuple(da.shape[dims.index(d)] for d in step_dims)
-        steps = int(np.prod(step_shape)) if step_dims else 1
         trk = _tracker()
-        resident = chunk_steps is None and step_dims == (self._time_name,)
         logger.info('Calculating vertical mean of {} over {} of {} levels...'.format(variable, len(sel), nlev))
-        if chunk_steps is not None and step_dims:
+        if streamed:
             runs = [(int(r[0]), len(r)) for r in np.split(sel, np.flatnonzero(np.diff(sel) != 1) + 1)]
-            dtype = np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
-            mean = trk.level_mean_cb(self._level_reader(da, dims, lev, step_dims, runs), (steps, len(sel), ny, nx), dtype, w[sel], skipna=skipna,
-                                     chunk_steps=int(chunk_steps))
+            mean = trk.level_mean_cb(view.reader(level_runs=runs), (view.steps, len(sel)) + view.shape[1:], _producer_dtype(da.dtype), w[sel],
+                                     skipna=skipna, chunk_steps=int(chunk_steps))
         else:
-            sort = [dims.index(d) for d in step_dims + (lev, self._latitude_name, self._longitude_name)]
-            arr = np.asarray(da.data).transpose(sort).reshape((steps, nlev, ny, nx))
+            arr = view.slab()
             if arr.dtype.kind != "f":
                 arr = arr.astype(np.float64)
             mean = trk.level_mean(arr, w, skipna=skipna, keep_resident=resident)
         if resident:
             mean.flags.writeable = False                     # (its twin stays in HBM for calc_anom: see _fingerprint)
-        lead = step_dims + (self._latitude_name, self._longitude_name)
-        out = mean.reshape(step_shape + (ny, nx)).transpose([lead.index(d) for d in out_dims])
+        out = view.restore(mean, out_dims)
         name = variable + '_vmean' if name is None else name
         attrs = {}
         if 'units' in da.attrs:
@@ -1343,25 +1395,6 @@ class contrack(object):
             trk.resident_level_mean() == (slab.shape[0], slab.shape[1], slab.shape[2], slab.dtype == np.float64)
 
     # ---- reversal of the meridional height gradient: the second family of blocking indices --------------------------------
-    def _step_reader(self, da, dims, step_dims):
-        """reader(t0, nt, out) of flat steps [t0, t0 + nt) -- the step dims flattened in their own order --, read as isel(outer step
-        dims = index, innermost step dim = slice): out is (nt, ny, nx)"""
-        sizes = [da.shape[dims.index(d)] for d in step_dims]
-        inner, n_in = step_dims[-1], sizes[-1]
-        left = tuple(d for d in dims if d not in step_dims[:-1])
-        sort = [left.index(d) for d in (inner, self._latitude_name, self._longitude_name)]
-
-        def reader(t0, nt, out):
-            done = 0
-            while done < nt:
-                o, t = divmod(t0 + done, n_in)
-                n = min(nt - done, n_in - t)
-                sel = dict(zip(step_dims[:-1], (int(v) for v in np.unravel_index(o, sizes[:-1])))) if len(sizes) > 1 else {}
-                sel[inner] = slice(t, t + n)
-                out[done:done + n] = np.asarray(da.isel(**sel).data).transpose(sort)
-                done += n
-        return reader
-
     def calc_reversal(self, variable, delta=15., ghgs=0., ghgn=-10., ghgs2=None, lat_bounds=(30, 75), hemisphere='both', stat='gradient', name='reversal',
                       chunk_steps=None):
         """adds the variable `name`: the two-dimensional blocking index of the reversal of the meridional gradient of `variable`
@@ -1385,33 +1418,22 @@ class contrack(object):
             raise ValueError("stat={!r}: one of {}".format(stat, _REVERSAL_STATS))
         if chunk_steps is not None and int(chunk_steps) < 0:
             raise ValueError("chunk_steps must be >= 0")
-        da = self.ds[variable]
-        dims = tuple(da.dims)
-        for d in (self._latitude_name, self._longitude_name):
-            if d not in dims:
-                raise ValueError("the variable {!r} has no dimension {!r} (dims {})".format(variable, d, dims))
+        da, view, resident, streamed = self._every_step(variable, chunk_steps)
+        dims = view.dims
         lat = np.asarray(self.ds[self._latitude_name].data)
         rows = reversal_limits(reversal_rows(lat, delta, lat_bounds, hemisphere, ghgs2 is not None), ghgs, ghgn, ghgs2)
-        step_dims = tuple(d for d in dims if d not in (self._latitude_name, self._longitude_name))
-        ny, nx = da.shape[dims.index(self._latitude_name)], da.shape[dims.index(self._longitude_name)]
-        step_shape = tuple(da.shape[dims.index(d)] for d in step_dims)
-        steps = int(np.prod(step_shape)) if step_dims else 1
         trk = _tracker()
-        resident = chunk_steps is None and step_dims == (self._time_name,)
-        logger.info('Calculating gradient reversal of {} on {} of {} rows...'.format(variable, int(np.count_nonzero(rows["eq"] >= 0)), ny))
-        if chunk_steps is not None and step_dims:
-            dtype = np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
-            res = trk.reversal_cb(self._step_reader(da, dims, step_dims), (steps, ny, nx), dtype, rows, mask=stat == 'mask', chunk_steps=int(chunk_steps))
+        logger.info('Calculating gradient reversal of {} on {} of {} rows...'.format(variable, int(np.count_nonzero(rows["eq"] >= 0)), view.shape[1]))
+        if streamed:
+            res = trk.reversal_cb(view.reader(), view.shape, _producer_dtype(da.dtype), rows, mask=stat == 'mask', chunk_steps=int(chunk_steps))
         else:
-            sort = [dims.index(d) for d in step_dims + (self._latitude_name, self._longitude_name)]
-            arr = np.asarray(da.data).transpose(sort).reshape((steps, ny, nx))
+            arr = view.slab()
             if arr.dtype.kind != "f":
                 arr = arr.astype(np.float64)
             res = trk.reversal(arr, rows, mask=stat == 'mask', keep_resident=resident)
         if resident:
             res.flags.writeable = False                      # (its twin stays in HBM for run_contrack: see _fingerprint)
-        lead = step_dims + (self._latitude_name, self._longitude_name)
-        out = res.reshape(step_shape + (ny, nx)).transpose([lead.index(d) for d in dims])
+        out = view.restore(res, dims)
         units = da.attrs.get('units')
         attrs = {'units': '1' if stat == 'mask' else '{} / degree'.format(units) if units else 'degree-1',
                  'long_name': da.attrs.get('long_name', variable) + (' gradient reversal mask' if stat == 'mask' else ' reversed equatorward gradient'),
@@ -1438,12 +1460,6 @@ class contrack(object):
         uniq, ids = np.unique(vals, return_inverse=True)
         return ids.astype(np.int32), uniq
 
-    def _slab_tll(self, variable):
-        da = self.ds[variable]
-        dims = tuple(da.dims)
-        sort = [dims.index(d) for d in (self._time_name, self._latitude_name, self._longitude_name)]
-        return np.asarray(da.data).transpose(sort), dims, sort
-
     def _wrap(self, like, data, dims, coords=None, attrs=None, name=None):
         """a labelled array of the same class as `like` (xarray.DataArray, or whatever duck-typed dataset is wrapped)"""
         try:                                         # (the climatology keeps the variable's name, as xarray's groupby().mean() does)
@@ -1459,7 +1475,7 @@ class contrack(object):
         start indices) do not change a climatology.  chunk_steps (extension): the variable is read slice by slice (`isel`) and
         passes through chunk-sized device buffers, once; the slab is never built on the host."""
         if segments is None and chunk_steps is None:
-            slab, dims, sort = self._slab_tll(variable)
+            slab = self._steps(self.ds[variable], (self._time_name,)).slab()
             ids, uniq = self._group_ids(groupby)
             if slab.dtype.kind != "f":
                 slab = slab.astype(np.float64)
@@ -1487,24 +1503,17 @@ class contrack(object):
         da = self.ds[variable]
         dims = tuple(da.dims)
         member, starts, T = self._segment_args(variable, da, dims, segments)
-        if member is not None:
-            M = da.shape[dims.index(member)]
-            if only is None:
-                ids = np.tile(ids, M)
-            if chunk_steps is not None:
-                return self._member_reader(da, dims, member, only) + (ids, starts, member)
-            sort4 = [dims.index(d) for d in (member, self._time_name, self._latitude_name, self._longitude_name)]
-            arr = np.asarray(da.data).transpose(sort4)
-            arr = arr.reshape((M * T,) + arr.shape[2:]) if only is None else arr[only]
-            slab = np.ascontiguousarray(arr, dtype=np.float32 if arr.dtype == np.float32 else np.float64)
-            return slab, slab.shape, slab.dtype, ids, starts, member
+        if member is not None and only is None:
+            ids = np.tile(ids, da.shape[dims.index(member)])
+        if member is None and chunk_steps is not None and len(dims) != 3:
+            raise ValueError("the variable {!r} must be 3-D (time, lat, lon in any order), it has dims {}".format(variable, dims))
+        view = self._steps(da, (member, self._time_name))
         if chunk_steps is not None:
-            if len(dims) != 3:
-                raise ValueError("the variable {!r} must be 3-D (time, lat, lon in any order), it has dims {}".format(variable, dims))
-            return self._time_reader(da, dims) + (ids, starts, None)
-        slab = self._slab_tll(variable)[0]
-        slab = np.ascontiguousarray(slab, dtype=np.float32 if slab.dtype == np.float32 else np.float64)
-        return slab, slab.shape, slab.dtype, ids, starts, None
+            shape = view.shape if only is None else (T,) + view.shape[1:]
+            return view.reader(only=only), shape, _producer_dtype(da.dtype), ids, starts, member
+        slab = view.slab(only)
+        slab = np.ascontiguousarray(slab, dtype=_producer_dtype(slab.dtype))
+        return slab, slab.shape, slab.dtype, ids, starts, member
 
     def calc_anom(self, variable, window=1, smooth=1, groupby='dayofyear', clim=None, segments=None, chunk_steps=None, pool=True):
         """adds the variable 'anom': departure of `variable` from its climatology (calc_clim, or the one given as `clim`:
@@ -1522,7 +1531,8 @@ class contrack(object):
         self._ensure_set_up()
         ids, uniq = self._group_ids(groupby)
         if segments is None and chunk_steps is None:
-            slab, dims, sort = self._slab_tll(variable)
+            view = self._steps(self.ds[variable], (self._time_name,))
+            slab = view.slab()
             if slab.dtype.kind != "f":
                 slab = slab.astype(np.float64)
         clim_arr = None
@@ -1562,8 +1572,7 @@ class contrack(object):
         else:
             anom, _ = _tracker().anomalies(slab, ids, len(uniq), window=window, smooth=smooth, clim=clim_arr, keep_resident=True)
         anom.flags.writeable = False                         # (its twin stays in HBM for run_contrack: see _fingerprint)
-        out = anom.transpose(np.argsort(sort))
-        self.ds['anom'] = (dims, out, attrs)
+        self.ds['anom'] = (view.dims, view.restore(anom, view.dims), attrs)
         # (fingerprint of the host twin, identity of the slab in HBM: another instance's calc_anom on the shared handle changes
         # the second and this instance's run_contrack goes back to its own host array)
         self._anom_resident = (_fingerprint(np.asarray(self.ds['anom'].data)), _tracker().resident_generation())
@@ -1593,11 +1602,7 @@ class contrack(object):
         if segments is not None:
             attrs['history'] += ', segments = {} ({}){}'.format(segments if isinstance(segments, str) else 'starts', 1 if starts is None else len(starts),
                                                                '' if member is None or pool else ', climatology per member')
-        if member is not None:
-            sort4 = [dims.index(d) for d in (member, self._time_name, self._latitude_name, self._longitude_name)]
-            return anom.reshape((self.ds[variable].shape[dims.index(member)], -1) + anom.shape[1:]).transpose(np.argsort(sort4))
-        sort = [dims.index(d) for d in (self._time_name, self._latitude_name, self._longitude_name)]
-        return anom.transpose(np.argsort(sort))
+        return self._steps(self.ds[variable], (member, self._time_name)).restore(anom, dims)
 
     def _resident_for(self, variable, arr, shape, is_f64, name='anom'):
         """True if `variable` is the field to track this instance left in HBM -- `name`: 'anom' for every consumer of calc_anom's
@@ -1610,20 +1615,29 @@ class contrack(object):
         return res[0] == _fingerprint(np.asarray(arr)) and res[1] == trk.resident_generation() and \
             trk.resident_anom() == (shape[0], shape[1], shape[2], bool(is_f64))
 
+    def _resident_field(self, variable, shape, is_f64):
+        """_resident_for as the consumers of calc_anom's slab ask it: is `variable` 'anom', its (steps, lat, lon) twin still in HBM?"""
+        return self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, shape, is_f64)
+
+    def _band_rows(self, lat_bounds, default_all=True):
+        """(y0, y1, bounds): the rows y0 <= y < y1 whose latitude lies inside lat_bounds (both ends included), which must be
+        neighbours; lat_bounds None with default_all: every row, bounds then the coordinate's own extremes"""
+        lat = np.asarray(self.ds[self._latitude_name].data, dtype=np.float64)
+        bounds = (lat.min(), lat.max()) if lat_bounds is None and default_all else lat_bounds
+        rows = np.nonzero((lat >= min(bounds)) & (lat <= max(bounds)))[0]
+        if len(rows) == 0 or not np.array_equal(rows, np.arange(rows[0], rows[-1] + 1)):
+            raise ValueError("latitude band {} selects no contiguous rows".format(lat_bounds))
+        return int(rows[0]), int(rows[-1]) + 1, bounds
+
     def _slab_pooled(self, variable, segments):
         """((steps, lat, lon) slab, members) for the percentile entries: the variable itself (segments None), or a 4-D variable with
         the member dimension `segments` flattened to (member * time, lat, lon) -- pooling over time is indifferent to the breaks"""
-        if segments is None:
-            return self._slab_tll(variable)[0], 1
-        if not isinstance(segments, str) or segments == 'gaps':
+        if segments is not None and (not isinstance(segments, str) or segments == 'gaps'):
             raise ValueError("segments={!r}: the percentile entries take the name of a member dimension (breaks along time do not "
                              "change a percentile over time)".format(segments))
         da = self.ds[variable]
-        dims = tuple(da.dims)
-        member = self._segment_args(variable, da, dims, segments)[0]
-        sort4 = [dims.index(d) for d in (member, self._time_name, self._latitude_name, self._longitude_name)]
-        arr = np.asarray(da.data).transpose(sort4)
-        return arr.reshape((-1,) + arr.shape[2:]), arr.shape[0]
+        view = self._steps(da, (self._segment_args(variable, da, tuple(da.dims), segments)[0], self._time_name))
+        return view.slab(), 1 if segments is None else view.step_shape[0]
 
     def percentile_threshold(self, variable='anom', q=0.90, lat_bounds=(50, 80), groupby=None, window=1, segments=None):
         """the more objective threshold of the reference's README (README.rst:150-151):
@@ -1641,19 +1655,16 @@ class contrack(object):
             _check_percentile_args(q, window)
         self._ensure_set_up()
         slab, M = self._slab_pooled(variable, segments)
-        lat = np.asarray(self.ds[self._latitude_name].data, dtype=np.float64)
-        rows = np.nonzero((lat >= min(lat_bounds)) & (lat <= max(lat_bounds)))[0]
-        if len(rows) == 0 or not np.array_equal(rows, np.arange(rows[0], rows[-1] + 1)):
-            raise ValueError("latitude band {} selects no contiguous rows".format(lat_bounds))
+        y0, y1, _ = self._band_rows(lat_bounds, default_all=False)
         if slab.dtype.kind != "f":
             slab = slab.astype(np.float64)
         ids, uniq = (None, None) if groupby is None else self._group_ids(groupby)
         if ids is not None and M > 1:
             ids = np.tile(ids, M)
-        resident = segments is None and self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, slab.shape, slab.dtype != np.float32)
+        resident = segments is None and self._resident_field(variable, slab.shape, slab.dtype != np.float32)
         if groupby is None:
-            return _tracker().percentile(None if resident else slab, int(rows[0]), int(rows[-1]) + 1, q)
-        vals = _tracker().percentile_groups(None if resident else slab, int(rows[0]), int(rows[-1]) + 1, ids, len(uniq), q, int(window))
+            return _tracker().percentile(None if resident else slab, y0, y1, q)
+        vals = _tracker().percentile_groups(None if resident else slab, y0, y1, ids, len(uniq), q, int(window))
         da = self.ds[variable]
         attrs = {'long_name': '{} percentile threshold'.format(variable), 'q': float(q), 'window': int(window),
                  'lat_bounds': (float(min(lat_bounds)), float(max(lat_bounds))),
@@ -1673,18 +1684,13 @@ class contrack(object):
         _check_percentile_args(q, window)
         self._ensure_set_up()
         slab, M = self._slab_pooled(variable, segments)
-        lat = np.asarray(self.ds[self._latitude_name].data, dtype=np.float64)
-        bounds = (lat.min(), lat.max()) if lat_bounds is None else lat_bounds
-        rows = np.nonzero((lat >= min(bounds)) & (lat <= max(bounds)))[0]
-        if len(rows) == 0 or not np.array_equal(rows, np.arange(rows[0], rows[-1] + 1)):
-            raise ValueError("latitude band {} selects no contiguous rows".format(lat_bounds))
+        y0, y1, bounds = self._band_rows(lat_bounds)
         if slab.dtype.kind != "f":
             slab = slab.astype(np.float64)
         ids, uniq = self._group_ids(groupby)
         if M > 1:
             ids = np.tile(ids, M)
-        resident = segments is None and self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, slab.shape, slab.dtype != np.float32)
-        y0, y1 = int(rows[0]), int(rows[-1]) + 1
+        resident = segments is None and self._resident_field(variable, slab.shape, slab.dtype != np.float32)
         band = _tracker().percentile_field(None if resident else slab, y0, y1, ids, len(uniq), q, int(window))
         vals = np.full((len(uniq),) + slab.shape[1:], np.nan)
         vals[:, y0:y1] = band
@@ -1707,11 +1713,7 @@ class contrack(object):
         _check_std_args(window, ddof)
         self._ensure_set_up()
         slab, M = self._slab_pooled(variable, segments)
-        lat = np.asarray(self.ds[self._latitude_name].data, dtype=np.float64)
-        bounds = (lat.min(), lat.max()) if lat_bounds is None else lat_bounds
-        rows = np.nonzero((lat >= min(bounds)) & (lat <= max(bounds)))[0]
-        if len(rows) == 0 or not np.array_equal(rows, np.arange(rows[0], rows[-1] + 1)):
-            raise ValueError("latitude band {} selects no contiguous rows".format(lat_bounds))
+        y0, y1, bounds = self._band_rows(lat_bounds)
         if slab.dtype.kind != "f":
             slab = slab.astype(np.float64)
         if groupby is None:
@@ -1722,8 +1724,7 @@ class contrack(object):
         _check_std_args(window, ddof, G, skipna)
         if M > 1:
             ids = np.tile(ids, M)
-        resident = segments is None and self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, slab.shape, slab.dtype != np.float32)
-        y0, y1 = int(rows[0]), int(rows[-1]) + 1
+        resident = segments is None and self._resident_field(variable, slab.shape, slab.dtype != np.float32)
         band = _tracker().std_field(None if resident else slab, y0, y1, ids, G, int(window), int(ddof), bool(skipna))
         return band, (y0, y1), uniq, slab.shape, (float(min(bounds)), float(max(bounds)))
 
@@ -1873,43 +1874,6 @@ class contrack(object):
             starts = None if segments is None else segment_starts(segments, T)
         return member, starts, T
 
-    def _time_reader(self, da, dims, integer=False):
-        """(reader(t0, nt, out), (T, ny, nx), dtype) of a 3-D variable read slice by slice along time (isel where there is one).
-        integer: a flag variable -- int32 buffers, every slice checked on its way in (_int32_chunk)"""
-        tname = self._time_name
-        sort = [dims.index(d) for d in (tname, self._latitude_name, self._longitude_name)]
-        shape = tuple(da.shape[i] for i in sort)
-        dtype = np.dtype(np.int32) if integer else np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
-        narrow = _int32_chunk if integer else (lambda a: a)
-
-        def reader(t0, nt, out):
-            part = da.isel(**{tname: slice(t0, t0 + nt)}) if hasattr(da, "isel") else None
-            arr = np.asarray(part.data if part is not None else np.asarray(da.data).take(range(t0, t0 + nt), axis=dims.index(tname)))
-            out[...] = narrow(arr).transpose(sort)
-        return reader, shape, dtype
-
-    def _member_reader(self, da, dims, member, only=None, integer=False):
-        """(reader, (M * T, ny, nx), dtype) of a 4-D variable: flat step m * T + t of the (M * T, lat, lon) series is step t of member
-        m, read as isel(member=m, time=slice) -- a chunk that spans two members in two pieces.  only=m: that member alone, (T, ny, nx).
-        integer: as in _time_reader."""
-        tname = self._time_name
-        M, T = da.shape[dims.index(member)], da.shape[dims.index(tname)]
-        dims3 = tuple(d for d in dims if d != member)                             # what isel(member=m) leaves
-        sort3 = [dims3.index(d) for d in (tname, self._latitude_name, self._longitude_name)]
-        shape = ((M if only is None else 1) * T,) + tuple(da.shape[dims.index(d)] for d in (self._latitude_name, self._longitude_name))
-        dtype = np.dtype(np.int32) if integer else np.dtype(np.float32) if np.dtype(da.dtype) == np.float32 else np.dtype(np.float64)
-        narrow = _int32_chunk if integer else (lambda a: a)
-
-        def reader(t0, nt, out):
-            done = 0
-            while done < nt:
-                m, t = divmod(t0 + done, T)
-                n = min(nt - done, T - t)
-                part = da.isel(**{member: m if only is None else only, tname: slice(t, t + n)})
-                out[done:done + n] = narrow(np.asarray(part.data)).transpose(sort3)
-                done += n
-        return reader, shape, dtype
-
     def run_contrack(self, variable, threshold, gorl, overlap, persistence, twosided=True, chunk_steps=None, segments=None):
         """Spatial and temporal tracking of closed contours; adds the integer variable 'flag' to the dataset.
 
@@ -1946,38 +1910,41 @@ class contrack(object):
         logger.info("Find individual contours...")
         if gorl not in _native.CMP_OPS:
             raise ValueError(_native.GORL_ERRMSG)
-        sort = [dims.index(d) for d in (self._time_name, self._latitude_name, self._longitude_name)]
+        # a member dimension is flattened to steps m * T + t, each member one segment; the threshold of a time step applies to every member
+        view = self._steps(da, (member, self._time_name))
         lat = self.ds[self._latitude_name].data
         wrow = row_weights(lat, self._dlat, self._dlon)
         trk = _tracker()
+
+        def thresholds(dtype):
+            if member is not None:
+                return self._member_threshold_args(threshold, member, view.step_shape[0], T, dtype)
+            return self._threshold_args(threshold, da.shape, [dims.index(d) for d in (self._time_name,) + view.tail], T, dtype)
         # threshold, 2-D labelling, overlap filter, 3-D tracking and persistence are ONE call into the library (the reference logs
         # them as it goes through them, contrack.py:646-772)
         logger.info("Apply overlap...")
         logger.info("Apply persistence...")
-        if chunk_steps is not None and member is not None:
-            # every member read slice by slice: flat step m * T + t is isel(member=m, time=t)
-            flag, n_tracked = self._run_members_streaming(trk, da, dims, member, starts, threshold, gorl, wrow, overlap, persistence, twosided,
-                                                          int(chunk_steps))
-            slab = None
-        elif chunk_steps is not None:
-            # the variable is read slice by slice and passes through chunk-sized device buffers
-            flag, n_tracked = self._run_streaming(trk, da, dims, sort, threshold, gorl, wrow, overlap, persistence, twosided, int(chunk_steps),
-                                                  starts)
-            slab = None
-        elif member is not None:
-            # (member, time, lat, lon) flattened to (member * time, lat, lon): each member is one segment
-            flag, n_tracked, slab = self._run_members(trk, da, dims, member, starts, threshold, gorl, wrow, overlap, persistence, twosided)
+        if chunk_steps is not None:
+            # the variable is read slice by slice when its turn comes and passes through chunk-sized device
+            # buffers -- a chunk that spans two members in two pieces; the flattened slab exists nowhere on the host
+            slab, reader, dtype = None, view.reader(), _producer_dtype(da.dtype)
+            thr, field = thresholds(dtype)
+            seg = {} if starts is None else {"segments": starts}        # (no segments: the call as it has always been made)
+            call = lambda t: trk.track_stream(reader, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, shape=view.shape, dtype=dtype,
+                                              chunk_steps=int(chunk_steps), **seg)
+            flag, n_tracked = call(thr) if field is None else _track_field(trk, field[0], field[1], call)
         else:
-            slab = np.asarray(da.data).transpose(sort)
-            thr, field = self._threshold_args(threshold, da.shape, sort, slab.shape[0], slab.dtype)
-            if self._resident_for(variable, da.data, slab.shape, slab.dtype != np.float32, name=getattr(self, "_anom_resident_name", 'anom')):
+            slab = view.slab()
+            if member is not None:                           # (without members the variable's own type decides a Python threshold's)
+                slab = np.ascontiguousarray(slab, dtype=_producer_dtype(slab.dtype))
+            thr, field = thresholds(slab.dtype)
+            if member is None and self._resident_for(variable, da.data, slab.shape, slab.dtype != np.float32,
+                                                     name=getattr(self, "_anom_resident_name", 'anom')):
                 # calc_anom (or calc_reversal) left this very slab in HBM: no host-to-device copy
                 call = lambda t: trk.track_resident(t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided)
-            elif slab.dtype == np.float32:
-                call = lambda t: trk.track(np.ascontiguousarray(slab), t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided)
             else:
-                call = lambda t: trk.track(np.ascontiguousarray(slab, dtype=np.float64), t, _native.CMP_OPS[gorl], wrow, overlap,
-                                           persistence, twosided, f64=True)
+                host = np.ascontiguousarray(slab, dtype=_producer_dtype(slab.dtype))
+                call = lambda t: trk.track(host, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, f64=host.dtype == np.float64)
             flag, n_tracked = _track_segments(trk, starts, lambda: call(thr) if field is None else _track_field(trk, field[0], field[1], call))
         if slab is not None and slab.nbytes > (4 << 30):
             trk.release_io()               # a big one-off slab: do not keep 2 x its size allocated on the GPU
@@ -1994,12 +1961,7 @@ class contrack(object):
                  'reference': 'https://github.com/steidani/ConTrack'}
         if segments is not None:
             attrs['history'] += ', segments = {} ({})'.format(segments if isinstance(segments, str) else 'starts', nseg)
-        if member is not None:
-            sort4 = [dims.index(d) for d in (member, self._time_name, self._latitude_name, self._longitude_name)]
-            out = flag.reshape((len(starts), T) + flag.shape[1:]).transpose(np.argsort(sort4))
-        else:
-            out = flag.transpose(np.argsort(sort))
-        self.ds['flag'] = (dims, out, attrs)
+        self.ds['flag'] = (dims, view.restore(flag, dims), attrs)
         st = _tracker().stats()
         if st.get("off_fused_path_reason", 0):
             # not an error: the result is the same, the call was slower (exact areas / host resolver)
@@ -2008,19 +1970,6 @@ class contrack(object):
                    4: "{} overlap decisions on rounding boundaries were re-evaluated with numpy-order sums".format(st.get("exact_fixups", 0))}
             logger.info("run_contrack left the fused device path: " + why.get(st["off_fused_path_reason"], "host resolver"))
         logger.info("Running contrack... DONE\n{} contours tracked".format(n_tracked))
-
-    def _run_members(self, trk, da, dims, member, starts, threshold, gorl, wrow, overlap, persistence, twosided):
-        """run_contrack over an extra dimension: the variable transposed to (member, time, lat, lon) and flattened in time, one
-        segment per member; the threshold of each time step applies to every member.  Returns (flag (M*T, ny, nx), n, slab)."""
-        sort4 = [dims.index(d) for d in (member, self._time_name, self._latitude_name, self._longitude_name)]
-        arr = np.asarray(da.data).transpose(sort4)
-        M, T = arr.shape[0], arr.shape[1]
-        slab = np.ascontiguousarray(arr.reshape((M * T,) + arr.shape[2:]), dtype=np.float32 if arr.dtype == np.float32 else np.float64)
-        thr, field = self._member_threshold_args(threshold, member, M, T, slab.dtype)
-        f64 = slab.dtype == np.float64
-        call = lambda t: trk.track(slab, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, f64=f64)
-        flag, n = _track_segments(trk, starts, lambda: call(thr) if field is None else _track_field(trk, field[0], field[1], call))
-        return flag, n, slab
 
     def _member_threshold_args(self, threshold, member, M, T, dtype):
         """(thr, field) of a call over M members of T steps each: the threshold of a time step applies to every member"""
@@ -2033,26 +1982,6 @@ class contrack(object):
             raise ValueError("segments={!r}: a numpy threshold field cannot be combined with a member dimension; give a number, a "
                              "per-time vector or a 'dayofyear' DataArray".format(member))
         return np.tile(self._thresholds_per_step(threshold, T, dtype), M), None
-
-    def _run_members_streaming(self, trk, da, dims, member, starts, threshold, gorl, wrow, overlap, persistence, twosided, chunk_steps):
-        """run_contrack over an extra dimension with the variable read slice by slice: flat step m * T + t of the (M * T, lat, lon)
-        series is step t of member m, read as isel(member=m, time=slice) -- a chunk that spans two members in two pieces; the
-        flattened slab exists nowhere on the host.  Returns (flag (M*T, ny, nx), n)."""
-        M, T = da.shape[dims.index(member)], da.shape[dims.index(self._time_name)]
-        reader, shape, dtype = self._member_reader(da, dims, member)
-        thr, field = self._member_threshold_args(threshold, member, M, T, dtype)
-        call = lambda t: trk.track_stream(reader, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, shape=shape, dtype=dtype,
-                                          chunk_steps=chunk_steps, segments=starts)
-        return call(thr) if field is None else _track_field(trk, field[0], field[1], call)
-
-    def _run_streaming(self, trk, da, dims, sort, threshold, gorl, wrow, overlap, persistence, twosided, chunk_steps, starts=None):
-        """run_contrack with the variable read slice by slice; starts: segment breaks of the call"""
-        reader, shape, dtype = self._time_reader(da, dims)                         # shape: (time, lat, lon)
-        thr, field = self._threshold_args(threshold, da.shape, sort, shape[0], dtype)
-        seg = {} if starts is None else {"segments": starts}        # (no segments: the call as it has always been made)
-        call = lambda t: trk.track_stream(reader, t, _native.CMP_OPS[gorl], wrow, overlap, persistence, twosided, shape=shape, dtype=dtype,
-                                          chunk_steps=chunk_steps, **seg)
-        return call(thr) if field is None else _track_field(trk, field[0], field[1], call)
 
     # ---- blocking frequency (README.rst:159-160), consumer of `flag` ------------------------------------------------------
     def _consumer_dims(self, name, what="flag variable"):
@@ -2073,17 +2002,9 @@ class contrack(object):
             return np.arange(size)
         return vals if vals.shape == (size,) else np.arange(size)
 
-    def _flat_slab(self, da, dims, member):
-        """the variable as (time, lat, lon), or with a member dimension as (member * time, lat, lon): flat step m * T + t"""
-        names = (self._time_name, self._latitude_name, self._longitude_name)
-        if member is None:
-            return np.asarray(da.data).transpose([dims.index(d) for d in names])
-        arr = np.asarray(da.data).transpose([dims.index(d) for d in (member,) + names])
-        return arr.reshape((-1,) + arr.shape[2:])
-
     @staticmethod
     def _group_plan(ids, uniq, T, M=None, pool=False):
-        """the groups of a map over the flat slab (_flat_slab) as the library takes them: (group, G, per_member).  ids: one group id
+        """the groups of a map over the flat slab (_Steps) as the library takes them: (group, G, per_member).  ids: one group id
         per time step (uniq: the groups' values) or None; M: the size of the member dimension, None without one.  Members that are
         not pooled keep maps of their own: the library sees group m * G + g at flat step m * T + t.  group None: one group."""
         G = 1 if ids is None else len(uniq)
@@ -2139,13 +2060,9 @@ class contrack(object):
         T = da.shape[dims.index(self._time_name)]
         M = None if member is None else da.shape[dims.index(member)]
         group, G, per_member = self._group_plan(ids, uniq, T, M, pool)
-        if chunk_steps is None:
-            source, shape = self._flat_slab(da, dims, member), None
-        elif member is None:
-            source, shape, _ = self._time_reader(da, dims, integer=True)
-        else:
-            source, shape, _ = self._member_reader(da, dims, member, integer=True)
-        counts = frequency_numpy(source, group, above=above, percent=False, chunk_steps=chunk_steps, shape=shape)
+        view = self._steps(da, (member, self._time_name))
+        source = view.slab() if chunk_steps is None else view.reader(integer=True)
+        counts = frequency_numpy(source, group, above=above, percent=False, chunk_steps=chunk_steps, shape=view.shape)
         counts = counts.reshape((-1,) + counts.shape[-2:])
         n = np.bincount(ids, minlength=G) if ids is not None else np.array([T])
         n = np.tile(n, M) if per_member else n * (M or 1)        # a group's size inside one member / over all of them
@@ -2184,13 +2101,9 @@ class contrack(object):
         if member is not None:                                   # every member a segment of its own, with the breaks inside it
             inner = np.zeros(1, dtype=np.int64) if starts is None else starts
             starts = (np.arange(M, dtype=np.int64)[:, None] * T + inner[None, :]).reshape(-1)
-        if chunk_steps is None:
-            source, shape = self._flat_slab(da, dims, member), None
-        elif member is None:
-            source, shape, _ = self._time_reader(da, dims, integer=True)
-        else:
-            source, shape, _ = self._member_reader(da, dims, member, integer=True)
-        maps = spells_numpy(source, group, above=above, by_id=by_id, min_duration=min_duration, segments=starts, chunk_steps=chunk_steps, shape=shape)
+        view = self._steps(da, (member, self._time_name))
+        source = view.slab() if chunk_steps is None else view.reader(integer=True)
+        maps = spells_numpy(source, group, above=above, by_id=by_id, min_duration=min_duration, segments=starts, chunk_steps=chunk_steps, shape=view.shape)
         maps = [a.reshape((-1,) + a.shape[-2:]) for a in maps]
         maps.append(spell_duration(maps[1], maps[0]))
         out_dims, coords, shaped = self._map_layout(dims, member, pool, groupby, uniq, M, G)
@@ -2232,19 +2145,14 @@ class contrack(object):
         M = None if member is None else fda.shape[dims.index(member)]
         group, G, per_member = self._group_plan(ids, uniq, T, M, pool)
         vtype = _native._field_dtype(vda.dtype)
+        fview, vview = self._steps(fda, (member, self._time_name)), self._steps(vda, (member, self._time_name))
         if chunk_steps is None:
-            flags, field = self._flat_slab(fda, dims, member), self._flat_slab(vda, vdims, member)
-            field = field.astype(vtype, copy=False)
-            resident = self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, field.shape, vtype == np.float64)
-            s, n = composite_numpy(flags, None if resident else field, group, above=above, skipna=skipna, dtype=vtype)
+            field = vview.slab().astype(vtype, copy=False)
+            resident = self._resident_field(variable, field.shape, vtype == np.float64)
+            s, n = composite_numpy(fview.slab(), None if resident else field, group, above=above, skipna=skipna, dtype=vtype)
         else:
-            if member is None:
-                fread, shape, _ = self._time_reader(fda, dims, integer=True)
-                vread = self._time_reader(vda, vdims)[0]
-            else:
-                fread, shape, _ = self._member_reader(fda, dims, member, integer=True)
-                vread = self._member_reader(vda, vdims, member)[0]
-            s, n = composite_numpy(fread, vread, group, above=above, skipna=skipna, chunk_steps=chunk_steps, shape=shape, dtype=vtype)
+            s, n = composite_numpy(fview.reader(integer=True), vview.reader(), group, above=above, skipna=skipna, chunk_steps=chunk_steps, shape=fview.shape,
+                                   dtype=vtype)
         s, n = s.reshape((-1,) + s.shape[-2:]), n.reshape((-1,) + n.shape[-2:])
         out = composite_mean(s, n) if stat == 'mean' else s
         out_dims, coords, shaped = self._map_layout(dims, member, pool, groupby, uniq, M, G)
@@ -2269,12 +2177,8 @@ class contrack(object):
         dims, member = self._consumer_dims(flag)
         if np.dtype(fda.dtype).kind not in "iub":
             raise ValueError("flag variable {!r} is not an integer field".format(flag))
-        lat = np.asarray(self.ds[self._latitude_name].data, dtype=np.float64)
-        bounds = (lat.min(), lat.max()) if lat_bounds is None else lat_bounds
-        rows = np.nonzero((lat >= min(bounds)) & (lat <= max(bounds)))[0]
-        if len(rows) == 0 or not np.array_equal(rows, np.arange(rows[0], rows[-1] + 1)):
-            raise ValueError("latitude band {} selects no contiguous rows".format(lat_bounds))
-        y01 = (int(rows[0]), int(rows[-1]) + 1)
+        y0, y1, bounds = self._band_rows(lat_bounds)
+        y01 = (y0, y1)
         weights = row_weights(np.asarray(self.ds[self._latitude_name].data), self._dlat, self._dlon).astype(np.float64)     # contrack.py:846-848
         T = fda.shape[dims.index(self._time_name)]
         M = None if member is None else fda.shape[dims.index(member)]
@@ -2285,23 +2189,19 @@ class contrack(object):
             if sorted(vdims) != sorted(dims) or any(vda.shape[vdims.index(d)] != fda.shape[dims.index(d)] for d in dims):
                 raise ValueError("the variable {!r} has dims {}, the flag variable {!r} has {}: they must be the same".format(variable, vdims, flag, dims))
             vtype = _native._field_dtype(vda.dtype)
+        fview = self._steps(fda, (member, self._time_name))
+        vview = None if vda is None else self._steps(vda, (member, self._time_name))
         if chunk_steps is None:
-            flags = self._flat_slab(fda, dims, member)
             field, gen = None, None
             if vda is not None:
-                field = self._flat_slab(vda, vdims, member).astype(vtype, copy=False)
+                field = vview.slab().astype(vtype, copy=False)
                 # (the anomaly slab calc_anom left in HBM: only the flags cross PCIe)
-                if self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, field.shape, vtype == np.float64):
+                if self._resident_field(variable, field.shape, vtype == np.float64):
                     field, gen = None, self._anom_resident[1]
-            tables = band_numpy(flags, y01, weights, field, sectors, columns, above=above, dtype=vtype, resident_gen=gen)
+            tables = band_numpy(fview.slab(), y01, weights, field, sectors, columns, above=above, dtype=vtype, resident_gen=gen)
         else:
-            if member is None:
-                fread, shape, _ = self._time_reader(fda, dims, integer=True)
-                vread = None if vda is None else self._time_reader(vda, vdims)[0]
-            else:
-                fread, shape, _ = self._member_reader(fda, dims, member, integer=True)
-                vread = None if vda is None else self._member_reader(vda, vdims, member)[0]
-            tables = band_numpy(fread, y01, weights, vread, sectors, columns, above=above, chunk_steps=chunk_steps, shape=shape, dtype=vtype)
+            tables = band_numpy(fview.reader(integer=True), y01, weights, None if vda is None else vview.reader(), sectors, columns, above=above,
+                                chunk_steps=chunk_steps, shape=fview.shape, dtype=vtype)
         return tables, dims, member, M, T, y01, weights, (float(min(bounds)), float(max(bounds))), fda
 
     def _band_layout(self, dims, member, M, T, last, last_values):
@@ -2446,23 +2346,19 @@ class contrack(object):
         T = fda.shape[fdims.index(self._time_name)]
         period = None if member is None else T
         vtype = np.dtype(np.float64) if np.dtype(vda.dtype) == np.float64 else np.dtype(np.float32)
+        fview, vview = self._steps(fda, (member, self._time_name)), self._steps(vda, (member, self._time_name))
         if chunk_steps is None:
-            flags, field = self._flat_slab(fda, fdims, member), self._flat_slab(vda, vdims, member)
+            field = vview.slab()
             if field.dtype != np.float64:
                 field = field.astype(np.float32, copy=False)
             # (the anomaly slab calc_anom left in HBM: only the flags cross PCIe)
-            resident = self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, field.shape, field.dtype == np.float64)
-            cols = lifecycle_numpy(flags, None if resident else field, wrow, lat, lon, self._time_labels(), dtype=field.dtype, period=period, indices=indices)
-        else:
-            if member is None:
-                fread, shape, _ = self._time_reader(fda, fdims, integer=True)
-                vread = self._time_reader(vda, vdims)[0]
-            else:
-                fread, shape, _ = self._member_reader(fda, fdims, member, integer=True)
-                vread = self._member_reader(vda, vdims, member)[0]
-            # (a variable of any other type than float64 becomes float32 in the copy into the chunk buffer, as in the resident call)
-            cols = lifecycle_numpy(fread, vread, wrow, lat, lon, self._time_labels(), chunk_steps=chunk_steps, shape=shape, dtype=vtype, period=period,
+            resident = self._resident_field(variable, field.shape, field.dtype == np.float64)
+            cols = lifecycle_numpy(fview.slab(), None if resident else field, wrow, lat, lon, self._time_labels(), dtype=field.dtype, period=period,
                                    indices=indices)
+        else:
+            # (a variable of any other type than float64 becomes float32 in the copy into the chunk buffer, as in the resident call)
+            cols = lifecycle_numpy(fview.reader(integer=True), vview.reader(), wrow, lat, lon, self._time_labels(), chunk_steps=chunk_steps,
+                                   shape=fview.shape, dtype=vtype, period=period, indices=indices)
         columns = ['Flag', 'Date', 'Longitude', 'Latitude', 'Intensity', 'Size']
         if member is not None:
             cols[member] = self._dim_values(member, fda.shape[fdims.index(member)])[cols.pop("Member")]
@@ -2538,13 +2434,13 @@ class contrack(object):
         dlat, dlon = (float(np.atleast_1d(d)[0]) for d in (self._dlat, self._dlon))
         half = (int(round(float(half_width[0]) / dlat)), int(round(float(half_width[1]) / dlon)))
         vtype = _native._field_dtype(vda.dtype)
+        view = self._steps(vda, (member, self._time_name))
         if chunk_steps is None:
-            field = self._flat_slab(vda, dims, member).astype(vtype, copy=False)
-            resident = self._resident_for(variable, self.ds['anom'].data if variable == 'anom' else None, field.shape, vtype == np.float64)
+            field = view.slab().astype(vtype, copy=False)
+            resident = self._resident_field(variable, field.shape, vtype == np.float64)
             s, n = centred_numpy(None if resident else field, t, row, col, bins, nb, half, wrap=wrap, skipna=skipna, shape=field.shape, dtype=vtype)
         else:
-            vread, shape, _ = self._time_reader(vda, dims) if member is None else self._member_reader(vda, dims, member)
-            s, n = centred_numpy(vread, t, row, col, bins, nb, half, wrap=wrap, skipna=skipna, chunk_steps=chunk_steps, shape=shape, dtype=vtype)
+            s, n = centred_numpy(view.reader(), t, row, col, bins, nb, half, wrap=wrap, skipna=skipna, chunk_steps=chunk_steps, shape=view.shape, dtype=vtype)
         out = composite_mean(s, n) if stat == 'mean' else s
         bdim = by if isinstance(by, str) else 'bin'
         out_dims = (bdim, 'rel_' + self._latitude_name, 'rel_' + self._longitude_name)

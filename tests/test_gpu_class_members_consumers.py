@@ -166,16 +166,22 @@ def test_int64_flags_are_narrowed_chunk_by_chunk():
     big[2, 15, 3, 4] = 2 ** 31                                             # flat step 47: the last chunk
     c = dataset(CANON, flag_dtype=np.int64, flag=big)
     seen = []
-    inner = c._member_reader
+    inner = c._steps
 
-    def spying(da, dims, member, only=None, integer=False):
-        reader, shape, dtype = inner(da, dims, member, only, integer)
+    def spying(da, step_dims, level=None):                                 # every reader the class builds, through its view
+        view = inner(da, step_dims, level)
+        build = view.reader
 
-        def spy(t0, nt, out):
-            seen.append((integer, t0))
-            reader(t0, nt, out)
-        return spy, shape, dtype
-    c._member_reader = spying
+        def reader(integer=False, **kwargs):
+            read = build(integer=integer, **kwargs)
+
+            def spy(t0, nt, out):
+                seen.append((integer, t0))
+                read(t0, nt, out)
+            return spy
+        view.reader = reader
+        return view
+    c._steps = spying
     with pytest.raises(ValueError, match="flag ids beyond int32"):
         c.run_lifecycle("flag", "z", chunk_steps=5)
     assert max(t0 for integer, t0 in seen if integer) == 45                  # raised from the chunk that holds it

@@ -114,6 +114,25 @@ def test_member_dimension_and_chunks(dims, monkeypatch):
     assert _tracker().resident_generation() == g                                # streamed calls keep nothing on the device
 
 
+def test_two_outer_step_dims_in_chunks():
+    """(run, member, time, lat, lon) = (2, 3, 4, 5, 8): 24 steps behind two outer step dims; chunks of 5 steps cross the runs of 4"""
+    lat = np.arange(30.0, 91.0, 15.0)
+    rng = np.random.default_rng(7)
+    z = ((5600.0 - 900.0 * np.sin(np.deg2rad(lat)) ** 2)[:, None] + 150.0 * rng.normal(0.0, 1.0, (2, 3, 4, 5, 8))).astype(np.float32)
+    days = (np.datetime64("2000-12-20") + np.arange(4)).astype("datetime64[ns]")
+    ds = minixr.make_dataset(np.zeros((4, 5, 8), dtype=np.float32), lat.astype(np.float32), (np.arange(8) * 45.0).astype(np.float32), time=days, var="base")
+    ds['run'], ds['member'] = minixr.DataArray(np.arange(2), ("run",), attrs={}), minixr.DataArray(np.arange(3), ("member",), attrs={})
+    ds['z'] = minixr.DataArray(z, ("run", "member") + TLL, attrs={"units": "m", "long_name": "geopotential height"})
+    c = contrack(ds=ds)
+    c.set_up()
+    c.calc_reversal('z')
+    c.calc_reversal('z', chunk_steps=5, name='rev_cs')
+    whole = np.asarray(c.ds['reversal'].data)
+    assert tuple(c.ds['rev_cs'].dims) == ("run", "member") + TLL and whole.shape == z.shape
+    assert ru.same_bits(whole.reshape(24, 5, 8), ru.reversal(z.reshape(24, 5, 8), lat.astype(np.float32))) and whole.any()
+    assert ru.same_bits(np.asarray(c.ds['rev_cs'].data), whole)
+
+
 def spy(monkeypatch):
     """counts the tracker's calls by path"""
     seen = dict(resident=0, host=0)
