@@ -187,8 +187,12 @@ static int std_launch_tile(ctk_handle *h, const VT *x_dev, const StdArgs &sa, co
 {
     const PctlArgs &a = sa.a;
     const int64_t nband = a.nband();
-    // (a launch may ask for more than 64 KB of dynamic LDS only after this)
-    HIPCHK(hipFuncSetAttribute((const void *)k_std_field<VT, TILE, SKIPNA, NARROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_bytes));
+    // (a launch may ask for more than 64 KB of dynamic LDS only after this.  The attribute belongs to the function, that is to every
+    // handle and host thread of the process: it is always set to the one constant ctk_std_plan never exceeds, so the order in which
+    // two threads set it cannot matter)
+    static_assert(CTK_STD_LDS_BYTES <= 0x7fffffff, "the attribute is an int");
+    if (f.lds_bytes > CTK_STD_LDS_BYTES) return ctk_set_error(CTK_E_INTERNAL, "k_std_field: a plan of %lld bytes of LDS (at most %d)", (long long)f.lds_bytes, CTK_STD_LDS_BYTES);
+    HIPCHK(hipFuncSetAttribute((const void *)k_std_field<VT, TILE, SKIPNA, NARROW>, hipFuncAttributeMaxDynamicSharedMemorySize, CTK_STD_LDS_BYTES));
     k_std_field<VT, TILE, SKIPNA, NARROW><<<(unsigned)((nband + TILE - 1) / TILE), CTK_STD_THREADS, (size_t)f.lds_bytes, h->stream>>>(
         x_dev, a.npix(), a.p0(), nband, (int)a.T, first, plen, p.planes, p.window, sa.ddof, o_std, o_mean, o_n);
     return CTK_OK;

@@ -21,7 +21,12 @@ An operation (`Op`) is a family, its arguments, and the reference function of th
     lifecycle           life_util.numpy_rows for t / label / shift / area, life_util.numpy_exact_rows for the exact records of ALL rows
     band                band_util.band (area per step, columns, sectors; the resident forms on the anomaly slab of oracle/anom_port.py)
     centred             centred_util.centred (the reader form also answers for the chunks its reader was asked for)
+    reversal            reversal_util.from_table on reversal_util.field over the shape's latitudes (REV_GRID: active rows in both
+                        hemispheres, the first and the last row of the grid neither read nor written)
 Every comparison is exact (bits or integers); there is no tolerance in this module.
+
+The resident slab of the field to track has two producers, anomalies(keep) and reversal(keep): a consumer's `src` says which one made
+the slab it works on (by_reversal), and its reference is computed on that producer's reference output (resident_slab).
 
 `Op.io` is what the call asks of the shared buffers, computed from its arguments as the library computes it (bytes of io_in, io_out
 and of one pinned buffer per direction; 0: not touched).  `Op.needs` / `Op.gives` / `Op.drops` name the resident slabs ("anom",
@@ -29,6 +34,7 @@ and of one pinned buffer per direction; 0: not touched).  `Op.needs` / `Op.gives
 compares `Op.io` with the handle's own capacities after every call (check_io), and `Op.breaks_exact` -- the call claims io_in /
 io_out -- is what decides in exact_rows_follow_their_slabs whether the exact rows of an earlier lifecycle call are stale."""
 import functools
+import time
 
 import numpy as np
 
@@ -42,6 +48,7 @@ import life_util
 import oracle
 import pctl_util
 import pfield_util
+import reversal_util
 import segment_util
 import spell_util
 import std_util
@@ -225,11 +232,68 @@ def want_quantile_values(x, key, q):
         return np.nanquantile(np.asarray(x)[:, y0:y1].astype(np.float64), q, axis=0).ravel()
 
 
+# ---- the reversal index: inputs and reference (reversal_util) -------------------------------------------------------------------
+# per shape: delta in degrees and the latitude band.  Active rows in both hemispheres; rows 0 and ny - 1 are neither active nor
+# anybody's partner, so of every plane only rows [r0, r1) with r0 > 0 travel in and rows [a0, a1) with a1 < ny travel out
+REV_GRID = {"mult4": (20.0, (30, 50)), "odd": (22.5, (40, 50)), "large": (12.0, (30, 66))}
+REV_GHGS2 = -5.0
+
+
+def rev_lat(key):
+    return np.linspace(90.0, -90.0, SHAPES[key][1])
+
+
+@functools.lru_cache(maxsize=None)
+def rev_input(key, dtype="f4", seed=0):
+    """reversal_util.field on the shape's latitudes: the mean profile of 500 hPa height with weather"""
+    T, ny, nx = SHAPES[key]
+    return _frozen(reversal_util.field(rev_lat(key), nx, steps=T, seed=seed, dtype=DT[dtype]))
+
+
+def rev_table(key, second=False):
+    delta, bounds = REV_GRID[key]
+    return reversal_util.table(rev_lat(key), delta=delta, ghgs2=REV_GHGS2 if second else None, lat_bounds=bounds)
+
+
+def rev_rows(key, second=False):
+    """(r0, r1, a0, a1): the rows some active row reads and the rows the active rows span (ctk_reversal_rows)"""
+    tab = rev_table(key, second)
+    act = np.flatnonzero(tab["eq"] >= 0)
+    read = np.concatenate([act, tab["eq"][act], tab["po"][act]] + ([tab["eq2"][act]] if second else []))
+    return int(read.min()), int(read.max()) + 1, int(act.min()), int(act.max()) + 1
+
+
+@functools.lru_cache(maxsize=None)
+def want_reversal(key, dtype="f4", seed=0, mask=False, second=False):
+    return _frozen(reversal_util.from_table(rev_input(key, dtype, seed), rev_table(key, second), mask=mask))
+
+
+# ---- what is resident: the `src` of a consumer -----------------------------------------------------------------------------------
+# (key, dtype, seed, segments) names the slab anomalies(..., keep=True) left, (key, dtype, seed, ("reversal", mask, second)) the one
+# reversal(..., keep=True) left: the fourth entry tells the producers apart
+def by_reversal(src):
+    return isinstance(src[3], tuple)
+
+
+def resident_slab(src):
+    """the reference's values of the resident slab a consumer works on"""
+    if by_reversal(src):
+        return want_reversal(src[0], src[1], src[2], *src[3][1:])
+    return want_anom(*src)[0]
+
+
+def resident_cut(src):
+    """(threshold, compare) that makes a flag of the slab: anomalies of 40 or more, an index above 0 (include/contrack_hip.h)"""
+    return (0.0, ">") if by_reversal(src) else (40.0, ">=")
+
+
+@functools.lru_cache(maxsize=None)
 def resident_flag(src):
-    """the flag a lifecycle / composite of the resident anomaly slab works on: the oracle's tracking of that slab"""
-    a = want_anom(*src)[0]
-    f, _ = want_track_indicator(indicator(a, 40.0, ">="), src[0])
-    return f
+    """the flag a lifecycle / composite of the resident anomaly slab works on: the oracle's tracking of that slab (cached: an
+    operation's run asks for it as well, and the C oracle is only ever called where the references are computed)"""
+    a = resident_slab(src)
+    f, _ = want_track_indicator(indicator(a, *resident_cut(src)), src[0])
+    return _frozen(f)
 
 
 @functools.lru_cache(maxsize=None)
@@ -540,13 +604,14 @@ def second_call_forms(key, thr=100.0, seed=1):
     return dict(speculative=speculative, kept=not forms & label_forms.DISCARDED_BIT, forms=forms)
 
 
-def track_resident(src, thr=40.0, gorl=">="):
+def track_resident(src, thr=None, gorl=None):
     key = src[0]
+    thr, gorl = (resident_cut(src)[0] if thr is None else thr), (gorl or resident_cut(src)[1])
 
     def run(trk, env):
         f, n = trk.track_resident(thresholds(key, thr), CMP[gorl], wrow(key), OVERLAP, 2, TWOSIDED)
         return f.copy(), n
-    return Op("track_resident", key, run, lambda: want_track_indicator(indicator(want_anom(*src)[0], thr, gorl), key), same_flag,
+    return Op("track_resident", key, run, lambda: want_track_indicator(indicator(resident_slab(src), thr, gorl), key), same_flag,
               dict(NO_IO, io_out=RUNS_IO_OUT), io_upto=dense_blocks(key), needs="anom", tracking=True)
 
 
@@ -632,7 +697,7 @@ def composite_resident(src, G=3):
 
     def run(trk, env):
         return trk.composite(resident_flag(src), None, ids, G, 0, True, 0, resident_f64=src[1] == "f8")
-    return Op("composite_resident", key, run, lambda: composite_util.composite(resident_flag(src), want_anom(*src)[0], ids, G, 0, True), same_composite,
+    return Op("composite_resident", key, run, lambda: composite_util.composite(resident_flag(src), resident_slab(src), ids, G, 0, True), same_composite,
               stream_io(key, 0, 4), needs="anom")
 
 
@@ -726,7 +791,7 @@ def band_resident(src, how="array", chunk_steps=0):
         f = resident_flag(src)
         return _band_call(trk, how, key, f, None, src[1], chunk_steps, sects, True, (_chunks_reader(f), None), resident_gen=env.generation, resident_f64=src[1] == "f8")
     y0, y1 = band_rows(key)
-    return Op("band_resident", key, run, lambda: band_util.band(resident_flag(src), y0, y1, band_weights(key), 0, want_anom(*src)[0], sects, True), same_band,
+    return Op("band_resident", key, run, lambda: band_util.band(resident_flag(src), y0, y1, band_weights(key), 0, resident_slab(src), sects, True), same_band,
               band_io(key, how, src[1], chunk_steps, False), needs="anom", note="%s chunk=%d" % (how, chunk_steps), args=dict(how=how))
 
 
@@ -876,7 +941,7 @@ def centred_resident(src, how="array", chunk_steps=5):
         if how == "cb":
             return trk.centred_cb(None, (T, ny, nx), DT[src[1]], t, row, col, bin, chunk_steps=chunk_steps, **kw)
         return trk.centred_dev(None, T, ny, nx, t, row, col, bin, f64=src[1] == "f8", **kw)
-    return Op("centred_resident", key, run, lambda: centred_util.centred(want_anom(*src)[0], *stamps(key), **kw), same_centred, NO_IO, needs="anom", note=how,
+    return Op("centred_resident", key, run, lambda: centred_util.centred(resident_slab(src), *stamps(key), **kw), same_centred, NO_IO, needs="anom", note=how,
               args=dict(how=how))
 
 
@@ -904,9 +969,9 @@ def lifecycle_resident(src):
 
     def run(trk, env):
         rows = trk.lifecycle(resident_flag(src), None, wrow(key), resident_f64=src[1] == "f8")
-        env.life = (rows, key, resident_flag(src), want_anom(*src)[0])
+        env.life = (rows, key, resident_flag(src), resident_slab(src))
         return rows, trk.lifecycle_exact(np.arange(len(rows)))
-    return Op("lifecycle_resident", key, run, lambda: want_life(resident_flag(src), want_anom(*src)[0], key), same_life, array_io(key, 0, 4), needs="anom")
+    return Op("lifecycle_resident", key, run, lambda: want_life(resident_flag(src), resident_slab(src), key), same_life, array_io(key, 0, 4), needs="anom")
 
 
 def lifecycle_stream(key, dtype="f4", chunk_steps=0, readers=True, seed=1):
@@ -988,6 +1053,95 @@ def level_mean(key, dtype="f4", how="array", chunk_steps=None, keep=False, fail_
                   args=dict(fail_chunk=fail_chunk))
     return Op(fam, key, run, lambda: want_level(key, dtype, seed), level_util.same_bits, io, gives=gives, drops=("level",),
               note="%s chunk=%s%s" % (dtype, chunk_steps, " keep" if keep else ""), args=dict(dtype=dtype))
+
+
+def level_mean_dev(key, dtype="f4", seed=4):
+    """slab and mean in the caller's device buffers: no staging buffer is claimed, a resident mean stays where it is -- under a new
+    identity, as include/contrack_hip.h says of every ctk_level_mean_* call (the runner's Env follows it)"""
+    T, ny, nx = SHAPES[key]
+
+    def run(trk, env):
+        x = level_input(key, dtype, seed)
+        out = np.empty((T, ny, nx), dtype=DT[dtype])
+        d_in, d_out = trk.malloc(x.nbytes), trk.malloc(out.nbytes)
+        try:
+            trk.h2d(d_in, x)
+            trk.memset(d_out, 0xff, out.nbytes)
+            before = trk.resident_level_mean(), trk.resident_level_mean_generation()
+            trk.level_mean_dev(d_in, T, NLEV, ny, nx, LEVEL_W, d_out, f64=dtype == "f8")
+            trk.d2h(out, d_out)
+        finally:
+            trk.free(d_in)
+            trk.free(d_out)
+        after = trk.resident_level_mean(), trk.resident_level_mean_generation()
+        if env.level_generation is not None:
+            env.level_generation = after[1]
+        return out, before, after
+    return Op("level_mean_dev", key, run, lambda: want_level(key, dtype, seed),
+              lambda got, want: level_util.same_bits(got[0], want) and got[1][0] == got[2][0] and got[1][1] != got[2][1], NO_IO, note=dtype, args=dict(dtype=dtype))
+
+
+# ---- reversal of the meridional gradient ----------------------------------------------------------------------------------------
+def reversal_io(key, how, esz, chunk_steps, keep, sink=True):
+    """reversal_stream_impl: ctk_stream_chunk of a whole plane; two input chunks in io_in (a reader: and a pinned chunk), two output
+    chunks in io_out only without keep_resident or with a writer (then also a pinned output chunk) -- with keep_resident the kernel
+    writes the resident slot and a host array is filled from there.  reversal_dev claims nothing"""
+    if how == "dev":
+        return NO_IO
+    writer = how == "cb" and sink
+    return stream_io(key, chunk_steps, esz, out_bytes=esz if (not keep or writer) else 0, reader=how == "cb", writer=writer)
+
+
+def reversal(key, dtype="f4", how="array", chunk_steps=0, keep=False, mask=False, second=False, sink="array", fail_chunk=None, fail_which="reader", seed=0):
+    """how: "array" (Tracker.reversal), "cb" (reversal_cb: a reader, and `sink` an "array" or a "writer"), "dev" (reversal_dev).
+    fail_chunk / fail_which: the reader or the writer gives up on that call of it; with keep, nothing may be resident afterwards.
+    A call without keep leaves the resident slot alone: it neither gives nor drops"""
+    assert how in ("array", "cb", "dev") and sink in ("array", "writer") and fail_which in ("reader", "writer") and not (how == "dev" and keep)
+    T, ny, nx = SHAPES[key]
+    esz = 4 if dtype == "f4" else 8
+
+    def run(trk, env):
+        z, tab = rev_input(key, dtype, seed), rev_table(key, second)
+        if how == "array":
+            return trk.reversal(z, tab, mask=mask, chunk_steps=chunk_steps, keep_resident=keep)
+        if how == "dev":
+            out = np.empty_like(z)
+            d_in, d_out = trk.malloc(z.nbytes), trk.malloc(z.nbytes)
+            try:
+                trk.h2d(d_in, z)
+                trk.memset(d_out, 0xff, z.nbytes)
+                gen = trk.resident_generation()
+                trk.reversal_dev(d_in, T, ny, nx, tab, d_out, mask=mask, f64=dtype == "f8")
+                trk.d2h(out, d_out)
+                return out if trk.resident_generation() == gen else None
+            finally:
+                trk.free(d_in)
+                trk.free(d_out)
+        out = np.full((T, ny, nx), 7, dtype=DT[dtype])
+        count = [0]
+
+        def writer(t0, nt, v):
+            count[0] += 1
+            if fail_which == "writer" and count[0] == fail_chunk:
+                raise ReaderGaveUp("the writer, chunk %d" % count[0])
+            out[t0:t0 + nt] = v
+        reader = _chunks_reader(z, fail_chunk if fail_which == "reader" else None)
+        try:
+            trk.reversal_cb(reader, (T, ny, nx), DT[dtype], tab, mask=mask, sink=out if sink == "array" and fail_chunk is None else writer, chunk_steps=chunk_steps,
+                            keep_resident=keep)
+        except ReaderGaveUp as e:
+            return e if trk.resident_anom() is None or not keep else None          # (with keep: nothing is left resident)
+        return out
+    fam = {"array": "reversal", "cb": "reversal_cb", "dev": "reversal_dev"}[how]
+    io = reversal_io(key, how, esz, chunk_steps, keep)
+    note = "%s chunk=%d%s%s%s" % (dtype, chunk_steps, " keep" if keep else "", " mask" if mask else "", " ghgs2" if second else "") + (" " + sink if how == "cb" else "")
+    if fail_chunk is not None:
+        assert how == "cb"
+        return Op(fam, key, run, lambda: None, gave_up, io, drops=("anom",) if keep else (), note="%s: the %s gives up on chunk %d" % (note, fail_which, fail_chunk),
+                  args=dict(fail_chunk=fail_chunk, fail_which=fail_which, how=how, keep=keep))
+    return Op(fam, key, run, lambda: want_reversal(key, dtype, seed, mask, second), lambda got, want: got is not None and reversal_util.same_bits(got, want), io,
+              gives=("anom", key, dtype, seed, ("reversal", mask, second)) if keep else None, drops=("anom",) if keep else (), note=note,
+              args=dict(dtype=dtype, how=how, keep=keep, mask=mask, second=second, sink=sink))
 
 
 def climatology(key, dtype="f4", segments=False, seed=3):
@@ -1094,7 +1248,7 @@ def percentile(key, dtype="f4", q=0.9, seed=3):
 def percentile_resident(src, q=0.9):
     key = src[0]
 
-    return Op("percentile_resident", key, lambda trk, env: _percentile(trk, env, None, key, q), lambda: want_quantile_values(want_anom(*src)[0], key, q),
+    return Op("percentile_resident", key, lambda trk, env: _percentile(trk, env, None, key, q), lambda: want_quantile_values(resident_slab(src), key, q),
               same_percentile, NO_IO, needs="anom")
 
 
@@ -1244,6 +1398,14 @@ def a_failed_stream_then_others():
     seq += [centred(L, "cb", "f4", chunk_steps=7, fail_chunk=3), track_stream(O, "f4", chunk_steps=9, callbacks=True), centred(L, "cb", "f4", chunk_steps=7)]
     # ... and a centred reader call directly after another family's failed stream
     seq += [frequency(L, "cb", chunk_steps=c, fail_chunk=3), centred(O, "cb", "f8", chunk_steps=4), lifecycle(S)]
+    # a reversal that was to leave its result resident and whose reader gives up on chunk 3 of 5 (the kernel has written two chunks
+    # into the resident slot): nothing is resident, every consumer refuses; then one whose writer gives up on its second chunk while
+    # a resident slab of the other producer is there (it is left alone: the call keeps nothing); the next streamed reversal is right
+    a, r = (S, "f4", 3, False), (L, "f4", 0, ("reversal", False, False))
+    seq += [anomalies(S, "f4", keep=True), reversal(L, "f4", "cb", chunk_steps=c, keep=True, fail_chunk=3), refuses(track_resident(r)), refuses(band_resident(r, "dev")),
+            spells(O, "cb", chunk_steps=6), track(O)]
+    seq += [anomalies(S, "f4", keep=True), reversal(L, "f4", "cb", chunk_steps=c, fail_chunk=2, fail_which="writer"), track_resident(a),
+            reversal(O, "f8", "cb", chunk_steps=8, second=True, sink="writer"), composite(S)]
     return seq
 
 
@@ -1274,12 +1436,39 @@ def exact_rows_follow_their_slabs():
     return seq
 
 
+def _reversal_consumers(src):
+    return ([track_resident(src), percentile_resident(src)] + [band_resident(src, how, chunk_steps=7 if how != "dev" else 0) for how in ("array", "cb", "dev")]
+            + [centred_resident(src, how) for how in ("array", "cb", "dev")])
+
+
+def reversal_between_the_others():
+    """the second producer of the resident slab among the first one's calls: a reversal that keeps nothing leaves the anomaly slab and
+    its generation alone (on a larger shape, so io_in and io_out grow under it); one that keeps replaces it, and the consumers then
+    work on the reversal's output; the anomalies of a resident vertical mean replace that in turn; two reversals of one shape and
+    type are told apart by their generation alone"""
+    a = (S, "f4", 3, False)
+    r = (O, "f4", 0, ("reversal", False, True))
+    lv = ("level", L, "f4", 4)
+    seq = [anomalies(S, "f4", keep=True),
+           reversal(L, "f8", chunk_steps=16), reversal(L, "f4", "dev", mask=True), generation_unchanged(a), track_resident(a), band_resident(a, "dev"), centred_resident(a, "array"),
+           reversal(O, "f4", chunk_steps=7, keep=True, second=True), generation_unchanged(r)] + _reversal_consumers(r) + [lifecycle_resident(r), composite_resident(r)]
+    seq += [level_mean(L, "f4", keep=True), level_mean_dev(S, "f8"), level_generation_unchanged(lv), anomalies_resident(lv)]
+    seq += [refuses(op) for op in _reversal_consumers(r)]
+    # a reader and a writer, float64, the mask, on the large shape; then the slab of another seed takes its place
+    m = (L, "f8", 0, ("reversal", True, False))
+    seq += [reversal(L, "f8", "cb", chunk_steps=13, keep=True, mask=True, sink="writer"), generation_unchanged(m), track_resident(m), percentile_resident(m), centred_resident(m, "dev")]
+    b = (O, "f4", 1, ("reversal", False, True))
+    seq += [reversal(O, "f4", keep=True, second=True), reversal(O, "f4", keep=True, second=True, seed=1), band_stale(b, "array"), band_stale(b, "dev"),
+            band_resident(b, "array", chunk_steps=7), track_resident(b)]
+    return seq
+
+
 WRITTEN = [io_grows_and_shrinks, pinned_chunks_up_and_down, resident_anomaly_survives, resident_level_mean_survives, invalidated_residents_refuse,
-           tracking_caches, sticky_settings_do_not_leak, a_failed_stream_then_others, exact_rows_follow_their_slabs]
+           tracking_caches, sticky_settings_do_not_leak, a_failed_stream_then_others, exact_rows_follow_their_slabs, reversal_between_the_others]
 
 
 # ---- the seeded sequences -------------------------------------------------------------------------------------------------------
-N_SEEDS, N_OPS = 22, 10                # 22 sequences: every one of the 40 families is drawn three times or more (a consumer drawn last is skipped)
+N_SEEDS, N_OPS = 26, 10                # 26 sequences: every one of the 44 families is drawn three times or more (a consumer drawn last is skipped)
 
 
 def _vocabulary():
@@ -1319,6 +1508,11 @@ def _vocabulary():
         "lifecycle_resident": lambda r, s: lifecycle_resident(s["anom"]),
         "level_mean": lambda r, s: level_mean(key(r), dt(r), "array", pick(r, (None, chunk(r))), keep=bool(r.integers(2))),
         "level_mean_cb": lambda r, s: level_mean(key(r), dt(r), "cb", chunk(r), keep=bool(r.integers(2))),
+        "level_mean_dev": lambda r, s: level_mean_dev(key(r), dt(r)),
+        "reversal": lambda r, s: reversal(key(r), dt(r), "array", pick(r, (0, chunk(r))), keep=bool(r.integers(2)), mask=bool(r.integers(2)), second=bool(r.integers(2))),
+        "reversal_cb": lambda r, s: reversal(key(r), dt(r), "cb", chunk(r), keep=bool(r.integers(2)), mask=bool(r.integers(2)), second=bool(r.integers(2)),
+                                             sink=pick(r, ("array", "writer"))),
+        "reversal_dev": lambda r, s: reversal(key(r), dt(r), "dev", mask=bool(r.integers(2)), second=bool(r.integers(2))),
         "anomalies": lambda r, s: anomalies(key(r), dt(r), keep=bool(r.integers(2)), segments=bool(r.integers(2))),
         "climatology": lambda r, s: climatology(key(r), dt(r), segments=bool(r.integers(2))),
         "climatology_resident": lambda r, s: climatology_resident(s["level"]),
@@ -1367,7 +1561,12 @@ def seeded(seed):
                 continue
             k = (S, O, L)[int(rng.integers(3))]
             d = ("f4", "f8")[int(rng.integers(2))]
-            producer = anomalies(k, d, keep=True) if need == "anom" else level_mean(k, d, keep=True)
+            if need == "level":
+                producer = level_mean(k, d, keep=True)
+            elif rng.integers(2):                                  # either producer of the resident slab
+                producer = reversal(k, d, chunk_steps=int(rng.integers(0, 20)), keep=True, mask=bool(rng.integers(2)), second=bool(rng.integers(2)))
+            else:
+                producer = anomalies(k, d, keep=True)
             ops.append(producer)
             apply_residency(state, producer)
         op = vocab[fam](rng, state)
@@ -1404,22 +1603,29 @@ def check_io(cap, op, got, raised=False):
     return bad
 
 
-def run_sequence(trk, ops, env=None):
+def run_sequence(trk, ops, env=None, wants=None, on_op=None):
     """every operation in order on `trk`, each compared with its reference: the list of failures (empty: all right) as
     (position, op, what).  After every tracking operation the handle's ambiguous_decisions must be 0.  After every operation the
     capacities of the shared buffers (Tracker.debug_io_bytes) are what Op.io says the handle asked for, from the capacities the
-    sequence found: (position, op, "io model", buffer, got, model) otherwise."""
+    sequence found: (position, op, "io model", buffer, got, model) otherwise.
+    wants: the references, one per operation, computed beforehand (tests/concurrent_util.py: in one thread, before several handles
+    run at once) instead of op.want().  on_op(position, op, t_start, t_end): called after every operation with time.perf_counter()
+    directly before and after op.run."""
     env = env or Env()
     bad = []
     cap = trk.debug_io_bytes()
     for i, op in enumerate(ops):
+        t_start = time.perf_counter()
         got = op.run(trk, env)
+        t_end = time.perf_counter()
+        if on_op is not None:
+            on_op(i, op, t_start, t_end)
         if op.gives is not None:
             if op.gives[0] == "anom":
                 env.stale_generation, env.generation = env.generation, trk.resident_generation()
             else:
                 env.level_generation = trk.resident_level_mean_generation()
-        if not op.same(got, op.want()):
+        if not op.same(got, op.want() if wants is None else wants[i]):
             bad.append((i, repr(op), "differs from its reference", getattr(op.same, "detail", "")))
         if op.tracking and trk.stats()["ambiguous_decisions"] != 0:
             bad.append((i, repr(op), "ambiguous_decisions = %d" % trk.stats()["ambiguous_decisions"]))

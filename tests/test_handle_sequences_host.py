@@ -234,7 +234,25 @@ def test_sticky_settings_sequence():
 def test_failed_stream_sequence():
     ops = hs.a_failed_stream_then_others()
     failing = [i for i, op in enumerate(ops) if op.args.get("fail_chunk")]
-    assert [ops[i].family for i in failing] == ["frequency_cb", "level_mean_cb", "track_stream", "band_cb", "band_cb", "centred_cb", "frequency_cb"]
+    assert [ops[i].family for i in failing] == ["frequency_cb", "level_mean_cb", "track_stream", "band_cb", "band_cb", "centred_cb", "frequency_cb", "reversal_cb", "reversal_cb"]
+    # the two reversals: the reader of one that keeps gives up on chunk 3 of 5 -- in the model nothing is resident afterwards and the
+    # consumers after it are refusals --, the writer of one that keeps nothing gives up on its second chunk -- the anomaly slab of
+    # the call before stays, its consumer is right --, and a streamed reversal with reader and writer follows
+    i, j = failing[7:]
+    assert ops[i].args["keep"] and ops[i].args["fail_which"] == "reader" and ops[i].args["fail_chunk"] == 3 and ops[i].io["chunks"] == 5 and ops[i].drops == ("anom",)
+    assert ops[i - 1].gives and ops[i - 1].gives[0] == "anom" and [op.args.get("refuse") for op in ops[i + 1:i + 3]] == [True, True]
+    assert ops[i].io["pin_in"] > 0 and ops[i].io["pin_out"] > 0 and ops[i].io["io_out"] > 0                    # a writer: the output chunks as well
+    assert not ops[j].args["keep"] and ops[j].args["fail_which"] == "writer" and ops[j].args["fail_chunk"] == 2 and ops[j].io["chunks"] == 5 and ops[j].drops == ()
+    assert ops[j - 1].gives and ops[j + 1].family == "track_resident" and not ops[j + 1].args.get("refuse")
+    assert ops[j + 2].family == "reversal_cb" and not ops[j + 2].args.get("fail_chunk") and ops[j + 2].io["chunks"] >= 3 and ops[j + 2].key != ops[j].key
+    state = {"anom": None, "level": None}
+    for op in ops:
+        if op.args.get("refuse"):
+            assert state[hs.CONSUMERS[op.family]] is None, op
+        elif op.needs:
+            assert state[op.needs] is not None, op
+        hs.apply_residency(state, op)
+    failing = failing[:7]
     # a band reader gives up on chunk 3 of 5 -- once the flag reader, once the field reader, which is called after the flag reader of
     # the same chunk --, and the very next call is a streamed band with readers on another shape, of at least three chunks (both
     # pinned twins and both table sets are used, the first set twice)
@@ -327,6 +345,89 @@ def test_exact_rows_sequence():
     assert not ops[-1].args.get("stale") and ops[-1].family == "lifecycle_exact"
 
 
+def test_reversal_grids_and_the_io_model_of_the_reversal_entries():
+    import reversal_util as ru
+    for key, (T, ny, nx) in hs.SHAPES.items():
+        for second in (False, True):
+            tab = hs.rev_table(key, second)
+            act = np.flatnonzero(tab["eq"] >= 0)
+            lat = hs.rev_lat(key)
+            assert (lat[act] > 0).any() and (lat[act] < 0).any(), key                       # active rows in both hemispheres
+            r0, r1, a0, a1 = hs.rev_rows(key, second)
+            assert 0 < r0 <= a0 < a1 <= r1 < ny, (key, r0, r1, a0, a1)                       # rows 0 and ny - 1: neither read nor written
+            for dtype in ("f4", "f8"):
+                w = hs.want_reversal(key, dtype, 0, False, second)
+                assert 0.05 <= ru.blocked_share(w, tab["eq"]) <= 0.5, (key, second)         # (as tests/test_gpu_reversal.py asks of its fixtures)
+                assert not w[:, :a0].any() and not w[:, a1:].any() and w.dtype == hs.DT[dtype]
+                assert ru.same_bits(hs.want_reversal(key, dtype, 0, True, second), (w != 0).astype(w.dtype))
+        assert not np.array_equal(hs.want_reversal(key, "f4", 0), hs.want_reversal(key, "f4", 1))            # another seed, another slab
+        assert np.count_nonzero(hs.want_reversal(key, "f4", 0)) > np.count_nonzero(hs.want_reversal(key, "f4", 0, False, True))      # the third criterion matters
+        # a gradient divided by another distance than the rows' own would be seen
+        assert ru.differing(hs.want_reversal(key, "f4", 0), ru.from_table(hs.rev_input(key, "f4", 0), hs.rev_table(key), div=15.0)) == np.count_nonzero(hs.want_reversal(key, "f4", 0))
+    # io: chunks of whole planes, two per direction; io_out only without keep or with a writer; pinned chunks for reader and writer
+    T, ny, nx = hs.SHAPES["odd"]
+    plane = ny * nx
+    a = hs.reversal("odd", "f8", chunk_steps=7)
+    assert {b: a.io[b] for b in hs.BUFFERS} == dict(io_in=2 * 7 * plane * 8, io_out=2 * 7 * plane * 8, pin_in=0, pin_out=0) and a.io["chunks"] == -(-T // 7)
+    k = hs.reversal("odd", "f8", chunk_steps=7, keep=True)
+    assert {b: k.io[b] for b in hs.BUFFERS} == dict(io_in=2 * 7 * plane * 8, io_out=0, pin_in=0, pin_out=0)
+    assert hs.reversal("odd", "f4").io["io_in"] == 2 * T * plane * 4 and hs.reversal("odd", "f4").io["chunks"] == 1
+    for keep in (False, True):
+        c = hs.reversal("odd", "f4", "cb", chunk_steps=5, keep=keep, sink="writer")
+        assert {b: c.io[b] for b in hs.BUFFERS} == dict(io_in=2 * 5 * plane * 4, io_out=2 * 5 * plane * 4, pin_in=5 * plane * 4, pin_out=5 * plane * 4)
+    assert {b: hs.reversal("odd", "f4", "dev").io[b] for b in hs.BUFFERS} == hs.NO_IO and {b: hs.level_mean_dev("odd").io[b] for b in hs.BUFFERS} == hs.NO_IO
+    # residency: only a call that keeps touches the slot
+    assert k.gives == ("anom", "odd", "f8", 0, ("reversal", False, False)) and k.drops == ("anom",) and a.gives is None and a.drops == ()
+    assert k.breaks_exact and a.breaks_exact and not hs.reversal("odd", "f4", "dev").breaks_exact and not hs.level_mean_dev("odd").breaks_exact
+    lm = hs.level_mean_dev("odd")
+    assert lm.gives is None and lm.drops == () and lm.needs is None
+
+
+def test_reversal_between_the_others_does():
+    seq = hs.reversal_between_the_others()
+    assert hs.reversal_between_the_others in hs.WRITTEN
+    fams = [op.family for op in seq]
+    assert fams[0] == "anomalies" and seq[0].gives[0] == "anom"
+    state = {"anom": None, "level": None}
+    producers, on = [], {"anomalies": set(), "reversal": set()}
+    for i, op in enumerate(seq):
+        if op.args.get("refuse"):
+            assert state[hs.CONSUMERS[op.family]] is None, (i, op)
+        elif op.needs:
+            assert state[op.needs] is not None, (i, op)
+            if op.needs == "anom" and not op.family.startswith("resident"):
+                on["reversal" if hs.by_reversal(state["anom"]) else "anomalies"].add(op.family)
+        before = state["anom"]
+        hs.apply_residency(state, op)
+        if op.family.startswith("reversal") and not op.args["keep"]:
+            assert state["anom"] == before and before is not None, (i, op)                   # keeps nothing: the slab stays
+        if op.gives and op.gives[0] == "anom":
+            producers.append(op.family)
+    assert producers == ["anomalies", "reversal", "reversal_cb", "reversal", "reversal"]
+    assert on["reversal"] >= {"track_resident", "band_resident", "centred_resident", "percentile_resident", "lifecycle_resident", "composite_resident"}
+    assert on["anomalies"] >= {"track_resident", "band_resident", "centred_resident"}
+    # the reversals that keep nothing come first and work on a larger shape than the resident slab: io_in and io_out grow under it
+    first_keep = next(i for i, op in enumerate(seq) if op.family == "reversal" and op.args["keep"])
+    plain = [op for op in seq[1:first_keep] if op.family.startswith("reversal")]
+    assert [op.family for op in plain] == ["reversal", "reversal_dev"] and plain[0].io["io_in"] > seq[0].io["io_in"] and plain[0].io["io_out"] > 0
+    assert fams[first_keep - 4:first_keep].count("resident_generation") == 1 and fams[first_keep + 1] == "resident_generation"
+    # the anomalies of the resident vertical mean replace the slab; every consumer of the reversal is then a refusal
+    ar = fams.index("anomalies_resident")
+    assert fams[ar - 3:ar] == ["level_mean", "level_mean_dev", "resident_level_generation"] and seq[ar - 3].gives[0] == "level"
+    n = len(hs._reversal_consumers(("odd", "f4", 0, ("reversal", False, True))))
+    assert all(op.args.get("refuse") for op in seq[ar + 1:ar + 1 + n]) and not seq[ar + 1 + n].args.get("refuse")
+    # the references of the consumers follow the producer: on the reversal's output they differ from those on the anomaly slab
+    a, r = ("odd", "f4", 3, False), ("odd", "f4", 0, ("reversal", False, True))
+    assert not np.array_equal(hs.resident_slab(a), hs.resident_slab(r), equal_nan=True) and hs.resident_cut(a) == (40.0, ">=") and hs.resident_cut(r) == (0.0, ">")
+    assert hs.track_resident(r).want()[1] > 10 and not np.array_equal(hs.track_resident(r).want()[0], hs.track_resident(a).want()[0])
+    assert not np.array_equal(hs.percentile_resident(r).want(), hs.percentile_resident(a).want(), equal_nan=True)
+    # two reversals of one shape and type with other values, then the stale generation
+    st = [i for i, op in enumerate(seq) if op.args.get("stale_generation")]
+    assert len(st) == 2 and [op.family for op in seq[st[0] - 2:st[0]]] == ["reversal", "reversal"]
+    g0, g1 = seq[st[0] - 2].gives, seq[st[0] - 1].gives
+    assert g0[1:3] == g1[1:3] and g0[3] != g1[3] and not np.array_equal(hs.resident_slab(g0[1:]), hs.resident_slab(g1[1:]))
+
+
 def test_seeded_generator_is_deterministic_and_covers_the_vocabulary():
     seqs = [hs.seeded(s) for s in range(hs.N_SEEDS)]
     again = [hs.seeded(s) for s in range(hs.N_SEEDS)]
@@ -344,8 +445,31 @@ def test_seeded_generator_is_deterministic_and_covers_the_vocabulary():
             keys.add(op.key)
             dtypes.add(op.args.get("dtype"))
     assert min(count.values()) >= 3, sorted(count.items(), key=lambda kv: kv[1])[:5]
-    # the eight families of band and centred are among them (with the 32 of before: 40)
-    assert len(hs.FAMILIES) == 40 and {f + g for f in ("band", "centred") for g in ("", "_cb", "_dev", "_resident")} <= set(hs.FAMILIES)
+    # the eight families of band and centred are among them (with the 32 of before: 40), and the three reversal entries and
+    # level_mean_dev: 44
+    assert len(hs.FAMILIES) == 44 and {f + g for f in ("band", "centred") for g in ("", "_cb", "_dev", "_resident")} <= set(hs.FAMILIES)
+    assert {"reversal", "reversal_cb", "reversal_dev", "level_mean_dev"} <= set(hs.FAMILIES)
+    # the seeded reversals: both dtypes, with and without keep, mask and third criterion, an array and a writer as the sink of the
+    # reader form; a missing anomaly slab was made by either producer, and consumers were drawn on a reversal's output
+    rev = [op for q in seqs for op in q if op.family.startswith("reversal")]
+    for k in ("keep", "mask", "second"):
+        assert {op.args[k] for op in rev} == {False, True}, k
+    assert {op.args["dtype"] for op in rev} == {"f4", "f8"} and {op.args["sink"] for op in rev if op.family == "reversal_cb"} == {"array", "writer"}
+    producers = {q[i].family for q in seqs for i in range(len(q) - 1) if q[i + 1].needs == "anom" and q[i].gives}
+    assert producers >= {"anomalies", "reversal"}
+    on_reversal = set()
+    for q in seqs:
+        state = {"anom": None, "level": None}
+        for op in q:
+            if op.needs == "anom" and hs.by_reversal(state["anom"]):
+                on_reversal.add(op.family)
+            hs.apply_residency(state, op)
+    assert len(on_reversal) >= 4, on_reversal
+    # io: every op names the four buffers, and nothing else decides breaks_exact
+    for q in seqs:
+        for op in q:
+            assert set(hs.BUFFERS) <= set(op.io) and all(isinstance(op.io[b], int) and op.io[b] >= 0 for b in hs.BUFFERS), op
+            assert op.gives is None or (op.gives[0] in op.drops and op.gives[1] == op.key), op
     for q in seqs:
         for op in q:
             if op.family in ("centred", "centred_cb") and op.io["chunks"] > 1:
@@ -356,13 +480,14 @@ def test_seeded_generator_is_deterministic_and_covers_the_vocabulary():
 
 def _one_of_each():
     k = hs.SMALLEST
-    a, lv = (k, "f4", 3, False), ("level", k, "f4", 4)
+    a, lv, r = (k, "f4", 3, False), ("level", k, "f4", 4), (k, "f4", 0, ("reversal", False, False))
     return [hs.track(k), hs.track(k, "f8", per_step=True), hs.track_field(k), hs.track_segments(k), hs.track_stream(k), hs.track_dev(k), hs.track_resident(a),
             hs.frequency(k), hs.spells(k, segments=True), hs.composite(k), hs.composite_resident(a), hs.lifecycle(k), hs.lifecycle_stream(k),
             hs.lifecycle_resident(a), hs.level_mean(k), hs.anomalies(k), hs.anomalies(k, "f8", segments=True), hs.anomalies_stream(k),
             hs.anomalies_resident(lv), hs.climatology(k), hs.climatology_resident(lv), hs.percentile(k), hs.percentile_resident(a), hs.percentile_groups(k), hs.percentile_field(k), hs.std_field(k),
             hs.band(k), hs.band(k, field="f8", columns=False), hs.band(k, field="f4", sectors=False), hs.band_resident(a), hs.centred(k), hs.centred(k, dtype="f8"),
-            hs.centred_resident(a)]
+            hs.centred_resident(a), hs.level_mean_dev(k), hs.reversal(k), hs.reversal(k, "f8", "cb", chunk_steps=5, keep=True, mask=True, second=True), hs.reversal(k, how="dev"),
+            hs.track_resident(r), hs.percentile_resident(r), hs.band_resident(r), hs.centred_resident(r), hs.lifecycle_resident(r), hs.composite_resident(r)]
 
 
 def test_every_reference_runs_on_the_smallest_shape():
