@@ -1,4 +1,5 @@
-"""ctypes binding of libcontrack_hip.so (include/contrack_hip.h).  No torch, no other HIP binding.
+"""ctypes binding of libcontrack_hip.so.  No torch, no other HIP binding.  Signatures, structs, callback types and return codes are
+read from include/contrack_hip.h and include/contrack_hip_debug.h when the module is imported (_abi.py); none is restated here.
 
 The library is the product's only compute path: if it is missing or no GPU is visible the calls raise
 -- there is no CPU fallback (the CPU restatement lives in oracle/ and is test infrastructure).
@@ -9,8 +10,11 @@ import weakref
 
 import numpy as np
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CTK_LIB", os.path.join(_HERE, "libcontrack_hip.so"))
+INCLUDE_DIR = os.environ.get("CTK_INCLUDE", os.path.join(os.path.dirname(_HERE), "include"))
 _lib = None
 
 CMP_OPS = {">=": 0, "ge": 0, "<=": 1, "le": 1, ">": 2, "gt": 2, "<": 3, "lt": 3}
@@ -19,57 +23,36 @@ GORL_ERRMSG = ' Please select from [>, >=, <, >=] for gorl'      # contrack.py:6
 TIMER_NAMES = ["k_threshold", "k_scan", "k_label2d", "k_overlap", "k_extent", "k_run_values", "k_relabel",
                "k_resolve", "k_resolve_final", "k_count", "host_seam_driver", "d2h", "h2d", "total"]
 
-EXPORTS = [
-    "ctk_version", "ctk_last_error", "ctk_device_count", "ctk_create", "ctk_destroy", "ctk_track_f32",
-    "ctk_track_f32_dev", "ctk_track_f64", "ctk_track_f64_dev", "ctk_release_io", "ctk_shard_label2d", "ctk_shard_label2d_f64", "ctk_shard_halo_size", "ctk_shard_halo_export",
-    "ctk_shard_halo_import", "ctk_shard_overlap", "ctk_shard_tables", "ctk_resolve", "ctk_result_free",
-    "ctk_result_info", "ctk_result_arrays", "ctk_result_nshards", "ctk_weights_to_limbs", "ctk_shard_extents", "ctk_shard_write",
-    "ctk_shard_count_tracked", "ctk_debug_mask", "ctk_debug_label2d", "ctk_debug_set_pair_capacity", "ctk_debug_set_mailbox", "ctk_debug_set_seam_caps", "ctk_debug_shard_exchange", "ctk_debug_set_shared_ops_reserve", "ctk_debug_set_spin", "ctk_debug_set_small_threads", "ctk_debug_forms", "ctk_debug_np_sum", "ctk_debug_boundary_resolve", "ctk_debug_boundary_resolve_breaks", "ctk_set_timing", "ctk_get_timings", "ctk_get_timing_sums", "ctk_set_device_resolve", "ctk_set_fused_pass", "ctk_set_result_transfer", "ctk_expand_runs_host", "ctk_set_filter_round", "ctk_get_stats", "ctk_get_stats_n", "ctk_debug_stream_ceiling", "ctk_debug_time_relabel",
-    "ctk_dev_malloc", "ctk_dev_free", "ctk_host_alloc", "ctk_host_free", "ctk_host_register", "ctk_host_unregister", "ctk_memcpy_h2d", "ctk_memcpy_d2h", "ctk_sync", "ctk_stream",
-    "ctk_synth_fill", "ctk_debug_live", "ctk_debug_io_bytes",
-    "ctk_comm_unique_id", "ctk_comm_init_rccl", "ctk_comm_group_create", "ctk_comm_group_destroy", "ctk_comm_init_local", "ctk_comm_init_shm",
-    "ctk_comm_destroy", "ctk_comm_rank", "ctk_comm_world", "ctk_comm_barrier", "ctk_comm_allgather_host", "ctk_comm_ops",
-    "ctk_comm_set_timeout", "ctk_comm_rccl_library", "ctk_comm_failed", "ctk_comm_abort_rank", "ctk_debug_fail_at", "ctk_synth_fill_window", "ctk_checksum_i32_dev", "ctk_dev_memset", "ctk_check_flag_dev",
-    "ctk_track_sharded_f32_dev", "ctk_track_sharded_f64_dev",
-    "ctk_anom_f32", "ctk_anom_f64", "ctk_resident_anom", "ctk_resident_anom_generation", "ctk_track_resident", "ctk_percentile_f32", "ctk_percentile_f64", "ctk_debug_percentile_values",
-    "ctk_lifecycle_f32", "ctk_lifecycle_f64", "ctk_lifecycle_f32_dev", "ctk_lifecycle_f64_dev", "ctk_lifecycle_rows", "ctk_lifecycle_exact",
-    "ctk_debug_lifecycle_plan", "ctk_debug_lifecycle_path",
-    "ctk_lifecycle_stream_f32", "ctk_lifecycle_stream_f64", "ctk_lifecycle_stream_cb", "ctk_lifecycle_stream_exact",
-    "ctk_track_stream_f32", "ctk_track_stream_f64", "ctk_track_stream_cb", "ctk_stream_times",
-    "ctk_set_threshold_field", "ctk_set_segments",
-    "ctk_track_stream_seg_f32", "ctk_track_stream_seg_f64", "ctk_track_stream_seg_cb", "ctk_track_sharded_seg_f32_dev", "ctk_track_sharded_seg_f64_dev",
-    "ctk_frequency_dev", "ctk_frequency", "ctk_frequency_cb", "ctk_debug_set_freq", "ctk_debug_time_freq",
-    "ctk_spells_dev", "ctk_spells", "ctk_spells_cb", "ctk_debug_set_spell", "ctk_debug_time_spell",
-    "ctk_percentile_groups_f32", "ctk_percentile_groups_f64", "ctk_debug_percentile_groups_sweeps", "ctk_debug_percentile_groups_plan", "ctk_debug_percentile_groups_state", "ctk_debug_time_percentile_groups",
-    "ctk_percentile_field_f32", "ctk_percentile_field_f64", "ctk_debug_percentile_field_plan", "ctk_debug_percentile_field_form", "ctk_debug_time_percentile_field",
-    "ctk_std_field_f32", "ctk_std_field_f64", "ctk_debug_std_field_plan", "ctk_debug_std_field_form", "ctk_debug_time_std_field",
-    "ctk_anom_seg_f32", "ctk_anom_seg_f64", "ctk_anom_stream_f32", "ctk_anom_stream_f64", "ctk_anom_stream_cb", "ctk_debug_anom_form", "ctk_debug_anom_plan", "ctk_debug_set_anom", "ctk_debug_anom_launch",
-    "ctk_level_mean_f32", "ctk_level_mean_f64", "ctk_level_mean_f32_dev", "ctk_level_mean_f64_dev", "ctk_level_mean_stream_f32", "ctk_level_mean_stream_f64",
-    "ctk_level_mean_stream_cb", "ctk_resident_level_mean", "ctk_resident_level_mean_generation", "ctk_anom_seg_resident", "ctk_debug_level_plan", "ctk_debug_level_form", "ctk_debug_time_level_mean", "ctk_debug_set_level",
-    "ctk_reversal_f32", "ctk_reversal_f64", "ctk_reversal_f32_dev", "ctk_reversal_f64_dev", "ctk_reversal_stream_cb",
-    "ctk_debug_reversal_plan", "ctk_debug_set_reversal", "ctk_debug_reversal_form", "ctk_debug_time_reversal",
-    "ctk_composite_f32_dev", "ctk_composite_f64_dev", "ctk_composite_f32", "ctk_composite_f64", "ctk_composite_cb",
-    "ctk_debug_composite_plan", "ctk_debug_set_composite", "ctk_debug_composite_launch", "ctk_debug_time_composite",
-    "ctk_centred_f32_dev", "ctk_centred_f64_dev", "ctk_centred_f32", "ctk_centred_f64", "ctk_centred_cb",
-    "ctk_debug_centred_plan", "ctk_debug_set_centred", "ctk_debug_centred_launch", "ctk_debug_time_centred",
-    "ctk_band_dev", "ctk_band_f32", "ctk_band_f64", "ctk_band_cb", "ctk_debug_band_plan", "ctk_debug_set_band", "ctk_debug_band_launch", "ctk_debug_time_band",
-]
-
-READ_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)       # ctk_read_chunk_fn
-WRITE_CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)      # ctk_write_chunk_fn, ctk_write_values_fn
-LIFE_PICK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64))      # ctk_life_pick_fn
-
-# ctk_life_row (include/contrack_hip.h)
-LIFE_ROW = np.dtype([("t", "<i4"), ("label", "<i4"), ("shift", "<i4"), ("pad", "<i4"),
-                     ("area", "<f8"), ("swv", "<f8"), ("swvy", "<f8"), ("swvx", "<f8")])
-
-
-# ctk_life_exact
-LIFE_EXACT = np.dtype([("area", "<f8"), ("swv", "<f8"), ("s", "<f8"), ("sy", "<f8"), ("sx", "<f8")])
-
 
 class ContrackHipError(RuntimeError):
     pass
+
+
+def _headers():
+    """the text of the C headers, which state the ABI once: what the library is compiled against and what this binding is made from"""
+    try:
+        return "\n".join(open(os.path.join(INCLUDE_DIR, h)).read() for h in _abi.HEADERS)
+    except OSError as e:
+        raise ContrackHipError("the C headers %s not found in %s (%s) -- they belong to the source tree next to the package; CTK_INCLUDE "
+                               "names another directory, as CTK_LIB names another library" % (", ".join(_abi.HEADERS), INCLUDE_DIR, e)) from None
+
+
+ABI = _abi.parse(_headers())
+EXPORTS = list(ABI.functions)
+CTK_E_INVALID, CTK_E_NOMEM, CTK_E_RANGE, CTK_E_COMM = (ABI.constants[k] for k in ("CTK_E_INVALID", "CTK_E_NOMEM", "CTK_E_RANGE", "CTK_E_COMM"))
+
+READ_CHUNK_FN = ABI.callbacks["ctk_read_chunk_fn"]
+WRITE_CHUNK_FN = ABI.callbacks["ctk_write_chunk_fn"]           # and ctk_write_values_fn: one signature, one ctypes class
+LIFE_PICK_FN = ABI.callbacks["ctk_life_pick_fn"]
+
+
+def _dtype(struct):
+    """a header struct of scalars as the numpy dtype with C's layout"""
+    return np.dtype([(n, np.dtype(t)) for n, t in ABI.structs[struct]], align=True)
+
+
+LIFE_ROW = _dtype("ctk_life_row")
+LIFE_EXACT = _dtype("ctk_life_exact")
 
 
 class CommError(ContrackHipError):
@@ -83,25 +66,22 @@ class InvalidArgumentError(ContrackHipError, ValueError):
 
 class BandSpec(C.Structure):
     """ctk_band_spec of include/contrack_hip.h"""
-    _fields_ = [("y0", C.c_int32), ("y1", C.c_int32), ("above", C.c_int32), ("nsect", C.c_int32), ("w", C.c_void_p), ("sectors", C.c_void_p),
-                ("columns", C.c_int32), ("resident", C.c_int32), ("resident_gen", C.c_uint64)]
+    _fields_ = ABI.structs["ctk_band_spec"]
 
 
 class BandOut(C.Structure):
     """ctk_band_out of include/contrack_hip.h"""
-    _fields_ = [(n, C.c_void_p) for n in "cnt area wx sec_cnt sec_area sec_wx".split()]
+    _fields_ = ABI.structs["ctk_band_out"]
 
 
 class FormQuery(C.Structure):
     """ctk_form_query of include/contrack_hip_debug.h"""
-    _fields_ = [(n, C.c_int64) for n in (
-        "T nt ny nx f64 aligned16 field max_runs_step total_runs n_labels last_nlab async_passes no_sys n_cus seg pslot path forced_extent forced_run_values forced_compact_init spec_set launched").split()]
+    _fields_ = ABI.structs["ctk_form_query"]
 
 
 class FormPlan(C.Structure):
     """ctk_form_plan of include/contrack_hip_debug.h"""
-    _fields_ = [(n, C.c_int64) for n in (
-        "thr_kind thr_u7 thr_rbt thr_grid rowcount_threads v0b v0_ok v0_runs need_glb spec_launched spec_bits missing missing_bits next_spec overlap_form extent_form write_kernel write_rb write_sub write_kb write_batched write_lds write_grid write_shape chunk_copy runval_threads compact_init_threads count_staged count_fused filter_sys filter_passes filter_blk filter_two_pc filter_nb filter_unite filter_merged filter_bits filter_bits_sync round_blk round_two_pc round_nb rowcount_groups").split()]
+    _fields_ = ABI.structs["ctk_form_plan"]
 
 
 def debug_band_plan(T, nx, aligned16=True, form=-1, rows=-1):
@@ -218,219 +198,12 @@ def lib():
             "libcontrack_hip.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C contrack_amd/csrc`; the HIP path has no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    p, i64, i32, dbl, sz = C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_size_t
-    pp = C.POINTER(C.c_void_p)
-    L.ctk_last_error.restype = C.c_char_p
-    L.ctk_create.argtypes = [pp, i32]
-    L.ctk_destroy.argtypes = [p]
-    L.ctk_destroy.restype = None
-    track_args = [p, p, i64, i32, i32, p, i32, p, dbl, i32, i32, p, C.POINTER(i64)]
-    L.ctk_track_f32.argtypes = track_args
-    L.ctk_track_f32_dev.argtypes = track_args
-    L.ctk_track_f64.argtypes = track_args
-    L.ctk_track_f64_dev.argtypes = track_args
-    L.ctk_release_io.argtypes = [p]
-    L.ctk_set_threshold_field.argtypes = [p, p, i32, i64, i32, i32, p, i64]
-    L.ctk_set_segments.argtypes = [p, p, i64]
-    L.ctk_track_stream_f32.argtypes = track_args + [i64]
-    L.ctk_track_stream_f64.argtypes = track_args + [i64]
-    L.ctk_track_stream_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, p, i32, p, dbl, i32, i32, WRITE_CHUNK_FN, p, C.POINTER(i64), i64]
-    L.ctk_track_stream_seg_f32.argtypes = track_args + [i64, p, i64]
-    L.ctk_track_stream_seg_f64.argtypes = track_args + [i64, p, i64]
-    L.ctk_track_stream_seg_cb.argtypes = L.ctk_track_stream_cb.argtypes + [p, i64]
-    L.ctk_stream_times.argtypes = [p, C.POINTER(dbl)]
-    L.ctk_frequency_dev.argtypes = [p, p, i64, i32, i32, p, i32, C.c_int32, p, i32]
-    L.ctk_frequency.argtypes = [p, p, i64, i32, i32, p, i32, C.c_int32, p, i64]
-    L.ctk_frequency_cb.argtypes = [p, i64, i32, i32, READ_CHUNK_FN, p, p, i32, C.c_int32, p, i64]
-    L.ctk_debug_set_freq.argtypes = [p, i64, i32]
-    spell_args = [p, i32, p, i64, C.c_int32, i32, i64, p, p, p]                 # group, ngroups, seg_starts, nseg, above, by_id, min_duration, 3 maps
-    L.ctk_spells_dev.argtypes = [p, p, i64, i32, i32] + spell_args
-    L.ctk_spells.argtypes = [p, p, i64, i32, i32] + spell_args + [i64]
-    L.ctk_spells_cb.argtypes = [p, i64, i32, i32, READ_CHUNK_FN, p] + spell_args + [i64]
-    L.ctk_debug_set_spell.argtypes = [p, i64]
-    L.ctk_debug_time_spell.argtypes = [p, p, i64, i32, i32] + spell_args + [i32, C.POINTER(dbl)]
-    for fn in (L.ctk_composite_f32_dev, L.ctk_composite_f64_dev):
-        fn.argtypes = [p, p, p, i64, i32, i32, p, i32, C.c_int32, i32, p, p, i32]
-    for fn in (L.ctk_composite_f32, L.ctk_composite_f64):
-        fn.argtypes = [p, p, p, i64, i32, i32, p, i32, C.c_int32, i32, p, p, i64]
-    L.ctk_composite_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, READ_CHUNK_FN, p, p, i32, C.c_int32, i32, p, p, i64]
-    L.ctk_debug_composite_plan.argtypes = [i32, i64, i32, p]
-    L.ctk_debug_set_composite.argtypes = [p, i32]
-    L.ctk_debug_composite_launch.argtypes = [p, p]
-    L.ctk_debug_time_composite.argtypes = [p, p, p, i32, i64, i32, i32, p, i32, C.c_int32, i32, p, p, i32, C.POINTER(dbl)]
-    L.ctk_debug_time_freq.argtypes = [p, p, i64, i32, i32, p, i32, C.c_int32, p, i32, C.POINTER(dbl)]
-    stamp_args = [i64, p, p, p, p, i32, i32, i32, i32, i32]                   # R, t, row, col, bin, nbins, hy, hx, wrap, skipna
-    for fn in (L.ctk_centred_f32_dev, L.ctk_centred_f64_dev):
-        fn.argtypes = [p, p, i64, i32, i32] + stamp_args + [p, p, i32]
-    for fn in (L.ctk_centred_f32, L.ctk_centred_f64):
-        fn.argtypes = [p, p, i64, i32, i32] + stamp_args + [p, p, i64]
-    L.ctk_centred_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p] + stamp_args + [p, p, i64]
-    L.ctk_debug_centred_plan.argtypes = [i32, i32, i32, i32, i64, i64, i32, i32, i32, p]
-    L.ctk_debug_set_centred.argtypes = [p, i32, i32, i32]
-    L.ctk_debug_centred_launch.argtypes = [p, p]
-    L.ctk_debug_time_centred.argtypes = [p, p, i32, i64, i32, i32] + stamp_args + [p, p, i32, i32, C.POINTER(dbl)]
-    band_tail = [C.POINTER(BandSpec), C.POINTER(BandOut)]
-    L.ctk_band_dev.argtypes = [p, p, p, i32, i64, i32, i32] + band_tail
-    for fn in (L.ctk_band_f32, L.ctk_band_f64):
-        fn.argtypes = [p, p, p, i64, i32, i32] + band_tail + [i64]
-    L.ctk_band_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, READ_CHUNK_FN, p] + band_tail + [i64]
-    L.ctk_debug_band_plan.argtypes = [i64, i32, i32, i32, i32, p]
-    L.ctk_debug_set_band.argtypes = [p, i32, i32]
-    L.ctk_debug_band_launch.argtypes = [p, p]
-    L.ctk_debug_time_band.argtypes = [p, p, p, i32, i64, i32, i32] + band_tail + [i32, C.POINTER(dbl)]
-    L.ctk_shard_label2d.argtypes = [p, p, i64, i32, i32, p, i32, p, i32]
-    L.ctk_shard_label2d_f64.argtypes = [p, p, i64, i32, i32, p, i32, p, i32]
-    L.ctk_shard_halo_size.argtypes = [p, C.POINTER(sz)]
-    L.ctk_shard_halo_export.argtypes = [p, pp, C.POINTER(sz)]
-    L.ctk_shard_halo_import.argtypes = [p, p, sz]
-    L.ctk_shard_overlap.argtypes = [p]
-    L.ctk_shard_tables.argtypes = [p, pp, C.POINTER(sz)]
-    L.ctk_resolve.argtypes = [pp, C.POINTER(sz), i32, dbl, i32, pp]
-    L.ctk_result_free.argtypes = [p]
-    L.ctk_result_free.restype = None
-    L.ctk_result_info.argtypes = [p] + [C.POINTER(i64)] * 5
-    L.ctk_result_arrays.argtypes = [p, pp, C.POINTER(i64), pp, C.POINTER(i64), pp, pp]
-    L.ctk_result_nshards.argtypes = [p]
-    L.ctk_weights_to_limbs.argtypes = [p, i32, i64, p, p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.ctk_shard_extents.argtypes = [p, p, i32, i64, pp, C.POINTER(i64)]
-    L.ctk_shard_write.argtypes = [p, i32, p, C.POINTER(i64), C.POINTER(i32)]
-    L.ctk_shard_count_tracked.argtypes = [p, C.POINTER(i64)]
-    L.ctk_debug_mask.argtypes = [p, p]
-    L.ctk_debug_label2d.argtypes = [p, i32, p]
-    L.ctk_debug_set_pair_capacity.argtypes = [p, C.c_uint32]
-    L.ctk_debug_set_mailbox.argtypes = [p, C.c_uint32, C.c_uint32]
-    L.ctk_debug_set_seam_caps.argtypes = [p, i32, i32]
-    L.ctk_debug_shard_exchange.argtypes = [p, p]
-    L.ctk_debug_set_shared_ops_reserve.argtypes = [p, i64]
-    L.ctk_debug_set_spin.argtypes = [p, dbl, i32]
-    L.ctk_debug_set_small_threads.argtypes = [p, i32, i32, i32]
-    L.ctk_debug_forms.argtypes = [C.POINTER(FormQuery), C.POINTER(FormPlan)]
-    L.ctk_debug_live.argtypes = [C.POINTER(C.c_int64)]
-    L.ctk_debug_np_sum.argtypes = [p, sz]
-    L.ctk_debug_np_sum.restype = dbl
-    L.ctk_debug_boundary_resolve.argtypes = [i32, p, p, p, p, p, p, p, p, p]
-    L.ctk_debug_boundary_resolve_breaks.argtypes = [i32, p, p, p, p, p, p, p, p, p, p]
-    L.ctk_set_timing.argtypes = [p, i32]
-    L.ctk_get_timings.argtypes = [p, p]
-    L.ctk_get_timing_sums.argtypes = [p, p, p, i32]
-    L.ctk_set_device_resolve.argtypes = [p, i32]
-    L.ctk_set_fused_pass.argtypes = [p, i32]
-    L.ctk_set_result_transfer.argtypes = [p, i32]
-    L.ctk_expand_runs_host.argtypes = [p, p, p, p, i64, i32, i32, p, p, p]
-    L.ctk_get_stats.argtypes = [p, p]
-    L.ctk_get_stats_n.argtypes = [p, p, i32]
-    L.ctk_debug_stream_ceiling.argtypes = [p, p, sz, i32, i32, p]
-    L.ctk_debug_time_relabel.argtypes = [p, p, i32, i32, i32, i32, p]
-    L.ctk_set_filter_round.argtypes = [p, i32]
-    L.ctk_dev_malloc.argtypes = [p, pp, sz]
-    L.ctk_dev_free.argtypes = [p, p]
-    L.ctk_host_alloc.argtypes = [p, pp, sz]
-    L.ctk_host_free.argtypes = [p, p]
-    L.ctk_host_register.argtypes = [p, p, sz]
-    L.ctk_host_unregister.argtypes = [p, p]
-    L.ctk_memcpy_h2d.argtypes = [p, p, p, sz]
-    L.ctk_memcpy_d2h.argtypes = [p, p, p, sz]
-    L.ctk_sync.argtypes = [p]
-    L.ctk_stream.argtypes = [p]
-    L.ctk_stream.restype = p
-    L.ctk_synth_fill.argtypes = [p, p, i64, i32, i32, C.c_uint64]
-    L.ctk_synth_fill_window.argtypes = [p, p, i64, i64, i32, i32, C.c_uint64]
-    L.ctk_checksum_i32_dev.argtypes = [p, p, i64, i64, p]
-    L.ctk_dev_memset.argtypes = [p, p, i32, sz]
-    L.ctk_check_flag_dev.argtypes = [p, p, p, i64, i32, i32, p, i32, i32, i64, p]
-    L.ctk_comm_set_timeout.argtypes = [p, dbl]
-    L.ctk_comm_failed.argtypes = [p, C.POINTER(i32), C.POINTER(i32)]
-    L.ctk_comm_abort_rank.argtypes = [p, i32]
-    L.ctk_debug_fail_at.argtypes = [p, i32]
-    for name in ("ctk_lifecycle_f32", "ctk_lifecycle_f64", "ctk_lifecycle_f32_dev", "ctk_lifecycle_f64_dev"):
-        getattr(L, name).argtypes = [p, p, p, i64, i32, i32, p, C.POINTER(i64)]
-    L.ctk_lifecycle_rows.argtypes = [p, p, i64]
-    L.ctk_lifecycle_exact.argtypes = [p, p, i64, p]
-    for name in ("ctk_lifecycle_stream_f32", "ctk_lifecycle_stream_f64"):
-        getattr(L, name).argtypes = [p, p, p, i64, i32, i32, p, i64, LIFE_PICK_FN, p, C.POINTER(i64), C.POINTER(i64)]
-    L.ctk_lifecycle_stream_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, READ_CHUNK_FN, p, p, i64, LIFE_PICK_FN, p, C.POINTER(i64), C.POINTER(i64)]
-    L.ctk_lifecycle_stream_exact.argtypes = [p, p, p, i64]
-    L.ctk_debug_lifecycle_plan.argtypes = [i64, i32, i32, i32, i64, i64, p]
-    L.ctk_debug_lifecycle_path.argtypes = [p, p, p, i64]
-    for name in ("ctk_anom_f32", "ctk_anom_f64"):
-        getattr(L, name).argtypes = [p, p, i64, i32, i32, p, i32, i32, i32, p, p, p, i32]
-    for name in ("ctk_anom_seg_f32", "ctk_anom_seg_f64"):
-        getattr(L, name).argtypes = L.ctk_anom_f32.argtypes + [p, i64]
-    for name in ("ctk_anom_stream_f32", "ctk_anom_stream_f64"):
-        getattr(L, name).argtypes = [p, p, i64, i32, i32, p, i32, i32, i32, p, i64, p, p, p, i64]
-    L.ctk_anom_stream_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p, p, i32, i32, i32, p, i64, p, p, WRITE_CHUNK_FN, p, i64]
-    L.ctk_debug_anom_form.argtypes = [p, C.POINTER(i64)]
-    L.ctk_debug_anom_plan.argtypes = [i32, i32, i64, i64, i64, i64, p]
-    L.ctk_debug_set_anom.argtypes = [p, i64, i64]
-    L.ctk_debug_anom_launch.argtypes = [p, p]
-    for name in ("ctk_level_mean_f32", "ctk_level_mean_f64"):
-        getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, p, i32, p, i32]
-    for name in ("ctk_level_mean_f32_dev", "ctk_level_mean_f64_dev"):
-        getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, p, i32, p]
-    for name in ("ctk_level_mean_stream_f32", "ctk_level_mean_stream_f64"):
-        getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, p, i32, p, i64, i32]
-    L.ctk_level_mean_stream_cb.argtypes = [p, i32, i64, i32, i32, i32, READ_CHUNK_FN, p, p, i32, WRITE_CHUNK_FN, p, i64, i32]
-    L.ctk_resident_level_mean.argtypes = [p, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-    L.ctk_resident_level_mean_generation.argtypes = [p, C.POINTER(C.c_uint64)]
-    L.ctk_anom_seg_resident.argtypes = [p, p, i32, i32, i32, p, p, p, i32, p, i64]
-    L.ctk_debug_level_plan.argtypes = [i32, i64, i64, i64, i32, p]
-    L.ctk_debug_level_form.argtypes = [p, p]
-    L.ctk_debug_set_level.argtypes = [p, i32, i64]
-    L.ctk_debug_time_level_mean.argtypes = [p, p, i32, i64, i32, i32, i32, p, i32, p, i32, C.POINTER(dbl)]
-    rows7 = [p, p, p, p, p, p, p]                                    # eq, po, eq2, dE, tS, tN, tS2
-    for name in ("ctk_reversal_f32", "ctk_reversal_f64"):
-        getattr(L, name).argtypes = [p, p, i64, i32, i32] + rows7 + [i32, p, i64, i32]
-    for name in ("ctk_reversal_f32_dev", "ctk_reversal_f64_dev"):
-        getattr(L, name).argtypes = [p, p, i64, i32, i32] + rows7 + [i32, p]
-    L.ctk_reversal_stream_cb.argtypes = [p, i32, i64, i32, i32, READ_CHUNK_FN, p] + rows7 + [i32, WRITE_CHUNK_FN, p, i64, i32]
-    L.ctk_debug_reversal_plan.argtypes = [i32, i64, i64, i64, i32, p]
-    L.ctk_debug_set_reversal.argtypes = [p, i32, i64]
-    L.ctk_debug_reversal_form.argtypes = [p, p]
-    L.ctk_debug_time_reversal.argtypes = [p, p, i32, i64, i32, i32] + rows7 + [i32, p, i32, C.POINTER(dbl)]
-    L.ctk_resident_anom.argtypes = [p, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-    L.ctk_resident_anom_generation.argtypes = [p, C.POINTER(C.c_uint64)]
-    L.ctk_track_resident.argtypes = [p, p, i32, p, dbl, i32, i32, p, C.POINTER(i64)]
-    for name in ("ctk_percentile_f32", "ctk_percentile_f64"):
-        getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, i32, dbl, C.POINTER(dbl)]
-    L.ctk_debug_percentile_values.argtypes = [p, p, i64]
-    L.ctk_debug_io_bytes.argtypes = [p, p]
-    for name in ("ctk_percentile_groups_f32", "ctk_percentile_groups_f64"):
-        getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, i32, p, i32, i32, dbl, p]
-    L.ctk_debug_percentile_groups_sweeps.argtypes = [p, C.POINTER(i64)]
-    L.ctk_debug_percentile_groups_plan.argtypes = [i32, i64, i32, i32, i64, p]
-    L.ctk_debug_percentile_groups_state.argtypes = [p, i32, p, p, p]
-    L.ctk_debug_time_percentile_groups.argtypes = [p, p, i64, i32, i32, i32, i32, p, i32, i32, dbl, i32, p, p]
-    for name in ("ctk_percentile_field_f32", "ctk_percentile_field_f64"):
-        getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, i32, p, i32, i32, dbl, p]
-    L.ctk_debug_percentile_field_plan.argtypes = [i32, i64, i32, i32, p]
-    L.ctk_debug_percentile_field_form.argtypes = [p, p]
-    L.ctk_debug_time_percentile_field.argtypes = [p, p, i32, i64, i32, i32, i32, i32, p, i32, i32, dbl, i32, p, p, p]
-    for name in ("ctk_std_field_f32", "ctk_std_field_f64"):
-        getattr(L, name).argtypes = [p, p, i64, i32, i32, i32, i32, p, i32, i32, i32, i32, p, p, p]
-    L.ctk_debug_std_field_plan.argtypes = [i32, i32, i32, p]
-    L.ctk_debug_std_field_form.argtypes = [p, p]
-    L.ctk_debug_time_std_field.argtypes = [p, p, i32, i64, i32, i32, i32, i32, p, i32, i32, i32, i32, i32, p, p]
-    L.ctk_comm_unique_id.argtypes = [p]
-    L.ctk_comm_init_rccl.argtypes = [p, p, i32, i32, pp]
-    L.ctk_comm_group_create.argtypes = [i32, pp]
-    L.ctk_comm_group_destroy.argtypes = [p]
-    L.ctk_comm_group_destroy.restype = None
-    L.ctk_comm_init_local.argtypes = [p, p, i32, pp]
-    L.ctk_comm_init_shm.argtypes = [p, C.c_char_p, i32, i32, pp]
-    L.ctk_comm_destroy.argtypes = [p]
-    L.ctk_comm_destroy.restype = None
-    L.ctk_comm_rank.argtypes = [p]
-    L.ctk_comm_world.argtypes = [p]
-    L.ctk_comm_barrier.argtypes = [p]
-    L.ctk_comm_allgather_host.argtypes = [p, p, p, sz]
-    L.ctk_comm_ops.argtypes = [p, C.POINTER(i64), C.POINTER(i64)]
-    L.ctk_comm_rccl_library.argtypes = []
-    L.ctk_comm_rccl_library.restype = C.c_char_p
-    sharded_args = [p, p, p, i64, i64, i64, i32, i32, p, i32, p, dbl, i32, i32, p, C.POINTER(i64)]
-    L.ctk_track_sharded_f32_dev.argtypes = sharded_args
-    L.ctk_track_sharded_f64_dev.argtypes = sharded_args
-    L.ctk_track_sharded_seg_f32_dev.argtypes = sharded_args + [p, i64]
-    L.ctk_track_sharded_seg_f64_dev.argtypes = sharded_args + [p, i64]
+    missing = [name for name in ABI.functions if not hasattr(L, name)]
+    if missing:
+        raise ContrackHipError("%s does not export %s, which the headers in %s declare" % (LIB_PATH, ", ".join(missing), INCLUDE_DIR))
+    for name, (restype, argtypes) in ABI.functions.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -554,7 +327,7 @@ def _spell_args(T, group=None, ngroups=None, segments=None, by_id=True, min_dura
 
 def _check_composite(rc):
     """check() for the composite entries: a bad argument is an InvalidArgumentError"""
-    if rc in (-1, -4):
+    if rc in (CTK_E_INVALID, CTK_E_RANGE):
         raise InvalidArgumentError("libcontrack_hip rc=%d: %s" % (rc, lib().ctk_last_error().decode("utf-8", "replace")))
     check(rc)
 
@@ -656,12 +429,12 @@ def _field_dtype(x):
 def check(rc):
     if rc != 0:
         msg = lib().ctk_last_error().decode("utf-8", "replace")
-        if rc == -3:
+        if rc == CTK_E_NOMEM:
             raise MemoryError(msg)
-        if rc in (-1, -4):
+        if rc in (CTK_E_INVALID, CTK_E_RANGE):
             raise ValueError(msg)
-        if rc == -7:
-            raise CommError("libcontrack_hip rc=-7: %s" % msg)
+        if rc == CTK_E_COMM:
+            raise CommError("libcontrack_hip rc=%d: %s" % (rc, msg))
         raise ContrackHipError("libcontrack_hip rc=%d: %s" % (rc, msg))
 
 
@@ -2171,7 +1944,7 @@ class Tracker:
             if len(chosen) > n:
                 raise ValueError("pick returned more indices than rows")
             np.ctypeslib.as_array(C.cast(idx, C.POINTER(C.c_int64)), shape=(max(int(n), 1),))[:len(chosen)] = chosen
-            nidx[0] = len(chosen)
+            C.cast(nidx, C.POINTER(C.c_int64))[0] = len(chosen)
         pcb = tr.wrap(LIFE_PICK_FN, pk) if pick is not None else LIFE_PICK_FN()          # (a NULL pointer: no rows are picked)
         n, nx_ = C.c_int64(0), C.c_int64(0)
         tail = (wrow.ctypes.data, int(chunk_steps), pcb, None, C.byref(n), C.byref(nx_))

@@ -21,6 +21,9 @@ def test_every_declared_entry_point_is_exported():
     missing = [n for n in prod + dbg if not hasattr(lib, n)]
     assert not missing, missing
     assert sorted(set(_native.EXPORTS) - set(prod) - set(dbg)) == []          # the binding's list names nothing undeclared
+    # the binding's list is what contrack_amd/_abi.py reads from the same headers: this expression finds the same names by its own route
+    assert sorted(_native.ABI.functions) == sorted(_native.EXPORTS) == sorted(prod + dbg)
+    assert len(set(_native.EXPORTS)) == len(_native.EXPORTS)
 
 
 def test_product_header_declares_no_test_hook():
