@@ -161,7 +161,7 @@ static int band_args_check(ctk_handle *h, const char *name, int64_t T, int ny, i
             return ctk_set_error(CTK_E_INVALID, "%s: sector %d = (x0=%d, len=%d) needs 0 <= x0 < %d and 1 <= len <= %d", name, s, x0, len, nx, nx);
     }
     if (!sp->columns && sp->nsect == 0) return ctk_set_error(CTK_E_INVALID, "%s: neither the column tables nor a sector is asked for", name);
-    if (T * (int64_t)std::max(sp->nsect, 1) > 0x7fffffffll * CTK_BAND_THREADS || T * (((int64_t)nx + 3) / 4) > 0x7fffffffll * CTK_BAND_THREADS)
+    if (!ctk_band_fits(T, nx, sp->nsect))
         return ctk_set_error(CTK_E_RANGE, "%s: T=%lld steps of %d columns are too many for one launch", name, (long long)T, nx);
     HIPCHK(hipSetDevice(h->device));
     return CTK_OK;

@@ -754,6 +754,13 @@ struct CtkBandPlan {
     int64_t quads;                // threads per step: ceil(nx / 4)
     unsigned grid;                // workgroups: ceil(T * quads / 256) (the entries refuse a T that does not fit)
 };
+// T steps go into one launch of k_band (a thread per quad of columns) and of k_band_sect (a thread per sector): gridDim.x * blockDim.x
+// stays below 2^32 work-items, as CTK_LEVEL_GRID_MAX keeps it for the striding kernels -- what the entries refuse otherwise
+inline bool ctk_band_fits(int64_t T, int nx, int nsect)
+{
+    const int64_t lim = 0xffffffffll - CTK_BAND_THREADS;                           // (a partial last workgroup is launched whole)
+    return T <= lim / std::max<int64_t>(nsect, 1) && T <= lim / (((int64_t)nx + 3) / 4);
+}
 // form: a test's choice (ctk_debug_set_band: 0 the vector form where it is legal, 1 the general form), rows: its batch, rounded down
 // to a power of two and capped; -1 the rule
 inline CtkBandPlan ctk_band_plan(int64_t T, int nx, bool aligned16, int form = -1, int rows = -1)
@@ -828,6 +835,7 @@ inline CtkCentredPlan ctk_centred_plan(int elem_bytes, int64_t nbins, int64_t wc
     p.threads = th;
     p.parts = (wcells + th - 1) / th;
     p.blocks = nbins * p.parts;
-    p.grid = (unsigned)std::min<int64_t>(p.blocks, CTK_CENTRED_GRID_MAX);
+    // (gridDim.x * blockDim.x stays below 2^32 work-items: the fed form's workgroups are 1024 wide, a quarter as many fit)
+    p.grid = (unsigned)std::min<int64_t>(p.blocks, p.form ? CTK_CENTRED_GRID_MAX / (64 * CTK_CENTRED_FED_WAVES / CTK_CENTRED_THREADS_MAX) : CTK_CENTRED_GRID_MAX);
     return p;
 }

@@ -97,7 +97,7 @@ def plan(elem_bytes, nbins, hy, hx, max_bin=0, kept=None, form=-1, unroll=-1, th
         u, th = 32 // max(elem_bytes, 4), 64
     u = min(u, 32)
     parts = (wcells + th - 1) // th
-    return dict(form=fed, unroll=u, threads=th, parts=parts, blocks=nbins * parts, grid=min(nbins * parts, 0xffffff))
+    return dict(form=fed, unroll=u, threads=th, parts=parts, blocks=nbins * parts, grid=min(nbins * parts, 0xffffff // 4 if fed else 0xffffff))
 
 
 def wide_case(dtype, T=23, ny=7, nx=12, R=40, nbins=3, seed=0):
