@@ -154,6 +154,16 @@ def reversal_plan(elem_bytes, ny, nx, steps, aligned=True):
     return dict(vec=int(v[0]), vpt=int(v[1]), bps=int(v[2]), blocks=int(v[3]), grid=int(v[4]), xcd=int(v[5]))
 
 
+def lwa_plan(elem_bytes, rows, nx, ndom=1, steps=1, aligned=True):
+    """ctk_debug_lwa_plan: what ctk_lwa_plan (csrc/ctk_forms.h) decides for a local-wave-activity launch whose longest domain has
+    `rows` rows, as a dict (ok 1 / 0 the domain does not fit in LDS, vec 1 vector / 0 scalar form, strip columns, nstrips, lds and
+    lds_sel bytes of the two kernels, blocks, grid, xcd of the integrals' launch, sel_blocks, sel_grid, sel_xcd of the contours');
+    no handle, no GPU"""
+    v = np.zeros(12, dtype=np.int64)
+    check(lib().ctk_debug_lwa_plan(int(elem_bytes), int(rows), int(nx), int(ndom), int(steps), int(bool(aligned)), v.ctypes.data))
+    return dict(zip(("ok", "vec", "strip", "nstrips", "lds", "lds_sel", "blocks", "grid", "xcd", "sel_blocks", "sel_grid", "sel_xcd"), (int(a) for a in v)))
+
+
 def composite_plan(elem_bytes, npix, unroll=-1):
     """ctk_debug_composite_plan: what ctk_composite_plan (csrc/ctk_forms.h) decides for a k_composite launch, as a dict (unroll: the
     widest batch of time steps, blocks, grid); unroll: what debug_set_composite would force; no handle, no GPU"""
@@ -271,6 +281,35 @@ def _reversal_rows(rows, ny):
             raise ValueError("rows[%r] must hold one value per latitude row (%d), not shape %s" % (key, ny, a.shape))
         keep.append(a)
     return [_ptr(a) for a in keep], keep
+
+
+LWA_PARTS = ('total', 'anticyclonic', 'cyclonic')
+
+
+def _lwa_rows(rows, ny):
+    """the row table of a local-wave-activity call (a mapping with dom_off, dom_rows, active, W, q, S; see contrack.lwa_rows) as the
+    seven table arguments of ctk_lwa_* (ndom first) and the arrays the pointers point into.  The library checks the values."""
+    off = np.ascontiguousarray(rows["dom_off"], dtype=np.int32)
+    if off.ndim != 1 or off.size not in (2, 3):
+        raise ValueError("rows['dom_off'] must hold ndom + 1 offsets for one or two domains")
+    dom = np.ascontiguousarray(rows["dom_rows"], dtype=np.int32)
+    if dom.ndim != 1 or dom.size < max(int(off.max()), 1):
+        raise ValueError("rows['dom_rows'] must hold the %d rows that dom_off names" % int(off.max()))
+    keep = [off, dom]
+    for key, dt in (("active", np.uint8), ("W", np.uint32), ("q", np.float64), ("S", np.float64)):
+        a = np.ascontiguousarray(rows[key], dtype=dt)
+        if a.shape != (ny,):
+            raise ValueError("rows[%r] must hold one value per latitude row (%d), not shape %s" % (key, ny, a.shape))
+        keep.append(a)
+    return [int(off.size) - 1] + [_ptr(a) for a in keep], keep
+
+
+def _lwa_part(part):
+    if isinstance(part, str):
+        if part not in LWA_PARTS:
+            raise ValueError("part={!r}: one of {}".format(part, LWA_PARTS))
+        return LWA_PARTS.index(part)
+    return int(part)
 
 
 def _group_ids(group, T):
@@ -1518,6 +1557,77 @@ class Tracker:
         """(form, workgroups) of the last reversal launch"""
         v = np.zeros(2, dtype=np.int64)
         check(lib().ctk_debug_reversal_form(self._h, v.ctypes.data))
+        return int(v[0]), int(v[1])
+
+    # ---- local wave activity (ctk_lwa_*) ---------------------------------------------------------------------------
+    def lwa(self, x, rows, part='total', chunk_steps=0, keep_resident=False, want_out=True, want_ref=False):
+        """x (steps, ny, nx) float32 / float64 (an array or np.memmap), a height field that falls towards the pole; rows: the row
+        table (contrack.lwa_rows: dom_off, dom_rows, active, W, q, S).  Returns the (steps, ny, nx) local wave activity in x's
+        dtype (None without want_out) -- part 'total' / 0, 'anticyclonic' / 1 or 'cyclonic' / 2; 0 on inactive rows
+        (include/contrack_hip.h) -- and, with want_ref, (that, ref): ref (steps, ny) the equivalent-latitude contours.
+        chunk_steps: steps per chunk on their way through the device (0: about 256 MB of input); same bits.  keep_resident: the
+        result stays in HBM as the field to track (track_resident)."""
+        x = _float_array(x, 3, "x must be (steps, lat, lon)")
+        steps, ny, nx = x.shape
+        args, _keep = _lwa_rows(rows, ny)
+        if not want_out and not keep_resident:
+            raise ValueError("want_out=False without keep_resident asks for nothing")
+        out = np.empty((steps, ny, nx), dtype=x.dtype) if want_out else None
+        ref = np.empty((steps, ny), dtype=x.dtype) if want_ref else None
+        fn = lib().ctk_lwa_f64 if x.dtype == np.float64 else lib().ctk_lwa_f32
+        check(fn(self._h, x.ctypes.data, steps, ny, nx, *args, _lwa_part(part), _ptr(out), _ptr(ref), int(chunk_steps or 0), int(bool(keep_resident))))
+        return (out, ref) if want_ref else out
+
+    def lwa_cb(self, reader, shape, dtype, rows, part='total', sink=None, chunk_steps=0, keep_resident=False, want_ref=False):
+        """lwa with a reader(t0, nt, out) that fills `out`, a (nt, ny, nx) view of pinned memory, with the steps [t0, t0 + nt);
+        shape = (steps, ny, nx).  sink: None (a new array is returned), False (nothing leaves the device: keep_resident), a
+        C-contiguous (steps, ny, nx) array of `dtype`, or a writer(t0, nt, values).  Reader and writer see every step once, in
+        rising order.  want_ref: returns (the array or None, ref)."""
+        if shape is None or dtype is None:
+            raise ValueError("a reader needs shape=(steps, ny, nx) and dtype")
+        steps, ny, nx = (int(v) for v in shape)
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("the field must be float32 or float64")
+        args, _keep = _lwa_rows(rows, ny)
+        out, sink = _value_sink(sink, (steps, ny, nx), dt, "steps", "field", "keep_resident", keep_resident)
+        ref = np.empty((steps, ny), dtype=dt) if want_ref else None
+        tr = _Trampolines()
+        rcb, wcb = tr.reader(reader, _float_ctype(dt), (ny, nx)), tr.writer(sink, _float_ctype(dt), (ny, nx))
+        tr.finish(lib().ctk_lwa_stream_cb(self._h, dt.itemsize, steps, ny, nx, rcb, None, *args, _lwa_part(part), wcb, None, _ptr(ref), int(chunk_steps or 0),
+                                          int(bool(keep_resident))))
+        return (out, ref) if want_ref else out
+
+    def lwa_dev(self, x_dev, steps, ny, nx, rows, out_dev, part='total', f64=False, want_ref=False):
+        """ctk_lwa_*_dev: x and out (steps, ny, nx) in device memory; want_ref: returns the contours (steps, ny) on the host"""
+        args, _keep = _lwa_rows(rows, ny)
+        ref = np.empty((int(steps), int(ny)), dtype=np.float64 if f64 else np.float32) if want_ref else None
+        fn = lib().ctk_lwa_f64_dev if f64 else lib().ctk_lwa_f32_dev
+        check(fn(self._h, x_dev, int(steps), int(ny), int(nx), *args, _lwa_part(part), out_dev, _ptr(ref)))
+        return ref
+
+    def time_lwa(self, x_dev, steps, ny, nx, rows, out_dev, stage, part='total', f64=False, reps=5):
+        """measurement (tools/lwa_probe.py): (best, mean) ms of one stage alone on 16-byte aligned slabs in device memory, HIP
+        events -- stage 1 the contours, 2 the integrals, 0 the plain copy kernel over the same two buffers (rows may be None)"""
+        args, _keep = ([1] + [None] * 6, None) if rows is None else _lwa_rows(rows, ny)
+        ms = (C.c_double * 2)()
+        check(lib().ctk_debug_time_lwa(self._h, x_dev, int(bool(f64)), int(steps), int(ny), int(nx), *args, _lwa_part(part), out_dev, int(stage), int(reps), ms))
+        return float(ms[0]), float(ms[1])
+
+    def debug_set_lwa(self, xcd=-1, grid_max=0):
+        """for the following lwa launches (both kernels) -- xcd: how workgroups map to XCDs (0 launch order, 1 one contiguous eighth
+        per XCD, n > 1 tiles of n; -1: the library's rule, ctk_lwa_plan); grid_max: a lower cap on the workgroups of a launch (0:
+        the rule's)"""
+        check(lib().ctk_debug_set_lwa(self._h, int(xcd), int(grid_max)))
+
+    def debug_lwa_form(self):
+        """the form of the last lwa launch: 1 vector (16-byte loads of the strip), 0 scalar, -1 none yet"""
+        return self.debug_lwa_launch()[0]
+
+    def debug_lwa_launch(self):
+        """(form, workgroups) of the last k_lwa_integral launch"""
+        v = np.zeros(2, dtype=np.int64)
+        check(lib().ctk_debug_lwa_form(self._h, v.ctypes.data))
         return int(v[0]), int(v[1])
 
     def anomalies_resident(self, group, ngroups, window=1, smooth=1, clim=None, segments=None, keep_resident=False, want_anom=True, want_clim=False):

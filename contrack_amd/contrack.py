@@ -724,6 +724,104 @@ def reversal_numpy(z, lat, delta=15., ghgs=0., ghgn=-10., ghgs2=None, lat_bounds
     return _tracker(device).reversal(z, rows, mask=stat == 'mask', chunk_steps=chunk_steps or 0)
 
 
+_LWA_PARTS = ('total', 'anticyclonic', 'cyclonic')
+
+
+def lwa_rows(lat, lat_bounds=(30, 75), hemisphere='both', radius=6.371e6):
+    """the row table of the local wave activity (ctk_lwa_*) on the latitude coordinate `lat` (degrees; rising, falling or in any
+    order, regular or not), as a dict:
+        ndom, dom_off (ndom + 1), dom_rows   one or two DOMAINS ('north': the rows with lat >= 0, 'south': lat <= 0, 'both': north
+                                             then south), each the row indices sorted by |lat|: from the equator side to the pole;
+                                             an equator row is in both
+        W (ny,) uint32    rint(max(cos(lat), 0) * 2^30): the area weight of a pixel of the row (a pole row: 0)
+        q (ny,) float64   max(cos(lat), 0) * dphi, dphi the trapezoid width of the row inside its domain in radians: half the
+                          distance between its two neighbours, at both ends half the distance to the one neighbour (an equator
+                          row takes the width it has in the first domain)
+        S (ny,) float64   radius / cos(lat) on ACTIVE rows, 0 elsewhere (radius 6.371e6: a height in m gives m^2)
+        active (ny,) uint8   lat_bounds[0] <= |lat| <= lat_bounds[1], 0 < lat_bounds[0], inside a requested domain
+    ValueError if the band reaches a pole row: no area lies poleward of it (W = 0), so it has no equivalent latitude."""
+    lat = np.asarray(lat, dtype=np.float64)
+    if lat.ndim != 1 or lat.size < 1 or not np.all(np.isfinite(lat)) or np.any(np.abs(lat) > 90):
+        raise ValueError("lat must be a 1-D coordinate of finite values within [-90, 90]")
+    if hemisphere not in _HEMISPHERES:
+        raise ValueError("hemisphere={!r}: one of {}".format(hemisphere, _HEMISPHERES))
+    b = np.asarray(lat_bounds, dtype=np.float64).reshape(-1)
+    if b.size != 2 or not np.all(np.isfinite(b)) or b[0] > b[1] or not b[0] > 0:
+        raise ValueError("lat_bounds must be (low, high) with 0 < low <= high, in degrees of |latitude|")
+    if not (np.isfinite(radius) and radius > 0):
+        raise ValueError("radius must be a length > 0, not {!r}".format(radius))
+    ny = lat.size
+    cosl = np.maximum(np.cos(np.deg2rad(lat)), 0.0)
+    W = np.rint(cosl * 2.0 ** 30).astype(np.uint32)
+    q, S, active, seen = np.zeros(ny), np.zeros(ny), np.zeros(ny, dtype=np.uint8), np.zeros(ny, dtype=bool)
+    doms = []
+    for name, inside in (('north', lat >= 0), ('south', lat <= 0)):
+        if hemisphere not in ('both', name):
+            continue
+        idx = np.flatnonzero(inside)
+        if not idx.size:
+            raise ValueError("lat has no row in the {}ern hemisphere".format(name))
+        dom = idx[np.argsort(np.abs(lat[idx]), kind='stable')]
+        phi = np.deg2rad(np.abs(lat[dom]))
+        dphi = np.zeros(dom.size)
+        if dom.size > 1:
+            dphi[1:-1] = (phi[2:] - phi[:-2]) / 2
+            dphi[0], dphi[-1] = (phi[1] - phi[0]) / 2, (phi[-1] - phi[-2]) / 2
+        new = ~seen[dom]
+        q[dom[new]] = cosl[dom[new]] * dphi[new]
+        seen[dom] = True
+        act = dom[(np.abs(lat[dom]) >= b[0]) & (np.abs(lat[dom]) <= b[1])]
+        poleward = np.cumsum(W[dom][::-1].astype(np.uint64))[::-1]                  # the area weight of a row and of those poleward of it
+        empty = dom[(poleward == 0) & np.isin(dom, act)]
+        if empty.size:
+            raise ValueError("lat_bounds {} reach the pole row(s) at latitude {}: no area lies poleward of them, so they have no equivalent "
+                             "latitude; end the band below the pole".format(tuple(b.tolist()), lat[empty].tolist()))
+        active[act] = 1
+        S[act] = np.float64(radius) / np.cos(np.deg2rad(lat[act]))
+        doms.append(dom.astype(np.int32))
+    return dict(ndom=len(doms), dom_off=np.concatenate([[0], np.cumsum([d.size for d in doms])]).astype(np.int32), dom_rows=np.concatenate(doms),
+                active=active, W=W, q=q, S=S)
+
+
+def lwa_numpy(z, lat, lat_bounds=(30, 75), hemisphere='both', radius=6.371e6, part='total', chunk_steps=None, device=None, return_reference=False,
+              shape=None, dtype=None):
+    """finite-amplitude local wave activity (Huang & Nakamura 2016; Chen, Lu, Burrows & Leung 2015; Martineau et al. 2017; Nakamura
+    & Huang 2018) of a (steps, lat, lon) float field z on the GPU (ctk_lwa_*).  z is a height field that FALLS towards the pole --
+    500 hPa geopotential height in metres, say; for a field that rises towards the pole, such as PV, pass its negative.  Per step,
+    hemisphere and active row j (lwa_rows): Z_j is the contour whose poleward area equals that of the cap poleward of row j
+    (exactly, by area-weighted selection among the hemisphere's pixels); per column, a = the integral of z - Z_j over the rows
+    poleward of j (j included) where z > Z_j (anticyclonic: a ridge displaced poleward), y = the integral of Z_j - z over the rows
+    equatorward of j where z < Z_j (cyclonic), both a cos(lat) dphi in float64; the result is radius / cos(lat_j) times a + y
+    (part='total'), a ('anticyclonic': what blocks are made of) or y ('cyclonic').  Inactive rows are 0; a row whose contour the
+    NaNs of the plane make unreachable is NaN.  The result has z's shape and dtype (float32 kept, anything else float64):
+    track_numpy(..., threshold=<a percentile of it>, gorl='>') tracks it as it is.
+    z: an array or np.memmap, or -- with shape=(steps, ny, nx) and dtype -- a reader(t0, nt, out) that fills out (nt, ny, nx).
+    chunk_steps: steps per chunk on their way through the device (None / 0: about 256 MB of input); same bits.
+    return_reference: returns (lwa, ref), ref (steps, ny) the contours Z_j (0 on inactive rows)."""
+    if part not in _LWA_PARTS:
+        raise ValueError("part={!r}: one of {}".format(part, _LWA_PARTS))
+    if chunk_steps is not None and int(chunk_steps) < 0:
+        raise ValueError("chunk_steps must be >= 0")
+    rows = lwa_rows(lat, lat_bounds, hemisphere, radius)
+    ny = len(rows["W"])
+    if callable(z):
+        if shape is None or dtype is None or len(shape) != 3:
+            raise ValueError("a reader needs shape=(steps, ny, nx) and dtype")
+        if int(shape[1]) != ny:
+            raise ValueError("lat holds {} values, the field has {} rows".format(ny, shape[1]))
+        return _tracker(device).lwa_cb(z, shape, dtype, rows, part=part, chunk_steps=chunk_steps or 0, want_ref=return_reference)
+    z = np.asarray(z) if not isinstance(z, np.memmap) else z
+    if z.ndim != 3:
+        raise ValueError("z must be (steps, lat, lon)")
+    if z.shape[1] != ny:
+        raise ValueError("lat holds {} values, the field has {} rows".format(ny, z.shape[1]))
+    if z.dtype.kind != "f":
+        if z.dtype.kind not in "iub":
+            raise TypeError("z must be a real numeric array")
+        z = z.astype(np.float64)
+    return _tracker(device).lwa(z, rows, part=part, chunk_steps=chunk_steps or 0, want_ref=return_reference)
+
+
 def percentile_groups_numpy(anom, rows, group, q, window=1, device=None):
     """the threshold recipe of README.rst:235-240 on a (time, lat, lon) float slab: per group g (one id in [0, G) per timestep,
     G = max(group) + 1, any order in time) the q-quantile of rows[0] <= y < rows[1] pooled over every timestep whose group lies in
@@ -1445,6 +1543,66 @@ class contrack(object):
             self._anom_resident = (_fingerprint(np.asarray(self.ds[name].data)), trk.resident_generation())
             self._anom_resident_name = name
         logger.info('Calculating gradient reversal... DONE')
+
+    # ---- finite-amplitude local wave activity: the third family of blocking indices ------------------------------------------
+    def calc_lwa(self, variable, lat_bounds=(30, 75), hemisphere='both', part='total', name='lwa', radius=6.371e6, chunk_steps=None, reference=None):
+        """adds the variable `name`: the finite-amplitude local wave activity of `variable` (Huang & Nakamura 2016; Chen, Lu,
+        Burrows & Leung 2015 for 500 hPa height, with the anticyclonic / cyclonic split; Martineau et al. 2017; Nakamura & Huang
+        2018), computed on the GPU (lwa_numpy).  `variable` is a height field that falls towards the pole; for a field that rises
+        towards the pole, such as PV, pass its negative.  At latitude phi (lat_bounds[0] <= |phi| <= lat_bounds[1], 0 <
+        lat_bounds[0], in the selected hemisphere: 'both', 'north', 'south') the contour Z whose poleward area equals that of the
+        cap poleward of phi is found per time step and hemisphere; the activity of a grid point is radius / cos(phi) times the
+        meridional integral of the displaced field: z - Z poleward of phi where z > Z ('anticyclonic': ridges, the part blocks
+        are made of) plus Z - z equatorward of phi where z < Z ('cyclonic': troughs); part='total' is their sum.  Units
+        `<units> m` (radius in m).  percentile_threshold(variable=name, ...) / percentile_field give the threshold, and
+        run_contrack(variable=name, threshold=..., gorl='>') tracks the blocked regions.  Every dimension besides latitude and
+        longitude (time, a member dimension ...) counts steps, each on its own; any dim order is accepted and kept.
+        chunk_steps: the variable is read slice by slice (`isel` on the step dims) and passes through chunk-sized device buffers;
+        the host slab is never built.  Without it, for a (time, lat, lon) variable in any order, the result also stays in HBM and
+        a following run_contrack(variable=name) starts from there (its host twin is read-only, as calc_anom's).
+        reference='<name>': also adds the contours Z as a (steps..., lat) variable (0 outside lat_bounds)."""
+        self._ensure_set_up()
+        if part not in _LWA_PARTS:
+            raise ValueError("part={!r}: one of {}".format(part, _LWA_PARTS))
+        if chunk_steps is not None and int(chunk_steps) < 0:
+            raise ValueError("chunk_steps must be >= 0")
+        da, view, resident, streamed = self._every_step(variable, chunk_steps)
+        dims = view.dims
+        lat = np.asarray(self.ds[self._latitude_name].data)
+        rows = lwa_rows(lat, lat_bounds, hemisphere, radius)
+        want_ref = reference is not None
+        trk = _tracker()
+        logger.info('Calculating local wave activity of {} on {} of {} rows...'.format(variable, int(np.count_nonzero(rows["active"])), view.shape[1]))
+        if streamed:
+            res = trk.lwa_cb(view.reader(), view.shape, _producer_dtype(da.dtype), rows, part=part, chunk_steps=int(chunk_steps), want_ref=want_ref)
+        else:
+            arr = view.slab()
+            if arr.dtype.kind != "f":
+                arr = arr.astype(np.float64)
+            res = trk.lwa(arr, rows, part=part, keep_resident=resident, want_ref=want_ref)
+        res, ref = res if want_ref else (res, None)
+        if resident:
+            res.flags.writeable = False                      # (its twin stays in HBM for run_contrack: see _fingerprint)
+        out = view.restore(res, dims)
+        units = da.attrs.get('units')
+        history = 'Calculated from {} with input attributes: lat_bounds = {}, hemisphere = {}, part = {}, radius = {}.'.format(
+            variable, tuple(np.asarray(lat_bounds).tolist()), hemisphere, part, radius)
+        attrs = {'units': '{} m'.format(units) if units else 'm',
+                 'long_name': da.attrs.get('long_name', variable) + (' local wave activity' if part == 'total' else ' {} local wave activity'.format(part)),
+                 'history': history}
+        self.ds[name] = (dims, out, attrs)
+        if want_ref:
+            ref_dims = tuple(d for d in dims if d != self._longitude_name)
+            rattrs = {'long_name': da.attrs.get('long_name', variable) + ' equivalent-latitude contour', 'history': history}
+            if units:
+                rattrs['units'] = units
+            have = view.step_dims + (self._latitude_name,)
+            self.ds[reference] = (ref_dims, ref.reshape(view.step_shape + ref.shape[1:]).transpose([have.index(d) for d in ref_dims]), rattrs)
+        if resident:
+            # (the resident slot now holds this field: the record of calc_anom's slab, if any, is replaced with it)
+            self._anom_resident = (_fingerprint(np.asarray(self.ds[name].data)), trk.resident_generation())
+            self._anom_resident_name = name
+        logger.info('Calculating local wave activity... DONE')
 
     # ---- climatology / anomaly (contrack.py:458-581) on the device: SURVEY.md section 8(f) row N2 ------------------------
     def _group_ids(self, groupby):

@@ -296,6 +296,11 @@ struct ctk_handle {
     DevBuf gr_tab;
     int gr_form = -1, gr_xcd_dbg = -1;
     int64_t gr_grid = 0, gr_grid_dbg = 0;
+    // local wave activity (ctk_lwa.hip): the row table of the running call and the contours (steps, ny) of the last one; the form of the
+    // last k_lwa_integral launch, its workgroups, and ctk_debug_set_lwa's two numbers (as the reversal's)
+    DevBuf lw_tab, lw_ref;
+    int lw_form = -1, lw_xcd_dbg = -1;
+    int64_t lw_grid = 0, lw_grid_dbg = 0;
     DevBuf io_in, io_out;                          // device copies of host-array calls (ctk_track_f32 / _f64)
     uint64_t io_gen = 0;                           // bumped by claim_io and ctk_release_io: WHOSE data io_in / io_out hold
     // streaming entries (ctk_track_stream_*): the slab passes through two chunk-sized device buffers per direction
@@ -3502,7 +3507,7 @@ extern "C" int ctk_release_io(ctk_handle *h)
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
     HIPCHK(hipSetDevice(h->device));
-    for (DevBuf *b : {&h->io_in, &h->io_out, &h->an_out, &h->an_raw, &h->lv_out, &h->gr_tab}) b->release();
+    for (DevBuf *b : {&h->io_in, &h->io_out, &h->an_out, &h->an_raw, &h->lv_out, &h->gr_tab, &h->lw_tab, &h->lw_ref}) b->release();
     h->an_T = -1; h->an_gen++; h->an_pct_n = -1;
     h->lv_T = -1; h->lv_gen++;
     h->io_gen++; h->lc_flag = nullptr; h->lc_field = nullptr;          // (the exact rows of a lifecycle call read those slabs)
@@ -3977,6 +3982,7 @@ extern "C" int ctk_lifecycle_rows(ctk_handle *h, ctk_life_row *rows, int64_t cap
 #include "ctk_std.hip"
 #include "ctk_level.hip"
 #include "ctk_reversal.hip"
+#include "ctk_lwa.hip"
 #include "ctk_composite.hip"
 #include "ctk_centred.hip"
 #include "ctk_band.hip"

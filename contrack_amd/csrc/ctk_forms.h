@@ -690,6 +690,54 @@ inline CtkReversalRows ctk_reversal_rows(const int32_t *eq, const int32_t *po, c
 }
 
 // ------------------------------------------------------------------------------------------------
+// local wave activity (ctk_lwa.hip): k_lwa_contour, one workgroup per (step, domain) -- a domain is the rows of one hemisphere from
+// the equator side to the pole --, and k_lwa_integral, one workgroup per (step, domain, strip of columns) with the strip's domain
+// rows in LDS.  A strip is as wide as keeps rows x strip within CTK_LWA_CELLS pixels: a thread per (active row, column) then walks
+// the domain, and about half the rows are active.  Vector form: 16-byte loads into LDS -- aligned base pointers, rows and strips of
+// a multiple of 4 pixels; scalar form: pixel by pixel, strips of any width.  The capacity edge is the narrowest strip (4 pixels, or
+// 1) of the longest domain in CTK_LWA_LDS_MAX bytes, and k_lwa_contour's four 8-byte words per row (+ 1, + one per wave): beyond that the
+// plan says ok = 0 and the call ends with CTK_E_INVALID -- there is no other form.
+// ------------------------------------------------------------------------------------------------
+#define CTK_LWA_THREADS 256           // k_lwa_integral
+#define CTK_LWA_SEL_THREADS 1024      // k_lwa_contour: one workgroup has a whole (step, domain) to itself
+#define CTK_LWA_CELLS 2048            // pixels of a strip in LDS that the strip width aims at (rows x strip)
+#define CTK_LWA_LDS_MAX 65536         // dynamic LDS of a workgroup of either kernel
+struct CtkLwaPlan {
+    int ok;                       // 0: the longest domain does not fit in LDS at the narrowest strip
+    int vec;                      // 1: 16-byte loads of the strip, 0: the scalar form
+    int strip;                    // columns of a strip (vector form: a multiple of 4)
+    int64_t nstrips;              // strips of a row
+    int64_t lds;                  // bytes of LDS of a k_lwa_integral workgroup: rows x strip pixels
+    int64_t lds_sel;              // ... of a k_lwa_contour workgroup: 32 bytes per row + 1 (every row may be active), 8 per wave
+    int64_t blocks;               // k_lwa_integral: steps x domains x strips, walked by ...
+    unsigned grid;                // ... this many workgroups (CTK_LEVEL_GRID_MAX at most)
+    int xcd;                      // xcd_chunk mode of that launch: 1 one contiguous eighth of the workgroups per XCD, 0 launch order
+    int64_t sel_blocks;           // k_lwa_contour: steps x domains, walked by ...
+    unsigned sel_grid;            // ... this many workgroups
+    int sel_xcd;                  // xcd_chunk mode of that launch
+};
+// rows: the longest domain; aligned: input and output base pointers are multiples of 16; grid_max: CTK_LEVEL_GRID_MAX, or a test's lower cap
+inline CtkLwaPlan ctk_lwa_plan(int elem_bytes, int64_t rows, int64_t nx, int64_t ndom, int64_t steps, bool aligned, int64_t grid_max = CTK_LEVEL_GRID_MAX)
+{
+    CtkLwaPlan p = {};
+    p.vec = aligned && nx % 4 == 0;
+    const int64_t unit = p.vec ? 4 : 1;
+    const int64_t widest = (nx + unit - 1) / unit * unit;
+    p.strip = (int)std::min<int64_t>(std::max<int64_t>(CTK_LWA_CELLS / std::max<int64_t>(rows, 1) / unit, 1) * unit, widest);
+    p.nstrips = (nx + p.strip - 1) / p.strip;
+    p.lds = rows * p.strip * elem_bytes;
+    p.lds_sel = (rows + 1) * 32 + CTK_LWA_SEL_THREADS / 64 * 8;
+    p.ok = rows * unit * elem_bytes <= CTK_LWA_LDS_MAX && p.lds_sel <= CTK_LWA_LDS_MAX;
+    p.blocks = steps * ndom * p.nstrips;
+    p.grid = (unsigned)std::min<int64_t>(p.blocks, std::min<int64_t>(std::max<int64_t>(grid_max, 1), CTK_LEVEL_GRID_MAX));
+    p.xcd = p.grid >= CTK_LEVEL_XCD_MIN ? 1 : 0;
+    p.sel_blocks = steps * ndom;
+    p.sel_grid = (unsigned)std::min<int64_t>(p.sel_blocks, std::min<int64_t>(std::max<int64_t>(grid_max, 1), CTK_LEVEL_GRID_MAX));
+    p.sel_xcd = p.sel_grid >= CTK_LEVEL_XCD_MIN ? 1 : 0;
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------
 // rules every streamed entry shares
 // ------------------------------------------------------------------------------------------------
 // steps per chunk: chunk_steps, or (0) about 256 MB of input -- step_bytes is what one step brings in, a plane or the selected levels of

@@ -494,8 +494,8 @@ int ctk_anom_stream_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 *
                        const int32_t *group, int ngroups, int window, int smooth, const int64_t *starts, int64_t nseg, const void *clim_in,
                        void *clim_out, ctk_write_values_fn writer, void *writer_user, int64_t chunk_steps);
 int ctk_resident_anom(ctk_handle *h, int64_t *T, int *ny, int *nx, int *is_f64);       /* T = -1: nothing resident */
-/* The resident slot holds THE FIELD TO TRACK, whichever producer wrote it last: the anomalies of ctk_anom_* or the gradient-reversal
- * index of ctk_reversal_* (below), each with keep_resident.  ctk_resident_anom reports its shape.
+/* The resident slot holds THE FIELD TO TRACK, whichever producer wrote it last: the anomalies of ctk_anom_*, the gradient-reversal
+ * index of ctk_reversal_* or the local wave activity of ctk_lwa_* (below), each with keep_resident.  ctk_resident_anom reports its shape.
  * Identity of the resident slab: changes whenever one of those calls writes the slot or ctk_release_io drops it.  Remember it
  * after the call that left YOUR slab resident and use the slab only while it is unchanged. */
 int ctk_resident_anom_generation(ctk_handle *h, uint64_t *generation);
@@ -657,6 +657,59 @@ int ctk_reversal_f64_dev(ctk_handle *h, const double *x_dev, int64_t steps, int 
 int ctk_reversal_stream_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, int64_t steps, int ny, int nx, ctk_read_chunk_fn reader, void *reader_user,
                            const int32_t *eq, const int32_t *po, const int32_t *eq2 /* or NULL */, const double *dE, const double *tS, const double *tN,
                            const double *tS2 /* or NULL */, int mask, ctk_write_values_fn writer, void *writer_user, int64_t chunk_steps, int keep_resident);
+
+/* ---- finite-amplitude local wave activity: the third family of blocking indices ----------------------------------------------------
+ * Huang & Nakamura (2016); Chen, Lu, Burrows & Leung (2015) for Z500, with the anticyclonic / cyclonic split; Martineau et al. (2017);
+ * Nakamura & Huang (2018).  The reference has no function for it; tests/lwa_util.py is the numpy statement of what follows.
+ * x: (steps, ny, nx), float32 or float64, C-contiguous -- a height field that FALLS towards the pole (for a field that rises towards
+ * the pole, such as PV, pass its negative).  The kernels never see latitudes; the caller passes a ROW TABLE (contrack.lwa_rows builds
+ * it from lat[ny], lat_bounds, the hemisphere and a radius):
+ *     ndom = 1 or 2 DOMAINS; domain d is the rows dom_rows[dom_off[d] .. dom_off[d + 1]) = (d_0 .. d_{n-1}), ordered FROM THE EQUATOR
+ *             SIDE TO THE POLE (the rows with lat >= 0, resp. lat <= 0, sorted by |lat|; an equator row is in both domains)
+ *     W[ny]   uint32, the area weight of a pixel of the row: rint(max(cos(lat), 0) * 2^30); a pole row has W = 0
+ *     q[ny]   float64, finite and >= 0: max(cos(lat), 0) * dphi, dphi the trapezoid width of the row inside its domain in radians
+ *     S[ny]   float64: radius / cos(lat) on active rows, finite and > 0 (0 elsewhere)
+ *     active[ny]  0 / 1: rows with lat_bounds[0] <= |lat| <= lat_bounds[1] (0 < lat_bounds[0]) inside a requested domain
+ * Per step, per domain and per active row j = d_p:
+ *  1. the equivalent-latitude contour Z_j.  cap_j = nx * sum_{p' >= p} W[d_p'], exact in uint64.  The non-NaN pixels of the domain's
+ *     rows are ordered by the integer key of their value (a total order; -0.0 before +0.0); A(k) = sum of W[row] over the pixels
+ *     with key <= k, exact in uint64; Z_j = the value of the smallest key with A(k) >= cap_j.  No such key (NaNs ate the area):
+ *     Z_j = NaN and the whole output row j of this step is NaN.
+ *  2. the integrals, per column c, in float64, multiply and add rounded separately (no fused multiply-add), each sum started from
+ *     +0.0 and added IN DOMAIN ORDER (rising p'):
+ *         a = sum_{p' >= p, z[d_p'][c] > Z_j} ((double)z - (double)Z_j) * q[d_p']     anticyclonic: the ridge poleward of the contour, row j included
+ *         y = sum_{p' <  p, z[d_p'][c] < Z_j} ((double)Z_j - (double)z) * q[d_p']     cyclonic: the trough equatorward of it
+ *     A NaN pixel fails both compares and is skipped; +-inf are ordinary values: what IEEE arithmetic gives is the answer.
+ *  3. out[j][c] = (dtype)((a + y) * S[j])  (part = 0, 'total');  (dtype)(a * S[j])  (part = 1, 'anticyclonic');  (dtype)(y * S[j])
+ *     (part = 2, 'cyclonic'): one rounding to x's dtype.  Inactive rows are 0 and are not read unless an active row's domain holds them.
+ * ref (may be NULL): (steps, ny) in x's dtype, the Z_j -- 0 on inactive rows, NaN on unreachable ones.
+ * out has x's shape and dtype: ctk_track_* with a threshold and the op '>' tracks it as it is.
+ * CTK_E_INVALID with a message, the handle usable: a null pointer, a size below 1, ndom not 1 or 2, dom_off not rising from 0 or a
+ * domain longer than ny, a row index outside [0, ny) or twice in one domain, an active row in no domain or in two, a q (of a domain's
+ * row) that is not finite or negative, an S that is not finite and > 0 on an active row, cap_j == 0 on an active row, nx * sum W
+ * of a domain >= 2^63 (a defensive check: uint32 weights on a plane below 2^31 pixels cannot reach it), part outside 0 .. 2, a plane of 2^31 pixels or more, a domain too long for the kernels' LDS (more than 2 043
+ * rows: ctk_lwa_plan, csrc/ctk_forms.h -- there is no other form), chunk_steps < 0, nothing to produce (out NULL and keep_resident 0).
+ *
+ * ctk_lwa_f32_dev / _f64_dev: x and out in device memory (ref on the host).
+ * ctk_lwa_f32 / _f64: host arrays (out may be NULL with keep_resident).  Of every plane only the rows the domains span are uploaded
+ * (one strided copy per chunk) and only the rows the active rows span are downloaded; the rest of out is zeroed on the host.  Two
+ * input and two output chunks, as ctk_reversal_*.  chunk_steps = 0: about 256 MB of input per chunk.  Same bits for every chunk_steps.
+ * ctk_lwa_stream_cb: reader and writer as ctk_reversal_stream_cb's (whole planes; writer may be NULL with keep_resident); ref holds
+ * elem_bytes per value.
+ * keep_resident != 0: the full-plane result stays in HBM in the resident slot of THE FIELD TO TRACK, as ctk_reversal_*'s does, with
+ * a new ctk_resident_anom_generation.  A failing call leaves an earlier resident slab alone (argument errors) or dropped, never half
+ * written and reported. */
+int ctk_lwa_f32(ctk_handle *h, const float *x, int64_t steps, int ny, int nx, int ndom, const int32_t *dom_off, const int32_t *dom_rows, const uint8_t *active,
+                const uint32_t *W, const double *q, const double *S, int part, float *out /* or NULL */, float *ref /* or NULL */, int64_t chunk_steps, int keep_resident);
+int ctk_lwa_f64(ctk_handle *h, const double *x, int64_t steps, int ny, int nx, int ndom, const int32_t *dom_off, const int32_t *dom_rows, const uint8_t *active,
+                const uint32_t *W, const double *q, const double *S, int part, double *out /* or NULL */, double *ref /* or NULL */, int64_t chunk_steps, int keep_resident);
+int ctk_lwa_f32_dev(ctk_handle *h, const float *x_dev, int64_t steps, int ny, int nx, int ndom, const int32_t *dom_off, const int32_t *dom_rows, const uint8_t *active,
+                    const uint32_t *W, const double *q, const double *S, int part, float *out_dev, float *ref /* host, or NULL */);
+int ctk_lwa_f64_dev(ctk_handle *h, const double *x_dev, int64_t steps, int ny, int nx, int ndom, const int32_t *dom_off, const int32_t *dom_rows, const uint8_t *active,
+                    const uint32_t *W, const double *q, const double *S, int part, double *out_dev, double *ref /* host, or NULL */);
+int ctk_lwa_stream_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, int64_t steps, int ny, int nx, ctk_read_chunk_fn reader, void *reader_user, int ndom,
+                      const int32_t *dom_off, const int32_t *dom_rows, const uint8_t *active, const uint32_t *W, const double *q, const double *S, int part,
+                      ctk_write_values_fn writer, void *writer_user, void *ref /* or NULL */, int64_t chunk_steps, int keep_resident);
 
 /* ---- the blocking-frequency climatology of the reference's tutorial (README.rst:159-160) ---------------------------------------
  *   xr.where(block['flag'] > 1, 1, 0).sum(dim='time') / block.ntime * 100     -- on the int32 flag slab (T, ny, nx), per group:

@@ -289,6 +289,24 @@ int ctk_debug_reversal_form(ctk_handle *h, int64_t *out2);
 int ctk_debug_time_reversal(ctk_handle *h, const void *x_dev, int is_f64, int64_t steps, int ny, int nx, const int32_t *eq, const int32_t *po, const int32_t *eq2,
                             const double *dE, const double *tS, const double *tN, const double *tS2, int mask, void *out_dev, int reps, double *ms2);
 
+/* what ctk_lwa_plan (csrc/ctk_forms.h) decides for a ctk_lwa_* launch over `steps` steps of ndom (1 / 2) domains, the longest of
+ * `rows` rows of nx pixels of elem_bytes (4 / 8), `aligned`: both base pointers are multiples of 16.  out12 = { 1 the domain fits in
+ * LDS / 0 the call is refused, 1 the vector form (16-byte loads of the strip; nx a multiple of 4) / 0 the scalar form, columns of a
+ * strip, strips of a row, LDS bytes of a k_lwa_integral workgroup, LDS bytes of a k_lwa_contour workgroup, workgroups of work (steps x
+ * domains x strips), workgroups launched (at most 2^24 - 1; the kernel strides over the rest), 1 if every XCD takes one contiguous
+ * eighth of them (0: launch order), and the same three for k_lwa_contour (steps x domains) }.  Host only: no handle, no GPU. */
+int ctk_debug_lwa_plan(int elem_bytes, int64_t rows, int64_t nx, int64_t ndom, int64_t steps, int aligned, int64_t *out12);
+/* test hook / experiments for the following k_lwa_contour and k_lwa_integral launches on this handle: as ctk_debug_set_level */
+int ctk_debug_set_lwa(ctk_handle *h, int xcd_mode, int64_t grid_max);
+/* test hook: out2 = { the form of the last k_lwa_integral launch on this handle (1 vector, 0 scalar, -1 none yet), its workgroups } */
+int ctk_debug_lwa_form(ctk_handle *h, int64_t *out2);
+/* measurement (tools/lwa_probe.py): one stage of ctk_lwa_*_dev alone on slabs in device memory (16-byte aligned; is_f64 != 0: float64)
+ * between HIP events: one launch that is not counted, then `reps` timed ones; ms2 = { best, mean }.  stage 1: the contours, stage 2:
+ * the integrals on the contours of one stage-1 run, stage 0: a plain copy kernel (one 16-byte load and one 16-byte store per lane)
+ * over the same two buffers, the yardstick (the table arguments may be NULL). */
+int ctk_debug_time_lwa(ctk_handle *h, const void *x_dev, int is_f64, int64_t steps, int ny, int nx, int ndom, const int32_t *dom_off, const int32_t *dom_rows,
+                       const uint8_t *active, const uint32_t *W, const double *q, const double *S, int part, void *out_dev, int stage, int reps, double *ms2);
+
 /* what ctk_composite_plan (csrc/ctk_forms.h) decides for a k_composite launch over planes of npix pixels and a field of elem_bytes
  * (4 / 8); unroll: what ctk_debug_set_composite would force (-1: the rule).  out3 = { the widest batch of time steps in flight,
  * workgroups of work (256 pixels each), workgroups launched (at most 2^24 - 1; the kernel strides over the rest) }.  Host only: no
