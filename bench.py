@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- timesteps/s labelled+tracked on synthetic ERA5-like Z500 anomaly slabs (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload era5_1deg_djf30|era5_025deg|...] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload era5_1deg_djf30|era5_025deg|...] [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs and no more: set-up, W warm-up steps, K timed steps, the dump if asked for, the line
+(`value`, `ms_per_step`, `n_tracked`, the event times the timed steps collected themselves).  `--full` adds everything else the
+benchmark measures or checks, each in runs of its own after the timed steps: per-group kernel times and the roofline with its live
+traffic counters, the plain stream ceilings, the host-array (`e2e`) and four-handle legs, the CPU baseline, the 0.25 deg block;
+for N > 1 the in-run parity check against one one-call run, the strong-scaling block and the CPU baseline.  The `--no-*` options
+trim a `--full` run.
 
 A "step" is one pass of the hot path (threshold -> 2-D labelling with longitude wrap -> overlap filter ->
 3-D tracking -> persistence -> flag) over one batch: the whole (T, ny, nx) slab of the workload, already
@@ -445,9 +452,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="era5_1deg_djf30")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the untimed passes that time every kernel group (profiling runs)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the 0.25 deg block (`secondary_025deg`) of the default N = 1 line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else (CPU baseline, per-group kernel times, roofline with "
+                         "live traffic counters, stream ceilings, host-array and four-handle legs, the 0.25 deg block; N > 1: in-run parity "
+                         "check, strong-scaling block); without it the run ends with the timed steps' own figures")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU legs")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the untimed passes that time every kernel group (profiling runs)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the 0.25 deg block (`secondary_025deg`) of the N = 1 line")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="N > 1: weak = one member of the workload per GPU, concatenated on the time axis (default); "
                          "strong = the single-GPU slab split over the GPUs")
@@ -455,11 +466,12 @@ def main():
                     help="after the timed steps, write what the last timed step computed (flag slab summary and a seeded sample of its "
                          "timesteps, n_tracked) as float64 DIR/<name>.npy, 64 MB at most; e.g. bench_outputs/ (N = 1 only)")
     ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic from the committed capture under profiles/ instead of two rocprofv3 --pmc child runs")
+    ap.add_argument("--no-live-pmc", action="store_true",
+                    help="--full: roofline.traffic from the committed capture under profiles/ instead of two rocprofv3 --pmc child runs")
     ap.add_argument("--no-parity-check", action="store_true",
-                    help="N > 1: skip the in-run parity check (rank 0 tracks the concatenated slab with one call and compares checksums)")
+                    help="--full, N > 1: skip the in-run parity check (rank 0 tracks the concatenated slab with one call and compares checksums)")
     ap.add_argument("--strong-steps", type=int, default=-1,
-                    help="N > 1: timesteps of the device-generated 0.25 deg slab of the strong-scaling block (0 = skip; default: the 10-year "
+                    help="--full, N > 1: timesteps of the device-generated 0.25 deg slab of the strong-scaling block (0 = skip; default: the 10-year "
                          "slab of BASELINE.json configs[2], 14600 steps -- the size the north_star's >= 6x is stated on --, falling back to "
                          "2000 steps if rank 0's GPU cannot hold it for the one-GPU reference time)")
     args = ap.parse_args()
@@ -481,7 +493,12 @@ def main():
         sys.exit(2)
     if world > 1 or os.environ.get("CTK_FORCE_DIST") == "1":
         import bench_dist
-        sys.exit(bench_dist.bench_main(args, wl, WORKLOADS, HBM_PEAK_GBS, cpu_baseline=cpu_baseline, pmc_traffic=pmc_traffic) or 0)
+        if not args.full:
+            # a plain run of the N > 1 leg: the timed steps alone -- no extra passes, parity run, strong-scaling block or CPU leg
+            args.no_extra = args.no_parity_check = args.no_cpu_baseline = True
+            args.strong_steps = 0
+        sys.exit(bench_dist.bench_main(args, wl, WORKLOADS, HBM_PEAK_GBS, cpu_baseline=cpu_baseline,
+                                       pmc_traffic=pmc_traffic if args.full else None) or 0)
 
     T, ny, nx = wl["T"], wl["ny"], wl["nx"]
     thr = np.full(T, np.float64(np.float32(wl["threshold"])))
@@ -526,6 +543,23 @@ def main():
     per.update({k: last[k] for k in ("host_seam_driver", "total", "d2h", "h2d")})
     # d_out still holds the last timed step's flags here: everything below (extra passes, stream ceiling) writes over it
     dumped = dump_outputs(trk, d_out, wl, n_tracked, args.dump_outputs) if args.dump_outputs else None
+    px = T * ny * nx
+    # the line of a plain run: what the timed steps gave (kernels_ms: their own event pairs around the two streaming kernels)
+    out = dict(metric="timesteps/sec labeled+tracked", value=value, unit="timesteps/s", n_gpus=1, steps=args.steps,
+               warmup=args.warmup, ms_per_step=ms_per_step, higher_is_better=True, scaling="weak", vs_baseline=None,
+               dtype="f32 compare / int32 labels / int64 exact areas", data="synthetic",
+               config=dict(workload="%s: %dx%dx%d float32, threshold %s %g, overlap %g, persistence %d, twosided %s" % (
+                   args.workload, T, ny, nx, wl["gorl"], wl["threshold"], wl["overlap"], wl["persistence"], wl["twosided"]),
+                   parallelism="1 GPU", n_tracked=n_tracked),
+               kernels_ms=per, workload_stats=trk.stats(), dumped_outputs=dumped,
+               path_effective_gbs=8.0 * px / (ms_per_step * 1e-3) / 1e9)
+    if not args.full:
+        trk.free(d_in)
+        trk.free(d_out)
+        trk.close()
+        print(json.dumps(out))
+        return
+    # ---- --full: everything below runs after the line's own figures are fixed and adds to it ----
     # per-group kernel times of the small kernels: a few extra, untimed passes with events around every group (each
     # event record is a command of its own and would stretch the timed passes)
     trk.set_timing(2)
@@ -547,7 +581,6 @@ def main():
                         acc2[k] = v
             per[k] = acc2.get(k, 0.0)
     # roofline of the dominant kernel (by average duration, HIP events on the library's stream)
-    px = T * ny * nx
     alg_bytes = {"k_threshold": 4.0 * px, "k_relabel": 4.0 * px}          # float32 read once / int32 written once
     kern = max(alg_bytes, key=lambda k: per.get(k, 0.0))
     achieved = alg_bytes[kern] / (per[kern] * 1e-3) / 1e9 if per.get(kern, 0) > 0 else 0.0
@@ -564,23 +597,16 @@ def main():
             live_pmc = live
         else:
             traffic_source = (traffic_source or "") + " [live rocprofv3 --pmc measurement not available: %s]" % why
-    out = dict(metric="timesteps/sec labeled+tracked", value=value, unit="timesteps/s", n_gpus=1, steps=args.steps,
-               warmup=args.warmup, ms_per_step=ms_per_step, higher_is_better=True, scaling="weak", vs_baseline=None,
-               dtype="f32 compare / int32 labels / int64 exact areas", data="synthetic",
-               config=dict(workload="%s: %dx%dx%d float32, threshold %s %g, overlap %g, persistence %d, twosided %s" % (
-                   args.workload, T, ny, nx, wl["gorl"], wl["threshold"], wl["overlap"], wl["persistence"], wl["twosided"]),
-                   parallelism="1 GPU", n_tracked=n_tracked,
-                   coverage=coverage),
-               roofline=dict(bound="hbm", kernel=kname, achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS,
+    out["config"]["coverage"] = coverage
+    out.update(roofline=dict(bound="hbm", kernel=kname, achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS,
                              traffic=traffic, traffic_source=traffic_source, algorithmic_bytes_per_launch=alg_bytes[kern],
                              avg_kernel_ms=per.get(kern),
                              other_streaming_kernel={k: dict(achieved=alg_bytes[k] / (per[k] * 1e-3) / 1e9, avg_kernel_ms=per[k])
                                                      for k in alg_bytes if k != kern and per.get(k, 0) > 0}),
-               kernels_ms=per, workload_stats=trk.stats(), pmc_live=live_pmc, dumped_outputs=dumped,
+               workload_stats=trk.stats(), pmc_live=live_pmc,      # (kernels_ms is `per`, which the extra passes filled in)
                # what a PLAIN 16-byte non-temporal stream reaches on this board, measured here on the same two buffers (best of 5): the write
                # kernel cannot beat the store stream, the threshold kernel not the load stream -- `frac` above stays against the 8 TB/s peak
                stream_ceiling=stream_ceiling(trk, d_in, d_out, nbytes, per),
-               path_effective_gbs=8.0 * px / (ms_per_step * 1e-3) / 1e9,
                # the two pixel-streaming kernels together move the path's algorithmic 8 B per pixel
                streaming=dict(bytes=8.0 * px, ms=per.get("k_threshold", 0.0) + per.get("k_relabel", 0.0),
                               achieved_gbs=8.0 * px / ((per.get("k_threshold", 0.0) + per.get("k_relabel", 0.0)) * 1e-3) / 1e9

@@ -2,6 +2,7 @@
 (the launcher is all that is used of torch), the shared-memory transport instead of RCCL (CTK_DIST_BACKEND=shm: RCCL refuses
 two ranks on one device), weak scaling = two members concatenated on the time axis.  The tracked count must equal the
 one-call result on the concatenated slab."""
+import functools
 import json
 import os
 import subprocess
@@ -13,12 +14,25 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+@functools.lru_cache(maxsize=None)
+def _one_call_n_tracked():
+    """the two members of era5_1deg_90 concatenated on the time axis, tracked by one call of one handle"""
+    from contrack_amd import _native, synth
+    from contrack_amd.contrack import row_weights
+    a = np.concatenate([synth.smooth_field(90, 181, 360, seed=r) for r in range(2)], axis=0)
+    lat, _ = synth.grid(181, 360)
+    w = row_weights(lat, np.float32(1.0), np.float32(1.0))
+    with _native.Tracker(0) as t:
+        _, n = t.track(a, np.full(180, 160.0), 0, w, 0.5, 5, True)
+    return n
+
+
 @pytest.mark.gpu
 def test_bench_two_ranks_weak_scaling():
     env = dict(os.environ, CTK_DIST_BACKEND="shm", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "era5_1deg_90",
-           "--strong-steps", "24"]
+           "--full", "--strong-steps", "24"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -40,23 +54,17 @@ def test_bench_two_ranks_weak_scaling():
     assert sb["speedup_vs_1gpu"] == pytest.approx(sb["ms_per_step_1gpu"] / sb["ms_per_step"])
     assert sb["collectives_per_step"]["allgathers"] >= 4
 
-    from contrack_amd import _native, synth
-    from contrack_amd.contrack import row_weights
-    a = np.concatenate([synth.smooth_field(90, 181, 360, seed=r) for r in range(2)], axis=0)
-    lat, _ = synth.grid(181, 360)
-    w = row_weights(lat, np.float32(1.0), np.float32(1.0))
-    with _native.Tracker(0) as t:
-        _, n = t.track(a, np.full(180, 160.0), 0, w, 0.5, 5, True)
-    assert out["config"]["n_tracked"] == n
+    assert out["config"]["n_tracked"] == _one_call_n_tracked()
 
 
 @pytest.mark.gpu
 def test_bench_gpus_2_without_a_launcher_starts_its_own_ranks():
-    """`python bench.py --gpus 2` with no WORLD_SIZE in the environment: the ranks are started by bench.py itself -- the line says
+    """`python bench.py --gpus 2 --full` with no WORLD_SIZE in the environment: the ranks are started by bench.py itself -- the line says
     n_gpus 2 (never a silent 1-GPU line), proves itself (parity_checked) and carries the CPU leg"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update(CTK_DIST_BACKEND="shm", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "era5_1deg_90", "--strong-steps", "0"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "era5_1deg_90", "--full",
+           "--strong-steps", "0"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -66,6 +74,27 @@ def test_bench_gpus_2_without_a_launcher_starts_its_own_ranks():
     assert out["config"]["parity_checked"] is True and out["config"]["parity"]["shards_equal"] == [True, True]
     assert out["cpu_baseline"]["value"] > 0
     assert "strong_025deg" not in out
+
+
+@pytest.mark.gpu
+def test_bench_gpus_2_plain_run_is_the_timed_steps_alone():
+    """without --full the N > 1 leg times its steps and prints the line: no parity run, no CPU leg, no strong-scaling block, no
+    extra passes (rank0_shard) -- and the tracked count is that of one call on the concatenated slab"""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    env.update(CTK_DIST_BACKEND="shm", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "era5_1deg_90"]
+    p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["n_gpus"] == 2 and out["steps"] == 2 and out["warmup"] == 1 and out["config"]["total_timesteps"] == 180
+    assert out["unit"] == "timesteps/s" and out["higher_is_better"] is True and out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(180 / (out["ms_per_step"] * 1e-3))
+    assert out["config"]["parity"] is None and out["config"]["parity_checked"] is False
+    assert not {"cpu_baseline", "strong_025deg", "rank0_shard"} & set(out)
+    assert out["roofline"]["traffic"] is None
+    assert out["config"]["n_tracked"] == _one_call_n_tracked()
 
 
 @pytest.mark.gpu

@@ -1,6 +1,6 @@
 """Kernel timeline of one bench pass from a rocprofv3 --kernel-trace CSV: python tools/timeline.py <dir> [pass]
-(pass: index among the k_threshold launches, default -6 = the last TIMED pass of bench.py, which appends 5 passes with
-events around every kernel group)"""
+(pass: index among the k_threshold launches, default -6 = the last TIMED pass of `bench.py --full`, which appends 5 passes with
+events around every kernel group; of a plain run or one with --no-extra the last timed pass is -1)"""
 import csv
 import glob
 import sys
