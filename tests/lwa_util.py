@@ -198,6 +198,132 @@ def sprinkle(z, tab, values, share=0.05, seed=0, steps=None):
     return z
 
 
+# ---- tables and fields made to order (the edge tests) ---------------------------------------------------------------------------------
+def custom_table(lengths, active, W="cos", ny=None, shared=False):
+    """a row table with the keys of rows() for one or two domains of the given lengths.  The first domain runs DOWN the rows from
+    lengths[0] - 1 to 0 (its pole is row 0, as on a grid from the north), the second up from there on; shared: the second domain
+    starts on the first row of the first, as the equator row does (inactive in both).  active[d]: the positions in domain d that
+    are active.  Position p of n has phi = linspace(0, 1.5, n)[p]; q = cos(phi) * its trapezoid width, S = 6.371e6 / cos(phi) on
+    active rows.  W: "cos" rint(cos(phi) * 2^30), "max" all 2^32 - 1, "one" all 1, or an array of one weight per ROW (zeros
+    allowed; an active row with no weight poleward of it is refused).  ny: the rows of the plane (default: those of the domains)."""
+    lengths = [int(n) for n in lengths]
+    assert len(lengths) in (1, 2) and len(active) == len(lengths) and min(lengths) >= 1 and not (shared and len(lengths) == 1)
+    doms = [list(range(lengths[0] - 1, -1, -1))]
+    if len(lengths) == 2:
+        first = lengths[0] - int(bool(shared))
+        doms.append(list(range(first, first + lengths[1])))
+    used = max(max(dom) for dom in doms) + 1
+    ny = used if ny is None else int(ny)
+    assert ny >= used
+    kind = W if isinstance(W, str) else None
+    Wr = np.zeros(ny, dtype=np.uint32) if kind else np.array(W, dtype=np.uint32)
+    assert Wr.shape == (ny,)
+    q, S, act = np.zeros(ny), np.zeros(ny), np.zeros(ny, dtype=np.uint8)
+    given = set()
+    for dom, pos in zip(doms, active):
+        n = len(dom)
+        phi = np.linspace(0.0, 1.5, n) if n > 1 else np.zeros(1)
+        width = np.gradient(phi) if n > 2 else np.full(n, 1.5 / 2 if n == 2 else 0.0)
+        if n > 2:
+            width[0], width[-1] = (phi[1] - phi[0]) / 2, (phi[-1] - phi[-2]) / 2
+        for p, j in enumerate(dom):
+            if j not in given:
+                q[j] = np.cos(phi[p]) * width[p]
+                if kind:
+                    Wr[j] = {"cos": np.rint(np.cos(phi[p]) * 2.0 ** 30), "max": 2 ** 32 - 1, "one": 1}[kind]
+                given.add(j)
+        for p in pos:
+            j = dom[int(p)]
+            assert not act[j] and not (shared and int(p) == 0), "an active row lies in one domain"
+            act[j] = 1
+            S[j] = 6.371e6 / np.cos(phi[int(p)])
+    off = np.cumsum([0] + [len(dom) for dom in doms]).astype(np.int32)
+    tab = dict(ndom=len(doms), dom_off=off, dom_rows=np.array([j for dom in doms for j in dom], dtype=np.int32), active=act, W=Wr, q=q, S=S)
+    for dom in doms:
+        assert all(c > 0 for c, j in zip(caps(tab, dom, 1), dom) if act[j]), "an active row has cap 0"
+    return tab
+
+
+def row_phi(tab, ny):
+    """phi of every row as custom_table laid it out (the first domain that names a row decides; rows of no domain: 0)"""
+    phi, given = np.zeros(ny), set()
+    for dom in domains(tab):
+        for p, v in enumerate(np.linspace(0.0, 1.5, len(dom)) if len(dom) > 1 else np.zeros(1)):
+            if dom[p] not in given:
+                phi[dom[p]] = v
+                given.add(dom[p])
+    return phi
+
+
+def steep_field(tab, nx, steps, seed, dtype, noise=60.0):
+    """5700 - 800 sin^2(phi) along each domain of a custom_table plus `noise` m of weather: the rows of a long domain differ by less
+    than a metre, so every row crosses its contour many times"""
+    ny = len(tab["W"])
+    rng = np.random.default_rng(seed)
+    z = 5700.0 - 800.0 * np.sin(row_phi(tab, ny))[None, :, None] ** 2 + rng.normal(0.0, noise, (steps, ny, nx))
+    return z.astype(dtype)
+
+
+def two_valued(tab, nx, steps, lo, hi, seed, dtype):
+    """every pixel is `lo` or `hi`; the share of `hi` falls from 0.9 at the first position of a domain to 0.1 at its pole, so that
+    the contours near the equator are `hi` and those near the pole `lo`"""
+    ny = len(tab["W"])
+    rng = np.random.default_rng(seed)
+    share = 0.9 - 0.8 * row_phi(tab, ny) / 1.5
+    return np.where(rng.random((steps, ny, nx)) < share[None, :, None], dtype(hi), dtype(lo)).astype(dtype)
+
+
+def bisection(plane, tab, dom):
+    """k_lwa_contour's search (csrc/ctk_lwa.hip) on one plane and one domain, restated in unsigned 64-bit integers: the key range of
+    the weighted non-NaN pixels, `rounds` halvings of every active row's interval, in each of them a binary search of `probes`
+    halvings over the pivots per pixel, the weights in na + 1 buckets, their suffix sums against the caps, and the clamp.  Returns
+    dict(keys: one per active row in domain order, None where the contour is out of reach; rounds; probes; per: buckets per
+    thread of the suffix scan; clamped: how often the clamp's `mid == hi` branch was taken).  A diagnostic: the yardstick is
+    contours / from_table."""
+    nx = plane.shape[1]
+    pos = [p for p, j in enumerate(dom) if tab["active"][j]]
+    na = len(pos)
+    every = caps(tab, dom, nx)
+    cap = np.array([every[p] for p in pos], dtype=np.uint64)
+    vals = plane[dom, :].reshape(-1)
+    w = np.repeat(tab["W"][dom].astype(np.uint64), nx)
+    ok = ~np.isnan(vals)
+    k, w = key(vals[ok]).astype(np.uint64), w[ok]                               # what a round sees: every non-NaN pixel, its weight may be 0
+    counted = w != 0
+    total = int(w.sum(dtype=np.uint64))
+    res = dict(keys=[None] * na, rounds=0, probes=int(na).bit_length(), per=(na + 1024) // 1024, clamped=0)
+    if na == 0:
+        return res
+    kmin, kmax = (int(k[counted].min()), int(k[counted].max())) if total else (2 ** 64 - 1, 0)
+    res["rounds"] = (kmax - kmin).bit_length() if total and kmax > kmin else 0
+    lo, hi = np.full(na, kmin, dtype=np.uint64), np.full(na, kmax, dtype=np.uint64)
+    one = np.uint64(1)
+    for _ in range(res["rounds"]):
+        mid = lo + ((hi - lo) >> one)
+        assert np.all(mid[:-1] >= mid[1:]), "the pivots fall with the active rows"
+        l, h = np.zeros(len(k), dtype=np.int64), np.full(len(k), na, dtype=np.int64)
+        for _t in range(res["probes"]):
+            go = l < h
+            m = np.where(go, (l + h) >> 1, 0)
+            up = mid[m] >= k
+            l, h = np.where(go & up, m + 1, l), np.where(go & ~up, m, h)
+        bucket = np.zeros(na + 1, dtype=np.uint64)
+        np.add.at(bucket, l, w)
+        behind = (np.cumsum(bucket[::-1], dtype=np.uint64)[::-1] - bucket)[:na]             # the buckets behind a: A(mid[a])
+        reach = behind >= cap
+        res["clamped"] += int(np.count_nonzero(~reach & (mid == hi)))
+        lo, hi = np.where(reach, lo, np.where(mid < hi, mid + one, hi)), np.where(reach, mid, hi)
+    res["keys"] = [int(lo[a]) if total >= int(cap[a]) else None for a in range(na)]
+    return res
+
+
+def contour_keys(plane, tab, dom):
+    """key(contours(...)) of the active rows as bisection gives them: Python integers, None where the contour is NaN"""
+    Z = contours(plane, tab, dom)[0]
+    pos = [p for p, j in enumerate(dom) if tab["active"][j]]
+    return [None if np.isnan(Z[p]) else int(key(Z[p:p + 1])[0]) for p in pos]
+
+
 # ---- diagnostics ------------------------------------------------------------------------------------------------------------------
 def nonzero_share(out, tab):
     """share of the pixels of the active rows that are finite and not 0"""

@@ -1,6 +1,7 @@
 """The numpy statement of the local wave activity (tests/lwa_util.py), contrack.lwa_rows and ctk_lwa_plan, without a GPU: what the
 definition gives on fields whose answer is known, that the vectorised statement is the per-pixel loop, that the row table follows its
-formulas on every kind of latitude axis, and that the library's plan is the restated one at its form and capacity edges."""
+formulas on every kind of latitude axis, that the library's plan is the restated one at its form and capacity edges, and that every
+case of tests/test_gpu_lwa_edges.py reaches the edge it is named for (lu.bisection: the kernel's search restated in integers)."""
 import math
 
 import numpy as np
@@ -175,6 +176,158 @@ def test_the_fixture_conditions_hold_on_the_statement():
     ref = lu.from_table(zn, low, return_ref=True)[1]
     bad, good = lu.nan_rows(ref, low)
     assert bad[0] >= 2 and good[0] >= 2 and bad[1] == 0
+
+
+# ---- the cases of tests/test_gpu_lwa_edges.py: each reaches the edge it is named for ---------------------------------------------------
+EDGE_GROUPS = ("cap", "scan", "weight", "probe", "strip", "pair", "zero", "round")
+_searched = {}
+
+
+def searched(name):
+    """[(step, domain, lu.bisection(...), the keys of lu.contours(...))] of an edge case, computed once"""
+    import test_gpu_lwa_edges as e
+    if name not in _searched:
+        z, tab = e.case(name)
+        _searched[name] = [(s, d, lu.bisection(z[s], tab, dom), lu.contour_keys(z[s], tab, dom)) for s in range(z.shape[0]) for d, dom in enumerate(lu.domains(tab))]
+    return _searched[name]
+
+
+def edge_parts(e, name):
+    """the parts the GPU test of a case compares"""
+    return (0, 1, 2) if e.CASES[name][0] in ("zero", "round") or name == "cap-nx4-f32" else (0,)
+
+
+@pytest.mark.parametrize("group", EDGE_GROUPS)
+def test_the_restated_bisection_finds_the_statements_contours_on_every_edge_case(group):
+    import test_gpu_lwa_edges as e
+    assert e.names(group)
+    for name in e.names(group):
+        for s, d, found, keys in searched(name):
+            assert found["keys"] == keys, (name, s, d)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+def test_the_restated_bisection_on_1_to_70_active_rows(dtype):
+    for na in range(1, 71):
+        tab = lu.custom_table([na + 3], [range(2, na + 2)])
+        z = lu.steep_field(tab, 8, 1, na, dtype, 400.0)
+        assert lu.nonzero_share(lu.from_table(z, tab), tab) >= 0.5, na
+        planes = (z, lu.quantised(z, 100.0), lu.sprinkle(lu.quantised(z, 50.0), tab, [np.nan, np.inf, -np.inf, 0.0, -0.0], share=0.15, seed=na))
+        for zz in planes:
+            dom = lu.domains(tab)[0]
+            found = lu.bisection(zz[0], tab, dom)
+            assert found["keys"] == lu.contour_keys(zz[0], tab, dom) and found["probes"] == na.bit_length() and found["per"] == 1, na
+
+
+@pytest.mark.parametrize("group", EDGE_GROUPS)
+def test_the_statement_is_the_per_pixel_loop_on_every_edge_case(group):
+    """all (step, active row, column) triples where the domains have fewer than 100 rows, 40 drawn ones per domain otherwise (the
+    loop is a Python loop over the domain's rows per pixel)"""
+    import test_gpu_lwa_edges as e
+    for name in e.names(group):
+        z, tab = e.case(name)
+        dtype = z.dtype.type
+        steps, _ny, nx = z.shape
+        outs = {part: e.want(name, part)[0] for part in edge_parts(e, name)}
+        rng = np.random.default_rng(len(name))
+        for dom in lu.domains(tab):
+            pos = [p for p, j in enumerate(dom) if tab["active"][j]]
+            if not pos:
+                continue
+            triples = [(s, p, c) for s in range(steps) for p in pos for c in range(nx)]
+            if len(dom) >= 100:
+                triples = [triples[i] for i in rng.choice(len(triples), 40, replace=False)] + [(steps - 1, pos[0], 0), (0, pos[-1], nx - 1)]
+            Z = {s: lu.contours(z[s], tab, dom)[0] for s in {t[0] for t in triples}}
+            for s, p, c in triples:
+                j = dom[p]
+                a, y = lu.pixel(z[s], tab, dom, p, c, Z[s][p])
+                with np.errstate(invalid="ignore", over="ignore"):
+                    vals = [np.array(dtype(v * tab["S"][j])) if not np.isnan(Z[s][p]) else np.array(dtype(np.nan)) for v in (a + y, a, y)]
+                assert all(lu.same_bits(vals[part], np.array(o[s, j, c])) for part, o in outs.items()), (name, s, j, c)
+
+
+def test_every_edge_case_reaches_the_edge_it_is_named_for():
+    import test_gpu_lwa_edges as e
+    for name in e.CASES:                                                         # the search widths follow n_act in every case
+        _z, tab = e.case(name)
+        for (s, d, found, _keys), dom in zip(searched(name), lu.domains(tab) * 99):
+            na = sum(int(tab["active"][j]) for j in dom)
+            assert found["probes"] == na.bit_length() and found["per"] == (2 if na >= 1024 else 1), (name, s, d)
+    per = {name: {f["per"] for _, _, f, _ in searched(name)} for name in e.names("cap") + e.names("scan") + e.names("weight")}
+    assert all(per[name] == {1} for name in per if "na1023" in name) and sum("na1023" in name for name in per) == 2
+    assert all(per[name] == {2} for name in per if "na1023" not in name) and len(per) == 4 + 12 + 2
+    gaps = e.case("scan-gaps-nx4-f32")[1]
+    assert int(gaps["active"].sum()) == 1024 and len(gaps["active"]) == 2043 and np.count_nonzero(np.diff(np.flatnonzero(gaps["active"])) > 1) > 300
+    probes = {int(e.case(name)[1]["active"].sum()): searched(name)[0][2]["probes"] for name in e.names("probe")}
+    assert sorted(probes) == list(e.PROBE_NA) and all(probes[2 ** b] == b + 1 and probes[2 ** b + 1] == b + 1 for b in range(1, 10))
+    assert all(probes[2 ** b - 1] == b for b in range(1, 10)) and probes[1] == 1
+    for dtype, bits in (("f32", 32), ("f64", 64)):
+        for kind, rounds in (("adjacent", 1), ("zeros", 1), ("span", bits)):
+            assert [f["rounds"] for _, _, f, _ in searched("round-%s-%s" % (kind, dtype))] == [rounds, rounds], (kind, dtype)
+        s0, s1 = (f for _, _, f, _ in searched("round-nan-" + dtype))
+        assert s0["clamped"] > 0 and None in s0["keys"] and s0["keys"][-1] is not None and s1["clamped"] == 0 and None not in s1["keys"]
+        assert [f["rounds"] for _, _, f, _ in searched("zero-flat-" + dtype)] == [0, 0]
+    # the plans: the LDS of both kernels at the capacity edge, strips of one unit in both forms
+    p = _native.lwa_plan(8, 2043, 4)
+    assert (p["ok"], p["lds"], p["lds_sel"], p["strip"], p["vec"]) == (1, 65376, 65536, 4, 1)
+    assert _native.lwa_plan(4, 2043, 1, aligned=False)["strip"] == 1 and _native.lwa_plan(4, 2043, 3)["strip"] == 1 and _native.lwa_plan(4, 2043, 4, aligned=False)["nstrips"] == 4
+    assert _native.lwa_plan(4, 600, 24)["nstrips"] == 6 and _native.lwa_plan(4, 600, 24)["strip"] == 4
+    # (a scalar strip is one column wide from 1 025 rows on -- 2 048 // rows --, not from 513: 600 rows x 5 columns are strips of 3 and 2)
+    p600, p1030 = _native.lwa_plan(4, 600, 5), _native.lwa_plan(4, 1030, 5)
+    assert (p600["strip"], p600["nstrips"]) == (3, 2) and (p1030["strip"], p1030["nstrips"]) == (1, 5) and p1030["vec"] == 0
+    assert _native.lwa_plan(4, 1024, 5)["strip"] == 2 and _native.lwa_plan(4, 1025, 5)["strip"] == 1 and _native.lwa_plan(4, 512, 8)["strip"] == 4 and _native.lwa_plan(4, 513, 8)["nstrips"] == 2
+    for name, (rows, nx, (vec, strip, nstrips)) in e.STRIP_PLANS.items():
+        p = _native.lwa_plan(4, rows, nx, 1, 3)
+        assert (p["vec"], p["strip"], p["nstrips"]) == (vec, strip, nstrips) and e.case(name)[0].shape == (3, rows, nx), name
+    # the weights: bucket sums near 2^45, caps below 2^63
+    wmax = e.case("weight-max")[1]
+    cap0 = lu.caps(wmax, lu.domains(wmax)[0], 4)[0]
+    assert cap0 == 4 * 2043 * (2 ** 32 - 1) and 2 ** 44 < cap0 < 2 ** 46 and np.all(e.case("weight-one")[1]["W"] == 1)
+    # the pairs: unequal numbers of active rows, a domain without one, a shared first row
+    acts = {name: [sum(int(tab["active"][j]) for j in dom) for dom in lu.domains(tab)] for name, tab in ((n, e.case(n)[1]) for n in e.names("pair"))}
+    assert {tuple(v) for v in acts.values()} == {(700, 10), (10, 700), (0, 10), (10, 0), (699, 10)}
+    first = [dom[0] for dom in lu.domains(e.case("pair-shared-nx4")[1])]
+    assert first[0] == first[1] and not e.case("pair-shared-nx4")[1]["active"][first[0]]
+
+
+@pytest.mark.parametrize("group", EDGE_GROUPS)
+def test_no_edge_case_can_pass_with_an_all_zero_output(group):
+    """ordinary cases: at least half of the statement's active pixels are finite and not 0, the condition of tests/test_gpu_lwa.py;
+    the two-valued planes (as all_equal there) hold both values among their active contours instead"""
+    import test_gpu_lwa_edges as e
+    for name in e.names(group):
+        z, tab = e.case(name)
+        out, ref = e.want(name)
+        if e.CASES[name][2]:
+            assert lu.nonzero_share(out, tab) >= 0.5, (name, lu.nonzero_share(out, tab))
+            continue
+        values = np.unique(lu.key(z.reshape(-1)))
+        assert len(values) == 2
+        for s in range(z.shape[0]):
+            assert set(np.unique(lu.key(ref[s, tab["active"] != 0]))) == set(values), (name, s)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_zero_weight_rows_share_their_neighbours_contour(dtype):
+    import test_gpu_lwa_edges as e
+    z, tab = e.case("zero-steep-" + dtype)
+    dom = lu.domains(tab)[0]
+    caps = lu.caps(tab, dom, 8)
+    same = list(e.ZERO_ROWS) + [e.ZERO_ROWS[-1] + 1]                              # positions 17 .. 21: nothing weighs between them
+    assert len({caps[p] for p in same}) == 1 and caps[same[0] - 1] > caps[same[0]] > caps[same[-1] + 1] and all(tab["active"][dom[p]] for p in same)
+    assert [int(tab["W"][dom[p]]) for p in same] == [0, 0, 0, 0, int(tab["W"][dom[21]])] and tab["W"][dom[21]] > 0
+    ref = e.want("zero-steep-" + dtype)[1]
+    for s in range(2):
+        assert len({float(ref[s, dom[p]]) for p in same}) == 1 and ref[s, dom[same[0] - 1]] > ref[s, dom[same[0]]] > ref[s, dom[same[-1] + 1]]
+        found = searched("zero-steep-" + dtype)[s][2]
+        a0 = same[0] - e.ZERO_ACTIVE[0]
+        assert len(set(found["keys"][a0:a0 + 5])) == 1
+    # weighted pixels all equal, other values on the rows that weigh nothing: no round, yet an output
+    z, tab = e.case("zero-flat-" + dtype)
+    out, ref = e.want("zero-flat-" + dtype)
+    weighted = (tab["W"] != 0) & (tab["active"] != 0)
+    assert len(np.unique(z)) > 50 and np.all(z[:, tab["W"] != 0] == 5500.0) and np.all(ref[:, tab["active"] != 0] == 5500.0)
+    assert np.count_nonzero(out[:, weighted]) >= 0.5 * out[:, weighted].size and np.all(np.isfinite(out))
 
 
 # ---- the plan ---------------------------------------------------------------------------------------------------------------------
