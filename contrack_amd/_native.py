@@ -154,6 +154,50 @@ def reversal_plan(elem_bytes, ny, nx, steps, aligned=True):
     return dict(vec=int(v[0]), vpt=int(v[1]), bps=int(v[2]), blocks=int(v[3]), grid=int(v[4]), xcd=int(v[5]))
 
 
+SUBSET_FORMS = ("bitmap", "search_lds", "search_glb", "row_lds", "row_glb")
+SUBSET_KINDS = {"id": ABI.constants["CTK_SUBSET_ID"], "mask": ABI.constants["CTK_SUBSET_MASK"]}
+
+
+def subset_plan(by_row, max_id, longest, ny, nx, steps=1, hits=False, aligned=True, grid_max=0):
+    """ctk_debug_subset_plan: what ctk_subset_plan (csrc/ctk_forms.h) decides for a subset launch from the table's shape -- by_row,
+    max_id the largest id of a by-id table, longest its ids or the longest slice of a row table, hits -- as a dict (form 0 .. 4 =
+    SUBSET_FORMS, vec 1 vector / 0 scalar, vpt pixels per thread, lds bytes, bps parts per step, blocks parts of work, grid
+    workgroups launched, xcd, and the rule's capacities: bitmap_bits, lds_ids, table_share, part_lanes); no handle, no GPU"""
+    v = np.zeros(12, dtype=np.int64)
+    check(lib().ctk_debug_subset_plan(int(bool(by_row)), int(max_id), int(longest), int(bool(hits)), int(ny), int(nx), int(steps), int(bool(aligned)),
+                                      int(grid_max), v.ctypes.data))
+    return dict(zip(("form", "vec", "vpt", "lds", "bps", "blocks", "grid", "xcd", "bitmap_bits", "lds_ids", "table_share", "part_lanes"), (int(a) for a in v)))
+
+
+def _subset_table(table):
+    """a table (off, ids) of a subset call (contrack.subset_table makes one) as C-contiguous int64 / int32 arrays; the library checks
+    their contents"""
+    off, ids = table
+    off, ids = np.ascontiguousarray(off, dtype=np.int64), np.ascontiguousarray(ids, dtype=np.int32)
+    if off.ndim != 1 or ids.ndim != 1 or len(off) < 2:
+        raise ValueError("a table is (off, ids): off int64 with 2 or T + 1 entries, ids int32")
+    return off, ids
+
+
+def _subset_kind(kind):
+    if kind not in SUBSET_KINDS:
+        raise ValueError("kind={!r}: 'id' or 'mask'".format(kind))
+    return SUBSET_KINDS[kind]
+
+
+class _SubsetCall:
+    """the arguments every subset entry shares, and the counters it fills"""
+
+    def __init__(self, table, invert, kind, want_hits=True):
+        self.off, self.ids = _subset_table(table)
+        self.hits = np.zeros(len(self.ids), dtype=np.uint64) if want_hits else None
+        self.n = C.c_int64(0)
+        self.table = (self.off.ctypes.data, len(self.off), self.ids.ctypes.data, len(self.ids), int(bool(invert)), _subset_kind(kind))
+
+    def counts(self):
+        return _ptr(self.hits), C.byref(self.n)
+
+
 def lwa_plan(elem_bytes, rows, nx, ndom=1, steps=1, aligned=True):
     """ctk_debug_lwa_plan: what ctk_lwa_plan (csrc/ctk_forms.h) decides for a local-wave-activity launch whose longest domain has
     `rows` rows, as a dict (ok 1 / 0 the domain does not fit in LDS, vec 1 vector / 0 scalar form, strip columns, nstrips, lds and
@@ -1558,6 +1602,63 @@ class Tracker:
         v = np.zeros(2, dtype=np.int64)
         check(lib().ctk_debug_reversal_form(self._h, v.ctypes.data))
         return int(v[0]), int(v[1])
+
+    # ---- selection of tracks or (step, track) rows of a flag slab (ctk_subset_*) -----------------------------------------
+    def subset(self, flag, table, invert=False, kind='id', chunk_steps=0, want_out=True, want_hits=True):
+        """flag (T, ny, nx) int32 host slab; table = (off, ids) (contrack.subset_table; include/contrack_hip.h states it).  Returns
+        (out, hits, n_selected): the int32 selection -- flag where the pixel's id is in the step's slice (invert: where it is a
+        positive id that is not), 0 elsewhere; kind='mask': 1 / 0 --, uint64 hits per entry of ids, the selected pixels.
+        want_out=False: a count-only call, out is None and nothing is downloaded; want_hits=False: hits is None.  chunk_steps:
+        steps per chunk on their way through the device (0: about 256 MB); same bytes."""
+        flag = _flag_i32(flag, "subset_cb, or contrack.subset_numpy")
+        T, ny, nx = flag.shape
+        c = _SubsetCall(table, invert, kind, want_hits)
+        out = np.empty((T, ny, nx), dtype=np.int32) if want_out else None
+        check(lib().ctk_subset(self._h, flag.ctypes.data, T, ny, nx, *c.table, _ptr(out), *c.counts(), int(chunk_steps or 0)))
+        return out, c.hits, int(c.n.value)
+
+    def subset_cb(self, reader, shape, table, invert=False, kind='id', sink=None, chunk_steps=0, want_hits=True):
+        """the same with a reader(t0, nt, out) that fills `out`, an int32 (nt, ny, nx) view of pinned memory, with the steps
+        [t0, t0 + nt); shape = (T, ny, nx).  sink: None (a new array is returned), False (count only: no writer is called), a
+        C-contiguous int32 (T, ny, nx) array, or a writer(t0, nt, values).  Returns (out or None, hits, n_selected)."""
+        if shape is None:
+            raise ValueError("a reader needs shape=(T, ny, nx)")
+        T, ny, nx = (int(v) for v in shape)
+        c = _SubsetCall(table, invert, kind, want_hits)
+        out, sink = _value_sink(sink, (T, ny, nx), np.dtype(np.int32), "T", "flag", "the counts", True)
+        tr = _Trampolines()
+        rcb, wcb = tr.reader(reader, C.c_int32, (ny, nx)), tr.writer(sink, C.c_int32, (ny, nx))
+        tr.finish(lib().ctk_subset_cb(self._h, T, ny, nx, rcb, None, *c.table, wcb, None, *c.counts(), int(chunk_steps or 0)))
+        return out, c.hits, int(c.n.value)
+
+    def subset_dev(self, flag_dev, T, ny, nx, table, out_dev, invert=False, kind='id', want_hits=True):
+        """ctk_subset_dev: flag and out (T, ny, nx) int32 in device memory; out_dev None: count only, out_dev == flag_dev: in place.
+        Returns (hits, n_selected)."""
+        c = _SubsetCall(table, invert, kind, want_hits)
+        check(lib().ctk_subset_dev(self._h, flag_dev, int(T), int(ny), int(nx), *c.table, out_dev, *c.counts()))
+        return c.hits, int(c.n.value)
+
+    def time_subset(self, flag_dev, T, ny, nx, table, out_dev, invert=False, kind='id', want_hits=False, want_n_selected=True, reps=5):
+        """measurement (tools/subset_probe.py): (best, mean) ms of k_subset alone on slabs in device memory, HIP events; table None:
+        the plain copy kernel over the same two buffers, the yardstick"""
+        c = None if table is None else _SubsetCall(table, invert, kind, False)
+        args = (None, 0, None, 0, 0, 0) if c is None else c.table
+        ms = (C.c_double * 2)()
+        check(lib().ctk_debug_time_subset(self._h, flag_dev, int(T), int(ny), int(nx), *args, out_dev, int(bool(want_hits)), int(bool(want_n_selected)),
+                                          int(reps), ms))
+        return float(ms[0]), float(ms[1])
+
+    def debug_set_subset(self, xcd=-1, grid_max=0):
+        """for the following subset launches -- xcd: how workgroups map to XCDs (0 launch order, 1 one contiguous eighth per XCD,
+        n > 1 tiles of n; -1: the library's rule, ctk_subset_plan); grid_max: a lower cap on the workgroups of a launch (0: the
+        rule's)"""
+        check(lib().ctk_debug_set_subset(self._h, int(xcd), int(grid_max)))
+
+    def debug_subset_launch(self):
+        """(form, vec, workgroups) of the last subset launch: form 0 .. 4 = SUBSET_FORMS (-1: none yet), vec 1 vector / 0 scalar"""
+        v = np.zeros(3, dtype=np.int64)
+        check(lib().ctk_debug_subset_form(self._h, v.ctypes.data))
+        return int(v[0]), int(v[1]), int(v[2])
 
     # ---- local wave activity (ctk_lwa_*) ---------------------------------------------------------------------------
     def lwa(self, x, rows, part='total', chunk_steps=0, keep_resident=False, want_out=True, want_ref=False):

@@ -281,6 +281,93 @@ def spells_numpy(flag, group=None, above=0, by_id=True, min_duration=1, segments
     return tuple(a[0] for a in out) if group is None else out
 
 
+def _positive_int32(ids, what="ids"):
+    ids = np.asarray(ids).reshape(-1)
+    if ids.size and ids.dtype.kind not in "iub":
+        raise ValueError("{} must be integers".format(what))
+    ids = ids.astype(np.int64)
+    if ids.size and (ids.min() < 1 or ids.max() > np.iinfo(np.int32).max):
+        raise ValueError("{} must lie in 1 .. 2^31 - 1 (0 and negative values are background)".format(what))
+    return ids
+
+
+def subset_table(ids=None, steps=None, T=None):
+    """the table (off int64, ids int32) the subset entries take (include/contrack_hip.h), sorted, duplicates removed, validated.
+    ids alone: the tracks to keep at every step -- off = [0, K].  steps and ids, one pair per wanted (step, track) row, with T, the
+    number of steps of the slab: off has T + 1 entries and ids[off[t]:off[t + 1]] are the ids wanted at step t."""
+    if ids is None:
+        raise ValueError("subset_table needs ids (and steps with T for rows)")
+    ids = _positive_int32(ids)
+    if steps is None:
+        ids = np.unique(ids)
+        return np.array([0, len(ids)], dtype=np.int64), ids.astype(np.int32)
+    if T is None or int(T) < 1:
+        raise ValueError("a row table needs T, the number of steps of the slab (at least 1)")
+    T = int(T)
+    steps = np.asarray(steps).reshape(-1)
+    if steps.size and steps.dtype.kind not in "iub":
+        raise ValueError("steps must be integers")
+    steps = steps.astype(np.int64)
+    if steps.shape != ids.shape:
+        raise ValueError("steps and ids must pair up: {} steps, {} ids".format(steps.size, ids.size))
+    if steps.size and (steps.min() < 0 or steps.max() >= T):
+        raise ValueError("steps must lie in [0, {})".format(T))
+    pairs = np.unique(steps * (1 << 31) + ids)                                    # (sorted by step, then id)
+    off = np.zeros(T + 1, dtype=np.int64)
+    off[1:] = np.cumsum(np.bincount(pairs >> 31, minlength=T))
+    return off, (pairs & ((1 << 31) - 1)).astype(np.int32)
+
+
+def subset_numpy(flag, table, invert=False, kind='id', chunk_steps=None, device=None, shape=None, return_hits=False):
+    """a (time, lat, lon) integer flag slab restricted to the tracks or (step, track) rows of `table` (subset_table): where a
+    pixel's id is in its step's slice the id stays (kind='mask': becomes 1), everything else becomes 0; invert keeps the positive
+    ids that are NOT in the slice instead.  Values <= 0 are background either way.  Runs on the GPU (ctk_subset); int32 and
+    narrower flags are read as they are, wider ones are converted to int32 chunk by chunk (an id beyond int32 raises ValueError).
+    Returns (out int32, n_selected) -- with return_hits (out, n_selected, hits): uint64 per entry of the table's ids, the pixels
+    that entry found, whatever invert is.  chunk_steps: time steps per chunk on their way through the device (None or 0: about
+    256 MB); with shape=(T, ny, nx) `flag` may be a reader(t0, nt, out) that fills an int32 (nt, ny, nx) buffer (ctk_subset_cb)."""
+    steps = 0 if chunk_steps is None else int(chunk_steps)
+    if steps < 0:
+        raise ValueError("chunk_steps={} (at least 0)".format(steps))
+    source, shape, is_array = _flag_source(flag, shape)
+    trk = _tracker(device)
+    if is_array:
+        out, hits, n = trk.subset(source, table, invert, kind, steps, want_hits=return_hits)
+    else:
+        out, hits, n = trk.subset_cb(source, shape, table, invert, kind, chunk_steps=steps, want_hits=return_hits)
+    return (out, n, hits) if return_hits else (out, n)
+
+
+def track_table(frame):
+    """one row per track of a life-cycle frame (run_lifecycle's DataFrame or a row selection of it) -- per (Flag, member) where the
+    frame has a seventh, member column -- with what one selects tracks on: Onset and Decay (the first and last Date), Duration (the
+    number of rows), OnsetLongitude, OnsetLatitude, DecayLongitude, DecayLatitude, MaxIntensity, MeanIntensity, MaxSize, MeanSize,
+    PathLength (the sum of the great-circle distances in km between consecutive centres, rows in the frame's order) and Displacement
+    (onset to decay), both with contrack.greatcircle_dist.  Host only (pandas)."""
+    import pandas as pd
+
+    def dist(*lonlat):
+        return float(contrack.greatcircle_dist(None, *lonlat))
+    base = ['Flag', 'Date', 'Longitude', 'Latitude', 'Intensity', 'Size']
+    missing = [c for c in base if c not in frame.columns]
+    if missing:
+        raise ValueError("the frame lacks the columns {}".format(missing))
+    member = [c for c in frame.columns if c not in base + ['Step', 'Row', 'Col']]
+    if len(member) > 1:
+        raise ValueError("the frame has more than one column besides run_lifecycle's: {}".format(member))
+    keys = ['Flag'] + member
+    columns = keys + ['Onset', 'Decay', 'Duration', 'OnsetLongitude', 'OnsetLatitude', 'DecayLongitude', 'DecayLatitude', 'MaxIntensity',
+                      'MeanIntensity', 'MaxSize', 'MeanSize', 'PathLength', 'Displacement']
+    rows = []
+    for key, g in frame.groupby(keys, sort=True):
+        key = key if isinstance(key, tuple) else (key,)
+        lon, lat = g['Longitude'].to_numpy(), g['Latitude'].to_numpy()
+        path = sum((dist(lon[i], lat[i], lon[i + 1], lat[i + 1]) for i in range(len(g) - 1)), 0.0)
+        rows.append(tuple(key) + (g['Date'].iloc[0], g['Date'].iloc[-1], len(g), lon[0], lat[0], lon[-1], lat[-1], g['Intensity'].max(), g['Intensity'].mean(),
+                                  g['Size'].max(), g['Size'].mean(), path, dist(lon[0], lat[0], lon[-1], lat[-1])))
+    return pd.DataFrame(rows, columns=columns)
+
+
 def composite_mean(sum, n):
     """sum / n in float64, NaN where n == 0 (numpy's 0 / 0): the mean of a composite from what composite_numpy returns"""
     sum = np.asarray(sum, dtype=np.float64)
@@ -2524,6 +2611,63 @@ class contrack(object):
         if indices:
             columns += ['Step', 'Row', 'Col']
         return pd.DataFrame(cols, columns=columns)
+
+    # ---- selection: the flag of chosen tracks or (step, track) rows, what the consumers of `flag` then take ----------------------
+    def select_blocks(self, flag='flag', ids=None, frame=None, invert=False, out='id', name='flag_sel', chunk_steps=None, check=True):
+        """adds the variable `name`: the flag variable restricted to the blocks a study picked, computed on the GPU (subset_numpy).
+        Exactly one of
+          ids:   the tracks to keep, at every step (the Atlantic blocks, those of ten days or more: track_table helps to pick them);
+          frame: rows of run_lifecycle(indices=True) -- 'Flag', 'Step' and, for a 4-D flag, the member column --, every row one
+                 (step, track) to keep (only the mature days, only the days the centre lies in a sector).
+        Pixels of the kept blocks keep their id (out='mask': become 1), all others become 0; invert=True keeps every block pixel
+        that was NOT asked for instead.  `name` has the flag's dims (any order, a member dimension included) and is int32:
+        calc_frequency, calc_spells, calc_composite, calc_hovmoller and calc_blocked_area take it as they take `flag`.
+        chunk_steps: the flag is read slice by slice (`isel`), as calc_frequency does; same values.
+        check=True: an id or row that matches no pixel raises ValueError (the frame comes from another run) and nothing is added.
+        Returns the number of selected pixels."""
+        self._ensure_set_up()
+        if (ids is None) == (frame is None):
+            raise ValueError("select_blocks takes exactly one of ids and frame")
+        if out not in _native.SUBSET_KINDS:
+            raise ValueError("out={!r}: 'id' or 'mask'".format(out))
+        da = self.ds[flag]
+        dims, member = self._consumer_dims(flag)
+        if np.dtype(da.dtype).kind not in "iub":
+            raise ValueError("flag must be an integer field")
+        T = da.shape[dims.index(self._time_name)]
+        view = self._steps(da, (member, self._time_name))
+        if ids is not None:
+            table = subset_table(ids)
+            asked = '{} ids'.format(len(table[1]))
+        else:
+            need = ['Flag', 'Step'] + ([member] if member is not None else [])
+            missing = [c for c in need if c not in frame]
+            if missing:
+                raise ValueError("the frame lacks the columns {}: pass rows of run_lifecycle(..., indices=True)".format(missing))
+            step = np.asarray(frame['Step']).astype(np.int64)
+            if step.size and (step.min() < 0 or step.max() >= T):
+                raise ValueError("the frame's Step must lie in [0, {})".format(T))
+            if member is not None:
+                values = self._dim_values(member, da.shape[dims.index(member)])
+                order = np.argsort(values, kind='stable')
+                col = np.asarray(frame[member])
+                pos = np.minimum(np.searchsorted(values[order], col), len(values) - 1)
+                if (values[order][pos] != col).any():
+                    raise ValueError("the frame's column {!r} holds values that are not on that dimension".format(member))
+                step = order[pos].astype(np.int64) * T + step
+            table = subset_table(np.asarray(frame['Flag']), step, view.steps)
+            asked = '{} rows'.format(len(table[1]))
+        source = view.slab() if chunk_steps is None else view.reader(integer=True)
+        res, n, hits = subset_numpy(source, table, invert=invert, kind=out, chunk_steps=chunk_steps, shape=view.shape, return_hits=True)
+        if check and (hits == 0).any():
+            lost = np.flatnonzero(hits == 0)
+            at = np.searchsorted(table[0], lost, side='right') - 1                # the flat step of a row table's entry
+            some = ', '.join(str(int(table[1][e])) if ids is not None else '(step {}, id {})'.format(int(s), int(table[1][e])) for e, s in zip(lost[:5], at[:5]))
+            raise ValueError("{} of the {} requested match no pixel of {!r} (the first: {}): do they come from another run?".format(len(lost), asked, flag, some))
+        attrs = {'units': '1', 'long_name': 'contrack selected {}'.format('mask' if out == 'mask' else 'flag'),
+                 'history': 'Selected from {} with input attributes: {}, invert = {}, out = {}.'.format(flag, asked, bool(invert), out)}
+        self.ds[name] = (dims, view.restore(res, dims), attrs)
+        return n
 
     def calc_centred_composite(self, variable, frame, half_width=(20., 40.), by=None, nbins=None, max_age=None, stat='mean', skipna=False, wrap=True,
                                chunk_steps=None, return_count=False):

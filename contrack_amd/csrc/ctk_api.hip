@@ -301,6 +301,12 @@ struct ctk_handle {
     DevBuf lw_tab, lw_ref;
     int lw_form = -1, lw_xcd_dbg = -1;
     int64_t lw_grid = 0, lw_grid_dbg = 0;
+    // selection of tracks or rows of a flag slab (ctk_subset.hip): the table of the running call (offsets, ids, bitmap words) and
+    // its counters (the words n_selected is summed from, then one per entry); form, vector or scalar and workgroups of the last k_subset launch (form -1: none
+    // yet); ctk_debug_set_subset's two numbers (as the reversal's)
+    DevBuf sb_tab, sb_hits;
+    int sb_form = -1, sb_vec = 0, sb_xcd_dbg = -1;
+    int64_t sb_grid = 0, sb_grid_dbg = 0;
     DevBuf io_in, io_out;                          // device copies of host-array calls (ctk_track_f32 / _f64)
     uint64_t io_gen = 0;                           // bumped by claim_io and ctk_release_io: WHOSE data io_in / io_out hold
     // streaming entries (ctk_track_stream_*): the slab passes through two chunk-sized device buffers per direction
@@ -3983,6 +3989,7 @@ extern "C" int ctk_lifecycle_rows(ctk_handle *h, ctk_life_row *rows, int64_t cap
 #include "ctk_level.hip"
 #include "ctk_reversal.hip"
 #include "ctk_lwa.hip"
+#include "ctk_subset.hip"
 #include "ctk_composite.hip"
 #include "ctk_centred.hip"
 #include "ctk_band.hip"

@@ -738,6 +738,63 @@ inline CtkLwaPlan ctk_lwa_plan(int elem_bytes, int64_t rows, int64_t nx, int64_t
 }
 
 // ------------------------------------------------------------------------------------------------
+// selection of tracks or (step, track) rows of a flag slab (ctk_subset.hip): k_subset, one thread per 16 bytes of adjacent pixels of
+// one step (vector form: every plane starts on a 16-byte boundary) or per pixel (scalar form).  A workgroup takes a PART of one step,
+// CTK_SUBSET_TILES tiles of 256 lanes, per load of its table; the table's shape picks the form:
+//     by id, no hits, largest id below CTK_SUBSET_BITMAP_BITS    a bitmap over [0, largest id] in LDS
+//     by id, at most CTK_SUBSET_LDS_IDS ids                      binary search over the sorted ids in LDS (hits: counters beside them)
+//     by id, more                                                binary search in global memory
+//     by row, longest slice at most CTK_SUBSET_LDS_IDS           the step's slice in LDS, searched
+//     by row, longer                                             the step's slice searched in global memory
+// The by-id forms load the table once per workgroup, which then strides over as many parts as keep the table at CTK_SUBSET_TABLE_SHARE
+// bytes per part or less (a part is 16 KB of flags) -- one part where the table is that small: a workgroup per part measured 0.92 of
+// the copy kernel where 2048 striding ones reached 0.71-0.79 (profiles/NOTES.md); the row forms load a slice per part and launch one
+// workgroup per part.  CTK_LEVEL_GRID_MAX workgroups at most, the rest by striding.
+// ------------------------------------------------------------------------------------------------
+#define CTK_SUBSET_THREADS 256
+#define CTK_SUBSET_TILES 4                    // tiles of 256 lanes per part: their loads are in flight together
+#define CTK_SUBSET_BITMAP_BITS (1ll << 18)    // 32 KB of LDS: five workgroups per CU
+#define CTK_SUBSET_LDS_IDS 4096               // 16 KB of ids, 16 KB of uint32 counters with hits
+#define CTK_SUBSET_TABLE_SHARE 1024           // bytes of table a by-id workgroup loads per part it takes, at most
+#define CTK_SUBSET_BITMAP 0
+#define CTK_SUBSET_SEARCH_LDS 1
+#define CTK_SUBSET_SEARCH_GLB 2
+#define CTK_SUBSET_ROW_LDS 3
+#define CTK_SUBSET_ROW_GLB 4
+struct CtkSubsetPlan {
+    int form;                     // CTK_SUBSET_BITMAP .. CTK_SUBSET_ROW_GLB
+    int vec;                      // 1: a 16-byte load and a 16-byte store per lane, 0: the scalar form
+    int vpt;                      // pixels per thread: 4 or 1
+    int64_t lds;                  // bytes of dynamic LDS of a workgroup
+    int64_t bps;                  // parts per step
+    int64_t blocks;               // bps * steps: (step, part) pairs, walked by ...
+    unsigned grid;                // ... this many workgroups
+    int xcd;                      // xcd_chunk mode of the launch: 1 one contiguous eighth of the workgroups per XCD, 0 launch order
+};
+// by_row: the table has a slice per step; max_id: the largest id of a by-id table (0: an empty one); longest: the ids of a by-id table,
+// the longest slice of a row table; hits: the call counts per entry; aligned: the flag's and the output's base pointers are multiples
+// of 16; grid_max: CTK_LEVEL_GRID_MAX, or a test's lower cap
+inline CtkSubsetPlan ctk_subset_plan(bool by_row, int64_t max_id, int64_t longest, bool hits, int64_t npix, int64_t steps, bool aligned,
+                                     int64_t grid_max = CTK_LEVEL_GRID_MAX)
+{
+    CtkSubsetPlan p = {};
+    if (by_row) p.form = longest <= CTK_SUBSET_LDS_IDS ? CTK_SUBSET_ROW_LDS : CTK_SUBSET_ROW_GLB;
+    else p.form = !hits && max_id < CTK_SUBSET_BITMAP_BITS ? CTK_SUBSET_BITMAP : longest <= CTK_SUBSET_LDS_IDS ? CTK_SUBSET_SEARCH_LDS : CTK_SUBSET_SEARCH_GLB;
+    p.lds = p.form == CTK_SUBSET_BITMAP ? ((max_id >> 5) + 1) * 4
+          : p.form == CTK_SUBSET_SEARCH_LDS || p.form == CTK_SUBSET_ROW_LDS ? longest * (hits ? 8 : 4) : 0;
+    p.vec = aligned && npix % 4 == 0;
+    p.vpt = p.vec ? 4 : 1;
+    const int64_t lanes = (npix + p.vpt - 1) / p.vpt, per_part = (int64_t)CTK_SUBSET_THREADS * CTK_SUBSET_TILES;
+    p.bps = (lanes + per_part - 1) / per_part;
+    p.blocks = p.bps * steps;
+    const int64_t per_load = by_row ? 1 : std::max<int64_t>((p.lds + CTK_SUBSET_TABLE_SHARE - 1) / CTK_SUBSET_TABLE_SHARE, 1);          // parts per table load
+    const int64_t cap = std::min<int64_t>(std::max<int64_t>(grid_max, 1), CTK_LEVEL_GRID_MAX);
+    p.grid = (unsigned)std::min<int64_t>((p.blocks + per_load - 1) / per_load, cap);
+    p.xcd = p.grid >= CTK_LEVEL_XCD_MIN ? 1 : 0;
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------
 // rules every streamed entry shares
 // ------------------------------------------------------------------------------------------------
 // steps per chunk: chunk_steps, or (0) about 256 MB of input -- step_bytes is what one step brings in, a plane or the selected levels of

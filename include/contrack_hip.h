@@ -711,6 +711,46 @@ int ctk_lwa_stream_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */
                       const int32_t *dom_off, const int32_t *dom_rows, const uint8_t *active, const uint32_t *W, const double *q, const double *S, int part,
                       ctk_write_values_fn writer, void *writer_user, void *ref /* or NULL */, int64_t chunk_steps, int keep_resident);
 
+/* ---- selection: the chosen tracks, or (step, track) rows, of a flag slab ----------------------------------------------------------
+ * A study rarely wants every block: it picks tracks from the life-cycle frame (the Atlantic ones, those of ten days or more) or rows
+ * of it (the mature days, the days the centre lies in a sector) and needs the int32 flag slab (T, ny, nx) restricted to them before
+ * ctk_frequency_*, ctk_spells_*, ctk_composite_* or ctk_band_*.  tests/subset_util.py is the numpy statement of what follows.
+ * A TABLE is off[n_off] (int64) and ids[n_ids] (int32):
+ *     by id:   n_off = 2, off = {0, K}: the K ids, all > 0 and strictly increasing, apply to every step
+ *     by row:  n_off = T + 1, off[0] = 0, non-decreasing, off[T] = n_ids: ids[off[t] .. off[t + 1]) are the ids wanted at step t, all
+ *              > 0 and strictly increasing inside the slice
+ * (T = 1: both readings say the same.)  Per step t and pixel p, with f = flag[t][p]:
+ *     found = f > 0 and f is in the slice of step t
+ *     sel   = found            (invert == 0)          sel = f > 0 and not found     (invert != 0)
+ *     out[t][p] = sel ? (kind == CTK_SUBSET_ID ? f : 1) : 0
+ *     hits[e] += 1 for the entry e of ids that found it, whatever invert is ;  n_selected += sel
+ * So values <= 0 are background: never selected, never counted, 0 in the output, with invert too; an id listed at another step only
+ * is not found at this one; an empty table selects nothing, or with invert every f > 0.  All of it is integers: there is no tolerance.
+ * out may be NULL when hits or n_selected is given: a count-only call, nothing is written or downloaded.  hits (host, n_ids values,
+ * overwritten) and n_selected may each be NULL.
+ * CTK_E_INVALID with a message, the handle usable and nothing written: a null required pointer, T, ny or nx < 1, a plane of 2^31
+ * pixels or more, n_off neither 2 nor T + 1, off not as stated, an id <= 0, a slice that is not strictly increasing, kind not
+ * CTK_SUBSET_ID or CTK_SUBSET_MASK, chunk_steps < 0, nothing to produce (out, hits and n_selected all NULL).
+ *
+ * ctk_subset_dev: flag and out in HBM; a lane writes only the elements it read, so out_dev == flag_dev selects in place.  The result
+ * feeds the _dev entries of the consumers without crossing PCIe.
+ * ctk_subset / _cb: a host array or a reader callback (int32 elements) and a host array or a writer callback (NULL: count only); two
+ * input and two output chunks, chunk k + 1 travels in while the kernel works on chunk k and chunk k - 1 leaves (chunk_steps = 0: about
+ * 256 MB per chunk).  The table is uploaded once, hits accumulate in HBM over the chunks and are copied out at the end.  The same bytes
+ * for every chunk_steps.  Reader and writer are called in increasing t0, once per chunk; a non-zero return ends the call with
+ * CTK_E_INVALID and leaves nothing in flight.  out == flag is allowed in ctk_subset.
+ * No subset call touches the resident slot of the field to track: ctk_resident_anom_generation stays what it was. */
+#define CTK_SUBSET_ID 0
+#define CTK_SUBSET_MASK 1
+int ctk_subset_dev(ctk_handle *h, const int32_t *flag_dev, int64_t T, int ny, int nx, const int64_t *off, int64_t n_off, const int32_t *ids, int64_t n_ids,
+                   int invert, int kind, int32_t *out_dev /* or NULL; == flag_dev: in place */, uint64_t *hits /* host [n_ids] or NULL */,
+                   int64_t *n_selected /* or NULL */);
+int ctk_subset(ctk_handle *h, const int32_t *flag, int64_t T, int ny, int nx, const int64_t *off, int64_t n_off, const int32_t *ids, int64_t n_ids, int invert,
+               int kind, int32_t *out /* host or NULL */, uint64_t *hits /* host [n_ids] or NULL */, int64_t *n_selected /* or NULL */, int64_t chunk_steps);
+int ctk_subset_cb(ctk_handle *h, int64_t T, int ny, int nx, ctk_read_chunk_fn reader, void *reader_user, const int64_t *off, int64_t n_off, const int32_t *ids,
+                  int64_t n_ids, int invert, int kind, ctk_write_chunk_fn writer /* or NULL */, void *writer_user, uint64_t *hits /* host [n_ids] or NULL */,
+                  int64_t *n_selected /* or NULL */, int64_t chunk_steps);
+
 /* ---- the blocking-frequency climatology of the reference's tutorial (README.rst:159-160) ---------------------------------------
  *   xr.where(block['flag'] > 1, 1, 0).sum(dim='time') / block.ntime * 100     -- on the int32 flag slab (T, ny, nx), per group:
  *   counts[g][y][x] = #{t : group[t] == g and flag[t][y][x] > above}            (exact; the caller divides: counts / n[g] * 100)

@@ -289,6 +289,30 @@ int ctk_debug_reversal_form(ctk_handle *h, int64_t *out2);
 int ctk_debug_time_reversal(ctk_handle *h, const void *x_dev, int is_f64, int64_t steps, int ny, int nx, const int32_t *eq, const int32_t *po, const int32_t *eq2,
                             const double *dE, const double *tS, const double *tN, const double *tS2, int mask, void *out_dev, int reps, double *ms2);
 
+/* what ctk_subset_plan (csrc/ctk_forms.h) decides for a ctk_subset_* launch over `steps` steps of planes of ny rows of nx pixels from
+ * the table's shape: by_row (0: by id), max_id the largest id of a by-id table (0: an empty one), longest the ids of a by-id table or
+ * the longest slice of a row table, want_hits; `aligned`: both base pointers are multiples of 16; grid_max: a lower cap on the
+ * workgroups of a launch (0: the rule's).  out12 = { the form: 0 bitmap in LDS (by id, no hits, max_id below the bitmap's bits), 1
+ * sorted ids in LDS (by id, at most the LDS ids), 2 sorted ids in global memory, 3 the step's slice in LDS (by row, longest at most
+ * the LDS ids), 4 the step's slice in global memory; 1 the vector form (16 bytes per lane; every plane starts on a 16-byte boundary:
+ * ny * nx a multiple of 4) / 0 the scalar form; pixels per thread; LDS bytes of a workgroup; parts per step; parts of work (per step x
+ * steps); workgroups launched (by id one per ceil(LDS bytes / out12[10]) parts, by row one per part, at most 2^24 - 1; the kernel strides over the rest); 1 if every XCD
+ * takes one contiguous eighth of them (0: launch order); the capacities of the rule: bits of the bitmap, ids in LDS, bytes of table
+ * per part of a by-id workgroup; lanes of a part }.  Host only: no handle, no GPU. */
+int ctk_debug_subset_plan(int by_row, int64_t max_id, int64_t longest, int want_hits, int64_t ny, int64_t nx, int64_t steps, int aligned, int64_t grid_max,
+                          int64_t *out12);
+/* test hook / experiments for the following k_subset launches on this handle: as ctk_debug_set_level */
+int ctk_debug_set_subset(ctk_handle *h, int xcd_mode, int64_t grid_max);
+/* test hook: out3 = { the form of the last k_subset launch on this handle (0 .. 4 as above, -1 none yet), 1 vector / 0 scalar, its
+ * workgroups } */
+int ctk_debug_subset_form(ctk_handle *h, int64_t *out3);
+/* measurement (tools/subset_probe.py): k_subset alone on slabs in device memory (the arguments of ctk_subset_dev; out_dev NULL: count
+ * only; want_hits / want_n_selected: the counters are kept, not returned) between HIP events: one launch that is not counted, then
+ * `reps` timed ones; ms2 = { best, mean }.  off == NULL: a plain copy kernel (one 16-byte load and one 16-byte store per lane) over
+ * the same two buffers instead, the yardstick. */
+int ctk_debug_time_subset(ctk_handle *h, const int32_t *flag_dev, int64_t T, int ny, int nx, const int64_t *off, int64_t n_off, const int32_t *ids, int64_t n_ids,
+                          int invert, int kind, int32_t *out_dev, int want_hits, int want_n_selected, int reps, double *ms2);
+
 /* what ctk_lwa_plan (csrc/ctk_forms.h) decides for a ctk_lwa_* launch over `steps` steps of ndom (1 / 2) domains, the longest of
  * `rows` rows of nx pixels of elem_bytes (4 / 8), `aligned`: both base pointers are multiples of 16.  out12 = { 1 the domain fits in
  * LDS / 0 the call is refused, 1 the vector form (16-byte loads of the strip; nx a multiple of 4) / 0 the scalar form, columns of a
