@@ -617,6 +617,23 @@ def _value_sink(sink, shape, dt, steps, what, instead, has_instead):
     return sink, sink
 
 
+def _values_cb(reader, shape, dims, dtype, bind, sink, keep_resident):
+    """What level_mean_cb, reversal_cb and lwa_cb share: the reader's shape (dims: its words in the ValueError) and dtype checked, then
+    the family's own arguments -- bind(dtype, shape) checks them and returns call(reader, writer), the library call --, then the sink
+    (_value_sink) and the two trampolines made and the call carried out.  Returns the array the entry returns, or None."""
+    if shape is None or dtype is None:
+        raise ValueError("a reader needs shape=%s and dtype" % dims)
+    shape = tuple(int(v) for v in shape)
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("the field must be float32 or float64")
+    call = bind(dt, shape)
+    out, sink = _value_sink(sink, (shape[0],) + shape[-2:], dt, "steps", "field", "keep_resident", keep_resident)
+    tr = _Trampolines()
+    tr.finish(call(tr.reader(reader, _float_ctype(dt), shape[1:]), tr.writer(sink, _float_ctype(dt), shape[-2:])))
+    return out
+
+
 def _flag_i32(flag, wider_hint):
     """the flag slab of an array entry as C-contiguous int32 (time, lat, lon); narrower integers are widened, wider ones are
     refused: `wider_hint` names the entries that take them"""
@@ -1480,21 +1497,14 @@ class Tracker:
         (rising level order) of the steps [t0, t0 + nt); shape_sel = (steps, nsel, ny, nx), weights_sel their nsel non-zero
         weights.  sink: None (a new array is returned), False (nothing leaves the device: keep_resident), a C-contiguous
         (steps, ny, nx) array of `dtype`, or a writer(t0, nt, values).  Reader and writer see every step once, in rising order."""
-        if shape_sel is None or dtype is None:
-            raise ValueError("a reader needs shape=(steps, nsel, ny, nx) and dtype")
-        steps, nsel, ny, nx = (int(v) for v in shape_sel)
-        dt = np.dtype(dtype)
-        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise ValueError("the field must be float32 or float64")
-        w = _level_weights(weights_sel, nsel)
-        if np.any(w == 0):
-            raise ValueError("a reader delivers the selected levels only: every weight must be > 0")
-        out, sink = _value_sink(sink, (steps, ny, nx), dt, "steps", "field", "keep_resident", keep_resident)
-        tr = _Trampolines()
-        rcb, wcb = tr.reader(reader, _float_ctype(dt), (nsel, ny, nx)), tr.writer(sink, _float_ctype(dt), (ny, nx))
-        tr.finish(lib().ctk_level_mean_stream_cb(self._h, dt.itemsize, steps, nsel, ny, nx, rcb, None, w.ctypes.data, int(bool(skipna)), wcb, None,
-                                                 int(chunk_steps or 0), int(bool(keep_resident))))
-        return out
+        def bind(dt, shape):
+            steps, nsel, ny, nx = shape
+            w = _level_weights(weights_sel, nsel)
+            if np.any(w == 0):
+                raise ValueError("a reader delivers the selected levels only: every weight must be > 0")
+            return lambda rcb, wcb: lib().ctk_level_mean_stream_cb(self._h, dt.itemsize, steps, nsel, ny, nx, rcb, None, w.ctypes.data, int(bool(skipna)), wcb,
+                                                                   None, int(chunk_steps or 0), int(bool(keep_resident)))
+        return _values_cb(reader, shape_sel, "(steps, nsel, ny, nx)", dtype, bind, sink, keep_resident)
 
     def level_mean_dev(self, x_dev, steps, nlev, ny, nx, weights, out_dev, skipna=False, f64=False):
         """ctk_level_mean_*_dev: x (steps, nlev, ny, nx) and out (steps, ny, nx) in device memory"""
@@ -1510,10 +1520,20 @@ class Tracker:
                                               out_dev, int(reps), ms))
         return float(ms[0]), float(ms[1])
 
+    def _debug_set(self, family, xcd, grid_max):
+        """ctk_debug_set_<family> of the map families (level, reversal, subset, lwa): both numbers hold for its following launches"""
+        check(getattr(lib(), "ctk_debug_set_" + family)(self._h, int(xcd), int(grid_max)))
+
+    def _debug_launch(self, family, n):
+        """the n words ctk_debug_<family>_form of those families reports of the last launch"""
+        v = np.zeros(n, dtype=np.int64)
+        check(getattr(lib(), "ctk_debug_%s_form" % family)(self._h, v.ctypes.data))
+        return tuple(int(a) for a in v)
+
     def debug_set_level(self, xcd=-1, grid_max=0):
         """for the following level_mean launches -- xcd: how workgroups map to XCDs (0 launch order, 1 one contiguous eighth per XCD,
         n > 1 tiles of n; -1: the library's rule, ctk_level_plan); grid_max: a lower cap on the workgroups of a launch (0: the rule's)"""
-        check(lib().ctk_debug_set_level(self._h, int(xcd), int(grid_max)))
+        self._debug_set("level", xcd, grid_max)
 
     def debug_level_form(self):
         """the form of the last level_mean launch: 1 vector (16 bytes per lane), 0 scalar, -1 none yet"""
@@ -1521,9 +1541,7 @@ class Tracker:
 
     def debug_level_launch(self):
         """(form, workgroups) of the last level_mean launch"""
-        v = np.zeros(2, dtype=np.int64)
-        check(lib().ctk_debug_level_form(self._h, v.ctypes.data))
-        return int(v[0]), int(v[1])
+        return self._debug_launch("level", 2)
 
     def resident_level_mean(self):
         """(steps, ny, nx, is float64) of the vertical mean kept in HBM, or None"""
@@ -1559,19 +1577,12 @@ class Tracker:
         shape = (steps, ny, nx).  sink: None (a new array is returned), False (nothing leaves the device: keep_resident), a
         C-contiguous (steps, ny, nx) array of `dtype`, or a writer(t0, nt, values).  Reader and writer see every step once, in
         rising order."""
-        if shape is None or dtype is None:
-            raise ValueError("a reader needs shape=(steps, ny, nx) and dtype")
-        steps, ny, nx = (int(v) for v in shape)
-        dt = np.dtype(dtype)
-        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise ValueError("the field must be float32 or float64")
-        ptrs, _keep = _reversal_rows(rows, ny)
-        out, sink = _value_sink(sink, (steps, ny, nx), dt, "steps", "field", "keep_resident", keep_resident)
-        tr = _Trampolines()
-        rcb, wcb = tr.reader(reader, _float_ctype(dt), (ny, nx)), tr.writer(sink, _float_ctype(dt), (ny, nx))
-        tr.finish(lib().ctk_reversal_stream_cb(self._h, dt.itemsize, steps, ny, nx, rcb, None, *ptrs, int(bool(mask)), wcb, None, int(chunk_steps or 0),
-                                               int(bool(keep_resident))))
-        return out
+        def bind(dt, shape):
+            steps, ny, nx = shape
+            ptrs, keep = _reversal_rows(rows, ny)
+            return lambda rcb, wcb, _keep=keep: lib().ctk_reversal_stream_cb(self._h, dt.itemsize, steps, ny, nx, rcb, None, *ptrs, int(bool(mask)), wcb, None,
+                                                                             int(chunk_steps or 0), int(bool(keep_resident)))
+        return _values_cb(reader, shape, "(steps, ny, nx)", dtype, bind, sink, keep_resident)
 
     def reversal_dev(self, x_dev, steps, ny, nx, rows, out_dev, mask=False, f64=False):
         """ctk_reversal_*_dev: x and out (steps, ny, nx) in device memory"""
@@ -1591,7 +1602,7 @@ class Tracker:
         """for the following reversal launches -- xcd: how workgroups map to XCDs (0 launch order, 1 one contiguous eighth per XCD,
         n > 1 tiles of n; -1: the library's rule, ctk_reversal_plan); grid_max: a lower cap on the workgroups of a launch (0: the
         rule's)"""
-        check(lib().ctk_debug_set_reversal(self._h, int(xcd), int(grid_max)))
+        self._debug_set("reversal", xcd, grid_max)
 
     def debug_reversal_form(self):
         """the form of the last reversal launch: 1 vector (16 bytes per lane), 0 scalar, -1 none yet"""
@@ -1599,9 +1610,7 @@ class Tracker:
 
     def debug_reversal_launch(self):
         """(form, workgroups) of the last reversal launch"""
-        v = np.zeros(2, dtype=np.int64)
-        check(lib().ctk_debug_reversal_form(self._h, v.ctypes.data))
-        return int(v[0]), int(v[1])
+        return self._debug_launch("reversal", 2)
 
     # ---- selection of tracks or (step, track) rows of a flag slab (ctk_subset_*) -----------------------------------------
     def subset(self, flag, table, invert=False, kind='id', chunk_steps=0, want_out=True, want_hits=True):
@@ -1652,13 +1661,11 @@ class Tracker:
         """for the following subset launches -- xcd: how workgroups map to XCDs (0 launch order, 1 one contiguous eighth per XCD,
         n > 1 tiles of n; -1: the library's rule, ctk_subset_plan); grid_max: a lower cap on the workgroups of a launch (0: the
         rule's)"""
-        check(lib().ctk_debug_set_subset(self._h, int(xcd), int(grid_max)))
+        self._debug_set("subset", xcd, grid_max)
 
     def debug_subset_launch(self):
         """(form, vec, workgroups) of the last subset launch: form 0 .. 4 = SUBSET_FORMS (-1: none yet), vec 1 vector / 0 scalar"""
-        v = np.zeros(3, dtype=np.int64)
-        check(lib().ctk_debug_subset_form(self._h, v.ctypes.data))
-        return int(v[0]), int(v[1]), int(v[2])
+        return self._debug_launch("subset", 3)
 
     # ---- local wave activity (ctk_lwa_*) ---------------------------------------------------------------------------
     def lwa(self, x, rows, part='total', chunk_steps=0, keep_resident=False, want_out=True, want_ref=False):
@@ -1684,19 +1691,16 @@ class Tracker:
         shape = (steps, ny, nx).  sink: None (a new array is returned), False (nothing leaves the device: keep_resident), a
         C-contiguous (steps, ny, nx) array of `dtype`, or a writer(t0, nt, values).  Reader and writer see every step once, in
         rising order.  want_ref: returns (the array or None, ref)."""
-        if shape is None or dtype is None:
-            raise ValueError("a reader needs shape=(steps, ny, nx) and dtype")
-        steps, ny, nx = (int(v) for v in shape)
-        dt = np.dtype(dtype)
-        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise ValueError("the field must be float32 or float64")
-        args, _keep = _lwa_rows(rows, ny)
-        out, sink = _value_sink(sink, (steps, ny, nx), dt, "steps", "field", "keep_resident", keep_resident)
-        ref = np.empty((steps, ny), dtype=dt) if want_ref else None
-        tr = _Trampolines()
-        rcb, wcb = tr.reader(reader, _float_ctype(dt), (ny, nx)), tr.writer(sink, _float_ctype(dt), (ny, nx))
-        tr.finish(lib().ctk_lwa_stream_cb(self._h, dt.itemsize, steps, ny, nx, rcb, None, *args, _lwa_part(part), wcb, None, _ptr(ref), int(chunk_steps or 0),
-                                          int(bool(keep_resident))))
+        ref = None
+
+        def bind(dt, shape):
+            nonlocal ref
+            steps, ny, nx = shape
+            args, keep = _lwa_rows(rows, ny)
+            ref = np.empty((steps, ny), dtype=dt) if want_ref else None
+            return lambda rcb, wcb, _keep=keep: lib().ctk_lwa_stream_cb(self._h, dt.itemsize, steps, ny, nx, rcb, None, *args, _lwa_part(part), wcb, None, _ptr(ref),
+                                                                        int(chunk_steps or 0), int(bool(keep_resident)))
+        out = _values_cb(reader, shape, "(steps, ny, nx)", dtype, bind, sink, keep_resident)
         return (out, ref) if want_ref else out
 
     def lwa_dev(self, x_dev, steps, ny, nx, rows, out_dev, part='total', f64=False, want_ref=False):
@@ -1719,7 +1723,7 @@ class Tracker:
         """for the following lwa launches (both kernels) -- xcd: how workgroups map to XCDs (0 launch order, 1 one contiguous eighth
         per XCD, n > 1 tiles of n; -1: the library's rule, ctk_lwa_plan); grid_max: a lower cap on the workgroups of a launch (0:
         the rule's)"""
-        check(lib().ctk_debug_set_lwa(self._h, int(xcd), int(grid_max)))
+        self._debug_set("lwa", xcd, grid_max)
 
     def debug_lwa_form(self):
         """the form of the last lwa launch: 1 vector (16-byte loads of the strip), 0 scalar, -1 none yet"""
@@ -1727,9 +1731,7 @@ class Tracker:
 
     def debug_lwa_launch(self):
         """(form, workgroups) of the last k_lwa_integral launch"""
-        v = np.zeros(2, dtype=np.int64)
-        check(lib().ctk_debug_lwa_form(self._h, v.ctypes.data))
-        return int(v[0]), int(v[1])
+        return self._debug_launch("lwa", 2)
 
     def anomalies_resident(self, group, ngroups, window=1, smooth=1, clim=None, segments=None, keep_resident=False, want_anom=True, want_clim=False):
         """anomalies(..., segments=...) of the resident vertical mean (ctk_anom_seg_resident): nothing crosses PCIe on the way in.

@@ -214,6 +214,18 @@ struct StreamIO {
     int64_t passes_in = 0;                         // how often the input was streamed (2: the call had to re-read it)
 };
 
+// What a map family (level mean, reversal, local wave activity, subset) remembers of its launches and what its ctk_debug_set_* hook
+// overrides in the following ones
+struct LaunchKnobs {
+    int form = -1;                                 // kernel form of the last launch (-1: none yet)
+    int64_t grid = 0;                              // ... and its workgroups
+    int xcd_dbg = -1;                              // ctk_debug_set_*: xcd_chunk mode of the launches (-1: the plan's)
+    int64_t grid_dbg = 0;                          // ... a lower cap on the workgroups of a launch (0: none)
+    int64_t cap() const { return grid_dbg > 0 ? grid_dbg : CTK_LEVEL_GRID_MAX; }      // the cap to pass to the plan
+    int xcd(int planned) const { return xcd_dbg >= 0 ? xcd_dbg : planned; }           // the xcd_chunk mode of a launch, given the plan's
+    void launched(int f, int64_t g) { form = f; grid = g; }
+};
+
 // Every GPU resource below is an owner of ctk_own.h and goes with the handle: ctk_destroy names none of them.  Members are destroyed
 // in reverse order of declaration, so the streams stay declared ahead of everything that is enqueued on them.
 struct ctk_handle {
@@ -287,26 +299,21 @@ struct ctk_handle {
     DevBuf lv_out, lv_tab;
     int64_t lv_T = -1; int lv_ny = 0, lv_nx = 0; bool lv_f64 = false;
     uint64_t lv_gen = 0;                           // bumped by every ctk_level_mean_* call and by ctk_release_io: WHICH mean is resident
-    int lv_form = -1;                              // form of the last k_level_mean launch (1 vector, 0 scalar; -1: none yet)
-    int lv_xcd_dbg = -1;                           // ctk_debug_set_level: xcd_chunk mode of the launches (-1: ctk_level_plan's)
-    int64_t lv_grid_dbg = 0, lv_grid = 0;          // ... a lower cap on the workgroups of a launch (0: none); workgroups of the last launch
+    LaunchKnobs lv_knobs;                          // the k_level_mean launches (form: 1 vector, 0 scalar); ctk_debug_set_level
     // reversal of the meridional gradient (ctk_reversal.hip): the row table of the running call (four float64 and three int32 per row);
-    // the form of the last k_reversal launch (1 vector, 0 scalar; -1: none yet) and its workgroups; ctk_debug_set_reversal's xcd_chunk
-    // mode (-1: ctk_reversal_plan's) and lower cap on the workgroups of a launch (0: none)
+    // the k_reversal launches (form: 1 vector, 0 scalar) and ctk_debug_set_reversal
     DevBuf gr_tab;
-    int gr_form = -1, gr_xcd_dbg = -1;
-    int64_t gr_grid = 0, gr_grid_dbg = 0;
-    // local wave activity (ctk_lwa.hip): the row table of the running call and the contours (steps, ny) of the last one; the form of the
-    // last k_lwa_integral launch, its workgroups, and ctk_debug_set_lwa's two numbers (as the reversal's)
+    LaunchKnobs gr_knobs;
+    // local wave activity (ctk_lwa.hip): the row table of the running call and the contours (steps, ny) of the last one; the
+    // k_lwa_integral launches (form: 1 vector, 0 scalar) and ctk_debug_set_lwa, whose two numbers hold for k_lwa_contour too
     DevBuf lw_tab, lw_ref;
-    int lw_form = -1, lw_xcd_dbg = -1;
-    int64_t lw_grid = 0, lw_grid_dbg = 0;
+    LaunchKnobs lw_knobs;
     // selection of tracks or rows of a flag slab (ctk_subset.hip): the table of the running call (offsets, ids, bitmap words) and
-    // its counters (the words n_selected is summed from, then one per entry); form, vector or scalar and workgroups of the last k_subset launch (form -1: none
-    // yet); ctk_debug_set_subset's two numbers (as the reversal's)
+    // its counters (the words n_selected is summed from, then one per entry); the k_subset launches (form: CTK_SUBSET_BITMAP ..
+    // CTK_SUBSET_ROW_GLB of ctk_forms.h), whether the last one was vector or scalar, and ctk_debug_set_subset
     DevBuf sb_tab, sb_hits;
-    int sb_form = -1, sb_vec = 0, sb_xcd_dbg = -1;
-    int64_t sb_grid = 0, sb_grid_dbg = 0;
+    LaunchKnobs sb_knobs;
+    int sb_vec = 0;
     DevBuf io_in, io_out;                          // device copies of host-array calls (ctk_track_f32 / _f64)
     uint64_t io_gen = 0;                           // bumped by claim_io and ctk_release_io: WHOSE data io_in / io_out hold
     // streaming entries (ctk_track_stream_*): the slab passes through two chunk-sized device buffers per direction
@@ -910,6 +917,35 @@ static int time_launches(ctk_handle *h, const char *who, int reps, double *ms2, 
         best = std::min(best, (double)m); sum += m;
     }
     ms2[0] = best; ms2[1] = sum / reps;
+    return CTK_OK;
+}
+
+// The yardstick of the map families' ctk_debug_time_* hooks: k_copy16 over the whole 16-byte words of two 16-byte aligned buffers of
+// `bytes` bytes, timed as above, in the workgroup order a family's launch of this size takes (its ctk_debug_set_* mode included)
+static int time_copy16(ctk_handle *h, const char *who, const LaunchKnobs &k, const void *src, void *dst, int64_t bytes, int reps, double *ms2)
+{
+    const int64_t n16 = bytes / 16;
+    const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>((n16 + 255) / 256, 1), CTK_LEVEL_GRID_MAX);
+    const int xcd = k.xcd(grid >= CTK_LEVEL_XCD_MIN ? 1 : 0);
+    return time_launches(h, who, reps, ms2, [&]() -> int {
+        k_copy16<<<grid, 256, 0, h->stream>>>((const i32x4 *)src, (i32x4 *)dst, n16, xcd);
+        HIPCHK(hipGetLastError());
+        return CTK_OK;
+    });
+}
+
+// the bodies of the map families' ctk_debug_set_* and two-word ctk_debug_*_form hooks; k: the family's record in the handle
+static int knobs_set(const char *who, ctk_handle *h, LaunchKnobs ctk_handle::*k, int xcd_mode, int64_t grid_max)
+{
+    if (!h || xcd_mode < -1 || grid_max < 0) return ctk_set_error(CTK_E_INVALID, "%s: bad argument", who);
+    (h->*k).xcd_dbg = xcd_mode;
+    (h->*k).grid_dbg = grid_max;
+    return CTK_OK;
+}
+static int knobs_form(ctk_handle *h, LaunchKnobs ctk_handle::*k, int64_t *out2)
+{
+    if (!h || !out2) return ctk_set_error(CTK_E_INVALID, "null argument");
+    out2[0] = (h->*k).form; out2[1] = (h->*k).grid;
     return CTK_OK;
 }
 
@@ -3349,6 +3385,121 @@ static int stream_produce_end(ctk_handle *h, const StreamIO &io, int rc, double 
     HIPCHK(hipStreamSynchronize(h->stream));
     stream_ms_set(h, io);
     h->ms[CTK_T_H2D] = io.ms_in; h->ms[CTK_T_D2H] = io.ms_out; h->ms[CTK_T_TOTAL] = now_ms() - t_call;
+    return CTK_OK;
+}
+
+// What the producers of one plane per step share around stream_produce, as small functions each takes what fits it: ctk_level.hip the
+// output side, ctk_subset.hip the upload, ctk_reversal.hip and ctk_lwa.hip all of it through the row-band producer below.
+
+// the io of a *_stream_cb export of values: reader and writer as given, elem_bytes and the reader checked; who: the export
+static int stream_cb_io(const char *who, const ctk_handle *h, int elem_bytes, ctk_read_chunk_fn reader, void *reader_user, ctk_write_values_fn writer, void *writer_user,
+                        StreamIO &io)
+{
+    if (elem_bytes != 4 && elem_bytes != 8) return ctk_set_error(CTK_E_INVALID, "%s: elem_bytes must be 4 (float32) or 8 (float64)", who);
+    if (h && !reader) return ctk_set_error(CTK_E_INVALID, "%s: null reader", who);
+    io.read = reader; io.read_user = reader_user; io.write_v = writer; io.write_user = writer_user;
+    return CTK_OK;
+}
+
+// Producer::upload of chunks that travel whole: c.nt steps of `step` bytes, from the pinned chunk the reader filled or from io.host_in
+static int upload_steps(ctk_handle *h, const StreamIO &io, const ProduceIn &c, size_t step)
+{
+    const char *src = c.src ? c.src : (const char *)io.host_in + (size_t)c.c0 * step;
+    HIPCHK(hipMemcpyAsync(c.dev, src, (size_t)c.nt * step, hipMemcpyHostToDevice, h->copy_stream));
+    return CTK_OK;
+}
+
+// the output side of a call that may keep its result: with keep_resident all `steps` planes stay in `resident` and chunk buffers are
+// wanted for a writer only; without, two chunks in io_out, with pinned twins for a writer
+static int produce_out_setup(ctk_handle *h, const StreamIO &io, DevBuf &resident, int64_t steps, size_t plane, int keep_resident)
+{
+    if (keep_resident) {
+        CTKCHK(ensure(h, resident, (size_t)steps * plane));
+        if (io.write_v) CTKCHK(stream_setup(h, 0, (size_t)io.chunk * plane, true));
+    } else {
+        CTKCHK(stream_setup(h, 0, (size_t)io.chunk * plane, io.write_v != nullptr));
+    }
+    return CTK_OK;
+}
+// ... and where the planes of chunk c go then
+static char *produce_out_dev(ctk_handle *h, const StreamIO &io, const DevBuf &resident, const ProduceIn &c, size_t plane, int keep_resident)
+{
+    return keep_resident ? (char *)resident.p + (size_t)c.c0 * plane : (char *)h->io_out.p + (size_t)c.b * (size_t)io.chunk * plane;
+}
+
+// rows of every plane of `out` (steps, ny, nx) outside the `width` bytes from byte `off` on: zero
+static void zero_other_rows(void *out, int64_t steps, size_t plane, size_t off, size_t width)
+{
+    if (width == plane) return;
+    for (int64_t s = 0; s < steps; s++) {
+        char *p = (char *)out + (size_t)s * plane;
+        memset(p, 0, off);
+        memset(p + off + width, 0, plane - off - width);
+    }
+}
+
+// The row-band plane producer (ctk_reversal_*, ctk_lwa_*): a kernel over (steps, ny, nx) planes that reads only the rows [r0, r1) of a
+// plane and writes zeros outside its rows [a0, a1).  Of a host array only rows [r0, r1) of every plane travel to the device (one
+// strided copy per chunk, the plane as pitch) and only rows [a0, a1) travel back; the rest of the output array is zeroed on the host.
+// The device chunks keep the full-plane layout, readers fill and writers get whole planes.  keep_resident: the full-plane result is
+// written into the resident slot of the field to track (an_out), where ctk_track_resident and the `resident` consumers find it.
+struct RowBands { int r0, r1, a0, a1; };
+
+// its argument checks, in the order the entries report them, and the chunk plan: io.esz and io.chunk are set, no buffer is touched
+static int row_band_begin(ctk_handle *h, StreamIO &io, int64_t steps, size_t plane, size_t esz, int64_t chunk_steps, int keep_resident, const char *name)
+{
+    if (!io.read && !io.host_in) return ctk_set_error(CTK_E_INVALID, "%s: null input", name);
+    const bool sink = io.host_out_v || io.write_v;
+    if (!sink && !keep_resident) return ctk_set_error(CTK_E_INVALID, "%s: nothing to produce (no output and keep_resident = 0)", name);
+    if (chunk_steps < 0) return ctk_set_error(CTK_E_INVALID, "%s: chunk_steps = %lld", name, (long long)chunk_steps);
+    HIPCHK(hipSetDevice(h->device));
+    io.esz = esz;
+    io.chunk = ctk_stream_chunk(chunk_steps, steps, plane);
+    return CTK_OK;
+}
+
+// ... and the call itself after row_band_begin.  tables: uploads the family's device tables once the chunk buffers stand; launch:
+// queues the kernels of chunk c on the handle's stream, the planes of its steps going to `out`.
+static int row_band_produce(ctk_handle *h, StreamIO &io, int64_t steps, int ny, int nx, const RowBands &rb, int keep_resident, const char *name,
+                            const std::function<int()> &tables, const std::function<int(const ProduceIn &c, char *out)> &launch)
+{
+    const size_t row = (size_t)nx * io.esz, plane = (size_t)ny * row;
+    const double t_call = now_ms();
+    CTKCHK(stream_setup(h, (size_t)io.chunk * plane, 0, io.read != nullptr));
+    if (keep_resident) { h->an_T = -1; h->an_gen++; h->an_pct_n = -1; }           // the resident slab (if any) is dropped or about to be overwritten
+    CTKCHK(produce_out_setup(h, io, h->an_out, steps, plane, keep_resident));
+    CTKCHK(tables());
+    const size_t in_off = (size_t)rb.r0 * row, in_w = (size_t)(rb.r1 - rb.r0) * row, out_off = (size_t)rb.a0 * row, out_w = (size_t)(rb.a1 - rb.a0) * row;
+    // the rows of `out` that nothing is downloaded into are zeroed by a helper thread while the chunks travel (other bytes than the
+    // copies write; at 1 degree, one hemisphere, that is three quarters of the array)
+    struct Joiner { std::thread t; ~Joiner() { if (t.joinable()) t.join(); } } zero;
+    if (io.host_out_v) zero.t = std::thread(zero_other_rows, io.host_out_v, steps, plane, out_off, out_w);
+    // the chunks (stream_produce): io.host_in is the whole (steps, ny, nx) array (rows [r0, r1) of every plane travel), io.read a
+    // reader of whole planes.  The results go to io.host_out_v (rows [a0, a1) of every plane) / io.write_v (whole planes) chunk by
+    // chunk and (keep) into an_out.
+    Producer p;
+    p.in_bytes = (size_t)io.chunk * plane; p.out_step = plane;
+    p.upload = [&](const ProduceIn &c) -> int {
+        if (in_w == plane) return upload_steps(h, io, c, plane);
+        // (an empty band: a reversal table without an active row.  ctk_lwa_* never has one: lwa_check wants a row in every domain.)
+        const char *src = c.src ? c.src : (const char *)io.host_in + (size_t)c.c0 * plane;
+        if (in_w) HIPCHK(hipMemcpy2DAsync(c.dev + in_off, plane, src + in_off, plane, in_w, (size_t)c.nt, hipMemcpyHostToDevice, h->copy_stream));      // row s of the copy: rows [r0, r1) of step c0 + s
+        return CTK_OK;
+    };
+    p.launch = [&](const ProduceIn &c, ProduceOut &o) -> int {
+        o.t0 = c.c0; o.nt = c.nt;
+        o.dev = produce_out_dev(h, io, h->an_out, c, plane, keep_resident);
+        return launch(c, o.dev);
+    };
+    if (out_w != plane)
+        p.download = [&](const ProduceOut &o, char *dst) -> int {
+            if (out_w) HIPCHK(hipMemcpy2D(dst + out_off, plane, o.dev + out_off, plane, out_w, (size_t)o.nt, hipMemcpyDeviceToHost));
+            return CTK_OK;
+        };
+    const int rc = stream_produce(h, io, steps, name, p);
+    if (zero.t.joinable()) zero.t.join();
+    CTKCHK(stream_produce_end(h, io, rc, t_call));
+    if (keep_resident) { h->an_T = steps; h->an_ny = ny; h->an_nx = nx; h->an_f64 = io.esz == 8; }
     return CTK_OK;
 }
 

@@ -176,6 +176,16 @@ __device__ __forceinline__ unsigned xcd_chunk(unsigned b, unsigned n, int on)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// a plain copy of n16 16-byte words, one load and one store per lane, in the workgroup order of xcd_chunk: the floor of a read-once,
+// write-once kernel over the same two buffers (time_copy16, ctk_api.hip)
+__global__ __launch_bounds__(256) void k_copy16(const i32x4 *__restrict__ src, i32x4 *__restrict__ dst, int64_t n16, int xcd)
+{
+    for (int64_t b = xcd_chunk(blockIdx.x, gridDim.x, xcd); b * 256 < n16; b += gridDim.x) {
+        const int64_t i = b * 256 + threadIdx.x;
+        if (i < n16) dst[i] = src[i];
+    }
+}
 // SGPRs cost occupancy on this board (round 6, tools/occupancy_probe.hip: workgroups of 256 threads per CU with 16 SGPRs in use 8, with 86 or
 // 94: 7, with 102 or 108: 6 -- whatever the guides say about a fixed SGPR allotment per wave).  Kernels that take a struct of a dozen pointers by
 // value and hold it in SGPRs end at 100-106: six waves per SIMD, i.e. six instead of eight 256-thread workgroups per CU, ONE instead of two

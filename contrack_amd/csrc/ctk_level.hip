@@ -153,9 +153,9 @@ static int launch_level(ctk_handle *h, const VT *x, int64_t nlev, int64_t npix, 
                         int skipna, VT *out)
 {
     const bool aligned = (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
-    const CtkLevelPlan pl = ctk_level_plan((int)sizeof(VT), nsel, npix, steps, aligned, h->lv_grid_dbg > 0 ? h->lv_grid_dbg : CTK_LEVEL_GRID_MAX);
-    h->lv_form = pl.vec; h->lv_grid = pl.grid;
-    const int xcd = h->lv_xcd_dbg >= 0 ? h->lv_xcd_dbg : pl.xcd;
+    const CtkLevelPlan pl = ctk_level_plan((int)sizeof(VT), nsel, npix, steps, aligned, h->lv_knobs.cap());
+    h->lv_knobs.launched(pl.vec, pl.grid);
+    const int xcd = h->lv_knobs.xcd(pl.xcd);
 #define CTK_LEVEL_LAUNCH(V, S) k_level_mean<VT, V, S><<<pl.grid, CTK_LEVEL_THREADS, 0, h->stream>>>(x, nlev, npix, pl.bps, pl.blocks, nsel, w_dev, lev_dev, wsum, out, xcd)
     if (pl.vec) { if (skipna) CTK_LEVEL_LAUNCH(true, true); else CTK_LEVEL_LAUNCH(true, false); }
     else        { if (skipna) CTK_LEVEL_LAUNCH(false, true); else CTK_LEVEL_LAUNCH(false, false); }
@@ -217,12 +217,7 @@ static int level_stream_impl(ctk_handle *h, StreamIO &io, int64_t steps, int64_t
     const double t_call = now_ms();
     h->lv_T = -1; h->lv_gen++;                                         // the resident mean (if any) is dropped or about to be overwritten
     CTKCHK(stream_setup(h, (size_t)io.chunk * (size_t)K * plane, 0, io.read != nullptr));
-    if (keep_resident) {
-        CTKCHK(ensure(h, h->lv_out, (size_t)steps * plane));
-        if (io.write_v) CTKCHK(stream_setup(h, 0, (size_t)io.chunk * plane, true));
-    } else {
-        CTKCHK(stream_setup(h, 0, (size_t)io.chunk * plane, io.write_v != nullptr));
-    }
+    CTKCHK(produce_out_setup(h, io, h->lv_out, steps, plane, keep_resident));
     const double *w_dev = nullptr;
     const int32_t *lev_dev = nullptr;
     CTKCHK(level_table(h, sel, true, &w_dev, &lev_dev));
@@ -231,11 +226,7 @@ static int level_stream_impl(ctk_handle *h, StreamIO &io, int64_t steps, int64_t
     Producer p;
     p.in_bytes = (size_t)io.chunk * (size_t)K * plane; p.out_step = plane;
     p.upload = [&](const ProduceIn &c) -> int {
-        if (c.src || K == nlev) {
-            const char *src = c.src ? c.src : (const char *)io.host_in + (size_t)c.c0 * (size_t)nlev * plane;
-            HIPCHK(hipMemcpyAsync(c.dev, src, (size_t)c.nt * (size_t)K * plane, hipMemcpyHostToDevice, h->copy_stream));
-            return CTK_OK;
-        }
+        if (c.src || K == nlev) return upload_steps(h, io, c, (size_t)K * plane);
         for (const CtkLevelRun &r : sel.runs)                                   // row s of the copy: the run's planes of step c0 + s
             HIPCHK(hipMemcpy2DAsync(c.dev + (size_t)r.k0 * plane, (size_t)K * plane, (const char *)io.host_in + ((size_t)c.c0 * (size_t)nlev + (size_t)r.l0) * plane,
                                     (size_t)nlev * plane, (size_t)r.len * plane, (size_t)c.nt, hipMemcpyHostToDevice, h->copy_stream));
@@ -243,7 +234,7 @@ static int level_stream_impl(ctk_handle *h, StreamIO &io, int64_t steps, int64_t
     };
     p.launch = [&](const ProduceIn &c, ProduceOut &o) -> int {
         o.t0 = c.c0; o.nt = c.nt;
-        o.dev = keep_resident ? (char *)h->lv_out.p + (size_t)c.c0 * plane : (char *)h->io_out.p + (size_t)c.b * (size_t)io.chunk * plane;
+        o.dev = produce_out_dev(h, io, h->lv_out, c, plane, keep_resident);
         return launch_level<VT>(h, (const VT *)c.dev, K, npix, c.nt, (int)K, w_dev, lev_dev, sel.wsum, skipna, (VT *)o.dev);
     };
     CTKCHK(stream_produce_end(h, io, stream_produce(h, io, steps, name, p), t_call));
@@ -282,10 +273,8 @@ extern "C" int ctk_level_mean_stream_f64(ctk_handle *h, const double *x, int64_t
 extern "C" int ctk_level_mean_stream_cb(ctk_handle *h, int elem_bytes, int64_t steps, int nsel, int ny, int nx, ctk_read_chunk_fn reader, void *reader_user,
                                         const double *weights_sel, int skipna, ctk_write_values_fn writer, void *writer_user, int64_t chunk_steps, int keep_resident)
 {
-    if (elem_bytes != 4 && elem_bytes != 8) return ctk_set_error(CTK_E_INVALID, "ctk_level_mean_stream_cb: elem_bytes must be 4 (float32) or 8 (float64)");
-    if (h && !reader) return ctk_set_error(CTK_E_INVALID, "ctk_level_mean_stream_cb: null reader");
     StreamIO io;
-    io.read = reader; io.read_user = reader_user; io.write_v = writer; io.write_user = writer_user;
+    CTKCHK(stream_cb_io("ctk_level_mean_stream_cb", h, elem_bytes, reader, reader_user, writer, writer_user, io));
     if (elem_bytes == 8) return level_stream_impl<double>(h, io, steps, nsel, ny, nx, weights_sel, skipna, chunk_steps, keep_resident, "ctk_level_mean_stream_cb");
     return level_stream_impl<float>(h, io, steps, nsel, ny, nx, weights_sel, skipna, chunk_steps, keep_resident, "ctk_level_mean_stream_cb");
 }
@@ -336,9 +325,7 @@ extern "C" int ctk_debug_level_plan(int elem_bytes, int64_t nsel, int64_t npix, 
 // test hook: out2 = { the form of the last k_level_mean launch on this handle (1 vector, 0 scalar, -1 none yet), its workgroups }
 extern "C" int ctk_debug_level_form(ctk_handle *h, int64_t *out2)
 {
-    if (!h || !out2) return ctk_set_error(CTK_E_INVALID, "null argument");
-    out2[0] = h->lv_form; out2[1] = h->lv_grid;
-    return CTK_OK;
+    return knobs_form(h, &ctk_handle::lv_knobs, out2);
 }
 
 // test hook / experiments (tools/level_probe.py) for the following k_level_mean launches on this handle: the xcd_chunk mode (0 launch
@@ -346,10 +333,7 @@ extern "C" int ctk_debug_level_form(ctk_handle *h, int64_t *out2)
 // a small case walks the stride loop (0: CTK_LEVEL_GRID_MAX)
 extern "C" int ctk_debug_set_level(ctk_handle *h, int xcd_mode, int64_t grid_max)
 {
-    if (!h || xcd_mode < -1 || grid_max < 0) return ctk_set_error(CTK_E_INVALID, "ctk_debug_set_level: bad argument");
-    h->lv_xcd_dbg = xcd_mode;
-    h->lv_grid_dbg = grid_max;
-    return CTK_OK;
+    return knobs_set("ctk_debug_set_level", h, &ctk_handle::lv_knobs, xcd_mode, grid_max);
 }
 
 // measurement (tools/level_probe.py): k_level_mean alone between HIP events on slabs in device memory -- one launch that is not counted,

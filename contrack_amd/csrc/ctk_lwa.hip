@@ -208,15 +208,6 @@ __global__ __launch_bounds__(CTK_LWA_THREADS) CTK_SGPR_8WAVES void k_lwa_integra
     }
 }
 
-// a plain copy of n16 16-byte words: the floor of a read-once, write-once kernel over the same two buffers (ctk_debug_time_lwa)
-__global__ __launch_bounds__(256) void k_lwa_copy(const i32x4 *__restrict__ src, i32x4 *__restrict__ dst, int64_t n16, int xcd)
-{
-    for (int64_t b = xcd_chunk(blockIdx.x, gridDim.x, xcd); b * 256 < n16; b += gridDim.x) {
-        const int64_t i = b * 256 + threadIdx.x;
-        if (i < n16) dst[i] = src[i];
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------
@@ -300,7 +291,7 @@ static int lwa_check(const char *who, const void *h, int64_t steps, int ny, int 
 // the plan of a launch over `steps` steps, or CTK_E_INVALID at the capacity edge
 static int lwa_plan_of(ctk_handle *h, const char *who, int esz, const LwaHost &t, int nx, int64_t steps, bool aligned, CtkLwaPlan &pl)
 {
-    pl = ctk_lwa_plan(esz, t.max_rows, nx, (int64_t)t.dom_off.size() - 1, steps, aligned, h->lw_grid_dbg > 0 ? h->lw_grid_dbg : CTK_LEVEL_GRID_MAX);
+    pl = ctk_lwa_plan(esz, t.max_rows, nx, (int64_t)t.dom_off.size() - 1, steps, aligned, h->lw_knobs.cap());
     if (!pl.ok)
         return ctk_set_error(CTK_E_INVALID, "%s: a domain of %d rows does not fit in LDS (%d bytes: %d-byte pixels in strips of %d, 32 bytes per row for the contours)", who,
                              t.max_rows, CTK_LWA_LDS_MAX, esz, pl.vec ? 4 : 1);
@@ -334,7 +325,7 @@ static int launch_lwa_contour(ctk_handle *h, const VT *z, int ny, int nx, int64_
 {
     HIPCHK(hipMemsetAsync(ref, 0, (size_t)steps * ny * sizeof(VT), h->stream));
     if (t.act_pos.empty()) return CTK_OK;
-    const int xcd = h->lw_xcd_dbg >= 0 ? h->lw_xcd_dbg : pl.sel_xcd;
+    const int xcd = h->lw_knobs.xcd(pl.sel_xcd);
     k_lwa_contour<VT><<<pl.sel_grid, CTK_LWA_SEL_THREADS, (size_t)pl.lds_sel, h->stream>>>(z, ny, nx, pl.sel_blocks, tab, t.max_rows + 1, ref, xcd);
     HIPCHK(hipGetLastError());
     return CTK_OK;
@@ -344,9 +335,9 @@ static int launch_lwa_integral(ctk_handle *h, const VT *z, int ny, int nx, int64
                                VT *out)
 {
     HIPCHK(hipMemsetAsync(out, 0, (size_t)steps * ny * nx * sizeof(VT), h->stream));
-    h->lw_form = pl.vec; h->lw_grid = pl.grid;
+    h->lw_knobs.launched(pl.vec, pl.grid);
     if (t.act_pos.empty()) return CTK_OK;
-    const int xcd = h->lw_xcd_dbg >= 0 ? h->lw_xcd_dbg : pl.xcd;
+    const int xcd = h->lw_knobs.xcd(pl.xcd);
     if (pl.vec) k_lwa_integral<VT, true><<<pl.grid, CTK_LWA_THREADS, (size_t)pl.lds, h->stream>>>(z, ny, nx, pl.strip, (int)pl.nstrips, pl.blocks, tab, ref, part, out, xcd);
     else k_lwa_integral<VT, false><<<pl.grid, CTK_LWA_THREADS, (size_t)pl.lds, h->stream>>>(z, ny, nx, pl.strip, (int)pl.nstrips, pl.blocks, tab, ref, part, out, xcd);
     HIPCHK(hipGetLastError());
@@ -390,60 +381,24 @@ static int lwa_stream_impl(ctk_handle *h, StreamIO &io, int64_t steps, int ny, i
 {
     LwaHost t;
     CTKCHK(lwa_check(name, h, steps, ny, nx, a, t));
-    if (!io.read && !io.host_in) return ctk_set_error(CTK_E_INVALID, "%s: null input", name);
-    const bool sink = io.host_out_v || io.write_v;
-    if (!sink && !keep_resident) return ctk_set_error(CTK_E_INVALID, "%s: nothing to produce (no output and keep_resident = 0)", name);
-    if (chunk_steps < 0) return ctk_set_error(CTK_E_INVALID, "%s: chunk_steps = %lld", name, (long long)chunk_steps);
-    HIPCHK(hipSetDevice(h->device));
-    const size_t row = (size_t)nx * sizeof(VT), plane = (size_t)ny * row;
-    io.esz = sizeof(VT);
-    io.chunk = ctk_stream_chunk(chunk_steps, steps, plane);
+    CTKCHK(row_band_begin(h, io, steps, (size_t)ny * nx * sizeof(VT), sizeof(VT), chunk_steps, keep_resident, name));
     CtkLwaPlan pl0;
     CTKCHK(lwa_plan_of(h, name, (int)sizeof(VT), t, nx, io.chunk, true, pl0));     // (the capacity edge, before anything is touched)
-    const double t_call = now_ms();
-    CTKCHK(stream_setup(h, (size_t)io.chunk * plane, 0, io.read != nullptr));
-    if (keep_resident) {
-        h->an_T = -1; h->an_gen++; h->an_pct_n = -1;                   // the resident slab (if any) is dropped or about to be overwritten
-        CTKCHK(ensure(h, h->an_out, (size_t)steps * plane));
-        if (io.write_v) CTKCHK(stream_setup(h, 0, (size_t)io.chunk * plane, true));
-    } else {
-        CTKCHK(stream_setup(h, 0, (size_t)io.chunk * plane, io.write_v != nullptr));
-    }
     LwaTab tab;
-    CTKCHK(lwa_table(h, t, tab));
-    CTKCHK(ensure(h, h->lw_ref, (size_t)steps * ny * sizeof(VT)));              // the contours of the whole call: they leave at its end
-    struct Joiner { std::thread t; ~Joiner() { if (t.joinable()) t.join(); } } zero;
-    if (io.host_out_v) zero.t = std::thread(reversal_zero_rest, io.host_out_v, steps, plane, (size_t)t.a0 * row, (size_t)(t.a1 - t.a0) * row);
-    // the chunks (stream_produce), as ctk_reversal_*: rows [r0, r1) of every plane of io.host_in travel in (a reader fills whole
-    // planes), rows [a0, a1) travel out to io.host_out_v (a writer gets whole planes); the device chunks keep the full-plane layout
-    const size_t in_off = (size_t)t.r0 * row, in_w = (size_t)(t.r1 - t.r0) * row, out_off = (size_t)t.a0 * row, out_w = (size_t)(t.a1 - t.a0) * row;
-    Producer p;
-    p.in_bytes = (size_t)io.chunk * plane; p.out_step = plane;
-    p.upload = [&](const ProduceIn &c) -> int {
-        const char *src = c.src ? c.src : (const char *)io.host_in + (size_t)c.c0 * plane;
-        if (in_w == plane) HIPCHK(hipMemcpyAsync(c.dev, src, (size_t)c.nt * plane, hipMemcpyHostToDevice, h->copy_stream));
-        else HIPCHK(hipMemcpy2DAsync(c.dev + in_off, plane, src + in_off, plane, in_w, (size_t)c.nt, hipMemcpyHostToDevice, h->copy_stream));
-        return CTK_OK;
-    };
-    p.launch = [&](const ProduceIn &c, ProduceOut &o) -> int {
-        o.t0 = c.c0; o.nt = c.nt;
-        o.dev = keep_resident ? (char *)h->an_out.p + (size_t)c.c0 * plane : (char *)h->io_out.p + (size_t)c.b * (size_t)io.chunk * plane;
-        CtkLwaPlan pl;
-        CTKCHK(lwa_plan_of(h, name, (int)sizeof(VT), t, nx, c.nt, (((uintptr_t)c.dev | (uintptr_t)o.dev) & 15) == 0, pl));
-        VT *zr = (VT *)h->lw_ref.p + c.c0 * ny;
-        CTKCHK(launch_lwa_contour<VT>(h, (const VT *)c.dev, ny, nx, c.nt, tab, t, pl, zr));
-        return launch_lwa_integral<VT>(h, (const VT *)c.dev, ny, nx, c.nt, tab, t, pl, zr, a.part, (VT *)o.dev);
-    };
-    if (out_w != plane)
-        p.download = [&](const ProduceOut &o, char *dst) -> int {
-            if (out_w) HIPCHK(hipMemcpy2D(dst + out_off, plane, o.dev + out_off, plane, out_w, (size_t)o.nt, hipMemcpyDeviceToHost));
-            return CTK_OK;
-        };
-    const int rc = stream_produce(h, io, steps, name, p);
-    if (zero.t.joinable()) zero.t.join();
-    CTKCHK(stream_produce_end(h, io, rc, t_call));
+    CTKCHK(row_band_produce(
+        h, io, steps, ny, nx, {t.r0, t.r1, t.a0, t.a1}, keep_resident, name,
+        [&]() -> int {
+            CTKCHK(lwa_table(h, t, tab));
+            return ensure(h, h->lw_ref, (size_t)steps * ny * sizeof(VT));       // the contours of the whole call: they leave at its end
+        },
+        [&](const ProduceIn &c, char *out) -> int {
+            CtkLwaPlan pl;
+            CTKCHK(lwa_plan_of(h, name, (int)sizeof(VT), t, nx, c.nt, (((uintptr_t)c.dev | (uintptr_t)out) & 15) == 0, pl));
+            VT *zr = (VT *)h->lw_ref.p + c.c0 * ny;
+            CTKCHK(launch_lwa_contour<VT>(h, (const VT *)c.dev, ny, nx, c.nt, tab, t, pl, zr));
+            return launch_lwa_integral<VT>(h, (const VT *)c.dev, ny, nx, c.nt, tab, t, pl, zr, a.part, (VT *)out);
+        }));
     if (ref) HIPCHK(hipMemcpy(ref, h->lw_ref.p, (size_t)steps * ny * sizeof(VT), hipMemcpyDeviceToHost));
-    if (keep_resident) { h->an_T = steps; h->an_ny = ny; h->an_nx = nx; h->an_f64 = sizeof(VT) == 8; }
     return CTK_OK;
 }
 
@@ -467,11 +422,9 @@ extern "C" int ctk_lwa_stream_cb(ctk_handle *h, int elem_bytes, int64_t steps, i
                                  const int32_t *dom_rows, const uint8_t *active, const uint32_t *W, const double *q, const double *S, int part, ctk_write_values_fn writer,
                                  void *writer_user, void *ref, int64_t chunk_steps, int keep_resident)
 {
-    if (elem_bytes != 4 && elem_bytes != 8) return ctk_set_error(CTK_E_INVALID, "ctk_lwa_stream_cb: elem_bytes must be 4 (float32) or 8 (float64)");
-    if (h && !reader) return ctk_set_error(CTK_E_INVALID, "ctk_lwa_stream_cb: null reader");
     const LwaArgs a = {ndom, dom_off, dom_rows, active, W, q, S, part};
     StreamIO io;
-    io.read = reader; io.read_user = reader_user; io.write_v = writer; io.write_user = writer_user;
+    CTKCHK(stream_cb_io("ctk_lwa_stream_cb", h, elem_bytes, reader, reader_user, writer, writer_user, io));
     if (elem_bytes == 8) return lwa_stream_impl<double>(h, io, steps, ny, nx, a, (double *)ref, chunk_steps, keep_resident, "ctk_lwa_stream_cb");
     return lwa_stream_impl<float>(h, io, steps, ny, nx, a, (float *)ref, chunk_steps, keep_resident, "ctk_lwa_stream_cb");
 }
@@ -490,18 +443,13 @@ extern "C" int ctk_debug_lwa_plan(int elem_bytes, int64_t rows, int64_t nx, int6
 // test hook: out2 = { the form of the last k_lwa_integral launch on this handle (1 vector, 0 scalar, -1 none yet), its workgroups }
 extern "C" int ctk_debug_lwa_form(ctk_handle *h, int64_t *out2)
 {
-    if (!h || !out2) return ctk_set_error(CTK_E_INVALID, "null argument");
-    out2[0] = h->lw_form; out2[1] = h->lw_grid;
-    return CTK_OK;
+    return knobs_form(h, &ctk_handle::lw_knobs, out2);
 }
 
 // test hook / experiments (tools/lwa_probe.py) for the following launches of both kernels on this handle: as ctk_debug_set_reversal
 extern "C" int ctk_debug_set_lwa(ctk_handle *h, int xcd_mode, int64_t grid_max)
 {
-    if (!h || xcd_mode < -1 || grid_max < 0) return ctk_set_error(CTK_E_INVALID, "ctk_debug_set_lwa: bad argument");
-    h->lw_xcd_dbg = xcd_mode;
-    h->lw_grid_dbg = grid_max;
-    return CTK_OK;
+    return knobs_set("ctk_debug_set_lwa", h, &ctk_handle::lw_knobs, xcd_mode, grid_max);
 }
 
 // measurement (tools/lwa_probe.py): one stage alone between HIP events on slabs in device memory -- one launch that is not counted,
@@ -516,16 +464,7 @@ extern "C" int ctk_debug_time_lwa(ctk_handle *h, const void *x_dev, int is_f64, 
     if ((((uintptr_t)x_dev | (uintptr_t)out_dev) & 15) != 0) return ctk_set_error(CTK_E_INVALID, "ctk_debug_time_lwa: 16-byte aligned buffers");
     HIPCHK(hipSetDevice(h->device));
     const size_t esz = is_f64 ? 8 : 4;
-    if (stage == 0) {
-        const int64_t n16 = steps * (int64_t)ny * nx * (int64_t)esz / 16;
-        const unsigned cgrid = (unsigned)std::min<int64_t>(std::max<int64_t>((n16 + 255) / 256, 1), CTK_LEVEL_GRID_MAX);
-        const int cxcd = h->lw_xcd_dbg >= 0 ? h->lw_xcd_dbg : (cgrid >= CTK_LEVEL_XCD_MIN ? 1 : 0);
-        return time_launches(h, "ctk_debug_time_lwa", reps, ms2, [&]() -> int {
-            k_lwa_copy<<<cgrid, 256, 0, h->stream>>>((const i32x4 *)x_dev, (i32x4 *)out_dev, n16, cxcd);
-            HIPCHK(hipGetLastError());
-            return CTK_OK;
-        });
-    }
+    if (stage == 0) return time_copy16(h, "ctk_debug_time_lwa", h->lw_knobs, x_dev, out_dev, steps * (int64_t)ny * nx * (int64_t)esz, reps, ms2);
     LwaHost t;
     CTKCHK(lwa_check("ctk_debug_time_lwa", h, steps, ny, nx, a, t));
     CtkLwaPlan pl;

@@ -16,11 +16,8 @@
 // workgroup stays inside one step (ctk_reversal_plan, ctk_forms.h); large launches give every XCD one contiguous eighth of the
 // workgroups (xcd_chunk), so that all readers of a row share one L2.
 //
-// Host-array entries: of every plane only the rows [r0, r1) that some active row reads travel to the device (one strided copy per
-// chunk, the plane as pitch) and only the rows [a0, a1) the active rows span travel back; the rest of `out` is zeroed on the host.
-// The device chunks keep the full-plane layout, so the kernel is the one of the _dev entries.  Two input and two output chunks on the
-// handle's copy stream (stream_produce, ctk_api.hip).  keep_resident: the full-plane result is written into the resident slot of the
-// field to track (an_out), where ctk_track_resident and the `resident` consumers find it.
+// Host-array entries: the row-band plane producer of ctk_api.hip (row_band_produce) with the rows [r0, r1) that some active row reads
+// and the rows [a0, a1) the active rows span.  The device chunks keep the full-plane layout, so the kernel is the one of the _dev entries.
 #pragma once
 
 // the row table of a call on the device: dE, tS, tN, tS2 (ny float64 each), then eq, po, eq2 (ny int32 each)
@@ -67,16 +64,6 @@ __global__ __launch_bounds__(CTK_REVERSAL_THREADS) void k_reversal(const VT *__r
             }
         }
         *(V *)(out + s * npix + (int64_t)j * nx + c) = r;
-    }
-}
-
-// a plain copy of n16 16-byte words, one load and one store per lane: the floor of a read-once, write-once kernel over the same two
-// buffers (ctk_debug_time_reversal)
-__global__ __launch_bounds__(256) void k_reversal_copy(const i32x4 *__restrict__ src, i32x4 *__restrict__ dst, int64_t n16, int xcd)
-{
-    for (int64_t b = xcd_chunk(blockIdx.x, gridDim.x, xcd); b * 256 < n16; b += gridDim.x) {
-        const int64_t i = b * 256 + threadIdx.x;
-        if (i < n16) dst[i] = src[i];
     }
 }
 
@@ -134,9 +121,9 @@ template <typename VT>
 static int launch_reversal(ctk_handle *h, const VT *z, int ny, int nx, int64_t steps, const ReversalTab &tab, bool second, bool mask, VT *out)
 {
     const bool aligned = (((uintptr_t)z | (uintptr_t)out) & 15) == 0;
-    const CtkReversalPlan pl = ctk_reversal_plan((int)sizeof(VT), ny, nx, steps, aligned, h->gr_grid_dbg > 0 ? h->gr_grid_dbg : CTK_LEVEL_GRID_MAX);
-    h->gr_form = pl.vec; h->gr_grid = pl.grid;
-    const int xcd = h->gr_xcd_dbg >= 0 ? h->gr_xcd_dbg : pl.xcd;
+    const CtkReversalPlan pl = ctk_reversal_plan((int)sizeof(VT), ny, nx, steps, aligned, h->gr_knobs.cap());
+    h->gr_knobs.launched(pl.vec, pl.grid);
+    const int xcd = h->gr_knobs.xcd(pl.xcd);
     const uint32_t lpr = (uint32_t)(nx / pl.vpt);
 #define CTK_REVERSAL_LAUNCH(V, S, M) k_reversal<VT, V, S, M><<<pl.grid, CTK_REVERSAL_THREADS, 0, h->stream>>>(z, ny, nx, lpr, pl.bps, pl.blocks, tab, out, xcd)
 #define CTK_REVERSAL_SM(V) do { if (second) { if (mask) CTK_REVERSAL_LAUNCH(V, true, true); else CTK_REVERSAL_LAUNCH(V, true, false); } \
@@ -174,72 +161,16 @@ extern "C" int ctk_reversal_f64_dev(ctk_handle *h, const double *x_dev, int64_t 
     return reversal_dev_impl<double>(h, x_dev, steps, ny, nx, a, out_dev, "ctk_reversal_f64_dev");
 }
 
-// rows of every plane of `out` (steps, ny, nx) outside [a0, a1): zero
-static void reversal_zero_rest(void *out, int64_t steps, size_t plane, size_t off, size_t width)
-{
-    if (width == plane) return;
-    for (int64_t s = 0; s < steps; s++) {
-        char *p = (char *)out + (size_t)s * plane;
-        memset(p, 0, off);
-        memset(p + off + width, 0, plane - off - width);
-    }
-}
-
 template <typename VT>
 static int reversal_stream_impl(ctk_handle *h, StreamIO &io, int64_t steps, int ny, int nx, const ReversalArgs &a, int64_t chunk_steps, int keep_resident, const char *name)
 {
     CTKCHK(reversal_check(name, h, steps, ny, nx, a));
-    if (!io.read && !io.host_in) return ctk_set_error(CTK_E_INVALID, "%s: null input", name);
-    const bool sink = io.host_out_v || io.write_v;
-    if (!sink && !keep_resident) return ctk_set_error(CTK_E_INVALID, "%s: nothing to produce (no output and keep_resident = 0)", name);
-    if (chunk_steps < 0) return ctk_set_error(CTK_E_INVALID, "%s: chunk_steps = %lld", name, (long long)chunk_steps);
-    HIPCHK(hipSetDevice(h->device));
-    const size_t row = (size_t)nx * sizeof(VT), plane = (size_t)ny * row;
+    CTKCHK(row_band_begin(h, io, steps, (size_t)ny * nx * sizeof(VT), sizeof(VT), chunk_steps, keep_resident, name));
     const CtkReversalRows rr = ctk_reversal_rows(a.eq, a.po, a.eq2, ny);
-    io.esz = sizeof(VT);
-    io.chunk = ctk_stream_chunk(chunk_steps, steps, plane);
-    const double t_call = now_ms();
-    CTKCHK(stream_setup(h, (size_t)io.chunk * plane, 0, io.read != nullptr));
-    if (keep_resident) {
-        h->an_T = -1; h->an_gen++; h->an_pct_n = -1;                   // the resident slab (if any) is dropped or about to be overwritten
-        CTKCHK(ensure(h, h->an_out, (size_t)steps * plane));
-        if (io.write_v) CTKCHK(stream_setup(h, 0, (size_t)io.chunk * plane, true));
-    } else {
-        CTKCHK(stream_setup(h, 0, (size_t)io.chunk * plane, io.write_v != nullptr));
-    }
     ReversalTab tab;
-    CTKCHK(reversal_table(h, ny, a, tab));
-    // the rows of `out` that nothing is downloaded into are zeroed by a helper thread while the chunks travel (other bytes than the
-    // copies write; at 1 degree, one hemisphere, that is three quarters of the array)
-    struct Joiner { std::thread t; ~Joiner() { if (t.joinable()) t.join(); } } zero;
-    if (io.host_out_v) zero.t = std::thread(reversal_zero_rest, io.host_out_v, steps, plane, (size_t)rr.a0 * row, (size_t)(rr.a1 - rr.a0) * row);
-    // the chunks (stream_produce): io.host_in is the whole (steps, ny, nx) array (rows [r0, r1) of every plane travel), io.read a
-    // reader of whole planes.  The results go to io.host_out_v (rows [a0, a1) of every plane) / io.write_v (whole planes) chunk by
-    // chunk and (keep) into an_out.
-    const size_t in_off = (size_t)rr.r0 * row, in_w = (size_t)(rr.r1 - rr.r0) * row, out_off = (size_t)rr.a0 * row, out_w = (size_t)(rr.a1 - rr.a0) * row;
-    Producer p;
-    p.in_bytes = (size_t)io.chunk * plane; p.out_step = plane;
-    p.upload = [&](const ProduceIn &c) -> int {
-        const char *src = c.src ? c.src : (const char *)io.host_in + (size_t)c.c0 * plane;
-        if (in_w == plane) HIPCHK(hipMemcpyAsync(c.dev, src, (size_t)c.nt * plane, hipMemcpyHostToDevice, h->copy_stream));
-        else if (in_w) HIPCHK(hipMemcpy2DAsync(c.dev + in_off, plane, src + in_off, plane, in_w, (size_t)c.nt, hipMemcpyHostToDevice, h->copy_stream));      // row s of the copy: rows [r0, r1) of step c0 + s
-        return CTK_OK;
-    };
-    p.launch = [&](const ProduceIn &c, ProduceOut &o) -> int {
-        o.t0 = c.c0; o.nt = c.nt;
-        o.dev = keep_resident ? (char *)h->an_out.p + (size_t)c.c0 * plane : (char *)h->io_out.p + (size_t)c.b * (size_t)io.chunk * plane;
-        return launch_reversal<VT>(h, (const VT *)c.dev, ny, nx, c.nt, tab, a.eq2 != nullptr, a.mask != 0, (VT *)o.dev);
-    };
-    if (out_w != plane)
-        p.download = [&](const ProduceOut &o, char *dst) -> int {
-            if (out_w) HIPCHK(hipMemcpy2D(dst + out_off, plane, o.dev + out_off, plane, out_w, (size_t)o.nt, hipMemcpyDeviceToHost));
-            return CTK_OK;
-        };
-    const int rc = stream_produce(h, io, steps, name, p);
-    if (zero.t.joinable()) zero.t.join();
-    CTKCHK(stream_produce_end(h, io, rc, t_call));
-    if (keep_resident) { h->an_T = steps; h->an_ny = ny; h->an_nx = nx; h->an_f64 = sizeof(VT) == 8; }
-    return CTK_OK;
+    return row_band_produce(
+        h, io, steps, ny, nx, {rr.r0, rr.r1, rr.a0, rr.a1}, keep_resident, name, [&]() -> int { return reversal_table(h, ny, a, tab); },
+        [&](const ProduceIn &c, char *out) -> int { return launch_reversal<VT>(h, (const VT *)c.dev, ny, nx, c.nt, tab, a.eq2 != nullptr, a.mask != 0, (VT *)out); });
 }
 
 extern "C" int ctk_reversal_f32(ctk_handle *h, const float *x, int64_t steps, int ny, int nx, const int32_t *eq, const int32_t *po, const int32_t *eq2, const double *dE,
@@ -262,11 +193,9 @@ extern "C" int ctk_reversal_stream_cb(ctk_handle *h, int elem_bytes, int64_t ste
                                       const int32_t *po, const int32_t *eq2, const double *dE, const double *tS, const double *tN, const double *tS2, int mask,
                                       ctk_write_values_fn writer, void *writer_user, int64_t chunk_steps, int keep_resident)
 {
-    if (elem_bytes != 4 && elem_bytes != 8) return ctk_set_error(CTK_E_INVALID, "ctk_reversal_stream_cb: elem_bytes must be 4 (float32) or 8 (float64)");
-    if (h && !reader) return ctk_set_error(CTK_E_INVALID, "ctk_reversal_stream_cb: null reader");
     const ReversalArgs a = {eq, po, eq2, dE, tS, tN, tS2, mask};
     StreamIO io;
-    io.read = reader; io.read_user = reader_user; io.write_v = writer; io.write_user = writer_user;
+    CTKCHK(stream_cb_io("ctk_reversal_stream_cb", h, elem_bytes, reader, reader_user, writer, writer_user, io));
     if (elem_bytes == 8) return reversal_stream_impl<double>(h, io, steps, ny, nx, a, chunk_steps, keep_resident, "ctk_reversal_stream_cb");
     return reversal_stream_impl<float>(h, io, steps, ny, nx, a, chunk_steps, keep_resident, "ctk_reversal_stream_cb");
 }
@@ -284,9 +213,7 @@ extern "C" int ctk_debug_reversal_plan(int elem_bytes, int64_t ny, int64_t nx, i
 // test hook: out2 = { the form of the last k_reversal launch on this handle (1 vector, 0 scalar, -1 none yet), its workgroups }
 extern "C" int ctk_debug_reversal_form(ctk_handle *h, int64_t *out2)
 {
-    if (!h || !out2) return ctk_set_error(CTK_E_INVALID, "null argument");
-    out2[0] = h->gr_form; out2[1] = h->gr_grid;
-    return CTK_OK;
+    return knobs_form(h, &ctk_handle::gr_knobs, out2);
 }
 
 // test hook / experiments (tools/reversal_probe.py) for the following k_reversal launches on this handle: the xcd_chunk mode (0 launch
@@ -294,10 +221,7 @@ extern "C" int ctk_debug_reversal_form(ctk_handle *h, int64_t *out2)
 // that a small case walks the stride loop (0: CTK_LEVEL_GRID_MAX)
 extern "C" int ctk_debug_set_reversal(ctk_handle *h, int xcd_mode, int64_t grid_max)
 {
-    if (!h || xcd_mode < -1 || grid_max < 0) return ctk_set_error(CTK_E_INVALID, "ctk_debug_set_reversal: bad argument");
-    h->gr_xcd_dbg = xcd_mode;
-    h->gr_grid_dbg = grid_max;
-    return CTK_OK;
+    return knobs_set("ctk_debug_set_reversal", h, &ctk_handle::gr_knobs, xcd_mode, grid_max);
 }
 
 // measurement (tools/reversal_probe.py): k_reversal alone between HIP events on slabs in device memory -- one launch that is not
@@ -312,18 +236,10 @@ extern "C" int ctk_debug_time_reversal(ctk_handle *h, const void *x_dev, int is_
     if (eq) CTKCHK(reversal_check("ctk_debug_time_reversal", h, steps, ny, nx, a));
     else if ((((uintptr_t)x_dev | (uintptr_t)out_dev) & 15) != 0) return ctk_set_error(CTK_E_INVALID, "ctk_debug_time_reversal: the copy needs 16-byte aligned buffers");
     HIPCHK(hipSetDevice(h->device));
-    ReversalTab tab = {};
-    if (eq) CTKCHK(reversal_table(h, ny, a, tab));
-    const int64_t n16 = steps * (int64_t)ny * nx * (is_f64 ? 8 : 4) / 16;
-    const int64_t cblocks = (n16 + 255) / 256;
-    const unsigned cgrid = (unsigned)std::min<int64_t>(std::max<int64_t>(cblocks, 1), CTK_LEVEL_GRID_MAX);
-    const int cxcd = h->gr_xcd_dbg >= 0 ? h->gr_xcd_dbg : (cgrid >= CTK_LEVEL_XCD_MIN ? 1 : 0);
+    if (!eq) return time_copy16(h, "ctk_debug_time_reversal", h->gr_knobs, x_dev, out_dev, steps * (int64_t)ny * nx * (is_f64 ? 8 : 4), reps, ms2);
+    ReversalTab tab;
+    CTKCHK(reversal_table(h, ny, a, tab));
     return time_launches(h, "ctk_debug_time_reversal", reps, ms2, [&]() -> int {
-        if (!eq) {
-            k_reversal_copy<<<cgrid, 256, 0, h->stream>>>((const i32x4 *)x_dev, (i32x4 *)out_dev, n16, cxcd);
-            HIPCHK(hipGetLastError());
-            return CTK_OK;
-        }
         return is_f64 ? launch_reversal<double>(h, (const double *)x_dev, ny, nx, steps, tab, eq2 != nullptr, mask != 0, (double *)out_dev)
                       : launch_reversal<float>(h, (const float *)x_dev, ny, nx, steps, tab, eq2 != nullptr, mask != 0, (float *)out_dev);
     });

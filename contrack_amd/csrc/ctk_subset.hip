@@ -281,9 +281,9 @@ static void subset_launch_form(const CtkSubsetPlan &pl, hipStream_t st, bool hit
 static int launch_subset(ctk_handle *h, const int32_t *flag, int64_t npix, int64_t steps, const SubsetCall &c, int64_t step0, int32_t *out)
 {
     const bool aligned = (((uintptr_t)flag | (uintptr_t)out) & 15) == 0;
-    const CtkSubsetPlan pl = ctk_subset_plan(c.sh.by_row, c.sh.max_id, c.sh.longest, c.want_hits, npix, steps, aligned, h->sb_grid_dbg > 0 ? h->sb_grid_dbg : CTK_LEVEL_GRID_MAX);
-    h->sb_form = pl.form; h->sb_vec = pl.vec; h->sb_grid = pl.grid;
-    const int xcd = h->sb_xcd_dbg >= 0 ? h->sb_xcd_dbg : pl.xcd;
+    const CtkSubsetPlan pl = ctk_subset_plan(c.sh.by_row, c.sh.max_id, c.sh.longest, c.want_hits, npix, steps, aligned, h->sb_knobs.cap());
+    h->sb_knobs.launched(pl.form, pl.grid); h->sb_vec = pl.vec;
+    const int xcd = h->sb_knobs.xcd(pl.xcd);
     SubsetDev d = c.d;
     if (c.sh.by_row) d.off = c.off_dev + step0;
 #define CTK_SUBSET_FORM(F) do { if (pl.vec) subset_launch_form<F, true>(pl, h->stream, c.want_hits, flag, npix, d, out, xcd); \
@@ -348,11 +348,7 @@ static int subset_stream_impl(ctk_handle *h, StreamIO &io, int64_t T, int ny, in
     CTKCHK(subset_table(h, a, sh, hits != nullptr, n_selected != nullptr, c));
     Producer p;
     p.in_bytes = (size_t)io.chunk * plane; p.out_step = plane;
-    p.upload = [&](const ProduceIn &in) -> int {
-        const char *src = in.src ? in.src : (const char *)io.host_in + (size_t)in.c0 * plane;
-        HIPCHK(hipMemcpyAsync(in.dev, src, (size_t)in.nt * plane, hipMemcpyHostToDevice, h->copy_stream));
-        return CTK_OK;
-    };
+    p.upload = [&](const ProduceIn &in) -> int { return upload_steps(h, io, in, plane); };
     p.launch = [&](const ProduceIn &in, ProduceOut &o) -> int {
         if (sink) { o.t0 = in.c0; o.nt = in.nt; o.dev = (char *)h->io_out.p + (size_t)in.b * (size_t)io.chunk * plane; }
         return launch_subset(h, (const int32_t *)in.dev, npix, in.nt, c, in.c0, (int32_t *)o.dev);
@@ -399,17 +395,14 @@ extern "C" int ctk_debug_subset_plan(int by_row, int64_t max_id, int64_t longest
 extern "C" int ctk_debug_subset_form(ctk_handle *h, int64_t *out3)
 {
     if (!h || !out3) return ctk_set_error(CTK_E_INVALID, "null argument");
-    out3[0] = h->sb_form; out3[1] = h->sb_vec; out3[2] = h->sb_grid;
+    out3[0] = h->sb_knobs.form; out3[1] = h->sb_vec; out3[2] = h->sb_knobs.grid;
     return CTK_OK;
 }
 
 // test hook / experiments (tools/subset_probe.py) for the following k_subset launches on this handle: as ctk_debug_set_reversal
 extern "C" int ctk_debug_set_subset(ctk_handle *h, int xcd_mode, int64_t grid_max)
 {
-    if (!h || xcd_mode < -1 || grid_max < 0) return ctk_set_error(CTK_E_INVALID, "ctk_debug_set_subset: bad argument");
-    h->sb_xcd_dbg = xcd_mode;
-    h->sb_grid_dbg = grid_max;
-    return CTK_OK;
+    return knobs_set("ctk_debug_set_subset", h, &ctk_handle::sb_knobs, xcd_mode, grid_max);
 }
 
 // measurement (tools/subset_probe.py): k_subset alone between HIP events on slabs in device memory -- one launch that is not counted,
@@ -428,15 +421,7 @@ extern "C" int ctk_debug_time_subset(ctk_handle *h, const int32_t *flag_dev, int
     HIPCHK(hipSetDevice(h->device));
     SubsetCall c = {};
     if (off) CTKCHK(subset_table(h, a, sh, want_hits != 0, want_n_selected != 0, c));
-    const int64_t npix = (int64_t)ny * nx, n16 = T * npix / 4;
-    const unsigned cgrid = (unsigned)std::min<int64_t>(std::max<int64_t>((n16 + 255) / 256, 1), CTK_LEVEL_GRID_MAX);
-    const int cxcd = h->sb_xcd_dbg >= 0 ? h->sb_xcd_dbg : (cgrid >= CTK_LEVEL_XCD_MIN ? 1 : 0);
-    return time_launches(h, who, reps, ms2, [&]() -> int {
-        if (!off) {
-            k_reversal_copy<<<cgrid, 256, 0, h->stream>>>((const i32x4 *)flag_dev, (i32x4 *)out_dev, n16, cxcd);
-            HIPCHK(hipGetLastError());
-            return CTK_OK;
-        }
-        return launch_subset(h, flag_dev, npix, T, c, 0, out_dev);
-    });
+    const int64_t npix = (int64_t)ny * nx;
+    if (!off) return time_copy16(h, who, h->sb_knobs, flag_dev, out_dev, T * npix * 4, reps, ms2);
+    return time_launches(h, who, reps, ms2, [&]() -> int { return launch_subset(h, flag_dev, npix, T, c, 0, out_dev); });
 }
