@@ -198,6 +198,43 @@ class _SubsetCall:
         return _ptr(self.hits), C.byref(self.n)
 
 
+BLOCKSTAT_FORMS = ("row_lds", "row_glb")
+BLOCK_WANTS = {"shape": ABI.constants["CTK_BLOCK_SHAPE"], "peaks": ABI.constants["CTK_BLOCK_PEAKS"]}
+BLOCK_ROW = _dtype("ctk_block_row")
+
+
+def _block_want(want):
+    """want of a blockstat entry -- 'shape', 'peaks', a sequence of them, or the bit set itself -- as the bit set"""
+    if isinstance(want, (int, np.integer)):
+        return int(want)
+    names = (want,) if isinstance(want, str) else tuple(want)
+    unknown = [w for w in names if w not in BLOCK_WANTS]
+    if unknown or not names:
+        raise ValueError("want={!r}: 'shape', 'peaks' or both".format(want))
+    return sum(BLOCK_WANTS[w] for w in set(names))
+
+
+def blockstat_plan(want, longest, ny, nx, steps=1, elem_bytes=4, aligned=True, grid_max=0):
+    """ctk_debug_blockstat_plan: what ctk_blockstat_plan (csrc/ctk_forms.h) decides for a blockstat launch whose table's longest slice
+    has `longest` ids, as a dict (form 0 / 1 = BLOCKSTAT_FORMS, vec 1 vector / 0 scalar, vpt pixels per thread, lds bytes, bps parts
+    per step, blocks parts of work, grid workgroups launched, xcd, passes launches per chunk, words of an entry's bit set, entry
+    bytes of LDS per entry, and the rule's capacities: lds_budget, lds_entries at this nx, part_lanes); no handle, no GPU"""
+    v = np.zeros(14, dtype=np.int64)
+    check(lib().ctk_debug_blockstat_plan(_block_want(want), int(elem_bytes), int(longest), int(ny), int(nx), int(steps), int(bool(aligned)), int(grid_max),
+                                         v.ctypes.data))
+    return dict(zip(("form", "vec", "vpt", "lds", "bps", "blocks", "grid", "xcd", "passes", "words", "entry", "lds_budget", "lds_entries", "part_lanes"),
+                    (int(a) for a in v)))
+
+
+class _BlockstatCall:
+    """the arguments every blockstat entry shares, and the rows it fills"""
+
+    def __init__(self, table, want):
+        self.off, self.ids = _subset_table(table)
+        self.rows = np.zeros(len(self.ids), dtype=BLOCK_ROW)
+        self.args = (self.off.ctypes.data, len(self.off), self.ids.ctypes.data, len(self.ids), _block_want(want), self.rows.ctypes.data)
+
+
 def lwa_plan(elem_bytes, rows, nx, ndom=1, steps=1, aligned=True):
     """ctk_debug_lwa_plan: what ctk_lwa_plan (csrc/ctk_forms.h) decides for a local-wave-activity launch whose longest domain has
     `rows` rows, as a dict (ok 1 / 0 the domain does not fit in LDS, vec 1 vector / 0 scalar form, strip columns, nstrips, lds and
@@ -1666,6 +1703,67 @@ class Tracker:
     def debug_subset_launch(self):
         """(form, vec, workgroups) of the last subset launch: form 0 .. 4 = SUBSET_FORMS (-1: none yet), vec 1 vector / 0 scalar"""
         return self._debug_launch("subset", 3)
+
+    # ---- per-block peak and extent (ctk_blockstat_*) ---------------------------------------------------------------------
+    def blockstat(self, flag, table, x=None, want=('shape', 'peaks'), chunk_steps=0, resident_f64=False):
+        """flag (T, ny, nx) int32 host slab, table = (off, ids) a ROW table (contrack.subset_table(ids, steps, T)), x a float32 /
+        float64 field of the flag's shape.  Returns a structured array (BLOCK_ROW = ctk_block_row of include/contrack_hip.h, which
+        states every field), one row per entry of ids.  x None with 'peaks': the anomaly slab anomalies(keep_resident=True) left on
+        the device (resident_f64: its type), only the flags travel.  chunk_steps: steps per chunk on their way through the device
+        (0: about 256 MB); same bytes."""
+        flag = _flag_i32(flag, "blockstat_cb, or contrack.blockstat_numpy")
+        T, ny, nx = flag.shape
+        if x is None:
+            f64 = bool(resident_f64)
+        else:
+            x = np.ascontiguousarray(x, dtype=_field_dtype(np.asarray(x).dtype))
+            if x.shape != flag.shape:
+                raise ValueError("the field has shape %s, the flag %s" % (x.shape, flag.shape))
+            f64 = x.dtype == np.float64
+        c = _BlockstatCall(table, want)
+        fn = lib().ctk_blockstat_f64 if f64 else lib().ctk_blockstat_f32
+        check(fn(self._h, flag.ctypes.data, _ptr(x), T, ny, nx, *c.args, int(chunk_steps or 0)))
+        return c.rows
+
+    def blockstat_cb(self, flag_reader, field_reader, shape, dtype, table, want=('shape', 'peaks'), chunk_steps=0):
+        """the same with both slabs read chunk by chunk: flag_reader(t0, nt, out) fills an int32 (nt, ny, nx) view of pinned memory
+        with the steps [t0, t0 + nt), field_reader one of `dtype` (float32 / float64); the flag reader is called first.  Readers may
+        be arrays indexed by time.  field_reader None: the resident anomaly slab of `dtype`, or (without 'peaks') no field."""
+        if shape is None:
+            raise ValueError("a reader needs shape=(T, ny, nx)")
+        T, ny, nx = (int(v) for v in shape)
+        dt = np.dtype(np.float32 if dtype is None else dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("the field must be float32 or float64")
+        c = _BlockstatCall(table, want)
+        tr = _Trampolines()
+        fcb, xcb = tr.reader(flag_reader, C.c_int32, (ny, nx)), tr.reader(field_reader, _float_ctype(dt), (ny, nx))
+        tr.finish(lib().ctk_blockstat_cb(self._h, dt.itemsize, T, ny, nx, fcb, None, xcb, None, *c.args, int(chunk_steps or 0)))
+        return c.rows
+
+    def blockstat_dev(self, flag_dev, x_dev, T, ny, nx, table, want=('shape', 'peaks'), f64=False):
+        """ctk_blockstat_*_dev on an int32 flag and a float32 (f64: float64) field in device memory; x_dev None: the resident
+        anomaly slab, or (without 'peaks') no field.  Returns the rows."""
+        c = _BlockstatCall(table, want)
+        fn = lib().ctk_blockstat_f64_dev if f64 else lib().ctk_blockstat_f32_dev
+        check(fn(self._h, flag_dev, x_dev, int(T), int(ny), int(nx), *c.args))
+        return c.rows
+
+    def time_blockstat(self, flag_dev, x_dev, T, ny, nx, table, want=('shape', 'peaks'), f64=False, reps=5):
+        """measurement (tools/blockstat_probe.py): (best, mean) ms of the k_blockstat launches of the whole slab alone on slabs in
+        device memory, HIP events; table None: the plain stream of 16-byte loads over the same buffers, the yardstick"""
+        ms = (C.c_double * 2)()
+        if table is None:
+            args = (None, 0, None, 0, 0)
+        else:
+            c = _BlockstatCall(table, want)
+            args = c.args[:5]
+        check(lib().ctk_debug_time_blockstat(self._h, flag_dev, x_dev, int(bool(f64)), int(T), int(ny), int(nx), *args, int(reps), ms))
+        return float(ms[0]), float(ms[1])
+
+    def debug_blockstat_launch(self):
+        """(form, vec, workgroups) of the last blockstat launch: form 0 / 1 = BLOCKSTAT_FORMS (-1: none yet), vec 1 vector / 0 scalar"""
+        return self._debug_launch("blockstat", 3)
 
     # ---- local wave activity (ctk_lwa_*) ---------------------------------------------------------------------------
     def lwa(self, x, rows, part='total', chunk_steps=0, keep_resident=False, want_out=True, want_ref=False):

@@ -338,6 +338,45 @@ def subset_numpy(flag, table, invert=False, kind='id', chunk_steps=None, device=
     return (out, n, hits) if return_hits else (out, n)
 
 
+def blockstat_numpy(flag, table, x=None, want=('shape', 'peaks'), chunk_steps=None, device=None, shape=None, dtype=None):
+    """per (step, track) row of `table` -- a ROW table, subset_table(ids, steps, T) -- the block's pixel count, its lowest and highest
+    grid row, its zonal extent taken around the date line (west, width), and the largest and smallest value of the field `x` inside
+    it with the pixel index row * nx + col where each sits first: a structured array of _native.BLOCK_ROW (ctk_block_row of
+    include/contrack_hip.h, which states every field), one row per entry of the table's ids.  flag (time, lat, lon) integer, x of
+    the same shape (float64 stays, everything else is taken as float32); want: 'shape', 'peaks' or both ('shape' alone needs no
+    field).  Runs on the GPU (ctk_blockstat_*); everything is selection, so the rows are the same bytes whatever chunk_steps: time
+    steps per chunk on both slabs' way through the device (None or 0: about 256 MB).  x None with 'peaks': the anomaly slab
+    calc_anom left on the device (`dtype` its type), only the flags travel.  With shape=(T, ny, nx) and dtype, flag and x may be
+    readers reader(t0, nt, out) (ctk_blockstat_cb); flags wider than int32 are narrowed chunk by chunk (an id beyond int32 raises
+    ValueError)."""
+    steps = 0 if chunk_steps is None else int(chunk_steps)
+    if steps < 0:
+        raise ValueError("chunk_steps={} (at least 0)".format(steps))
+    bits = _native._block_want(want)
+    peaks = bool(bits & _native.BLOCK_WANTS['peaks'])
+    if not peaks:
+        x = None
+    if callable(flag) or callable(x):
+        if shape is None or (peaks and dtype is None and (x is None or callable(x))):
+            raise ValueError("a reader needs shape=(T, ny, nx) and the field's dtype")
+    fread, fshape, is_array = _flag_source(flag, shape)
+    shape = fshape if shape is None else shape
+    if x is not None and not callable(x):
+        x = x if isinstance(x, np.memmap) else np.asarray(x)
+        if tuple(x.shape) != tuple(int(v) for v in shape):
+            raise ValueError("the field has shape {}, the flag {}".format(x.shape, tuple(shape)))
+        dtype = _native._field_dtype(x.dtype)
+    dtype = np.dtype(dtype if dtype is not None else np.float32)
+    trk = _tracker(device)
+    if is_array and not callable(x):
+        return trk.blockstat(fread, table, x, bits, steps, resident_f64=dtype == np.float64)
+    xread = x
+    if x is not None and not callable(x):
+        def xread(t0, nt, out, slab=x):
+            out[...] = slab[t0:t0 + nt]
+    return trk.blockstat_cb(fread, xread, shape, dtype, table, bits, steps)
+
+
 def track_table(frame):
     """one row per track of a life-cycle frame (run_lifecycle's DataFrame or a row selection of it) -- per (Flag, member) where the
     frame has a seventh, member column -- with what one selects tracks on: Onset and Decay (the first and last Date), Duration (the
@@ -2612,6 +2651,27 @@ class contrack(object):
             columns += ['Step', 'Row', 'Col']
         return pd.DataFrame(cols, columns=columns)
 
+    def _frame_steps(self, frame, da, dims, member):
+        """the flat step m * T + t of every row of a life-cycle frame on the flag variable `da` (select_blocks, calc_block_stats): its
+        'Step' and, for a 4-D flag, the position of its member column's value on that dimension"""
+        T = da.shape[dims.index(self._time_name)]
+        need = ['Flag', 'Step'] + ([member] if member is not None else [])
+        missing = [c for c in need if c not in frame]
+        if missing:
+            raise ValueError("the frame lacks the columns {}: pass rows of run_lifecycle(..., indices=True)".format(missing))
+        step = np.asarray(frame['Step']).astype(np.int64)
+        if step.size and (step.min() < 0 or step.max() >= T):
+            raise ValueError("the frame's Step must lie in [0, {})".format(T))
+        if member is not None:
+            values = self._dim_values(member, da.shape[dims.index(member)])
+            order = np.argsort(values, kind='stable')
+            col = np.asarray(frame[member])
+            pos = np.minimum(np.searchsorted(values[order], col), len(values) - 1)
+            if (values[order][pos] != col).any():
+                raise ValueError("the frame's column {!r} holds values that are not on that dimension".format(member))
+            step = order[pos].astype(np.int64) * T + step
+        return step
+
     # ---- selection: the flag of chosen tracks or (step, track) rows, what the consumers of `flag` then take ----------------------
     def select_blocks(self, flag='flag', ids=None, frame=None, invert=False, out='id', name='flag_sel', chunk_steps=None, check=True):
         """adds the variable `name`: the flag variable restricted to the blocks a study picked, computed on the GPU (subset_numpy).
@@ -2640,22 +2700,7 @@ class contrack(object):
             table = subset_table(ids)
             asked = '{} ids'.format(len(table[1]))
         else:
-            need = ['Flag', 'Step'] + ([member] if member is not None else [])
-            missing = [c for c in need if c not in frame]
-            if missing:
-                raise ValueError("the frame lacks the columns {}: pass rows of run_lifecycle(..., indices=True)".format(missing))
-            step = np.asarray(frame['Step']).astype(np.int64)
-            if step.size and (step.min() < 0 or step.max() >= T):
-                raise ValueError("the frame's Step must lie in [0, {})".format(T))
-            if member is not None:
-                values = self._dim_values(member, da.shape[dims.index(member)])
-                order = np.argsort(values, kind='stable')
-                col = np.asarray(frame[member])
-                pos = np.minimum(np.searchsorted(values[order], col), len(values) - 1)
-                if (values[order][pos] != col).any():
-                    raise ValueError("the frame's column {!r} holds values that are not on that dimension".format(member))
-                step = order[pos].astype(np.int64) * T + step
-            table = subset_table(np.asarray(frame['Flag']), step, view.steps)
+            table = subset_table(np.asarray(frame['Flag']), self._frame_steps(frame, da, dims, member), view.steps)
             asked = '{} rows'.format(len(table[1]))
         source = view.slab() if chunk_steps is None else view.reader(integer=True)
         res, n, hits = subset_numpy(source, table, invert=invert, kind=out, chunk_steps=chunk_steps, shape=view.shape, return_hits=True)
@@ -2668,6 +2713,99 @@ class contrack(object):
                  'history': 'Selected from {} with input attributes: {}, invert = {}, out = {}.'.format(flag, asked, bool(invert), out)}
         self.ds[name] = (dims, view.restore(res, dims), attrs)
         return n
+
+    # ---- per-block peak and extent: what the literature selects rows of the life-cycle frame on ---------------------------------
+    def calc_block_stats(self, flag='flag', variable=None, frame=None, chunk_steps=None, indices=False, check=True):
+        """one row per row of `frame`, in the frame's order, with the two properties of a block at a time step that run_lifecycle
+        does not give: its extent and, with `variable`, its true peak and where it sits (blockstat_numpy, on the GPU).
+        frame: rows of run_lifecycle(indices=True) or any selection of them -- 'Flag', 'Step' and, for a 4-D flag, the member
+        column --; None: run_lifecycle(flag, variable, indices=True) is called first (and needs `variable`).  Returns a pandas
+        DataFrame: the frame's key columns ('Flag', 'Date' where the frame has it, the member column, 'Step'), then
+          N                          the pixels of the block at that step
+          South, North, LatExtent    the coordinate values of its lowest and highest grid row (r0, r1: South is the row with the
+                                     lower index, whichever way the latitudes run) and (r1 - r0 + 1) * dlat
+          West, East, LonExtent      lon[west], lon[(west + width - 1) % nx] and width * dlon, taken AROUND the date line: the
+                                     complement of the longest circular run of columns the block does not touch
+        and with `variable`
+          Max, MaxLatitude, MaxLongitude, Min, MinLatitude, MinLongitude
+                                     the largest and smallest value of the variable inside the block (NaN values apart) and the
+                                     actual coordinates, not truncated, of the first pixel in row-major order that holds each.
+        The usual "block intensity" is Max (Min for gorl='<'); run_lifecycle's Intensity is the area mean and lies between them.
+        indices=True adds the integer columns 'Row0', 'Row1', 'ColWest', 'Width' and, with `variable`, 'NValid', 'MaxRow', 'MaxCol',
+        'MinRow', 'MinCol'.  When `variable` is the anomaly calc_anom left in HBM nothing but the flags travels.  chunk_steps: both
+        variables are read slice by slice (`isel`) through chunk-sized device buffers; same values.  Dims in any order, a member
+        dimension included.  check=True: a row that matches no pixel raises ValueError (the frame comes from another run)."""
+        import pandas as pd
+        self._ensure_set_up()
+        fda = self.ds[flag]
+        dims, member = self._consumer_dims(flag)
+        if np.dtype(fda.dtype).kind not in "iub":
+            raise ValueError("flag variable {!r} is not an integer field".format(flag))
+        if frame is None:
+            if variable is None:
+                raise ValueError("calc_block_stats without a frame calls run_lifecycle, which needs `variable`")
+            frame = self.run_lifecycle(flag, variable, chunk_steps=chunk_steps, indices=True)
+        fview = self._steps(fda, (member, self._time_name))
+        step = self._frame_steps(frame, fda, dims, member)
+        ids = _positive_int32(np.asarray(frame['Flag']), "the frame's Flag")
+        table = subset_table(ids, step, fview.steps)
+        want = ('shape',) if variable is None else ('shape', 'peaks')
+        if variable is None:
+            field, vtype = None, None
+        else:
+            vda = self.ds[variable]
+            vdims = tuple(vda.dims)
+            if sorted(vdims) != sorted(dims) or any(vda.shape[vdims.index(d)] != fda.shape[dims.index(d)] for d in dims):
+                raise ValueError("the variable {!r} has dims {}, the flag variable {!r} has {}: they must be the same".format(variable, vdims, flag, dims))
+            vtype = _native._field_dtype(vda.dtype)
+            vview = self._steps(vda, (member, self._time_name))
+        if chunk_steps is None:
+            if variable is not None:
+                field = vview.slab().astype(vtype, copy=False)
+                if self._resident_field(variable, field.shape, vtype == np.float64):
+                    field = None                                                    # (only the flags cross PCIe)
+            rows = blockstat_numpy(fview.slab(), table, field, want=want, dtype=vtype)
+        else:
+            rows = blockstat_numpy(fview.reader(integer=True), table, None if variable is None else vview.reader(), want=want, chunk_steps=chunk_steps,
+                                   shape=fview.shape, dtype=vtype)
+        # the entry of every frame row: the table is the sorted set of (flat step, id) pairs
+        pairs = np.repeat(np.arange(fview.steps, dtype=np.int64), np.diff(table[0])) * (1 << 31) + table[1]
+        rows = rows[np.searchsorted(pairs, step * (1 << 31) + ids)]
+        if check and (rows['n'] == 0).any():
+            lost = np.flatnonzero(rows['n'] == 0)
+            some = ', '.join('(step {}, id {})'.format(int(step[i]), int(ids[i])) for i in lost[:5])
+            raise ValueError("{} of the {} rows requested match no pixel of {!r} (the first: {}): do they come from another run?".format(
+                len(lost), len(rows), flag, some))
+        lat = np.asarray(self.ds[self._latitude_name].data)
+        lon = np.asarray(self.ds[self._longitude_name].data)
+        nx = len(lon)
+
+        def at(coord, idx, live):
+            """coord[idx] as float64 where `live`, NaN elsewhere (an entry that matched nothing, or without a valid value)"""
+            return np.where(live, np.asarray(coord, dtype=np.float64)[np.where(live, idx, 0)], np.nan)
+        hit = rows['n'] > 0
+        dlat, dlon = (abs(float(np.atleast_1d(d)[0])) for d in (self._dlat, self._dlon))
+        r0, r1, west, width = (rows[k].astype(np.int64) for k in ('r0', 'r1', 'west', 'width'))
+        cols = {k: np.asarray(frame[k]) for k in ['Flag', 'Date', member, 'Step'] if k is not None and k in frame}
+        cols['N'] = rows['n'].astype(np.int64)
+        cols['South'], cols['North'] = at(lat, r0, hit), at(lat, r1, hit)
+        cols['LatExtent'] = np.where(hit, r1 - r0 + 1, 0) * dlat
+        cols['West'], cols['East'] = at(lon, west, hit), at(lon, (west + width - 1) % nx, hit)
+        cols['LonExtent'] = width * dlon
+        if variable is not None:
+            ok = rows['nv'] > 0
+            for name in ('max', 'min'):
+                p = rows[name + '_p']
+                cols[name.capitalize()] = rows[name].copy()
+                cols[name.capitalize() + 'Latitude'], cols[name.capitalize() + 'Longitude'] = at(lat, p // nx, ok), at(lon, p % nx, ok)
+        if indices:
+            cols['Row0'], cols['Row1'], cols['ColWest'], cols['Width'] = r0, r1, west, width
+            if variable is not None:
+                cols['NValid'] = rows['nv'].astype(np.int64)
+                for name in ('max', 'min'):
+                    p = rows[name + '_p']
+                    cols[name.capitalize() + 'Row'], cols[name.capitalize() + 'Col'] = np.where(p >= 0, p // nx, -1), np.where(p >= 0, p % nx, -1)
+        return pd.DataFrame(cols, columns=list(cols))
 
     def calc_centred_composite(self, variable, frame, half_width=(20., 40.), by=None, nbins=None, max_age=None, stat='mean', skipna=False, wrap=True,
                                chunk_steps=None, return_count=False):

@@ -314,6 +314,12 @@ struct ctk_handle {
     DevBuf sb_tab, sb_hits;
     LaunchKnobs sb_knobs;
     int sb_vec = 0;
+    // per-block peak and extent (ctk_blockstat.hip): the accumulators of the running call (two 64-bit and six 32-bit words per entry
+    // of the table, then the column bit sets) and its rows; the k_blockstat launches (form: CTK_BLOCKSTAT_ROW_LDS / _ROW_GLB of
+    // ctk_forms.h) and whether the last one was vector or scalar.  The table itself is sb_tab: a call of either family uploads its own.
+    DevBuf bs_acc, bs_rows;
+    LaunchKnobs bs_knobs;
+    int bs_vec = 0;
     DevBuf io_in, io_out;                          // device copies of host-array calls (ctk_track_f32 / _f64)
     uint64_t io_gen = 0;                           // bumped by claim_io and ctk_release_io: WHOSE data io_in / io_out hold
     // streaming entries (ctk_track_stream_*): the slab passes through two chunk-sized device buffers per direction
@@ -4142,6 +4148,7 @@ extern "C" int ctk_lifecycle_rows(ctk_handle *h, ctk_life_row *rows, int64_t cap
 #include "ctk_lwa.hip"
 #include "ctk_subset.hip"
 #include "ctk_composite.hip"
+#include "ctk_blockstat.hip"
 #include "ctk_centred.hip"
 #include "ctk_band.hip"
 

@@ -795,6 +795,57 @@ inline CtkSubsetPlan ctk_subset_plan(bool by_row, int64_t max_id, int64_t longes
 }
 
 // ------------------------------------------------------------------------------------------------
+// per-block peak and extent (ctk_blockstat.hip): k_blockstat in k_subset's row geometry -- a workgroup takes a PART of one step,
+// CTK_SUBSET_TILES tiles of CTK_SUBSET_THREADS lanes, a lane 16 bytes of flags (vector form: every plane starts on a 16-byte boundary)
+// or one pixel (scalar form) -- and reduces the pixels of the step's wanted ids into one record per entry:
+//     CTK_BLOCKSTAT_ROW_LDS    the step's slice, its records and its column bit sets in LDS; LDS atomics per pixel, one merge into the
+//                              records in HBM per touched entry and part
+//     CTK_BLOCKSTAT_ROW_GLB    the slice searched in global memory, the atomics straight on the records in HBM
+// An entry takes CTK_BLOCKSTAT_REC bytes of LDS (its id, two 64-bit and four 32-bit accumulators) and, when the shape is wanted, a bit
+// per column in whole words.  The LDS form runs while the longest slice fits CTK_BLOCKSTAT_LDS_BYTES: 32 KB, so that five workgroups
+// fit a CU's 160 KB -- 390 entries of a 360-column grid, 151 of a 1440-column one, where a step of a tracked slab has a few dozen.
+// float64 peaks take a second pass (key and position do not fit one 64-bit word): passes = 2.
+// ------------------------------------------------------------------------------------------------
+#define CTK_BLOCKSTAT_ROW_LDS 0
+#define CTK_BLOCKSTAT_ROW_GLB 1
+#define CTK_BLOCKSTAT_REC 36                   // bytes of LDS per entry without its bit set
+#define CTK_BLOCKSTAT_LDS_BYTES (32ll << 10)
+struct CtkBlockstatPlan {
+    int form;                     // CTK_BLOCKSTAT_ROW_LDS or CTK_BLOCKSTAT_ROW_GLB
+    int vec;                      // 1: a 16-byte load of flags per lane, 0: the scalar form
+    int vpt;                      // pixels per thread: 4 or 1
+    int passes;                   // launches of k_blockstat per chunk: 2 with float64 peaks, else 1
+    int64_t words;                // 32-bit words of an entry's column bit set: ceil(nx / 32), 0 without the shape
+    int64_t entry;                // bytes of LDS per entry: CTK_BLOCKSTAT_REC + 4 * words
+    int64_t lds;                  // bytes of dynamic LDS of a workgroup: longest * entry, 0 in the global form
+    int64_t bps;                  // parts per step
+    int64_t blocks;               // bps * steps: (step, part) pairs, walked by ...
+    unsigned grid;                // ... this many workgroups
+    int xcd;                      // xcd_chunk mode of the launch, as CtkSubsetPlan's
+};
+// shape, peaks: what the call wants; elem_bytes: of the field (4 or 8; without peaks it does not matter); longest: the longest slice
+// of the table; aligned: the flag's base pointer is a multiple of 16 (the field is read one value at a time, under the id test);
+// grid_max: CTK_LEVEL_GRID_MAX, or a test's lower cap
+inline CtkBlockstatPlan ctk_blockstat_plan(bool shape, bool peaks, int elem_bytes, int64_t longest, int64_t nx, int64_t npix, int64_t steps, bool aligned,
+                                           int64_t grid_max = CTK_LEVEL_GRID_MAX)
+{
+    CtkBlockstatPlan p = {};
+    p.words = shape ? (nx + 31) / 32 : 0;
+    p.entry = CTK_BLOCKSTAT_REC + 4 * p.words;
+    p.form = longest * p.entry <= CTK_BLOCKSTAT_LDS_BYTES ? CTK_BLOCKSTAT_ROW_LDS : CTK_BLOCKSTAT_ROW_GLB;
+    p.lds = p.form == CTK_BLOCKSTAT_ROW_LDS ? longest * p.entry : 0;
+    p.passes = peaks && elem_bytes == 8 ? 2 : 1;
+    p.vec = aligned && npix % 4 == 0;
+    p.vpt = p.vec ? 4 : 1;
+    const int64_t lanes = (npix + p.vpt - 1) / p.vpt, per_part = (int64_t)CTK_SUBSET_THREADS * CTK_SUBSET_TILES;
+    p.bps = (lanes + per_part - 1) / per_part;
+    p.blocks = p.bps * steps;
+    p.grid = (unsigned)std::min<int64_t>(p.blocks, std::min<int64_t>(std::max<int64_t>(grid_max, 1), CTK_LEVEL_GRID_MAX));
+    p.xcd = p.grid >= CTK_LEVEL_XCD_MIN ? 1 : 0;
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------
 // rules every streamed entry shares
 // ------------------------------------------------------------------------------------------------
 // steps per chunk: chunk_steps, or (0) about 256 MB of input -- step_bytes is what one step brings in, a plane or the selected levels of

@@ -751,6 +751,61 @@ int ctk_subset_cb(ctk_handle *h, int64_t T, int ny, int nx, ctk_read_chunk_fn re
                   int64_t n_ids, int invert, int kind, ctk_write_chunk_fn writer /* or NULL */, void *writer_user, uint64_t *hits /* host [n_ids] or NULL */,
                   int64_t *n_selected /* or NULL */, int64_t chunk_steps);
 
+/* ---- per-block peak and extent: what a study selects (step, track) rows on ----------------------------------------------------------
+ * The "block intensity" of the literature is the maximum anomaly inside the block (the minimum for gorl = '<'), not the area mean
+ * ctk_lifecycle_* gives; the position of that peak is the block centre of the hybrid indices, which test for a height reversal
+ * equatorward of the anomaly maximum (Barriopedro et al. 2010; Dunn-Sigouin & Son 2013); and a zonal extent of at least 15 degrees of
+ * longitude, with the meridional span, is part of nearly every blocking definition.  The reference has no function for it;
+ * tests/blockstat_util.py is the numpy statement of what follows.
+ * flag: (T, ny, nx) int32; x: a float32 / float64 field of the same shape; the key is a ROW table exactly as ctk_subset_* states it:
+ * off[T + 1] (int64) and ids[n_ids] (int32), all > 0 and strictly increasing inside a step's slice.  There is no by-id reading here:
+ * n_off must be T + 1.  For entry e = (t, id) of the table let P be the pixels of step t with flag == id, in row-major order; rows[e]:
+ *     n             |P|.  n == 0: the entry matched nothing and every other value holds its "empty" value, given in brackets
+ *     r0, r1        the lowest and the highest grid row of P                                                          [-1, -1]
+ *     west, width   occ[c] says whether some pixel of P lies in column c.  All columns occupied: west = 0, width = nx.  Otherwise
+ *                   take the maximal CIRCULAR runs of unoccupied columns -- a run may pass the seam; its start s is the column whose
+ *                   western neighbour, modulo nx, is occupied --, the longest of them and among equally long ones the lowest s:
+ *                   west = (s + len) % nx, width = nx - len                                                            [-1, 0]
+ *                   (a rule of its own: NOT the `shift` of ctk_lifecycle_*, which copies the reference's non-circular
+ *                   np.argmax(np.diff(cols)); lon.max() - lon.min() over a block on the seam gives 359 degrees)
+ *     nv            the pixels of P whose value is not NaN                                                                  [0]
+ *     max, max_p    the largest of those values in the total order -inf < ... < -0.0 < +0.0 < ... < +inf, as float64 (a float32
+ *                   value widens exactly), and the lowest pixel index row * nx + col that holds exactly it   [nv == 0: NaN, -1]
+ *     min, min_p    the same at the other end, again the lowest index                                        [nv == 0: NaN, -1]
+ * want: CTK_BLOCK_SHAPE (r0 .. width), CTK_BLOCK_PEAKS (nv .. min) or both; what is not wanted holds its empty value, n is always
+ * counted, and CTK_BLOCK_SHAPE alone needs no field.  All of it is integers and selected values: there is no tolerance, and the same
+ * bytes result whatever the kernel form and the chunking (k_blockstat, ctk_blockstat.hip).
+ * rows: host, n_ids entries, overwritten.  n_ids == 0: the call succeeds and writes nothing.
+ * CTK_E_INVALID with a message, the handle usable and nothing written: everything ctk_subset_* refuses for a row table, n_off != T + 1,
+ * want 0 or with unknown bits, CTK_BLOCK_PEAKS with no field and no resident anomaly slab of the call's shape and type, chunk_steps < 0.
+ *
+ * ctk_blockstat_*_dev: both slabs in HBM; x_dev == NULL with CTK_BLOCK_PEAKS: the anomaly slab ctk_anom_* left resident on this handle.
+ * ctk_blockstat_f32 / _f64: host arrays through chunk-sized device buffers as ctk_composite_f32 / _f64 (chunk_steps = 0: about 256 MB
+ * per chunk); x == NULL, or peaks not wanted: only the flags travel.  The records accumulate in HBM over the chunks and are copied
+ * out once.
+ * ctk_blockstat_cb: two readers with ctk_composite_cb's contract (the flag reader is called before the field reader for every chunk;
+ * field_reader == NULL: the resident anomaly slab of elem_bytes, or no field).
+ * No blockstat call touches the resident slot: ctk_resident_anom_generation stays what it was. */
+#define CTK_BLOCK_SHAPE 1
+#define CTK_BLOCK_PEAKS 2
+typedef struct ctk_block_row {
+    uint32_t n, nv;
+    int32_t r0, r1, west, width;
+    int64_t max_p, min_p;
+    double max, min;
+} ctk_block_row;
+int ctk_blockstat_f32_dev(ctk_handle *h, const int32_t *flag_dev, const float *x_dev /* or NULL */, int64_t T, int ny, int nx, const int64_t *off, int64_t n_off,
+                          const int32_t *ids, int64_t n_ids, int want, ctk_block_row *rows /* host [n_ids] */);
+int ctk_blockstat_f64_dev(ctk_handle *h, const int32_t *flag_dev, const double *x_dev /* or NULL */, int64_t T, int ny, int nx, const int64_t *off, int64_t n_off,
+                          const int32_t *ids, int64_t n_ids, int want, ctk_block_row *rows);
+int ctk_blockstat_f32(ctk_handle *h, const int32_t *flag, const float *x /* or NULL */, int64_t T, int ny, int nx, const int64_t *off, int64_t n_off, const int32_t *ids,
+                      int64_t n_ids, int want, ctk_block_row *rows, int64_t chunk_steps);
+int ctk_blockstat_f64(ctk_handle *h, const int32_t *flag, const double *x /* or NULL */, int64_t T, int ny, int nx, const int64_t *off, int64_t n_off, const int32_t *ids,
+                      int64_t n_ids, int want, ctk_block_row *rows, int64_t chunk_steps);
+int ctk_blockstat_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, int64_t T, int ny, int nx, ctk_read_chunk_fn flag_reader, void *flag_user,
+                     ctk_read_chunk_fn field_reader /* or NULL */, void *field_user, const int64_t *off, int64_t n_off, const int32_t *ids, int64_t n_ids, int want,
+                     ctk_block_row *rows, int64_t chunk_steps);
+
 /* ---- the blocking-frequency climatology of the reference's tutorial (README.rst:159-160) ---------------------------------------
  *   xr.where(block['flag'] > 1, 1, 0).sum(dim='time') / block.ntime * 100     -- on the int32 flag slab (T, ny, nx), per group:
  *   counts[g][y][x] = #{t : group[t] == g and flag[t][y][x] > above}            (exact; the caller divides: counts / n[g] * 100)

@@ -313,6 +313,24 @@ int ctk_debug_subset_form(ctk_handle *h, int64_t *out3);
 int ctk_debug_time_subset(ctk_handle *h, const int32_t *flag_dev, int64_t T, int ny, int nx, const int64_t *off, int64_t n_off, const int32_t *ids, int64_t n_ids,
                           int invert, int kind, int32_t *out_dev, int want_hits, int want_n_selected, int reps, double *ms2);
 
+/* what ctk_blockstat_plan (csrc/ctk_forms.h) decides for a ctk_blockstat_* launch over `steps` steps of planes of ny rows of nx pixels:
+ * want as the entries take it, elem_bytes of the field (4 or 8), longest the longest slice of the row table; `aligned`: the flag's
+ * base pointer is a multiple of 16; grid_max: a lower cap on the workgroups (0: the rule's).  out14 = { form: 0 the slice's records and
+ * bit sets in LDS, 1 atomics straight on the records in HBM; 1 vector (16 bytes of flags per lane) / 0 scalar; pixels per thread; bytes
+ * of dynamic LDS of a workgroup; parts per step; parts of work = parts per step * steps; workgroups launched; 1: every XCD takes one
+ * contiguous eighth of them; launches per chunk (2: float64 peaks); words of an entry's column bit set; bytes of LDS per entry; the
+ * LDS budget in bytes; the entries that fit it at this nx; lanes of a part }.  Host only: no handle, no GPU. */
+int ctk_debug_blockstat_plan(int want, int elem_bytes, int64_t longest, int64_t ny, int64_t nx, int64_t steps, int aligned, int64_t grid_max, int64_t *out14);
+/* test hook: out3 = { the form of the last k_blockstat launch on this handle (0 / 1 as above, -1 none yet), 1 vector / 0 scalar, its
+ * workgroups } */
+int ctk_debug_blockstat_form(ctk_handle *h, int64_t *out3);
+/* measurement (tools/blockstat_probe.py): the k_blockstat launches of the whole slab alone on slabs in device memory (the arguments of
+ * ctk_blockstat_*_dev; is_f64: the field's type) between HIP events: one round that is not counted, then `reps` timed ones; ms2 =
+ * { best, mean }.  The records go on accumulating and are not returned.  off == NULL: a plain stream of 16-byte loads over the flag
+ * slab and, where x_dev is given, the field slab instead, the yardstick. */
+int ctk_debug_time_blockstat(ctk_handle *h, const int32_t *flag_dev, const void *x_dev, int is_f64, int64_t T, int ny, int nx, const int64_t *off, int64_t n_off,
+                             const int32_t *ids, int64_t n_ids, int want, int reps, double *ms2);
+
 /* what ctk_lwa_plan (csrc/ctk_forms.h) decides for a ctk_lwa_* launch over `steps` steps of ndom (1 / 2) domains, the longest of
  * `rows` rows of nx pixels of elem_bytes (4 / 8), `aligned`: both base pointers are multiples of 16.  out12 = { 1 the domain fits in
  * LDS / 0 the call is refused, 1 the vector form (16-byte loads of the strip; nx a multiple of 4) / 0 the scalar form, columns of a
