@@ -1558,7 +1558,7 @@ class Tracker:
         return float(ms[0]), float(ms[1])
 
     def _debug_set(self, family, xcd, grid_max):
-        """ctk_debug_set_<family> of the map families (level, reversal, subset, lwa): both numbers hold for its following launches"""
+        """ctk_debug_set_<family> of the map families (level, reversal, subset, lwa, blockstat): both numbers hold for its following launches"""
         check(getattr(lib(), "ctk_debug_set_" + family)(self._h, int(xcd), int(grid_max)))
 
     def _debug_launch(self, family, n):
@@ -1760,6 +1760,12 @@ class Tracker:
             args = c.args[:5]
         check(lib().ctk_debug_time_blockstat(self._h, flag_dev, x_dev, int(bool(f64)), int(T), int(ny), int(nx), *args, int(reps), ms))
         return float(ms[0]), float(ms[1])
+
+    def debug_set_blockstat(self, xcd=-1, grid_max=0):
+        """for the following blockstat launches -- xcd: how workgroups map to XCDs (0 launch order, 1 one contiguous eighth per XCD,
+        n > 1 tiles of n; -1: the library's rule, ctk_blockstat_plan); grid_max: a lower cap on the workgroups of a launch (0: the
+        rule's)"""
+        self._debug_set("blockstat", xcd, grid_max)
 
     def debug_blockstat_launch(self):
         """(form, vec, workgroups) of the last blockstat launch: form 0 / 1 = BLOCKSTAT_FORMS (-1: none yet), vec 1 vector / 0 scalar"""

@@ -214,7 +214,7 @@ struct StreamIO {
     int64_t passes_in = 0;                         // how often the input was streamed (2: the call had to re-read it)
 };
 
-// What a map family (level mean, reversal, local wave activity, subset) remembers of its launches and what its ctk_debug_set_* hook
+// What a map family (level mean, reversal, local wave activity, subset, blockstat) remembers of its launches and what its ctk_debug_set_* hook
 // overrides in the following ones
 struct LaunchKnobs {
     int form = -1;                                 // kernel form of the last launch (-1: none yet)
@@ -316,7 +316,8 @@ struct ctk_handle {
     int sb_vec = 0;
     // per-block peak and extent (ctk_blockstat.hip): the accumulators of the running call (two 64-bit and six 32-bit words per entry
     // of the table, then the column bit sets) and its rows; the k_blockstat launches (form: CTK_BLOCKSTAT_ROW_LDS / _ROW_GLB of
-    // ctk_forms.h) and whether the last one was vector or scalar.  The table itself is sb_tab: a call of either family uploads its own.
+    // ctk_forms.h), whether the last one was vector or scalar, and ctk_debug_set_blockstat.  The table itself is sb_tab: a call of
+    // either family uploads its own.
     DevBuf bs_acc, bs_rows;
     LaunchKnobs bs_knobs;
     int bs_vec = 0;

@@ -440,6 +440,12 @@ extern "C" int ctk_debug_blockstat_plan(int want, int elem_bytes, int64_t longes
     return CTK_OK;
 }
 
+// test hook / experiments for the following k_blockstat launches on this handle: as ctk_debug_set_level
+extern "C" int ctk_debug_set_blockstat(ctk_handle *h, int xcd_mode, int64_t grid_max)
+{
+    return knobs_set("ctk_debug_set_blockstat", h, &ctk_handle::bs_knobs, xcd_mode, grid_max);
+}
+
 // test hook: out3 = { the form of the last k_blockstat launch on this handle (-1 none yet), 1 vector / 0 scalar, its workgroups }
 extern "C" int ctk_debug_blockstat_form(ctk_handle *h, int64_t *out3)
 {

@@ -321,6 +321,8 @@ int ctk_debug_time_subset(ctk_handle *h, const int32_t *flag_dev, int64_t T, int
  * contiguous eighth of them; launches per chunk (2: float64 peaks); words of an entry's column bit set; bytes of LDS per entry; the
  * LDS budget in bytes; the entries that fit it at this nx; lanes of a part }.  Host only: no handle, no GPU. */
 int ctk_debug_blockstat_plan(int want, int elem_bytes, int64_t longest, int64_t ny, int64_t nx, int64_t steps, int aligned, int64_t grid_max, int64_t *out14);
+/* test hook / experiments for the following k_blockstat launches on this handle: as ctk_debug_set_level */
+int ctk_debug_set_blockstat(ctk_handle *h, int xcd_mode, int64_t grid_max);
 /* test hook: out3 = { the form of the last k_blockstat launch on this handle (0 / 1 as above, -1 none yet), 1 vector / 0 scalar, its
  * workgroups } */
 int ctk_debug_blockstat_form(ctk_handle *h, int64_t *out3);

@@ -198,7 +198,7 @@ def test_header_declares_the_blockstat_entries():
     prod, dbg = tae.declared("contrack_hip.h"), tae.declared("contrack_hip_debug.h")
     for n in ("ctk_blockstat_f32", "ctk_blockstat_f64", "ctk_blockstat_f32_dev", "ctk_blockstat_f64_dev", "ctk_blockstat_cb"):
         assert n in prod and n in _native.EXPORTS and hasattr(_native.lib(), n), n
-    for n in ("ctk_debug_blockstat_plan", "ctk_debug_blockstat_form", "ctk_debug_time_blockstat"):
+    for n in ("ctk_debug_blockstat_plan", "ctk_debug_set_blockstat", "ctk_debug_blockstat_form", "ctk_debug_time_blockstat"):
         assert n in dbg and n not in prod and hasattr(_native.lib(), n), n
     assert _native.ABI.constants["CTK_BLOCK_SHAPE"] == bu.SHAPE == 1 and _native.ABI.constants["CTK_BLOCK_PEAKS"] == bu.PEAKS == 2
     assert _native.BLOCK_ROW == bu.ROW and _native.BLOCK_ROW.itemsize == 56         # the struct as the header has it is the statement's row
