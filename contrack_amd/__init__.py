@@ -14,7 +14,8 @@ entry underneath it, `frequency_numpy` the blocking frequency (README.rst:159-16
 `std_field_numpy` the per-grid-point standard-deviation threshold field per group of timesteps,
 `level_mean_numpy` the vertical mean over a pressure band that comes before them (weights: `level_weights`),
 `reversal_numpy` / `reversal_rows` / `reversal_limits` the gradient-reversal blocking index, the other producer of a field to track,
-`lwa_numpy` / `lwa_rows` the finite-amplitude local wave activity, the third one.
+`lwa_numpy` / `lwa_rows` the finite-amplitude local wave activity, the third one,
+`time_filter_numpy` / `filter_layout` / `lanczos_weights` a weighted filter or block means along time of a field on its way there.
 Compute goes through hand-written HIP kernels behind a ctypes C ABI
 (include/contrack_hip.h); there is no CPU fallback.
 """
@@ -22,7 +23,7 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name in ("contrack", "track_numpy", "frequency_numpy", "spells_numpy", "spell_duration", "composite_numpy", "composite_mean", "centred_numpy", "centred_stamps", "lifecycle_bins", "band_numpy", "band_total", "band_fraction", "lon_sector", "subset_numpy", "subset_table", "track_table", "blockstat_numpy", "anomalies_numpy", "percentile_field_numpy", "std_field_numpy", "level_mean_numpy", "level_weights", "reversal_numpy", "reversal_rows", "reversal_limits", "lwa_numpy", "lwa_rows", "row_weights", "prepare_thresholds"):
+    if name in ("contrack", "track_numpy", "frequency_numpy", "spells_numpy", "spell_duration", "composite_numpy", "composite_mean", "centred_numpy", "centred_stamps", "lifecycle_bins", "band_numpy", "band_total", "band_fraction", "lon_sector", "subset_numpy", "subset_table", "track_table", "blockstat_numpy", "anomalies_numpy", "percentile_field_numpy", "std_field_numpy", "level_mean_numpy", "level_weights", "reversal_numpy", "reversal_rows", "reversal_limits", "lwa_numpy", "lwa_rows", "time_filter_numpy", "filter_layout", "lanczos_weights", "row_weights", "prepare_thresholds"):
         import importlib
         _m = importlib.import_module(".contrack", __name__)     # (`from . import contrack` would ask __getattr__ for 'contrack' first)
         return getattr(_m, name)

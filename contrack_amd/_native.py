@@ -138,6 +138,52 @@ def anom_plan(elem_bytes, smooth, nt, npix, waves_wanted=0, grid_y_max=0):
     return dict(zip(("form", "lds", "tile", "gx", "gy"), (int(a) for a in v)))
 
 
+FILTER_EDGES = {"nan": ABI.constants["CTK_FILTER_EDGES_NAN"], "renorm": ABI.constants["CTK_FILTER_EDGES_RENORM"]}
+
+
+def filter_plan(elem_bytes, K, stride, nout, npix, waves_wanted=0, grid_y_max=0, forced=-1):
+    """ctk_debug_filter_plan: what ctk_filter_plan (csrc/ctk_forms.h) decides for a time-filter launch of nout outputs, as a dict (form 1
+    LDS ring / 0 plain, threads per workgroup, lds bytes, tile outputs per workgroup, gx, gy); waves_wanted / grid_y_max: 0 the rule's,
+    forced: -1 the rule's form.  Host only."""
+    v = np.zeros(6, dtype=np.int64)
+    check(lib().ctk_debug_filter_plan(int(elem_bytes), int(K), int(stride), int(nout), int(npix), int(waves_wanted), int(grid_y_max), int(forced), v.ctypes.data))
+    return dict(zip(("form", "threads", "lds", "tile", "gx", "gy"), (int(a) for a in v)))
+
+
+def _filter_weights(weights):
+    """(w as float64 array or None for box mode, K) of a `weights` that is an array of taps or an int K"""
+    if np.ndim(weights) == 0:
+        if isinstance(weights, (bool, np.bool_)) or int(weights) != weights:
+            raise ValueError("weights must be an array of taps or an int K (box mode)")
+        return None, int(weights)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.ndim != 1 or w.size < 1:
+        raise ValueError("weights must be a 1-D array of at least one tap")
+    return w, int(w.size)
+
+
+def filter_offset(K, stride, offset=None):
+    """the offset of a filter call: as given, or the default -- a centred window (-(K // 2)) at stride 1, blocks counted from the segment
+    start (0) otherwise"""
+    if offset is None:
+        return -(K // 2) if stride == 1 else 0
+    return int(offset)
+
+
+def filter_layout(T, K, stride=1, offset=None, segments=None):
+    """ctk_filter_layout: where the outputs of a time filter of K taps lie on an axis of T steps, as (first, label, out_starts) -- per
+    output the step of tap 0 and the label step first + K // 2, per segment its first output.  len(first) is T_out.  Host only."""
+    st = _seg_starts(segments if segments is not None else [])
+    off = filter_offset(int(K), int(stride), offset)
+    first = np.zeros(max(int(T), 1), dtype=np.int64)
+    out_starts = np.zeros(max(st.shape[0], 1), dtype=np.int64)
+    n = C.c_int64(0)
+    check(lib().ctk_filter_layout(int(T), int(K), int(stride), off, st.ctypes.data if st.size else None, st.shape[0], first.ctypes.data, out_starts.ctypes.data,
+                                  C.byref(n)))
+    first = first[:n.value].copy()
+    return first, first + int(K) // 2, out_starts
+
+
 def level_plan(elem_bytes, nsel, npix, steps, aligned=True):
     """ctk_debug_level_plan: what ctk_level_plan (csrc/ctk_forms.h) decides for a level_mean launch, as a dict (vec 1 vector / 0 scalar
     form, vpt pixels per thread, unroll, bps workgroups per step, blocks, grid, xcd); no handle, no GPU"""
@@ -1872,6 +1918,99 @@ class Tracker:
         v = np.zeros(8, dtype=np.int64)
         check(lib().ctk_debug_anom_launch(self._h, v.ctypes.data))
         return dict(zip(("form", "tile", "gx", "gy", "lds", "o0", "o1", "launches"), (int(a) for a in v)))
+
+    # ---- weighted filter / block mean along time (ctk_filter_*) ----------------------------------------------------
+    @staticmethod
+    def _filter_args(T, weights, stride, offset, edges, skipna, segments):
+        """(the arguments from w to nseg of the ctk_filter_* entries, T_out, what must stay alive during the call)"""
+        w, K = _filter_weights(weights)
+        if edges not in FILTER_EDGES:
+            raise ValueError("edges must be 'nan' or 'renorm'")
+        st = _seg_starts(segments if segments is not None else [])
+        off = filter_offset(K, int(stride), offset)
+        n = C.c_int64(0)
+        check(lib().ctk_filter_layout(int(T), K, int(stride), off, st.ctypes.data if st.size else None, st.shape[0], None, None, C.byref(n)))
+        return (_ptr(w), K, int(stride), off, FILTER_EDGES[edges], int(bool(skipna)), st.ctypes.data if st.size else None, st.shape[0]), int(n.value), (w, st)
+
+    def time_filter(self, x, weights, stride=1, offset=None, edges="nan", skipna=False, segments=None, chunk_steps=None, keep_resident=False, want_out=True,
+                    out=None):
+        """x (T, ny, nx) float32 / float64 (an array or np.memmap); weights: K taps, or an int K (box mode: the mean of K steps).
+        Output q of a segment has its taps at the steps S + offset + q * stride + (0 .. K - 1) and exists where its label step
+        (tap K // 2) lies in the segment; offset None: -(K // 2) at stride 1 (one output per step, centred), 0 otherwise (blocks from
+        the segment start).  Taps outside the segment: edges 'nan' gives NaN, 'renorm' divides by the sum of the used weights;
+        skipna: a NaN tap is left out the same way (include/contrack_hip.h).  Returns the (T_out, ny, nx) result in x's dtype (None
+        without want_out).  chunk_steps: steps per chunk on their way through the device (None / 0: about 256 MB); same bits.
+        keep_resident: the result stays in HBM in the level-mean slot, for anomalies_resident / time_filter_resident.
+        out: a C-contiguous (T_out, ny, nx) array of x's dtype to write into instead of a new one."""
+        x = _float_array(x, 3, "x must be (time, lat, lon)")
+        T, ny, nx = x.shape
+        if not want_out and not keep_resident:
+            raise ValueError("want_out=False without keep_resident asks for nothing")
+        mid, T_out, _keep = self._filter_args(T, weights, stride, offset, edges, skipna, segments)
+        if out is not None and (not want_out or out.dtype != x.dtype or out.shape != (T_out, ny, nx) or not out.flags.c_contiguous):
+            raise ValueError("out must be a C-contiguous (T_out, ny, nx) = (%d, %d, %d) array of x's dtype" % (T_out, ny, nx))
+        if out is None:
+            out = np.empty((T_out, ny, nx), dtype=x.dtype) if want_out else None
+        fn = lib().ctk_filter_f64 if x.dtype == np.float64 else lib().ctk_filter_f32
+        check(fn(self._h, x.ctypes.data, T, ny, nx, *mid, _ptr(out), T_out, int(chunk_steps or 0), int(bool(keep_resident))))
+        return out
+
+    def time_filter_cb(self, reader, shape, dtype, weights, stride=1, offset=None, edges="nan", skipna=False, segments=None, sink=None, chunk_steps=0,
+                       keep_resident=False):
+        """time_filter with a reader(t0, nt, out) that fills `out`, a (nt, ny, nx) view of pinned memory, with the steps [t0, t0 + nt);
+        shape = (T, ny, nx).  sink: None (a new array is returned), False (nothing leaves the device: keep_resident), a C-contiguous
+        (T_out, ny, nx) array of `dtype`, or a writer(t0, nt, values) of outputs.  The reader sees every step once, in rising order."""
+        if shape is None or dtype is None:
+            raise ValueError("a reader needs shape=(T, ny, nx) and dtype")
+        T, ny, nx = (int(v) for v in shape)
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("the field must be float32 or float64")
+        mid, T_out, _keep = self._filter_args(T, weights, stride, offset, edges, skipna, segments)
+        out, sink = _value_sink(sink, (T_out, ny, nx), dt, "T_out", "field", "keep_resident", keep_resident)
+        tr = _Trampolines()
+        rcb, wcb = tr.reader(reader, _float_ctype(dt), (ny, nx)), tr.writer(sink, _float_ctype(dt), (ny, nx))
+        tr.finish(lib().ctk_filter_stream_cb(self._h, dt.itemsize, T, ny, nx, rcb, None, *mid, wcb, None, T_out, int(chunk_steps or 0), int(bool(keep_resident))))
+        return out
+
+    def time_filter_resident(self, weights, stride=1, offset=None, edges="nan", skipna=False, segments=None, keep_resident=False, want_out=True):
+        """time_filter of the resident level mean (ctk_filter_resident): nothing crosses PCIe on the way in.  Returns the result in the
+        mean's dtype (None without want_out); keep_resident: it replaces the mean in the slot.  Raises if no mean is resident."""
+        shape = self.resident_level_mean()
+        if shape is None:
+            raise ContrackHipError("no vertical mean is resident on the device")
+        T, ny, nx, f64 = shape
+        if not want_out and not keep_resident:
+            raise ValueError("want_out=False without keep_resident asks for nothing")
+        mid, T_out, _keep = self._filter_args(T, weights, stride, offset, edges, skipna, segments)
+        out = np.empty((T_out, ny, nx), dtype=np.float64 if f64 else np.float32) if want_out else None
+        check(lib().ctk_filter_resident(self._h, *mid, _ptr(out), T_out, int(bool(keep_resident))))
+        return out
+
+    def time_filter_dev(self, x_dev, T, ny, nx, weights, out_dev, stride=1, offset=None, edges="nan", skipna=False, segments=None, f64=False):
+        """ctk_filter_*_dev: x (T, ny, nx) and out (T_out, ny, nx) in device memory; returns T_out"""
+        mid, T_out, _keep = self._filter_args(T, weights, stride, offset, edges, skipna, segments)
+        check((lib().ctk_filter_f64_dev if f64 else lib().ctk_filter_f32_dev)(self._h, x_dev, int(T), int(ny), int(nx), *mid, out_dev, T_out))
+        return T_out
+
+    def time_filter_kernel(self, x_dev, T, ny, nx, weights, out_dev, stride=1, offset=None, edges="nan", skipna=False, f64=False, copy_bytes=0, reps=5):
+        """measurement (tools/filter_probe.py): (best, mean) ms of the filter kernel alone on slabs in device memory, HIP events;
+        copy_bytes > 0: of the plain 16-byte copy kernel over that many bytes of the two buffers instead"""
+        mid, T_out, _keep = self._filter_args(T, weights, stride, offset, edges, skipna, None)
+        ms = (C.c_double * 2)()
+        check(lib().ctk_debug_time_filter(self._h, x_dev, int(bool(f64)), int(T), int(ny), int(nx), *mid[:6], out_dev, T_out, int(copy_bytes), int(reps), ms))
+        return float(ms[0]), float(ms[1])
+
+    def debug_set_filter(self, waves_wanted=0, grid_y_max=0, forced=-1):
+        """for the following time_filter launches: ctk_filter_plan's waves_wanted and grid_y_max (0: the rule's) and the form (1 LDS ring
+        where one fits, 0 plain, -1 the rule's), so that a small slab reaches every form and tile edge"""
+        check(lib().ctk_debug_set_filter(self._h, int(waves_wanted), int(grid_y_max), int(forced)))
+
+    def debug_filter_launch(self):
+        """dict of the last time-filter launch (form, threads, tile, gx, gy, lds, o0, o1) and `launches`, their number in the last call"""
+        v = np.zeros(9, dtype=np.int64)
+        check(lib().ctk_debug_filter_launch(self._h, v.ctypes.data))
+        return dict(zip(("form", "threads", "tile", "gx", "gy", "lds", "o0", "o1", "launches"), (int(a) for a in v)))
 
     def resident_anom(self):
         T, ny, nx, f = C.c_int64(0), C.c_int(0), C.c_int(0), C.c_int(0)

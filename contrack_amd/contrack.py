@@ -670,6 +670,84 @@ def anomalies_numpy(x, group, ngroups=None, window=1, smooth=1, clim=None, segme
     return trk.anomalies_stream(x, ids, G, window=window, smooth=smooth, clim=clim, chunk_steps=int(chunk_steps), segments=starts, want_clim=True)
 
 
+def lanczos_weights(ntaps, cutoff, cutoff2=None, kind='lowpass'):
+    """float64 weights of a Lanczos filter of `ntaps` (odd) taps, Duchon (1979): with n = (ntaps - 1) / 2 and k = -n .. n,
+        w[k] = sin(2 pi fc k) / (pi k) * sin(pi k / (n + 1)) / (pi k / (n + 1)),   w[0] = 2 fc
+    for the cut-off frequency fc in cycles per step (0 < fc <= 0.5).  kind 'lowpass': those weights normalised to sum 1;
+    'highpass': a unit impulse at the centre minus the low-pass; 'bandpass': the low-pass of the higher of cutoff / cutoff2 minus
+    the low-pass of the lower (passes the periods between 1 / higher and 1 / lower steps).  Host numpy."""
+    if int(ntaps) != ntaps or ntaps < 1 or int(ntaps) % 2 == 0:
+        raise ValueError("ntaps must be an odd positive integer, got {}".format(ntaps))
+    if kind not in ('lowpass', 'highpass', 'bandpass'):
+        raise ValueError("kind must be 'lowpass', 'highpass' or 'bandpass'")
+    if (kind == 'bandpass') != (cutoff2 is not None):
+        raise ValueError("cutoff2 is the second cut-off of kind='bandpass' (and only of it)")
+
+    def low(fc):
+        if not 0.0 < fc <= 0.5:
+            raise ValueError("a cut-off is a frequency in cycles per step, 0 < fc <= 0.5, got {}".format(fc))
+        n = (int(ntaps) - 1) // 2
+        k = np.arange(-n, n + 1, dtype=np.float64)
+        k[n] = 1.0                                           # (the centre is set below)
+        w = np.sin(2.0 * np.pi * fc * k) / (np.pi * k) * (np.sin(np.pi * k / (n + 1)) / (np.pi * k / (n + 1)))
+        w[n] = 2.0 * fc
+        return w / w.sum()
+    if kind == 'bandpass':
+        lo, hi = sorted((float(cutoff), float(cutoff2)))
+        return low(hi) - low(lo)
+    w = low(float(cutoff))
+    if kind == 'highpass':
+        w = -w
+        w[(int(ntaps) - 1) // 2] += 1.0
+    return w
+
+
+def filter_layout(T, weights, stride=1, offset=None, segments=None):
+    """where the outputs of time_filter_numpy lie: (label_steps, out_starts, first) -- per output its label step (tap K // 2) and the
+    step of tap 0, per segment its first output.  weights: the taps or an int K.  Host only."""
+    _, K = _native._filter_weights(weights)
+    first, label, out_starts = _native.filter_layout(T, K, stride, offset, None if segments is None else segment_starts(segments, T))
+    return label, out_starts, first
+
+
+def time_filter_numpy(x, weights, stride=1, offset=None, edges='nan', skipna=False, segments=None, chunk_steps=None, device=None, shape=None, dtype=None,
+                      layout=False):
+    """a weighted filter or a block mean along the time axis of a (time, lat, lon) float slab on the GPU.  weights: the K taps
+    (lanczos_weights, or any float64 array), or an int K: the plain mean of K steps.  Output q of a segment covers the steps
+    S + offset + q * stride + (0 .. K - 1) and is labelled with the step of tap K // 2; it exists where that step lies in the
+    segment.  offset None: -(K // 2) at stride 1 -- one output per step, the centred window of calc_anom's `smooth` --, 0 at a
+    larger stride: blocks counted from the segment start (6-hourly to daily: weights=4, stride=4).
+    edges: 'nan' -- an output whose window leaves its segment is NaN; 'renorm' -- the taps inside are used and the sum is divided
+    by the sum of their weights (weights >= 0 only).  skipna: NaN taps are left out in the same way.  segments: int array of
+    segment starts; no window crosses a break.  chunk_steps: stream the slab (an array, np.memmap, or a reader(t0, nt, out) with
+    `shape` and `dtype`) through chunk-sized device buffers (0: about 256 MB each); same bits.
+    Returns the (T_out, lat, lon) array in the slab's dtype, or (array, label_steps, out_starts) with layout=True."""
+    trk = _tracker(device)
+    if callable(x):
+        if shape is None:
+            raise ValueError("a reader needs shape=(T, ny, nx) and dtype")
+        T = int(shape[0])
+    else:
+        x = np.asarray(x) if not isinstance(x, np.memmap) else x
+        if x.ndim != 3:
+            raise ValueError("x must be (time, lat, lon)")
+        if x.dtype.kind != "f":
+            if x.dtype.kind not in "iub":
+                raise TypeError("x must be a real numeric array")
+            x = x.astype(np.float64)
+        T = x.shape[0]
+    starts = None if segments is None else segment_starts(segments, T)
+    if callable(x):
+        out = trk.time_filter_cb(x, shape, dtype, weights, stride=stride, offset=offset, edges=edges, skipna=skipna, segments=starts,
+                                 chunk_steps=int(chunk_steps or 0))
+    else:
+        out = trk.time_filter(x, weights, stride=stride, offset=offset, edges=edges, skipna=skipna, segments=starts, chunk_steps=chunk_steps)
+    if not layout:
+        return out
+    label, out_starts, _ = filter_layout(T, weights, stride, offset, starts)
+    return out, label, out_starts
+
+
 def level_weights(levels, bounds=None):
     """float64 weights of a vertical mean over a level coordinate (one per level, 0: not selected): the levels p with
     min(bounds) <= p <= max(bounds) (bounds None: all of them) get the trapezoid rule over the selected levels in coordinate order --
@@ -1617,6 +1695,77 @@ class contrack(object):
         trk = _tracker()
         return res[1] == _fingerprint(np.asarray(self.ds[variable].data)) and res[2] == trk.resident_level_mean_generation() and \
             trk.resident_level_mean() == (slab.shape[0], slab.shape[1], slab.shape[2], slab.dtype == np.float64)
+
+    # ---- a weighted filter or block means along time -------------------------------------------------------------------------
+    def calc_filter(self, variable, weights, stride=1, offset=None, edges='nan', skipna=False, segments=None, chunk_steps=None, name=None):
+        """a weighted filter or a block mean of `variable` along time on the GPU (time_filter_numpy states layout and arithmetic).
+        weights: the taps -- lanczos_weights(ntaps, cutoff ...) for a low-, high- or band-pass, any float64 array -- or an int K:
+        the plain mean of K steps.  edges: 'nan' (an output whose window leaves its segment is NaN) or 'renorm' (the taps inside,
+        divided by the sum of their weights); skipna: NaN taps are left out the same way.
+        segments: the meaning it has in calc_anom -- None, 'gaps', an int array of start indices, or the name of a member dimension
+        of a 4-D variable (any dim order); no window crosses a break.
+        stride == 1 (and the default offset): one output per step; adds the variable `name` (default variable + '_filt') with the
+        variable's dims and units.  Over time alone and without chunk_steps the result also stays in HBM and a following
+        calc_anom(variable=name) starts from there; if `variable` is itself the vertical mean calc_vertical_mean left there, it is
+        not uploaded either.
+        stride > 1 (6-hourly to daily means: weights=4, stride=4): the time axis changes, so the result is RETURNED as a labelled
+        array whose time coordinate is the time of each output's label step (tap K // 2) and nothing is added to the dataset.  A
+        member dimension stays in place; every member has the same number of outputs.
+        chunk_steps: the variable is read slice by slice (`isel`) and passes through chunk-sized device buffers."""
+        self._ensure_set_up()
+        da = self.ds[variable]
+        dims = tuple(da.dims)
+        member, starts, T = self._segment_args(variable, da, dims, segments)
+        if member is None and len(dims) != 3:
+            raise ValueError("the variable {!r} must be 3-D (time, lat, lon in any order), it has dims {}".format(variable, dims))
+        view = self._steps(da, (member, self._time_name))
+        _, K = _native._filter_weights(weights)
+        label, out_starts, _ = filter_layout(view.steps, weights, stride, offset, starts)
+        M = 1 if member is None else da.shape[dims.index(member)]
+        in_place = int(stride) == 1 and len(label) == view.steps          # one output per step: the variable's own time axis
+        resident = in_place and chunk_steps is None and member is None
+        kw = dict(stride=stride, offset=offset, edges=edges, skipna=skipna, segments=starts)
+        trk = _tracker()
+        logger.info('Filtering {} along {} ({} taps, stride {})...'.format(variable, self._time_name, K, stride))
+        if chunk_steps is not None:
+            out = trk.time_filter_cb(view.reader(), view.shape, _producer_dtype(da.dtype), weights, chunk_steps=int(chunk_steps), **kw)
+        else:
+            slab = view.slab()
+            slab = np.ascontiguousarray(slab, dtype=_producer_dtype(slab.dtype))
+            if resident and self._vmean_resident_for(variable, slab):       # (the mean left in HBM: nothing to upload, same bits)
+                out = trk.time_filter_resident(weights, keep_resident=True, **kw)
+            else:
+                out = trk.time_filter(slab, weights, keep_resident=resident, **kw)
+        if resident:
+            out.flags.writeable = False                      # (its twin stays in HBM for calc_anom: see _fingerprint)
+        n_out = len(label) // M                              # (segments of one length: every member has the same outputs)
+        have = view.step_dims + (self._latitude_name, self._longitude_name)
+        arr = out.reshape(((M,) if member is not None else ()) + (n_out,) + out.shape[1:]).transpose([have.index(d) for d in dims])
+        name = variable + '_filt' if name is None else name
+        attrs = {}
+        if 'units' in da.attrs:
+            attrs['units'] = da.attrs['units']
+        attrs['long_name'] = da.attrs.get('long_name', variable) + ' filtered in time'
+        attrs['history'] = 'Calculated from {} with input attributes: taps = {}{}, stride = {}, offset = {}, edges = {}{}, segments = {} ({}).'.format(
+            variable, K, ' (box)' if np.ndim(weights) == 0 else '', int(stride), _native.filter_offset(K, int(stride), offset), edges,
+            ', NaN taps skipped' if skipna else '', None if segments is None else (segments if isinstance(segments, str) else 'starts'),
+            1 if starts is None else len(starts))
+        if in_place:
+            self.ds[name] = (dims, arr, attrs)
+            self._vmean_resident = (name, _fingerprint(np.asarray(self.ds[name].data)), trk.resident_level_mean_generation()) if resident else None
+            logger.info('Filtering... DONE')
+            return None
+        if getattr(self, "_vmean_resident", None) is not None and chunk_steps is None and self._vmean_resident[0] == name:
+            self._vmean_resident = None
+        coords = {}
+        for d in dims:
+            try:
+                vals = np.asarray(self.ds[d].data)
+            except (KeyError, AttributeError):
+                continue
+            coords[d] = vals[label[:n_out]] if d == self._time_name else vals
+        logger.info('Filtering... DONE')
+        return self._wrap(da, arr, dims, coords, attrs, name)
 
     # ---- reversal of the meridional height gradient: the second family of blocking indices --------------------------------
     def calc_reversal(self, variable, delta=15., ghgs=0., ghgn=-10., ghgs2=None, lat_bounds=(30, 75), hemisphere='both', stat='gradient', name='reversal',

@@ -300,6 +300,12 @@ struct ctk_handle {
     int64_t lv_T = -1; int lv_ny = 0, lv_nx = 0; bool lv_f64 = false;
     uint64_t lv_gen = 0;                           // bumped by every ctk_level_mean_* call and by ctk_release_io: WHICH mean is resident
     LaunchKnobs lv_knobs;                          // the k_level_mean launches (form: 1 vector, 0 scalar); ctk_debug_set_level
+    // time filter (ctk_filter.hip): the table of the running call (K float64 weights, then one CtkFilterTap per output); the result of
+    // a call that keeps it or reads the resident mean, which then changes owner with lv_out (never filtered in place)
+    DevBuf fl_tab, fl_out;
+    int64_t fl_waves_dbg = 0, fl_gy_dbg = 0; int fl_form_dbg = -1;       // ctk_debug_set_filter: ctk_filter_plan's waves_wanted / grid_y_max / forced
+    int64_t fl_last[8] = {-1, 0, 0, 0, 0, 0, 0, 0};                      // the last launch_filter: form, threads, tile, gx, gy, lds, o0, o1 ...
+    int64_t fl_launches = 0;                                             // ... and how many of them the last ctk_filter_* call made
     // reversal of the meridional gradient (ctk_reversal.hip): the row table of the running call (four float64 and three int32 per row);
     // the k_reversal launches (form: 1 vector, 0 scalar) and ctk_debug_set_reversal
     DevBuf gr_tab;
@@ -3671,7 +3677,7 @@ extern "C" int ctk_release_io(ctk_handle *h)
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
     HIPCHK(hipSetDevice(h->device));
-    for (DevBuf *b : {&h->io_in, &h->io_out, &h->an_out, &h->an_raw, &h->lv_out, &h->gr_tab, &h->lw_tab, &h->lw_ref}) b->release();
+    for (DevBuf *b : {&h->io_in, &h->io_out, &h->an_out, &h->an_raw, &h->lv_out, &h->fl_out, &h->gr_tab, &h->lw_tab, &h->lw_ref}) b->release();
     h->an_T = -1; h->an_gen++; h->an_pct_n = -1;
     h->lv_T = -1; h->lv_gen++;
     h->io_gen++; h->lc_flag = nullptr; h->lc_field = nullptr;          // (the exact rows of a lifecycle call read those slabs)
@@ -4145,6 +4151,7 @@ extern "C" int ctk_lifecycle_rows(ctk_handle *h, ctk_life_row *rows, int64_t cap
 #include "ctk_pfield.hip"
 #include "ctk_std.hip"
 #include "ctk_level.hip"
+#include "ctk_filter.hip"
 #include "ctk_reversal.hip"
 #include "ctk_lwa.hip"
 #include "ctk_subset.hip"

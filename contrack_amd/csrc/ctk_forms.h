@@ -595,6 +595,59 @@ inline CtkAnomPlan ctk_anom_plan(int elem_bytes, int smooth, int64_t nt, int64_t
 }
 
 // ------------------------------------------------------------------------------------------------
+// weighted time filter and block means (ctk_filter.hip): k_filter_ring keeps the last K values of a lane's pixel in LDS while it walks
+// the steps of its tile of outputs; k_filter_plain reads every tap from memory -- for a K whose ring does not fit, and for
+// stride >= K, where no two outputs share a tap.
+// The ring of a workgroup is K * threads * elem_bytes.  Its budget stays CTK_ANOM_RING_BYTES: 160 KB of LDS per CU hold five such
+// workgroups, which at 256 threads are 20 waves per CU -- the occupancy k_anom_ring runs at.  A longer K takes fewer threads per
+// workgroup, 128, then 64 (one wave): 128 float32 / 64 float64 taps.  Five workgroups of one wave are 5 waves per CU; a kernel that long
+// is bound by its K LDS reads and float64 additions per output, not by loads in flight, so the lower occupancy costs little there,
+// and the plain form it replaces reads x K times.
+// ------------------------------------------------------------------------------------------------
+#define CTK_FILTER_THREADS 256        // the most threads of a workgroup (the launch bound of both kernels)
+#define CTK_FILTER_THREADS_MIN 64
+#define CTK_FILTER_RING_BYTES CTK_ANOM_RING_BYTES
+#define CTK_FILTER_TILE_MIN 32        // outputs per workgroup: the ring form reads K - stride halo steps per tile on top of tile * stride
+#define CTK_FILTER_TILE_MAX 1024      // (K = 121 at stride 1: the halo stays near a tenth of the reads)
+#define CTK_FILTER_MAX_TAPS (1 << 20)
+enum CtkFilterForm { CTK_FILTER_PLAIN = 0, CTK_FILTER_RING = 1 };
+struct CtkTimeFilterPlan {
+    int form;                     // CtkFilterForm
+    int threads;                  // per workgroup
+    size_t lds;                   // dynamic LDS of the launch (ring form)
+    int64_t tile;                 // outputs per workgroup
+    unsigned gx, gy;
+};
+// nout outputs of a plane of npix pixels.  waves_test: 0, grid_y_max: 65535, forced: -1 the rule -- or a test's values
+// (ctk_debug_set_filter): waves_test > 0 asks for that many waves and drops the rule's shortest tiles, so that a small slab reaches
+// a tile of one output and one longer than the slab; forced = CTK_FILTER_PLAIN always holds, forced = CTK_FILTER_RING where a ring fits
+inline CtkTimeFilterPlan ctk_filter_plan(int elem_bytes, int64_t K, int64_t stride, int64_t nout, int64_t npix, int64_t waves_test = 0, int64_t grid_y_max = 65535,
+                                         int forced = -1)
+{
+    CtkTimeFilterPlan p = {};
+    p.form = CTK_FILTER_PLAIN; p.threads = CTK_FILTER_THREADS;
+    int fit = 0;                                                                         // the most threads whose ring fits (0: none)
+    for (int th = CTK_FILTER_THREADS; th >= CTK_FILTER_THREADS_MIN && !fit; th /= 2)
+        if ((uint64_t)K * (uint64_t)th * (uint64_t)elem_bytes <= CTK_FILTER_RING_BYTES) fit = th;
+    if (fit && forced != CTK_FILTER_PLAIN && (stride < K || forced == CTK_FILTER_RING)) {
+        p.form = CTK_FILTER_RING; p.threads = fit; p.lds = (size_t)K * (size_t)fit * (size_t)elem_bytes;
+    }
+    const int64_t waves = (npix + 63) / 64;
+    // the longest tile that still leaves waves_wanted waves; the ring form: at least 8 x the halo, so that it stays below an eighth of the reads
+    int64_t tile = std::min<int64_t>(CTK_FILTER_TILE_MAX, std::max<int64_t>(1, nout * waves / (waves_test > 0 ? waves_test : CTK_ANOM_WAVES)));
+    if (waves_test <= 0) {
+        const int64_t halo8 = K > stride ? (8 * (K - stride) + stride - 1) / stride : 0;
+        tile = std::min<int64_t>(CTK_FILTER_TILE_MAX, std::max<int64_t>(tile, std::max<int64_t>(CTK_FILTER_TILE_MIN, halo8)));
+        if (p.form == CTK_FILTER_PLAIN) tile = CTK_FILTER_TILE_MIN;
+    }
+    tile = std::max(tile, (nout + grid_y_max - 1) / grid_y_max);                          // gridDim.y <= 65535
+    p.tile = tile;
+    p.gx = (unsigned)((npix + p.threads - 1) / p.threads);
+    p.gy = (unsigned)std::max<int64_t>(1, (nout + tile - 1) / tile);
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------
 // vertical mean over the selected levels (ctk_level.hip): k_level_mean, one thread per 16 bytes of adjacent pixels of one step (vector
 // form: every level plane starts on a 16-byte boundary) or per pixel (scalar form); a workgroup stays inside one step, so the step of a
 // workgroup is a scalar and `steps` never sits in a grid dimension that ends at 65 535

@@ -970,6 +970,60 @@ int ctk_band_f64(ctk_handle *h, const int32_t *flag, const double *x, int64_t T,
 int ctk_band_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, int64_t T, int ny, int nx, ctk_read_chunk_fn flag_reader, void *flag_user,
                 ctk_read_chunk_fn field_reader, void *field_user, const ctk_band_spec *spec, const ctk_band_out *out, int64_t chunk_steps);
 
+/* ---- a weighted filter or a block mean along time ---------------------------------------------------------------------------------
+ * The low-, high- and band-pass filters of the blocking literature (Lanczos weights, Duchon 1979) and means over blocks of steps
+ * (6-hourly to daily, daily to pentads).  The reference has no function for it; tests/filter_util.py is the numpy statement of what
+ * follows.  x: (T, ny, nx), float32 or float64, C-contiguous.  w: K float64 weights (weighted mode), or NULL (box mode: the mean of
+ * the K taps).  1 <= K <= 2^20, stride >= 1, offset of either sign.  Segment starts as everywhere: 0 first, strictly increasing,
+ * the last below T; nseg = 0: one segment.  Segment s is the steps [S, E).
+ * Layout: output q = 0, 1, ... of segment s has its taps i = 0 .. K - 1 at the steps first + i, first = S + offset + q * stride, and
+ * its label step at first + K / 2 (integer division).  The output exists iff S <= label < E.  Outputs are numbered through the
+ * segments in order; a segment may have none.  T_out <= T.  With stride = 1 and offset = -(K / 2) there is one output per step,
+ * its window K / 2 steps back and (K - 1) / 2 forward -- the window of ctk_anom_*'s `smooth` --, and T_out == T.
+ * The used taps of an output are [k0, k1), the i with S <= first + i < E; its window is complete iff k0 == 0 and k1 == K.
+ * Value, per output and pixel, everything in float64, the used taps in rising i, no fused multiply-add:
+ *     weighted:  s = 0, ws = 0, n = 0;  per tap  v = (double)x[first + i];  skipna and v is NaN: the tap is skipped;
+ *                otherwise  s = s + (w[i] * v)  -- the product rounded, then added --,  ws = ws + w[i],  n = n + 1
+ *     box:       the same with  s = s + v
+ *     result:    NaN where edges == CTK_FILTER_EDGES_NAN and the window is incomplete, and where n == 0;
+ *                box: (dtype)(s / (double)n);  weighted with no tap missing (complete, none skipped): (dtype)s;
+ *                weighted with taps missing (incomplete under CTK_FILTER_EDGES_RENORM, or skipped): (dtype)(s / ws)
+ * so CTK_FILTER_EDGES_RENORM changes the ends of a segment only.  Without skipna NaN and +-inf propagate by IEEE arithmetic.
+ * The bits are those of that loop whatever the kernel form, thread count, tile, alignment, chunking or source.
+ * CTK_E_INVALID with a message (also with a NULL handle), the handle usable: T, K, stride, ny or nx below 1, a weight that is NaN or
+ * inf, edges == CTK_FILTER_EDGES_RENORM or skipna with a negative weight or a sum of weights that is not positive (a band-pass
+ * cannot be renormalised), bad segment starts, T_out that is not the layout's, chunk_steps < 0, nothing to produce.
+ *
+ * ctk_filter_layout (host only, no handle): T_out, and where not NULL first_out[T_out] (T entries are always enough) and
+ * out_starts[max(nseg, 1)], the first output of every segment.
+ * ctk_filter_f32_dev / _f64_dev: x and out (T_out, ny, nx) in device memory, not overlapping.
+ * ctk_filter_f32 / _f64: host arrays (out may be NULL with keep_resident).  The slab passes through two chunk buffers of
+ * chunk_steps + K - 1 steps (0: about 256 MB per chunk; below K - 1 it is raised to K - 1); the last K - 1 steps of a chunk stay on
+ * the device for the next, so no step is uploaded twice.  An output leaves with the chunk that holds step first + K - 1.
+ * ctk_filter_stream_cb: reader and writer (may be NULL with keep_resident) as ctk_level_mean_stream_cb's, one plane per step; the
+ * writer receives outputs [t0, t0 + nt) in rising order, not with every chunk.  Neither is asked for a step twice.
+ * keep_resident != 0: the result also stays in HBM as the resident level mean (ctk_resident_level_mean reports T_out steps, its
+ * generation advances), where ctk_anom_seg_resident and ctk_filter_resident take it as they take a vertical mean.
+ * ctk_filter_resident: x is the resident level mean (CTK_E_INVALID if there is none): shape and dtype are its; out (NULL: none) holds
+ * T_out planes of that dtype; keep_resident != 0: the result replaces the mean in the slot.  It is never filtered in place. */
+#define CTK_FILTER_EDGES_NAN 0
+#define CTK_FILTER_EDGES_RENORM 1
+int ctk_filter_layout(int64_t T, int K, int64_t stride, int64_t offset, const int64_t *starts, int64_t nseg, int64_t *first_out, int64_t *out_starts,
+                      int64_t *T_out);
+int ctk_filter_f32_dev(ctk_handle *h, const float *x_dev, int64_t T, int ny, int nx, const double *w, int K, int64_t stride, int64_t offset, int edges,
+                       int skipna, const int64_t *starts, int64_t nseg, float *out_dev, int64_t T_out);
+int ctk_filter_f64_dev(ctk_handle *h, const double *x_dev, int64_t T, int ny, int nx, const double *w, int K, int64_t stride, int64_t offset, int edges,
+                       int skipna, const int64_t *starts, int64_t nseg, double *out_dev, int64_t T_out);
+int ctk_filter_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, const double *w, int K, int64_t stride, int64_t offset, int edges, int skipna,
+                   const int64_t *starts, int64_t nseg, float *out, int64_t T_out, int64_t chunk_steps, int keep_resident);
+int ctk_filter_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, const double *w, int K, int64_t stride, int64_t offset, int edges, int skipna,
+                   const int64_t *starts, int64_t nseg, double *out, int64_t T_out, int64_t chunk_steps, int keep_resident);
+int ctk_filter_stream_cb(ctk_handle *h, int elem_bytes /* 4: float32, 8: float64 */, int64_t T, int ny, int nx, ctk_read_chunk_fn reader, void *reader_user,
+                         const double *w, int K, int64_t stride, int64_t offset, int edges, int skipna, const int64_t *starts, int64_t nseg,
+                         ctk_write_values_fn writer, void *writer_user, int64_t T_out, int64_t chunk_steps, int keep_resident);
+int ctk_filter_resident(ctk_handle *h, const double *w, int K, int64_t stride, int64_t offset, int edges, int skipna, const int64_t *starts, int64_t nseg,
+                        void *out, int64_t T_out, int keep_resident);
+
 #ifdef __cplusplus
 }
 #endif

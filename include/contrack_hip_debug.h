@@ -219,6 +219,25 @@ int ctk_debug_set_anom(ctk_handle *h, int64_t waves_wanted, int64_t grid_y_max);
  * output step launches nothing) */
 int ctk_debug_anom_launch(ctk_handle *h, int64_t *out8);
 
+/* what ctk_filter_plan (csrc/ctk_forms.h) decides for nout outputs of a plane of npix pixels, K taps at `stride` (host only: no handle,
+ * no GPU); waves_wanted / grid_y_max: 0 the rule's 16 384 and 65 535, or a test's values (a waves_wanted of a test's also drops the rule's
+ * shortest tiles: 1 << 40 gives one output per workgroup, 1 the longest tile); forced: -1 the rule's form, 0 the plain form,
+ * 1 the LDS ring where one fits; out6 = { form (1 k_filter_ring, 0 k_filter_plain), threads per workgroup, dynamic LDS in bytes, tile
+ * (outputs per workgroup), gridDim.x, gridDim.y } */
+int ctk_debug_filter_plan(int elem_bytes, int K, int64_t stride, int64_t nout, int64_t npix, int64_t waves_wanted, int64_t grid_y_max, int forced, int64_t *out6);
+/* test hook for the following filter launches of ctk_filter_* on this handle: the same three values (negative waves_wanted / grid_y_max
+ * and a form outside -1 .. 1: refused), so that a small slab reaches the tile edges and every form */
+int ctk_debug_set_filter(ctk_handle *h, int64_t waves_wanted, int64_t grid_y_max, int forced);
+/* test hook: out9 = { form, threads, tile, gridDim.x, gridDim.y, LDS bytes, o0, o1 } of the last filter launch on this handle (outputs
+ * [o0, o1); form -1: none yet), then the number of launches the last ctk_filter_* call made (a streamed chunk that completes no output
+ * launches nothing) */
+int ctk_debug_filter_launch(ctk_handle *h, int64_t *out9);
+/* measurement (tools/filter_probe.py) on slabs in device memory, one segment: the filter kernel alone between HIP events, one launch
+ * that is not counted, then `reps` timed ones; copy_bytes > 0: the plain 16-byte copy kernel over that many bytes of the same two
+ * buffers instead; ms2 = { best, mean } */
+int ctk_debug_time_filter(ctk_handle *h, const void *x_dev, int is_f64, int64_t T, int ny, int nx, const double *w, int K, int64_t stride, int64_t offset,
+                          int edges, int skipna, void *out_dev, int64_t T_out, int64_t copy_bytes, int reps, double *ms2);
+
 /* what ctk_pfield_plan (csrc/ctk_forms.h) decides for keys of `keybytes` (4 / 8) bytes, a longest pool of max_pool_steps timesteps,
  * ngroups and window: out4 = { form (0 direct, 1 ring), the ring form's cap in pool timesteps, pixels per workgroup, bytes of the ring
  * (0: direct form) }.  Host only: no handle, no GPU. */
