@@ -4,8 +4,9 @@
 //       resident in HBM for run_contrack (ctk_track_resident): the producer of the hot path's input no longer pays PCIe twice.
 //   N3  the percentile threshold of README.rst:150-151: per grid point of a latitude band the q-quantile over time (exact
 //       order statistics by radix selection, numpy's linear interpolation), then the mean over the band.
-//       Over independent time segments (members, seasons) and streamed through chunk-sized buffers: ctk_anom_seg.hip, which launches
-//       k_clim_raw / k_clim_roll from here unchanged and replaces k_anom by a form that reads every input once per tile.
+//       The entries (ctk_anom_*, over independent time segments, streamed through chunk-sized buffers) are in ctk_anom_seg.hip, which
+//       launches k_clim_raw / k_clim_roll from here unchanged: ctk_anom_* is its host path with no segments and k_anom from here, the
+//       segmented entries replace k_anom by a form that reads every input once per tile.
 // The reference evaluates these with xarray, which cannot be installed in the build container: what is implemented is the
 // numpy restatement in oracle/anom_port.py (PARITY UNPINNED, see its header); sums in float64, results rounded to the input's
 // dtype where xarray keeps it.
@@ -141,8 +142,8 @@ static int pctl_slab(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx,
         HIPCHK(hipMemcpyAsync(h->io_in.p, x_host, bytes, hipMemcpyHostToDevice, h->stream));
         *x_dev = (const VT *)h->io_in.p;
     } else {
-        if (h->an_T != T || h->an_ny != ny || h->an_nx != nx || h->an_f64 != (sizeof(VT) == 8)) return ctk_set_error(CTK_E_STATE, "%s: no matching anomaly slab is resident", who);
-        *x_dev = (const VT *)h->an_out.p;
+        *x_dev = (const VT *)h->an_slab.find(T, ny, nx, sizeof(VT) == 8);
+        if (!*x_dev) return ctk_set_error(CTK_E_STATE, "%s: no matching anomaly slab is resident", who);
     }
     return CTK_OK;
 }
@@ -165,76 +166,13 @@ static void launch_quantile(ctk_handle *h, const VT *x_dev, int64_t T, int64_t n
     k_nanmean<<<1, 1024, 0, h->stream>>>(qv, nband, qv + nband);
 }
 
-template <typename VT>
-static int anom_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
-                     const VT *clim_in, VT *anom_out, VT *clim_out, int keep_resident)
-{
-    if (!h || !x_host || !group || T < 1 || ny < 1 || nx < 1 || ngroups < 1 || window < 1 || smooth < 1 || (!anom_out && !clim_out && !keep_resident))
-        return ctk_set_error(CTK_E_INVALID, "ctk_anom: bad arguments");
-    for (int64_t t = 0; t < T; t++) if (group[t] < 0 || group[t] >= ngroups) return ctk_set_error(CTK_E_INVALID, "ctk_anom: group[%lld] = %d outside 0..%d", (long long)t, group[t], ngroups - 1);
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    const int64_t npix = (int64_t)ny * nx;
-    const size_t esz = sizeof(VT), n = (size_t)T * (size_t)npix;
-    CTKCHK(claim_io(h, h->io_in, n * esz));
-    CTKCHK(ensure(h, h->an_clim, (size_t)ngroups * npix * esz));
-    h->an_pct_n = -1;                                                  // (an_raw is overwritten below)
-    CTKCHK(ensure(h, h->an_raw, (size_t)ngroups * npix * esz));
-    CTKCHK(ensure(h, h->an_idx, ((size_t)2 * T + ngroups + 2) * 4));
-    HIPCHK(hipMemcpy(h->io_in.p, x_host, n * esz, hipMemcpyHostToDevice));
-    // timesteps sorted by group, group offsets, group of every timestep
-    std::vector<int32_t> idx((size_t)2 * T + ngroups + 1);
-    int32_t *tlist = idx.data(), *goff = tlist + T, *grp = goff + ngroups + 1;
-    steps_by_group(group, T, ngroups, tlist, goff);
-    memcpy(grp, group, (size_t)T * 4);
-    HIPCHK(hipMemcpy(h->an_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
-    const int32_t *d_tlist = P<int32_t>(h->an_idx), *d_goff = d_tlist + T, *d_grp = d_goff + ngroups + 1;
-    const unsigned gx = (unsigned)((npix + 255) / 256);
-    if (clim_in) {
-        HIPCHK(hipMemcpy(h->an_clim.p, clim_in, (size_t)ngroups * npix * esz, hipMemcpyHostToDevice));
-    } else {
-        k_clim_raw<VT><<<dim3(gx, (unsigned)ngroups), 256, 0, s>>>((const VT *)h->io_in.p, d_tlist, d_goff, npix, (VT *)h->an_raw.p);
-        k_clim_roll<VT><<<dim3(gx, (unsigned)std::min(ngroups, 64)), 256, 0, s>>>((const VT *)h->an_raw.p, ngroups, window, npix, (VT *)h->an_clim.p);
-        HIPCHK(hipGetLastError());
-    }
-    if (clim_out) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipMemcpy(clim_out, h->an_clim.p, (size_t)ngroups * npix * esz, hipMemcpyDeviceToHost)); }
-    if (anom_out || keep_resident) {
-        h->an_T = -1; h->an_gen++;                                     // the resident slab (if any) is being overwritten
-        CTKCHK(ensure(h, h->an_out, n * esz));                         // (only here: a climatology-only call leaves an_out alone)
-        const int tseg = 32;
-        k_anom<VT><<<dim3(gx, (unsigned)((T + tseg - 1) / tseg)), 256, 0, s>>>((const VT *)h->io_in.p, (const VT *)h->an_clim.p, d_grp, T, npix, smooth, tseg,
-                                                                             (VT *)h->an_out.p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
-        h->an_T = T; h->an_ny = ny; h->an_nx = nx; h->an_f64 = sizeof(VT) == 8;
-        if (anom_out) {
-            if (!h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
-            if (!h->bounce || !bounce_copy(*h->bounce, h->device, h->an_out.p, anom_out, n * esz, false))
-                HIPCHK(hipMemcpy(anom_out, h->an_out.p, n * esz, hipMemcpyDeviceToHost));
-        }
-    }
-    if ((anom_out || keep_resident) && !keep_resident) h->an_T = -1;      // (a climatology-only call leaves an earlier resident slab alone)
-    return CTK_OK;
-}
-
-extern "C" int ctk_anom_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
-                            const float *clim_in, float *anom_out, float *clim_out, int keep_resident)
-{
-    return anom_impl<float>(h, x, T, ny, nx, group, ngroups, window, smooth, clim_in, anom_out, clim_out, keep_resident);
-}
-extern "C" int ctk_anom_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
-                            const double *clim_in, double *anom_out, double *clim_out, int keep_resident)
-{
-    return anom_impl<double>(h, x, T, ny, nx, group, ngroups, window, smooth, clim_in, anom_out, clim_out, keep_resident);
-}
-
 // WHICH slab is resident: a number that changes whenever the resident slab is written (any ctk_anom_* call that produces
 // anomalies) or dropped (ctk_release_io).  A caller that left a slab resident remembers the number and runs on the slab only
 // while it is unchanged -- two class instances sharing one handle cannot take each other's anomalies for their own.
 extern "C" int ctk_resident_anom_generation(ctk_handle *h, uint64_t *generation)
 {
     if (!h || !generation) return ctk_set_error(CTK_E_INVALID, "null argument");
-    *generation = h->an_gen;
+    *generation = h->an_slab.gen;
     return CTK_OK;
 }
 
@@ -242,10 +180,7 @@ extern "C" int ctk_resident_anom_generation(ctk_handle *h, uint64_t *generation)
 extern "C" int ctk_resident_anom(ctk_handle *h, int64_t *T, int *ny, int *nx, int *is_f64)
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
-    if (T) *T = h->an_T;
-    if (ny) *ny = h->an_ny;
-    if (nx) *nx = h->an_nx;
-    if (is_f64) *is_f64 = h->an_f64 ? 1 : 0;
+    h->an_slab.report(T, ny, nx, is_f64);
     return CTK_OK;
 }
 
@@ -254,9 +189,10 @@ extern "C" int ctk_track_resident(ctk_handle *h, const double *thr, int cmp_op, 
                                   int32_t *flag, int64_t *n_tracked)
 {
     if (!h || !flag) return ctk_set_error(CTK_E_INVALID, "null argument");
-    if (h->an_T < 1) return ctk_set_error(CTK_E_STATE, "ctk_track_resident: no anomaly slab is resident (ctk_anom_* with keep_resident)");
+    const ResidentSlab &a = h->an_slab;
+    if (!a.held()) return ctk_set_error(CTK_E_STATE, "ctk_track_resident: no anomaly slab is resident (ctk_anom_* with keep_resident)");
     HIPCHK(hipSetDevice(h->device));
-    return track_to_host(h, h->an_out.p, h->an_f64, h->an_T, h->an_ny, h->an_nx, thr, cmp_op, wrow, overlap, persistence, twosided, flag, n_tracked, nullptr);
+    return track_to_host(h, a.buf.p, a.f64, a.T, a.ny, a.nx, thr, cmp_op, wrow, overlap, persistence, twosided, flag, n_tracked, nullptr);
 }
 
 template <typename VT, typename KT>

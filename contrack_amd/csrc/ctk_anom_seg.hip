@@ -1,8 +1,10 @@
-// ctk_anom_seg.hip -- calc_clim / calc_anom (row N2, ctk_anom.hip) over independent time segments, resident and streamed (included by
-// ctk_api.hip).  The climatology is the one of ctk_anom_*: pooled over every timestep of a group whatever its segment.  The smoothing
-// stays inside a segment: anom[t] is the mean over the centred window of `smooth` steps only if that window lies inside t's segment,
-// else NaN -- as ctk_anom_* gives where the window leaves the axis.  Sums and rounding places are k_anom's, so one segment gives
-// ctk_anom_*'s bits.
+// ctk_anom_seg.hip -- the entries of calc_clim / calc_anom (row N2, ctk_anom.hip): one host slab (ctk_anom_*), over independent time
+// segments, resident and streamed (included by ctk_api.hip).  The climatology is pooled over every timestep of a group whatever its
+// segment.  The smoothing stays inside a segment: anom[t] is the mean over the centred window of `smooth` steps, each raw anomaly
+// rounded to the slab's type and added in float64 in rising step order, only if that window lies inside t's segment, else NaN.
+// ctk_anom_* is the same host path with no segments -- one, the whole axis: NaN where the window leaves the axis -- so it takes at
+// most 2^31 - 1 steps, as every entry on a slab in HBM does (anom_seg_args).  It launches k_anom (ctk_anom.hip), which needs no
+// segment test; sums and rounding places here are k_anom's, so one segment gives ctk_anom_*'s bits.
 //
 // k_anom_ring: one thread per pixel and tile of output steps.  The thread walks the steps its tile needs once (tile + smooth - 1 of
 // them), computes each raw anomaly x[j] - clim[group[j]] once and keeps the last `smooth` of them in a ring in LDS (slot k of lane l at
@@ -158,16 +160,16 @@ static int launch_anom_seg(ctk_handle *h, const VT *x, int64_t xbase, int64_t xl
     return CTK_OK;
 }
 
-// ctk_anom_* with segments on a slab in device memory (anom_impl's steps, the anomaly kernel replaced): the uploaded copy of a host
-// slab (anom_seg_impl), or the resident vertical mean (ctk_anom_seg_resident, ctk_level.hip); the caller has checked the arguments
-// (anom_seg_args)
+// climatology and anomalies of a slab in device memory: the uploaded copy of a host slab (anom_seg_impl), or the resident vertical
+// mean (ctk_anom_seg_resident, ctk_level.hip); the caller has checked the arguments (anom_seg_args).  whole_axis: ctk_anom_* -- no
+// segments are given and the anomalies come from k_anom (ctk_anom.hip) instead of the planned form
 template <typename VT>
 static int anom_seg_dev(ctk_handle *h, const VT *x_dev, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
-                        const VT *clim_in, VT *anom_out, VT *clim_out, int keep_resident, const int64_t *starts, int64_t nseg)
+                        const VT *clim_in, VT *anom_out, VT *clim_out, int keep_resident, const int64_t *starts, int64_t nseg, bool whole_axis = false)
 {
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    h->an_launches = 0;
+    if (!whole_axis) h->an_launches = 0;                               // (ctk_anom_* leaves what ctk_debug_anom_launch reports alone)
     const int64_t npix = (int64_t)ny * nx;
     const size_t esz = sizeof(VT), n = (size_t)T * (size_t)npix, cb = (size_t)ngroups * npix * esz;
     CTKCHK(ensure(h, h->an_clim, cb));
@@ -191,45 +193,60 @@ static int anom_seg_dev(ctk_handle *h, const VT *x_dev, int64_t T, int ny, int n
     }
     if (clim_out) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipMemcpy(clim_out, h->an_clim.p, cb, hipMemcpyDeviceToHost)); }
     if (anom_out || keep_resident) {
-        std::vector<uint8_t> valid;
-        anom_window_valid(starts, nseg, T, smooth, valid);
-        HIPCHK(hipMemcpy(h->an_valid.p, valid.data(), (size_t)T, hipMemcpyHostToDevice));
-        h->an_T = -1; h->an_gen++;                                     // the resident slab (if any) is being overwritten
-        CTKCHK(ensure(h, h->an_out, n * esz));                         // (only here: a climatology-only call leaves an_out alone)
-        CTKCHK(launch_anom_seg<VT>(h, x_dev, 0, 0, T, (const VT *)h->an_clim.p, d_grp, P<uint8_t>(h->an_valid), npix, smooth, 0, T, (VT *)h->an_out.p));
-        HIPCHK(hipStreamSynchronize(s));
-        if (keep_resident) { h->an_T = T; h->an_ny = ny; h->an_nx = nx; h->an_f64 = sizeof(VT) == 8; }
-        if (anom_out) {
-            if (!h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
-            if (!h->bounce || !bounce_copy(*h->bounce, h->device, h->an_out.p, anom_out, n * esz, false))
-                HIPCHK(hipMemcpy(anom_out, h->an_out.p, n * esz, hipMemcpyDeviceToHost));
+        DevBuf &out = h->an_slab.buf;
+        h->an_slab.drop();                                             // the resident slab (if any) is being overwritten
+        CTKCHK(ensure(h, out, n * esz));                               // (only here: a climatology-only call leaves the slab alone)
+        if (whole_axis) {                                              // (0.7 % ahead of the ring form at smooth 1 on 0.25 degree planes: profiles/NOTES.md)
+            const int tseg = 32;
+            k_anom<VT><<<dim3(gx, (unsigned)((T + tseg - 1) / tseg)), 256, 0, s>>>(x_dev, (const VT *)h->an_clim.p, d_grp, T, npix, smooth, tseg, (VT *)out.p);
+            HIPCHK(hipGetLastError());
+        } else {
+            std::vector<uint8_t> valid;
+            anom_window_valid(starts, nseg, T, smooth, valid);
+            HIPCHK(hipMemcpy(h->an_valid.p, valid.data(), (size_t)T, hipMemcpyHostToDevice));
+            CTKCHK(launch_anom_seg<VT>(h, x_dev, 0, 0, T, (const VT *)h->an_clim.p, d_grp, P<uint8_t>(h->an_valid), npix, smooth, 0, T, (VT *)out.p));
         }
+        HIPCHK(hipStreamSynchronize(s));
+        if (keep_resident) h->an_slab.keep(T, ny, nx, sizeof(VT) == 8);
+        if (anom_out) CTKCHK(download(h, out.p, anom_out, n * esz));
     }
     return CTK_OK;
 }
 
+// a host slab: uploaded into io_in, then anom_seg_dev.  who: the entry, as its messages name it
 template <typename VT>
-static int anom_seg_impl(ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
-                         const VT *clim_in, VT *anom_out, VT *clim_out, int keep_resident, const int64_t *starts, int64_t nseg)
+static int anom_seg_impl(const char *who, ctk_handle *h, const VT *x_host, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                         const VT *clim_in, VT *anom_out, VT *clim_out, int keep_resident, const int64_t *starts, int64_t nseg, bool whole_axis = false)
 {
-    if (h && (!x_host || (!anom_out && !clim_out && !keep_resident))) return ctk_set_error(CTK_E_INVALID, "ctk_anom_seg: bad arguments");
-    CTKCHK(anom_seg_args("ctk_anom_seg", h, T, ny, nx, group, ngroups, window, smooth, starts, nseg));
+    if (h && (!x_host || (!anom_out && !clim_out && !keep_resident))) return ctk_set_error(CTK_E_INVALID, "%s: bad arguments", who);
+    CTKCHK(anom_seg_args(who, h, T, ny, nx, group, ngroups, window, smooth, starts, nseg));
     HIPCHK(hipSetDevice(h->device));
     const size_t bytes = (size_t)T * (size_t)ny * (size_t)nx * sizeof(VT);
     CTKCHK(claim_io(h, h->io_in, bytes));
     HIPCHK(hipMemcpy(h->io_in.p, x_host, bytes, hipMemcpyHostToDevice));
-    return anom_seg_dev<VT>(h, (const VT *)h->io_in.p, T, ny, nx, group, ngroups, window, smooth, clim_in, anom_out, clim_out, keep_resident, starts, nseg);
+    return anom_seg_dev<VT>(h, (const VT *)h->io_in.p, T, ny, nx, group, ngroups, window, smooth, clim_in, anom_out, clim_out, keep_resident, starts, nseg, whole_axis);
 }
 
+// ctk_anom_*: no segments (one, the whole axis).  T above 2^31 - 1 is refused (anom_seg_args): the step lists are int32
+extern "C" int ctk_anom_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                            const float *clim_in, float *anom_out, float *clim_out, int keep_resident)
+{
+    return anom_seg_impl<float>("ctk_anom", h, x, T, ny, nx, group, ngroups, window, smooth, clim_in, anom_out, clim_out, keep_resident, nullptr, 0, true);
+}
+extern "C" int ctk_anom_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
+                            const double *clim_in, double *anom_out, double *clim_out, int keep_resident)
+{
+    return anom_seg_impl<double>("ctk_anom", h, x, T, ny, nx, group, ngroups, window, smooth, clim_in, anom_out, clim_out, keep_resident, nullptr, 0, true);
+}
 extern "C" int ctk_anom_seg_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
                                 const float *clim_in, float *anom_out, float *clim_out, int keep_resident, const int64_t *starts, int64_t nseg)
 {
-    return anom_seg_impl<float>(h, x, T, ny, nx, group, ngroups, window, smooth, clim_in, anom_out, clim_out, keep_resident, starts, nseg);
+    return anom_seg_impl<float>("ctk_anom_seg", h, x, T, ny, nx, group, ngroups, window, smooth, clim_in, anom_out, clim_out, keep_resident, starts, nseg);
 }
 extern "C" int ctk_anom_seg_f64(ctk_handle *h, const double *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
                                 const double *clim_in, double *anom_out, double *clim_out, int keep_resident, const int64_t *starts, int64_t nseg)
 {
-    return anom_seg_impl<double>(h, x, T, ny, nx, group, ngroups, window, smooth, clim_in, anom_out, clim_out, keep_resident, starts, nseg);
+    return anom_seg_impl<double>("ctk_anom_seg", h, x, T, ny, nx, group, ngroups, window, smooth, clim_in, anom_out, clim_out, keep_resident, starts, nseg);
 }
 
 // test hook: the kernel form of the last ctk_anom_seg_* / ctk_anom_stream_* launch on this handle (CtkAnomForm; -1: none yet)
@@ -321,34 +338,15 @@ static int anom_stream_impl(ctk_handle *h, StreamIO &io, int64_t T, int ny, int 
         anom_window_valid(starts, nseg, T, smooth, valid);
         CTKCHK(ensure(h, h->an_valid, (size_t)T));
         HIPCHK(hipMemcpy(h->an_valid.p, valid.data(), (size_t)T, hipMemcpyHostToDevice));
-        // pass 2 (stream_produce): the chunks pass through two windows [smooth - 1 steps kept from the chunk before | chunk] in io_in
-        // and two output buffers in io_out
-        const int64_t halo = smooth - 1, fwd = (smooth - 1) / 2;
-        int64_t o_done = 0;
-        Producer p;
-        p.in_bytes = (size_t)(io.chunk + halo) * plane; p.out_step = plane;
-        p.upload = [&](const ProduceIn &c) -> int {
-            const char *src = c.src ? c.src : (const char *)io.host_in + (size_t)c.c0 * plane;
-            HIPCHK(hipMemcpyAsync(c.dev + (size_t)halo * plane, src, (size_t)c.nt * plane, hipMemcpyHostToDevice, h->copy_stream));
-            return CTK_OK;
-        };
-        p.launch = [&](const ProduceIn &c, ProduceOut &o) -> int {
-            // steps [c0 - halo, c0 + nt) are in the window now (the first chunk has nothing in front of it): the outputs whose window
-            // ends inside them, and everything that is left once the last chunk is there
-            const bool last = c.c0 + c.nt == T;
-            const int64_t xlo = c.c0 == 0 ? 0 : c.c0 - halo, o0 = o_done, o1 = last ? T : std::max<int64_t>(o_done, c.c0 + c.nt - fwd);
-            if (o1 > o0) {
-                o.t0 = o0; o.nt = o1 - o0; o.dev = (char *)h->io_out.p + (size_t)c.b * (size_t)(io.chunk + smooth) * plane;
-                CTKCHK(launch_anom_seg<VT>(h, (const VT *)c.dev, c.c0 - halo, xlo, c.c0 + c.nt, (const VT *)h->an_clim.p, d_grp, P<uint8_t>(h->an_valid), npix, smooth,
-                                           o0, o1, (VT *)o.dev));
-            }
-            // the last `halo` steps in front of the next chunk (a chunk that is not the last has nt == chunk >= halo steps: they lie in its body)
-            if (!last && halo > 0)
-                HIPCHK(hipMemcpyAsync((char *)h->io_in.p + (size_t)(c.b ^ 1) * p.in_bytes, c.dev + (size_t)c.nt * plane, (size_t)halo * plane, hipMemcpyDeviceToDevice, h->stream));
-            o_done = o1;
-            return CTK_OK;
-        };
-        rc = stream_produce(h, io, T, name, p);
+        // pass 2 (window_produce): windows of smooth - 1 kept steps and a chunk in io_in, two output buffers in io_out.  Complete
+        // once the steps below `end` are there: the outputs whose window ends below it, and everything once the last chunk is there
+        const int64_t fwd = (smooth - 1) / 2;
+        rc = window_produce(
+            h, io, T, smooth - 1, plane, name, [&](int64_t end, int64_t from) { return end >= T ? T : std::max(from, end - fwd); },
+            [&](int b, int64_t) { return (char *)h->io_out.p + (size_t)b * (size_t)(io.chunk + smooth) * plane; },
+            [&](const char *win, int64_t xbase, int64_t xlo, int64_t xhi, int64_t o0, int64_t o1, char *out) {
+                return launch_anom_seg<VT>(h, (const VT *)win, xbase, xlo, xhi, (const VT *)h->an_clim.p, d_grp, P<uint8_t>(h->an_valid), npix, smooth, o0, o1, (VT *)out);
+            });
     }
     return stream_produce_end(h, io, rc, t_call);
 }

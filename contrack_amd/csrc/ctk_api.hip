@@ -226,6 +226,33 @@ struct LaunchKnobs {
     void launched(int f, int64_t g) { form = f; grid = g; }
 };
 
+// A slab that stays in HBM between calls (the field to track, the vertical mean): its buffer, the shape and type of what the buffer
+// holds (T = -1: nothing) and a generation that says WHICH slab that is -- a caller that left one remembers the number and reads the
+// slot only while it is unchanged.  The rule stands here and nowhere else: drop() BEFORE the buffer is overwritten, keep() AFTER the
+// kernels that filled it have been synchronised, find() / held() before it is read.
+struct ResidentSlab {
+    DevBuf buf;
+    int64_t T = -1; int ny = 0, nx = 0; bool f64 = false;
+    uint64_t gen = 0;
+    void drop() { T = -1; gen++; }                 // the slab, if any, is gone or about to be overwritten
+    void keep(int64_t T_, int ny_, int nx_, bool f64_) { T = T_; ny = ny_; nx = nx_; f64 = f64_; }       // (the generation is the preceding drop()'s)
+    bool held() const { return T >= 1 && buf.p; }
+    void *find(int64_t T_, int ny_, int nx_, bool f64_) const                     // null: nothing of exactly this shape and type is held
+    {
+        return held() && T == T_ && ny == ny_ && nx == nx_ && f64 == f64_ ? buf.p : nullptr;
+    }
+    void report(int64_t *T_, int *ny_, int *nx_, int *is_f64) const               // the ctk_resident_* getters (T = -1: none)
+    {
+        if (T_) *T_ = T;
+        if (ny_) *ny_ = ny;
+        if (nx_) *nx_ = nx;
+        if (is_f64) *is_f64 = f64 ? 1 : 0;
+    }
+    // the finished result in `other` becomes the slab (T_ < 1: none), `other` gets the old buffer as scratch
+    void adopt(DevBuf &other, int64_t T_, int ny_, int nx_, bool f64_) { buf.swap(other); gen++; keep(T_ >= 1 ? T_ : -1, ny_, nx_, f64_); }
+    void release() { buf.release(); drop(); }
+};
+
 // Every GPU resource below is an owner of ctk_own.h and goes with the handle: ctk_destroy names none of them.  Members are destroyed
 // in reverse order of declaration, so the streams stay declared ahead of everything that is enqueued on them.
 struct ctk_handle {
@@ -256,8 +283,8 @@ struct ctk_handle {
     // run_lifecycle reductions
     DevBuf lc_rows, lc_cnt, lc_wlo, lc_whi, lc_w, lc_work, lc_ovf, lc_ekeys, lc_offs, lc_sw, lc_sp, lc_out, lc_cross, lc_gtab, lc_occ, lc_cp;
     const int32_t *lc_flag = nullptr; const void *lc_field = nullptr;       // slabs of the last ctk_lifecycle_* call (for the exact rows)
-    // ... which live in io_out / io_in (or an_out) after a host-array call: lc_own 1, lc_own 2 with the resident anomaly slab as the field;
-    // then ctk_lifecycle_exact reads them only while io_gen (and an_gen) are what the call left.  0: the caller's own device pointers
+    // ... which live in io_out / io_in (or an_slab) after a host-array call: lc_own 1, lc_own 2 with the resident anomaly slab as the field;
+    // then ctk_lifecycle_exact reads them only while io_gen (and an_slab.gen) are what the call left.  0: the caller's own device pointers
     int lc_own = 0; uint64_t lc_io_gen = 0, lc_an_gen = 0;
     bool lc_f64 = false; int64_t lc_T = 0; int lc_ny = 0, lc_nx = 0;
     // which path the time steps of the last ctk_lifecycle_* call took (ctk_debug_lifecycle_path); lc_path_T < 0: no finished call
@@ -284,24 +311,23 @@ struct ctk_handle {
     bool fz_init = false;                          // k_compact_init ran (the resolver arrays are initialised), k_overlap prepared the pair arrays
     bool in_one_call = false;                      // inside ctk_track_*_dev (the staged entries never take the fused path)
     bool guard_on = false;                         // kernels behind the resolver check the device counters before touching the tables
-    // calc_anom / percentile (ctk_anom.hip): resident anomaly slab, climatology, scratch
-    DevBuf an_out, an_clim, an_raw, an_idx;
+    // calc_anom / percentile (ctk_anom.hip): the resident field to track (anomalies, reversal index, wave activity), climatology, scratch
+    ResidentSlab an_slab;
+    DevBuf an_clim, an_raw, an_idx;
     DevBuf an_acc, an_valid;                       // ctk_anom_stream_*: float64 sums + int32 counts per (group, pixel); ctk_anom_seg_*: window-inside-segment per step
     int an_form = -1;                              // kernel form the last ctk_anom_seg_* / ctk_anom_stream_* call took (CtkAnomForm; -1: none yet)
     int64_t an_waves_dbg = 0, an_gy_dbg = 0;       // ctk_debug_set_anom: waves_wanted / grid_y_max of ctk_anom_plan for the launches (0: the rule's)
     int64_t an_last[6] = {0, 0, 0, 0, 0, 0};       // the last launch_anom_seg: tile, gx, gy, lds, o0, o1 ...
     int64_t an_launches = 0;                       // ... and how many of them the last ctk_anom_seg_* / ctk_anom_stream_* call made
-    int64_t an_T = -1; int an_ny = 0, an_nx = 0; bool an_f64 = false;
-    uint64_t an_gen = 0;                           // bumped whenever the resident slab is written or dropped: WHICH slab is resident
     int64_t an_pct_n = -1;                         // an_raw holds the per-pixel quantiles of the last ctk_percentile_* call (-1: it does not)
-    // vertical mean (ctk_level.hip): the resident mean slab in a buffer of its own (io_in is reused by every tracking call), the table
-    // of weights and level indices of the running call
-    DevBuf lv_out, lv_tab;
-    int64_t lv_T = -1; int lv_ny = 0, lv_nx = 0; bool lv_f64 = false;
-    uint64_t lv_gen = 0;                           // bumped by every ctk_level_mean_* call and by ctk_release_io: WHICH mean is resident
+    // vertical mean (ctk_level.hip): the resident mean slab in a buffer of its own (io_in is reused by every tracking call; its
+    // generation changes with every ctk_level_mean_* call, every kept filter result and ctk_release_io), the table of weights and
+    // level indices of the running call
+    ResidentSlab lv_slab;
+    DevBuf lv_tab;
     LaunchKnobs lv_knobs;                          // the k_level_mean launches (form: 1 vector, 0 scalar); ctk_debug_set_level
     // time filter (ctk_filter.hip): the table of the running call (K float64 weights, then one CtkFilterTap per output); the result of
-    // a call that keeps it or reads the resident mean, which then changes owner with lv_out (never filtered in place)
+    // a call that keeps it or reads the resident mean, which the slot then adopts (never filtered in place)
     DevBuf fl_tab, fl_out;
     int64_t fl_waves_dbg = 0, fl_gy_dbg = 0; int fl_form_dbg = -1;       // ctk_debug_set_filter: ctk_filter_plan's waves_wanted / grid_y_max / forced
     int64_t fl_last[8] = {-1, 0, 0, 0, 0, 0, 0, 0};                      // the last launch_filter: form, threads, tile, gx, gy, lds, o0, o1 ...
@@ -2928,6 +2954,15 @@ bool bounce_copy(BouncePool &pool, int device, void *dev, void *host, size_t byt
 }
 }  // namespace
 
+// a finished result from device memory into the caller's host array: the bounce lanes; plain hipMemcpy for small results / if the lanes fail
+static int download(ctk_handle *h, const void *dev, void *host, size_t bytes)
+{
+    if (!h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
+    if (!h->bounce || !bounce_copy(*h->bounce, h->device, const_cast<void *>(dev), host, bytes, false))
+        HIPCHK(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
+    return CTK_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // The result of a host-array entry over PCIe.  The device pass ends with the value of every foreground RUN (k_run_values) and the
 // bit mask the runs were cut from: 30 MB at 2707 x 181 x 360, where the dense int32 slab k_relabel would write is 706 MB -- 12.4 ms
@@ -3196,13 +3231,7 @@ static int track_to_host(ctk_handle *h, const void *a_dev, bool f64, int64_t T, 
         }
         break;
     }
-    // the parallel copy; plain hipMemcpy for small results / if the lanes fail
-    if (!h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
-    if (!h->bounce || !bounce_copy(*h->bounce, h->device, f_dev, flag, n * 4, false)) {
-        hipError_t e = hipMemcpy(flag, f_dev, n * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return ctk_set_error(CTK_E_NODEVICE, "D2H copy failed: %s", hipGetErrorString(e));
-    }
-    return CTK_OK;
+    return download(h, f_dev, flag, n * 4);
 }
 
 static int track_host_impl(ctk_handle *h, const void *anom, bool f64, int64_t T, int ny, int nx, const double *thr, int cmp_op, const float *wrow,
@@ -3455,7 +3484,7 @@ static void zero_other_rows(void *out, int64_t steps, size_t plane, size_t off, 
 // plane and writes zeros outside its rows [a0, a1).  Of a host array only rows [r0, r1) of every plane travel to the device (one
 // strided copy per chunk, the plane as pitch) and only rows [a0, a1) travel back; the rest of the output array is zeroed on the host.
 // The device chunks keep the full-plane layout, readers fill and writers get whole planes.  keep_resident: the full-plane result is
-// written into the resident slot of the field to track (an_out), where ctk_track_resident and the `resident` consumers find it.
+// written into the resident slot of the field to track (an_slab), where ctk_track_resident and the `resident` consumers find it.
 struct RowBands { int r0, r1, a0, a1; };
 
 // its argument checks, in the order the entries report them, and the chunk plan: io.esz and io.chunk are set, no buffer is touched
@@ -3479,8 +3508,8 @@ static int row_band_produce(ctk_handle *h, StreamIO &io, int64_t steps, int ny, 
     const size_t row = (size_t)nx * io.esz, plane = (size_t)ny * row;
     const double t_call = now_ms();
     CTKCHK(stream_setup(h, (size_t)io.chunk * plane, 0, io.read != nullptr));
-    if (keep_resident) { h->an_T = -1; h->an_gen++; h->an_pct_n = -1; }           // the resident slab (if any) is dropped or about to be overwritten
-    CTKCHK(produce_out_setup(h, io, h->an_out, steps, plane, keep_resident));
+    if (keep_resident) { h->an_slab.drop(); h->an_pct_n = -1; }
+    CTKCHK(produce_out_setup(h, io, h->an_slab.buf, steps, plane, keep_resident));
     CTKCHK(tables());
     const size_t in_off = (size_t)rb.r0 * row, in_w = (size_t)(rb.r1 - rb.r0) * row, out_off = (size_t)rb.a0 * row, out_w = (size_t)(rb.a1 - rb.a0) * row;
     // the rows of `out` that nothing is downloaded into are zeroed by a helper thread while the chunks travel (other bytes than the
@@ -3489,7 +3518,7 @@ static int row_band_produce(ctk_handle *h, StreamIO &io, int64_t steps, int ny, 
     if (io.host_out_v) zero.t = std::thread(zero_other_rows, io.host_out_v, steps, plane, out_off, out_w);
     // the chunks (stream_produce): io.host_in is the whole (steps, ny, nx) array (rows [r0, r1) of every plane travel), io.read a
     // reader of whole planes.  The results go to io.host_out_v (rows [a0, a1) of every plane) / io.write_v (whole planes) chunk by
-    // chunk and (keep) into an_out.
+    // chunk and (keep) into an_slab.
     Producer p;
     p.in_bytes = (size_t)io.chunk * plane; p.out_step = plane;
     p.upload = [&](const ProduceIn &c) -> int {
@@ -3501,7 +3530,7 @@ static int row_band_produce(ctk_handle *h, StreamIO &io, int64_t steps, int ny, 
     };
     p.launch = [&](const ProduceIn &c, ProduceOut &o) -> int {
         o.t0 = c.c0; o.nt = c.nt;
-        o.dev = produce_out_dev(h, io, h->an_out, c, plane, keep_resident);
+        o.dev = produce_out_dev(h, io, h->an_slab.buf, c, plane, keep_resident);
         return launch(c, o.dev);
     };
     if (out_w != plane)
@@ -3512,8 +3541,44 @@ static int row_band_produce(ctk_handle *h, StreamIO &io, int64_t steps, int ny, 
     const int rc = stream_produce(h, io, steps, name, p);
     if (zero.t.joinable()) zero.t.join();
     CTKCHK(stream_produce_end(h, io, rc, t_call));
-    if (keep_resident) { h->an_T = steps; h->an_ny = ny; h->an_nx = nx; h->an_f64 = io.esz == 8; }
+    if (keep_resident) h->an_slab.keep(steps, ny, nx, io.esz == 8);
     return CTK_OK;
+}
+
+// The windowed producer (pass 2 of ctk_anom_stream_*, ctk_filter_*): a kernel whose outputs read up to `halo` steps in front of their
+// chunk.  The chunks pass through two windows [halo steps kept from the chunk before | chunk] in io_in -- io.chunk >= halo, and the
+// caller's stream_setup gave each window (io.chunk + halo) * plane bytes --: a chunk is uploaded behind the halo and its last `halo`
+// steps are copied in front of the next one on the device, so the reader is never asked for a step twice.
+//   done_at(end, from)  the outputs, counted on from `from`, that are complete once the steps below `end` are there (end == steps: all)
+//   place(b, o0)        where the outputs from o0 on of the chunk in buffer b go
+//   launch              queues their kernel on the handle's stream: plane 0 of `window` is step xbase, its steps [xlo, xhi) may be
+//                       read, the outputs [o0, o1) go to `out`
+static int window_produce(ctk_handle *h, StreamIO &io, int64_t steps, int64_t halo, size_t plane, const char *name,
+                          const std::function<int64_t(int64_t end, int64_t from)> &done_at, const std::function<char *(int b, int64_t o0)> &place,
+                          const std::function<int(const char *window, int64_t xbase, int64_t xlo, int64_t xhi, int64_t o0, int64_t o1, char *out)> &launch)
+{
+    int64_t o_done = 0;
+    Producer p;
+    p.in_bytes = (size_t)(io.chunk + halo) * plane; p.out_step = plane;
+    p.upload = [&](const ProduceIn &c) -> int {
+        const char *src = c.src ? c.src : (const char *)io.host_in + (size_t)c.c0 * plane;
+        HIPCHK(hipMemcpyAsync(c.dev + (size_t)halo * plane, src, (size_t)c.nt * plane, hipMemcpyHostToDevice, h->copy_stream));
+        return CTK_OK;
+    };
+    p.launch = [&](const ProduceIn &c, ProduceOut &o) -> int {
+        // steps [c0 - halo, c0 + nt) are in the window now (the first chunk has nothing in front of it)
+        const int64_t xlo = c.c0 == 0 ? 0 : c.c0 - halo, o0 = o_done, o1 = done_at(c.c0 + c.nt, o_done);
+        if (o1 > o0) {
+            o.t0 = o0; o.nt = o1 - o0; o.dev = place(c.b, o0);
+            CTKCHK(launch(c.dev, c.c0 - halo, xlo, c.c0 + c.nt, o0, o1, o.dev));
+        }
+        // the last `halo` steps in front of the next chunk (a chunk that is not the last has nt == chunk >= halo steps: they lie in its body)
+        if (c.c0 + c.nt < steps && halo > 0)
+            HIPCHK(hipMemcpyAsync((char *)h->io_in.p + (size_t)(c.b ^ 1) * p.in_bytes, c.dev + (size_t)c.nt * plane, (size_t)halo * plane, hipMemcpyDeviceToDevice, h->stream));
+        o_done = o1;
+        return CTK_OK;
+    };
+    return stream_produce(h, io, steps, name, p);
 }
 
 // output phase: k_relabel writes chunk k+1 into one device buffer while chunk k leaves the other
@@ -3677,9 +3742,9 @@ extern "C" int ctk_release_io(ctk_handle *h)
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
     HIPCHK(hipSetDevice(h->device));
-    for (DevBuf *b : {&h->io_in, &h->io_out, &h->an_out, &h->an_raw, &h->lv_out, &h->fl_out, &h->gr_tab, &h->lw_tab, &h->lw_ref}) b->release();
-    h->an_T = -1; h->an_gen++; h->an_pct_n = -1;
-    h->lv_T = -1; h->lv_gen++;
+    for (DevBuf *b : {&h->io_in, &h->io_out, &h->an_raw, &h->fl_out, &h->gr_tab, &h->lw_tab, &h->lw_ref}) b->release();
+    h->an_slab.release(); h->an_pct_n = -1;
+    h->lv_slab.release();
     h->io_gen++; h->lc_flag = nullptr; h->lc_field = nullptr;          // (the exact rows of a lifecycle call read those slabs)
     h->bounce.reset();
     h->rle.reset();
@@ -3975,7 +4040,7 @@ static int lifecycle_dev_impl(ctk_handle *h, const int32_t *flag_dev, const void
     h->lc_plan = r.plan;
     r.cap = std::max<size_t>(h->lc_rows.cap / sizeof(CtkLifeRowDev), (size_t)T * 16 + 1024);
     h->lc_flag = flag_dev; h->lc_field = field_dev; h->lc_f64 = f64; h->lc_T = T; h->lc_ny = ny; h->lc_nx = nx;
-    h->lc_own = own; h->lc_io_gen = h->io_gen; h->lc_an_gen = h->an_gen;
+    h->lc_own = own; h->lc_io_gen = h->io_gen; h->lc_an_gen = h->an_slab.gen;
     int rc = life_launch(h, r);
     if (rc == CTK_OK) rc = life_settle(h, r);
     h->lc_attempts = r.attempts; h->lc_given_up = r.given_up; h->lc_fb_launches = r.fb_launches;
@@ -4015,7 +4080,7 @@ static int lifecycle_host_impl(ctk_handle *h, const int32_t *flag, const void *f
     if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
     if (T < 0 || ny < 1 || nx < 1 || (T > 0 && !flag)) return ctk_set_error(CTK_E_INVALID, "ctk_lifecycle: bad shape or null pointer");
     // field == NULL: the anomaly slab that ctk_anom_* left resident (no second trip over PCIe for it)
-    if (T > 0 && !field && !(h->an_T == T && h->an_ny == ny && h->an_nx == nx && h->an_f64 == f64 && h->an_out.p))
+    if (T > 0 && !field && !h->an_slab.find(T, ny, nx, f64))
         return ctk_set_error(CTK_E_STATE, "ctk_lifecycle: field = NULL needs a resident anomaly slab of this shape and type (ctk_anom_* with keep_resident)");
     HIPCHK(hipSetDevice(h->device));
     const size_t n = (size_t)T * ny * nx, esz = f64 ? 8 : 4;
@@ -4028,7 +4093,7 @@ static int lifecycle_host_impl(ctk_handle *h, const int32_t *flag, const void *f
             CTKCHK(claim_io(h, h->io_in, n * esz));
             v_dev = h->io_in.p;
             HIPCHK(hipMemcpy(v_dev, field, n * esz, hipMemcpyHostToDevice));
-        } else v_dev = h->an_out.p;
+        } else v_dev = h->an_slab.buf.p;
     }
     return lifecycle_dev_impl(h, (const int32_t *)f_dev, v_dev, f64, T, ny, nx, wrow, nrows, field ? 1 : 2);
 }
@@ -4057,7 +4122,7 @@ extern "C" int ctk_lifecycle_exact(ctk_handle *h, const int64_t *row_idx, int64_
     if (!h || n < 0 || (n > 0 && (!row_idx || !out))) return ctk_set_error(CTK_E_INVALID, "ctk_lifecycle_exact: bad arguments");
     if (n == 0) return CTK_OK;
     if (h->lc_streamed) return ctk_set_error(CTK_E_STATE, "ctk_lifecycle_exact: the last call was streamed, its slabs are gone (ctk_lifecycle_stream_exact holds the rows it picked)");
-    if (h->lc_own && (h->lc_io_gen != h->io_gen || (h->lc_own == 2 && h->lc_an_gen != h->an_gen)))
+    if (h->lc_own && (h->lc_io_gen != h->io_gen || (h->lc_own == 2 && h->lc_an_gen != h->an_slab.gen)))
         return ctk_set_error(CTK_E_STATE, "ctk_lifecycle_exact: a later call on this handle overwrote or released the slabs of the last ctk_lifecycle_* call; run it again first");
     if (!h->lc_flag || !h->lc_field) return ctk_set_error(CTK_E_STATE, "ctk_lifecycle_exact needs a ctk_lifecycle_* call first");
     HIPCHK(hipSetDevice(h->device));

@@ -179,12 +179,12 @@ static int band_out_check(const char *name, const ctk_band_spec *sp, const ctk_b
 // spec->resident: the anomaly slab ctk_anom_* left on this handle, if it is the one the caller means (shape, type and generation)
 static int band_resident(ctk_handle *h, const char *name, const ctk_band_spec *sp, bool f64, int64_t T, int ny, int nx, const void **x_dev)
 {
-    if (!(h->an_T == T && h->an_ny == ny && h->an_nx == nx && h->an_f64 == f64 && h->an_out.p))
+    *x_dev = h->an_slab.find(T, ny, nx, f64);
+    if (!*x_dev)
         return ctk_set_error(CTK_E_STATE, "%s: the field is the resident anomaly slab, but none of this shape and type is resident (ctk_anom_* with keep_resident)", name);
-    if (h->an_gen != sp->resident_gen)
+    if (h->an_slab.gen != sp->resident_gen)
         return ctk_set_error(CTK_E_STATE, "%s: the resident anomaly slab is generation %llu, the call names the stale generation %llu", name,
-                             (unsigned long long)h->an_gen, (unsigned long long)sp->resident_gen);
-    *x_dev = h->an_out.p;
+                             (unsigned long long)h->an_slab.gen, (unsigned long long)sp->resident_gen);
     return CTK_OK;
 }
 

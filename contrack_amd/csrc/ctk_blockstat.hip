@@ -256,7 +256,7 @@ static int blockstat_check(const char *who, ctk_handle *h, int64_t T, int ny, in
 // x == NULL with peaks wanted: the resident anomaly slab of the call's shape and type (comp_resident's test), or the call is refused
 static int blockstat_resident(const char *who, ctk_handle *h, bool f64, int64_t T, int ny, int nx, const void **x_dev)
 {
-    *x_dev = comp_resident_slab(h, f64, T, ny, nx);
+    *x_dev = h->an_slab.find(T, ny, nx, f64);
     if (!*x_dev)
         return ctk_set_error(CTK_E_INVALID, "%s: peaks wanted and no field given, which needs a resident anomaly slab of this shape and type (ctk_anom_* with keep_resident)", who);
     return CTK_OK;

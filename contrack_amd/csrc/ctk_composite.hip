@@ -125,15 +125,11 @@ static int launch_composite(ctk_handle *h, const int32_t *flag_dev, const void *
 }
 
 // x == NULL: the anomaly slab that ctk_anom_* left resident on this handle, if its shape and type are the call's
-static const void *comp_resident_slab(const ctk_handle *h, bool f64, int64_t T, int ny, int nx)          // (null: there is none of this shape and type)
-{
-    return h->an_T == T && h->an_ny == ny && h->an_nx == nx && h->an_f64 == f64 ? h->an_out.p : nullptr;
-}
 static int comp_resident(ctk_handle *h, const char *name, bool f64, int64_t T, int ny, int nx, const void **x_dev)
 {
-    if (!comp_resident_slab(h, f64, T, ny, nx))
+    *x_dev = h->an_slab.find(T, ny, nx, f64);
+    if (!*x_dev)
         return ctk_set_error(CTK_E_STATE, "%s: no field given, which needs a resident anomaly slab of this shape and type (ctk_anom_* with keep_resident)", name);
-    *x_dev = h->an_out.p;
     return CTK_OK;
 }
 

@@ -236,14 +236,6 @@ static int launch_filter(ctk_handle *h, const FilterArgs &a, const FilterTable &
     return CTK_OK;
 }
 
-// the result of a call that keeps it lies in fl_out: it becomes the resident level mean (the buffers change owner; what lv_out held is
-// fl_out's scratch from now on)
-static void filter_keep(ctk_handle *h, const FilterArgs &a, int64_t T_out, bool f64)
-{
-    h->lv_out.swap(h->fl_out);
-    h->lv_T = T_out > 0 ? T_out : -1; h->lv_ny = a.ny; h->lv_nx = a.nx; h->lv_f64 = f64;
-}
-
 template <typename VT>
 static int filter_dev_impl(ctk_handle *h, const VT *x_dev, const FilterArgs &a, VT *out_dev, int64_t T_out, const char *who)
 {
@@ -303,38 +295,20 @@ static int filter_stream_impl(ctk_handle *h, StreamIO &io, const FilterArgs &a, 
     for (int64_t c0 = 0, o = 0; c0 < a.T; c0 += io.chunk) { const int64_t o1 = done_at(c0 + io.chunk, o); most = std::max(most, o1 - o); o = o1; }
     CTKCHK(stream_setup(h, (size_t)(io.chunk + halo) * plane, 0, io.read != nullptr));
     if (keep_resident) {
-        h->lv_gen++;                                                               // (the resident mean changes at the end of the call)
         CTKCHK(ensure(h, h->fl_out, (size_t)std::max<int64_t>(n_out, 1) * plane));
         if (io.write_v) CTKCHK(stream_setup(h, 0, (size_t)most * plane, true));
     } else {
         CTKCHK(stream_setup(h, 0, (size_t)most * plane, io.write_v != nullptr));
     }
-    int64_t o_done = 0;
-    Producer p;
-    p.in_bytes = (size_t)(io.chunk + halo) * plane; p.out_step = plane;
-    p.upload = [&](const ProduceIn &c) -> int {
-        const char *src = c.src ? c.src : (const char *)io.host_in + (size_t)c.c0 * plane;
-        HIPCHK(hipMemcpyAsync(c.dev + (size_t)halo * plane, src, (size_t)c.nt * plane, hipMemcpyHostToDevice, h->copy_stream));
-        return CTK_OK;
-    };
-    p.launch = [&](const ProduceIn &c, ProduceOut &o) -> int {
-        // steps [c0 - halo, c0 + nt) are in the window now (the first chunk has nothing in front of it).  An output that has not left
-        // yet has first + K - 1 >= c0, so its first tap is in the window.
-        const bool last = c.c0 + c.nt == a.T;
-        const int64_t xlo = c.c0 == 0 ? 0 : c.c0 - halo, o0 = o_done, o1 = done_at(c.c0 + c.nt, o_done);
-        if (o1 > o0) {
-            o.t0 = o0; o.nt = o1 - o0;
-            o.dev = keep_resident ? (char *)h->fl_out.p + (size_t)o0 * plane : (char *)h->io_out.p + (size_t)c.b * (size_t)most * plane;
-            CTKCHK(launch_filter<VT>(h, a, ft, (const VT *)c.dev, c.c0 - halo, xlo, c.c0 + c.nt, o0, o1, (VT *)o.dev));
-        }
-        // the last `halo` steps in front of the next chunk (a chunk that is not the last has nt == chunk >= halo steps: they lie in its body)
-        if (!last && halo > 0)
-            HIPCHK(hipMemcpyAsync((char *)h->io_in.p + (size_t)(c.b ^ 1) * p.in_bytes, c.dev + (size_t)c.nt * plane, (size_t)halo * plane, hipMemcpyDeviceToDevice, h->stream));
-        o_done = o1;
-        return CTK_OK;
-    };
-    CTKCHK(stream_produce_end(h, io, stream_produce(h, io, a.T, name, p), t_call));
-    if (keep_resident) filter_keep(h, a, n_out, sizeof(VT) == 8);
+    // (window_produce: an output that has not left yet has first + K - 1 >= c0, so its first tap is in the window of K - 1 kept steps)
+    const int rc = window_produce(
+        h, io, a.T, halo, plane, name, done_at,
+        [&](int b, int64_t o0) { return keep_resident ? (char *)h->fl_out.p + (size_t)o0 * plane : (char *)h->io_out.p + (size_t)b * (size_t)most * plane; },
+        [&](const char *win, int64_t xbase, int64_t xlo, int64_t xhi, int64_t o0, int64_t o1, char *out) {
+            return launch_filter<VT>(h, a, ft, (const VT *)win, xbase, xlo, xhi, o0, o1, (VT *)out);
+        });
+    CTKCHK(stream_produce_end(h, io, rc, t_call));
+    if (keep_resident) h->lv_slab.adopt(h->fl_out, n_out, a.ny, a.nx, sizeof(VT) == 8);     // (the result becomes the resident level mean)
     return CTK_OK;
 }
 
@@ -377,14 +351,10 @@ static int filter_resident_impl(ctk_handle *h, const FilterArgs &a, VT *out, int
     const int64_t n_out = (int64_t)ft.taps.size();
     if (n_out != T_out) return ctk_set_error(CTK_E_INVALID, "%s: T_out = %lld, the layout has %lld outputs (ctk_filter_layout)", who, (long long)T_out, (long long)n_out);
     CTKCHK(ensure(h, h->fl_out, (size_t)std::max<int64_t>(n_out, 1) * plane));
-    CTKCHK(launch_filter<VT>(h, a, ft, (const VT *)h->lv_out.p, 0, 0, a.T, 0, n_out, (VT *)h->fl_out.p));
+    CTKCHK(launch_filter<VT>(h, a, ft, (const VT *)h->lv_slab.buf.p, 0, 0, a.T, 0, n_out, (VT *)h->fl_out.p));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (out && n_out) {
-        if (!h->bounce) h->bounce.reset(new (std::nothrow) BouncePool());
-        if (!h->bounce || !bounce_copy(*h->bounce, h->device, h->fl_out.p, out, (size_t)n_out * plane, false))
-            HIPCHK(hipMemcpy(out, h->fl_out.p, (size_t)n_out * plane, hipMemcpyDeviceToHost));
-    }
-    if (keep_resident) { h->lv_gen++; filter_keep(h, a, n_out, sizeof(VT) == 8); }
+    if (out && n_out) CTKCHK(download(h, h->fl_out.p, out, (size_t)n_out * plane));
+    if (keep_resident) h->lv_slab.adopt(h->fl_out, n_out, a.ny, a.nx, sizeof(VT) == 8);
     return CTK_OK;
 }
 
@@ -392,11 +362,12 @@ extern "C" int ctk_filter_resident(ctk_handle *h, const double *w, int K, int64_
                                    void *out, int64_t T_out, int keep_resident)
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "ctk_filter_resident: null handle");
-    if (h->lv_T < 1 || !h->lv_out.p) return ctk_set_error(CTK_E_INVALID, "ctk_filter_resident: no vertical mean is resident (ctk_level_mean_* or ctk_filter_* with keep_resident)");
+    const ResidentSlab &m = h->lv_slab;
+    if (!m.held()) return ctk_set_error(CTK_E_INVALID, "ctk_filter_resident: no vertical mean is resident (ctk_level_mean_* or ctk_filter_* with keep_resident)");
     if (!out && !keep_resident) return ctk_set_error(CTK_E_INVALID, "ctk_filter_resident: nothing to produce (no output and keep_resident = 0)");
-    const FilterArgs a{h->lv_T, h->lv_ny, h->lv_nx, w, K, stride, offset, edges, skipna, starts, nseg};
+    const FilterArgs a{m.T, m.ny, m.nx, w, K, stride, offset, edges, skipna, starts, nseg};
     CTKCHK(filter_check("ctk_filter_resident", h, a));
-    if (h->lv_f64) return filter_resident_impl<double>(h, a, (double *)out, T_out, keep_resident);
+    if (m.f64) return filter_resident_impl<double>(h, a, (double *)out, T_out, keep_resident);
     return filter_resident_impl<float>(h, a, (float *)out, T_out, keep_resident);
 }
 

@@ -178,7 +178,7 @@ static int level_dev_impl(ctk_handle *h, const VT *x_dev, int64_t steps, int nle
     LevelSel sel;
     CTKCHK(level_select(who, weights, nlev, sel));
     HIPCHK(hipSetDevice(h->device));
-    h->lv_gen++;
+    h->lv_slab.gen++;                                                  // (the slab is not touched; every ctk_level_mean_* call changes the number, the header says)
     const double *w_dev = nullptr;
     const int32_t *lev_dev = nullptr;
     CTKCHK(level_table(h, sel, false, &w_dev, &lev_dev));
@@ -215,14 +215,14 @@ static int level_stream_impl(ctk_handle *h, StreamIO &io, int64_t steps, int64_t
     io.esz = sizeof(VT);
     io.chunk = ctk_stream_chunk(chunk_steps, steps, (size_t)K * plane);
     const double t_call = now_ms();
-    h->lv_T = -1; h->lv_gen++;                                         // the resident mean (if any) is dropped or about to be overwritten
+    h->lv_slab.drop();
     CTKCHK(stream_setup(h, (size_t)io.chunk * (size_t)K * plane, 0, io.read != nullptr));
-    CTKCHK(produce_out_setup(h, io, h->lv_out, steps, plane, keep_resident));
+    CTKCHK(produce_out_setup(h, io, h->lv_slab.buf, steps, plane, keep_resident));
     const double *w_dev = nullptr;
     const int32_t *lev_dev = nullptr;
     CTKCHK(level_table(h, sel, true, &w_dev, &lev_dev));
     // the chunks (stream_produce): io.host_in is the whole (steps, nlev, ny, nx) array (the runs pick its selected levels), io.read a
-    // reader of compact chunks (nt, nsel, ny, nx).  The means go to io.host_out_v / io.write_v chunk by chunk and (keep) into lv_out.
+    // reader of compact chunks (nt, nsel, ny, nx).  The means go to io.host_out_v / io.write_v chunk by chunk and (keep) into lv_slab.
     Producer p;
     p.in_bytes = (size_t)io.chunk * (size_t)K * plane; p.out_step = plane;
     p.upload = [&](const ProduceIn &c) -> int {
@@ -234,11 +234,11 @@ static int level_stream_impl(ctk_handle *h, StreamIO &io, int64_t steps, int64_t
     };
     p.launch = [&](const ProduceIn &c, ProduceOut &o) -> int {
         o.t0 = c.c0; o.nt = c.nt;
-        o.dev = produce_out_dev(h, io, h->lv_out, c, plane, keep_resident);
+        o.dev = produce_out_dev(h, io, h->lv_slab.buf, c, plane, keep_resident);
         return launch_level<VT>(h, (const VT *)c.dev, K, npix, c.nt, (int)K, w_dev, lev_dev, sel.wsum, skipna, (VT *)o.dev);
     };
     CTKCHK(stream_produce_end(h, io, stream_produce(h, io, steps, name, p), t_call));
-    if (keep_resident) { h->lv_T = steps; h->lv_ny = ny; h->lv_nx = nx; h->lv_f64 = sizeof(VT) == 8; }
+    if (keep_resident) h->lv_slab.keep(steps, ny, nx, sizeof(VT) == 8);
     return CTK_OK;
 }
 
@@ -283,10 +283,7 @@ extern "C" int ctk_level_mean_stream_cb(ctk_handle *h, int elem_bytes, int64_t s
 extern "C" int ctk_resident_level_mean(ctk_handle *h, int64_t *steps, int *ny, int *nx, int *is_f64)
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "null handle");
-    if (steps) *steps = h->lv_T;
-    if (ny) *ny = h->lv_ny;
-    if (nx) *nx = h->lv_nx;
-    if (is_f64) *is_f64 = h->lv_f64 ? 1 : 0;
+    h->lv_slab.report(steps, ny, nx, is_f64);
     return CTK_OK;
 }
 
@@ -294,7 +291,7 @@ extern "C" int ctk_resident_level_mean(ctk_handle *h, int64_t *steps, int *ny, i
 extern "C" int ctk_resident_level_mean_generation(ctk_handle *h, uint64_t *generation)
 {
     if (!h || !generation) return ctk_set_error(CTK_E_INVALID, "null argument");
-    *generation = h->lv_gen;
+    *generation = h->lv_slab.gen;
     return CTK_OK;
 }
 
@@ -303,13 +300,14 @@ extern "C" int ctk_anom_seg_resident(ctk_handle *h, const int32_t *group, int ng
                                      int keep_resident, const int64_t *starts, int64_t nseg)
 {
     if (!h) return ctk_set_error(CTK_E_INVALID, "ctk_anom_seg_resident: null handle");
-    if (h->lv_T < 1 || !h->lv_out.p) return ctk_set_error(CTK_E_INVALID, "ctk_anom_seg_resident: no vertical mean is resident (ctk_level_mean_* with keep_resident)");
+    const ResidentSlab &m = h->lv_slab;
+    if (!m.held()) return ctk_set_error(CTK_E_INVALID, "ctk_anom_seg_resident: no vertical mean is resident (ctk_level_mean_* with keep_resident)");
     if (!anom_out && !clim_out && !keep_resident) return ctk_set_error(CTK_E_INVALID, "ctk_anom_seg_resident: bad arguments");
-    CTKCHK(anom_seg_args("ctk_anom_seg_resident", h, h->lv_T, h->lv_ny, h->lv_nx, group, ngroups, window, smooth, starts, nseg));
-    if (h->lv_f64)
-        return anom_seg_dev<double>(h, (const double *)h->lv_out.p, h->lv_T, h->lv_ny, h->lv_nx, group, ngroups, window, smooth, (const double *)clim_in, (double *)anom_out,
+    CTKCHK(anom_seg_args("ctk_anom_seg_resident", h, m.T, m.ny, m.nx, group, ngroups, window, smooth, starts, nseg));
+    if (m.f64)
+        return anom_seg_dev<double>(h, (const double *)m.buf.p, m.T, m.ny, m.nx, group, ngroups, window, smooth, (const double *)clim_in, (double *)anom_out,
                                     (double *)clim_out, keep_resident, starts, nseg);
-    return anom_seg_dev<float>(h, (const float *)h->lv_out.p, h->lv_T, h->lv_ny, h->lv_nx, group, ngroups, window, smooth, (const float *)clim_in, (float *)anom_out,
+    return anom_seg_dev<float>(h, (const float *)m.buf.p, m.T, m.ny, m.nx, group, ngroups, window, smooth, (const float *)clim_in, (float *)anom_out,
                                (float *)clim_out, keep_resident, starts, nseg);
 }
 

@@ -457,7 +457,8 @@ int ctk_lifecycle_stream_exact(ctk_handle *h, int64_t *row_idx, ctk_life_exact *
  * group: T ids in [0, ngroups) (the class maps the time coordinate's dayofyear / month ... to them).  clim_in (optional,
  * [ngroups][ny][nx]): use this climatology instead of computing one (the `clim=` argument).  anom_out / clim_out: optional host
  * outputs.  keep_resident != 0: the anomaly slab stays in HBM and ctk_track_resident / ctk_percentile_* (x = NULL) run on it
- * without another host-to-device copy.  Sums in float64, results in the slab's dtype (xarray's dtype rules).  The xarray calls
+ * without another host-to-device copy.  Sums in float64, results in the slab's dtype (xarray's dtype rules).  T <= 2^31 - 1
+ * (CTK_E_INVALID beyond, checked before x is read): the steps are int32 in the group lists, as for ctk_anom_seg_*.  The xarray calls
  * themselves cannot be run in the build container: checked against the numpy restatement oracle/anom_port.py (parity unpinned). */
 int ctk_anom_f32(ctk_handle *h, const float *x, int64_t T, int ny, int nx, const int32_t *group, int ngroups, int window, int smooth,
                  const float *clim_in, float *anom_out, float *clim_out, int keep_resident);

@@ -1350,7 +1350,7 @@ def resident_anomaly_survives():
     src = (S, "f4", 3, False)
     between = [frequency(L), spells(O), level_mean(O), percentile(L), percentile_groups(L), percentile_field(O), std_field(L), track(L), lifecycle(O),
                band(L, field="f4", chunk_steps=16), centred(L, "array", "f8", chunk_steps=7), centred(O, "cb", chunk_steps=4)]
-    # climatology-only calls on slabs LARGER than the resident one, from the host and from a resident vertical mean: an_out is not theirs
+    # climatology-only calls on slabs LARGER than the resident one, from the host and from a resident vertical mean: the anomaly slot is not theirs
     clim_only = [climatology(L, "f8"), climatology(L, "f4", segments=True), level_mean(L, "f8", keep=True), climatology_resident(("level", L, "f8", 4))]
     return [anomalies(S, "f4", keep=True)] + between + clim_only + [generation_unchanged(src)] + _resident_consumers(src)
 
@@ -1427,7 +1427,7 @@ def exact_rows_follow_their_slabs():
     # field = None: the field is the resident anomaly slab, which any anomaly call writes or drops
     seq += [anomalies(S, "f4", keep=True), lifecycle_resident(src), exact_rows_again(), anomalies_stream(S, chunk_steps=5, callbacks=False), exact_rows_stale(),
             lifecycle_resident(src), exact_rows_again(), anomalies(S, "f4", keep=True), exact_rows_stale(), lifecycle_resident(src), exact_rows_again()]
-    # ... also one that writes no staging buffer: the anomalies of a resident vertical mean go from lv_out to an_out, so only the
+    # ... also one that writes no staging buffer: the anomalies of a resident vertical mean go from the mean's slot to the anomaly slot, so only the
     # generation of the resident anomaly slab tells.  The climatology of that (larger) mean alone writes neither: the rows stay right
     lv = ("level", L, "f4", 4)
     seq += [level_mean(L, "f4", keep=True), anomalies(S, "f4", keep=True), lifecycle_resident(src), exact_rows_again(),

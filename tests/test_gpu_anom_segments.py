@@ -46,15 +46,16 @@ def test_one_segment_is_the_unsegmented_call(trk, case):
     forms = set()
     for window in (1, 4, 31):
         for smooth in (1, 2, 3, 5, 16, BIG_SMOOTH):
+            want, want_c = expected(x, group, G, window, smooth, [0])
             plain, clim = trk.anomalies(x, group, G, window=window, smooth=smooth, want_clim=True)
+            assert same(plain, want) and same(clim, want_c), (window, smooth, "unsegmented")        # (ctk_anom_* is the same host path)
             for seg in ([0], []):
                 got, gclim = trk.anomalies(x, group, G, window=window, smooth=smooth, want_clim=True, segments=seg)
                 form = trk.debug_anom_form()
                 assert form == (PLAIN if smooth == BIG_SMOOTH else RING), (smooth, form)
                 forms.add(form)
+                assert same(got, want) and same(gclim, want_c), (window, smooth, seg)
                 assert same(got, plain) and same(gclim, clim), (window, smooth, seg)
-        want, _ = expected(x, group, G, window, 5, [0])
-        assert same(trk.anomalies(x, group, G, window=window, smooth=5, segments=[0])[0], want)
     assert forms == {RING, PLAIN}
 
 

@@ -1,12 +1,12 @@
 """calc_anom on a host slab, four ways in one process (profiles/NOTES.md): ms per call, best and median of `reps` after a warm-up, host
 clock around calls that end in a synchronisation.
   (a) Tracker.anomalies                      -- ctk_anom_*: k_anom reads x, group and clim `smooth` times per output
-  (b) Tracker.anomalies(segments=[0])        -- ctk_anom_seg_*: the LDS ring form, same bits
+  (b) Tracker.anomalies(segments=[0])        -- ctk_anom_seg_*: the same host path with the LDS ring form, same bits
       both with the climatology handed in and the result left resident: the upload of the slab and the anomaly kernel, nothing else;
       h2d = the upload alone (a plain copy of the pageable slab into device memory), so a - h2d and b - h2d are the kernels
   (c) Tracker.anomalies_stream from the host array, no climatology given: the slab in twice, the anomalies out once, in chunks
   (d) plain copies of the same bytes between pinned (registered) host memory and the device: two slabs in, one out -- the floor of (c)
-One JSON line per smoothing.  Daily steps from 1981-01-01, groups = day of year, window 31, float32.
+One JSON line per smoothing (1, the default; 2; 16).  Daily steps from 1981-01-01, groups = day of year, window 31, float32.
 Usage: python tools/anom_probe.py [T ny nx [reps]]      (default: 2707 181 360 5)"""
 import json
 import os
@@ -58,7 +58,7 @@ with _native.Tracker(0) as trk:
         for buf in (x, out):
             _native.check(L.ctk_host_unregister(trk.handle, buf.ctypes.data))
         ms_h2d = timed(lambda: trk.h2d(d, x))                                     # (pageable again, as (a) and (b) take it)
-        for smooth in (2, 16):
+        for smooth in (1, 2, 16):
             a = trk.anomalies(x, group, G, window=W, smooth=smooth, clim=clim)[0]
             b = trk.anomalies(x, group, G, window=W, smooth=smooth, clim=clim, segments=[0])[0]
             form = trk.debug_anom_form()
